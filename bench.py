@@ -7,8 +7,14 @@ original embedding, landmark distance matrix, 40-step alpha sweep with Chung-Lu 
 score).  metric = m * A / T  (m original edges, A alphas evaluated, T wall time per step).
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs bench_out   # + the last step's outputs, bench_out/<name>.npy
+  python bench.py --full                                                    # + roofline, CPU baseline, other configurations
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps, writes the outputs if asked and prints the line.  Everything else it can
+measure (per-kernel event timers and the roofline, the back-to-back scatter, the CPU baseline, the other BASELINE
+configurations, N > 1: one embedding per GPU) runs with --full only.
 """
 import argparse
 import json
@@ -125,6 +131,23 @@ def full_size_oracle(workload):
                      "provenance says so (the reference's O(n^2 d) loop is not runnable at this size)", "provenance": prov}
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # all arrays of --dump-outputs together (npy headers aside): under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """`arrays`: name -> array, written as <path>/<name>.npy in float64 (ids and counts included: exact below 2^53).  Each
+    array may take an equal share of DUMP_BUDGET_BYTES; a larger one is replaced by a fixed, seeded sample of its rows, in
+    order (the same rows in every run of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 8 // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > cap:
+            rows = max(1, cap // (a.size // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def _crc(a):
     import zlib
 
@@ -215,6 +238,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)  # a step is ~33 ms at the headline: ten of them average out most of the jitter
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="headline", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel event timers and the roofline, the "
+                         "back-to-back scatter, the CPU baseline, the other BASELINE configurations, N > 1: one embedding per "
+                         "GPU.  The --no-* options and --profile-all below act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): the score "
+                         "vector, the per-alpha trace and, on one GPU, the landmark state (large arrays as a seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-all", action="store_true",
                     help="event timers around every kernel family (default: only the kernels priced against a roofline)")
@@ -387,10 +417,12 @@ def main():
     # Inside the TIMED region only the timers of the fits run (the dominant kernel, whose live figure is the line's `roofline`);
     # the other roofline kernels are timed in a few extra, untimed steps behind it (TIMED_KERNELS / ROOFLINE_KERNELS below):
     # 60 event pairs per step were 0.25 ms of serialisation inside the number they were there to explain.
+    # A plain run (no --full) keeps every timer off: its line carries no per-kernel figures.
     TIMED_KERNELS = ("fit_persistent", "fit_symv")
-    ctx.profile_select(() if args.profile_all else TIMED_KERNELS)
-    ctx.profile_enable(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile_select(() if args.profile_all else TIMED_KERNELS)
+        ctx.profile_enable(True)
+        ctx.profile_reset()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -401,10 +433,22 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    prof = ctx.profile()
+    prof = ctx.profile() if args.full else {}
     phases = ctx.phase_ms()
     trace = ctx.last_trace
-    if not args.profile_all:  # the other kernels that carry a roofline entry: the same step, a few more times, outside the timed region
+    if args.dump_outputs and rank == 0:  # what the caller of the last timed score receives, before anything else runs
+        # the trace marks an alpha whose divergence / AUC was no longer evaluated (that score's sweep had stopped) with NaN:
+        # written as the evaluated values and a 0/1 mask of the alphas they belong to
+        div_ok, auc_ok = ~np.isnan(trace["div"]), ~np.isnan(trace["auc"])
+        outputs = {"result": res, "trace_iters": trace["iters"],
+                   "trace_div": np.asarray(trace["div"])[div_ok], "trace_div_evaluated": div_ok,
+                   "trace_auc": np.asarray(trace["auc"])[auc_ok], "trace_auc_evaluated": auc_ok}
+        if world == 1:  # the landmark state that score left on the device (cge_landmarks_fetch)
+            names = ("landmark_dii", "landmark_embedding", "landmark_community", "landmark_edges", "landmark_edge_weights",
+                     "landmark_weights", "v_to_l")
+            outputs.update(zip(names, ctx.landmarks_fetch()))
+        dump_outputs(args.dump_outputs, outputs)
+    if args.full and not args.profile_all:  # the other kernels that carry a roofline entry: the same step, a few more times, outside the timed region
         extra = 3 if args.workload != "cfg5" else 1
         ctx.profile_select(tuple(k for k in ROOFLINE_KERNELS if k not in TIMED_KERNELS))
         ctx.profile_reset()
@@ -418,7 +462,7 @@ def main():
     # each other -- inside a step the pass starts cold (40 MB of edge words and the tables come from HBM behind the landmark
     # phase's traffic) and the timer also spans the gap between its two launches
     scatter_b2b = None
-    if world == 1 and args.workload != "cfg5" and not args.no_back_to_back:
+    if args.full and world == 1 and args.workload != "cfg5" and not args.no_back_to_back:
         try:
             ctx.profile_select(("edge_scatter",))
             ctx.profile_reset()
@@ -437,7 +481,7 @@ def main():
     # graph) has no exchange at all: every rank scores its own embedding of the resident graph, no collective, the job's
     # rate is the sum.  Reported beside the strong-scaling value of the contract, never instead of it.
     independent = None
-    if world > 1 and not dev_emb and not args.no_independent:
+    if args.full and world > 1 and not dev_emb and not args.no_independent:
         ctx.clear_collectives()
         rng = np.random.default_rng(args.seed + 7919 * (rank + 1))
         emb_r = np.asfortranarray(g["embedding"] + 0.05 * rng.standard_normal(g["embedding"].shape))
@@ -581,7 +625,7 @@ def main():
                  "edge_scatter_wedges": ("wedge_pass_kernel", "wedge_tile_kernel"),
                  "group_stats": ("group_cov_mfma_kernel", "group_cov_final_kernel", "gather_means_kernel"), "group_eig": ("group_eig_kernel",),
                  "max_pair_dist": ("max_pair_kernel",)}
-    if os.path.exists(pmc_file) and args.workload == "headline" and world == 1:
+    if args.full and os.path.exists(pmc_file) and args.workload == "headline" and world == 1:
         try:
             pmc = json.load(open(pmc_file))["kernels"]
         except Exception:
@@ -642,7 +686,7 @@ def main():
                               "bytes_per_step": nbytes / (args.steps + args.warmup)}
         if independent is not None:
             out["independent_embeddings"] = independent
-    if world == 1 and not args.no_cpu_baseline and not directed and not dev_emb:
+    if args.full and world == 1 and not args.no_cpu_baseline and not directed and not dev_emb:
         try:
             out["cpu_baseline"] = cpu_baseline(g, wl)
             fs = full_size_oracle(args.workload) if args.scale == 1.0 else None
@@ -654,7 +698,7 @@ def main():
     ctx.close()  # tear the context down before interpreter exit (profilers finalise their HIP hooks at exit)
     # The other single-GPU configurations of BASELINE.json on the same clock.  LAST key of the line: the driver keeps the
     # line's tail.  Headline `value` / `config` / `roofline` above are untouched by it.
-    if world == 1 and args.workload == "headline" and args.scale == 1.0 and not args.no_other_configs:
+    if args.full and world == 1 and args.workload == "headline" and args.scale == 1.0 and not args.no_other_configs:
         del g
         torch.cuda.empty_cache()
         other = {"headline": {"ms_per_step": round(sec_per_step * 1e3, 4), "steps": args.steps, "value": value,

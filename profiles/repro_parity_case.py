@@ -1,12 +1,13 @@
 """Re-run one case of tests/test_gpu_parity.py::test_randomised_parity_sweep (with the wide dimensions of CGE_STRESS_WIDE)
 through every fit form and the oracle, printing the per-alpha local-score tallies: python3 profiles/repro_parity_case.py <case>"""
 import os, sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import cge.jl_amd as cg
 from cge.jl_amd import api, synth
 import importlib.util
-spec = importlib.util.spec_from_file_location("cge_oracle_py", "/root/repo/oracle/oracle.py")
+spec = importlib.util.spec_from_file_location("cge_oracle_py", os.path.join(ROOT, "oracle", "oracle.py"))
 orc_mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(orc_mod)
 case = int(sys.argv[1]) if len(sys.argv) > 1 else 212
 rng = np.random.default_rng(1000 + case)
