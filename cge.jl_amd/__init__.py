@@ -10,7 +10,7 @@ from .args import (METHODS, ParseError, parseargs, split_cluster_diameter, split
 
 
 def __getattr__(name):  # lazy: importing the package must not need the GPU library (parseargs is pure host)
-    if name in ("landmarks", "wGCL", "wGCL_directed", "score", "Context", "draw_samples", "library_path",
+    if name in ("landmarks", "wGCL", "wGCL_directed", "score", "score_batch", "Context", "draw_samples", "library_path",
                 "load_library", "CGEError"):
         from . import api
 

@@ -65,6 +65,11 @@ class ScoreArgs(C.Structure):
                 ("split", C.c_int), ("seed", C.c_int64), ("auc_samples", C.c_int64)]
 
 
+class EmbeddingBatch(C.Structure):
+    _fields_ = [("embeddings", C.c_void_p), ("K", C.c_int64), ("d", C.c_int64), ("on_device", C.c_int),
+                ("row_major", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
 
@@ -398,6 +403,48 @@ class Context:
         self.last_trace = tr.as_dict()
         return out[: olen.value].copy()
 
+    def score_batch(self, embeddings, clusters, land, forced=4, method="rss", directed=False, split=False, seed=-1,
+                    auc_samples=10000, d=None, row_major=True):
+        """`score` for K embeddings of the resident graph in one call (cge_score_batch): a list of the K result vectors, each
+        equal to what `score` gives on that embedding; their traces in `last_traces`.  `embeddings`: a list of (n, d) float64
+        arrays, a (K, n, d) array, or a list of device pointers (ints, as `set_embedding_device`; then `d` is required).
+        Afterwards the last embedding is the resident one."""
+        if isinstance(embeddings, np.ndarray) and embeddings.ndim == 3:
+            embeddings = list(embeddings)
+        embeddings = list(embeddings)
+        K = len(embeddings)
+        if K < 1:
+            raise ValueError("score_batch: no embeddings")
+        on_device = all(isinstance(e, (int, np.integer)) for e in embeddings)
+        keep = []
+        if on_device:
+            if d is None:
+                raise ValueError("score_batch: device pointers need d")
+            ptrs = (C.c_void_p * K)(*[int(e) for e in embeddings])
+        else:
+            for e in embeddings:
+                e, ef = _colmajor(e)
+                keep.append(ef)
+                if e.ndim != 2 or (d is not None and e.shape[1] != d):
+                    raise ValueError("score_batch: every embedding is (n, d) with one common d")
+                d = e.shape[1]
+            ptrs = (C.c_void_p * K)(*[ef.ctypes.data for ef in keep])
+        b = EmbeddingBatch()
+        b.embeddings = C.cast(ptrs, C.c_void_p).value
+        b.K, b.d, b.on_device, b.row_major = K, int(d), int(on_device), int(bool(row_major) and on_device)
+        flat, off = _flatten_clusters(clusters if clusters else [])
+        a = ScoreArgs()
+        a.clusters_flat, a.clusters_off, a.n_clusters = _p(flat).value, _p(off).value, len(off) - 1
+        a.land, a.forced, a.method = int(land), int(forced), _method_code(method)
+        a.directed, a.split, a.seed, a.auc_samples = int(bool(directed)), int(bool(split)), int(seed), int(auc_samples)
+        out = np.zeros((K, 7))
+        olen = (C.c_int * K)()
+        trs = (Trace * K)()
+        self._check(self.L.cge_score_batch(self.h, C.byref(a), C.byref(b), _p(out), olen, trs))
+        self.d = int(d)
+        self.last_traces = [trs[k].as_dict() for k in range(K)]
+        return [out[k, : olen[k]].copy() for k in range(K)]
+
     # ---- kernel-level ----------------------------------------------------------------------------------
     def edge_scatter(self, v_to_l, N, Cn, directed=False, e0=0, e1=None, want_wedges=True, want_vect_c=True):
         e1 = self.m if e1 is None else e1
@@ -633,6 +680,17 @@ def score(edges, eweights, vweights, comm, clusters, embedding, land, forced=4, 
     ctx = ctx or default_context()
     ctx.set_inputs(edges, eweights, vweights, comm, embedding)
     return ctx.score(clusters, land, forced, method, directed, split, seed, auc_samples)
+
+
+def score_batch(edges, eweights, vweights, comm, clusters, embeddings, land, forced=4, method="rss", directed=False,
+                split=False, seed=-1, auc_samples=10000, ctx=None):
+    """`score` for several embeddings of one graph: a list of result vectors (Context.score_batch)."""
+    ctx = ctx or default_context()
+    embeddings = list(embeddings)
+    n = int(np.asarray(embeddings[0]).shape[0])
+    ctx.set_graph(edges, eweights, n)
+    ctx.set_vertex_data(comm, vweights)
+    return ctx.score_batch(embeddings, clusters, land, forced, method, directed, split, seed, auc_samples)
 
 
 def draw_samples(ctx, seed, S, directed=False, n_sets=1):

@@ -63,6 +63,17 @@ class ParseError(Exception):
     pass
 
 
+def read_embedding(fn_embed, no_vertices):
+    """An embedding file as parseargs reads it (src/auxilary.jl:150-167): (n, d) float64, Fortran-ordered, rows by vertex id."""
+    embedding, _ = _readdlm(fn_embed)  # a node2vec header line (:151-156) is skipped by the reader
+    if embedding.shape[0] != no_vertices:
+        raise AssertionError("No. rows in embedding and no. vertices in a graph differ.")
+    first = embedding[:, 0]
+    if np.all(first == np.floor(first)):  # convert.(Int, ...) succeeds (:161-167)
+        embedding = embedding[np.argsort(first.astype(np.int64), kind="stable"), 1:]
+    return np.asfortranarray(embedding)
+
+
 def parseargs(argv=None, exit_on_error=True):
     """Returns (edges, eweights, vweight, comm, clusters, embedding, verbose, landmarks, forced,
     method, directed, split, seed, samples) exactly as src/auxilary.jl:220.
@@ -130,13 +141,7 @@ def parseargs(argv=None, exit_on_error=True):
         fn_embed = _flag_value(argv, "-e")
         if not os.path.isfile(fn_embed):
             raise AssertionError(f"{fn_embed} is not a file")
-        embedding, _ = _readdlm(fn_embed)  # a node2vec header line (:151-156) is skipped by the reader
-        if embedding.shape[0] != no_vertices:
-            raise AssertionError("No. rows in embedding and no. vertices in a graph differ.")
-        first = embedding[:, 0]
-        if np.all(first == np.floor(first)):  # convert.(Int, ...) succeeds (:161-167)
-            embedding = embedding[np.argsort(first.astype(np.int64), kind="stable"), 1:]
-        embedding = np.asfortranarray(embedding)
+        embedding = read_embedding(fn_embed, no_vertices)
 
         landmarks = -1
         if "-l" in argv:

@@ -1,0 +1,199 @@
+// batch_host.cpp -- the alpha sweeps of cge_score_batch's launch groups in lock-step ("Scoring several embeddings").
+// Every member of a group was prepared by host_wgcl_sweep on the fused path and handed over (SweepHandoff).  An alpha of the group
+// is three launches for all its live members -- fit_flow_multi_kernel (the members' fused fits side by side), bvec_bins_multi_kernel
+// and the two JS kernels with the member in blockIdx.y -- and one copy of the members' scalars to the host.  Per member the host
+// keeps what host_wgcl_sweep keeps: its T rotating through three vectors, its patience counters (src/divergence.jl:215-223,
+// :242-253), its partial sums added in block order.  So a member's iterates, iteration counts and scores are those of its own
+// cge_score.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "common.hpp"
+
+bool batch_group_closes(int g_sum, int g_nw, int g_size, int G, int NW, int cus) {
+    return g_size > 0 && (g_sum + G > cus || NW != g_nw || g_size >= CGE_BATCH_MAX);
+}
+
+void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
+    const double delta = 0.001, AlphaMax = 10.0, AlphaStep = 0.25; // src/divergence.jl:35-37
+    const i64 n_alpha_total = (i64)std::floor((AlphaMax + delta) / AlphaStep + 1e-9);
+    const int K = (int)group.size();
+    if (K < 1) return;
+    hipStream_t st = c->stream;
+    // the scalars of an alpha per member, laid out as host_wgcl_sweep's (tallies, the shared-verdict slot, JS partials, the fit's flags)
+    constexpr i64 RES_AUC = 0, RES_JS = 2 * CGE_PARTIAL_BLOCKS + 2, RES_FIT = RES_JS + 2 * CGE_PARTIAL_BLOCKS,
+                  RES_STRIDE = RES_FIT + 16;
+    const int NW = group[0]->h.NW;
+    i64 vtot = 0;
+    std::vector<i64> voff(K);
+    for (int j = 0; j < K; j++) {
+        voff[j] = vtot;
+        vtot += packed_len(group[j]->h.C);
+    }
+    c->batch_scal.ensure((size_t)K * RES_STRIDE);
+    c->batch_vectB.ensure((size_t)vtot);
+    c->batch_jspart.ensure((size_t)2 * K * 3 * CGE_PARTIAL_BLOCKS);
+    c->batch_pin.ensure((size_t)2 * K * RES_STRIDE);
+    double *scal = c->batch_scal.p;
+
+    struct Live {
+        int div_counter = 5, auc_counter = 5; // :38
+        bool skip_div = false, skip_auc = false, done = false;
+        double best_div = INFINITY, best_div_ext = INFINITY, best_div_int = INFINITY, best_auc_err = INFINITY, best_auc = INFINITY;
+        double best_alpha = -1.0, best_alpha_auc = -1.0;
+        int tpar = 0;        // the part of T that holds the current iterate
+        i64 next_enqueue = 1; // the next alpha to enqueue
+        DevBuf<char> epi;    // the epilogue tables with the tallies pointed at this member's scalars
+    };
+    std::vector<Live> live(K);
+    for (int j = 0; j < K; j++) {
+        SweepHandoff &h = group[j]->h;
+        std::vector<cge_fit_fused> e = h.h_epi;
+        for (cge_fit_fused &f : e) f.auc_part = scal + (i64)j * RES_STRIDE + RES_AUC;
+        live[j].epi.ensure(e.size() * sizeof(cge_fit_fused));
+        HIP_CHECK(hipMemcpyAsync(live[j].epi.p, e.data(), e.size() * sizeof(cge_fit_fused), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // (pageable source)
+        if (group[j]->trace) group[j]->trace->n_alpha = 0;
+    }
+    auto running = [&](int j) { return !live[j].done && !group[j]->redo; };
+
+    // one alpha for the members in `A`: the fits, vect_B, JS, the scalars to pinned slot (ia & 1), an event
+    auto enqueue = [&](i64 ia, const std::vector<int> &A) {
+        if (A.empty()) return;
+        const double alpha = AlphaStep * (double)ia;
+        cge_flow_multi tab{};
+        cge_bins_multi bins{};
+        cge_js_multi js{};
+        int nb = 0, nj = 0;
+        i64 maxC = 0;
+        tab.n = (int)A.size();
+        for (int i = 0; i < (int)A.size(); i++) {
+            const int j = A[i];
+            Live &L = live[j];
+            SweepHandoff &h = group[j]->h;
+            const bool want_auc = !L.skip_auc, want_div = !L.skip_div;
+            const int Nt = (int)((h.N + 63) / 64), tnext = (L.tpar + 1) % 3;
+            double *sj = scal + (i64)j * RES_STRIDE;
+            cge_flow_problem &q = tab.p[i];
+            q.Lh = h.Lh.p; q.Ll = h.Ll.p; q.alpha = alpha;
+            q.epi = reinterpret_cast<const cge_fit_fused *>(L.epi.p) + (h.n_sets == 1 ? 0 : ia - 1);
+            q.want = (want_div ? 1 : 0) | (want_auc ? 2 : 0);
+            q.T0 = h.T.p + (i64)L.tpar * h.Tld;
+            q.Tout = h.T.p + (i64)tnext * h.Tld;
+            q.w = h.w;
+            q.flags = reinterpret_cast<int *>(sj + RES_FIT);
+            q.N = h.N; q.Tld = h.Tld; q.Nt = Nt; q.G = h.G;
+            L.tpar = tnext;
+            L.next_enqueue = ia + 1;
+            if (!want_div) continue;
+            double *vB = c->batch_vectB.p + voff[j];
+            bins.p[nb++] = cge_bins_problem{h.bt_part.p, h.cm_off.p, h.bt_fc.p, h.bt_ns.p, h.bt_base.p, h.C, Nt, 0, vB};
+            maxC = std::max(maxC, h.C);
+            const int modes[2] = {h.split ? 1 : 0, 2};
+            for (int u = 0; u < (h.split ? 2 : 1); u++, nj++)
+                js.p[nj] = cge_js_problem{h.vectC.p, vB, packed_len(h.C), h.C, modes[u], 0,
+                                          c->batch_jspart.p + (i64)nj * 3 * CGE_PARTIAL_BLOCKS, sj + RES_JS + u * CGE_PARTIAL_BLOCKS};
+        }
+        k_fit_flow_multi(c, tab, NW, 0.25, delta, c->batch_flow);
+        c->stat_fit_batched_launches++;
+        k_bins_js_multi(c, bins, nb, maxC, js, nj);
+        const int slot = (int)(ia & 1);
+        HIP_CHECK(hipMemcpyAsync(c->batch_pin.p + (i64)slot * K * RES_STRIDE, scal, sizeof(double) * K * RES_STRIDE,
+                                 hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipEventRecord(c->sweep_ev[slot], st));
+    };
+
+    for (i64 ia = 1; ia <= n_alpha_total; ia++) {
+        std::vector<int> A, B;
+        for (int j = 0; j < K; j++)
+            if (running(j) && live[j].next_enqueue == ia) A.push_back(j);
+        enqueue(ia, A);
+        // the next alpha of every member that cannot end at this one is enqueued before the host waits (host_wgcl_sweep's overlap)
+        bool any = false;
+        for (int j = 0; j < K; j++) {
+            if (!running(j)) continue;
+            any = true;
+            const Live &L = live[j];
+            const bool may_end_here = (L.skip_div || L.div_counter == 1) && (L.skip_auc || L.auc_counter == 1);
+            if (!may_end_here && ia < n_alpha_total && L.next_enqueue == ia + 1) B.push_back(j);
+        }
+        if (!any) break;
+        enqueue(ia + 1, B);
+        HIP_CHECK(hipEventSynchronize(c->sweep_ev[ia & 1]));
+        const double alpha = AlphaStep * (double)ia;
+        for (int j = 0; j < K; j++) {
+            if (!running(j)) continue;
+            Live &L = live[j];
+            BatchMember &mb = *group[j];
+            const double *res = c->batch_pin.p + (i64)(ia & 1) * K * RES_STRIDE + (i64)j * RES_STRIDE;
+            const int *hf = reinterpret_cast<const int *>(res + RES_FIT);
+            if (hf[2] || !hf[0]) { // abandoned (a wait timed out): the member is scored again on its own
+                note_fit_fallback(c);
+                mb.redo = true;
+                continue;
+            }
+            const i64 iters = hf[1];
+            c->stat_fit_batched_alphas++;
+            double auc_val = NAN, div_val = NAN, div_int = 0.0, div_ext = 0.0;
+            double hs[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+            if (!L.skip_auc)
+                for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { hs[0] += res[RES_AUC + 2 * b]; hs[1] += res[RES_AUC + 2 * b + 1]; }
+            if (!L.skip_div) {
+                double fa = 0.0, fb = 0.0;
+                for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { fa += res[RES_JS + b]; fb += res[RES_JS + CGE_PARTIAL_BLOCKS + b]; }
+                if (!mb.h.split) hs[2] = fa / 2.0;
+                else { hs[3] = fa / 2.0; hs[4] = fb / 2.0; }
+            }
+            if (!L.skip_auc) {
+                const double auc = 1.0 - hs[0] / hs[1]; // :213
+                auc_val = auc;
+                if (auc < L.best_auc) {
+                    L.best_auc = auc;
+                    L.best_auc_err = 1.96 * std::sqrt(auc * (1.0 - auc) / (double)mb.h.S); // :217
+                    L.best_alpha_auc = alpha;
+                    L.auc_counter = 5;
+                } else {
+                    L.auc_counter -= 1;
+                    L.skip_auc = L.auc_counter == 0;
+                }
+            }
+            if (!L.skip_div) {
+                double f;
+                if (!mb.h.split)
+                    f = hs[2];
+                else {
+                    div_int = hs[3];
+                    div_ext = hs[4];
+                    f = (div_int + div_ext) / 2.0;
+                }
+                div_val = f;
+                if (f < L.best_div) {
+                    L.best_div = f;
+                    L.best_alpha = alpha;
+                    L.best_div_ext = !mb.h.split ? 0.0 : div_ext;
+                    L.best_div_int = !mb.h.split ? 0.0 : div_int;
+                    L.div_counter = 5;
+                } else {
+                    L.div_counter -= 1;
+                    L.skip_div = L.div_counter == 0;
+                }
+            }
+            if (mb.trace && mb.trace->n_alpha < 64) {
+                mb.trace->iters[mb.trace->n_alpha] = iters;
+                mb.trace->div[mb.trace->n_alpha] = div_val;
+                mb.trace->auc[mb.trace->n_alpha] = auc_val;
+                mb.trace->n_alpha++;
+            }
+            if ((L.skip_div && L.skip_auc) || ia == n_alpha_total) { // :253
+                L.done = true;
+                double *out = mb.out;
+                out[0] = L.best_alpha; out[1] = L.best_div; out[2] = L.best_div_ext; out[3] = L.best_div_int;
+                out[4] = L.best_alpha_auc; out[5] = L.best_auc; out[6] = L.best_auc_err; // :256
+                *mb.out_len = 7;
+            }
+        }
+    }
+    HIP_CHECK(hipStreamSynchronize(st)); // (an alpha enqueued ahead for a member that then stopped: nothing reads it)
+    if (c->stat_fit_batched_alphas > 0 && !c->fit_persistent_broken) c->fit_fallback_streak = 0; // clean persistent sweeps
+}

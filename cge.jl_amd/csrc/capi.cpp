@@ -1251,10 +1251,10 @@ int cge_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cg
 }
 
 
-int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, cge_trace *trace) {
-    if (!c || !a || !out || !out_len) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+// cge_score's work on the resident inputs.  `defer` (cge_score_batch): a sweep on the fused path is prepared and handed over
+// instead of run (host_wgcl_sweep); `reuse_samples`: the local score's samples of this graph and seed are already in c->smp.
+static void score_one(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, cge_trace *trace, SweepHandoff *defer,
+                      bool reuse_samples) {
     hipStream_t st = c->stream;
     check_resident(c, "score");
     c->phases.ms.clear();
@@ -1272,7 +1272,7 @@ int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, 
     // enqueued early -- behind the first synchronisation of the landmark phase, whose host-side set-up then leaves the device idle
     // for a few hundred microseconds; the verdict is looked at where the samples used to be drawn (a star graph's early return or
     // an error in between leaves the draw pending: see above)
-    const bool samples_early = landmarks && samples_can_start_early(c, a->seed, false);
+    const bool samples_early = landmarks && !reuse_samples && samples_can_start_early(c, a->seed, false);
     // (the hook captures this call's arguments: whatever happens, it does not outlive the call)
     struct HookGuard {
         cge_ctx *c;
@@ -1319,7 +1319,7 @@ int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, 
                 k_degrees_unpack(c, X.p, N, c->s_degout.p, c->s_degin.p, star.p);
             } else
                 k_wedge_degrees(c, c->wedges.p, N, c->s_degout.p, c->s_degin.p, star.p);
-            if (star_exit(N)) return CGE_OK;
+            if (star_exit(N)) return;
             G.deg_in = c->s_degin.p;
             G.deg_out = c->s_degout.p;
         }
@@ -1362,14 +1362,15 @@ int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, 
             HIP_CHECK(hipMemsetAsync(star.p, 0, sizeof(i32) * N, st));
             k_edge_degrees(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, c->m, c->s_degout.p, c->s_degin.p,
                            star.p);
-            if (star_exit(N)) return CGE_OK;
+            if (star_exit(N)) return;
             G.deg_in = c->s_degin.p;
             G.deg_out = c->s_degout.p;
         }
     }
     t0 = now_ms();
     SampleSet &smp = c->smp;
-    if (samples_early && c->samp_pending.on) make_samples(c, a->seed, a->auc_samples, directed, false, smp, 2);
+    if (reuse_samples) { // (cge_score_batch: drawn for the first member; they depend on the graph and the seed only)
+    } else if (samples_early && c->samp_pending.on) make_samples(c, a->seed, a->auc_samples, directed, false, smp, 2);
     else {
         smp.reset();
         make_samples(c, a->seed, a->auc_samples, directed, directed && !landmarks, smp);
@@ -1377,11 +1378,128 @@ int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, 
     c->phases.ms["samples"] = now_ms() - t0;
     t0 = now_ms();
     host_wgcl_sweep(c, G, landmarks ? &ov : nullptr, c->src.p, c->dst.p, c->h_w.empty() ? nullptr : c->h_w.data(), c->m, directed, a->split, smp,
-                    out, out_len, trace);
+                    out, out_len, trace, defer);
     HIP_CHECK(hipStreamSynchronize(st));
-    c->phases.ms["sweep"] = now_ms() - t0;
+    c->phases.ms[defer && defer->deferred ? "sweep_setup" : "sweep"] = now_ms() - t0;
     flush_timers(c);
+}
+int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, cge_trace *trace) {
+    if (!c || !a || !out || !out_len) return CGE_E_ARG;
+    CGE_TRY(c)
+    HIP_CHECK(hipSetDevice(c->device));
+    score_one(c, a, out, out_len, trace, nullptr, false);
     CGE_CATCH(c)
+}
+
+// ---- cge_score_batch: K embeddings of the resident graph ("Scoring several embeddings") ----------------------------
+static void upload_member(cge_ctx *c, const cge_embedding_batch *b, i64 k) {
+    const int rc = b->on_device ? cge_set_embedding_device(c, b->embeddings[k], c->n, b->d, b->row_major)
+                                : cge_set_embedding(c, b->embeddings[k], c->n, b->d);
+    if (rc != CGE_OK) CGE_THROW(rc, "score_batch: embedding %lld: %s", (long long)k, c->err.c_str());
+}
+static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embedding_batch *b, double *out, int *out_len,
+                             cge_trace *traces) {
+    const i64 K = b->K;
+    if (!c->src.p || !c->vw.p || !c->comm.p || c->n <= 0 || c->m <= 0)
+        CGE_THROW(CGE_E_ARG, "score_batch: graph and vertex data must be resident (cge_set_graph / cge_set_vertex_data)");
+    if (c->has_coll || c->rccl_comm || c->edges_sharded || c->rows_sharded || c->opt_shard_ingest || c->opt_shard_rows)
+        CGE_THROW(CGE_E_ARG, "score_batch: not under collectives or sharding (one embedding per rank is the multi-GPU form)");
+    for (i64 k = 0; k < K; k++)
+        if (!b->embeddings[k]) CGE_THROW(CGE_E_ARG, "score_batch: embedding %lld is NULL", (long long)k);
+    if (b->on_device)
+        for (i64 k = 0; k < K; k++) {
+            hipPointerAttribute_t at;
+            if (hipPointerGetAttributes(&at, b->embeddings[k]) != hipSuccess || at.type != hipMemoryTypeDevice) {
+                (void)hipGetLastError();
+                CGE_THROW(CGE_E_ARG, "score_batch: embedding %lld is not device memory", (long long)k);
+            }
+        }
+    int dev = 0, cus = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    // the members that can take the batched sweep (undirected landmark mode, the fused fit); the sweep decides the rest
+    // (one member, or a member whose fit takes more than half the chip, shares nothing: it is scored as cge_score scores it)
+    const bool batchable = K >= 2 && a->land != -1 && !a->directed && c->opt_fit_fused && c->opt_fit_persistent != 1;
+    c->stat_fit_batched_launches = c->stat_fit_batched_alphas = 0;
+    c->smp.reset();
+    bool have_samples = false;
+    std::vector<std::unique_ptr<BatchMember>> group;
+    std::vector<i64> redo, group_k;
+    int g_sum = 0, g_nw = 0;
+    double batch_ms = 0.0;
+    auto run_group = [&]() {
+        if (group.empty()) return;
+        std::vector<BatchMember *> g;
+        for (auto &m : group) g.push_back(m.get());
+        const double t0 = now_ms();
+        host_batch_sweep(c, g);
+        batch_ms += now_ms() - t0;
+        for (size_t i = 0; i < group.size(); i++)
+            if (group[i]->redo) redo.push_back(group_k[i]);
+        group.clear(); group_k.clear();
+        g_sum = 0;
+    };
+    for (i64 k = 0; k < K; k++) {
+        upload_member(c, b, k);
+        std::unique_ptr<BatchMember> m(new BatchMember());
+        m->h.max_G = cus / 2;
+        m->out = out + 7 * k; m->out_len = out_len + k; m->trace = traces ? traces + k : nullptr;
+        score_one(c, a, m->out, m->out_len, m->trace, batchable ? &m->h : nullptr, have_samples);
+        have_samples = have_samples || c->smp.n_sets > 0;
+        if (!m->h.deferred) continue; // (scored: the sequential path)
+        if (batch_group_closes(g_sum, g_nw, (int)group.size(), m->h.G, m->h.NW, cus)) run_group();
+        g_sum += m->h.G;
+        g_nw = m->h.NW;
+        group.push_back(std::move(m));
+        group_k.push_back(k);
+    }
+    run_group();
+    flush_timers(c);
+    // members whose batched fit was abandoned: cge_score's own path (which falls back to one launch per iteration as it must)
+    std::sort(redo.begin(), redo.end());
+    for (i64 k : redo) {
+        upload_member(c, b, k);
+        score_one(c, a, out + 7 * k, out_len + k, traces ? traces + k : nullptr, nullptr, true);
+    }
+    if (!redo.empty() && redo.back() != K - 1) { // the resident embedding and landmark state are the last member's
+        upload_member(c, b, K - 1);
+        landmarks_run_impl(c, a->clusters_flat, a->clusters_off, a->n_clusters, a->land, a->forced, a->method, a->directed,
+                           a->directed != 0 || c->opt_landmark_edges != 0);
+    }
+    c->phases.ms["batch_sweep"] = batch_ms; // the launch groups' sweeps, all members (the other phases: the last member's)
+}
+int cge_score_batch(cge_ctx *c, const cge_score_args *a, const cge_embedding_batch *b, double *out, int *out_len,
+                    cge_trace *traces) {
+    if (!c || !a || !b || !out || !out_len || !b->embeddings || b->K < 1 || b->d <= 0 || (b->row_major && !b->on_device))
+        return CGE_E_ARG;
+    for (i64 k = 0; k < b->K; k++) out_len[k] = 0;
+    int rc;
+    try {
+        HIP_CHECK(hipSetDevice(c->device));
+        score_batch_impl(c, a, b, out, out_len, traces);
+        rc = CGE_OK;
+    } catch (const CgeError &e) {
+        c->err = e.msg;
+        rc = e.code;
+    } catch (const std::bad_alloc &) {
+        c->err = "host allocation failed";
+        rc = CGE_E_OOM;
+    } catch (const std::exception &e) {
+        c->err = e.what();
+        rc = CGE_E_ARG;
+    }
+    // on every exit: no sample draw left pending, no hand-off slot taken for armed, no hook left behind
+    c->after_unique = nullptr;
+    c->flow_armed_words = 0;
+    if (c->samp_pending.on) {
+        (void)hipStreamSynchronize(c->stream);
+        c->samp_pending.on = false;
+    }
+    if (rc != CGE_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        for (i64 k = 0; k < b->K; k++) out_len[k] = 0;
+    }
+    return rc;
 }
 
 // ---- helpers ----------------------------------------------------------------------------------------
@@ -1554,6 +1672,8 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "fit_iterations")) *value = c->stat_fit_iters;
     else if (!strcmp(key, "fit_fused_alphas")) *value = c->stat_fit_fused; // alphas of the last sweep whose chain rode on the fit's launch
     else if (!strcmp(key, "fit_persistent_fallbacks")) *value = c->stat_fit_fallbacks;
+    else if (!strcmp(key, "fit_batched_launches")) *value = c->stat_fit_batched_launches;
+    else if (!strcmp(key, "fit_batched_alphas")) *value = c->stat_fit_batched_alphas;
     else if (!strcmp(key, "landmark_batches")) *value = c->stat_lm_batches;
     else if (!strcmp(key, "landmark_batch_rows")) *value = c->stat_lm_rows;
     else if (!strcmp(key, "landmark_splits")) *value = c->stat_lm_splits;
@@ -1644,6 +1764,18 @@ int cge_host_eig_top(const double *A, int64_t d, double *v) {
     if (!A || !v || d <= 0) return CGE_E_ARG;
     host_eig_top(A, d, v);
     return CGE_OK;
+}
+int cge_batch_pack_test(const int64_t *N, int64_t K, int cus, int32_t *group_of) {
+    if (!N || !group_of || K < 0 || cus <= 0) return CGE_E_ARG;
+    int groups = 0, g_sum = 0, g_nw = 0, g_size = 0;
+    for (i64 k = 0; k < K; k++) {
+        int G = 0, NW = 0;
+        if (N[k] < 256 || !k_fit_flow_geometry_cus(N[k], cus, &G, &NW)) { group_of[k] = -1; continue; } // (sequential)
+        if (g_size == 0 || batch_group_closes(g_sum, g_nw, g_size, G, NW, cus)) { groups++; g_sum = 0; g_size = 0; }
+        g_sum += G; g_nw = NW; g_size++;
+        group_of[k] = groups - 1;
+    }
+    return groups;
 }
 int cge_host_pos_draw(int64_t seed, int64_t stream_id, int64_t S, int64_t m, int64_t *pos_idx) {
     if (!pos_idx || S <= 0 || m <= 0) return CGE_E_ARG;

@@ -87,6 +87,11 @@ struct DevBuf {
         n = 0;
         borrowed = false;
     }
+    void swap(DevBuf &o) { // (ownership changes hands; the device pointers stay valid)
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        std::swap(borrowed, o.borrowed);
+    }
     void borrow(const DevBuf &o) {
         if (p == o.p && n == o.n && borrowed) return;
         release();
@@ -362,6 +367,11 @@ struct cge_ctx {
     DevBuf<char> sw_fused_epi;           // the fused chain's tables, one cge_fit_fused per sample set (wgcl_host.cpp)
     int opt_fit_fused = 1;               // 1 (default): landmark-mode sweeps let the rest of an alpha's chain ride on the fit's launch
     i64 stat_fit_fused = 0;              // alphas of the last sweep that did
+    // cge_score_batch (batch_host.cpp): the launch groups' scalars, vect_B, JS partials and hand-off slots; per call: multi-problem
+    // fit launches and the member-alphas they fitted
+    DevBuf<double> batch_scal, batch_vectB, batch_jspart, batch_flow;
+    PinBuf<double> batch_pin;
+    i64 stat_fit_batched_launches = 0, stat_fit_batched_alphas = 0;
     DevBuf<i32> sw_rl_order, sw_rl_comm; // exact mode, N > 8192: the score graph relabelled by community (wgcl_host.cpp)
     DevBuf<double> sw_rl_emb, sw_rl_vec, sw_rl_T;
     DevBuf<unsigned> fp_sync;
@@ -782,6 +792,29 @@ struct cge_chain_tail {
 void k_bins_js(cge_ctx *c, const i32 *cm_off, i64 N, i64 C, const double *vC, double *vectB, int n_modes, double *fpart,
                const cge_chain_tail *tail = nullptr);
 bool k_fit_flow_arm_region(cge_ctx *c, i64 N, i64 Tld, uint4 **ptr, i64 *n16, unsigned *word); // the fit's hand-off slots (for the tail above)
+// ---- cge_score_batch: several fused fits in one launch, and the bins / JS launches of all of them (kernels_fitp.hip, kernels_fit.hip)
+// One problem of fit_flow_multi_kernel: the arguments of its fit_flow_kernel<1, NW, true, 1> launch (and its FlowFused), its
+// grid size G and its first workgroup wg0 in the concatenated grid
+struct cge_flow_problem {
+    const double *Lh; const float *Ll; double alpha; const cge_fit_fused *epi; int want, pad0;
+    const double *T0; double *Tout; const double *w;
+    double *ring, *P, *fq; unsigned *sync; int *flags;
+    i64 N, Tld; int Nt, G, wg0, pad1;
+};
+// the geometry fit_flow_kernel uses for N (false: the persistent form does not apply), and the hand-off slots one problem needs
+bool k_fit_flow_geometry(i64 N, int *G, int *NW);
+i64 k_fit_flow_slot_doubles(i64 N, i64 Tld);
+#define CGE_BATCH_MAX 16 // problems per launch group (G >= 16 for every fused problem: 256 CUs hold no more than 16)
+struct cge_flow_multi { cge_flow_problem p[CGE_BATCH_MAX]; int n, pad; }; // passed by value (kernel arguments)
+// lay the problems' slots out in `flow` (k_fit_flow_slot_doubles each, in order), arm them all and launch; ring / P / fq / sync
+// and wg0 are filled in here.  The problems share NW; the sum of their G must not exceed the CU count (the caller packs them).
+void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, double delta, DevBuf<double> &flow);
+bool k_fit_flow_multi_fits(int NW); // the multi-problem kernel of NW waves gets a workgroup on a CU
+struct cge_bins_problem { const double *partial; const i32 *cm_off, *fc, *ns, *base; i64 C; int Nt, pad; double *vectB; };
+struct cge_js_problem { const double *vC, *vB; i64 len, C; int mode, pad; double *part, *fpart; };
+struct cge_bins_multi { cge_bins_problem p[CGE_BATCH_MAX]; };
+struct cge_js_multi { cge_js_problem p[2 * CGE_BATCH_MAX]; }; // (--split-global: two entries per problem)
+void k_bins_js_multi(cge_ctx *c, const cge_bins_multi &bins, int n_bins, i64 max_C, const cge_js_multi &js, int n_js);
 void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_off, i64 N, int directed); // the tile partials only
 void k_auc_prepare(cge_ctx *c, const i32 *v2l, const i32 *old2new, const double *vw_orig, const double *lweight, const i32 *pi,
                    const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, i32 *aidx, double *afac, double *aden);
@@ -864,6 +897,37 @@ struct OrigView { // original graph pieces needed in landmark mode (device, 0-ba
     double hi = 0.0;             // diameter
     const i32 *h_lcomm = nullptr; // host copy of the landmarks' communities (the score graph's G.comm), when the caller has one
 };
+// What a landmark-mode sweep on the fused path has prepared when cge_score_batch takes it over instead of running it
+// (host_wgcl_sweep with `defer`): the buffers the fused fit, vect_B and JS read, moved out of the context (their device
+// pointers stay valid), and the host copy of the epilogue tables (auc_part is re-pointed by the batch).
+struct SweepHandoff {
+    int max_G = 0;          // (set by the batch) a fit of more workgroups shares no launch: the sweep runs as cge_score's
+    bool deferred = false;
+    i64 N = 0, C = 0, S = 0, n_sets = 0, Tld = 0;
+    int split = 0, G = 0, NW = 0; // (G, NW: the geometry of its fit)
+    DevBuf<double> Lh, vw, bt_part, vectC, T, fused_pw;
+    DevBuf<float> Ll;
+    DevBuf<i32> comm, bt_fc, bt_ns, bt_base, cm_off;
+    std::vector<std::unique_ptr<DevSamples>> dsets;
+    std::vector<cge_fit_fused> h_epi;
+    const double *w = nullptr; // the fit's targets (inside `vw`)
+};
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
                      const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],
-                     int *out_len, cge_trace *trace);
+                     int *out_len, cge_trace *trace, SweepHandoff *defer = nullptr);
+// cge_score_batch's launch groups: members in order, a group closes when the next member's G would take the sum beyond
+// `cus` or its NW differs; group_of[k] = the group of member k (-1: not batched, G[k] <= 0).  Returns the number of groups.
+bool batch_group_closes(int g_sum, int g_nw, int g_size, int G, int NW, int cus);
+// one member of a batch whose sweep was handed over: its outputs, and `redo` = its persistent fit was abandoned (the batch
+// scores it again on its own, through cge_score's path)
+struct BatchMember {
+    SweepHandoff h;
+    double *out = nullptr;
+    int *out_len = nullptr;
+    cge_trace *trace = nullptr;
+    bool redo = false;
+};
+// the alpha sweeps of one launch group in lock-step (sum of G <= CUs, one NW, at most CGE_BATCH_MAX members)
+void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group);
+// fit_flow_kernel's geometry for N landmarks on `cus` CUs (no device needed); false: the fused form does not apply
+bool k_fit_flow_geometry_cus(i64 N, int cus, int *G, int *NW);

@@ -543,6 +543,26 @@ __global__ __launch_bounds__(256) void bvec_bins_kernel(const double *__restrict
         vectB[directed ? e : C * ca - ca * (ca - 1) / 2 + (cb - ca)] = acc;
     }
 }
+// cge_score_batch: bvec_bins_kernel for several undirected problems, problem blockIdx.y -- its loop with the block index and grid
+// size of the problem, so every bin is the same additions in the same order (a copy: bvec_bins_kernel's code stays as it is)
+__global__ __launch_bounds__(256) void bvec_bins_multi_kernel(const cge_bins_multi tab) {
+    const cge_bins_problem &q = tab.p[blockIdx.y];
+    const i64 C = q.C, total = C * C, stride = (i64)gridDim.x * blockDim.x;
+    const int Nt = q.Nt;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const i64 ca = e / C, cb = e - ca * C;
+        if (cb < ca) continue;
+        const i32 a0 = q.cm_off[ca], a1 = q.cm_off[ca + 1], b0 = q.cm_off[cb], b1 = q.cm_off[cb + 1];
+        double acc = 0.0;
+        if (a1 > a0 && b1 > b0)
+            for (int I = a0 >> 6; I <= (a1 - 1) >> 6; I++)
+                for (int J = b0 >> 6; J <= (b1 - 1) >> 6; J++) {
+                    if (J < I) continue;
+                    acc = __dadd_rn(acc, q.partial[(i64)q.base[I * Nt + J] + (i64)(ca - q.fc[I]) * q.ns[J] + (cb - q.fc[J])]);
+                }
+        q.vectB[C * ca - ca * (ca - 1) / 2 + (cb - ca)] = acc;
+    }
+}
 void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_off, i64 N, int directed) {
     ScopedKernelTimer t(c, "bvec");
     const int Nt = (int)((N + 63) / 64);
@@ -635,6 +655,35 @@ __global__ __launch_bounds__(256) void js_terms_kernel(const double *__restrict_
         }
     f = block_sum_256(f, sh);
     if (threadIdx.x == 0) fpart[blockIdx.x] = f;
+}
+// cge_score_batch: js_sums_kernel / js_terms_kernel for several undirected (problem, mode) entries, entry blockIdx.y (copies of
+// their bodies: the same additions in the same order, while their own code stays as it is)
+__global__ __launch_bounds__(256) void js_sums_multi_kernel(const cge_js_multi tab) {
+    const cge_js_problem &q = tab.p[blockIdx.y];
+    __shared__ double sh[256];
+    double s1 = 0.0, s2 = 0.0, cnt = 0.0;
+    for (i64 k = (i64)blockIdx.x * 256 + threadIdx.x; k < q.len; k += (i64)gridDim.x * 256)
+        if (js_selected(k, q.C, 0, q.mode)) { s1 += q.vC[k]; s2 += q.vB[k]; cnt += 1.0; }
+    s1 = block_sum_256(s1, sh);
+    s2 = block_sum_256(s2, sh);
+    cnt = block_sum_256(cnt, sh);
+    if (threadIdx.x == 0) { q.part[3 * blockIdx.x] = s1; q.part[3 * blockIdx.x + 1] = s2; q.part[3 * blockIdx.x + 2] = cnt; }
+}
+__global__ __launch_bounds__(256) void js_terms_multi_kernel(const cge_js_multi tab) {
+    const cge_js_problem &q = tab.p[blockIdx.y];
+    __shared__ double sh[256];
+    double s1 = 0.0, s2 = 0.0, cnt = 0.0;
+    for (int b = 0; b < JS_BLOCKS; b++) { s1 += q.part[3 * b]; s2 += q.part[3 * b + 1]; cnt += q.part[3 * b + 2]; }
+    const double sp1 = s1 + cnt, sp2 = s2 + cnt;
+    double f = 0.0;
+    for (i64 k = (i64)blockIdx.x * 256 + threadIdx.x; k < q.len; k += (i64)gridDim.x * 256)
+        if (js_selected(k, q.C, 0, q.mode)) {
+            const double p = (q.vC[k] + 1.0) / sp1, r = (q.vB[k] + 1.0) / sp2;
+            const double m = (p + r) / 2.0;
+            f += p * log(p / m) + r * log(r / m);
+        }
+    f = block_sum_256(f, sh);
+    if (threadIdx.x == 0) q.fpart[blockIdx.x] = f;
 }
 __global__ void js_final_kernel(const double *__restrict__ fpart, double *__restrict__ out) { // one wave
     const double v = fpart[threadIdx.x]; // JS_BLOCKS == 64: one load per lane, then the sum in block order
@@ -846,6 +895,20 @@ void k_js(cge_ctx *c, const double *vC, const double *vB, i64 len, i64 C, int di
     hipLaunchKernelGGL(js_terms_kernel, dim3(JS_BLOCKS), dim3(256), 0, c->stream, vC, vB, len, C, directed, mode,
                        c->js_part.p, fpart);
     if (!partials) hipLaunchKernelGGL(js_final_kernel, dim3(1), dim3(64), 0, c->stream, fpart, out);
+}
+// cge_score_batch: vect_B from the tile partials of n_probs problems, then the JS block sums of n_js entries (fpart of each = the
+// CGE_PARTIAL_BLOCKS partials the host adds) -- one launch per step for all of them
+void k_bins_js_multi(cge_ctx *c, const cge_bins_multi &bins, int n_probs, i64 max_C, const cge_js_multi &js, int n_js) {
+    if (n_probs > 0) {
+        ScopedKernelTimer t(c, "bvec_batched");
+        hipLaunchKernelGGL(bvec_bins_multi_kernel, dim3(grid_for(max_C * max_C, 256, 1024), (unsigned)n_probs), dim3(256), 0, c->stream,
+                           bins);
+    }
+    if (n_js > 0) {
+        ScopedKernelTimer t(c, "js_batched");
+        hipLaunchKernelGGL(js_sums_multi_kernel, dim3(JS_BLOCKS, (unsigned)n_js), dim3(256), 0, c->stream, js);
+        hipLaunchKernelGGL(js_terms_multi_kernel, dim3(JS_BLOCKS, (unsigned)n_js), dim3(256), 0, c->stream, js);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

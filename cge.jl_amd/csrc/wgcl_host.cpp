@@ -99,7 +99,7 @@ static void sampled_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi
 
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
                      const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],
-                     int *out_len, cge_trace *trace) {
+                     int *out_len, cge_trace *trace, SweepHandoff *defer) {
     const double delta = 0.001, AlphaMax = 10.0, AlphaStep = 0.25; // :35-37 / :288-290
     ScoreGraph G = G_in; // the per-vertex arrays may be replaced by community-sorted copies (below)
     const i64 N = G.N, C = G.C, d = G.d;
@@ -407,6 +407,37 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
         pk.flush();
     }
     c->stat_fit_fused = 0;
+
+    // cge_score_batch: a sweep on the fused path is prepared here and run by the batch, beside other members' sweeps
+    // (batch_host.cpp); what its alphas read moves out of the context into the hand-off, everything else stays scratch
+    if (defer) defer->deferred = false;
+    int fG = 0, fNW = 0;
+    if (defer && fuse && fuse_auc && use_persistent && !shard_samples && !c->has_coll && k_fit_flow_geometry(N, &fG, &fNW) &&
+        fG <= defer->max_G && k_fit_flow_multi_fits(fNW)) {
+        SweepHandoff &h = *defer;
+        k_pow_prepare(c, D.p, N, true, true);
+        h.Lh.swap(c->sw_Lh); h.Ll.swap(c->sw_Ll);
+        c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the hand-off)
+        h.comm.swap(c->sw_rl_comm); h.vw.swap(c->sw_rl_vec);
+        h.bt_fc.swap(c->sw_bt_fc); h.bt_ns.swap(c->sw_bt_ns); h.bt_base.swap(c->sw_bt_base); h.bt_part.swap(c->sw_bt_part);
+        h.cm_off.swap(d_cm_off); h.fused_pw.swap(c->sw_fused_pw);
+        h.dsets.clear();
+        for (i64 t = 0; t < smp.n_sets; t++) {
+            h.dsets.emplace_back(std::move(dsets[t]));
+            dsets[t].reset(new DevSamples());
+        }
+        h.vectC.ensure(vlen); // (the context's vect_C is landmark state of the member: copied)
+        HIP_CHECK(hipMemcpyAsync(h.vectC.p, G.vectC, sizeof(double) * vlen, hipMemcpyDeviceToDevice, st));
+        h.T.ensure((size_t)3 * Tld); // T rotates through three parts (as TT above); T_0 = ones
+        HIP_CHECK(hipMemcpyAsync(h.T.p, TT.p, sizeof(double) * 3 * Tld, hipMemcpyDeviceToDevice, st));
+        h.N = N; h.C = C; h.S = S; h.n_sets = smp.n_sets; h.Tld = Tld; h.split = split;
+        h.G = fG; h.NW = fNW;
+        h.h_epi = h_epi;
+        h.w = G.vw;
+        h.deferred = true;
+        HIP_CHECK(hipStreamSynchronize(st)); // (the staging packer's host memory)
+        return;
+    }
 
     // ---- alpha sweep ---------------------------------------------------------------------------
     int alpha_div_counter = 5, alpha_auc_counter = 5; // :38

@@ -1,0 +1,52 @@
+#!/usr/bin/env python3
+"""cge_compare.py -- score several embeddings of one graph in one call (cge_score_batch).
+
+The flags of cge_cli.py, with `-e` given once per embedding; prints one line per embedding: the file name, a tab, and its
+result vector as cge_cli.py prints it (the same vector cge_cli.py gives for that file alone).
+
+    python cge_compare.py -g graph.edgelist -c graph.ecg -e a.embedding -e b.embedding -l 200 --seed 42
+"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def split_embeddings(argv):
+    """(argv with the first -e only, [every -e file in order])"""
+    files, rest, i = [], [], 0
+    while i < len(argv):
+        if argv[i] == "-e" and i + 1 < len(argv):
+            files.append(argv[i + 1])
+            i += 2
+            continue
+        rest.append(argv[i])
+        i += 1
+    return (rest + ["-e", files[0]] if files else rest), files
+
+
+def main(argv=None):
+    import cge.jl_amd as CGE
+    from cge.jl_amd import api
+    from cge.jl_amd.args import read_embedding
+    from cge_cli import julia_vector
+
+    argv = list(sys.argv[1:] if argv is None else argv)
+    first_argv, files = split_embeddings(argv)
+    (edges, weights, vweights, comm, clusters, embed, verbose, land, forced, method, directed, split, seed,
+     samples) = CGE.parseargs(first_argv)
+    if not files:
+        return 1
+    n = embed.shape[0]
+    embeddings = [embed] + [read_embedding(f, n) for f in files[1:]]  # (the library's parallel text reader)
+    ctx = api.default_context()
+    ctx.set_graph(edges, weights, n)
+    ctx.set_vertex_data(comm, vweights)
+    results = ctx.score_batch(embeddings, clusters, land, forced, method, directed, split, seed, samples)
+    for f, r in zip(files, results):
+        print(f"{f}\t{julia_vector(r)}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

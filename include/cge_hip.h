@@ -204,6 +204,26 @@ typedef struct {
 } cge_score_args;
 int cge_score(cge_ctx *ctx, const cge_score_args *args, double out[7], int *out_len, cge_trace *trace);
 
+/* cge_score for K embeddings of the resident graph in one call: member k's vector (out + 7 k, out_len[k] = 7, or 6 for the
+ * directed star return) and trace (traces + k, optional) are what cge_score(args) gives on that embedding on this context with
+ * the same options -- the same bits and iteration counts.  The graph and the vertex data must be resident; the resident
+ * embedding is replaced member by member, and afterwards the resident embedding and landmark state are the LAST member's.
+ * Undirected landmark-mode members on the fused persistent fit (>= 256 landmarks, options fit_fused = 1, fit_persistent != 1)
+ * share their sweeps: the members' fits of an alpha run in ONE launch (launch groups of at most the CU count in workgroups,
+ * run one after another), and so do their vect_B and JS; the local score's samples are drawn once.  Every other member
+ * (directed, exact mode land = -1, fewer landmarks) is scored on its own, as cge_score would.  Not under collectives or
+ * sharding (CGE_E_ARG: one embedding per rank is the multi-GPU form).  On an error (e.g. CGE_E_HOMOGENEOUS of a member) the
+ * call returns it with every out_len[k] = 0; the context stays usable.  Stats "fit_batched_launches" / "fit_batched_alphas":
+ * multi-problem fit launches of the last call and the member-alphas they fitted.                                            */
+typedef struct {
+    const double *const *embeddings; /* K pointers, each n x d (the resident graph's n), one common d */
+    int64_t K, d;
+    int on_device;                   /* 0: host, column-major (as cge_set_embedding); 1: device (as cge_set_embedding_device) */
+    int row_major;                   /* device pointers only: 1 = a vertex's d features contiguous */
+} cge_embedding_batch;
+int cge_score_batch(cge_ctx *ctx, const cge_score_args *args, const cge_embedding_batch *batch, double *out /* K x 7 */,
+                    int *out_len /* K */, cge_trace *traces /* K or NULL */);
+
 /* ---- louvain_clust(): src/clustering.jl:14-68 (called by parseargs when `-c` is omitted, src/auxilary.jl:115-121) ----
  * The communities the reference writes to <file>.ecg: LEVEL 1 of Louvain (`hierarchy -l 1`: the partition after the first
  * pass of local moving), here computed on the resident graph (cge_set_graph; weights honoured) by synchronous rounds on
@@ -304,6 +324,7 @@ int cge_set_option(cge_ctx *ctx, const char *key, int64_t value);
 /* "landmarks" (N of the last run, no side effects), "diameter_path" (1 brute / 2 pruned), "diameter_candidate_pairs", "diameter_candidate_tiles", "diameter_refs" (reference points) of the last run;
  * "collective_calls" / "collective_bytes" = all-reduces issued by the in-library RCCL path since cge_create;
  * "diameter_bits" = the bit pattern of the last `hi` (reinterpret the int64 as a double);
+ * "fit_batched_launches" / "fit_batched_alphas" = multi-problem fit launches of the last cge_score_batch and the member-alphas they fitted;
  * "fit_persistent_alphas" = alphas of the last sweep fitted by a persistent launch, "fit_persistent_fallbacks" = persistent fits abandoned since the context was created, "fit_iterations" = Chung-Lu
  * iterations of the last sweep (all alphas); "landmark_batches" / "landmark_batch_rows" / "landmark_splits" =
  * device batches of the last runsplit, the rows they covered, the groups they split; "cut_tie_tasks" = groups of the size / diameter rules
@@ -336,7 +357,8 @@ int cge_profile_select(cge_ctx *ctx, const char *names);
 int cge_profile_get(cge_ctx *ctx, const char *name, int64_t *launches, double *total_ms);
 int cge_profile_names(cge_ctx *ctx, char *buf, int64_t buf_len); /* comma-separated */
 /* wall-clock phase timers of the last cge_score call: "landmarks","aggregate","scatter","dist",
- * "diameter","sweep","samples" (milliseconds, host clock around stream-synchronised phases)      */
+ * "diameter","sweep","samples" (milliseconds, host clock around stream-synchronised phases); after cge_score_batch the
+ * last member's, and "batch_sweep" = the shared sweeps of all launch groups ("sweep_setup": a member's set-up of one) */
 int cge_phase_ms(cge_ctx *ctx, const char *phase, double *ms);
 int cge_phase_names(cge_ctx *ctx, char *buf, int64_t buf_len); /* comma-separated, incl. the lm_* sub-phases */
 

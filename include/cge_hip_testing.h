@@ -9,6 +9,11 @@ extern "C" {
 #endif
 /* principal eigenvector of a symmetric d x d matrix (replaces eigvecs(A)[:, end], src/landmarks.jl:99) */
 int cge_host_eig_top(const double *A, int64_t d, double *v);
+/* cge_score_batch's launch groups for members of N[k] landmarks on `cus` CUs (no device work): group_of[k] = the launch group of
+ * member k, -1 for a member outside the fused fit's geometry (scored on its own); returns the number of groups.  Members keep
+ * their order; a group closes when the next member's workgroups would exceed `cus`, its waves per workgroup differ, or it holds
+ * 16 members. */
+int cge_batch_pack_test(const int64_t *N, int64_t K, int cus, int32_t *group_of);
 /* the sampler's counter-based draw of positive rows: pos_idx[k] in 1..m (no device work) */
 int cge_host_pos_draw(int64_t seed, int64_t stream_id, int64_t S, int64_t m, int64_t *pos_idx);
 /* kernel-level hook (needs the GPU): principal eigenvectors of T symmetric d x d matrices (row-major, back to
