@@ -2,11 +2,10 @@
 // Every member of a group was prepared by host_wgcl_sweep on the fused path and handed over (SweepHandoff).  An alpha of the group
 // is three launches for all its live members -- fit_flow_multi_kernel (the members' fused fits side by side), bvec_bins_multi_kernel
 // and the two JS kernels with the member in blockIdx.y -- and one copy of the members' scalars to the host.  Per member the host
-// keeps what host_wgcl_sweep keeps: its T rotating through three vectors, its patience counters (src/divergence.jl:215-223,
-// :242-253), its partial sums added in block order.  So a member's iterates, iteration counts and scores are those of its own
-// cge_score.
+// keeps what host_wgcl_sweep keeps: its T rotating through three vectors and its alpha bookkeeping (AlphaBook: the patience
+// counters of src/divergence.jl:215-223, :242-253, the partial sums added in block order).  So a member's iterates, iteration
+// counts and scores are those of its own cge_score.
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 #include "common.hpp"
@@ -16,14 +15,10 @@ bool batch_group_closes(int g_sum, int g_nw, int g_size, int G, int NW, int cus)
 }
 
 void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
-    const double delta = 0.001, AlphaMax = 10.0, AlphaStep = 0.25; // src/divergence.jl:35-37
-    const i64 n_alpha_total = (i64)std::floor((AlphaMax + delta) / AlphaStep + 1e-9);
+    const i64 n_alpha = AlphaBook::n_alpha;
     const int K = (int)group.size();
     if (K < 1) return;
     hipStream_t st = c->stream;
-    // the scalars of an alpha per member, laid out as host_wgcl_sweep's (tallies, the shared-verdict slot, JS partials, the fit's flags)
-    constexpr i64 RES_AUC = 0, RES_JS = 2 * CGE_PARTIAL_BLOCKS + 2, RES_FIT = RES_JS + 2 * CGE_PARTIAL_BLOCKS,
-                  RES_STRIDE = RES_FIT + 16;
     const int NW = group[0]->h.NW;
     i64 vtot = 0;
     std::vector<i64> voff(K);
@@ -35,18 +30,16 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
     c->batch_vectB.ensure((size_t)vtot);
     c->batch_jspart.ensure((size_t)2 * K * 3 * CGE_PARTIAL_BLOCKS);
     c->batch_pin.ensure((size_t)2 * K * RES_STRIDE);
-    double *scal = c->batch_scal.p;
+    double *scal = c->batch_scal.p; // the members' scalars of an alpha (RES_*), RES_STRIDE apart
 
     struct Live {
-        int div_counter = 5, auc_counter = 5; // :38
-        bool skip_div = false, skip_auc = false, done = false;
-        double best_div = INFINITY, best_div_ext = INFINITY, best_div_int = INFINITY, best_auc_err = INFINITY, best_auc = INFINITY;
-        double best_alpha = -1.0, best_alpha_auc = -1.0;
-        int tpar = 0;        // the part of T that holds the current iterate
+        int tpar = 0;         // the part of T that holds the current iterate
         i64 next_enqueue = 1; // the next alpha to enqueue
-        DevBuf<char> epi;    // the epilogue tables with the tallies pointed at this member's scalars
+        DevBuf<char> epi;     // the epilogue tables with the tallies pointed at this member's scalars
+        bool done = false;
     };
     std::vector<Live> live(K);
+    std::vector<AlphaBook> book;
     for (int j = 0; j < K; j++) {
         SweepHandoff &h = group[j]->h;
         std::vector<cge_fit_fused> e = h.h_epi;
@@ -54,14 +47,14 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
         live[j].epi.ensure(e.size() * sizeof(cge_fit_fused));
         HIP_CHECK(hipMemcpyAsync(live[j].epi.p, e.data(), e.size() * sizeof(cge_fit_fused), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st)); // (pageable source)
-        if (group[j]->trace) group[j]->trace->n_alpha = 0;
+        book.emplace_back(h.S, h.split, group[j]->trace);
     }
     auto running = [&](int j) { return !live[j].done && !group[j]->redo; };
 
     // one alpha for the members in `A`: the fits, vect_B, JS, the scalars to pinned slot (ia & 1), an event
     auto enqueue = [&](i64 ia, const std::vector<int> &A) {
         if (A.empty()) return;
-        const double alpha = AlphaStep * (double)ia;
+        const double alpha = AlphaBook::AlphaStep * (double)ia;
         cge_flow_multi tab{};
         cge_bins_multi bins{};
         cge_js_multi js{};
@@ -72,7 +65,7 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
             const int j = A[i];
             Live &L = live[j];
             SweepHandoff &h = group[j]->h;
-            const bool want_auc = !L.skip_auc, want_div = !L.skip_div;
+            const bool want_auc = !book[j].skip_auc, want_div = !book[j].skip_div;
             const int Nt = (int)((h.N + 63) / 64), tnext = (L.tpar + 1) % 3;
             double *sj = scal + (i64)j * RES_STRIDE;
             cge_flow_problem &q = tab.p[i];
@@ -95,7 +88,7 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
                 js.p[nj] = cge_js_problem{h.vectC.p, vB, packed_len(h.C), h.C, modes[u], 0,
                                           c->batch_jspart.p + (i64)nj * 3 * CGE_PARTIAL_BLOCKS, sj + RES_JS + u * CGE_PARTIAL_BLOCKS};
         }
-        k_fit_flow_multi(c, tab, NW, 0.25, delta, c->batch_flow);
+        k_fit_flow_multi(c, tab, NW, 0.25, AlphaBook::delta, c->batch_flow);
         c->stat_fit_batched_launches++;
         k_bins_js_multi(c, bins, nb, maxC, js, nj);
         const int slot = (int)(ia & 1);
@@ -104,7 +97,7 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
         HIP_CHECK(hipEventRecord(c->sweep_ev[slot], st));
     };
 
-    for (i64 ia = 1; ia <= n_alpha_total; ia++) {
+    for (i64 ia = 1; ia <= n_alpha; ia++) {
         std::vector<int> A, B;
         for (int j = 0; j < K; j++)
             if (running(j) && live[j].next_enqueue == ia) A.push_back(j);
@@ -114,17 +107,13 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
         for (int j = 0; j < K; j++) {
             if (!running(j)) continue;
             any = true;
-            const Live &L = live[j];
-            const bool may_end_here = (L.skip_div || L.div_counter == 1) && (L.skip_auc || L.auc_counter == 1);
-            if (!may_end_here && ia < n_alpha_total && L.next_enqueue == ia + 1) B.push_back(j);
+            if (!book[j].may_end_here() && ia < n_alpha && live[j].next_enqueue == ia + 1) B.push_back(j);
         }
         if (!any) break;
         enqueue(ia + 1, B);
         HIP_CHECK(hipEventSynchronize(c->sweep_ev[ia & 1]));
-        const double alpha = AlphaStep * (double)ia;
         for (int j = 0; j < K; j++) {
             if (!running(j)) continue;
-            Live &L = live[j];
             BatchMember &mb = *group[j];
             const double *res = c->batch_pin.p + (i64)(ia & 1) * K * RES_STRIDE + (i64)j * RES_STRIDE;
             const int *hf = reinterpret_cast<const int *>(res + RES_FIT);
@@ -133,64 +122,11 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
                 mb.redo = true;
                 continue;
             }
-            const i64 iters = hf[1];
             c->stat_fit_batched_alphas++;
-            double auc_val = NAN, div_val = NAN, div_int = 0.0, div_ext = 0.0;
-            double hs[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            if (!L.skip_auc)
-                for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { hs[0] += res[RES_AUC + 2 * b]; hs[1] += res[RES_AUC + 2 * b + 1]; }
-            if (!L.skip_div) {
-                double fa = 0.0, fb = 0.0;
-                for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { fa += res[RES_JS + b]; fb += res[RES_JS + CGE_PARTIAL_BLOCKS + b]; }
-                if (!mb.h.split) hs[2] = fa / 2.0;
-                else { hs[3] = fa / 2.0; hs[4] = fb / 2.0; }
-            }
-            if (!L.skip_auc) {
-                const double auc = 1.0 - hs[0] / hs[1]; // :213
-                auc_val = auc;
-                if (auc < L.best_auc) {
-                    L.best_auc = auc;
-                    L.best_auc_err = 1.96 * std::sqrt(auc * (1.0 - auc) / (double)mb.h.S); // :217
-                    L.best_alpha_auc = alpha;
-                    L.auc_counter = 5;
-                } else {
-                    L.auc_counter -= 1;
-                    L.skip_auc = L.auc_counter == 0;
-                }
-            }
-            if (!L.skip_div) {
-                double f;
-                if (!mb.h.split)
-                    f = hs[2];
-                else {
-                    div_int = hs[3];
-                    div_ext = hs[4];
-                    f = (div_int + div_ext) / 2.0;
-                }
-                div_val = f;
-                if (f < L.best_div) {
-                    L.best_div = f;
-                    L.best_alpha = alpha;
-                    L.best_div_ext = !mb.h.split ? 0.0 : div_ext;
-                    L.best_div_int = !mb.h.split ? 0.0 : div_int;
-                    L.div_counter = 5;
-                } else {
-                    L.div_counter -= 1;
-                    L.skip_div = L.div_counter == 0;
-                }
-            }
-            if (mb.trace && mb.trace->n_alpha < 64) {
-                mb.trace->iters[mb.trace->n_alpha] = iters;
-                mb.trace->div[mb.trace->n_alpha] = div_val;
-                mb.trace->auc[mb.trace->n_alpha] = auc_val;
-                mb.trace->n_alpha++;
-            }
-            if ((L.skip_div && L.skip_auc) || ia == n_alpha_total) { // :253
-                L.done = true;
-                double *out = mb.out;
-                out[0] = L.best_alpha; out[1] = L.best_div; out[2] = L.best_div_ext; out[3] = L.best_div_int;
-                out[4] = L.best_alpha_auc; out[5] = L.best_auc; out[6] = L.best_auc_err; // :256
-                *mb.out_len = 7;
+            book[j].take(res, AlphaBook::AlphaStep * (double)ia, hf[1]);
+            if (book[j].ended() || ia == n_alpha) {
+                live[j].done = true;
+                book[j].write(mb.out, mb.out_len);
             }
         }
     }

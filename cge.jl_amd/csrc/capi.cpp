@@ -970,9 +970,8 @@ static void make_samples(cge_ctx *c, i64 seed, i64 S, int directed, bool exact_d
     }
     // seeded: one set reused at every alpha (Random.seed! before each draw, src/divergence.jl:184,193);
     // unseeded: a fresh set per alpha, keyed by an arbitrary fixed base seed and the alpha index
-    const i64 n_alpha = 40;
     smp.S = S;
-    smp.n_sets = (seed != -1) ? 1 : n_alpha;
+    smp.n_sets = (seed != -1) ? 1 : AlphaBook::n_alpha;
     const i64 base = (seed != -1) ? seed : 0x5eedc0de;
     if (sampler_uses_device(c)) { // large resident graph: drawn, rejected and kept on the device (the same stream of draws)
         smp.on_device = true;
@@ -1118,8 +1117,12 @@ static void upload_i64_as_i32(cge_ctx *c, const i64 *h, i64 cnt, i64 lo, i64 hi,
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 
-// star-graph guard of wGCL_directed (src/divergence.jl:321-334)
-static bool is_star(const std::vector<i32> &star, i64 N) {
+// star-graph guard of wGCL_directed (src/divergence.jl:321-334): the star counts of the degree pass are read back; a star graph
+// gets the reference's 6-element return (true)
+static bool star_return(cge_ctx *c, const i32 *d_star, i64 N, double out[7], int *out_len) {
+    std::vector<i32> star(N);
+    HIP_CHECK(hipMemcpyAsync(star.data(), d_star, sizeof(i32) * N, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
     bool has_nm1 = false, has_2nm1 = false;
     i64 sum = 0, cnt2 = 0;
     for (i64 i = 0; i < N; i++) {
@@ -1128,7 +1131,40 @@ static bool is_star(const std::vector<i32> &star, i64 N) {
         sum += star[i];
         if (star[i] == 2) cnt2++;
     }
-    return (has_nm1 && sum == 2 * (N - 1)) || (has_2nm1 && cnt2 == N - 1);
+    if (!((has_nm1 && sum == 2 * (N - 1)) || (has_2nm1 && cnt2 == N - 1))) return false;
+    out[0] = -1.0;
+    for (int k = 1; k < 6; k++) out[k] = 0.0;
+    *out_len = 6;
+    return true;
+}
+
+// the exact mode's directed degree pass: in- / out-degrees (c->s_degin / s_degout) and star counts from the score graph's edges
+static void edge_degrees(cge_ctx *c, const i32 *src, const i32 *dst, const double *w, i64 m, i64 N, DevBuf<i32> &star) {
+    hipStream_t st = c->stream;
+    c->s_degin.ensure(N);
+    c->s_degout.ensure(N);
+    star.ensure(N);
+    HIP_CHECK(hipMemsetAsync(c->s_degin.p, 0, sizeof(double) * N, st));
+    HIP_CHECK(hipMemsetAsync(c->s_degout.p, 0, sizeof(double) * N, st));
+    HIP_CHECK(hipMemsetAsync(star.p, 0, sizeof(i32) * N, st));
+    k_edge_degrees(c, src, dst, w, m, c->s_degout.p, c->s_degin.p, star.p);
+}
+
+// what a landmark-mode sweep reads of the original graph: the resident one, with `lweight` as the landmarks' weights
+static OrigView resident_orig_view(cge_ctx *c, const double *lweight) {
+    OrigView ov;
+    ov.n = c->n; ov.m = c->m; ov.Xr = c->Xr.p; ov.vw = c->vw.p; ov.v2l = c->v2l.p; ov.lweight = lweight;
+    ov.src = c->src.p; ov.dst = c->dst.p; ov.h_w = c->h_w.empty() ? nullptr : c->h_w.data();
+    return ov;
+}
+
+// the diameter of the landmark embedding `lemb` (0-based communities `lcomm`), the largest of the ranks' shares: full_graph_D's
+// normaliser (src/divergence.jl:104-114)
+static double landmark_diameter(cge_ctx *c, const double *lemb, const double *lweight, const std::vector<i32> &lcomm, i64 C, i64 N) {
+    double hi = resident_diameter_lm(c, lemb, lweight, lcomm, C, N, c->has_coll ? c->coll.rank : 0, c->has_coll ? c->coll.world : 1);
+    hi = allreduce_scalar_max(c, hi);
+    c->stat_last_hi = hi;
+    return hi;
 }
 
 int cge_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cge_trace *trace) {
@@ -1175,23 +1211,9 @@ int cge_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cg
     G.N = N; G.d = d; G.C = C;
     G.emb = c->s_emb.p; G.dist = c->s_dist.p; G.vw = c->s_vw.p; G.comm = c->s_comm.p; G.vectC = c->s_vectC.p;
     if (directed) {
-        c->s_degin.ensure(N);
-        c->s_degout.ensure(N);
         DevBuf<i32> star;
-        star.ensure(N);
-        HIP_CHECK(hipMemsetAsync(c->s_degin.p, 0, sizeof(double) * N, st));
-        HIP_CHECK(hipMemsetAsync(c->s_degout.p, 0, sizeof(double) * N, st));
-        HIP_CHECK(hipMemsetAsync(star.p, 0, sizeof(i32) * N, st));
-        k_edge_degrees(c, g_src.p, g_dst.p, g_w.p, a->m, c->s_degout.p, c->s_degin.p, star.p);
-        std::vector<i32> hstar(N);
-        HIP_CHECK(hipMemcpyAsync(hstar.data(), star.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (is_star(hstar, N)) {
-            out[0] = -1.0;
-            for (int k = 1; k < 6; k++) out[k] = 0.0;
-            *out_len = 6;
-            return CGE_OK;
-        }
+        edge_degrees(c, g_src.p, g_dst.p, g_w.p, a->m, N, star);
+        if (star_return(c, star.p, N, out, out_len)) return CGE_OK;
         G.deg_in = c->s_degin.p;
         G.deg_out = c->s_degout.p;
     }
@@ -1218,15 +1240,10 @@ int cge_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cg
             for (i64 i = 0; i < a->n_v_to_l; i++) v2l0[i] = (i32)(a->v_to_l[i] - 1);
             build_landmark_index(c, v2l0, N);
         }
-        ov.n = c->n; ov.m = c->m; ov.Xr = c->Xr.p; ov.vw = c->vw.p; ov.v2l = c->v2l.p;
-        ov.lweight = c->s_vw.p; ov.src = c->src.p; ov.dst = c->dst.p; ov.h_w = c->h_w.empty() ? nullptr : c->h_w.data();
+        ov = resident_orig_view(c, c->s_vw.p);
         std::vector<i32> lcomm0(N);
         for (i64 i = 0; i < N; i++) lcomm0[i] = (i32)(a->comm[i] - 1);
-        double hi = resident_diameter_lm(c, c->s_emb.p, c->s_vw.p, lcomm0, C, N, c->has_coll ? c->coll.rank : 0,
-                                         c->has_coll ? c->coll.world : 1);
-        hi = allreduce_scalar_max(c, hi);
-        ov.hi = hi;
-        c->stat_last_hi = hi;
+        ov.hi = landmark_diameter(c, c->s_emb.p, c->s_vw.p, lcomm0, C, N);
     } else {
         // exact mode: make the score graph the resident graph so the sampler can reject its edges
         int rc = cge_set_graph(c, a->edges_src, a->edges_dst, a->eweights, a->m, N);
@@ -1264,19 +1281,22 @@ static void score_one(cge_ctx *c, const cge_score_args *a, double out[7], int *o
     OrigView ov;
     std::vector<i32> lcomm_host;
     const bool landmarks = a->land != -1;
-    if (c->samp_pending.on) { // (a score that failed between the two halves of its draw)
-        HIP_CHECK(hipStreamSynchronize(st));
-        c->samp_pending.on = false;
-    }
     // The local score's samples depend on the resident graph and the seed only: their draw and the first round of the rejection are
     // enqueued early -- behind the first synchronisation of the landmark phase, whose host-side set-up then leaves the device idle
-    // for a few hundred microseconds; the verdict is looked at where the samples used to be drawn (a star graph's early return or
-    // an error in between leaves the draw pending: see above)
+    // for a few hundred microseconds; the verdict is looked at where the samples used to be drawn
     const bool samples_early = landmarks && !reuse_samples && samples_can_start_early(c, a->seed, false);
-    // (the hook captures this call's arguments: whatever happens, it does not outlive the call)
+    // Whatever happens, neither the hook (it captures this call's arguments) nor its draw outlives the call: a star graph's early
+    // return or an error in between leaves the draw pending, and it is drained here (a score that got through has looked at its
+    // draw: no synchronisation then)
     struct HookGuard {
         cge_ctx *c;
-        ~HookGuard() { c->after_unique = nullptr; }
+        ~HookGuard() {
+            c->after_unique = nullptr;
+            if (c->samp_pending.on) {
+                (void)hipStreamSynchronize(c->stream);
+                c->samp_pending.on = false;
+            }
+        }
     } hook_guard{c};
     c->after_unique = nullptr;
     if (samples_early)
@@ -1287,16 +1307,6 @@ static void score_one(cge_ctx *c, const cge_score_args *a, double out[7], int *o
     DevBuf<double> &zeros = c->sw_zeros;
     double t0;
     DevBuf<i32> &star = c->s_star;
-    auto star_exit = [&](i64 Nv) -> bool { // star-graph guard of wGCL_directed (src/divergence.jl:321-334)
-        std::vector<i32> hstar(Nv);
-        HIP_CHECK(hipMemcpyAsync(hstar.data(), star.p, sizeof(i32) * Nv, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (!is_star(hstar, Nv)) return false;
-        out[0] = -1.0;
-        for (int k = 1; k < 6; k++) out[k] = 0.0;
-        *out_len = 6;
-        return true;
-    };
     if (landmarks) {
         landmarks_run_impl(c, a->clusters_flat, a->clusters_off, a->n_clusters, a->land, a->forced, a->method, directed,
                            directed != 0 || c->opt_landmark_edges != 0);
@@ -1319,26 +1329,17 @@ static void score_one(cge_ctx *c, const cge_score_args *a, double out[7], int *o
                 k_degrees_unpack(c, X.p, N, c->s_degout.p, c->s_degin.p, star.p);
             } else
                 k_wedge_degrees(c, c->wedges.p, N, c->s_degout.p, c->s_degin.p, star.p);
-            if (star_exit(N)) return;
+            if (star_return(c, star.p, N, out, out_len)) return;
             G.deg_in = c->s_degin.p;
             G.deg_out = c->s_degout.p;
         }
         t0 = now_ms();
-        ov.n = c->n; ov.m = c->m; ov.Xr = c->Xr.p; ov.vw = c->vw.p; ov.v2l = c->v2l.p; ov.lweight = c->lweight.p;
-        ov.src = c->src.p; ov.dst = c->dst.p; ov.h_w = c->h_w.empty() ? nullptr : c->h_w.data();
-        double hi = 0.0;
+        ov = resident_orig_view(c, c->lweight.p);
         lcomm_host.resize(N); // community of a landmark = community of any member (landmarks never span two): :427
-        {
-            std::vector<i32> &lcomm0 = lcomm_host;
-            HIP_CHECK(hipMemcpyAsync(lcomm0.data(), c->lcomm.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            hi = resident_diameter_lm(c, c->lemb.p, c->lweight.p, lcomm0, C, N, c->has_coll ? c->coll.rank : 0,
-                                      c->has_coll ? c->coll.world : 1);
-            hi = allreduce_scalar_max(c, hi);
-        }
+        HIP_CHECK(hipMemcpyAsync(lcomm_host.data(), c->lcomm.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        ov.hi = landmark_diameter(c, c->lemb.p, c->lweight.p, lcomm_host, C, N);
         ov.h_lcomm = lcomm_host.data(); // (the sweep groups the landmarks by community: no second read-back)
-        ov.hi = hi;
-        c->stat_last_hi = hi;
         c->phases.ms["diameter"] = now_ms() - t0; // what the main thread still waited for
     } else {
         if (c->edges_sharded)
@@ -1354,15 +1355,8 @@ static void score_one(cge_ctx *c, const cge_score_args *a, double out[7], int *o
         G.N = N; G.d = d; G.C = C;
         G.emb = c->Xr.p; G.dist = zeros.p; G.vw = c->vw.p; G.comm = c->comm.p; G.vectC = c->vectC.p;
         if (directed) {
-            c->s_degin.ensure(N);
-            c->s_degout.ensure(N);
-            star.ensure(N);
-            HIP_CHECK(hipMemsetAsync(c->s_degin.p, 0, sizeof(double) * N, st));
-            HIP_CHECK(hipMemsetAsync(c->s_degout.p, 0, sizeof(double) * N, st));
-            HIP_CHECK(hipMemsetAsync(star.p, 0, sizeof(i32) * N, st));
-            k_edge_degrees(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, c->m, c->s_degout.p, c->s_degin.p,
-                           star.p);
-            if (star_exit(N)) return;
+            edge_degrees(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, c->m, N, star);
+            if (star_return(c, star.p, N, out, out_len)) return;
             G.deg_in = c->s_degin.p;
             G.deg_out = c->s_degout.p;
         }
@@ -1488,13 +1482,8 @@ int cge_score_batch(cge_ctx *c, const cge_score_args *a, const cge_embedding_bat
         c->err = e.what();
         rc = CGE_E_ARG;
     }
-    // on every exit: no sample draw left pending, no hand-off slot taken for armed, no hook left behind
-    c->after_unique = nullptr;
+    // on every exit: no hand-off slot taken for armed (score_one leaves no hook and no pending sample draw behind)
     c->flow_armed_words = 0;
-    if (c->samp_pending.on) {
-        (void)hipStreamSynchronize(c->stream);
-        c->samp_pending.on = false;
-    }
     if (rc != CGE_OK) {
         (void)hipStreamSynchronize(c->stream);
         for (i64 k = 0; k < b->K; k++) out_len[k] = 0;

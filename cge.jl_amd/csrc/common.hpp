@@ -614,6 +614,12 @@ void k_rss_rounds(cge_ctx *c, const double *Xr, const double *vw, const i32 *sro
 #define CGE_RR_MAXROUNDS 63
 #define CGE_CHUNK_ROWS 1024 // rows per chunk of a batch (build_batch); the rounds kernel uses r >> 10
 #define CGE_PARTIAL_BLOCKS 64 // block partials of the JS / AUC reductions (summed in block order)
+// The scalars of one alpha as the device leaves them and the host reads them from a pinned slot (host_wgcl_sweep, and per member
+// host_batch_sweep): the AUC block tallies (two per block), the shared verdict right behind them (one all-reduce(sum) covers
+// both; the slot after it only keeps RES_JS 16-byte aligned), the JS block sums of two modes, the fit's flags.  RES_LEN doubles
+// are copied out; an alpha's scalars are RES_STRIDE doubles apart.
+constexpr i64 RES_AUC = 0, RES_VERD = 2 * CGE_PARTIAL_BLOCKS, RES_JS = RES_VERD + 2, RES_FIT = RES_JS + 2 * CGE_PARTIAL_BLOCKS,
+              RES_LEN = RES_FIT + 2, RES_STRIDE = RES_FIT + 16;
 #define CGE_PREFIX_STRIDE 8 // the sorted-order WSSE prefix is stored every 8th row of a chunk (CGE_CHUNK_ROWS % 8 == 0)
 void k_gather_means(cge_ctx *c, const double *arena, const i64 *off, i64 T, i64 d, double *mean);
 void k_gather_rows(cge_ctx *c, const i32 *arena, const i32 *task_off, const i32 *task_row_off, const i32 *chunk_task,
@@ -911,6 +917,26 @@ struct SweepHandoff {
     std::vector<std::unique_ptr<DevSamples>> dsets;
     std::vector<cge_fit_fused> h_epi;
     const double *w = nullptr; // the fit's targets (inside `vw`)
+};
+// The alpha bookkeeping of one sweep, the reference's (src/divergence.jl:35-38, :213-223, :242-253, :256): the patience counters,
+// the skip flags and the best values.  host_wgcl_sweep keeps one, host_batch_sweep one per member (wgcl_host.cpp).
+struct AlphaBook {
+    static constexpr double delta = 0.001, AlphaMax = 10.0, AlphaStep = 0.25; // :35-37 / :288-290
+    static constexpr i64 n_alpha = (i64)((AlphaMax + delta) / AlphaStep + 1e-9); // alpha = ia AlphaStep, ia = 1 .. n_alpha
+    int div_counter = 5, auc_counter = 5; // :38
+    bool skip_div = false, skip_auc = false;
+    double best_div, best_div_ext, best_div_int, best_auc_err, best_auc, best_alpha = -1.0, best_alpha_auc = -1.0;
+    i64 S;             // samples of the local score (its error bar, :217)
+    int split;         // --split-global: the divergence is the mean of the internal and external ones
+    cge_trace *trace;  // optional; emptied by the constructor, one entry per alpha taken (at most 64)
+    AlphaBook(i64 S_, int split_, cge_trace *trace_);
+    // the sweep may end at this alpha (both counters at their last value, or done): the next alpha is not enqueued ahead
+    bool may_end_here() const { return (skip_div || div_counter == 1) && (skip_auc || auc_counter == 1); }
+    bool ended() const { return skip_div && skip_auc; } // :253
+    // one alpha's scalars (laid out RES_*, fitted in `iters` iterations): the block partials added in block order, then the AUC's
+    // counter and best values, the divergence's, the trace
+    void take(const double *res, double alpha, i64 iters);
+    void write(double out[7], int *out_len) const; // the reference's 7-vector (:256)
 };
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
                      const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],

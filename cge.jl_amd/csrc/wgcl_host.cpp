@@ -97,39 +97,30 @@ static void sampled_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi
     }
 }
 
-void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
-                     const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],
-                     int *out_len, cge_trace *trace, SweepHandoff *defer) {
-    const double delta = 0.001, AlphaMax = 10.0, AlphaStep = 0.25; // :35-37 / :288-290
-    ScoreGraph G = G_in; // the per-vertex arrays may be replaced by community-sorted copies (below)
+// ---- the set-up of a sweep -------------------------------------------------------------------------
+
+// How a sweep lays its score graph out: the community -> members CSR, whether the graph is relabelled by community (the sweep's
+// numbering) and whether the rest of an alpha's chain rides on the fit's launch (vect_B by tiles or not: c->bvec_blocks).
+struct SweepLayout {
+    std::vector<i32> cm_off, cm_mem; // community -> members, in the sweep's numbering
+    bool relabel = false, fuse = false;
+    i64 bt_total = 0;    // tile partials in all
+    DevBuf<i32> old2new; // (relabel) a vertex's number in the sweep
+};
+
+// The layout decision, the tile tables and the relabelled copies of the score graph's per-vertex arrays (G points at them then).
+static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay) {
     const i64 N = G.N, C = G.C, d = G.d;
-    hipStream_t st = c->stream;
-    const i64 vlen = directed ? C * C : packed_len(C);
-    if ((double)N * (double)N * 8.0 * 2.2 > 200e9) CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit", (long long)N);
-
-    DevBuf<double> &D = c->sw_D, &GD = c->sw_GD, &T1 = c->sw_T1, &T2 = c->sw_T2, &S1 = c->sw_S1, &S2 = c->sw_S2,
-                   &rowbins = c->sw_rowbins, &vectB = c->sw_vectB, &scal = c->sw_scal, &lohi = c->sw_lohi,
-                   &fitstate = c->sw_fitstate;
-    DevBuf<int> &flags = c->sw_flags; // [0]=done, [1]=iters
-    D.ensure((size_t)N * N);
-    GD.ensure((size_t)N * N);
-    T1.ensure(N); T2.ensure(N); S1.ensure(N); S2.ensure(N);
-    rowbins.ensure((size_t)N * C);
-    vectB.ensure(vlen);
-    scal.ensure(4 * CGE_PARTIAL_BLOCKS + 18); // per alpha: AUC block tallies (+ the shared verdict), JS block sums (two modes), the fit's verdict
-    lohi.ensure(2);
-    fitstate.ensure(4);
-    flags.ensure(4);
-    c->sw_fring.ensure(4);
-
+    std::vector<i32> &cm_off = lay.cm_off, &cm_mem = lay.cm_mem;
     // community -> members CSR of the score graph
     std::vector<i32> hcomm(N);
     if (orig && orig->h_lcomm) std::memcpy(hcomm.data(), orig->h_lcomm, sizeof(i32) * N); // (the caller read them back for the diameter)
     else {
-        HIP_CHECK(hipMemcpyAsync(hcomm.data(), G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipMemcpyAsync(hcomm.data(), G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    std::vector<i32> cm_off(C + 1, 0), cm_mem(N);
+    cm_off.assign(C + 1, 0);
+    cm_mem.resize(N);
     for (i64 i = 0; i < N; i++) {
         if (hcomm[i] < 0 || hcomm[i] >= C) CGE_THROW(CGE_E_ARG, "community id out of range");
         cm_off[hcomm[i] + 1]++;
@@ -144,7 +135,6 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     // vect_B then reads its members as contiguous runs of a row -- with the vertex ids of a real graph (no relation to
     // the communities) it was a 8-byte gather per element, 93 ms per alpha at n = 60 000 against 3 ms for the stream.
     // Only what is indexed by vertex moves: embedding rows, weights / degrees, communities, the sampled pairs.
-    DevBuf<i32> d_old2new;
     // (also the landmark graph of a landmark-mode score with more than 8192 landmarks -- config 5 has 12 000; the local
     // score then reads T through the landmark ids of the original numbering, see the un-permuted copy in the sweep)
     // Option bvec_blocks = 1: an exact-mode sweep is relabelled from 256 vertices on and vect_B is summed BY TILES (kernels_fit.hip:
@@ -171,7 +161,6 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     // copy from pageable memory (~20 us of idle stream) per table and a synchronisation wherever a table is a local
     WordPacker pk(c);
     std::vector<i32> bt_fc, bt_ns, bt_base;
-    i64 bt_total = 0; // tile partials in all
     if (blocks) { // per 64-vertex block of the relabelled graph: first community and number of communities; per tile: its partials
         const i64 Nt = (N + 63) / 64;
         std::vector<i32> comm_new(N);
@@ -198,7 +187,7 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
                 if (directed || J >= I) tot += (i64)bt_ns[I] * bt_ns[J];
                 if (tot > (i64)1 << 30) blocks_ok = false;
             }
-        bt_total = tot;
+        lay.bt_total = tot;
         if (blocks_ok) {
             c->sw_bt_fc.ensure(Nt); c->sw_bt_ns.ensure(Nt); c->sw_bt_base.ensure(Nt * Nt + 1); c->sw_bt_part.ensure(std::max<i64>(tot, 1) + 1); // (+ the +0.0 slot of k_bins_prepare)
             pk.add(c->sw_bt_fc.p, bt_fc.data(), Nt);
@@ -206,100 +195,97 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
             pk.add(c->sw_bt_base.p, bt_base.data(), Nt * Nt);
         }
     }
-    bool fuse = fuse_req && blocks_ok && pieces_ok;
+    lay.fuse = fuse_req && blocks_ok && pieces_ok;
     if (!blocks_req && !tiles_req) blocks_ok = false;
-    const bool relabel = (N > 8192 && c->opt_exact_relabel) || blocks_ok;
+    lay.relabel = (N > 8192 && c->opt_exact_relabel) || blocks_ok;
     c->bvec_blocks = blocks_ok;
-    c->bvec_contig = relabel && N >= 64 * C; // a wave per (row, community) pays off for communities of a wave's width or more
-    if (relabel) {
-        DevBuf<i32> &d_order = c->sw_rl_order;
-        d_order.ensure(N);
-        d_old2new.ensure(N);
-        std::vector<i32> old2new(N);
-        for (i64 q = 0; q < N; q++) old2new[cm_mem[q]] = (i32)q;
-        pk.add(d_order.p, cm_mem.data(), N);
-        pk.add(d_old2new.p, old2new.data(), N);
-        pk.flush(); // (with the tile tables above)
-        c->sw_rl_emb.ensure((size_t)N * d);
-        c->sw_rl_vec.ensure((size_t)4 * N);
-        c->sw_rl_comm.ensure(N);
-        k_permute_rows(c, G.emb, d_order.p, N, d, c->sw_rl_emb.p);
-        G.emb = c->sw_rl_emb.p;
-        double *v = c->sw_rl_vec.p;
-        if (G.dist) { k_permute_rows(c, G.dist, d_order.p, N, 1, v); G.dist = v; }
-        if (G.vw) { k_permute_rows(c, G.vw, d_order.p, N, 1, v + N); G.vw = v + N; }
-        if (G.deg_in) { k_permute_rows(c, G.deg_in, d_order.p, N, 1, v + 2 * N); G.deg_in = v + 2 * N; }
-        if (G.deg_out) { k_permute_rows(c, G.deg_out, d_order.p, N, 1, v + 3 * N); G.deg_out = v + 3 * N; }
-        k_permute_i32(c, G.comm, d_order.p, N, c->sw_rl_comm.p);
-        G.comm = c->sw_rl_comm.p;
-        for (i64 q = 0; q < N; q++) cm_mem[q] = (i32)q; // the member lists in the new numbering (the old ones sit in the staging buffer)
-    }
+    c->bvec_contig = lay.relabel && N >= 64 * C; // a wave per (row, community) pays off for communities of a wave's width or more
+    if (!lay.relabel) return;
+    DevBuf<i32> &d_order = c->sw_rl_order;
+    d_order.ensure(N);
+    lay.old2new.ensure(N);
+    std::vector<i32> old2new(N);
+    for (i64 q = 0; q < N; q++) old2new[cm_mem[q]] = (i32)q;
+    pk.add(d_order.p, cm_mem.data(), N);
+    pk.add(lay.old2new.p, old2new.data(), N);
+    pk.flush(); // (with the tile tables above)
+    c->sw_rl_emb.ensure((size_t)N * d);
+    c->sw_rl_vec.ensure((size_t)4 * N);
+    c->sw_rl_comm.ensure(N);
+    k_permute_rows(c, G.emb, d_order.p, N, d, c->sw_rl_emb.p);
+    G.emb = c->sw_rl_emb.p;
+    double *v = c->sw_rl_vec.p;
+    if (G.dist) { k_permute_rows(c, G.dist, d_order.p, N, 1, v); G.dist = v; }
+    if (G.vw) { k_permute_rows(c, G.vw, d_order.p, N, 1, v + N); G.vw = v + N; }
+    if (G.deg_in) { k_permute_rows(c, G.deg_in, d_order.p, N, 1, v + 2 * N); G.deg_in = v + 2 * N; }
+    if (G.deg_out) { k_permute_rows(c, G.deg_out, d_order.p, N, 1, v + 3 * N); G.deg_out = v + 3 * N; }
+    k_permute_i32(c, G.comm, d_order.p, N, c->sw_rl_comm.p);
+    G.comm = c->sw_rl_comm.p;
+    for (i64 q = 0; q < N; q++) cm_mem[q] = (i32)q; // the member lists in the new numbering (the old ones sit in the staging buffer)
+}
 
-    // D and its normalisation (:79-93 / :359-375)
-    k_dist_matrix(c, G.emb, G.dist, N, d, D.p);
-    k_minmax_upper(c, D.p, N, lohi.p);
-    k_normalise(c, D.p, N, lohi.p);
-    DevBuf<i32> &d_cm_off = c->sw_cm_off, &d_cm_mem = c->sw_cm_mem;
-    d_cm_off.ensure(C + 1);
-    d_cm_mem.ensure(N);
-    pk.add(d_cm_off.p, cm_off.data(), C + 1);
-    pk.add(d_cm_mem.p, cm_mem.data(), N);
+// D and its normalisation (:79-93 / :359-375), the community tables on the device, the starting T (:118) / Tin, Tout
+// (:399-402), and TT, the three parts T rotates through in an undirected sweep.  Returns TT's leading dimension.
+static i64 prepare_distances(cge_ctx *c, const ScoreGraph &G, const SweepLayout &lay, int directed) {
+    const i64 N = G.N, C = G.C;
+    hipStream_t st = c->stream;
+    double *D = c->sw_D.p, *T1 = c->sw_T1.p, *T2 = c->sw_T2.p;
+    k_dist_matrix(c, G.emb, G.dist, N, G.d, D);
+    k_minmax_upper(c, D, N, c->sw_lohi.p);
+    k_normalise(c, D, N, c->sw_lohi.p);
+    WordPacker pk(c);
+    c->sw_cm_off.ensure(C + 1);
+    c->sw_cm_mem.ensure(N);
+    pk.add(c->sw_cm_off.p, lay.cm_off.data(), C + 1);
+    pk.add(c->sw_cm_mem.p, lay.cm_mem.data(), N);
     std::vector<i32> cm_pos(N); // position of every vertex in the community-sorted list
-    for (i64 q = 0; q < N; q++) cm_pos[cm_mem[q]] = (i32)q;
+    for (i64 q = 0; q < N; q++) cm_pos[lay.cm_mem[q]] = (i32)q;
     c->sw_cm_pos.ensure(N);
     pk.add(c->sw_cm_pos.p, cm_pos.data(), N);
+    const std::vector<double> ones(N, 1.0); // T (:118)
     if (!directed) { // (the directed sweep reads the degrees back first, below)
-        std::vector<double> ones(N, 1.0); // T (:118)
-        pk.add(T1.p, ones.data(), N);
-        pk.add(T2.p, ones.data(), N);
-        pk.flush();
-    } else
-        pk.flush();
-    if (c->bvec_blocks && !directed) k_bins_prepare(c, d_cm_off.p, N, C, bt_total); // where every bin's tile partials sit
-
-    // T (:118) / Tin,Tout (:399-402)
-    std::vector<double> hT1(N, 1.0), hT2(N, 1.0);
-    if (directed) {
-        std::vector<double> din(N), dout(N);
+        pk.add(T1, ones.data(), N);
+        pk.add(T2, ones.data(), N);
+    }
+    pk.flush();
+    if (c->bvec_blocks && !directed) k_bins_prepare(c, c->sw_cm_off.p, N, C, lay.bt_total); // where every bin's tile partials sit
+    if (directed) { // Tin / Tout: zero where the in- / out-degree is
+        std::vector<double> din(N), dout(N), hTin(N, 1.0), hTout(N, 1.0);
         HIP_CHECK(hipMemcpyAsync(din.data(), G.deg_in, sizeof(double) * N, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(dout.data(), G.deg_out, sizeof(double) * N, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         for (i64 i = 0; i < N; i++) {
-            if (din[i] == 0) hT1[i] = 0.0;  // Tin
-            if (dout[i] == 0) hT2[i] = 0.0; // Tout
+            if (din[i] == 0) hTin[i] = 0.0;
+            if (dout[i] == 0) hTout[i] = 0.0;
         }
-    }
-    if (directed) {
-        pk.add(T1.p, hT1.data(), N);
-        pk.add(T2.p, hT2.data(), N);
+        pk.add(T1, hTin.data(), N);
+        pk.add(T2, hTout.data(), N);
         pk.flush();
     }
-    const double *Tin = T1.p, *Tout = T2.p; // directed
-    // undirected: T rotates through the three parts of TT (Tld doubles each, zero beyond N); Tcur = the current iterate.
-    // Three, so that T_0 of an alpha survives the fit of the next alpha, which may be enqueued before this one is checked.
+    // undirected: T rotates through the three parts of TT (Tld doubles each, zero beyond N).  Three, so that T_0 of an alpha
+    // survives the fit of the next alpha, which may be enqueued before this one is checked.
     DevBuf<double> &TT = c->fp_T;
     const i64 Tld = (N + 63) / 64 * 64;
-    int tpar = 0;
     TT.ensure((size_t)3 * Tld);
     c->fp_Tsave.ensure(N);
     HIP_CHECK(hipMemsetAsync(TT.p, 0, sizeof(double) * 3 * Tld, st));
-    HIP_CHECK(hipMemcpyAsync(TT.p, T1.p, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
-    double *Tcur = TT.p;
-    // sample tallies split over the ranks: with the in-library communicator (stream-ordered, no host synchronisation in the
-    // enqueued chain) from 10^5 samples on; option "shard_samples" = 2 forces it (tests, also through the hook), 0 disables
-    const bool shard_samples = c->has_coll && smp.S >= c->coll.world &&
-                               (c->opt_shard_samples == 2 || (c->opt_shard_samples == 1 && c->rccl_comm && smp.S >= 100000));
-    fit_sweep_begin(c);
-    bool use_persistent = !directed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
-                          (c->opt_fit_persistent >= 2 || N >= 128);
-    bool use_persistent_dir = directed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
-                              (c->opt_fit_persistent >= 2 || N >= 128);
-    // one launch (pair) per iteration, when the register-resident form does not apply: over the upper tiles only
-    // (kernels_fitp.hip: k_fit_sym_step)
-    c->stat_fit_persistent = 0;
-    c->stat_fit_iters = 0;
+    HIP_CHECK(hipMemcpyAsync(TT.p, T1, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+    return Tld;
+}
 
-    // ---- samples -> device ---------------------------------------------------------------------
+// full_graph_D of a set's sampled pairs, normalised by hi (lo == 0) :104-114
+static void pair_distances(cge_ctx *c, const OrigView &orig, i64 d, i64 S, DevSamples &ds) {
+    ds.dpos.ensure(S); ds.dneg.ensure(S);
+    sampled_pair_dist(c, orig.Xr, d, ds.pi.p, ds.pj.p, S, orig.hi, ds.dpos.p);
+    sampled_pair_dist(c, orig.Xr, d, ds.ni.p, ds.nj.p, S, orig.hi, ds.dneg.p);
+}
+
+// The samples to the device (c->dsets, one DevSamples per set): the sampled edges of the graph the local score samples from,
+// their weights and, in landmark mode, full_graph_D of the sampled pairs.  `remap` (a relabelled exact-mode sweep): the pairs
+// go into the sweep's numbering.
+static void samples_to_device(cge_ctx *c, const SampleSet &smp, i64 N, i64 d, const OrigView *orig, const i32 *ex_src,
+                              const i32 *ex_dst, const double *ex_hw, i64 ex_m, int directed, const i32 *remap) {
+    hipStream_t st = c->stream;
     const bool landmarks = orig != nullptr;
     const i64 S = smp.S;
     const i32 *e_src = landmarks ? orig->src : ex_src, *e_dst = landmarks ? orig->dst : ex_dst;
@@ -315,16 +301,12 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
             const i32 *pos_pairs = (directed && !landmarks && smp.d_pos2.p) ? smp.d_pos2.p + t * S : pos; // the overwriting draw (:510)
             k_prep_samples(c, pos, pos_pairs, smp.d_ni.p + t * S, smp.d_nj.p + t * S, e_src, e_dst, c->w.p, S, directed, ds.pi.p,
                            ds.pj.p, ds.ni.p, ds.nj.p, ds.wts.p);
-            if (landmarks) { // full_graph_D of the sampled pairs, normalised by hi (lo == 0) :104-114
-                ds.dpos.ensure(S); ds.dneg.ensure(S);
-                sampled_pair_dist(c, orig->Xr, d, ds.pi.p, ds.pj.p, S, orig->hi, ds.dpos.p);
-                sampled_pair_dist(c, orig->Xr, d, ds.ni.p, ds.nj.p, S, orig->hi, ds.dneg.p);
-            }
+            if (landmarks) pair_distances(c, *orig, d, S, ds);
         }
     } else {
         DevBuf<i32> d_idx, d_tmp;
         std::vector<i64> rows0(S);
-        std::vector<i32> hs, hd, hs2, hd2;
+        std::vector<i32> hs, hd;
         for (i64 t = 0; t < smp.n_sets; t++) {
             DevSamples &ds = *dsets[t];
             for (i64 k = 0; k < S; k++) {
@@ -357,399 +339,479 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
             HIP_CHECK(hipMemcpyAsync(ds.ni.p, ni.data(), sizeof(i32) * S, hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(ds.nj.p, nj.data(), sizeof(i32) * S, hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(ds.wts.p, wts.data(), sizeof(double) * S, hipMemcpyHostToDevice, st));
-            if (landmarks) { // full_graph_D of the sampled pairs, normalised by hi (lo == 0) :104-114
-                ds.dpos.ensure(S); ds.dneg.ensure(S);
-                sampled_pair_dist(c, orig->Xr, d, ds.pi.p, ds.pj.p, S, orig->hi, ds.dpos.p);
-                sampled_pair_dist(c, orig->Xr, d, ds.ni.p, ds.nj.p, S, orig->hi, ds.dneg.p);
-            }
+            if (landmarks) pair_distances(c, *orig, d, S, ds);
             HIP_CHECK(hipStreamSynchronize(st)); // host vectors go out of scope
         }
     }
-
-    if (relabel && !landmarks) // the sampled pairs index the score graph: into the new numbering (GD is a full symmetric matrix here)
+    if (remap) // the sampled pairs index the score graph: into the new numbering (GD is a full symmetric matrix here)
         for (i64 t = 0; t < smp.n_sets; t++) {
             DevSamples &ds = *dsets[t];
-            k_remap_i32(c, ds.pi.p, d_old2new.p, S);
-            k_remap_i32(c, ds.pj.p, d_old2new.p, S);
-            k_remap_i32(c, ds.ni.p, d_old2new.p, S);
-            k_remap_i32(c, ds.nj.p, d_old2new.p, S);
+            k_remap_i32(c, ds.pi.p, remap, S);
+            k_remap_i32(c, ds.pj.p, remap, S);
+            k_remap_i32(c, ds.ni.p, remap, S);
+            k_remap_i32(c, ds.nj.p, remap, S);
         }
+}
 
-    // ---- the fused chain's table, one per sample set (device copies: the fit's epilogue loads them after its loop) ----------
-    constexpr i64 RES_AUC_EARLY = 0; // == RES_AUC below
-    const i64 fz_s0 = shard_samples ? S * c->coll.rank / c->coll.world : 0;
-    const i64 fz_s1 = shard_samples ? S * (c->coll.rank + 1) / c->coll.world : S;
-    const bool fuse_auc = landmarks && fz_s1 - fz_s0 < 65536 && fz_s1 > fz_s0; // (beyond: auc_landmark_kernel's wide form, as its own launch)
-    std::vector<cge_fit_fused> h_epi;
-    if (fuse) {
-        h_epi.resize(smp.n_sets);
-        for (i64 t = 0; t < smp.n_sets; t++) {
-            const DevSamples &ds = *dsets[t];
-            cge_fit_fused &e = h_epi[t];
-            e = cge_fit_fused{};
-            e.comm = G.comm; e.fc = c->sw_bt_fc.p; e.ns = c->sw_bt_ns.p; e.base = c->sw_bt_base.p; e.partial = c->sw_bt_part.p;
-            e.S = fz_s1 - fz_s0;
-            e.dpos = ds.dpos.p + fz_s0; e.dneg = ds.dneg.p + fz_s0; e.wts = ds.wts.p + fz_s0;
-            if (fuse_auc && e.S > 0) { // everything of the tally that depends neither on alpha nor on T, once
-                DevSamples &dsw = *dsets[t];
-                dsw.aidx.ensure((size_t)4 * e.S); dsw.afac.ensure((size_t)8 * e.S + CGE_PARTIAL_BLOCKS);
-                c->sw_fused_pw.ensure((size_t)2 * e.S);
-                k_auc_prepare(c, orig->v2l, d_old2new.p, orig->vw, orig->lweight, ds.pi.p + fz_s0, ds.pj.p + fz_s0, ds.ni.p + fz_s0,
-                              ds.nj.p + fz_s0, e.wts, e.S, dsw.aidx.p, dsw.afac.p, dsw.afac.p + 8 * e.S);
-                e.aidx = dsw.aidx.p; e.afac = dsw.afac.p; e.aden = dsw.afac.p + 8 * e.S; e.apw = c->sw_fused_pw.p;
-            }
-            e.auc_part = scal.p + RES_AUC_EARLY;
+// The fused chain's tables, one per sample set (host copies in h_epi; the device copies, which the fit's epilogue loads after
+// its loop, in c->sw_fused_epi).  The local score tallies the samples [s0, s1) of every set; fuse_auc: on the fit's launch.
+static void fused_tables(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *old2new, i64 n_sets, i64 s0, i64 s1,
+                         bool fuse_auc, std::vector<cge_fit_fused> &h_epi) {
+    h_epi.resize(n_sets);
+    for (i64 t = 0; t < n_sets; t++) {
+        DevSamples &ds = *c->dsets[t];
+        cge_fit_fused &e = h_epi[t];
+        e = cge_fit_fused{};
+        e.comm = G.comm; e.fc = c->sw_bt_fc.p; e.ns = c->sw_bt_ns.p; e.base = c->sw_bt_base.p; e.partial = c->sw_bt_part.p;
+        e.S = s1 - s0;
+        e.dpos = ds.dpos.p + s0; e.dneg = ds.dneg.p + s0; e.wts = ds.wts.p + s0;
+        if (fuse_auc && e.S > 0) { // everything of the tally that depends neither on alpha nor on T, once
+            ds.aidx.ensure((size_t)4 * e.S); ds.afac.ensure((size_t)8 * e.S + CGE_PARTIAL_BLOCKS);
+            c->sw_fused_pw.ensure((size_t)2 * e.S);
+            k_auc_prepare(c, orig->v2l, old2new, orig->vw, orig->lweight, ds.pi.p + s0, ds.pj.p + s0, ds.ni.p + s0,
+                          ds.nj.p + s0, e.wts, e.S, ds.aidx.p, ds.afac.p, ds.afac.p + 8 * e.S);
+            e.aidx = ds.aidx.p; e.afac = ds.afac.p; e.aden = ds.afac.p + 8 * e.S; e.apw = c->sw_fused_pw.p;
         }
-        c->sw_fused_epi.ensure(h_epi.size() * sizeof(cge_fit_fused));
-        static_assert(sizeof(cge_fit_fused) % 8 == 0, "packed as 4-byte words");
-        pk.add(reinterpret_cast<i32 *>(c->sw_fused_epi.p), reinterpret_cast<const i32 *>(h_epi.data()),
-               (i64)(h_epi.size() * sizeof(cge_fit_fused) / 4));
-        pk.flush();
+        e.auc_part = c->sw_scal.p + RES_AUC;
     }
-    c->stat_fit_fused = 0;
+    c->sw_fused_epi.ensure(h_epi.size() * sizeof(cge_fit_fused));
+    static_assert(sizeof(cge_fit_fused) % 8 == 0, "packed as 4-byte words");
+    WordPacker pk(c);
+    pk.add(reinterpret_cast<i32 *>(c->sw_fused_epi.p), reinterpret_cast<const i32 *>(h_epi.data()),
+           (i64)(h_epi.size() * sizeof(cge_fit_fused) / 4));
+    pk.flush();
+}
 
-    // cge_score_batch: a sweep on the fused path is prepared here and run by the batch, beside other members' sweeps
-    // (batch_host.cpp); what its alphas read moves out of the context into the hand-off, everything else stays scratch
-    if (defer) defer->deferred = false;
+// cge_score_batch: a sweep on the fused path is prepared here and run by the batch, beside other members' sweeps
+// (batch_host.cpp); what its alphas read moves out of the context into the hand-off, everything else stays scratch.
+// False: its fit does not share a launch (the sweep runs here).
+static bool hand_off(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, const SampleSet &smp, int split, i64 Tld,
+                     std::vector<cge_fit_fused> &h_epi) {
+    const i64 N = G.N, vlen = packed_len(G.C);
     int fG = 0, fNW = 0;
-    if (defer && fuse && fuse_auc && use_persistent && !shard_samples && !c->has_coll && k_fit_flow_geometry(N, &fG, &fNW) &&
-        fG <= defer->max_G && k_fit_flow_multi_fits(fNW)) {
-        SweepHandoff &h = *defer;
-        k_pow_prepare(c, D.p, N, true, true);
-        h.Lh.swap(c->sw_Lh); h.Ll.swap(c->sw_Ll);
-        c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the hand-off)
-        h.comm.swap(c->sw_rl_comm); h.vw.swap(c->sw_rl_vec);
-        h.bt_fc.swap(c->sw_bt_fc); h.bt_ns.swap(c->sw_bt_ns); h.bt_base.swap(c->sw_bt_base); h.bt_part.swap(c->sw_bt_part);
-        h.cm_off.swap(d_cm_off); h.fused_pw.swap(c->sw_fused_pw);
-        h.dsets.clear();
-        for (i64 t = 0; t < smp.n_sets; t++) {
-            h.dsets.emplace_back(std::move(dsets[t]));
-            dsets[t].reset(new DevSamples());
+    if (!k_fit_flow_geometry(N, &fG, &fNW) || fG > h.max_G || !k_fit_flow_multi_fits(fNW)) return false;
+    hipStream_t st = c->stream;
+    k_pow_prepare(c, c->sw_D.p, N, true, true);
+    h.Lh.swap(c->sw_Lh); h.Ll.swap(c->sw_Ll);
+    c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the hand-off)
+    h.comm.swap(c->sw_rl_comm); h.vw.swap(c->sw_rl_vec);
+    h.bt_fc.swap(c->sw_bt_fc); h.bt_ns.swap(c->sw_bt_ns); h.bt_base.swap(c->sw_bt_base); h.bt_part.swap(c->sw_bt_part);
+    h.cm_off.swap(c->sw_cm_off); h.fused_pw.swap(c->sw_fused_pw);
+    h.dsets.clear();
+    for (i64 t = 0; t < smp.n_sets; t++) {
+        h.dsets.emplace_back(std::move(c->dsets[t]));
+        c->dsets[t].reset(new DevSamples());
+    }
+    h.vectC.ensure(vlen); // (the context's vect_C is landmark state of the member: copied)
+    HIP_CHECK(hipMemcpyAsync(h.vectC.p, G.vectC, sizeof(double) * vlen, hipMemcpyDeviceToDevice, st));
+    h.T.ensure((size_t)3 * Tld); // T rotates through three parts (as TT); T_0 = ones
+    HIP_CHECK(hipMemcpyAsync(h.T.p, c->fp_T.p, sizeof(double) * 3 * Tld, hipMemcpyDeviceToDevice, st));
+    h.N = N; h.C = G.C; h.S = smp.S; h.n_sets = smp.n_sets; h.Tld = Tld; h.split = split;
+    h.G = fG; h.NW = fNW;
+    h.h_epi = std::move(h_epi);
+    h.w = G.vw;
+    h.deferred = true;
+    HIP_CHECK(hipStreamSynchronize(st)); // (the staging packer's host memory)
+    return true;
+}
+
+// ---- one alpha -------------------------------------------------------------------------------------
+
+// What the host keeps of an alpha in flight until it collects it (two at most: slot = alpha index mod 2)
+struct AlphaSlot {
+    bool fit_async = false;      // the fit was only enqueued: its verdict arrives with the alpha's scalars
+    bool fused = false;          // the rest of the chain rode on the fit's launch
+    bool shared_verdict = false; // N > 1, tallies split: the verdict of the fit travelled with the all-reduced tallies
+    int t0_par = 0;              // the part of TT that held T_0 of this alpha
+    i64 iters = 0;
+};
+
+// The form of the fit from alpha to alpha (a persistent form, once given up, stays given up for the sweep), the part of TT that
+// holds the current iterate (undirected) and the last iteration count (the first batch of a launch-per-iteration fit)
+struct FitForm {
+    bool persistent = false, persistent_dir = false;
+    int tpar = 0;
+    i64 prev_iters = 16;
+};
+
+// One launch (pair) per iteration: `launch(k)` enqueues iteration k, in batches -- the first as long as the previous fit, at
+// most 32 from then on.  After each batch the host reads the fit's flags ([0] done, [1] iterations) and, when `ring` is given,
+// the changes of the undirected fit's last iterations.  Returns the iterations.
+template <class Launch>
+static i64 fit_by_launches(cge_ctx *c, i64 prev_iters, double alpha, const int *flags, const unsigned long long *ring,
+                           Launch launch) {
+    hipStream_t st = c->stream;
+    i64 batch = std::max<i64>(4, std::min<i64>(prev_iters, 128));
+    for (i64 k = 0;;) {
+        for (i64 b = 0; b < batch; b++, k++) launch(k);
+        int hf[2];
+        unsigned long long hr[3];
+        HIP_CHECK(hipMemcpyAsync(hf, flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+        if (ring) HIP_CHECK(hipMemcpyAsync(hr, ring, sizeof(hr), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        const i64 iters = hf[1];
+        if (hf[0]) return iters;
+        if (ring) {
+            double flast;
+            std::memcpy(&flast, &hr[(k - 1) % 3], sizeof(double));
+            if (!(flast > AlphaBook::delta)) return iters; // the last launch of the batch was the converging iteration (iters == k)
         }
-        h.vectC.ensure(vlen); // (the context's vect_C is landmark state of the member: copied)
-        HIP_CHECK(hipMemcpyAsync(h.vectC.p, G.vectC, sizeof(double) * vlen, hipMemcpyDeviceToDevice, st));
-        h.T.ensure((size_t)3 * Tld); // T rotates through three parts (as TT above); T_0 = ones
-        HIP_CHECK(hipMemcpyAsync(h.T.p, TT.p, sizeof(double) * 3 * Tld, hipMemcpyDeviceToDevice, st));
-        h.N = N; h.C = C; h.S = S; h.n_sets = smp.n_sets; h.Tld = Tld; h.split = split;
-        h.G = fG; h.NW = fNW;
-        h.h_epi = h_epi;
-        h.w = G.vw;
-        h.deferred = true;
-        HIP_CHECK(hipStreamSynchronize(st)); // (the staging packer's host memory)
+        if (iters > c->opt_fit_max_iters) CGE_THROW(CGE_E_ASSERT, "Chung-Lu fit did not converge at alpha=%g (%lld iterations; the reference's `while diff > delta` would not return)", alpha, (long long)iters);
+        batch = std::max<i64>(4, std::min<i64>(batch, 32));
+    }
+}
+
+// The undirected fit of one alpha from T_0 = part fit.tpar of TT.  The persistent form (GD's upper triangle in registers,
+// kernels_fitp.hip) is only enqueued -- with the rest of the alpha's chain riding on it when `ff` is given (ff_dev: its
+// device copy) -- and its verdict is looked at when the alpha is collected; else one launch per iteration (k_fit_sym_step,
+// over the upper tiles only).  `upper`: GD's upper triangle suffices (the power matrix made here when the fused launch does not
+// apply after all).
+static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double alpha, bool upper,
+                           const cge_fit_fused *ff, const cge_fit_fused *ff_dev, FitForm &fit, AlphaSlot &sl) {
+    hipStream_t st = c->stream;
+    double *const GD = c->sw_GD.p, *const TT = c->fp_T.p;
+    int *flags = c->sw_flags.p;
+    if (!fit.persistent) HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
+    sl.t0_par = fit.tpar;
+    if (fit.persistent) {
+        const int tnext = (fit.tpar + 1) % 3;
+        if (k_fit_flow_enqueue(c, ff ? nullptr : GD, N, TT + (i64)fit.tpar * Tld, TT + (i64)tnext * Tld, Tld, w, 0.25,
+                               AlphaBook::delta, (int *)(c->sw_scal.p + RES_FIT), ff, ff_dev)) {
+            sl.fused = ff != nullptr;
+            sl.fit_async = true;
+            fit.tpar = tnext;
+            return;
+        }
+        fit.persistent = false; // the register-resident form does not apply to this size: one launch per iteration from here on
+        if (ff) { // (the fused launch was to supply the matrix)
+            k_pow_prepare(c, c->sw_D.p, N, upper);
+            k_pow_matrix(c, c->sw_D.p, N, alpha, GD, upper);
+        }
+        HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
+    }
+    // T alternates between two parts of TT
+    HIP_CHECK(hipMemsetAsync(c->sw_fring.p, 0, sizeof(unsigned long long) * 4, st));
+    double *Tb2[2] = {TT + (i64)fit.tpar * Tld, TT + (i64)((fit.tpar + 1) % 3) * Tld};
+    sl.iters = fit_by_launches(c, fit.prev_iters, alpha, flags, c->sw_fring.p, [&](i64 k) {
+        k_fit_sym_step(c, GD, Tb2[k & 1], Tb2[(k + 1) & 1], w, N, 0.25, AlphaBook::delta, (int)k, c->sw_fring.p, flags, flags + 1);
+    });
+    if (sl.iters & 1) fit.tpar = (fit.tpar + 1) % 3;
+}
+
+// The directed fit of one alpha, Tin / Tout (sw_T1 / sw_T2) updated in place: the whole fit in one launch (kernels_fitp.hip) or
+// one launch pair per iteration.  The default persistent form is only enqueued: the rest of the alpha's chain is queued behind
+// it and its verdict arrives with the alpha's scalars (Tin / Tout are written on success only, so a failed launch is redone
+// from the same iterates with one launch pair per iteration).
+static void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm &fit, AlphaSlot &sl) {
+    hipStream_t st = c->stream;
+    const i64 N = G.N;
+    const double *GD = c->sw_GD.p;
+    double *Tin = c->sw_T1.p, *Tout = c->sw_T2.p;
+    int *flags = c->sw_flags.p;
+    HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
+    const double init[2] = {0.9, 1.0}; // epsilon, diff (:434-435)
+    HIP_CHECK(hipMemcpyAsync(c->sw_fitstate.p, init, sizeof(init), hipMemcpyHostToDevice, st));
+    bool enqueued_only = false;
+    if (fit.persistent_dir && k_fit_persistent_dir(c, GD, N, Tin, Tout, G.deg_in, G.deg_out, 0.9, 1.0, AlphaBook::delta,
+                                                   &sl.iters, (int *)(c->sw_scal.p + RES_FIT), &enqueued_only)) {
+        if (enqueued_only) sl.fit_async = true;
+        else c->stat_fit_persistent++;
         return;
     }
+    if (fit.persistent_dir) { // abandoned: Tin / Tout are untouched; one launch pair per iteration from here on
+        fit.persistent_dir = false;
+        HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
+    }
+    sl.iters = fit_by_launches(c, fit.prev_iters, alpha, flags, nullptr, [&](i64) {
+        k_fit_symv_dir(c, GD, Tin, Tout, N, c->sw_S1.p, c->sw_S2.p, flags);
+        k_fit_update_dir(c, Tin, Tout, c->sw_S1.p, c->sw_S2.p, G.deg_in, G.deg_out, N, AlphaBook::delta, flags, flags + 1,
+                         c->sw_fitstate.p);
+    });
+}
 
-    // ---- alpha sweep ---------------------------------------------------------------------------
-    int alpha_div_counter = 5, alpha_auc_counter = 5; // :38
-    bool skip_div = false, skip_auc = false;
-    double best_div = INFINITY, best_div_ext = INFINITY, best_div_int = INFINITY, best_auc_err = INFINITY,
-           best_auc = INFINITY; // typemax(Float64)
-    double best_alpha = -1.0, best_alpha_auc = -1.0;
-    if (trace) trace->n_alpha = 0;
-    const i64 n_alpha_total = (i64)std::floor((AlphaMax + delta) / AlphaStep + 1e-9);
-    i64 prev_iters = 16;
-    // An alpha is a chain on the stream: pow, the fit, AUC, vect_B, JS, scalars -> pinned host memory, an event.  With the
-    // enqueue-only persistent fit (undirected) nothing in the chain needs the host, so the chain of alpha i+1 is
-    // enqueued before the host waits for alpha i -- unless the sweep may end at alpha i (both patience counters at their
-    // last value), so nothing is ever computed in vain.  T alternates between the two halves of TT; the scalars and the
-    // fit's verdict of an alpha land in slot (alpha index mod 2).
-    struct AlphaSlot {
-        bool fit_async = false, did_auc = false, did_div = false;
-        bool fused = false; // the rest of the chain rode on the fit's launch
-        bool shared_verdict = false; // N > 1, tallies split: the verdict of the fit travelled with the all-reduced tallies
-        int t0_par = 0;  // the half of TT that held T_0 of this alpha
-        i64 iters = 0;
-    } slots[2];
-    // RES_VERD sits right behind the tallies: one all-reduce(sum) covers both (the slot after it only keeps RES_JS 16-byte aligned)
-    static_assert(RES_AUC_EARLY == 0, "");
-    constexpr i64 RES_AUC = 0, RES_VERD = 2 * CGE_PARTIAL_BLOCKS, RES_JS = RES_VERD + 2, RES_FIT = RES_JS + 2 * CGE_PARTIAL_BLOCKS,
-                  RES_LEN = RES_FIT + 2, RES_STRIDE = RES_FIT + 16;
-    c->pin_scal.ensure(2 * RES_STRIDE);
-    // (Round 4 tried the next alpha's power matrix on a side stream beside this alpha's vect_B / JS / AUC: +0.65 ms, the two
-    // cross-queue dependencies per alpha cost more than they hid -- profiles/r04_pow_overlap_ab.txt; removed in round 5, when
-    // the power matrix moved into the fit's prologue anyway.)
-    auto enqueue_alpha = [&](i64 ia, bool want_auc, bool want_div) {
-        AlphaSlot &sl = slots[ia & 1];
-        const int slot = (int)(ia & 1);
-        const double alpha = AlphaStep * (double)ia;
-        sl = AlphaSlot();
-        sl.did_auc = want_auc;
-        sl.did_div = want_div;
-        // the undirected persistent fit and vect_B read the upper triangle only; the exact-mode AUC, the directed vect_B
-        // and the launch-per-iteration fits read whole rows
-        const bool gd_upper = landmarks && !directed;
-        double *const GDc = GD.p; // this alpha's matrix
-        const bool fused_now = fuse && use_persistent && c->pow_logs_blocked_N == N; // (a fallback in mid-sweep ends it: the matrix is needed then)
-        if (fuse && !fused_now && c->pow_logs_N != N) k_pow_prepare(c, D.p, N, landmarks && !directed); // (left the fused path: the row-major logarithm)
-        bool auc_done = false, bvec_partials = false, copied_out = false;
-        if (!fused_now) k_pow_matrix(c, D.p, N, alpha, GDc, gd_upper);
-        if (directed || !use_persistent) HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4, st));
+// The local score's tallies of one alpha (samples [s0, s1) of `ds`: this rank's share) into the block partials of the scalars.
+// Landmark mode reads T through the landmark ids of the original numbering: a relabelled sweep (old2new) un-permutes it first.
+static void local_score_tallies(cge_ctx *c, const double *Ta, const double *Tb, i64 N, int directed, const OrigView *orig,
+                                const i32 *old2new, const DevSamples &ds, i64 s0, i64 s1, double alpha) {
+    double *part = c->sw_scal.p + RES_AUC;
+    if (!orig) {
+        k_auc_exact(c, c->sw_GD.p, Ta, Tb, N, ds.pi.p + s0, ds.pj.p + s0, ds.ni.p + s0, ds.nj.p + s0, ds.wts.p + s0, s1 - s0,
+                    nullptr, part);
+        return;
+    }
+    if (old2new) {
+        c->sw_rl_T.ensure((size_t)2 * N);
+        k_permute_rows(c, Ta, old2new, N, 1, c->sw_rl_T.p);
+        Ta = c->sw_rl_T.p;
         if (directed) {
-            const double init[2] = {0.9, 1.0}; // epsilon, diff (:434-435)
-            HIP_CHECK(hipMemcpyAsync(fitstate.p, init, sizeof(init), hipMemcpyHostToDevice, st));
-        }
-        i64 iters = 0;
-        bool dir_async = false;
-        i64 batch = std::max<i64>(4, std::min<i64>(prev_iters, 128));
-        if (!directed) {
-            bool fitted = false;
-            sl.t0_par = tpar;
-            if (use_persistent) { // the whole fit in one launch, GD's upper triangle in registers (kernels_fitp.hip)
-                const int tnext = (tpar + 1) % 3;
-                cge_fit_fused ff{};
-                const cge_fit_fused *ffp = nullptr, *ffd = nullptr;
-                if (fused_now) {
-                    const i64 set = smp.n_sets == 1 ? 0 : ia - 1;
-                    ff = h_epi[set];
-                    ff.Lh = c->sw_Lh.p; ff.Ll = c->sw_Ll.p; ff.alpha = alpha;
-                    if (!want_div) ff.partial = nullptr;
-                    if (!(want_auc && fuse_auc)) ff.auc_part = nullptr;
-                    ffp = &ff;
-                    ffd = reinterpret_cast<const cge_fit_fused *>(c->sw_fused_epi.p) + set;
-                }
-                if (k_fit_flow_enqueue(c, fused_now ? nullptr : GDc, N, TT.p + (i64)tpar * Tld, TT.p + (i64)tnext * Tld,
-                                                           Tld, G.vw, 0.25, delta, (int *)(scal.p + RES_FIT), ffp, ffd)) {
-                    if (fused_now) {
-                        auc_done = ff.auc_part != nullptr;
-                        bvec_partials = ff.partial != nullptr;
-                        sl.fused = true;
-                    }
-                    sl.fit_async = true; // the verdict is looked at when the alpha is collected
-                    fitted = true;
-                    tpar = tnext;
-                } else { // the register-resident form does not apply to this size: one launch per iteration from here on
-                    use_persistent = false;
-                    if (fused_now) { // (the fused launch was to supply the matrix)
-                        k_pow_prepare(c, D.p, N, landmarks && !directed);
-                        k_pow_matrix(c, D.p, N, alpha, GDc, gd_upper);
-                    }
-                    HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4, st));
-                }
-            }
-            if (!fitted) {
-                // one launch per iteration (kernels_fit.hip: fit_step_kernel); T alternates between the two buffers
-                HIP_CHECK(hipMemsetAsync(c->sw_fring.p, 0, sizeof(unsigned long long) * 4, st));
-                double *Tb2[2] = {TT.p + (i64)tpar * Tld, TT.p + (i64)((tpar + 1) % 3) * Tld};
-                i64 k = 0;
-                for (;;) {
-                    for (i64 b = 0; b < batch; b++, k++)
-                        k_fit_sym_step(c, GDc, Tb2[k & 1], Tb2[(k + 1) & 1], G.vw, N, 0.25, delta, (int)k, c->sw_fring.p, flags.p,
-                                       flags.p + 1);
-                    int hf[2];
-                    unsigned long long hr[3];
-                    HIP_CHECK(hipMemcpyAsync(hf, flags.p, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
-                    HIP_CHECK(hipMemcpyAsync(hr, c->sw_fring.p, sizeof(hr), hipMemcpyDeviceToHost, st));
-                    HIP_CHECK(hipStreamSynchronize(st));
-                    iters = hf[1];
-                    if (hf[0]) break;
-                    double flast;
-                    std::memcpy(&flast, &hr[(k - 1) % 3], sizeof(double));
-                    if (!(flast > delta)) break; // the last launch of the batch was the converging iteration (iters == k)
-                    if (iters > c->opt_fit_max_iters) CGE_THROW(CGE_E_ASSERT, "Chung-Lu fit did not converge at alpha=%g (%lld iterations; the reference's `while diff > delta` would not return)", alpha, (long long)iters);
-                    batch = std::max<i64>(4, std::min<i64>(batch, 32));
-                }
-                if (iters & 1) tpar = (tpar + 1) % 3;
-            }
-            Tcur = TT.p + (i64)tpar * Tld;
-        } else if (use_persistent_dir &&
-                   k_fit_persistent_dir(c, GDc, N, T1.p, T2.p, G.deg_in, G.deg_out, 0.9, 1.0, delta, &iters, (int *)(scal.p + RES_FIT),
-                                        &dir_async)) {
-            // the whole directed fit in one launch (kernels_fitp.hip).  The default form is only enqueued: the rest of the
-            // alpha's chain is queued behind it and its verdict arrives with the alpha's scalars (Tin / Tout are written
-            // on success only, so a failed launch is redone from the same iterates with one launch pair per iteration).
-            if (dir_async) sl.fit_async = true;
-            else c->stat_fit_persistent++;
+            k_permute_rows(c, Tb, old2new, N, 1, c->sw_rl_T.p + N);
+            Tb = c->sw_rl_T.p + N;
         } else
-        for (;;) {
-            if (use_persistent_dir) { // abandoned: T1 / T2 are untouched; one launch pair per iteration from here on
-                use_persistent_dir = false;
-                HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4, st));
-            }
-            for (i64 b = 0; b < batch; b++) {
-                k_fit_symv_dir(c, GDc, T1.p, T2.p, N, S1.p, S2.p, flags.p);
-                k_fit_update_dir(c, T1.p, T2.p, S1.p, S2.p, G.deg_in, G.deg_out, N, delta, flags.p, flags.p + 1,
-                                 fitstate.p);
-            }
-            int hf[2];
-            HIP_CHECK(hipMemcpyAsync(hf, flags.p, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            iters = hf[1];
-            if (hf[0]) break;
-            if (iters > c->opt_fit_max_iters) CGE_THROW(CGE_E_ASSERT, "Chung-Lu fit did not converge at alpha=%g (%lld iterations; the reference's `while diff > delta` would not return)", alpha, (long long)iters);
-            batch = std::max<i64>(4, std::min<i64>(batch, 32));
-        }
-        sl.iters = iters;
-        if (!sl.fit_async) prev_iters = iters;
-        const double *Ta = directed ? Tout : Tcur, *Tb = directed ? Tin : Tcur;
-        const double *Ta_auc = Ta, *Tb_auc = Tb;
-        if (want_auc && !auc_done && relabel && landmarks) { // v_to_l holds the landmark ids of the original numbering
-            c->sw_rl_T.ensure((size_t)2 * N);
-            k_permute_rows(c, Ta, d_old2new.p, N, 1, c->sw_rl_T.p);
-            Ta_auc = Tb_auc = c->sw_rl_T.p;
-            if (directed) {
-                k_permute_rows(c, Tb, d_old2new.p, N, 1, c->sw_rl_T.p + N);
-                Tb_auc = c->sw_rl_T.p + N;
-            }
-        }
-        if (want_auc && !auc_done) {
-            const DevSamples &ds = *dsets[smp.n_sets == 1 ? 0 : ia - 1];
-            // N > 1 with many samples: rank r tallies the samples [S r / W, S (r + 1) / W) and the block tallies
-            // are summed over the ranks -- the same array on every rank afterwards, so all ranks take the same early stops
-            const i64 s0 = shard_samples ? S * c->coll.rank / c->coll.world : 0;
-            const i64 s1 = shard_samples ? S * (c->coll.rank + 1) / c->coll.world : S;
-            if (landmarks)
-                k_auc_landmark(c, Ta_auc, Tb_auc, orig->v2l, orig->vw, orig->lweight, ds.pi.p + s0, ds.pj.p + s0, ds.ni.p + s0,
-                               ds.nj.p + s0, ds.dpos.p + s0, ds.dneg.p + s0, ds.wts.p + s0, s1 - s0, alpha, nullptr,
-                               scal.p + RES_AUC);
-            else
-                k_auc_exact(c, GDc, Ta, Tb, N, ds.pi.p + s0, ds.pj.p + s0, ds.ni.p + s0, ds.nj.p + s0, ds.wts.p + s0, s1 - s0,
-                            nullptr, scal.p + RES_AUC);
-        }
-        if (shard_samples) {
-            // The verdict of an enqueued fit is rank-local (a hand-off may time out on one rank only), but a redo re-issues
-            // this exchange and changes what the rank enqueues from then on: the ranks must take it together.  So the verdict
-            // rides along as one more summand -- at EVERY alpha of a sweep with split tallies, with or without a local score --
-            // and every rank redoes the alpha when any rank's fit was abandoned: the ranks never leave lock-step.
-            k_fit_verdict(c, (const int *)(scal.p + RES_FIT), sl.fit_async ? 1 : 0, scal.p + RES_VERD);
-            sl.shared_verdict = true;
-            if (want_auc) cge_allreduce_dev(c, scal.p + RES_AUC, 2 * CGE_PARTIAL_BLOCKS + 1, 0);
-            else cge_allreduce_dev(c, scal.p + RES_VERD, 1, 0);
-        }
+            Tb = Ta;
+    }
+    k_auc_landmark(c, Ta, Tb, orig->v2l, orig->vw, orig->lweight, ds.pi.p + s0, ds.pj.p + s0, ds.ni.p + s0, ds.nj.p + s0,
+                   ds.dpos.p + s0, ds.dneg.p + s0, ds.wts.p + s0, s1 - s0, alpha, nullptr, part);
+}
+
+// vect_B and its divergence(s) of one alpha (want_div), then the alpha's scalars to pinned slot `slot` and an event.
+// bvec_partials: vect_B's tile partials came with the fit.  arm: the next alpha's persistent fit may take its hand-off slots
+// armed by this alpha's last launch.
+static void divergence_and_copy_out(cge_ctx *c, const ScoreGraph &G, int directed, int split, const double *Ta,
+                                    const double *Tb, bool want_div, bool bvec_partials, bool arm, i64 Tld, int slot) {
+    hipStream_t st = c->stream;
+    const i64 N = G.N, C = G.C, vlen = directed ? C * C : packed_len(C);
+    const double *GD = c->sw_GD.p;
+    const i32 *cm_off = c->sw_cm_off.p;
+    double *scal = c->sw_scal.p, *vectB = c->sw_vectB.p, *host_out = c->pin_scal.p + RES_STRIDE * slot;
+    if (want_div && (bvec_partials || c->bvec_blocks) && !directed && !c->opt_test_bvec_plain) {
+        // tile partials (from the fit's epilogue, or one pass over GD) -> vect_B and its divergence(s) in one launch
+        if (!bvec_partials) k_bvec_tiles(c, GD, Ta, Tb, cm_off, N, directed);
+        // the last launch of the alpha: it also hands the alpha's scalars to the host's pinned slot and arms the hand-off
+        // slots of the next alpha's persistent fit (instead of a copy and a fill of their own)
+        cge_chain_tail tail{};
+        tail.host_out = host_out;
+        tail.scal = scal;
+        tail.res_js = (int)RES_JS;
+        tail.res_len = (int)RES_LEN;
+        const bool arms = arm && k_fit_flow_arm_region(c, N, Tld, &tail.arm, &tail.arm_n16, &tail.arm_word);
+        if (!arms) { tail.arm = nullptr; tail.arm_n16 = 0; }
+        k_bins_js(c, cm_off, N, C, G.vectC, vectB, split ? 2 : 1, scal + RES_JS, &tail);
+        if (arms) c->flow_armed_words = 4 * tail.arm_n16;
+    } else {
         if (want_div) {
-            if ((bvec_partials || c->bvec_blocks) && !directed && !c->opt_test_bvec_plain) {
-                // tile partials (from the fit's epilogue, or one pass over GD) -> vect_B and its divergence(s) in one launch
-                if (!bvec_partials) k_bvec_tiles(c, GDc, Ta, Tb, d_cm_off.p, N, directed);
-                // the last launch of the alpha: it also hands the alpha's scalars to the host's pinned slot and arms the hand-off
-                // slots of the next alpha's persistent fit (instead of a copy and a fill of their own)
-                cge_chain_tail tail{};
-                tail.host_out = c->pin_scal.p + RES_STRIDE * slot;
-                tail.scal = scal.p;
-                tail.res_js = (int)RES_JS;
-                tail.res_len = (int)RES_LEN;
-                bool arms = false;
-                if (use_persistent && ia < n_alpha_total) arms = k_fit_flow_arm_region(c, N, Tld, &tail.arm, &tail.arm_n16, &tail.arm_word);
-                if (!arms) { tail.arm = nullptr; tail.arm_n16 = 0; }
-                k_bins_js(c, d_cm_off.p, N, C, G.vectC, vectB.p, split ? 2 : 1, scal.p + RES_JS, &tail);
-                if (arms) c->flow_armed_words = 4 * tail.arm_n16;
-                copied_out = true;
-            } else {
-                if (bvec_partials) k_bvec_bins(c, d_cm_off.p, N, C, directed, vectB.p); // the tile partials came with the fit
-                else k_bvec(c, GDc, Ta, Tb, c->sw_cm_pos.p, d_cm_off.p, d_cm_mem.p, N, C, directed, rowbins.p, vectB.p);
-                if (!split)
-                    k_js(c, G.vectC, vectB.p, vlen, C, directed, 0, nullptr, scal.p + RES_JS);
-                else {
-                    k_js(c, G.vectC, vectB.p, vlen, C, directed, 1, nullptr, scal.p + RES_JS);
-                    k_js(c, G.vectC, vectB.p, vlen, C, directed, 2, nullptr, scal.p + RES_JS + CGE_PARTIAL_BLOCKS);
-                }
+            if (bvec_partials) k_bvec_bins(c, cm_off, N, C, directed, vectB); // the tile partials came with the fit
+            else k_bvec(c, GD, Ta, Tb, c->sw_cm_pos.p, cm_off, c->sw_cm_mem.p, N, C, directed, c->sw_rowbins.p, vectB);
+            if (!split)
+                k_js(c, G.vectC, vectB, vlen, C, directed, 0, nullptr, scal + RES_JS);
+            else {
+                k_js(c, G.vectC, vectB, vlen, C, directed, 1, nullptr, scal + RES_JS);
+                k_js(c, G.vectC, vectB, vlen, C, directed, 2, nullptr, scal + RES_JS + CGE_PARTIAL_BLOCKS);
             }
         }
         // the block partials of the alpha's reductions and (behind them) the verdict of an enqueued fit, one copy; the host
         // adds the partials in block order -- what the one-thread "final" kernels did, without their launches
-        if (!copied_out)
-            HIP_CHECK(hipMemcpyAsync(c->pin_scal.p + RES_STRIDE * slot, scal.p, sizeof(double) * RES_LEN, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipEventRecord(c->sweep_ev[slot], st));
-    };
+        HIP_CHECK(hipMemcpyAsync(host_out, scal, sizeof(double) * RES_LEN, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipEventRecord(c->sweep_ev[slot], st));
+}
 
+// What the alphas of one sweep read: the score graph in the sweep's numbering and what its set-up decided
+struct SweepView {
+    const ScoreGraph &G;
+    const OrigView *orig; // landmark mode
+    int directed, split;
+    i64 Tld;
+    const i32 *old2new;   // a relabelled sweep: a vertex's number in the sweep
+    bool fuse, fuse_auc;  // the rest of the chain rides on the fit's launch; the local score's tallies too
+    const std::vector<cge_fit_fused> &h_epi;
+    i64 n_sets, s0, s1;   // sample sets; this rank's samples of each
+    bool shard;           // the tallies are split over the ranks
+};
+
+// One alpha's chain on the stream: pow, the fit, the local score's tallies, vect_B, JS, the scalars -> pinned slot (ia mod 2), an
+// event.  With the enqueue-only persistent fit nothing in the chain needs the host, so the sweep enqueues alpha i + 1 before it
+// waits for alpha i.
+static void enqueue_alpha(cge_ctx *c, const SweepView &sw, i64 ia, bool want_auc, bool want_div, FitForm &fit, AlphaSlot &sl) {
+    const ScoreGraph &G = sw.G;
+    const i64 N = G.N, set = sw.n_sets == 1 ? 0 : ia - 1;
+    const double alpha = AlphaBook::AlphaStep * (double)ia;
+    // the undirected persistent fit and vect_B read the upper triangle only; the exact-mode AUC, the directed vect_B
+    // and the launch-per-iteration fits read whole rows
+    const bool upper = sw.orig && !sw.directed;
+    sl = AlphaSlot();
+    const bool fused_now = sw.fuse && fit.persistent && c->pow_logs_blocked_N == N; // (a fallback in mid-sweep ends it: the matrix is needed then)
+    if (sw.fuse && !fused_now && c->pow_logs_N != N) k_pow_prepare(c, c->sw_D.p, N, upper); // (left the fused path: the row-major logarithm)
+    if (!fused_now) k_pow_matrix(c, c->sw_D.p, N, alpha, c->sw_GD.p, upper);
+    cge_fit_fused ff{};
+    if (fused_now) { // this alpha's copy of the epilogue table: what is not wanted is left out
+        ff = sw.h_epi[set];
+        ff.Lh = c->sw_Lh.p; ff.Ll = c->sw_Ll.p; ff.alpha = alpha;
+        if (!want_div) ff.partial = nullptr;
+        if (!(want_auc && sw.fuse_auc)) ff.auc_part = nullptr;
+    }
+    if (!sw.directed)
+        fit_undirected(c, N, G.vw, sw.Tld, alpha, upper, fused_now ? &ff : nullptr,
+                       fused_now ? reinterpret_cast<const cge_fit_fused *>(c->sw_fused_epi.p) + set : nullptr, fit, sl);
+    else
+        fit_directed(c, G, alpha, fit, sl);
+    if (!sl.fit_async) fit.prev_iters = sl.iters;
+    const double *Tcur = c->fp_T.p + (i64)fit.tpar * sw.Tld;
+    const double *Ta = sw.directed ? c->sw_T2.p : Tcur, *Tb = sw.directed ? c->sw_T1.p : Tcur; // (Tout, Tin)
+    if (want_auc && !(sl.fused && ff.auc_part))
+        local_score_tallies(c, Ta, Tb, N, sw.directed, sw.orig, sw.old2new, *c->dsets[set], sw.s0, sw.s1, alpha);
+    if (sw.shard) {
+        // The verdict of an enqueued fit is rank-local (a hand-off may time out on one rank only), but a redo re-issues
+        // this exchange and changes what the rank enqueues from then on: the ranks must take it together.  So the verdict
+        // rides along as one more summand -- at EVERY alpha of a sweep with split tallies, with or without a local score --
+        // and every rank redoes the alpha when any rank's fit was abandoned: the ranks never leave lock-step.
+        double *scal = c->sw_scal.p;
+        k_fit_verdict(c, (const int *)(scal + RES_FIT), sl.fit_async ? 1 : 0, scal + RES_VERD);
+        sl.shared_verdict = true;
+        if (want_auc) cge_allreduce_dev(c, scal + RES_AUC, 2 * CGE_PARTIAL_BLOCKS + 1, 0);
+        else cge_allreduce_dev(c, scal + RES_VERD, 1, 0);
+    }
+    divergence_and_copy_out(c, G, sw.directed, sw.split, Ta, Tb, want_div, sl.fused && ff.partial,
+                            fit.persistent && ia < AlphaBook::n_alpha, sw.Tld, (int)(ia & 1));
+}
+
+// ---- the sweep -------------------------------------------------------------------------------------
+
+void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
+                     const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],
+                     int *out_len, cge_trace *trace, SweepHandoff *defer) {
+    ScoreGraph G = G_in; // the per-vertex arrays may be replaced by community-sorted copies (plan_layout)
+    const i64 N = G.N, C = G.C, S = smp.S;
+    const i64 vlen = directed ? C * C : packed_len(C);
+    if ((double)N * (double)N * 8.0 * 2.2 > 200e9) CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit", (long long)N);
+    c->sw_D.ensure((size_t)N * N);
+    c->sw_GD.ensure((size_t)N * N);
+    c->sw_T1.ensure(N); c->sw_T2.ensure(N); c->sw_S1.ensure(N); c->sw_S2.ensure(N);
+    c->sw_rowbins.ensure((size_t)N * C);
+    c->sw_vectB.ensure(vlen);
+    c->sw_scal.ensure(RES_STRIDE); // an alpha's scalars (RES_*)
+    c->sw_lohi.ensure(2);
+    c->sw_fitstate.ensure(4);
+    c->sw_flags.ensure(4); // [0]=done, [1]=iters
+    c->sw_fring.ensure(4);
+
+    SweepLayout lay;
+    plan_layout(c, G, orig, directed, lay);
+    const i64 Tld = prepare_distances(c, G, lay, directed);
+    // sample tallies split over the ranks: with the in-library communicator (stream-ordered, no host synchronisation in the
+    // enqueued chain) from 10^5 samples on; option "shard_samples" = 2 forces it (tests, also through the hook), 0 disables
+    const bool shard = c->has_coll && S >= c->coll.world &&
+                       (c->opt_shard_samples == 2 || (c->opt_shard_samples == 1 && c->rccl_comm && S >= 100000));
+    fit_sweep_begin(c);
+    FitForm fit;
+    fit.persistent = !directed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
+                     (c->opt_fit_persistent >= 2 || N >= 128);
+    fit.persistent_dir = directed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
+                         (c->opt_fit_persistent >= 2 || N >= 128);
+    c->stat_fit_persistent = 0;
+    c->stat_fit_iters = 0;
+    samples_to_device(c, smp, N, G.d, orig, ex_src, ex_dst, ex_hw, ex_m, directed,
+                      lay.relabel && !orig ? lay.old2new.p : nullptr);
+    // N > 1 with many samples: rank r tallies the samples [S r / W, S (r + 1) / W) and the block tallies are summed
+    // over the ranks -- the same array on every rank afterwards, so all ranks take the same early stops
+    const i64 s0 = shard ? S * c->coll.rank / c->coll.world : 0, s1 = shard ? S * (c->coll.rank + 1) / c->coll.world : S;
+    const bool fuse_auc = orig && s1 - s0 < 65536 && s1 > s0; // (beyond: auc_landmark_kernel's wide form, as its own launch)
+    std::vector<cge_fit_fused> h_epi;
+    if (lay.fuse) fused_tables(c, G, orig, lay.old2new.p, smp.n_sets, s0, s1, fuse_auc, h_epi);
+    c->stat_fit_fused = 0;
+    if (defer) defer->deferred = false;
+    if (defer && lay.fuse && fuse_auc && fit.persistent && !shard && !c->has_coll && hand_off(c, *defer, G, smp, split, Tld, h_epi))
+        return;
+
+    // ---- alpha sweep: alpha i + 1 is enqueued before the host waits for alpha i, unless the sweep may end at alpha i (so
+    // nothing is ever computed in vain) or the fit of alpha i needs the host
+    // (Round 4 tried the next alpha's power matrix on a side stream beside this alpha's vect_B / JS / AUC: +0.65 ms, the two
+    // cross-queue dependencies per alpha cost more than they hid -- profiles/r04_pow_overlap_ab.txt; removed in round 5, when
+    // the power matrix moved into the fit's prologue anyway.)
+    const SweepView sw{G, orig, directed, split, Tld, lay.old2new.p, lay.fuse, fuse_auc, h_epi, smp.n_sets, s0, s1, shard};
+    AlphaBook book(S, split, trace);
+    AlphaSlot slots[2];
+    c->pin_scal.ensure(2 * RES_STRIDE);
     // log2(1 - D) once for the whole sweep (the upper tiles only when every alpha reads only those); a fallback of the
     // persistent fit in mid-sweep makes k_pow_matrix use the library pow for the whole rows it then needs
-    k_pow_prepare(c, D.p, N, landmarks && !directed, fuse);
+    k_pow_prepare(c, c->sw_D.p, N, orig && !directed, lay.fuse);
     i64 next_enqueue = 1;
-    for (i64 ia = 1; ia <= n_alpha_total; ia++) {
-        const double alpha = AlphaStep * (double)ia;
+    for (i64 ia = 1; ia <= AlphaBook::n_alpha; ia++) {
         AlphaSlot &sl = slots[ia & 1];
         if (next_enqueue == ia) {
-            enqueue_alpha(ia, !skip_auc, !skip_div);
+            enqueue_alpha(c, sw, ia, !book.skip_auc, !book.skip_div, fit, sl);
             next_enqueue = ia + 1;
         }
-        const bool may_end_here = (skip_div || alpha_div_counter == 1) && (skip_auc || alpha_auc_counter == 1);
         // (directed: Tin / Tout are updated in place, so the next alpha is not queued before this one's verdict is known)
-        if (sl.fit_async && !directed && !may_end_here && ia < n_alpha_total) { // keep the device busy while the host reads alpha ia
-            enqueue_alpha(ia + 1, !skip_auc, !skip_div);
+        if (sl.fit_async && !directed && !book.may_end_here() && ia < AlphaBook::n_alpha) { // keep the device busy meanwhile
+            enqueue_alpha(c, sw, ia + 1, !book.skip_auc, !book.skip_div, fit, slots[(ia + 1) & 1]);
             next_enqueue = ia + 2;
         }
         HIP_CHECK(hipEventSynchronize(c->sweep_ev[ia & 1]));
-        const bool peer_failed = sl.shared_verdict && c->pin_scal.p[RES_STRIDE * (ia & 1) + RES_VERD] != 0.0;
+        const double *res = c->pin_scal.p + RES_STRIDE * (ia & 1);
+        const bool peer_failed = sl.shared_verdict && res[RES_VERD] != 0.0;
         if (peer_failed && !sl.fit_async) // cannot happen while the ranks are in lock-step (they enqueue the same form of fit)
             CGE_THROW(CGE_E_COLLECTIVE, "another rank abandoned a persistent fit this rank did not enqueue: the ranks diverged");
         if (sl.fit_async) {
-            const int *hf = (const int *)(c->pin_scal.p + RES_STRIDE * (ia & 1) + RES_FIT);
+            const int *hf = (const int *)(res + RES_FIT);
             if (hf[2] || !hf[0] || peer_failed) { // a wait timed out (here or on another rank): drain what was enqueued behind
-                HIP_CHECK(hipStreamSynchronize(st)); // it and redo this alpha from its T_0 (still in place) with one launch per
-                note_fit_fallback(c);                // iteration, as every later alpha
-                if (directed) use_persistent_dir = false;
+                HIP_CHECK(hipStreamSynchronize(c->stream)); // it and redo this alpha from its T_0 (still in place) with one
+                note_fit_fallback(c);                       // launch per iteration, as every later alpha
+                if (directed) fit.persistent_dir = false;
                 else {
-                    use_persistent = false;
-                    tpar = sl.t0_par;
+                    fit.persistent = false;
+                    fit.tpar = sl.t0_par;
                 }
                 next_enqueue = ia;
                 ia--;
                 continue;
             }
             sl.iters = hf[1];
-            prev_iters = sl.iters;
+            fit.prev_iters = sl.iters;
             c->stat_fit_persistent++;
             if (sl.fused) c->stat_fit_fused++;
         }
-        const i64 iters = sl.iters;
-        c->stat_fit_iters += iters;
-        double auc_val = NAN, div_val = NAN, div_int = 0.0, div_ext = 0.0;
-        const double *res = c->pin_scal.p + RES_STRIDE * (ia & 1);
-        double hs[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (!skip_auc)
-            for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { hs[0] += res[RES_AUC + 2 * b]; hs[1] += res[RES_AUC + 2 * b + 1]; }
-        if (!skip_div) {
-            double fa = 0.0, fb = 0.0;
-            for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { fa += res[RES_JS + b]; fb += res[RES_JS + CGE_PARTIAL_BLOCKS + b]; }
-            if (!split) hs[2] = fa / 2.0;
-            else { hs[3] = fa / 2.0; hs[4] = fb / 2.0; }
-        }
-        if (!skip_auc) {
-            const double auc = 1.0 - hs[0] / hs[1]; // :213
-            auc_val = auc;
-            if (auc < best_auc) {
-                best_auc = auc;
-                best_auc_err = 1.96 * std::sqrt(auc * (1.0 - auc) / (double)S); // :217
-                best_alpha_auc = alpha;
-                alpha_auc_counter = 5;
-            } else {
-                alpha_auc_counter -= 1;
-                skip_auc = alpha_auc_counter == 0;
-            }
-        }
-        if (!skip_div) {
-            double f;
-            if (!split)
-                f = hs[2];
-            else {
-                div_int = hs[3];
-                div_ext = hs[4];
-                f = (div_int + div_ext) / 2.0;
-            }
-            div_val = f;
-            if (f < best_div) {
-                best_div = f;
-                best_alpha = alpha;
-                best_div_ext = !split ? 0.0 : div_ext;
-                best_div_int = !split ? 0.0 : div_int;
-                alpha_div_counter = 5;
-            } else {
-                alpha_div_counter -= 1;
-                skip_div = alpha_div_counter == 0;
-            }
-        }
-        if (trace && trace->n_alpha < 64) {
-            trace->iters[trace->n_alpha] = iters;
-            trace->div[trace->n_alpha] = div_val;
-            trace->auc[trace->n_alpha] = auc_val;
-            trace->n_alpha++;
-        }
-        if (skip_div && skip_auc) break; // :253
+        c->stat_fit_iters += sl.iters;
+        book.take(res, AlphaBook::AlphaStep * (double)ia, sl.iters);
+        if (book.ended()) break;
     }
+    book.write(out, out_len);
+    if (c->stat_fit_persistent > 0 && !c->fit_persistent_broken) c->fit_fallback_streak = 0; // a clean persistent sweep
+}
+
+// ---- the alpha bookkeeping (common.hpp) ------------------------------------------------------------
+AlphaBook::AlphaBook(i64 S_, int split_, cge_trace *trace_) : S(S_), split(split_), trace(trace_) {
+    best_div = best_div_ext = best_div_int = best_auc_err = best_auc = INFINITY; // typemax(Float64)
+    if (trace) trace->n_alpha = 0;
+}
+
+void AlphaBook::take(const double *res, double alpha, i64 iters) {
+    double auc_val = NAN, div_val = NAN;
+    if (!skip_auc) {
+        double num = 0.0, den = 0.0;
+        for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { num += res[RES_AUC + 2 * b]; den += res[RES_AUC + 2 * b + 1]; }
+        const double auc = 1.0 - num / den; // :213
+        auc_val = auc;
+        if (auc < best_auc) {
+            best_auc = auc;
+            best_auc_err = 1.96 * std::sqrt(auc * (1.0 - auc) / (double)S); // :217
+            best_alpha_auc = alpha;
+            auc_counter = 5;
+        } else {
+            auc_counter -= 1;
+            skip_auc = auc_counter == 0;
+        }
+    }
+    if (!skip_div) {
+        double fa = 0.0, fb = 0.0; // all (or internal) / external
+        for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { fa += res[RES_JS + b]; fb += res[RES_JS + CGE_PARTIAL_BLOCKS + b]; }
+        const double div_int = fa / 2.0, div_ext = fb / 2.0;
+        const double f = !split ? fa / 2.0 : (div_int + div_ext) / 2.0;
+        div_val = f;
+        if (f < best_div) {
+            best_div = f;
+            best_alpha = alpha;
+            best_div_ext = !split ? 0.0 : div_ext;
+            best_div_int = !split ? 0.0 : div_int;
+            div_counter = 5;
+        } else {
+            div_counter -= 1;
+            skip_div = div_counter == 0;
+        }
+    }
+    if (trace && trace->n_alpha < 64) {
+        trace->iters[trace->n_alpha] = iters;
+        trace->div[trace->n_alpha] = div_val;
+        trace->auc[trace->n_alpha] = auc_val;
+        trace->n_alpha++;
+    }
+}
+
+void AlphaBook::write(double out[7], int *out_len) const {
     out[0] = best_alpha; out[1] = best_div; out[2] = best_div_ext; out[3] = best_div_int;
     out[4] = best_alpha_auc; out[5] = best_auc; out[6] = best_auc_err; // :256
     *out_len = 7;
-    if (c->stat_fit_persistent > 0 && !c->fit_persistent_broken) c->fit_fallback_streak = 0; // a clean persistent sweep
 }
+
 
 // ---- small helpers ---------------------------------------------------------------------------------
 void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out); // kernels_fit.hip

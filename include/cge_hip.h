@@ -19,9 +19,8 @@
  *     (outputs excepted); outputs are caller-allocated;
  *   - every function returns an int status (0 = ok, <0 = error; cge_last_error() has the text);
  *     nothing throws or exits across the boundary;
- *   - a cge_ctx is bound to ONE GPU and is not re-entrant: one host thread drives it (cge_score
- *     itself starts a second host thread on a shadow context of its own; nothing of that crosses
- *     the boundary).  Multi-GPU runs are one process (one ctx) per GPU; the cross-GPU exchange
+ *   - a cge_ctx is bound to ONE GPU and is not re-entrant: one host thread drives it.
+ *     Multi-GPU runs are one process (one ctx) per GPU; the cross-GPU exchange
  *     steps are issued by the library itself on an RCCL communicator (cge_rccl_unique_id +
  *     cge_comm_init_rccl: ncclAllReduce on the ctx stream), or, where no RCCL communicator can be
  *     made (gloo tests, two ranks on one GPU), go through the cge_collectives hook.
@@ -310,16 +309,12 @@ int cge_max_pair_dist(cge_ctx *ctx, int part, int nparts, double *hi, int64_t *a
  *             The sums are grouped differently from a one-rank run (last-bit differences of elements 5-7).
  * "pow_exp2": 1 (default) = GD = (1 - D)^alpha as exp2(alpha * log2(1 - D)) with log2 computed once per score to ~70
  *             bits (a double and a float per entry; below one ulp, like the library pow); 0 = the library pow per alpha.
- * "test_bvec_plain": testing hook, 1 = vect_B through the kernels that serve score graphs of more than 8192 vertices /
- *             512 communities (no LDS staging); same additions in the same order, hence the same bits.
  * "exact_relabel": exact mode (v_to_l empty) beyond 8192 vertices: 1 (default) = the score graph is relabelled by community
  *             inside the sweep, so that vect_B's row sums are contiguous pieces of a row; 0 = vertices as given (A/B and
  *             tests; same iteration counts, scores equal up to the rounding of the fit's summation order).
  * "bvec_blocks": 1 = sweeps from 256 vertices on relabel the score graph by community and sum vect_B by 64 x 64 tiles (one read of
  *             GD); 0 (default) = row bins + row sums + fold below 8192 vertices (beyond that the sweep is relabelled and uses the
- *             tiles anyway).  Same results up to the rounding of the summation order; measured no faster at the headline.
- * "fit_persistent_test_timeout": testing hook, 1 = every persistent launch gives up at once (the host then
- *             restores the iterate and falls back to one launch per iteration).                              */
+ *             tiles anyway).  Same results up to the rounding of the summation order; measured no faster at the headline.  */
 int cge_set_option(cge_ctx *ctx, const char *key, int64_t value);
 /* "landmarks" (N of the last run, no side effects), "diameter_path" (1 brute / 2 pruned), "diameter_candidate_pairs", "diameter_candidate_tiles", "diameter_refs" (reference points) of the last run;
  * "collective_calls" / "collective_bytes" = all-reduces issued by the in-library RCCL path since cge_create;

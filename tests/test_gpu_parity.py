@@ -728,8 +728,9 @@ def test_wgcl_asserts_mirror_reference(ctx, test115):
 
 def test_score_that_fails_between_the_halves_of_its_sample_draw(ctx, synth20k):
     """cge_score enqueues the local score's sample draws behind the first synchronisation of the landmark phase and looks at
-    them where the sweep starts.  A score that raises in between (a homogeneous community: src/landmarks.jl:165-167) leaves a
-    draw pending; the next score on the context drains it and gives what a fresh context gives."""
+    them where the sweep starts.  A score that raises in between (a homogeneous community: src/landmarks.jl:165-167) drains
+    the pending draw on its way out: a draw of the caller's own goes through right after it (on the device: the graph has more
+    than 5 793 vertices), and the next score gives what a fresh context gives."""
     from cge.jl_amd import api
 
     g = synth20k
@@ -741,6 +742,7 @@ def test_score_that_fails_between_the_halves_of_its_sample_draw(ctx, synth20k):
     ctx.set_embedding(np.tile(np.arange(1.0, d + 1.0), (n, 1)))
     with pytest.raises(api.CGEError, match="homogenous"):
         ctx.score(g["clusters"], 120, 4, "rss", seed=1, auc_samples=5000)
+    drawn = ctx.draw_samples(1, 5000)
     ctx.set_vertex_data(g["comm"], g["vweights"])
     ctx.set_embedding(g["embedding"])
     again = ctx.score(g["clusters"], 120, 4, "rss", seed=1, auc_samples=5000)
@@ -748,6 +750,8 @@ def test_score_that_fails_between_the_halves_of_its_sample_draw(ctx, synth20k):
     fresh = api.Context()
     try:
         fresh.set_inputs(g["edges"], g["eweights"], g["vweights"], g["comm"], g["embedding"])
+        for got, exp in zip(drawn, fresh.draw_samples(1, 5000)):
+            assert np.array_equal(got, exp)
         assert np.array_equal(good, fresh.score(g["clusters"], 120, 4, "rss", seed=1, auc_samples=5000))
     finally:
         fresh.close()
