@@ -471,6 +471,18 @@ class Context:
         self._check(self.L.cge_group_eig(self.h, _p(A), C.c_int64(T), C.c_int64(d), _p(v)))
         return v
 
+    def diameter_bounds_test(self, v_to_l, N, lcomm, C_, pass_):
+        """Testing hook: the bound matrix of the pruned diameter for a landmark assignment (1-based ids) by one named pass
+        (0 fp64, 1 f32, 2 bf16 split).  Returns (P (N, nref), pass that ran, reference points (nref, d), centring mean (d,))."""
+        v2l, lc = _i64(v_to_l), _i64(lcomm)
+        w = int(C_) if C_ >= 32 else int(N)  # the number of reference points (include/cge_hip_testing.h)
+        P, ref, mean = np.zeros((N, w)), np.zeros((w, self.d)), np.zeros(self.d)
+        nref, ran = C.c_int64(), C.c_int()
+        self._check(self.L.cge_diameter_bounds_test(self.h, _p(v2l), C.c_int64(N), _p(lc), C.c_int64(C_), C.c_int(pass_), _p(P),
+                                                    C.byref(nref), C.byref(ran), _p(ref), _p(mean)))
+        assert nref.value == w
+        return P, ran.value, ref, mean
+
     def pow_test(self, x, alpha, method):
         """Testing hook: (1 - x)^alpha on the device; method 0 = library pow, 1 = the sweep's exp2(alpha * log2(1 - x))."""
         x = _f64(x)

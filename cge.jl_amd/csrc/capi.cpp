@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "../../include/cge_hip_testing.h"
+#include <limits>
 
 void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out);
 
@@ -376,7 +377,14 @@ static void embedding_resident(cge_ctx *c, i64 n, i64 d) {
         k_scale_vector(c, c->gmean.p, d, 1.0 / (double)n);
     } else
         k_col_mean(c, c->Xr.p, n, d, c->gmean.p);
+    // A NaN or an Inf anywhere in the embedding reaches its column's mean.  The reference's `hi` is then NaN (extrema() over
+    // distances that hold a NaN, src/divergence.jl:113), and the diameter entry points answer that instead of the maximum over
+    // the pairs that happen to compare: a comparison with NaN is false, so the tile kernels would skip those pairs silently.
+    std::vector<double> hmean(d);
+    HIP_CHECK(hipMemcpyAsync(hmean.data(), c->gmean.p, sizeof(double) * d, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->emb_nonfinite = false;
+    for (double m : hmean) c->emb_nonfinite |= !std::isfinite(m);
     c->centred_ready = false;
     c->lm_ready = false;
 }
@@ -1008,44 +1016,24 @@ static bool samples_can_start_early(cge_ctx *c, i64 seed, bool exact_directed) {
     return seed != -1 && !exact_directed && sampler_uses_device(c) && !c->edges_sharded;
 }
 
-// exact distance of one vertex pair with dist()'s own arithmetic (src/auxilary.jl:14-20)
-static double exact_pair_distance(cge_ctx *c, i64 bi, i64 bj) {
-    DevBuf<i32> &pij = c->epd_i;
-    DevBuf<double> &dd = c->epd_d;
-    pij.ensure(2);
-    dd.ensure(1);
-    if (c->rows_sharded) { // the two rows come from their owners (zero-filled gather, exact), then the same kernel on the pair
-        const i64 d = c->d;
-        const i32 l[2] = {c->h_glob2loc[bi], c->h_glob2loc[bj]}, two[2] = {0, bi == bj ? 0 : 1};
-        DevBuf<double> &rows = c->dm_seed;
-        rows.ensure(2 * d + 2);
-        double hi = 0.0;
-        HIP_CHECK(hipMemcpyAsync(pij.p, l, sizeof(l), hipMemcpyHostToDevice, c->stream));
-        k_gather_rows_f64(c, c->Xr.p, c->n_loc, d, 1, pij.p, 2, rows.p);
-        allreduce(c, rows.p, 2 * d, 2);
-        HIP_CHECK(hipMemcpyAsync(pij.p, two, sizeof(two), hipMemcpyHostToDevice, c->stream));
-        k_pair_dist(c, rows.p, d, pij.p, pij.p + 1, 1, 1.0, dd.p);
-        HIP_CHECK(hipMemcpyAsync(&hi, dd.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        return hi;
-    }
-    const i32 h[2] = {(i32)bi, (i32)bj};
-    double hi = 0.0;
-    HIP_CHECK(hipMemcpyAsync(pij.p, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-    k_pair_dist(c, c->Xr.p, c->d, pij.p, pij.p + 1, 1, 1.0, dd.p);
-    HIP_CHECK(hipMemcpyAsync(&hi, dd.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    return hi;
-}
-
 // diameter of the resident embedding (this rank's share), brute force over all pair tiles
 static double resident_diameter(cge_ctx *c, int part, int nparts, i64 *ai, i64 *aj) {
+    if (c->emb_nonfinite) { // (embedding_resident)
+        c->stat_diameter_path = 1;
+        c->stat_hi_i = c->stat_hi_j = 0;
+        if (ai) *ai = 1;
+        if (aj) *aj = 1;
+        return std::numeric_limits<double>::quiet_NaN();
+    }
     ensure_centred(c);
     double bv;
     i64 bi, bj;
-    k_max_pair(c, c->Xc.p, c->rnorm.p, c->n, c->ldn, c->dpad, part, nparts, &bv, &bi, &bj);
+    std::vector<double> wg_best;
+    k_max_pair(c, c->Xc.p, c->rnorm.p, c->n, c->ldn, c->dpad, part, nparts, &bv, &bi, &bj, &wg_best);
     c->stat_diameter_path = 1;
-    const double hi = bv >= 0.0 ? exact_pair_distance(c, bi, bj) : 0.0;
+    // the pairs whose Gram value is within rounding of the largest one are evaluated with dist()'s own arithmetic
+    // (src/auxilary.jl:14-20) and the largest of THOSE values is `hi` (diameter_host.cpp: gram_delta)
+    const double hi = host_brute_exact(c, part, nparts, bv, wg_best, &bi, &bj);
     c->stat_hi_i = bi; c->stat_hi_j = bj;
     if (ai) *ai = bi + 1;
     if (aj) *aj = bj + 1;
@@ -1055,13 +1043,14 @@ static double resident_diameter(cge_ctx *c, int part, int nparts, i64 *ai, i64 *
 // the same with landmark-pair pruning in front (diameter_host.cpp); `mu` = N reference points (device, row-major)
 static double resident_diameter_lm(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C,
                                    i64 N, int part, int nparts) {
+    if (c->emb_nonfinite) return resident_diameter(c, part, nparts, nullptr, nullptr); // NaN, as the reference's extrema()
     if ((c->opt_diameter != 1 || c->rows_sharded) && (i64)c->h_mem_off.size() == N + 1) { // (sharded rows: the pruned search only)
-        double d2;
+        double hi;
         i64 bi, bj;
-        if (host_diameter_pruned(c, mu, lw, lcomm, C, N, c->h_mem_off, c->h_mem, part, nparts, &d2, &bi, &bj)) {
+        if (host_diameter_pruned(c, mu, lw, lcomm, C, N, c->h_mem_off, c->h_mem, part, nparts, &hi, &bi, &bj)) {
             c->stat_diameter_path = 2;
             c->stat_hi_i = bi; c->stat_hi_j = bj;
-            return exact_pair_distance(c, bi, bj);
+            return hi; // (already in dist()'s arithmetic)
         }
     }
     return resident_diameter(c, part, nparts, nullptr, nullptr);
@@ -1782,6 +1771,17 @@ int cge_group_eig(void *ctx, const double *A, int64_t T, int64_t d, double *v) {
     k_group_eig(c, dA.p, T, d, dv.p);
     HIP_CHECK(hipMemcpyAsync(v, dv.p, sizeof(double) * T * d, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
+    CGE_CATCH(c)
+}
+
+// testing hook (include/cge_hip_testing.h): the gather and one bound pass of the pruned diameter
+int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int64_t *lcomm, int64_t C, int pass, double *P,
+                             int64_t *nref, int *pass_ran, double *ref_points, double *mean) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !v2l || !lcomm || !P || !nref || !pass_ran || N <= 0 || C <= 0 || pass < 0 || pass > 2) return CGE_E_ARG;
+    CGE_TRY(c)
+    HIP_CHECK(hipSetDevice(c->device));
+    host_diameter_bounds_test(c, v2l, N, lcomm, C, pass, P, nref, pass_ran, ref_points, mean);
     CGE_CATCH(c)
 }
 

@@ -410,11 +410,14 @@ struct cge_ctx {
     // diameter scratch
     DevBuf<double> mp_recs;  // MaxRec records (3 doubles each)
     DevBuf<i64> mp_count;
+    DevBuf<i32> nt_pairs, nt_idx, nt_tiles; // near-tied pairs of the arg-max (vertex ids) / their split index arrays
+    DevBuf<double> nt_out, nt_rows; // their dist() values / the gathered rows (option shard_rows)
     DevBuf<double> mp_rd2, mp_refmu; // reference-point distances / centroids of the pruned diameter
     DevBuf<double> mp_commax;        // per-community maxima of the bound matrix (two-level candidate selection)
     DevBuf<i32> mp_plist;            // surviving community pairs (int2 each)
     DevBuf<i32> mp_lref, mp_refoff, mp_refmem;
     DevBuf<double> gmean;    // global feature mean (the centre used by Xc)
+    bool emb_nonfinite = false; // a NaN / Inf in the resident embedding (seen in gmean): the diameter is NaN
     DevBuf<double> Xs, rns, Ms, mnorm, Pm; // landmark-sorted centred copy, centroids, P matrix
     DevBuf<double> pc_groups;              // per (16-row group, reference point) maxima of the bound pass
     DevBuf<float> Xs32, Ms32;              // fp32 copies: operands of the fp32-MFMA bound pass (upper bounds only)
@@ -664,7 +667,7 @@ void k_dist_matrix(cge_ctx *c, const double *emb, const double *diag, i64 N, i64
 void k_minmax_upper(cge_ctx *c, const double *D, i64 N, double *lo_hi);
 void k_normalise(cge_ctx *c, double *D, i64 N, const double *lo_hi);
 void k_max_pair(cge_ctx *c, const double *Xc, const double *rnorm, i64 n, i64 ldn, i64 dpad, int part, int nparts,
-                double *best_val, i64 *best_i, i64 *best_j);
+                double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best = nullptr);
 void k_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi, const i32 *pj, i64 S, double inv_scale_den,
                  double *out);
 void k_diameter_layout(cge_ctx *c, const i32 *mem_off, const i32 *mem, const i32 *soff, i64 N, i32 *pos2node, i32 *sub_land,
@@ -681,8 +684,11 @@ double cge_allreduce_scalar_max(cge_ctx *c, double v); // max of one double over
 bool cge_exchange_fits(cge_ctx *c, size_t need);
 void k_pcent(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, const double *Ms, const double *mnorm,
              i64 ldm, i64 n_land, i64 N, i64 dpad, const i32 *soff, double *P, int part = 0, int nparts = 1);
+void k_max_pair_tile_list(i64 ldn, int part, int nparts, const std::vector<double> &wg, double thr, std::vector<int2> &out);
+i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 nrows, i64 dpad, const void *tiles, i64 t0, i64 t1,
+                   int tri, double thr, const i32 *ids, void *out, i64 cap);
 void k_pair_list(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, i64 npos, i64 dpad, const void *tiles,
-                 i64 ntiles, double *best_val, i64 *best_i, i64 *best_j);
+                 i64 ntiles, double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best = nullptr);
 i64 k_bound_select(cge_ctx *c, const double *Q, const i32 *lref, const double *mu_ref, i64 N, i64 nref, i64 d, double L,
                    void *list, i64 cap, const i32 *ref_off = nullptr, const i32 *ref_mem = nullptr, const double *Ms_fm = nullptr,
                    i64 dpad = 0, i64 ldm = 0,
@@ -855,9 +861,12 @@ void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i
                    std::vector<i64> &group_ids /*0-based*/, bool want_index = false); // also fills c->v2l / lm_mem / lm_memoff (device)
 void host_eig_top(const double *A, i64 d, double *v); // largest-eigenvalue eigenvector, sign: max |.| component > 0
 // diameter_host.cpp
+double host_brute_exact(cge_ctx *c, int part, int nparts, double bv, const std::vector<double> &wg_best, i64 *bi, i64 *bj);
+void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lcomm1, i64 C, int pass, double *P, i64 *nref_out,
+                               int *pass_ran, double *ref_out, double *mean_out);
 bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C, i64 N,
                           const std::vector<i32> &mem_off, const std::vector<i32> &mem, int part, int nparts,
-                          double *best_d2, i64 *bi, i64 *bj);
+                          double *hi, i64 *bi, i64 *bj);
 // wgcl_host.cpp
 // ---- counter-based RNG of the sampler (splitmix64 finaliser over a 4-word counter): the same stream on host and device
 __host__ __device__ inline uint64_t cge_sm64(uint64_t x) {

@@ -13,6 +13,7 @@
 // When fewer than half of the brute-force tiles can be pruned the brute-force kernel runs instead.
 #include <algorithm>
 #include <cmath>
+#include <functional>
 
 #include "common.hpp"
 
@@ -21,49 +22,191 @@ struct BoundRec {
     double B;
     i32 a, b;
 };
+// the answer: the largest dist() value of the pairs evaluated so far; ties go to the smallest (i, j)
+struct ExactBest {
+    double hi = -1.0;
+    i64 i = 0, j = 0;
+    void offer(double v, i64 a, i64 b) {
+        if (a > b) std::swap(a, b);
+        if (v > hi || (v == hi && (a < i || (a == i && b < j)))) { hi = v; i = a; j = b; }
+    }
+};
 } // namespace
 
-// returns false when the caller should fall back to brute force
-// `mu` = N landmark centroids (device, row-major), `lw` their weights (device) and `lcomm` their communities
-// (host, 0-based, C communities).  Reference points: the community centroids when there are at least 32
-// communities (the MFMA pass is then n*C*d instead of n*N*d), else the landmark centroids themselves.
-//
-// THE EXACT STAGE WORKS ON GATHERED ROWS (round 4).  The bound pass reads the bf16 planes (or the f32 copy) of the
-// landmark-sorted rows, so no fp64 copy of the whole embedding is written any more (it was 1 GB written and 1 GB cleared per
-// score at the headline); the few landmarks that survive the bounds are gathered per round -- centred, feature-major, fp64 --
-// into `xe`, and the fp64-MFMA tile kernel runs on that.
-//
-// OPTION shard_rows (c->rows_sharded): `mem_off` / the device index hold THIS RANK's members (local row ids, other ranks'
-// landmarks are empty ranges), c->h_gl_off the global sizes.  Every rank bounds its own rows (all-reduce(max) of the bound
-// matrix), the seed row of the farthest-point sweep is fetched from its owner, and the gathered rows of a round are
-// completed by an all-reduce of the zero-filled gather (op 2: exact), so a candidate pair whose landmarks live on two ranks
-// is evaluated like any other; the rounds are taken in lock-step (the best value so far is all-reduced after each).
-bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C, i64 N,
-                          const std::vector<i32> &mem_off, const std::vector<i32> &mem, int part, int nparts,
-                          double *best_d2, i64 *bi, i64 *bj) {
+// THE ARG-MAX IS RANKED IN ONE ARITHMETIC AND `hi` IS DEFINED IN ANOTHER.  The tile kernels rank pairs by the Gram value
+// g(p) = fl(fl(r_i + r_j) - 2 <x_i, x_j>) of the centred rows; the reference takes the maximum of s(p), dist()'s sequential sum of
+// the squared differences of the rows as given.  Against the exact squared distance D(p), with u = 2^-53, K = dpad >= d and
+// r = the largest squared norm of a centred row:
+//   centring rounds every coordinate once: D moves by at most 2 sqrt(D) u (|x_i| + |x_j|) <= 4 u (r_i + r_j);
+//   the norms are sums of K squares: (K + 1) u (r_i + r_j);  the K-term product sum, in whatever order the matrix instruction
+//   adds it: 2 K u |x_i||x_j| <= K u (r_i + r_j);  the two final operations: <= 4 u (r_i + r_j)
+//       => |g(p) - D(p)| <= (2K + 9) u (r_i + r_j);
+//   s(p) is a sum of d non-negative terms, each a rounded difference squared: |s(p) - D(p)| <= (d + 2) u D(p) <= 2 (d + 2) u (r_i + r_j)
+//       => |g(p) - s(p)| <= (4K + 13) u (r_i + r_j) <= (4K + 13) 2^-52 r =: eta   (any other summation order of s obeys it too).
+// If p* maximises s and q maximises g, g(p*) >= s(p*) - eta >= s(q) - eta >= g(q) - 2 eta.  So every pair that can hold the
+// reference's maximum has a Gram value of at least  g(q) - delta,  delta = (8K + 32) 2^-52 r  (the +6 covers the second-order
+// terms: K u < 2^-43).  Those pairs -- one, unless the data is tied to the last bits -- are evaluated with dist()'s own arithmetic
+// (k_pair_dist) and the largest VALUE wins, ties going to the smallest (i, j): the bits of the reference's `hi` whatever the
+// data.  Evaluating more pairs than these cannot change the answer (each value is a genuine distance), so a lower threshold
+// in an earlier round is harmless.
+static double gram_delta(i64 dpad, double rmax) { return (double)(8 * dpad + 32) * 2.220446049250313e-16 * rmax; }
+
+// dist() of `cnt` vertex pairs (global ids) into `eb`.  Option shard_rows: collective -- the ranks pool their pairs (a slot per
+// rank in a zero-filled buffer, the words added: exact), fetch the rows from their owners the same way, and every rank
+// evaluates every pair: all of them end with the same answer.
+static void dm_eval_pairs(cge_ctx *c, const int2 *pairs, i64 cnt, ExactBest &eb) {
+    const i64 d = c->d;
+    hipStream_t st = c->stream;
+    const i64 CH = 1 << 16;
+    if (!c->rows_sharded) {
+        std::vector<i32> ij;
+        std::vector<double> val;
+        for (i64 k0 = 0; k0 < cnt; k0 += CH) {
+            const i64 kc = std::min(CH, cnt - k0);
+            ij.resize(2 * kc);
+            val.resize(kc);
+            for (i64 k = 0; k < kc; k++) { ij[k] = pairs[k0 + k].x; ij[kc + k] = pairs[k0 + k].y; }
+            c->nt_idx.ensure(2 * kc);
+            c->nt_out.ensure(kc);
+            HIP_CHECK(hipMemcpyAsync(c->nt_idx.p, ij.data(), sizeof(i32) * 2 * kc, hipMemcpyHostToDevice, st));
+            k_pair_dist(c, c->Xr.p, d, c->nt_idx.p, c->nt_idx.p + kc, kc, 1.0, c->nt_out.p);
+            HIP_CHECK(hipMemcpyAsync(val.data(), c->nt_out.p, sizeof(double) * kc, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st)); // (also: ij is reused)
+            for (i64 k = 0; k < kc; k++) eb.offer(val[k], ij[k], ij[kc + k]);
+        }
+        return;
+    }
+    const int W = c->coll.world, me = c->coll.rank;
+    const i64 RCH = 4096; // pairs per rank and step
+    const i64 steps = (i64)cge_allreduce_scalar_max(c, (double)((cnt + RCH - 1) / RCH));
+    std::vector<int2> all((size_t)W * RCH);
+    std::vector<i32> loc, two;
+    std::vector<double> val;
+    for (i64 s = 0; s < steps; s++) {
+        const i64 k0 = s * RCH, kc = std::max<i64>(0, std::min(RCH, cnt - k0));
+        c->nt_pairs.ensure((size_t)2 * W * RCH);
+        HIP_CHECK(hipMemsetAsync(c->nt_pairs.p, 0, sizeof(int2) * W * RCH, st));
+        std::vector<int2> mine(kc);
+        for (i64 k = 0; k < kc; k++) mine[k] = make_int2(pairs[k0 + k].x + 1, pairs[k0 + k].y + 1); // (0 = no pair)
+        if (kc > 0) HIP_CHECK(hipMemcpyAsync(c->nt_pairs.p + (size_t)2 * me * RCH, mine.data(), sizeof(int2) * kc, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // (`mine` leaves scope)
+        cge_allreduce_dev(c, reinterpret_cast<double *>(c->nt_pairs.p), W * RCH, 2);
+        HIP_CHECK(hipMemcpyAsync(all.data(), c->nt_pairs.p, sizeof(int2) * W * RCH, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        loc.clear();
+        std::vector<int2> got;
+        for (const int2 &q : all)
+            if (q.x > 0 && q.y > 0) {
+                got.push_back(make_int2(q.x - 1, q.y - 1));
+                loc.push_back(c->h_glob2loc[q.x - 1]);
+                loc.push_back(c->h_glob2loc[q.y - 1]);
+            }
+        const i64 T = (i64)got.size();
+        if (T == 0) continue; // (the same on every rank)
+        two.resize(2 * T);
+        for (i64 k = 0; k < T; k++) { two[k] = (i32)(2 * k); two[T + k] = (i32)(2 * k + 1); }
+        val.resize(T);
+        c->nt_idx.ensure(4 * T);
+        c->nt_rows.ensure((size_t)2 * T * d);
+        c->nt_out.ensure(T);
+        HIP_CHECK(hipMemcpyAsync(c->nt_idx.p, loc.data(), sizeof(i32) * 2 * T, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(c->nt_idx.p + 2 * T, two.data(), sizeof(i32) * 2 * T, hipMemcpyHostToDevice, st));
+        k_gather_rows_f64(c, c->Xr.p, c->n_loc, d, 1, c->nt_idx.p, 2 * T, c->nt_rows.p); // (rows of other ranks: zeros)
+        cge_allreduce_dev(c, c->nt_rows.p, 2 * T * d, 2);
+        k_pair_dist(c, c->nt_rows.p, d, c->nt_idx.p + 2 * T, c->nt_idx.p + 3 * T, T, 1.0, c->nt_out.p);
+        HIP_CHECK(hipMemcpyAsync(val.data(), c->nt_out.p, sizeof(double) * T, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        // (pair_dist_kernel answers 0 for equal INDICES: here the two rows of a pair always differ in index, and equal rows give 0 anyway)
+        for (i64 k = 0; k < T; k++) eb.offer(got[k].x == got[k].y ? 0.0 : val[k], got[k].x, got[k].y);
+    }
+}
+
+// Every pair of the listed tiles whose Gram value reaches `thr`, handed to `flush` in lists of at most NT_CAP pairs.  `tl` = the
+// tiles of the arg-max launch that can hold such a pair: those of the workgroups whose own best value reaches `thr` (wg[b]:
+// workgroup b took the tiles b, b + wg.size(), ...) -- one workgroup's share unless the data is tied.  A launch whose list
+// overflows (massively tied data: whole tiles within delta of the maximum) is repeated on fewer tiles -- one tile holds 16384
+// pairs, so the halving ends -- and the tied tiles end up evaluated wholly in dist()'s arithmetic.
+static const i64 NT_CAP = (i64)1 << 20;
+template <class Flush>
+static void dm_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 nrows, i64 dpad, const std::vector<int2> &tl,
+                       int tri, double thr, const i32 *ids, Flush flush) {
+    const i64 ntiles = (i64)tl.size();
+    if (ntiles == 0) return;
+    c->nt_pairs.ensure((size_t)2 * NT_CAP);
+    c->nt_tiles.ensure((size_t)2 * ntiles);
+    HIP_CHECK(hipMemcpyAsync(c->nt_tiles.p, tl.data(), sizeof(int2) * ntiles, hipMemcpyHostToDevice, c->stream));
+    std::vector<int2> h;
+    i64 t0 = 0, step = std::min<i64>(ntiles, (i64)1 << 17); // (a launch counts its pairs in 32 bits)
+    while (t0 < ntiles) {
+        const i64 t1 = std::min(ntiles, t0 + step);
+        const i64 cnt = k_pair_collect(c, Xs, rns, ld, nrows, dpad, c->nt_tiles.p, t0, t1, tri, thr, ids, c->nt_pairs.p, NT_CAP);
+        if (cnt > NT_CAP) {
+            if (t1 - t0 <= 1) CGE_THROW(CGE_E_ARG, "diameter: a tile with more pairs than it has entries");
+            step = (t1 - t0 + 1) / 2;
+            continue;
+        }
+        if (cnt > 0) {
+            h.resize(cnt);
+            HIP_CHECK(hipMemcpyAsync(h.data(), c->nt_pairs.p, sizeof(int2) * cnt, hipMemcpyDeviceToHost, c->stream));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            flush(h.data(), cnt);
+        }
+        t0 = t1;
+    }
+}
+
+// the brute-force path's last step (capi.cpp: resident_diameter): `bv` = the largest Gram value of this shard's tiles and `wg`
+// the workgroups' own (k_max_pair; bv negative: the shard holds no pair); returns `hi` and a pair attaining it
+double host_brute_exact(cge_ctx *c, int part, int nparts, double bv, const std::vector<double> &wg, i64 *bi, i64 *bj) {
+    ExactBest eb;
+    if (bv > -1.0) { // (identical rows can leave a Gram value a rounding below zero; -1 is "no pair")
+        double rmax = 0.0;
+        k_argmax_mapped(c, c->rnorm.p, c->n, nullptr, &rmax);
+        const double thr = bv - gram_delta(c->dpad, rmax);
+        std::vector<int2> tl;
+        k_max_pair_tile_list(c->ldn, part, nparts, wg, thr, tl);
+        dm_collect(c, c->Xc.p, c->rnorm.p, c->ldn, c->n, c->dpad, tl, 1, thr, nullptr,
+                   [&](const int2 *p, i64 cnt) { dm_eval_pairs(c, p, cnt, eb); });
+    }
+    if (eb.hi < 0.0) { *bi = *bj = 0; return 0.0; }
+    *bi = eb.i;
+    *bj = eb.j;
+    return eb.hi;
+}
+
+// What the bound pass reads, left on the device by dm_prepare: the landmark-sorted layout, the reference points, the gathered
+// operands of the pass the fitness verdict settled on, the row norms and the seed of the farthest-point sweep.
+struct DmPrep {
+    std::vector<i64> soff; // landmark a owns the sorted positions [soff[a], soff[a + 1])
+    i64 npos = 0, lds_rows = 0;
+    const i32 *d_off = nullptr, *d_mem = nullptr; // the landmark index on the device
+    bool by_comm = false;                         // reference points: community centroids (else the landmark centroids)
+    i64 nref = 0, ldm = 0, KP = 0;
+    const double *mu_ref = nullptr;
+    bool b16 = false, f32 = false; // the pass that runs (neither: fp64)
+    double seed_norm = -1.0;
+    i64 seed_vertex = -1;
+};
+
+// layout, reference points, gather and the fitness verdict of the low-precision passes (host_diameter_pruned's first stage,
+// shared with the kernel-level testing hook); returns false when there are no member lists on the host
+static bool dm_prepare(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C, i64 N,
+                       const std::vector<i32> &mem_off, const std::vector<i32> &mem, DmPrep &S,
+                       const std::function<void(const char *)> &lap) {
     const i64 n = c->n, d = c->d, dpad = c->dpad;
     const bool RS = c->rows_sharded;
-    const i64 n_rows = lm_rows(c);
-    const int W = RS ? c->coll.world : 1, me = RS ? c->coll.rank : 0;
     hipStream_t st = c->stream;
-    c->stat_cand_pairs = c->stat_cand_tiles = 0;
-    double tphase = now_ms();
-    auto lap = [&](const char *name) { // host wall time per stage (the stream is not synchronised here)
-        const double t = now_ms();
-        c->phases.ms[name] += t - tphase;
-        tphase = t;
-    };
-    if (RS && ((i64)c->h_gl_off.size() != N + 1 || !c->lm_index_on_device || mem_off.data() != c->h_mem_off.data()))
-        CGE_THROW(CGE_E_ARG, "diameter (shard_rows): the landmark index of this context's own landmark phase is required");
-    const std::vector<i32> &gl_off = RS ? c->h_gl_off : mem_off; // sizes of the WHOLE landmarks
     // ---- landmark-sorted layout: landmark a owns positions [soff[a], soff[a] + cnt16[a]) (this rank's members) ------------
-    std::vector<i64> soff(N + 1, 0);
+    std::vector<i64> &soff = S.soff;
+    soff.assign(N + 1, 0);
     for (i64 a = 0; a < N; a++) soff[a + 1] = soff[a] + ((mem_off[a + 1] - mem_off[a] + 15) / 16) * 16;
-    const i64 npos = soff[N];
-    const i64 lds_rows = (npos + 127) / 128 * 128 + 128;
+    const i64 npos = S.npos = soff[N];
+    const i64 lds_rows = S.lds_rows = (npos + 127) / 128 * 128 + 128;
     c->pos2node.ensure(std::max<i64>(npos, 1));
     c->sub_land.ensure(lds_rows / 16);
-    const i32 *d_off = c->lm_memoff.p, *d_mem = c->lm_mem.p;
+    const i32 *&d_off = S.d_off, *&d_mem = S.d_mem;
+    d_off = c->lm_memoff.p;
+    d_mem = c->lm_mem.p;
     {
         std::vector<i32> soff32(soff.begin(), soff.end());
         c->dm_soff.ensure(N + 1);
@@ -85,11 +228,12 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
     }
     lap("dm_layout");
     // ---- reference points ---------------------------------------------------------------------------------
-    const bool by_comm = C >= 32 && (i64)lcomm.size() == N && lw != nullptr;
-    const i64 nref = by_comm ? C : N;
+    const bool by_comm = S.by_comm = C >= 32 && (i64)lcomm.size() == N && lw != nullptr;
+    const i64 nref = S.nref = by_comm ? C : N;
     c->stat_nref = nref;
     std::vector<i32> lref(N);
-    const double *mu_ref = mu;
+    const double *&mu_ref = S.mu_ref;
+    mu_ref = mu;
     if (by_comm) {
         std::vector<i32> roff(C + 1, 0), rmem(N);
         for (i64 a = 0; a < N; a++) {
@@ -118,15 +262,16 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
         pk.add(c->mp_lref.p, lref.data(), N);
         pk.flush();
     }
-    const i64 ldm = (nref + 127) / 128 * 128;
+    const i64 ldm = S.ldm = (nref + 127) / 128 * 128;
     c->rns.ensure(lds_rows);
     c->Ms.ensure((size_t)ldm * dpad);
     c->mnorm.ensure(ldm);
     c->Pm.ensure((size_t)N * nref);
     // the maxima as upper bounds from a low-precision matrix pass (kernels_dist.hip (2b), (2c)) or exactly in fp64
-    bool b16 = c->opt_diameter_f32 >= 2 && k_pcent_bf16_applies(dpad);
-    bool f32 = c->opt_diameter_f32 != 0 && !b16;
-    const i64 KP = (dpad + 31) / 32 * 32;
+    bool &b16 = S.b16, &f32 = S.f32;
+    b16 = c->opt_diameter_f32 >= 2 && k_pcent_bf16_applies(dpad);
+    f32 = c->opt_diameter_f32 != 0 && !b16;
+    const i64 KP = S.KP = (dpad + 31) / 32 * 32;
     if (f32) {
         c->Xs32.ensure((size_t)lds_rows * dpad);
         c->Ms32.ensure((size_t)ldm * dpad);
@@ -151,8 +296,8 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
     if (lowp) HIP_CHECK(hipMemcpyAsync(&unfit, c->dm_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     // the seed of the farthest-point sweep: the vertex farthest from the centre (largest squared norm of the centred rows, just
     // computed by the gather); its read-back is the synchronisation the flag needs anyway
-    double seed_norm = -1.0;
-    i64 seed_vertex = k_argmax_mapped(c, c->rns.p, npos, c->pos2node.p, &seed_norm); // (a row id of this rank)
+    S.seed_norm = -1.0;
+    S.seed_vertex = k_argmax_mapped(c, c->rns.p, npos, c->pos2node.p, &S.seed_norm); // (a row id of this rank)
     // The exact fp64 pass (below) instead of a low-precision one when a centred value lies beyond 2^+-100 or is not finite
     // (bit 0), or when NO centred value reaches 2^-40 (bit 1 clear): products below 2^-126 are flushed to zero in the fp32
     // accumulators, an absolute error of < 3K 2^-126 per dot product that the relative margin e only covers while the
@@ -170,10 +315,68 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
         c->Xs.ensure((size_t)lds_rows * dpad);
         k_gather_centre_fm(c, c->Xr.p, c->pos2node.p, c->gmean.p, c->Xs.p, c->rns.p, npos, d, lds_rows, dpad, nullptr, nullptr, KP, nullptr);
     }
+    c->stat_bound_pass = b16 ? 2 : (f32 ? 1 : 0);
+    return true;
+}
+
+// the bound pass dm_prepare settled on: c->Pm (N x nref) = upper bounds of max_{i in a} ||x_i - ref_r||^2
+static void dm_bound_pass(cge_ctx *c, const DmPrep &S, i64 N, int part, int nparts) {
+    const i64 dpad = c->dpad;
+    if (S.npos > 0) {
+        if (S.b16)
+            k_pcent_bf16(c, c->Xb16.p, c->rns.p, S.lds_rows, c->Mb16.p, c->mnorm.p, S.ldm, N, S.nref, S.KP, c->sub_land.p, c->Pm.p, part, nparts);
+        else if (S.f32)
+            k_pcent_f32(c, c->Xs32.p, c->rns.p, S.lds_rows, c->Ms32.p, c->mnorm.p, S.ldm, N, S.nref, dpad, c->dm_soff.p, c->Pm.p, part, nparts);
+        else
+            k_pcent(c, c->Xs.p, c->rns.p, S.lds_rows, c->Ms.p, c->mnorm.p, S.ldm, N, S.nref, dpad, c->sub_land.p, c->Pm.p, part, nparts);
+    } else
+        HIP_CHECK(hipMemsetAsync(c->Pm.p, 0, sizeof(double) * (size_t)(N * S.nref), c->stream));
+}
+
+// returns false when the caller should fall back to brute force
+// `mu` = N landmark centroids (device, row-major), `lw` their weights (device) and `lcomm` their communities
+// (host, 0-based, C communities).  Reference points: the community centroids when there are at least 32
+// communities (the MFMA pass is then n*C*d instead of n*N*d), else the landmark centroids themselves.
+//
+// THE EXACT STAGE WORKS ON GATHERED ROWS (round 4).  The bound pass reads the bf16 planes (or the f32 copy) of the
+// landmark-sorted rows, so no fp64 copy of the whole embedding is written any more (it was 1 GB written and 1 GB cleared per
+// score at the headline); the few landmarks that survive the bounds are gathered per round -- centred, feature-major, fp64 --
+// into `xe`, and the fp64-MFMA tile kernel runs on that.
+//
+// OPTION shard_rows (c->rows_sharded): `mem_off` / the device index hold THIS RANK's members (local row ids, other ranks'
+// landmarks are empty ranges), c->h_gl_off the global sizes.  Every rank bounds its own rows (all-reduce(max) of the bound
+// matrix), the seed row of the farthest-point sweep is fetched from its owner, and the gathered rows of a round are
+// completed by an all-reduce of the zero-filled gather (op 2: exact), so a candidate pair whose landmarks live on two ranks
+// is evaluated like any other; the rounds are taken in lock-step (the best value so far is all-reduced after each).
+bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C, i64 N,
+                          const std::vector<i32> &mem_off, const std::vector<i32> &mem, int part, int nparts,
+                          double *hi, i64 *bi, i64 *bj) {
+    const i64 n = c->n, d = c->d, dpad = c->dpad;
+    const bool RS = c->rows_sharded;
+    const i64 n_rows = lm_rows(c);
+    const int W = RS ? c->coll.world : 1, me = RS ? c->coll.rank : 0;
+    hipStream_t st = c->stream;
+    c->stat_cand_pairs = c->stat_cand_tiles = 0;
+    double tphase = now_ms();
+    auto lap = [&](const char *name) { // host wall time per stage (the stream is not synchronised here)
+        const double t = now_ms();
+        c->phases.ms[name] += t - tphase;
+        tphase = t;
+    };
+    if (RS && ((i64)c->h_gl_off.size() != N + 1 || !c->lm_index_on_device || mem_off.data() != c->h_mem_off.data()))
+        CGE_THROW(CGE_E_ARG, "diameter (shard_rows): the landmark index of this context's own landmark phase is required");
+    const std::vector<i32> &gl_off = RS ? c->h_gl_off : mem_off; // sizes of the WHOLE landmarks
+    DmPrep S;
+    if (!dm_prepare(c, mu, lw, lcomm, C, N, mem_off, mem, S, lap)) return false;
+    const i64 nref = S.nref, ldm = S.ldm;
+    const i32 *d_off = S.d_off, *d_mem = S.d_mem;
+    const bool by_comm = S.by_comm;
+    const double *mu_ref = S.mu_ref;
+    const double seed_norm = S.seed_norm;
+    const i64 seed_vertex = S.seed_vertex;
     // Q is a maximum over vertices: with several ranks each takes its share of the vertex tiles (all of its own rows when the
     // rows are sharded) and the maxima are combined by one all-reduce(max)
     const bool shard_q = !RS && nparts > 1 && c->has_coll && (c->rccl_comm || (c->xptr && (size_t)(N * nref) <= c->xcap));
-    c->stat_bound_pass = b16 ? 2 : (f32 ? 1 : 0);
     // One farthest-point sweep from the vertex farthest from the centre (a memory-bound read of Xr) on the side stream, LAUNCHED
     // AHEAD of the bound pass: its small workgroups then fill the CUs first and the sweep runs at its own speed (~0.3 ms) while
     // the bound pass's one-workgroup-per-CU tiles move in beside them -- launched behind it, the sweep was left the gaps
@@ -214,9 +417,10 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
         std::swap(c->stream, c->copy_stream);
     }
     // the sweep's result (a double and an id in c->mp_recs) is read before the bound pass may reuse that scratch
-    double L = 0.0;
+    double L = 0.0, rmax = seed_norm; // (rmax: the largest squared norm of a centred row, of all ranks)
     i64 far_i = seed_glob, far_j = seed_glob;
     if (RS) {
+        rmax = cge_allreduce_scalar_max(c, seed_norm);
         double v = -1.0;
         i64 q = 0;
         k_farthest_collect(c, &v, &q);
@@ -225,18 +429,7 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
         const double qid = cge_allreduce_scalar_max(c, (W - (int)claim) == me ? (double)(c->h_loc2glob[q] + 1) : 0.0);
         if (Lmax > L) { L = Lmax; far_j = (i64)qid - 1; }
     }
-    if (npos > 0) {
-        if (b16)
-            k_pcent_bf16(c, c->Xb16.p, c->rns.p, lds_rows, c->Mb16.p, c->mnorm.p, ldm, N, nref, KP, c->sub_land.p, c->Pm.p,
-                         shard_q ? part : 0, shard_q ? nparts : 1);
-        else if (f32)
-            k_pcent_f32(c, c->Xs32.p, c->rns.p, lds_rows, c->Ms32.p, c->mnorm.p, ldm, N, nref, dpad, c->dm_soff.p, c->Pm.p,
-                        shard_q ? part : 0, shard_q ? nparts : 1);
-        else
-            k_pcent(c, c->Xs.p, c->rns.p, lds_rows, c->Ms.p, c->mnorm.p, ldm, N, nref, dpad, c->sub_land.p, c->Pm.p,
-                    shard_q ? part : 0, shard_q ? nparts : 1);
-    } else
-        HIP_CHECK(hipMemsetAsync(c->Pm.p, 0, sizeof(double) * (size_t)(N * nref), st));
+    dm_bound_pass(c, S, N, shard_q ? part : 0, shard_q ? nparts : 1);
     if (shard_q || RS) cge_allreduce_dev(c, c->Pm.p, N * nref, 1);
     lap("dm_refs_pcent");
     // ---- lower bound from the farthest-point sweep ----------------------------------------------------------
@@ -255,6 +448,17 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
     }
     lap("dm_farthest");
     // ---- candidate landmark pairs ---------------------------------------------------------------------------
+    // The sweep's L is a distance in a THIRD arithmetic (16 partial sums per row): it enters the search as a bound on the Gram
+    // values, delta below itself (gram_delta: eta covers any summation order), and its pair as the first evaluated candidate.
+    // The selection below and the stop test of the rounds compare bounds with relative margins of 1e-9 on either side: with
+    // rmax <= L (the seed is the row farthest from the centre, and some row lies at least that far from it) delta is below
+    // 2e-12 L for every d <= 512, so those margins already leave delta of room a hundred times over.
+    const double delta = gram_delta(dpad, std::max(rmax, 0.0));
+    ExactBest eb;
+    {
+        const int2 far = make_int2((int)far_i, (int)far_j);
+        dm_eval_pairs(c, &far, 1, eb);
+    }
     const i64 cap = std::min<i64>(N * (N + 1) / 2, (i64)4 << 20);
     c->bound_list.ensure((size_t)2 * cap);
     const i64 cnt = k_bound_select(c, c->Pm.p, c->mp_lref.p, mu_ref, N, nref, d, L * (1.0 - 1e-9), c->bound_list.p, cap,
@@ -288,9 +492,10 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
     if (!RS && c->opt_diameter != 2 && tiles_total > 0.5 * nT * (nT + 1) / 2) return false; // pruning too weak: brute force
     // ---- exact evaluation in decreasing-bound order, round by round, on the gathered rows of the round's landmarks --------
     const int xparts = RS ? W : nparts, xpart = RS ? me : part; // who evaluates which tile of a round
-    double best = L; // the farthest-point pair is a valid answer so far
-    double my_best = -1.0;
-    i64 best_gi = -1, best_gj = -1;
+    double best = L - delta; // a lower bound of the largest Gram value: the farthest-point pair is a valid answer so far
+    std::vector<double> wg_best; // the best Gram value of each workgroup of a round's arg-max launch
+    std::vector<int2> near;      // the round's tiles that can hold a near-tie
+    std::vector<int2> pool;      // (option shard_rows: a round's near-ties of this rank, evaluated together with the other ranks')
     size_t left = cand.size(); // the heap is cand[0, left)
     i64 tile_cap = 4096, global_tile = 0;
     const i64 pos_cap = std::max<i64>(8192, ((i64)512 << 20) / (dpad * 8)); // <= 512 MB of gathered rows per round
@@ -356,6 +561,7 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
                 }
         }
         for (i32 a : lms) in_round[a] = 0;
+        double v = -1.0;
         if (!tiles.empty()) {
             c->stat_cand_tiles += (i64)tiles.size();
             c->tile_list.ensure(2 * tiles.size());
@@ -364,37 +570,91 @@ bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const 
                 pk.add(reinterpret_cast<i32 *>(c->tile_list.p), reinterpret_cast<const i32 *>(tiles.data()), (i64)(2 * tiles.size()));
                 pk.flush();
             }
-            double v;
             i64 pi, pj;
-            k_pair_list(c, c->xe.p, c->xe_rns.p, ldE, E, dpad, c->tile_list.p, (i64)tiles.size(), &v, &pi, &pj);
-            if (v > best) {
-                i32 g2[2] = {0, 0};
-                HIP_CHECK(hipMemcpyAsync(&g2[0], c->xe_glob.p + pi, sizeof(i32), hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipMemcpyAsync(&g2[1], c->xe_glob.p + pj, sizeof(i32), hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                best = my_best = v;
-                best_gi = (i64)g2[0] - 1;
-                best_gj = (i64)g2[1] - 1;
-            }
+            k_pair_list(c, c->xe.p, c->xe_rns.p, ldE, E, dpad, c->tile_list.p, (i64)tiles.size(), &v, &pi, &pj, &wg_best);
         }
-        if (RS) best = cge_allreduce_scalar_max(c, best); // the rounds are taken in lock-step with one threshold
+        if (RS) v = cge_allreduce_scalar_max(c, v); // the rounds are taken in lock-step with one threshold
+        if (v > best) best = v;
+        if (v >= best - delta) { // the round holds pairs that may carry the maximum: their dist() values decide
+            pool.clear();
+            near.clear();
+            if (!tiles.empty())
+                for (size_t t = 0; t < tiles.size(); t++)
+                    if (wg_best[t % wg_best.size()] >= best - delta) near.push_back(tiles[t]);
+            if (!near.empty())
+                dm_collect(c, c->xe.p, c->xe_rns.p, ldE, E, dpad, near, 0, best - delta, c->xe_glob.p,
+                           [&](const int2 *p, i64 cnt) {
+                               if (RS) pool.insert(pool.end(), p, p + cnt);
+                               else dm_eval_pairs(c, p, cnt, eb);
+                           });
+            if (RS) dm_eval_pairs(c, pool.data(), (i64)pool.size(), eb);
+        }
         tile_cap = 131072;
     }
     lap("dm_exact");
-    if (RS && best > L) { // somebody's tile beat the sweep: the lowest rank that holds the best value names the pair
-        const double claim = cge_allreduce_scalar_max(c, my_best == best ? (double)(W - me) : 0.0);
-        const bool mine = (W - (int)claim) == me;
-        const double gi = cge_allreduce_scalar_max(c, mine ? (double)(best_gi + 1) : 0.0);
-        const double gj = cge_allreduce_scalar_max(c, mine ? (double)(best_gj + 1) : 0.0);
-        far_i = (i64)gi - 1;
-        far_j = (i64)gj - 1;
-    } else if (!RS && best_gi >= 0) {
-        far_i = best_gi;
-        far_j = best_gj;
-    }
-    if (far_i > far_j) std::swap(far_i, far_j);
-    *best_d2 = best;
-    *bi = far_i;
-    *bj = far_j;
+    *hi = eb.hi;
+    *bi = eb.i;
+    *bj = eb.j;
     return true;
+}
+
+// Testing hook (include/cge_hip_testing.h: cge_diameter_bounds_test): dm_prepare and dm_bound_pass -- the same launch wrappers
+// as host_diameter_pruned, in the same order -- on the resident embedding for a caller-supplied landmark assignment.  The
+// landmarks' centroids (the plain mean of their members, weight = their size) are formed on the host.
+void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lcomm1, i64 C, int pass, double *P, i64 *nref_out,
+                               int *pass_ran, double *ref_out, double *mean_out) {
+    const i64 n = c->n, d = c->d;
+    if (!c->Xr.p || n <= 0 || d <= 0) CGE_THROW(CGE_E_ARG, "diameter bounds: embedding not resident");
+    if (c->rows_sharded) CGE_THROW(CGE_E_ARG, "diameter bounds: the testing hook needs every row on one rank");
+    if (pass == 2 && !k_pcent_bf16_applies(c->dpad)) CGE_THROW(CGE_E_ARG, "diameter bounds: the bf16 split pass needs d <= 128");
+    hipStream_t st = c->stream;
+    std::vector<i32> mem_off(N + 1, 0), mem(n), lc(N);
+    for (i64 i = 0; i < n; i++) {
+        if (v2l[i] < 1 || v2l[i] > N) CGE_THROW(CGE_E_ARG, "diameter bounds: landmark id %lld outside 1..%lld", (long long)v2l[i], (long long)N);
+        mem_off[v2l[i]]++;
+    }
+    for (i64 a = 0; a < N; a++) {
+        if (mem_off[a + 1] == 0) CGE_THROW(CGE_E_ARG, "diameter bounds: landmark %lld has no member", (long long)(a + 1));
+        if (lcomm1[a] < 1 || lcomm1[a] > C) CGE_THROW(CGE_E_ARG, "diameter bounds: community %lld outside 1..%lld", (long long)lcomm1[a], (long long)C);
+        lc[a] = (i32)(lcomm1[a] - 1);
+        mem_off[a + 1] += mem_off[a];
+    }
+    {
+        std::vector<char> seen(C, 0);
+        for (i64 a = 0; a < N; a++) seen[lc[a]] = 1;
+        for (i64 q = 0; q < C; q++)
+            if (!seen[q]) CGE_THROW(CGE_E_ARG, "diameter bounds: community %lld has no landmark", (long long)(q + 1));
+    }
+    {
+        std::vector<i32> cur(mem_off.begin(), mem_off.end() - 1);
+        for (i64 i = 0; i < n; i++) mem[cur[v2l[i] - 1]++] = (i32)i;
+    }
+    std::vector<double> X((size_t)n * d), mu((size_t)N * d, 0.0), lw(N);
+    HIP_CHECK(hipMemcpyAsync(X.data(), c->Xr.p, sizeof(double) * n * d, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (i64 a = 0; a < N; a++) {
+        const i64 cnt = mem_off[a + 1] - mem_off[a];
+        lw[a] = (double)cnt;
+        for (i64 q = mem_off[a]; q < mem_off[a + 1]; q++)
+            for (i64 k = 0; k < d; k++) mu[a * d + k] += X[(i64)mem[q] * d + k];
+        for (i64 k = 0; k < d; k++) mu[a * d + k] /= (double)cnt;
+    }
+    DevBuf<double> dmu, dlw;
+    dmu.ensure((size_t)N * d);
+    dlw.ensure(N);
+    HIP_CHECK(hipMemcpyAsync(dmu.p, mu.data(), sizeof(double) * N * d, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dlw.p, lw.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    struct KeepOption { int &ref; int val; ~KeepOption() { ref = val; } } keep{c->opt_diameter_f32, c->opt_diameter_f32};
+    c->opt_diameter_f32 = pass;
+    DmPrep S;
+    if (!dm_prepare(c, dmu.p, dlw.p, lc, C, N, mem_off, mem, S, [](const char *) {}))
+        CGE_THROW(CGE_E_ARG, "diameter bounds: no landmark index");
+    dm_bound_pass(c, S, N, 0, 1);
+    HIP_CHECK(hipMemcpyAsync(P, c->Pm.p, sizeof(double) * (size_t)(N * S.nref), hipMemcpyDeviceToHost, st));
+    if (ref_out) HIP_CHECK(hipMemcpyAsync(ref_out, S.mu_ref, sizeof(double) * (size_t)(S.nref * d), hipMemcpyDeviceToHost, st));
+    if (mean_out) HIP_CHECK(hipMemcpyAsync(mean_out, c->gmean.p, sizeof(double) * d, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    *nref_out = S.nref;
+    *pass_ran = c->stat_bound_pass;
 }

@@ -156,7 +156,7 @@ struct MaxRec {
     i64 i, j;
 };
 
-__device__ __forceinline__ void tile_from_linear(i64 t, i64 nS, i64 &SI, i64 &I, i64 &J) {
+__host__ __device__ __forceinline__ void tile_from_linear(i64 t, i64 nS, i64 &SI, i64 &I, i64 &J) {
     // Linear order: super-blocks (SI, SJ >= SI) row-major; inside a super-block tiles row-major.
     const i64 per = (i64)MP_SB * MP_SB;
     const i64 sb = t / per, loc = t - sb * per;
@@ -243,11 +243,16 @@ __global__ __launch_bounds__(256, 2) void max_pair_kernel(const double *__restri
 // Rows are the landmark-sorted copy Xs (every landmark padded to a multiple of 16 rows, so a 16-row
 // MFMA sub-tile belongs to one landmark: sub_land[pos/16], -1 in the tail padding).  Results are
 // combined with integer atomic max on the bit pattern (values are clamped to >= 0).
+// The fp64 expansion |x|^2 - 2 <x, m> + |m|^2 rounds too: the two norms (a sum of K squares each) carry a relative (K + 1) u,
+// the K-term product sum an absolute K u |x||m| <= K u (|x|^2 + |m|^2) / 2, the three final operations 3 u (|x|^2 + |m|^2),
+// u = 2^-53 -- together below (K + 3) 2^-52 (|x|^2 + |m|^2).  Like (2b) and (2c) the pass therefore returns
+// (|x|^2 + |m|^2)(1 + e) - 2 <x, m> with e = (K + 8) 2^-52: an upper bound of |x - m|^2 whatever the rounding did, not the
+// nearest double of it (it was returned uninflated until a kernel-level test compared it with a long double maximum).
 __global__ __launch_bounds__(256, 2) void pcent_kernel(const double *__restrict__ Xs, const double *__restrict__ rns,
                                                        i64 lds_rows, const double *__restrict__ Ms,
                                                        const double *__restrict__ mnorm, i64 ldm, i64 N, i64 dpad,
                                                        const i32 *__restrict__ sub_land,
-                                                       unsigned long long *__restrict__ P, i64 I0, i64 I1) {
+                                                       unsigned long long *__restrict__ P, i64 I0, i64 I1, double e1) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4, c2 = lane * 2;
@@ -262,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void pcent_kernel(const double *__restrict_
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const i64 col = j0 + wc * 64 + b * 16 + lr;
-            const double mn = mnorm[col];
+            const double mn = mnorm[col] * e1;
             double cur = 0.0;
             int curland = -1;
 #pragma unroll
@@ -271,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void pcent_kernel(const double *__restrict_
                 const int land = sub_land[r0 >> 4]; // wave-uniform
                 double v = -1e300;
 #pragma unroll
-                for (int r = 0; r < 4; r++) v = fmax(v, rns[r0 + lk + 4 * r] - 2.0 * acc[a][b][r]);
+                for (int r = 0; r < 4; r++) v = fmax(v, rns[r0 + lk + 4 * r] * e1 - 2.0 * acc[a][b][r]);
                 v = fmax(v, __shfl_xor(v, 16));
                 v = fmax(v, __shfl_xor(v, 32));
                 if (land != curland) {
@@ -707,7 +712,44 @@ __global__ __launch_bounds__(256, 2) void pair_list_kernel(const double *__restr
     reduce_best(best, best_i, best_j, lds, recs);
 }
 
-static void best_of_recs(cge_ctx *c, const MaxRec *d_recs, int nwg, double *bv, i64 *bi, i64 *bj) {
+// (3b) the near-ties of (1) and (3): every pair of the listed tiles whose Gram value reaches `thr` (the arg-max value less the
+// rounding bound of the Gram formula, diameter_host.cpp) is appended to `out` as vertex ids; the caller evaluates them with
+// dist()'s own arithmetic.  `tri` != 0: tiles of max_pair_kernel (pairs i < j, ids = rows), else of pair_list_kernel
+// (ids[position] = vertex id + 1).  *count may pass cap: the caller then asks again for fewer tiles.
+__global__ __launch_bounds__(256, 2) void pair_collect_kernel(const double *__restrict__ Xs, const double *__restrict__ rns, i64 ld,
+                                                              i64 nrows, i64 dpad, const int2 *__restrict__ tiles, i64 t0, i64 t1,
+                                                              int tri, double thr, const i32 *__restrict__ ids,
+                                                              int2 *__restrict__ out, unsigned *__restrict__ count, unsigned cap) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4, c2 = lane * 2;
+    const i64 nchunk = dpad / MP_BK;
+    for (i64 t = t0 + blockIdx.x; t < t1; t += gridDim.x) {
+        const i64 i0 = tiles[t].x, j0 = tiles[t].y;
+        d4 acc[4][4];
+        gram_tile_128(Xs + (i64)wave * ld + i0 + c2, Xs + (i64)wave * ld + j0 + c2, ld, ld, nchunk, lds, acc, wave, c2, wr, wc, lr, lk);
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const i64 j = j0 + wc * 64 + b * 16 + lr;
+            const double rj = rns[j]; // (padded to ld)
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const i64 i = i0 + wr * 64 + a * 16 + lk + 4 * r;
+                    const bool in = tri ? (j < nrows && i < j) : (i < nrows && j < nrows);
+                    if (in && rns[i] + rj - 2.0 * acc[a][b][r] >= thr) { // the expression of the arg-max kernels: the same bits
+                        const unsigned at = atomicAdd(count, 1u);
+                        if (at < cap) out[at] = ids ? make_int2(ids[i] - 1, ids[j] - 1) : make_int2((int)i, (int)j);
+                    }
+                }
+        }
+    }
+}
+
+// `wg` (optional): the workgroups' own best values -- workgroup b took the tiles b, b + nwg, ... of its launch, so the near-ties of
+// the arg-max can only sit in the tiles of the workgroups whose best value reaches the threshold
+static void best_of_recs(cge_ctx *c, const MaxRec *d_recs, int nwg, double *bv, i64 *bi, i64 *bj, std::vector<double> *wg = nullptr) {
     std::vector<MaxRec> h(nwg);
     HIP_CHECK(hipMemcpyAsync(h.data(), d_recs, sizeof(MaxRec) * nwg, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -716,6 +758,10 @@ static void best_of_recs(cge_ctx *c, const MaxRec *d_recs, int nwg, double *bv, 
         if (h[k].val > *bv || (h[k].val == *bv && (h[k].i < *bi || (h[k].i == *bi && h[k].j < *bj)))) {
             *bv = h[k].val; *bi = h[k].i; *bj = h[k].j;
         }
+    if (wg) {
+        wg->resize(nwg);
+        for (int k = 0; k < nwg; k++) (*wg)[k] = h[k].val;
+    }
 }
 #define MP_NWG 512
 #define MP_LDS_BYTES ((size_t)2 * 2 * MP_BK * MP_LD * sizeof(double))
@@ -723,7 +769,7 @@ static void best_of_recs(cge_ctx *c, const MaxRec *d_recs, int nwg, double *bv, 
 // Shard `part` of `nparts` owns the super-block rows SI with SI % nparts == part (balanced to
 // one super-row; no tile is visited twice across shards).
 void k_max_pair(cge_ctx *c, const double *Xc, const double *rnorm, i64 n, i64 ldn, i64 dpad, int part, int nparts,
-                double *best_val, i64 *best_i, i64 *best_j) {
+                double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best) {
     c->mp_recs.ensure(MP_NWG * 3);
     MaxRec *recs = reinterpret_cast<MaxRec *>(c->mp_recs.p);
     {
@@ -731,7 +777,7 @@ void k_max_pair(cge_ctx *c, const double *Xc, const double *rnorm, i64 n, i64 ld
         hipLaunchKernelGGL(max_pair_kernel, dim3(MP_NWG), dim3(256), MP_LDS_BYTES, c->stream, Xc, rnorm, n, ldn, dpad,
                            part, nparts, recs);
     }
-    best_of_recs(c, recs, MP_NWG, best_val, best_i, best_j);
+    best_of_recs(c, recs, MP_NWG, best_val, best_i, best_j, wg_best);
 }
 
 // P is (number of landmarks) x nref, row stride nref: P[a][r] = max over the rows of landmark a of ||x - ref_r||^2
@@ -743,7 +789,8 @@ void k_pcent(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, cons
     const i64 ntiles = (I1 - I0) * (ldm / MP_BN);
     if (ntiles <= 0) return;
     hipLaunchKernelGGL(pcent_kernel, dim3((unsigned)std::min<i64>(ntiles, 2048)), dim3(256), MP_LDS_BYTES, c->stream, Xs,
-                       rns, lds_rows, Ms, mnorm, ldm, N, dpad, sub_land, reinterpret_cast<unsigned long long *>(P), I0, I1);
+                       rns, lds_rows, Ms, mnorm, ldm, N, dpad, sub_land, reinterpret_cast<unsigned long long *>(P), I0, I1,
+                       1.0 + (double)(dpad + 8) * 2.220446049250313e-16); // 1 + e, e = (K + 8) 2^-52
 }
 
 // `soff` = device copy of the landmark offsets of the sorted layout (N_land + 1 entries, multiples of 16).  With several
@@ -796,7 +843,7 @@ void k_pcent_bf16(cge_ctx *c, const unsigned short *Xb, const double *rns, i64 l
 }
 
 void k_pair_list(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, i64 npos, i64 dpad, const void *tiles,
-                 i64 ntiles, double *best_val, i64 *best_i, i64 *best_j) {
+                 i64 ntiles, double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best) {
     c->mp_recs.ensure(MP_NWG * 3);
     MaxRec *recs = reinterpret_cast<MaxRec *>(c->mp_recs.p);
     const int nwg = (int)std::max<i64>(1, std::min<i64>(ntiles, MP_NWG));
@@ -805,7 +852,41 @@ void k_pair_list(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, 
         hipLaunchKernelGGL(pair_list_kernel, dim3(nwg), dim3(256), MP_LDS_BYTES, c->stream, Xs, rns, lds_rows, npos,
                            dpad, reinterpret_cast<const int2 *>(tiles), ntiles, recs);
     }
-    best_of_recs(c, recs, nwg, best_val, best_i, best_j);
+    best_of_recs(c, recs, nwg, best_val, best_i, best_j, wg_best);
+}
+
+// the tiles of max_pair_kernel's shard (`part`, `nparts`) that the workgroups with a best value of at least `thr` took
+// (`wg` from k_max_pair), as (first row, first column)
+void k_max_pair_tile_list(i64 ldn, int part, int nparts, const std::vector<double> &wg, double thr, std::vector<int2> &out) {
+    const i64 nT = ldn / MP_BM, nS = (nT + MP_SB - 1) / MP_SB, total = nS * (nS + 1) / 2 * MP_SB * MP_SB;
+    out.clear();
+    for (i64 b = 0; b < (i64)wg.size(); b++) {
+        if (!(wg[b] >= thr)) continue;
+        for (i64 t = b; t < total; t += (i64)wg.size()) {
+            i64 SI, I, J;
+            tile_from_linear(t, nS, SI, I, J);
+            if (I >= nT || J >= nT || J < I || (SI % nparts) != part) continue;
+            out.push_back(make_int2((int)(I * MP_BM), (int)(J * MP_BN)));
+        }
+    }
+}
+// returns the number of pairs found (synchronises); above `cap` the list is incomplete
+i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 nrows, i64 dpad, const void *tiles, i64 t0, i64 t1,
+                   int tri, double thr, const i32 *ids, void *out, i64 cap) {
+    if (t1 <= t0) return 0;
+    c->mp_count.ensure(2);
+    unsigned *cnt = reinterpret_cast<unsigned *>(c->mp_count.p);
+    HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned), c->stream));
+    {
+        ScopedKernelTimer t(c, "pair_collect");
+        hipLaunchKernelGGL(pair_collect_kernel, dim3((unsigned)std::min<i64>(t1 - t0, MP_NWG)), dim3(256), MP_LDS_BYTES, c->stream, Xs, rns,
+                           ld, nrows, dpad, reinterpret_cast<const int2 *>(tiles), t0, t1, tri, thr, ids,
+                           reinterpret_cast<int2 *>(out), cnt, (unsigned)cap);
+    }
+    unsigned h = 0;
+    HIP_CHECK(hipMemcpyAsync(&h, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    return (i64)h;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -243,8 +243,12 @@ int cge_edge_scatter(cge_ctx *ctx, const int64_t *v_to_l, int64_t N, int64_t C, 
                      int64_t e1, double *wedges_out, double *vect_C_out);
 /* point-set diameter `hi` = maximum(full_graph_D) (src/divergence.jl:104-113) of the resident
  * embedding.  Shard `part` of `nparts` visits its share of the pair tiles (nparts = 1: all);
- * returns the distance of the shard's arg-max pair computed with dist()'s own arithmetic
- * (src/auxilary.jl:14-20), so the max over shards is the reference's `hi`.                      */
+ * returns the largest distance of the shard's pairs in dist()'s own arithmetic (src/auxilary.jl:14-20;
+ * every pair within the Gram formula's rounding bound of the tiles' arg-max is evaluated that way),
+ * so the max over shards has the bits of the reference's `hi` whatever the data.  arg_i < arg_j
+ * (1-based): a pair attaining it, the smallest (i, j) among ties -- (1, 2) when all rows are equal;
+ * a shard without pairs answers 0.  A NaN or Inf anywhere in the embedding: hi = NaN (what
+ * extrema() returns in the reference), arg_i = arg_j = 1.                                        */
 int cge_max_pair_dist(cge_ctx *ctx, int part, int nparts, double *hi, int64_t *arg_i, int64_t *arg_j);
 
 /* ---- options / statistics --------------------------------------------------------------------- */

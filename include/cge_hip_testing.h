@@ -20,6 +20,16 @@ int cge_host_pos_draw(int64_t seed, int64_t stream_id, int64_t S, int64_t m, int
  * back) by the batched device solvers that landmarks uses (d <= 128: register-resident; d <= 512: global-memory
  * resident); returns CGE_E_ARG for d > 512 */
 int cge_group_eig(void *ctx, const double *A, int64_t T, int64_t d, double *v);
+/* kernel-level hook (needs the GPU): the bound matrix of the pruned diameter for the resident embedding and a caller-supplied
+ * landmark assignment -- the layout, the reference points, the gather with its fitness verdict and ONE bound pass, by the launch
+ * wrappers cge_score's diameter uses.  v2l[i] in 1..N (every landmark non-empty; its centroid is the mean of its members),
+ * lcomm[a] in 1..C (every community non-empty).  pass: 0 fp64, 1 f32, 2 the bf16 split (CGE_E_ARG for d > 128, where it does
+ * not apply).  P (N x nref doubles, row-major): P[a][r] >= max over the members i of a of ||x_i - ref_r||^2 on the centred rows;
+ * nref = C reference points (the community centroids) for C >= 32, else the N landmark centroids; pass_ran = the pass after
+ * the fitness verdict (0 when a centred value is unfit for the low-precision passes).  Optional: ref_points (nref x d,
+ * row-major, uncentred) and mean (d): what the device centred with */
+int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int64_t *lcomm, int64_t C, int pass, double *P,
+                             int64_t *nref, int *pass_ran, double *ref_points, double *mean);
 /* out[i] = (1 - x[i])^alpha on the device (host vectors): method 0 = the library pow, 1 = exp2(alpha * log2(1 - x)) with
  * the logarithm in double + float parts, as the alpha sweep computes GD = (1 - D)^alpha (src/divergence.jl:142-148) */
 int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method, double *out);
