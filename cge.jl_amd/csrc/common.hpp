@@ -76,28 +76,18 @@ template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
-    bool borrowed = false; // a view of another context's buffer (the side context of cge_score): never freed here
     DevBuf() {}
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { release(); }
     void release() {
-        if (p && !borrowed) (void)hipFree(p);
+        if (p) (void)hipFree(p);
         p = nullptr;
         n = 0;
-        borrowed = false;
     }
     void swap(DevBuf &o) { // (ownership changes hands; the device pointers stay valid)
         std::swap(p, o.p);
         std::swap(n, o.n);
-        std::swap(borrowed, o.borrowed);
-    }
-    void borrow(const DevBuf &o) {
-        if (p == o.p && n == o.n && borrowed) return;
-        release();
-        p = o.p;
-        n = o.n;
-        borrowed = o.p != nullptr;
     }
     // grow-only allocation (contents are NOT preserved)
     void ensure(size_t count) {
@@ -318,7 +308,6 @@ struct cge_ctx {
     int be_per = 16;                    // edges per thread of the edge pass the chunks were cut for (kernels_scatter.hip)
     DevBuf<unsigned short> be_keys, be_runoff;
     DevBuf<unsigned short> v2l16;       // uint16 landmark of every vertex (padded like comm16): table of the landmark-pair passes
-    DevBuf<unsigned> be_base, be_cursor;
     std::vector<double> h_Xr; // host mirror, row-major (cut rules + RSS run on the host)
     std::vector<i32> h_comm;
     std::vector<double> h_vw;
@@ -352,7 +341,7 @@ struct cge_ctx {
     DevBuf<int> sw_flags;
     DevBuf<unsigned long long> sw_fring;
     // persistent Chung-Lu fit (kernels_fitp.hip): T double buffer, partial vectors, per-workgroup maxima, barrier words
-    DevBuf<double> fp_T, fp_Tsave, fp_P, fp_fpart, fp_fq, fp_Td, fp_flow;
+    DevBuf<double> fp_T, fp_Tsave, fp_P, fp_fpart, fp_Td, fp_flow;
     DevBuf<double> ls_eigscr;            // wide eigen-solver: partial vectors of its tile sweeps (kernels_lm.hip)
     bool bvec_contig = false;            // the score graph of the running sweep has contiguous communities (relabelled)
     bool bvec_blocks = false;            // ... and vect_B is summed by tiles (kernels_fit.hip: bvec_tile_kernel + bvec_bins_kernel)
@@ -374,7 +363,6 @@ struct cge_ctx {
     i64 stat_fit_batched_launches = 0, stat_fit_batched_alphas = 0;
     DevBuf<i32> sw_rl_order, sw_rl_comm; // exact mode, N > 8192: the score graph relabelled by community (wgcl_host.cpp)
     DevBuf<double> sw_rl_emb, sw_rl_vec, sw_rl_T;
-    DevBuf<unsigned> fp_sync;
     DevBuf<int> fp_flags;
     PinBuf<double> pin_scal;    // the scalars of an alpha (AUC sums, divergences, the fit's verdict), two alphas in flight
     hipEvent_t sweep_ev[2] = {nullptr, nullptr};
@@ -447,8 +435,9 @@ struct cge_ctx {
     DevBuf<double> ls_part, ls_mean, ls_sw, ls_cov, ls_vec, ls_z, ls_sums;
     DevBuf<unsigned char> ls_side, ls_state;
     DevBuf<double> ls_params; // per-task round parameters of the rss rule
-    PinBuf<double> pin_sums, pin_params, pin_cmeans;
-    PinBuf<i32> pin_rows[2], pin_row_task[2]; // [0]: cluster upload staging, [1]: rows of a host-built (generic rss path) batch
+    PinBuf<double> pin_sums, pin_params;
+    PinBuf<i32> pin_clusters;               // runsplit: the initial clusters on their way into the member arena
+    PinBuf<i32> pin_hb_rows, pin_hb_row_task; // rows / row -> task of a host-built batch (the generic rss path)
     // sorted-prefix rss path
     DevBuf<i32> sp_srows, sp_meta, sp_rounds, sp_tro, sp_perm, sp_status, sort_idx, sort_idx2, sort_keys32, sort_k32b, sort_cnt;
     DevBuf<unsigned char> sort_keys8;
@@ -457,10 +446,7 @@ struct cge_ctx {
     i64 lm_arena_used = 0;
     DevBuf<double> lm_means; // weighted means of groups, known from their parents' splits (d doubles each)
     i64 lm_means_used = 0;
-    // covariances of the groups that have been split (d*d doubles each, about the group's own mean): a child's covariance is
-    // its parent's minus its sibling's, so only the smaller child of a pair is summed over its rows (landmarks_host.cpp)
-    DevBuf<i64> ls_moff;
-    PinBuf<i64> pin_moff;
+    DevBuf<i64> ls_moff; // the groups' offsets into lm_means, one per task of a batch
     // small host <-> device tables of a landmark batch travel packed: one pinned staging area, one copy, one kernel that
     // scatters (gathers) the 4-byte words to (from) their device arrays (landmarks_host.cpp: WordPacker)
     PinBuf<i32> pin_tab[2], pin_res;
@@ -482,7 +468,6 @@ struct cge_ctx {
     // grow-only scratch of per-score helpers (no hipMalloc / hipFree inside a scoring call after the first: a hipFree waits
     // for every stream of the device)
     DevBuf<i32> epd_i, s_star;
-    DevBuf<double> epd_d;
     DevBuf<i64> wed_cnt;
     DevBuf<double> cc_dense; // dense C x C stage of vect_C beyond 2048 communities (tiled two-pass form)
     DevBuf<unsigned> samp_attempt;

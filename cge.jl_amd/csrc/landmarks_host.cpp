@@ -17,10 +17,7 @@
 #include <atomic>
 #include <cfloat>
 #include <cmath>
-#include <deque>
 #include <memory>
-#include <thread>
-#include <unordered_map>
 
 #include "common.hpp"
 
@@ -51,7 +48,6 @@ struct Group {
     // split (the WSSE column sums of a child are sum w x and sum w): d doubles at this offset of the means arena
     // (c->lm_means), -1 = compute it on the device.  cmean_off: the two children's means, low then high.
     i64 mean_off = -1, cmean_off = -1;
-    Group *parent = nullptr; // (children of a cached split)
     int owner = 0;           // option shard_rows: the rank that holds this group's rows (off / coff / mean_off are -1 elsewhere)
 };
 
@@ -76,7 +72,6 @@ struct GroupPool {
     Group &back() { return chunks[(used - 1) / CH][(used - 1) % CH]; }
 };
 
-inline cge_ctx *root_of(cge_ctx *x) { return x; } // (rounds 3-4 ran half batches on shadow contexts of a root; removed in round 5)
 // Growth copies the arena into a larger allocation: everything that may still read or write the old one has to be done.
 template <typename T>
 void arena_grow(cge_ctx *c, DevBuf<T> &buf, i64 used, i64 need) {
@@ -91,8 +86,7 @@ void arena_grow(cge_ctx *c, DevBuf<T> &buf, i64 used, i64 need) {
     buf.n = (size_t)cap;
 }
 // reserve `cnt` entries of the member arena (ranges handed out earlier stay valid as offsets)
-i64 arena_alloc(cge_ctx *x, i64 cnt) {
-    cge_ctx *c = root_of(x);
+i64 arena_alloc(cge_ctx *c, i64 cnt) {
     const i64 need = c->lm_arena_used + cnt;
     if ((i64)c->lm_arena.n < need || !c->lm_arena.p) arena_grow(c, c->lm_arena, c->lm_arena_used, need);
     const i64 at = c->lm_arena_used;
@@ -100,8 +94,7 @@ i64 arena_alloc(cge_ctx *x, i64 cnt) {
     return at;
 }
 // reserve `cnt` doubles of the means arena (same growth rule as the member arena)
-i64 means_alloc(cge_ctx *x, i64 cnt) {
-    cge_ctx *c = root_of(x);
+i64 means_alloc(cge_ctx *c, i64 cnt) {
     const i64 need = c->lm_means_used + cnt;
     if ((i64)c->lm_means.n < need || !c->lm_means.p) arena_grow(c, c->lm_means, c->lm_means_used, need);
     const i64 at = c->lm_means_used;
@@ -467,10 +460,10 @@ void build_batch_host(cge_ctx *c, Group *const *groups, i64 T, Batch &B) {
     std::vector<i64> lens(T);
     for (i64 t = 0; t < T; t++) lens[t] = (i64)groups[t]->what.size();
     batch_tables(B, lens);
-    c->pin_rows[1].ensure(B.R);
-    c->pin_row_task[1].ensure(B.R);
-    B.rows = c->pin_rows[1].p;
-    B.row_task = c->pin_row_task[1].p;
+    c->pin_hb_rows.ensure(B.R);
+    c->pin_hb_row_task.ensure(B.R);
+    B.rows = c->pin_hb_rows.p;
+    B.row_task = c->pin_hb_row_task.p;
     parallel_for(c, T, [&](i64 t) {
         const Group *g = groups[t];
         const i64 o = B.task_row_off[t], k = (i64)g->what.size();
@@ -552,9 +545,8 @@ struct RssState {
 };
 void rule_rss_batched(cge_ctx *c, const Batch &B, Group *const *groups, const double *z, std::vector<RssState> &st) {
     const i64 T = B.T, d = c->d, width = 2 * (2 * d + 1);
-    cge_ctx *hr = root_of(c); // the host mirrors live in the root context
-    cge_ensure_host_embedding(hr); // generic round-based path only (ties at the maximum of z, NaNs)
-    const double *hX = hr->h_Xr.data(), *hw = lm_hvw(hr); // (option shard_rows: this rank's rows, local ids)
+    cge_ensure_host_embedding(c); // generic round-based path only (ties at the maximum of z, NaNs)
+    const double *hX = c->h_Xr.data(), *hw = lm_hvw(c); // (option shard_rows: this rank's rows, local ids)
     st.assign(T, RssState());
     parallel_for(c, T, [&](i64 t) {
         RssState &S = st[t];
@@ -653,25 +645,21 @@ void rule_rss_batched(cge_ctx *c, const Batch &B, Group *const *groups, const do
     }
 }
 
-// What a rule leaves behind for every task of a batch: the children's member lists are already in the arena range of
-// the batch (task t at base + task_row_off[t], low first); the host gets the sizes, values and means.
-struct CutResult {
-    std::vector<i32> nlow;
-    std::vector<double> vlow, vhigh;
-    std::vector<char> done; // 0 = this task still needs the generic host path
-};
-
-// One (half) batch in flight on one context (the root or its second lane): everything from the batch tables to the
-// rule's cut is ENQUEUED on that context's stream without a host synchronisation (lane_enqueue), the results are read
-// when the host comes back for them (lane_collect).  Two of these run half a chain out of phase (compute_splits).
-struct LaneRun {
-    cge_ctx *x = nullptr; // where it runs
+// One batch of groups being split, on the context's stream.  split_enqueue queues everything from the batch tables to the
+// rule's cut without a host synchronisation; split_collect books the results when the host comes back for them.  The two
+// stay apart because what the heap needs is fetched BEFORE the children's member lists are written: the host parses the
+// results while that sort still runs (it only feeds the device-side arena; the next batch queues behind it on the stream).
+// What a rule leaves behind for task t: the children's member lists in the arena at base + task_row_off[t] (low first),
+// their means at mbase + 2 t d, and on the host the size of the low child, the two values and `done`.
+struct SplitBatch {
     Group *const *groups = nullptr;
     i64 T = 0;
     int method = 0;
     Batch B;
     i64 base = 0, mbase = -1; // children ranges, children means (arena offsets)
-    CutResult cr;
+    std::vector<i32> nlow;
+    std::vector<double> vlow, vhigh;
+    std::vector<char> done; // 0 = this task still needs the generic host path
     std::unique_ptr<WordGatherer> wg;
     size_t i_status = 0, i_meta = 0, i_vals = 0, i_nlow = 0;
 };
@@ -681,9 +669,8 @@ struct LaneRun {
 // writes the children's member lists in the reference's order (seed first, then every absorbed batch in ascending
 // original index, :163-164, :189, :194, :204-206) by one stable radix pass over per-row bucket keys.
 // Tasks the rank-range argument does not cover (a tie at the maximum of z, NaNs) are left to the generic path.
-void rule_rss_sorted_enqueue(LaneRun &L) {
-    cge_ctx *c = L.x;
-    const Batch &B = L.B;
+void rule_rss_sorted_enqueue(cge_ctx *c, SplitBatch &S) {
+    const Batch &B = S.B;
     const i64 T = B.T, R = B.R, d = c->d, W = 2 * d + 1;
     c->sp_srows.ensure(R); c->sp_zs.ensure(R); c->sp_perm.ensure(R); c->sp_status.ensure(T);
     c->sp_ctot.ensure((size_t)B.NC * W); c->sp_coff.ensure((size_t)B.NC * W);
@@ -695,79 +682,73 @@ void rule_rss_sorted_enqueue(LaneRun &L) {
     k_sorted_prefix(c, c->Xr.p, lm_vw(c), c->sp_srows.p, c->ls_cb.p, c->ls_ce.p, B.NC, c->ls_tco.p, T, d, c->sp_ctot.p,
                     c->sp_coff.p, c->sp_prefix.p);
     k_rss_rounds(c, c->Xr.p, lm_vw(c), c->sp_srows.p, c->sp_zs.p, c->sp_tro.p, c->ls_tco.p, c->sp_prefix.p, c->sp_coff.p,
-                 T, d, c->sp_meta.p, c->sp_rounds.p, c->sp_vals.p, c->lm_means.p + L.mbase); // the children's means stay on the device
+                 T, d, c->sp_meta.p, c->sp_rounds.p, c->sp_vals.p, c->lm_means.p + S.mbase); // the children's means stay on the device
     k_rss_child_keys(c, c->sp_perm.p, c->ls_row_task.p, c->sp_tro.p, c->sp_meta.p, c->sp_rounds.p, R, T, c->ls_keys.p,
                      c->ls_nlow.p);
-    // what the host needs for the heap (status, rounds, children values and sizes) is fetched BEFORE the children's member
-    // lists are written: the host replays the heap and builds the next batch while that sort still runs (it only feeds the
-    // device-side arena; the next batch queues behind it on the same stream)
-    L.wg.reset(new WordGatherer(c));
-    L.i_status = L.wg->add(c->sp_status.p, T); L.i_meta = L.wg->add(c->sp_meta.p, 2 * T);
-    L.i_vals = L.wg->add(c->sp_vals.p, 2 * T); L.i_nlow = L.wg->add(c->ls_nlow.p, T);
-    L.wg->fetch_async();
-    k_sort_children(c, c->ls_keys.p, c->ls_rows.p, c->sp_tro.p, c->ls_cb.p, c->ls_ce.p, c->ls_tco.p, B.NC, R, T, 7, c->lm_arena.p + L.base);
+    // status, rounds, children values and sizes first, the children's member lists behind them
+    S.wg.reset(new WordGatherer(c));
+    S.i_status = S.wg->add(c->sp_status.p, T); S.i_meta = S.wg->add(c->sp_meta.p, 2 * T);
+    S.i_vals = S.wg->add(c->sp_vals.p, 2 * T); S.i_nlow = S.wg->add(c->ls_nlow.p, T);
+    S.wg->fetch_async();
+    k_sort_children(c, c->ls_keys.p, c->ls_rows.p, c->sp_tro.p, c->ls_cb.p, c->ls_ce.p, c->ls_tco.p, B.NC, R, T, 7, c->lm_arena.p + S.base);
 }
-void rule_rss_sorted_collect(LaneRun &L) {
-    const i64 T = L.B.T, d = L.x->d;
-    CutResult &out = L.cr;
-    L.wg->wait();
-    const i32 *status = L.wg->get<i32>(L.i_status), *meta = L.wg->get<i32>(L.i_meta);
-    const double *vals = L.wg->get<double>(L.i_vals);
-    std::memcpy(out.nlow.data(), L.wg->get<i32>(L.i_nlow), sizeof(i32) * T);
+void rule_rss_sorted_collect(cge_ctx *c, SplitBatch &S) {
+    const i64 T = S.B.T, d = c->d;
+    S.wg->wait();
+    const i32 *status = S.wg->get<i32>(S.i_status), *meta = S.wg->get<i32>(S.i_meta);
+    const double *vals = S.wg->get<double>(S.i_vals);
+    std::memcpy(S.nlow.data(), S.wg->get<i32>(S.i_nlow), sizeof(i32) * T);
     for (i64 t = 0; t < T; t++) {
-        Group *g = L.groups[t];
-        if (status[t] == 2) { g->rc = CGE_E_HOMOGENEOUS; out.done[t] = 1; continue; }
-        if (status[t] == 1 || meta[2 * t + 1] != 0) { out.done[t] = 0; continue; }
-        out.vlow[t] = vals[2 * t];
-        out.vhigh[t] = vals[2 * t + 1];
-        g->cmean_off = L.mbase + 2 * t * d;
+        Group *g = S.groups[t];
+        if (status[t] == 2) { g->rc = CGE_E_HOMOGENEOUS; S.done[t] = 1; continue; }
+        if (status[t] == 1 || meta[2 * t + 1] != 0) { S.done[t] = 0; continue; }
+        S.vlow[t] = vals[2 * t];
+        S.vhigh[t] = vals[2 * t + 1];
+        g->cmean_off = S.mbase + 2 * t * d;
         g->rc = CGE_OK;
-        out.done[t] = 1;
+        S.done[t] = 1;
     }
 }
 
 // split_cluster_rss2 on the device (kernels_lm.hip: rss2_walk_kernel).  The children are rank ranges of the sorted
 // order, in that order (`p[1:low]`, `p[high:end]`, src/landmarks.jl:151): the sorted rows ARE the two lists.
-void rule_rss2_enqueue(LaneRun &L) {
-    cge_ctx *c = L.x;
-    const Batch &B = L.B;
+void rule_rss2_enqueue(cge_ctx *c, SplitBatch &S) {
+    const Batch &B = S.B;
     const i64 T = B.T, R = B.R, d = c->d;
     hipStream_t st = c->stream;
     c->sp_srows.ensure(R); c->sp_zs.ensure(R); c->sp_perm.ensure(R); c->sp_status.ensure(T);
     c->sp_meta.ensure(2 * T); c->sp_vals.ensure(2 * T);
     k_segmented_sort_z(c, c->ls_z.p, c->ls_rows.p, c->ls_row_task.p, c->sp_tro.p, R, T, c->sp_zs.p, c->sp_perm.p,
                        c->sp_srows.p, c->sp_status.p, B.max_len);
-    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p + L.base, c->sp_srows.p, sizeof(i32) * R, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p + S.base, c->sp_srows.p, sizeof(i32) * R, hipMemcpyDeviceToDevice, st));
     c->r2_rows = R;
-    k_rss2_walk(c, c->Xr.p, lm_vw(c), c->sp_srows.p, c->sp_tro.p, T, d, c->sp_meta.p, c->sp_vals.p, c->lm_means.p + L.mbase);
-    L.wg.reset(new WordGatherer(c));
-    L.i_meta = L.wg->add(c->sp_meta.p, 2 * T); L.i_vals = L.wg->add(c->sp_vals.p, 2 * T);
-    L.wg->fetch_async();
+    k_rss2_walk(c, c->Xr.p, lm_vw(c), c->sp_srows.p, c->sp_tro.p, T, d, c->sp_meta.p, c->sp_vals.p, c->lm_means.p + S.mbase);
+    S.wg.reset(new WordGatherer(c));
+    S.i_meta = S.wg->add(c->sp_meta.p, 2 * T); S.i_vals = S.wg->add(c->sp_vals.p, 2 * T);
+    S.wg->fetch_async();
 }
-void rule_rss2_collect(LaneRun &L) {
-    const i64 T = L.B.T, d = L.x->d;
-    CutResult &out = L.cr;
-    L.wg->wait();
-    const i32 *meta = L.wg->get<i32>(L.i_meta);
-    const double *vals = L.wg->get<double>(L.i_vals);
+void rule_rss2_collect(cge_ctx *c, SplitBatch &S) {
+    const i64 T = S.B.T, d = c->d;
+    S.wg->wait();
+    const i32 *meta = S.wg->get<i32>(S.i_meta);
+    const double *vals = S.wg->get<double>(S.i_vals);
     for (i64 t = 0; t < T; t++) {
-        Group *g = L.groups[t];
-        out.nlow[t] = meta[2 * t] + 1; // low = ranks [0, lo], high = ranks [hi, k) with hi == lo + 1
-        out.vlow[t] = vals[2 * t];
-        out.vhigh[t] = vals[2 * t + 1];
-        g->cmean_off = L.mbase + 2 * t * d;
+        Group *g = S.groups[t];
+        S.nlow[t] = meta[2 * t] + 1; // low = ranks [0, lo], high = ranks [hi, k) with hi == lo + 1
+        S.vlow[t] = vals[2 * t];
+        S.vhigh[t] = vals[2 * t + 1];
+        g->cmean_off = S.mbase + 2 * t * d;
         g->rc = CGE_OK;
-        out.done[t] = 1;
+        S.done[t] = 1;
     }
 }
 
 // split_cluster_size / split_cluster_diameter on the device (kernels_lm.hip: cut_sides_kernel): the side of every row,
 // the children's WSSE column sums (values and means) by the side-sums pass, and the two member lists -- the rows of
 // either side in the rows' own order -- by a stable one-bit sort.
-void rule_cut_enqueue(LaneRun &L, bool use_median) {
-    cge_ctx *c = L.x;
-    const Batch &B = L.B;
-    const i64 T = B.T, R = B.R, d = c->d, width = 2 * (2 * d + 1);
+void rule_cut_enqueue(cge_ctx *c, SplitBatch &S, bool use_median) {
+    const Batch &B = S.B;
+    const i64 T = B.T, R = B.R, d = c->d;
     hipStream_t st = c->stream;
     if (use_median) { // the median needs the sorted projections
         c->sp_srows.ensure(R); c->sp_zs.ensure(R); c->sp_perm.ensure(R); c->sp_status.ensure(T);
@@ -776,7 +757,7 @@ void rule_cut_enqueue(LaneRun &L, bool use_median) {
     }
     c->ls_nlow.ensure(T);
     k_cut_sides(c, c->ls_z.p, use_median ? c->sp_zs.p : nullptr, c->sp_tro.p, T, use_median ? 1 : 0, c->ls_side.p, c->ls_nlow.p,
-                root_of(c)->cut_ties.p);
+                c->cut_ties.p);
     c->pin_res.ensure((size_t)T); // pinned: the copies do not stall the host, the event below covers them
     HIP_CHECK(hipMemcpyAsync(c->pin_res.p, c->ls_nlow.p, sizeof(i32) * T, hipMemcpyDeviceToHost, st));
     k_group_side_sums(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_side.p, c->ls_cb.p, c->ls_ce.p, B.NC, c->ls_tco.p, B.T, d,
@@ -784,40 +765,36 @@ void rule_cut_enqueue(LaneRun &L, bool use_median) {
     // the children's values and means from the sums, on the device: the means go straight into the arena (the next batch reads
     // them there), the host reads two doubles per task (round 4; it used to fetch the sums, divide and upload the means: a
     // round trip and a stream synchronisation per batch, thirty times per score with the cut rules)
-    (void)width;
     c->sp_vals.ensure(2 * T);
-    k_side_values_means(c, c->ls_sums.p, T, d, c->sp_vals.p, c->lm_means.p + L.mbase);
+    k_side_values_means(c, c->ls_sums.p, T, d, c->sp_vals.p, c->lm_means.p + S.mbase);
     c->pin_sums.ensure((size_t)2 * T);
     HIP_CHECK(hipMemcpyAsync(c->pin_sums.p, c->sp_vals.p, sizeof(double) * 2 * T, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipEventRecord(c->copy_done, st));
-    // the children's member lists last: the host already has what its heap needs and builds the next batch meanwhile
-    k_sort_children(c, c->ls_side.p, c->ls_rows.p, c->sp_tro.p, c->ls_cb.p, c->ls_ce.p, c->ls_tco.p, L.B.NC, R, T, 2, c->lm_arena.p + L.base);
+    // the children's member lists last: the host already has what its heap needs
+    k_sort_children(c, c->ls_side.p, c->ls_rows.p, c->sp_tro.p, c->ls_cb.p, c->ls_ce.p, c->ls_tco.p, B.NC, R, T, 2, c->lm_arena.p + S.base);
 }
-void rule_cut_collect(LaneRun &L) {
-    cge_ctx *c = L.x;
-    const i64 T = L.B.T, d = c->d, width = 2 * (2 * d + 1);
-    CutResult &out = L.cr;
+void rule_cut_collect(cge_ctx *c, SplitBatch &S) {
+    const i64 T = S.B.T, d = c->d;
     HIP_CHECK(hipEventSynchronize(c->copy_done));
     const double *vals = c->pin_sums.p; // (-total_rss of the two children, computed beside the means on the device)
-    std::memcpy(out.nlow.data(), c->pin_res.p, sizeof(i32) * T);
-    (void)width;
+    std::memcpy(S.nlow.data(), c->pin_res.p, sizeof(i32) * T);
     for (i64 t = 0; t < T; t++) {
-        Group *g = L.groups[t];
-        out.vlow[t] = vals[2 * t];
-        out.vhigh[t] = vals[2 * t + 1];
-        g->cmean_off = L.mbase + 2 * t * d;
+        Group *g = S.groups[t];
+        S.vlow[t] = vals[2 * t];
+        S.vhigh[t] = vals[2 * t + 1];
+        g->cmean_off = S.mbase + 2 * t * d; // (the means are in the arena already; the next batch reads them on the same stream)
         g->rc = CGE_OK;
-        out.done[t] = 1;
+        S.done[t] = 1;
     }
-    // (the means are in the arena already, written on this lane's stream; a second lane starts behind an event of this stream)
 }
 
 // The generic round-based rss path for the tasks the sorted-order kernels declined (ties at the maximum of z, NaNs):
 // their member lists and projections come to the host, rule_rss_batched runs on a sub-batch, and the children's
 // lists go back into the tasks' arena ranges.
-void rss_generic_tasks(cge_ctx *c, const Batch &B, Group *const *groups, i64 base, const std::vector<i64> &todo,
-                       CutResult &out) {
-    const i64 d = c->d, width = 2 * (2 * d + 1);
+void rss_generic_tasks(cge_ctx *c, SplitBatch &out, const std::vector<i64> &todo) {
+    const Batch &B = out.B;
+    Group *const *groups = out.groups;
+    const i64 d = c->d, width = 2 * (2 * d + 1), base = out.base;
     hipStream_t st = c->stream;
     std::vector<Group *> fg;
     std::vector<std::vector<i32>> rows(todo.size());
@@ -885,35 +862,33 @@ void rss_generic_tasks(cge_ctx *c, const Batch &B, Group *const *groups, i64 bas
     }
 }
 
-// Enqueue the split of every task of a (half) batch on L.x: mean, covariance, principal eigenvector, projection, the
-// rule's 1-D cut, the children's member lists, values and means -- no host synchronisation (except the d > 512 host
-// eigen-solver).  `after_cov` (optional): recorded behind the covariance, the point the other lane's start waits for.
-void lane_enqueue(LaneRun &L) {
-    cge_ctx *c = L.x, *root = root_of(c);
-    const i64 d = c->d, T = L.T;
+// Enqueue the split of every task of a batch: mean, covariance, principal eigenvector, projection, the rule's 1-D cut,
+// the children's member lists, values and means -- no host synchronisation (except the d > 512 host eigen-solver).
+void split_enqueue(cge_ctx *c, SplitBatch &S) {
+    const i64 d = c->d, T = S.T;
     hipStream_t st = c->stream;
-    Batch &B = L.B;
+    Batch &B = S.B;
     bool have_means = true; // known from the parents' splits: gathered from the means arena, no pass over the rows
-    for (i64 t = 0; t < T && have_means; t++) have_means = L.groups[t]->mean_off >= 0;
+    for (i64 t = 0; t < T && have_means; t++) have_means = S.groups[t]->mean_off >= 0;
     {
-        PhaseAcc pa(root, "lm_pack");
-        build_batch(c, L.groups, T, B);
+        PhaseAcc pa(c, "lm_pack");
+        build_batch(c, S.groups, T, B);
         std::vector<i64> moff;
         if (have_means) {
             moff.resize(T);
-            for (i64 t = 0; t < T; t++) moff[t] = L.groups[t]->mean_off;
+            for (i64 t = 0; t < T; t++) moff[t] = S.groups[t]->mean_off;
         }
         upload_batch(c, B, have_means ? moff.data() : nullptr);
     }
     const i64 R = B.R, NC = B.NC;
-    root->stat_lm_batches++;
-    root->stat_lm_rows += R;
-    root->stat_lm_splits += T;
+    c->stat_lm_batches++;
+    c->stat_lm_rows += R;
+    c->stat_lm_splits += T;
     c->ls_mean.ensure((size_t)T * d); c->ls_sw.ensure(T);
     c->ls_cov.ensure((size_t)T * d * d);
     c->ls_vec.ensure((size_t)T * d); c->ls_z.ensure(R);
     {
-        PhaseAcc pa(root, "lm_pca_dev");
+        PhaseAcc pa(c, "lm_pca_dev");
         double *covp = c->ls_cov.p;
         {
             ScopedKernelTimer tm(c, "group_stats");
@@ -941,51 +916,44 @@ void lane_enqueue(LaneRun &L) {
         }
     }
     // ---- the cut: children lists into the arena, sizes / values / means to the host -----------------------------
-    L.cr.nlow.assign(T, 0);
-    L.cr.vlow.assign(T, 0.0);
-    L.cr.vhigh.assign(T, 0.0);
-    L.cr.done.assign(T, 0);
-    if (L.method == CGE_METHOD_RSS) rule_rss_sorted_enqueue(L);
-    else if (L.method == CGE_METHOD_RSS2) rule_rss2_enqueue(L);
-    else rule_cut_enqueue(L, L.method == CGE_METHOD_SIZE);
+    S.nlow.assign(T, 0);
+    S.vlow.assign(T, 0.0);
+    S.vhigh.assign(T, 0.0);
+    S.done.assign(T, 0);
+    if (S.method == CGE_METHOD_RSS) rule_rss_sorted_enqueue(c, S);
+    else if (S.method == CGE_METHOD_RSS2) rule_rss2_enqueue(c, S);
+    else rule_cut_enqueue(c, S, S.method == CGE_METHOD_SIZE);
 }
 // ... and book the results when they have arrived
-void lane_collect(LaneRun &L) {
-    cge_ctx *c = L.x, *root = root_of(c);
-    const i64 T = L.T;
-    const Batch &B = L.B;
+void split_collect(cge_ctx *c, SplitBatch &S) {
+    const i64 T = S.T;
     {
-        PhaseAcc pa(root, "lm_cut");
-        if (L.method == CGE_METHOD_RSS) {
-            rule_rss_sorted_collect(L);
+        PhaseAcc pa(c, "lm_cut");
+        if (S.method == CGE_METHOD_RSS) {
+            rule_rss_sorted_collect(c, S);
             std::vector<i64> todo;
             for (i64 t = 0; t < T; t++)
-                if (!L.cr.done[t]) todo.push_back(t);
-            if (!todo.empty()) rss_generic_tasks(c, B, L.groups, L.base, todo, L.cr);
-        } else if (L.method == CGE_METHOD_RSS2)
-            rule_rss2_collect(L);
+                if (!S.done[t]) todo.push_back(t);
+            if (!todo.empty()) rss_generic_tasks(c, S, todo);
+        } else if (S.method == CGE_METHOD_RSS2)
+            rule_rss2_collect(c, S);
         else
-            rule_cut_collect(L);
+            rule_cut_collect(c, S);
     }
     for (i64 t = 0; t < T; t++) {
-        Group *g = L.groups[t];
+        Group *g = S.groups[t];
         if (g->rc != CGE_OK) continue;
-        const i64 nl = L.cr.nlow[t], nh = g->len - nl;
+        const i64 nl = S.nlow[t], nh = g->len - nl;
         if (nl <= 0 || nh <= 0) { g->rc = CGE_E_EMPTY_CLUSTER; continue; }
-        g->coff = L.base + B.task_row_off[t];
+        g->coff = S.base + S.B.task_row_off[t];
         g->nlow = nl;
-        g->vlow = nl > 1 ? L.cr.vlow[t] : DBL_EPSILON;
-        g->vhigh = nh > 1 ? L.cr.vhigh[t] : DBL_EPSILON;
+        g->vlow = nl > 1 ? S.vlow[t] : DBL_EPSILON;
+        g->vhigh = nh > 1 ? S.vhigh[t] : DBL_EPSILON;
     }
 }
 
-// Compute the split of every task, on the device.  The host only books the results.
-// TWO LANES: the chain of a batch is a dozen dependent kernels of very different character -- covariance (MFMA),
-// eigen-solver (126 dependent Householder steps: latency, most of the chip idle), projection / sort / scan / rounds (HBM
-// gathers).  A batch is therefore cut into two halves that run on two streams half a chain out of phase (the second
-// half starts when the first half's covariance is done), so one half's eigen-solver overlaps the other's memory-bound
-// kernels, and the host side of one half (tables, result parsing) overlaps the device side of the other.  The halves
-// are independent (disjoint groups, disjoint arena ranges); results do not depend on the split.
+// Compute the split of every task, on the device, one batch at a time on the context's stream; the host only books the
+// results.  Groups of one or two rows need no device work; the others go in sub-batches, each enqueued and then collected.
 void compute_splits(cge_ctx *c, std::vector<Group *> &tasks, int method) {
     const i64 d = c->d;
     std::vector<Group *> big;
@@ -1014,24 +982,20 @@ void compute_splits(cge_ctx *c, std::vector<Group *> &tasks, int method) {
     const i64 max_tasks = std::max<i64>(1, (i64)(1ull << 27) / (d * d));
     for (size_t b0 = 0; b0 < big.size(); b0 += (size_t)max_tasks) {
         const size_t b1 = std::min(big.size(), b0 + (size_t)max_tasks);
-        LaneRun L;
-        L.x = c;
-        L.groups = &big[b0];
-        L.T = (i64)(b1 - b0);
-        L.method = method;
+        SplitBatch S;
+        S.groups = &big[b0];
+        S.T = (i64)(b1 - b0);
+        S.method = method;
         i64 r = 0;
-        for (i64 t = 0; t < L.T; t++) r += L.groups[t]->len;
-        L.base = arena_alloc(c, r); // the children of task t: [base + task_row_off[t], + len)
-        L.mbase = means_alloc(c, 2 * L.T * d);
-        lane_enqueue(L);
-        lane_collect(L);
+        for (i64 t = 0; t < S.T; t++) r += S.groups[t]->len;
+        S.base = arena_alloc(c, r); // the children of task t: [base + task_row_off[t], + len)
+        S.mbase = means_alloc(c, 2 * S.T * d);
+        split_enqueue(c, S);
+        split_collect(c, S);
     }
 }
 
-// N > 1, option shard_rows: a group's rows live on ONE rank (its community's owner), which computes the split; what the
-// replicated heap needs of it -- status, size of the low child, the two children's values: four 8-byte words per group --
-// is gathered by one all-reduce into a zero-filled buffer (op 2: integer sum of the words, exact).  The member lists, the
-// means and the arena offsets never leave the owner.
+// ---- N > 1: what the ranks exchange during runsplit ----------------------------------------------------------------
 // Owner-only work between two collectives must not leave the other ranks waiting in the next one: an error raised by it is
 // caught (guarded_work), travels with the words of that exchange -- one slot per rank behind them -- and AFTER the exchange
 // every rank throws: the failing rank its own error, the others the same code ("every rank leaves by the same door").
@@ -1046,7 +1010,17 @@ static void throw_if_a_rank_failed(cge_ctx *c, const RankError &mine, const doub
         if (slots[r] != 0.0)
             CGE_THROW((int)slots[r], "%s: rank %d failed with code %d (its message is on that rank); every rank stops here", where, r, (int)slots[r]);
 }
-void exchange_group_words(cge_ctx *c, std::vector<double> &w);
+// in: this rank's words, zeros elsewhere; out: everybody's (op 2: integer sum of the words, exact; op 1: maximum)
+void exchange_group_words(cge_ctx *c, std::vector<double> &w, int op = 2) {
+    if (w.empty()) return;
+    PhaseAcc px(c, "lm_exchange");
+    DevBuf<double> &X = c->samp_xchg; // (free during the landmark phase)
+    X.ensure(w.size());
+    HIP_CHECK(hipMemcpyAsync(X.p, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, c->stream));
+    cge_allreduce_dev(c, X.p, (i64)w.size(), op);
+    HIP_CHECK(hipMemcpyAsync(w.data(), X.p, sizeof(double) * w.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
 // the exchange of exchange_group_words with the ranks' verdicts behind the words
 static void exchange_group_words_checked(cge_ctx *c, std::vector<double> &w, const RankError &mine, const char *where) {
     const size_t n0 = w.size();
@@ -1058,16 +1032,74 @@ static void exchange_group_words_checked(cge_ctx *c, std::vector<double> &w, con
     w.resize(n0);
     throw_if_a_rank_failed(c, mine, slots.data(), where);
 }
-void exchange_group_words(cge_ctx *c, std::vector<double> &w) { // in: this rank's words, zeros elsewhere; out: everybody's
-    if (w.empty()) return;
-    PhaseAcc px(c, "lm_exchange");
-    DevBuf<double> &X = c->samp_xchg; // (free during the landmark phase)
-    X.ensure(w.size());
-    HIP_CHECK(hipMemcpyAsync(X.p, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, c->stream));
-    cge_allreduce_dev(c, X.p, (i64)w.size(), 2);
-    HIP_CHECK(hipMemcpyAsync(w.data(), X.p, sizeof(double) * w.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-}
+
+// Gather group records over the ranks: the exchange of groups that were split on different ranks (a sharded batch of the
+// global phase, the forced phase split over the ranks).  Every rank enters what it owns into the zero-filled exchange
+// buffer, one all-reduce (op 2: integer sum of the words, exact) gives every rank everything.  The buffer, in doubles:
+//   [ member words: (rows + 1) / 2 ][ counts: n_counts ][ n_rec records of n_scal scalars + n_mean means doubles ][ W verdicts ]
+// The caller decides who owns what and rebuilds its groups from the gathered records.
+struct GroupGather {
+    i64 rows = 0, n_counts = 0, n_rec = 0, n_scal = 0, n_mean = 0;
+    std::vector<double> counts, scal; // in: this rank's leading counts and record scalars, zeros elsewhere; out: everybody's
+    std::vector<i64> seg;             // per owned member list: offset in the member arena, position among the member words, length
+    std::vector<i64> moff, mslot;     // per owned means block (n_mean doubles): offset in the means arena, record
+    i64 per() const { return n_scal + n_mean; }
+    i64 words() const { return (rows + 1) / 2 + n_counts + n_rec * per(); } // (the W verdict slots come on top)
+    // valid after run(), on the device: everybody's member lists and records
+    i32 *members(cge_ctx *c) const { return reinterpret_cast<i32 *>(c->xptr); }
+    double *records(cge_ctx *c) const { return c->xptr + (rows + 1) / 2 + n_counts; }
+    void shape(i64 rows_, i64 n_counts_, i64 n_rec_, i64 n_scal_, i64 n_mean_) {
+        rows = rows_; n_counts = n_counts_; n_rec = n_rec_; n_scal = n_scal_; n_mean = n_mean_;
+        counts.assign((size_t)n_counts, 0.0);
+        scal.assign((size_t)(n_rec * n_scal), 0.0);
+    }
+    // `mine`: what this rank's work before the exchange raised; a failing rank enters its verdict only
+    void run(cge_ctx *c, const RankError &mine, const char *where) {
+        const i64 W = c->coll.world, need = words();
+        hipStream_t st = c->stream;
+        double *X = c->xptr, *Mc = X + (rows + 1) / 2, *Mg = records(c);
+        HIP_CHECK(hipMemsetAsync(X, 0, sizeof(double) * (need + W), st));
+        const double my_verdict = (double)mine.code;
+        DevBuf<i64> d_seg, d_moff;
+        if (mine.code)
+            HIP_CHECK(hipMemcpyAsync(X + need + c->coll.rank, &my_verdict, sizeof(double), hipMemcpyHostToDevice, st));
+        else {
+            if (!seg.empty()) {
+                d_seg.ensure(seg.size());
+                HIP_CHECK(hipMemcpyAsync(d_seg.p, seg.data(), sizeof(i64) * seg.size(), hipMemcpyHostToDevice, st));
+                k_copy_segments(c, c->lm_arena.p, d_seg.p, (i64)seg.size() / 3, members(c));
+            }
+            if (n_counts > 0) HIP_CHECK(hipMemcpyAsync(Mc, counts.data(), sizeof(double) * n_counts, hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpy2DAsync(Mg, sizeof(double) * per(), scal.data(), sizeof(double) * n_scal, sizeof(double) * n_scal,
+                                       (size_t)n_rec, hipMemcpyHostToDevice, st));
+            if (!moff.empty()) {
+                const size_t nq = moff.size();
+                d_moff.ensure(2 * nq);
+                HIP_CHECK(hipMemcpyAsync(d_moff.p, moff.data(), sizeof(i64) * nq, hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(d_moff.p + nq, mslot.data(), sizeof(i64) * nq, hipMemcpyHostToDevice, st));
+                k_gather_means_slots(c, c->lm_means.p, d_moff.p, d_moff.p + nq, (i64)nq, n_mean, per(), n_scal, Mg);
+            }
+        }
+        cge_allreduce_dev(c, X, need + W, 2);
+        std::vector<double> slots((size_t)W);
+        HIP_CHECK(hipMemcpyAsync(slots.data(), X + need, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+        if (n_counts > 0) HIP_CHECK(hipMemcpyAsync(counts.data(), Mc, sizeof(double) * n_counts, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpy2DAsync(scal.data(), sizeof(double) * n_scal, Mg, sizeof(double) * per(), sizeof(double) * n_scal,
+                                   (size_t)n_rec, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // (also: the staging of seg / moff is done with)
+        throw_if_a_rank_failed(c, mine, slots.data(), where);
+    }
+    // the gathered means blocks, record by record, into the means arena at `mbase`
+    void means_to_arena(cge_ctx *c, i64 mbase) const {
+        HIP_CHECK(hipMemcpy2DAsync(c->lm_means.p + mbase, sizeof(double) * n_mean, records(c) + n_scal, sizeof(double) * per(),
+                                   sizeof(double) * n_mean, (size_t)n_rec, hipMemcpyDeviceToDevice, c->stream));
+    }
+};
+
+// N > 1, option shard_rows: a group's rows live on ONE rank (its community's owner), which computes the split; what the
+// replicated heap needs of it -- status, size of the low child, the two children's values: four 8-byte words per group --
+// is gathered by one all-reduce into a zero-filled buffer (op 2: integer sum of the words, exact).  The member lists, the
+// means and the arena offsets never leave the owner.
 void compute_splits_rowsharded(cge_ctx *c, std::vector<Group *> &batch, int method) {
     const i64 T = (i64)batch.size();
     const int me = c->coll.rank;
@@ -1100,34 +1132,41 @@ void compute_splits_rowsharded(cge_ctx *c, std::vector<Group *> &batch, int meth
     }
 }
 
+// Longest first, each to the least loaded rank (deterministic): owner[i] of W ranks for items of these lengths.
+std::vector<int> balance_over_ranks(const std::vector<i64> &len, i64 W) {
+    const i64 T = (i64)len.size();
+    std::vector<i64> ord(T), load(W, 0);
+    std::vector<int> owner(T, 0);
+    for (i64 t = 0; t < T; t++) ord[t] = t;
+    std::stable_sort(ord.begin(), ord.end(), [&](i64 a, i64 b) { return len[a] > len[b]; });
+    for (i64 t : ord) {
+        const int r = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+        owner[t] = r;
+        load[r] += len[t];
+    }
+    return owner;
+}
+
 // N > 1, global phase: the groups of a batch are independent, so every rank cuts its share (longest first, each to the
 // least loaded rank) and the results -- status, cut position, children values, children member lists and means -- are
-// gathered by one all-reduce into zero-filled buffers (hook op 2, exact).  EVERY rank, owner or not, then re-allocates the
-// children ranges and means in the batch's order and takes the gathered values: all ranks stay in identical state.
+// gathered (GroupGather).  EVERY rank, owner or not, then re-allocates the children ranges and means in the batch's order
+// and takes the gathered values: all ranks stay in identical state.
 // Worth it only for batches with enough rows to outweigh the exchange.
 void compute_splits_sharded(cge_ctx *c, std::vector<Group *> &batch, int method) {
     if (c->rows_sharded) { compute_splits_rowsharded(c, batch, method); return; }
     const i64 W = c->has_coll ? c->coll.world : 1, d = c->d, T = (i64)batch.size();
-    i64 R = 0;
-    for (Group *g : batch) R += g->len;
-    const i64 s_words = (R + 1) / 2, m_per = 5 + 2 * d; // per group: rc, nlow, vlow, vhigh, means flag, two means
-    const i64 x_need = s_words + T * m_per;
+    std::vector<i64> len(T), prefix(T + 1, 0);
+    for (i64 t = 0; t < T; t++) { len[t] = batch[t]->len; prefix[t + 1] = prefix[t] + len[t]; }
+    const i64 R = prefix[T];
+    GroupGather G;
+    G.shape(R, 0, T, 5, 2 * d); // per group: rc, nlow, vlow, vhigh, means flag, two means
     // (option value 2: every batch, whatever its size -- the tests)
     if (W <= 1 || !c->opt_shard_forced || (c->opt_shard_forced == 1 && (T < 2 * W || R * d < ((i64)1 << 23))) ||
-        !cge_exchange_fits(c, (size_t)(x_need + W))) {
+        !cge_exchange_fits(c, (size_t)(G.words() + W))) {
         compute_splits(c, batch, method);
         return;
     }
-    hipStream_t st = c->stream;
-    std::vector<i64> ord(T), load(W, 0), prefix(T + 1, 0);
-    std::vector<int> owner(T, 0);
-    for (i64 t = 0; t < T; t++) { ord[t] = t; prefix[t + 1] = prefix[t] + batch[t]->len; }
-    std::stable_sort(ord.begin(), ord.end(), [&](i64 a, i64 b) { return batch[a]->len > batch[b]->len; });
-    for (i64 t : ord) {
-        const int r = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        owner[t] = r;
-        load[r] += batch[t]->len;
-    }
+    const std::vector<int> owner = balance_over_ranks(len, W);
     const int me = c->coll.rank;
     const i64 A0 = c->lm_arena_used, M0 = c->lm_means_used;
     std::vector<Group *> mine;
@@ -1135,79 +1174,37 @@ void compute_splits_sharded(cge_ctx *c, std::vector<Group *> &batch, int method)
         if (owner[t] == me) mine.push_back(batch[t]);
     const RankError err = guarded_work([&] { if (!mine.empty()) compute_splits(c, mine, method); });
     PhaseAcc px(c, "lm_exchange");
-    double *X = c->xptr;
-    i32 *S = reinterpret_cast<i32 *>(X);
-    double *Mg = X + s_words;
-    HIP_CHECK(hipMemsetAsync(X, 0, sizeof(double) * (x_need + W), st)); // (W verdict slots behind the words)
-    const double my_verdict = (double)err.code;
-    if (err.code) HIP_CHECK(hipMemcpyAsync(X + x_need + me, &my_verdict, sizeof(double), hipMemcpyHostToDevice, st));
-    std::vector<i64> seg, moff, mslot;
-    std::vector<double> hg((size_t)T * 5, 0.0);
     for (i64 t = 0; t < T && !err.code; t++) {
         if (owner[t] != me) continue;
-        Group *g = batch[t];
-        hg[5 * t] = (double)g->rc;
+        const Group *g = batch[t];
+        double *rec = &G.scal[5 * t];
+        rec[0] = (double)g->rc;
         if (g->rc != CGE_OK) continue;
-        hg[5 * t + 1] = (double)g->nlow;
-        hg[5 * t + 2] = g->vlow;
-        hg[5 * t + 3] = g->vhigh;
-        hg[5 * t + 4] = g->cmean_off >= 0 ? 1.0 : 0.0;
-        seg.push_back(g->coff); seg.push_back(prefix[t]); seg.push_back(g->len);
-        if (g->cmean_off >= 0) { // the two means are adjacent in the means arena: two rows of d for the gather kernel
-            moff.push_back(g->cmean_off); mslot.push_back(2 * t);
-            moff.push_back(g->cmean_off + d); mslot.push_back(2 * t + 1);
-        }
+        rec[1] = (double)g->nlow;
+        rec[2] = g->vlow;
+        rec[3] = g->vhigh;
+        rec[4] = g->cmean_off >= 0 ? 1.0 : 0.0;
+        G.seg.push_back(g->coff); G.seg.push_back(prefix[t]); G.seg.push_back(g->len);
+        if (g->cmean_off >= 0) { G.moff.push_back(g->cmean_off); G.mslot.push_back(t); } // low and high are adjacent: one block of 2d
     }
-    DevBuf<i64> d_seg, d_moff;
-    if (!seg.empty()) {
-        d_seg.ensure(seg.size());
-        HIP_CHECK(hipMemcpyAsync(d_seg.p, seg.data(), sizeof(i64) * seg.size(), hipMemcpyHostToDevice, st));
-        k_copy_segments(c, c->lm_arena.p, d_seg.p, (i64)seg.size() / 3, S);
-    }
-    HIP_CHECK(hipMemcpy2DAsync(Mg, sizeof(double) * m_per, hg.data(), sizeof(double) * 5, sizeof(double) * 5, (size_t)T,
-                               hipMemcpyHostToDevice, st));
-    if (!moff.empty()) { // slot q = 2t + (0 low / 1 high) -> Mg + t * m_per + 5 + (q & 1) * d: stride d over a view that starts at
-        // Mg + 5 only works when m_per == 2d; use the generic form: one record per HALF group of stride m_per / 2 is not
-        // integral, so the kernel gets (slot, stride, lead) per row through two launches (low halves, high halves)
-        std::vector<i64> off_lo, off_hi, slot_t;
-        for (size_t q = 0; q < moff.size(); q += 2) { off_lo.push_back(moff[q]); off_hi.push_back(moff[q + 1]); slot_t.push_back(mslot[q] / 2); }
-        const size_t nq = slot_t.size();
-        d_moff.ensure(3 * nq);
-        HIP_CHECK(hipMemcpyAsync(d_moff.p, off_lo.data(), sizeof(i64) * nq, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(d_moff.p + nq, off_hi.data(), sizeof(i64) * nq, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(d_moff.p + 2 * nq, slot_t.data(), sizeof(i64) * nq, hipMemcpyHostToDevice, st));
-        k_gather_means_slots(c, c->lm_means.p, d_moff.p, d_moff.p + 2 * nq, (i64)nq, d, m_per, 5, Mg);
-        k_gather_means_slots(c, c->lm_means.p, d_moff.p + nq, d_moff.p + 2 * nq, (i64)nq, d, m_per, 5 + d, Mg);
-        HIP_CHECK(hipStreamSynchronize(st)); // off_lo / off_hi / slot_t go out of scope
-    }
-    cge_allreduce_dev(c, X, x_need + W, 2);
-    {
-        std::vector<double> slots((size_t)W);
-        HIP_CHECK(hipMemcpyAsync(slots.data(), X + x_need, sizeof(double) * W, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        throw_if_a_rank_failed(c, err, slots.data(), "runsplit (sharded batch)");
-    }
+    G.run(c, err, "runsplit (sharded batch)");
     // every rank: the same ranges and means in the batch's order, the gathered values
     c->lm_arena_used = A0;
     c->lm_means_used = M0;
     const i64 base = arena_alloc(c, R), mbase = means_alloc(c, T * 2 * d);
-    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p + base, S, sizeof(i32) * R, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpy2DAsync(c->lm_means.p + mbase, sizeof(double) * 2 * d, Mg + 5, sizeof(double) * m_per, sizeof(double) * 2 * d,
-                               (size_t)T, hipMemcpyDeviceToDevice, st));
-    std::vector<double> all((size_t)T * 5);
-    HIP_CHECK(hipMemcpy2DAsync(all.data(), sizeof(double) * 5, Mg, sizeof(double) * m_per, sizeof(double) * 5, (size_t)T,
-                               hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p + base, G.members(c), sizeof(i32) * R, hipMemcpyDeviceToDevice, c->stream));
+    G.means_to_arena(c, mbase);
     for (i64 t = 0; t < T; t++) {
         Group *g = batch[t];
+        const double *rec = &G.scal[5 * t];
         g->has_split = true;
-        g->rc = (int)all[5 * t];
+        g->rc = (int)rec[0];
         if (g->rc != CGE_OK) continue;
         g->coff = base + prefix[t];
-        g->nlow = (i64)all[5 * t + 1];
-        g->vlow = all[5 * t + 2];
-        g->vhigh = all[5 * t + 3];
-        g->cmean_off = all[5 * t + 4] != 0.0 ? mbase + t * 2 * d : -1;
+        g->nlow = (i64)rec[1];
+        g->vlow = rec[2];
+        g->vhigh = rec[3];
+        g->cmean_off = rec[4] != 0.0 ? mbase + t * 2 * d : -1;
     }
 }
 
@@ -1229,7 +1226,6 @@ void materialise_children(std::vector<Group *> &tasks, GroupPool &pool, i64 c_d)
         g->clo->len = g->nlow;
         g->clo->value = g->vlow;
         g->clo->mean_off = g->cmean_off;
-        g->clo->parent = g;
         g->clo->owner = g->owner;
         pool.emplace_back();
         g->chi = &pool.back();
@@ -1237,7 +1233,6 @@ void materialise_children(std::vector<Group *> &tasks, GroupPool &pool, i64 c_d)
         g->chi->len = g->len - g->nlow;
         g->chi->value = g->vhigh;
         g->chi->mean_off = g->cmean_off >= 0 ? g->cmean_off + c_d : -1;
-        g->chi->parent = g;
         g->chi->owner = g->owner;
     }
 }
@@ -1262,69 +1257,70 @@ void advance_heaps(cge_ctx *c, std::vector<Heap *> &heaps, const std::vector<i64
     std::vector<Group *> frontier, stack, keep; // (reused by every round: no allocation per round)
     std::vector<double> vals;
     for (;;) {
-        PhaseAcc *ph = new PhaseAcc(c, "lm_heap"); // replay + choice of the next batch (host)
         std::vector<Group *> batch;
-        for (size_t q = 0; q < heaps.size(); q++) {
-            Heap &h = *heaps[q];
-            while ((i64)h.len() < targets[q] && h.top()->has_split) replay_one(h);
-            if ((i64)h.len() >= targets[q]) continue;
-            if (!speculate) {
-                batch.push_back(h.top());
-                continue;
-            }
-            const i64 remaining = targets[q] - (i64)h.len();
-            frontier.clear(); stack.clear(); vals.clear();
-            // Exactly `remaining` more pops will happen.  A node can only be among them if its value ranks within
-            // `remaining` among ALL known unpopped nodes (cached splits and unsplit ones alike): nodes still to be
-            // discovered only add competitors.  So every unsplit node above that threshold is a candidate and
-            // every one below it is certainly never popped.
-            for (size_t i = 1; i <= h.len(); i++) stack.push_back(h.at(i));
-            while (!stack.empty()) {
-                Group *g = stack.back();
-                stack.pop_back();
-                if (g->len > 1 || g == h.top() || g->has_split) vals.push_back(g->value);
-                if (!g->has_split) {
-                    if (g->len > 1 || g == h.top()) frontier.push_back(g);
-                } else if (g->rc == CGE_OK) {
-                    stack.push_back(g->clo);
-                    stack.push_back(g->chi);
+        {
+            PhaseAcc ph(c, "lm_heap"); // replay + choice of the next batch (host)
+            for (size_t q = 0; q < heaps.size(); q++) {
+                Heap &h = *heaps[q];
+                while ((i64)h.len() < targets[q] && h.top()->has_split) replay_one(h);
+                if ((i64)h.len() >= targets[q]) continue;
+                if (!speculate) {
+                    batch.push_back(h.top());
+                    continue;
                 }
+                const i64 remaining = targets[q] - (i64)h.len();
+                frontier.clear(); stack.clear(); vals.clear();
+                // Exactly `remaining` more pops will happen.  A node can only be among them if its value ranks within
+                // `remaining` among ALL known unpopped nodes (cached splits and unsplit ones alike): nodes still to be
+                // discovered only add competitors.  So every unsplit node above that threshold is a candidate and
+                // every one below it is certainly never popped.
+                for (size_t i = 1; i <= h.len(); i++) stack.push_back(h.at(i));
+                while (!stack.empty()) {
+                    Group *g = stack.back();
+                    stack.pop_back();
+                    if (g->len > 1 || g == h.top() || g->has_split) vals.push_back(g->value);
+                    if (!g->has_split) {
+                        if (g->len > 1 || g == h.top()) frontier.push_back(g);
+                    } else if (g->rc == CGE_OK) {
+                        stack.push_back(g->clo);
+                        stack.push_back(g->chi);
+                    }
+                }
+                if (frontier.empty()) continue;
+                double thr = INFINITY;
+                if ((i64)vals.size() > remaining) {
+                    std::nth_element(vals.begin(), vals.begin() + (remaining - 1), vals.end());
+                    thr = vals[remaining - 1];
+                }
+                {
+                    keep.clear();
+                    for (Group *g : frontier)
+                        if (g->value <= thr || g == h.top()) keep.push_back(g);
+                    frontier.swap(keep);
+                }
+                // Every candidate COULD be popped, but a good half of a large frontier never is (its competitors' children
+                // outrank it).  Splitting only the most valuable part per round costs a round or two more and saves the
+                // eigen-problems of the rest; what is left over is reconsidered, with more known, in the next round.
+                // (never fewer than 256 at a time: the last pops would otherwise trickle through many tiny rounds)
+                const int spec_pct = (method == CGE_METHOD_SIZE || method == CGE_METHOD_DIAMETER) ? 10
+                                     : (c->d > 128 ? 25 : 40); // wide embeddings: a wasted split costs a memory-resident eigen-problem
+                i64 take = std::max<i64>(std::min<i64>(remaining, 256), (i64)((double)remaining * spec_pct / 100.0));
+                // The register-resident eigen-solver of 64 < d <= 128 holds two matrices per CU: 512 at a time, and a batch of 800
+                // costs two rounds (0.98 ms) where 512 cost one (0.51).  The batch is cut DOWN to a multiple of 512: one round more
+                // at the headline (8 batches), eigen-solver 4.7 -> 4.0 ms, landmarks 13.1 -> 12.3 ms (rounding up: 13.6).
+                if (c->d > 64 && c->d <= 128 && take > 512) take = take / 512 * 512;
+                if ((i64)frontier.size() > take) {
+                    std::nth_element(frontier.begin(), frontier.begin() + (take - 1), frontier.end(),
+                                     [](const Group *a, const Group *b) { return a->value < b->value; });
+                    const double cut = frontier[take - 1]->value;
+                    keep.clear();
+                    for (Group *g : frontier)
+                        if (g->value <= cut || g == h.top()) keep.push_back(g);
+                    frontier.swap(keep);
+                }
+                batch.insert(batch.end(), frontier.begin(), frontier.end());
             }
-            if (frontier.empty()) continue;
-            double thr = INFINITY;
-            if ((i64)vals.size() > remaining) {
-                std::nth_element(vals.begin(), vals.begin() + (remaining - 1), vals.end());
-                thr = vals[remaining - 1];
-            }
-            {
-                keep.clear();
-                for (Group *g : frontier)
-                    if (g->value <= thr || g == h.top()) keep.push_back(g);
-                frontier.swap(keep);
-            }
-            // Every candidate COULD be popped, but a good half of a large frontier never is (its competitors' children
-            // outrank it).  Splitting only the most valuable part per round costs a round or two more and saves the
-            // eigen-problems of the rest; what is left over is reconsidered, with more known, in the next round.
-            // (never fewer than 256 at a time: the last pops would otherwise trickle through many tiny rounds)
-            const int spec_pct = (method == CGE_METHOD_SIZE || method == CGE_METHOD_DIAMETER) ? 10
-                                 : (c->d > 128 ? 25 : 40); // wide embeddings: a wasted split costs a memory-resident eigen-problem
-            i64 take = std::max<i64>(std::min<i64>(remaining, 256), (i64)((double)remaining * spec_pct / 100.0));
-            // The register-resident eigen-solver of 64 < d <= 128 holds two matrices per CU: 512 at a time, and a batch of 800
-            // costs two rounds (0.98 ms) where 512 cost one (0.51).  The batch is cut DOWN to a multiple of 512: one round more
-            // at the headline (8 batches), eigen-solver 4.7 -> 4.0 ms, landmarks 13.1 -> 12.3 ms (rounding up: 13.6).
-            if (c->d > 64 && c->d <= 128 && take > 512) take = take / 512 * 512;
-            if ((i64)frontier.size() > take) {
-                std::nth_element(frontier.begin(), frontier.begin() + (take - 1), frontier.end(),
-                                 [](const Group *a, const Group *b) { return a->value < b->value; });
-                const double cut = frontier[take - 1]->value;
-                keep.clear();
-                for (Group *g : frontier)
-                    if (g->value <= cut || g == h.top()) keep.push_back(g);
-                frontier.swap(keep);
-            }
-            batch.insert(batch.end(), frontier.begin(), frontier.end());
         }
-        delete ph;
         if (batch.empty()) break;
         if (speculate) compute_splits_sharded(c, batch, method); // the global phase (N > 1: split over the ranks)
         else compute_splits(c, batch, method);
@@ -1333,337 +1329,278 @@ void advance_heaps(cge_ctx *c, std::vector<Heap *> &heaps, const std::vector<i64
     }
 }
 
-} // namespace
+// ---- runsplit, stage by stage ------------------------------------------------------------------------------------
+// Where the initial clusters went: a_off[q] = where cluster q starts in this rank's member arena (-1: another rank's
+// rows), owner[q] = the rank that holds its rows (0 when every rank holds all rows).
+struct StagedClusters {
+    std::vector<i64> a_off;
+    std::vector<int> owner;
+};
+// The local heap of a community beyond `forced` (:282-313).  The forced phase leaves `out`: its groups in pop order, the
+// order in which the global heap receives them (:309-312).
+struct Local {
+    Heap h;
+    i64 cidx = 0;  // the cluster
+    int owner = 0; // the rank that runs this heap
+    std::vector<Group *> out;
+    void drain() { while (h.len() > 0) out.push_back(h.pop()); }
+};
 
-// group_ids[i] = 0-based group (= heap position - 1) of vertex i; also leaves on the device c->v2l (the same, int32)
-// and the landmark -> members index c->lm_memoff / c->lm_mem (ascending inside a landmark), mirrored in
-// c->h_mem_off / c->h_mem when `want_index`.
-void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
-                   std::vector<i64> &group_ids, bool want_index) {
-    const i64 n = c->n, d = c->d;
-    hipStream_t st = c->stream;
-    const bool RS = c->rows_sharded; // option shard_rows: this rank holds (and splits) the rows of its own communities only
-    const int me = RS ? c->coll.rank : 0;
-    if (!c->Xr.p || c->Xr.n < (size_t)(lm_rows(c) * d) || (i64)c->h_vw.size() != n)
-        CGE_THROW(CGE_E_ARG, "runsplit: embedding / vertex weights are not resident");
-    GroupPool pool;
-    Heap H;
-    PhaseAcc *pinit = new PhaseAcc(c, "lm_init");
-    // sort(initial_clusters): lexicographic (:281)
+// sort(initial_clusters): lexicographic (:281)
+std::vector<i64> sorted_cluster_order(const i64 *cl_flat, const i64 *cl_off, i64 ncl) {
     std::vector<i64> order(ncl);
     for (i64 i = 0; i < ncl; i++) order[i] = i;
     std::sort(order.begin(), order.end(), [&](i64 a, i64 b) {
         return std::lexicographical_compare(cl_flat + cl_off[a], cl_flat + cl_off[a + 1], cl_flat + cl_off[b],
                                             cl_flat + cl_off[b + 1]);
     });
-    // the member arena starts as the clusters themselves (0-based), cluster q at cl_off[q]
-    const i64 total = cl_off[ncl];
-    c->lm_arena_used = 0;
-    c->lm_means_used = 0;
-    c->stat_lm_batches = c->stat_lm_rows = c->stat_lm_splits = 0;
-    c->cut_ties.ensure(1);
-    HIP_CHECK(hipMemsetAsync(c->cut_ties.p, 0, sizeof(int), c->stream));
-    // option shard_rows: cl_owner[q] = the rank that holds cluster q's rows (the owner of its first member's community; a
-    // cluster has to lie inside one rank's rows), a_off[q] = where an OWNED cluster starts in this rank's arena (local ids)
-    std::vector<int> cl_owner;
-    std::vector<i64> a_off_v;
-    if (RS) {
-        cl_owner.assign(ncl, 0);
-        a_off_v.assign(ncl + 1, 0);
-        int bad = 0;
-        for (i64 q = 0; q < ncl; q++) {
-            a_off_v[q + 1] = a_off_v[q];
-            if (cl_off[q + 1] <= cl_off[q]) continue;
-            const i64 v0 = cl_flat[cl_off[q]];
-            if (v0 < 1 || v0 > n) { bad = 1; continue; }
-            cl_owner[q] = c->comm_owner[c->h_comm[v0 - 1]];
-            if (cl_owner[q] == me) a_off_v[q + 1] += cl_off[q + 1] - cl_off[q];
-        }
-        c->pin_rows[0].ensure(std::max<i64>(a_off_v[ncl], 1));
-        i32 *stage = c->pin_rows[0].p;
-        std::atomic<int> abad{bad};
-        parallel_for(c, ncl, [&](i64 q) {
-            const bool mine = cl_owner[q] == me;
-            for (i64 t = cl_off[q]; t < cl_off[q + 1]; t++) {
-                const i64 v = cl_flat[t];
-                if (v < 1 || v > n) { abad.store(1); continue; }
-                const i32 l = c->h_glob2loc[v - 1];
-                if (mine != (l >= 0)) { abad.store(2); continue; } // a cluster that spans two ranks' rows
-                if (mine) stage[a_off_v[q] + (t - cl_off[q])] = l;
-            }
-        });
-        // every rank must leave by the same door: the verdicts are exchanged before anybody throws
-        std::vector<double> verdict(1, (double)abad.load());
-        {
-            DevBuf<double> &X = c->samp_xchg;
-            X.ensure(1);
-            HIP_CHECK(hipMemcpyAsync(X.p, verdict.data(), sizeof(double), hipMemcpyHostToDevice, st));
-            cge_allreduce_dev(c, X.p, 1, 1);
-            HIP_CHECK(hipMemcpyAsync(verdict.data(), X.p, sizeof(double), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
-        if (verdict[0] == 1.0) CGE_THROW(CGE_E_ARG, "cluster member out of range 1..%lld", (long long)n);
-        if (verdict[0] != 0.0)
-            CGE_THROW(CGE_E_ARG, "option shard_rows: a cluster spans the rows of two ranks (the rows are sharded by the community "
-                                 "vector of cge_set_vertex_data: clusters must refine it)");
-        if (a_off_v[ncl] > 0) {
-            arena_alloc(c, a_off_v[ncl]);
-            HIP_CHECK(hipMemcpyAsync(c->lm_arena.p, stage, sizeof(i32) * a_off_v[ncl], hipMemcpyHostToDevice, st));
-        }
-    } else {
-        c->pin_rows[0].ensure(total);
-        i32 *stage = c->pin_rows[0].p;
-        std::atomic<int> bad{0};
-        parallel_for(c, 64, [&](i64 part) {
-            for (i64 q = total * part / 64; q < total * (part + 1) / 64; q++) {
-                if (cl_flat[q] < 1 || cl_flat[q] > n) { bad.store(1); continue; }
-                stage[q] = (i32)(cl_flat[q] - 1);
-            }
-        });
-        if (bad.load()) CGE_THROW(CGE_E_ARG, "cluster member out of range 1..%lld", (long long)n);
-        arena_alloc(c, total);
-        HIP_CHECK(hipMemcpyAsync(c->lm_arena.p, stage, sizeof(i32) * total, hipMemcpyHostToDevice, st));
-    }
-    // where cluster q starts in this rank's arena (-1: another rank's rows)
-    auto a_off = [&](i64 q) -> i64 { return !RS ? cl_off[q] : (cl_owner[q] == me ? a_off_v[q] : -1); };
+    return order;
+}
 
-    // ---- forced per-community phase (:282-313): every big community owns a local heap -----------
-    struct Local { Heap h; i64 pos; };
-    std::vector<Local> locals;
-    bool sharded_forced = false;
-    // global-heap insertion order must follow the sorted community order, so first split all the
-    // local heaps (independent of each other), then insert community by community.
+// The member arena starts as the clusters themselves (0-based), cluster q at cl_off[q].
+StagedClusters stage_clusters(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl) {
+    const i64 n = c->n, total = cl_off[ncl];
+    c->pin_clusters.ensure(total);
+    i32 *stage = c->pin_clusters.p;
+    std::atomic<int> bad{0};
+    parallel_for(c, 64, [&](i64 part) {
+        for (i64 q = total * part / 64; q < total * (part + 1) / 64; q++) {
+            if (cl_flat[q] < 1 || cl_flat[q] > n) { bad.store(1); continue; }
+            stage[q] = (i32)(cl_flat[q] - 1);
+        }
+    });
+    if (bad.load()) CGE_THROW(CGE_E_ARG, "cluster member out of range 1..%lld", (long long)n);
+    arena_alloc(c, total);
+    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p, stage, sizeof(i32) * total, hipMemcpyHostToDevice, c->stream));
+    return StagedClusters{std::vector<i64>(cl_off, cl_off + ncl), std::vector<int>(ncl, 0)};
+}
+// Option shard_rows: this rank holds (and splits) the rows of its own communities only.  A cluster belongs to the owner of
+// its first member's community and has to lie inside that rank's rows; the owned clusters go into the arena back to back,
+// as local row ids.
+StagedClusters stage_clusters_rowsharded(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl) {
+    const i64 n = c->n;
+    const int me = c->coll.rank;
+    StagedClusters sc{std::vector<i64>(ncl, -1), std::vector<int>(ncl, 0)};
+    std::vector<i64> at(ncl + 1, 0); // where an OWNED cluster starts
+    int bad = 0;
     for (i64 q = 0; q < ncl; q++) {
-        const i64 cidx = order[q], len = cl_off[cidx + 1] - cl_off[cidx];
-        if (len > forced) {
-            locals.push_back(Local{Heap(), q});
+        const i64 len = cl_off[q + 1] - cl_off[q], v0 = len > 0 ? cl_flat[cl_off[q]] : 1;
+        if (v0 < 1 || v0 > n) bad = 1;
+        else if (len > 0) sc.owner[q] = c->comm_owner[c->h_comm[v0 - 1]];
+        const bool mine = sc.owner[q] == me;
+        if (mine) sc.a_off[q] = at[q];
+        at[q + 1] = at[q] + (mine ? len : 0);
+    }
+    c->pin_clusters.ensure(std::max<i64>(at[ncl], 1));
+    i32 *stage = c->pin_clusters.p;
+    std::atomic<int> abad{bad};
+    parallel_for(c, ncl, [&](i64 q) {
+        const bool mine = sc.owner[q] == me;
+        for (i64 t = cl_off[q]; t < cl_off[q + 1]; t++) {
+            const i64 v = cl_flat[t];
+            if (v < 1 || v > n) { abad.store(1); continue; }
+            const i32 l = c->h_glob2loc[v - 1];
+            if (mine != (l >= 0)) { abad.store(2); continue; } // a cluster that spans two ranks' rows
+            if (mine) stage[at[q] + (t - cl_off[q])] = l;
+        }
+    });
+    // every rank must leave by the same door: the verdicts are exchanged (their maximum) before anybody throws
+    std::vector<double> verdict(1, (double)abad.load());
+    exchange_group_words(c, verdict, 1);
+    if (verdict[0] == 1.0) CGE_THROW(CGE_E_ARG, "cluster member out of range 1..%lld", (long long)n);
+    if (verdict[0] != 0.0)
+        CGE_THROW(CGE_E_ARG, "option shard_rows: a cluster spans the rows of two ranks (the rows are sharded by the community "
+                             "vector of cge_set_vertex_data: clusters must refine it)");
+    if (at[ncl] > 0) {
+        arena_alloc(c, at[ncl]);
+        HIP_CHECK(hipMemcpyAsync(c->lm_arena.p, stage, sizeof(i32) * at[ncl], hipMemcpyHostToDevice, c->stream));
+    }
+    return sc;
+}
+
+// Every community beyond `forced` owns a local heap, seeded with the community itself.
+std::vector<Local> seed_local_heaps(const i64 *cl_off, const std::vector<i64> &order, i64 forced, const StagedClusters &sc,
+                                    GroupPool &pool) {
+    std::vector<Local> locals;
+    for (i64 cidx : order) {
+        const i64 len = cl_off[cidx + 1] - cl_off[cidx];
+        if (len <= forced) continue;
+        pool.emplace_back();
+        Group *g = &pool.back();
+        g->off = sc.a_off[cidx];
+        g->len = len;
+        g->owner = sc.owner[cidx];
+        locals.emplace_back();
+        locals.back().cidx = cidx;
+        locals.back().owner = g->owner;
+        locals.back().h.put(g);
+    }
+    return locals;
+}
+// The roots' heap values.  Needed with forced <= 1 only: with forced >= 2 every root is popped from its one-element heap and
+// its value is never compared.  (Option shard_rows: the other ranks' roots get theirs with the forced phase's exchange.)
+void root_values(cge_ctx *c, std::vector<Local> &locals) {
+    PhaseAcc pa(c, "lm_roots");
+    std::vector<Group *> roots;
+    for (auto &L : locals)
+        if (!c->rows_sharded || L.owner == c->coll.rank) roots.push_back(L.h.top());
+    device_group_values(c, roots);
+}
+
+// ---- forced per-community phase (:282-313) ----
+// The local heaps are independent of each other: first all of them are split, then the merge inserts community by community.
+// Bring the local heaps of rank `only` (-1: all of them) to `forced` groups.
+void advance_local_heaps(cge_ctx *c, std::vector<Local> &locals, int only, i64 forced, int method, GroupPool &pool) {
+    std::vector<Heap *> hs;
+    for (auto &L : locals)
+        if (only < 0 || L.owner == only) hs.push_back(&L.h);
+    if (!hs.empty()) advance_heaps(c, hs, std::vector<i64>(hs.size(), forced), method, pool, false);
+}
+// every heap on this rank
+void forced_local(cge_ctx *c, std::vector<Local> &locals, i64 forced, int method, GroupPool &pool) {
+    advance_local_heaps(c, locals, -1, forced, method, pool);
+    for (auto &L : locals) L.drain();
+}
+// N > 1: every rank splits its share of the communities (balanced by rows) and the results -- member lists in pop order,
+// lengths, heap values, means -- are gathered (GroupGather).  Afterwards EVERY rank, owner or not, rebuilds the groups from
+// the gathered data, so all ranks continue from identical state.  An error of this rank's heaps -- the reference's own
+// "Trying to split homogenous cluster" included -- travels with the exchange, so that every rank stops instead of waiting.
+void forced_over_ranks(cge_ctx *c, std::vector<Local> &locals, const i64 *cl_off, i64 forced, int method, GroupPool &pool,
+                       GroupGather &G) {
+    const i64 nbig = (i64)locals.size(), d = c->d, total = G.rows;
+    const int me = c->coll.rank;
+    std::vector<i64> len(nbig);
+    for (i64 b = 0; b < nbig; b++) len[b] = locals[b].h.top()->len;
+    const std::vector<int> owner = balance_over_ranks(len, c->coll.world);
+    for (i64 b = 0; b < nbig; b++) locals[b].owner = owner[b];
+    RankError err = guarded_work([&] { advance_local_heaps(c, locals, me, forced, method, pool); });
+    PhaseAcc px(c, "lm_exchange");
+    // counts per community; per group {len, value, means flag} and the mean; the member lists into their community's range
+    if (!err.code) err = guarded_work([&] {
+        for (i64 b = 0; b < nbig; b++) {
+            Local &L = locals[b];
+            if (L.owner != me) continue;
+            if ((i64)L.h.len() > forced) CGE_THROW(CGE_E_ASSERT, "forced phase: a local heap grew beyond its target");
+            L.drain();
+            G.counts[b] = (double)L.out.size();
+            i64 at = cl_off[L.cidx], sl = b * forced;
+            for (const Group *g : L.out) {
+                G.seg.push_back(g->off); G.seg.push_back(at); G.seg.push_back(g->len);
+                G.scal[3 * sl] = (double)g->len;
+                G.scal[3 * sl + 1] = g->value;
+                G.scal[3 * sl + 2] = g->mean_off >= 0 ? 1.0 : 0.0;
+                if (g->mean_off >= 0) { G.moff.push_back(g->mean_off); G.mslot.push_back(sl); }
+                at += g->len;
+                sl++;
+            }
+            if (at != cl_off[L.cidx + 1]) CGE_THROW(CGE_E_ASSERT, "forced phase: groups do not cover their community");
+        }
+    });
+    G.run(c, err, "forced phase (sharded)");
+    // every rank: communities back into the start of the arena, one means block, fresh groups
+    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p, G.members(c), sizeof(i32) * total, hipMemcpyDeviceToDevice, c->stream));
+    c->lm_arena_used = total;
+    c->lm_means_used = 0;
+    const i64 mbase = means_alloc(c, nbig * forced * d);
+    G.means_to_arena(c, mbase);
+    for (i64 b = 0; b < nbig; b++) {
+        Local &L = locals[b];
+        L.out.clear();
+        i64 at = cl_off[L.cidx];
+        for (i64 sl = b * forced; sl < b * forced + (i64)G.counts[b]; sl++) {
+            const double *rec = &G.scal[3 * sl];
             pool.emplace_back();
             Group *g = &pool.back();
-            g->off = a_off(cidx);
-            g->len = len;
-            g->owner = RS ? cl_owner[cidx] : 0;
-            locals.back().h.put(g);
+            g->off = at;
+            g->len = (i64)rec[0];
+            g->value = rec[1];
+            g->mean_off = rec[2] != 0.0 ? mbase + sl * d : -1;
+            at += g->len;
+            L.out.push_back(g);
+        }
+        if (at != cl_off[L.cidx + 1]) CGE_THROW(CGE_E_ASSERT, "forced phase: gathered groups do not cover their community");
+    }
+}
+// Option shard_rows: every rank runs the local heaps of ITS communities; the replicated global heap needs, of every group
+// they end with, its length and value only: one gather of 1 + 2 max(forced, 1) words per community.  A reference error --
+// "Trying to split homogenous cluster", an empty child -- is raised by the owner of the community alone: it must reach the
+// other ranks, who would otherwise wait in the exchange for ever.
+void forced_rowsharded(cge_ctx *c, std::vector<Local> &locals, i64 forced, int method, GroupPool &pool) {
+    const i64 nbig = (i64)locals.size(), cap = std::max<i64>(forced, 1), per = 1 + 2 * cap;
+    const int me = c->coll.rank;
+    std::vector<double> w((size_t)nbig * per, 0.0);
+    const RankError err = guarded_work([&] {
+        advance_local_heaps(c, locals, me, forced, method, pool);
+        for (i64 b = 0; b < nbig; b++) {
+            Local &L = locals[b];
+            if (L.owner != me) continue;
+            if ((i64)L.h.len() > cap) CGE_THROW(CGE_E_ASSERT, "forced phase: a local heap grew beyond its target");
+            L.drain();
+            double *rec = &w[b * per];
+            *rec++ = (double)L.out.size();
+            for (const Group *g : L.out) { *rec++ = (double)g->len; *rec++ = g->value; }
+        }
+    });
+    exchange_group_words_checked(c, w, err, "forced phase (shard_rows)");
+    for (i64 b = 0; b < nbig; b++) {
+        Local &L = locals[b];
+        const double *rec = &w[b * per];
+        const i64 cnt = (i64)rec[0];
+        if (cnt < 1 || cnt > cap) CGE_THROW(CGE_E_COLLECTIVE, "forced phase (shard_rows): no rank answered for a community of rank %d", L.owner);
+        if (L.owner == me) continue; // its own groups, with their rows
+        for (i64 s = 0; s < cnt; s++) {
+            pool.emplace_back();
+            Group *g = &pool.back();
+            g->off = -1;
+            g->len = (i64)rec[1 + 2 * s];
+            g->value = rec[2 + 2 * s];
+            g->owner = L.owner;
+            L.out.push_back(g);
         }
     }
-    delete pinit;
-    if (!locals.empty()) {
-        if (forced <= 1) { // with forced >= 2 every root is popped from its one-element heap: its value is never compared
-            PhaseAcc pa(c, "lm_roots");
-            std::vector<Group *> roots;
-            for (auto &L : locals)
-                if (!RS || L.h.top()->owner == me) roots.push_back(L.h.top());
-            device_group_values(c, roots);
-            // (option shard_rows: the other ranks' roots get their values with the forced phase's exchange below)
-        }
-        // N > 1: the local heaps are independent of each other, so every rank splits its share of the communities
-        // (balanced by rows) and the results -- member lists in pop order, lengths, heap values, means -- are gathered by ONE
-        // all-reduce into zero-filled buffers (op 2: integer sum of the words, exact).  Afterwards EVERY rank, owner or not,
-        // rebuilds the groups from the gathered data, so all ranks continue from identical state.
-        const i64 nbig = (i64)locals.size(), W = c->has_coll ? c->coll.world : 1;
-        const i64 s_words = (total + 1) / 2, m_per = 3 + d; // per group: length, value, mean flag, mean
-        const i64 x_need = s_words + nbig + nbig * forced * m_per;
-        const bool shard = !RS && W > 1 && c->opt_shard_forced && forced >= 2 && cge_exchange_fits(c, (size_t)(x_need + W));
-        std::vector<int> owner(nbig, 0);
-        if (RS) {
-            // option shard_rows: every rank runs the local heaps of ITS communities; the replicated global heap needs, of every
-            // group they end with, its length and value only (pop order): one gather of 1 + 2 max(forced, 1) words per community
-            const i64 per = 1 + 2 * std::max<i64>(forced, 1);
-            std::vector<Heap *> hs;
-            std::vector<i64> tg;
-            for (i64 b = 0; b < nbig; b++) {
-                owner[b] = locals[b].h.top()->owner;
-                if (owner[b] == me) { hs.push_back(&locals[b].h); tg.push_back(forced); }
-            }
-            std::vector<double> w((size_t)nbig * per, 0.0);
-            std::vector<std::vector<Group *>> popped(nbig);
-            // (a reference error -- "Trying to split homogenous cluster", an empty child -- is raised by the owner of the
-            // community alone: it must reach the other ranks, who would otherwise wait in the exchange for ever)
-            const RankError err = guarded_work([&] {
-                if (!hs.empty()) advance_heaps(c, hs, tg, method, pool, false);
-                for (i64 b = 0; b < nbig; b++) {
-                    if (owner[b] != me) continue;
-                    Heap &L = locals[b].h;
-                    if ((i64)L.len() > std::max<i64>(forced, 1)) CGE_THROW(CGE_E_ASSERT, "forced phase: a local heap grew beyond its target");
-                    while (L.len() > 0) popped[b].push_back(L.pop()); // pop order = the order in which the global heap receives them (:309-312)
-                    w[b * per] = (double)popped[b].size();
-                    for (size_t s_ = 0; s_ < popped[b].size(); s_++) {
-                        w[b * per + 1 + 2 * s_] = (double)popped[b][s_]->len;
-                        w[b * per + 2 + 2 * s_] = popped[b][s_]->value;
-                    }
-                }
-            });
-            exchange_group_words_checked(c, w, err, "forced phase (shard_rows)");
-            for (i64 b = 0; b < nbig; b++) {
-                Heap &L = locals[b].h;
-                L = Heap();
-                const i64 cnt = (i64)w[b * per];
-                if (cnt < 1 || cnt > std::max<i64>(forced, 1)) CGE_THROW(CGE_E_COLLECTIVE, "forced phase (shard_rows): no rank answered for a community of rank %d", owner[b]);
-                for (i64 s_ = 0; s_ < cnt; s_++) {
-                    Group *g;
-                    if (owner[b] == me)
-                        g = popped[b][s_];
-                    else {
-                        pool.emplace_back();
-                        g = &pool.back();
-                        g->off = -1;
-                        g->len = (i64)w[b * per + 1 + 2 * s_];
-                        g->value = w[b * per + 2 + 2 * s_];
-                        g->owner = owner[b];
-                    }
-                    L.a.push_back(Heap::Ent{g->value, g}); // kept in pop order: the merge below reads the array front to back
-                }
-            }
-            sharded_forced = true;
-        }
-        if (shard) { // longest first, each to the least loaded rank (deterministic)
-            std::vector<i64> ord(nbig), load(W, 0);
-            for (i64 b = 0; b < nbig; b++) ord[b] = b;
-            std::stable_sort(ord.begin(), ord.end(), [&](i64 a, i64 b) { return locals[a].h.top()->len > locals[b].h.top()->len; });
-            for (i64 b : ord) {
-                const int r = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-                owner[b] = r;
-                load[r] += locals[b].h.top()->len;
-            }
-        }
-        const int me_f = shard ? c->coll.rank : 0;
-        RankError ferr;
-        if (!RS) {
-            std::vector<Heap *> hs;
-            std::vector<i64> tg;
-            for (i64 b = 0; b < nbig; b++)
-                if (owner[b] == me_f) { hs.push_back(&locals[b].h); tg.push_back(forced); }
-            // (sharded: an error of this rank's heaps -- the reference's own "Trying to split homogenous cluster" included --
-            // travels with the exchange below, so that every rank stops instead of waiting for this one)
-            ferr = guarded_work([&] { if (!hs.empty()) advance_heaps(c, hs, tg, method, pool, false); });
-            if (!shard && ferr.code) throw CgeError{ferr.code, ferr.msg};
-        }
-        if (shard) {
-            const int me = me_f;
-            PhaseAcc px(c, "lm_exchange");
-            double *X = c->xptr;
-            i32 *S = reinterpret_cast<i32 *>(X);
-            double *Mc = X + s_words, *Mg = Mc + nbig; // counts per community; per group {len, value, flag, mean[d]}
-            HIP_CHECK(hipMemsetAsync(X, 0, sizeof(double) * (x_need + W), st)); // (W verdict slots behind the words)
-            std::vector<i64> seg, moff;
-            std::vector<double> hc(nbig, 0.0), hg((size_t)nbig * forced * 3, 0.0);
-            std::vector<i64> gslot; // slot (b * forced + s) of every owned group, in the order of `moff`
-            if (!ferr.code) ferr = guarded_work([&] {
-            for (i64 b = 0; b < nbig; b++) {
-                if (owner[b] != me) continue;
-                Heap &L = locals[b].h;
-                const i64 cidx = order[locals[b].pos];
-                i64 at = cl_off[cidx], s_ = 0;
-                if ((i64)L.len() > forced) CGE_THROW(CGE_E_ASSERT, "forced phase: a local heap grew beyond its target");
-                hc[b] = (double)L.len();
-                while (L.len() > 0) { // pop order = the order in which the global heap receives them (:309-312)
-                    Group *g = L.pop();
-                    seg.push_back(g->off); seg.push_back(at); seg.push_back(g->len);
-                    const size_t sl = (size_t)(b * forced + s_);
-                    hg[3 * sl] = (double)g->len;
-                    hg[3 * sl + 1] = g->value;
-                    hg[3 * sl + 2] = g->mean_off >= 0 ? 1.0 : 0.0;
-                    if (g->mean_off >= 0) { moff.push_back(g->mean_off); gslot.push_back((i64)sl); }
-                    at += g->len;
-                    s_++;
-                }
-                if (at != cl_off[cidx + 1]) CGE_THROW(CGE_E_ASSERT, "forced phase: groups do not cover their community");
-            }
-            });
-            const double my_verdict = (double)ferr.code;
-            if (ferr.code) {
-                HIP_CHECK(hipMemcpyAsync(X + x_need + me, &my_verdict, sizeof(double), hipMemcpyHostToDevice, st));
-                seg.clear(); moff.clear(); gslot.clear();
-                std::fill(hc.begin(), hc.end(), 0.0);
-            }
-            // member lists -> their community's range of S; {len, value, flag} and the means -> Mg
-            DevBuf<i64> d_seg, d_moff;
-            if (!seg.empty()) {
-                d_seg.ensure(seg.size());
-                HIP_CHECK(hipMemcpyAsync(d_seg.p, seg.data(), sizeof(i64) * seg.size(), hipMemcpyHostToDevice, st));
-                k_copy_segments(c, c->lm_arena.p, d_seg.p, (i64)seg.size() / 3, S);
-            }
-            HIP_CHECK(hipMemcpyAsync(Mc, hc.data(), sizeof(double) * nbig, hipMemcpyHostToDevice, st));
-            // the three scalars of every slot (strided into Mg) and the means
-            HIP_CHECK(hipMemcpy2DAsync(Mg, sizeof(double) * m_per, hg.data(), sizeof(double) * 3, sizeof(double) * 3,
-                                       (size_t)nbig * forced, hipMemcpyHostToDevice, st));
-            if (!moff.empty()) {
-                d_moff.ensure(2 * moff.size());
-                HIP_CHECK(hipMemcpyAsync(d_moff.p, moff.data(), sizeof(i64) * moff.size(), hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync(d_moff.p + moff.size(), gslot.data(), sizeof(i64) * gslot.size(), hipMemcpyHostToDevice, st));
-                k_gather_means_slots(c, c->lm_means.p, d_moff.p, d_moff.p + moff.size(), (i64)moff.size(), d, m_per, 3, Mg);
-            }
-            cge_allreduce_dev(c, X, x_need + W, 2);
-            {
-                std::vector<double> slots((size_t)W);
-                HIP_CHECK(hipMemcpyAsync(slots.data(), X + x_need, sizeof(double) * W, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                throw_if_a_rank_failed(c, ferr, slots.data(), "forced phase (sharded)");
-            }
-            // every rank: communities back into the start of the arena, one means block, fresh groups
-            HIP_CHECK(hipMemcpyAsync(c->lm_arena.p, S, sizeof(i32) * total, hipMemcpyDeviceToDevice, st));
-            c->lm_arena_used = total;
-            std::vector<double> all((size_t)nbig + (size_t)nbig * forced * m_per);
-            HIP_CHECK(hipMemcpyAsync(all.data(), Mc, sizeof(double) * all.size(), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            c->lm_means_used = 0;
-            const i64 mbase = means_alloc(c, nbig * forced * d);
-            HIP_CHECK(hipMemcpy2DAsync(c->lm_means.p + mbase, sizeof(double) * d, Mg + 3, sizeof(double) * m_per, sizeof(double) * d,
-                                       (size_t)nbig * forced, hipMemcpyDeviceToDevice, st));
-            for (i64 b = 0; b < nbig; b++) {
-                Heap &L = locals[b].h;
-                L = Heap(); // (an unsplit root of another rank's community, or empty after the pops above)
-                const i64 cidx = order[locals[b].pos], cnt = (i64)all[b];
-                i64 at = cl_off[cidx];
-                for (i64 s_ = 0; s_ < cnt; s_++) {
-                    const double *rec = &all[(size_t)nbig + (size_t)(b * forced + s_) * m_per];
-                    pool.emplace_back();
-                    Group *g = &pool.back();
-                    g->off = at;
-                    g->len = (i64)rec[0];
-                    g->value = rec[1];
-                    g->mean_off = rec[2] != 0.0 ? mbase + (b * forced + s_) * d : -1;
-                    at += g->len;
-                    L.a.push_back(Heap::Ent{g->value, g}); // kept in pop order: the merge below reads the array front to back
-                }
-                if (at != cl_off[cidx + 1]) CGE_THROW(CGE_E_ASSERT, "forced phase: gathered groups do not cover their community");
-            }
-            HIP_CHECK(hipStreamSynchronize(st)); // seg / moff staging goes out of scope
-            sharded_forced = true;
-        }
+}
+// The one place that chooses among the three.  Each leaves every local heap's groups in pop order (Local::out).
+void forced_phase(cge_ctx *c, std::vector<Local> &locals, const i64 *cl_off, i64 total, i64 forced, int method, GroupPool &pool) {
+    const i64 nbig = (i64)locals.size(), W = c->has_coll ? c->coll.world : 1;
+    if (c->rows_sharded) return forced_rowsharded(c, locals, forced, method, pool);
+    if (W > 1 && c->opt_shard_forced && forced >= 2) {
+        GroupGather G;
+        G.shape(total, nbig, nbig * forced, 3, c->d); // a count per community; per group: length, value, means flag, mean
+        if (cge_exchange_fits(c, (size_t)(G.words() + W))) return forced_over_ranks(c, locals, cl_off, forced, method, pool, G);
     }
-    PhaseAcc *pmerge = new PhaseAcc(c, "lm_merge");
+    forced_local(c, locals, forced, method, pool);
+}
+
+// The merge (:309-312): global-heap insertion follows the sorted community order -- a small community's members one by one,
+// a big one's groups in pop order.
+void merge_into_global(cge_ctx *c, const i64 *cl_off, const std::vector<i64> &order, i64 forced, const StagedClusters &sc,
+                       const std::vector<Local> &locals, GroupPool &pool, Heap &H) {
+    PhaseAcc pa(c, "lm_merge");
     size_t li = 0;
-    for (i64 q = 0; q < ncl; q++) {
-        const i64 cidx = order[q], len = cl_off[cidx + 1] - cl_off[cidx];
-        if (len <= forced) {
-            for (i64 t = cl_off[cidx]; t < cl_off[cidx + 1]; t++) {
-                pool.emplace_back();
-                Group *g = &pool.back();
-                g->off = a_off(cidx) >= 0 ? a_off(cidx) + (t - cl_off[cidx]) : -1;
-                g->len = 1;
-                g->value = DBL_EPSILON; // eps() (:284)
-                g->owner = RS ? cl_owner[cidx] : 0;
-                H.put(g);
-            }
-        } else {
-            Heap &L = locals[li++].h;
-            if (sharded_forced) { // already in pop order
-                for (size_t q2 = 1; q2 < L.a.size(); q2++) H.put(L.a[q2].g);
-            } else
-                while (L.len() > 0) H.put(L.pop()); // :309-312
+    for (i64 cidx : order) {
+        if (cl_off[cidx + 1] - cl_off[cidx] > forced) {
+            for (Group *g : locals[li++].out) H.put(g);
+            continue;
+        }
+        for (i64 t = cl_off[cidx]; t < cl_off[cidx + 1]; t++) {
+            pool.emplace_back();
+            Group *g = &pool.back();
+            g->off = sc.a_off[cidx] >= 0 ? sc.a_off[cidx] + (t - cl_off[cidx]) : -1;
+            g->len = 1;
+            g->value = DBL_EPSILON; // eps() (:284)
+            g->owner = sc.owner[cidx];
+            H.put(g);
         }
     }
-    delete pmerge;
-    // ---- global phase (:316-335) ----------------------------------------------------------------------------
-    {
-        std::vector<Heap *> hs{&H};
-        std::vector<i64> tg{nland};
-        advance_heaps(c, hs, tg, method, pool, true);
-    }
-    // ---- the heap array is the numbering (:337-342): v2l and the landmark index, on the device -----------------------
+}
+
+// The heap array is the numbering (:337-342): v2l and the landmark index, on the device.
+void final_index(cge_ctx *c, const Heap &H, std::vector<i64> &group_ids, bool want_index) {
     PhaseAcc pfin(c, "lm_final");
-    const i64 NG = (i64)H.len();
-    const i64 nrows = lm_rows(c);
+    const i64 n = c->n, NG = (i64)H.len(), nrows = lm_rows(c);
+    const bool RS = c->rows_sharded;
+    const int me = RS ? c->coll.rank : 0;
+    hipStream_t st = c->stream;
     c->pin_small.ensure((size_t)2 * NG + 2);
     i32 *goff = c->pin_small.p, *glen = goff + NG;
     c->h_mem_off.assign(NG + 1, 0);
@@ -1716,4 +1653,41 @@ void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i
     parallel_for(c, 64, [&](i64 part) {
         for (i64 i = n * part / 64; i < n * (part + 1) / 64; i++) group_ids[i] = c->h_v2l0[i];
     });
+}
+
+} // namespace
+
+// group_ids[i] = 0-based group (= heap position - 1) of vertex i; also leaves on the device c->v2l (the same, int32)
+// and the landmark -> members index c->lm_memoff / c->lm_mem (ascending inside a landmark), mirrored in
+// c->h_mem_off / c->h_mem when `want_index`.
+void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
+                   std::vector<i64> &group_ids, bool want_index) {
+    if (!c->Xr.p || c->Xr.n < (size_t)(lm_rows(c) * c->d) || (i64)c->h_vw.size() != c->n)
+        CGE_THROW(CGE_E_ARG, "runsplit: embedding / vertex weights are not resident");
+    GroupPool pool;
+    Heap H;
+    std::vector<i64> order;
+    StagedClusters sc;
+    std::vector<Local> locals;
+    {
+        PhaseAcc pa(c, "lm_init");
+        order = sorted_cluster_order(cl_flat, cl_off, ncl);
+        c->lm_arena_used = 0;
+        c->lm_means_used = 0;
+        c->stat_lm_batches = c->stat_lm_rows = c->stat_lm_splits = 0;
+        c->cut_ties.ensure(1);
+        HIP_CHECK(hipMemsetAsync(c->cut_ties.p, 0, sizeof(int), c->stream));
+        sc = c->rows_sharded ? stage_clusters_rowsharded(c, cl_flat, cl_off, ncl) : stage_clusters(c, cl_flat, cl_off, ncl);
+        locals = seed_local_heaps(cl_off, order, forced, sc, pool);
+    }
+    if (!locals.empty()) {
+        if (forced <= 1) root_values(c, locals);
+        forced_phase(c, locals, cl_off, cl_off[ncl], forced, method, pool);
+    }
+    merge_into_global(c, cl_off, order, forced, sc, locals, pool, H);
+    { // the global phase (:316-335)
+        std::vector<Heap *> hs{&H};
+        advance_heaps(c, hs, std::vector<i64>{nland}, method, pool, true);
+    }
+    final_index(c, H, group_ids, want_index);
 }
