@@ -388,16 +388,6 @@ static void embedding_resident(cge_ctx *c, i64 n, i64 d) {
     c->centred_ready = false;
     c->lm_ready = false;
 }
-static void ensure_centred(cge_ctx *c) {
-    if (c->centred_ready) return;
-    if (c->rows_sharded) CGE_THROW(CGE_E_ARG, "the brute-force diameter over the whole embedding needs every row on one rank; the resident rows are sharded (option shard_rows)");
-    if (!c->Xr.p || c->d <= 0) CGE_THROW(CGE_E_ARG, "diameter: embedding not resident");
-    c->Xc.alloc_exact((size_t)c->ldn * c->dpad);
-    c->rnorm.alloc_exact((size_t)c->ldn);
-    k_gather_centre_fm(c, c->Xr.p, nullptr, c->gmean.p, c->Xc.p, c->rnorm.p, c->n, c->d, c->ldn, c->dpad);
-    c->centred_ready = true;
-}
-
 int cge_set_embedding(cge_ctx *c, const double *X, int64_t n, int64_t d) {
     if (!c || !X || n <= 0 || d <= 0) return CGE_E_ARG;
     CGE_TRY(c)
@@ -1016,46 +1006,6 @@ static bool samples_can_start_early(cge_ctx *c, i64 seed, bool exact_directed) {
     return seed != -1 && !exact_directed && sampler_uses_device(c) && !c->edges_sharded;
 }
 
-// diameter of the resident embedding (this rank's share), brute force over all pair tiles
-static double resident_diameter(cge_ctx *c, int part, int nparts, i64 *ai, i64 *aj) {
-    if (c->emb_nonfinite) { // (embedding_resident)
-        c->stat_diameter_path = 1;
-        c->stat_hi_i = c->stat_hi_j = 0;
-        if (ai) *ai = 1;
-        if (aj) *aj = 1;
-        return std::numeric_limits<double>::quiet_NaN();
-    }
-    ensure_centred(c);
-    double bv;
-    i64 bi, bj;
-    std::vector<double> wg_best;
-    k_max_pair(c, c->Xc.p, c->rnorm.p, c->n, c->ldn, c->dpad, part, nparts, &bv, &bi, &bj, &wg_best);
-    c->stat_diameter_path = 1;
-    // the pairs whose Gram value is within rounding of the largest one are evaluated with dist()'s own arithmetic
-    // (src/auxilary.jl:14-20) and the largest of THOSE values is `hi` (diameter_host.cpp: gram_delta)
-    const double hi = host_brute_exact(c, part, nparts, bv, wg_best, &bi, &bj);
-    c->stat_hi_i = bi; c->stat_hi_j = bj;
-    if (ai) *ai = bi + 1;
-    if (aj) *aj = bj + 1;
-    return hi;
-}
-
-// the same with landmark-pair pruning in front (diameter_host.cpp); `mu` = N reference points (device, row-major)
-static double resident_diameter_lm(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C,
-                                   i64 N, int part, int nparts) {
-    if (c->emb_nonfinite) return resident_diameter(c, part, nparts, nullptr, nullptr); // NaN, as the reference's extrema()
-    if ((c->opt_diameter != 1 || c->rows_sharded) && (i64)c->h_mem_off.size() == N + 1) { // (sharded rows: the pruned search only)
-        double hi;
-        i64 bi, bj;
-        if (host_diameter_pruned(c, mu, lw, lcomm, C, N, c->h_mem_off, c->h_mem, part, nparts, &hi, &bi, &bj)) {
-            c->stat_diameter_path = 2;
-            c->stat_hi_i = bi; c->stat_hi_j = bj;
-            return hi; // (already in dist()'s arithmetic)
-        }
-    }
-    return resident_diameter(c, part, nparts, nullptr, nullptr);
-}
-
 // landmark -> members CSR (ascending vertex id) from a 0-based assignment
 static void build_landmark_index(cge_ctx *c, const std::vector<i32> &v2l0, i64 N) {
     const i64 n = (i64)v2l0.size();
@@ -1090,7 +1040,7 @@ int cge_max_pair_dist(cge_ctx *c, int part, int nparts, double *hi, int64_t *arg
     if (!c || !hi || nparts < 1 || part < 0 || part >= nparts) return CGE_E_ARG;
     CGE_TRY(c)
     HIP_CHECK(hipSetDevice(c->device));
-    *hi = resident_diameter(c, part, nparts, arg_i, arg_j);
+    *hi = host_diameter_brute(c, part, nparts, arg_i, arg_j);
     CGE_CATCH(c)
 }
 
@@ -1145,15 +1095,6 @@ static OrigView resident_orig_view(cge_ctx *c, const double *lweight) {
     ov.n = c->n; ov.m = c->m; ov.Xr = c->Xr.p; ov.vw = c->vw.p; ov.v2l = c->v2l.p; ov.lweight = lweight;
     ov.src = c->src.p; ov.dst = c->dst.p; ov.h_w = c->h_w.empty() ? nullptr : c->h_w.data();
     return ov;
-}
-
-// the diameter of the landmark embedding `lemb` (0-based communities `lcomm`), the largest of the ranks' shares: full_graph_D's
-// normaliser (src/divergence.jl:104-114)
-static double landmark_diameter(cge_ctx *c, const double *lemb, const double *lweight, const std::vector<i32> &lcomm, i64 C, i64 N) {
-    double hi = resident_diameter_lm(c, lemb, lweight, lcomm, C, N, c->has_coll ? c->coll.rank : 0, c->has_coll ? c->coll.world : 1);
-    hi = allreduce_scalar_max(c, hi);
-    c->stat_last_hi = hi;
-    return hi;
 }
 
 int cge_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cge_trace *trace) {
@@ -1232,7 +1173,7 @@ int cge_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cg
         ov = resident_orig_view(c, c->s_vw.p);
         std::vector<i32> lcomm0(N);
         for (i64 i = 0; i < N; i++) lcomm0[i] = (i32)(a->comm[i] - 1);
-        ov.hi = landmark_diameter(c, c->s_emb.p, c->s_vw.p, lcomm0, C, N);
+        ov.hi = host_diameter_landmarks(c, c->s_emb.p, c->s_vw.p, lcomm0, C, N);
     } else {
         // exact mode: make the score graph the resident graph so the sampler can reject its edges
         int rc = cge_set_graph(c, a->edges_src, a->edges_dst, a->eweights, a->m, N);
@@ -1327,7 +1268,7 @@ static void score_one(cge_ctx *c, const cge_score_args *a, double out[7], int *o
         lcomm_host.resize(N); // community of a landmark = community of any member (landmarks never span two): :427
         HIP_CHECK(hipMemcpyAsync(lcomm_host.data(), c->lcomm.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        ov.hi = landmark_diameter(c, c->lemb.p, c->lweight.p, lcomm_host, C, N);
+        ov.hi = host_diameter_landmarks(c, c->lemb.p, c->lweight.p, lcomm_host, C, N);
         ov.h_lcomm = lcomm_host.data(); // (the sweep groups the landmarks by community: no second read-back)
         c->phases.ms["diameter"] = now_ms() - t0; // what the main thread still waited for
     } else {

@@ -24,6 +24,16 @@
 typedef int64_t i64;
 typedef int32_t i32;
 
+// records the diameter's kernels (kernels_dist.hip) write and its host code (diameter_host.cpp) reads
+struct MaxRec { // a workgroup's best: value max, ties -> smallest (i, j)
+    double val;
+    i64 i, j;
+};
+struct BoundRec { // a candidate landmark pair a <= b and the upper bound of its pairs' squared distances
+    double B;
+    i32 a, b;
+};
+
 struct CgeError {
     int code;
     std::string msg;
@@ -396,13 +406,14 @@ struct cge_ctx {
     DevBuf<i32> sw_cm_off, sw_cm_mem, sw_cm_pos; // community -> members CSR of the score graph and its inverse
     DevBuf<double> sw_zeros, sw_zsum;
     // diameter scratch
-    DevBuf<double> mp_recs;  // MaxRec records (3 doubles each)
+    DevBuf<MaxRec> mp_recs;
     DevBuf<i64> mp_count;
-    DevBuf<i32> nt_pairs, nt_idx, nt_tiles; // near-tied pairs of the arg-max (vertex ids) / their split index arrays
+    DevBuf<int2> nt_pairs, nt_tiles; // near-tied pairs of the arg-max (vertex ids) / the tiles searched for them
+    DevBuf<i32> nt_idx;              // the pairs' split index arrays
     DevBuf<double> nt_out, nt_rows; // their dist() values / the gathered rows (option shard_rows)
     DevBuf<double> mp_rd2, mp_refmu; // reference-point distances / centroids of the pruned diameter
     DevBuf<double> mp_commax;        // per-community maxima of the bound matrix (two-level candidate selection)
-    DevBuf<i32> mp_plist;            // surviving community pairs (int2 each)
+    DevBuf<int2> mp_plist;           // surviving community pairs
     DevBuf<i32> mp_lref, mp_refoff, mp_refmem;
     DevBuf<double> gmean;    // global feature mean (the centre used by Xc)
     bool emb_nonfinite = false; // a NaN / Inf in the resident embedding (seen in gmean): the diameter is NaN
@@ -418,8 +429,8 @@ struct cge_ctx {
     int opt_diameter_f32 = 2;              // the point-to-reference maxima: 2 = bf16 matrix pipe, operands split in two terms (K <= 128; else 1),
                                            // 1 = fp32-input MFMA, 0 = fp64 MFMA; 1 and 2 are upper bounds with a rigorous error margin
     DevBuf<i32> pos2node, sub_land, dm_soff, dm_memoff, dm_mem;
-    DevBuf<double> bound_list;             // BoundRec records (2 doubles each)
-    DevBuf<i32> tile_list;
+    DevBuf<BoundRec> bound_list;           // candidate landmark pairs
+    DevBuf<int2> tile_list;                // a round's tiles (first row, first column)
     std::vector<i32> h_mem_off, h_mem;     // landmark -> members (ascending vertex id), host copy
     DevBuf<uint64_t> uniq_hash;            // row hashes of the unique-row check
     DevBuf<unsigned long long> uniq_table; // ... and the device set that counts the distinct ones
@@ -670,14 +681,12 @@ bool cge_exchange_fits(cge_ctx *c, size_t need);
 void k_pcent(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, const double *Ms, const double *mnorm,
              i64 ldm, i64 n_land, i64 N, i64 dpad, const i32 *soff, double *P, int part = 0, int nparts = 1);
 void k_max_pair_tile_list(i64 ldn, int part, int nparts, const std::vector<double> &wg, double thr, std::vector<int2> &out);
-i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 nrows, i64 dpad, const void *tiles, i64 t0, i64 t1,
-                   int tri, double thr, const i32 *ids, void *out, i64 cap);
-void k_pair_list(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, i64 npos, i64 dpad, const void *tiles,
+i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 nrows, i64 dpad, const int2 *tiles, i64 t0, i64 t1,
+                   int tri, double thr, const i32 *ids, int2 *out, i64 cap);
+void k_pair_list(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, i64 npos, i64 dpad, const int2 *tiles,
                  i64 ntiles, double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best = nullptr);
-i64 k_bound_select(cge_ctx *c, const double *Q, const i32 *lref, const double *mu_ref, i64 N, i64 nref, i64 d, double L,
-                   void *list, i64 cap, const i32 *ref_off = nullptr, const i32 *ref_mem = nullptr, const double *Ms_fm = nullptr,
-                   i64 dpad = 0, i64 ldm = 0,
-                   bool rd2_ready = false);
+i64 k_bound_select(cge_ctx *c, const double *Q, const i32 *lref, i64 N, i64 nref, double L, BoundRec *list, i64 cap,
+                   const i32 *ref_off = nullptr, const i32 *ref_mem = nullptr);
 void k_ref_dist2_fm(cge_ctx *c, const double *Ms_fm, i64 nref, i64 dpad, i64 ldm);
 i64 k_argmax_mapped(cge_ctx *c, const double *v, i64 n, const i32 *map, double *val = nullptr);
 void k_pair_local_idx(cge_ctx *c, const i32 *pi, const i32 *pj, i64 S, const i32 *glob2loc, i32 *idx);
@@ -685,7 +694,6 @@ void k_pair_dist_rows(cge_ctx *c, const double *B, i64 d, const i32 *pi, const i
 void k_position_ids(cge_ctx *c, const i32 *pos2node, const i32 *loc2glob, i64 npos, i32 *ids); // map[argmax v] (synchronises the stream)
 void k_ref_centroids(cge_ctx *c, const double *mu, const double *lw, const i32 *ref_off, const i32 *ref_mem, i64 nref,
                      i64 d, double *out);
-void k_farthest(cge_ctx *c, const double *Xr, i64 n, i64 d, i64 src, double *best_val, i64 *best_i);
 void k_farthest_enqueue(cge_ctx *c, const double *Xr, i64 n, i64 d, i64 src, const double *srow = nullptr); // launch only (c->stream) ...
 void k_farthest_collect(cge_ctx *c, double *best_val, i64 *best_i);            // ... and its result (synchronises c->stream)
 void k_col_mean(cge_ctx *c, const double *Xrow, i64 n, i64 d, double *mean, double sums_only = 0.0);
@@ -846,12 +854,14 @@ void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i
                    std::vector<i64> &group_ids /*0-based*/, bool want_index = false); // also fills c->v2l / lm_mem / lm_memoff (device)
 void host_eig_top(const double *A, i64 d, double *v); // largest-eigenvalue eigenvector, sign: max |.| component > 0
 // diameter_host.cpp
-double host_brute_exact(cge_ctx *c, int part, int nparts, double bv, const std::vector<double> &wg_best, i64 *bi, i64 *bj);
+// the exact diameter of the resident embedding by brute force over this rank's share of the pair tiles (NaN for a non-finite
+// embedding); `ai` / `aj` (optional): a pair attaining it, 1-based
+double host_diameter_brute(cge_ctx *c, int part, int nparts, i64 *ai, i64 *aj);
+// the same by landmark-pair pruning (brute force where the bounds prune too little), the largest of the ranks' shares:
+// `lemb` = N landmark centroids (device, row-major), `lweight` their weights (device), `lcomm` their communities (0-based, C)
+double host_diameter_landmarks(cge_ctx *c, const double *lemb, const double *lweight, const std::vector<i32> &lcomm, i64 C, i64 N);
 void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lcomm1, i64 C, int pass, double *P, i64 *nref_out,
                                int *pass_ran, double *ref_out, double *mean_out);
-bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C, i64 N,
-                          const std::vector<i32> &mem_off, const std::vector<i32> &mem, int part, int nparts,
-                          double *hi, i64 *bi, i64 *bj);
 // wgcl_host.cpp
 // ---- counter-based RNG of the sampler (splitmix64 finaliser over a 4-word counter): the same stream on host and device
 __host__ __device__ inline uint64_t cge_sm64(uint64_t x) {

@@ -1,27 +1,20 @@
-// diameter_host.cpp -- exact point-set diameter `hi = maximum(full_graph_D)` (src/divergence.jl:104-113)
-// by branch-and-bound over landmark pairs, with the brute-force MFMA kernel as fallback.
-//
-// For x_i in landmark a and x_j in landmark b, with ANY reference points mu_a, mu_b:
-//   ||x_i - x_j||^2 <= P_ab + P_ba - ||mu_a - mu_b||^2 + 2 sqrt(P_aa P_bb),   P_ab = max_{i in a} ||x_i - mu_b||^2
-// (expand both sides; the only inequality is Cauchy-Schwarz on <x_i - mu_a, x_j - mu_b>).
-// 1. P (N x N) by one fp64-MFMA pass of all n vertices against the N centroids (n*N*d FMA, ~1 % of the
-//    brute-force work for N = 4000 landmarks on 10^6 vertices);
-// 2. a lower bound L of the diameter^2 from three farthest-point sweeps;
-// 3. every landmark pair whose bound reaches L is evaluated exactly, in decreasing bound order, L rising
-//    as better pairs are found; pairs whose bound falls below L are dropped.
-// The result is the exact arg-max pair whatever the data; only the amount of pruning is data dependent.
-// When fewer than half of the brute-force tiles can be pruned the brute-force kernel runs instead.
+// diameter_host.cpp -- the exact point-set diameter `hi = maximum(full_graph_D)` (src/divergence.jl:104-113): the largest dist()
+// value of any two rows of the resident embedding, with the reference's bits whatever the data.  DESIGN.md 4.5 has the method
+// and its proofs; this file holds, top to bottom:
+//   gram_delta, dm_eval_pairs, dm_collect   the near-ties of an arg-max launch, evaluated in dist()'s own arithmetic;
+//   host_diameter_brute                     every pair tile of the embedding (this rank's share), no pruning;
+//   dm_prepare, dm_bound_pass               the landmark-sorted layout and the bounds P[a][r] >= max_{i in a} ||x_i - ref_r||^2;
+//   host_diameter_pruned                    branch and bound over landmark pairs, a list of stages sharing a DmSearch;
+//   host_diameter_landmarks                 the entry of a score: pruned, brute force where the bounds prune too little;
+//   host_diameter_bounds_test               the testing hook of the bound passes.
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <limits>
 
 #include "common.hpp"
 
 namespace {
-struct BoundRec {
-    double B;
-    i32 a, b;
-};
 // the answer: the largest dist() value of the pairs evaluated so far; ties go to the smallest (i, j)
 struct ExactBest {
     double hi = -1.0;
@@ -30,6 +23,12 @@ struct ExactBest {
         if (a > b) std::swap(a, b);
         if (v > hi || (v == hi && (a < i || (a == i && b < j)))) { hi = v; i = a; j = b; }
     }
+};
+// while one lives, the launch wrappers (they enqueue on c->stream) work on the side stream
+struct SideStream {
+    cge_ctx *c;
+    explicit SideStream(cge_ctx *c_) : c(c_) { std::swap(c->stream, c->copy_stream); }
+    ~SideStream() { std::swap(c->stream, c->copy_stream); }
 };
 } // namespace
 
@@ -84,13 +83,13 @@ static void dm_eval_pairs(cge_ctx *c, const int2 *pairs, i64 cnt, ExactBest &eb)
     std::vector<double> val;
     for (i64 s = 0; s < steps; s++) {
         const i64 k0 = s * RCH, kc = std::max<i64>(0, std::min(RCH, cnt - k0));
-        c->nt_pairs.ensure((size_t)2 * W * RCH);
+        c->nt_pairs.ensure((size_t)W * RCH);
         HIP_CHECK(hipMemsetAsync(c->nt_pairs.p, 0, sizeof(int2) * W * RCH, st));
         std::vector<int2> mine(kc);
         for (i64 k = 0; k < kc; k++) mine[k] = make_int2(pairs[k0 + k].x + 1, pairs[k0 + k].y + 1); // (0 = no pair)
-        if (kc > 0) HIP_CHECK(hipMemcpyAsync(c->nt_pairs.p + (size_t)2 * me * RCH, mine.data(), sizeof(int2) * kc, hipMemcpyHostToDevice, st));
+        if (kc > 0) HIP_CHECK(hipMemcpyAsync(c->nt_pairs.p + (size_t)me * RCH, mine.data(), sizeof(int2) * kc, hipMemcpyHostToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st)); // (`mine` leaves scope)
-        cge_allreduce_dev(c, reinterpret_cast<double *>(c->nt_pairs.p), W * RCH, 2);
+        cge_allreduce_dev(c, reinterpret_cast<double *>(c->nt_pairs.p), W * RCH, 2); // (an int2 is one 8-byte word)
         HIP_CHECK(hipMemcpyAsync(all.data(), c->nt_pairs.p, sizeof(int2) * W * RCH, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         loc.clear();
@@ -132,8 +131,8 @@ static void dm_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, 
                        int tri, double thr, const i32 *ids, Flush flush) {
     const i64 ntiles = (i64)tl.size();
     if (ntiles == 0) return;
-    c->nt_pairs.ensure((size_t)2 * NT_CAP);
-    c->nt_tiles.ensure((size_t)2 * ntiles);
+    c->nt_pairs.ensure((size_t)NT_CAP);
+    c->nt_tiles.ensure((size_t)ntiles);
     HIP_CHECK(hipMemcpyAsync(c->nt_tiles.p, tl.data(), sizeof(int2) * ntiles, hipMemcpyHostToDevice, c->stream));
     std::vector<int2> h;
     i64 t0 = 0, step = std::min<i64>(ntiles, (i64)1 << 17); // (a launch counts its pairs in 32 bits)
@@ -155,22 +154,44 @@ static void dm_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, 
     }
 }
 
-// the brute-force path's last step (capi.cpp: resident_diameter): `bv` = the largest Gram value of this shard's tiles and `wg`
-// the workgroups' own (k_max_pair; bv negative: the shard holds no pair); returns `hi` and a pair attaining it
-double host_brute_exact(cge_ctx *c, int part, int nparts, double bv, const std::vector<double> &wg, i64 *bi, i64 *bj) {
+static void ensure_centred(cge_ctx *c) {
+    if (c->centred_ready) return;
+    if (c->rows_sharded) CGE_THROW(CGE_E_ARG, "the brute-force diameter over the whole embedding needs every row on one rank; the resident rows are sharded (option shard_rows)");
+    if (!c->Xr.p || c->d <= 0) CGE_THROW(CGE_E_ARG, "diameter: embedding not resident");
+    c->Xc.alloc_exact((size_t)c->ldn * c->dpad);
+    c->rnorm.alloc_exact((size_t)c->ldn);
+    k_gather_centre_fm(c, c->Xr.p, nullptr, c->gmean.p, c->Xc.p, c->rnorm.p, c->n, c->d, c->ldn, c->dpad);
+    c->centred_ready = true;
+}
+
+// Brute force over this rank's share of the pair tiles.  The arg-max launch leaves the largest Gram value `bv` of the shard's
+// tiles and the workgroups' own (bv negative: the shard holds no pair); the pairs within rounding of it are evaluated with
+// dist()'s own arithmetic (src/auxilary.jl:14-20) and the largest of THOSE values is `hi` (gram_delta).
+double host_diameter_brute(cge_ctx *c, int part, int nparts, i64 *ai, i64 *aj) {
     ExactBest eb;
-    if (bv > -1.0) { // (identical rows can leave a Gram value a rounding below zero; -1 is "no pair")
-        double rmax = 0.0;
-        k_argmax_mapped(c, c->rnorm.p, c->n, nullptr, &rmax);
-        const double thr = bv - gram_delta(c->dpad, rmax);
-        std::vector<int2> tl;
-        k_max_pair_tile_list(c->ldn, part, nparts, wg, thr, tl);
-        dm_collect(c, c->Xc.p, c->rnorm.p, c->ldn, c->n, c->dpad, tl, 1, thr, nullptr,
-                   [&](const int2 *p, i64 cnt) { dm_eval_pairs(c, p, cnt, eb); });
+    if (c->emb_nonfinite) // (capi.cpp: embedding_resident)
+        eb.hi = std::numeric_limits<double>::quiet_NaN(); // as the reference's extrema()
+    else {
+        ensure_centred(c);
+        double bv;
+        i64 bi, bj;
+        std::vector<double> wg;
+        k_max_pair(c, c->Xc.p, c->rnorm.p, c->n, c->ldn, c->dpad, part, nparts, &bv, &bi, &bj, &wg);
+        if (bv > -1.0) { // (identical rows can leave a Gram value a rounding below zero; -1 is "no pair")
+            double rmax = 0.0;
+            k_argmax_mapped(c, c->rnorm.p, c->n, nullptr, &rmax);
+            const double thr = bv - gram_delta(c->dpad, rmax);
+            std::vector<int2> tl;
+            k_max_pair_tile_list(c->ldn, part, nparts, wg, thr, tl);
+            dm_collect(c, c->Xc.p, c->rnorm.p, c->ldn, c->n, c->dpad, tl, 1, thr, nullptr,
+                       [&](const int2 *p, i64 cnt) { dm_eval_pairs(c, p, cnt, eb); });
+        }
+        if (eb.hi < 0.0) eb.hi = 0.0; // (no pair: vertex 1 with itself)
     }
-    if (eb.hi < 0.0) { *bi = *bj = 0; return 0.0; }
-    *bi = eb.i;
-    *bj = eb.j;
+    c->stat_diameter_path = 1;
+    c->stat_hi_i = eb.i; c->stat_hi_j = eb.j;
+    if (ai) *ai = eb.i + 1;
+    if (aj) *aj = eb.j + 1;
     return eb.hi;
 }
 
@@ -333,269 +354,307 @@ static void dm_bound_pass(cge_ctx *c, const DmPrep &S, i64 N, int part, int npar
         HIP_CHECK(hipMemsetAsync(c->Pm.p, 0, sizeof(double) * (size_t)(N * S.nref), c->stream));
 }
 
-// returns false when the caller should fall back to brute force
-// `mu` = N landmark centroids (device, row-major), `lw` their weights (device) and `lcomm` their communities
-// (host, 0-based, C communities).  Reference points: the community centroids when there are at least 32
-// communities (the MFMA pass is then n*C*d instead of n*N*d), else the landmark centroids themselves.
+// ---- the pruned search: what its stages share ------------------------------------------------------------------------------
+// `mu` = N landmark centroids (device, row-major), `lw` their weights (device) and `lcomm` their communities (host, 0-based, C
+// communities).  Reference points: the community centroids when there are at least 32 communities (the MFMA pass is then
+// n*C*d instead of n*N*d), else the landmark centroids themselves.
 //
-// THE EXACT STAGE WORKS ON GATHERED ROWS (round 4).  The bound pass reads the bf16 planes (or the f32 copy) of the
-// landmark-sorted rows, so no fp64 copy of the whole embedding is written any more (it was 1 GB written and 1 GB cleared per
-// score at the headline); the few landmarks that survive the bounds are gathered per round -- centred, feature-major, fp64 --
-// into `xe`, and the fp64-MFMA tile kernel runs on that.
+// THE EXACT STAGE WORKS ON GATHERED ROWS: no fp64 copy of the whole landmark-sorted embedding is written; the few landmarks that
+// survive the bounds are gathered per round -- centred, feature-major, fp64 -- into `xe`, and the tile kernel runs on that.
 //
 // OPTION shard_rows (c->rows_sharded): `mem_off` / the device index hold THIS RANK's members (local row ids, other ranks'
 // landmarks are empty ranges), c->h_gl_off the global sizes.  Every rank bounds its own rows (all-reduce(max) of the bound
 // matrix), the seed row of the farthest-point sweep is fetched from its owner, and the gathered rows of a round are
 // completed by an all-reduce of the zero-filled gather (op 2: exact), so a candidate pair whose landmarks live on two ranks
 // is evaluated like any other; the rounds are taken in lock-step (the best value so far is all-reduced after each).
-bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C, i64 N,
-                          const std::vector<i32> &mem_off, const std::vector<i32> &mem, int part, int nparts,
-                          double *hi, i64 *bi, i64 *bj) {
-    const i64 n = c->n, d = c->d, dpad = c->dpad;
-    const bool RS = c->rows_sharded;
-    const i64 n_rows = lm_rows(c);
-    const int W = RS ? c->coll.world : 1, me = RS ? c->coll.rank : 0;
-    hipStream_t st = c->stream;
-    c->stat_cand_pairs = c->stat_cand_tiles = 0;
-    double tphase = now_ms();
-    auto lap = [&](const char *name) { // host wall time per stage (the stream is not synchronised here)
-        const double t = now_ms();
-        c->phases.ms[name] += t - tphase;
-        tphase = t;
-    };
-    if (RS && ((i64)c->h_gl_off.size() != N + 1 || !c->lm_index_on_device || mem_off.data() != c->h_mem_off.data()))
-        CGE_THROW(CGE_E_ARG, "diameter (shard_rows): the landmark index of this context's own landmark phase is required");
-    const std::vector<i32> &gl_off = RS ? c->h_gl_off : mem_off; // sizes of the WHOLE landmarks
-    DmPrep S;
-    if (!dm_prepare(c, mu, lw, lcomm, C, N, mem_off, mem, S, lap)) return false;
-    const i64 nref = S.nref, ldm = S.ldm;
-    const i32 *d_off = S.d_off, *d_mem = S.d_mem;
-    const bool by_comm = S.by_comm;
-    const double *mu_ref = S.mu_ref;
-    const double seed_norm = S.seed_norm;
-    const i64 seed_vertex = S.seed_vertex;
-    // Q is a maximum over vertices: with several ranks each takes its share of the vertex tiles (all of its own rows when the
-    // rows are sharded) and the maxima are combined by one all-reduce(max)
-    const bool shard_q = !RS && nparts > 1 && c->has_coll && (c->rccl_comm || (c->xptr && (size_t)(N * nref) <= c->xcap));
-    // One farthest-point sweep from the vertex farthest from the centre (a memory-bound read of Xr) on the side stream, LAUNCHED
-    // AHEAD of the bound pass: its small workgroups then fill the CUs first and the sweep runs at its own speed (~0.3 ms) while
-    // the bound pass's one-workgroup-per-CU tiles move in beside them -- launched behind it, the sweep was left the gaps
-    // (1.0 ms, the longer of the two concurrent branches).  Its result is collected after the bound pass has been enqueued.
-    i64 seed_glob = seed_vertex;
-    if (RS) {
-        // the seed is the farthest of ALL ranks' rows: the largest norm wins (ties: the lowest rank), its owner hands the row
-        // itself (and its vertex id) to everybody; the sweep then runs over every rank's own rows on the main stream
-        const double vmax = cge_allreduce_scalar_max(c, seed_norm);
-        const double claim = cge_allreduce_scalar_max(c, (seed_norm == vmax && seed_vertex >= 0) ? (double)(W - me) : 0.0);
-        const int winner = W - (int)claim;
-        c->dm_seed.ensure(d + 1);
-        HIP_CHECK(hipMemsetAsync(c->dm_seed.p, 0, sizeof(double) * (d + 1), st));
-        if (winner == me) {
-            HIP_CHECK(hipMemcpyAsync(c->dm_seed.p, c->Xr.p + seed_vertex * d, sizeof(double) * d, hipMemcpyDeviceToDevice, st));
-            const double gid = (double)(c->h_loc2glob[seed_vertex] + 1);
-            HIP_CHECK(hipMemcpyAsync(c->dm_seed.p + d, &gid, sizeof(double), hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipStreamSynchronize(st)); // gid is a stack variable
-        }
-        cge_allreduce_dev(c, c->dm_seed.p, d + 1, 2);
-        double gid = 0.0;
-        HIP_CHECK(hipMemcpyAsync(&gid, c->dm_seed.p + d, sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        seed_glob = (i64)gid - 1;
-        k_farthest_enqueue(c, c->Xr.p, n_rows, d, 0, c->dm_seed.p);
-        k_ref_dist2_fm(c, c->Ms.p, nref, dpad, ldm);
-    } else {
-        std::swap(c->stream, c->copy_stream);
-        try {
-            k_farthest_enqueue(c, c->Xr.p, n, d, seed_vertex);
-            // the reference points' mutual distances (candidate selection) do not depend on the bound pass either: beside it
-            // (the gathers that wrote Ms are done: the seed's read-back above synchronised the main stream)
-            k_ref_dist2_fm(c, c->Ms.p, nref, dpad, ldm);
-        } catch (...) {
-            std::swap(c->stream, c->copy_stream);
-            throw;
-        }
-        std::swap(c->stream, c->copy_stream);
-    }
-    // the sweep's result (a double and an id in c->mp_recs) is read before the bound pass may reuse that scratch
-    double L = 0.0, rmax = seed_norm; // (rmax: the largest squared norm of a centred row, of all ranks)
-    i64 far_i = seed_glob, far_j = seed_glob;
-    if (RS) {
-        rmax = cge_allreduce_scalar_max(c, seed_norm);
-        double v = -1.0;
-        i64 q = 0;
-        k_farthest_collect(c, &v, &q);
-        const double Lmax = cge_allreduce_scalar_max(c, v);
-        const double claim = cge_allreduce_scalar_max(c, v == Lmax ? (double)(W - me) : 0.0);
-        const double qid = cge_allreduce_scalar_max(c, (W - (int)claim) == me ? (double)(c->h_loc2glob[q] + 1) : 0.0);
-        if (Lmax > L) { L = Lmax; far_j = (i64)qid - 1; }
-    }
-    dm_bound_pass(c, S, N, shard_q ? part : 0, shard_q ? nparts : 1);
-    if (shard_q || RS) cge_allreduce_dev(c, c->Pm.p, N * nref, 1);
-    lap("dm_refs_pcent");
-    // ---- lower bound from the farthest-point sweep ----------------------------------------------------------
-    if (!RS) {
-        std::swap(c->stream, c->copy_stream);
-        try {
-            double v;
-            i64 q;
-            k_farthest_collect(c, &v, &q);
-            if (v > L) { L = v; far_i = seed_vertex; far_j = q; }
-        } catch (...) {
-            std::swap(c->stream, c->copy_stream);
-            throw;
-        }
-        std::swap(c->stream, c->copy_stream);
-    }
-    lap("dm_farthest");
-    // ---- candidate landmark pairs ---------------------------------------------------------------------------
-    // The sweep's L is a distance in a THIRD arithmetic (16 partial sums per row): it enters the search as a bound on the Gram
-    // values, delta below itself (gram_delta: eta covers any summation order), and its pair as the first evaluated candidate.
-    // The selection below and the stop test of the rounds compare bounds with relative margins of 1e-9 on either side: with
-    // rmax <= L (the seed is the row farthest from the centre, and some row lies at least that far from it) delta is below
-    // 2e-12 L for every d <= 512, so those margins already leave delta of room a hundred times over.
-    const double delta = gram_delta(dpad, std::max(rmax, 0.0));
+struct DmSearch {
+    cge_ctx *c;
+    const bool RS;                  // option shard_rows ...
+    const int W, me;                // ... and then the ranks that hold the rows, this one among them (else 1, 0)
+    const int part, nparts;         // this rank's share of work on rows that every rank holds
+    const i64 N;
+    const std::vector<i32> &gl_off; // sizes of the WHOLE landmarks
+    DmPrep prep;
+    double rmax = -1.0;             // the largest squared norm of a centred row, of all ranks
+    double L = 0.0;                 // the sweep's lower bound of the diameter^2 and its pair (global vertex ids; the seed first)
+    i64 far_i = -1, far_j = -1;
+    double delta = 0.0;             // gram_delta of this embedding
     ExactBest eb;
-    {
-        const int2 far = make_int2((int)far_i, (int)far_j);
-        dm_eval_pairs(c, &far, 1, eb);
+    double best = 0.0;              // a lower bound of the largest Gram value
+    std::vector<BoundRec> cand;     // the candidate landmark pairs: a heap in [0, left), largest bound first
+    size_t left = 0;
+    double tphase = now_ms();
+    void lap(const char *name) { const double t = now_ms(); c->phases.ms[name] += t - tphase; tphase = t; } // host wall time per stage
+    i64 len16(i64 a) const { return (i64)((gl_off[a + 1] - gl_off[a] + 15) / 16 * 16); } // positions of the WHOLE landmark
+    // the 128x128 tiles of a candidate pair: tile rows (x < ta) times tile columns (y < tb), of a landmark with itself those with y >= x
+    i64 pair_tiles(const BoundRec &r, const std::function<void(i64, i64)> &visit = nullptr) const {
+        const i64 ta = (len16(r.a) + 127) / 128, tb = (len16(r.b) + 127) / 128;
+        if (visit)
+            for (i64 x = 0; x < ta; x++)
+                for (i64 y = (r.a == r.b ? x : 0); y < tb; y++) visit(x, y);
+        return r.a == r.b ? ta * (ta + 1) / 2 : ta * tb;
     }
-    const i64 cap = std::min<i64>(N * (N + 1) / 2, (i64)4 << 20);
-    c->bound_list.ensure((size_t)2 * cap);
-    const i64 cnt = k_bound_select(c, c->Pm.p, c->mp_lref.p, mu_ref, N, nref, d, L * (1.0 - 1e-9), c->bound_list.p, cap,
-                                   by_comm ? c->mp_refoff.p : nullptr, by_comm ? c->mp_refmem.p : nullptr, nullptr, dpad, ldm, true);
+};
+static bool cand_later(const BoundRec &x, const BoundRec &y) { // x comes after y: decreasing bound, ties by landmark pair
+    return x.B < y.B || (x.B == y.B && (x.a > y.a || (x.a == y.a && x.b > y.b)));
+}
+
+// The lowest rank among those whose `v` is the largest of all ranks' wins (`can`: this rank may win); *vmax = that largest value.
+// Collective: every rank of the shard_rows group calls it, and gets the same answer (world when nobody can win).
+static int dm_elect(cge_ctx *c, double v, bool can, double *vmax) {
+    const int W = c->coll.world, me = c->coll.rank;
+    *vmax = cge_allreduce_scalar_max(c, v);
+    const double claim = cge_allreduce_scalar_max(c, (v == *vmax && can) ? (double)(W - me) : 0.0);
+    return W - (int)claim;
+}
+
+// One farthest-point sweep from the vertex farthest from the centre (a memory-bound read of Xr) and the reference points' mutual
+// distances (candidate selection), enqueued on the side stream AHEAD of the bound pass: neither depends on it (the gathers that
+// wrote Ms are done: the seed's read-back in dm_prepare synchronised the main stream).  Launched first, the sweep's small
+// workgroups fill the CUs and it runs at its own speed (~0.3 ms) while the bound pass's one-workgroup-per-CU tiles move in
+// beside them -- launched behind it, the sweep was left the gaps (1.0 ms, the longer of the two concurrent branches).
+static void dm_seed_sweep(DmSearch &S) {
+    cge_ctx *c = S.c;
+    const DmPrep &P = S.prep;
+    const i64 d = c->d;
+    if (!S.RS) {
+        S.far_i = S.far_j = P.seed_vertex;
+        S.rmax = P.seed_norm;
+        SideStream side(c);
+        k_farthest_enqueue(c, c->Xr.p, c->n, d, P.seed_vertex);
+        k_ref_dist2_fm(c, c->Ms.p, P.nref, c->dpad, P.ldm);
+        return;
+    }
+    // option shard_rows: the seed is the farthest of ALL ranks' rows, its owner hands the row itself (and its vertex id) to
+    // everybody; the sweep then runs over every rank's own rows on the main stream
+    hipStream_t st = c->stream;
+    const int winner = dm_elect(c, P.seed_norm, P.seed_vertex >= 0, &S.rmax);
+    c->dm_seed.ensure(d + 1);
+    HIP_CHECK(hipMemsetAsync(c->dm_seed.p, 0, sizeof(double) * (d + 1), st));
+    if (winner == S.me) {
+        HIP_CHECK(hipMemcpyAsync(c->dm_seed.p, c->Xr.p + P.seed_vertex * d, sizeof(double) * d, hipMemcpyDeviceToDevice, st));
+        const double gid = (double)(c->h_loc2glob[P.seed_vertex] + 1);
+        HIP_CHECK(hipMemcpyAsync(c->dm_seed.p + d, &gid, sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // gid is a stack variable
+    }
+    cge_allreduce_dev(c, c->dm_seed.p, d + 1, 2);
+    double gid = 0.0;
+    HIP_CHECK(hipMemcpyAsync(&gid, c->dm_seed.p + d, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    S.far_i = S.far_j = (i64)gid - 1;
+    k_farthest_enqueue(c, c->Xr.p, lm_rows(c), d, 0, c->dm_seed.p);
+    k_ref_dist2_fm(c, c->Ms.p, P.nref, c->dpad, P.ldm);
+}
+
+// The bound pass (c->Pm) and the sweep's lower bound L.  The sweep left its result (a double and an id per workgroup) in
+// c->mp_recs, scratch of the arg-max launches.  With shard_rows the sweep shares the main stream with everything else and its
+// result is collected BEFORE the bound pass; without, it runs on the side stream and is collected AFTER the bound pass has been
+// enqueued (the bound passes do not touch c->mp_recs): a collect in front would wait for the sweep with the bound pass not
+// yet launched, and the overlap the sweep was launched ahead for would be gone.
+static void dm_bounds(DmSearch &S) {
+    cge_ctx *c = S.c;
+    const DmPrep &P = S.prep;
+    double v = -1.0, Lmax;
+    i64 q = 0;
+    if (S.RS) {
+        k_farthest_collect(c, &v, &q);
+        const int winner = dm_elect(c, v, true, &Lmax);
+        const double qid = cge_allreduce_scalar_max(c, winner == S.me ? (double)(c->h_loc2glob[q] + 1) : 0.0);
+        if (Lmax > S.L) { S.L = Lmax; S.far_j = (i64)qid - 1; }
+    }
+    // P is a maximum over vertices: with several ranks each takes its share of the vertex tiles (all of its own rows when the
+    // rows are sharded) and the maxima are combined by one all-reduce(max)
+    const bool shard_q = !S.RS && S.nparts > 1 && c->has_coll && (c->rccl_comm || (c->xptr && (size_t)(S.N * P.nref) <= c->xcap));
+    dm_bound_pass(c, P, S.N, shard_q ? S.part : 0, shard_q ? S.nparts : 1);
+    if (shard_q || S.RS) cge_allreduce_dev(c, c->Pm.p, S.N * P.nref, 1);
+    S.lap("dm_refs_pcent");
+    if (!S.RS) {
+        SideStream side(c);
+        k_farthest_collect(c, &v, &q);
+        if (v > S.L) { S.L = v; S.far_j = q; }
+    }
+    S.lap("dm_farthest");
+}
+
+// The candidate landmark pairs: those whose bound reaches L, as a heap.  Returns false when the bounds prune too little.
+// The sweep's L is a distance in a THIRD arithmetic (16 partial sums per row): it enters the search as a bound on the Gram
+// values, delta below itself (gram_delta: eta covers any summation order), and its pair as the first evaluated candidate.
+// The selection here and the stop test of the rounds compare bounds with relative margins of 1e-9 on either side: with
+// rmax <= L (the seed is the row farthest from the centre, and some row lies at least that far from it) delta is below
+// 2e-12 L for every d <= 512, so those margins already leave delta of room a hundred times over.
+static bool dm_select(DmSearch &S) {
+    cge_ctx *c = S.c;
+    const DmPrep &P = S.prep;
+    S.delta = gram_delta(c->dpad, std::max(S.rmax, 0.0));
+    const int2 far = make_int2((int)S.far_i, (int)S.far_j);
+    dm_eval_pairs(c, &far, 1, S.eb);
+    const i64 cap = std::min<i64>(S.N * (S.N + 1) / 2, (i64)4 << 20);
+    c->bound_list.ensure((size_t)cap);
+    const i64 cnt = k_bound_select(c, c->Pm.p, c->mp_lref.p, S.N, P.nref, S.L * (1.0 - 1e-9), c->bound_list.p, cap,
+                                   P.by_comm ? c->mp_refoff.p : nullptr, P.by_comm ? c->mp_refmem.p : nullptr);
     c->stat_cand_pairs = cnt;
     if (cnt > cap) {
-        if (RS) CGE_THROW(CGE_E_ARG, "diameter (shard_rows): the bounds prune too little (more than %lld candidate landmark pairs) and the brute-force "
-                                     "fallback needs every row on one rank", (long long)cap);
+        if (S.RS) CGE_THROW(CGE_E_ARG, "diameter (shard_rows): the bounds prune too little (more than %lld candidate landmark pairs) and the brute-force "
+                                       "fallback needs every row on one rank", (long long)cap);
         return false;
     }
-    std::vector<BoundRec> cand(cnt);
+    S.cand.resize(cnt);
     if (cnt > 0) {
-        HIP_CHECK(hipMemcpyAsync(cand.data(), c->bound_list.p, sizeof(BoundRec) * cnt, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipMemcpyAsync(S.cand.data(), c->bound_list.p, sizeof(BoundRec) * cnt, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    lap("dm_select");
+    S.lap("dm_select");
     // candidates are consumed in decreasing-bound order (ties: by landmark pair) until the bound drops below the best
     // pair found: a heap delivers exactly that order without sorting the (mostly never visited) tail
-    auto later = [](const BoundRec &x, const BoundRec &y) { // x comes after y
-        return x.B < y.B || (x.B == y.B && (x.a > y.a || (x.a == y.a && x.b > y.b)));
-    };
-    std::make_heap(cand.begin(), cand.end(), later);
-    auto len16 = [&](i64 a) { return (i64)((gl_off[a + 1] - gl_off[a] + 15) / 16 * 16); }; // positions of the WHOLE landmark
-    auto ntiles_of = [&](i64 a) { return (len16(a) + 127) / 128; };
+    std::make_heap(S.cand.begin(), S.cand.end(), cand_later);
+    S.left = S.cand.size();
     double tiles_total = 0.0;
-    for (const auto &r : cand) {
-        const double ta = (double)ntiles_of(r.a), tb = (double)ntiles_of(r.b);
-        tiles_total += (r.a == r.b) ? ta * (ta + 1) / 2 : ta * tb;
-    }
-    const double nT = (double)((n + 127) / 128);
-    if (!RS && c->opt_diameter != 2 && tiles_total > 0.5 * nT * (nT + 1) / 2) return false; // pruning too weak: brute force
-    // ---- exact evaluation in decreasing-bound order, round by round, on the gathered rows of the round's landmarks --------
-    const int xparts = RS ? W : nparts, xpart = RS ? me : part; // who evaluates which tile of a round
-    double best = L - delta; // a lower bound of the largest Gram value: the farthest-point pair is a valid answer so far
-    std::vector<double> wg_best; // the best Gram value of each workgroup of a round's arg-max launch
-    std::vector<int2> near;      // the round's tiles that can hold a near-tie
-    std::vector<int2> pool;      // (option shard_rows: a round's near-ties of this rank, evaluated together with the other ranks')
-    size_t left = cand.size(); // the heap is cand[0, left)
-    i64 tile_cap = 4096, global_tile = 0;
-    const i64 pos_cap = std::max<i64>(8192, ((i64)512 << 20) / (dpad * 8)); // <= 512 MB of gathered rows per round
-    std::vector<int2> tiles;
-    std::vector<BoundRec> round;
-    std::vector<i32> eoff(N + 1);
-    std::vector<char> in_round(N, 0);
-    std::vector<i32> lms;
-    while (left > 0) {
-        round.clear();
-        lms.clear();
-        i64 E = 0, ntile = 0;
-        while (left > 0 && ntile < tile_cap) {
-            std::pop_heap(cand.begin(), cand.begin() + left, later);
-            const BoundRec r = cand[left - 1];
-            if (r.B * (1.0 + 1e-9) + 1e-9 < best) { left = 0; break; } // decreasing order: nothing further can win
-            const i64 extra = (in_round[r.a] ? 0 : len16(r.a)) + ((r.b != r.a && !in_round[r.b]) ? len16(r.b) : 0);
-            if (!round.empty() && E + extra > pos_cap) { // the round is full: the pair goes back, the next round takes it
-                std::push_heap(cand.begin(), cand.begin() + left, later);
-                break;
-            }
-            left--;
-            round.push_back(r);
-            for (i32 a : {r.a, r.b})
-                if (!in_round[a]) { in_round[a] = 1; lms.push_back(a); E += len16(a); }
-            const i64 ta = ntiles_of(r.a), tb = ntiles_of(r.b);
-            ntile += (r.a == r.b) ? ta * (ta + 1) / 2 : ta * tb;
-        }
-        if (round.empty()) break;
-        // positions of the round: its landmarks in ascending id, each padded to 16 (a landmark outside the round: no position)
-        {
-            i64 at = 0;
-            for (i64 a = 0; a < N; a++) {
-                eoff[a] = (i32)at;
-                if (in_round[a]) at += len16(a);
-            }
-            eoff[N] = (i32)at;
-        }
-        const i64 ldE = (E + 127) / 128 * 128 + 128;
-        c->dm_soffE.ensure(N + 1); c->xe_pos.ensure(E); c->xe_glob.ensure(E + 2); c->xe_sub.ensure(ldE / 16);
-        c->xe.ensure((size_t)ldE * dpad); c->xe_rns.ensure(ldE);
-        {
-            WordPacker pk(c);
-            pk.add(c->dm_soffE.p, eoff.data(), N + 1);
-            pk.flush();
-        }
-        k_diameter_layout(c, d_off, d_mem, c->dm_soffE.p, N, c->xe_pos.p, c->xe_sub.p, ldE / 16);
-        k_gather_centre_fm(c, c->Xr.p, c->xe_pos.p, c->gmean.p, c->xe.p, c->xe_rns.p, E, d, ldE, dpad);
-        k_position_ids(c, c->xe_pos.p, RS ? c->loc2glob.p : nullptr, E, c->xe_glob.p);
-        if (RS) { // every rank has filled the rows it owns: the ranks add the words (zeros elsewhere: exact)
-            HIP_CHECK(hipMemsetAsync(c->xe_glob.p + E, 0, sizeof(i32) * 2, st));
-            cge_allreduce_dev(c, c->xe.p, ldE * dpad, 2);
-            cge_allreduce_dev(c, c->xe_rns.p, ldE, 2);
-            cge_allreduce_dev(c, reinterpret_cast<double *>(c->xe_glob.p), (E + 1) / 2, 2);
-        }
-        tiles.clear();
-        for (const BoundRec &r : round) {
-            const i64 ta = ntiles_of(r.a), tb = ntiles_of(r.b);
-            for (i64 x = 0; x < ta; x++)
-                for (i64 y = (r.a == r.b ? x : 0); y < tb; y++) {
-                    if ((global_tile++ % xparts) != xpart) continue;
-                    tiles.push_back(make_int2((int)(eoff[r.a] + 128 * x), (int)(eoff[r.b] + 128 * y)));
-                }
-        }
-        for (i32 a : lms) in_round[a] = 0;
-        double v = -1.0;
-        if (!tiles.empty()) {
-            c->stat_cand_tiles += (i64)tiles.size();
-            c->tile_list.ensure(2 * tiles.size());
-            {
-                WordPacker pk(c);
-                pk.add(reinterpret_cast<i32 *>(c->tile_list.p), reinterpret_cast<const i32 *>(tiles.data()), (i64)(2 * tiles.size()));
-                pk.flush();
-            }
-            i64 pi, pj;
-            k_pair_list(c, c->xe.p, c->xe_rns.p, ldE, E, dpad, c->tile_list.p, (i64)tiles.size(), &v, &pi, &pj, &wg_best);
-        }
-        if (RS) v = cge_allreduce_scalar_max(c, v); // the rounds are taken in lock-step with one threshold
-        if (v > best) best = v;
-        if (v >= best - delta) { // the round holds pairs that may carry the maximum: their dist() values decide
-            pool.clear();
-            near.clear();
-            if (!tiles.empty())
-                for (size_t t = 0; t < tiles.size(); t++)
-                    if (wg_best[t % wg_best.size()] >= best - delta) near.push_back(tiles[t]);
-            if (!near.empty())
-                dm_collect(c, c->xe.p, c->xe_rns.p, ldE, E, dpad, near, 0, best - delta, c->xe_glob.p,
-                           [&](const int2 *p, i64 cnt) {
-                               if (RS) pool.insert(pool.end(), p, p + cnt);
-                               else dm_eval_pairs(c, p, cnt, eb);
-                           });
-            if (RS) dm_eval_pairs(c, pool.data(), (i64)pool.size(), eb);
-        }
-        tile_cap = 131072;
-    }
-    lap("dm_exact");
-    *hi = eb.hi;
-    *bi = eb.i;
-    *bj = eb.j;
+    for (const BoundRec &r : S.cand) tiles_total += (double)S.pair_tiles(r);
+    const double nT = (double)((c->n + 127) / 128);
+    if (!S.RS && c->opt_diameter != 2 && tiles_total > 0.5 * nT * (nT + 1) / 2) return false; // pruning too weak: brute force
+    S.best = S.L - S.delta; // the farthest-point pair is a valid answer so far
     return true;
+}
+
+// A round of the exact evaluation: the next candidates, as many as fit the tile and row budgets, on the gathered rows of their landmarks
+struct DmRound {
+    std::vector<BoundRec> pairs;
+    std::vector<i32> lms;       // its landmarks ...
+    std::vector<char> in_round; // ... as flags (all clear between rounds)
+    std::vector<i32> eoff;      // landmark a owns the positions [eoff[a], eoff[a + 1]) of the round (outside the round: none)
+    i64 E = 0, ldE = 0;         // positions / the row stride of xe
+    i64 tile_cap = 4096;        // the first round is short: it usually raises `best` past most of the candidates
+    i64 global_tile = 0;        // tiles so far: tile t is evaluated by rank t % (ranks)
+    explicit DmRound(i64 N) : in_round(N, 0), eoff(N + 1) {}
+};
+
+// pops the round's pairs off the heap; false: nothing left that can win
+static bool dm_round_fill(DmSearch &S, DmRound &R) {
+    const i64 pos_cap = std::max<i64>(8192, ((i64)512 << 20) / (S.c->dpad * 8)); // <= 512 MB of gathered rows per round
+    std::vector<BoundRec> &cand = S.cand;
+    R.pairs.clear();
+    R.lms.clear();
+    R.E = 0;
+    i64 ntile = 0;
+    while (S.left > 0 && ntile < R.tile_cap) {
+        std::pop_heap(cand.begin(), cand.begin() + S.left, cand_later);
+        const BoundRec r = cand[S.left - 1];
+        if (r.B * (1.0 + 1e-9) + 1e-9 < S.best) { S.left = 0; break; } // decreasing order: nothing further can win
+        const i64 extra = (R.in_round[r.a] ? 0 : S.len16(r.a)) + ((r.b != r.a && !R.in_round[r.b]) ? S.len16(r.b) : 0);
+        if (!R.pairs.empty() && R.E + extra > pos_cap) { // the round is full: the pair goes back, the next round takes it
+            std::push_heap(cand.begin(), cand.begin() + S.left, cand_later);
+            break;
+        }
+        S.left--;
+        R.pairs.push_back(r);
+        for (i32 a : {r.a, r.b})
+            if (!R.in_round[a]) { R.in_round[a] = 1; R.lms.push_back(a); R.E += S.len16(a); }
+        ntile += S.pair_tiles(r);
+    }
+    R.tile_cap = 131072;
+    return !R.pairs.empty();
+}
+
+// positions of the round -- its landmarks in ascending id, each padded to 16 -- and their rows: centred, feature-major, with
+// norms and vertex ids
+static void dm_round_gather(DmSearch &S, DmRound &R) {
+    cge_ctx *c = S.c;
+    const i64 N = S.N, d = c->d, dpad = c->dpad, E = R.E;
+    i64 at = 0;
+    for (i64 a = 0; a < N; a++) {
+        R.eoff[a] = (i32)at;
+        if (R.in_round[a]) at += S.len16(a);
+    }
+    R.eoff[N] = (i32)at;
+    for (i32 a : R.lms) R.in_round[a] = 0;
+    const i64 ldE = R.ldE = (E + 127) / 128 * 128 + 128;
+    c->dm_soffE.ensure(N + 1); c->xe_pos.ensure(E); c->xe_glob.ensure(E + 2); c->xe_sub.ensure(ldE / 16);
+    c->xe.ensure((size_t)ldE * dpad); c->xe_rns.ensure(ldE);
+    WordPacker pk(c);
+    pk.add(c->dm_soffE.p, R.eoff.data(), N + 1);
+    pk.flush();
+    k_diameter_layout(c, S.prep.d_off, S.prep.d_mem, c->dm_soffE.p, N, c->xe_pos.p, c->xe_sub.p, ldE / 16);
+    k_gather_centre_fm(c, c->Xr.p, c->xe_pos.p, c->gmean.p, c->xe.p, c->xe_rns.p, E, d, ldE, dpad);
+    k_position_ids(c, c->xe_pos.p, S.RS ? c->loc2glob.p : nullptr, E, c->xe_glob.p);
+    if (S.RS) { // every rank has filled the rows it owns: the ranks add the words (zeros elsewhere: exact)
+        HIP_CHECK(hipMemsetAsync(c->xe_glob.p + E, 0, sizeof(i32) * 2, c->stream));
+        cge_allreduce_dev(c, c->xe.p, ldE * dpad, 2);
+        cge_allreduce_dev(c, c->xe_rns.p, ldE, 2);
+        cge_allreduce_dev(c, reinterpret_cast<double *>(c->xe_glob.p), (E + 1) / 2, 2);
+    }
+}
+
+// this rank's tiles of the round through the arg-max kernel; when the round's best Gram value comes within delta of the best
+// so far, its near-ties are collected and their dist() values decide
+static void dm_round_eval(DmSearch &S, DmRound &R) {
+    cge_ctx *c = S.c;
+    const int xparts = S.RS ? S.W : S.nparts, xpart = S.RS ? S.me : S.part; // who evaluates which tile
+    std::vector<int2> tiles, near, pool; // this rank's tiles / those that can hold a near-tie / (shard_rows) its near-ties, pooled with the other ranks'
+    std::vector<double> wg_best;         // the best Gram value of each workgroup of the arg-max launch
+    for (const BoundRec &r : R.pairs)
+        S.pair_tiles(r, [&](i64 x, i64 y) {
+            if ((R.global_tile++ % xparts) == xpart) tiles.push_back(make_int2((int)(R.eoff[r.a] + 128 * x), (int)(R.eoff[r.b] + 128 * y)));
+        });
+    double v = -1.0;
+    if (!tiles.empty()) {
+        c->stat_cand_tiles += (i64)tiles.size();
+        c->tile_list.ensure(tiles.size());
+        WordPacker pk(c);
+        pk.add(c->tile_list.p, tiles.data(), (i64)tiles.size());
+        pk.flush();
+        i64 pi, pj;
+        k_pair_list(c, c->xe.p, c->xe_rns.p, R.ldE, R.E, c->dpad, c->tile_list.p, (i64)tiles.size(), &v, &pi, &pj, &wg_best);
+    }
+    if (S.RS) v = cge_allreduce_scalar_max(c, v); // the rounds are taken in lock-step with one threshold
+    if (v > S.best) S.best = v;
+    const double thr = S.best - S.delta;
+    if (!(v >= thr)) return; // else the round holds pairs that may carry the maximum
+    for (size_t t = 0; t < tiles.size(); t++)
+        if (wg_best[t % wg_best.size()] >= thr) near.push_back(tiles[t]);
+    dm_collect(c, c->xe.p, c->xe_rns.p, R.ldE, R.E, c->dpad, near, 0, thr, c->xe_glob.p, [&](const int2 *p, i64 cnt) {
+        if (S.RS) pool.insert(pool.end(), p, p + cnt);
+        else dm_eval_pairs(c, p, cnt, S.eb);
+    });
+    if (S.RS) dm_eval_pairs(c, pool.data(), (i64)pool.size(), S.eb);
+}
+
+// returns false when the caller should fall back to brute force
+// (the landmark index is the one this context's landmark phase left: c->h_mem_off / c->h_mem)
+static bool host_diameter_pruned(cge_ctx *c, const double *mu, const double *lw, const std::vector<i32> &lcomm, i64 C, i64 N,
+                                 int part, int nparts, ExactBest &eb) {
+    const bool RS = c->rows_sharded;
+    c->stat_cand_pairs = c->stat_cand_tiles = 0;
+    if (RS && ((i64)c->h_gl_off.size() != N + 1 || !c->lm_index_on_device))
+        CGE_THROW(CGE_E_ARG, "diameter (shard_rows): the landmark index of this context's own landmark phase is required");
+    DmSearch S{c, RS, RS ? c->coll.world : 1, RS ? c->coll.rank : 0, part, nparts, N, RS ? c->h_gl_off : c->h_mem_off};
+    if (!dm_prepare(c, mu, lw, lcomm, C, N, c->h_mem_off, c->h_mem, S.prep, [&](const char *name) { S.lap(name); })) return false;
+    dm_seed_sweep(S);
+    dm_bounds(S);
+    if (!dm_select(S)) return false;
+    DmRound R(N);
+    while (dm_round_fill(S, R)) {
+        dm_round_gather(S, R);
+        dm_round_eval(S, R);
+    }
+    S.lap("dm_exact");
+    eb = S.eb;
+    return true;
+}
+
+// The diameter of a score, full_graph_D's normaliser (src/divergence.jl:104-114): the largest of the ranks' shares.  Brute force when
+// the option asks for it, without a landmark index, or when the bounds prune too little (sharded rows: the pruned search only).
+double host_diameter_landmarks(cge_ctx *c, const double *lemb, const double *lweight, const std::vector<i32> &lcomm, i64 C, i64 N) {
+    const int part = c->has_coll ? c->coll.rank : 0, nparts = c->has_coll ? c->coll.world : 1;
+    ExactBest eb;
+    if (!c->emb_nonfinite && (c->opt_diameter != 1 || c->rows_sharded) && (i64)c->h_mem_off.size() == N + 1 &&
+        host_diameter_pruned(c, lemb, lweight, lcomm, C, N, part, nparts, eb)) {
+        c->stat_diameter_path = 2;
+        c->stat_hi_i = eb.i; c->stat_hi_j = eb.j;
+    } else
+        eb.hi = host_diameter_brute(c, part, nparts, nullptr, nullptr);
+    const double hi = cge_allreduce_scalar_max(c, eb.hi);
+    c->stat_last_hi = hi;
+    return hi;
 }
 
 // Testing hook (include/cge_hip_testing.h: cge_diameter_bounds_test): dm_prepare and dm_bound_pass -- the same launch wrappers

@@ -151,11 +151,6 @@ void k_normalise(cge_ctx *c, double *D, i64 N, const double *lo_hi) {
 //
 // MFMA operand maps (cdna_hip_programming.md §3, f64 note): A lane l -> A[row l&15][k l>>4],
 // B lane l -> B[k l>>4][col l&15]; C/D lane l, reg r -> row (l>>4) + 4r, col l&15.
-struct MaxRec {
-    double val;
-    i64 i, j;
-};
-
 __host__ __device__ __forceinline__ void tile_from_linear(i64 t, i64 nS, i64 &SI, i64 &I, i64 &J) {
     // Linear order: super-blocks (SI, SJ >= SI) row-major; inside a super-block tiles row-major.
     const i64 per = (i64)MP_SB * MP_SB;
@@ -198,6 +193,11 @@ __device__ __forceinline__ void reduce_best(double best, i64 best_i, i64 best_j,
     }
 }
 
+// The Gram value of a pair from the squared norms of its centred rows and their dot product: g = fl(fl(r_i + r_j) - 2 <x_i, x_j>).
+// The arg-max kernels (1), (3) and the near-tie kernel (3b) all rank pairs by THIS expression: the near-tie guarantee
+// (diameter_host.cpp) needs the three to agree bit for bit.
+__device__ __forceinline__ double gram_value(double ri, double rj, double dot) { return ri + rj - 2.0 * dot; }
+
 // (1) brute force over all tile pairs J >= I of ONE operand
 __global__ __launch_bounds__(256, 2) void max_pair_kernel(const double *__restrict__ Xc,
                                                           const double *__restrict__ rnorm, i64 n, i64 ldn, i64 dpad,
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void max_pair_kernel(const double *__restri
                 for (int r = 0; r < 4; r++) {
                     const i64 i = i0 + wr * 64 + a * 16 + lk + 4 * r;
                     if (j < n && i < j) {
-                        const double v = rnorm[i] + rj - 2.0 * acc[a][b][r];
+                        const double v = gram_value(rnorm[i], rj, acc[a][b][r]);
                         if (v > best) { best = v; best_i = i; best_j = j; }
                     }
                 }
@@ -703,7 +703,7 @@ __global__ __launch_bounds__(256, 2) void pair_list_kernel(const double *__restr
                 for (int r = 0; r < 4; r++) {
                     const i64 i = i0 + wr * 64 + a * 16 + lk + 4 * r;
                     if (i < npos && j < npos) { // rows past npos are zero padding (not vertices)
-                        const double v = rns[i] + rj - 2.0 * acc[a][b][r];
+                        const double v = gram_value(rns[i], rj, acc[a][b][r]);
                         if (v > best) { best = v; best_i = i; best_j = j; }
                     }
                 }
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(256, 2) void pair_collect_kernel(const double *__re
                 for (int r = 0; r < 4; r++) {
                     const i64 i = i0 + wr * 64 + a * 16 + lk + 4 * r;
                     const bool in = tri ? (j < nrows && i < j) : (i < nrows && j < nrows);
-                    if (in && rns[i] + rj - 2.0 * acc[a][b][r] >= thr) { // the expression of the arg-max kernels: the same bits
+                    if (in && gram_value(rns[i], rj, acc[a][b][r]) >= thr) {
                         const unsigned at = atomicAdd(count, 1u);
                         if (at < cap) out[at] = ids ? make_int2(ids[i] - 1, ids[j] - 1) : make_int2((int)i, (int)j);
                     }
@@ -770,8 +770,8 @@ static void best_of_recs(cge_ctx *c, const MaxRec *d_recs, int nwg, double *bv, 
 // one super-row; no tile is visited twice across shards).
 void k_max_pair(cge_ctx *c, const double *Xc, const double *rnorm, i64 n, i64 ldn, i64 dpad, int part, int nparts,
                 double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best) {
-    c->mp_recs.ensure(MP_NWG * 3);
-    MaxRec *recs = reinterpret_cast<MaxRec *>(c->mp_recs.p);
+    c->mp_recs.ensure(MP_NWG);
+    MaxRec *recs = c->mp_recs.p;
     {
         ScopedKernelTimer t(c, "max_pair_dist");
         hipLaunchKernelGGL(max_pair_kernel, dim3(MP_NWG), dim3(256), MP_LDS_BYTES, c->stream, Xc, rnorm, n, ldn, dpad,
@@ -842,15 +842,15 @@ void k_pcent_bf16(cge_ctx *c, const unsigned short *Xb, const double *rns, i64 l
     }
 }
 
-void k_pair_list(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, i64 npos, i64 dpad, const void *tiles,
+void k_pair_list(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, i64 npos, i64 dpad, const int2 *tiles,
                  i64 ntiles, double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best) {
-    c->mp_recs.ensure(MP_NWG * 3);
-    MaxRec *recs = reinterpret_cast<MaxRec *>(c->mp_recs.p);
+    c->mp_recs.ensure(MP_NWG);
+    MaxRec *recs = c->mp_recs.p;
     const int nwg = (int)std::max<i64>(1, std::min<i64>(ntiles, MP_NWG));
     {
         ScopedKernelTimer t(c, "pair_list");
         hipLaunchKernelGGL(pair_list_kernel, dim3(nwg), dim3(256), MP_LDS_BYTES, c->stream, Xs, rns, lds_rows, npos,
-                           dpad, reinterpret_cast<const int2 *>(tiles), ntiles, recs);
+                           dpad, tiles, ntiles, recs);
     }
     best_of_recs(c, recs, nwg, best_val, best_i, best_j, wg_best);
 }
@@ -871,8 +871,8 @@ void k_max_pair_tile_list(i64 ldn, int part, int nparts, const std::vector<doubl
     }
 }
 // returns the number of pairs found (synchronises); above `cap` the list is incomplete
-i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 nrows, i64 dpad, const void *tiles, i64 t0, i64 t1,
-                   int tri, double thr, const i32 *ids, void *out, i64 cap) {
+i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 nrows, i64 dpad, const int2 *tiles, i64 t0, i64 t1,
+                   int tri, double thr, const i32 *ids, int2 *out, i64 cap) {
     if (t1 <= t0) return 0;
     c->mp_count.ensure(2);
     unsigned *cnt = reinterpret_cast<unsigned *>(c->mp_count.p);
@@ -880,8 +880,7 @@ i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 
     {
         ScopedKernelTimer t(c, "pair_collect");
         hipLaunchKernelGGL(pair_collect_kernel, dim3((unsigned)std::min<i64>(t1 - t0, MP_NWG)), dim3(256), MP_LDS_BYTES, c->stream, Xs, rns,
-                           ld, nrows, dpad, reinterpret_cast<const int2 *>(tiles), t0, t1, tri, thr, ids,
-                           reinterpret_cast<int2 *>(out), cnt, (unsigned)cap);
+                           ld, nrows, dpad, tiles, t0, t1, tri, thr, ids, out, cnt, (unsigned)cap);
     }
     unsigned h = 0;
     HIP_CHECK(hipMemcpyAsync(&h, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -895,10 +894,6 @@ i64 k_pair_collect(cge_ctx *c, const double *Xs, const double *rns, i64 ld, i64 
 //                  <= P_ab + P_ba - D2_ab + 2 sqrt(P_aa P_bb)  =: B_ab .
 // Pairs with B_ab (slightly inflated for rounding) >= L, a known lower bound of the diameter^2,
 // are appended to `list` as (B, a, b); *count may exceed cap (then the caller falls back).
-struct BoundRec {
-    double B;
-    i32 a, b;
-};
 // Bounds with reference points: landmark a uses reference lref[a] (its community centroid, or itself).
 //   B_ab = Q[a][ref(b)] + Q[b][ref(a)] - ||ref(a) - ref(b)||^2 + 2 sqrt(Q[a][ref(a)] Q[b][ref(b)])
 // rd2 = nref x nref squared distances of the reference points.
@@ -933,20 +928,6 @@ __global__ __launch_bounds__(256) void ref_dist2_fm_kernel(const double *__restr
             s += df * df;
         }
         rd2[a * nref + b] = s;
-    }
-}
-// squared distances of the nref reference points (row-major nref x d)
-__global__ void ref_dist2_kernel(const double *__restrict__ mu, i64 nref, i64 d, double *__restrict__ rd2) {
-    const i64 total = nref * nref, stride = (i64)gridDim.x * blockDim.x;
-    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const i64 a = e / nref, b = e - a * nref;
-        const double *ma = mu + a * d, *mb = mu + b * d;
-        double s = 0.0;
-        for (i64 k = 0; k < d; k++) {
-            const double df = ma[k] - mb[k];
-            s += df * df;
-        }
-        rd2[e] = s;
     }
 }
 // ---- the same selection in two levels, when the reference points are the landmarks' communities -----------------------
@@ -1005,41 +986,33 @@ __global__ __launch_bounds__(256) void bound_expand_kernel(const double *__restr
         }
     }
 }
-// `ref_off` / `ref_mem` (optional, device): the landmarks grouped by reference point (lref[a] = community of a): two-level form
 // the squared distances of the reference points from their centred feature-major copy, into c->mp_rd2 -- on c->stream, which the
-// caller may have pointed at a side stream: they do not depend on the bound pass and run beside it (k_bound_select(..., Ms_fm =
-// nullptr, rd2_ready = true) then takes them as they are)
+// caller may have pointed at a side stream: they do not depend on the bound pass and run beside it (k_bound_select reads them)
 void k_ref_dist2_fm(cge_ctx *c, const double *Ms_fm, i64 nref, i64 dpad, i64 ldm) {
     c->mp_rd2.ensure((size_t)nref * nref);
     // (differences of centred values: the centre cancels; the 1e-9 margins of the bound cover the rounding)
     hipLaunchKernelGGL(ref_dist2_fm_kernel, dim3((unsigned)nref), dim3(256), 0, c->stream, Ms_fm, nref, dpad, ldm, c->mp_rd2.p);
 }
-i64 k_bound_select(cge_ctx *c, const double *Q, const i32 *lref, const double *mu_ref, i64 N, i64 nref, i64 d, double L,
-                   void *list, i64 cap, const i32 *ref_off, const i32 *ref_mem, const double *Ms_fm, i64 dpad, i64 ldm,
-                   bool rd2_ready) {
+// the candidate landmark pairs (bounds Q, reference-point distances c->mp_rd2 from k_ref_dist2_fm) into `list`; returns their
+// number (synchronises).  `ref_off` / `ref_mem` (optional, device): the landmarks grouped by reference point (lref[a] = community
+// of a): two-level form
+i64 k_bound_select(cge_ctx *c, const double *Q, const i32 *lref, i64 N, i64 nref, double L, BoundRec *list, i64 cap,
+                   const i32 *ref_off, const i32 *ref_mem) {
     c->mp_count.ensure(2);
-    c->mp_rd2.ensure((size_t)nref * nref);
     HIP_CHECK(hipMemsetAsync(c->mp_count.p, 0, 2 * sizeof(i64), c->stream));
     ScopedKernelTimer tm(c, "bound_select");
-    if (rd2_ready) {
-    } else if (Ms_fm)
-        hipLaunchKernelGGL(ref_dist2_fm_kernel, dim3((unsigned)nref), dim3(256), 0, c->stream, Ms_fm, nref, dpad, ldm, c->mp_rd2.p);
-    else
-        hipLaunchKernelGGL(ref_dist2_kernel, dim3(grid_for(nref * nref, 256)), dim3(256), 0, c->stream, mu_ref, nref, d,
-                           c->mp_rd2.p);
     if (ref_off && ref_mem) {
         c->mp_commax.ensure((size_t)nref * nref);
-        c->mp_plist.ensure((size_t)nref * (nref + 1)); // int2 per community pair
+        c->mp_plist.ensure((size_t)nref * (nref + 1) / 2); // one per community pair
         hipLaunchKernelGGL(comm_max_kernel, dim3((unsigned)nref), dim3(256), 0, c->stream, Q, ref_off, ref_mem, nref, c->mp_commax.p);
         hipLaunchKernelGGL(comm_pairs_kernel, dim3(grid_for(nref * nref, 256)), dim3(256), 0, c->stream, c->mp_commax.p, c->mp_rd2.p,
-                           nref, L, reinterpret_cast<int2 *>(c->mp_plist.p), reinterpret_cast<unsigned *>(c->mp_count.p + 1));
+                           nref, L, c->mp_plist.p, reinterpret_cast<unsigned *>(c->mp_count.p + 1));
         hipLaunchKernelGGL(bound_expand_kernel, dim3(2048), dim3(256), 0, c->stream, Q, c->mp_rd2.p, ref_off, ref_mem, nref, L,
-                           reinterpret_cast<const int2 *>(c->mp_plist.p), reinterpret_cast<const unsigned *>(c->mp_count.p + 1),
-                           reinterpret_cast<BoundRec *>(list), cap, reinterpret_cast<unsigned long long *>(c->mp_count.p));
+                           c->mp_plist.p, reinterpret_cast<const unsigned *>(c->mp_count.p + 1), list, cap,
+                           reinterpret_cast<unsigned long long *>(c->mp_count.p));
     } else
         hipLaunchKernelGGL(bound_select_kernel, dim3(grid_for(N * N, 256)), dim3(256), 0, c->stream, Q, lref, c->mp_rd2.p, N,
-                           nref, L, reinterpret_cast<BoundRec *>(list), cap,
-                           reinterpret_cast<unsigned long long *>(c->mp_count.p));
+                           nref, L, list, cap, reinterpret_cast<unsigned long long *>(c->mp_count.p));
     i64 cnt = 0;
     HIP_CHECK(hipMemcpyAsync(&cnt, c->mp_count.p, sizeof(i64), hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1111,8 +1084,8 @@ __global__ __launch_bounds__(256) void argmax_kernel(const double *__restrict__ 
 }
 i64 k_argmax_mapped(cge_ctx *c, const double *v, i64 n, const i32 *map, double *val) {
     if (n <= 0) { if (val) *val = -1.0; return -1; }
-    c->mp_recs.ensure(MP_NWG * 3);
-    MaxRec *recs = reinterpret_cast<MaxRec *>(c->mp_recs.p);
+    c->mp_recs.ensure(MP_NWG);
+    MaxRec *recs = c->mp_recs.p;
     const int nwg = (int)std::max<i64>(1, std::min<i64>((n + 255) / 256, 256));
     hipLaunchKernelGGL(argmax_kernel, dim3(nwg), dim3(256), 768 * sizeof(double), c->stream, v, n, map, recs);
     double bv;
@@ -1125,17 +1098,13 @@ i64 k_argmax_mapped(cge_ctx *c, const double *v, i64 n, const i32 *map, double *
 // may use c->mp_recs in between (the bound passes do not).
 static const int FAR_NWG = 1024 > MP_NWG ? MP_NWG : 1024;
 void k_farthest_enqueue(cge_ctx *c, const double *Xr, i64 n, i64 d, i64 src, const double *srow) {
-    c->mp_recs.ensure(MP_NWG * 3);
-    MaxRec *recs = reinterpret_cast<MaxRec *>(c->mp_recs.p);
+    c->mp_recs.ensure(MP_NWG);
+    MaxRec *recs = c->mp_recs.p;
     hipLaunchKernelGGL(farthest_kernel, dim3(FAR_NWG), dim3(256), 768 * sizeof(double), c->stream, Xr, n, d, src, srow, recs);
 }
 void k_farthest_collect(cge_ctx *c, double *best_val, i64 *best_i) {
     i64 bj;
-    best_of_recs(c, reinterpret_cast<MaxRec *>(c->mp_recs.p), FAR_NWG, best_val, best_i, &bj);
-}
-void k_farthest(cge_ctx *c, const double *Xr, i64 n, i64 d, i64 src, double *best_val, i64 *best_i) {
-    k_farthest_enqueue(c, Xr, n, d, src, nullptr);
-    k_farthest_collect(c, best_val, best_i);
+    best_of_recs(c, c->mp_recs.p, FAR_NWG, best_val, best_i, &bj);
 }
 
 // ------------------------------------------------------------------------------------------------
