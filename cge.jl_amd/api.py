@@ -70,6 +70,15 @@ class EmbeddingBatch(C.Structure):
                 ("row_major", C.c_int)]
 
 
+class EmbeddingView(C.Structure):
+    """cge_embedding_view (include/cge_hip.h): an (n, d) embedding where and as its owner holds it."""
+    _fields_ = [("data", C.c_void_p), ("d", C.c_int64), ("ld", C.c_int64), ("dtype", C.c_int), ("on_device", C.c_int),
+                ("row_major", C.c_int)]
+
+
+DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
+_NP_DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
 
@@ -173,6 +182,58 @@ def _colmajor(a):  # (rows, cols) array -> flat buffer in Julia (column-major) o
     return a, a.ravel(order="K")
 
 
+def _view_layout(n, d, s0, s1):
+    """(row_major, ld) of an (n, d) matrix with element strides (s0, s1) that a view can describe in place -- unit stride along
+    one axis, the other at least the packed pitch -- or None (both axes strided, a negative or a zero stride)."""
+    if (d == 1 or s1 == 1) and (n == 1 or s0 >= d):
+        return 1, (s0 if n > 1 else d)
+    if (n == 1 or s0 == 1) and (d == 1 or s1 >= n):
+        return 0, (s1 if d > 1 else n)
+    return None
+
+
+def embedding_view(x):
+    """(EmbeddingView, owner) for an (n, d) embedding, described where it lies; needs no GPU.  `owner` is the array or tensor the
+    view points into (n = owner.shape[0]); keep it alive while the view is in use.
+
+    numpy arrays of float64 / float32 / float16 and torch tensors (any device) of float64 / float32 / float16 / bfloat16 that
+    are C- or F-contiguous, or a 2-D slice of such a matrix (unit stride along one axis: `X[:, :64]`, `X[5:, :]`), are taken in
+    place: no copy, the leading dimension comes from the strides.  Any other striding costs one packed copy in the same dtype;
+    other numpy dtypes (integers, ...) become float64, as `set_embedding` makes them.  A plain int is not accepted (raw device
+    pointers: `Context.set_embedding_device`)."""
+    if isinstance(x, (int, np.integer)):
+        raise TypeError("embedding_view: a raw pointer is not a view (Context.set_embedding_device takes device pointers)")
+    torch = sys.modules.get("torch")
+    v = EmbeddingView()
+    if torch is not None and isinstance(x, torch.Tensor):
+        codes = {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32, torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
+        t = x.detach()
+        if t.dtype not in codes:
+            raise ValueError(f"embedding_view: tensor dtype {t.dtype} (float64, float32, float16 or bfloat16)")
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("embedding_view: an embedding is a non-empty (n, d) matrix")
+        lay = _view_layout(t.shape[0], t.shape[1], *t.stride())
+        if lay is None:
+            t = t.contiguous()
+            lay = 1, t.shape[1]
+        v.data, v.d, v.dtype, v.on_device = t.data_ptr(), t.shape[1], codes[t.dtype], int(t.is_cuda)
+        v.row_major, v.ld = lay
+        return v, t
+    a = np.asarray(x)
+    if a.dtype not in _NP_DTYPES:
+        a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("embedding_view: an embedding is a non-empty (n, d) matrix")
+    sz = a.dtype.itemsize
+    lay = None if a.strides[0] % sz or a.strides[1] % sz else _view_layout(a.shape[0], a.shape[1], a.strides[0] // sz, a.strides[1] // sz)
+    if lay is None:
+        a = np.ascontiguousarray(a)
+        lay = 1, a.shape[1]
+    v.data, v.d, v.dtype, v.on_device = a.ctypes.data, a.shape[1], _NP_DTYPES[a.dtype], 0
+    v.row_major, v.ld = lay
+    return v, a
+
+
 def _edge_cols(edges):
     e = np.asarray(edges, dtype=np.int64)
     if e.size == 0:
@@ -238,6 +299,7 @@ class Context:
             raise CGEError(rc, "cge_create failed (no MI355X visible?)")
         self.h = h
         self.device = device
+        self.stream = int(stream) if stream else None
         self._keep = []  # objects the C side holds pointers to (collective hook)
         self.n = self.m = self.d = 0
         global _atexit_registered
@@ -283,6 +345,36 @@ class Context:
         self._check(self.L.cge_set_embedding_device(self.h, C.c_void_p(dev_ptr), C.c_int64(n), C.c_int64(d),
                                                     C.c_int(1 if row_major else 0)))
         self.d = d
+
+    def _view(self, x):
+        """`embedding_view(x)`, ready for a call on this context: a CUDA tensor must live on the context's GPU, and what its
+        current torch stream has enqueued is finished first (unless that stream is the context's own)."""
+        v, owner = embedding_view(x)
+        if v.on_device:
+            import torch
+
+            if owner.device.index != self.device:
+                raise ValueError(f"embedding on {owner.device}, the context is on GPU {self.device}")
+            st = torch.cuda.current_stream(owner.device)
+            if self.stream is None or st.cuda_stream != self.stream:
+                st.synchronize()
+        return v, owner
+
+    def set_embedding_view(self, x):
+        """The (n, d) embedding `x` -- a numpy array or a torch tensor, on the host or on this GPU, float64 / float32 / float16
+        (/ bfloat16), C- or F-ordered or a slice -- made resident as it is (cge_set_embedding_view): it travels in its own type and
+        is widened to float64 on the device, which is exact.  Same results as `set_embedding(x.astype(float64))`."""
+        v, owner = self._view(x)
+        self._check(self.L.cge_set_embedding_view(self.h, C.byref(v), C.c_int64(owner.shape[0])))
+        self.d = int(v.d)
+
+    def resident_embedding(self):
+        """Testing hook (include/cge_hip_testing.h): (rows held by this rank as an (r, d) float64 array, their 0-based ids)."""
+        r, d = C.c_int64(), C.c_int64()
+        self.L.cge_resident_embedding_test(self.h, None, C.c_int64(0), C.byref(r), C.byref(d), None)  # (the sizes)
+        out, ids = np.empty((r.value, d.value)), np.empty(r.value, dtype=np.int32)
+        self._check(self.L.cge_resident_embedding_test(self.h, _p(out), C.c_int64(out.size), C.byref(r), C.byref(d), _p(ids)))
+        return out, ids
 
     def set_vertex_data(self, comm, vweights):
         cm = None if comm is None else _i64(np.asarray(comm).ravel())
@@ -443,6 +535,37 @@ class Context:
         self._check(self.L.cge_score_batch(self.h, C.byref(a), C.byref(b), _p(out), olen, trs))
         self.d = int(d)
         self.last_traces = [trs[k].as_dict() for k in range(K)]
+        return [out[k, : olen[k]].copy() for k in range(K)]
+
+    def score_views(self, embeddings, clusters, land, forced=4, method="rss", directed=False, split=False, seed=-1,
+                    auc_samples=10000):
+        """`score_batch` with every member passed as `set_embedding_view` takes it (cge_score_views): the members may differ in
+        width, dtype, layout and location -- numpy arrays and torch tensors, host and GPU, mixed.  Returns the list of result
+        vectors, each equal to what `set_embedding_view` + `score` gives on that member; traces in `last_traces`.  Afterwards
+        the last embedding is the resident one."""
+        embeddings = list(embeddings)
+        K = len(embeddings)
+        if K < 1:
+            raise ValueError("score_views: no embeddings")
+        views, keep = (EmbeddingView * K)(), []
+        for k, e in enumerate(embeddings):
+            v, owner = self._view(e)
+            if owner.shape[0] != self.n:
+                raise ValueError(f"score_views: embedding {k} has {owner.shape[0]} rows, the resident graph {self.n} vertices")
+            views[k] = v
+            keep.append(owner)
+        flat, off = _flatten_clusters(clusters if clusters else [])
+        a = ScoreArgs()
+        a.clusters_flat, a.clusters_off, a.n_clusters = _p(flat).value, _p(off).value, len(off) - 1
+        a.land, a.forced, a.method = int(land), int(forced), _method_code(method)
+        a.directed, a.split, a.seed, a.auc_samples = int(bool(directed)), int(bool(split)), int(seed), int(auc_samples)
+        out = np.zeros((K, 7))
+        olen = (C.c_int * K)()
+        trs = (Trace * K)()
+        self._check(self.L.cge_score_views(self.h, C.byref(a), views, C.c_int64(K), _p(out), olen, trs))
+        self.d = int(views[K - 1].d)
+        self.last_traces = [trs[k].as_dict() for k in range(K)]
+        del keep
         return [out[k, : olen[k]].copy() for k in range(K)]
 
     # ---- kernel-level ----------------------------------------------------------------------------------

@@ -74,13 +74,16 @@ def read_embedding(fn_embed, no_vertices):
     return np.asfortranarray(embedding)
 
 
-def parseargs(argv=None, exit_on_error=True):
+def parseargs(argv=None, exit_on_error=True, embedding_reader=None):
     """Returns (edges, eweights, vweight, comm, clusters, embedding, verbose, landmarks, forced,
     method, directed, split, seed, samples) exactly as src/auxilary.jl:220.
 
     edges: int64 (m,2) Fortran-ordered (two contiguous columns, like Julia's Matrix{Int});
     comm: int64 (n,1); embedding: float64 (n,d) Fortran-ordered; clusters: list of 1-based int64
-    arrays (empty dict when no landmarks are requested, as in the reference :173,:199-208)."""
+    arrays (empty dict when no landmarks are requested, as in the reference :173,:199-208).
+
+    `embedding_reader(file, no_vertices)` (optional) reads the `-e` file instead of `read_embedding`; what it returns is
+    handed back as it is (cge_compare.py: `.npy` files in their own dtype)."""
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
         verbose = "-v" in argv
@@ -141,7 +144,7 @@ def parseargs(argv=None, exit_on_error=True):
         fn_embed = _flag_value(argv, "-e")
         if not os.path.isfile(fn_embed):
             raise AssertionError(f"{fn_embed} is not a file")
-        embedding = read_embedding(fn_embed, no_vertices)
+        embedding = (embedding_reader or read_embedding)(fn_embed, no_vertices)
 
         landmarks = -1
         if "-l" in argv:

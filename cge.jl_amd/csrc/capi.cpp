@@ -496,6 +496,178 @@ int cge_set_embedding_device(cge_ctx *c, const double *X_dev, int64_t n, int64_t
     CGE_CATCH(c)
 }
 
+// ---- embedding views: fp64 / fp32 / fp16 / bf16, host or device, either layout, with a leading dimension ------------------------
+// ("Embedding views").  A host view travels in its own type -- raw bytes through the pinned staging -- and is widened
+// on the device (kernels_ingest.hip) behind each chunk, as the fp64 path transposes behind each chunk.
+static int view_check(const cge_embedding_view *v, i64 n, std::string &msg) {
+    char b[256];
+    b[0] = 0;
+    if (!v) snprintf(b, sizeof b, "embedding view: NULL view");
+    else if (!v->data) snprintf(b, sizeof b, "embedding view: NULL data");
+    else if (n <= 0 || v->d <= 0) snprintf(b, sizeof b, "embedding view: n = %lld, d = %lld (both must be positive)", (long long)n, (long long)v->d);
+    else if (v->dtype < CGE_DTYPE_F64 || v->dtype > CGE_DTYPE_BF16) snprintf(b, sizeof b, "embedding view: unknown dtype %d", v->dtype);
+    else if (v->ld < 0 || (v->ld != 0 && v->ld < (v->row_major ? v->d : n)))
+        snprintf(b, sizeof b, "embedding view: leading dimension %lld below the packed %lld", (long long)v->ld, (long long)(v->row_major ? v->d : n));
+    else if ((uintptr_t)v->data % cge_dtype_size(v->dtype) != 0)
+        snprintf(b, sizeof b, "embedding view: data pointer not aligned to its %d-byte elements", (int)cge_dtype_size(v->dtype));
+    else return CGE_OK;
+    msg = b;
+    return CGE_E_ARG;
+}
+int cge_embedding_view_check(const cge_embedding_view *v, int64_t n, char *err, int64_t err_len) {
+    std::string msg;
+    const int rc = view_check(v, n, msg);
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", msg.c_str());
+    return rc;
+}
+// bytes [a0, a1) of a packed image made of runs of `run` bytes, run j starting at base + (idx ? idx[j] : j) * pitch
+static void copy_runs(unsigned char *o, size_t a0, size_t a1, const unsigned char *base, size_t run, size_t pitch, const i32 *idx) {
+    if (!idx && run == pitch) { memcpy(o, base + a0, a1 - a0); return; }
+    for (size_t e = a0; e < a1;) {
+        const size_t j = e / run, at = e % run, len = std::min(a1 - e, run - at);
+        memcpy(o + (e - a0), base + (idx ? (size_t)idx[j] : j) * pitch + at, len);
+        e += len;
+    }
+}
+static void set_view_impl(cge_ctx *c, const cge_embedding_view *v, i64 n) {
+    std::string msg;
+    if (view_check(v, n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s", msg.c_str());
+    HIP_CHECK(hipSetDevice(c->device));
+    if (c->n && c->n != n) CGE_THROW(CGE_E_ASSERT, "No. rows in embedding and no. vertices in a graph differ.");
+    const i64 d = v->d;
+    const int dt = v->dtype;
+    const bool rm = v->row_major != 0;
+    const i64 ld = v->ld ? v->ld : (rm ? d : n);
+    const size_t es = cge_dtype_size(dt);
+    if (v->on_device) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, v->data) != hipSuccess || at.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError();
+            CGE_THROW(CGE_E_ARG, "set_embedding_view: the pointer of a device view is not device memory");
+        }
+        if (at.device != c->device)
+            CGE_THROW(CGE_E_ARG, "set_embedding_view: the device view lies on GPU %d, the context is on GPU %d", at.device, c->device);
+        if (rows_shard_wanted(c)) { // option shard_rows: this rank's rows are gathered out of the caller's matrix
+            rows_assign_ownership(c);
+            c->Xr.alloc_exact((size_t)c->n_loc * d);
+            k_ingest_gather(c, v->data, dt, ld, d, rm, c->loc2glob.p, c->n_loc, c->Xr.p);
+        } else {
+            rows_unshard(c);
+            c->Xr.alloc_exact((size_t)n * d);
+            if (rm && dt == CGE_DTYPE_F64 && ld == d)
+                HIP_CHECK(hipMemcpyAsync(c->Xr.p, v->data, sizeof(double) * (size_t)n * d, hipMemcpyDeviceToDevice, c->stream));
+            else if (rm)
+                k_ingest_rows(c, v->data, dt, ld, n, d, c->Xr.p);
+            else
+                k_ingest_cols(c, v->data, dt, ld, c->Xr.p, n, d, 0, 0, d);
+        }
+        HIP_CHECK(hipStreamSynchronize(c->stream)); // the caller may free or reuse its buffer on return
+        embedding_resident(c, n, d);
+        return;
+    }
+    const unsigned char *X = (const unsigned char *)v->data;
+    const size_t pitch = (size_t)ld * es;
+    DevBuf<unsigned char> raw; // the typed image on the device: this rank's packed rows, or a ring of two chunks
+    // a packed typed image of `nl` rows (row-major: rows of d; column-major: columns of nl) in `raw` -> rows of Xr at `dst`
+    auto widen_image = [&](i64 nl, double *dst) {
+        if (rm) k_ingest_rows(c, raw.p, dt, d, nl, d, dst);
+        else k_ingest_cols(c, raw.p, dt, nl, dst, nl, d, 0, 0, d);
+    };
+    if (rows_shard_wanted(c)) {
+        // option shard_rows: this rank uploads and KEEPS the rows of its own communities only, in the caller's type: whole rows of
+        // a row-major view, a gather of elements per column of a column-major one (as cge_set_embedding, for any element size)
+        rows_assign_ownership(c);
+        const i64 nl = c->n_loc;
+        const i32 *l2g = c->h_loc2glob.data();
+        raw.alloc_exact((size_t)nl * d * es);
+        if (rm)
+            staged_upload<unsigned char>(c, raw.p, (size_t)nl * d * es, [&](unsigned char *o, size_t a0, size_t a1) {
+                copy_runs(o, a0, a1, X, (size_t)d * es, pitch, l2g);
+            });
+        else { // element e of the (nl x d, column-major) slice: column e / nl, local row e % nl -- a typed fill per element size
+#define CGE_GATHER_COLS(U)                                                                                       \
+    staged_upload<U>(c, (U *)raw.p, (size_t)nl * d, [&](U *o, size_t a0, size_t a1) {                           \
+        const U *Xu = (const U *)X;                                                                              \
+        size_t k = a0 / (size_t)nl, i = a0 % (size_t)nl;                                                         \
+        for (size_t e = a0; e < a1; e++) {                                                                       \
+            o[e - a0] = Xu[k * (size_t)ld + (size_t)l2g[i]];                                                     \
+            if (++i == (size_t)nl) { i = 0; k++; }                                                               \
+        }                                                                                                        \
+    })
+            if (es == 8) CGE_GATHER_COLS(uint64_t);
+            else if (es == 4) CGE_GATHER_COLS(uint32_t);
+            else CGE_GATHER_COLS(uint16_t);
+#undef CGE_GATHER_COLS
+        }
+        c->Xr.alloc_exact((size_t)nl * d);
+        widen_image(nl, c->Xr.p);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        raw.release();
+        embedding_resident(c, n, d);
+        return;
+    }
+    rows_unshard(c);
+    if (ingest_sharded(c)) {
+        // option shard_ingest: every rank uploads its n / world rows in the caller's type, widens them into its place of Xr, and
+        // the fp64 pieces are all-gathered device to device (cge_set_embedding has the layout of the padded Xr)
+        const i64 W = c->coll.world, r = c->coll.rank, per = (n + W - 1) / W;
+        const i64 r0 = std::min<i64>(n, per * r), r1 = std::min<i64>(n, r0 + per), nl = r1 - r0;
+        c->Xr.alloc_exact((size_t)per * W * d);
+        if (nl < per) HIP_CHECK(hipMemsetAsync(c->Xr.p + (size_t)(per * r + nl) * d, 0, sizeof(double) * (size_t)(per - nl) * d, c->stream));
+        if (nl > 0) {
+            raw.alloc_exact((size_t)nl * d * es);
+            const unsigned char *base = X + (size_t)r0 * (rm ? pitch : es);
+            const size_t run = (size_t)(rm ? d : nl) * es;
+            staged_upload<unsigned char>(c, raw.p, (size_t)nl * d * es,
+                                         [&](unsigned char *o, size_t a0, size_t a1) { copy_runs(o, a0, a1, base, run, pitch, nullptr); });
+            widen_image(nl, c->Xr.p + (size_t)per * r * d);
+        }
+        cge_allgather_dev(c, c->Xr.p, per * d);
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        raw.release();
+        embedding_resident(c, n, d);
+        return;
+    }
+    c->Xr.alloc_exact((size_t)n * d);
+    const size_t cap = CGE_STAGE_BYTES, total = (size_t)n * d * es;
+    if (rm) {
+        // row-major: the packed image has Xr's own order, so a chunk is any run of elements (a multiple of 16 bytes: the ring slots
+        // and the chunk's place in Xr stay aligned for the vector loads and stores) and is widened in place behind its copy
+        const size_t chunk = std::min(cap, std::max((size_t)2 << 20, ((total + 7) / 8 + 15) / 16 * 16));
+        raw.alloc_exact(2 * chunk);
+        staged_upload_chunks<unsigned char>(c, raw.p, total, chunk, 2,
+                                            [&](unsigned char *o, size_t a0, size_t a1) { copy_runs(o, a0, a1, X, (size_t)d * es, pitch, nullptr); },
+                                            [&](unsigned char *piece, size_t off, size_t len) {
+                                                k_ingest_rows(c, piece, dt, (i64)(len / es), 1, (i64)(len / es), c->Xr.p + off / es);
+                                            });
+    } else if ((size_t)n * es <= cap) { // column-major: chunks of whole columns, widened and transposed behind their copy
+        const size_t colb = (size_t)n * es, kc = std::min<size_t>((size_t)d, cap / colb), chunk = kc * colb;
+        raw.alloc_exact(2 * chunk);
+        staged_upload_chunks<unsigned char>(c, raw.p, total, chunk, 2,
+                                            [&](unsigned char *o, size_t a0, size_t a1) { copy_runs(o, a0, a1, X, colb, pitch, nullptr); },
+                                            [&](unsigned char *piece, size_t off, size_t len) {
+                                                k_ingest_cols(c, piece, dt, n, c->Xr.p, n, (i64)(len / colb), 0, (i64)(off / colb), d);
+                                            });
+    } else { // one column in row pieces
+        raw.alloc_exact(2 * cap);
+        for (i64 k = 0; k < d; k++)
+            staged_upload_chunks<unsigned char>(c, raw.p, (size_t)n * es, cap, 2,
+                                                [&](unsigned char *o, size_t a0, size_t a1) { memcpy(o, X + (size_t)k * pitch + a0, a1 - a0); },
+                                                [&](unsigned char *piece, size_t off, size_t len) {
+                                                    k_ingest_cols(c, piece, dt, (i64)(len / es), c->Xr.p, (i64)(len / es), 1, (i64)(off / es), k, d);
+                                                });
+    }
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    raw.release();
+    embedding_resident(c, n, d);
+}
+int cge_set_embedding_view(cge_ctx *c, const cge_embedding_view *v, int64_t n) {
+    if (!c || !v) return CGE_E_ARG;
+    CGE_TRY(c)
+    set_view_impl(c, v, n);
+    CGE_CATCH(c)
+}
+
 int cge_set_vertex_data(cge_ctx *c, const int64_t *comm, const double *vw, int64_t n) {
     if (!c || n <= 0) return CGE_E_ARG;
     CGE_TRY(c)
@@ -1316,28 +1488,26 @@ int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, 
 }
 
 // ---- cge_score_batch: K embeddings of the resident graph ("Scoring several embeddings") ----------------------------
-static void upload_member(cge_ctx *c, const cge_embedding_batch *b, i64 k) {
-    const int rc = b->on_device ? cge_set_embedding_device(c, b->embeddings[k], c->n, b->d, b->row_major)
-                                : cge_set_embedding(c, b->embeddings[k], c->n, b->d);
-    if (rc != CGE_OK) CGE_THROW(rc, "score_batch: embedding %lld: %s", (long long)k, c->err.c_str());
+// What differs between cge_score_batch and cge_score_views is how member k becomes the resident embedding (`upload`) and what is
+// checked of the members before any work (`check`, after the checks of the context); `who` names the entry point in messages.
+struct BatchSource {
+    const char *who;
+    i64 K;
+    std::function<void()> check;
+    std::function<int(i64)> upload; // a status of the boundary; the message is in c->err
+};
+static void upload_member(cge_ctx *c, const BatchSource &b, i64 k) {
+    const int rc = b.upload(k);
+    if (rc != CGE_OK) CGE_THROW(rc, "%s: embedding %lld: %s", b.who, (long long)k, std::string(c->err).c_str());
 }
-static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embedding_batch *b, double *out, int *out_len,
+static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const BatchSource &b, double *out, int *out_len,
                              cge_trace *traces) {
-    const i64 K = b->K;
+    const i64 K = b.K;
     if (!c->src.p || !c->vw.p || !c->comm.p || c->n <= 0 || c->m <= 0)
-        CGE_THROW(CGE_E_ARG, "score_batch: graph and vertex data must be resident (cge_set_graph / cge_set_vertex_data)");
+        CGE_THROW(CGE_E_ARG, "%s: graph and vertex data must be resident (cge_set_graph / cge_set_vertex_data)", b.who);
     if (c->has_coll || c->rccl_comm || c->edges_sharded || c->rows_sharded || c->opt_shard_ingest || c->opt_shard_rows)
-        CGE_THROW(CGE_E_ARG, "score_batch: not under collectives or sharding (one embedding per rank is the multi-GPU form)");
-    for (i64 k = 0; k < K; k++)
-        if (!b->embeddings[k]) CGE_THROW(CGE_E_ARG, "score_batch: embedding %lld is NULL", (long long)k);
-    if (b->on_device)
-        for (i64 k = 0; k < K; k++) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, b->embeddings[k]) != hipSuccess || at.type != hipMemoryTypeDevice) {
-                (void)hipGetLastError();
-                CGE_THROW(CGE_E_ARG, "score_batch: embedding %lld is not device memory", (long long)k);
-            }
-        }
+        CGE_THROW(CGE_E_ARG, "%s: not under collectives or sharding (one embedding per rank is the multi-GPU form)", b.who);
+    b.check();
     int dev = 0, cus = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -1392,11 +1562,9 @@ static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embe
     }
     c->phases.ms["batch_sweep"] = batch_ms; // the launch groups' sweeps, all members (the other phases: the last member's)
 }
-int cge_score_batch(cge_ctx *c, const cge_score_args *a, const cge_embedding_batch *b, double *out, int *out_len,
-                    cge_trace *traces) {
-    if (!c || !a || !b || !out || !out_len || !b->embeddings || b->K < 1 || b->d <= 0 || (b->row_major && !b->on_device))
-        return CGE_E_ARG;
-    for (i64 k = 0; k < b->K; k++) out_len[k] = 0;
+// the boundary of both batch entry points: every exit leaves the context usable, an error leaves every out_len at 0
+static int score_batch_run(cge_ctx *c, const cge_score_args *a, const BatchSource &b, double *out, int *out_len, cge_trace *traces) {
+    for (i64 k = 0; k < b.K; k++) out_len[k] = 0;
     int rc;
     try {
         HIP_CHECK(hipSetDevice(c->device));
@@ -1416,9 +1584,51 @@ int cge_score_batch(cge_ctx *c, const cge_score_args *a, const cge_embedding_bat
     c->flow_armed_words = 0;
     if (rc != CGE_OK) {
         (void)hipStreamSynchronize(c->stream);
-        for (i64 k = 0; k < b->K; k++) out_len[k] = 0;
+        for (i64 k = 0; k < b.K; k++) out_len[k] = 0;
     }
     return rc;
+}
+static void check_device_pointer(const char *who, const void *p, i64 k) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        CGE_THROW(CGE_E_ARG, "%s: embedding %lld is not device memory", who, (long long)k);
+    }
+}
+int cge_score_batch(cge_ctx *c, const cge_score_args *a, const cge_embedding_batch *b, double *out, int *out_len,
+                    cge_trace *traces) {
+    if (!c || !a || !b || !out || !out_len || !b->embeddings || b->K < 1 || b->d <= 0 || (b->row_major && !b->on_device))
+        return CGE_E_ARG;
+    BatchSource s;
+    s.who = "score_batch";
+    s.K = b->K;
+    s.check = [&]() {
+        for (i64 k = 0; k < b->K; k++)
+            if (!b->embeddings[k]) CGE_THROW(CGE_E_ARG, "score_batch: embedding %lld is NULL", (long long)k);
+        if (b->on_device)
+            for (i64 k = 0; k < b->K; k++) check_device_pointer(s.who, b->embeddings[k], k);
+    };
+    s.upload = [&](i64 k) {
+        return b->on_device ? cge_set_embedding_device(c, b->embeddings[k], c->n, b->d, b->row_major)
+                            : cge_set_embedding(c, b->embeddings[k], c->n, b->d);
+    };
+    return score_batch_run(c, a, s, out, out_len, traces);
+}
+int cge_score_views(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, int64_t K, double *out, int *out_len,
+                    cge_trace *traces) {
+    if (!c || !a || !views || !out || !out_len || K < 1) return CGE_E_ARG;
+    BatchSource s;
+    s.who = "score_views";
+    s.K = K;
+    s.check = [&]() {
+        for (i64 k = 0; k < K; k++) {
+            std::string msg;
+            if (view_check(views + k, c->n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "score_views: embedding %lld: %s", (long long)k, msg.c_str());
+            if (views[k].on_device) check_device_pointer(s.who, views[k].data, k);
+        }
+    };
+    s.upload = [&](i64 k) { return cge_set_embedding_view(c, views + k, c->n); };
+    return score_batch_run(c, a, s, out, out_len, traces);
 }
 
 // ---- helpers ----------------------------------------------------------------------------------------
@@ -1777,6 +1987,25 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
     HIP_CHECK(hipMemcpyAsync(out_ref, da.p, sizeof(double) * n_rows, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(out_new, db.p, sizeof(double) * n_rows, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
+    CGE_CATCH(c)
+}
+
+// testing hook (include/cge_hip_testing.h): the resident row-major matrix itself, so that the tests of the embedding views compare
+// every element and not a score
+int cge_resident_embedding_test(void *ctx, double *out, int64_t capacity_doubles, int64_t *rows, int64_t *d, int32_t *ids_out) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !rows || !d) return CGE_E_ARG;
+    CGE_TRY(c)
+    HIP_CHECK(hipSetDevice(c->device));
+    if (!c->Xr.p || c->d <= 0) CGE_THROW(CGE_E_ARG, "embedding not resident");
+    const i64 nl = lm_rows(c);
+    *rows = nl;
+    *d = c->d;
+    if (!out || capacity_doubles < nl * c->d) CGE_THROW(CGE_E_ARG, "resident embedding: %lld x %lld doubles do not fit the buffer", (long long)nl, (long long)c->d);
+    HIP_CHECK(hipMemcpyAsync(out, c->Xr.p, sizeof(double) * (size_t)nl * c->d, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (ids_out)
+        for (i64 i = 0; i < nl; i++) ids_out[i] = c->rows_sharded ? c->h_loc2glob[i] : (i32)i;
     CGE_CATCH(c)
 }
 

@@ -586,6 +586,11 @@ void cge_ensure_host_embedding(cge_ctx *c); // capi.cpp: fetch the host mirror o
 // layout
 void k_transpose_to_rowmajor(cge_ctx *c, const double *Xcol, double *Xrow, i64 n, i64 d);
 void k_transpose_piece(cge_ctx *c, const double *piece, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d); // rows [i0, i0 + rows) x columns [k0, k0 + cols), column-major piece -> its place in the row-major matrix
+// kernels_ingest.hip: an embedding view (dtype = CGE_DTYPE_*, ld in elements) widened into row-major fp64
+size_t cge_dtype_size(int dtype);
+void k_ingest_rows(cge_ctx *c, const void *src, int dtype, i64 ld, i64 rows, i64 d, double *dst); // dst[i * d + k] = src[i * ld + k]
+void k_ingest_cols(cge_ctx *c, const void *src, int dtype, i64 ld, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d); // k_transpose_piece of a typed piece src[k * ld + i]
+void k_ingest_gather(cge_ctx *c, const void *X, int dtype, i64 ld, i64 d, int row_major, const i32 *idx, i64 cnt, double *out); // k_gather_rows_f64 of a typed matrix
 void k_row_hash(cge_ctx *c, const double *Xrow, uint64_t *hash, i64 n, i64 d);
 i64 k_count_distinct(cge_ctx *c, const uint64_t *hash, i64 n); // distinct values among the hashes (device set; synchronises)
 // landmark split primitives (batched over tasks; rows = concatenated 0-based vertex ids)

@@ -76,6 +76,29 @@ function set_inputs!(c::Ctx, edges::Matrix{Int}, weights::Vector{Float64}, vweig
     end
 end
 
+# cge_embedding_view (include/cge_hip.h): an embedding as its owner holds it -- element type, layout, leading dimension
+struct EmbeddingView
+    data::Ptr{Cvoid}
+    d::Int64
+    ld::Int64        # leading dimension in elements; 0 = packed
+    dtype::Cint      # 0 Float64, 1 Float32, 2 Float16, 3 bfloat16
+    on_device::Cint
+    row_major::Cint  # a Julia Matrix is column-major: 0
+end
+view_dtype(::Type{Float64}) = Cint(0)
+view_dtype(::Type{Float32}) = Cint(1)
+view_dtype(::Type{Float16}) = Cint(2)
+
+# The embedding in its own element type (Float32 / Float16 go over the link as they are and are widened on the device; the
+# results are those of the Float64 matrix `Float64.(embedding)`).  The graph must be resident (set_inputs! or cge_set_graph).
+function set_embedding!(c::Ctx, embedding::Matrix{T}) where {T<:Union{Float64,Float32,Float16}}
+    n, d = size(embedding)
+    GC.@preserve embedding begin
+        v = EmbeddingView(pointer(embedding), d, n, view_dtype(T), 0, 0)
+        check(c, ccall((:cge_set_embedding_view, LIB), Cint, (Ptr{Cvoid}, Ref{EmbeddingView}, Int64), c.h, Ref(v), n))
+    end
+end
+
 """
     landmarks(edges, weights, vweights, clusters, comm, embedding, verbose, land, forced, method, directed)
 

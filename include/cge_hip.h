@@ -116,6 +116,31 @@ int cge_set_embedding(cge_ctx *ctx, const double *X_colmajor, int64_t n, int64_t
  * would otherwise cross PCIe): n x d doubles, row-major (row_major = 1: a vertex's d features contiguous) or column-major
  * like Julia's Matrix (0).  Copied (the caller keeps ownership and may free the buffer on return).                      */
 int cge_set_embedding_device(cge_ctx *ctx, const double *X_dev, int64_t n, int64_t d, int row_major);
+/* The embedding AS THE CALLER HOLDS IT: fp64 / fp32 / fp16 / bf16 elements, in host memory or in this GPU's, row-major (a torch
+ * tensor, a C-order numpy array) or column-major (Julia's Matrix), packed or with a leading dimension (a column slice X[:, :64] of a
+ * wider matrix).  A host view crosses the link in its own type (half or a quarter of the fp64 bytes) and is widened on the device
+ * behind each chunk of the upload; a device view is widened in one pass.  Widening to fp64 is exact, so the resident matrix holds,
+ * bit for bit, what the caller's own conversion to double would have produced (signed zeros, subnormals and infinities included; a
+ * NaN stays a NaN) and every result is that of cge_set_embedding / cge_set_embedding_device on the widened matrix.  Options
+ * shard_rows / shard_ingest apply as they do to the fp64 forms (a device view is not ingest-sharded, as cge_set_embedding_device). */
+#define CGE_DTYPE_F64 0
+#define CGE_DTYPE_F32 1
+#define CGE_DTYPE_F16 2   /* IEEE binary16 */
+#define CGE_DTYPE_BF16 3
+typedef struct {
+    const void *data;   /* element (i, k): row-major data[i * ld + k], column-major data[k * ld + i] */
+    int64_t d;          /* features */
+    int64_t ld;         /* leading dimension in ELEMENTS; 0 = packed (d row-major, n column-major) */
+    int dtype;          /* CGE_DTYPE_* */
+    int on_device;      /* 0 host (borrowed for the call), 1 this GPU's memory (copied; caller may free on return) */
+    int row_major;      /* 1 = a vertex's features contiguous; allowed for host pointers too */
+} cge_embedding_view;
+/* Is `v` a well-formed view of n rows?  Needs no context and no GPU.  CGE_E_ARG (and a message in `err`, optional) for a NULL view
+ * or NULL data, d <= 0, n <= 0, an unknown dtype, a non-zero ld below the packed value, a data pointer that is not aligned to its
+ * element size.  cge_set_embedding_view and cge_score_views call it first. */
+int cge_embedding_view_check(const cge_embedding_view *v, int64_t n, char *err, int64_t err_len);
+/* cge_set_embedding / cge_set_embedding_device for a view.  A device view whose pointer is not device memory: CGE_E_ARG. */
+int cge_set_embedding_view(cge_ctx *ctx, const cge_embedding_view *v, int64_t n);
 /* comm::Matrix{Int} n x 1 (src/auxilary.jl:122-139) and vweight (src/auxilary.jl:104-110) */
 int cge_set_vertex_data(cge_ctx *ctx, const int64_t *comm, const double *vweights, int64_t n);
 
@@ -222,6 +247,13 @@ typedef struct {
 } cge_embedding_batch;
 int cge_score_batch(cge_ctx *ctx, const cge_score_args *args, const cge_embedding_batch *batch, double *out /* K x 7 */,
                     int *out_len /* K */, cge_trace *traces /* K or NULL */);
+/* cge_score_batch with one view per member (of the resident graph's n rows): the members may differ in d, dtype, layout and
+ * location -- a 32-dimensional fp32 tensor on the device can be ranked against a 64-dimensional fp64 host matrix.  The same
+ * contract: member k's vector, trace and iteration counts are what cge_score gives after cge_set_embedding_view(views + k) on this
+ * context; the same launch sharing, stats and error behaviour, the same refusal under collectives or sharding; afterwards the
+ * last member is resident. */
+int cge_score_views(cge_ctx *ctx, const cge_score_args *args, const cge_embedding_view *views, int64_t K,
+                    double *out /* K x 7 */, int *out_len /* K */, cge_trace *traces /* K or NULL */);
 
 /* ---- louvain_clust(): src/clustering.jl:14-68 (called by parseargs when `-c` is omitted, src/auxilary.jl:115-121) ----
  * The communities the reference writes to <file>.ecg: LEVEL 1 of Louvain (`hierarchy -l 1`: the partition after the first

@@ -50,6 +50,10 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *   "fit_persistent_test_timeout" 1: the persistent fit abandons every launch at once (the fallback path runs);
  *   "test_bvec_plain"             1: vect_B by the kernels of score graphs beyond the LDS budget / 512 communities.              */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
+/* needs the GPU: the resident row-major fp64 matrix as this rank holds it (all n rows; under shard_rows its own rows, in
+ * local order, with their global 0-based ids in ids_out, which may be NULL otherwise).  *rows and *d are set first; a capacity
+ * below rows * d doubles (or a NULL out) returns CGE_E_ARG with them set, so a caller can ask for the sizes */
+int cge_resident_embedding_test(void *ctx, double *out, int64_t capacity_doubles, int64_t *rows, int64_t *d, int32_t *ids_out);
 #ifdef __cplusplus
 }
 #endif
