@@ -11,23 +11,6 @@
 
 void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out);
 
-#define CGE_TRY(ctx) try {
-#define CGE_CATCH(ctx)                                             \
-    }                                                              \
-    catch (const CgeError &e) {                                    \
-        if (ctx) (ctx)->err = e.msg;                               \
-        return e.code;                                             \
-    }                                                              \
-    catch (const std::bad_alloc &) {                               \
-        if (ctx) (ctx)->err = "host allocation failed";            \
-        return CGE_E_OOM;                                          \
-    }                                                              \
-    catch (const std::exception &e) {                              \
-        if (ctx) (ctx)->err = e.what();                            \
-        return CGE_E_ARG;                                          \
-    }                                                              \
-    return CGE_OK;
-
 static void flush_timers(cge_ctx *c) {
     for (auto &kv : c->timers) {
         for (auto &pr : kv.second.pending) {
@@ -39,52 +22,6 @@ static void flush_timers(cge_ctx *c) {
         }
         kv.second.pending.clear();
     }
-}
-
-// Pageable host memory -> device through two pinned staging buffers: the host workers convert / copy chunk k into one
-// buffer while chunk k-1 is on the wire from the other (a plain hipMemcpy from pageable memory is a single-threaded
-// bounce copy).  fill(dst, e0, e1) writes elements [e0, e1) of the output into `dst` (e1 - e0 <= chunk) and may be
-// called from several threads on disjoint sub-ranges.
-template <typename T, typename F, typename A>
-static void staged_upload_chunks(cge_ctx *c, T *dev, size_t total, size_t chunk, size_t dev_ring, F fill, A after) {
-    for (int b = 0; b < 2; b++) c->stage[b].ensure(CGE_STAGE_BYTES);
-    const int nt = std::max(1, std::min(c->n_threads, 8)); // (more fill threads than that slow the link down: profiles/r05_microbench_upload.txt)
-    for (size_t off = 0, k = 0; off < total; off += chunk, k++) {
-        const int b = (int)(k & 1);
-        if (k >= 2) HIP_CHECK(hipEventSynchronize(c->stage_ev[b])); // the copy that last read this buffer is done
-        const size_t len = std::min(chunk, total - off);
-        T *dst = (T *)c->stage[b].p;
-        const size_t per = (len + nt - 1) / nt;
-        const std::function<void(i64)> job = [&](i64 t) {
-            const size_t a = std::min(len, (size_t)t * per), e = std::min(len, a + per);
-            if (e > a) fill(dst + a, off + a, off + e);
-        };
-        c->pool->run(nt, job);
-        T *where = dev_ring ? dev + (k % dev_ring) * chunk : dev + off; // (a ring on the device: `after` consumes the chunk in stream order)
-        HIP_CHECK(hipMemcpyAsync(where, dst, sizeof(T) * len, hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipEventRecord(c->stage_ev[b], c->stream));
-        after(where, off, len);
-    }
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-}
-template <typename T, typename F>
-static void staged_upload(cge_ctx *c, T *dev, size_t total, F fill) {
-    // at least ~8 chunks, so that the fill of one overlaps the copy of the one before it (a 40 MB column of edge ids in one
-    // 64 MiB chunk would be filled, then copied), of at least 2 MiB, at most a staging buffer
-    const size_t cap = CGE_STAGE_BYTES / sizeof(T), lo = ((size_t)2 << 20) / sizeof(T);
-    const size_t chunk = std::min(cap, std::max(lo, (total + 7) / 8));
-    staged_upload_chunks<T>(c, dev, total, chunk, 0, fill, [](T *, size_t, size_t) {});
-}
-
-// host mirror of the row-major embedding: only the generic round-based rss path (ties at the maximum of z, NaNs) and the
-// exact unique-row count read it, so it is fetched on first demand instead of at every upload (1 GB at the headline)
-void cge_ensure_host_embedding(cge_ctx *c) {
-    const size_t need = (size_t)lm_rows(c) * (size_t)c->d; // (option shard_rows: this rank's rows, local ids)
-    if (c->h_Xr.size() == need) return;
-    if (!c->Xr.p || need == 0) CGE_THROW(CGE_E_ARG, "embedding not resident");
-    c->h_Xr.resize(need);
-    HIP_CHECK(hipMemcpyAsync(c->h_Xr.data(), c->Xr.p, sizeof(double) * need, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 
 extern "C" {
@@ -220,69 +157,6 @@ int cge_set_exchange_buffer(cge_ctx *c, void *dev_ptr, int64_t cap) {
 // ---- resident inputs ------------------------------------------------------------------------------
 static void allreduce(cge_ctx *c, double *dev, i64 count, int op);
 static double allreduce_scalar_max(cge_ctx *c, double v);
-// N > 1 with option "shard_ingest": which rows of the caller's edge list / embedding this rank uploads
-static bool ingest_sharded(const cge_ctx *c) { return c->opt_shard_ingest && c->has_coll && c->coll.world > 1; }
-
-// ---- option "shard_rows": the embedding rows sharded by community (common.hpp) ---------------------------------------------
-static bool rows_shard_wanted(const cge_ctx *c) { return c->opt_shard_rows && c->has_coll && c->coll.world > 1; }
-static void rows_unshard(cge_ctx *c) {
-    c->rows_sharded = false;
-    c->n_loc = 0;
-    c->h_loc2glob.clear(); c->h_glob2loc.clear(); c->comm_owner.clear(); c->h_vw_loc.clear();
-    c->loc2glob.release(); c->glob2loc.release(); c->comm_loc.release(); c->vw_loc.release();
-}
-// local copies of the per-vertex tables the row passes read (weights, communities of this rank's rows)
-static void rows_refresh_local_tables(cge_ctx *c) {
-    if (!c->rows_sharded) return;
-    const i64 nl = c->n_loc;
-    if ((i64)c->h_vw.size() == c->n) {
-        c->h_vw_loc.resize(nl);
-        for (i64 i = 0; i < nl; i++) c->h_vw_loc[i] = c->h_vw[c->h_loc2glob[i]];
-        c->vw_loc.alloc_exact(nl);
-        HIP_CHECK(hipMemcpyAsync(c->vw_loc.p, c->h_vw_loc.data(), sizeof(double) * nl, hipMemcpyHostToDevice, c->stream));
-    }
-    std::vector<i32> cl(nl);
-    for (i64 i = 0; i < nl; i++) cl[i] = c->h_comm[c->h_loc2glob[i]];
-    c->comm_loc.alloc_exact(nl);
-    HIP_CHECK(hipMemcpyAsync(c->comm_loc.p, cl.data(), sizeof(i32) * nl, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-}
-// THE OWNERSHIP RULE (the same on every rank: it reads the replicated community vector only): communities by decreasing
-// size (ties: lower id first), each to the rank with the fewest rows so far (ties: lower rank).  cge.jl_amd/dist.py
-// restates it (community_owner) and tests/test_distributed_gloo.py holds the two together.
-static void rows_assign_ownership(cge_ctx *c) {
-    const i64 n = c->n, C = c->n_comm_max, W = c->coll.world;
-    if ((i64)c->h_comm.size() != n || C <= 0)
-        CGE_THROW(CGE_E_ARG, "option shard_rows: upload the communities (cge_set_vertex_data) before the embedding -- the rows are sharded by community");
-    std::vector<i64> size(C, 0), ord(C), load(W, 0);
-    for (i64 i = 0; i < n; i++) size[c->h_comm[i]]++;
-    for (i64 q = 0; q < C; q++) ord[q] = q;
-    std::stable_sort(ord.begin(), ord.end(), [&](i64 a, i64 b) { return size[a] > size[b]; });
-    c->comm_owner.assign(C, 0);
-    for (i64 q : ord) {
-        const int r = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        c->comm_owner[q] = r;
-        load[r] += size[q];
-    }
-    const int me = c->coll.rank;
-    c->h_glob2loc.assign(n, -1);
-    c->h_loc2glob.clear();
-    c->h_loc2glob.reserve(load[me]);
-    for (i64 i = 0; i < n; i++)
-        if (c->comm_owner[c->h_comm[i]] == me) {
-            c->h_glob2loc[i] = (i32)c->h_loc2glob.size();
-            c->h_loc2glob.push_back((i32)i);
-        }
-    c->n_loc = (i64)c->h_loc2glob.size();
-    if (c->n_loc <= 0) CGE_THROW(CGE_E_ARG, "option shard_rows: fewer communities than ranks (rank %d would own no row)", me);
-    c->loc2glob.alloc_exact(c->n_loc);
-    c->glob2loc.alloc_exact(n);
-    HIP_CHECK(hipMemcpyAsync(c->loc2glob.p, c->h_loc2glob.data(), sizeof(i32) * c->n_loc, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(c->glob2loc.p, c->h_glob2loc.data(), sizeof(i32) * n, hipMemcpyHostToDevice, c->stream));
-    c->rows_sharded = true;
-    rows_refresh_local_tables(c);
-}
-
 int cge_set_graph(cge_ctx *c, const int64_t *src, const int64_t *dst, const double *w, int64_t m, int64_t n) {
     if (!c || !src || !dst || m <= 0 || n <= 0 || n >= (1LL << 31)) return CGE_E_ARG;
     CGE_TRY(c)
@@ -355,316 +229,6 @@ int cge_set_graph(cge_ctx *c, const int64_t *src, const int64_t *dst, const doub
     c->n = n;
     c->lm_ready = false;
     c->blocked_ready = false; // the blocked copy of the edge list is rebuilt by the first edge pass
-    CGE_CATCH(c)
-}
-
-// what every form of embedding upload ends with: sizes, the global feature mean (the centre of the diameter kernels'
-// operands).  The centred feature-major copy of the brute-force diameter kernel is built on first use (it is as large as
-// the embedding and the pruned path never reads it).
-static void embedding_resident(cge_ctx *c, i64 n, i64 d) {
-    c->h_Xr.clear();
-    c->h_Xr.shrink_to_fit();
-    c->n = n;
-    c->d = d;
-    c->ldn = (n + 127) / 128 * 128;
-    c->dpad = (d + 15) / 16 * 16;
-    c->Xc.release();
-    c->rnorm.release();
-    c->gmean.alloc_exact((size_t)d);
-    if (c->rows_sharded) { // column sums of the local rows, added over the ranks (every rank ends with the same bits), / n
-        k_col_mean(c, c->Xr.p, c->n_loc, d, c->gmean.p, 1.0);
-        allreduce(c, c->gmean.p, d, 0);
-        k_scale_vector(c, c->gmean.p, d, 1.0 / (double)n);
-    } else
-        k_col_mean(c, c->Xr.p, n, d, c->gmean.p);
-    // A NaN or an Inf anywhere in the embedding reaches its column's mean.  The reference's `hi` is then NaN (extrema() over
-    // distances that hold a NaN, src/divergence.jl:113), and the diameter entry points answer that instead of the maximum over
-    // the pairs that happen to compare: a comparison with NaN is false, so the tile kernels would skip those pairs silently.
-    std::vector<double> hmean(d);
-    HIP_CHECK(hipMemcpyAsync(hmean.data(), c->gmean.p, sizeof(double) * d, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->emb_nonfinite = false;
-    for (double m : hmean) c->emb_nonfinite |= !std::isfinite(m);
-    c->centred_ready = false;
-    c->lm_ready = false;
-}
-int cge_set_embedding(cge_ctx *c, const double *X, int64_t n, int64_t d) {
-    if (!c || !X || n <= 0 || d <= 0) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    if (c->n && c->n != n) CGE_THROW(CGE_E_ASSERT, "No. rows in embedding and no. vertices in a graph differ.");
-    DevBuf<double> col;
-    if (rows_shard_wanted(c)) {
-        // N > 1, option "shard_rows": this rank uploads and KEEPS the rows of its own communities only (n / world rows over
-        // its own PCIe link, nothing over xGMI): the caller's column-major matrix is read as a gather of rows per column
-        rows_assign_ownership(c);
-        const i64 nl = c->n_loc;
-        const i32 *l2g = c->h_loc2glob.data();
-        col.alloc_exact((size_t)nl * d);
-        staged_upload<double>(c, col.p, (size_t)nl * d, [&](double *o, size_t a0, size_t a1) {
-            for (size_t e = a0; e < a1; e++) { // element e of the (nl x d, column-major) slice: column e / nl, local row e % nl
-                const size_t k = e / (size_t)nl, i = e % (size_t)nl;
-                o[e - a0] = X[k * (size_t)n + (size_t)l2g[i]];
-            }
-        });
-        c->Xr.alloc_exact((size_t)nl * d);
-        k_transpose_to_rowmajor(c, col.p, c->Xr.p, nl, d);
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        col.release();
-        embedding_resident(c, n, d);
-        return CGE_OK;
-    }
-    rows_unshard(c);
-    if (ingest_sharded(c)) {
-        // N > 1, option "shard_ingest": every rank uploads n / world ROWS (a strided piece of each column of the caller's
-        // column-major matrix) over its own PCIe link, transposes them into its place of Xr, and the pieces are all-gathered
-        // device to device (xGMI) -- instead of world full uploads side by side.  Equal pieces of `per` rows (ncclAllGather):
-        // Xr carries up to world - 1 rows of padding behind row n.
-        const i64 W = c->coll.world, r = c->coll.rank, per = (n + W - 1) / W;
-        const i64 r0 = std::min<i64>(n, per * r), r1 = std::min<i64>(n, r0 + per), nl = r1 - r0;
-        c->Xr.alloc_exact((size_t)per * W * d);
-        if (nl < per) HIP_CHECK(hipMemsetAsync(c->Xr.p + (size_t)(per * r + nl) * d, 0, sizeof(double) * (size_t)(per - nl) * d, c->stream));
-        if (nl > 0) {
-            col.alloc_exact((size_t)nl * d);
-            staged_upload<double>(c, col.p, (size_t)nl * d, [&](double *o, size_t a0, size_t a1) {
-                for (size_t e = a0; e < a1;) { // element e of the (nl x d, column-major) slice: column e / nl, row r0 + e % nl
-                    const size_t k = e / (size_t)nl, i = e % (size_t)nl, run = std::min<size_t>(a1 - e, (size_t)nl - i);
-                    memcpy(o + (e - a0), X + k * (size_t)n + (size_t)r0 + i, sizeof(double) * run);
-                    e += run;
-                }
-            });
-            k_transpose_to_rowmajor(c, col.p, c->Xr.p + (size_t)per * r * d, nl, d);
-        }
-        cge_allgather_dev(c, c->Xr.p, per * d);
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        col.release();
-        embedding_resident(c, n, d);
-        return CGE_OK;
-    }
-    // The caller's column-major matrix goes up in chunks of whole columns (of row pieces of one column, when a column is
-    // longer than a staging buffer); every chunk is transposed into its place of the row-major Xr right behind its copy, on the
-    // stream, while the next chunk is on the wire: no n x d column-major device buffer, no separate transpose pass.
-    c->Xr.alloc_exact((size_t)n * d);
-    const size_t cap = CGE_STAGE_BYTES / sizeof(double);
-    if ((size_t)n <= cap) {
-        const size_t kc = std::min<size_t>((size_t)d, cap / (size_t)n), chunk = kc * (size_t)n; // whole columns per chunk
-        col.alloc_exact(2 * chunk);
-        staged_upload_chunks<double>(c, col.p, (size_t)n * d, chunk, 2,
-                                     [&](double *o, size_t e0, size_t e1) { memcpy(o, X + e0, sizeof(double) * (e1 - e0)); },
-                                     [&](double *piece, size_t off, size_t len) {
-                                         k_transpose_piece(c, piece, c->Xr.p, n, (i64)(len / (size_t)n), 0, (i64)(off / (size_t)n), d);
-                                     });
-    } else { // one column in row pieces
-        col.alloc_exact(2 * cap);
-        for (i64 k = 0; k < d; k++)
-            staged_upload_chunks<double>(c, col.p, (size_t)n, cap, 2,
-                                         [&](double *o, size_t e0, size_t e1) { memcpy(o, X + (size_t)k * n + e0, sizeof(double) * (e1 - e0)); },
-                                         [&](double *piece, size_t off, size_t len) { k_transpose_piece(c, piece, c->Xr.p, (i64)len, 1, (i64)off, k, d); });
-    }
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    col.release();
-    embedding_resident(c, n, d);
-    CGE_CATCH(c)
-}
-
-int cge_set_embedding_device(cge_ctx *c, const double *X_dev, int64_t n, int64_t d, int row_major) {
-    if (!c || !X_dev || n <= 0 || d <= 0) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    if (c->n && c->n != n) CGE_THROW(CGE_E_ASSERT, "No. rows in embedding and no. vertices in a graph differ.");
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, X_dev) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        CGE_THROW(CGE_E_ARG, "set_embedding_device: the pointer is not device memory");
-    }
-    if (rows_shard_wanted(c)) { // option shard_rows: this rank's rows are gathered out of the caller's matrix
-        rows_assign_ownership(c);
-        c->Xr.alloc_exact((size_t)c->n_loc * d);
-        k_gather_rows_f64(c, X_dev, n, d, row_major, c->loc2glob.p, c->n_loc, c->Xr.p);
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        embedding_resident(c, n, d);
-        return CGE_OK;
-    }
-    rows_unshard(c);
-    c->Xr.alloc_exact((size_t)n * d);
-    if (row_major)
-        HIP_CHECK(hipMemcpyAsync(c->Xr.p, X_dev, sizeof(double) * (size_t)n * d, hipMemcpyDeviceToDevice, c->stream));
-    else
-        k_transpose_to_rowmajor(c, X_dev, c->Xr.p, n, d);
-    HIP_CHECK(hipStreamSynchronize(c->stream)); // the caller may free or reuse its buffer on return
-    embedding_resident(c, n, d);
-    CGE_CATCH(c)
-}
-
-// ---- embedding views: fp64 / fp32 / fp16 / bf16, host or device, either layout, with a leading dimension ------------------------
-// ("Embedding views").  A host view travels in its own type -- raw bytes through the pinned staging -- and is widened
-// on the device (kernels_ingest.hip) behind each chunk, as the fp64 path transposes behind each chunk.
-static int view_check(const cge_embedding_view *v, i64 n, std::string &msg) {
-    char b[256];
-    b[0] = 0;
-    if (!v) snprintf(b, sizeof b, "embedding view: NULL view");
-    else if (!v->data) snprintf(b, sizeof b, "embedding view: NULL data");
-    else if (n <= 0 || v->d <= 0) snprintf(b, sizeof b, "embedding view: n = %lld, d = %lld (both must be positive)", (long long)n, (long long)v->d);
-    else if (v->dtype < CGE_DTYPE_F64 || v->dtype > CGE_DTYPE_BF16) snprintf(b, sizeof b, "embedding view: unknown dtype %d", v->dtype);
-    else if (v->ld < 0 || (v->ld != 0 && v->ld < (v->row_major ? v->d : n)))
-        snprintf(b, sizeof b, "embedding view: leading dimension %lld below the packed %lld", (long long)v->ld, (long long)(v->row_major ? v->d : n));
-    else if ((uintptr_t)v->data % cge_dtype_size(v->dtype) != 0)
-        snprintf(b, sizeof b, "embedding view: data pointer not aligned to its %d-byte elements", (int)cge_dtype_size(v->dtype));
-    else return CGE_OK;
-    msg = b;
-    return CGE_E_ARG;
-}
-int cge_embedding_view_check(const cge_embedding_view *v, int64_t n, char *err, int64_t err_len) {
-    std::string msg;
-    const int rc = view_check(v, n, msg);
-    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", msg.c_str());
-    return rc;
-}
-// bytes [a0, a1) of a packed image made of runs of `run` bytes, run j starting at base + (idx ? idx[j] : j) * pitch
-static void copy_runs(unsigned char *o, size_t a0, size_t a1, const unsigned char *base, size_t run, size_t pitch, const i32 *idx) {
-    if (!idx && run == pitch) { memcpy(o, base + a0, a1 - a0); return; }
-    for (size_t e = a0; e < a1;) {
-        const size_t j = e / run, at = e % run, len = std::min(a1 - e, run - at);
-        memcpy(o + (e - a0), base + (idx ? (size_t)idx[j] : j) * pitch + at, len);
-        e += len;
-    }
-}
-static void set_view_impl(cge_ctx *c, const cge_embedding_view *v, i64 n) {
-    std::string msg;
-    if (view_check(v, n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s", msg.c_str());
-    HIP_CHECK(hipSetDevice(c->device));
-    if (c->n && c->n != n) CGE_THROW(CGE_E_ASSERT, "No. rows in embedding and no. vertices in a graph differ.");
-    const i64 d = v->d;
-    const int dt = v->dtype;
-    const bool rm = v->row_major != 0;
-    const i64 ld = v->ld ? v->ld : (rm ? d : n);
-    const size_t es = cge_dtype_size(dt);
-    if (v->on_device) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, v->data) != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void)hipGetLastError();
-            CGE_THROW(CGE_E_ARG, "set_embedding_view: the pointer of a device view is not device memory");
-        }
-        if (at.device != c->device)
-            CGE_THROW(CGE_E_ARG, "set_embedding_view: the device view lies on GPU %d, the context is on GPU %d", at.device, c->device);
-        if (rows_shard_wanted(c)) { // option shard_rows: this rank's rows are gathered out of the caller's matrix
-            rows_assign_ownership(c);
-            c->Xr.alloc_exact((size_t)c->n_loc * d);
-            k_ingest_gather(c, v->data, dt, ld, d, rm, c->loc2glob.p, c->n_loc, c->Xr.p);
-        } else {
-            rows_unshard(c);
-            c->Xr.alloc_exact((size_t)n * d);
-            if (rm && dt == CGE_DTYPE_F64 && ld == d)
-                HIP_CHECK(hipMemcpyAsync(c->Xr.p, v->data, sizeof(double) * (size_t)n * d, hipMemcpyDeviceToDevice, c->stream));
-            else if (rm)
-                k_ingest_rows(c, v->data, dt, ld, n, d, c->Xr.p);
-            else
-                k_ingest_cols(c, v->data, dt, ld, c->Xr.p, n, d, 0, 0, d);
-        }
-        HIP_CHECK(hipStreamSynchronize(c->stream)); // the caller may free or reuse its buffer on return
-        embedding_resident(c, n, d);
-        return;
-    }
-    const unsigned char *X = (const unsigned char *)v->data;
-    const size_t pitch = (size_t)ld * es;
-    DevBuf<unsigned char> raw; // the typed image on the device: this rank's packed rows, or a ring of two chunks
-    // a packed typed image of `nl` rows (row-major: rows of d; column-major: columns of nl) in `raw` -> rows of Xr at `dst`
-    auto widen_image = [&](i64 nl, double *dst) {
-        if (rm) k_ingest_rows(c, raw.p, dt, d, nl, d, dst);
-        else k_ingest_cols(c, raw.p, dt, nl, dst, nl, d, 0, 0, d);
-    };
-    if (rows_shard_wanted(c)) {
-        // option shard_rows: this rank uploads and KEEPS the rows of its own communities only, in the caller's type: whole rows of
-        // a row-major view, a gather of elements per column of a column-major one (as cge_set_embedding, for any element size)
-        rows_assign_ownership(c);
-        const i64 nl = c->n_loc;
-        const i32 *l2g = c->h_loc2glob.data();
-        raw.alloc_exact((size_t)nl * d * es);
-        if (rm)
-            staged_upload<unsigned char>(c, raw.p, (size_t)nl * d * es, [&](unsigned char *o, size_t a0, size_t a1) {
-                copy_runs(o, a0, a1, X, (size_t)d * es, pitch, l2g);
-            });
-        else { // element e of the (nl x d, column-major) slice: column e / nl, local row e % nl -- a typed fill per element size
-#define CGE_GATHER_COLS(U)                                                                                       \
-    staged_upload<U>(c, (U *)raw.p, (size_t)nl * d, [&](U *o, size_t a0, size_t a1) {                           \
-        const U *Xu = (const U *)X;                                                                              \
-        size_t k = a0 / (size_t)nl, i = a0 % (size_t)nl;                                                         \
-        for (size_t e = a0; e < a1; e++) {                                                                       \
-            o[e - a0] = Xu[k * (size_t)ld + (size_t)l2g[i]];                                                     \
-            if (++i == (size_t)nl) { i = 0; k++; }                                                               \
-        }                                                                                                        \
-    })
-            if (es == 8) CGE_GATHER_COLS(uint64_t);
-            else if (es == 4) CGE_GATHER_COLS(uint32_t);
-            else CGE_GATHER_COLS(uint16_t);
-#undef CGE_GATHER_COLS
-        }
-        c->Xr.alloc_exact((size_t)nl * d);
-        widen_image(nl, c->Xr.p);
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        raw.release();
-        embedding_resident(c, n, d);
-        return;
-    }
-    rows_unshard(c);
-    if (ingest_sharded(c)) {
-        // option shard_ingest: every rank uploads its n / world rows in the caller's type, widens them into its place of Xr, and
-        // the fp64 pieces are all-gathered device to device (cge_set_embedding has the layout of the padded Xr)
-        const i64 W = c->coll.world, r = c->coll.rank, per = (n + W - 1) / W;
-        const i64 r0 = std::min<i64>(n, per * r), r1 = std::min<i64>(n, r0 + per), nl = r1 - r0;
-        c->Xr.alloc_exact((size_t)per * W * d);
-        if (nl < per) HIP_CHECK(hipMemsetAsync(c->Xr.p + (size_t)(per * r + nl) * d, 0, sizeof(double) * (size_t)(per - nl) * d, c->stream));
-        if (nl > 0) {
-            raw.alloc_exact((size_t)nl * d * es);
-            const unsigned char *base = X + (size_t)r0 * (rm ? pitch : es);
-            const size_t run = (size_t)(rm ? d : nl) * es;
-            staged_upload<unsigned char>(c, raw.p, (size_t)nl * d * es,
-                                         [&](unsigned char *o, size_t a0, size_t a1) { copy_runs(o, a0, a1, base, run, pitch, nullptr); });
-            widen_image(nl, c->Xr.p + (size_t)per * r * d);
-        }
-        cge_allgather_dev(c, c->Xr.p, per * d);
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        raw.release();
-        embedding_resident(c, n, d);
-        return;
-    }
-    c->Xr.alloc_exact((size_t)n * d);
-    const size_t cap = CGE_STAGE_BYTES, total = (size_t)n * d * es;
-    if (rm) {
-        // row-major: the packed image has Xr's own order, so a chunk is any run of elements (a multiple of 16 bytes: the ring slots
-        // and the chunk's place in Xr stay aligned for the vector loads and stores) and is widened in place behind its copy
-        const size_t chunk = std::min(cap, std::max((size_t)2 << 20, ((total + 7) / 8 + 15) / 16 * 16));
-        raw.alloc_exact(2 * chunk);
-        staged_upload_chunks<unsigned char>(c, raw.p, total, chunk, 2,
-                                            [&](unsigned char *o, size_t a0, size_t a1) { copy_runs(o, a0, a1, X, (size_t)d * es, pitch, nullptr); },
-                                            [&](unsigned char *piece, size_t off, size_t len) {
-                                                k_ingest_rows(c, piece, dt, (i64)(len / es), 1, (i64)(len / es), c->Xr.p + off / es);
-                                            });
-    } else if ((size_t)n * es <= cap) { // column-major: chunks of whole columns, widened and transposed behind their copy
-        const size_t colb = (size_t)n * es, kc = std::min<size_t>((size_t)d, cap / colb), chunk = kc * colb;
-        raw.alloc_exact(2 * chunk);
-        staged_upload_chunks<unsigned char>(c, raw.p, total, chunk, 2,
-                                            [&](unsigned char *o, size_t a0, size_t a1) { copy_runs(o, a0, a1, X, colb, pitch, nullptr); },
-                                            [&](unsigned char *piece, size_t off, size_t len) {
-                                                k_ingest_cols(c, piece, dt, n, c->Xr.p, n, (i64)(len / colb), 0, (i64)(off / colb), d);
-                                            });
-    } else { // one column in row pieces
-        raw.alloc_exact(2 * cap);
-        for (i64 k = 0; k < d; k++)
-            staged_upload_chunks<unsigned char>(c, raw.p, (size_t)n * es, cap, 2,
-                                                [&](unsigned char *o, size_t a0, size_t a1) { memcpy(o, X + (size_t)k * pitch + a0, a1 - a0); },
-                                                [&](unsigned char *piece, size_t off, size_t len) {
-                                                    k_ingest_cols(c, piece, dt, (i64)(len / es), c->Xr.p, (i64)(len / es), 1, (i64)(off / es), k, d);
-                                                });
-    }
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    raw.release();
-    embedding_resident(c, n, d);
-}
-int cge_set_embedding_view(cge_ctx *c, const cge_embedding_view *v, int64_t n) {
-    if (!c || !v) return CGE_E_ARG;
-    CGE_TRY(c)
-    set_view_impl(c, v, n);
     CGE_CATCH(c)
 }
 
@@ -1488,26 +1052,22 @@ int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, 
 }
 
 // ---- cge_score_batch: K embeddings of the resident graph ("Scoring several embeddings") ----------------------------
-// What differs between cge_score_batch and cge_score_views is how member k becomes the resident embedding (`upload`) and what is
-// checked of the members before any work (`check`, after the checks of the context); `who` names the entry point in messages.
-struct BatchSource {
-    const char *who;
-    i64 K;
-    std::function<void()> check;
-    std::function<int(i64)> upload; // a status of the boundary; the message is in c->err
-};
-static void upload_member(cge_ctx *c, const BatchSource &b, i64 k) {
-    const int rc = b.upload(k);
-    if (rc != CGE_OK) CGE_THROW(rc, "%s: embedding %lld: %s", b.who, (long long)k, std::string(c->err).c_str());
+// A member is a cge_embedding_view (cge_score_batch describes its fp64 matrices as views); `who` names the entry point in messages.
+static void upload_member(cge_ctx *c, const char *who, const cge_embedding_view *views, i64 k) {
+    const int rc = cge_set_embedding_view(c, views + k, c->n); // a status of the boundary; the message is in c->err
+    if (rc != CGE_OK) CGE_THROW(rc, "%s: embedding %lld: %s", who, (long long)k, std::string(c->err).c_str());
 }
-static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const BatchSource &b, double *out, int *out_len,
-                             cge_trace *traces) {
-    const i64 K = b.K;
+static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
+                             int *out_len, cge_trace *traces) {
     if (!c->src.p || !c->vw.p || !c->comm.p || c->n <= 0 || c->m <= 0)
-        CGE_THROW(CGE_E_ARG, "%s: graph and vertex data must be resident (cge_set_graph / cge_set_vertex_data)", b.who);
+        CGE_THROW(CGE_E_ARG, "%s: graph and vertex data must be resident (cge_set_graph / cge_set_vertex_data)", who);
     if (c->has_coll || c->rccl_comm || c->edges_sharded || c->rows_sharded || c->opt_shard_ingest || c->opt_shard_rows)
-        CGE_THROW(CGE_E_ARG, "%s: not under collectives or sharding (one embedding per rank is the multi-GPU form)", b.who);
-    b.check();
+        CGE_THROW(CGE_E_ARG, "%s: not under collectives or sharding (one embedding per rank is the multi-GPU form)", who);
+    for (i64 k = 0; k < K; k++) { // the members, before any work
+        std::string msg;
+        if (view_check(views + k, c->n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s: embedding %lld: %s", who, (long long)k, msg.c_str());
+        if (views[k].on_device) check_device_pointer(c, (std::string(who) + ": embedding " + std::to_string(k)).c_str(), views[k].data);
+    }
     int dev = 0, cus = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -1534,7 +1094,7 @@ static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const BatchSou
         g_sum = 0;
     };
     for (i64 k = 0; k < K; k++) {
-        upload_member(c, b, k);
+        upload_member(c, who, views, k);
         std::unique_ptr<BatchMember> m(new BatchMember());
         m->h.max_G = cus / 2;
         m->out = out + 7 * k; m->out_len = out_len + k; m->trace = traces ? traces + k : nullptr;
@@ -1552,23 +1112,24 @@ static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const BatchSou
     // members whose batched fit was abandoned: cge_score's own path (which falls back to one launch per iteration as it must)
     std::sort(redo.begin(), redo.end());
     for (i64 k : redo) {
-        upload_member(c, b, k);
+        upload_member(c, who, views, k);
         score_one(c, a, out + 7 * k, out_len + k, traces ? traces + k : nullptr, nullptr, true);
     }
     if (!redo.empty() && redo.back() != K - 1) { // the resident embedding and landmark state are the last member's
-        upload_member(c, b, K - 1);
+        upload_member(c, who, views, K - 1);
         landmarks_run_impl(c, a->clusters_flat, a->clusters_off, a->n_clusters, a->land, a->forced, a->method, a->directed,
                            a->directed != 0 || c->opt_landmark_edges != 0);
     }
     c->phases.ms["batch_sweep"] = batch_ms; // the launch groups' sweeps, all members (the other phases: the last member's)
 }
 // the boundary of both batch entry points: every exit leaves the context usable, an error leaves every out_len at 0
-static int score_batch_run(cge_ctx *c, const cge_score_args *a, const BatchSource &b, double *out, int *out_len, cge_trace *traces) {
-    for (i64 k = 0; k < b.K; k++) out_len[k] = 0;
+static int score_batch_run(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
+                           int *out_len, cge_trace *traces) {
+    for (i64 k = 0; k < K; k++) out_len[k] = 0;
     int rc;
     try {
         HIP_CHECK(hipSetDevice(c->device));
-        score_batch_impl(c, a, b, out, out_len, traces);
+        score_batch_impl(c, a, views, K, who, out, out_len, traces);
         rc = CGE_OK;
     } catch (const CgeError &e) {
         c->err = e.msg;
@@ -1584,51 +1145,26 @@ static int score_batch_run(cge_ctx *c, const cge_score_args *a, const BatchSourc
     c->flow_armed_words = 0;
     if (rc != CGE_OK) {
         (void)hipStreamSynchronize(c->stream);
-        for (i64 k = 0; k < b.K; k++) out_len[k] = 0;
+        for (i64 k = 0; k < K; k++) out_len[k] = 0;
     }
     return rc;
-}
-static void check_device_pointer(const char *who, const void *p, i64 k) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        CGE_THROW(CGE_E_ARG, "%s: embedding %lld is not device memory", who, (long long)k);
-    }
 }
 int cge_score_batch(cge_ctx *c, const cge_score_args *a, const cge_embedding_batch *b, double *out, int *out_len,
                     cge_trace *traces) {
     if (!c || !a || !b || !out || !out_len || !b->embeddings || b->K < 1 || b->d <= 0 || (b->row_major && !b->on_device))
         return CGE_E_ARG;
-    BatchSource s;
-    s.who = "score_batch";
-    s.K = b->K;
-    s.check = [&]() {
-        for (i64 k = 0; k < b->K; k++)
-            if (!b->embeddings[k]) CGE_THROW(CGE_E_ARG, "score_batch: embedding %lld is NULL", (long long)k);
-        if (b->on_device)
-            for (i64 k = 0; k < b->K; k++) check_device_pointer(s.who, b->embeddings[k], k);
-    };
-    s.upload = [&](i64 k) {
-        return b->on_device ? cge_set_embedding_device(c, b->embeddings[k], c->n, b->d, b->row_major)
-                            : cge_set_embedding(c, b->embeddings[k], c->n, b->d);
-    };
-    return score_batch_run(c, a, s, out, out_len, traces);
+    std::vector<cge_embedding_view> views; // K packed fp64 views of one shape (a NULL member: the view check refuses it)
+    try {
+        for (i64 k = 0; k < b->K; k++) views.push_back({b->embeddings[k], b->d, 0, CGE_DTYPE_F64, b->on_device, b->row_major});
+    } catch (const std::bad_alloc &) {
+        return CGE_E_OOM;
+    }
+    return score_batch_run(c, a, views.data(), b->K, "score_batch", out, out_len, traces);
 }
 int cge_score_views(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, int64_t K, double *out, int *out_len,
                     cge_trace *traces) {
     if (!c || !a || !views || !out || !out_len || K < 1) return CGE_E_ARG;
-    BatchSource s;
-    s.who = "score_views";
-    s.K = K;
-    s.check = [&]() {
-        for (i64 k = 0; k < K; k++) {
-            std::string msg;
-            if (view_check(views + k, c->n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "score_views: embedding %lld: %s", (long long)k, msg.c_str());
-            if (views[k].on_device) check_device_pointer(s.who, views[k].data, k);
-        }
-    };
-    s.upload = [&](i64 k) { return cge_set_embedding_view(c, views + k, c->n); };
-    return score_batch_run(c, a, s, out, out_len, traces);
+    return score_batch_run(c, a, views, K, "score_views", out, out_len, traces);
 }
 
 // ---- helpers ----------------------------------------------------------------------------------------

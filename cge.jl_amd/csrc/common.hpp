@@ -54,6 +54,24 @@ struct CgeError {
                       hipGetErrorString(_e), __FILE__, __LINE__);                                       \
     } while (0)
 
+// the body of an extern "C" entry point: an exception becomes the context's message and a status
+#define CGE_TRY(ctx) try {
+#define CGE_CATCH(ctx)                                             \
+    }                                                              \
+    catch (const CgeError &e) {                                    \
+        if (ctx) (ctx)->err = e.msg;                               \
+        return e.code;                                             \
+    }                                                              \
+    catch (const std::bad_alloc &) {                               \
+        if (ctx) (ctx)->err = "host allocation failed";            \
+        return CGE_E_OOM;                                          \
+    }                                                              \
+    catch (const std::exception &e) {                              \
+        if (ctx) (ctx)->err = e.what();                            \
+        return CGE_E_ARG;                                          \
+    }                                                              \
+    return CGE_OK;
+
 // Every kernel launch of the library is followed by hipGetLastError: a refused launch (dynamic LDS beyond what the device
 // grants, a bad grid) raises CGE_E_HIP instead of leaving the output at its memset zeros.
 inline void cge_launch_check(const char *what, const char *file, int line) {
@@ -580,17 +598,60 @@ static inline unsigned grid_for(i64 work, int block, i64 cap = 256 * 8) {
 }
 
 #define CGE_STAGE_BYTES ((size_t)64 << 20) // one staging buffer of the uploads (profiles/r05_microbench_upload.txt: 64 MiB chunks reach the link's 54-57 GB/s)
-void cge_ensure_host_embedding(cge_ctx *c); // capi.cpp: fetch the host mirror of Xr on first demand
+// Pageable host memory -> device through two pinned staging buffers: the host workers convert / copy chunk k into one
+// buffer while chunk k-1 is on the wire from the other (a plain hipMemcpy from pageable memory is a single-threaded
+// bounce copy).  fill(dst, e0, e1) writes elements [e0, e1) of the output into `dst` (e1 - e0 <= chunk) and may be
+// called from several threads on disjoint sub-ranges.
+template <typename T, typename F, typename A>
+static void staged_upload_chunks(cge_ctx *c, T *dev, size_t total, size_t chunk, size_t dev_ring, F fill, A after) {
+    for (int b = 0; b < 2; b++) c->stage[b].ensure(CGE_STAGE_BYTES);
+    const int nt = std::max(1, std::min(c->n_threads, 8)); // (more fill threads than that slow the link down: profiles/r05_microbench_upload.txt)
+    for (size_t off = 0, k = 0; off < total; off += chunk, k++) {
+        const int b = (int)(k & 1);
+        if (k >= 2) HIP_CHECK(hipEventSynchronize(c->stage_ev[b])); // the copy that last read this buffer is done
+        const size_t len = std::min(chunk, total - off);
+        T *dst = (T *)c->stage[b].p;
+        const size_t per = (len + nt - 1) / nt;
+        const std::function<void(i64)> job = [&](i64 t) {
+            const size_t a = std::min(len, (size_t)t * per), e = std::min(len, a + per);
+            if (e > a) fill(dst + a, off + a, off + e);
+        };
+        c->pool->run(nt, job);
+        T *where = dev_ring ? dev + (k % dev_ring) * chunk : dev + off; // (a ring on the device: `after` consumes the chunk in stream order)
+        HIP_CHECK(hipMemcpyAsync(where, dst, sizeof(T) * len, hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(hipEventRecord(c->stage_ev[b], c->stream));
+        after(where, off, len);
+    }
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+template <typename T, typename F>
+static void staged_upload(cge_ctx *c, T *dev, size_t total, F fill) {
+    // at least ~8 chunks, so that the fill of one overlaps the copy of the one before it (a 40 MB column of edge ids in one
+    // 64 MiB chunk would be filled, then copied), of at least 2 MiB, at most a staging buffer
+    const size_t cap = CGE_STAGE_BYTES / sizeof(T), lo = ((size_t)2 << 20) / sizeof(T);
+    const size_t chunk = std::min(cap, std::max(lo, (total + 7) / 8));
+    staged_upload_chunks<T>(c, dev, total, chunk, 0, fill, [](T *, size_t, size_t) {});
+}
+
+// ---- embedding_host.cpp: everything that makes an embedding resident ----------------------------------------------------------
+void cge_ensure_host_embedding(cge_ctx *c); // fetch the host mirror of Xr on first demand
+bool ingest_sharded(const cge_ctx *c);      // N > 1 with option "shard_ingest": a rank uploads its share of the edge list / the rows
+void rows_unshard(cge_ctx *c);              // option "shard_rows": drop the ownership tables (the rows are whole again)
+void rows_refresh_local_tables(cge_ctx *c); // ... and re-make this rank's copies of the per-vertex tables
+int view_check(const cge_embedding_view *v, i64 n, std::string &msg); // cge_embedding_view_check; the message in `msg`
+void check_device_pointer(const cge_ctx *c, const char *who, const void *p); // CGE_E_ARG unless p is memory of the context's GPU
 
 // ---- kernels_*.hip entry points (host launchers) ---------------------------------------------
-// layout
-void k_transpose_to_rowmajor(cge_ctx *c, const double *Xcol, double *Xrow, i64 n, i64 d);
-void k_transpose_piece(cge_ctx *c, const double *piece, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d); // rows [i0, i0 + rows) x columns [k0, k0 + cols), column-major piece -> its place in the row-major matrix
 // kernels_ingest.hip: an embedding view (dtype = CGE_DTYPE_*, ld in elements) widened into row-major fp64
 size_t cge_dtype_size(int dtype);
 void k_ingest_rows(cge_ctx *c, const void *src, int dtype, i64 ld, i64 rows, i64 d, double *dst); // dst[i * d + k] = src[i * ld + k]
-void k_ingest_cols(cge_ctx *c, const void *src, int dtype, i64 ld, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d); // k_transpose_piece of a typed piece src[k * ld + i]
-void k_ingest_gather(cge_ctx *c, const void *X, int dtype, i64 ld, i64 d, int row_major, const i32 *idx, i64 cnt, double *out); // k_gather_rows_f64 of a typed matrix
+// rows [i0, i0 + rows) x columns [k0, k0 + cols) of the row-major Xrow (row pitch d) from the column-major piece src[k * ld + i]
+void k_ingest_cols(cge_ctx *c, const void *src, int dtype, i64 ld, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d);
+// out[i][k] = X[idx[i]][k] of a row-major (X[g * ld + k]) or column-major (X[k * ld + g]) matrix; a negative index: a zero row
+void k_ingest_gather(cge_ctx *c, const void *X, int dtype, i64 ld, i64 d, int row_major, const i32 *idx, i64 cnt, double *out);
+// the fp64 forms of the last two for scratch matrices (packed, no kernel timer: they run inside the diameter search and the sampler)
+void k_transpose_to_rowmajor(cge_ctx *c, const double *Xcol, double *Xrow, i64 n, i64 d);
+void k_gather_rows_f64(cge_ctx *c, const double *X, i64 n, i64 d, int row_major, const i32 *idx, i64 cnt, double *out);
 void k_row_hash(cge_ctx *c, const double *Xrow, uint64_t *hash, i64 n, i64 d);
 i64 k_count_distinct(cge_ctx *c, const uint64_t *hash, i64 n); // distinct values among the hashes (device set; synchronises)
 // landmark split primitives (batched over tasks; rows = concatenated 0-based vertex ids)
@@ -707,7 +768,6 @@ void k_pack_landmarks(cge_ctx *c, double *lemb, double *lweight, double *dii, i3
 void k_scatter_u64(cge_ctx *c, const uint64_t *src, const i32 *idx, i64 cnt, uint64_t *dst);
 void k_scatter_i32(cge_ctx *c, const i32 *src, const i32 *idx, i64 cnt, i32 add, i32 *dst); // dst[idx[i]] = src[i] + add
 void k_add_i32(cge_ctx *c, const i32 *src, i64 n, i32 add, i32 *dst);
-void k_gather_rows_f64(cge_ctx *c, const double *X, i64 n, i64 d, int row_major, const i32 *idx, i64 cnt, double *out);
 void k_gather_centre_fm(cge_ctx *c, const double *src_rowmajor, const i32 *idx, const double *mean, double *dst,
                         double *rnorm, i64 npos, i64 d, i64 ld, i64 dpad, float *dst32 = nullptr,
                         unsigned short *planes = nullptr, i64 KP = 0, int *flag = nullptr); // planes: two bf16 terms, row-major [2][ld][KP]

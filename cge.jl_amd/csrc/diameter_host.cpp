@@ -169,7 +169,7 @@ static void ensure_centred(cge_ctx *c) {
 // dist()'s own arithmetic (src/auxilary.jl:14-20) and the largest of THOSE values is `hi` (gram_delta).
 double host_diameter_brute(cge_ctx *c, int part, int nparts, i64 *ai, i64 *aj) {
     ExactBest eb;
-    if (c->emb_nonfinite) // (capi.cpp: embedding_resident)
+    if (c->emb_nonfinite) // (embedding_host.cpp: embedding_resident)
         eb.hi = std::numeric_limits<double>::quiet_NaN(); // as the reference's extrema()
     else {
         ensure_centred(c);

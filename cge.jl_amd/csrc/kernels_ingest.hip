@@ -7,8 +7,10 @@
 //
 // Three families, each templated on the source type:
 //   rows   : row-major source -> Xr, a streaming convert (16-byte loads and stores per lane where the alignment allows);
-//   cols   : column-major source (the whole matrix or an uploaded piece, as transpose_kernel of kernels_lm.hip) -> Xr through LDS;
-//   gather : listed rows of a device-resident source of either layout (option shard_rows), as gather_rows_f64_kernel.
+//   cols   : column-major source (the whole matrix or an uploaded piece) -> Xr through LDS;
+//   gather : listed rows of a device-resident source of either layout (option shard_rows).
+// They are the library's only layout kernels: k_transpose_to_rowmajor and k_gather_rows_f64 at the end are the fp64 instances of
+// cols and gather for scratch matrices.
 #include "common.hpp"
 
 namespace {
@@ -145,9 +147,7 @@ void k_ingest_rows(cge_ctx *c, const void *src, int dtype, i64 ld, i64 rows, i64
                                                   ld, rows, d, dst));
     }
 }
-void k_ingest_cols(cge_ctx *c, const void *src, int dtype, i64 ld, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d) {
-    if (rows <= 0 || cols <= 0) return;
-    ScopedKernelTimer kt(c, "ingest_cols");
+static void launch_cols(cge_ctx *c, const void *src, int dtype, i64 ld, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d) {
     const size_t es = cge_dtype_size(dtype);
     const i64 kmax = (i64)65535 * 32; // columns of one launch (grid.y)
     for (i64 ka = 0; ka < cols; ka += kmax) {
@@ -158,9 +158,24 @@ void k_ingest_cols(cge_ctx *c, const void *src, int dtype, i64 ld, double *Xrow,
                                                   rows, kc, i0, k0 + ka, d));
     }
 }
+static void launch_gather(cge_ctx *c, const void *X, int dtype, i64 ld, i64 d, int row_major, const i32 *idx, i64 cnt, double *out) {
+    INGEST_DISPATCH(dtype, hipLaunchKernelGGL(ingest_gather_kernel<S>, dim3(grid_for(cnt * d, 256, 8192)), dim3(256), 0, c->stream,
+                                              (const S::raw *)X, ld, d, row_major, idx, cnt, out));
+}
+void k_ingest_cols(cge_ctx *c, const void *src, int dtype, i64 ld, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d) {
+    if (rows <= 0 || cols <= 0) return;
+    ScopedKernelTimer kt(c, "ingest_cols");
+    launch_cols(c, src, dtype, ld, Xrow, rows, cols, i0, k0, d);
+}
 void k_ingest_gather(cge_ctx *c, const void *X, int dtype, i64 ld, i64 d, int row_major, const i32 *idx, i64 cnt, double *out) {
     if (cnt <= 0 || d <= 0) return;
     ScopedKernelTimer kt(c, "ingest_gather");
-    INGEST_DISPATCH(dtype, hipLaunchKernelGGL(ingest_gather_kernel<S>, dim3(grid_for(cnt * d, 256, 8192)), dim3(256), 0, c->stream,
-                                              (const S::raw *)X, ld, d, row_major, idx, cnt, out));
+    launch_gather(c, X, dtype, ld, d, row_major, idx, cnt, out);
+}
+// packed fp64 scratch matrices, no timer (common.hpp): a column-major n x d matrix -> row-major; listed rows of an n x d matrix
+void k_transpose_to_rowmajor(cge_ctx *c, const double *Xcol, double *Xrow, i64 n, i64 d) {
+    if (n > 0 && d > 0) launch_cols(c, Xcol, CGE_DTYPE_F64, n, Xrow, n, d, 0, 0, d);
+}
+void k_gather_rows_f64(cge_ctx *c, const double *X, i64 n, i64 d, int row_major, const i32 *idx, i64 cnt, double *out) {
+    if (cnt > 0 && d > 0) launch_gather(c, X, CGE_DTYPE_F64, row_major ? d : n, d, row_major, idx, cnt, out);
 }

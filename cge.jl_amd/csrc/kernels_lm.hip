@@ -84,34 +84,6 @@ void k_wave_tree_test(cge_ctx *c, const double *x, i64 n_rows, double *out_ref, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// column-major (n x d, Julia) -> row-major (node-major).  32x32 tiles through LDS.  The source may be a PIECE of the matrix --
-// rows [i0, i0 + rows) of the columns [k0, k0 + cols), column-major with leading dimension `rows` -- as the chunks of the
-// embedding's upload arrive (cge_set_embedding transposes every chunk behind its copy: no n x d column-major device buffer
-// and no separate pass over it).
-__global__ void transpose_kernel(const double *__restrict__ Xcol, double *__restrict__ Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d) {
-    __shared__ double tile[32][33];
-    i64 ib = (i64)blockIdx.x * 32, kb = (i64)blockIdx.y * 32;
-    int tx = threadIdx.x, ty = threadIdx.y; // 32 x 8
-    for (int r = ty; r < 32; r += 8) {
-        i64 i = ib + tx, k = kb + r;
-        if (i < rows && k < cols) tile[r][tx] = Xcol[i + k * rows];
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        i64 i = ib + r, k = kb + tx;
-        if (i < rows && k < cols) Xrow[(i0 + i) * d + k0 + k] = tile[tx][r];
-    }
-}
-void k_transpose_to_rowmajor(cge_ctx *c, const double *Xcol, double *Xrow, i64 n, i64 d) {
-    dim3 grid((unsigned)((n + 31) / 32), (unsigned)((d + 31) / 32));
-    hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, c->stream, Xcol, Xrow, n, d, (i64)0, (i64)0, d);
-}
-void k_transpose_piece(cge_ctx *c, const double *piece, double *Xrow, i64 rows, i64 cols, i64 i0, i64 k0, i64 d) {
-    dim3 grid((unsigned)((rows + 31) / 32), (unsigned)((cols + 31) / 32));
-    hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, c->stream, piece, Xrow, rows, cols, i0, k0, d);
-}
-
-// ------------------------------------------------------------------------------------------------
 // Global mean (any centre is valid: distances are translation invariant), then the centred
 // feature-major copy Xc[k*n + i] and squared row norms for the diameter kernel.
 __global__ void colsum_partial_kernel(const double *__restrict__ Xrow, i64 n, i64 d, double *__restrict__ part) {
@@ -216,20 +188,6 @@ __global__ void scale_vector_kernel(double *__restrict__ v, i64 n, double f) {
 }
 void k_scale_vector(cge_ctx *c, double *v, i64 n, double f) {
     hipLaunchKernelGGL(scale_vector_kernel, dim3(grid_for(n, 256, 1 << 20)), dim3(256), 0, c->stream, v, n, f);
-}
-// out[i][k] = X[idx[i]][k] for a row-major (n x d) or column-major X: this rank's rows of a device-resident embedding
-__global__ void gather_rows_f64_kernel(const double *__restrict__ X, i64 n, i64 d, int row_major, const i32 *__restrict__ idx,
-                                       i64 cnt, double *__restrict__ out) {
-    const i64 total = cnt * d, stride = (i64)gridDim.x * blockDim.x;
-    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const i64 i = e / d, k = e - i * d, g = idx[i];
-        out[e] = g < 0 ? 0.0 : (row_major ? X[g * d + k] : X[k * n + g]); // (a negative index: a zero row -- another rank fills it)
-    }
-}
-void k_gather_rows_f64(cge_ctx *c, const double *X, i64 n, i64 d, int row_major, const i32 *idx, i64 cnt, double *out) {
-    if (cnt <= 0) return;
-    hipLaunchKernelGGL(gather_rows_f64_kernel, dim3(grid_for(cnt * d, 256, 8192)), dim3(256), 0, c->stream, X, n, d, row_major,
-                       idx, cnt, out);
 }
 // The planes-only form (round 4): when the bound pass reads the bf16 planes (row-major) and nobody needs the feature-major
 // fp64 copy, no transposition is needed at all -- a wave takes whole rows (two consecutive features per lane: one 16-byte

@@ -110,11 +110,14 @@ int cge_comm_finalize(cge_ctx *ctx);
  * outside 1..n leaves NO resident graph (the previous one is released, landmark state is invalidated); upload again.   */
 /* src/dst: the two columns of the reference's `edges::Matrix{Int}` (src/auxilary.jl:106); w: eweights */
 int cge_set_graph(cge_ctx *ctx, const int64_t *src, const int64_t *dst, const double *w, int64_t m, int64_t n);
-/* embedding::Matrix{Float64} n x d column-major (src/auxilary.jl:164) */
+/* embedding::Matrix{Float64} n x d column-major (src/auxilary.jl:164).  A shorthand for cge_set_embedding_view (below) of the view
+ * {X_colmajor, d, ld = 0, CGE_DTYPE_F64, on_device = 0, row_major = 0}: there is one ingest, and this is one of its forms. */
 int cge_set_embedding(cge_ctx *ctx, const double *X_colmajor, int64_t n, int64_t d);
 /* The same for an embedding that already lives in THIS GPU's memory (a host framework's tensor; 41 GB at configuration 5
  * would otherwise cross PCIe): n x d doubles, row-major (row_major = 1: a vertex's d features contiguous) or column-major
- * like Julia's Matrix (0).  Copied (the caller keeps ownership and may free the buffer on return).                      */
+ * like Julia's Matrix (0).  Copied (the caller keeps ownership and may free the buffer on return).  A shorthand for the view
+ * {X_dev, d, ld = 0, CGE_DTYPE_F64, on_device = 1, row_major}; as for every device view, a pointer that is not device memory,
+ * or that lies on another GPU than the context's (the kernels dereference it on the context's GPU), is CGE_E_ARG.        */
 int cge_set_embedding_device(cge_ctx *ctx, const double *X_dev, int64_t n, int64_t d, int row_major);
 /* The embedding AS THE CALLER HOLDS IT: fp64 / fp32 / fp16 / bf16 elements, in host memory or in this GPU's, row-major (a torch
  * tensor, a C-order numpy array) or column-major (Julia's Matrix), packed or with a leading dimension (a column slice X[:, :64] of a
@@ -139,7 +142,8 @@ typedef struct {
  * or NULL data, d <= 0, n <= 0, an unknown dtype, a non-zero ld below the packed value, a data pointer that is not aligned to its
  * element size.  cge_set_embedding_view and cge_score_views call it first. */
 int cge_embedding_view_check(const cge_embedding_view *v, int64_t n, char *err, int64_t err_len);
-/* cge_set_embedding / cge_set_embedding_device for a view.  A device view whose pointer is not device memory: CGE_E_ARG. */
+/* Makes the view the resident embedding (cge_set_embedding / cge_set_embedding_device are shorthands for it).  A device view whose
+ * pointer is not device memory, or lies on another GPU than the context's (the kernels dereference it there): CGE_E_ARG. */
 int cge_set_embedding_view(cge_ctx *ctx, const cge_embedding_view *v, int64_t n);
 /* comm::Matrix{Int} n x 1 (src/auxilary.jl:122-139) and vweight (src/auxilary.jl:104-110) */
 int cge_set_vertex_data(cge_ctx *ctx, const int64_t *comm, const double *vweights, int64_t n);

@@ -4,11 +4,13 @@
 At the headline shape (n = 10^6, d = 128), in one process, each form is uploaded once to warm up and then `--reps` times; the
 wall time of a call is stream-synchronised (every upload entry point returns after its last kernel).  The forms:
 
-    f64_F_host_set_embedding   cge_set_embedding of the float64 column-major array: the path as it always was, the baseline
+    f64_F_host_set_embedding   cge_set_embedding of the float64 column-major array (the fp64 host view): the baseline
     f32_C_host                 cge_set_embedding_view, float32 row-major on the host
     f32_F_host                 ... float32 column-major on the host
     bf16_C_host                ... bfloat16 row-major on the host
     f32_C_device               ... float32 row-major in this GPU's memory
+    f64_F_device               cge_set_embedding_device, float64 column-major in this GPU's memory
+    f64_C_device               ... float64 row-major (the form bench.py uploads)
 
 Per form: median / min milliseconds, the bytes that crossed the link and their rate over the whole call, and -- from a separate,
 event-timed repetition -- the widening kernels' own time and the bytes they read + wrote per second (the copy ceiling of the chip
@@ -46,6 +48,8 @@ def main():
     x32f = np.asfortranarray(x32)
     xb = torch.from_numpy(x32).to(torch.bfloat16)
     x32d = torch.from_numpy(x32).cuda()
+    x64fd = torch.from_numpy(x64f.T).cuda()  # (d, n) C-order: the column-major (n, d) matrix
+    x64cd = x64fd.t().contiguous()
     torch.cuda.synchronize()
     ctx = api.Context(0)
     ctx.set_graph(np.array([[1, n]], dtype=np.int64), np.ones(1), n)
@@ -53,6 +57,8 @@ def main():
              ("f32_C_host", lambda: ctx.set_embedding_view(x32), 4 * n * d, 4),
              ("f32_F_host", lambda: ctx.set_embedding_view(x32f), 4 * n * d, 4),
              ("bf16_C_host", lambda: ctx.set_embedding_view(xb), 2 * n * d, 2),
+             ("f64_F_device", lambda: ctx.set_embedding_device(x64fd.data_ptr(), n, d, row_major=False), 0, 8),
+             ("f64_C_device", lambda: ctx.set_embedding_device(x64cd.data_ptr(), n, d, row_major=True), 0, 8),
              ("f32_C_device", lambda: ctx.set_embedding_view(x32d), 0, 4)]
     out = {"n": n, "d": d, "reps": args.reps, "forms": {}}
     for name, call, link_bytes, es in forms:

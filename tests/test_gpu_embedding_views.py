@@ -219,6 +219,64 @@ def test_host_fp16_column_longer_than_a_staging_buffer(ctx):
     assert np.array_equal(got.view(np.uint64), np.ascontiguousarray(ref).view(np.uint64))
 
 
+# ---- 2b. the fp64 entry points are views: cge_set_embedding / cge_set_embedding_device go through the same ingest -----------------
+@pytest.mark.parametrize("form", ["set_embedding", "device_colmajor", "device_rowmajor"])
+def test_fp64_entry_points_keep_the_callers_bits(ctx, form):
+    """set_embedding (column-major host) and set_embedding_device (either layout) of float64: the resident matrix is the caller's
+    array, bit for bit, at the shapes that straddle the 64 x 32 tile and the 16-byte vector edge."""
+    import torch
+
+    for kind in ("finite", "inf"):
+        for n, d in SHAPES:
+            x = _values("float64", n, d, kind)
+            ref = x.numpy()
+            _graph_of(ctx, n)
+            if form == "set_embedding":
+                ctx.set_embedding(ref)
+            else:
+                row_major = form == "device_rowmajor"
+                t = (x if row_major else x.t()).contiguous().cuda()  # (d, n) C-order: the column-major (n, d) matrix
+                torch.cuda.synchronize()
+                ctx.set_embedding_device(t.data_ptr(), n, d, row_major=row_major)
+            assert ctx.d == d
+            _assert_resident(ctx, ref, np.arange(n))
+
+
+def test_host_fp64_column_major_matrix_in_more_than_one_chunk(ctx):
+    """set_embedding of 70 000 x 128 float64: 71.68 MB against a 64 MiB staging buffer -- 119 whole columns fit a chunk, two chunks.
+    The smallest d = 128 shape that reaches the branch."""
+    n, d = 70_000, 128
+    x = np.asfortranarray(np.random.default_rng(6).standard_normal((n, d)))
+    assert x.nbytes > 64 << 20 and (64 << 20) // (8 * n) == 119 and x.flags.f_contiguous
+    _graph_of(ctx, n)
+    ctx.set_embedding(x)
+    _assert_resident(ctx, np.ascontiguousarray(x))
+
+
+def test_host_fp64_column_longer_than_a_staging_buffer(ctx):
+    """set_embedding of (8 388 609, 2) float64: one column is 8 bytes longer than a 64 MiB staging buffer, so every column goes up
+    in row pieces.  134 MB up, 134 MB back.  The bit patterns: a counter times an odd constant, the top exponent bit cleared (so
+    every value is finite), both signs."""
+    n, d = 8_388_609, 2
+    bits = (np.arange(n * d, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)) & np.uint64(0xBFFFFFFFFFFFFFFF)
+    x = bits.view(np.float64).reshape(d, n).T
+    assert x.shape == (n, d) and x.strides == (8, 8 * n) and 8 * n == (64 << 20) + 8
+    _graph_of(ctx, n)
+    ctx.set_embedding(x)
+    _assert_resident(ctx, np.ascontiguousarray(x))
+
+
+def test_a_host_pointer_handed_to_set_embedding_device_is_refused(ctx):
+    a = np.asfortranarray(_values("float64", 31, 3).numpy())
+    _graph_of(ctx, 31)
+    rc = ctx.L.cge_set_embedding_device(ctx.h, C.c_void_p(a.ctypes.data), C.c_int64(31), C.c_int64(3), C.c_int(0))
+    assert rc == -7  # CGE_E_ARG: the pointer's attributes are asked for, nothing is dereferenced
+    err = ctx.L.cge_last_error(ctx.h)
+    assert b"not device memory" in err and b"set_embedding_device" in err
+    ctx.set_embedding(a)  # the context is as usable as before
+    _assert_resident(ctx, np.ascontiguousarray(a), np.arange(31))
+
+
 # ---- 3. results follow ----------------------------------------------------------------------------------------------------------
 def _scored(ctx, g, **kw):
     res = ctx.score(g["clusters"], 400, seed=5, auc_samples=6000, **kw)
