@@ -133,3 +133,98 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
     HIP_CHECK(hipStreamSynchronize(st)); // (an alpha enqueued ahead for a member that then stopped: nothing reads it)
     if (c->stat_fit_batched_alphas > 0 && !c->fit_persistent_broken) c->fit_fallback_streak = 0; // clean persistent sweeps
 }
+
+// ---- cge_score_batch: K embeddings of the resident graph ("Scoring several embeddings") ----------------------------
+// A member is a cge_embedding_view (cge_score_batch describes its fp64 matrices as views); `who` names the entry point in messages.
+static void upload_member(cge_ctx *c, const char *who, const cge_embedding_view *views, i64 k) {
+    try {
+        set_embedding_view(c, "set_embedding_view", views + k, c->n);
+    } catch (const CgeError &e) {
+        CGE_THROW(e.code, "%s: embedding %lld: %s", who, (long long)k, e.msg.c_str());
+    } catch (const std::bad_alloc &) { // (with the text and the codes of the boundary, CGE_CATCH)
+        CGE_THROW(CGE_E_OOM, "%s: embedding %lld: host allocation failed", who, (long long)k);
+    } catch (const std::exception &e) {
+        CGE_THROW(CGE_E_ARG, "%s: embedding %lld: %s", who, (long long)k, e.what());
+    }
+}
+static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
+                             int *out_len, cge_trace *traces) {
+    if (!c->src.p || !c->vw.p || !c->comm.p || c->n <= 0 || c->m <= 0)
+        CGE_THROW(CGE_E_ARG, "%s: graph and vertex data must be resident (cge_set_graph / cge_set_vertex_data)", who);
+    if (c->has_coll || c->rccl_comm || c->edges_sharded || c->rows_sharded || c->opt_shard_ingest || c->opt_shard_rows)
+        CGE_THROW(CGE_E_ARG, "%s: not under collectives or sharding (one embedding per rank is the multi-GPU form)", who);
+    for (i64 k = 0; k < K; k++) { // the members, before any work
+        std::string msg;
+        if (view_check(views + k, c->n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s: embedding %lld: %s", who, (long long)k, msg.c_str());
+        if (views[k].on_device) check_device_pointer(c, (std::string(who) + ": embedding " + std::to_string(k)).c_str(), views[k].data);
+    }
+    int dev = 0, cus = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    // the members that can take the batched sweep (undirected landmark mode, the fused fit); the sweep decides the rest
+    // (one member, or a member whose fit takes more than half the chip, shares nothing: it is scored as cge_score scores it)
+    const bool batchable = K >= 2 && a->land != -1 && !a->directed && c->opt_fit_fused && c->opt_fit_persistent != 1;
+    c->stat_fit_batched_launches = c->stat_fit_batched_alphas = 0;
+    c->smp.reset();
+    bool have_samples = false;
+    std::vector<std::unique_ptr<BatchMember>> group;
+    std::vector<i64> redo, group_k;
+    int g_sum = 0, g_nw = 0;
+    double batch_ms = 0.0;
+    auto run_group = [&]() {
+        if (group.empty()) return;
+        std::vector<BatchMember *> g;
+        for (auto &m : group) g.push_back(m.get());
+        const double t0 = now_ms();
+        host_batch_sweep(c, g);
+        batch_ms += now_ms() - t0;
+        for (size_t i = 0; i < group.size(); i++)
+            if (group[i]->redo) redo.push_back(group_k[i]);
+        group.clear(); group_k.clear();
+        g_sum = 0;
+    };
+    for (i64 k = 0; k < K; k++) {
+        upload_member(c, who, views, k);
+        std::unique_ptr<BatchMember> m(new BatchMember());
+        m->h.max_G = cus / 2;
+        m->out = out + 7 * k; m->out_len = out_len + k; m->trace = traces ? traces + k : nullptr;
+        host_score(c, a, m->out, m->out_len, m->trace, batchable ? &m->h : nullptr, have_samples);
+        have_samples = have_samples || c->smp.n_sets > 0;
+        if (!m->h.deferred) continue; // (scored: the sequential path)
+        if (batch_group_closes(g_sum, g_nw, (int)group.size(), m->h.G, m->h.NW, cus)) run_group();
+        g_sum += m->h.G;
+        g_nw = m->h.NW;
+        group.push_back(std::move(m));
+        group_k.push_back(k);
+    }
+    run_group();
+    flush_timers(c);
+    // members whose batched fit was abandoned: cge_score's own path (which falls back to one launch per iteration as it must)
+    std::sort(redo.begin(), redo.end());
+    for (i64 k : redo) {
+        upload_member(c, who, views, k);
+        host_score(c, a, out + 7 * k, out_len + k, traces ? traces + k : nullptr, nullptr, true);
+    }
+    if (!redo.empty() && redo.back() != K - 1) { // the resident embedding and landmark state are the last member's
+        upload_member(c, who, views, K - 1);
+        host_landmarks_run(c, score_landmark_run(c, a));
+    }
+    c->phases.ms["batch_sweep"] = batch_ms; // the launch groups' sweeps, all members (the other phases: the last member's)
+}
+// the boundary of both batch entry points: every exit leaves the context usable, an error leaves every out_len at 0
+int score_batch_run(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
+                    int *out_len, cge_trace *traces) {
+    for (i64 k = 0; k < K; k++) out_len[k] = 0;
+    const int rc = [&]() -> int {
+        CGE_TRY_ON_DEVICE(c)
+        score_batch_impl(c, a, views, K, who, out, out_len, traces);
+        CGE_CATCH(c)
+    }();
+    // on every exit: no hand-off slot taken for armed (host_score leaves no pending sample draw behind)
+    c->flow_armed_words = 0;
+    if (rc != CGE_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        for (i64 k = 0; k < K; k++) out_len[k] = 0;
+    }
+    return rc;
+}

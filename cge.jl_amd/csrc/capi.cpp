@@ -1,17 +1,12 @@
-// capi.cpp -- the extern "C" surface declared in include/cge_hip.h.
-#include <algorithm>
-#include <cmath>
-#include <future>
-#include <thread>
-#include <unordered_set>
-
+// capi.cpp -- the extern "C" surface declared in include/cge_hip.h: argument checks, the context's device, a call into a host
+// module (graph_host / embedding_host / landmarks_host / diameter_host / score_host / batch_host; collectives.cpp has the
+// entries of the rank exchange), scalars copied out, an exception turned into a status.  Also the option and statistics tables,
+// the profiling entries and the test hooks of include/cge_hip_testing.h.
 #include "common.hpp"
 #include "../../include/cge_hip_testing.h"
-#include <limits>
 
-void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out);
-
-static void flush_timers(cge_ctx *c) {
+// the event pairs of the finished launches become milliseconds; the events go back to the pool
+void flush_timers(cge_ctx *c) {
     for (auto &kv : c->timers) {
         for (auto &pr : kv.second.pending) {
             float ms = 0.f;
@@ -22,6 +17,13 @@ static void flush_timers(cge_ctx *c) {
         }
         kv.second.pending.clear();
     }
+}
+template <class Map> // the keys of a map, comma-separated, into the caller's buffer
+static int key_names(const Map &m, char *buf, int64_t buf_len) {
+    std::string s;
+    for (auto &kv : m) s += (s.empty() ? "" : ",") + kv.first;
+    snprintf(buf, (size_t)buf_len, "%s", s.c_str());
+    return CGE_OK;
 }
 
 extern "C" {
@@ -48,9 +50,8 @@ int cge_create(cge_ctx **out, int device, void *stream) {
         HIP_CHECK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
         HIP_CHECK(hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&c->copy_done, hipEventDisableTiming));
-        for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&c->sweep_ev[i], hipEventDisableTiming));
-        for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&c->tab_ev[i], hipEventDisableTiming));
-        for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming));
+        for (hipEvent_t *ev : {c->sweep_ev, c->tab_ev, c->stage_ev})
+            for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
         unsigned hc = std::thread::hardware_concurrency();
         c->n_threads = (int)std::max(1u, std::min(hc ? hc : 8u, 16u));
         c->pool = new ThreadPool(c->n_threads - 1);
@@ -96,12 +97,9 @@ void cge_destroy(cge_ctx *c) {
     if (c->copy_ev) (void)hipEventDestroy(c->copy_ev);
     if (c->copy_done) (void)hipEventDestroy(c->copy_done);
     if (c->samp_ev) (void)hipEventDestroy(c->samp_ev);
-    for (int i = 0; i < 2; i++) {
-        if (c->sweep_ev[i]) (void)hipEventDestroy(c->sweep_ev[i]);
-        if (c->tab_ev[i]) (void)hipEventDestroy(c->tab_ev[i]);
-    }
-    for (int i = 0; i < 2; i++)
-        if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
+    for (hipEvent_t *ev : {c->sweep_ev, c->tab_ev, c->stage_ev})
+        for (int i = 0; i < 2; i++)
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
     delete c->pool;
     c->pool = nullptr;
     delete c;
@@ -117,475 +115,27 @@ int cge_set_host_threads(cge_ctx *c, int n) {
     return CGE_OK;
 }
 
-int cge_set_collectives(cge_ctx *c, const cge_collectives *coll) {
-    if (!c) return CGE_E_ARG;
-    if (!coll || !coll->allreduce_f64 || coll->world <= 1) {
-        c->has_coll = false;
-        c->coll_ext = cge_collectives_ext{};
-        return CGE_OK;
-    }
-    c->coll = *coll;
-    c->coll_ext = cge_collectives_ext{};
-    c->has_coll = true;
-    return CGE_OK;
-}
-int cge_set_collectives_ext(cge_ctx *c, const cge_collectives_ext *ext) {
-    if (!c) return CGE_E_ARG;
-    c->coll_ext = ext ? *ext : cge_collectives_ext{};
-    return CGE_OK;
-}
-
-int cge_exchange_buffer(cge_ctx *c, int64_t min_doubles, void **dev_ptr, int64_t *cap) {
-    if (!c) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    if ((size_t)min_doubles > c->xown.n || !c->xown.p) c->xown.alloc_exact((size_t)std::max<i64>(min_doubles, 1024));
-    c->xptr = c->xown.p;
-    c->xcap = c->xown.n;
-    if (dev_ptr) *dev_ptr = c->xptr;
-    if (cap) *cap = (int64_t)c->xcap;
-    CGE_CATCH(c)
-}
-
-int cge_set_exchange_buffer(cge_ctx *c, void *dev_ptr, int64_t cap) {
-    if (!c || !dev_ptr || cap < 1) return CGE_E_ARG;
-    c->xptr = (double *)dev_ptr;
-    c->xcap = (size_t)cap;
-    return CGE_OK;
-}
-
 // ---- resident inputs ------------------------------------------------------------------------------
-static void allreduce(cge_ctx *c, double *dev, i64 count, int op);
-static double allreduce_scalar_max(cge_ctx *c, double v);
 int cge_set_graph(cge_ctx *c, const int64_t *src, const int64_t *dst, const double *w, int64_t m, int64_t n) {
-    if (!c || !src || !dst || m <= 0 || n <= 0 || n >= (1LL << 31)) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    // N > 1, option "shard_ingest": this rank uploads and keeps rows [e0, e1) of the list only (the edge passes are sums over
-    // edges: every rank scatters what it holds and the all-reduce adds; the sampler's look-ups are exchanged, kernels_fit.hip).
-    // Not for graphs small enough for the sampler to enumerate their non-edges on the host (wgcl_host.cpp).
-    const bool shard = ingest_sharded(c) && (double)n * (double)(n - 1) > 33554432.0 && m >= c->coll.world;
-    const i64 e0 = shard ? m * c->coll.rank / c->coll.world : 0, e1 = shard ? m * (c->coll.rank + 1) / c->coll.world : m;
-    const i64 ml = e1 - e0;
-    c->src.alloc_exact(ml);
-    c->dst.alloc_exact(ml);
-    // ids: validated and narrowed to 0-based int32 by the host workers on their way into the staging buffers
-    std::atomic<i64> bad{-1};
-    for (int col = 0; col < 2; col++) {
-        const int64_t *h = (col ? dst : src) + e0;
-        staged_upload<i32>(c, col ? c->dst.p : c->src.p, (size_t)ml, [&](i32 *o, size_t a0, size_t a1) {
-            for (size_t e = a0; e < a1; e++) {
-                const int64_t v = h[e];
-                if (v < 1 || v > n) { i64 exp = -1; bad.compare_exchange_strong(exp, (i64)e); }
-                o[e - a0] = (i32)(v - 1);
-            }
-        });
-    }
-    // (sharded: every rank must take the same exit -- the verdicts are exchanged before anybody throws)
-    const bool any_bad = shard ? allreduce_scalar_max(c, bad.load() >= 0 ? 1.0 : 0.0) != 0.0 : bad.load() >= 0;
-    if (any_bad) {
-        c->src.release(); c->dst.release(); c->m = c->m_total = 0; // (the previous resident graph is gone: cge_hip.h says so)
-        c->blocked_ready = false; c->be_nchunks = 0; c->lm_ready = false;
-        if (bad.load() >= 0)
-            CGE_THROW(CGE_E_ARG, "edge %lld has a vertex id outside 1..%lld", (long long)(e0 + bad.load()) + 1, (long long)n);
-        CGE_THROW(CGE_E_ARG, "an edge held by another rank has a vertex id outside 1..%lld", (long long)n);
-    }
-    // weights: all ones (an unweighted list, src/auxilary.jl:105) => neither a device copy nor a host mirror is kept
-    bool unit = true;
-    if (w) {
-        const int nt = std::max(1, c->n_threads);
-        std::vector<char> nonunit(nt, 0);
-        const i64 per = (ml + nt - 1) / nt;
-        const std::function<void(i64)> job = [&](i64 t) {
-            const i64 a = std::min<i64>(ml, t * per), e = std::min<i64>(ml, a + per);
-            char f = 0;
-            for (i64 k = a; k < e && !f; k++) f = w[e0 + k] != 1.0;
-            nonunit[t] = f;
-        };
-        c->pool->run(nt, job);
-        for (char f : nonunit) unit = unit && !f;
-    }
-    if (shard) unit = allreduce_scalar_max(c, unit ? 0.0 : 1.0) == 0.0;
-    c->unit_weights = unit;
-    c->h_w.clear();
-    c->w.release();
-    if (!unit) {
-        c->h_w.assign(w + e0, w + e1); // mirror: weights of host-side sample draws
-        c->w.alloc_exact(ml);
-        staged_upload<double>(c, c->w.p, (size_t)ml, [&](double *o, size_t a0, size_t a1) { memcpy(o, w + e0 + a0, sizeof(double) * (a1 - a0)); });
-    }
-    c->m_total = m;
-    c->e_first = e0;
-    c->edges_sharded = shard;
-    m = ml;
-    c->m = m;
-    if (c->n && c->n != n) { // another vertex set: nothing that was sized for the old one may survive (stale or short buffers)
-        c->h_Xr.clear(); c->h_vw.clear(); c->h_comm.clear();
-        c->Xr.release(); c->Xc.release(); c->rnorm.release(); c->vw.release(); c->comm.release(); c->comm16.release();
-        c->d = 0;
-        c->centred_ready = false;
-        rows_unshard(c);
-    }
-    c->n = n;
-    c->lm_ready = false;
-    c->blocked_ready = false; // the blocked copy of the edge list is rebuilt by the first edge pass
+    if (!c) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    set_graph(c, src, dst, w, m, n);
     CGE_CATCH(c)
 }
 
 int cge_set_vertex_data(cge_ctx *c, const int64_t *comm, const double *vw, int64_t n) {
-    if (!c || n <= 0) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    if (c->n && c->n != n) CGE_THROW(CGE_E_ASSERT, "No. communities (%lld) differ from no. nodes (%lld)", (long long)n, (long long)c->n);
-    c->n = n;
-    if (comm && c->rows_sharded) {
-        // the rows are sharded BY COMMUNITY: another community vector is another ownership -- the resident rows are dropped
-        // (upload the embedding again after this call)
-        bool same = (i64)c->h_comm.size() == n;
-        for (i64 i = 0; same && i < n; i++) same = c->h_comm[i] == (i32)(comm[i] - 1);
-        if (!same) {
-            c->Xr.release(); c->h_Xr.clear();
-            c->d = 0;
-            rows_unshard(c);
-        }
-    }
-    if (comm) {
-        c->h_comm.resize(n);
-        i64 cmax = 0;
-        for (i64 i = 0; i < n; i++) {
-            if (comm[i] < 1) CGE_THROW(CGE_E_ARG, "community ids must be 1-based");
-            c->h_comm[i] = (i32)(comm[i] - 1);
-            cmax = std::max<i64>(cmax, comm[i]);
-        }
-        c->n_comm_max = cmax;
-        c->comm.alloc_exact(n);
-        HIP_CHECK(hipMemcpyAsync(c->comm.p, c->h_comm.data(), sizeof(i32) * n, hipMemcpyHostToDevice, c->stream));
-        c->comm16.release();
-        if (cmax < 65536) {
-            const i64 npad = (n + CGE_COMM16_PAD - 1) / CGE_COMM16_PAD * CGE_COMM16_PAD; // whole vertex blocks (edge pass)
-            std::vector<unsigned short> c16(npad, 0);
-            for (i64 i = 0; i < n; i++) c16[i] = (unsigned short)c->h_comm[i];
-            c->comm16.alloc_exact(npad);
-            HIP_CHECK(hipMemcpyAsync(c->comm16.p, c16.data(), sizeof(unsigned short) * npad, hipMemcpyHostToDevice, c->stream));
-            HIP_CHECK(hipStreamSynchronize(c->stream)); // c16 goes out of scope
-        }
-    }
-    if (vw) {
-        c->h_vw.assign(vw, vw + n);
-        c->vw.alloc_exact(n);
-        HIP_CHECK(hipMemcpyAsync(c->vw.p, c->h_vw.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    rows_refresh_local_tables(c);
-    c->lm_ready = false;
+    if (!c) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    set_vertex_data(c, comm, vw, n);
     CGE_CATCH(c)
 }
 
 // ---- landmarks ------------------------------------------------------------------------------------
-// `size(unique(embedding, dims=1), 1)` clamp (src/landmarks.jl:371-376).  Equal rows have equal
-// hashes, so #distinct hashes <= #unique rows: once `land` distinct hashes are seen no clamp can
-// apply; otherwise count exactly on the host mirror.
-static i64 clamp_to_unique_rows(cge_ctx *c, i64 land, int *truncated) {
-    const i64 n = c->n, d = c->d;
-    *truncated = 0;
-    if (land <= 1) return land;
-    // `land` distinct hashes among a prefix of the rows already prove `land` distinct rows: hash 8*land rows first,
-    // the whole matrix only when that prefix does not settle it.  The distinct hashes are counted on the device (a set
-    // of atomicCAS slots): one 8-byte read-back instead of the hashes themselves and a host set.
-    i64 done = 0;
-    c->uniq_hash.ensure(n);
-    if (c->rows_sharded) {
-        // option shard_rows: every rank hashes its rows, the hashes are gathered by vertex id (8 bytes per vertex) and every
-        // rank counts the distinct ones; only if that leaves the clamp open are the rows with a shared hash -- the only
-        // candidates for equal rows -- gathered and compared bit for bit
-        const i64 nl = c->n_loc;
-        DevBuf<uint64_t> hl;
-        hl.ensure(nl);
-        k_row_hash(c, c->Xr.p, hl.p, nl, d);
-        HIP_CHECK(hipMemsetAsync(c->uniq_hash.p, 0, sizeof(uint64_t) * n, c->stream));
-        k_scatter_u64(c, hl.p, c->loc2glob.p, nl, c->uniq_hash.p);
-        allreduce(c, reinterpret_cast<double *>(c->uniq_hash.p), n, 2);
-        if (k_count_distinct(c, c->uniq_hash.p, n) >= land) return land;
-        std::vector<uint64_t> hh(n);
-        HIP_CHECK(hipMemcpyAsync(hh.data(), c->uniq_hash.p, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        std::vector<i64> ix(n);
-        for (i64 i = 0; i < n; i++) ix[i] = i;
-        std::sort(ix.begin(), ix.end(), [&](i64 a, i64 b) { return hh[a] < hh[b] || (hh[a] == hh[b] && a < b); });
-        std::vector<i32> dup; // vertices whose hash is shared, grouped by hash
-        std::vector<i64> run_off(1, 0);
-        i64 uniq = 0;
-        for (i64 a = 0; a < n;) {
-            i64 b = a + 1;
-            while (b < n && hh[ix[b]] == hh[ix[a]]) b++;
-            if (b - a > 1) {
-                for (i64 q = a; q < b; q++) dup.push_back((i32)ix[q]);
-                run_off.push_back((i64)dup.size());
-            } else
-                uniq++;
-            a = b;
-        }
-        if (!dup.empty()) {
-            const i64 nd = (i64)dup.size();
-            std::vector<i32> lidx(nd);
-            for (i64 q = 0; q < nd; q++) lidx[q] = c->h_glob2loc[dup[q]];
-            DevBuf<i32> didx;
-            DevBuf<double> rows;
-            didx.ensure(nd);
-            rows.ensure((size_t)nd * d);
-            HIP_CHECK(hipMemcpyAsync(didx.p, lidx.data(), sizeof(i32) * nd, hipMemcpyHostToDevice, c->stream));
-            k_gather_rows_f64(c, c->Xr.p, nl, d, 1, didx.p, nd, rows.p);
-            allreduce(c, rows.p, nd * d, 2);
-            std::vector<double> hr((size_t)nd * d);
-            HIP_CHECK(hipMemcpyAsync(hr.data(), rows.p, sizeof(double) * nd * d, hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            for (size_t r = 0; r + 1 < run_off.size(); r++) {
-                std::vector<i64> q(run_off[r + 1] - run_off[r]);
-                for (size_t t = 0; t < q.size(); t++) q[t] = run_off[r] + (i64)t;
-                std::sort(q.begin(), q.end(), [&](i64 a, i64 b) { return memcmp(&hr[a * d], &hr[b * d], sizeof(double) * d) < 0; });
-                uniq++;
-                for (size_t t = 1; t < q.size(); t++)
-                    if (memcmp(&hr[q[t - 1] * d], &hr[q[t] * d], sizeof(double) * d) != 0) uniq++;
-            }
-        }
-        if (land > uniq) {
-            *truncated = 1;
-            return uniq;
-        }
-        return land;
-    }
-    for (int pass = 0; pass < 2 && done < n; pass++) {
-        const i64 upto = pass == 0 ? std::min<i64>(n, 8 * land) : n;
-        k_row_hash(c, c->Xr.p + done * d, c->uniq_hash.p + done, upto - done, d);
-        if (k_count_distinct(c, c->uniq_hash.p, upto) >= land) return land;
-        done = upto;
-    }
-    // fewer distinct hashes than `land`: count bitwise-distinct rows exactly
-    std::vector<i64> ix(n);
-    for (i64 i = 0; i < n; i++) ix[i] = i;
-    cge_ensure_host_embedding(c);
-    const double *X = c->h_Xr.data();
-    auto cmp = [&](i64 a, i64 b) { return memcmp(X + a * d, X + b * d, sizeof(double) * d) < 0; };
-    std::sort(ix.begin(), ix.end(), cmp);
-    i64 uniq = n > 0 ? 1 : 0;
-    for (i64 i = 1; i < n; i++)
-        if (memcmp(X + ix[i - 1] * d, X + ix[i] * d, sizeof(double) * d) != 0) uniq++;
-    if (land > uniq) {
-        *truncated = 1;
-        return uniq;
-    }
-    return land;
-}
-
-static void allreduce(cge_ctx *c, double *dev, i64 count, int op) {
-    if (!c->has_coll) return;
-    if (c->rccl_comm) { // in-library RCCL: stream-ordered, in place, no host synchronisation
-        cge_rccl_allreduce(c, dev, count, op);
-        return;
-    }
-    // the hook works on the ctx exchange buffer (the host side wrapped that pointer once); a vector that lives elsewhere
-    // and is longer than the buffer goes through it in pieces (an all-reduce is element-wise)
-    if (!c->xptr || c->xcap == 0 || (dev == c->xptr && (size_t)count > c->xcap))
-        CGE_THROW(CGE_E_COLLECTIVE, "exchange buffer too small: need %lld doubles, have %lld", (long long)count, (long long)c->xcap);
-    for (i64 off = 0; off < count; off += (i64)c->xcap) {
-        const i64 piece = std::min<i64>((i64)c->xcap, count - off);
-        if (dev != c->xptr)
-            HIP_CHECK(hipMemcpyAsync(c->xptr, dev + off, sizeof(double) * piece, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->coll.allreduce_f64(c->coll.user, c->xptr, piece, op) != 0) CGE_THROW(CGE_E_COLLECTIVE, "allreduce hook failed");
-        c->stat_coll_calls++;
-        c->stat_coll_bytes += 8 * piece;
-        if (dev != c->xptr)
-            HIP_CHECK(hipMemcpyAsync(dev + off, c->xptr, sizeof(double) * piece, hipMemcpyDeviceToDevice, c->stream));
-    }
-}
-
-static double allreduce_scalar_max(cge_ctx *c, double v) {
-    if (!c->has_coll) return v;
-    if (!cge_exchange_fits(c, 1)) CGE_THROW(CGE_E_COLLECTIVE, "no exchange buffer set");
-    HIP_CHECK(hipMemcpyAsync(c->xptr, &v, sizeof(double), hipMemcpyHostToDevice, c->stream));
-    allreduce(c, c->xptr, 1, 1);
-    HIP_CHECK(hipMemcpyAsync(&v, c->xptr, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    return v;
-}
-
-static void build_landmark_index(cge_ctx *c, const std::vector<i32> &v2l0, i64 N);
-// the resident inputs a landmark / score run reads: all present and all sized for the same vertex set
-static void check_resident(cge_ctx *c, const char *who) {
-    if (!c->Xr.p || !c->vw.p || !c->comm.p || !c->src.p)
-        CGE_THROW(CGE_E_ARG, "%s: graph, embedding and vertex data must be resident (cge_set_graph / cge_set_embedding / "
-                             "cge_set_vertex_data; a cge_wgcl call in exact mode replaces the resident graph)", who);
-    const size_t n = (size_t)c->n;
-    const size_t rows = (size_t)lm_rows(c);
-    if (c->rows_sharded && (!c->vw_loc.p || !c->comm_loc.p))
-        CGE_THROW(CGE_E_ARG, "%s: option shard_rows needs the vertex weights and communities resident (cge_set_vertex_data)", who);
-    if (c->n <= 0 || c->d <= 0 || c->m <= 0 || c->Xr.n < rows * (size_t)c->d || c->vw.n < n || c->comm.n < n ||
-        c->src.n < (size_t)c->m || c->dst.n < (size_t)c->m)
-        CGE_THROW(CGE_E_ARG, "%s: resident inputs are inconsistent (n = %lld, d = %lld, m = %lld): upload them again", who,
-                  (long long)c->n, (long long)c->d, (long long)c->m);
-}
-// per-edge scatter of the resident graph into the landmark-pair matrix (and its positive-entry count)
-// the row block of the landmark-pair matrix this rank ends up with after the reduce-scatter: equal blocks of `per` rows
-static inline i64 wedge_rows_per_rank(const cge_ctx *c, i64 N) { return c->has_coll ? (N + c->coll.world - 1) / c->coll.world : N; }
-static void scatter_wedges(cge_ctx *c, int directed) {
-    const i64 N = c->N;
-    hipStream_t st = c->stream;
-    const i64 per = wedge_rows_per_rank(c, N), Npad = c->has_coll ? per * c->coll.world : N; // (padding rows behind row N: zeros)
-    c->wedges.ensure((size_t)Npad * N);
-    c->wedges_block_only = false;
-    DevBuf<i64> &cnt = c->wed_cnt;
-    cnt.ensure(1);
-    // this rank's share of the edges: of a replicated list its slice of the chunks; of a sharded list all that it holds
-    const int rank = (c->has_coll && !c->edges_sharded) ? c->coll.rank : 0, world = (c->has_coll && !c->edges_sharded) ? c->coll.world : 1;
-    // the tiled two-pass form on the blocked copy of the edge list (kernels_scatter.hip): the tiles are written whole, the
-    // positive entries counted on the way (one rank) -- else the gather + atomics kernel into a zeroed matrix
-    bool tiled = (c->blocked_ready || (k_blocked_edges_possible(c) && k_build_blocked_edges(c))) &&
-                 k_wedge_scatter_blocked(c, c->v2l.p, N, c->be_nchunks * rank / world, c->be_nchunks * (rank + 1) / world, directed,
-                                         c->wedges.p, cnt.p);
-    if (!tiled) {
-        HIP_CHECK(hipMemsetAsync(c->wedges.p, 0, sizeof(double) * N * N, st));
-        const i64 e0 = c->m * rank / world, e1 = c->m * (rank + 1) / world;
-        k_edge_scatter(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, e0, e1, c->v2l.p, c->comm.p, N,
-                       c->n_comm_max, directed, c->wedges.p, nullptr);
-    }
-    if (c->has_coll) {
-        // every rank has summed ITS edges into a full N x N matrix; the sums over the ranks go out BY ROW BLOCK (SURVEY 8(e):
-        // reduce-scatter, not all-reduce): rank r ends with rows [per r, per (r + 1)).  What reads the matrix afterwards works
-        // on row blocks (the count below, the directed score's degrees); landmarks_fetch all-gathers the blocks when the host
-        // asks for the edge list.  Through the hook (gloo tests) or a librccl without the symbol: an all-reduce.
-        if (Npad > N) HIP_CHECK(hipMemsetAsync(c->wedges.p + (size_t)N * N, 0, sizeof(double) * (size_t)(Npad - N) * N, st));
-        // Option "wedges_reduce_scatter" (default 0: the all-reduce, after which every consumer -- cge_landmarks_fetch on ONE
-        // rank included -- is local).  With it the matrix goes out by row blocks; the consumers then work on blocks, and a
-        // fetch of the edge list is COLLECTIVE (every rank must call it: the blocks are all-gathered).
-        bool by_blocks = false;
-        if (c->opt_wedges_rs) {
-            if (c->rccl_comm) by_blocks = cge_rccl_reduce_scatter(c, c->wedges.p, per * N);
-            else if (c->coll_ext.reduce_scatter_f64 && c->xptr && (size_t)(per * N * c->coll.world) <= c->xcap) {
-                const i64 tot = per * N * c->coll.world;
-                HIP_CHECK(hipMemcpyAsync(c->xptr, c->wedges.p, sizeof(double) * tot, hipMemcpyDeviceToDevice, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                if (c->coll_ext.reduce_scatter_f64(c->coll.user, c->xptr, per * N) != 0) CGE_THROW(CGE_E_COLLECTIVE, "reduce-scatter hook failed");
-                c->stat_coll_calls++;
-                c->stat_coll_bytes += 8 * tot;
-                HIP_CHECK(hipMemcpyAsync(c->wedges.p, c->xptr, sizeof(double) * tot, hipMemcpyDeviceToDevice, st));
-                by_blocks = true;
-            }
-        }
-        if (by_blocks) c->wedges_block_only = true;
-        else allreduce(c, c->wedges.p, N * N, 0);
-        const i64 r0 = std::min<i64>(N, per * c->coll.rank), r1 = std::min<i64>(N, r0 + per);
-        k_compact_count(c, c->wedges.p, N, directed, cnt.p, r0, r1);
-        allreduce(c, reinterpret_cast<double *>(cnt.p), 1, 2); // (integer sum of the ranks' counts)
-    } else if (!tiled)
-        k_compact_count(c, c->wedges.p, N, directed, cnt.p);
-    HIP_CHECK(hipMemcpyAsync(&c->n_ledges, cnt.p, sizeof(i64), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->wedges_ready = true;
-}
-// the whole matrix on this rank (landmarks_fetch): the row blocks of a reduce-scattered matrix are all-gathered in place
-static void wedges_whole(cge_ctx *c) {
-    if (!c->wedges_block_only) return;
-    cge_allgather_dev(c, c->wedges.p, wedge_rows_per_rank(c, c->N) * c->N);
-    c->wedges_block_only = false;
-}
-
-// vect_C of the resident graph (src/divergence.jl:59-63 / :337-345 on the original edges): the blocked two-pass form
-// (kernels_scatter.hip) where it applies, else the gather + atomics kernel; this rank's share, then the all-reduce
-static void scatter_vectC_resident(cge_ctx *c, i64 C, int directed, double *vectC) {
-    const i64 vlen = directed ? C * C : packed_len(C);
-    const int rank = (c->has_coll && !c->edges_sharded) ? c->coll.rank : 0, world = (c->has_coll && !c->edges_sharded) ? c->coll.world : 1;
-    bool done = false;
-    if (k_edge_scatter_blocked_applies(c, C) && (c->blocked_ready || k_build_blocked_edges(c))) {
-        k_edge_scatter_blocked(c, c->be_nchunks * rank / world, c->be_nchunks * (rank + 1) / world, C, directed, vectC);
-        done = true;
-    } else if (C > 1 && C <= 16384 && (c->blocked_ready || (k_blocked_edges_possible(c) && k_build_blocked_edges(c)))) {
-        // beyond the 2048 row counters of the row-bucketed form: the community pairs as a dense C x C matrix through the
-        // TILED two-pass form of the landmark-pair matrix (tiles of rows in LDS, written whole), then packed
-        DevBuf<i64> &cnt = c->wed_cnt;
-        cnt.ensure(1);
-        double *dense = vectC;
-        if (!directed) { c->cc_dense.ensure((size_t)C * C); dense = c->cc_dense.p; }
-        if (k_wedge_scatter_blocked(c, c->comm.p, C, c->be_nchunks * rank / world, c->be_nchunks * (rank + 1) / world, directed,
-                                    dense, cnt.p, "edge_scatter")) {
-            if (!directed) k_pack_upper(c, dense, C, vectC);
-            done = true;
-        }
-    }
-    if (!done) {
-        HIP_CHECK(hipMemsetAsync(vectC, 0, sizeof(double) * vlen, c->stream));
-        k_edge_scatter(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, c->m * rank / world, c->m * (rank + 1) / world,
-                       nullptr, c->comm.p, 1, C, directed, nullptr, vectC);
-    }
-    if (c->has_coll) allreduce(c, vectC, vlen, 0);
-}
-
-static void landmarks_run_impl(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 land, i64 forced,
-                               int method, int directed, bool need_wedges) {
-    check_resident(c, "landmarks");
-    if (method < 0 || method > 3) CGE_THROW(CGE_E_ARG, "unknown split method %d", method);
-    const i64 d = c->d;
-    hipStream_t st = c->stream;
-    double t0 = now_ms();
-    land = clamp_to_unique_rows(c, land, &c->lm_truncated);
-    c->phases.ms["lm_unique"] = now_ms() - t0;
-    if (c->after_unique) { // (cge_score: the sample draws go in here -- the host now sets up runsplit for a few hundred microseconds)
-        std::function<void()> f;
-        f.swap(c->after_unique);
-        f();
-    }
-    std::vector<i64> gid;
-    host_runsplit(c, cl_flat, cl_off, ncl, land, forced, method, gid, true); // leaves v2l and the landmark index on the device
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->phases.ms["landmarks"] = now_ms() - t0;
-    t0 = now_ms();
-    const i64 N = (i64)c->h_mem_off.size() - 1; // every group is non-empty
-    c->N = N;
-    c->h_v2l.clear(); // v_to_l (:379) is read back from the device by landmarks_fetch
-    c->lemb.ensure((size_t)N * d);
-    c->lweight.ensure(N);
-    c->dii.ensure(N);
-    c->lcomm.ensure(N);
-    {
-        ScopedKernelTimer tm(c, "landmark_aggregate");
-        k_landmark_aggregate(c, c->Xr.p, lm_vw(c), lm_comm(c), c->lm_memoff.p, c->lm_mem.p, N, d, c->lemb.p, c->lweight.p, c->dii.p,
-                             c->lcomm.p);
-    }
-    if (c->rows_sharded) {
-        // option shard_rows: a landmark's members live on one rank, which has just aggregated it (the others wrote zeros for
-        // it); centroids, weights, d_ii and communities of ALL landmarks on every rank by one gather (N (d + 3) words)
-        DevBuf<double> &X = c->samp_xchg;
-        const i64 words = N * (d + 3);
-        X.ensure(words);
-        k_pack_landmarks(c, c->lemb.p, c->lweight.p, c->dii.p, c->lcomm.p, N, d, X.p, 0);
-        allreduce(c, X.p, words, 2);
-        k_pack_landmarks(c, c->lemb.p, c->lweight.p, c->dii.p, c->lcomm.p, N, d, X.p, 1);
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->phases.ms["aggregate"] = now_ms() - t0;
-    t0 = now_ms();
-    // per-edge scatter.  vect_C (C x C cluster pairs, from the original edges: every landmark lies in one
-    // community, so this equals the reference's sum over landmark edges, src/divergence.jl:59-63) is what the
-    // score needs; the N x N landmark-pair matrix (src/landmarks.jl:433-451) only feeds landmarks_fetch.
-    const i64 C = c->n_comm_max;
-    const i64 vlen = directed ? C * C : packed_len(C);
-    c->vectC.ensure(vlen);
-    scatter_vectC_resident(c, C, directed, c->vectC.p);
-    c->lm_directed = directed;
-    c->wedges_ready = false;
-    c->n_ledges = -1;
-    if (need_wedges) scatter_wedges(c, directed);
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->phases.ms["scatter"] = now_ms() - t0;
-    c->lm_ready = true;
-}
-
 int cge_landmarks_run(cge_ctx *c, const int64_t *cl_flat, const int64_t *cl_off, int64_t ncl, int64_t land,
                       int64_t forced, int method, int directed, int64_t *N_out, int64_t *n_ledges_out, int *truncated) {
     if (!c || !cl_flat || !cl_off) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    landmarks_run_impl(c, cl_flat, cl_off, ncl, land, forced, method, directed, true);
+    CGE_TRY_ON_DEVICE(c)
+    host_landmarks_run(c, LandmarkRun{cl_flat, cl_off, ncl, land, forced, method, directed, true});
     if (N_out) *N_out = c->N;
     if (n_ledges_out) *n_ledges_out = c->n_ledges;
     if (truncated) *truncated = c->lm_truncated;
@@ -594,86 +144,26 @@ int cge_landmarks_run(cge_ctx *c, const int64_t *cl_flat, const int64_t *cl_off,
 
 int cge_landmarks_info(cge_ctx *c, int64_t *N_out, int64_t *n_ledges_out, int *truncated) {
     if (!c) return CGE_E_ARG;
-    if (!c->lm_ready) {
-        c->err = "landmarks_info: run cge_landmarks_run first";
-        return CGE_E_ARG;
-    }
-    if (!c->wedges_ready) { // the score path skips the landmark-pair matrix; build it on first demand
-        try {
-            HIP_CHECK(hipSetDevice(c->device));
-            scatter_wedges(c, c->lm_directed);
-        } catch (const CgeError &e) {
-            c->err = e.msg;
-            return e.code;
-        }
-    }
+    CGE_TRY_ON_DEVICE(c)
+    host_landmarks_info(c);
     if (N_out) *N_out = c->N;
     if (n_ledges_out) *n_ledges_out = c->n_ledges;
     if (truncated) *truncated = c->lm_truncated;
-    return CGE_OK;
+    CGE_CATCH(c)
 }
 
 int cge_landmarks_fetch(cge_ctx *c, double *dii, double *embed, int64_t *cluster, int64_t *ledges, double *lw_e,
                         double *lweight, int64_t *v_to_l) {
     if (!c) return CGE_E_ARG;
-    CGE_TRY(c)
-    if (!c->lm_ready) CGE_THROW(CGE_E_ARG, "landmarks_fetch: run cge_landmarks_run first");
-    HIP_CHECK(hipSetDevice(c->device));
-    if (!c->wedges_ready) scatter_wedges(c, c->lm_directed);
-    if (ledges || lw_e) wedges_whole(c);
-    const i64 N = c->N, d = c->d, n = c->n;
-    hipStream_t st = c->stream;
-    if (dii) HIP_CHECK(hipMemcpyAsync(dii, c->dii.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    if (lweight) HIP_CHECK(hipMemcpyAsync(lweight, c->lweight.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    std::vector<double> rm;
-    std::vector<i32> lc;
-    if (embed) {
-        rm.resize((size_t)N * d);
-        HIP_CHECK(hipMemcpyAsync(rm.data(), c->lemb.p, sizeof(double) * N * d, hipMemcpyDeviceToHost, st));
-    }
-    if (cluster) {
-        lc.resize(N);
-        HIP_CHECK(hipMemcpyAsync(lc.data(), c->lcomm.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-    }
-    std::vector<double> we;
-    if (ledges || lw_e) {
-        we.resize((size_t)N * N);
-        HIP_CHECK(hipMemcpyAsync(we.data(), c->wedges.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (embed)
-        for (i64 l = 0; l < N; l++)
-            for (i64 k = 0; k < d; k++) embed[l + k * N] = rm[l * d + k]; // column-major out
-    if (cluster)
-        for (i64 l = 0; l < N; l++) cluster[l] = lc[l] + 1;
-    if (ledges || lw_e) { // rows in idx order / N*(i-1)+j order, w > 0 only (src/landmarks.jl:441-463)
-        const i64 ne = c->n_ledges;
-        i64 k = 0;
-        for (i64 a = 0; a < N; a++)
-            for (i64 b = c->lm_directed ? 0 : a; b < N; b++) {
-                const double wv = we[a * N + b];
-                if (wv > 0) {
-                    if (k >= ne) CGE_THROW(CGE_E_ASSERT, "landmark edge count changed between run and fetch");
-                    if (ledges) { ledges[k] = a + 1; ledges[k + ne] = b + 1; }
-                    if (lw_e) lw_e[k] = wv;
-                    k++;
-                }
-            }
-    }
-    if (v_to_l) { // 1-based landmark of every vertex (:379), from the device copy the score path works on
-        std::vector<i32> v0(n);
-        HIP_CHECK(hipMemcpyAsync(v0.data(), c->v2l.p, sizeof(i32) * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        for (i64 i = 0; i < n; i++) v_to_l[i] = (i64)v0[i] + 1;
-    }
+    CGE_TRY_ON_DEVICE(c)
+    host_landmarks_fetch(c, dii, embed, cluster, ledges, lw_e, lweight, v_to_l);
     CGE_CATCH(c)
 }
 
 int cge_runsplit(cge_ctx *c, const int64_t *cl_flat, const int64_t *cl_off, int64_t ncl, int64_t nland,
                  int64_t forced, int method, int64_t *group_ids) {
     if (!c || !group_ids) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     if (!c->Xr.p || !c->vw.p) CGE_THROW(CGE_E_ARG, "runsplit: embedding and vertex weights must be resident");
     std::vector<i64> gid;
     host_runsplit(c, cl_flat, cl_off, ncl, nland, forced, method, gid);
@@ -685,470 +175,36 @@ int cge_runsplit(cge_ctx *c, const int64_t *cl_flat, const int64_t *cl_off, int6
 int cge_draw_samples(cge_ctx *c, int64_t seed, int64_t stream_id, int64_t S, int directed, int64_t *pos_idx,
                      int64_t *neg_i, int64_t *neg_j) {
     if (!c || S <= 0 || !pos_idx || !neg_i || !neg_j) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     if (!c->src.p) CGE_THROW(CGE_E_ARG, "draw_samples: no resident graph");
     if (c->edges_sharded) CGE_THROW(CGE_E_ARG, "draw_samples: the resident edge list is sharded over the ranks (option shard_ingest); cge_score draws on the device");
     host_draw_samples(c, seed, stream_id, S, directed, pos_idx, neg_i, neg_j);
     CGE_CATCH(c)
 }
 
-// whether make_samples can be started ahead of the rest of a score: one seeded set, drawn on the device from a local edge list
-static bool samples_can_start_early(cge_ctx *c, i64 seed, bool exact_directed);
-// phase 0: everything; 1: enqueue the draws and the first rejection round, no synchronisation (samples_can_start_early only);
-// 2: the rest of a draw begun with phase 1
-static void make_samples(cge_ctx *c, i64 seed, i64 S, int directed, bool exact_directed, SampleSet &smp, int phase = 0) {
-    if (phase == 2) {
-        k_draw_samples_finish(c);
-        return;
-    }
-    // seeded: one set reused at every alpha (Random.seed! before each draw, src/divergence.jl:184,193);
-    // unseeded: a fresh set per alpha, keyed by an arbitrary fixed base seed and the alpha index
-    smp.S = S;
-    smp.n_sets = (seed != -1) ? 1 : AlphaBook::n_alpha;
-    const i64 base = (seed != -1) ? seed : 0x5eedc0de;
-    if (sampler_uses_device(c)) { // large resident graph: drawn, rejected and kept on the device (the same stream of draws)
-        smp.on_device = true;
-        smp.d_pos.ensure(smp.n_sets * S); smp.d_ni.ensure(smp.n_sets * S); smp.d_nj.ensure(smp.n_sets * S);
-        if (phase == 1) { // (one set, no second draw: samples_can_start_early)
-            k_draw_samples_begin(c, base, 0, S, directed, smp.d_pos.p, smp.d_ni.p, smp.d_nj.p);
-            return;
-        }
-        for (i64 t = 0; t < smp.n_sets; t++)
-            k_draw_samples_dev(c, base, t, S, directed, smp.d_pos.p + t * S, smp.d_ni.p + t * S, smp.d_nj.p + t * S);
-        if (exact_directed) { // the un-reseeded second positive draw of :510 (its non-edges are not used)
-            smp.d_pos2.ensure(smp.n_sets * S);
-            DevBuf<i32> di, dj;
-            di.ensure(S); dj.ensure(S);
-            for (i64 t = 0; t < smp.n_sets; t++)
-                k_draw_samples_dev(c, base + 0x7777, 1000 + t, S, directed, smp.d_pos2.p + t * S, di.p, dj.p);
-        }
-        return;
-    }
-    smp.pos_idx.resize(smp.n_sets * S);
-    smp.neg_i.resize(smp.n_sets * S);
-    smp.neg_j.resize(smp.n_sets * S);
-    for (i64 t = 0; t < smp.n_sets; t++)
-        host_draw_samples(c, base, t, S, directed, &smp.pos_idx[t * S], &smp.neg_i[t * S], &smp.neg_j[t * S]);
-    if (exact_directed) { // the un-reseeded second positive draw of :510
-        smp.pos_idx2.resize(smp.n_sets * S);
-        std::vector<i64> di(S), dj(S);
-        for (i64 t = 0; t < smp.n_sets; t++)
-            host_draw_samples(c, base + 0x7777, 1000 + t, S, directed, &smp.pos_idx2[t * S], di.data(), dj.data());
-    }
-}
-
-static bool samples_can_start_early(cge_ctx *c, i64 seed, bool exact_directed) {
-    return seed != -1 && !exact_directed && sampler_uses_device(c) && !c->edges_sharded;
-}
-
-// landmark -> members CSR (ascending vertex id) from a 0-based assignment
-static void build_landmark_index(cge_ctx *c, const std::vector<i32> &v2l0, i64 N) {
-    const i64 n = (i64)v2l0.size();
-    if (c->rows_sharded) { // this rank's members (local row ids, ascending) + the global sizes; the index goes to the device
-        const i64 nl = c->n_loc;
-        c->h_gl_off.assign(N + 1, 0);
-        c->h_mem_off.assign(N + 1, 0);
-        c->h_mem.resize(nl);
-        for (i64 i = 0; i < n; i++) c->h_gl_off[v2l0[i] + 1]++;
-        for (i64 i = 0; i < nl; i++) c->h_mem_off[v2l0[c->h_loc2glob[i]] + 1]++;
-        for (i64 l = 0; l < N; l++) { c->h_gl_off[l + 1] += c->h_gl_off[l]; c->h_mem_off[l + 1] += c->h_mem_off[l]; }
-        std::vector<i32> cur(c->h_mem_off.begin(), c->h_mem_off.end() - 1);
-        for (i64 i = 0; i < nl; i++) c->h_mem[cur[v2l0[c->h_loc2glob[i]]]++] = (i32)i;
-        c->lm_memoff.ensure(N + 1);
-        c->lm_mem.ensure(nl);
-        HIP_CHECK(hipMemcpyAsync(c->lm_memoff.p, c->h_mem_off.data(), sizeof(i32) * (N + 1), hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipMemcpyAsync(c->lm_mem.p, c->h_mem.data(), sizeof(i32) * nl, hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->lm_index_on_device = true;
-        return;
-    }
-    c->lm_index_on_device = false;
-    c->h_mem_off.assign(N + 1, 0);
-    c->h_mem.resize(n);
-    for (i64 i = 0; i < n; i++) c->h_mem_off[v2l0[i] + 1]++;
-    for (i64 l = 0; l < N; l++) c->h_mem_off[l + 1] += c->h_mem_off[l];
-    std::vector<i32> cur(c->h_mem_off.begin(), c->h_mem_off.end() - 1);
-    for (i64 i = 0; i < n; i++) c->h_mem[cur[v2l0[i]]++] = (i32)i;
-}
-
 int cge_max_pair_dist(cge_ctx *c, int part, int nparts, double *hi, int64_t *arg_i, int64_t *arg_j) {
     if (!c || !hi || nparts < 1 || part < 0 || part >= nparts) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     *hi = host_diameter_brute(c, part, nparts, arg_i, arg_j);
     CGE_CATCH(c)
 }
 
 // ---- wGCL -------------------------------------------------------------------------------------------
-static void upload_i64_as_i32(cge_ctx *c, const i64 *h, i64 cnt, i64 lo, i64 hi, DevBuf<i32> &out, const char *what) {
-    std::vector<i32> t(cnt);
-    for (i64 i = 0; i < cnt; i++) {
-        if (h[i] < lo || h[i] > hi) CGE_THROW(CGE_E_ARG, "%s: id %lld outside %lld..%lld", what, (long long)h[i], (long long)lo, (long long)hi);
-        t[i] = (i32)(h[i] - 1);
-    }
-    out.ensure(cnt);
-    HIP_CHECK(hipMemcpyAsync(out.p, t.data(), sizeof(i32) * cnt, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-}
-
-// star-graph guard of wGCL_directed (src/divergence.jl:321-334): the star counts of the degree pass are read back; a star graph
-// gets the reference's 6-element return (true)
-static bool star_return(cge_ctx *c, const i32 *d_star, i64 N, double out[7], int *out_len) {
-    std::vector<i32> star(N);
-    HIP_CHECK(hipMemcpyAsync(star.data(), d_star, sizeof(i32) * N, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    bool has_nm1 = false, has_2nm1 = false;
-    i64 sum = 0, cnt2 = 0;
-    for (i64 i = 0; i < N; i++) {
-        if (star[i] == N - 1) has_nm1 = true;
-        if (star[i] == 2 * (N - 1)) has_2nm1 = true;
-        sum += star[i];
-        if (star[i] == 2) cnt2++;
-    }
-    if (!((has_nm1 && sum == 2 * (N - 1)) || (has_2nm1 && cnt2 == N - 1))) return false;
-    out[0] = -1.0;
-    for (int k = 1; k < 6; k++) out[k] = 0.0;
-    *out_len = 6;
-    return true;
-}
-
-// the exact mode's directed degree pass: in- / out-degrees (c->s_degin / s_degout) and star counts from the score graph's edges
-static void edge_degrees(cge_ctx *c, const i32 *src, const i32 *dst, const double *w, i64 m, i64 N, DevBuf<i32> &star) {
-    hipStream_t st = c->stream;
-    c->s_degin.ensure(N);
-    c->s_degout.ensure(N);
-    star.ensure(N);
-    HIP_CHECK(hipMemsetAsync(c->s_degin.p, 0, sizeof(double) * N, st));
-    HIP_CHECK(hipMemsetAsync(c->s_degout.p, 0, sizeof(double) * N, st));
-    HIP_CHECK(hipMemsetAsync(star.p, 0, sizeof(i32) * N, st));
-    k_edge_degrees(c, src, dst, w, m, c->s_degout.p, c->s_degin.p, star.p);
-}
-
-// what a landmark-mode sweep reads of the original graph: the resident one, with `lweight` as the landmarks' weights
-static OrigView resident_orig_view(cge_ctx *c, const double *lweight) {
-    OrigView ov;
-    ov.n = c->n; ov.m = c->m; ov.Xr = c->Xr.p; ov.vw = c->vw.p; ov.v2l = c->v2l.p; ov.lweight = lweight;
-    ov.src = c->src.p; ov.dst = c->dst.p; ov.h_w = c->h_w.empty() ? nullptr : c->h_w.data();
-    return ov;
-}
-
 int cge_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cge_trace *trace) {
     if (!c || !a || !out || !out_len) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int directed = a->directed;
-    // the score graph of this entry point (and the init_* graph it may upload) is held whole on every rank
-    struct KeepOption { int &ref; int val; ~KeepOption() { ref = val; } } keep_ingest{c->opt_shard_ingest, c->opt_shard_ingest};
-    c->opt_shard_ingest = 0;
-    if (!a->edges_src || !a->edges_dst || a->m <= 0) CGE_THROW(CGE_E_ARG, "wGCL: empty edge list");
-    i64 N = 0;
-    for (i64 e = 0; e < a->m; e++) N = std::max(N, std::max(a->edges_src[e], a->edges_dst[e])); // maximum(edges) :41
-    const bool landmarks = a->n_v_to_l > 0;                                                      // :44
-    if (a->n_comm != N) CGE_THROW(CGE_E_ASSERT, "AssertionError: No. communities not matching no. vertices"); // :50
-    if (a->n_distances != N) CGE_THROW(CGE_E_ASSERT, "AssertionError: Distances vector length is not equal to no. vertices"); // :81
-    if (a->embed_rows < N) CGE_THROW(CGE_E_ARG, "wGCL: embedding has fewer rows than vertices");
-    i64 C = 0;
-    for (i64 i = 0; i < N; i++) C = std::max(C, a->comm[i]);
-    const i64 d = a->d;
-
-    // score graph -> device scratch
-    DevBuf<i32> g_src, g_dst;
-    DevBuf<double> g_w, colbuf;
-    upload_i64_as_i32(c, a->edges_src, a->m, 1, N, g_src, "edges");
-    upload_i64_as_i32(c, a->edges_dst, a->m, 1, N, g_dst, "edges");
-    g_w.ensure(a->m);
-    HIP_CHECK(hipMemcpyAsync(g_w.p, a->eweights, sizeof(double) * a->m, hipMemcpyHostToDevice, st));
-    upload_i64_as_i32(c, a->comm, N, 1, C, c->s_comm, "comm");
-    colbuf.ensure((size_t)a->embed_rows * d);
-    HIP_CHECK(hipMemcpyAsync(colbuf.p, a->embed, sizeof(double) * a->embed_rows * d, hipMemcpyHostToDevice, st));
-    c->s_emb.ensure((size_t)a->embed_rows * d);
-    k_transpose_to_rowmajor(c, colbuf.p, c->s_emb.p, a->embed_rows, d);
-    c->s_dist.ensure(N);
-    c->s_vw.ensure(N);
-    HIP_CHECK(hipMemcpyAsync(c->s_dist.p, a->distances, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->s_vw.p, a->vweights, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    const i64 vlen = directed ? C * C : packed_len(C);
-    c->s_vectC.ensure(vlen);
-    HIP_CHECK(hipMemsetAsync(c->s_vectC.p, 0, sizeof(double) * vlen, st));
-    k_edge_scatter(c, g_src.p, g_dst.p, g_w.p, 0, a->m, nullptr, c->s_comm.p, N, C, directed, nullptr, c->s_vectC.p);
-    ScoreGraph G;
-    G.N = N; G.d = d; G.C = C;
-    G.emb = c->s_emb.p; G.dist = c->s_dist.p; G.vw = c->s_vw.p; G.comm = c->s_comm.p; G.vectC = c->s_vectC.p;
-    if (directed) {
-        DevBuf<i32> star;
-        edge_degrees(c, g_src.p, g_dst.p, g_w.p, a->m, N, star);
-        if (star_return(c, star.p, N, out, out_len)) return CGE_OK;
-        G.deg_in = c->s_degin.p;
-        G.deg_out = c->s_degout.p;
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-
-    // the graph the local score samples from: the original graph in landmark mode, else the score graph
-    OrigView ov;
-    if (landmarks) {
-        const bool have_init = a->init_embed && a->init_edges_src && a->init_edges_dst && a->init_vweights;
-        if (have_init) { // (re)load the original graph as the resident one
-            const i64 n0 = a->n_init;
-            if (a->n_v_to_l != n0) CGE_THROW(CGE_E_ARG, "wGCL: v_to_l and init_vweights differ in length");
-            int rc = cge_set_graph(c, a->init_edges_src, a->init_edges_dst, a->init_eweights, a->m_init, n0);
-            if (rc) throw CgeError{rc, c->err};
-            rc = cge_set_embedding(c, a->init_embed, n0, d);
-            if (rc) throw CgeError{rc, c->err};
-            rc = cge_set_vertex_data(c, nullptr, a->init_vweights, n0);
-            if (rc) throw CgeError{rc, c->err};
-        } else if (!c->Xr.p || !c->src.p || !c->vw.p || c->n != a->n_v_to_l)
-            CGE_THROW(CGE_E_ARG, "wGCL: landmark mode needs init_* arrays or matching resident inputs");
-        upload_i64_as_i32(c, a->v_to_l, a->n_v_to_l, 1, N, c->v2l, "v_to_l");
-        {
-            std::vector<i32> v2l0(a->n_v_to_l);
-            for (i64 i = 0; i < a->n_v_to_l; i++) v2l0[i] = (i32)(a->v_to_l[i] - 1);
-            build_landmark_index(c, v2l0, N);
-        }
-        ov = resident_orig_view(c, c->s_vw.p);
-        std::vector<i32> lcomm0(N);
-        for (i64 i = 0; i < N; i++) lcomm0[i] = (i32)(a->comm[i] - 1);
-        ov.hi = host_diameter_landmarks(c, c->s_emb.p, c->s_vw.p, lcomm0, C, N);
-    } else {
-        // exact mode: make the score graph the resident graph so the sampler can reject its edges
-        int rc = cge_set_graph(c, a->edges_src, a->edges_dst, a->eweights, a->m, N);
-        if (rc) throw CgeError{rc, c->err};
-    }
-    SampleSet smp;
-    if (a->pos_idx && a->neg_i && a->neg_j && a->n_sample_sets > 0) {
-        if (c->edges_sharded) CGE_THROW(CGE_E_ARG, "wGCL: caller-drawn samples index the whole edge list, the resident one is sharded (option shard_ingest)");
-        smp.S = a->auc_samples;
-        smp.n_sets = a->n_sample_sets;
-        const i64 tot = smp.S * smp.n_sets;
-        smp.pos_idx.assign(a->pos_idx, a->pos_idx + tot);
-        smp.neg_i.assign(a->neg_i, a->neg_i + tot);
-        smp.neg_j.assign(a->neg_j, a->neg_j + tot);
-        if (a->pos_idx2) smp.pos_idx2.assign(a->pos_idx2, a->pos_idx2 + tot);
-    } else
-        make_samples(c, a->seed, a->auc_samples, directed, directed && !landmarks, smp);
-    host_wgcl_sweep(c, G, landmarks ? &ov : nullptr, c->src.p, c->dst.p, c->h_w.empty() ? nullptr : c->h_w.data(), c->m, directed, a->split, smp,
-                    out, out_len, trace);
-    flush_timers(c);
+    CGE_TRY_ON_DEVICE(c)
+    host_wgcl(c, a, out, out_len, trace);
     CGE_CATCH(c)
 }
 
-
-// cge_score's work on the resident inputs.  `defer` (cge_score_batch): a sweep on the fused path is prepared and handed over
-// instead of run (host_wgcl_sweep); `reuse_samples`: the local score's samples of this graph and seed are already in c->smp.
-static void score_one(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, cge_trace *trace, SweepHandoff *defer,
-                      bool reuse_samples) {
-    hipStream_t st = c->stream;
-    check_resident(c, "score");
-    c->phases.ms.clear();
-    const int directed = a->directed;
-    const i64 d = c->d;
-    ScoreGraph G;
-    OrigView ov;
-    std::vector<i32> lcomm_host;
-    const bool landmarks = a->land != -1;
-    // The local score's samples depend on the resident graph and the seed only: their draw and the first round of the rejection are
-    // enqueued early -- behind the first synchronisation of the landmark phase, whose host-side set-up then leaves the device idle
-    // for a few hundred microseconds; the verdict is looked at where the samples used to be drawn
-    const bool samples_early = landmarks && !reuse_samples && samples_can_start_early(c, a->seed, false);
-    // Whatever happens, neither the hook (it captures this call's arguments) nor its draw outlives the call: a star graph's early
-    // return or an error in between leaves the draw pending, and it is drained here (a score that got through has looked at its
-    // draw: no synchronisation then)
-    struct HookGuard {
-        cge_ctx *c;
-        ~HookGuard() {
-            c->after_unique = nullptr;
-            if (c->samp_pending.on) {
-                (void)hipStreamSynchronize(c->stream);
-                c->samp_pending.on = false;
-            }
-        }
-    } hook_guard{c};
-    c->after_unique = nullptr;
-    if (samples_early)
-        c->after_unique = [c, a, directed]() {
-            c->smp.reset();
-            make_samples(c, a->seed, a->auc_samples, directed, false, c->smp, 1);
-        };
-    DevBuf<double> &zeros = c->sw_zeros;
-    double t0;
-    DevBuf<i32> &star = c->s_star;
-    if (landmarks) {
-        landmarks_run_impl(c, a->clusters_flat, a->clusters_off, a->n_clusters, a->land, a->forced, a->method, directed,
-                           directed != 0 || c->opt_landmark_edges != 0);
-        c->after_unique = nullptr;
-        const i64 N = c->N, C = c->n_comm_max;
-        // wGCL's own `maximum(edges)` / size asserts (src/divergence.jl:41,50): the highest-numbered
-        // landmark must carry an edge -- always true when every vertex has positive weight
-        G.N = N; G.d = d; G.C = C;
-        G.emb = c->lemb.p; G.dist = c->dii.p; G.vw = c->lweight.p; G.comm = c->lcomm.p; G.vectC = c->vectC.p;
-        if (directed) { // degrees / star counts of the landmark graph from the landmark-pair matrix
-            c->s_degin.ensure(N);
-            c->s_degout.ensure(N);
-            star.ensure(N);
-            if (c->wedges_block_only) { // a reduce-scattered matrix: this rank's row block, then the ranks add the three vectors
-                const i64 per = wedge_rows_per_rank(c, N), r0 = std::min<i64>(N, per * c->coll.rank), r1 = std::min<i64>(N, r0 + per);
-                DevBuf<double> &X = c->samp_xchg;
-                X.ensure(3 * N);
-                k_wedge_degrees_block(c, c->wedges.p, N, r0, r1, X.p);
-                allreduce(c, X.p, 3 * N, 0);
-                k_degrees_unpack(c, X.p, N, c->s_degout.p, c->s_degin.p, star.p);
-            } else
-                k_wedge_degrees(c, c->wedges.p, N, c->s_degout.p, c->s_degin.p, star.p);
-            if (star_return(c, star.p, N, out, out_len)) return;
-            G.deg_in = c->s_degin.p;
-            G.deg_out = c->s_degout.p;
-        }
-        t0 = now_ms();
-        ov = resident_orig_view(c, c->lweight.p);
-        lcomm_host.resize(N); // community of a landmark = community of any member (landmarks never span two): :427
-        HIP_CHECK(hipMemcpyAsync(lcomm_host.data(), c->lcomm.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        ov.hi = host_diameter_landmarks(c, c->lemb.p, c->lweight.p, lcomm_host, C, N);
-        ov.h_lcomm = lcomm_host.data(); // (the sweep groups the landmarks by community: no second read-back)
-        c->phases.ms["diameter"] = now_ms() - t0; // what the main thread still waited for
-    } else {
-        if (c->edges_sharded)
-            CGE_THROW(CGE_E_ARG, "score: exact mode reads the whole edge list on every rank; the resident one is sharded (option shard_ingest)");
-        if (c->rows_sharded)
-            CGE_THROW(CGE_E_ARG, "score: exact mode reads every embedding row on every rank; the resident rows are sharded (option shard_rows)");
-        const i64 N = c->n, C = c->n_comm_max;
-        zeros.ensure(N);
-        HIP_CHECK(hipMemsetAsync(zeros.p, 0, sizeof(double) * N, st)); // distances = zeros (CGE_CLI.jl:4)
-        const i64 vlen = directed ? C * C : packed_len(C);
-        c->vectC.ensure(vlen);
-        scatter_vectC_resident(c, C, directed, c->vectC.p);
-        G.N = N; G.d = d; G.C = C;
-        G.emb = c->Xr.p; G.dist = zeros.p; G.vw = c->vw.p; G.comm = c->comm.p; G.vectC = c->vectC.p;
-        if (directed) {
-            edge_degrees(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, c->m, N, star);
-            if (star_return(c, star.p, N, out, out_len)) return;
-            G.deg_in = c->s_degin.p;
-            G.deg_out = c->s_degout.p;
-        }
-    }
-    t0 = now_ms();
-    SampleSet &smp = c->smp;
-    if (reuse_samples) { // (cge_score_batch: drawn for the first member; they depend on the graph and the seed only)
-    } else if (samples_early && c->samp_pending.on) make_samples(c, a->seed, a->auc_samples, directed, false, smp, 2);
-    else {
-        smp.reset();
-        make_samples(c, a->seed, a->auc_samples, directed, directed && !landmarks, smp);
-    }
-    c->phases.ms["samples"] = now_ms() - t0;
-    t0 = now_ms();
-    host_wgcl_sweep(c, G, landmarks ? &ov : nullptr, c->src.p, c->dst.p, c->h_w.empty() ? nullptr : c->h_w.data(), c->m, directed, a->split, smp,
-                    out, out_len, trace, defer);
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->phases.ms[defer && defer->deferred ? "sweep_setup" : "sweep"] = now_ms() - t0;
-    flush_timers(c);
-}
 int cge_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, cge_trace *trace) {
     if (!c || !a || !out || !out_len) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    score_one(c, a, out, out_len, trace, nullptr, false);
+    CGE_TRY_ON_DEVICE(c)
+    host_score(c, a, out, out_len, trace, nullptr, false);
     CGE_CATCH(c)
 }
 
-// ---- cge_score_batch: K embeddings of the resident graph ("Scoring several embeddings") ----------------------------
-// A member is a cge_embedding_view (cge_score_batch describes its fp64 matrices as views); `who` names the entry point in messages.
-static void upload_member(cge_ctx *c, const char *who, const cge_embedding_view *views, i64 k) {
-    const int rc = cge_set_embedding_view(c, views + k, c->n); // a status of the boundary; the message is in c->err
-    if (rc != CGE_OK) CGE_THROW(rc, "%s: embedding %lld: %s", who, (long long)k, std::string(c->err).c_str());
-}
-static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
-                             int *out_len, cge_trace *traces) {
-    if (!c->src.p || !c->vw.p || !c->comm.p || c->n <= 0 || c->m <= 0)
-        CGE_THROW(CGE_E_ARG, "%s: graph and vertex data must be resident (cge_set_graph / cge_set_vertex_data)", who);
-    if (c->has_coll || c->rccl_comm || c->edges_sharded || c->rows_sharded || c->opt_shard_ingest || c->opt_shard_rows)
-        CGE_THROW(CGE_E_ARG, "%s: not under collectives or sharding (one embedding per rank is the multi-GPU form)", who);
-    for (i64 k = 0; k < K; k++) { // the members, before any work
-        std::string msg;
-        if (view_check(views + k, c->n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s: embedding %lld: %s", who, (long long)k, msg.c_str());
-        if (views[k].on_device) check_device_pointer(c, (std::string(who) + ": embedding " + std::to_string(k)).c_str(), views[k].data);
-    }
-    int dev = 0, cus = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    // the members that can take the batched sweep (undirected landmark mode, the fused fit); the sweep decides the rest
-    // (one member, or a member whose fit takes more than half the chip, shares nothing: it is scored as cge_score scores it)
-    const bool batchable = K >= 2 && a->land != -1 && !a->directed && c->opt_fit_fused && c->opt_fit_persistent != 1;
-    c->stat_fit_batched_launches = c->stat_fit_batched_alphas = 0;
-    c->smp.reset();
-    bool have_samples = false;
-    std::vector<std::unique_ptr<BatchMember>> group;
-    std::vector<i64> redo, group_k;
-    int g_sum = 0, g_nw = 0;
-    double batch_ms = 0.0;
-    auto run_group = [&]() {
-        if (group.empty()) return;
-        std::vector<BatchMember *> g;
-        for (auto &m : group) g.push_back(m.get());
-        const double t0 = now_ms();
-        host_batch_sweep(c, g);
-        batch_ms += now_ms() - t0;
-        for (size_t i = 0; i < group.size(); i++)
-            if (group[i]->redo) redo.push_back(group_k[i]);
-        group.clear(); group_k.clear();
-        g_sum = 0;
-    };
-    for (i64 k = 0; k < K; k++) {
-        upload_member(c, who, views, k);
-        std::unique_ptr<BatchMember> m(new BatchMember());
-        m->h.max_G = cus / 2;
-        m->out = out + 7 * k; m->out_len = out_len + k; m->trace = traces ? traces + k : nullptr;
-        score_one(c, a, m->out, m->out_len, m->trace, batchable ? &m->h : nullptr, have_samples);
-        have_samples = have_samples || c->smp.n_sets > 0;
-        if (!m->h.deferred) continue; // (scored: the sequential path)
-        if (batch_group_closes(g_sum, g_nw, (int)group.size(), m->h.G, m->h.NW, cus)) run_group();
-        g_sum += m->h.G;
-        g_nw = m->h.NW;
-        group.push_back(std::move(m));
-        group_k.push_back(k);
-    }
-    run_group();
-    flush_timers(c);
-    // members whose batched fit was abandoned: cge_score's own path (which falls back to one launch per iteration as it must)
-    std::sort(redo.begin(), redo.end());
-    for (i64 k : redo) {
-        upload_member(c, who, views, k);
-        score_one(c, a, out + 7 * k, out_len + k, traces ? traces + k : nullptr, nullptr, true);
-    }
-    if (!redo.empty() && redo.back() != K - 1) { // the resident embedding and landmark state are the last member's
-        upload_member(c, who, views, K - 1);
-        landmarks_run_impl(c, a->clusters_flat, a->clusters_off, a->n_clusters, a->land, a->forced, a->method, a->directed,
-                           a->directed != 0 || c->opt_landmark_edges != 0);
-    }
-    c->phases.ms["batch_sweep"] = batch_ms; // the launch groups' sweeps, all members (the other phases: the last member's)
-}
-// the boundary of both batch entry points: every exit leaves the context usable, an error leaves every out_len at 0
-static int score_batch_run(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
-                           int *out_len, cge_trace *traces) {
-    for (i64 k = 0; k < K; k++) out_len[k] = 0;
-    int rc;
-    try {
-        HIP_CHECK(hipSetDevice(c->device));
-        score_batch_impl(c, a, views, K, who, out, out_len, traces);
-        rc = CGE_OK;
-    } catch (const CgeError &e) {
-        c->err = e.msg;
-        rc = e.code;
-    } catch (const std::bad_alloc &) {
-        c->err = "host allocation failed";
-        rc = CGE_E_OOM;
-    } catch (const std::exception &e) {
-        c->err = e.what();
-        rc = CGE_E_ARG;
-    }
-    // on every exit: no hand-off slot taken for armed (score_one leaves no hook and no pending sample draw behind)
-    c->flow_armed_words = 0;
-    if (rc != CGE_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        for (i64 k = 0; k < K; k++) out_len[k] = 0;
-    }
-    return rc;
-}
+// cge_score_batch: K embeddings of the resident graph (batch_host.cpp); a member is a cge_embedding_view
 int cge_score_batch(cge_ctx *c, const cge_score_args *a, const cge_embedding_batch *b, double *out, int *out_len,
                     cge_trace *traces) {
     if (!c || !a || !b || !out || !out_len || !b->embeddings || b->K < 1 || b->d <= 0 || (b->row_major && !b->on_device))
@@ -1172,63 +228,23 @@ int64_t cge_idx(int64_t n, int64_t i, int64_t j) { return n * (i - 1) - (i - 1) 
 
 int cge_js(cge_ctx *c, const double *vC, const double *vB, int64_t len, const uint8_t *vI, int internal, double *out) {
     if (!c || !vC || !vB || !out || len <= 0) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    // vI (when given) selects bins; the device kernel derives the diagonal mask from the packed/square
-    // layout, so here the selected bins are compacted on the host first and scored with mode 0.
-    std::vector<double> p, q;
-    for (i64 k = 0; k < len; k++)
-        if (!vI || ((vI[k] != 0) == (internal != 0))) { p.push_back(vC[k]); q.push_back(vB[k]); }
-    const i64 L = (i64)p.size();
-    DevBuf<double> dp, dq, r;
-    dp.ensure(L); dq.ensure(L); r.ensure(1);
-    HIP_CHECK(hipMemcpyAsync(dp.p, p.data(), sizeof(double) * L, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(dq.p, q.data(), sizeof(double) * L, hipMemcpyHostToDevice, c->stream));
-    k_js(c, dp.p, dq.p, L, 1, 0, 0, r.p);
-    HIP_CHECK(hipMemcpyAsync(out, r.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
+    CGE_TRY_ON_DEVICE(c)
+    host_js(c, vC, vB, len, vI, internal, out);
     CGE_CATCH(c)
 }
 
 int cge_edge_scatter(cge_ctx *c, const int64_t *v_to_l, int64_t N, int64_t C, int directed, int64_t e0, int64_t e1,
                      double *wedges_out, double *vect_C_out) {
     if (!c || N <= 0 || C <= 0 || e0 < 0 || e1 < e0) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
-    if (!c->src.p || !c->comm.p) CGE_THROW(CGE_E_ARG, "edge_scatter: graph and vertex data must be resident");
-    if (c->edges_sharded) CGE_THROW(CGE_E_ARG, "edge_scatter: the resident edge list is sharded over the ranks (option shard_ingest)");
-    if (e1 > c->m) CGE_THROW(CGE_E_ARG, "edge_scatter: edge range beyond m");
-    hipStream_t st = c->stream;
-    DevBuf<i32> dv;
-    if (v_to_l) upload_i64_as_i32(c, v_to_l, c->n, 1, N, dv, "v_to_l");
-    const i64 vlen = directed ? C * C : packed_len(C);
-    DevBuf<double> dw, dc;
-    if (wedges_out) {
-        if (!v_to_l) CGE_THROW(CGE_E_ARG, "edge_scatter: wedges need v_to_l");
-        dw.ensure((size_t)N * N);
-        HIP_CHECK(hipMemsetAsync(dw.p, 0, sizeof(double) * N * N, st));
-    }
-    if (vect_C_out) {
-        dc.ensure(vlen);
-        HIP_CHECK(hipMemsetAsync(dc.p, 0, sizeof(double) * vlen, st));
-    }
-    if (!wedges_out && vect_C_out && e0 == 0 && e1 == c->m && C == c->n_comm_max && !c->has_coll)
-        scatter_vectC_resident(c, C, directed, dc.p); // the score path's forms of the whole-list pass
-    else
-        k_edge_scatter(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, e0, e1, v_to_l ? dv.p : nullptr,
-                       c->comm.p, N, C, directed, wedges_out ? dw.p : nullptr, vect_C_out ? dc.p : nullptr);
-    if (wedges_out) HIP_CHECK(hipMemcpyAsync(wedges_out, dw.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
-    if (vect_C_out) HIP_CHECK(hipMemcpyAsync(vect_C_out, dc.p, sizeof(double) * vlen, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    flush_timers(c);
+    CGE_TRY_ON_DEVICE(c)
+    host_edge_scatter(c, v_to_l, N, C, directed, e0, e1, wedges_out, vect_C_out);
     CGE_CATCH(c)
 }
 
 // ---- louvain_clust (src/clustering.jl:14-68): level-1 communities of the resident graph -------------------------------
 int cge_louvain(cge_ctx *c, int64_t *comm_out, int64_t *n_comm, double *modularity, int64_t *rounds) {
     if (!c || !comm_out) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     if (!c->src.p || c->m <= 0 || c->n <= 0) CGE_THROW(CGE_E_ARG, "louvain: no resident graph (cge_set_graph)");
     if (c->edges_sharded) CGE_THROW(CGE_E_ARG, "louvain: the resident edge list is sharded over the ranks (option shard_ingest)");
     k_louvain_level1(c, comm_out, n_comm, modularity, rounds);
@@ -1238,89 +254,58 @@ int cge_louvain(cge_ctx *c, int64_t *comm_out, int64_t *n_comm, double *modulari
 // ---- options / statistics ---------------------------------------------------------------------------
 int cge_set_option(cge_ctx *c, const char *key, int64_t value) {
     if (!c || !key) return CGE_E_ARG;
-    if (!strcmp(key, "diameter")) { // 0 auto, 1 brute force, 2 pruned only
-        if (value < 0 || value > 2) return CGE_E_ARG;
-        c->opt_diameter = (int)value;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "diameter_f32")) { // point-to-reference maxima of the pruned diameter: 2 (default) bf16 matrix pipe on two-term operands
-        if (value < 0 || value > 2) return CGE_E_ARG; // (K <= 128, else as 1), 1 fp32-input MFMA (both: rigorous upper bounds); 0: fp64 MFMA
-        c->opt_diameter_f32 = (int)value;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "fit_persistent")) { // 0 auto, 1 never, 2 whenever the score graph fits the register file
-        if (value < 0 || value > 2) return CGE_E_ARG;
-        c->opt_fit_persistent = (int)value;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "pow_exp2")) { // 1 (default): (1 - D)^alpha from log2(1 - D) kept per score; 0: the library pow per alpha
-        c->opt_pow_exp2 = value != 0;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "shard_runsplit")) { // N > 1 only: 0 = runsplit replicated, 1 (default) = forced phase and big batches of the
-        if (value < 0 || value > 2) return CGE_E_ARG; // global phase split over the ranks, 2 = every batch (tests)
-        c->opt_shard_forced = (int)value;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "shard_samples")) { // N > 1: 0 = tallies replicated, 1 (default) = split from 10^5 samples on with the in-library communicator, 2 = always
-        if (value < 0 || value > 2) return CGE_E_ARG;
-        c->opt_shard_samples = (int)value;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "exact_relabel")) { // exact mode beyond 8192 vertices: 1 (default) = score graph relabelled by community, 0 = as given (A/B, tests)
-        c->opt_exact_relabel = value != 0;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "bvec_blocks")) { // 1: sweeps from 256 vertices on relabel the score graph by community and sum vect_B by tiles
-        c->opt_bvec_blocks = value != 0; // (measured slower); 0 (default): row bins + row sums + fold
-        return CGE_OK;
-    }
-    if (!strcmp(key, "wedges_reduce_scatter")) { // N > 1: 1 = the N x N landmark-pair matrix is reduce-scattered by row blocks (a fetch of
-        c->opt_wedges_rs = value != 0;            // the landmark edge list is then collective); 0 (default): all-reduced, every consumer local
-        return CGE_OK;
-    }
-    if (!strcmp(key, "fit_fused")) { // 1 (default): in landmark mode the power matrix, vect_B's tile sums and the local score's tallies ride
-        c->opt_fit_fused = value != 0; // on the launch of the undirected persistent fit; 0: separate launches (A/B, cross-check)
-        return CGE_OK;
-    }
-    if (!strcmp(key, "shard_ingest")) { // N > 1: 1 = cge_set_graph keeps this rank's slice of the edge list only and cge_set_embedding uploads a
-        // slice of rows per rank and all-gathers them over xGMI (set the collectives first); 0 (default): every rank uploads and keeps everything
-        c->opt_shard_ingest = value != 0;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "shard_rows")) { // N > 1: 1 = cge_set_embedding / cge_set_embedding_device keep the rows of this rank's communities only
-        // (sharded BY COMMUNITY; set the collectives and upload the communities first); 0 (default): every rank holds every row
-        c->opt_shard_rows = value != 0;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "landmark_edges")) { // 1: cge_score also builds the landmark-pair matrix / edge count that landmarks() returns
-        c->opt_landmark_edges = value != 0; // (src/landmarks.jl:433-463; the undirected score itself does not read it); 0 (default): on first fetch
-        return CGE_OK;
-    }
-    if (!strcmp(key, "fit_max_iterations")) { // iterations after which a Chung-Lu fit that has not converged raises CGE_E_ASSERT (default 2 000 000)
-        if (value < 1) return CGE_E_ARG;
-        c->opt_fit_max_iters = value;
-        return CGE_OK;
-    }
+    const auto is = [&](const char *k) { return !strcmp(key, k); };
+    const auto ranged = [&](auto &field, int64_t lo, int64_t hi) { // lo <= value <= hi, else refused
+        if (value < lo || value > hi) return (int)CGE_E_ARG;
+        field = (std::remove_reference_t<decltype(field)>)value;
+        return (int)CGE_OK;
+    };
+    const auto flag = [&](auto &field) { field = value != 0; return (int)CGE_OK; };
+    if (is("diameter")) return ranged(c->opt_diameter, 0, 2); // 0 auto, 1 brute force, 2 pruned only
+    // point-to-reference maxima of the pruned diameter: 2 (default) bf16 matrix pipe on two-term operands (K <= 128, else as 1),
+    // 1 fp32-input MFMA (both: rigorous upper bounds); 0: fp64 MFMA
+    if (is("diameter_f32")) return ranged(c->opt_diameter_f32, 0, 2);
+    if (is("fit_persistent")) return ranged(c->opt_fit_persistent, 0, 2); // 0 auto, 1 never, 2 whenever the score graph fits the register file
+    if (is("pow_exp2")) return flag(c->opt_pow_exp2); // 1 (default): (1 - D)^alpha from log2(1 - D) kept per score; 0: the library pow per alpha
+    // N > 1 only: 0 = runsplit replicated, 1 (default) = forced phase and big batches of the global phase split over the ranks,
+    // 2 = every batch (tests)
+    if (is("shard_runsplit")) return ranged(c->opt_shard_forced, 0, 2);
+    // N > 1: 0 = tallies replicated, 1 (default) = split from 10^5 samples on with the in-library communicator, 2 = always
+    if (is("shard_samples")) return ranged(c->opt_shard_samples, 0, 2);
+    // exact mode beyond 8192 vertices: 1 (default) = score graph relabelled by community, 0 = as given (A/B, tests)
+    if (is("exact_relabel")) return flag(c->opt_exact_relabel);
+    // 1: sweeps from 256 vertices on relabel the score graph by community and sum vect_B by tiles (measured slower); 0 (default):
+    // row bins + row sums + fold
+    if (is("bvec_blocks")) return flag(c->opt_bvec_blocks);
+    // N > 1: 1 = the N x N landmark-pair matrix is reduce-scattered by row blocks (a fetch of the landmark edge list is then
+    // collective); 0 (default): all-reduced, every consumer local
+    if (is("wedges_reduce_scatter")) return flag(c->opt_wedges_rs);
+    // 1 (default): in landmark mode the power matrix, vect_B's tile sums and the local score's tallies ride on the launch of the
+    // undirected persistent fit; 0: separate launches (A/B, cross-check)
+    if (is("fit_fused")) return flag(c->opt_fit_fused);
+    // N > 1: 1 = cge_set_graph keeps this rank's slice of the edge list only and cge_set_embedding uploads a slice of rows per rank
+    // and all-gathers them over xGMI (set the collectives first); 0 (default): every rank uploads and keeps everything
+    if (is("shard_ingest")) return flag(c->opt_shard_ingest);
+    // N > 1: 1 = cge_set_embedding / cge_set_embedding_device keep the rows of this rank's communities only (sharded BY COMMUNITY;
+    // set the collectives and upload the communities first); 0 (default): every rank holds every row
+    if (is("shard_rows")) return flag(c->opt_shard_rows);
+    // 1: cge_score also builds the landmark-pair matrix / edge count that landmarks() returns (src/landmarks.jl:433-463; the
+    // undirected score itself does not read it); 0 (default): on first fetch
+    if (is("landmark_edges")) return flag(c->opt_landmark_edges);
+    // iterations after which a Chung-Lu fit that has not converged raises CGE_E_ASSERT (default 2 000 000)
+    if (is("fit_max_iterations")) return ranged(c->opt_fit_max_iters, 1, INT64_MAX);
     return CGE_E_ARG;
 }
 // the testing knobs (include/cge_hip_testing.h): not part of the boundary
 int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     cge_ctx *c = (cge_ctx *)ctx;
     if (!c || !key) return CGE_E_ARG;
-    if (!strcmp(key, "test_bvec_plain")) { // testing: 1 = vect_B by the kernels of score graphs beyond the LDS budget
-        c->opt_test_bvec_plain = value != 0;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "fit_persistent_test_delay")) { // testing: start skew of the persistent fits' tile waves, in naps of ~3 us
-        if (value < 0 || value > 100000) return CGE_E_ARG;
-        c->opt_fit_test_delay = (int)value;
-        return CGE_OK;
-    }
-    if (!strcmp(key, "fit_persistent_test_timeout")) { // testing: 1 = the persistent fit abandons every launch at once
-        c->opt_fit_test_timeout = value != 0;
-        return CGE_OK;
-    }
+    // 1 = vect_B by the kernels of score graphs beyond the LDS budget
+    if (!strcmp(key, "test_bvec_plain")) { c->opt_test_bvec_plain = value != 0; return CGE_OK; }
+    // start skew of the persistent fits' tile waves, in naps of ~3 us
+    if (!strcmp(key, "fit_persistent_test_delay") && value >= 0 && value <= 100000) { c->opt_fit_test_delay = (int)value; return CGE_OK; }
+    // 1 = the persistent fit abandons every launch at once
+    if (!strcmp(key, "fit_persistent_test_timeout")) { c->opt_fit_test_timeout = value != 0; return CGE_OK; }
     return CGE_E_ARG;
 }
 int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
@@ -1398,24 +383,10 @@ int cge_profile_get(cge_ctx *c, const char *name, int64_t *launches, double *tot
     return CGE_OK;
 }
 int cge_profile_names(cge_ctx *c, char *buf, int64_t buf_len) {
-    if (!c || !buf || buf_len <= 0) return CGE_E_ARG;
-    std::string s;
-    for (auto &kv : c->timers) {
-        if (!s.empty()) s += ",";
-        s += kv.first;
-    }
-    snprintf(buf, (size_t)buf_len, "%s", s.c_str());
-    return CGE_OK;
+    return !c || !buf || buf_len <= 0 ? CGE_E_ARG : key_names(c->timers, buf, buf_len);
 }
 int cge_phase_names(cge_ctx *c, char *buf, int64_t buf_len) {
-    if (!c || !buf || buf_len <= 0) return CGE_E_ARG;
-    std::string s;
-    for (auto &kv : c->phases.ms) {
-        if (!s.empty()) s += ",";
-        s += kv.first;
-    }
-    snprintf(buf, (size_t)buf_len, "%s", s.c_str());
-    return CGE_OK;
+    return !c || !buf || buf_len <= 0 ? CGE_E_ARG : key_names(c->phases.ms, buf, buf_len);
 }
 int cge_phase_ms(cge_ctx *c, const char *phase, double *ms) {
     if (!c || !phase || !ms) return CGE_E_ARG;
@@ -1466,8 +437,7 @@ int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int
                              int64_t *nref, int *pass_ran, double *ref_points, double *mean) {
     cge_ctx *c = (cge_ctx *)ctx;
     if (!c || !v2l || !lcomm || !P || !nref || !pass_ran || N <= 0 || C <= 0 || pass < 0 || pass > 2) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     host_diameter_bounds_test(c, v2l, N, lcomm, C, pass, P, nref, pass_ran, ref_points, mean);
     CGE_CATCH(c)
 }
@@ -1484,8 +454,7 @@ int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method
 int cge_segment_sort_test(void *ctx, const double *z, const int32_t *task_row_off, int64_t T, double *zs_out, int32_t *perm_out) {
     cge_ctx *c = (cge_ctx *)ctx;
     if (!c || !z || !task_row_off || !zs_out || !perm_out || T <= 0) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     const i64 R = task_row_off[T];
     if (R <= 0) CGE_THROW(CGE_E_ARG, "segment_sort_test: no rows");
     std::vector<i32> rt(R), rows(R);
@@ -1514,8 +483,7 @@ int cge_segment_sort_test(void *ctx, const double *z, const int32_t *task_row_of
 int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_ref, double *out_new) {
     cge_ctx *c = (cge_ctx *)ctx;
     if (!c || !x || !out_ref || !out_new || n_rows <= 0) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     DevBuf<double> dx, da, db;
     dx.ensure((size_t)n_rows * 64); da.ensure(n_rows); db.ensure(n_rows);
     HIP_CHECK(hipMemcpyAsync(dx.p, x, sizeof(double) * n_rows * 64, hipMemcpyHostToDevice, c->stream));
@@ -1531,8 +499,7 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
 int cge_resident_embedding_test(void *ctx, double *out, int64_t capacity_doubles, int64_t *rows, int64_t *d, int32_t *ids_out) {
     cge_ctx *c = (cge_ctx *)ctx;
     if (!c || !rows || !d) return CGE_E_ARG;
-    CGE_TRY(c)
-    HIP_CHECK(hipSetDevice(c->device));
+    CGE_TRY_ON_DEVICE(c)
     if (!c->Xr.p || c->d <= 0) CGE_THROW(CGE_E_ARG, "embedding not resident");
     const i64 nl = lm_rows(c);
     *rows = nl;
@@ -1546,40 +513,3 @@ int cge_resident_embedding_test(void *ctx, double *out, int64_t capacity_doubles
 }
 
 } // extern "C"
-
-bool cge_exchange_fits(cge_ctx *c, size_t need) {
-    if (c->xptr && need <= c->xcap) return true;
-    if (!c->rccl_comm || (c->xptr && c->xptr != c->xown.p)) return false;
-    c->xown.alloc_exact(std::max<size_t>(need + need / 4, 1 << 20));
-    c->xptr = c->xown.p;
-    c->xcap = c->xown.n;
-    return true;
-}
-
-// all-gather of 8-byte words in place (the sharded ingest of the embedding): ncclAllGather on the ctx stream with the
-// in-library communicator; through the hook (tests), or with a librccl that lacks the symbol, a zero-filled all-reduce of
-// the words as integers -- exact on the bit patterns (a sum of doubles would turn -0.0 into +0.0)
-void cge_allgather_dev(cge_ctx *c, double *buf, i64 wpr) {
-    if (!c->has_coll || wpr <= 0) return;
-    if (c->rccl_comm && cge_rccl_allgather(c, buf, wpr)) return;
-    const i64 W = c->coll.world, r = c->coll.rank, total = wpr * W;
-    if (!c->rccl_comm && c->coll_ext.allgather && c->xptr && (size_t)total <= c->xcap) { // the hook's own all-gather, through the exchange buffer
-        if (buf != c->xptr)
-            HIP_CHECK(hipMemcpyAsync(c->xptr + wpr * r, buf + wpr * r, sizeof(double) * (size_t)wpr, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->coll_ext.allgather(c->coll.user, c->xptr, wpr) != 0) CGE_THROW(CGE_E_COLLECTIVE, "all-gather hook failed");
-        c->stat_coll_calls++;
-        c->stat_coll_bytes += 8 * total;
-        if (buf != c->xptr) HIP_CHECK(hipMemcpyAsync(buf, c->xptr, sizeof(double) * (size_t)total, hipMemcpyDeviceToDevice, c->stream));
-        return;
-    }
-    if (r > 0) HIP_CHECK(hipMemsetAsync(buf, 0, sizeof(double) * (size_t)(wpr * r), c->stream));
-    if (r + 1 < W) HIP_CHECK(hipMemsetAsync(buf + wpr * (r + 1), 0, sizeof(double) * (size_t)(wpr * (W - 1 - r)), c->stream));
-    const i64 piece = c->rccl_comm ? total : (i64)c->xcap;
-    if (piece <= 0) CGE_THROW(CGE_E_COLLECTIVE, "all-gather: no exchange buffer set");
-    for (i64 off = 0; off < total; off += piece) allreduce(c, buf + off, std::min(piece, total - off), 2);
-}
-
-// for the other translation units (diameter_host.cpp)
-void cge_allreduce_dev(cge_ctx *c, double *dev, i64 count, int op) { allreduce(c, dev, count, op); }
-double cge_allreduce_scalar_max(cge_ctx *c, double v) { return allreduce_scalar_max(c, v); }

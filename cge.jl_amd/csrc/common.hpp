@@ -56,6 +56,7 @@ struct CgeError {
 
 // the body of an extern "C" entry point: an exception becomes the context's message and a status
 #define CGE_TRY(ctx) try {
+#define CGE_TRY_ON_DEVICE(ctx) CGE_TRY(ctx) HIP_CHECK(hipSetDevice((ctx)->device)); // ... on the context's device
 #define CGE_CATCH(ctx)                                             \
     }                                                              \
     catch (const CgeError &e) {                                    \
@@ -513,7 +514,6 @@ struct cge_ctx {
     } samp_pending;
     PinBuf<unsigned long long> samp_pin_cnt;
     hipEvent_t samp_ev = nullptr;
-    std::function<void()> after_unique; // cge_score: work to enqueue behind the first synchronisation of the landmark phase (once)
     SampleSet smp;                 // library-drawn samples of the running score
     std::vector<std::unique_ptr<DevSamples>> dsets; // their device form (wgcl_host.cpp)
 
@@ -558,6 +558,8 @@ struct ScopedKernelTimer {
         t->launches++;
     }
 };
+
+void flush_timers(cge_ctx *c); // capi.cpp: the event pairs of the finished launches become milliseconds, the events go back to the pool
 
 #define CGE_FIT_TIMEOUT_TICKS 100000000LL // 1 s of the 100 MHz wall clock, re-armed at every Chung-Lu iteration
 static inline void note_fit_fallback(cge_ctx *c) {
@@ -633,7 +635,24 @@ static void staged_upload(cge_ctx *c, T *dev, size_t total, F fill) {
     staged_upload_chunks<T>(c, dev, total, chunk, 0, fill, [](T *, size_t, size_t) {});
 }
 
+// ---- collectives.cpp: the exchanges between ranks, in place on the ctx stream (in-library RCCL, or the hook of
+// cge_set_collectives through the exchange buffer); all of them do nothing without collectives ---------------------------------
+void cge_allreduce_dev(cge_ctx *c, double *dev, i64 count, int op /*0 sum, 1 max of doubles, 2 sum of int64*/);
+double cge_allreduce_scalar_max(cge_ctx *c, double v); // max of one double over the ranks (synchronises); v itself without collectives
+void cge_allgather_dev(cge_ctx *c, double *buf, i64 words_per_rank); // world pieces of 8-byte words; this rank's piece is filled in
+// sum of doubles over world blocks, rank r ends with block r.  true: went out by blocks; false: no such op here, the caller all-reduces
+bool cge_reduce_scatter_dev(cge_ctx *c, double *buf, i64 words_per_rank);
+// can the exchange buffer hold `need` doubles?  With the in-library communicator a library-owned buffer grows on demand
+// (contents are not preserved); a caller-provided one (cge_set_exchange_buffer, the hook path) is what it is.
+bool cge_exchange_fits(cge_ctx *c, size_t need);
+
+// ---- graph_host.cpp: the resident graph and vertex data (what cge_set_graph / cge_set_vertex_data do; they throw) ---------------
+void set_graph(cge_ctx *c, const int64_t *src, const int64_t *dst, const double *w, i64 m, i64 n);
+void set_vertex_data(cge_ctx *c, const int64_t *comm, const double *vw, i64 n);
+void check_resident(cge_ctx *c, const char *who); // graph, embedding and vertex data resident and sized for one vertex set
+
 // ---- embedding_host.cpp: everything that makes an embedding resident ----------------------------------------------------------
+void set_embedding_view(cge_ctx *c, const char *who, const cge_embedding_view *v, i64 n); // the ingest; `who` names the entry point in messages
 void cge_ensure_host_embedding(cge_ctx *c); // fetch the host mirror of Xr on first demand
 bool ingest_sharded(const cge_ctx *c);      // N > 1 with option "shard_ingest": a rank uploads its share of the edge list / the rows
 void rows_unshard(cge_ctx *c);              // option "shard_rows": drop the ownership tables (the rows are whole again)
@@ -734,16 +753,6 @@ void k_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi, const i32 *
                  double *out);
 void k_diameter_layout(cge_ctx *c, const i32 *mem_off, const i32 *mem, const i32 *soff, i64 N, i32 *pos2node, i32 *sub_land,
                        i64 n_sub);
-void cge_allreduce_dev(cge_ctx *c, double *dev, i64 count, int op /*0 sum, 1 max*/); // no-op without collectives
-void cge_rccl_allreduce(cge_ctx *c, void *dev, i64 count, int op); // collectives.cpp: in place, on the ctx stream
-bool cge_rccl_allgather(cge_ctx *c, void *dev, i64 words_per_rank); // in place (rank r's piece at r * words_per_rank); false: no such symbol
-// all-gather of 8-byte words in place: `buf` holds world pieces of `words_per_rank`, this rank's piece is filled in
-void cge_allgather_dev(cge_ctx *c, double *buf, i64 words_per_rank);
-bool cge_rccl_reduce_scatter(cge_ctx *c, void *dev, i64 words_per_rank); // in place: rank r's sums land at r * words_per_rank; false: no such symbol
-double cge_allreduce_scalar_max(cge_ctx *c, double v); // max of one double over the ranks (synchronises); v itself without collectives
-// can the exchange buffer hold `need` doubles?  With the in-library communicator a library-owned buffer grows on demand
-// (contents are not preserved); a caller-provided one (cge_set_exchange_buffer, the hook path) is what it is.
-bool cge_exchange_fits(cge_ctx *c, size_t need);
 void k_pcent(cge_ctx *c, const double *Xs, const double *rns, i64 lds_rows, const double *Ms, const double *mnorm,
              i64 ldm, i64 n_land, i64 N, i64 dpad, const i32 *soff, double *P, int part = 0, int nparts = 1);
 void k_max_pair_tile_list(i64 ldn, int part, int nparts, const std::vector<double> &wg, double thr, std::vector<int2> &out);
@@ -910,6 +919,7 @@ void k_auc_landmark(cge_ctx *c, const double *Ta, const double *Tb, const i32 *v
                     const double *dpos, const double *dneg, const double *wts, i64 S, double alpha, double *out2, double *partials = nullptr);
 void k_auc_exact(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, i64 N, const i32 *pi,
                  const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, double *out2, double *partials = nullptr);
+void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out); // kernels_fit.hip: out[k] = arr[idx[k]]
 void k_mark_edge_hits(cge_ctx *c, const i32 *src, const i32 *dst, i64 m, int directed, const uint64_t *table,
                       i64 table_size, i32 *hit);
 
@@ -1024,5 +1034,26 @@ struct BatchMember {
 };
 // the alpha sweeps of one launch group in lock-step (sum of G <= CUs, one NW, at most CGE_BATCH_MAX members)
 void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group);
+int score_batch_run(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
+                    int *out_len, cge_trace *traces);
+// score_host.cpp: what the entry points of the same names (cge_*) do
+struct LandmarkRun { // cge_landmarks_run's arguments; need_wedges: build the N x N landmark-pair matrix too (else on first demand)
+    const i64 *cl_flat, *cl_off;
+    i64 ncl, land, forced; // (land: once lm_clamp has run, clamped to the unique rows)
+    int method, directed;
+    bool need_wedges;
+    double t0 = 0.0; // start of the phase being timed (c->phases)
+};
+LandmarkRun score_landmark_run(const cge_ctx *c, const cge_score_args *a); // the landmark run of a cge_score
+void host_landmarks_run(cge_ctx *c, LandmarkRun R);
+void host_landmarks_info(cge_ctx *c, const char *who = "landmarks_info"); // the last run's landmark-pair matrix, built on first demand
+void host_landmarks_fetch(cge_ctx *c, double *dii, double *embed, int64_t *cluster, int64_t *ledges, double *lw_e, double *lweight,
+                          int64_t *v_to_l);
+void host_score(cge_ctx *c, const cge_score_args *a, double out[7], int *out_len, cge_trace *trace, SweepHandoff *defer,
+                bool reuse_samples); // `defer` / `reuse_samples`: a member of cge_score_batch
+void host_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, cge_trace *trace);
+void host_js(cge_ctx *c, const double *vC, const double *vB, i64 len, const uint8_t *vI, int internal, double *out);
+void host_edge_scatter(cge_ctx *c, const int64_t *v_to_l, i64 N, i64 C, int directed, i64 e0, i64 e1, double *wedges_out,
+                       double *vect_C_out);
 // fit_flow_kernel's geometry for N landmarks on `cus` CUs (no device needed); false: the fused form does not apply
 bool k_fit_flow_geometry_cus(i64 N, int cus, int *G, int *NW);

@@ -305,7 +305,7 @@ static void ingest_finish(Ingest &S) {
     embedding_resident(c, S.n, S.d);
 }
 
-static void embedding_ingest(cge_ctx *c, const char *who, const cge_embedding_view *v, i64 n) {
+void set_embedding_view(cge_ctx *c, const char *who, const cge_embedding_view *v, i64 n) {
     Ingest S{c, who, v, n};
     ingest_check(S);
     ingest_place(S);
@@ -327,7 +327,7 @@ int cge_embedding_view_check(const cge_embedding_view *v, int64_t n, char *err, 
 int cge_set_embedding_view(cge_ctx *c, const cge_embedding_view *v, int64_t n) {
     if (!c || !v) return CGE_E_ARG;
     CGE_TRY(c)
-    embedding_ingest(c, "set_embedding_view", v, n);
+    set_embedding_view(c, "set_embedding_view", v, n);
     CGE_CATCH(c)
 }
 
@@ -336,7 +336,7 @@ int cge_set_embedding(cge_ctx *c, const double *X, int64_t n, int64_t d) {
     if (!c || !X || n <= 0 || d <= 0) return CGE_E_ARG;
     const cge_embedding_view v = {X, d, 0, CGE_DTYPE_F64, 0, 0};
     CGE_TRY(c)
-    embedding_ingest(c, "set_embedding", &v, n);
+    set_embedding_view(c, "set_embedding", &v, n);
     CGE_CATCH(c)
 }
 
@@ -344,7 +344,7 @@ int cge_set_embedding_device(cge_ctx *c, const double *X_dev, int64_t n, int64_t
     if (!c || !X_dev || n <= 0 || d <= 0) return CGE_E_ARG;
     const cge_embedding_view v = {X_dev, d, 0, CGE_DTYPE_F64, 1, row_major};
     CGE_TRY(c)
-    embedding_ingest(c, "set_embedding_device", &v, n);
+    set_embedding_view(c, "set_embedding_device", &v, n);
     CGE_CATCH(c)
 }
 

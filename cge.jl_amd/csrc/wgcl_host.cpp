@@ -814,7 +814,6 @@ void AlphaBook::write(double out[7], int *out_len) const {
 
 
 // ---- small helpers ---------------------------------------------------------------------------------
-void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out); // kernels_fit.hip
 
 static void gather_rows(cge_ctx *c, const i32 *d_arr, const std::vector<i64> &rows0, std::vector<i32> &out,
                         DevBuf<i32> &d_idx, DevBuf<i32> &d_out) {

@@ -28,7 +28,7 @@ import numpy as np
 
 
 def edge_shard(m: int, rank: int, world: int):
-    """Rows of the edge list owned by `rank` -- the same formula as capi.cpp:landmarks_run_impl."""
+    """Rows of the edge list owned by `rank` -- the same formula as score_host.cpp:edge_share."""
     return m * rank // world, m * (rank + 1) // world
 
 
@@ -51,7 +51,7 @@ def candidate_tile_shard(n_tiles: int, rank: int, world: int):
 
 def community_owner(comm, world: int):
     """Option shard_rows: owner rank of every community (index = community id, 1-based ids -> entry id - 1 ... here: returns
-    an array indexed by the 0-based community) -- the same rule as capi.cpp:rows_assign_ownership: communities by decreasing
+    an array indexed by the 0-based community) -- the same rule as embedding_host.cpp:rows_assign_ownership: communities by decreasing
     size (ties: lower id first), each to the rank with the fewest rows so far (ties: lower rank).  `comm`: 1-based ids."""
     comm = np.asarray(comm).reshape(-1)
     size = np.bincount(comm - 1)

@@ -677,6 +677,112 @@ def test_score_directed_device_resident(ctx, orc, test115):
     assert list(ctx.score([], -1, directed=True, seed=1, auc_samples=10)) == [-1.0, 0.0, 0.0, 0.0, 0.0, 0.0]
 
 
+def test_score_directed_landmark_mode_star_graph_then_the_next_score(ctx, test115):
+    """cge_score -d in LANDMARK mode on a star graph (the exact-mode form is in the test above): 8 vertices, every vertex its own
+    landmark, once with every edge pointing away from the hub (the first condition of src/divergence.jl:321-334: a count of
+    N - 1 and 2 (N - 1) in all) and once with both directions (the second: a count of 2 (N - 1) and N - 1 counts of 2).  Both
+    give the 6-element return (the degrees and star counts come from the landmark-pair matrix), and the early return leaves
+    nothing behind in the context: the next score of a graph that is no star equals a fresh context's bit for bit.  (8 vertices
+    are sampled on the host: the early sample draw that such a return leaves pending needs the larger graph of the next test.)"""
+    from cge.jl_amd import api
+
+    a = test115
+    k = 8
+    away = np.stack([np.ones(k - 1, np.int64), np.arange(2, k + 1)], axis=1)
+    emb = np.random.default_rng(0).random((k, 4))  # 8 distinct rows: the unique-row clamp leaves 8 landmarks
+    for edges in (away, np.concatenate([away, away[:, ::-1]])):
+        edges = np.asfortranarray(edges)
+        ctx.set_inputs(edges, np.ones(len(edges)), np.ones(k), np.ones((k, 1), np.int64), emb)
+        out = ctx.score([list(range(1, k + 1))], k, 1, "rss", directed=True, seed=1, auc_samples=10)
+        assert ctx.landmarks_info()[0] == k
+        assert len(out) == 6 and out[0] == -1.0
+
+    def score115(c):
+        c.set_inputs(a["edges"], a["eweights"], a["vweights"], a["comm"], a["embedding"])
+        return c.score(a["clusters"], 30, 2, "rss", directed=True, split=True, seed=5, auc_samples=3000)
+
+    got = score115(ctx)
+    fresh = api.Context(0)
+    try:
+        exp = score115(fresh)
+    finally:
+        fresh.close()
+    assert len(got) == 7 and np.array_equal(got, exp)
+
+
+def test_score_directed_landmark_mode_star_return_with_the_early_sample_draw_pending(ctx):
+    """The same two star shapes among the LANDMARKS of a graph of 6000 vertices: from 5794 vertices on (n (n - 1) > 2^25) the
+    seeded local score's samples are drawn on the device, and cge_score enqueues that draw between the unique-row clamp and
+    runsplit -- so the 6-element return of a star graph leaves a draw pending, which must be drained.  8 communities = 8 clusters
+    = 8 landmarks; edges only between the vertices of cluster 1 and those of the others, away from cluster 1 and both ways.
+    The next score, of a graph that is no star and starts an early draw of its own, equals a fresh context's bit for bit."""
+    from cge.jl_amd import api, synth
+
+    n, k = 6000, 8
+    per = n // k
+    comm = np.repeat(np.arange(1, k + 1, dtype=np.int64), per).reshape(-1, 1)
+    clusters = [list(range(1 + per * q, 1 + per * (q + 1))) for q in range(k)]
+    spokes = np.arange(per + 1, n + 1, dtype=np.int64)  # every vertex outside cluster 1 hangs on one vertex of cluster 1
+    away = np.stack([spokes % per + 1, spokes], axis=1)
+    emb = np.random.default_rng(0).random((n, 4))  # distinct rows: the unique-row clamp leaves the 8 landmarks
+    for edges in (away, np.concatenate([away, away[:, ::-1]])):
+        edges = np.asfortranarray(edges)
+        ctx.set_inputs(edges, np.ones(len(edges)), np.ones(n), comm, emb)
+        out = ctx.score(clusters, k, 1, "rss", directed=True, seed=1, auc_samples=1000)
+        assert ctx.landmarks_info()[0] == k
+        assert len(out) == 6 and out[0] == -1.0
+
+    g = synth.abcd_like(n, 8 * n, 12, 8, seed=19, directed=True)
+
+    def score(c):
+        c.set_inputs(g["edges"], g["eweights"], g["vweights"], g["comm"], g["embedding"])
+        return c.score(g["clusters"], 60, 2, "rss", directed=True, seed=5, auc_samples=3000)
+
+    got = score(ctx)
+    fresh = api.Context(0)
+    try:
+        exp = score(fresh)
+    finally:
+        fresh.close()
+    assert len(got) == 7 and np.array_equal(got, exp)
+
+
+def test_wgcl_init_graph_with_a_vertex_id_out_of_range(ctx, test115):
+    """cge_wgcl in landmark mode makes its init_* arrays the resident graph by the code behind cge_set_graph: an init_edges list
+    with one source id n + 1 is refused with cge_set_graph's own code and message (naming the same edge), and a valid call on the
+    same context afterwards gives the 7-vector a fresh context gives."""
+    import cge.jl_amd as cg
+    from cge.jl_amd import api
+
+    a = test115
+    n = len(a["vweights"])
+    lm = cg.landmarks(a["edges"], a["eweights"], a["vweights"], a["clusters"], a["comm"], a["embedding"], False, 30, 2, "rss",
+                      False, ctx=ctx)
+    dii, lemb, lcomm, ledges, lw, lweight, v2l = lm
+
+    def wgcl(c, init_edges):
+        return cg.wGCL(ledges, lw, lcomm, lemb, dii, lweight, a["vweights"], v2l, init_edges, a["eweights"], a["embedding"],
+                       False, 7, 2000, ctx=c)
+
+    K = 17
+    bad = np.array(a["edges"], dtype=np.int64, order="F")
+    bad[K - 1, 0] = n + 1
+    with pytest.raises(api.CGEError) as by_set_graph:
+        ctx.set_graph(bad, a["eweights"], n)
+    with pytest.raises(api.CGEError) as by_wgcl:
+        wgcl(ctx, bad)
+    assert by_wgcl.value.code == by_set_graph.value.code == -7
+    assert str(by_wgcl.value) == str(by_set_graph.value)
+    assert str(by_wgcl.value).endswith(f": edge {K} has a vertex id outside 1..{n}")
+    got = wgcl(ctx, a["edges"])
+    fresh = api.Context(0)
+    try:
+        exp = wgcl(fresh, a["edges"])
+    finally:
+        fresh.close()
+    assert len(got) == 7 and np.array_equal(got, exp)
+
+
 def test_directed_exact_mode_device_sampler_with_the_second_draw(ctx):
     """Directed exact mode on a graph large enough for the device sampler (n(n-1) > 2^25): the un-reseeded second positive
     draw of src/divergence.jl:510 overwrites the pairs but not the weights -- the fused path (draws and preparation on the
