@@ -10,8 +10,14 @@
 // guards keep simultaneous moves from chasing each other: two singletons only merge towards the smaller id, and a vertex
 // may only move in every other round (by a hash of its id).  The host keeps the best partition seen (synchronous rounds
 // are not monotone in the modularity) and stops after three rounds without an improvement of more than 1e-6 (the
-// reference's own threshold) or when nothing moves.  Not bit-comparable with the reference (whose visiting order is
-// random): tests compare modularity and structure with the sequential restatement in the oracle and with networkx.
+// reference's own threshold) or when nothing WANTS to move: no vertex has a strictly better community that the singleton
+// guard allows.  A vertex that the turn guard alone holds back keeps the pass going (its turn is the next round), so a round
+// in which nothing moved is not the end by itself.  When every edge is a self loop there is nothing to move and the
+// singleton partition is returned with its own modularity (a self loop counts once in k_v and once in "in").
+// Not bit-comparable with the reference (whose visiting order is random): tests compare modularity and structure with the
+// sequential restatement in the oracle and with networkx, and the rounds themselves -- partition, round count, modularity
+// -- with the numpy restatement tests/louvain_ref.py, exactly on integer and dyadic weights (-ffp-contract=off: the sums
+// are exact there, whatever their order).
 #include "common.hpp"
 
 #include <rocprim/rocprim.hpp>
@@ -61,13 +67,14 @@ __global__ void lv_keys_kernel(const i32 *__restrict__ adj, const i32 *__restric
     for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < len; q += stride) keys[q] = (unsigned)comm[adj[q]];
 }
 // one thread per vertex: the runs of its community-sorted adjacency segment -> the community of largest gain.
-// stats[0] += moves, stats[1] += sum_v (k_{v,own} + self_v)  (the "in" part of the modularity of the CURRENT partition)
+// stats[0] += moves, stats[1] += sum_v (k_{v,own} + self_v)  (the "in" part of the modularity of the CURRENT partition),
+// stats[3] += vertices that want to move: a strictly better community that the singleton guard allows, on turn or not
 __global__ void lv_decide_kernel(const i32 *__restrict__ off, const unsigned *__restrict__ skeys, const double *__restrict__ saw,
                                  const double *__restrict__ self, const double *__restrict__ k, const double *__restrict__ tot,
                                  const i32 *__restrict__ size, const i32 *__restrict__ comm, i64 n, double m2, int round,
                                  i32 *__restrict__ newcomm, double *__restrict__ stats) {
     const i64 v = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    double in_part = 0.0, moved = 0.0;
+    double in_part = 0.0, moved = 0.0, wants = 0.0;
     if (v < n) {
         const i32 own = comm[v];
         const double kv = k[v];
@@ -90,13 +97,20 @@ __global__ void lv_decide_kernel(const i32 *__restrict__ off, const unsigned *__
             if (inc > best_inc) { best = c; best_inc = inc; }
         }
         const bool my_turn = ((((unsigned)v * 2654435761u) >> 15) & 1u) == (unsigned)(round & 1);
-        if (best != own && (!my_turn || (size[own] == 1 && size[best] == 1 && best > own))) best = own;
+        if (best != own && size[own] == 1 && size[best] == 1 && best > own) best = own;
+        wants = best != own ? 1.0 : 0.0;
+        if (!my_turn) best = own;
         newcomm[v] = best;
         moved = best != own ? 1.0 : 0.0;
     }
-    for (int o = 32; o > 0; o >>= 1) { in_part += __shfl_down(in_part, o); moved += __shfl_down(moved, o); }
+    for (int o = 32; o > 0; o >>= 1) {
+        in_part += __shfl_down(in_part, o);
+        moved += __shfl_down(moved, o);
+        wants += __shfl_down(wants, o);
+    }
     if ((threadIdx.x & 63) == 0) {
         if (moved != 0.0) unsafeAtomicAdd(&stats[0], moved);
+        if (wants != 0.0) unsafeAtomicAdd(&stats[3], wants);
         if (in_part != 0.0) unsafeAtomicAdd(&stats[1], in_part);
     }
 }
@@ -156,17 +170,17 @@ void k_louvain_level1(cge_ctx *c, i64 *comm_out_host, i64 *n_comm, double *quali
     adj.ensure(len); keys.ensure(len); skeys.ensure(len);
     if (weighted) { aw.ensure(len); saw.ensure(len); }
     self.ensure(n); k.ensure(n); tot.ensure(n); comm.ensure(n); newcomm.ensure(n); size.ensure(n); best.ensure(n);
-    stats.ensure(4);
+    stats.ensure(5); // moves, in, sum tot^2, wants (cleared every round); m2
     HIP_CHECK(hipMemsetAsync(self.p, 0, sizeof(double) * n, st));
-    HIP_CHECK(hipMemsetAsync(stats.p, 0, sizeof(double) * 4, st));
+    HIP_CHECK(hipMemsetAsync(stats.p, 0, sizeof(double) * 5, st));
     hipLaunchKernelGGL(lv_fill_kernel, dim3(grid_for(m, 256)), dim3(256), 0, st, c->src.p, c->dst.p, weighted ? c->w.p : nullptr, m,
                        off.p, cur.p, adj.p, weighted ? aw.p : nullptr, self.p);
     hipLaunchKernelGGL(lv_degree_kernel, dim3(gv), dim3(256), 0, st, off.p, weighted ? aw.p : nullptr, self.p, n, k.p, tot.p, comm.p,
-                       size.p, stats.p + 3);
-    double hs[4];
+                       size.p, stats.p + 4);
+    double hs[5];
     HIP_CHECK(hipMemcpyAsync(hs, stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    const double m2 = hs[3];
+    const double m2 = hs[4];
     int bits = 1;
     while (((i64)1 << bits) < n) bits++;
     double best_q = -1e300;
@@ -190,11 +204,11 @@ void k_louvain_level1(cge_ctx *c, i64 *comm_out_host, i64 *n_comm, double *quali
                 HIP_CHECK(rocprim::segmented_radix_sort_keys(c->sort_tmp.p, bytes, keys.p, skeys.p, (unsigned)len, (unsigned)n, off.p,
                                                              off.p + 1, 0, bits, st));
             }
-            HIP_CHECK(hipMemsetAsync(stats.p, 0, sizeof(double) * 3, st));
+            HIP_CHECK(hipMemsetAsync(stats.p, 0, sizeof(double) * 4, st));
             hipLaunchKernelGGL(lv_decide_kernel, dim3(gv), dim3(256), 0, st, off.p, skeys.p, weighted ? saw.p : nullptr, self.p, k.p,
                                tot.p, size.p, comm.p, n, m2, round, newcomm.p, stats.p);
             hipLaunchKernelGGL(lv_totsq_kernel, dim3(gv), dim3(256), 0, st, tot.p, size.p, n, stats.p);
-            HIP_CHECK(hipMemcpyAsync(hs, stats.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(hs, stats.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
             const double q = hs[1] / m2 - hs[2] / (m2 * m2); // modularity of the partition this round STARTED from
             if (q > best_q + 1e-6) {
@@ -203,11 +217,19 @@ void k_louvain_level1(cge_ctx *c, i64 *comm_out_host, i64 *n_comm, double *quali
                 HIP_CHECK(hipMemcpyAsync(best.p, comm.p, sizeof(i32) * n, hipMemcpyDeviceToDevice, st));
             } else if (++since_best >= 3)
                 break;
-            if (hs[0] == 0.0) break; // nothing wants to move
+            if (hs[3] == 0.0) break;    // nothing wants to move
+            if (hs[0] == 0.0) continue; // everything that wants to is off turn: the next round is theirs
             hipLaunchKernelGGL(lv_apply_kernel, dim3(gv), dim3(256), 0, st, comm.p, newcomm.p, k.p, n, tot.p, size.p);
         }
     } else {
+        // no edge between two vertices: the singletons stay.  in = sum_v self_v, tot_v = k_v
         best_q = 0.0;
+        if (m2 > 0.0) {
+            hipLaunchKernelGGL(lv_totsq_kernel, dim3(gv), dim3(256), 0, st, tot.p, size.p, n, stats.p);
+            HIP_CHECK(hipMemcpyAsync(hs, stats.p, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            best_q = 1.0 - hs[2] / (m2 * m2); // len == 0: k_v = self_v, so "in" is m2 itself
+        }
         HIP_CHECK(hipMemcpyAsync(best.p, comm.p, sizeof(i32) * n, hipMemcpyDeviceToDevice, st));
     }
     // renumber 0.. in ascending order of the surviving community ids

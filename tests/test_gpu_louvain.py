@@ -9,7 +9,9 @@ import sys
 import numpy as np
 import pytest
 
+import louvain_graphs as lg
 from conftest import GOLDEN, ROOT
+from louvain_ref import modularity, sync_level1
 
 pytestmark = pytest.mark.gpu
 nx = pytest.importorskip("networkx")
@@ -85,3 +87,56 @@ def test_louvain_clust_writes_the_ecg_file_and_parseargs_uses_it(ctx, tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     vec = [float(x) for x in r.stdout.strip().strip("[]").split(",")]
     assert len(vec) == 7 and all(np.isfinite(vec)) and 0.25 <= vec[0] <= 10.0
+
+
+# ---- the rounds themselves: the device against tests/louvain_ref.py (numpy, fp64, the same expressions) ---------------------
+EXACT_CASES = {
+    "path5": lg.path(5), "path24": lg.path(24), "cycle17": lg.cycle(17), "star7": lg.star(7),
+    "ring6x4": lg.clique_chain(6, 4, ring=True), "chain5x5": lg.clique_chain(5, 5), "barbell5_3": lg.barbell(5, 3),
+    "triangles_through_a_vertex": lg.barbell(3, 1),
+    **{f"random{n}": lg.random_multigraph(n, seed=n) for n in (2, 3, 63, 64, 65, 255, 256, 257, 1000, 4097)},
+    "star_of_cliques5001": lg.star_of_cliques(1000, 5),
+    "self_loop_only_vertex": (np.array([[0, 1], [1, 2], [0, 2], [3, 3], [4, 5], [2, 4]]), 7),
+    "all_self_loops": (np.array([[0, 0], [1, 1]]), 2),
+    "all_self_loops_repeated": (np.array([[0, 0], [2, 2], [2, 2], [4, 4]]), 5),
+}
+
+
+def _device(ctx, e, w, n):
+    ctx.set_graph(e + 1, np.ones(len(e)) if w is None else w, n)
+    return ctx.louvain()
+
+
+@pytest.mark.parametrize("weights", ["unit", "dyadic"])
+@pytest.mark.parametrize("name", list(EXACT_CASES))
+def test_device_rounds_equal_the_restatement(ctx, name, weights):
+    """Integer and dyadic weights (multiples of 1/4 up to 4): every sum is exact in any order, so partition, number of
+    communities and round count are equal and the modularity agrees to the last few bits."""
+    e, n = EXACT_CASES[name]
+    w = None if weights == "unit" else np.random.default_rng(len(e)).integers(1, 17, size=len(e)) / 4.0
+    comm, nc, q, rounds = _device(ctx, e, w, n)
+    r_comm, r_nc, r_q, r_rounds = sync_level1(e, w, n)
+    print(name, weights, "device", nc, q, rounds, "restatement", r_nc, r_q, r_rounds)
+    assert (nc, rounds) == (r_nc, r_rounds) and np.array_equal(comm, r_comm)
+    assert q == pytest.approx(r_q, abs=1e-12)
+
+
+@pytest.mark.parametrize("cliques,size", [(8, 5), (30, 5), (12, 7)])
+def test_real_weights_find_the_cliques_and_report_their_modularity(ctx, cliques, size):
+    """Weights 1.3 / 0.7: sums may round differently from the restatement's and from run to run (atomics), so the structure
+    and the quality are checked, not the rounds.  1e-12: fewer than 10^3 terms of order 1, summed in any order."""
+    e, w, n, labels = lg.weighted_clique_ring(cliques, size)
+    comm, nc, q, rounds = _device(ctx, e, w, n)
+    print(cliques, size, "device", nc, q, rounds, "formula", modularity(e, w, n, comm))
+    assert nc == cliques + 2 and np.array_equal(comm, labels)
+    assert q == pytest.approx(modularity(e, w, n, comm), abs=1e-12)
+    comm2, _, q2, _ = ctx.louvain()
+    assert modularity(e, w, n, comm2) == pytest.approx(modularity(e, w, n, comm), abs=1e-12) and q2 == pytest.approx(q, abs=1e-12)
+
+
+def test_reference_fixture_against_the_restatement(ctx):
+    e = np.loadtxt(os.path.join(GOLDEN, "test115", "test.edgelist"), dtype=np.int64)[:, :2]
+    comm, nc, q, rounds = _device(ctx, e, None, 115)
+    _, _, r_q, r_rounds = sync_level1(e, None, 115)
+    print("device", nc, q, rounds, "restatement", r_q, r_rounds)
+    assert q >= r_q and rounds == r_rounds
