@@ -76,6 +76,14 @@ class EmbeddingView(C.Structure):
                 ("row_major", C.c_int)]
 
 
+class VectBProblem(C.Structure):
+    """cge_vect_b_problem (include/cge_hip_testing.h): one problem of the testing hook cge_vect_b_test."""
+    _fields_ = [("GD", C.c_void_p), ("Ta", C.c_void_p), ("Tb", C.c_void_p), ("comm", C.c_void_p), ("N", C.c_int64),
+                ("C", C.c_int64), ("vC", C.c_void_p), ("vectB", C.c_void_p), ("js_dev", C.c_void_p), ("js_fused", C.c_void_p)]
+
+
+VECT_B_GUARD = 64  # CGE_VECT_B_GUARD
+
 DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
 _NP_DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
 
@@ -611,6 +619,51 @@ class Context:
         x = _f64(x)
         out = np.empty_like(x)
         self._check(self.L.cge_pow_test(self.h, _p(x), C.c_int64(x.size), C.c_double(alpha), C.c_int(method), _p(out)))
+        return out
+
+    def vect_b_test(self, GD, Ta, Tb, comm, C_, directed=False, form=0, landmarks=False, vC=None, n_modes=1, second=None,
+                    vB=None):
+        """Testing hook (include/cge_hip_testing.h: cge_vect_b_test): vect_B of one problem by a named form of the sweep
+        (0 = what a sweep of this shape picks) and, with vC, its divergence by the device-side modes.  `second`: the
+        (GD, Ta, Tb, comm, C[, vC]) of form 6's other problem.  GD = None with vB and vC: the "JS only" mode.
+        Returns a dict: form_ran, vectB, guard (the doubles behind the vector on the device: all NaN unless something wrote
+        past its end), js_dev (3,), js_fused (n_modes,) for forms 5 and 6; second_* for form 6's other problem."""
+        keep, out = [], {}
+
+        def problem(GD, Ta, Tb, comm, C_, vC, vB, tag):
+            C_ = int(C_)
+            ln = C_ * C_ if directed else C_ * (C_ + 1) // 2
+            q = VectBProblem()
+            if GD is not None:
+                GD, Ta, Tb, comm = _f64(GD), _f64(Ta), _f64(Tb), _i64(comm)
+                q.N = GD.shape[0]
+                assert GD.shape == (q.N, q.N) and Ta.shape == Tb.shape == comm.shape == (q.N,)
+                vect = np.zeros(ln + VECT_B_GUARD)
+                q.GD, q.Ta, q.Tb, q.comm = (a.ctypes.data for a in (GD, Ta, Tb, comm))
+            else:
+                vect = _f64(vB).copy()
+                q.N = C_
+                assert vect.shape == (ln,) and vC is not None
+            q.C = C_
+            js_dev, js_fused = np.full(3, np.nan), np.full(2, np.nan)
+            if vC is not None:
+                vC = _f64(vC)
+                assert vC.shape == (ln,)
+                q.vC = vC.ctypes.data
+            q.vectB, q.js_dev, q.js_fused = vect.ctypes.data, js_dev.ctypes.data, js_fused.ctypes.data
+            keep.extend((GD, Ta, Tb, comm, vC, vect, js_dev, js_fused))
+            out[tag + "vectB"], out[tag + "guard"] = vect[:ln], vect[ln:]
+            out[tag + "js_dev"], out[tag + "js_fused"] = js_dev, js_fused[:n_modes]
+            return q
+
+        p1 = problem(GD, Ta, Tb, comm, C_, vC, vB, "")
+        p2 = None
+        if second is not None:
+            p2 = problem(*second[:5], second[5] if len(second) > 5 else None, None, "second_")
+        ran = C.c_int(-1)
+        self._check(self.L.cge_vect_b_test(self.h, C.byref(p1), C.byref(p2) if p2 is not None else None, C.c_int(int(directed)),
+                                           C.c_int(form), C.c_int(int(landmarks)), C.c_int(n_modes), C.byref(ran)))
+        out["form_ran"] = ran.value
         return out
 
     def segment_sort_test(self, z, offsets):

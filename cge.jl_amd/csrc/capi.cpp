@@ -450,6 +450,16 @@ int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method
     CGE_CATCH(c)
 }
 
+// testing hook (include/cge_hip_testing.h): vect_B by one named form of the sweep, and its divergence by the device-side modes
+int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_problem *p2, int directed, int form, int landmarks,
+                    int n_modes, int *form_ran) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !p || !form_ran || form < 0 || form > 6 || n_modes < 1 || n_modes > 2) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_vect_b_test(c, p, p2, directed != 0, form, landmarks, n_modes, form_ran);
+    CGE_CATCH(c)
+}
+
 // testing hook (include/cge_hip_testing.h): the per-group stable sort of the projections as runsplit calls it
 int cge_segment_sort_test(void *ctx, const double *z, const int32_t *task_row_off, int64_t T, double *zs_out, int32_t *perm_out) {
     cge_ctx *c = (cge_ctx *)ctx;

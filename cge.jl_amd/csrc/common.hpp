@@ -911,7 +911,8 @@ void k_fit_update_dir(cge_ctx *c, double *Tin, double *Tout, const double *Sin, 
                       const double *deg_in, const double *deg_out, i64 N, double delta, int *done, int *iters,
                       double *state /* [0]=eps,[1]=diff */);
 void k_bvec(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_pos, const i32 *cm_off,
-            const i32 *cm_mem, i64 N, i64 C, int directed, double *rowbins, double *vectB);
+            const i32 *cm_mem, i64 N, i64 C, int directed, double *rowbins, double *vectB, int form = 0);
+int k_bvec_form(const cge_ctx *c, i64 N); // the form k_bvec takes: 1 staged row bins, 2 plain gather, 3 contiguous rows, 4 tiles + bins
 void k_js(cge_ctx *c, const double *vC, const double *vB, i64 len, i64 C, int directed, int mode /*0 all,1 int,2 ext*/,
           double *out, double *partials = nullptr);
 void k_auc_landmark(cge_ctx *c, const double *Ta, const double *Tb, const i32 *v2l, const double *vw_orig,
@@ -1017,6 +1018,9 @@ struct AlphaBook {
     void take(const double *res, double alpha, i64 iters);
     void write(double out[7], int *out_len) const; // the reference's 7-vector (:256)
 };
+struct cge_vect_b_problem; // (include/cge_hip_testing.h)
+void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b_problem *p2, int directed, int form,
+                      int landmarks, int n_modes, int *form_ran); // the testing hook of vect_B's forms (wgcl_host.cpp)
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
                      const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],
                      int *out_len, cge_trace *trace, SweepHandoff *defer = nullptr);

@@ -575,11 +575,20 @@ void k_bvec_bins(cge_ctx *c, const i32 *cm_off, i64 N, i64 C, int directed, doub
     hipLaunchKernelGGL(bvec_bins_kernel, dim3(grid_for(C * C, 256, 1024)), dim3(256), 0, c->stream, c->sw_bt_part.p, cm_off,
                        c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, C, Nt, directed, vectB);
 }
+// The form k_bvec takes for the layout the context holds: 4 tiles + bins, 1 staged row bins, 3 contiguous rows, 2 plain gather
+int k_bvec_form(const cge_ctx *c, i64 N) {
+    if (c->opt_test_bvec_plain) return 2; // testing: the forms for score graphs beyond the LDS budget / 512 communities
+    if (c->bvec_blocks) return 4;
+    if (N * sizeof(double) <= 64 * 1024) return 1;
+    return c->bvec_contig ? 3 : 2;
+}
+// form 0: k_bvec_form's (every sweep); 1..4: that form (the testing hook cge_vect_b_test, which checks that it applies)
 void k_bvec(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_pos, const i32 *cm_off,
-            const i32 *cm_mem, i64 N, i64 C, int directed, double *rowbins, double *vectB) {
+            const i32 *cm_mem, i64 N, i64 C, int directed, double *rowbins, double *vectB, int form) {
     ScopedKernelTimer t(c, "bvec");
-    const int plain = c->opt_test_bvec_plain; // testing: the forms for score graphs beyond the LDS budget / 512 communities
-    if (c->bvec_blocks && !plain) {
+    const int plain = c->opt_test_bvec_plain;
+    if (form == 0) form = k_bvec_form(c, N);
+    if (form == 4) {
         const int Nt = (int)((N + 63) / 64);
         hipLaunchKernelGGL(bvec_tile_kernel, dim3((unsigned)Nt, (unsigned)Nt), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off, c->sw_bt_fc.p,
                            c->sw_bt_ns.p, c->sw_bt_base.p, N, Nt, directed, c->sw_bt_part.p);
@@ -587,10 +596,10 @@ void k_bvec(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, co
                            c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, C, Nt, directed, vectB);
         return;
     }
-    if (N * sizeof(double) <= 64 * 1024 && !plain)
+    if (form == 1)
         hipLaunchKernelGGL((bvec_rows_kernel<1>), dim3((unsigned)N), dim3(256), N * sizeof(double), c->stream, GD, Ta,
                            Tb, cm_off, cm_mem, cm_pos, N, C, directed, rowbins);
-    else if (c->bvec_contig && !plain)
+    else if (form == 3)
         hipLaunchKernelGGL(bvec_rows_contig_kernel, dim3((unsigned)N), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off, N, C,
                            directed, rowbins);
     else

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "../../include/cge_hip_testing.h"
 
 // the counter-based RNG of the sampler lives in common.hpp (the device draws the same stream)
 static inline uint64_t ctr_rand(uint64_t seed, uint64_t stream, uint64_t k, uint64_t attempt, uint64_t which) {
@@ -108,17 +109,14 @@ struct SweepLayout {
     DevBuf<i32> old2new; // (relabel) a vertex's number in the sweep
 };
 
-// The layout decision, the tile tables and the relabelled copies of the score graph's per-vertex arrays (G points at them then).
-static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay) {
-    const i64 N = G.N, C = G.C, d = G.d;
+// The layout decision from the communities alone (hcomm: 0-based, on the host): the community CSR, the tile tables (on the
+// device when the tiles apply), c->bvec_blocks / c->bvec_contig and, for a relabelled sweep, the order (lay.cm_mem) and its
+// inverse on the device.  landmarks: a landmark-mode sweep.  force_relabel: the testing hook's contiguous-row form below 8193
+// vertices (every sweep passes false).  Shared by plan_layout and the testing hook cge_vect_b_test.
+static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int directed, bool landmarks, bool force_relabel,
+                          SweepLayout &lay) {
     std::vector<i32> &cm_off = lay.cm_off, &cm_mem = lay.cm_mem;
     // community -> members CSR of the score graph
-    std::vector<i32> hcomm(N);
-    if (orig && orig->h_lcomm) std::memcpy(hcomm.data(), orig->h_lcomm, sizeof(i32) * N); // (the caller read them back for the diameter)
-    else {
-        HIP_CHECK(hipMemcpyAsync(hcomm.data(), G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-    }
     cm_off.assign(C + 1, 0);
     cm_mem.resize(N);
     for (i64 i = 0; i < N; i++) {
@@ -151,7 +149,7 @@ static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int dir
     // Every undirected landmark-mode sweep of >= 256 landmarks is relabelled and sums vect_B by tiles then, whichever form of the
     // fit runs (so that all forms add in the same order and give the same bits); the fused launch itself needs the default
     // persistent form with one tile per wave.
-    const bool tiles_req = orig != nullptr && !directed && c->opt_fit_fused && c->opt_exact_relabel && N >= 256 &&
+    const bool tiles_req = landmarks && !directed && c->opt_fit_fused && c->opt_exact_relabel && N >= 256 &&
                            C >= 2 && !c->opt_test_bvec_plain;
     const bool fuse_req = tiles_req && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
                           c->opt_pow_exp2 && k_fit_flow_fused_applies(c, N);
@@ -197,7 +195,7 @@ static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int dir
     }
     lay.fuse = fuse_req && blocks_ok && pieces_ok;
     if (!blocks_req && !tiles_req) blocks_ok = false;
-    lay.relabel = (N > 8192 && c->opt_exact_relabel) || blocks_ok;
+    lay.relabel = (N > 8192 && c->opt_exact_relabel) || blocks_ok || force_relabel;
     c->bvec_blocks = blocks_ok;
     c->bvec_contig = lay.relabel && N >= 64 * C; // a wave per (row, community) pays off for communities of a wave's width or more
     if (!lay.relabel) return;
@@ -209,6 +207,21 @@ static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int dir
     pk.add(d_order.p, cm_mem.data(), N);
     pk.add(lay.old2new.p, old2new.data(), N);
     pk.flush(); // (with the tile tables above)
+}
+
+// The layout decision, the tile tables and the relabelled copies of the score graph's per-vertex arrays (G points at them then).
+static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay) {
+    const i64 N = G.N, d = G.d;
+    std::vector<i32> hcomm(N);
+    if (orig && orig->h_lcomm) std::memcpy(hcomm.data(), orig->h_lcomm, sizeof(i32) * N); // (the caller read them back for the diameter)
+    else {
+        HIP_CHECK(hipMemcpyAsync(hcomm.data(), G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    layout_tables(c, hcomm.data(), N, G.C, directed, orig != nullptr, false, lay);
+    if (!lay.relabel) return;
+    const DevBuf<i32> &d_order = c->sw_rl_order;
+    std::vector<i32> &cm_mem = lay.cm_mem;
     c->sw_rl_emb.ensure((size_t)N * d);
     c->sw_rl_vec.ensure((size_t)4 * N);
     c->sw_rl_comm.ensure(N);
@@ -224,6 +237,19 @@ static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int dir
     for (i64 q = 0; q < N; q++) cm_mem[q] = (i32)q; // the member lists in the new numbering (the old ones sit in the staging buffer)
 }
 
+// The community tables of a layout for the device (sw_cm_off, sw_cm_mem, sw_cm_pos), on the caller's packer; cm_pos is the
+// caller's, since the packer reads it at its flush.  Shared by the sweep and the testing hook cge_vect_b_test.
+static void community_tables(cge_ctx *c, const SweepLayout &lay, i64 N, i64 C, WordPacker &pk, std::vector<i32> &cm_pos) {
+    c->sw_cm_off.ensure(C + 1);
+    c->sw_cm_mem.ensure(N);
+    pk.add(c->sw_cm_off.p, lay.cm_off.data(), C + 1);
+    pk.add(c->sw_cm_mem.p, lay.cm_mem.data(), N);
+    cm_pos.resize(N); // position of every vertex in the community-sorted list
+    for (i64 q = 0; q < N; q++) cm_pos[lay.cm_mem[q]] = (i32)q;
+    c->sw_cm_pos.ensure(N);
+    pk.add(c->sw_cm_pos.p, cm_pos.data(), N);
+}
+
 // D and its normalisation (:79-93 / :359-375), the community tables on the device, the starting T (:118) / Tin, Tout
 // (:399-402), and TT, the three parts T rotates through in an undirected sweep.  Returns TT's leading dimension.
 static i64 prepare_distances(cge_ctx *c, const ScoreGraph &G, const SweepLayout &lay, int directed) {
@@ -234,14 +260,8 @@ static i64 prepare_distances(cge_ctx *c, const ScoreGraph &G, const SweepLayout 
     k_minmax_upper(c, D, N, c->sw_lohi.p);
     k_normalise(c, D, N, c->sw_lohi.p);
     WordPacker pk(c);
-    c->sw_cm_off.ensure(C + 1);
-    c->sw_cm_mem.ensure(N);
-    pk.add(c->sw_cm_off.p, lay.cm_off.data(), C + 1);
-    pk.add(c->sw_cm_mem.p, lay.cm_mem.data(), N);
-    std::vector<i32> cm_pos(N); // position of every vertex in the community-sorted list
-    for (i64 q = 0; q < N; q++) cm_pos[lay.cm_mem[q]] = (i32)q;
-    c->sw_cm_pos.ensure(N);
-    pk.add(c->sw_cm_pos.p, cm_pos.data(), N);
+    std::vector<i32> cm_pos;
+    community_tables(c, lay, N, C, pk, cm_pos);
     const std::vector<double> ones(N, 1.0); // T (:118)
     if (!directed) { // (the directed sweep reads the degrees back first, below)
         pk.add(T1, ones.data(), N);
@@ -812,6 +832,173 @@ void AlphaBook::write(double out[7], int *out_len) const {
     *out_len = 7;
 }
 
+
+// ---- the testing hook of vect_B (include/cge_hip_testing.h: cge_vect_b_test) ------------------------------------------
+
+namespace {
+struct VbOptions { // the two options that choose vect_B's form, as the hook sets them for a forced form; restored on the way out
+    cge_ctx *c;
+    int blocks, plain;
+    explicit VbOptions(cge_ctx *c_) : c(c_), blocks(c_->opt_bvec_blocks), plain(c_->opt_test_bvec_plain) {}
+    ~VbOptions() { c->opt_bvec_blocks = blocks; c->opt_test_bvec_plain = plain; }
+};
+} // namespace
+
+static i64 vb_len(i64 C, int directed) { return directed ? C * C : packed_len(C); }
+
+// One problem as a sweep lays it out -- layout_tables, the host arrays permuted by its order (the sweep computes GD from permuted
+// rows), GD / Ta / Tb in sw_GD / sw_T1 / sw_T2, community_tables, k_bins_prepare -- after the checks of a forced form, which
+// come before anything is launched.  Returns the form to run.
+static int vb_prepare(cge_ctx *c, const cge_vect_b_problem &p, int directed, int form, bool landmarks) {
+    const i64 N = p.N, C = p.C;
+    if (form == 1 && N * sizeof(double) > 64 * 1024)
+        CGE_THROW(CGE_E_ARG, "vect_b_test: a row of %lld vertices does not fit the LDS of the staged row bins", (long long)N);
+    if (form >= 4 && (N < 256 || C < 2))
+        CGE_THROW(CGE_E_ARG, "vect_b_test: the tiles need 256 vertices and 2 communities (N = %lld, C = %lld)", (long long)N, (long long)C);
+    if (form == 2) c->opt_test_bvec_plain = 1;
+    else if (form != 0) { c->opt_test_bvec_plain = 0; c->opt_bvec_blocks = form >= 4; }
+    std::vector<i32> hcomm(N);
+    for (i64 i = 0; i < N; i++) {
+        if (p.comm[i] < 1 || p.comm[i] > C) CGE_THROW(CGE_E_ARG, "vect_b_test: community id out of range");
+        hcomm[i] = (i32)(p.comm[i] - 1);
+    }
+    SweepLayout lay;
+    layout_tables(c, hcomm.data(), N, C, directed, form == 0 && landmarks, form == 3, lay);
+    if (form >= 4 && !c->bvec_blocks)
+        CGE_THROW(CGE_E_ARG, "vect_b_test: the tiles decline this layout (more than 64 community ids in a 64-vertex block)");
+    const int run = form != 0 ? form : (c->bvec_blocks && !directed && !c->opt_test_bvec_plain) ? 5 : k_bvec_form(c, N);
+    hipStream_t st = c->stream;
+    c->sw_GD.ensure((size_t)N * N);
+    c->sw_T1.ensure(N); c->sw_T2.ensure(N);
+    c->sw_rowbins.ensure((size_t)N * C);
+    std::vector<double> hGD, hTa, hTb; // (relabelled) in the sweep's numbering
+    if (lay.relabel) {
+        const std::vector<i32> order = lay.cm_mem;
+        hGD.resize((size_t)N * N); hTa.resize(N); hTb.resize(N);
+        for (i64 q = 0; q < N; q++) {
+            const i64 a = order[q];
+            hTa[q] = p.Ta[a]; hTb[q] = p.Tb[a];
+            double *dst = hGD.data() + q * N;
+            if (directed)
+                for (i64 r = 0; r < N; r++) dst[r] = p.GD[a * N + order[r]];
+            else // the caller's upper triangle is the matrix
+                for (i64 r = 0; r < N; r++) {
+                    const i64 b = order[r];
+                    dst[r] = a <= b ? p.GD[a * N + b] : p.GD[b * N + a];
+                }
+        }
+        for (i64 q = 0; q < N; q++) lay.cm_mem[q] = (i32)q; // the member lists in the new numbering, as plan_layout leaves them
+    }
+    HIP_CHECK(hipMemcpyAsync(c->sw_GD.p, lay.relabel ? hGD.data() : p.GD, sizeof(double) * N * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->sw_T1.p, lay.relabel ? hTa.data() : p.Ta, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->sw_T2.p, lay.relabel ? hTb.data() : p.Tb, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    WordPacker pk(c);
+    std::vector<i32> cm_pos;
+    community_tables(c, lay, N, C, pk, cm_pos);
+    pk.flush();
+    if (c->bvec_blocks && !directed) k_bins_prepare(c, c->sw_cm_off.p, N, C, lay.bt_total);
+    HIP_CHECK(hipStreamSynchronize(st)); // (the host copies go out of scope)
+    return run;
+}
+
+// the block partials of a divergence added in block order, then halved: what AlphaBook::take and js_final_kernel do
+static double vb_fold(const double *fpart) {
+    double f = 0.0;
+    for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) f += fpart[b];
+    return f / 2.0;
+}
+
+void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b_problem *p2, int directed, int form,
+                      int landmarks, int n_modes, int *form_ran) {
+    const cge_vect_b_problem *probs[2] = {p1, form == 6 ? p2 : nullptr};
+    if ((form == 5 || form == 6) && directed) CGE_THROW(CGE_E_ARG, "vect_b_test: form %d is undirected only", form);
+    if (form == 6 && (!p2 || !p2->GD || p2->C >= p1->C)) CGE_THROW(CGE_E_ARG, "vect_b_test: form 6 takes a second problem of fewer communities");
+    for (const cge_vect_b_problem *p : probs) {
+        if (!p) continue;
+        if (p->N <= 0 || p->C <= 0 || !p->vectB) CGE_THROW(CGE_E_ARG, "vect_b_test: empty problem");
+        if (p->GD && (!p->Ta || !p->Tb || !p->comm)) CGE_THROW(CGE_E_ARG, "vect_b_test: Ta, Tb and comm go with GD");
+        if (p->vC && !p->js_dev) CGE_THROW(CGE_E_ARG, "vect_b_test: vC without js_dev");
+        if ((double)p->N * (double)p->C > 1e9) CGE_THROW(CGE_E_ARG, "vect_b_test: problem too large");
+    }
+    if (!p1->GD && (!p1->vC || form != 0)) CGE_THROW(CGE_E_ARG, "vect_b_test: the JS-only mode takes vC, vectB and form 0");
+    hipStream_t st = c->stream;
+    VbOptions restore(c);
+    const i64 G = CGE_VECT_B_GUARD;
+    const i64 len[2] = {vb_len(p1->C, directed), probs[1] ? vb_len(probs[1]->C, directed) : 0};
+    const i64 off[2] = {0, len[0] + G};
+    // both vectors back to back, each followed by a guard of NaNs that nothing may write
+    std::vector<double> hv((size_t)(len[0] + len[1] + 2 * G), std::nan(""));
+    if (!p1->GD) std::memcpy(hv.data(), p1->vectB, sizeof(double) * len[0]);
+    DevBuf<double> vB, vC, fpart, part, jsd;
+    vB.ensure(hv.size());
+    HIP_CHECK(hipMemcpyAsync(vB.p, hv.data(), sizeof(double) * hv.size(), hipMemcpyHostToDevice, st));
+    { // vect_C of both problems (zeros where the caller has none and the form reads one)
+        std::vector<double> hc((size_t)(len[0] + len[1]), 0.0);
+        for (int q = 0; q < 2; q++)
+            if (probs[q] && probs[q]->vC) std::memcpy(hc.data() + (q ? len[0] : 0), probs[q]->vC, sizeof(double) * len[q]);
+        vC.ensure(hc.size());
+        HIP_CHECK(hipMemcpyAsync(vC.p, hc.data(), sizeof(double) * hc.size(), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    const double *vCp[2] = {vC.p, vC.p + len[0]};
+    const int nm = n_modes == 2 ? 2 : 1;
+    fpart.ensure((size_t)4 * CGE_PARTIAL_BLOCKS);
+    int run = 0;
+    if (p1->GD && form != 6) {
+        run = vb_prepare(c, *p1, directed, form, landmarks != 0);
+        const i64 N = p1->N, C = p1->C;
+        if (run == 5) {
+            k_bvec_tiles(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, N, directed);
+            k_bins_js(c, c->sw_cm_off.p, N, C, vCp[0], vB.p, nm, fpart.p);
+        } else
+            k_bvec(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_pos.p, c->sw_cm_off.p, c->sw_cm_mem.p, N, C, directed,
+                   c->sw_rowbins.p, vB.p, run);
+    } else if (p1->GD) { // form 6: the tile partials of the first problem leave the context, as a batch member's do
+        run = 6;
+        DevBuf<i32> fc1, ns1, base1, off1;
+        DevBuf<double> part1;
+        vb_prepare(c, *p1, 0, 6, false);
+        k_bvec_tiles(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, p1->N, 0);
+        HIP_CHECK(hipStreamSynchronize(st));
+        fc1.swap(c->sw_bt_fc); ns1.swap(c->sw_bt_ns); base1.swap(c->sw_bt_base); part1.swap(c->sw_bt_part); off1.swap(c->sw_cm_off);
+        vb_prepare(c, *p2, 0, 6, false);
+        k_bvec_tiles(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, p2->N, 0);
+        cge_bins_multi bins{};
+        cge_js_multi js{};
+        bins.p[0] = cge_bins_problem{part1.p, off1.p, fc1.p, ns1.p, base1.p, p1->C, (int)((p1->N + 63) / 64), 0, vB.p + off[0]};
+        bins.p[1] = cge_bins_problem{c->sw_bt_part.p, c->sw_cm_off.p, c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, p2->C,
+                                     (int)((p2->N + 63) / 64), 0, vB.p + off[1]};
+        part.ensure((size_t)4 * 3 * CGE_PARTIAL_BLOCKS);
+        int nj = 0;
+        for (int q = 0; q < 2; q++)
+            for (int u = 0; u < nm; u++, nj++)
+                js.p[nj] = cge_js_problem{vCp[q], vB.p + off[q], len[q], probs[q]->C, nm == 1 ? 0 : 1 + u, 0,
+                                          part.p + (i64)nj * 3 * CGE_PARTIAL_BLOCKS, fpart.p + (i64)nj * CGE_PARTIAL_BLOCKS};
+        k_bins_js_multi(c, bins, 2, p1->C, js, nj);
+        HIP_CHECK(hipStreamSynchronize(st)); // (the first problem's tables are released below)
+    }
+    *form_ran = run;
+    std::vector<double> hf((size_t)4 * CGE_PARTIAL_BLOCKS, 0.0);
+    if (run >= 5) HIP_CHECK(hipMemcpyAsync(hf.data(), fpart.p, sizeof(double) * hf.size(), hipMemcpyDeviceToHost, st));
+    // k_js modes 0, 1, 2 over the vector(s) the form left
+    jsd.ensure(6);
+    double hj[6] = {0, 0, 0, 0, 0, 0};
+    for (int q = 0; q < 2; q++)
+        if (probs[q] && probs[q]->vC)
+            for (int mode = 0; mode < 3; mode++)
+                k_js(c, vCp[q], vB.p + off[q], len[q], probs[q]->C, directed, mode, jsd.p + 3 * q + mode);
+    HIP_CHECK(hipMemcpyAsync(hj, jsd.p, sizeof(hj), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hv.data(), vB.p, sizeof(double) * hv.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int q = 0; q < 2; q++) {
+        const cge_vect_b_problem *p = probs[q];
+        if (!p) continue;
+        if (p->GD) std::memcpy(p->vectB, hv.data() + off[q], sizeof(double) * (len[q] + G));
+        if (p->vC) std::memcpy(p->js_dev, hj + 3 * q, sizeof(double) * 3);
+        if (p->js_fused && run >= 5)
+            for (int u = 0; u < nm; u++) p->js_fused[u] = vb_fold(hf.data() + (i64)((run == 6 ? q * nm : 0) + u) * CGE_PARTIAL_BLOCKS);
+    }
+}
 
 // ---- small helpers ---------------------------------------------------------------------------------
 

@@ -33,6 +33,33 @@ int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int
 /* out[i] = (1 - x[i])^alpha on the device (host vectors): method 0 = the library pow, 1 = exp2(alpha * log2(1 - x)) with
  * the logarithm in double + float parts, as the alpha sweep computes GD = (1 - D)^alpha (src/divergence.jl:142-148) */
 int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method, double *out);
+/* kernel-level hook (needs the GPU): vect_B, the community-pair sums of P_ij = (Ta_i Tb_j) GD_ij (src/divergence.jl:226-234,
+ * :530-538), by ONE named form of the alpha sweep -- the sweep's own layout decision, tables and launch wrappers -- and the
+ * divergence of the result from vC by the device-side mode selection.
+ *   A problem: GD (N x N, row-major; the undirected forms read j >= i only), Ta, Tb (N; undirected callers pass one vector
+ *   twice), comm (N ids in 1..C, any vertex order, ids without a member allowed), optional vC (the vector's length).
+ *   vectB receives the vector (packed C (C + 1) / 2 undirected, C C directed) followed by CGE_VECT_B_GUARD doubles that sat
+ *   behind it on the device and must still be NaN.  With vC: js_dev[3] = k_js modes 0 (all bins), 1 (internal), 2 (external)
+ *   over the computed vector; forms 5 and 6 also give js_fused[n_modes] (n_modes 1: all bins; 2: internal, external) = the
+ *   block partials of the one-launch form added in block order, then halved, as the sweep's host does (js_fused may be NULL).
+ *   GD == NULL ("JS only", form 0): vectB is an input of the vector's length and only js_dev is computed.
+ * form 0: what a sweep of this shape picks with the context's options (landmarks != 0: a landmark-mode sweep, else exact mode);
+ *      1: staged row bins; 2: plain gather; 3: contiguous rows of the relabelled graph; 4: tiles + bins; 5: tiles + the bins
+ *      and the divergence in one launch; 6: tiles + the batch's bins / JS launches over two problems, p and p2 (p2->C < p->C;
+ *      p2 is read by this form only).  *form_ran = the form that ran.  A relabelled form permutes GD, Ta, Tb and comm by the
+ *      layout's order on the host, as the sweep computes GD from permuted rows.
+ * CGE_E_ARG, with a message and before any launch, where the form does not apply: form 1 with N > 8192; forms 4-6 with
+ * N < 256, C < 2 or more than 64 community ids in a 64-vertex block of the relabelled graph; forms 5, 6 directed. */
+#define CGE_VECT_B_GUARD 64
+typedef struct cge_vect_b_problem {
+    const double *GD, *Ta, *Tb;
+    const int64_t *comm;
+    int64_t N, C;
+    const double *vC;
+    double *vectB, *js_dev, *js_fused;
+} cge_vect_b_problem;
+int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_problem *p2, int directed, int form, int landmarks,
+                    int n_modes, int *form_ran);
 /* needs the GPU and a communicator (cge_comm_init_rccl; one rank is enough): host array -> device -> the in-library
  * ncclAllReduce (op 0 sum / 1 max of doubles, 2 sum of the words as int64) -> host */
 int cge_rccl_selftest(void *ctx, double *host_inout, int64_t count, int op);

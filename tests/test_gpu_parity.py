@@ -1043,6 +1043,8 @@ def test_draw_samples_are_non_edges(ctx, synth20k):
 
 
 def test_js_kernel(ctx, orc):
+    """cge_js against the oracle.  It filters vI on the host and launches mode 0 only: the device-side selection of the
+    internal / external bins (k_js modes 1 and 2, the one-launch forms) is covered by tests/test_gpu_vect_b.py."""
     rng = np.random.default_rng(0)
     for C, directed in ((7, False), (12, True), (64, False)):
         ln = C * C if directed else C * (C + 1) // 2

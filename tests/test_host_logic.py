@@ -69,6 +69,21 @@ def test_library_loads_and_exports_every_declared_symbol():
                 assert api.idx(n, i, j) == orc.idx(n, i, j)
 
 
+def test_vect_b_hook_is_declared_and_refuses_a_null_context():
+    """The kernel-level hook of vect_B's forms (tests/test_gpu_vect_b.py): among the declared symbols the export test walks, and
+    CGE_E_ARG for a null context or a null problem before anything touches a device."""
+    from cge.jl_amd import api
+
+    assert "cge_vect_b_test" in _declared("cge_hip_testing.h")
+    lib = api.load_library()
+    p, ran = api.VectBProblem(), C.c_int(-1)
+    assert C.sizeof(p) == 10 * 8  # cge_vect_b_problem: ten 8-byte fields
+    for form in (0, 1, 6):
+        assert lib.cge_vect_b_test(None, C.byref(p), None, 0, form, 0, 1, C.byref(ran)) == -7
+    assert lib.cge_vect_b_test(None, None, None, 0, 0, 0, 1, C.byref(ran)) == -7
+    assert ran.value == -1
+
+
 def test_create_fails_loudly_without_gpu():
     import torch
 
