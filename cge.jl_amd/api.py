@@ -76,6 +76,26 @@ class EmbeddingView(C.Structure):
                 ("row_major", C.c_int)]
 
 
+class GraphView(C.Structure):
+    """cge_graph_view (include/cge_hip.h): an edge list where and as its owner holds it."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("stride", C.c_int64), ("id_dtype", C.c_int), ("base", C.c_int),
+                ("w", C.c_void_p), ("w_dtype", C.c_int), ("on_device", C.c_int)]
+
+
+class VertexView(C.Structure):
+    """cge_vertex_view (include/cge_hip.h): community ids and (optionally) vertex weights where their owner holds them."""
+    _fields_ = [("comm", C.c_void_p), ("id_dtype", C.c_int), ("base", C.c_int), ("vweights", C.c_void_p), ("vw_dtype", C.c_int),
+                ("on_device", C.c_int)]
+
+
+class ResidentGraph(C.Structure):
+    """cge_resident_graph (include/cge_hip_testing.h)."""
+    _fields_ = [("n", C.c_int64), ("m", C.c_int64), ("n_comm_max", C.c_int64), ("n_comm16", C.c_int64), ("unit", C.c_int),
+                ("have", C.c_int), ("src", C.c_void_p), ("dst", C.c_void_p), ("comm", C.c_void_p), ("w", C.c_void_p),
+                ("vweight", C.c_void_p), ("comm16", C.c_void_p), ("cap_edges", C.c_int64), ("cap_vertices", C.c_int64),
+                ("cap_comm16", C.c_int64)]
+
+
 class VectBProblem(C.Structure):
     """cge_vect_b_problem (include/cge_hip_testing.h): one problem of the testing hook cge_vect_b_test."""
     _fields_ = [("GD", C.c_void_p), ("Ta", C.c_void_p), ("Tb", C.c_void_p), ("comm", C.c_void_p), ("N", C.c_int64),
@@ -86,6 +106,19 @@ VECT_B_GUARD = 64  # CGE_VECT_B_GUARD
 
 DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
 _NP_DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
+
+ID_I64, ID_I32 = 0, 1
+
+
+class _FromComm:
+    """`clusters=FROM_COMM`: the clusters parseargs builds from the communities (src/auxilary.jl:199-208), derived by the library
+    from the resident community vector (n_clusters = -1 of the C-ABI)."""
+
+    def __repr__(self):
+        return "FROM_COMM"
+
+
+FROM_COMM = _FromComm()
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
@@ -242,6 +275,126 @@ def embedding_view(x):
     return v, a
 
 
+def _as_described(x, int_ids, what):
+    """(owner, pointer, itemsize, element strides or None, dtype code, on_device) of a numpy array or torch tensor taken as it is:
+    ids are int32 / int64 (anything else becomes int64), reals float64 / float32 (anything else becomes float64)."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(x, torch.Tensor):
+        t = x.detach()
+        codes = {torch.int64: ID_I64, torch.int32: ID_I32} if int_ids else {torch.float64: DTYPE_F64, torch.float32: DTYPE_F32}
+        if t.dtype not in codes:
+            t = t.to(torch.int64 if int_ids else torch.float64)
+        return t, t.data_ptr(), t.element_size(), tuple(t.stride()), codes[t.dtype], int(t.is_cuda)
+    if isinstance(x, (int, np.integer)):
+        raise TypeError(f"{what}: a raw pointer is not a view")
+    a = np.asarray(x)
+    codes = ({np.dtype(np.int64): ID_I64, np.dtype(np.int32): ID_I32} if int_ids else
+             {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32})
+    if a.dtype not in codes:
+        a = np.asarray(a, dtype=np.int64 if int_ids else np.float64)
+    sz = a.dtype.itemsize
+    strides = None if any(b % sz for b in a.strides) else tuple(b // sz for b in a.strides)
+    return a, a.ctypes.data, sz, strides, codes[a.dtype], 0
+
+
+def _packed(owner):
+    """One packed (C-order) copy in the same dtype, where the owner lives."""
+    return owner.contiguous() if hasattr(owner, "contiguous") else np.ascontiguousarray(owner)
+
+
+def _flat_vector(x, int_ids, what):
+    """A 1-D (or (n, 1) / (1, n)) vector described in place when it has unit stride, packed once otherwise."""
+    owner, ptr, sz, strides, code, dev = _as_described(x, int_ids, what)
+    if owner.ndim == 2 and 1 in tuple(owner.shape):
+        owner = owner.reshape(-1)
+        owner, ptr, sz, strides, code, dev = _as_described(owner, int_ids, what)
+    if owner.ndim != 1 or owner.shape[0] < 1:
+        raise ValueError(f"{what}: a non-empty vector is expected")
+    if owner.shape[0] > 1 and (strides is None or strides[0] != 1):
+        owner = _packed(owner)
+        owner, ptr, sz, strides, code, dev = _as_described(owner, int_ids, what)
+    return owner, ptr, code, dev
+
+
+def graph_view(edge_index, weights=None, base=-1):
+    """(GraphView, owners, m) for an edge list described where it lies; needs no GPU.  Keep `owners` alive while the view is in use.
+
+    `edge_index`: a numpy array or a torch tensor (any device) of shape (2, m) -- PyG's edge_index -- or (m, 2) -- the reference's
+    `edges` --, int32 or int64; a (2, 2) array is taken as (2, m).  C- and F-ordered arrays, slices (`ei[:, 1:]`) and regular steps
+    are taken in place: the two endpoint columns and their common stride come from the array's strides.  One packed copy in the
+    same dtype is made only when no stride form fits (a negative or zero step); other dtypes become int64.  `weights`: m edge
+    weights, float64 / float32 (others become float64), in the same place (host / GPU) as the ids; None = an unweighted list.
+    `base`: 0 or 1, or -1 to decide it as parseargs does (the minimum id must be 0 or 1)."""
+    owner, ptr, sz, strides, code, dev = _as_described(edge_index, True, "graph_view")
+    if owner.ndim != 2 or 2 not in tuple(owner.shape) or 0 in tuple(owner.shape):
+        raise ValueError("graph_view: an edge list is a non-empty (2, m) or (m, 2) array")
+    rows = owner.shape[0] == 2  # (2, m): the endpoints are the two rows
+    m = int(owner.shape[1] if rows else owner.shape[0])
+
+    def form(strides):
+        if strides is None:
+            return None
+        col, step = (strides[0], strides[1]) if rows else (strides[1], strides[0])  # endpoint offset, step from edge to edge
+        if m == 1:
+            step = 1
+        return (col, step) if step >= 1 and col != 0 else None
+
+    f = form(strides)
+    if f is None:
+        owner = _packed(owner)
+        owner, ptr, sz, strides, code, dev = _as_described(owner, True, "graph_view")
+        f = form(strides)
+    g = GraphView()
+    g.src, g.dst, g.stride, g.id_dtype, g.base, g.on_device = ptr, ptr + f[0] * sz, f[1], code, int(base), dev
+    owners = [owner]
+    if weights is not None:
+        w, wptr, wcode, wdev = _flat_vector(weights, False, "graph_view: weights")
+        if w.shape[0] != m:
+            raise ValueError(f"graph_view: {w.shape[0]} weights for {m} edges")
+        if wdev != dev:
+            raise ValueError("graph_view: the ids and the weights must both be on the host or both on the GPU")
+        g.w, g.w_dtype = wptr, wcode
+        owners.append(w)
+    return g, owners, m
+
+
+def vertex_view(comm, vweights=None, base=-1):
+    """(VertexView, owners, n) for community ids (n, or (n, 1); int32 / int64; None leaves the resident ones) and vertex weights
+    (float64 / float32; None = derive them from the resident edge list, src/auxilary.jl:104-110), described where they lie."""
+    v = VertexView()
+    v.base = int(base)
+    owners, n, dev = [], None, None
+    if comm is not None:
+        c, ptr, code, dev = _flat_vector(comm, True, "vertex_view: comm")
+        v.comm, v.id_dtype, n = ptr, code, int(c.shape[0])
+        owners.append(c)
+    if vweights is not None:
+        w, wptr, wcode, wdev = _flat_vector(vweights, False, "vertex_view: vweights")
+        if n is not None and (w.shape[0] != n or wdev != dev):
+            raise ValueError("vertex_view: comm and vweights must have one length and one place (host or GPU)")
+        v.vweights, v.vw_dtype, n, dev = wptr, wcode, int(w.shape[0]), wdev
+        owners.append(w)
+    v.on_device = int(dev or 0)
+    return v, owners, n
+
+
+def clusters_of(comm):
+    """parseargs' clusters (src/auxilary.jl:199-208) of a community vector, in pure Python: one list of 1-based vertex ids per
+    community that occurs, ascending inside a cluster, clusters by ascending community id.  What FROM_COMM derives."""
+    groups = {}
+    for i, q in enumerate(np.asarray(comm).ravel().tolist()):
+        groups.setdefault(q, []).append(i + 1)
+    return [np.asarray(groups[q], dtype=np.int64) for q in sorted(groups)]
+
+
+def _cluster_args(clusters):
+    """(flat, off, n_clusters) as the C-ABI takes clusters; FROM_COMM: n_clusters = -1, no arrays."""
+    if clusters is FROM_COMM:
+        return None, None, -1
+    flat, off = _flatten_clusters(clusters if clusters is not None and len(clusters) else [])
+    return flat, off, len(off) - 1
+
+
 def _edge_cols(edges):
     e = np.asarray(edges, dtype=np.int64)
     if e.size == 0:
@@ -359,13 +512,7 @@ class Context:
         current torch stream has enqueued is finished first (unless that stream is the context's own)."""
         v, owner = embedding_view(x)
         if v.on_device:
-            import torch
-
-            if owner.device.index != self.device:
-                raise ValueError(f"embedding on {owner.device}, the context is on GPU {self.device}")
-            st = torch.cuda.current_stream(owner.device)
-            if self.stream is None or st.cuda_stream != self.stream:
-                st.synchronize()
+            self._sync_with(owner)
         return v, owner
 
     def set_embedding_view(self, x):
@@ -384,6 +531,66 @@ class Context:
         self._check(self.L.cge_resident_embedding_test(self.h, _p(out), C.c_int64(out.size), C.byref(r), C.byref(d), _p(ids)))
         return out, ids
 
+    def _sync_with(self, owner):
+        """A CUDA tensor handed to this context: it must live on the context's GPU, and what its current torch stream has
+        enqueued is finished first (unless that stream is the context's own)."""
+        import torch
+
+        if owner.device.index != self.device:
+            raise ValueError(f"tensor on {owner.device}, the context is on GPU {self.device}")
+        st = torch.cuda.current_stream(owner.device)
+        if self.stream is None or st.cuda_stream != self.stream:
+            st.synchronize()
+
+    def set_graph_view(self, edge_index, weights=None, n=0, base=-1):
+        """The edge list as held -- `api.graph_view(edge_index, weights, base)`: a (2, m) or (m, 2) int32 / int64 numpy array or
+        torch tensor, 0- or 1-based, on the host or on this GPU -- made the resident graph (cge_set_graph_view): the same resident
+        state as `set_graph` of the same edges.  n = 0: the vertex count is the maximum id.  Returns n."""
+        g, owners, m = graph_view(edge_index, weights, base)
+        if g.on_device:
+            for o in owners:
+                self._sync_with(o)
+        n_out = C.c_int64()
+        self._check(self.L.cge_set_graph_view(self.h, C.byref(g), C.c_int64(m), C.c_int64(int(n)), C.byref(n_out)))
+        self.m, self.n = m, n_out.value
+        del owners
+        return self.n
+
+    def set_vertex_view(self, comm, vweights=None, base=-1):
+        """Community ids (and vertex weights) as held (`api.vertex_view`); vweights=None derives them from the resident edge
+        list in the reference's order of addition (src/auxilary.jl:104-110)."""
+        v, owners, n = vertex_view(comm, vweights, base)
+        if n is None:
+            n = self.n
+        if v.on_device:
+            for o in owners:
+                self._sync_with(o)
+        self._check(self.L.cge_set_vertex_view(self.h, C.byref(v), C.c_int64(n)))
+        del owners
+
+    def vertex_weights(self):
+        """The resident vweight (n,), e.g. the derived one, for `wGCL`'s vweights argument (cge_vertex_weights)."""
+        out = np.empty(self.n)
+        self._check(self.L.cge_vertex_weights(self.h, _p(out), C.c_int64(self.n)))
+        return out
+
+    def resident_graph(self):
+        """Testing hook (include/cge_hip_testing.h: cge_resident_graph_test): what the context holds, copied from the device:
+        dict(n, m, unit, n_comm_max, src, dst (int32, 0-based), w (None for a unit list), comm, comm16, vweight (None when absent))."""
+        r = ResidentGraph()
+        self._check(self.L.cge_resident_graph_test(self.h, C.byref(r)))  # (the sizes)
+        n, m = r.n, r.m
+        src, dst = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        w = None if r.unit or not m else np.empty(m)
+        comm = np.empty(n, dtype=np.int32) if r.have & 1 else None
+        c16 = np.empty(r.n_comm16, dtype=np.uint16) if r.n_comm16 else None
+        vw = np.empty(n) if r.have & 2 else None
+        r.src, r.dst, r.w, r.comm, r.comm16, r.vweight = (None if a is None else a.ctypes.data for a in (src, dst, w, comm, c16, vw))
+        r.cap_edges, r.cap_vertices, r.cap_comm16 = m, n, r.n_comm16
+        self._check(self.L.cge_resident_graph_test(self.h, C.byref(r)))
+        return {"n": n, "m": m, "unit": bool(r.unit), "n_comm_max": r.n_comm_max, "src": src, "dst": dst, "w": w, "comm": comm,
+                "comm16": c16, "vweight": vw}
+
     def set_vertex_data(self, comm, vweights):
         cm = None if comm is None else _i64(np.asarray(comm).ravel())
         vw = None if vweights is None else _f64(vweights)
@@ -398,9 +605,9 @@ class Context:
 
     # ---- landmarks ----------------------------------------------------------------------------------
     def landmarks_run(self, clusters, land, forced, method, directed=False):
-        flat, off = _flatten_clusters(clusters)
+        flat, off, ncl = _cluster_args(clusters)
         N, ne, tr = C.c_int64(), C.c_int64(), C.c_int()
-        self._check(self.L.cge_landmarks_run(self.h, _p(flat), _p(off), C.c_int64(len(clusters)), C.c_int64(land),
+        self._check(self.L.cge_landmarks_run(self.h, _p(flat), _p(off), C.c_int64(ncl), C.c_int64(land),
                                              C.c_int64(forced), C.c_int(_method_code(method)),
                                              C.c_int(1 if directed else 0), C.byref(N), C.byref(ne), C.byref(tr)))
         self.N, self.n_ledges, self.truncated = N.value, ne.value, bool(tr.value)
@@ -427,9 +634,9 @@ class Context:
         return dii, embed, cluster.reshape(-1, 1), ledges, lw, lweight, v_to_l
 
     def runsplit(self, clusters, nland, forced, method):
-        flat, off = _flatten_clusters(clusters)
+        flat, off, ncl = _cluster_args(clusters)
         out = np.zeros(self.n, dtype=np.int64)
-        self._check(self.L.cge_runsplit(self.h, _p(flat), _p(off), C.c_int64(len(clusters)), C.c_int64(nland),
+        self._check(self.L.cge_runsplit(self.h, _p(flat), _p(off), C.c_int64(ncl), C.c_int64(nland),
                                         C.c_int64(forced), C.c_int(_method_code(method)), _p(out)))
         return out
 
@@ -491,9 +698,9 @@ class Context:
 
     def score(self, clusters, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000):
         """example/CGE_CLI.jl:10-24 on the resident inputs; land = -1 => exact mode."""
-        flat, off = _flatten_clusters(clusters if clusters else [])
+        flat, off, ncl = _cluster_args(clusters)
         a = ScoreArgs()
-        a.clusters_flat, a.clusters_off, a.n_clusters = _p(flat).value, _p(off).value, len(off) - 1
+        a.clusters_flat, a.clusters_off, a.n_clusters = getattr(_p(flat), "value", None), getattr(_p(off), "value", None), ncl
         a.land, a.forced, a.method = int(land), int(forced), _method_code(method)
         a.directed, a.split, a.seed, a.auc_samples = int(bool(directed)), int(bool(split)), int(seed), int(auc_samples)
         out = np.zeros(7)
@@ -532,9 +739,9 @@ class Context:
         b = EmbeddingBatch()
         b.embeddings = C.cast(ptrs, C.c_void_p).value
         b.K, b.d, b.on_device, b.row_major = K, int(d), int(on_device), int(bool(row_major) and on_device)
-        flat, off = _flatten_clusters(clusters if clusters else [])
+        flat, off, ncl = _cluster_args(clusters)
         a = ScoreArgs()
-        a.clusters_flat, a.clusters_off, a.n_clusters = _p(flat).value, _p(off).value, len(off) - 1
+        a.clusters_flat, a.clusters_off, a.n_clusters = getattr(_p(flat), "value", None), getattr(_p(off), "value", None), ncl
         a.land, a.forced, a.method = int(land), int(forced), _method_code(method)
         a.directed, a.split, a.seed, a.auc_samples = int(bool(directed)), int(bool(split)), int(seed), int(auc_samples)
         out = np.zeros((K, 7))
@@ -562,9 +769,9 @@ class Context:
                 raise ValueError(f"score_views: embedding {k} has {owner.shape[0]} rows, the resident graph {self.n} vertices")
             views[k] = v
             keep.append(owner)
-        flat, off = _flatten_clusters(clusters if clusters else [])
+        flat, off, ncl = _cluster_args(clusters)
         a = ScoreArgs()
-        a.clusters_flat, a.clusters_off, a.n_clusters = _p(flat).value, _p(off).value, len(off) - 1
+        a.clusters_flat, a.clusters_off, a.n_clusters = getattr(_p(flat), "value", None), getattr(_p(off), "value", None), ncl
         a.land, a.forced, a.method = int(land), int(forced), _method_code(method)
         a.directed, a.split, a.seed, a.auc_samples = int(bool(directed)), int(bool(split)), int(seed), int(auc_samples)
         out = np.zeros((K, 7))
@@ -879,6 +1086,23 @@ def score_batch(edges, eweights, vweights, comm, clusters, embeddings, land, for
     ctx.set_graph(edges, eweights, n)
     ctx.set_vertex_data(comm, vweights)
     return ctx.score_batch(embeddings, clusters, land, forced, method, directed, split, seed, auc_samples)
+
+
+def score_tensors(edge_index, embeddings, comm, land, forced=4, method="rss", directed=False, split=False, seed=-1,
+                  auc_samples=10000, weights=None, base=-1, ctx=None):
+    """The whole call on tensors as held: `edge_index` ((2, m) or (m, 2), int32 / int64, 0- or 1-based), one embedding or a list
+    of embeddings ((n, d); float64 / float32 / float16 / bfloat16), `comm` (n community ids) -- numpy arrays or torch tensors,
+    host or GPU.  The graph goes in as a view, the vertex weights and the clusters are derived by the library, the embeddings are
+    scored by `score_views`.  Returns the result vector (one embedding) or the list of vectors; traces in `ctx.last_traces`."""
+    ctx = ctx or default_context()
+    one = hasattr(embeddings, "shape") and len(embeddings.shape) == 2
+    members = [embeddings] if one else list(embeddings)
+    if not members:
+        raise ValueError("score_tensors: no embeddings")
+    ctx.set_graph_view(edge_index, weights, n=int(members[0].shape[0]), base=base)
+    ctx.set_vertex_view(comm, None, base=base)
+    res = ctx.score_views(members, FROM_COMM, land, forced, method, directed, split, seed, auc_samples)
+    return res[0] if one else res
 
 
 def draw_samples(ctx, seed, S, directed=False, n_sets=1):

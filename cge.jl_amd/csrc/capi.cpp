@@ -130,10 +130,38 @@ int cge_set_vertex_data(cge_ctx *c, const int64_t *comm, const double *vw, int64
     CGE_CATCH(c)
 }
 
+// the graph and vertex views (graph_host.cpp): cge_set_graph / cge_set_vertex_data above are shorthands for them
+int cge_graph_view_check(const cge_graph_view *g, int64_t m, char *err, int64_t err_len) {
+    std::string msg;
+    const int rc = graph_view_check(g, m, msg);
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", msg.c_str());
+    return rc;
+}
+int cge_set_graph_view(cge_ctx *c, const cge_graph_view *g, int64_t m, int64_t n, int64_t *n_out) {
+    if (!c || !g) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    set_graph_view(c, "set_graph_view", g, m, n);
+    if (n_out) *n_out = c->n;
+    CGE_CATCH(c)
+}
+int cge_set_vertex_view(cge_ctx *c, const cge_vertex_view *v, int64_t n) {
+    if (!c || !v) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    set_vertex_view(c, "set_vertex_view", v, n, true);
+    CGE_CATCH(c)
+}
+int cge_vertex_weights(cge_ctx *c, double *out, int64_t n) {
+    if (!c || !out) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    if (!c->vw.p || n != c->n || (i64)c->h_vw.size() != n) CGE_THROW(CGE_E_ARG, "vertex_weights: no vertex weights of %lld vertices are resident", (long long)n);
+    memcpy(out, c->h_vw.data(), sizeof(double) * (size_t)n);
+    CGE_CATCH(c)
+}
+
 // ---- landmarks ------------------------------------------------------------------------------------
 int cge_landmarks_run(cge_ctx *c, const int64_t *cl_flat, const int64_t *cl_off, int64_t ncl, int64_t land,
                       int64_t forced, int method, int directed, int64_t *N_out, int64_t *n_ledges_out, int *truncated) {
-    if (!c || !cl_flat || !cl_off) return CGE_E_ARG;
+    if (!c || (ncl != -1 && (!cl_flat || !cl_off))) return CGE_E_ARG; // (n_clusters = -1: derived from the resident communities)
     CGE_TRY_ON_DEVICE(c)
     host_landmarks_run(c, LandmarkRun{cl_flat, cl_off, ncl, land, forced, method, directed, true});
     if (N_out) *N_out = c->N;
@@ -519,6 +547,37 @@ int cge_resident_embedding_test(void *ctx, double *out, int64_t capacity_doubles
     HIP_CHECK(hipStreamSynchronize(c->stream));
     if (ids_out)
         for (i64 i = 0; i < nl; i++) ids_out[i] = c->rows_sharded ? c->h_loc2glob[i] : (i32)i;
+    CGE_CATCH(c)
+}
+
+// testing hook (include/cge_hip_testing.h): the resident graph and vertex data themselves, copied from the DEVICE tables
+int cge_resident_graph_test(void *ctx, cge_resident_graph *o) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !o) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    const bool graph = c->src.p && c->dst.p && c->m > 0;
+    o->n = c->n;
+    o->m = graph ? c->m : 0;
+    o->unit = graph && c->unit_weights ? 1 : 0;
+    o->n_comm_max = c->comm.p ? c->n_comm_max : 0;
+    o->n_comm16 = c->comm16.p ? (i64)c->comm16.n : 0;
+    o->have = (c->comm.p ? 1 : 0) | (c->vw.p ? 2 : 0);
+    const size_t m = (size_t)o->m, n = (size_t)c->n;
+    if (((o->src || o->dst || o->w) && o->cap_edges < o->m) || ((o->comm || o->vweight) && o->cap_vertices < o->n) ||
+        (o->comm16 && o->cap_comm16 < o->n_comm16))
+        CGE_THROW(CGE_E_ARG, "resident graph: n = %lld, m = %lld, %lld comm16 entries do not fit the buffers", (long long)o->n,
+                  (long long)o->m, (long long)o->n_comm16);
+    if (o->src && m) HIP_CHECK(hipMemcpyAsync(o->src, c->src.p, sizeof(i32) * m, hipMemcpyDeviceToHost, c->stream));
+    if (o->dst && m) HIP_CHECK(hipMemcpyAsync(o->dst, c->dst.p, sizeof(i32) * m, hipMemcpyDeviceToHost, c->stream));
+    if (o->w && m && !o->unit) {
+        if (!c->w.p || c->h_w.size() != m) CGE_THROW(CGE_E_ARG, "resident graph: a weighted list without its weights or their host mirror");
+        HIP_CHECK(hipMemcpyAsync(o->w, c->w.p, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (o->comm && c->comm.p) HIP_CHECK(hipMemcpyAsync(o->comm, c->comm.p, sizeof(i32) * n, hipMemcpyDeviceToHost, c->stream));
+    if (o->comm16 && c->comm16.p)
+        HIP_CHECK(hipMemcpyAsync(o->comm16, c->comm16.p, sizeof(unsigned short) * c->comm16.n, hipMemcpyDeviceToHost, c->stream));
+    if (o->vweight && c->vw.p) HIP_CHECK(hipMemcpyAsync(o->vweight, c->vw.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
     CGE_CATCH(c)
 }
 

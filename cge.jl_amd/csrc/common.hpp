@@ -647,8 +647,23 @@ bool cge_reduce_scatter_dev(cge_ctx *c, double *buf, i64 words_per_rank);
 bool cge_exchange_fits(cge_ctx *c, size_t need);
 
 // ---- graph_host.cpp: the resident graph and vertex data (what cge_set_graph / cge_set_vertex_data do; they throw) ---------------
+// ONE ingest each: a cge_graph_view / cge_vertex_view (include/cge_hip.h); `who` names the entry point in messages.  set_graph /
+// set_vertex_data are the views of their arguments (1-based int64 host columns, fp64 weights).
+int graph_view_check(const cge_graph_view *g, i64 m, std::string &msg); // cge_graph_view_check; the message in `msg`
+void set_graph_view(cge_ctx *c, const char *who, const cge_graph_view *g, i64 m, i64 n); // n = 0: the maximum id; c->n afterwards
+// derive_vw: vweights == NULL means "derive them from the resident edge list" (else: leave the resident ones)
+void set_vertex_view(cge_ctx *c, const char *who, const cge_vertex_view *v, i64 n, bool derive_vw);
 void set_graph(cge_ctx *c, const int64_t *src, const int64_t *dst, const double *w, i64 m, i64 n);
 void set_vertex_data(cge_ctx *c, const int64_t *comm, const double *vw, i64 n);
+// clusters::Vector{Vector{Int}} of the resident communities (src/auxilary.jl:199-208), flat + offsets, 1-based ids (n_clusters = -1)
+void clusters_from_comm(const cge_ctx *c, std::vector<i64> &flat, std::vector<i64> &off);
+// kernels_graph.hip: a device-resident graph view made into the resident tables (ids: CGE_ID_*, stride in elements)
+void k_id_extrema(cge_ctx *c, const void *a, const void *b, i64 stride, int id_dtype, i64 count, i64 *d_minmax); // b may be NULL
+void k_graph_ingest(cge_ctx *c, const void *src, const void *dst, i64 stride, int id_dtype, i64 base, i64 n, const void *w, int w_dtype,
+                    i64 m, i32 *osrc, i32 *odst, double *ow, i64 *flags); // flags[0] lowest bad edge (m: none), flags[1] some weight != 1
+void k_vertex_ingest(cge_ctx *c, const void *ids, int id_dtype, i64 base, i64 n, i32 *comm, unsigned short *comm16);
+void k_vertex_weights_unit(cge_ctx *c, const i32 *src, const i32 *dst, i64 m, i64 n, double *vw);
+void k_vertex_weights_ordered(cge_ctx *c, const i32 *src, const i32 *dst, const double *w, i64 m, i64 n, double *vw);
 void check_resident(cge_ctx *c, const char *who); // graph, embedding and vertex data resident and sized for one vertex set
 
 // ---- embedding_host.cpp: everything that makes an embedding resident ----------------------------------------------------------

@@ -1664,6 +1664,12 @@ void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i
                    std::vector<i64> &group_ids, bool want_index) {
     if (!c->Xr.p || c->Xr.n < (size_t)(lm_rows(c) * c->d) || (i64)c->h_vw.size() != c->n)
         CGE_THROW(CGE_E_ARG, "runsplit: embedding / vertex weights are not resident");
+    std::vector<i64> derived_flat, derived_off; // n_clusters = -1: the clusters parseargs builds from the resident communities
+    if (ncl == -1) {
+        clusters_from_comm(c, derived_flat, derived_off);
+        cl_flat = derived_flat.data(); cl_off = derived_off.data(); ncl = (i64)derived_off.size() - 1;
+    } else if (!cl_flat || !cl_off || ncl < 0)
+        CGE_THROW(CGE_E_ARG, "runsplit: no clusters (pass them, or n_clusters = -1 to derive them from the resident communities)");
     GroupPool pool;
     Heap H;
     std::vector<i64> order;

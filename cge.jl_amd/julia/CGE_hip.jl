@@ -99,6 +99,70 @@ function set_embedding!(c::Ctx, embedding::Matrix{T}) where {T<:Union{Float64,Fl
     end
 end
 
+# cge_graph_view / cge_vertex_view (include/cge_hip.h): the edge list and the vertex data as their owner holds them
+struct GraphView
+    src::Ptr{Cvoid}
+    dst::Ptr{Cvoid}
+    stride::Int64    # in elements: 1 = two columns (a Julia m x 2 Matrix: dst = src + m elements)
+    id_dtype::Cint   # 0 Int64, 1 Int32
+    base::Cint       # 0, 1, or -1 = the minimum id must be 0 or 1 (src/auxilary.jl:92-98)
+    w::Ptr{Cvoid}    # C_NULL = an unweighted list
+    w_dtype::Cint    # 0 Float64, 1 Float32
+    on_device::Cint
+end
+struct VertexView
+    comm::Ptr{Cvoid}
+    id_dtype::Cint
+    base::Cint
+    vweights::Ptr{Cvoid}   # C_NULL = derive them from the resident edge list (src/auxilary.jl:104-110)
+    vw_dtype::Cint
+    on_device::Cint
+end
+id_dtype(::Type{Int64}) = Cint(0)
+id_dtype(::Type{Int32}) = Cint(1)
+
+# The edge list as held (an m x 2 Matrix of Int64 or Int32, 0- or 1-based); n = 0: the maximum id.  Returns n.
+function set_graph_view!(c::Ctx, edges::Matrix{T}, weights::Union{Nothing,Vector{W}} = nothing; n::Integer = 0,
+                         base::Integer = -1) where {T<:Union{Int64,Int32},W<:Union{Float64,Float32}}
+    m = size(edges, 1)
+    n_out = Ref{Int64}(0)
+    GC.@preserve edges weights begin
+        w = weights === nothing ? C_NULL : Ptr{Cvoid}(pointer(weights))
+        g = GraphView(pointer(edges), pointer(edges, m + 1), 1, id_dtype(T), base, w,
+                      weights === nothing ? Cint(0) : view_dtype(W), 0)
+        check(c, ccall((:cge_set_graph_view, LIB), Cint, (Ptr{Cvoid}, Ref{GraphView}, Int64, Int64, Ref{Int64}),
+                       c.h, Ref(g), m, n, n_out))
+    end
+    return n_out[]
+end
+
+# Communities as held; the vertex weights are derived by the library when `vweights` is nothing.
+function set_vertex_view!(c::Ctx, comm::Array{T}, vweights::Union{Nothing,Vector{Float64}} = nothing;
+                          base::Integer = -1) where {T<:Union{Int64,Int32}}
+    n = length(comm)
+    GC.@preserve comm vweights begin
+        vw = vweights === nothing ? C_NULL : Ptr{Cvoid}(pointer(vweights))
+        v = VertexView(pointer(comm), id_dtype(T), base, vw, 0, 0)
+        check(c, ccall((:cge_set_vertex_view, LIB), Cint, (Ptr{Cvoid}, Ref{VertexView}, Int64), c.h, Ref(v), n))
+    end
+end
+
+# the resident vweight (e.g. the derived one), for wGCL's `vweights` argument
+function vertex_weights(c::Ctx, n::Integer)
+    out = Vector{Float64}(undef, n)
+    check(c, ccall((:cge_vertex_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), c.h, out, n))
+    return out
+end
+
+# clusters derived from the resident communities (src/auxilary.jl:199-208): n_clusters = -1, the two pointers are ignored
+function landmarks_run_from_comm!(c::Ctx, land::Int, forced::Int, method::Function, directed::Bool)
+    N, ne, trunc = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)
+    check(c, ccall((:cge_landmarks_run, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int64, Int64, Int64, Cint, Cint, Ref{Int64}, Ref{Int64}, Ref{Cint}),
+                   c.h, C_NULL, C_NULL, -1, land, forced, method_code(method), directed, N, ne, trunc))
+    return N[], ne[], trunc[] != 0
+end
+
 """
     landmarks(edges, weights, vweights, clusters, comm, embedding, verbose, land, forced, method, directed)
 

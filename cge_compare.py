@@ -44,6 +44,8 @@ def read_any_embedding(path, n):
 
 
 def main(argv=None):
+    import numpy as np
+
     import cge.jl_amd as CGE
     from cge.jl_amd import api
     from cge_cli import julia_vector
@@ -57,9 +59,11 @@ def main(argv=None):
     n = embed.shape[0]
     embeddings = [embed] + [read_any_embedding(f, n) for f in files[1:]]  # (text: the library's parallel reader)
     ctx = api.default_context()
-    ctx.set_graph(edges, weights, n)
-    ctx.set_vertex_data(comm, vweights)
-    results = ctx.score_views(embeddings, clusters, land, forced, method, directed, split, seed, samples)
+    # parseargs' arrays as they are; vweight (src/auxilary.jl:104-110) and the clusters (:199-208) are derived by the library
+    # from what is resident -- the same bits and the same clusters as parseargs' own, without its host passes over them
+    ctx.set_graph_view(np.asarray(edges), np.asarray(weights, dtype=np.float64), n=n, base=1)
+    ctx.set_vertex_view(comm, None, base=1)
+    results = ctx.score_views(embeddings, api.FROM_COMM, land, forced, method, directed, split, seed, samples)
     for f, r in zip(files, results):
         print(f"{f}\t{julia_vector(r)}")
     return 0

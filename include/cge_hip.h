@@ -145,14 +145,67 @@ int cge_embedding_view_check(const cge_embedding_view *v, int64_t n, char *err, 
 /* Makes the view the resident embedding (cge_set_embedding / cge_set_embedding_device are shorthands for it).  A device view whose
  * pointer is not device memory, or lies on another GPU than the context's (the kernels dereference it there): CGE_E_ARG. */
 int cge_set_embedding_view(cge_ctx *ctx, const cge_embedding_view *v, int64_t n);
-/* comm::Matrix{Int} n x 1 (src/auxilary.jl:122-139) and vweight (src/auxilary.jl:104-110) */
+/* comm::Matrix{Int} n x 1 (src/auxilary.jl:122-139) and vweight (src/auxilary.jl:104-110).  A shorthand for cge_set_vertex_view
+ * (below) of {comm, CGE_ID_I64, base 1, vweights, CGE_DTYPE_F64, host}, except that NULL vweights leave the resident ones. */
 int cge_set_vertex_data(cge_ctx *ctx, const int64_t *comm, const double *vweights, int64_t n);
+
+/* ---- graph views: the edge list and the vertex data AS THE CALLER HOLDS THEM ------------------------------------------------
+ * What parseargs does to an edge file between `readdlm` and landmarks() (src/auxilary.jl:86-139), for arrays instead of text: a
+ * PyG-style edge_index (2 x m, int32 or int64, 0-based, in GPU memory) is described in place, rebased, checked and narrowed by
+ * the library, and vweight (the per-edge scatter of :104-110) and the clusters (:199-208) are derived from what is resident.
+ * cge_set_graph / cge_set_vertex_data are shorthands for the views of their arguments: there is one ingest.                   */
+#define CGE_ID_I64 0
+#define CGE_ID_I32 1
+typedef struct {
+    const void *src, *dst;  /* endpoint of edge e: src[e * stride], dst[e * stride], in ELEMENTS */
+    int64_t stride;         /* 1: two columns, or the two rows of a (2, m) tensor; 2: an (m, 2) C-order array (dst = src + 1); any value >= 1 */
+    int id_dtype;           /* CGE_ID_* */
+    int base;               /* 0 or 1; -1 = decided as parseargs does: the minimum id must be 0 or 1 (src/auxilary.jl:92-98) */
+    const void *w;          /* eweights; NULL = an unweighted list (unit weights, :105) */
+    int w_dtype;            /* CGE_DTYPE_F64 or CGE_DTYPE_F32 (widening is exact); F16 / BF16 are CGE_E_ARG */
+    int on_device;          /* 0: host, borrowed for the call; 1: this GPU's memory, copied -- all pointers of a view in one place */
+} cge_graph_view;
+/* Is `g` a well-formed view of m edges?  Needs no context and no GPU.  CGE_E_ARG (and a message in `err`, optional) for a NULL
+ * view, NULL src / dst, m <= 0, stride < 1, an unknown id or weight dtype (F16 / BF16 weights included), a base outside
+ * {-1, 0, 1}, a pointer that is not aligned to its element, and src / dst ranges that overlap otherwise than as the two
+ * interleaved columns their stride describes. */
+int cge_graph_view_check(const cge_graph_view *g, int64_t m, char *err, int64_t err_len);
+/* Makes the view the resident graph: afterwards the context holds, bit for bit, what cge_set_graph leaves for the same edges
+ * given as 1-based int64 columns with fp64 weights (0-based int32 ids, the unit-weight verdict, the weights and their host
+ * mirror), so every result downstream is the same.  n = 0: the number of vertices is the maximum id (:99); *n_out (optional)
+ * receives it.  All checks are made on the 64-bit ids before they are narrowed and before anything is indexed by one:
+ * base = -1 and a minimum other than 0 or 1 is CGE_E_ASSERT "Vertices should be either 0-based or 1-based" (:93); an id outside
+ * the vertex range is CGE_E_ARG naming the lowest offending edge (1-based row).  After such an error NO graph is resident.
+ * A device view is rebased, checked, narrowed and widened by kernels (only scalars, and the weights' host mirror of a weighted
+ * list, come back); a pointer that is not memory of the context's GPU is CGE_E_ARG; it is not ingest-sharded (as
+ * cge_set_embedding_device).  A host view goes through the staging workers of cge_set_graph, option shard_ingest included. */
+int cge_set_graph_view(cge_ctx *ctx, const cge_graph_view *g, int64_t m, int64_t n /* 0 = maximum id, :99 */, int64_t *n_out);
+
+typedef struct {
+    const void *comm;       /* n community ids, or NULL (leave the resident ones) */
+    int id_dtype, base;     /* as above; base -1 = minimum must be 0 or 1 (:133-139) */
+    const void *vweights;   /* n vertex weights; NULL = DERIVE them from the resident edge list (:104-110) */
+    int vw_dtype;           /* F64 / F32 */
+    int on_device;
+} cge_vertex_view;
+/* comm (src/auxilary.jl:122-139) rebased, checked (>= 1 after rebasing, CGE_E_ARG otherwise; base = -1 and a minimum other than
+ * 0 or 1: CGE_E_ASSERT "Communities should be either 0-based or 1-based", :134) and narrowed into the tables cge_set_vertex_data
+ * builds.  vweights == NULL: vweight[v] = the weights of v's incident edges added in edge order starting from 0.0, an edge
+ * counting for its source and then for its target (a self-loop twice in a row), i.e. the bits of the loop at :107-110; an
+ * isolated vertex gets 0.0.  Needs the resident graph (of n vertices) whole on this rank: on an edge list sharded over the ranks
+ * (option shard_ingest) the derivation is CGE_E_ARG -- a sum in edge order cannot be put together from per-rank partial sums. */
+int cge_set_vertex_view(cge_ctx *ctx, const cge_vertex_view *v, int64_t n);
+/* the resident vweight (n doubles), for callers of the reference-shaped entries (cge_wgcl takes vweights as an argument) */
+int cge_vertex_weights(cge_ctx *ctx, double *out, int64_t n);
 
 /* ---- landmarks(): src/landmarks.jl:365-466 --------------------------------------------------- */
 /* clusters::Vector{Vector{Int}} as CSR: members clusters_flat[off[c] .. off[c+1]) (1-based ids).
  * Runs on the resident inputs; results stay on the device (for cge_wgcl / cge_score) and can be
  * fetched.  `*N_out` = number of landmarks, `*n_ledges_out` = rows of landmark_edges (w > 0),
- * `*truncated` = 1 when the reference's @warn at :374 would have fired.                          */
+ * `*truncated` = 1 when the reference's @warn at :374 would have fired.
+ * n_clusters == -1 (here, in cge_runsplit and in cge_score_args): the clusters are DERIVED from the resident communities as
+ * parseargs builds them (src/auxilary.jl:199-208) -- one cluster per community that occurs, members in ascending vertex id;
+ * the two pointers are ignored (runsplit orders the clusters itself, so their order is immaterial).                        */
 int cge_landmarks_run(cge_ctx *ctx, const int64_t *clusters_flat, const int64_t *clusters_off, int64_t n_clusters,
                       int64_t land, int64_t forced, int method, int directed, int64_t *N_out,
                       int64_t *n_ledges_out, int *truncated);

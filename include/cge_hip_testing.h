@@ -81,6 +81,21 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value);
  * local order, with their global 0-based ids in ids_out, which may be NULL otherwise).  *rows and *d are set first; a capacity
  * below rows * d doubles (or a NULL out) returns CGE_E_ARG with them set, so a caller can ask for the sizes */
 int cge_resident_embedding_test(void *ctx, double *out, int64_t capacity_doubles, int64_t *rows, int64_t *d, int32_t *ids_out);
+/* needs the GPU: the resident graph and vertex data as this rank holds them, so that the tests of the graph views compare every
+ * element and not a score.  The sizes come first (always set): n, m (edges held by this rank), unit (1 = an unweighted list: no
+ * weights are kept), n_comm_max, n_comm16 (entries of the padded uint16 community table, 0 = none), have (bit 0 communities, bit
+ * 1 vertex weights resident).  Every array pointer may be NULL (not copied); the capacities are in elements and a pointer whose
+ * capacity is too small is CGE_E_ARG.  src / dst: m 0-based int32 ids; w: m doubles (not written for a unit list); comm: n
+ * 0-based int32; comm16: n_comm16 entries; vweight: n doubles */
+typedef struct cge_resident_graph {
+    int64_t n, m, n_comm_max, n_comm16;
+    int unit, have;
+    int32_t *src, *dst, *comm;
+    double *w, *vweight;
+    uint16_t *comm16;
+    int64_t cap_edges, cap_vertices, cap_comm16;
+} cge_resident_graph;
+int cge_resident_graph_test(void *ctx, cge_resident_graph *out);
 #ifdef __cplusplus
 }
 #endif
