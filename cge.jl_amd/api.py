@@ -809,6 +809,28 @@ class Context:
         self._check(self.L.cge_group_eig(self.h, _p(A), C.c_int64(T), C.c_int64(d), _p(v)))
         return v
 
+    def group_stats_test(self, ids, offsets, side=None, mean_in=None):
+        """Testing hook (include/cge_hip_testing.h: cge_group_stats_test): the statistics stage of a landmark split for groups of
+        the resident rows (0-based ids back to back, offsets (T + 1,)) by the split's own batch builder and launch wrappers.
+        mean_in (T, d): the groups' means are given (gathered, not computed; sw is NaN then).  side (R,) of 0 / 1 / 2: also the
+        side sums.  Returns a dict: mean (T, d), sw (T,), cov (T, d, d), vec (T, d), z (R,), sums (T, 2, 2 d + 1) or None."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        T, d = off.size - 1, self.d
+        assert T >= 1 and off[0] == 0 and off[-1] == ids.size
+        mean, sw, cov = np.empty((T, d)), np.full(T, np.nan), np.empty((T, d, d))
+        vec, z, sums = np.empty((T, d)), np.empty(ids.size), None
+        if side is not None:
+            side = np.ascontiguousarray(side, dtype=np.uint8)
+            assert side.shape == ids.shape
+            sums = np.empty((T, 2, 2 * d + 1))
+        if mean_in is not None:
+            mean_in = _f64(mean_in)
+            assert mean_in.shape == (T, d)
+        self._check(self.L.cge_group_stats_test(self.h, _p(ids), _p(off), C.c_int64(T), _p(side), _p(mean_in), _p(mean), _p(sw),
+                                                _p(cov), _p(vec), _p(z), _p(sums)))
+        return {"mean": mean, "sw": sw, "cov": cov, "vec": vec, "z": z, "sums": sums}
+
     def diameter_bounds_test(self, v_to_l, N, lcomm, C_, pass_):
         """Testing hook: the bound matrix of the pruned diameter for a landmark assignment (1-based ids) by one named pass
         (0 fp64, 1 f32, 2 bf16 split).  Returns (P (N, nref), pass that ran, reference points (nref, d), centring mean (d,))."""

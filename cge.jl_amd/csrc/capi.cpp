@@ -460,6 +460,16 @@ int cge_group_eig(void *ctx, const double *A, int64_t T, int64_t d, double *v) {
     CGE_CATCH(c)
 }
 
+// testing hook (include/cge_hip_testing.h): the statistics stage of a split and the side sums, for caller-supplied groups
+int cge_group_stats_test(void *ctx, const int32_t *ids, const int32_t *task_row_off, int64_t T, const uint8_t *side, const double *mean_in,
+                         double *mean, double *sw, double *cov, double *vec, double *z, double *sums) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !ids || !task_row_off || T <= 0 || !mean || !cov || !vec || !z || (!mean_in && !sw) || (side && !sums)) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_group_stats_test(c, ids, task_row_off, T, side, mean_in, mean, sw, cov, vec, z, sums);
+    CGE_CATCH(c)
+}
+
 // testing hook (include/cge_hip_testing.h): the gather and one bound pass of the pruned diameter
 int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int64_t *lcomm, int64_t C, int pass, double *P,
                              int64_t *nref, int *pass_ran, double *ref_points, double *mean) {

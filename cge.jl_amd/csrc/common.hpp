@@ -944,6 +944,8 @@ void k_mark_edge_hits(cge_ctx *c, const i32 *src, const i32 *dst, i64 m, int dir
 void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
                    std::vector<i64> &group_ids /*0-based*/, bool want_index = false); // also fills c->v2l / lm_mem / lm_memoff (device)
 void host_eig_top(const double *A, i64 d, double *v); // largest-eigenvalue eigenvector, sign: max |.| component > 0
+void host_group_stats_test(cge_ctx *c, const i32 *ids, const i32 *task_row_off, i64 T, const unsigned char *side, const double *mean_in,
+                           double *mean, double *sw, double *cov, double *vec, double *z, double *sums);
 // diameter_host.cpp
 // the exact diameter of the resident embedding by brute force over this rank's share of the pair tiles (NaN for a non-finite
 // embedding); `ai` / `aj` (optional): a pair attaining it, 1-based

@@ -661,19 +661,10 @@ void k_group_cov(cge_ctx *c, const double *Xr, const double *vw, const i32 *rows
             hipLaunchKernelGGL((group_cov_mfma_kernel<false>), dim3((unsigned)n_chunks, (unsigned)(nT * (nT - 1) / 2)), block,
                                2 * stage, c->stream, Xr, vw, rows, chunk_task, chunk_beg, chunk_end, d, nT, mean, part, task_chunk_off, cov);
     } else {
-        const int dpv = (int)((d + 7) / 8 * 8);
-        int RT = 64;
-        while ((size_t)RT * (dpv + 2) * sizeof(double) > 64 * 1024 && RT > 4) RT /= 2;
+        const int dpv = (int)((d + 7) / 8 * 8), RT = 64; // d < 48: a tile of 64 rows takes at most 64 x 50 doubles of LDS
         const size_t lds = (size_t)RT * (dpv + 2) * sizeof(double);
-        if (dpv >= 128)
-            hipLaunchKernelGGL(group_cov_partial_kernel<8>, grid, block, lds, c->stream, Xr, vw, rows, chunk_task,
-                               chunk_beg, chunk_end, d, dpv, RT, mean, part);
-        else if (dpv >= 64)
-            hipLaunchKernelGGL(group_cov_partial_kernel<4>, grid, block, lds, c->stream, Xr, vw, rows, chunk_task,
-                               chunk_beg, chunk_end, d, dpv, RT, mean, part);
-        else
-            hipLaunchKernelGGL(group_cov_partial_kernel<2>, grid, block, lds, c->stream, Xr, vw, rows, chunk_task,
-                               chunk_beg, chunk_end, d, dpv, RT, mean, part);
+        hipLaunchKernelGGL(group_cov_partial_kernel<2>, grid, block, lds, c->stream, Xr, vw, rows, chunk_task, chunk_beg,
+                           chunk_end, d, dpv, RT, mean, part);
     }
     const i64 dd = d * d;
     dim3 g2((unsigned)std::min<i64>((dd + 255) / 256, 64), (unsigned)n_tasks);

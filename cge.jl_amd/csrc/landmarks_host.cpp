@@ -862,59 +862,67 @@ void rss_generic_tasks(cge_ctx *c, SplitBatch &out, const std::vector<i64> &todo
     }
 }
 
-// Enqueue the split of every task of a batch: mean, covariance, principal eigenvector, projection, the rule's 1-D cut,
-// the children's member lists, values and means -- no host synchronisation (except the d > 512 host eigen-solver).
-void split_enqueue(cge_ctx *c, SplitBatch &S) {
-    const i64 d = c->d, T = S.T;
+// The statistics stage of a batch of groups, on the context's stream: the batch tables (B), per task the weighted mean (gathered
+// from the means arena when every group knows its own, else one pass over the rows), the covariance about it and its principal
+// eigenvector, per row the projection -- left in c->ls_mean / ls_sw (computed means only) / ls_cov / ls_vec / ls_z.  No host
+// synchronisation (except the d > 512 host eigen-solver).  split_enqueue and the testing hook host_group_stats_test run it; the
+// hook alone passes `cov_keep` (device, T d d doubles): a copy of the covariances, which the d > 128 eigen-solver overwrites.
+void group_stats_enqueue(cge_ctx *c, Group *const *groups, i64 T, Batch &B, double *cov_keep = nullptr) {
+    const i64 d = c->d;
     hipStream_t st = c->stream;
-    Batch &B = S.B;
     bool have_means = true; // known from the parents' splits: gathered from the means arena, no pass over the rows
-    for (i64 t = 0; t < T && have_means; t++) have_means = S.groups[t]->mean_off >= 0;
+    for (i64 t = 0; t < T && have_means; t++) have_means = groups[t]->mean_off >= 0;
     {
         PhaseAcc pa(c, "lm_pack");
-        build_batch(c, S.groups, T, B);
+        build_batch(c, groups, T, B);
         std::vector<i64> moff;
         if (have_means) {
             moff.resize(T);
-            for (i64 t = 0; t < T; t++) moff[t] = S.groups[t]->mean_off;
+            for (i64 t = 0; t < T; t++) moff[t] = groups[t]->mean_off;
         }
         upload_batch(c, B, have_means ? moff.data() : nullptr);
     }
     const i64 R = B.R, NC = B.NC;
-    c->stat_lm_batches++;
-    c->stat_lm_rows += R;
-    c->stat_lm_splits += T;
     c->ls_mean.ensure((size_t)T * d); c->ls_sw.ensure(T);
     c->ls_cov.ensure((size_t)T * d * d);
     c->ls_vec.ensure((size_t)T * d); c->ls_z.ensure(R);
+    PhaseAcc pa(c, "lm_pca_dev");
+    double *covp = c->ls_cov.p;
     {
-        PhaseAcc pa(c, "lm_pca_dev");
-        double *covp = c->ls_cov.p;
-        {
-            ScopedKernelTimer tm(c, "group_stats");
-            if (have_means) // the offsets went up with the batch's tables
-                k_gather_means(c, c->lm_means.p, c->ls_moff.p, T, d, c->ls_mean.p);
-            else {
-                k_group_mean(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_ct.p, c->ls_cb.p, c->ls_ce.p, NC, c->ls_tco.p, T, d,
-                             c->ls_part.p, c->ls_mean.p, c->ls_sw.p);
-            }
-            k_group_cov(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_ct.p, c->ls_cb.p, c->ls_ce.p, NC, c->ls_tco.p, T, d,
-                        c->ls_mean.p, c->ls_part.p, covp);
+        ScopedKernelTimer tm(c, "group_stats");
+        if (have_means) // the offsets went up with the batch's tables
+            k_gather_means(c, c->lm_means.p, c->ls_moff.p, T, d, c->ls_mean.p);
+        else {
+            k_group_mean(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_ct.p, c->ls_cb.p, c->ls_ce.p, NC, c->ls_tco.p, T, d,
+                         c->ls_part.p, c->ls_mean.p, c->ls_sw.p);
         }
-        if (!k_group_eig(c, covp, T, d, c->ls_vec.p)) { // d > 512: host solver on a worker pool
-            std::vector<double> cov((size_t)T * d * d), vec((size_t)T * d);
-            HIP_CHECK(hipMemcpyAsync(cov.data(), covp, sizeof(double) * cov.size(), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            parallel_for(c, T, [&](i64 t) { host_eig_top(&cov[(size_t)t * d * d], d, &vec[(size_t)t * d]); });
-            HIP_CHECK(hipMemcpyAsync(c->ls_vec.p, vec.data(), sizeof(double) * vec.size(), hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipStreamSynchronize(st)); // vec goes out of scope
-        }
-        {
-            ScopedKernelTimer tm(c, "group_project");
-            k_group_project(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_row_task.p, R, d, c->ls_mean.p, c->ls_vec.p,
-                            c->ls_z.p);
-        }
+        k_group_cov(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_ct.p, c->ls_cb.p, c->ls_ce.p, NC, c->ls_tco.p, T, d,
+                    c->ls_mean.p, c->ls_part.p, covp);
     }
+    if (cov_keep) HIP_CHECK(hipMemcpyAsync(cov_keep, covp, sizeof(double) * T * d * d, hipMemcpyDeviceToDevice, st));
+    if (!k_group_eig(c, covp, T, d, c->ls_vec.p)) { // d > 512: host solver on a worker pool
+        std::vector<double> cov((size_t)T * d * d), vec((size_t)T * d);
+        HIP_CHECK(hipMemcpyAsync(cov.data(), covp, sizeof(double) * cov.size(), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        parallel_for(c, T, [&](i64 t) { host_eig_top(&cov[(size_t)t * d * d], d, &vec[(size_t)t * d]); });
+        HIP_CHECK(hipMemcpyAsync(c->ls_vec.p, vec.data(), sizeof(double) * vec.size(), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // vec goes out of scope
+    }
+    {
+        ScopedKernelTimer tm(c, "group_project");
+        k_group_project(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_row_task.p, R, d, c->ls_mean.p, c->ls_vec.p,
+                        c->ls_z.p);
+    }
+}
+
+// Enqueue the split of every task of a batch: mean, covariance, principal eigenvector, projection, the rule's 1-D cut,
+// the children's member lists, values and means -- no host synchronisation (except the d > 512 host eigen-solver).
+void split_enqueue(cge_ctx *c, SplitBatch &S) {
+    const i64 T = S.T;
+    group_stats_enqueue(c, S.groups, T, S.B);
+    c->stat_lm_batches++;
+    c->stat_lm_rows += S.B.R;
+    c->stat_lm_splits += T;
     // ---- the cut: children lists into the arena, sizes / values / means to the host -----------------------------
     S.nlow.assign(T, 0);
     S.vlow.assign(T, 0.0);
@@ -1656,6 +1664,58 @@ void final_index(cge_ctx *c, const Heap &H, std::vector<i64> &group_ids, bool wa
 }
 
 } // namespace
+
+// testing hook (include/cge_hip_testing.h: cge_group_stats_test): the statistics stage of a split and the side sums for
+// caller-supplied groups of the resident rows -- the member lists go into the arena and the means into the means arena as a
+// runsplit leaves them there, then build_batch / upload_batch / group_stats_enqueue / side_sums run as they do for a split
+void host_group_stats_test(cge_ctx *c, const i32 *ids, const i32 *task_row_off, i64 T, const unsigned char *side, const double *mean_in,
+                           double *mean, double *sw, double *cov, double *vec, double *z, double *sums) {
+    const i64 d = c->d, nrows = lm_rows(c);
+    if (!c->Xr.p || d <= 0 || c->Xr.n < (size_t)(nrows * d) || !c->vw.p || (i64)c->h_vw.size() != c->n)
+        CGE_THROW(CGE_E_ARG, "group_stats_test: embedding / vertex weights are not resident");
+    if (c->rows_sharded) CGE_THROW(CGE_E_ARG, "group_stats_test: not with option shard_rows");
+    if (side && d > 512) CGE_THROW(CGE_E_ARG, "group_stats_test: side sums need d <= 512");
+    if (task_row_off[0] != 0) CGE_THROW(CGE_E_ARG, "group_stats_test: task_row_off[0] != 0");
+    for (i64 t = 0; t < T; t++)
+        if (task_row_off[t + 1] <= task_row_off[t]) CGE_THROW(CGE_E_ARG, "group_stats_test: empty group %lld", (long long)t);
+    const i64 R = task_row_off[T];
+    std::vector<char> seen((size_t)nrows, 0);
+    for (i64 j = 0; j < R; j++) {
+        if (ids[j] < 0 || ids[j] >= nrows) CGE_THROW(CGE_E_ARG, "group_stats_test: id %d outside the %lld resident rows", ids[j], (long long)nrows);
+        if (seen[ids[j]]) CGE_THROW(CGE_E_ARG, "group_stats_test: id %d in two groups", ids[j]);
+        seen[ids[j]] = 1;
+        if (side && side[j] > 2) CGE_THROW(CGE_E_ARG, "group_stats_test: side %d of row %lld", (int)side[j], (long long)j);
+    }
+    hipStream_t st = c->stream;
+    c->lm_arena_used = 0; // (every runsplit starts its arenas from zero too)
+    c->lm_means_used = 0;
+    const i64 base = arena_alloc(c, R), mbase = mean_in ? means_alloc(c, T * d) : -1;
+    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p + base, ids, sizeof(i32) * R, hipMemcpyHostToDevice, st));
+    if (mean_in) HIP_CHECK(hipMemcpyAsync(c->lm_means.p + mbase, mean_in, sizeof(double) * T * d, hipMemcpyHostToDevice, st));
+    std::vector<Group> groups((size_t)T);
+    std::vector<Group *> gp((size_t)T);
+    for (i64 t = 0; t < T; t++) {
+        groups[t].off = base + task_row_off[t];
+        groups[t].len = task_row_off[t + 1] - task_row_off[t];
+        groups[t].mean_off = mean_in ? mbase + t * d : -1;
+        gp[t] = &groups[t];
+    }
+    Batch B;
+    DevBuf<double> cov_keep;
+    cov_keep.ensure((size_t)T * d * d);
+    group_stats_enqueue(c, gp.data(), T, B, cov_keep.p);
+    HIP_CHECK(hipMemcpyAsync(mean, c->ls_mean.p, sizeof(double) * T * d, hipMemcpyDeviceToHost, st));
+    if (!mean_in) HIP_CHECK(hipMemcpyAsync(sw, c->ls_sw.p, sizeof(double) * T, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(cov, cov_keep.p, sizeof(double) * T * d * d, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(vec, c->ls_vec.p, sizeof(double) * T * d, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(z, c->ls_z.p, sizeof(double) * R, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (side) {
+        const std::vector<unsigned char> sd(side, side + R);
+        const double *s2 = side_sums(c, B, sd);
+        std::memcpy(sums, s2, sizeof(double) * (size_t)T * 2 * (2 * d + 1));
+    }
+}
 
 // group_ids[i] = 0-based group (= heap position - 1) of vertex i; also leaves on the device c->v2l (the same, int32)
 // and the landmark -> members index c->lm_memoff / c->lm_mem (ascending inside a landmark), mirrored in

@@ -20,6 +20,22 @@ int cge_host_pos_draw(int64_t seed, int64_t stream_id, int64_t S, int64_t m, int
  * back) by the batched device solvers that landmarks uses (d <= 128: register-resident; d <= 512: global-memory
  * resident); returns CGE_E_ARG for d > 512 */
 int cge_group_eig(void *ctx, const double *A, int64_t T, int64_t d, double *v);
+/* kernel-level hook (needs the GPU): the statistics stage of a landmark split and the side sums for T caller-supplied groups of
+ * the resident embedding and vertex weights, by the split's own batch builder, chunk tables and launch wrappers (the member
+ * lists and the means are placed in the arenas a runsplit keeps them in; the arenas start from zero, as for a runsplit).
+ *   ids: the groups' 0-based row ids back to back, group t = ids[task_row_off[t] .. task_row_off[t + 1]); the groups are
+ *   disjoint, at least one row each, ids in any order (R = task_row_off[T] rows in all).
+ *   Out: mean[T][d]; sw[T] = the groups' weight sums (written only when the means are computed); cov[T][d][d] =
+ *   sum_j w_j (x_j - mean)(x_j - mean)^T; vec[T][d] = its principal eigenvector; z[R] = the rows' projections
+ *   sum_c (x_jc - mean_c) sqrt(w_j) vec_c.
+ *   mean_in (optional, T x d): every group's mean is known -- it is gathered from the means arena (k_gather_means) and not
+ *   computed (k_group_mean), as for a child that inherits its mean from its parent's side sums; mean returns it unchanged.
+ *   side (optional, R flags 0 / 1 / 2; d <= 512) with sums[T][2][2 d + 1]: per group and side 1, 2 the sums of w x^2 [d],
+ *   w x [d] and w over the rows with that flag (0: in neither).
+ * CGE_E_ARG with a message for an empty group, an id outside the resident rows or in two groups, a flag above 2 or a context with
+ * option shard_rows. */
+int cge_group_stats_test(void *ctx, const int32_t *ids, const int32_t *task_row_off, int64_t T, const uint8_t *side, const double *mean_in,
+                         double *mean, double *sw, double *cov, double *vec, double *z, double *sums);
 /* kernel-level hook (needs the GPU): the bound matrix of the pruned diameter for the resident embedding and a caller-supplied
  * landmark assignment -- the layout, the reference points, the gather with its fitness verdict and ONE bound pass, by the launch
  * wrappers cge_score's diameter uses.  v2l[i] in 1..N (every landmark non-empty; its centroid is the mean of its members),

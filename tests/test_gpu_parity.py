@@ -195,6 +195,32 @@ def test_group_eig_kernel(ctx, d):
             assert np.max(np.abs(ref - v[t])) < 1e-10 / gap, (d, t)
 
 
+@pytest.mark.parametrize("d", [2, 3, 5, 17, 32, 33, 64, 65, 100, 127, 128, 129, 200, 256, 333, 512])
+def test_group_eig_kernel_families(ctx, d):
+    """The same two device solvers on the matrices real embeddings produce and random Wishart matrices never do
+    (tests/eig_matrices.py: clustered and repeated top eigenvalues, graded spectra, rank 1 and 2, near-isotropic clouds,
+    diagonal and splitting tridiagonal matrices, entries of 1e+-150), one batch of 64 with the families in turn.  Criterion
+    (eig_matrices.judge): unit norm, sign, and residual and Rayleigh deficit within 8 max(U, numpy.linalg.eigh's own on the
+    same matrix), U = eps sqrt(d) ||A||_2 -- no vector comparison across a tiny gap.  The matrix at position 37 gives the
+    same bits alone."""
+    import eig_matrices as em
+
+    names = list(em.FAMILIES)
+    fam = {name: em.family_matrix(name, d) for name in names}
+    order = [names[i % len(names)] for i in range(64)]
+    v = ctx.group_eig(np.stack([fam[name] for name in order]))
+    fails = []
+    for i, name in enumerate(order[: len(names)]):
+        res, dfc, lim_res, lim_dfc, why = em.judge(fam[name], v[i])
+        print(f"group_eig d={d} {name} residual={res:.3f}U deficit={dfc:.3f}U limits={lim_res:.1f}U,{lim_dfc:.1f}U")
+        fails += [(name, w) for w in why]
+    for i, name in enumerate(order):  # a repeated matrix: the same bits wherever it stands in the batch
+        assert np.array_equal(v[i], v[i % len(names)]), (d, i, name)
+    alone = ctx.group_eig(fam[order[37]][None])
+    assert np.array_equal(alone[0].view(np.int64), v[37].view(np.int64)), (d, order[37])
+    assert not fails, (d, fails)
+
+
 @pytest.mark.parametrize("d,method", [(200, "rss"), (256, "size"), (96, "diameter"), (65, "rss2"), (128, "rss2"), (129, "rss")])
 def test_landmarks_parity_wide_embeddings(ctx, orc, d, method):
     """Embedding dimensions beyond one MFMA tile / one register-resident covariance: the global-memory eigen-solver
