@@ -831,6 +831,27 @@ class Context:
                                                 _p(cov), _p(vec), _p(z), _p(sums)))
         return {"mean": mean, "sw": sw, "cov": cov, "vec": vec, "z": z, "sums": sums}
 
+    def group_cut_test(self, ids, offsets, method, z=None, force_generic=False):
+        """Testing hook (include/cge_hip_testing.h: cge_group_cut_test): the cut stage of a landmark split for groups of at least
+        3 resident rows (0-based ids back to back, offsets (T + 1,)) by rule `method` (a CGE_METHOD_* code) on the projections z
+        (R,), or behind the statistics stage when z is None.  Returns a dict: rc (T,), nlow (T,), children (R,), vlow (T,),
+        vhigh (T,), cmeans (T, 2, d), route (T,), ties."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        T, d = off.size - 1, self.d
+        assert T >= 1 and off[0] == 0 and off[-1] == ids.size
+        if z is not None:
+            z = _f64(z)
+            assert z.shape == ids.shape
+        rc, nlow, children = np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32), np.full(ids.size, -1, dtype=np.int32)
+        vlow, vhigh, cmeans = np.zeros(T), np.zeros(T), np.full((T, 2, d), np.nan)
+        route, ties = np.zeros(T, dtype=np.int32), C.c_int32()
+        self._check(self.L.cge_group_cut_test(self.h, _p(ids), _p(off), C.c_int64(T), C.c_int(int(method)), _p(z),
+                                              C.c_int(1 if force_generic else 0), _p(rc), _p(nlow), _p(children), _p(vlow),
+                                              _p(vhigh), _p(cmeans), _p(route), C.byref(ties)))
+        return {"rc": rc, "nlow": nlow, "children": children, "vlow": vlow, "vhigh": vhigh, "cmeans": cmeans, "route": route,
+                "ties": ties.value}
+
     def diameter_bounds_test(self, v_to_l, N, lcomm, C_, pass_):
         """Testing hook: the bound matrix of the pruned diameter for a landmark assignment (1-based ids) by one named pass
         (0 fp64, 1 f32, 2 bf16 split).  Returns (P (N, nref), pass that ran, reference points (nref, d), centring mean (d,))."""
@@ -968,7 +989,7 @@ class Context:
         self._check(self.L.cge_louvain(self.h, _p(out), C.byref(nc), C.byref(q), C.byref(rounds)))
         return out, nc.value, q.value, rounds.value
 
-    _TEST_OPTIONS = ("fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain")
+    _TEST_OPTIONS = ("fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel")
 
     def set_option(self, key, value):
         if key in self._TEST_OPTIONS:  # the testing knobs are not part of the boundary (include/cge_hip_testing.h)

@@ -330,6 +330,8 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     if (!c || !key) return CGE_E_ARG;
     // 1 = vect_B by the kernels of score graphs beyond the LDS budget
     if (!strcmp(key, "test_bvec_plain")) { c->opt_test_bvec_plain = value != 0; return CGE_OK; }
+    // 1 = rss2 by the one-kernel walk at every width (the comparator of the chain + merge form)
+    if (!strcmp(key, "test_rss2_one_kernel")) { c->opt_test_rss2_one_kernel = value != 0; return CGE_OK; }
     // start skew of the persistent fits' tile waves, in naps of ~3 us
     if (!strcmp(key, "fit_persistent_test_delay") && value >= 0 && value <= 100000) { c->opt_fit_test_delay = (int)value; return CGE_OK; }
     // 1 = the persistent fit abandons every launch at once
@@ -467,6 +469,17 @@ int cge_group_stats_test(void *ctx, const int32_t *ids, const int32_t *task_row_
     if (!c || !ids || !task_row_off || T <= 0 || !mean || !cov || !vec || !z || (!mean_in && !sw) || (side && !sums)) return CGE_E_ARG;
     CGE_TRY_ON_DEVICE(c)
     host_group_stats_test(c, ids, task_row_off, T, side, mean_in, mean, sw, cov, vec, z, sums);
+    CGE_CATCH(c)
+}
+
+// testing hook (include/cge_hip_testing.h): the cut stage of a split on caller-supplied projections
+int cge_group_cut_test(void *ctx, const int32_t *ids, const int32_t *task_row_off, int64_t T, int method, const double *z, int force_generic,
+                       int32_t *rc, int32_t *nlow, int32_t *children, double *vlow, double *vhigh, double *cmeans, int32_t *route,
+                       int32_t *ties) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !ids || !task_row_off || T <= 0 || !rc || !nlow || !children || !vlow || !vhigh || !cmeans || !route || !ties) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_group_cut_test(c, ids, task_row_off, T, method, z, force_generic, rc, nlow, children, vlow, vhigh, cmeans, route, ties);
     CGE_CATCH(c)
 }
 

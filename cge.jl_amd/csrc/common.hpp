@@ -404,6 +404,7 @@ struct cge_ctx {
     bool opt_exact_relabel = true; // exact mode, N > 8192: relabel the score graph by community (wgcl_host.cpp)
     int opt_shard_samples = 1; // N > 1: 1 = local-score tallies split over the ranks from 10^5 samples on (in-library RCCL), 2 = always, 0 = never
     int opt_shard_forced = 1; // N > 1: the forced per-community phase of runsplit is split over the ranks
+    int opt_test_rss2_one_kernel = 0; // testing: rss2 by rss2_walk_kernel at every width (the comparator of the chain + merge form)
     int opt_test_bvec_plain = 0; // testing: vect_B without LDS staging / rows in flight (the forms of very large score graphs)
     int opt_fit_persistent = 0; // 0 auto (score graphs of >= 128 vertices that fit the register file), 1 never, 2 whenever it fits
     i64 opt_fit_max_iters = 2000000; // a Chung-Lu fit that has not met `diff <= delta` (src/divergence.jl:151,434) after this many
@@ -946,6 +947,8 @@ void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i
 void host_eig_top(const double *A, i64 d, double *v); // largest-eigenvalue eigenvector, sign: max |.| component > 0
 void host_group_stats_test(cge_ctx *c, const i32 *ids, const i32 *task_row_off, i64 T, const unsigned char *side, const double *mean_in,
                            double *mean, double *sw, double *cov, double *vec, double *z, double *sums);
+void host_group_cut_test(cge_ctx *c, const i32 *ids, const i32 *task_row_off, i64 T, int method, const double *z, int force_generic,
+                         i32 *rc, i32 *nlow, i32 *children, double *vlow, double *vhigh, double *cmeans, i32 *route, i32 *ties);
 // diameter_host.cpp
 // the exact diameter of the resident embedding by brute force over this rank's share of the pair tiles (NaN for a non-finite
 // embedding); `ai` / `aj` (optional): a pair attaining it, 1-based

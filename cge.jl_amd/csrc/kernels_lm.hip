@@ -1691,7 +1691,7 @@ void k_rss2_walk(cge_ctx *c, const double *Xr, const double *vw, const i32 *srow
                  i32 *meta, double *vals, double *cmeans) {
     if (d > 64 * RR_SLOTS) CGE_THROW(CGE_E_ARG, "embedding dimension %lld > %d not supported", (long long)d, 64 * RR_SLOTS);
     const int ns0 = d <= 64 ? 1 : d <= 128 ? 2 : d <= 256 ? 4 : 8;
-    if (ns0 <= 2 && c->r2_rows > 0) { // chain + merge (the register blocks of the chain allow d <= 128)
+    if (ns0 <= 2 && c->r2_rows > 0 && !c->opt_test_rss2_one_kernel) { // chain + merge (the register blocks of the chain allow d <= 128)
         ScopedKernelTimer t(c, "rss2_walk");
         const i64 R = c->r2_rows, slots = R / R2_BR + n_tasks + 2, stride = 2 * ns0 * 64 + 64;
         c->r2_F.ensure((size_t)2 * R);
@@ -1738,30 +1738,37 @@ __global__ __launch_bounds__(256) void cut_sides_kernel(const double *__restrict
     const i64 o = task_row_off[t], k = task_row_off[t + 1] - o;
     if (k <= 0) { if (tid == 0 && nlow_out) nlow_out[t] = 0; return; }
     double cut;
-    if (use_median)
-        cut = (k & 1) ? zs[o + k / 2] : zs[o + k / 2 - 1] / 2.0 + zs[o + k / 2] / 2.0;
-    else {
+    // A NaN among the projections makes the reference's median and its minimum / maximum NaN: no row is below such a cut, the
+    // low child comes out empty and the split fails (CGE_E_EMPTY_CLUSTER).  The sort puts NaNs at the two ends of the order, so
+    // the middle of the sorted array alone would be finite, and fmin / fmax skip a NaN: it is propagated by hand.
+    if (use_median) {
+        const double a = zs[o], b = zs[o + k - 1];
+        cut = (a != a || b != b) ? a + b : (k & 1) ? zs[o + k / 2] : zs[o + k / 2 - 1] / 2.0 + zs[o + k / 2] / 2.0;
+    } else {
         double lo = z[o], hi = z[o];
+        int nan = 0;
         i64 j = tid;
         for (; j + 768 < k; j += 1024) { // four loads in flight per thread
             const double v0 = z[o + j], v1 = z[o + j + 256], v2 = z[o + j + 512], v3 = z[o + j + 768];
             lo = fmin(fmin(lo, v0), fmin(fmin(v1, v2), v3));
             hi = fmax(fmax(hi, v0), fmax(fmax(v1, v2), v3));
+            nan |= (v0 != v0) | (v1 != v1) | (v2 != v2) | (v3 != v3);
         }
         for (; j < k; j += 256) {
             const double v = z[o + j];
             lo = fmin(lo, v);
             hi = fmax(hi, v);
+            nan |= v != v;
         }
         for (int off = 32; off > 0; off >>= 1) {
             lo = fmin(lo, __shfl_xor(lo, off));
             hi = fmax(hi, __shfl_xor(hi, off));
         }
         if (lane == 0) { slo[wv] = lo; shi[wv] = hi; }
-        __syncthreads();
+        const int any_nan = __syncthreads_or(nan);
         lo = fmin(fmin(slo[0], slo[1]), fmin(slo[2], slo[3])); // (min / max: any grouping gives the same value)
         hi = fmax(fmax(shi[0], shi[1]), fmax(shi[2], shi[3]));
-        cut = (lo + hi) / 2.0;
+        cut = any_nan ? __longlong_as_double(0x7ff8000000000000LL) : (lo + hi) / 2.0;
     }
     // the parallel pass: sides as if there were no tie (a tie provisionally high), the low side counted
     int cnt = 0, tie = 0;

@@ -660,6 +660,8 @@ struct SplitBatch {
     std::vector<i32> nlow;
     std::vector<double> vlow, vhigh;
     std::vector<char> done; // 0 = this task still needs the generic host path
+    std::vector<char> generic; // 1 = the generic host path booked this task (rss)
+    bool force_generic = false; // testing (cge_group_cut_test): rss by the generic host path for every task
     std::unique_ptr<WordGatherer> wg;
     size_t i_status = 0, i_meta = 0, i_vals = 0, i_nlow = 0;
 };
@@ -915,6 +917,20 @@ void group_stats_enqueue(cge_ctx *c, Group *const *groups, i64 T, Batch &B, doub
     }
 }
 
+// The cut stage of a batch whose tables (S.B) are uploaded and whose projections are in c->ls_z: the rule's 1-D cut -- children
+// lists into the arena, sizes / values / means to the host.  split_enqueue and the testing hook host_group_cut_test run it.
+void cut_enqueue(cge_ctx *c, SplitBatch &S) {
+    const i64 T = S.T;
+    S.nlow.assign(T, 0);
+    S.vlow.assign(T, 0.0);
+    S.vhigh.assign(T, 0.0);
+    S.done.assign(T, 0);
+    S.generic.assign(T, 0);
+    if (S.method == CGE_METHOD_RSS) {
+        if (!S.force_generic) rule_rss_sorted_enqueue(c, S);
+    } else if (S.method == CGE_METHOD_RSS2) rule_rss2_enqueue(c, S);
+    else rule_cut_enqueue(c, S, S.method == CGE_METHOD_SIZE);
+}
 // Enqueue the split of every task of a batch: mean, covariance, principal eigenvector, projection, the rule's 1-D cut,
 // the children's member lists, values and means -- no host synchronisation (except the d > 512 host eigen-solver).
 void split_enqueue(cge_ctx *c, SplitBatch &S) {
@@ -923,14 +939,7 @@ void split_enqueue(cge_ctx *c, SplitBatch &S) {
     c->stat_lm_batches++;
     c->stat_lm_rows += S.B.R;
     c->stat_lm_splits += T;
-    // ---- the cut: children lists into the arena, sizes / values / means to the host -----------------------------
-    S.nlow.assign(T, 0);
-    S.vlow.assign(T, 0.0);
-    S.vhigh.assign(T, 0.0);
-    S.done.assign(T, 0);
-    if (S.method == CGE_METHOD_RSS) rule_rss_sorted_enqueue(c, S);
-    else if (S.method == CGE_METHOD_RSS2) rule_rss2_enqueue(c, S);
-    else rule_cut_enqueue(c, S, S.method == CGE_METHOD_SIZE);
+    cut_enqueue(c, S);
 }
 // ... and book the results when they have arrived
 void split_collect(cge_ctx *c, SplitBatch &S) {
@@ -938,10 +947,10 @@ void split_collect(cge_ctx *c, SplitBatch &S) {
     {
         PhaseAcc pa(c, "lm_cut");
         if (S.method == CGE_METHOD_RSS) {
-            rule_rss_sorted_collect(c, S);
+            if (!S.force_generic) rule_rss_sorted_collect(c, S);
             std::vector<i64> todo;
             for (i64 t = 0; t < T; t++)
-                if (!S.done[t]) todo.push_back(t);
+                if (!S.done[t]) { todo.push_back(t); S.generic[t] = 1; }
             if (!todo.empty()) rss_generic_tasks(c, S, todo);
         } else if (S.method == CGE_METHOD_RSS2)
             rule_rss2_collect(c, S);
@@ -1714,6 +1723,77 @@ void host_group_stats_test(cge_ctx *c, const i32 *ids, const i32 *task_row_off, 
         const std::vector<unsigned char> sd(side, side + R);
         const double *s2 = side_sums(c, B, sd);
         std::memcpy(sums, s2, sizeof(double) * (size_t)T * 2 * (2 * d + 1));
+    }
+}
+
+// testing hook (include/cge_hip_testing.h: cge_group_cut_test): the cut stage of a split (cut_enqueue + split_collect) for
+// caller-supplied groups, on caller-supplied projections (z) or behind the statistics stage (z == NULL: split_enqueue as a whole)
+void host_group_cut_test(cge_ctx *c, const i32 *ids, const i32 *task_row_off, i64 T, int method, const double *z, int force_generic,
+                         i32 *rc, i32 *nlow, i32 *children, double *vlow, double *vhigh, double *cmeans, i32 *route, i32 *ties) {
+    const i64 d = c->d, nrows = lm_rows(c);
+    if (!c->Xr.p || d <= 0 || c->Xr.n < (size_t)(nrows * d) || !c->vw.p || (i64)c->h_vw.size() != c->n)
+        CGE_THROW(CGE_E_ARG, "group_cut_test: embedding / vertex weights are not resident");
+    if (c->rows_sharded) CGE_THROW(CGE_E_ARG, "group_cut_test: not with option shard_rows");
+    if (method != CGE_METHOD_RSS && method != CGE_METHOD_RSS2 && method != CGE_METHOD_SIZE && method != CGE_METHOD_DIAMETER)
+        CGE_THROW(CGE_E_ARG, "group_cut_test: unknown method %d", method);
+    if ((method == CGE_METHOD_RSS || method == CGE_METHOD_RSS2) && d > 512) // (what k_rss_rounds / k_rss2_walk refuse, before any launch)
+        CGE_THROW(CGE_E_ARG, "group_cut_test: embedding dimension %lld > 512 not supported by rss / rss2", (long long)d);
+    if (task_row_off[0] != 0) CGE_THROW(CGE_E_ARG, "group_cut_test: task_row_off[0] != 0");
+    for (i64 t = 0; t < T; t++)
+        if (task_row_off[t + 1] - task_row_off[t] < 3)
+            CGE_THROW(CGE_E_ARG, "group_cut_test: group %lld has fewer than 3 rows (such groups never reach the device)", (long long)t);
+    const i64 R = task_row_off[T];
+    std::vector<char> seen((size_t)nrows, 0);
+    for (i64 j = 0; j < R; j++) {
+        if (ids[j] < 0 || ids[j] >= nrows) CGE_THROW(CGE_E_ARG, "group_cut_test: id %d outside the %lld resident rows", ids[j], (long long)nrows);
+        if (seen[ids[j]]) CGE_THROW(CGE_E_ARG, "group_cut_test: id %d in two groups", ids[j]);
+        seen[ids[j]] = 1;
+    }
+    hipStream_t st = c->stream;
+    c->lm_arena_used = 0; // (every runsplit starts its arenas from zero too)
+    c->lm_means_used = 0;
+    const i64 base = arena_alloc(c, R);
+    HIP_CHECK(hipMemcpyAsync(c->lm_arena.p + base, ids, sizeof(i32) * R, hipMemcpyHostToDevice, st));
+    std::vector<Group> groups((size_t)T);
+    std::vector<Group *> gp((size_t)T);
+    for (i64 t = 0; t < T; t++) {
+        groups[t].off = base + task_row_off[t];
+        groups[t].len = task_row_off[t + 1] - task_row_off[t];
+        gp[t] = &groups[t];
+    }
+    c->cut_ties.ensure(1);
+    HIP_CHECK(hipMemsetAsync(c->cut_ties.p, 0, sizeof(int), st));
+    SplitBatch S;
+    S.groups = gp.data();
+    S.T = T;
+    S.method = method;
+    S.force_generic = method == CGE_METHOD_RSS && force_generic != 0;
+    S.base = arena_alloc(c, R);
+    S.mbase = means_alloc(c, 2 * T * d);
+    if (z) { // the projections are given: the batch tables alone, then the cut
+        build_batch(c, gp.data(), T, S.B);
+        upload_batch(c, S.B);
+        c->ls_z.ensure(R);
+        HIP_CHECK(hipMemcpyAsync(c->ls_z.p, z, sizeof(double) * R, hipMemcpyHostToDevice, st));
+        cut_enqueue(c, S);
+    } else
+        split_enqueue(c, S);
+    split_collect(c, S);
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipMemcpy(children, c->lm_arena.p + S.base, sizeof(i32) * R, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(ties, c->cut_ties.p, sizeof(i32), hipMemcpyDeviceToHost));
+    for (i64 t = 0; t < T; t++) {
+        const Group &g = groups[t];
+        rc[t] = g.rc;
+        nlow[t] = S.nlow[t];
+        route[t] = S.generic[t];
+        vlow[t] = g.rc == CGE_OK ? g.vlow : 0.0;
+        vhigh[t] = g.rc == CGE_OK ? g.vhigh : 0.0;
+        double *m = cmeans + (size_t)t * 2 * d;
+        if (g.rc == CGE_OK && g.cmean_off >= 0)
+            HIP_CHECK(hipMemcpy(m, c->lm_means.p + g.cmean_off, sizeof(double) * 2 * d, hipMemcpyDeviceToHost));
+        else
+            for (i64 q = 0; q < 2 * d; q++) m[q] = std::nan("");
     }
 }
 

@@ -36,6 +36,25 @@ int cge_group_eig(void *ctx, const double *A, int64_t T, int64_t d, double *v);
  * option shard_rows. */
 int cge_group_stats_test(void *ctx, const int32_t *ids, const int32_t *task_row_off, int64_t T, const uint8_t *side, const double *mean_in,
                          double *mean, double *sw, double *cov, double *vec, double *z, double *sums);
+/* kernel-level hook (needs the GPU): the cut stage of a landmark split -- the per-group sort of the projections, the rule's
+ * one-dimensional cut, the children's member lists, values and means -- for T caller-supplied groups (as for
+ * cge_group_stats_test, here of at least 3 rows each: shorter groups never reach the device) by the split's own batch builder,
+ * launch wrappers and collect step, the generic host path of the rss tasks the sorted form declines included.  The arenas start
+ * from zero and the counter of tie tasks is zeroed first.
+ *   method: a CGE_METHOD_* code.  z (R doubles, one per row in ids order): the projections, in place of the statistics stage, so
+ *   a caller decides every tie and every order; z == NULL: the statistics stage runs first (the whole split).  force_generic
+ *   (rss only): non-zero sends every task through the generic host path instead of the sorted form.
+ *   Out: rc[T] = the task's code (CGE_OK, CGE_E_HOMOGENEOUS, CGE_E_EMPTY_CLUSTER); nlow[T] = rows of the low child;
+ *   children[R] = the children lists, task t at task_row_off[t], low child first; vlow[T], vhigh[T] = the children's values as
+ *   the split books them (DBL_EPSILON for a one-row child; 0 for a failed task); cmeans[T][2][d] = the children's means from the
+ *   means arena (NaN for a failed task); route[T] = 0 the device form, 1 the generic host path; *ties = tasks of the size /
+ *   diameter rules that held a row ON the cut.
+ * CGE_E_ARG with a message, before any launch, for a group of fewer than 3 rows, an id outside the resident rows or in two
+ * groups, an unknown method, rss / rss2 with d > 512 or a context with option shard_rows (size / diameter with d > 512: the
+ * side sums behind the cut refuse, CGE_E_ARG too). */
+int cge_group_cut_test(void *ctx, const int32_t *ids, const int32_t *task_row_off, int64_t T, int method, const double *z, int force_generic,
+                       int32_t *rc, int32_t *nlow, int32_t *children, double *vlow, double *vhigh, double *cmeans, int32_t *route,
+                       int32_t *ties);
 /* kernel-level hook (needs the GPU): the bound matrix of the pruned diameter for the resident embedding and a caller-supplied
  * landmark assignment -- the layout, the reference points, the gather with its fitness verdict and ONE bound pass, by the launch
  * wrappers cge_score's diameter uses.  v2l[i] in 1..N (every landmark non-empty; its centroid is the mean of its members),
@@ -91,7 +110,9 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *   "fit_persistent_test_delay"   n: the tile waves of the persistent fits nap n x ~3 us before their first load (start skew, as
  *                                 under contention);
  *   "fit_persistent_test_timeout" 1: the persistent fit abandons every launch at once (the fallback path runs);
- *   "test_bvec_plain"             1: vect_B by the kernels of score graphs beyond the LDS budget / 512 communities.              */
+ *   "test_bvec_plain"             1: vect_B by the kernels of score graphs beyond the LDS budget / 512 communities;
+ *   "test_rss2_one_kernel"        1: rss2 by the one-kernel walk (rss2_walk_kernel) at every width, d <= 128 included, where the
+ *                                 chain + merge form runs otherwise: the two forms give the same bits.                           */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
 /* needs the GPU: the resident row-major fp64 matrix as this rank holds it (all n rows; under shard_rows its own rows, in
  * local order, with their global 0-based ids in ids_out, which may be NULL otherwise).  *rows and *d are set first; a capacity
