@@ -462,7 +462,7 @@ struct cge_ctx {
     int stat_bound_pass = 0;            // bound pass of the last pruned diameter: 2 bf16-split, 1 fp32 MFMA, 0 fp64 MFMA
     i64 stat_nref = 0; // reference points of the last pruned diameter (communities or landmarks)
     // scratch of the batched split engine (landmarks_host.cpp)
-    DevBuf<i32> ls_rows, ls_row_task, ls_ct, ls_cb, ls_ce, ls_tco;
+    DevBuf<i32> ls_rows, ls_row_task, ls_ct, ls_cb, ls_ce, ls_co, ls_tco; // ls_co: the chunks' launch order (batch_tables)
     DevBuf<double> ls_part, ls_mean, ls_sw, ls_cov, ls_vec, ls_z, ls_sums;
     DevBuf<unsigned char> ls_side, ls_state;
     DevBuf<double> ls_params; // per-task round parameters of the rss rule
@@ -694,8 +694,8 @@ void k_group_mean(cge_ctx *c, const double *Xr, const double *vw, const i32 *row
                   const i32 *chunk_beg, const i32 *chunk_end, i64 n_chunks, const i32 *task_chunk_off, i64 n_tasks,
                   i64 d, double *part, double *mean, double *sw);
 void k_group_cov(cge_ctx *c, const double *Xr, const double *vw, const i32 *rows, const i32 *chunk_task,
-                 const i32 *chunk_beg, const i32 *chunk_end, i64 n_chunks, const i32 *task_chunk_off, i64 n_tasks,
-                 i64 d, const double *mean, double *part, double *cov);
+                 const i32 *chunk_beg, const i32 *chunk_end, const i32 *chunk_order, i64 n_chunks, const i32 *task_chunk_off,
+                 i64 n_tasks, i64 d, const double *mean, double *part, double *cov);
 void k_group_side_sums(cge_ctx *c, const double *Xr, const double *vw, const i32 *rows, const unsigned char *side,
                        const i32 *chunk_beg, const i32 *chunk_end, i64 n_chunks, const i32 *task_chunk_off, i64 n_tasks,
                        i64 d, double *part, double *out);

@@ -532,13 +532,22 @@ __global__ __launch_bounds__(256) void group_cov_partial_kernel(const double *__
 // 128 contiguous features).  The rows are gathered from the embedding by vertex id, centred and scaled on the
 // way into LDS (no intermediate Y buffer); chunks are padded with zero rows to a multiple of 16.  A diagonal tile
 // (the only one when d <= 128) stages its operand once.
-template <bool SAME>
-__global__ __launch_bounds__(256, 2) void group_cov_mfma_kernel(const double *__restrict__ Xr,
+// Launch order: block -> chunk through chunk_order, longest chunk first (batch_tables) -- the kernel is bound per chunk (a
+// workgroup's latency chain over up to 64 stages of 16 rows), not per row, and a batch of a few hundred chunks of unequal length
+// ran as long as a long chunk that started late.  It says when a chunk is worked on, not which wave accumulates a block or in
+// which order its rows arrive: the bits stay.  (Half-tile work units, two workgroups of 18 blocks per chunk, were built and
+// measured too: no gain over this form, and every row gathered twice -- profiles/r14_split_stats_results.txt.)
+// PAIR (d even): a thread's two columns are one aligned 16-byte load.  A compile-time choice: as a run-time branch inside the
+// loader it put a different number of loads on its two sides, and the compiler, no longer able to count the loads behind the
+// ones it waits for, drained them all (vmcnt(0)) in front of every stage's LDS stores -- no prefetch left.
+template <bool SAME, bool PAIR>
+__global__ __launch_bounds__(256, SAME ? 3 : 2) void group_cov_mfma_kernel(const double *__restrict__ Xr,
                                                                 const double *__restrict__ vw,
                                                                 const i32 *__restrict__ rows,
                                                                 const i32 *__restrict__ chunk_task,
                                                                 const i32 *__restrict__ chunk_beg,
-                                                                const i32 *__restrict__ chunk_end, i64 d, i64 nT,
+                                                                const i32 *__restrict__ chunk_end,
+                                                                const i32 *__restrict__ chunk_order, i64 d, i64 nT,
                                                                 const double *__restrict__ mean,
                                                                 double *__restrict__ part /* [chunk][d*d] */,
                                                                 const i32 *__restrict__ task_chunk_off, double *__restrict__ cov) {
@@ -547,7 +556,7 @@ __global__ __launch_bounds__(256, 2) void group_cov_mfma_kernel(const double *__
     __shared__ double s_sq[CGE_CHUNK_ROWS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4, c2 = lane * 2;
-    const i64 ch = blockIdx.x;
+    const i64 ch = chunk_order[blockIdx.x]; // the launch order: longest chunk first
     i64 ta, tb; // tile pair: all of them, or (SAME) the diagonal ones
     if (SAME) {
         ta = tb = blockIdx.y;
@@ -567,7 +576,6 @@ __global__ __launch_bounds__(256, 2) void group_cov_mfma_kernel(const double *__
     }
     const double *mu = mean + (i64)chunk_task[ch] * d;
     const i64 ca = a0 + c2, cb = b0 + c2;
-    const bool pair_ok = (d & 1) == 0; // 16-byte aligned pairs
     const double ma0 = ca < d ? mu[ca] : 0.0, ma1 = ca + 1 < d ? mu[ca + 1] : 0.0;
     const double mb0 = (!SAME && cb < d) ? mu[cb] : 0.0, mb1 = (!SAME && cb + 1 < d) ? mu[cb + 1] : 0.0;
     __syncthreads();
@@ -580,7 +588,7 @@ __global__ __launch_bounds__(256, 2) void group_cov_mfma_kernel(const double *__
         const i64 e0 = col < d ? col : 0, e1 = col + 1 < d ? col + 1 : 0;
         RawRow r;
         r.sq = kr < len ? s_sq[krc] : 0.0;
-        if (pair_ok) r.x = *reinterpret_cast<const d2 *>(x + e0); // d even, col even: e1 == e0 + 1 whenever col < d
+        if constexpr (PAIR) r.x = *reinterpret_cast<const d2 *>(x + e0); // d even, col even: e1 == e0 + 1 whenever col < d
         else r.x = (d2){x[e0], x[e1]};
         return r;
     };
@@ -594,7 +602,7 @@ __global__ __launch_bounds__(256, 2) void group_cov_mfma_kernel(const double *__
     }
     if (SAME) { // upper-triangular blocks only, mirrored on the way out
         d4 acc[9];
-        auto la = [&](i64 kc, int q) { return load(kc, q, ca); };
+        auto la = [&](i64 kc, int q) { return load(kc, q, ca); }; // (valid beyond the last stage: the chunk's first row, scale 0)
         auto fa = [&](const RawRow &r) { return finish(r, ca, ma0, ma1); };
         switch (wave) {
         case 0: syrk_tile_128_wave<0>(la, fa, len16 / MP_BK, lds, acc, wave, c2, lr, lk); break;
@@ -649,17 +657,23 @@ __global__ void group_cov_final_kernel(const double *__restrict__ part, const i3
     }
 }
 void k_group_cov(cge_ctx *c, const double *Xr, const double *vw, const i32 *rows, const i32 *chunk_task,
-                 const i32 *chunk_beg, const i32 *chunk_end, i64 n_chunks, const i32 *task_chunk_off, i64 n_tasks,
-                 i64 d, const double *mean, double *part, double *cov) {
+                 const i32 *chunk_beg, const i32 *chunk_end, const i32 *chunk_order, i64 n_chunks, const i32 *task_chunk_off,
+                 i64 n_tasks, i64 d, const double *mean, double *part, double *cov) {
     dim3 grid((unsigned)n_chunks), block(256);
     if (d >= 48) { // fp64 MFMA SYRK (below a full tile too: a chunk is bound by its latency chain, not by the flops of the padding)
         const i64 nT = (d + 127) / 128;
         const size_t stage = (size_t)2 * MP_BK * MP_LD * sizeof(double);
-        hipLaunchKernelGGL((group_cov_mfma_kernel<true>), dim3((unsigned)n_chunks, (unsigned)nT), block, stage, c->stream,
-                           Xr, vw, rows, chunk_task, chunk_beg, chunk_end, d, nT, mean, part, task_chunk_off, cov);
-        if (nT > 1)
-            hipLaunchKernelGGL((group_cov_mfma_kernel<false>), dim3((unsigned)n_chunks, (unsigned)(nT * (nT - 1) / 2)), block,
-                               2 * stage, c->stream, Xr, vw, rows, chunk_task, chunk_beg, chunk_end, d, nT, mean, part, task_chunk_off, cov);
+        const dim3 gd((unsigned)n_chunks, (unsigned)nT), go((unsigned)n_chunks, (unsigned)(nT * (nT - 1) / 2));
+#define CGE_COV_LAUNCH(SAME, PAIR, GRID, LDS)                                                                                \
+    hipLaunchKernelGGL((group_cov_mfma_kernel<SAME, PAIR>), GRID, block, LDS, c->stream, Xr, vw, rows, chunk_task, chunk_beg, \
+                       chunk_end, chunk_order, d, nT, mean, part, task_chunk_off, cov)
+        if ((d & 1) == 0) CGE_COV_LAUNCH(true, true, gd, stage);
+        else CGE_COV_LAUNCH(true, false, gd, stage);
+        if (nT > 1) { // the tiles above the diagonal
+            if ((d & 1) == 0) CGE_COV_LAUNCH(false, true, go, 2 * stage);
+            else CGE_COV_LAUNCH(false, false, go, 2 * stage);
+        }
+#undef CGE_COV_LAUNCH
     } else {
         const int dpv = (int)((d + 7) / 8 * 8), RT = 64; // d < 48: a tile of 64 rows takes at most 64 x 50 doubles of LDS
         const size_t lds = (size_t)RT * (dpv + 2) * sizeof(double);
@@ -1933,6 +1947,55 @@ __device__ __forceinline__ double fast_rcp(double q) {
     r = fma(fma(-q, r, 1.0), r, r);
     return r;
 }
+// Largest eigenvalue of the symmetric tridiagonal matrix (diag[0..d), sub-diagonal off[0..d-1)) by 64-way multisection on the
+// Sturm count, one wave (both device eigen-solvers): lane l counts the negative pivots q_i of the section point l + 1 of 65 in
+// [lo, hi]; the first lane whose count is d closes the bracket.  A round is one dependent chain of d - 1 steps
+// q = diag[i] - x - off[i-1]^2 / q, the serial stage a launch is as long as, so the chain carries nothing it need not:
+// off2[i] = off[i-1] * off[i-1] (off2[0] unused) is computed once by the caller, not in every step of every round; the operands
+// of STURM_B steps are read from LDS in one batch ahead of them (the LU's way, see EB below) instead of one waited-for read
+// per pair of steps; and the zero pivot is replaced BEHIND the reciprocal -- 1 / tiny, computed once, is selected when
+// q == 0.0, the compare running beside v_rcp_f64 and not in front of it.  The same products, the same reciprocal of the same
+// value, the same subtractions in the same order: the same bits as the step-by-step loop.
+constexpr int STURM_B = 8;
+__device__ __forceinline__ double sturm_top_eigenvalue(const double *diag, const double *off2, int d, double glo, double ghi,
+                                                       double tiny, int lane) {
+    const double rtiny = fast_rcp(tiny);
+    double lo = glo, hi = ghi + tiny;
+    for (int it = 0; it < 64; it++) {
+        const double x = lo + (hi - lo) * ((double)(lane + 1) / 65.0);
+        int cnt = 0;
+        double q = diag[0] - x;
+        if (q < 0) cnt++;
+        auto step = [&](double dg, double o2) {
+            const double r = fast_rcp(q);
+            q = dg - x - o2 * (q == 0.0 ? rtiny : r);
+            if (q < 0) cnt++;
+        };
+        int i = 1;
+        for (; i + STURM_B <= d; i += STURM_B) {
+            double dg[STURM_B], o2[STURM_B];
+#pragma unroll
+            for (int u = 0; u < STURM_B; u++) { dg[u] = diag[i + u]; o2[u] = off2[i + u]; }
+#pragma unroll
+            for (int u = 0; u < STURM_B; u++) step(dg[u], o2[u]);
+        }
+        for (; i < d; i++) step(diag[i], off2[i]);
+        const unsigned long long mask = __ballot(cnt >= d);
+        double nlo, nhi;
+        if (mask == 0ULL) {
+            nlo = __shfl(x, 63);
+            nhi = hi;
+        } else {
+            const int f = __ffsll((long long)mask) - 1;
+            nhi = __shfl(x, f);
+            nlo = (f > 0) ? __shfl(x, f - 1) : lo;
+        }
+        if (!(nhi > nlo) || (nlo == lo && nhi == hi)) break;
+        lo = fmax(lo, nlo);
+        hi = fmin(hi, nhi);
+    }
+    return 0.5 * (lo + hi);
+}
 // acc += (lane N of the reader's row of 16 lanes of `bc`) * a as ONE instruction: gfx950's fp64 FMA takes a DPP broadcast on its
 // first factor at the plain FMA's rate (profiles/microbench_dpp_fmac.hip), so a value that is the same for all lanes needs no
 // LDS broadcast read and no v_readlane.  `bc` must have been written at least two instructions earlier (dpp_fence).
@@ -2209,6 +2272,7 @@ __global__ __launch_bounds__(256, 2) void group_eig_kernel(const double *__restr
         glo = diag[tid] - rad;
         ghi = diag[tid] + rad;
         gn = fabs(diag[tid]) + rad;
+        tri[tid] = tid > 0 ? off[tid - 1] * off[tid - 1] : 0.0; // off2 of the multisection (tri is free until the inverse iteration)
     }
     for (int o2 = 32; o2 > 0; o2 >>= 1) {
         glo = fmin(glo, __shfl_xor(glo, o2));
@@ -2224,32 +2288,8 @@ __global__ __launch_bounds__(256, 2) void group_eig_kernel(const double *__restr
     const double tiny = fmax(gn, 2.2250738585072014e-308) * 2.220446049250313e-16;
     // ---- largest eigenvalue: 64-way multisection on the Sturm count (wave 0) ------------------------------
     if (tid < 64) {
-        double lo = glo, hi = ghi + tiny;
-        for (int it = 0; it < 64; it++) {
-            const double x = lo + (hi - lo) * ((double)(tid + 1) / 65.0);
-            int cnt = 0;
-            double q = diag[0] - x;
-            if (q < 0) cnt++;
-            for (int i = 1; i < d; i++) {
-                if (q == 0.0) q = tiny;
-                q = diag[i] - x - (off[i - 1] * off[i - 1]) * fast_rcp(q);
-                if (q < 0) cnt++;
-            }
-            const unsigned long long mask = __ballot(cnt >= d);
-            double nlo, nhi;
-            if (mask == 0ULL) {
-                nlo = __shfl(x, 63);
-                nhi = hi;
-            } else {
-                const int f = __ffsll((long long)mask) - 1;
-                nhi = __shfl(x, f);
-                nlo = (f > 0) ? __shfl(x, f - 1) : lo;
-            }
-            if (!(nhi > nlo) || (nlo == lo && nhi == hi)) break;
-            lo = fmax(lo, nlo);
-            hi = fmin(hi, nhi);
-        }
-        if (tid == 0) red[4] = 0.5 * (lo + hi);
+        const double top = sturm_top_eigenvalue(diag, tri, d, glo, ghi, tiny, tid);
+        if (tid == 0) red[4] = top;
     }
     __syncthreads();
     if (diag_stage == 2) { if (tid < d) out[tid] = red[4]; return; } // timing diagnostic only
@@ -2685,6 +2725,7 @@ __global__ __launch_bounds__(EWP_T, EWP_OCC) void group_eig_panel_kernel(double 
     // the tridiagonal matrix -> LDS (the panel storage is free now)
     double *diag = sh, *off = diag + d, *beta = off + d, *tri = beta + d; // tri: 4 d
     unsigned char *swp = reinterpret_cast<unsigned char *>(tri + 4 * d);
+    double *off2 = sh + 8 * d; // off[i-1]^2 for the multisection: behind swp (d bytes), in front of v (sh + 16 d)
     for (int i = tid; i < d; i += EWP_T) {
         diag[i] = A[i * d + i];
         off[i] = (i + 2 < d) ? A[(i + 2) * d + i] : ((i == d - 2) ? A[(i + 1) * d + i] : 0.0); // the element below the diagonal
@@ -2698,6 +2739,7 @@ __global__ __launch_bounds__(EWP_T, EWP_OCC) void group_eig_panel_kernel(double 
         glo = fmin(glo, diag[i] - rad);
         ghi = fmax(ghi, diag[i] + rad);
         gn = fmax(gn, fabs(diag[i]) + rad);
+        off2[i] = i > 0 ? off[i - 1] * off[i - 1] : 0.0;
     }
     for (int o2 = 32; o2 > 0; o2 >>= 1) {
         glo = fmin(glo, __shfl_xor(glo, o2));
@@ -2714,32 +2756,8 @@ __global__ __launch_bounds__(EWP_T, EWP_OCC) void group_eig_panel_kernel(double 
     const double tiny = fmax(gn, 2.2250738585072014e-308) * 2.220446049250313e-16;
     // ---- largest eigenvalue: 64-way multisection on the Sturm count (wave 0) ------------------------------
     if (tid < 64) {
-        double lo = glo, hi = ghi + tiny;
-        for (int it = 0; it < 64; it++) {
-            const double x = lo + (hi - lo) * ((double)(tid + 1) / 65.0);
-            int cnt = 0;
-            double qq = diag[0] - x;
-            if (qq < 0) cnt++;
-            for (int i = 1; i < d; i++) {
-                if (qq == 0.0) qq = tiny;
-                qq = diag[i] - x - (off[i - 1] * off[i - 1]) * fast_rcp(qq);
-                if (qq < 0) cnt++;
-            }
-            const unsigned long long mask = __ballot(cnt >= d);
-            double nlo, nhi;
-            if (mask == 0ULL) {
-                nlo = __shfl(x, 63);
-                nhi = hi;
-            } else {
-                const int f = __ffsll((long long)mask) - 1;
-                nhi = __shfl(x, f);
-                nlo = (f > 0) ? __shfl(x, f - 1) : lo;
-            }
-            if (!(nhi > nlo) || (nlo == lo && nhi == hi)) break;
-            lo = fmax(lo, nlo);
-            hi = fmin(hi, nhi);
-        }
-        if (tid == 0) red[4] = 0.5 * (lo + hi);
+        const double top = sturm_top_eigenvalue(diag, off2, d, glo, ghi, tiny, tid);
+        if (tid == 0) red[4] = top;
     }
     panel_sync();
     // ---- inverse iteration (lane 0 of wave 0 runs the recurrences, the wave the element-wise parts) -----------------

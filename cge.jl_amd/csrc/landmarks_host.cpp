@@ -349,7 +349,7 @@ namespace {
 struct Batch {
     i64 T = 0, R = 0, NC = 0, max_len = 0; // max_len: rows of the longest group
     i32 *rows = nullptr, *row_task = nullptr; // host-built batches only: pinned staging owned by the ctx
-    std::vector<i32> chunk_task, chunk_beg, chunk_end, task_chunk_off, task_row_off, task_off;
+    std::vector<i32> chunk_task, chunk_beg, chunk_end, chunk_order, task_chunk_off, task_row_off, task_off;
 };
 // chunk tables from the groups' lengths; `lens` = what.size() for a host-built batch
 void batch_tables(Batch &B, const std::vector<i64> &lens) {
@@ -376,6 +376,16 @@ void batch_tables(Batch &B, const std::vector<i64> &lens) {
     B.task_row_off[T] = (i32)pos;
     B.task_chunk_off[T] = (i32)B.chunk_task.size();
     B.NC = (i64)B.chunk_task.size();
+    // The chunks' launch order, longest first (descending 16-row padded length, ties in chunk order: a counting sort): a kernel
+    // whose workgroup takes a whole chunk maps blockIdx.x through it, so that the long chunks of a batch start first and the short
+    // ones fill in behind them.  It says WHEN a chunk is worked on, nothing else: the tables above are indexed by chunk as ever.
+    const i64 NB = CH / 16 + 1;
+    std::vector<i32> first(NB + 1, 0);
+    auto bucket = [&](i64 ch) { return NB - 1 - (B.chunk_end[ch] - B.chunk_beg[ch] + 15) / 16; };
+    for (i64 ch = 0; ch < B.NC; ch++) first[bucket(ch) + 1]++;
+    for (i64 b = 0; b < NB; b++) first[b + 1] += first[b];
+    B.chunk_order.resize(B.NC);
+    for (i64 ch = 0; ch < B.NC; ch++) B.chunk_order[first[bucket(ch)]++] = (i32)ch;
 }
 // The other direction: device arrays -> one device staging area (one kernel) -> pinned memory (one copy).  fetch()
 // waits for its copy (fetch_async() + wait() split the two halves); the pointers returned by get() are valid until the next
@@ -421,13 +431,14 @@ struct WordGatherer {
 void upload_tables(cge_ctx *c, const Batch &B, WordPacker &pk) { // grow-only scratch owned by the ctx
     const i64 d = c->d;
     c->ls_rows.ensure(B.R); c->ls_row_task.ensure(B.R); c->ls_ct.ensure(B.NC); c->ls_cb.ensure(B.NC);
-    c->ls_ce.ensure(B.NC); c->ls_tco.ensure(B.T + 1); c->sp_tro.ensure(B.T + 1);
+    c->ls_ce.ensure(B.NC); c->ls_co.ensure(B.NC); c->ls_tco.ensure(B.T + 1); c->sp_tro.ensure(B.T + 1);
     c->ls_part.ensure((size_t)B.NC * std::max(d * d, 2 * (2 * d + 1)));
     c->ls_side.ensure(B.R);
     c->ls_sums.ensure((size_t)B.T * 2 * (2 * d + 1));
     pk.add(c->ls_ct.p, B.chunk_task.data(), B.NC);
     pk.add(c->ls_cb.p, B.chunk_beg.data(), B.NC);
     pk.add(c->ls_ce.p, B.chunk_end.data(), B.NC);
+    pk.add(c->ls_co.p, B.chunk_order.data(), B.NC);
     pk.add(c->ls_tco.p, B.task_chunk_off.data(), B.T + 1);
     pk.add(c->sp_tro.p, B.task_row_off.data(), B.T + 1);
 }
@@ -898,7 +909,7 @@ void group_stats_enqueue(cge_ctx *c, Group *const *groups, i64 T, Batch &B, doub
             k_group_mean(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_ct.p, c->ls_cb.p, c->ls_ce.p, NC, c->ls_tco.p, T, d,
                          c->ls_part.p, c->ls_mean.p, c->ls_sw.p);
         }
-        k_group_cov(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_ct.p, c->ls_cb.p, c->ls_ce.p, NC, c->ls_tco.p, T, d,
+        k_group_cov(c, c->Xr.p, lm_vw(c), c->ls_rows.p, c->ls_ct.p, c->ls_cb.p, c->ls_ce.p, c->ls_co.p, NC, c->ls_tco.p, T, d,
                     c->ls_mean.p, c->ls_part.p, covp);
     }
     if (cov_keep) HIP_CHECK(hipMemcpyAsync(cov_keep, covp, sizeof(double) * T * d * d, hipMemcpyDeviceToDevice, st));

@@ -99,28 +99,35 @@ __device__ __forceinline__ void gram_tile_128(const double *__restrict__ pa, con
 
 // The diagonal tile of a SYRK, G = A_tile * A_tile^T: only the 36 upper-triangular 16x16 blocks of the 8x8 block
 // grid are computed.  Wave w owns block-rows w and 7-w (8-w + w+1 = 9 blocks each way: the four waves are balanced);
-// slot q < 8-w is block (w, w+q), slot q >= 8-w is block (7-w, 7-w + q-(8-w)).  Same staging as gram_tile_128_ld
-// with SAME = true.  acc[q] has the MFMA C/D layout of its block: lane l, register r -> row (l>>4)+4r, col l&15.
+// slot q < 8-w is block (w, w+q), slot q >= 8-w is block (7-w, 7-w + q-(8-w)).  acc[q] has the MFMA C/D layout of its
+// block: lane l, register r -> row (l>>4)+4r, col l&15.
+// Staging as in gram_tile_128_ld with SAME = true, but with the loads of TWO stages in flight (the operand is gathered row by
+// row: one stage of MFMAs, ~1 us, did not cover a gather): stage kc + 2 is requested before the MFMAs of stage kc, stage kc + 1
+// (requested an iteration earlier) goes to LDS behind them.  The loop is unrolled by two so that the two register sets swap
+// roles without a copy (a copy of a register that a load has yet to fill waits for the load).  The requests are UNCONDITIONAL:
+// la(kc, q) must be valid for kc <= nchunk + 1 (what it returns beyond the last stage is never staged) -- behind a branch that
+// issues loads on one side only, the wait in front of the LDS stores could not leave the younger stage's loads in flight; for
+// the same reason la must issue the same number of loads on every path (the compiler then waits with vmcnt(4..7), not 0).
 template <int W, class LA, class FA>
 __device__ __forceinline__ void syrk_tile_128_wave(LA la, FA fa, i64 nchunk, double *lds, d4 (&acc)[9], int wave, int c2,
                                                    int lr, int lk) {
     const size_t stage_doubles = (size_t)MP_BK * MP_LD;
 #pragma unroll
     for (int q = 0; q < 9; q++) acc[q] = (d4){0.0, 0.0, 0.0, 0.0};
-    decltype(la((i64)0, 0)) ra[4];
+    decltype(la((i64)0, 0)) r0[4], r1[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) ra[q] = la((i64)0, q);
+    for (int q = 0; q < 4; q++) r0[q] = la((i64)0, q);
+#pragma unroll
+    for (int q = 0; q < 4; q++) r1[q] = la((i64)1, q);
     __syncthreads(); // the previous tile's readers are done with both stages
 #pragma unroll
-    for (int q = 0; q < 4; q++) *reinterpret_cast<d2 *>(lds + (wave + 4 * q) * MP_LD + c2) = fa(ra[q]);
+    for (int q = 0; q < 4; q++) *reinterpret_cast<d2 *>(lds + (wave + 4 * q) * MP_LD + c2) = fa(r0[q]);
     __syncthreads();
-    for (i64 kc = 0; kc < nchunk; kc++) {
+    // one stage: rs holds the rows of stage kc + 1, rl takes those of stage kc + 2
+    auto stage = [&](i64 kc, decltype(r0) &rs, decltype(r0) &rl) {
         const int s = (int)(kc & 1);
-        const bool more = kc + 1 < nchunk;
-        if (more) {
 #pragma unroll
-            for (int q = 0; q < 4; q++) ra[q] = la(kc + 1, q);
-        }
+        for (int q = 0; q < 4; q++) rl[q] = la(kc + 2, q);
         const double *As = lds + (size_t)s * stage_doubles;
 #pragma unroll
         for (int ks = 0; ks < MP_BK / 4; ks++) {
@@ -134,12 +141,16 @@ __device__ __forceinline__ void syrk_tile_128_wave(LA la, FA fa, i64 nchunk, dou
             for (int q = 0; q <= W; q++)
                 acc[8 - W + q] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[7 - W], f[7 - W + q], acc[8 - W + q], 0, 0, 0);
         }
-        if (more) {
+        if (kc + 1 < nchunk) {
             double *An = lds + (size_t)(s ^ 1) * stage_doubles;
 #pragma unroll
-            for (int q = 0; q < 4; q++) *reinterpret_cast<d2 *>(An + (wave + 4 * q) * MP_LD + c2) = fa(ra[q]);
+            for (int q = 0; q < 4; q++) *reinterpret_cast<d2 *>(An + (wave + 4 * q) * MP_LD + c2) = fa(rs[q]);
         }
         __syncthreads();
+    };
+    for (i64 kc = 0; kc < nchunk; kc += 2) {
+        stage(kc, r1, r0);
+        if (kc + 1 < nchunk) stage(kc + 1, r0, r1);
     }
 }
 // block coordinates of slot q of wave w (see above)
