@@ -871,6 +871,18 @@ class Context:
         self._check(self.L.cge_pow_test(self.h, _p(x), C.c_int64(x.size), C.c_double(alpha), C.c_int(method), _p(out)))
         return out
 
+    def packed_gd_test(self, emb, diag, alpha, pow_method):
+        """Testing hook (include/cge_hip_testing.h: cge_packed_gd_test): the packed form's extrema pass and generator on an
+        embedding (N, d) with `diag` on the diagonal of D.  Returns ((lo, hi), GD (N, N)): GD is written for j >= i and inside
+        the diagonal 64 x 64 tiles; everything else stays NaN."""
+        emb, diag = _f64(emb), _f64(diag)
+        N, d = emb.shape
+        assert diag.shape == (N,)
+        lo_hi, GD = np.zeros(2), np.full((N, N), np.nan)
+        self._check(self.L.cge_packed_gd_test(self.h, _p(emb), _p(diag), C.c_int64(N), C.c_int64(d), C.c_double(alpha),
+                                              C.c_int(pow_method), _p(lo_hi), _p(GD)))
+        return lo_hi, GD
+
     def vect_b_test(self, GD, Ta, Tb, comm, C_, directed=False, form=0, landmarks=False, vC=None, n_modes=1, second=None,
                     vB=None):
         """Testing hook (include/cge_hip_testing.h: cge_vect_b_test): vect_B of one problem by a named form of the sweep
@@ -989,7 +1001,8 @@ class Context:
         self._check(self.L.cge_louvain(self.h, _p(out), C.byref(nc), C.byref(q), C.byref(rounds)))
         return out, nc.value, q.value, rounds.value
 
-    _TEST_OPTIONS = ("fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel")
+    _TEST_OPTIONS = ("fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
+                     "exact_resident_limit")
 
     def set_option(self, key, value):
         if key in self._TEST_OPTIONS:  # the testing knobs are not part of the boundary (include/cge_hip_testing.h)

@@ -321,6 +321,9 @@ int cge_set_option(cge_ctx *c, const char *key, int64_t value) {
     // undirected score itself does not read it); 0 (default): on first fetch
     if (is("landmark_edges")) return flag(c->opt_landmark_edges);
     // iterations after which a Chung-Lu fit that has not converged raises CGE_E_ASSERT (default 2 000 000)
+    // an undirected exact sweep on the upper tiles of the current alpha's GD alone (about 4 N^2 bytes instead of 17.6 - 28 N^2):
+    // 0 (default) = where the resident matrices would be refused, 1 = wherever the form applies (N >= 256, C >= 2, exact_relabel)
+    if (is("exact_packed")) return ranged(c->opt_exact_packed, 0, 1);
     if (is("fit_max_iterations")) return ranged(c->opt_fit_max_iters, 1, INT64_MAX);
     return CGE_E_ARG;
 }
@@ -336,6 +339,8 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     if (!strcmp(key, "fit_persistent_test_delay") && value >= 0 && value <= 100000) { c->opt_fit_test_delay = (int)value; return CGE_OK; }
     // 1 = the persistent fit abandons every launch at once
     if (!strcmp(key, "fit_persistent_test_timeout")) { c->opt_fit_test_timeout = value != 0; return CGE_OK; }
+    // bytes that replace the 200e9 of the resident exact sweep's guard (0: the default)
+    if (!strcmp(key, "exact_resident_limit") && value >= 0) { c->opt_test_resident_limit = (double)value; return CGE_OK; }
     return CGE_E_ARG;
 }
 int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
@@ -350,6 +355,8 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "diameter_arg_j")) *value = c->stat_hi_j + 1;
     else if (!strcmp(key, "fit_persistent_alphas")) *value = c->stat_fit_persistent;
     else if (!strcmp(key, "fit_iterations")) *value = c->stat_fit_iters;
+    else if (!strcmp(key, "exact_packed")) *value = c->stat_exact_packed; // the last sweep ran on the packed upper tiles
+    else if (!strcmp(key, "exact_matrix_bytes")) *value = c->stat_exact_matrix_bytes; // O(N^2) device bytes the last exact sweep required
     else if (!strcmp(key, "fit_fused_alphas")) *value = c->stat_fit_fused; // alphas of the last sweep whose chain rode on the fit's launch
     else if (!strcmp(key, "fit_persistent_fallbacks")) *value = c->stat_fit_fallbacks;
     else if (!strcmp(key, "fit_batched_launches")) *value = c->stat_fit_batched_launches;
@@ -498,6 +505,16 @@ int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method
     if (!c || !x || !out || n <= 0) return CGE_E_ARG;
     CGE_TRY(c)
     k_pow_test(c, x, n, alpha, method, out);
+    CGE_CATCH(c)
+}
+
+// testing hook (include/cge_hip_testing.h): the packed form's extrema pass and generator on a caller's embedding
+int cge_packed_gd_test(void *ctx, const double *emb, const double *diag, int64_t N, int64_t d, double alpha, int pow_method,
+                       double *lo_hi, double *GD) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !emb || !diag || !lo_hi || !GD || N <= 0 || d <= 0 || (pow_method != 0 && pow_method != 1)) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_packed_gd_test(c, emb, diag, N, d, alpha, pow_method, lo_hi, GD);
     CGE_CATCH(c)
 }
 

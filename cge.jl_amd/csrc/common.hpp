@@ -369,6 +369,14 @@ struct cge_ctx {
     DevBuf<double> sw_D, sw_GD, sw_T1, sw_T2, sw_S1, sw_S2, sw_rowbins, sw_vectB, sw_scal, sw_lohi, sw_fitstate, sw_mm;
     DevBuf<int> sw_flags;
     DevBuf<unsigned long long> sw_fring;
+    // The packed form of an undirected exact sweep (wgcl_host.cpp): GD of the current alpha as its upper 64 x 64 tiles only
+    // (cge_packed_index below), made from the embedding rows every alpha; no D, no logarithm, no row-major GD
+    DevBuf<double> sw_PK;
+    int opt_exact_packed = 0;           // 0 auto (where the resident matrices would be refused), 1 whenever the form applies
+    double opt_test_resident_limit = 0; // testing: replaces the 200e9 bytes of the resident form's guard (0: the default)
+    i64 stat_exact_packed = 0;          // the last sweep ran packed
+    i64 stat_exact_matrix_bytes = 0;    // O(N^2) device bytes the last exact sweep required
+    bool sweep_used_fp_P = false;       // the running sweep fitted an alpha by one launch pair per iteration (fp_P)
     // persistent Chung-Lu fit (kernels_fitp.hip): T double buffer, partial vectors, per-workgroup maxima, barrier words
     DevBuf<double> fp_T, fp_Tsave, fp_P, fp_fpart, fp_Td, fp_flow;
     DevBuf<double> ls_eigscr;            // wide eigen-solver: partial vectors of its tile sweeps (kernels_lm.hip)
@@ -763,6 +771,11 @@ void k_louvain_level1(cge_ctx *c, i64 *comm_out_host, i64 *n_comm, double *quali
 void k_dist_matrix(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double *D);
 void k_minmax_upper(cge_ctx *c, const double *D, i64 N, double *lo_hi);
 void k_normalise(cge_ctx *c, double *D, i64 N, const double *lo_hi);
+// The packed form of an exact sweep (kernels_dist.hip): the extrema of D over j >= i without storing D, and GD of one alpha
+// straight from the embedding rows into the upper tiles (cge_packed_index).  pow_method: 1 = exp2 of the logarithm, 0 = library pow
+void k_packed_extrema(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double *lo_hi);
+void k_packed_gd(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, const double *lo_hi, double alpha,
+                 int pow_method, double *PK);
 void k_max_pair(cge_ctx *c, const double *Xc, const double *rnorm, i64 n, i64 ldn, i64 dpad, int part, int nparts,
                 double *best_val, i64 *best_i, i64 *best_j, std::vector<double> *wg_best = nullptr);
 void k_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi, const i32 *pj, i64 S, double inv_scale_den,
@@ -910,7 +923,8 @@ struct cge_js_problem { const double *vC, *vB; i64 len, C; int mode, pad; double
 struct cge_bins_multi { cge_bins_problem p[CGE_BATCH_MAX]; };
 struct cge_js_multi { cge_js_problem p[2 * CGE_BATCH_MAX]; }; // (--split-global: two entries per problem)
 void k_bins_js_multi(cge_ctx *c, const cge_bins_multi &bins, int n_bins, i64 max_C, const cge_js_multi &js, int n_js);
-void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_off, i64 N, int directed); // the tile partials only
+void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_off, i64 N, int directed,
+                  bool packed = false); // the tile partials only (packed: GD is the upper tiles of cge_packed_index, undirected)
 void k_auc_prepare(cge_ctx *c, const i32 *v2l, const i32 *old2new, const double *vw_orig, const double *lweight, const i32 *pi,
                    const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, i32 *aidx, double *afac, double *aden);
 void k_bvec_bins(cge_ctx *c, const i32 *cm_off, i64 N, i64 C, int directed, double *vectB); // folds the tile partials into vect_B
@@ -920,7 +934,7 @@ bool k_fit_persistent_dir(cge_ctx *c, const double *GD, i64 N, double *Tin, doub
 void k_fit_verdict(cge_ctx *c, const int *flags, int async, double *out); // 1.0 when an enqueued fit was abandoned
 // the same iteration over the upper 64 x 64 tiles only (kernels_fitp.hip): half the matrix traffic
 void k_fit_sym_step(cge_ctx *c, const double *GD, const double *Tin, double *Tout, const double *w, i64 N, double eps,
-                double delta, int k, unsigned long long *fring, int *done, int *iters);
+                double delta, int k, unsigned long long *fring, int *done, int *iters, bool packed = false);
 void k_fit_symv_dir(cge_ctx *c, const double *GD, const double *Tin, const double *Tout, i64 N, double *Sin,
                     double *Sout, const int *done);
 void k_fit_update_dir(cge_ctx *c, double *Tin, double *Tout, const double *Sin, const double *Sout,
@@ -935,7 +949,8 @@ void k_auc_landmark(cge_ctx *c, const double *Ta, const double *Tb, const i32 *v
                     const double *lweight, const i32 *pi, const i32 *pj, const i32 *ni, const i32 *nj,
                     const double *dpos, const double *dneg, const double *wts, i64 S, double alpha, double *out2, double *partials = nullptr);
 void k_auc_exact(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, i64 N, const i32 *pi,
-                 const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, double *out2, double *partials = nullptr);
+                 const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, double *out2, double *partials = nullptr,
+                 bool packed = false);
 void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out); // kernels_fit.hip: out[k] = arr[idx[k]]
 void k_mark_edge_hits(cge_ctx *c, const i32 *src, const i32 *dst, i64 m, int directed, const uint64_t *table,
                       i64 table_size, i32 *hit);
@@ -959,6 +974,32 @@ double host_diameter_landmarks(cge_ctx *c, const double *lemb, const double *lwe
 void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lcomm1, i64 C, int pass, double *P, i64 *nref_out,
                                int *pass_ran, double *ref_out, double *mean_out);
 // wgcl_host.cpp
+// ---- the packed form of an exact sweep's matrix: the NT = Nt (Nt + 1) / 2 upper 64 x 64 tiles (Nt = ceil(N / 64)), 4096 doubles
+// each, in row-major order of the upper triangle (fit_symtile_kernel's numbering of t).  Diagonal tiles are stored whole, elements
+// outside the matrix are 0.  Inside a tile the fit's lane 8 rq + cq owns the 8 x 8 block of rows 8 rq.., columns 8 cq..; the
+// element (a, b) of that block sits at ((4 a + b / 2) * 64 + lane) * 2 + b % 2, so that each of the fit's 32 two-double loads is
+// one contiguous kilobyte over the wave.  Every producer and consumer -- device and host -- addresses the buffer through these.
+#define CGE_TILE_DOUBLES 4096
+__host__ __device__ inline i64 cge_upper_tile(i64 I, i64 J, i64 Nt) { return I * Nt - I * (I - 1) / 2 + (J - I); } // I <= J
+__host__ __device__ inline int cge_tile_slot(int r, int q) { // row r, column q of the tile
+    const int lane = 8 * (r >> 3) + (q >> 3), a = r & 7, b = q & 7;
+    return ((4 * a + (b >> 1)) * 64 + lane) * 2 + (b & 1);
+}
+// element (i, j) of the symmetric matrix; below the diagonal tiles the mirrored element (j, i) is the one stored
+__host__ __device__ inline i64 cge_packed_index(i64 i, i64 j, i64 Nt) {
+    if ((i >> 6) > (j >> 6)) { const i64 s = i; i = j; j = s; }
+    return cge_upper_tile(i >> 6, j >> 6, Nt) * CGE_TILE_DOUBLES + cge_tile_slot((int)(i & 63), (int)(j & 63));
+}
+// tile t of the row-major upper triangle -> (I, J): start(I) = I Nt - I (I - 1) / 2
+__host__ __device__ inline void cge_upper_tile_of(i64 t, i64 Nt, i64 &I, i64 &J) {
+    const double bb = 2.0 * (double)Nt + 1.0;
+    I = (i64)((bb - sqrt(bb * bb - 8.0 * (double)t)) * 0.5);
+    if (I < 0) I = 0;
+    if (I > Nt - 1) I = Nt - 1;
+    while (I + 1 < Nt && (I + 1) * Nt - (I + 1) * I / 2 <= t) I++;
+    while (I > 0 && I * Nt - I * (I - 1) / 2 > t) I--;
+    J = I + (t - (I * Nt - I * (I - 1) / 2));
+}
 // ---- counter-based RNG of the sampler (splitmix64 finaliser over a 4-word counter): the same stream on host and device
 __host__ __device__ inline uint64_t cge_sm64(uint64_t x) {
     x += 0x9e3779b97f4a7c15ULL;
@@ -1039,6 +1080,8 @@ struct AlphaBook {
     void write(double out[7], int *out_len) const; // the reference's 7-vector (:256)
 };
 struct cge_vect_b_problem; // (include/cge_hip_testing.h)
+void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
+                         double *GD);
 void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b_problem *p2, int directed, int form,
                       int landmarks, int n_modes, int *form_ran); // the testing hook of vect_B's forms (wgcl_host.cpp)
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,

@@ -1,6 +1,8 @@
 // kernels_dist.hip -- distance kernels.
 //   k_dist_matrix : D[i,j] = dist(i,j,embed), diagonal = distances[i]      src/divergence.jl:79-91
 //   k_minmax_upper / k_normalise : lo,hi = extrema(D); D = (D-lo)/(hi-lo)  src/divergence.jl:92-93
+//   k_packed_extrema / k_packed_gd : the same three, and the power, tile by tile for the packed form of an exact
+//                   sweep -- only the upper tiles of the current alpha's GD are stored   src/divergence.jl:79-93, :142-148
 //   k_max_pair    : arg-max of all n(n-1)/2 pairwise distances (the `hi` of
 //                   extrema(full_graph_D), never materialised)             src/divergence.jl:104-113
 //   k_pair_dist   : distances of sampled pairs                              src/divergence.jl:189,198
@@ -16,15 +18,10 @@
 // unfused sub/mul/add, i.e. the arithmetic of dist() (src/auxilary.jl:14-20) term for term.
 #define DT 64
 #define DK 16
-__global__ __launch_bounds__(256) void dist_matrix_kernel(const double *__restrict__ emb,
-                                                          const double *__restrict__ diag, i64 N, i64 d,
-                                                          double *__restrict__ D) {
-    __shared__ double As[DT][DK + 1], Bs[DT][DK + 1];
-    const i64 bi = blockIdx.y, bj = blockIdx.x;
-    if (bj < bi) return; // upper triangle of tiles; the mirror is written by the same block
-    const i64 i0 = bi * DT, j0 = bj * DT;
-    const int ty = threadIdx.x / 16, tx = threadIdx.x % 16; // thread tile rows ty*4.., cols tx*4..
-    double acc[4][4];
+// The squared distances of the 64 x 64 tile at (i0, j0), thread (ty, tx) its 4 x 4 sub-tile: shared by the matrix kernel and the
+// packed form's kernels below, so that all of them add the same terms in the same order.
+__device__ __forceinline__ void tile_dist2(const double *__restrict__ emb, i64 N, i64 d, i64 i0, i64 j0, int ty, int tx,
+                                           double (*As)[DK + 1], double (*Bs)[DK + 1], double acc[4][4]) {
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
@@ -54,6 +51,17 @@ __global__ __launch_bounds__(256) void dist_matrix_kernel(const double *__restri
                 }
         }
     }
+}
+__global__ __launch_bounds__(256) void dist_matrix_kernel(const double *__restrict__ emb,
+                                                          const double *__restrict__ diag, i64 N, i64 d,
+                                                          double *__restrict__ D) {
+    __shared__ double As[DT][DK + 1], Bs[DT][DK + 1];
+    const i64 bi = blockIdx.y, bj = blockIdx.x;
+    if (bj < bi) return; // upper triangle of tiles; the mirror is written by the same block
+    const i64 i0 = bi * DT, j0 = bj * DT;
+    const int ty = threadIdx.x / 16, tx = threadIdx.x % 16; // thread tile rows ty*4.., cols tx*4..
+    double acc[4][4];
+    tile_dist2(emb, N, d, i0, j0, ty, tx, As, Bs, acc);
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
@@ -137,6 +145,121 @@ __global__ void normalise_kernel(double *__restrict__ D, i64 total, const double
 }
 void k_normalise(cge_ctx *c, double *D, i64 N, const double *lo_hi) {
     hipLaunchKernelGGL(normalise_kernel, dim3(grid_for(N * N, 256)), dim3(256), 0, c->stream, D, N * N, lo_hi);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The packed form of an exact sweep (wgcl_host.cpp): nothing N x N but the upper tiles of the current alpha's GD.
+// Extrema of D over j >= i (diagonal = diag, src/divergence.jl:92): the workgroups stride over the upper tiles, every thread keeps
+// the extrema of its elements, one (lo, hi) per workgroup; minmax_final_kernel folds them.  min / max are order-free, so the two
+// scalars carry the bits of k_minmax_upper on the stored matrix.
+#include "pow_parts.hpp"
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+#define PK_MM_BLOCKS 4096
+__global__ __launch_bounds__(256) void packed_extrema_kernel(const double *__restrict__ emb, const double *__restrict__ diag, i64 N,
+                                                             i64 d, i64 Nt, i64 NT, double *__restrict__ part) {
+    __shared__ double As[DT][DK + 1], Bs[DT][DK + 1];
+    __shared__ double slo[256], shi[256];
+    const int ty = threadIdx.x / 16, tx = threadIdx.x % 16;
+    double lo = INFINITY, hi = -INFINITY;
+    for (i64 t = blockIdx.x; t < NT; t += gridDim.x) {
+        i64 I, J;
+        cge_upper_tile_of(t, Nt, I, J);
+        double acc[4][4];
+        tile_dist2(emb, N, d, I * DT, J * DT, ty, tx, As, Bs, acc);
+#pragma unroll
+        for (int a = 0; a < 4; a++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const i64 i = I * DT + ty * 4 + a, j = J * DT + tx * 4 + b;
+                if (i < N && j < N && j >= i) {
+                    const double v = (i == j) ? diag[i] : sqrt(acc[a][b]);
+                    lo = fmin(lo, v);
+                    hi = fmax(hi, v);
+                }
+            }
+    }
+    slo[threadIdx.x] = lo;
+    shi[threadIdx.x] = hi;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            slo[threadIdx.x] = fmin(slo[threadIdx.x], slo[threadIdx.x + s]);
+            shi[threadIdx.x] = fmax(shi[threadIdx.x], shi[threadIdx.x + s]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = slo[0];
+        part[2 * blockIdx.x + 1] = shi[0];
+    }
+}
+void k_packed_extrema(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double *lo_hi) {
+    const i64 Nt = (N + DT - 1) / DT, NT = Nt * (Nt + 1) / 2;
+    const int nb = (int)std::min<i64>(NT, PK_MM_BLOCKS);
+    DevBuf<double> &part = c->sw_mm;
+    part.ensure((size_t)2 * nb);
+    {
+        ScopedKernelTimer t(c, "packed_extrema");
+        hipLaunchKernelGGL(packed_extrema_kernel, dim3(nb), dim3(256), 0, c->stream, emb, diag, N, d, Nt, NT, part.p);
+    }
+    hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(256), 0, c->stream, part.p, nb, lo_hi);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+// GD of one alpha, one workgroup per upper tile: dist_matrix_kernel's distances, normalise_kernel's two operations, the power by
+// pow_parts.hpp (POW_EXP2: log_parts then exp2_parts, the bits of log_matrix_kernel + exp2_matrix_kernel) or the library pow, and
+// the tile stored packed -- two neighbouring columns per store; a diagonal tile holds both halves, each from its own (i, j), which
+// compute the same value (the squared difference does not notice the order of its operands).  Outside the matrix: 0.
+template <bool POW_EXP2>
+__global__ __launch_bounds__(256) void packed_gd_kernel(const double *__restrict__ emb, const double *__restrict__ diag, i64 N, i64 d,
+                                                        i64 Nt, const double *__restrict__ lo_hi, double alpha,
+                                                        double *__restrict__ PK) {
+    __shared__ double As[DT][DK + 1], Bs[DT][DK + 1];
+    const i64 t = blockIdx.x;
+    i64 I, J;
+    cge_upper_tile_of(t, Nt, I, J);
+    const int ty = threadIdx.x / 16, tx = threadIdx.x % 16;
+    double acc[4][4];
+    tile_dist2(emb, N, d, I * DT, J * DT, ty, tx, As, Bs, acc);
+    const double lo = lo_hi[0], den = lo_hi[1] - lo_hi[0];
+    double *tile = PK + t * CGE_TILE_DOUBLES;
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const i64 i = I * DT + ty * 4 + a, j = J * DT + tx * 4 + b;
+            double g = 0.0;
+            if (i < N && j < N) {
+                const double v = (i == j) ? diag[i] : sqrt(acc[a][b]);
+                const double x = (v - lo) / den;
+                if (POW_EXP2) {
+                    double Lh;
+                    float Ll;
+                    log_parts(x, Lh, Ll);
+                    g = exp2_parts(alpha, Lh, Ll);
+                } else
+                    g = pow(1.0 - x, alpha);
+            }
+            acc[a][b] = g;
+        }
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b += 2) {
+            dbl2 v;
+            v.x = acc[a][b];
+            v.y = acc[a][b + 1];
+            *reinterpret_cast<dbl2 *>(tile + cge_tile_slot(ty * 4 + a, tx * 4 + b)) = v;
+        }
+}
+void k_packed_gd(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, const double *lo_hi, double alpha,
+                 int pow_method, double *PK) {
+    ScopedKernelTimer t(c, "packed_gd");
+    const i64 Nt = (N + DT - 1) / DT, NT = Nt * (Nt + 1) / 2;
+    if (NT > 0x7fffffffLL) CGE_THROW(CGE_E_ARG, "packed exact sweep: %lld tiles exceed a launch", (long long)NT);
+    if (pow_method)
+        hipLaunchKernelGGL(packed_gd_kernel<true>, dim3((unsigned)NT), dim3(256), 0, c->stream, emb, diag, N, d, Nt, lo_hi, alpha, PK);
+    else
+        hipLaunchKernelGGL(packed_gd_kernel<false>, dim3((unsigned)NT), dim3(256), 0, c->stream, emb, diag, N, d, Nt, lo_hi, alpha, PK);
 }
 
 // ------------------------------------------------------------------------------------------------

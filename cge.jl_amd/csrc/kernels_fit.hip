@@ -462,6 +462,8 @@ __global__ void bvec_fold_kernel(const double *__restrict__ Z, i64 C, int direct
 // partials of the tiles its rectangle touches (I ascending, then J): every sum has a fixed order, nothing is atomic, GD is
 // read once, and the row bins (N x C doubles written and read back) are gone: 57 -> ~20 us per alpha at the headline.
 // fc[b] / ns[b]: first community and number of communities (empty ones included) of the 64-vertex block b.
+// PACKED (undirected): GD is the upper tiles alone (common.hpp: cge_packed_index); the same products from the same elements.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void bvec_tile_kernel(const double *__restrict__ GD, const double *__restrict__ Ta,
                                                         const double *__restrict__ Tb, const i32 *__restrict__ cm_off,
                                                         const i32 *__restrict__ fc, const i32 *__restrict__ ns,
@@ -485,7 +487,7 @@ __global__ __launch_bounds__(256) void bvec_tile_kernel(const double *__restrict
         for (int u = 0; u < 16; u++) {
             const i64 i = (i64)64 * I + 16 * w + u;
             const bool live = i < N && j < N && (directed || j >= i);
-            g[u] = live ? GD[i * N + j] : 0.0;
+            g[u] = live ? GD[PACKED ? cge_packed_index(i, j, Nt) : i * N + j] : 0.0;
         }
 #pragma unroll
         for (int u = 0; u < 16; u++) {
@@ -563,11 +565,17 @@ __global__ __launch_bounds__(256) void bvec_bins_multi_kernel(const cge_bins_mul
         q.vectB[C * ca - ca * (ca - 1) / 2 + (cb - ca)] = acc;
     }
 }
-void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_off, i64 N, int directed) {
+void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_off, i64 N, int directed,
+                  bool packed) {
     ScopedKernelTimer t(c, "bvec");
     const int Nt = (int)((N + 63) / 64);
-    hipLaunchKernelGGL(bvec_tile_kernel, dim3((unsigned)Nt, (unsigned)Nt), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off, c->sw_bt_fc.p,
-                       c->sw_bt_ns.p, c->sw_bt_base.p, N, Nt, directed, c->sw_bt_part.p);
+    if (packed && directed) CGE_THROW(CGE_E_ASSERT, "vect_B by tiles: the packed matrix is undirected");
+    if (packed)
+        hipLaunchKernelGGL(bvec_tile_kernel<true>, dim3((unsigned)Nt, (unsigned)Nt), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off,
+                           c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, N, Nt, directed, c->sw_bt_part.p);
+    else
+        hipLaunchKernelGGL(bvec_tile_kernel<false>, dim3((unsigned)Nt, (unsigned)Nt), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off, c->sw_bt_fc.p,
+                           c->sw_bt_ns.p, c->sw_bt_base.p, N, Nt, directed, c->sw_bt_part.p);
 }
 void k_bvec_bins(cge_ctx *c, const i32 *cm_off, i64 N, i64 C, int directed, double *vectB) {
     ScopedKernelTimer t(c, "bvec");
@@ -590,7 +598,7 @@ void k_bvec(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, co
     if (form == 0) form = k_bvec_form(c, N);
     if (form == 4) {
         const int Nt = (int)((N + 63) / 64);
-        hipLaunchKernelGGL(bvec_tile_kernel, dim3((unsigned)Nt, (unsigned)Nt), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off, c->sw_bt_fc.p,
+        hipLaunchKernelGGL(bvec_tile_kernel<false>, dim3((unsigned)Nt, (unsigned)Nt), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off, c->sw_bt_fc.p,
                            c->sw_bt_ns.p, c->sw_bt_base.p, N, Nt, directed, c->sw_bt_part.p);
         hipLaunchKernelGGL(bvec_bins_kernel, dim3(grid_for(C * C, 256, 1024)), dim3(256), 0, c->stream, c->sw_bt_part.p, cm_off,
                            c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, C, Nt, directed, vectB);
@@ -981,6 +989,8 @@ void k_auc_prepare(cge_ctx *c, const i32 *v2l, const i32 *old2new, const double 
     hipLaunchKernelGGL(auc_prepare_kernel, dim3(AUC_BLOCKS), dim3(256), 0, c->stream, v2l, old2new, vw_orig, lweight, pi, pj, ni, nj,
                        wts, S, aidx, afac, aden);
 }
+// PACKED: GD is the upper tiles alone and N is their count per side, Nt (common.hpp: cge_packed_index takes any (i, j))
+template <bool PACKED>
 __global__ __launch_bounds__(256) void auc_exact_kernel(const double *__restrict__ GD, const double *__restrict__ Ta,
                                                         const double *__restrict__ Tb, i64 N,
                                                         const i32 *__restrict__ pi, const i32 *__restrict__ pj,
@@ -991,8 +1001,8 @@ __global__ __launch_bounds__(256) void auc_exact_kernel(const double *__restrict
     double num = 0.0, den = 0.0;
     for (i64 k = (i64)blockIdx.x * 256 + threadIdx.x; k < S; k += (i64)gridDim.x * 256) {
         const i64 i = pi[k], j = pj[k], u = ni[k], v = nj[k];
-        const double pos = (Ta[i] * Tb[j]) * GD[i * N + j];
-        const double neg = (Ta[u] * Tb[v]) * GD[u * N + v];
+        const double pos = (Ta[i] * Tb[j]) * GD[PACKED ? cge_packed_index(i, j, N) : i * N + j];
+        const double neg = (Ta[u] * Tb[v]) * GD[PACKED ? cge_packed_index(u, v, N) : u * N + v];
         const double w = wts[k];
         num += (pos > neg ? 1.0 : 0.0) * w;
         den += w;
@@ -1049,19 +1059,20 @@ void k_auc_landmark(cge_ctx *c, const double *Ta, const double *Tb, const i32 *v
     if (!partials) hipLaunchKernelGGL(auc_final_kernel, dim3(1), dim3(64), 0, c->stream, part, AUC_BLOCKS, out2);
 }
 void k_auc_exact(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, i64 N, const i32 *pi,
-                 const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, double *out2, double *partials) {
+                 const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, double *out2, double *partials, bool packed) {
     ScopedKernelTimer t(c, "auc_tally");
     double *own = auc_partials(c);
     double *part = partials ? partials : own;
-    if (S >= AUC_WIDE_MIN_SAMPLES) {
-        double *wide = own + 2 * AUC_BLOCKS;
-        hipLaunchKernelGGL(auc_exact_kernel, dim3(AUC_BLOCKS * AUC_WIDE), dim3(256), 0, c->stream, GD, Ta, Tb, N, pi, pj, ni,
-                           nj, wts, S, wide);
-        hipLaunchKernelGGL(auc_fold_kernel, dim3(1), dim3(64), 0, c->stream, wide, part);
-    } else {
-        hipLaunchKernelGGL(auc_exact_kernel, dim3(AUC_BLOCKS), dim3(256), 0, c->stream, GD, Ta, Tb, N, pi, pj, ni, nj, wts,
-                           S, part);
-    }
+    const bool is_wide = S >= AUC_WIDE_MIN_SAMPLES;
+    double *wide = own + 2 * AUC_BLOCKS;
+    const dim3 grid(is_wide ? AUC_BLOCKS * AUC_WIDE : AUC_BLOCKS);
+    if (packed) // (the kernel's N: the tiles per side)
+        hipLaunchKernelGGL(auc_exact_kernel<true>, grid, dim3(256), 0, c->stream, GD, Ta, Tb, (N + 63) / 64, pi, pj, ni, nj, wts, S,
+                           is_wide ? wide : part);
+    else
+        hipLaunchKernelGGL(auc_exact_kernel<false>, grid, dim3(256), 0, c->stream, GD, Ta, Tb, N, pi, pj, ni, nj, wts, S,
+                           is_wide ? wide : part);
+    if (is_wide) hipLaunchKernelGGL(auc_fold_kernel, dim3(1), dim3(64), 0, c->stream, wide, part);
     if (!partials) hipLaunchKernelGGL(auc_final_kernel, dim3(1), dim3(64), 0, c->stream, part, AUC_BLOCKS, out2);
 }
 

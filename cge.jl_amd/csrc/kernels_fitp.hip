@@ -214,6 +214,9 @@ __global__ __launch_bounds__(64 * NW) void fit_flow_multi_kernel(const cge_flow_
 // order-free) in fring[k % 3]; the launch of iteration k + 1 starts by reading f_k -- when it is <= delta the fit is over
 // (iters = k + 1, the final T is the one iteration k wrote, exactly the reference's `while diff > delta`) and every later
 // launch of the batch returns at `*done`; fring[(k+1) % 3] is cleared by iteration k for iteration k + 1.  Traffic per iteration: 4 N^2 (+ N^2 / 4 for the partial vectors) instead of 8 N^2 bytes.
+// PACKED: GD is the upper tiles alone (common.hpp: cge_packed_index) -- lane 8 rq + cq finds its 8 x 8 block of tile t through
+// cge_tile_slot, zeros outside the matrix included, and does the same FMAs and additions on it.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void fit_symtile_kernel(const double *__restrict__ GD, const double *__restrict__ T, i64 N,
                                                           int Nt, i64 NT, double delta, int k,
                                                           const unsigned long long *__restrict__ fring,
@@ -236,7 +239,17 @@ __global__ __launch_bounds__(256) void fit_symtile_kernel(const double *__restri
     const i64 J = I + (t - (I * Nt - I * (I - 1) / 2));
     const i64 r0 = 64 * I + 8 * rq, c0 = 64 * J + 8 * cq;
     double g[8][8];
-    if ((N & 1) == 0 && r0 + 8 <= N && c0 + 8 <= N) { // the common case: 16-byte loads, no guards
+    if (PACKED) {
+        const double *tile = GD + t * CGE_TILE_DOUBLES;
+#pragma unroll
+        for (int a = 0; a < 8; a++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const dbl2f v = *reinterpret_cast<const dbl2f *>(tile + cge_tile_slot(8 * rq + a, 8 * cq + 2 * b));
+                g[a][2 * b] = v.x;
+                g[a][2 * b + 1] = v.y;
+            }
+    } else if ((N & 1) == 0 && r0 + 8 <= N && c0 + 8 <= N) { // the common case: 16-byte loads, no guards
 #pragma unroll
         for (int a = 0; a < 8; a++) {
             const dbl2f *row = reinterpret_cast<const dbl2f *>(GD + (r0 + a) * N + c0);
@@ -589,13 +602,17 @@ __global__ __launch_bounds__(64 * NW) void fit_flow_dir_kernel(const double *__r
 } // namespace
 
 void k_fit_sym_step(cge_ctx *c, const double *GD, const double *Tin, double *Tout, const double *w, i64 N, double eps,
-                    double delta, int k, unsigned long long *fring, int *done, int *iters) {
+                    double delta, int k, unsigned long long *fring, int *done, int *iters, bool packed) {
     const int Nt = (int)((N + 63) / 64);
     const i64 NT = (i64)Nt * (Nt + 1) / 2;
     c->fp_P.ensure((size_t)Nt * Nt * 64);
     ScopedKernelTimer t(c, "fit_symv");
-    hipLaunchKernelGGL(fit_symtile_kernel, dim3((unsigned)((NT + 3) / 4)), dim3(256), 0, c->stream, GD, Tin, N, Nt, NT, delta, k,
-                       fring, done, c->fp_P.p);
+    if (packed)
+        hipLaunchKernelGGL(fit_symtile_kernel<true>, dim3((unsigned)((NT + 3) / 4)), dim3(256), 0, c->stream, GD, Tin, N, Nt, NT, delta,
+                           k, fring, done, c->fp_P.p);
+    else
+        hipLaunchKernelGGL(fit_symtile_kernel<false>, dim3((unsigned)((NT + 3) / 4)), dim3(256), 0, c->stream, GD, Tin, N, Nt, NT, delta, k,
+                           fring, done, c->fp_P.p);
     hipLaunchKernelGGL(fit_symreduce_kernel, dim3((unsigned)Nt), dim3(256), 0, c->stream, c->fp_P.p, Tin, Tout, w, N, Nt, eps,
                        delta, k, fring, done, iters);
 }

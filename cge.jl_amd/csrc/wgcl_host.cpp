@@ -113,8 +113,9 @@ struct SweepLayout {
 // device when the tiles apply), c->bvec_blocks / c->bvec_contig and, for a relabelled sweep, the order (lay.cm_mem) and its
 // inverse on the device.  landmarks: a landmark-mode sweep.  force_relabel: the testing hook's contiguous-row form below 8193
 // vertices (every sweep passes false).  Shared by plan_layout and the testing hook cge_vect_b_test.
+// packed_req: the sweep wants the packed form of its matrix, which goes with the tile form of vect_B at any N >= 256.
 static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int directed, bool landmarks, bool force_relabel,
-                          SweepLayout &lay) {
+                          SweepLayout &lay, bool packed_req = false) {
     std::vector<i32> &cm_off = lay.cm_off, &cm_mem = lay.cm_mem;
     // community -> members CSR of the score graph
     cm_off.assign(C + 1, 0);
@@ -140,7 +141,7 @@ static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int direct
     // profiles/r04_bvec_tiles_ab.txt); landmark-mode sweeps always do (below).
     // (beyond 8192 vertices the sweep is relabelled anyway and the staged row-bin kernel no longer fits LDS: there the tile
     // form replaces the plain gather -- config 5, N = 12 000: 1.1 ms per alpha for the row bins alone)
-    const bool blocks_req = (c->opt_bvec_blocks || N > 8192) && c->opt_exact_relabel && N >= 256 && C >= 2 &&
+    const bool blocks_req = (c->opt_bvec_blocks || N > 8192 || packed_req) && c->opt_exact_relabel && N >= 256 && C >= 2 &&
                             !c->opt_test_bvec_plain;
     // Round 5, the default in landmark mode wherever the undirected persistent fit runs with one tile per wave: the rest of
     // an alpha's chain RIDES ON THE FIT'S LAUNCH (kernels_fitp.hip, fit_flow_kernel<.., true>: the power matrix in its
@@ -210,7 +211,7 @@ static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int direct
 }
 
 // The layout decision, the tile tables and the relabelled copies of the score graph's per-vertex arrays (G points at them then).
-static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay) {
+static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay, bool packed_req) {
     const i64 N = G.N, d = G.d;
     std::vector<i32> hcomm(N);
     if (orig && orig->h_lcomm) std::memcpy(hcomm.data(), orig->h_lcomm, sizeof(i32) * N); // (the caller read them back for the diameter)
@@ -218,7 +219,7 @@ static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int dir
         HIP_CHECK(hipMemcpyAsync(hcomm.data(), G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    layout_tables(c, hcomm.data(), N, G.C, directed, orig != nullptr, false, lay);
+    layout_tables(c, hcomm.data(), N, G.C, directed, orig != nullptr, false, lay, packed_req);
     if (!lay.relabel) return;
     const DevBuf<i32> &d_order = c->sw_rl_order;
     std::vector<i32> &cm_mem = lay.cm_mem;
@@ -252,13 +253,18 @@ static void community_tables(cge_ctx *c, const SweepLayout &lay, i64 N, i64 C, W
 
 // D and its normalisation (:79-93 / :359-375), the community tables on the device, the starting T (:118) / Tin, Tout
 // (:399-402), and TT, the three parts T rotates through in an undirected sweep.  Returns TT's leading dimension.
-static i64 prepare_distances(cge_ctx *c, const ScoreGraph &G, const SweepLayout &lay, int directed) {
+// packed: only lo, hi -- D is never stored; every alpha makes its GD from the embedding rows (k_packed_gd).
+static i64 prepare_distances(cge_ctx *c, const ScoreGraph &G, const SweepLayout &lay, int directed, bool packed) {
     const i64 N = G.N, C = G.C;
     hipStream_t st = c->stream;
     double *D = c->sw_D.p, *T1 = c->sw_T1.p, *T2 = c->sw_T2.p;
-    k_dist_matrix(c, G.emb, G.dist, N, G.d, D);
-    k_minmax_upper(c, D, N, c->sw_lohi.p);
-    k_normalise(c, D, N, c->sw_lohi.p);
+    if (packed)
+        k_packed_extrema(c, G.emb, G.dist, N, G.d, c->sw_lohi.p);
+    else {
+        k_dist_matrix(c, G.emb, G.dist, N, G.d, D);
+        k_minmax_upper(c, D, N, c->sw_lohi.p);
+        k_normalise(c, D, N, c->sw_lohi.p);
+    }
     WordPacker pk(c);
     std::vector<i32> cm_pos;
     community_tables(c, lay, N, C, pk, cm_pos);
@@ -485,11 +491,11 @@ static i64 fit_by_launches(cge_ctx *c, i64 prev_iters, double alpha, const int *
 // kernels_fitp.hip) is only enqueued -- with the rest of the alpha's chain riding on it when `ff` is given (ff_dev: its
 // device copy) -- and its verdict is looked at when the alpha is collected; else one launch per iteration (k_fit_sym_step,
 // over the upper tiles only).  `upper`: GD's upper triangle suffices (the power matrix made here when the fused launch does not
-// apply after all).
-static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double alpha, bool upper,
+// apply after all).  `packed`: the matrix is the upper tiles in sw_PK (never persistent).
+static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double alpha, bool upper, bool packed,
                            const cge_fit_fused *ff, const cge_fit_fused *ff_dev, FitForm &fit, AlphaSlot &sl) {
     hipStream_t st = c->stream;
-    double *const GD = c->sw_GD.p, *const TT = c->fp_T.p;
+    double *const GD = packed ? c->sw_PK.p : c->sw_GD.p, *const TT = c->fp_T.p;
     int *flags = c->sw_flags.p;
     if (!fit.persistent) HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
     sl.t0_par = fit.tpar;
@@ -512,8 +518,10 @@ static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double a
     // T alternates between two parts of TT
     HIP_CHECK(hipMemsetAsync(c->sw_fring.p, 0, sizeof(unsigned long long) * 4, st));
     double *Tb2[2] = {TT + (i64)fit.tpar * Tld, TT + (i64)((fit.tpar + 1) % 3) * Tld};
+    c->sweep_used_fp_P = true;
     sl.iters = fit_by_launches(c, fit.prev_iters, alpha, flags, c->sw_fring.p, [&](i64 k) {
-        k_fit_sym_step(c, GD, Tb2[k & 1], Tb2[(k + 1) & 1], w, N, 0.25, AlphaBook::delta, (int)k, c->sw_fring.p, flags, flags + 1);
+        k_fit_sym_step(c, GD, Tb2[k & 1], Tb2[(k + 1) & 1], w, N, 0.25, AlphaBook::delta, (int)k, c->sw_fring.p, flags, flags + 1,
+                       packed);
     });
     if (sl.iters & 1) fit.tpar = (fit.tpar + 1) % 3;
 }
@@ -552,11 +560,11 @@ static void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm 
 // The local score's tallies of one alpha (samples [s0, s1) of `ds`: this rank's share) into the block partials of the scalars.
 // Landmark mode reads T through the landmark ids of the original numbering: a relabelled sweep (old2new) un-permutes it first.
 static void local_score_tallies(cge_ctx *c, const double *Ta, const double *Tb, i64 N, int directed, const OrigView *orig,
-                                const i32 *old2new, const DevSamples &ds, i64 s0, i64 s1, double alpha) {
+                                const i32 *old2new, const DevSamples &ds, i64 s0, i64 s1, double alpha, bool packed) {
     double *part = c->sw_scal.p + RES_AUC;
     if (!orig) {
-        k_auc_exact(c, c->sw_GD.p, Ta, Tb, N, ds.pi.p + s0, ds.pj.p + s0, ds.ni.p + s0, ds.nj.p + s0, ds.wts.p + s0, s1 - s0,
-                    nullptr, part);
+        k_auc_exact(c, packed ? c->sw_PK.p : c->sw_GD.p, Ta, Tb, N, ds.pi.p + s0, ds.pj.p + s0, ds.ni.p + s0, ds.nj.p + s0,
+                    ds.wts.p + s0, s1 - s0, nullptr, part, packed);
         return;
     }
     if (old2new) {
@@ -575,17 +583,19 @@ static void local_score_tallies(cge_ctx *c, const double *Ta, const double *Tb, 
 
 // vect_B and its divergence(s) of one alpha (want_div), then the alpha's scalars to pinned slot `slot` and an event.
 // bvec_partials: vect_B's tile partials came with the fit.  arm: the next alpha's persistent fit may take its hand-off slots
-// armed by this alpha's last launch.
+// armed by this alpha's last launch.  packed: GD is the upper tiles in sw_PK (vect_B goes by tiles then).
 static void divergence_and_copy_out(cge_ctx *c, const ScoreGraph &G, int directed, int split, const double *Ta,
-                                    const double *Tb, bool want_div, bool bvec_partials, bool arm, i64 Tld, int slot) {
+                                    const double *Tb, bool want_div, bool bvec_partials, bool arm, i64 Tld, int slot, bool packed) {
     hipStream_t st = c->stream;
     const i64 N = G.N, C = G.C, vlen = directed ? C * C : packed_len(C);
-    const double *GD = c->sw_GD.p;
+    const double *GD = packed ? c->sw_PK.p : c->sw_GD.p;
+    if (packed && want_div && !(c->bvec_blocks && !directed && !c->opt_test_bvec_plain))
+        CGE_THROW(CGE_E_ASSERT, "packed exact sweep without the tile form of vect_B");
     const i32 *cm_off = c->sw_cm_off.p;
     double *scal = c->sw_scal.p, *vectB = c->sw_vectB.p, *host_out = c->pin_scal.p + RES_STRIDE * slot;
     if (want_div && (bvec_partials || c->bvec_blocks) && !directed && !c->opt_test_bvec_plain) {
         // tile partials (from the fit's epilogue, or one pass over GD) -> vect_B and its divergence(s) in one launch
-        if (!bvec_partials) k_bvec_tiles(c, GD, Ta, Tb, cm_off, N, directed);
+        if (!bvec_partials) k_bvec_tiles(c, GD, Ta, Tb, cm_off, N, directed, packed);
         // the last launch of the alpha: it also hands the alpha's scalars to the host's pinned slot and arms the hand-off
         // slots of the next alpha's persistent fit (instead of a copy and a fill of their own)
         cge_chain_tail tail{};
@@ -626,6 +636,7 @@ struct SweepView {
     const std::vector<cge_fit_fused> &h_epi;
     i64 n_sets, s0, s1;   // sample sets; this rank's samples of each
     bool shard;           // the tallies are split over the ranks
+    bool packed;          // an exact sweep on the upper tiles of the current alpha's GD alone (sw_PK)
 };
 
 // One alpha's chain on the stream: pow, the fit, the local score's tallies, vect_B, JS, the scalars -> pinned slot (ia mod 2), an
@@ -641,7 +652,8 @@ static void enqueue_alpha(cge_ctx *c, const SweepView &sw, i64 ia, bool want_auc
     sl = AlphaSlot();
     const bool fused_now = sw.fuse && fit.persistent && c->pow_logs_blocked_N == N; // (a fallback in mid-sweep ends it: the matrix is needed then)
     if (sw.fuse && !fused_now && c->pow_logs_N != N) k_pow_prepare(c, c->sw_D.p, N, upper); // (left the fused path: the row-major logarithm)
-    if (!fused_now) k_pow_matrix(c, c->sw_D.p, N, alpha, c->sw_GD.p, upper);
+    if (sw.packed) k_packed_gd(c, G.emb, G.dist, N, G.d, c->sw_lohi.p, alpha, c->opt_pow_exp2, c->sw_PK.p);
+    else if (!fused_now) k_pow_matrix(c, c->sw_D.p, N, alpha, c->sw_GD.p, upper);
     cge_fit_fused ff{};
     if (fused_now) { // this alpha's copy of the epilogue table: what is not wanted is left out
         ff = sw.h_epi[set];
@@ -650,7 +662,7 @@ static void enqueue_alpha(cge_ctx *c, const SweepView &sw, i64 ia, bool want_auc
         if (!(want_auc && sw.fuse_auc)) ff.auc_part = nullptr;
     }
     if (!sw.directed)
-        fit_undirected(c, N, G.vw, sw.Tld, alpha, upper, fused_now ? &ff : nullptr,
+        fit_undirected(c, N, G.vw, sw.Tld, alpha, upper, sw.packed, fused_now ? &ff : nullptr,
                        fused_now ? reinterpret_cast<const cge_fit_fused *>(c->sw_fused_epi.p) + set : nullptr, fit, sl);
     else
         fit_directed(c, G, alpha, fit, sl);
@@ -658,7 +670,7 @@ static void enqueue_alpha(cge_ctx *c, const SweepView &sw, i64 ia, bool want_auc
     const double *Tcur = c->fp_T.p + (i64)fit.tpar * sw.Tld;
     const double *Ta = sw.directed ? c->sw_T2.p : Tcur, *Tb = sw.directed ? c->sw_T1.p : Tcur; // (Tout, Tin)
     if (want_auc && !(sl.fused && ff.auc_part))
-        local_score_tallies(c, Ta, Tb, N, sw.directed, sw.orig, sw.old2new, *c->dsets[set], sw.s0, sw.s1, alpha);
+        local_score_tallies(c, Ta, Tb, N, sw.directed, sw.orig, sw.old2new, *c->dsets[set], sw.s0, sw.s1, alpha, sw.packed);
     if (sw.shard) {
         // The verdict of an enqueued fit is rank-local (a hand-off may time out on one rank only), but a redo re-issues
         // this exchange and changes what the rank enqueues from then on: the ranks must take it together.  So the verdict
@@ -671,10 +683,31 @@ static void enqueue_alpha(cge_ctx *c, const SweepView &sw, i64 ia, bool want_auc
         else cge_allreduce_dev(c, scal + RES_VERD, 1, 0);
     }
     divergence_and_copy_out(c, G, sw.directed, sw.split, Ta, Tb, want_div, sl.fused && ff.partial,
-                            fit.persistent && ia < AlphaBook::n_alpha, sw.Tld, (int)(ia & 1));
+                            fit.persistent && ia < AlphaBook::n_alpha, sw.Tld, (int)(ia & 1), sw.packed);
 }
 
 // ---- the sweep -------------------------------------------------------------------------------------
+
+// The packed form's two O(N^2) buffers: the upper tiles of GD (sw_PK) and the fit's partial vectors (fp_P).  What the context still
+// holds of the resident form from earlier sweeps -- D, GD, the logarithm -- is released first, so that a context that scored a
+// smaller graph can score a large one; then whatever has to grow must fit the free memory.
+static void packed_buffers(cge_ctx *c, i64 N) {
+    const i64 Nt = (N + 63) / 64, NT = Nt * (Nt + 1) / 2;
+    const size_t pk_words = (size_t)NT * CGE_TILE_DOUBLES, fp_words = (size_t)Nt * Nt * 64;
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->sw_D.release(); c->sw_GD.release(); c->sw_Lh.release(); c->sw_Ll.release();
+    c->pow_logs_N = c->pow_logs_blocked_N = 0;
+    size_t need = 0;
+    if (c->sw_PK.n < pk_words) { c->sw_PK.release(); need += pk_words * sizeof(double); }
+    if (c->fp_P.n < fp_words) { c->fp_P.release(); need += fp_words * sizeof(double); }
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b)
+        CGE_THROW(CGE_E_OOM, "exact sweep of %lld vertices: the packed matrix and the fit's partial vectors need %llu bytes, %llu are free",
+                  (long long)N, (unsigned long long)need, (unsigned long long)free_b);
+    c->sw_PK.ensure(pk_words);
+    c->fp_P.ensure(fp_words);
+}
 
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
                      const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],
@@ -682,9 +715,14 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     ScoreGraph G = G_in; // the per-vertex arrays may be replaced by community-sorted copies (plan_layout)
     const i64 N = G.N, C = G.C, S = smp.S;
     const i64 vlen = directed ? C * C : packed_len(C);
-    if ((double)N * (double)N * 8.0 * 2.2 > 200e9) CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit", (long long)N);
-    c->sw_D.ensure((size_t)N * N);
-    c->sw_GD.ensure((size_t)N * N);
+    // The resident form keeps D, GD and (when they fit) the logarithm on the device; beyond its limit an undirected exact sweep
+    // runs PACKED where that form applies (the tile form of vect_B: N >= 256, C >= 2, exact_relabel, the tile tables accept the
+    // layout), option "exact_packed" = 1 wherever it applies.  Directed sweeps stay resident, with the limit.
+    const double resident_limit = c->opt_test_resident_limit > 0 ? c->opt_test_resident_limit : 200e9;
+    const bool beyond = (double)N * (double)N * 8.0 * 2.2 > resident_limit;
+    const bool packed_req = !orig && !directed && (beyond || c->opt_exact_packed == 1);
+    c->stat_exact_packed = 0;
+    if (beyond && !packed_req) CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit", (long long)N);
     c->sw_T1.ensure(N); c->sw_T2.ensure(N); c->sw_S1.ensure(N); c->sw_S2.ensure(N);
     c->sw_rowbins.ensure((size_t)N * C);
     c->sw_vectB.ensure(vlen);
@@ -695,15 +733,27 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     c->sw_fring.ensure(4);
 
     SweepLayout lay;
-    plan_layout(c, G, orig, directed, lay);
-    const i64 Tld = prepare_distances(c, G, lay, directed);
+    plan_layout(c, G, orig, directed, lay, packed_req);
+    const bool packed = packed_req && c->bvec_blocks && !c->opt_test_bvec_plain;
+    if (beyond && !packed)
+        CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit (the packed form of an exact sweep does not apply to it)",
+                  (long long)N);
+    const i64 Nt64 = (N + 63) / 64;
+    if (packed) packed_buffers(c, N);
+    else {
+        c->sw_PK.release(); // (held only while packed sweeps run)
+        c->sw_D.ensure((size_t)N * N);
+        c->sw_GD.ensure((size_t)N * N);
+    }
+    c->sweep_used_fp_P = false;
+    const i64 Tld = prepare_distances(c, G, lay, directed, packed);
     // sample tallies split over the ranks: with the in-library communicator (stream-ordered, no host synchronisation in the
     // enqueued chain) from 10^5 samples on; option "shard_samples" = 2 forces it (tests, also through the hook), 0 disables
     const bool shard = c->has_coll && S >= c->coll.world &&
                        (c->opt_shard_samples == 2 || (c->opt_shard_samples == 1 && c->rccl_comm && S >= 100000));
     fit_sweep_begin(c);
     FitForm fit;
-    fit.persistent = !directed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
+    fit.persistent = !directed && !packed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
                      (c->opt_fit_persistent >= 2 || N >= 128);
     fit.persistent_dir = directed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
                          (c->opt_fit_persistent >= 2 || N >= 128);
@@ -727,13 +777,13 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     // (Round 4 tried the next alpha's power matrix on a side stream beside this alpha's vect_B / JS / AUC: +0.65 ms, the two
     // cross-queue dependencies per alpha cost more than they hid -- profiles/r04_pow_overlap_ab.txt; removed in round 5, when
     // the power matrix moved into the fit's prologue anyway.)
-    const SweepView sw{G, orig, directed, split, Tld, lay.old2new.p, lay.fuse, fuse_auc, h_epi, smp.n_sets, s0, s1, shard};
+    const SweepView sw{G, orig, directed, split, Tld, lay.old2new.p, lay.fuse, fuse_auc, h_epi, smp.n_sets, s0, s1, shard, packed};
     AlphaBook book(S, split, trace);
     AlphaSlot slots[2];
     c->pin_scal.ensure(2 * RES_STRIDE);
     // log2(1 - D) once for the whole sweep (the upper tiles only when every alpha reads only those); a fallback of the
     // persistent fit in mid-sweep makes k_pow_matrix use the library pow for the whole rows it then needs
-    k_pow_prepare(c, c->sw_D.p, N, orig && !directed, lay.fuse);
+    if (!packed) k_pow_prepare(c, c->sw_D.p, N, orig && !directed, lay.fuse);
     i64 next_enqueue = 1;
     for (i64 ia = 1; ia <= AlphaBook::n_alpha; ia++) {
         AlphaSlot &sl = slots[ia & 1];
@@ -775,6 +825,12 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
         if (book.ended()) break;
     }
     book.write(out, out_len);
+    c->stat_exact_packed = packed;
+    if (!orig) { // the O(N^2) device storage this sweep required
+        const i64 fpP = c->sweep_used_fp_P ? Nt64 * Nt64 * 64 * (i64)sizeof(double) : 0;
+        const i64 logs = c->pow_logs_N == N ? N * N * 12 : 0;
+        c->stat_exact_matrix_bytes = packed ? Nt64 * (Nt64 + 1) / 2 * CGE_TILE_DOUBLES * (i64)sizeof(double) + fpP : 16 * N * N + logs + fpP;
+    }
     if (c->stat_fit_persistent > 0 && !c->fit_persistent_broken) c->fit_fallback_streak = 0; // a clean persistent sweep
 }
 
@@ -998,6 +1054,33 @@ void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b
         if (p->js_fused && run >= 5)
             for (int u = 0; u < nm; u++) p->js_fused[u] = vb_fold(hf.data() + (i64)((run == 6 ? q * nm : 0) + u) * CGE_PARTIAL_BLOCKS);
     }
+}
+
+// ---- the testing hook of the packed form (include/cge_hip_testing.h: cge_packed_gd_test) -------------------------------
+// The extrema pass and the generator through the sweep's own launch wrappers on a caller's embedding; the tiles are unpacked on
+// the host through cge_packed_index: GD[i][j] for j >= i, and both halves of the diagonal tiles.
+void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
+                         double *GD) {
+    hipStream_t st = c->stream;
+    const i64 Nt = (N + 63) / 64, NT = Nt * (Nt + 1) / 2;
+    DevBuf<double> demb, ddiag, dlohi, PK;
+    demb.ensure((size_t)N * d); ddiag.ensure(N); dlohi.ensure(2); PK.ensure((size_t)NT * CGE_TILE_DOUBLES);
+    HIP_CHECK(hipMemcpyAsync(demb.p, emb, sizeof(double) * N * d, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(ddiag.p, diag, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    k_packed_extrema(c, demb.p, ddiag.p, N, d, dlohi.p);
+    k_packed_gd(c, demb.p, ddiag.p, N, d, dlohi.p, alpha, pow_method, PK.p);
+    std::vector<double> h((size_t)NT * CGE_TILE_DOUBLES);
+    HIP_CHECK(hipMemcpyAsync(h.data(), PK.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(lo_hi, dlohi.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (i64 i = 0; i < N; i++)
+        for (i64 j = i / 64 * 64; j < N; j++) GD[i * N + j] = h[cge_packed_index(i, j, Nt)];
+    for (i64 I = 0; I < Nt; I++) // outside the matrix: zeros, which the fit adds unmasked
+        for (i64 J = I; J < Nt; J++)
+            for (i64 r = 0; r < 64; r++)
+                for (i64 q = 0; q < 64; q++)
+                    if ((64 * I + r >= N || 64 * J + q >= N) && h[cge_packed_index(64 * I + r, 64 * J + q, Nt)] != 0.0)
+                        CGE_THROW(CGE_E_ASSERT, "packed_gd_test: a non-zero outside the matrix (tile %lld, %lld)", (long long)I, (long long)J);
 }
 
 // ---- small helpers ---------------------------------------------------------------------------------

@@ -95,6 +95,15 @@ typedef struct cge_vect_b_problem {
 } cge_vect_b_problem;
 int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_problem *p2, int directed, int form, int landmarks,
                     int n_modes, int *form_ran);
+/* kernel-level hook (needs the GPU): the packed form of an exact sweep (cge_hip.h, option "exact_packed") on a caller's
+ * embedding, through the sweep's own launch wrappers -- the extrema pass (lo_hi[0], lo_hi[1] = extrema of D over j >= i with
+ * diag on the diagonal, D never stored) and the generator of one alpha (distances, normalisation, power; pow_method 1 = exp2 of
+ * the logarithm, 0 = the library pow).  The upper tiles are unpacked on the host through the address inline every consumer uses:
+ * GD (N x N, row-major) is written for j >= i and, inside the diagonal 64 x 64 tiles, for j < i too (those tiles are stored
+ * whole); the rest of each row is left as the caller filled it.  Any N >= 1 (the N >= 256 rule belongs to the sweep).
+ * CGE_E_ASSERT when a tile element outside the matrix is not 0 */
+int cge_packed_gd_test(void *ctx, const double *emb /* N x d row-major, host */, const double *diag /* N */, int64_t N, int64_t d,
+                       double alpha, int pow_method, double *lo_hi /* 2 */, double *GD /* N x N row-major, host */);
 /* needs the GPU and a communicator (cge_comm_init_rccl; one rank is enough): host array -> device -> the in-library
  * ncclAllReduce (op 0 sum / 1 max of doubles, 2 sum of the words as int64) -> host */
 int cge_rccl_selftest(void *ctx, double *host_inout, int64_t count, int op);
@@ -111,6 +120,9 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *                                 under contention);
  *   "fit_persistent_test_timeout" 1: the persistent fit abandons every launch at once (the fallback path runs);
  *   "test_bvec_plain"             1: vect_B by the kernels of score graphs beyond the LDS budget / 512 communities;
+ *   "exact_resident_limit"        b: b bytes replace the 200e9 of the resident exact sweep's guard, so that the auto rule of
+ *                                 option "exact_packed" and the CGE_E_OOM refusal can be driven at a few hundred vertices (0: the
+ *                                 default).  This one does change which form runs;
  *   "test_rss2_one_kernel"        1: rss2 by the one-kernel walk (rss2_walk_kernel) at every width, d <= 128 included, where the
  *                                 chain + merge form runs otherwise: the two forms give the same bits.                           */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
