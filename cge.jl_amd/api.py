@@ -1001,7 +1001,24 @@ class Context:
         self._check(self.L.cge_louvain(self.h, _p(out), C.byref(nc), C.byref(q), C.byref(rounds)))
         return out, nc.value, q.value, rounds.value
 
-    _TEST_OPTIONS = ("fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
+    def louvain_levels(self, max_levels=0):
+        """The Louvain hierarchy of the resident graph (cge_louvain_levels): a list with one (comm 0-based (n,) of the ORIGINAL
+        vertices, n_comm, modularity, rounds) per level; entry 0 is `louvain()`'s result.  max_levels > 0 stops there; otherwise
+        the hierarchy ends at the first level that merges nothing (not reported, except level 1)."""
+        count, cap = C.c_int64(), (int(max_levels) if 0 < int(max_levels) < 8 else 8)  # (a count-only call would run the whole hierarchy once more; beyond 8 levels it is run again)
+        while True:
+            comm = np.zeros((cap, self.n), dtype=np.int64)
+            nc, q, rounds = np.zeros(cap, dtype=np.int64), np.zeros(cap), np.zeros(cap, dtype=np.int64)
+            rc = self.L.cge_louvain_levels(self.h, C.c_int64(int(max_levels)), C.c_int64(cap), _p(comm), C.byref(count), _p(nc),
+                                           _p(q), _p(rounds))
+            if rc == -7 and count.value > cap:  # CGE_E_ARG that names the count
+                cap = count.value
+                continue
+            self._check(rc)
+            break
+        return [(comm[l], int(nc[l]), float(q[l]), int(rounds[l])) for l in range(count.value)]
+
+    _TEST_OPTIONS = ("louvain_wave_len", "fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
                      "exact_resident_limit")
 
     def set_option(self, key, value):

@@ -38,7 +38,7 @@ METHODS = {
 USAGE = (
     "\n\nUsage:\n"
     "\tpython cge_cli.py -g edgelist -e embedding [-c communities] [--seed seed] [--samples-local samples] [-v] [-d] "
-    "[--split-global] [-l [landmarks]] [-f [forced]] [--force-exact] [-m method]\n"
+    "[--split-global] [-l [landmarks]] [-f [forced]] [--force-exact] [-m method] [--louvain-level level]\n"
 )
 
 
@@ -83,7 +83,11 @@ def parseargs(argv=None, exit_on_error=True, embedding_reader=None):
     arrays (empty dict when no landmarks are requested, as in the reference :173,:199-208).
 
     `embedding_reader(file, no_vertices)` (optional) reads the `-e` file instead of `read_embedding`; what it returns is
-    handed back as it is (cge_compare.py: `.npy` files in their own dtype)."""
+    handed back as it is (cge_compare.py: `.npy` files in their own dtype).
+
+    `--louvain-level K` is an EXTENSION, the reference has no such flag: without `-c` the communities are level K of the Louvain
+    hierarchy (K >= 1: level K, or the last level when the hierarchy is shorter; -1: the last level) instead of the level 1 the
+    reference writes.  The flag is consulted only when `-c` is absent; absent flag means level 1."""
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
         verbose = "-v" in argv
@@ -116,10 +120,13 @@ def parseargs(argv=None, exit_on_error=True, embedding_reader=None):
         else:  # :115-121: no -c => Louvain communities (level 1) of the graph itself, written to <edgelist>.ecg
             from .clustering import louvain_clust
 
+            level = int(_flag_value(argv, "--louvain-level")) if "--louvain-level" in argv else 1  # (an extension)
+            if level < 1 and level != -1:
+                raise AssertionError("--louvain-level is 1, 2, ... or -1 (the last level)")
             if no_cols == 2:
-                louvain_clust(float(v_min), fn_edges)
+                louvain_clust(float(v_min), fn_edges, level=level)
             else:
-                louvain_clust(fn_edges, edges, eweights)
+                louvain_clust(fn_edges, edges, eweights, level=level)
             fn_comm = fn_edges + ".ecg"
         comm_raw, _ = _readdlm(fn_comm)
         if not np.all(comm_raw == np.floor(comm_raw)):

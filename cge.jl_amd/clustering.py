@@ -5,6 +5,9 @@ The reference shells out to three executables of ``louvain_jll`` through files i
 line has no ``-c`` (src/auxilary.jl:115-121).  Here the communities come from the device (``cge_louvain``,
 csrc/kernels_louvain.hip) and the same file is written.  The reference visits the vertices in an unseeded random order,
 so its own runs do not agree with each other; quality (modularity) is what the tests compare.
+
+An extension: ``level=`` asks for another level of the hierarchy that the reference's ``louvain -l -1`` computes and its
+``hierarchy -l 1`` throws away (src/clustering.jl:20-24), through ``cge_louvain_levels``.
 """
 from __future__ import annotations
 
@@ -17,22 +20,31 @@ def _write_ecg(path, ids, comm):
         f.write("\n")
 
 
-def _communities(edges1, weights, ctx):
+def _communities(edges1, weights, ctx, level=1):
     """edges1: (m, 2) 1-based int64; returns comm (n,) for vertices 1..n, 0-based consecutive labels."""
     from . import api
 
+    level = int(level)
+    if level < 1 and level != -1:
+        raise ValueError("louvain_clust: level is 1, 2, ... or -1 (the last level)")
     ctx = ctx or api.default_context()
     n = int(edges1.max())
     ctx.set_graph(np.asfortranarray(edges1), np.ones(len(edges1)) if weights is None else weights, n)
-    comm, n_comm, q, rounds = ctx.louvain()
+    if level == 1:
+        comm, n_comm, q, rounds = ctx.louvain()
+    else:  # level k, or the last when the hierarchy is shorter (-1: the last)
+        comm, n_comm, q, rounds = ctx.louvain_levels(max_levels=max(level, 0))[-1]
     return comm, n_comm, q
 
 
-def louvain_clust(*args, ctx=None):
+def louvain_clust(*args, ctx=None, level=1):
     """``louvain_clust(v_min::Float64, edges::String)`` (src/clustering.jl:14-29) or
     ``louvain_clust(filename::String, edges::Array{Int,2}, weights::Array{Float64,1})`` (:42-68).  Writes
     ``<file>.ecg`` with one "vertex community" line per vertex, vertex ids in the edge file's own base (the reference
-    drops the phantom vertex 0 of a 1-based file, :25-28)."""
+    drops the phantom vertex 0 of a 1-based file, :25-28).
+
+    ``level`` (keyword only; an extension, the reference always writes level 1): k >= 1 writes level k of the Louvain
+    hierarchy, or its last level if it has fewer; -1 writes the last level."""
     from . import api
 
     if len(args) == 2:
@@ -40,13 +52,13 @@ def louvain_clust(*args, ctx=None):
         raw, _ = api.read_table(path, column_major=False)
         e = raw[:, :2].astype(np.int64)
         shift = 1 if float(v_min) == 0.0 else 0
-        comm, _, _ = _communities(e + shift, None, ctx)
+        comm, _, _ = _communities(e + shift, None, ctx, level)
         n = len(comm)
         _write_ecg(path + ".ecg", np.arange(n) + (1 - shift), comm)
         return path + ".ecg"
     if len(args) == 3:
         filename, edges, weights = args
-        comm, _, _ = _communities(np.asarray(edges, dtype=np.int64), np.asarray(weights, dtype=np.float64), ctx)
+        comm, _, _ = _communities(np.asarray(edges, dtype=np.int64), np.asarray(weights, dtype=np.float64), ctx, level)
         _write_ecg(filename + ".ecg", np.arange(len(comm)) + 1, comm)  # the weighted form always drops row 0 (:67)
         return filename + ".ecg"
     raise TypeError("louvain_clust(v_min, edges_file) or louvain_clust(filename, edges, weights)")

@@ -278,6 +278,20 @@ int cge_louvain(cge_ctx *c, int64_t *comm_out, int64_t *n_comm, double *modulari
     k_louvain_level1(c, comm_out, n_comm, modularity, rounds);
     CGE_CATCH(c)
 }
+// the hierarchy (src/clustering.jl:20-24: `louvain -l -1` computes every level, `hierarchy -l 1` keeps the first)
+int cge_louvain_levels(cge_ctx *c, int64_t max_levels, int64_t levels_cap, int64_t *comm_out, int64_t *n_levels, int64_t *n_comm,
+                       double *modularity, int64_t *rounds) {
+    if (!c || !n_levels || levels_cap < 0) return CGE_E_ARG;
+    if (levels_cap > 0 && (!comm_out || !n_comm || !modularity || !rounds)) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    if (!c->src.p || c->m <= 0 || c->n <= 0) CGE_THROW(CGE_E_ARG, "louvain: no resident graph (cge_set_graph)");
+    if (c->edges_sharded) CGE_THROW(CGE_E_ARG, "louvain: the resident edge list is sharded over the ranks (option shard_ingest)");
+    *n_levels = k_louvain_levels(c, max_levels, levels_cap, comm_out, n_comm, modularity, rounds);
+    if (levels_cap > 0 && *n_levels > levels_cap)
+        CGE_THROW(CGE_E_ARG, "louvain: the hierarchy has %lld levels, the caller's arrays hold %lld", (long long)*n_levels,
+                  (long long)levels_cap);
+    CGE_CATCH(c)
+}
 
 // ---- options / statistics ---------------------------------------------------------------------------
 int cge_set_option(cge_ctx *c, const char *key, int64_t value) {
@@ -340,6 +354,8 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     // 1 = the persistent fit abandons every launch at once
     if (!strcmp(key, "fit_persistent_test_timeout")) { c->opt_fit_test_timeout = value != 0; return CGE_OK; }
     // bytes that replace the 200e9 of the resident exact sweep's guard (0: the default)
+    // Louvain levels >= 2: segments longer than this are decided by a wave (-2: the default, -1: every vertex, 2^31 - 1: none)
+    if (!strcmp(key, "louvain_wave_len") && value >= -2 && value <= INT32_MAX) { c->opt_test_louvain_wave_len = value; return CGE_OK; }
     if (!strcmp(key, "exact_resident_limit") && value >= 0) { c->opt_test_resident_limit = (double)value; return CGE_OK; }
     return CGE_E_ARG;
 }

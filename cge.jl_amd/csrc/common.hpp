@@ -413,6 +413,8 @@ struct cge_ctx {
     int opt_shard_samples = 1; // N > 1: 1 = local-score tallies split over the ranks from 10^5 samples on (in-library RCCL), 2 = always, 0 = never
     int opt_shard_forced = 1; // N > 1: the forced per-community phase of runsplit is split over the ranks
     int opt_test_rss2_one_kernel = 0; // testing: rss2 by rss2_walk_kernel at every width (the comparator of the chain + merge form)
+    i64 opt_test_louvain_wave_len = -2; // testing: Louvain levels >= 2 decide segments longer than this by a wave (-2: the default
+                                        // length, -1: every vertex, 2^31 - 1: none); the results must not depend on it
     int opt_test_bvec_plain = 0; // testing: vect_B without LDS staging / rows in flight (the forms of very large score graphs)
     int opt_fit_persistent = 0; // 0 auto (score graphs of >= 128 vertices that fit the register file), 1 never, 2 whenever it fits
     i64 opt_fit_max_iters = 2000000; // a Chung-Lu fit that has not met `diff <= delta` (src/divergence.jl:151,434) after this many
@@ -767,6 +769,8 @@ void k_compact_count(cge_ctx *c, const double *wedges, i64 N, int directed, i64 
 void k_wedge_degrees_block(cge_ctx *c, const double *wedges, i64 N, i64 row0, i64 row1, double *out3N);
 void k_degrees_unpack(cge_ctx *c, const double *in3N, i64 N, double *deg_out, double *deg_in, i32 *star);
 void k_louvain_level1(cge_ctx *c, i64 *comm_out_host, i64 *n_comm, double *quality, i64 *rounds); // kernels_louvain.hip
+// the whole hierarchy (or its first max_levels > 0 levels): returns their number, writes the first levels_cap of them
+i64 k_louvain_levels(cge_ctx *c, i64 max_levels, i64 levels_cap, i64 *comm_out_host, i64 *n_comm, double *quality, i64 *rounds);
 // distances
 void k_dist_matrix(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double *D);
 void k_minmax_upper(cge_ctx *c, const double *D, i64 N, double *lo_hi);

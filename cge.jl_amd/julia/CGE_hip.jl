@@ -154,6 +154,21 @@ function vertex_weights(c::Ctx, n::Integer)
     return out
 end
 
+# The Louvain hierarchy of the resident graph (cge_louvain_levels; src/clustering.jl:20-24 keeps level 1 of it): one
+# (comm 0-based of the n original vertices, n_comm, modularity, rounds) per level; max_levels <= 0: until a level merges nothing
+function louvain_levels(c::Ctx, n::Integer; max_levels::Integer = 0)
+    count = Ref{Int64}(0)
+    check(c, ccall((:cge_louvain_levels, LIB), Cint,
+                   (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                   c.h, max_levels, 0, C_NULL, count, C_NULL, C_NULL, C_NULL))
+    cap = count[]
+    comm, nc, q, rounds = Matrix{Int64}(undef, n, cap), Vector{Int64}(undef, cap), Vector{Float64}(undef, cap), Vector{Int64}(undef, cap)
+    check(c, ccall((:cge_louvain_levels, LIB), Cint,
+                   (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                   c.h, max_levels, cap, comm, count, nc, q, rounds))
+    return [(comm[:, l], nc[l], q[l], rounds[l]) for l in 1:count[]]
+end
+
 # clusters derived from the resident communities (src/auxilary.jl:199-208): n_clusters = -1, the two pointers are ignored
 function landmarks_run_from_comm!(c::Ctx, land::Int, forced::Int, method::Function, directed::Bool)
     N, ne, trunc = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)

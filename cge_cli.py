@@ -6,6 +6,9 @@ ONLY thing on stdout, printed the way Julia's `println(::Vector{Float64})` print
 evaluated alpha and a newline go to stderr (src/divergence.jl:140,255).
 
     python cge_cli.py -g graph.edgelist -c graph.ecg -e graph.embedding -l 200 --seed 42
+
+An extension, not a flag of the reference: without `-c`, `--louvain-level K` takes level K of the Louvain hierarchy of the
+graph (-1: the last level) for the communities instead of level 1.
 """
 import os
 import sys

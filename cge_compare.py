@@ -8,6 +8,8 @@ A `-e` file ending in `.npy` is an (n, d) array, rows in vertex order; it is map
 dtype (float64 / float32 / float16), so `.npy` files of different dtype and width can be mixed with text embeddings.
 
     python cge_compare.py -g graph.edgelist -c graph.ecg -e a.embedding -e b.embedding -l 200 --seed 42
+
+As in cge_cli.py, `--louvain-level K` (an extension; the reference has no such flag) chooses the Louvain level when `-c` is absent.
 """
 import os
 import sys

@@ -323,6 +323,20 @@ int cge_score_views(cge_ctx *ctx, const cge_score_args *args, const cge_embeddin
  * the device.  comm_out[v] (v = 0 .. n-1) in 0 .. *n_comm-1; *modularity = modularity of that partition.  The reference
  * visits the vertices in an unseeded random order, so partitions are comparable in quality, not in identity.            */
 int cge_louvain(cge_ctx *ctx, int64_t *comm_out, int64_t *n_comm, double *modularity, int64_t *rounds);
+/* The whole hierarchy.  The reference runs `louvain -l -1`, which computes every level, and `hierarchy -l 1` then keeps the
+ * first (src/clustering.jl:20-24); here a caller may ask for level 2, 3, or the last.  Level L + 1 is the same pass on level
+ * L's graph contracted by level L's communities (`partition2graph_binary`), and the hierarchy ends at the first level that
+ * merges nothing; that level is not reported, except level 1, which always is and equals cge_louvain's result.  So every
+ * reported level after the first has strictly fewer communities than the one before.
+ * Row l of comm_out (levels_cap x n, level-major) = level l + 1's community of every ORIGINAL vertex, 0-based and consecutive;
+ * n_comm[l], modularity[l] (of that partition on the resident graph), rounds[l] go with it.  *n_levels = the number of levels
+ * the hierarchy has under max_levels (<= 0: until a level merges nothing).  levels_cap = 0 (every array may be NULL) asks for
+ * that number alone; more levels than levels_cap > 0 is CGE_E_ARG, with *n_levels set and named in the message, and the first
+ * levels_cap rows written.  Argument checks as cge_louvain: no resident graph, or a sharded edge list, is CGE_E_ARG.
+ * On integer and dyadic weights every level is determined to the bit; on other weights only the quality is comparable.  */
+int cge_louvain_levels(cge_ctx *ctx, int64_t max_levels /* <= 0: until a level merges nothing */, int64_t levels_cap,
+                       int64_t *comm_out /* levels_cap x n, level-major; may be NULL with levels_cap 0 */, int64_t *n_levels,
+                       int64_t *n_comm /* [levels_cap] */, double *modularity /* [levels_cap] */, int64_t *rounds /* [levels_cap] */);
 
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */

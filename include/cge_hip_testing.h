@@ -123,6 +123,8 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *   "exact_resident_limit"        b: b bytes replace the 200e9 of the resident exact sweep's guard, so that the auto rule of
  *                                 option "exact_packed" and the CGE_E_OOM refusal can be driven at a few hundred vertices (0: the
  *                                 default).  This one does change which form runs;
+ *   "louvain_wave_len"            l: levels >= 2 of cge_louvain_levels decide the vertices whose adjacency segment is longer than
+ *                                 l by one wave each (-2: the default length, -1: every vertex, 2^31 - 1: none, the lane form alone);
  *   "test_rss2_one_kernel"        1: rss2 by the one-kernel walk (rss2_walk_kernel) at every width, d <= 128 included, where the
  *                                 chain + merge form runs otherwise: the two forms give the same bits.                           */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
