@@ -104,6 +104,13 @@ class VectBProblem(C.Structure):
 
 VECT_B_GUARD = 64  # CGE_VECT_B_GUARD
 
+
+class FitProblem(C.Structure):
+    """cge_fit_problem (include/cge_hip_testing.h): one problem of the testing hook cge_fit_test."""
+    _fields_ = [("D", C.c_void_p), ("w", C.c_void_p), ("w2", C.c_void_p), ("T0", C.c_void_p), ("T0b", C.c_void_p),
+                ("T", C.c_void_p), ("Tb", C.c_void_p), ("GD", C.c_void_p), ("N", C.c_int64), ("alpha", C.c_double),
+                ("iters", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32)]
+
 DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
 _NP_DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
 
@@ -927,6 +934,46 @@ class Context:
                                            C.c_int(form), C.c_int(int(landmarks)), C.c_int(n_modes), C.byref(ran)))
         out["form_ran"] = ran.value
         return out
+
+    def fit_test(self, problems, directed=False, form=0, eps=None, delta=0.001, want_GD=False):
+        """Testing hook (include/cge_hip_testing.h: cge_fit_test): one Chung-Lu fit per problem from a chosen start by a named
+        form of the sweep (0 = what an exact-mode sweep of the shape picks).  A problem is a dict: D (N, N), alpha, w, T0
+        (undirected) or D, alpha, w = deg_in, w2 = deg_out, T0 = Tin, T0b = Tout (directed); several problems are form 5 only.
+        eps defaults to the sweep's (0.25 undirected, 0.9 directed).  Returns (form_ran, [dict(T, Tb, GD, iters, status)]): Tb
+        and GD are None where they do not apply / were not asked for."""
+        if isinstance(problems, dict):
+            problems = [problems]
+        n = len(problems)
+        arr = (FitProblem * n)()
+        keep, outs = [], []
+        for q, pr in zip(arr, problems):
+            D = _f64(pr["D"])
+            N = D.shape[0]
+            assert D.shape == (N, N)
+            w, T0 = _f64(pr["w"]), _f64(pr["T0"])
+            assert w.shape == T0.shape == (N,)
+            T = np.full(N, np.nan)
+            q.D, q.w, q.T0, q.T, q.N, q.alpha = D.ctypes.data, w.ctypes.data, T0.ctypes.data, T.ctypes.data, N, float(pr["alpha"])
+            out = {"T": T, "Tb": None, "GD": None}
+            if directed:
+                w2, T0b, Tb = _f64(pr["w2"]), _f64(pr["T0b"]), np.full(N, np.nan)
+                assert w2.shape == T0b.shape == (N,)
+                q.w2, q.T0b, q.Tb = w2.ctypes.data, T0b.ctypes.data, Tb.ctypes.data
+                out["Tb"] = Tb
+                keep.extend((w2, T0b))
+            if want_GD:
+                out["GD"] = np.full((N, N), np.nan)
+                q.GD = out["GD"].ctypes.data
+            q.iters, q.status = -1, -1
+            keep.extend((D, w, T0))
+            outs.append(out)
+        ran = C.c_int(-1)
+        eps = (0.9 if directed else 0.25) if eps is None else eps
+        self._check(self.L.cge_fit_test(self.h, arr, C.c_int(n), C.c_int(int(directed)), C.c_int(form), C.c_double(eps),
+                                        C.c_double(delta), C.byref(ran)))
+        for q, out in zip(arr, outs):
+            out["iters"], out["status"] = int(q.iters), int(q.status)
+        return ran.value, outs
 
     def segment_sort_test(self, z, offsets):
         """Testing hook: the per-group stable sort of runsplit's projections; returns (sorted z, local permutation)."""

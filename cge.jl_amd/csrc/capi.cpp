@@ -544,6 +544,15 @@ int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_pro
     CGE_CATCH(c)
 }
 
+// testing hook (include/cge_hip_testing.h): one Chung-Lu fit from a caller's start by one named form of the sweep
+int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int directed, int form, double eps, double delta, int *form_ran) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !problems || !form_ran || form < 0 || form > 5 || n_problems < 1) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_fit_test(c, problems, n_problems, directed != 0, form, eps, delta, form_ran);
+    CGE_CATCH(c)
+}
+
 // testing hook (include/cge_hip_testing.h): the per-group stable sort of the projections as runsplit calls it
 int cge_segment_sort_test(void *ctx, const double *z, const int32_t *task_row_off, int64_t T, double *zs_out, int32_t *perm_out) {
     cge_ctx *c = (cge_ctx *)ctx;

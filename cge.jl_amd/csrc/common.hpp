@@ -892,6 +892,7 @@ bool k_fit_flow_enqueue(cge_ctx *c, const double *GD, i64 N, const double *T0, d
                         double eps, double delta, int *dev_flags, const cge_fit_fused *ff = nullptr,
                         const cge_fit_fused *ff_dev = nullptr); // ff_dev: the device copy of *ff the epilogue reads (alpha, partial and
                                                                 // auc_part are taken from *ff: they change per alpha)
+bool k_fit_flow_applies(i64 N, i64 Tld); // the persistent fits' geometry (fit_flow_kernel reading GD, fit_flow_dir_kernel) accepts N on this device
 bool k_fit_flow_fused_applies(cge_ctx *c, i64 N); // the geometry the fused instances exist for (one tile per wave, one quarter block per workgroup)
 void k_bins_prepare(cge_ctx *c, const i32 *cm_off, i64 N, i64 C, i64 n_partials); // once per sweep, behind the tile tables
 // what bins_js_kernel, the last launch of an alpha's chain, does on the way out: the alpha's scalars straight into the host's
@@ -1086,6 +1087,9 @@ struct AlphaBook {
 struct cge_vect_b_problem; // (include/cge_hip_testing.h)
 void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
                          double *GD);
+struct cge_fit_problem; // (include/cge_hip_testing.h)
+void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int form, double eps, double delta,
+                   int *form_ran); // the testing hook of the Chung-Lu fit's forms (wgcl_host.cpp)
 void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b_problem *p2, int directed, int form,
                       int landmarks, int n_modes, int *form_ran); // the testing hook of vect_B's forms (wgcl_host.cpp)
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,

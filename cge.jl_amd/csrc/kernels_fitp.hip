@@ -637,6 +637,10 @@ static bool flow_geometry(i64 N, i64 Tld, int *G_out, int *NW_out, int *tpw_out)
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     return flow_geometry_cus(N, Tld, cus, G_out, NW_out, tpw_out);
 }
+bool k_fit_flow_applies(i64 N, i64 Tld) {
+    int G = 0, NW = 0, tpw = 0;
+    return flow_geometry(N, Tld, &G, &NW, &tpw);
+}
 bool k_fit_flow_fused_applies(cge_ctx *c, i64 N) {
     int G = 0, NW = 0, tpw = 0;
     return flow_geometry(N, (N + 63) / 64 * 64, &G, &NW, &tpw) && tpw == 1 && 4 * (int)((N + 63) / 64) <= G;

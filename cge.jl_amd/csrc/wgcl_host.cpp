@@ -453,19 +453,27 @@ struct AlphaSlot {
 };
 
 // The form of the fit from alpha to alpha (a persistent form, once given up, stays given up for the sweep), the part of TT that
-// holds the current iterate (undirected) and the last iteration count (the first batch of a launch-per-iteration fit)
+// holds the current iterate (undirected) and the last iteration count (the first batch of a launch-per-iteration fit).  eps,
+// delta: the step and the stopping threshold -- a sweep's are the reference's (0.25 undirected :119, 0.9 directed :434; delta
+// :35); the testing hook cge_fit_test passes its caller's.
 struct FitForm {
     bool persistent = false, persistent_dir = false;
     int tpar = 0;
     i64 prev_iters = 16;
+    double eps = 0.25, delta = AlphaBook::delta;
 };
+
+// Whether a sweep starts on the persistent form of its fit (the geometry is asked at the first launch)
+static bool persistent_wanted(const cge_ctx *c, i64 N) {
+    return !c->fit_persistent_broken && c->opt_fit_persistent != 1 && (c->opt_fit_persistent >= 2 || N >= 128);
+}
 
 // One launch (pair) per iteration: `launch(k)` enqueues iteration k, in batches -- the first as long as the previous fit, at
 // most 32 from then on.  After each batch the host reads the fit's flags ([0] done, [1] iterations) and, when `ring` is given,
 // the changes of the undirected fit's last iterations.  Returns the iterations.
 template <class Launch>
-static i64 fit_by_launches(cge_ctx *c, i64 prev_iters, double alpha, const int *flags, const unsigned long long *ring,
-                           Launch launch) {
+static i64 fit_by_launches(cge_ctx *c, i64 prev_iters, double alpha, double delta, const int *flags,
+                           const unsigned long long *ring, Launch launch) {
     hipStream_t st = c->stream;
     i64 batch = std::max<i64>(4, std::min<i64>(prev_iters, 128));
     for (i64 k = 0;;) {
@@ -480,7 +488,7 @@ static i64 fit_by_launches(cge_ctx *c, i64 prev_iters, double alpha, const int *
         if (ring) {
             double flast;
             std::memcpy(&flast, &hr[(k - 1) % 3], sizeof(double));
-            if (!(flast > AlphaBook::delta)) return iters; // the last launch of the batch was the converging iteration (iters == k)
+            if (!(flast > delta)) return iters; // the last launch of the batch was the converging iteration (iters == k)
         }
         if (iters > c->opt_fit_max_iters) CGE_THROW(CGE_E_ASSERT, "Chung-Lu fit did not converge at alpha=%g (%lld iterations; the reference's `while diff > delta` would not return)", alpha, (long long)iters);
         batch = std::max<i64>(4, std::min<i64>(batch, 32));
@@ -501,8 +509,8 @@ static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double a
     sl.t0_par = fit.tpar;
     if (fit.persistent) {
         const int tnext = (fit.tpar + 1) % 3;
-        if (k_fit_flow_enqueue(c, ff ? nullptr : GD, N, TT + (i64)fit.tpar * Tld, TT + (i64)tnext * Tld, Tld, w, 0.25,
-                               AlphaBook::delta, (int *)(c->sw_scal.p + RES_FIT), ff, ff_dev)) {
+        if (k_fit_flow_enqueue(c, ff ? nullptr : GD, N, TT + (i64)fit.tpar * Tld, TT + (i64)tnext * Tld, Tld, w, fit.eps,
+                               fit.delta, (int *)(c->sw_scal.p + RES_FIT), ff, ff_dev)) {
             sl.fused = ff != nullptr;
             sl.fit_async = true;
             fit.tpar = tnext;
@@ -519,8 +527,8 @@ static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double a
     HIP_CHECK(hipMemsetAsync(c->sw_fring.p, 0, sizeof(unsigned long long) * 4, st));
     double *Tb2[2] = {TT + (i64)fit.tpar * Tld, TT + (i64)((fit.tpar + 1) % 3) * Tld};
     c->sweep_used_fp_P = true;
-    sl.iters = fit_by_launches(c, fit.prev_iters, alpha, flags, c->sw_fring.p, [&](i64 k) {
-        k_fit_sym_step(c, GD, Tb2[k & 1], Tb2[(k + 1) & 1], w, N, 0.25, AlphaBook::delta, (int)k, c->sw_fring.p, flags, flags + 1,
+    sl.iters = fit_by_launches(c, fit.prev_iters, alpha, fit.delta, flags, c->sw_fring.p, [&](i64 k) {
+        k_fit_sym_step(c, GD, Tb2[k & 1], Tb2[(k + 1) & 1], w, N, fit.eps, fit.delta, (int)k, c->sw_fring.p, flags, flags + 1,
                        packed);
     });
     if (sl.iters & 1) fit.tpar = (fit.tpar + 1) % 3;
@@ -537,10 +545,10 @@ static void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm 
     double *Tin = c->sw_T1.p, *Tout = c->sw_T2.p;
     int *flags = c->sw_flags.p;
     HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
-    const double init[2] = {0.9, 1.0}; // epsilon, diff (:434-435)
+    const double init[2] = {fit.eps, 1.0}; // epsilon, diff (:434-435)
     HIP_CHECK(hipMemcpyAsync(c->sw_fitstate.p, init, sizeof(init), hipMemcpyHostToDevice, st));
     bool enqueued_only = false;
-    if (fit.persistent_dir && k_fit_persistent_dir(c, GD, N, Tin, Tout, G.deg_in, G.deg_out, 0.9, 1.0, AlphaBook::delta,
+    if (fit.persistent_dir && k_fit_persistent_dir(c, GD, N, Tin, Tout, G.deg_in, G.deg_out, fit.eps, 1.0, fit.delta,
                                                    &sl.iters, (int *)(c->sw_scal.p + RES_FIT), &enqueued_only)) {
         if (enqueued_only) sl.fit_async = true;
         else c->stat_fit_persistent++;
@@ -550,11 +558,23 @@ static void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm 
         fit.persistent_dir = false;
         HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
     }
-    sl.iters = fit_by_launches(c, fit.prev_iters, alpha, flags, nullptr, [&](i64) {
+    sl.iters = fit_by_launches(c, fit.prev_iters, alpha, fit.delta, flags, nullptr, [&](i64) {
         k_fit_symv_dir(c, GD, Tin, Tout, N, c->sw_S1.p, c->sw_S2.p, flags);
-        k_fit_update_dir(c, Tin, Tout, c->sw_S1.p, c->sw_S2.p, G.deg_in, G.deg_out, N, AlphaBook::delta, flags, flags + 1,
+        k_fit_update_dir(c, Tin, Tout, c->sw_S1.p, c->sw_S2.p, G.deg_in, G.deg_out, N, fit.delta, flags, flags + 1,
                          c->sw_fitstate.p);
     });
+}
+
+// An enqueued persistent fit was abandoned: what was enqueued behind it is drained, and this fit and every later one of the
+// sweep go by one launch per iteration -- this one again from its T_0, which is still in place.
+static void leave_persistent(cge_ctx *c, int directed, FitForm &fit, const AlphaSlot &sl) {
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    note_fit_fallback(c);
+    if (directed) fit.persistent_dir = false;
+    else {
+        fit.persistent = false;
+        fit.tpar = sl.t0_par;
+    }
 }
 
 // The local score's tallies of one alpha (samples [s0, s1) of `ds`: this rank's share) into the block partials of the scalars.
@@ -753,10 +773,9 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
                        (c->opt_shard_samples == 2 || (c->opt_shard_samples == 1 && c->rccl_comm && S >= 100000));
     fit_sweep_begin(c);
     FitForm fit;
-    fit.persistent = !directed && !packed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
-                     (c->opt_fit_persistent >= 2 || N >= 128);
-    fit.persistent_dir = directed && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
-                         (c->opt_fit_persistent >= 2 || N >= 128);
+    fit.persistent = !directed && !packed && persistent_wanted(c, N);
+    fit.persistent_dir = directed && persistent_wanted(c, N);
+    fit.eps = directed ? 0.9 : 0.25;
     c->stat_fit_persistent = 0;
     c->stat_fit_iters = 0;
     samples_to_device(c, smp, N, G.d, orig, ex_src, ex_dst, ex_hw, ex_m, directed,
@@ -804,14 +823,8 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
         if (sl.fit_async) {
             const int *hf = (const int *)(res + RES_FIT);
             if (hf[2] || !hf[0] || peer_failed) { // a wait timed out (here or on another rank): drain what was enqueued behind
-                HIP_CHECK(hipStreamSynchronize(c->stream)); // it and redo this alpha from its T_0 (still in place) with one
-                note_fit_fallback(c);                       // launch per iteration, as every later alpha
-                if (directed) fit.persistent_dir = false;
-                else {
-                    fit.persistent = false;
-                    fit.tpar = sl.t0_par;
-                }
-                next_enqueue = ia;
+                leave_persistent(c, directed, fit, sl);     // it and redo this alpha from its T_0 (still in place) with one
+                next_enqueue = ia;                          // launch per iteration, as every later alpha
                 ia--;
                 continue;
             }
@@ -1054,6 +1067,231 @@ void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b
         if (p->js_fused && run >= 5)
             for (int u = 0; u < nm; u++) p->js_fused[u] = vb_fold(hf.data() + (i64)((run == 6 ? q * nm : 0) + u) * CGE_PARTIAL_BLOCKS);
     }
+}
+
+// ---- the testing hook of the Chung-Lu fit (include/cge_hip_testing.h: cge_fit_test) -------------------------------------------
+// One fit from a caller's start through fit_undirected / fit_directed (forms 0-4) or k_fit_flow_multi (form 5), on the buffers a
+// sweep keeps them in.  Everything that can refuse does so before the first launch.
+
+// D to sw_D and, when the form or the caller reads it, GD = (1 - D)^alpha to sw_GD by the sweep's two launches (upper: the upper
+// tiles alone, as a landmark-mode sweep makes it; everything else of sw_GD is NaN) and to the caller's GD
+static void ft_matrices(cge_ctx *c, const cge_fit_problem &p, bool upper, bool need_gd) {
+    hipStream_t st = c->stream;
+    const i64 N = p.N;
+    c->sw_D.ensure((size_t)N * N);
+    HIP_CHECK(hipMemcpyAsync(c->sw_D.p, p.D, sizeof(double) * N * N, hipMemcpyHostToDevice, st));
+    if (need_gd || p.GD) {
+        c->sw_GD.ensure((size_t)N * N);
+        HIP_CHECK(hipMemsetAsync(c->sw_GD.p, 0xFF, sizeof(double) * N * N, st)); // (all bits set: a NaN)
+        k_pow_prepare(c, c->sw_D.p, N, upper);
+        k_pow_matrix(c, c->sw_D.p, N, p.alpha, c->sw_GD.p, upper);
+        if (p.GD) HIP_CHECK(hipMemcpyAsync(p.GD, c->sw_GD.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// the verdict of an enqueued persistent fit: flags [0] converged, [1] iterations, [2] abandoned
+static bool ft_verdict(cge_ctx *c, const int *dev_flags, i64 *iters) {
+    int hf[4];
+    HIP_CHECK(hipMemcpyAsync(hf, dev_flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    *iters = hf[1];
+    return !(hf[2] || !hf[0]);
+}
+
+static int ft_undirected(cge_ctx *c, cge_fit_problem &p, int form, double eps, double delta) {
+    hipStream_t st = c->stream;
+    const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
+    ft_matrices(c, p, true, form != 4);
+    if (form == 2) { // the upper tiles of GD, zeros outside the matrix, through the address inline every consumer uses
+        std::vector<double> h((size_t)N * N), pk((size_t)(Nt * (Nt + 1) / 2) * CGE_TILE_DOUBLES, 0.0);
+        HIP_CHECK(hipMemcpyAsync(h.data(), c->sw_GD.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (i64 i = 0; i < N; i++)
+            for (i64 j = i / 64 * 64; j < N; j++) pk[cge_packed_index(i, j, Nt)] = h[i * N + j];
+        c->sw_PK.ensure(pk.size());
+        HIP_CHECK(hipMemcpyAsync(c->sw_PK.p, pk.data(), sizeof(double) * pk.size(), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (form == 4) k_pow_prepare(c, c->sw_D.p, N, true, true);
+    // T_0 in part 0 of TT (zero beyond N), NaN in the rows of the two other parts
+    DevBuf<double> dw;
+    dw.ensure(N);
+    c->fp_T.ensure((size_t)3 * Tld);
+    c->sw_scal.ensure(RES_STRIDE);
+    c->sw_flags.ensure(4);
+    c->sw_fring.ensure(4);
+    const std::vector<double> nan_n(N, std::nan(""));
+    HIP_CHECK(hipMemsetAsync(c->fp_T.p, 0, sizeof(double) * 3 * Tld, st));
+    HIP_CHECK(hipMemcpyAsync(c->fp_T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->fp_T.p + Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->fp_T.p + 2 * Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dw.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    c->flow_armed_words = 0; // (no alpha of a sweep armed the hand-off slots of this launch)
+    FitForm fit;
+    fit.eps = eps;
+    fit.delta = delta;
+    fit.persistent = form == 3 || form == 4 || (form == 0 && persistent_wanted(c, N));
+    cge_fit_fused ff{};
+    ff.Lh = c->sw_Lh.p; ff.Ll = c->sw_Ll.p; ff.alpha = p.alpha; // (no partial, no auc_part: nothing is wanted of the epilogue)
+    AlphaSlot sl;
+    fit_undirected(c, N, dw.p, Tld, p.alpha, true, form == 2, form == 4 ? &ff : nullptr, nullptr, fit, sl);
+    int ran = form == 2 ? 2 : 1;
+    p.status = 0;
+    if (sl.fit_async) {
+        ran = form == 4 ? 4 : 3;
+        if (!ft_verdict(c, (const int *)(c->sw_scal.p + RES_FIT), &sl.iters)) {
+            if (form == 0) { // as the sweep: again from T_0 with one launch pair per iteration
+                leave_persistent(c, 0, fit, sl);
+                sl = AlphaSlot();
+                fit_undirected(c, N, dw.p, Tld, p.alpha, true, false, nullptr, nullptr, fit, sl);
+                ran = 1;
+            } else
+                p.status = 1;
+        }
+    } else if (form == 3 || form == 4)
+        CGE_THROW(CGE_E_ASSERT, "fit_test: the persistent launch of form %d was declined (N = %lld)", form, (long long)N);
+    p.iters = sl.iters;
+    HIP_CHECK(hipMemcpyAsync(p.T, c->fp_T.p + (i64)fit.tpar * Tld, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (form == 2) c->sw_PK.release(); // (held only while packed sweeps run)
+    return ran;
+}
+
+static int ft_directed(cge_ctx *c, cge_fit_problem &p, int form, double eps, double delta) {
+    hipStream_t st = c->stream;
+    const i64 N = p.N;
+    ft_matrices(c, p, false, true);
+    DevBuf<double> din, dout;
+    din.ensure(N); dout.ensure(N);
+    c->sw_T1.ensure(N); c->sw_T2.ensure(N); c->sw_S1.ensure(N); c->sw_S2.ensure(N);
+    c->sw_scal.ensure(RES_STRIDE);
+    c->sw_flags.ensure(4);
+    c->sw_fitstate.ensure(4);
+    HIP_CHECK(hipMemcpyAsync(c->sw_T1.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->sw_T2.p, p.T0b, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(din.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dout.p, p.w2, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    ScoreGraph G;
+    G.N = N;
+    G.deg_in = din.p; G.deg_out = dout.p;
+    FitForm fit;
+    fit.eps = eps;
+    fit.delta = delta;
+    fit.persistent_dir = form == 3 || (form == 0 && persistent_wanted(c, N));
+    AlphaSlot sl;
+    fit_directed(c, G, p.alpha, fit, sl);
+    int ran = 1;
+    p.status = 0;
+    if (sl.fit_async) {
+        ran = 3;
+        if (!ft_verdict(c, (const int *)(c->sw_scal.p + RES_FIT), &sl.iters)) {
+            if (form == 0) {
+                leave_persistent(c, 1, fit, sl);
+                sl = AlphaSlot();
+                fit_directed(c, G, p.alpha, fit, sl);
+                ran = 1;
+            } else
+                p.status = 1;
+        }
+    } else if (form == 3)
+        CGE_THROW(CGE_E_ASSERT, "fit_test: the persistent launch of form 3 was declined (N = %lld)", (long long)N);
+    p.iters = sl.iters;
+    HIP_CHECK(hipMemcpyAsync(p.T, c->sw_T1.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(p.Tb, c->sw_T2.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return ran;
+}
+
+// form 5: every problem with its own logarithm, T, weights and flags, as the members of a batch keep them (batch_host.cpp)
+static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, int NW, double eps, double delta) {
+    hipStream_t st = c->stream;
+    struct Member {
+        DevBuf<double> Lh, T, w;
+        DevBuf<float> Ll;
+    };
+    std::vector<std::unique_ptr<Member>> mem;
+    DevBuf<int> flags;
+    DevBuf<double> flow;
+    flags.ensure((size_t)4 * n);
+    HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4 * n, st));
+    cge_flow_multi tab{};
+    tab.n = n;
+    for (int i = 0; i < n; i++) {
+        cge_fit_problem &p = probs[i];
+        const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
+        mem.emplace_back(new Member());
+        Member &m = *mem.back();
+        ft_matrices(c, p, true, false);
+        k_pow_prepare(c, c->sw_D.p, N, true, true);
+        HIP_CHECK(hipStreamSynchronize(st));
+        m.Lh.swap(c->sw_Lh); m.Ll.swap(c->sw_Ll);
+        c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the member)
+        m.T.ensure((size_t)2 * Tld); // T_0 (zero beyond N), then the result (NaN until written)
+        m.w.ensure(N);
+        const std::vector<double> nan_n(N, std::nan(""));
+        HIP_CHECK(hipMemsetAsync(m.T.p, 0, sizeof(double) * 2 * Tld, st));
+        HIP_CHECK(hipMemcpyAsync(m.T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(m.T.p + Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(m.w.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        cge_flow_problem &q = tab.p[i];
+        q.Lh = m.Lh.p; q.Ll = m.Ll.p; q.alpha = p.alpha;
+        q.epi = nullptr; q.want = 0;
+        q.T0 = m.T.p; q.Tout = m.T.p + Tld; q.w = m.w.p;
+        q.flags = flags.p + 4 * i;
+        q.N = N; q.Tld = Tld; q.Nt = (int)Nt; q.G = G[i];
+    }
+    k_fit_flow_multi(c, tab, NW, eps, delta, flow);
+    for (int i = 0; i < n; i++) {
+        cge_fit_problem &p = probs[i];
+        p.status = ft_verdict(c, flags.p + 4 * i, &p.iters) ? 0 : 1;
+        HIP_CHECK(hipMemcpyAsync(p.T, tab.p[i].Tout, sizeof(double) * p.N, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int form, double eps, double delta, int *form_ran) {
+    if (n > 1 && form != 5) CGE_THROW(CGE_E_ARG, "fit_test: %d problems in one call are form 5 only", n);
+    if (n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ARG, "fit_test: form 5 takes at most %d problems", CGE_BATCH_MAX);
+    if (directed && (form == 2 || form == 4 || form == 5)) CGE_THROW(CGE_E_ARG, "fit_test: form %d is undirected only", form);
+    if ((form == 4 || form == 5) && !c->opt_pow_exp2)
+        CGE_THROW(CGE_E_ARG, "fit_test: form %d makes its power matrix from the stored logarithm (option pow_exp2)", form);
+    if (!(eps > 0.0) || !(delta >= 0.0)) CGE_THROW(CGE_E_ARG, "fit_test: eps > 0 and delta >= 0");
+    int G[CGE_BATCH_MAX], NW0 = 0, sumG = 0, cus = 0, dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    for (int i = 0; i < n; i++) {
+        const cge_fit_problem &p = probs[i];
+        if (p.N <= 0 || !p.D || !p.w || !p.T0 || !p.T) CGE_THROW(CGE_E_ARG, "fit_test: empty problem");
+        if (directed && (!p.w2 || !p.T0b || !p.Tb)) CGE_THROW(CGE_E_ARG, "fit_test: a directed problem takes w2, T0b and Tb");
+        if (p.N > 46340) CGE_THROW(CGE_E_ARG, "fit_test: problem too large");
+        const i64 Tld = (p.N + 63) / 64 * 64;
+        if (form == 3 && !k_fit_flow_applies(p.N, Tld))
+            CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
+        if (form == 4 && !k_fit_flow_fused_applies(c, p.N))
+            CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the fused persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
+        if (form == 5) {
+            int NW = 0;
+            if (!k_fit_flow_geometry(p.N, &G[i], &NW))
+                CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the fused persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
+            if (i > 0 && NW != NW0)
+                CGE_THROW(CGE_E_ARG, "fit_test: form 5 takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", i, NW, NW0);
+            NW0 = NW;
+            sumG += G[i];
+        }
+    }
+    if (form == 5 && sumG > cus)
+        CGE_THROW(CGE_E_ARG, "fit_test: the problems of form 5 need %d workgroups in all, the device has %d CUs", sumG, cus);
+    if (form == 5 && !k_fit_flow_multi_fits(NW0))
+        CGE_THROW(CGE_E_ARG, "fit_test: fit_flow_multi_kernel of %d waves gets no workgroup on a CU", NW0);
+    if (form == 5) {
+        ft_multi(c, probs, n, G, NW0, eps, delta);
+        *form_ran = 5;
+    } else
+        *form_ran = directed ? ft_directed(c, probs[0], form, eps, delta) : ft_undirected(c, probs[0], form, eps, delta);
 }
 
 // ---- the testing hook of the packed form (include/cge_hip_testing.h: cge_packed_gd_test) -------------------------------

@@ -95,6 +95,46 @@ typedef struct cge_vect_b_problem {
 } cge_vect_b_problem;
 int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_problem *p2, int directed, int form, int landmarks,
                     int n_modes, int *form_ran);
+/* kernel-level hook (needs the GPU): ONE Chung-Lu fit (src/divergence.jl:150-168, directed :434-467) from a caller's start, by
+ * one named form of the alpha sweep -- the sweep's own fit functions, launch wrappers and geometry decisions -- so that a test
+ * sees the iterate itself and the iteration count, not a score.
+ *   A problem: D (N x N, row-major, symmetric, values in [0, 1]) and alpha: the fit reads GD = (1 - D)^alpha, made by
+ *   k_pow_prepare + k_pow_matrix under the context's option "pow_exp2" (the fused forms 4 and 5 make it in their prologue from
+ *   the tile-blocked logarithm).  The undirected forms read D on and above the diagonal 64 x 64 tiles only: j >= i, and the part
+ *   of each diagonal tile below the diagonal (the tiles are read whole); every other element of D may hold anything.  The
+ *   directed forms read all of it.
+ *   w (N): the vertex weights (undirected) / deg_in (directed); w2 (N): deg_out (directed only).  T0 (N): the start T
+ *   (undirected) / Tin (directed); T0b (N): the start Tout (directed only).
+ *   Out: T, Tb (N; Tb directed only) = the iterate the fit left, copied from the device buffer the fit writes.  Undirected: that
+ *   buffer holds NaN before the launch, so rows nothing wrote stay NaN (all of them after an abandoned launch).  Directed: the
+ *   fit updates Tin / Tout in place on success only, so an abandoned launch returns the start.  GD (optional, N x N): the power
+ *   matrix by k_pow_prepare + k_pow_matrix (undirected: the upper tiles; NaN where nothing was written).  iters = the
+ *   iterations taken (iters updates were applied; the change f of the last one is <= delta); status = 0 converged, 1 the
+ *   persistent launch was abandoned (context option "fit_persistent_test_timeout", or a wait that timed out).
+ *   eps, delta: the step and the stopping threshold (a sweep: 0.25 / 0.001 undirected, 0.9 / 0.001 directed); the directed
+ *   diff starts at 1.0 (:435).  The launch-per-iteration forms stop with CGE_E_ASSERT beyond option "fit_max_iterations".
+ * form 0: what an exact-mode sweep of this shape picks on this device (the persistent form reading GD from 128 vertices on
+ *         where its geometry applies, else one launch (pair) per iteration; an abandoned persistent launch is redone by launches,
+ *         as the sweep does);
+ *      1: one launch (pair) per iteration -- undirected fit_symtile_kernel + fit_symreduce_kernel over the upper tiles, directed
+ *         fit_symv_dir_kernel + fit_update_dir_kernel;
+ *      2: undirected, the same on the packed tiles (GD packed on the host through cge_packed_index, zeros outside the matrix);
+ *      3: persistent, reading GD (fit_flow_kernel / fit_flow_dir_kernel);
+ *      4: undirected, the fused instance of fit_flow_kernel without an epilogue output (needs option "pow_exp2");
+ *      5: undirected, fit_flow_multi_kernel over n_problems (1..CGE_BATCH_MAX = 16) problems with slots and flags of their own.
+ *      *form_ran = the form that ran.  n_problems > 1: form 5 only.
+ * CGE_E_ARG, with a message and before any launch, where a form does not apply: forms 3-5 where the geometry of the persistent
+ * fit declines N on this device; forms 2, 4, 5 directed; forms 4, 5 without "pow_exp2"; form 5 with problems of different waves
+ * per workgroup or more workgroups in all than the device has CUs. */
+typedef struct cge_fit_problem {
+    const double *D, *w, *w2, *T0, *T0b;
+    double *T, *Tb, *GD;
+    int64_t N;
+    double alpha;
+    int64_t iters;
+    int32_t status, pad;
+} cge_fit_problem;
+int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int directed, int form, double eps, double delta, int *form_ran);
 /* kernel-level hook (needs the GPU): the packed form of an exact sweep (cge_hip.h, option "exact_packed") on a caller's
  * embedding, through the sweep's own launch wrappers -- the extrema pass (lo_hi[0], lo_hi[1] = extrema of D over j >= i with
  * diag on the diagonal, D never stored) and the generator of one alpha (distances, normalisation, power; pow_method 1 = exp2 of

@@ -320,7 +320,7 @@ def test_wgcl_exact_mode_original_graph(ctx, orc, test115):
 @pytest.mark.parametrize("n", [40, 130, 700, 1500])
 def test_fit_persistent_kernel_matches_stepwise_and_oracle(ctx, orc, n):
     """The Chung-Lu fixed point (src/divergence.jl:150-168) as one persistent launch per alpha (register-resident
-    upper triangle, grid barriers) against one launch per iteration and against the oracle: same iteration counts,
+    upper triangle, the data as its own signal: sentinel-armed slots) against one launch per iteration and against the oracle: same iteration counts,
     same scores.  Sizes cover one tile, ragged last tiles, and several tiles per wave row."""
     import cge.jl_amd as cg
     from cge.jl_amd import api, synth
@@ -387,7 +387,7 @@ def test_fit_persistent_directed_matches_stepwise_and_oracle(ctx, orc, n):
 
 def test_fit_persistent_handoffs_under_varied_geometry(ctx):
     """The cross-workgroup hand-offs of the persistent fits (partial vectors, iterates, maxima through write-through
-    stores and dependency counters) on many grid geometries -- from a handful of workgroups to every CU with two tile
+    stores into sentinel-armed slots that their consumers poll) on many grid geometries -- from a handful of workgroups to every CU with two tile
     slots per wave, ragged last tiles, undirected and directed: a stale read anywhere would change an iterate, hence
     an iteration count or a score; both must equal the launch-per-iteration path, run after run."""
     import cge.jl_amd as cg

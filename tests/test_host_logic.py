@@ -84,6 +84,22 @@ def test_vect_b_hook_is_declared_and_refuses_a_null_context():
     assert ran.value == -1
 
 
+def test_fit_hook_is_declared_and_refuses_a_null_context():
+    """The kernel-level hook of the Chung-Lu fit's forms (tests/test_gpu_fit.py): among the declared symbols the export test
+    walks, and CGE_E_ARG for a null context or null problems before anything touches a device."""
+    from cge.jl_amd import api
+
+    assert "cge_fit_test" in _declared("cge_hip_testing.h")
+    lib = api.load_library()
+    p, ran = api.FitProblem(), C.c_int(-1)
+    assert C.sizeof(p) == 12 * 8  # cge_fit_problem: eight pointers, N, alpha, iters, status + pad
+    for directed in (0, 1):
+        for form in (0, 1, 5):
+            assert lib.cge_fit_test(None, C.byref(p), 1, directed, form, C.c_double(0.25), C.c_double(0.001), C.byref(ran)) == -7
+    assert lib.cge_fit_test(None, None, 1, 0, 0, C.c_double(0.25), C.c_double(0.001), C.byref(ran)) == -7
+    assert ran.value == -1
+
+
 def test_create_fails_loudly_without_gpu():
     import torch
 
