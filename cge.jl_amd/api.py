@@ -111,6 +111,17 @@ class FitProblem(C.Structure):
                 ("T", C.c_void_p), ("Tb", C.c_void_p), ("GD", C.c_void_p), ("N", C.c_int64), ("alpha", C.c_double),
                 ("iters", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32)]
 
+
+class LandmarkGraphIO(C.Structure):
+    """cge_landmark_graph_io (include/cge_hip_testing.h): the arguments of the testing hook cge_landmark_graph_test."""
+    _fields_ = [("v2l", C.c_void_p), ("N", C.c_int64), ("directed", C.c_int32), ("wedge_form", C.c_int32), ("part", C.c_int64),
+                ("nparts", C.c_int64), ("world", C.c_int64), ("lemb", C.c_void_p), ("lweight", C.c_void_p), ("dii", C.c_void_p),
+                ("lcomm", C.c_void_p), ("wedges", C.c_void_p), ("positive", C.c_void_p), ("deg_out", C.c_void_p),
+                ("deg_in", C.c_void_p), ("star", C.c_void_p), ("deg_block", C.c_void_p), ("u_deg_out", C.c_void_p),
+                ("u_deg_in", C.c_void_p), ("u_star", C.c_void_p), ("n_chunks", C.c_int64), ("ntile", C.c_int64),
+                ("form_ran", C.c_int32), ("rshift", C.c_int32), ("colbits", C.c_int32), ("pad", C.c_int32)]
+
+
 DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
 _NP_DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
 
@@ -211,6 +222,21 @@ def _method_code(method):
     if isinstance(method, str):
         return {"rss": 0, "rss2": 1, "size": 2, "diameter": 3}[method]
     return int(method)
+
+
+def wedge_geometry_test(N, weighted, n_chunks):
+    """Host-only hook (include/cge_hip_testing.h: cge_wedge_geometry_test): the geometry of the tiled form of the landmark-pair
+    matrix.  None where the form declines, else a dict rshift, colbits, ntile, lds_pass1, lds_pass2."""
+    L = load_library()
+    ap, rs, cb = C.c_int(), C.c_int(), C.c_int()
+    nt, l1, l2 = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = L.cge_wedge_geometry_test(C.c_int64(N), C.c_int(int(bool(weighted))), C.c_int64(n_chunks), C.byref(ap), C.byref(rs),
+                                   C.byref(cb), C.byref(nt), C.byref(l1), C.byref(l2))
+    if rc:
+        raise CGEError(rc, "cge_wedge_geometry_test")
+    if not ap.value:
+        return None
+    return {"rshift": rs.value, "colbits": cb.value, "ntile": nt.value, "lds_pass1": l1.value, "lds_pass2": l2.value}
 
 
 def _p(a):
@@ -870,6 +896,43 @@ class Context:
                                                     C.byref(nref), C.byref(ran), _p(ref), _p(mean)))
         assert nref.value == w
         return P, ran.value, ref, mean
+
+    def landmark_graph_test(self, v_to_l, N, directed=False, wedge_form=0, part=0, nparts=1, aggregate=False, wedges=True,
+                            positive=None, degrees=False, world=0):
+        """Testing hook (include/cge_hip_testing.h: cge_landmark_graph_test): the landmark graph of the assignment v_to_l (n ids
+        in 1..N) over the resident inputs, by the landmark run's own aggregate, scatter and degree steps.  aggregate: lemb (N, d),
+        lweight, dii, lcomm (0-based).  wedges: the (N, N) landmark-pair matrix of share `part` of `nparts` by wedge_form (0 what
+        a run picks, 1 tiled, 2 gather + count); positive (default: with wedges): the count of its positive entries.  degrees: deg_out, deg_in, star from the matrix.  world > 0:
+        deg_block (world, 3 N) and u_deg_out, u_deg_in, u_star (the unpacked sum of the blocks).  Returns a dict of what was
+        asked for, with form_ran, n_chunks, rshift, colbits, ntile."""
+        v2l = _i64(v_to_l)
+        N = int(N)
+        io, out = LandmarkGraphIO(), {}
+        io.v2l, io.N, io.directed, io.wedge_form = v2l.ctypes.data, N, int(bool(directed)), int(wedge_form)
+        io.part, io.nparts, io.world = int(part), int(nparts), int(world)
+
+        def want(key, shape, dtype=np.float64):
+            out[key] = np.full(shape, -1 if dtype != np.float64 else np.nan, dtype=dtype)
+            setattr(io, key, out[key].ctypes.data)
+
+        if aggregate:
+            d = getattr(self, "d", 1)  # (no embedding was set through this object: the call refuses)
+            want("lemb", (N, d)), want("lweight", N), want("dii", N), want("lcomm", N, np.int32)
+        positive = bool(wedges) if positive is None else positive
+        if wedges:
+            want("wedges", (N, N))
+        if positive:
+            want("positive", 1, np.int64)
+        if degrees:
+            want("deg_out", N), want("deg_in", N), want("star", N, np.int32)
+        if world:
+            want("deg_block", (world, 3 * N)), want("u_deg_out", N), want("u_deg_in", N), want("u_star", N, np.int32)
+        self._check(self.L.cge_landmark_graph_test(self.h, C.byref(io)))
+        if positive:
+            out["positive"] = int(out["positive"][0])
+        out.update(form_ran=int(io.form_ran), n_chunks=int(io.n_chunks), rshift=int(io.rshift), colbits=int(io.colbits),
+                   ntile=int(io.ntile))
+        return out
 
     def pow_test(self, x, alpha, method):
         """Testing hook: (1 - x)^alpha on the device; method 0 = library pow, 1 = the sweep's exp2(alpha * log2(1 - x))."""

@@ -516,6 +516,26 @@ int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int
     CGE_CATCH(c)
 }
 
+// testing hook (include/cge_hip_testing.h): aggregate, landmark-pair matrix and degrees of a caller's assignment
+int cge_landmark_graph_test(void *ctx, cge_landmark_graph_io *io) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !io || !io->v2l || io->N <= 0 || io->wedge_form < 0 || io->wedge_form > 2) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_landmark_graph_test(c, io);
+    CGE_CATCH(c)
+}
+// host-only hook (include/cge_hip_testing.h): the tiled form's geometry, as k_wedge_scatter_blocked reads it
+int cge_wedge_geometry_test(int64_t N, int weighted, int64_t n_chunks, int *applies, int *rshift, int *colbits, int64_t *ntile,
+                            int64_t *lds_pass1, int64_t *lds_pass2) {
+    if (!applies || !rshift || !colbits || !ntile || !lds_pass1 || !lds_pass2) return CGE_E_ARG;
+    WedgeGeometry G;
+    *applies = k_wedge_geometry(N, weighted ? 8 : 4, n_chunks, &G) ? 1 : 0;
+    if (!*applies) return CGE_OK;
+    *rshift = G.rshift; *colbits = G.colbits; *ntile = G.ntile;
+    *lds_pass1 = (int64_t)G.lds1; *lds_pass2 = (int64_t)G.lds2;
+    return CGE_OK;
+}
+
 int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method, double *out) {
     cge_ctx *c = (cge_ctx *)ctx;
     if (!c || !x || !out || n <= 0) return CGE_E_ARG;

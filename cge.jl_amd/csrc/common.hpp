@@ -756,6 +756,10 @@ bool k_blocked_edges_possible(const cge_ctx *c);
 void k_pack_upper(cge_ctx *c, const double *dense, i64 C, double *packed);
 bool k_build_blocked_edges(cge_ctx *c);
 void k_edge_scatter_blocked(cge_ctx *c, i64 c0, i64 c1, i64 C, int directed, double *vectC);
+// the tiled form's geometry for N landmarks: tiles of 1 << rshift rows, keys of rshift + colbits bits, the dynamic LDS of the two
+// passes; host arithmetic only (elt = 4 bytes per cell for unit weights, 8 for a weighted list); false: the form declines
+struct WedgeGeometry { int rshift, colbits; i64 ntile, ntpad; size_t lds1, lds2; };
+bool k_wedge_geometry(i64 N, size_t elt, i64 nchunks, WedgeGeometry *g);
 // the N x N landmark-pair matrix by the tiled two-pass form (kernels_scatter.hip); false: does not apply
 bool k_wedge_scatter_blocked(cge_ctx *c, const i32 *v2l, i64 N, i64 c0, i64 c1, int directed, double *wedges, i64 *positive,
                              const char *timer = "edge_scatter_wedges");
@@ -978,6 +982,9 @@ double host_diameter_brute(cge_ctx *c, int part, int nparts, i64 *ai, i64 *aj);
 double host_diameter_landmarks(cge_ctx *c, const double *lemb, const double *lweight, const std::vector<i32> &lcomm, i64 C, i64 N);
 void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lcomm1, i64 C, int pass, double *P, i64 *nref_out,
                                int *pass_ran, double *ref_out, double *mean_out);
+// score_host.cpp
+struct cge_landmark_graph_io;
+void host_landmark_graph_test(cge_ctx *c, cge_landmark_graph_io *io);
 // wgcl_host.cpp
 // ---- the packed form of an exact sweep's matrix: the NT = Nt (Nt + 1) / 2 upper 64 x 64 tiles (Nt = ceil(N / 64)), 4096 doubles
 // each, in row-major order of the upper triangle (fit_symtile_kernel's numbering of t).  Diagonal tiles are stored whole, elements

@@ -553,10 +553,14 @@ __global__ __launch_bounds__(WT_THREADS) void wedge_tile_kernel(const unsigned s
     }
 }
 
-// geometry of the tiled form for N landmarks; false: it does not apply (the caller uses the gather + atomics kernel)
-static bool wedge_geometry(const cge_ctx *c, i64 N, i64 nchunks, int *rshift, int *colbits, i64 *ntile, size_t *lds2) {
+// geometry of the tiled form for N landmarks over `nchunks` chunks, `elt` bytes per cell of a tile (4: unit weights, counted; 8:
+// weighted, summed); false: it does not apply (the caller uses the gather + atomics kernel).  Both passes' LDS sizes are decided
+// here, so that what is launched is what was checked: pass 1 keeps one counter per tile beside the 64 KB table slice, pass 2 the
+// tile itself -- one row of N > 8192 (unit) / 4096 (weighted) landmarks, so ntile = N there and pass 1 is what limits N.
+#define WEDGE_LDS_GRANT ((size_t)160 * 1024) // what cge_allow_lds asks for both kernels
+bool k_wedge_geometry(i64 N, size_t elt, i64 nchunks, WedgeGeometry *g) {
     if (N < 1 || N > 65535 || nchunks <= 0) return false;
-    const size_t elt = c->unit_weights ? 4 : 8, fixed = sizeof(unsigned) * (2 * WT_THREADS + 32);
+    const size_t fixed = sizeof(unsigned) * (2 * WT_THREADS + 32);
     int cb = 1;
     while (((i64)1 << cb) < N) cb++;
     int rs = 0;
@@ -564,8 +568,12 @@ static bool wedge_geometry(const cge_ctx *c, i64 N, i64 nchunks, int *rshift, in
     if (((size_t)1 << rs) * N * elt + fixed > (size_t)150 * 1024) return false;
     const i64 nt = (N + ((i64)1 << rs) - 1) >> rs;
     if (nchunks * (nt + 1) > ((i64)1 << 27)) return false; // the per-chunk tile offsets would outgrow what pass 2 can gather
-    *rshift = rs; *colbits = cb; *ntile = nt;
-    *lds2 = ((size_t)1 << rs) * N * elt + fixed;
+    const i64 ntpad = (nt + EB_THREADS - 1) / EB_THREADS * EB_THREADS; // a thread of pass 1 scans ntpad / 1024 counters
+    const size_t lds1 = (size_t)2 * (1 << EB_VBITS) + sizeof(unsigned) * ((size_t)ntpad + 18);
+    if (lds1 > WEDGE_LDS_GRANT) return false; // (unit weights, N >= 23553: one counter per row no longer fits beside the slice)
+    g->rshift = rs; g->colbits = cb; g->ntile = nt; g->ntpad = ntpad;
+    g->lds1 = lds1;
+    g->lds2 = ((size_t)1 << rs) * N * elt + fixed;
     return true;
 }
 
@@ -574,10 +582,11 @@ static bool wedge_geometry(const cge_ctx *c, i64 N, i64 nchunks, int *rshift, in
 bool k_wedge_scatter_blocked(cge_ctx *c, const i32 *v2l, i64 N, i64 c0, i64 c1, int directed, double *wedges, i64 *positive,
                              const char *timer) {
     const i64 nwg = c1 - c0;
-    int rshift, colbits;
-    i64 ntile;
-    size_t lds2;
-    if (!c->blocked_ready || !wedge_geometry(c, N, std::max<i64>(nwg, 1), &rshift, &colbits, &ntile, &lds2)) return false;
+    WedgeGeometry G;
+    if (!c->blocked_ready || !k_wedge_geometry(N, c->unit_weights ? 4 : 8, std::max<i64>(nwg, 1), &G)) return false;
+    const int rshift = G.rshift, colbits = G.colbits, ntpad = (int)G.ntpad;
+    const i64 ntile = G.ntile;
+    const size_t lds1 = G.lds1, lds2 = G.lds2;
     hipStream_t st = c->stream;
     HIP_CHECK(hipMemsetAsync(positive, 0, sizeof(i64), st));
     if (nwg <= 0) { // an empty shard still owes zeros
@@ -591,15 +600,13 @@ bool k_wedge_scatter_blocked(cge_ctx *c, const i32 *v2l, i64 N, i64 c0, i64 c1, 
     c->be_runoff.ensure((size_t)nwg * (ntile + 1));
     ScopedKernelTimer t(c, timer);
     hipLaunchKernelGGL(wedge_table_kernel, dim3(grid_for(npad, 256)), dim3(256), 0, st, v2l, c->n, npad, c->v2l16.p);
-    const int ntpad = (int)((ntile + EB_THREADS - 1) / EB_THREADS * EB_THREADS);
-    const size_t lds1 = (size_t)2 * (1 << EB_VBITS) + sizeof(unsigned) * ((size_t)ntpad + 18);
     const bool wt = !c->unit_weights;
 #define WG_GO(W, D)                                                                                                        \
     do {                                                                                                                   \
         auto k1 = wedge_pass_kernel<16, W, D>;                                                                              \
         auto k2 = wedge_tile_kernel<W>;                                                                                     \
-        cge_allow_lds((const void *)k1, 160 * 1024);                                                                        \
-        cge_allow_lds((const void *)k2, 160 * 1024);                                                                        \
+        cge_allow_lds((const void *)k1, WEDGE_LDS_GRANT);                                                                   \
+        cge_allow_lds((const void *)k2, WEDGE_LDS_GRANT);                                                                   \
         hipLaunchKernelGGL(k1, dim3((unsigned)nwg), dim3(EB_THREADS), lds1, st, c->be_edge.p, c->be_w.p, c->be_chunk.p, (int)c0, \
                            c->v2l16.p, (int)ntile, ntpad, rshift, colbits, c->be_keys.p, c->be_wkeys.p, c->be_runoff.p);    \
         hipLaunchKernelGGL(k2, dim3((unsigned)ntile), dim3(WT_THREADS), lds2, st, c->be_keys.p, c->be_wkeys.p, c->be_runoff.p, \

@@ -4,6 +4,7 @@
 // score's sample draw is enqueued between lm_clamp and lm_split.  cge_wgcl (everything as host arrays): wgcl_upload_score_graph
 // -> wgcl_original_graph -> wgcl_samples -> the sweep.  Every exchange between ranks goes through collectives.cpp.
 #include "common.hpp"
+#include "../../include/cge_hip_testing.h"
 
 // ---- shares of the ranks ------------------------------------------------------------------------------------------------------
 // This rank's share of the edges: of a replicated list its slice [lo(cnt), hi(cnt)) of the edges or chunks; of a sharded list
@@ -19,10 +20,12 @@ static EdgeShare edge_share(const cge_ctx *c) {
 }
 // the row block [r0, r1) of the N x N landmark-pair matrix this rank ends up with after a reduce-scatter: equal blocks of `per` rows
 struct RowBlock { i64 per, r0, r1; };
-static RowBlock wedge_row_block(const cge_ctx *c, i64 N) {
-    if (!c->has_coll) return {N, 0, N};
-    const i64 per = (N + c->coll.world - 1) / c->coll.world, r0 = std::min<i64>(N, per * c->coll.rank);
+static RowBlock row_block_of(i64 N, i64 rank, i64 world) {
+    const i64 per = (N + world - 1) / world, r0 = std::min<i64>(N, per * rank);
     return {per, r0, std::min<i64>(N, r0 + per)};
+}
+static RowBlock wedge_row_block(const cge_ctx *c, i64 N) {
+    return c->has_coll ? row_block_of(N, c->coll.rank, c->coll.world) : RowBlock{N, 0, N};
 }
 
 // ---- the unique-row clamp -----------------------------------------------------------------------------------------------------
@@ -131,6 +134,22 @@ static void scatter_vectC_resident(cge_ctx *c, i64 C, int directed, double *vect
     if (c->has_coll) cge_allreduce_dev(c, vectC, vlen, 0);
 }
 
+// One share of the edges summed into a full N x N landmark-pair matrix: the tiled two-pass form on the blocked copy of the edge
+// list (kernels_scatter.hip: the tiles are written whole and *cnt counts the positive entries on the way) -- else the gather +
+// atomics kernel into a zeroed matrix, which leaves *cnt alone.  form 0: the tiled form where it applies; 2: the gather form
+// (the testing hook names it).  Returns whether the tiled form ran.
+static bool scatter_wedges_share(cge_ctx *c, const i32 *v2l, i64 N, int directed, const EdgeShare &mine, int form, double *wedges,
+                                 i64 *cnt) {
+    const bool tiled = form != 2 && (c->blocked_ready || (k_blocked_edges_possible(c) && k_build_blocked_edges(c))) &&
+                       k_wedge_scatter_blocked(c, v2l, N, mine.lo(c->be_nchunks), mine.hi(c->be_nchunks), directed, wedges, cnt);
+    if (!tiled) {
+        HIP_CHECK(hipMemsetAsync(wedges, 0, sizeof(double) * N * N, c->stream));
+        k_edge_scatter(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, mine.lo(c->m), mine.hi(c->m), v2l, c->comm.p, N,
+                       c->n_comm_max, directed, wedges, nullptr);
+    }
+    return tiled;
+}
+
 // the landmark-pair matrix (src/landmarks.jl:433-451) and its positive-entry count
 static void scatter_wedges(cge_ctx *c, int directed) {
     const i64 N = c->N;
@@ -141,16 +160,7 @@ static void scatter_wedges(cge_ctx *c, int directed) {
     c->wedges_block_only = false;
     DevBuf<i64> &cnt = c->wed_cnt;
     cnt.ensure(1);
-    const EdgeShare mine = edge_share(c);
-    // the tiled two-pass form on the blocked copy of the edge list (kernels_scatter.hip): the tiles are written whole, the
-    // positive entries counted on the way (one rank) -- else the gather + atomics kernel into a zeroed matrix
-    bool tiled = (c->blocked_ready || (k_blocked_edges_possible(c) && k_build_blocked_edges(c))) &&
-                 k_wedge_scatter_blocked(c, c->v2l.p, N, mine.lo(c->be_nchunks), mine.hi(c->be_nchunks), directed, c->wedges.p, cnt.p);
-    if (!tiled) {
-        HIP_CHECK(hipMemsetAsync(c->wedges.p, 0, sizeof(double) * N * N, st));
-        k_edge_scatter(c, c->src.p, c->dst.p, c->unit_weights ? nullptr : c->w.p, mine.lo(c->m), mine.hi(c->m), c->v2l.p, c->comm.p, N,
-                       c->n_comm_max, directed, c->wedges.p, nullptr);
-    }
+    const bool tiled = scatter_wedges_share(c, c->v2l.p, N, directed, edge_share(c), 0, c->wedges.p, cnt.p);
     if (c->has_coll) {
         // every rank has summed ITS edges into a full N x N matrix.  Option "wedges_reduce_scatter" (default 0): the sums over
         // the ranks are all-reduced, after which every consumer -- cge_landmarks_fetch on ONE rank included -- is local.  With it
@@ -187,16 +197,21 @@ static void lm_split(cge_ctx *c, LandmarkRun &R) {
     c->h_v2l.clear();                    // v_to_l (:379) is read back from the device by landmarks_fetch
 }
 
+// centroids, weights, d_ii and communities (c->lemb, lweight, dii, lcomm) of the N landmarks of the device index c->lm_memoff /
+// c->lm_mem over the rows this rank holds
+static void aggregate_landmarks(cge_ctx *c, i64 N) {
+    const i64 d = c->d;
+    c->lemb.ensure((size_t)N * d);
+    c->lweight.ensure(N); c->dii.ensure(N); c->lcomm.ensure(N);
+    ScopedKernelTimer tm(c, "landmark_aggregate");
+    k_landmark_aggregate(c, c->Xr.p, lm_vw(c), lm_comm(c), c->lm_memoff.p, c->lm_mem.p, N, d, c->lemb.p, c->lweight.p, c->dii.p,
+                         c->lcomm.p);
+}
+
 static void lm_aggregate(cge_ctx *c, LandmarkRun &R) {
     R.t0 = now_ms();
     const i64 N = c->N, d = c->d;
-    c->lemb.ensure((size_t)N * d);
-    c->lweight.ensure(N); c->dii.ensure(N); c->lcomm.ensure(N);
-    {
-        ScopedKernelTimer tm(c, "landmark_aggregate");
-        k_landmark_aggregate(c, c->Xr.p, lm_vw(c), lm_comm(c), c->lm_memoff.p, c->lm_mem.p, N, d, c->lemb.p, c->lweight.p, c->dii.p,
-                             c->lcomm.p);
-    }
+    aggregate_landmarks(c, N);
     if (c->rows_sharded) {
         // option shard_rows: a landmark's members live on one rank, which has just aggregated it (the others wrote zeros for
         // it); centroids, weights, d_ii and communities of ALL landmarks on every rank by one gather (N (d + 3) words)
@@ -691,5 +706,123 @@ void host_edge_scatter(cge_ctx *c, const int64_t *v_to_l, i64 N, i64 C, int dire
     if (wedges_out) HIP_CHECK(hipMemcpyAsync(wedges_out, dw.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
     if (vect_C_out) HIP_CHECK(hipMemcpyAsync(vect_C_out, dc.p, sizeof(double) * vlen, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
+    flush_timers(c);
+}
+
+// Testing hook (include/cge_hip_testing.h: cge_landmark_graph_test): the stage between the split and the score graph on a
+// caller's assignment -- build_landmark_index + aggregate_landmarks, scatter_wedges_share with the one-rank count behind it, and
+// the degree kernels of the directed score, each as lm_aggregate, scatter_wedges and score_graph_landmarks call them.  The
+// shares and row blocks of pretend ranks come from EdgeShare and row_block_of.
+void host_landmark_graph_test(cge_ctx *c, cge_landmark_graph_io *io) {
+    const i64 N = io->N, n = c->n, d = c->d;
+    hipStream_t st = c->stream;
+    const bool want_agg = io->lemb || io->lweight || io->dii || io->lcomm;
+    const bool want_deg = io->deg_out || io->deg_in || io->star;
+    const bool want_blk = io->deg_block || io->u_deg_out || io->u_deg_in || io->u_star;
+    const bool want_mat = io->wedges || io->positive || want_deg || want_blk;
+    if (c->rows_sharded || c->edges_sharded)
+        CGE_THROW(CGE_E_ARG, "landmark_graph_test: not with option shard_rows / shard_ingest (every row and edge on one rank)");
+    if (n <= 0) CGE_THROW(CGE_E_ARG, "landmark_graph_test: nothing is resident");
+    if (want_mat && (!c->src.p || !c->dst.p || c->m <= 0 || (!c->unit_weights && !c->w.p)))
+        CGE_THROW(CGE_E_ARG, "landmark_graph_test: the graph is not resident (cge_set_graph)");
+    if (want_agg && (!c->Xr.p || d <= 0 || c->Xr.n < (size_t)(n * d) || !c->vw.p || !c->comm.p || c->vw.n < (size_t)n || c->comm.n < (size_t)n))
+        CGE_THROW(CGE_E_ARG, "landmark_graph_test: the aggregate needs the embedding and the vertex data resident");
+    if (io->nparts < 1 || io->part < 0 || io->part >= io->nparts) CGE_THROW(CGE_E_ARG, "landmark_graph_test: part %lld of %lld", (long long)io->part, (long long)io->nparts);
+    if (want_blk && (io->world < 1 || io->world > 64)) CGE_THROW(CGE_E_ARG, "landmark_graph_test: world %lld outside 1..64", (long long)io->world);
+    if (want_blk && (!io->deg_block || !io->u_deg_out || !io->u_deg_in || !io->u_star))
+        CGE_THROW(CGE_E_ARG, "landmark_graph_test: the block form of the degrees returns deg_block and the three unpacked vectors together");
+    if (want_mat && N > 46340) CGE_THROW(CGE_E_ARG, "landmark_graph_test: N = %lld, the matrix is beyond 2^31 entries", (long long)N);
+    std::vector<i32> v2l0(n);
+    for (i64 i = 0; i < n; i++) {
+        if (io->v2l[i] < 1 || io->v2l[i] > N)
+            CGE_THROW(CGE_E_ARG, "landmark_graph_test: v_to_l: id %lld outside 1..%lld", (long long)io->v2l[i], (long long)N);
+        v2l0[i] = (i32)(io->v2l[i] - 1);
+    }
+    if (want_agg) {
+        std::vector<char> seen(N, 0);
+        for (i64 i = 0; i < n; i++) seen[v2l0[i]] = 1;
+        for (i64 l = 0; l < N; l++)
+            if (!seen[l]) CGE_THROW(CGE_E_ARG, "landmark_graph_test: landmark %lld has no member (the aggregate needs one)", (long long)(l + 1));
+    }
+    // the geometry of this share, before any launch
+    const EdgeShare mine{io->part, io->nparts};
+    WedgeGeometry G{};
+    bool geom = false;
+    io->n_chunks = 0;
+    if (want_mat) {
+        const bool blocked = c->blocked_ready || (k_blocked_edges_possible(c) && k_build_blocked_edges(c));
+        io->n_chunks = blocked ? c->be_nchunks : 0;
+        geom = blocked && k_wedge_geometry(N, c->unit_weights ? 4 : 8, std::max<i64>(mine.hi(c->be_nchunks) - mine.lo(c->be_nchunks), 1), &G);
+        if (io->wedge_form == 1 && !geom)
+            CGE_THROW(CGE_E_ARG, "landmark_graph_test: the tiled form declines N = %lld over %lld chunks (%s)", (long long)N,
+                      (long long)io->n_chunks, blocked ? "its geometry" : "no blocked edge list");
+    }
+    // what a landmark run left behind is replaced
+    c->lm_ready = false;
+    c->wedges_ready = false;
+    c->n_ledges = -1;
+    c->h_v2l.clear();
+    c->v2l.ensure(n);
+    HIP_CHECK(hipMemcpyAsync(c->v2l.p, v2l0.data(), sizeof(i32) * n, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    io->form_ran = 0;
+    io->rshift = io->colbits = -1;
+    io->ntile = -1;
+    if (want_agg) {
+        build_landmark_index(c, v2l0, N);
+        c->lm_memoff.ensure(N + 1);
+        c->lm_mem.ensure(n);
+        HIP_CHECK(hipMemcpyAsync(c->lm_memoff.p, c->h_mem_off.data(), sizeof(i32) * (N + 1), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(c->lm_mem.p, c->h_mem.data(), sizeof(i32) * n, hipMemcpyHostToDevice, st));
+        c->lm_index_on_device = true;
+        aggregate_landmarks(c, N);
+        if (io->lemb) HIP_CHECK(hipMemcpyAsync(io->lemb, c->lemb.p, sizeof(double) * N * d, hipMemcpyDeviceToHost, st));
+        if (io->lweight) HIP_CHECK(hipMemcpyAsync(io->lweight, c->lweight.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        if (io->dii) HIP_CHECK(hipMemcpyAsync(io->dii, c->dii.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        if (io->lcomm) HIP_CHECK(hipMemcpyAsync(io->lcomm, c->lcomm.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (want_mat) {
+        c->wedges.ensure((size_t)N * N);
+        c->wedges_block_only = false;
+        DevBuf<i64> &cnt = c->wed_cnt;
+        cnt.ensure(1);
+        const bool tiled = scatter_wedges_share(c, c->v2l.p, N, io->directed, mine, io->wedge_form, c->wedges.p, cnt.p);
+        if (tiled != (io->wedge_form == 2 ? false : geom))
+            CGE_THROW(CGE_E_ASSERT, "landmark_graph_test: the tiled form %s against its geometry's verdict", tiled ? "ran" : "declined");
+        if (!tiled) k_compact_count(c, c->wedges.p, N, io->directed, cnt.p); // (one rank: scatter_wedges)
+        io->form_ran = tiled ? 1 : 2;
+        if (tiled) { io->rshift = G.rshift; io->colbits = G.colbits; io->ntile = G.ntile; }
+        if (io->wedges) HIP_CHECK(hipMemcpyAsync(io->wedges, c->wedges.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
+        if (io->positive) HIP_CHECK(hipMemcpyAsync(io->positive, cnt.p, sizeof(i64), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (want_deg || want_blk) { c->s_degin.ensure(N); c->s_degout.ensure(N); c->s_star.ensure(N); }
+    if (want_deg) {
+        k_wedge_degrees(c, c->wedges.p, N, c->s_degout.p, c->s_degin.p, c->s_star.p);
+        if (io->deg_out) HIP_CHECK(hipMemcpyAsync(io->deg_out, c->s_degout.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        if (io->deg_in) HIP_CHECK(hipMemcpyAsync(io->deg_in, c->s_degin.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        if (io->star) HIP_CHECK(hipMemcpyAsync(io->star, c->s_star.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (want_blk) { // every pretend rank's row block, the ranks' sum (in rank order) on the host, then the unpack
+        DevBuf<double> X;
+        X.ensure(3 * N);
+        std::vector<double> sum(3 * N, 0.0);
+        for (i64 r = 0; r < io->world; r++) {
+            const RowBlock blk = row_block_of(N, r, io->world);
+            double *out = io->deg_block + r * 3 * N;
+            k_wedge_degrees_block(c, c->wedges.p, N, blk.r0, blk.r1, X.p);
+            HIP_CHECK(hipMemcpyAsync(out, X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            for (i64 k = 0; k < 3 * N; k++) sum[k] += out[k];
+        }
+        HIP_CHECK(hipMemcpyAsync(X.p, sum.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
+        k_degrees_unpack(c, X.p, N, c->s_degout.p, c->s_degin.p, c->s_star.p);
+        HIP_CHECK(hipMemcpyAsync(io->u_deg_out, c->s_degout.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(io->u_deg_in, c->s_degin.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(io->u_star, c->s_star.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
     flush_timers(c);
 }

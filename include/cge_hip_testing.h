@@ -65,6 +65,48 @@ int cge_group_cut_test(void *ctx, const int32_t *ids, const int32_t *task_row_of
  * row-major, uncentred) and mean (d): what the device centred with */
 int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int64_t *lcomm, int64_t C, int pass, double *P,
                              int64_t *nref, int *pass_ran, double *ref_points, double *mean);
+/* kernel-level hook (needs the GPU): the stage of a landmark run that turns an assignment into the landmark graph, on a caller's
+ * v2l[n] (ids in 1..N) over the resident graph and vertex data, by the stage's own functions and launch wrappers (the ones
+ * cge_landmarks_run and cge_score call).  Every output pointer may be NULL: that work is skipped.  The call drops the results of
+ * an earlier cge_landmarks_run (its buffers are used).
+ *   Aggregate (src/landmarks.jl:387-430; needs the embedding and the vertex data, every landmark with at least one member): the
+ *   landmark -> members index with ascending members, then k_landmark_aggregate: lemb[N][d] (row-major), lweight[N], dii[N],
+ *   lcomm[N] (0-based community of the last member).
+ *   The landmark-pair matrix (:433-451; landmarks without a member allowed): wedges[N][N] row-major and *positive, the count of
+ *   its positive entries (on and above the diagonal when undirected), from the share `part` of `nparts` of the edges that a rank
+ *   takes -- of the chunks of the blocked edge list for the tiled form, of the m edges for the gather form.
+ *   wedge_form 0: what a run picks; 1: the tiled two-pass form (k_wedge_scatter_blocked); 2: k_edge_scatter + k_compact_count.
+ *   Degrees of the directed score from that matrix: deg_out[N], deg_in[N], star[N] by k_wedge_degrees; deg_block[world][3 N] by
+ *   k_wedge_degrees_block on the row block of each of `world` pretend ranks; u_deg_out, u_deg_in, u_star [N] = k_degrees_unpack
+ *   of the blocks' sum (added in rank order).
+ *   Out: form_ran (1 or 2), n_chunks (of the blocked edge list; 0 when there is none), and the tiled form's geometry for this
+ *   share when it ran (rshift, colbits, ntile; -1 otherwise).
+ * CGE_E_ARG with a message, before any launch: an id outside 1..N, missing residents, a landmark without a member when the
+ * aggregate is asked for, part / nparts / world out of range, a context with option shard_rows or shard_ingest, wedge_form 1 where
+ * the blocked edge list or the geometry declines. */
+typedef struct cge_landmark_graph_io {
+    const int64_t *v2l;
+    int64_t N;
+    int32_t directed, wedge_form;
+    int64_t part, nparts, world;
+    double *lemb, *lweight, *dii;
+    int32_t *lcomm;
+    double *wedges;
+    int64_t *positive;
+    double *deg_out, *deg_in;
+    int32_t *star;
+    double *deg_block, *u_deg_out, *u_deg_in;
+    int32_t *u_star;
+    int64_t n_chunks, ntile;
+    int32_t form_ran, rshift, colbits, pad;
+} cge_landmark_graph_io;
+int cge_landmark_graph_test(void *ctx, cge_landmark_graph_io *io);
+/* host-only (no device work, no context): the geometry of the tiled form of the landmark-pair matrix for N landmarks over
+ * n_chunks chunks of a unit (weighted = 0) or weighted edge list, as the launch reads it.  *applies = 0: the form declines (the
+ * other outputs are not written).  Else tiles of 1 << rshift rows, 16-bit keys of rshift + colbits bits, ntile tiles and the
+ * dynamic LDS in bytes of pass 1 (wedge_pass_kernel) and pass 2 (wedge_tile_kernel). */
+int cge_wedge_geometry_test(int64_t N, int weighted, int64_t n_chunks, int *applies, int *rshift, int *colbits, int64_t *ntile,
+                            int64_t *lds_pass1, int64_t *lds_pass2);
 /* out[i] = (1 - x[i])^alpha on the device (host vectors): method 0 = the library pow, 1 = exp2(alpha * log2(1 - x)) with
  * the logarithm in double + float parts, as the alpha sweep computes GD = (1 - D)^alpha (src/divergence.jl:142-148) */
 int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method, double *out);

@@ -100,6 +100,28 @@ def test_fit_hook_is_declared_and_refuses_a_null_context():
     assert ran.value == -1
 
 
+def test_landmark_graph_hooks_are_declared_and_refuse_a_null_context():
+    """The kernel-level hook of the landmark graph stage (tests/test_gpu_landmark_graph.py) and the host-only hook of the tiled
+    form's geometry (tests/test_landmark_graph_ref.py): among the declared symbols the export test walks; CGE_E_ARG for a null
+    context, null arguments, no assignment or an unknown form before anything touches a device."""
+    from cge.jl_amd import api
+
+    names = _declared("cge_hip_testing.h")
+    assert "cge_landmark_graph_test" in names and "cge_wedge_geometry_test" in names
+    lib = api.load_library()
+    io = api.LandmarkGraphIO()
+    assert C.sizeof(io) == 23 * 8  # cge_landmark_graph_io: 14 pointers, N, part, nparts, world, n_chunks, ntile, six 4-byte fields
+    v2l = (C.c_int64 * 3)(1, 2, 1)
+    io.v2l, io.N, io.nparts, io.form_ran = C.addressof(v2l), 2, 1, -5
+    assert lib.cge_landmark_graph_test(None, C.byref(io)) == -7
+    assert lib.cge_landmark_graph_test(None, None) == -7
+    assert io.form_ran == -5
+    ap = C.c_int(-1)
+    assert lib.cge_wedge_geometry_test(C.c_int64(4000), 0, C.c_int64(105), C.byref(ap), None, None, None, None, None) == -7
+    assert ap.value == -1
+    assert api.wedge_geometry_test(4000, False, 105)["rshift"] == 2
+
+
 def test_create_fails_loudly_without_gpu():
     import torch
 
