@@ -122,6 +122,23 @@ class LandmarkGraphIO(C.Structure):
                 ("form_ran", C.c_int32), ("rshift", C.c_int32), ("colbits", C.c_int32), ("pad", C.c_int32)]
 
 
+class LocalScoreIO(C.Structure):
+    """cge_local_score_io (include/cge_hip_testing.h): the arguments of the testing hook cge_local_score_test."""
+    _fields_ = [("S", C.c_int64), ("seed", C.c_int64), ("stream_id", C.c_int64), ("directed", C.c_int32),
+                ("draw_route", C.c_int32), ("form", C.c_int32), ("pad", C.c_int32),
+                ("pos", C.c_void_p), ("neg_i", C.c_void_p), ("neg_j", C.c_void_p), ("attempt", C.c_void_p), ("rounds", C.c_int64),
+                ("pos_in", C.c_void_p), ("pos2_in", C.c_void_p), ("neg_i_in", C.c_void_p), ("neg_j_in", C.c_void_p),
+                ("pi", C.c_void_p), ("pj", C.c_void_p), ("ni", C.c_void_p), ("nj", C.c_void_p), ("wts", C.c_void_p),
+                ("pi_in", C.c_void_p), ("pj_in", C.c_void_p), ("ni_in", C.c_void_p), ("nj_in", C.c_void_p),
+                ("wts_in", C.c_void_p), ("hi", C.c_double), ("dpos", C.c_void_p), ("dneg", C.c_void_p),
+                ("dpos_in", C.c_void_p), ("dneg_in", C.c_void_p), ("N", C.c_int64), ("alpha", C.c_double),
+                ("Ta", C.c_void_p), ("Tb", C.c_void_p), ("vw", C.c_void_p), ("lweight", C.c_void_p), ("GD", C.c_void_p),
+                ("v2l", C.c_void_p), ("old2new", C.c_void_p), ("part", C.c_void_p), ("out2", C.c_void_p),
+                ("D", C.c_void_p), ("w", C.c_void_p), ("T0", C.c_void_p), ("eps", C.c_double), ("delta", C.c_double),
+                ("T", C.c_void_p), ("afac", C.c_void_p), ("aden", C.c_void_p), ("aidx", C.c_void_p), ("iters", C.c_int64),
+                ("status", C.c_int32), ("pad2", C.c_int32)]
+
+
 DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
 _NP_DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
 
@@ -1037,6 +1054,77 @@ class Context:
         for q, out in zip(arr, outs):
             out["iters"], out["status"] = int(q.iters), int(q.status)
         return ran.value, outs
+
+    def local_score_test(self, S, directed=False, draw=None, draws=None, pos2=None, pairs=None, prepare=False, hi=None,
+                         distances=False, dists=None, tally=None):
+        """Testing hook (include/cge_hip_testing.h: cge_local_score_test): the stages of the local score on the resident graph
+        and embedding; every id is 0-based.
+          draw = (seed, stream_id, route): the device sampler (route 1 k_draw_samples_dev, 2 _begin + _finish) -> pos, neg_i,
+            neg_j, attempt, rounds;
+          draws = (pos, neg_i, neg_j), pos2: supplied draws for Prepare; prepare=True -> pi, pj, ni, nj, wts;
+          pairs = (pi, pj, ni, nj, wts): supplied pairs in place of Prepare; hi with distances=True -> dpos, dneg;
+          dists = (dpos, dneg): supplied distances for the tally;
+          tally = dict(form, N, alpha, Ta, Tb, v2l, vw, lweight, old2new, GD, D, w, T0, eps, delta) -> part (64, 2), out2 and,
+            form 4, T, aidx (4, S), afac (8, S), aden (64,), iters, status.
+        Returns a dict of what the stages that were asked for give."""
+        S = int(S)
+        io, out, keep = LocalScoreIO(), {}, []
+        io.S, io.directed = S, int(bool(directed))
+
+        def give(key, a, dtype):
+            if a is None:
+                return
+            a = np.ascontiguousarray(a, dtype=dtype)
+            keep.append(a)
+            setattr(io, key, a.ctypes.data)
+
+        def want(key, shape, dtype=np.float64):
+            fill = np.nan if dtype == np.float64 else -1 if dtype == np.int32 else np.iinfo(dtype).max
+            out[key] = np.full(shape, fill, dtype=dtype)
+            setattr(io, key, out[key].ctypes.data)
+
+        n_out = max(S, 1)
+        if draw is not None:
+            io.seed, io.stream_id, io.draw_route = int(draw[0]), int(draw[1]), int(draw[2])
+            want("pos", n_out, np.int32), want("neg_i", n_out, np.int32), want("neg_j", n_out, np.int32)
+            want("attempt", n_out, np.uint32)
+        if draws is not None:
+            for key, a in zip(("pos_in", "neg_i_in", "neg_j_in"), draws):
+                give(key, a, np.int32)
+        give("pos2_in", pos2, np.int32)
+        if prepare:
+            for key in ("pi", "pj", "ni", "nj"):
+                want(key, n_out, np.int32)
+            want("wts", n_out)
+        if pairs is not None:
+            for key, a in zip(("pi_in", "pj_in", "ni_in", "nj_in"), pairs[:4]):
+                give(key, a, np.int32)
+            give("wts_in", pairs[4], np.float64)
+        if hi is not None:
+            io.hi = float(hi)
+        if distances:
+            want("dpos", n_out), want("dneg", n_out)
+        if dists is not None:
+            give("dpos_in", dists[0], np.float64), give("dneg_in", dists[1], np.float64)
+        if tally is not None:
+            t = dict(tally)
+            io.form, io.N, io.alpha = int(t.pop("form")), int(t.pop("N")), float(t.pop("alpha", 1.0))
+            io.eps, io.delta = float(t.pop("eps", 0.25)), float(t.pop("delta", 0.001))
+            for key in ("v2l", "old2new"):
+                give(key, t.pop(key, None), np.int32)
+            for key in ("Ta", "Tb", "vw", "lweight", "GD", "D", "w", "T0"):
+                give(key, t.pop(key, None), np.float64)
+            assert not t, sorted(t)
+            want("part", (64, 2)), want("out2", 2)
+            if io.form == 4:
+                want("T", max(io.N, 1)), want("aidx", (4, n_out), np.int32), want("afac", (8, n_out)), want("aden", 64)
+            io.iters, io.status = -1, -1
+        self._check(self.L.cge_local_score_test(self.h, C.byref(io)))
+        if draw is not None:
+            out["rounds"] = int(io.rounds)
+        if tally is not None and io.form == 4:
+            out["iters"], out["status"] = int(io.iters), int(io.status)
+        return out
 
     def segment_sort_test(self, z, offsets):
         """Testing hook: the per-group stable sort of runsplit's projections; returns (sorted z, local permutation)."""

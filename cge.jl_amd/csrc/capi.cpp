@@ -573,6 +573,15 @@ int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int direc
     CGE_CATCH(c)
 }
 
+// testing hook (include/cge_hip_testing.h): the local score's sampler, prepared pairs, pair distances and tallies, stage by stage
+int cge_local_score_test(void *ctx, cge_local_score_io *io) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !io || io->form < 0 || io->form > 4 || io->draw_route < 0 || io->draw_route > 2) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_local_score_test(c, io);
+    CGE_CATCH(c)
+}
+
 // testing hook (include/cge_hip_testing.h): the per-group stable sort of the projections as runsplit calls it
 int cge_segment_sort_test(void *ctx, const double *z, const int32_t *task_row_off, int64_t T, double *zs_out, int32_t *perm_out) {
     cge_ctx *c = (cge_ctx *)ctx;

@@ -1091,6 +1091,8 @@ struct AlphaBook {
     void take(const double *res, double alpha, i64 iters);
     void write(double out[7], int *out_len) const; // the reference's 7-vector (:256)
 };
+struct cge_local_score_io; // (include/cge_hip_testing.h)
+void host_local_score_test(cge_ctx *c, cge_local_score_io *io); // the testing hook of the local score's stages (wgcl_host.cpp)
 struct cge_vect_b_problem; // (include/cge_hip_testing.h)
 void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
                          double *GD);

@@ -1099,7 +1099,10 @@ static bool ft_verdict(cge_ctx *c, const int *dev_flags, i64 *iters) {
     return !(hf[2] || !hf[0]);
 }
 
-static int ft_undirected(cge_ctx *c, cge_fit_problem &p, int form, double eps, double delta) {
+// epi / epi_dev (form 4, the hook of the local score): the host and device copies of the epilogue's table (fused_tables); the
+// launch then wants the tally of the epilogue and not vect_B, as enqueue_alpha asks for it once the divergence is skipped.
+static int ft_undirected(cge_ctx *c, cge_fit_problem &p, int form, double eps, double delta, const cge_fit_fused *epi = nullptr,
+                         const cge_fit_fused *epi_dev = nullptr) {
     hipStream_t st = c->stream;
     const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
     ft_matrices(c, p, true, form != 4);
@@ -1134,9 +1137,10 @@ static int ft_undirected(cge_ctx *c, cge_fit_problem &p, int form, double eps, d
     fit.delta = delta;
     fit.persistent = form == 3 || form == 4 || (form == 0 && persistent_wanted(c, N));
     cge_fit_fused ff{};
-    ff.Lh = c->sw_Lh.p; ff.Ll = c->sw_Ll.p; ff.alpha = p.alpha; // (no partial, no auc_part: nothing is wanted of the epilogue)
+    if (epi) { ff = *epi; ff.partial = nullptr; } // (else no partial, no auc_part: nothing is wanted of the epilogue)
+    ff.Lh = c->sw_Lh.p; ff.Ll = c->sw_Ll.p; ff.alpha = p.alpha;
     AlphaSlot sl;
-    fit_undirected(c, N, dw.p, Tld, p.alpha, true, form == 2, form == 4 ? &ff : nullptr, nullptr, fit, sl);
+    fit_undirected(c, N, dw.p, Tld, p.alpha, true, form == 2, form == 4 ? &ff : nullptr, form == 4 ? epi_dev : nullptr, fit, sl);
     int ran = form == 2 ? 2 : 1;
     p.status = 0;
     if (sl.fit_async) {
@@ -1292,6 +1296,227 @@ void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int 
         *form_ran = 5;
     } else
         *form_ran = directed ? ft_directed(c, probs[0], form, eps, delta) : ft_undirected(c, probs[0], form, eps, delta);
+}
+
+// ---- the testing hook of the local score (include/cge_hip_testing.h: cge_local_score_test) -----------------------------------
+// The stages of the local score on the buffers a sweep keeps them in (the first DevSamples of the context): the device sampler,
+// k_prep_samples, sampled_pair_dist and the tallies -- k_auc_landmark / k_auc_exact, or the epilogue of the fused fit through
+// fused_tables and ft_undirected.  Every check comes before the first launch.
+static void ls_range(const char *what, const i32 *v, i64 cnt, i64 lim) {
+    for (i64 k = 0; k < cnt; k++)
+        if (v[k] < 0 || v[k] >= lim)
+            CGE_THROW(CGE_E_ARG, "local_score_test: %s[%lld] = %d outside 0..%lld", what, (long long)k, (int)v[k], (long long)(lim - 1));
+}
+template <class T>
+static void ls_up(cge_ctx *c, DevBuf<T> &dev, const T *host, i64 cnt) {
+    dev.ensure((size_t)cnt);
+    HIP_CHECK(hipMemcpyAsync(dev.p, host, sizeof(T) * cnt, hipMemcpyHostToDevice, c->stream));
+}
+template <class T>
+static void ls_down(cge_ctx *c, T *host, const T *dev, i64 cnt) {
+    if (host) HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(T) * cnt, hipMemcpyDeviceToHost, c->stream));
+}
+
+void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
+    hipStream_t st = c->stream;
+    const i64 S = io->S, n = c->n, m = c->m, N = io->N;
+    const int directed = io->directed != 0, form = io->form;
+    const bool landmark_form = form == 1 || form == 4, exact_form = form == 2 || form == 3;
+    // the stages that run
+    const bool draw = io->draw_route != 0;
+    const bool pairs_in = io->pi_in || io->pj_in || io->ni_in || io->nj_in || io->wts_in;
+    const bool draws_in = io->pos_in || io->neg_i_in || io->neg_j_in;
+    const bool dist = io->dpos || io->dneg || (landmark_form && !io->dpos_in);
+    const bool prep = io->pi || io->pj || io->ni || io->nj || io->wts || ((dist || form != 0) && !pairs_in);
+    // ---- the checks --------------------------------------------------------------------------------------------------------------
+    if (S < 1 || S >= ((i64)1 << 28)) CGE_THROW(CGE_E_ARG, "local_score_test: S = %lld samples", (long long)S);
+    if (c->rows_sharded || c->edges_sharded)
+        CGE_THROW(CGE_E_ARG, "local_score_test: not with option shard_rows / shard_ingest (every row and edge on one rank)");
+    if ((draw || prep) && (!c->src.p || !c->dst.p || m <= 0 || n < 2 || (!c->unit_weights && !c->w.p)))
+        CGE_THROW(CGE_E_ARG, "local_score_test: the graph is not resident (cge_set_graph)");
+    if (prep && pairs_in) CGE_THROW(CGE_E_ARG, "local_score_test: the pairs are prepared or supplied, not both");
+    if (pairs_in && (!io->pi_in || !io->pj_in || !io->ni_in || !io->nj_in || !io->wts_in))
+        CGE_THROW(CGE_E_ARG, "local_score_test: supplied pairs are pi_in, pj_in, ni_in, nj_in and wts_in together");
+    if (draws_in && (!io->pos_in || !io->neg_i_in || !io->neg_j_in))
+        CGE_THROW(CGE_E_ARG, "local_score_test: supplied draws are pos_in, neg_i_in and neg_j_in together");
+    if (prep && !draws_in && !draw) CGE_THROW(CGE_E_ARG, "local_score_test: Prepare takes pos_in, neg_i_in and neg_j_in, or a draw");
+    if (io->pos2_in && !prep) CGE_THROW(CGE_E_ARG, "local_score_test: pos2_in goes with Prepare");
+    if ((io->dpos_in != nullptr) != (io->dneg_in != nullptr)) CGE_THROW(CGE_E_ARG, "local_score_test: dpos_in and dneg_in go together");
+    if (io->dpos_in && form == 0) CGE_THROW(CGE_E_ARG, "local_score_test: dpos_in and dneg_in go with a tally");
+    if ((landmark_form || dist) && n < 1) CGE_THROW(CGE_E_ARG, "local_score_test: nothing is resident");
+    if (dist && (!c->Xr.p || c->d <= 0 || c->Xr.n < (size_t)(n * c->d)))
+        CGE_THROW(CGE_E_ARG, "local_score_test: the embedding is not resident (cge_set_embedding)");
+    if (dist && !(io->hi > 0.0)) CGE_THROW(CGE_E_ARG, "local_score_test: hi = %g (the distances are divided by it)", io->hi);
+    if (form != 0 && (N < 1 || N > 46340)) CGE_THROW(CGE_E_ARG, "local_score_test: N = %lld", (long long)N);
+    if (exact_form && prep && N != n)
+        CGE_THROW(CGE_E_ARG, "local_score_test: forms 2 and 3 on prepared pairs take N = n (N = %lld, n = %lld)", (long long)N, (long long)n);
+    if (draws_in && prep) {
+        ls_range("pos_in", io->pos_in, S, m);
+        ls_range("neg_i_in", io->neg_i_in, S, n);
+        ls_range("neg_j_in", io->neg_j_in, S, n);
+    }
+    if (io->pos2_in) ls_range("pos2_in", io->pos2_in, S, m);
+    if (pairs_in) {
+        const i64 lim = exact_form ? (dist ? std::min(N, n) : N) : n;
+        ls_range("pi_in", io->pi_in, S, lim);
+        ls_range("pj_in", io->pj_in, S, lim);
+        ls_range("ni_in", io->ni_in, S, lim);
+        ls_range("nj_in", io->nj_in, S, lim);
+    }
+    if (landmark_form) {
+        if (!io->v2l || !io->vw || !io->lweight) CGE_THROW(CGE_E_ARG, "local_score_test: forms 1 and 4 take v2l, vw and lweight");
+        ls_range("v2l", io->v2l, n, N);
+        if (io->old2new) {
+            ls_range("old2new", io->old2new, N, N);
+            std::vector<char> seen(N, 0);
+            for (i64 l = 0; l < N; l++) {
+                if (seen[io->old2new[l]]) CGE_THROW(CGE_E_ARG, "local_score_test: old2new is not a permutation (%d twice)", (int)io->old2new[l]);
+                seen[io->old2new[l]] = 1;
+            }
+        }
+    }
+    if (form == 1 && !io->Ta) CGE_THROW(CGE_E_ARG, "local_score_test: form 1 takes Ta");
+    if (exact_form && (!io->GD || !io->Ta)) CGE_THROW(CGE_E_ARG, "local_score_test: forms 2 and 3 take GD and Ta");
+    if ((form == 3 || form == 4) && directed) CGE_THROW(CGE_E_ARG, "local_score_test: form %d is undirected only", form);
+    if (form == 4) {
+        if (!io->D || !io->w || !io->T0) CGE_THROW(CGE_E_ARG, "local_score_test: form 4 takes D, w and T0");
+        if (!(io->eps > 0.0) || !(io->delta >= 0.0)) CGE_THROW(CGE_E_ARG, "local_score_test: eps > 0 and delta >= 0");
+        if (!c->opt_pow_exp2)
+            CGE_THROW(CGE_E_ARG, "local_score_test: form 4 makes its power matrix from the stored logarithm (option pow_exp2)");
+        if (!k_fit_flow_fused_applies(c, N))
+            CGE_THROW(CGE_E_ARG, "local_score_test: the geometry of the fused persistent fit declines N = %lld", (long long)N);
+    }
+    // ---- Draw --------------------------------------------------------------------------------------------------------------------
+    while (c->dsets.empty()) c->dsets.emplace_back(new DevSamples());
+    DevSamples &ds = *c->dsets[0];
+    DevBuf<i32> d_pos, d_pos2, d_ni, d_nj;
+    io->rounds = 0;
+    if (draw) {
+        d_pos.ensure(S); d_ni.ensure(S); d_nj.ensure(S);
+        if (io->draw_route == 1)
+            k_draw_samples_dev(c, io->seed, io->stream_id, S, directed, d_pos.p, d_ni.p, d_nj.p);
+        else {
+            k_draw_samples_begin(c, io->seed, io->stream_id, S, directed, d_pos.p, d_ni.p, d_nj.p);
+            k_draw_samples_finish(c);
+        }
+        io->rounds = c->samp_pending.round;
+        ls_down(c, io->pos, d_pos.p, S);
+        ls_down(c, io->neg_i, d_ni.p, S);
+        ls_down(c, io->neg_j, d_nj.p, S);
+        ls_down(c, io->attempt, c->samp_attempt.p, S);
+    }
+    // ---- Prepare -----------------------------------------------------------------------------------------------------------------
+    if (prep) {
+        if (draws_in) {
+            ls_up(c, d_pos, io->pos_in, S);
+            ls_up(c, d_ni, io->neg_i_in, S);
+            ls_up(c, d_nj, io->neg_j_in, S);
+        }
+        if (io->pos2_in) ls_up(c, d_pos2, io->pos2_in, S);
+        ds.pi.ensure(S); ds.pj.ensure(S); ds.ni.ensure(S); ds.nj.ensure(S); ds.wts.ensure(S);
+        k_prep_samples(c, d_pos.p, io->pos2_in ? d_pos2.p : d_pos.p, d_ni.p, d_nj.p, c->src.p, c->dst.p, c->w.p, S, directed, ds.pi.p,
+                       ds.pj.p, ds.ni.p, ds.nj.p, ds.wts.p);
+        ls_down(c, io->pi, ds.pi.p, S);
+        ls_down(c, io->pj, ds.pj.p, S);
+        ls_down(c, io->ni, ds.ni.p, S);
+        ls_down(c, io->nj, ds.nj.p, S);
+        ls_down(c, io->wts, ds.wts.p, S);
+    } else if (pairs_in) {
+        ls_up(c, ds.pi, io->pi_in, S);
+        ls_up(c, ds.pj, io->pj_in, S);
+        ls_up(c, ds.ni, io->ni_in, S);
+        ls_up(c, ds.nj, io->nj_in, S);
+        ls_up(c, ds.wts, io->wts_in, S);
+    }
+    // ---- Distances ---------------------------------------------------------------------------------------------------------------
+    if (dist) {
+        ds.dpos.ensure(S); ds.dneg.ensure(S);
+        sampled_pair_dist(c, c->Xr.p, c->d, ds.pi.p, ds.pj.p, S, io->hi, ds.dpos.p);
+        sampled_pair_dist(c, c->Xr.p, c->d, ds.ni.p, ds.nj.p, S, io->hi, ds.dneg.p);
+        ls_down(c, io->dpos, ds.dpos.p, S);
+        ls_down(c, io->dneg, ds.dneg.p, S);
+    }
+    if (io->dpos_in) { // (behind the copies out of the distance stage, when that ran for its outputs)
+        ls_up(c, ds.dpos, io->dpos_in, S);
+        ls_up(c, ds.dneg, io->dneg_in, S);
+    }
+    // ---- Tally -------------------------------------------------------------------------------------------------------------------
+    DevBuf<double> dTa, dTb, dvw, dlw, dout2;
+    DevBuf<i32> dv2l, do2n;
+    std::vector<double> hpart(2 * CGE_PARTIAL_BLOCKS, std::nan(""));
+    if (landmark_form) {
+        ls_up(c, dv2l, io->v2l, n);
+        ls_up(c, dvw, io->vw, n);
+        ls_up(c, dlw, io->lweight, N);
+        if (io->old2new) ls_up(c, do2n, io->old2new, N);
+    }
+    if (form >= 1 && form <= 3) {
+        ls_up(c, dTa, io->Ta, N);
+        if (io->Tb) ls_up(c, dTb, io->Tb, N);
+        dout2.ensure(2);
+    }
+    if (form == 1) {
+        const double *Ta = dTa.p, *Tb = io->Tb ? dTb.p : dTa.p;
+        if (io->old2new) { // T is stored in sweep order: un-permuted, as local_score_tallies does
+            c->sw_rl_T.ensure((size_t)2 * N);
+            k_permute_rows(c, Ta, do2n.p, N, 1, c->sw_rl_T.p);
+            Ta = c->sw_rl_T.p;
+            if (io->Tb) {
+                k_permute_rows(c, Tb, do2n.p, N, 1, c->sw_rl_T.p + N);
+                Tb = c->sw_rl_T.p + N;
+            } else
+                Tb = Ta;
+        }
+        k_auc_landmark(c, Ta, Tb, dv2l.p, dvw.p, dlw.p, ds.pi.p, ds.pj.p, ds.ni.p, ds.nj.p, ds.dpos.p, ds.dneg.p, ds.wts.p, S, io->alpha,
+                       dout2.p);
+    } else if (exact_form) {
+        const bool packed = form == 3;
+        const i64 Nt = (N + 63) / 64;
+        std::vector<double> pk;
+        if (packed) { // the upper tiles of GD, zeros outside the matrix, through the address inline every consumer uses
+            pk.assign((size_t)(Nt * (Nt + 1) / 2) * CGE_TILE_DOUBLES, 0.0);
+            for (i64 i = 0; i < N; i++)
+                for (i64 j = i / 64 * 64; j < N; j++) pk[cge_packed_index(i, j, Nt)] = io->GD[i * N + j];
+            ls_up(c, c->sw_PK, pk.data(), (i64)pk.size());
+        } else
+            ls_up(c, c->sw_GD, io->GD, N * N);
+        k_auc_exact(c, packed ? c->sw_PK.p : c->sw_GD.p, dTa.p, io->Tb ? dTb.p : dTa.p, N, ds.pi.p, ds.pj.p, ds.ni.p, ds.nj.p, ds.wts.p, S,
+                    dout2.p, nullptr, packed);
+        HIP_CHECK(hipStreamSynchronize(st)); // (pk goes out of scope)
+    }
+    if (form >= 1 && form <= 3) {
+        ls_down(c, hpart.data(), c->auc_part.p, 2 * CGE_PARTIAL_BLOCKS);
+        ls_down(c, io->out2, dout2.p, 2);
+    }
+    if (form == 4) {
+        c->sw_scal.ensure(RES_STRIDE);
+        HIP_CHECK(hipMemsetAsync(c->sw_scal.p + RES_AUC, 0xFF, sizeof(double) * 2 * CGE_PARTIAL_BLOCKS, st)); // (NaN until the epilogue writes)
+        OrigView orig;
+        orig.n = n; orig.v2l = dv2l.p; orig.vw = dvw.p; orig.lweight = dlw.p;
+        ScoreGraph G;
+        G.N = N;
+        std::vector<cge_fit_fused> h_epi;
+        fused_tables(c, G, &orig, io->old2new ? do2n.p : nullptr, 1, 0, S, true, h_epi);
+        std::vector<double> hT(N);
+        cge_fit_problem p{};
+        p.D = io->D; p.w = io->w; p.T0 = io->T0; p.T = io->T ? io->T : hT.data(); p.N = N; p.alpha = io->alpha;
+        ft_undirected(c, p, 4, io->eps, io->delta, &h_epi[0], reinterpret_cast<const cge_fit_fused *>(c->sw_fused_epi.p));
+        io->iters = p.iters;
+        io->status = p.status;
+        ls_down(c, hpart.data(), c->sw_scal.p + RES_AUC, 2 * CGE_PARTIAL_BLOCKS);
+        ls_down(c, io->aidx, ds.aidx.p, 4 * S);
+        ls_down(c, io->afac, ds.afac.p, 8 * S);
+        ls_down(c, io->aden, ds.afac.p + 8 * S, (i64)CGE_PARTIAL_BLOCKS);
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (form == 3) c->sw_PK.release(); // (held only while packed sweeps run)
+    if (form != 0 && io->part) std::memcpy(io->part, hpart.data(), sizeof(double) * hpart.size());
+    if (form == 4 && io->out2) { // the block tallies in block order, as the sweep's host adds them
+        double num = 0.0, den = 0.0;
+        for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { num += hpart[2 * b]; den += hpart[2 * b + 1]; }
+        io->out2[0] = num;
+        io->out2[1] = den;
+    }
 }
 
 // ---- the testing hook of the packed form (include/cge_hip_testing.h: cge_packed_gd_test) -------------------------------

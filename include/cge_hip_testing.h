@@ -177,6 +177,74 @@ typedef struct cge_fit_problem {
     int32_t status, pad;
 } cge_fit_problem;
 int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int directed, int form, double eps, double delta, int *form_ran);
+/* kernel-level hook (needs the GPU): the local half of the score (elements 5-7, src/divergence.jl:178-213, :485-517) stage by
+ * stage -- the device sampler, the prepared pairs, full_graph_D of the sampled pairs and the tallies -- on the resident graph,
+ * embedding and a caller's landmark data, by the sweep's own functions and launch wrappers.  A struct of optional stages: an
+ * output that is NULL is not copied out, and a stage none of whose outputs is wanted and that no later stage needs is not run.
+ * Every id is 0-based, as the device holds it.  S samples (all stages).
+ *   Draw (draw_route 1: k_draw_samples_dev; 2: k_draw_samples_begin, then k_draw_samples_finish; 0: no draw) from seed and
+ *   stream_id over the resident graph WHATEVER ITS SIZE (a score draws on the device beyond n (n - 1) = 2^25 only; that rule is
+ *   the library's and stays).  Out: pos[S] (rows of the resident edge list), neg_i[S], neg_j[S], attempt[S] = the attempt number
+ *   that gave each non-edge (the sampler's samp_attempt), *rounds = rounds of the rejection that ran.
+ *   Prepare (k_prep_samples over the resident edge list) from pos_in / neg_i_in / neg_j_in, or the pairs just drawn where
+ *   pos_in == NULL; pos2_in (optional): the overwriting draw of :510 -- the pairs come from pos2_in, the weights from pos_in.
+ *   Out: pi, pj, ni, nj [S], wts[S].
+ *   Distances (sampled_pair_dist on the resident embedding, divided by `hi`) of the prepared pairs, or of pi_in, pj_in, ni_in,
+ *   nj_in (with wts_in, in place of Prepare).  Out: dpos[S], dneg[S].
+ *   Tally (form != 0) over the prepared or supplied pairs and weights; dpos_in / dneg_in stand in for the distance stage, so a
+ *   caller decides every tie.  Out: part[2 x 64] = the block tallies {num, den} and out2[2] = their sums in block order.
+ *     form 1: k_auc_landmark on Ta, Tb (N; Tb == NULL: Ta), v2l[n], vw[n], lweight[N], alpha; out2 by auc_final_kernel.  old2new
+ *             (optional, N): Ta / Tb are stored in sweep order (T[old2new[l]] belongs to landmark l) and un-permuted by
+ *             k_permute_rows first, as local_score_tallies does;
+ *     form 2: k_auc_exact on GD (N x N, row-major), Ta, Tb; the pairs index the N score-graph vertices;
+ *     form 3: the same on the packed tiles (GD packed on the host through cge_packed_index; undirected: i <= j);
+ *     form 4: the epilogue of the fused persistent fit, launched as enqueue_alpha launches it with the tally wanted and vect_B
+ *             not: tables by fused_tables / k_auc_prepare (through old2new when given), the fit of cge_fit_test form 4 on D (N x N),
+ *             w, T0 (sweep order), alpha, eps, delta.  Also out: T[N] = the iterate the launch left, aidx[4 S], afac[8 S],
+ *             aden[64] as prepared, iters, status (1: the launch was abandoned -- part stays NaN); out2 is added on the host in
+ *             block order, as the sweep's host does.
+ * CGE_E_ARG with a message, before any launch: S < 1, a missing resident (graph for Draw / Prepare, embedding for Distances), a
+ * context with option shard_rows or shard_ingest, a row of pos_in / pos2_in outside the edge list, a pair id outside the
+ * vertices (the landmark forms and the distances: n; forms 2, 3: N, and N = n on prepared pairs), v2l or old2new outside
+ * 0..N-1 or old2new not a permutation, a stage without its inputs or with two sources of them, hi <= 0, N outside 1..46340,
+ * forms 3, 4 directed, form 4 with eps <= 0 or delta < 0, without option "pow_exp2" or where the geometry of the fused fit
+ * declines N.  The draw itself returns CGE_E_ARG ("could not find enough non-edges") when a sample is still an edge after 64
+ * rounds; the context stays usable.
+ * Not covered here: the exchange variants of options shard_rows / shard_ingest (pair_dist_rows_kernel, prep_*_sharded_kernel,
+ * check_neg_flag_kernel) need a communicator and stay with tests/test_gpu_two_ranks.py; the multi-problem launch shares the
+ * epilogue body and tests/test_gpu_batch.py holds its members to the single launch bit for bit. */
+typedef struct cge_local_score_io {
+    int64_t S, seed, stream_id;
+    int32_t directed, draw_route, form, pad;
+    /* Draw */
+    int32_t *pos, *neg_i, *neg_j;
+    uint32_t *attempt;
+    int64_t rounds;
+    /* Prepare */
+    const int32_t *pos_in, *pos2_in, *neg_i_in, *neg_j_in;
+    int32_t *pi, *pj, *ni, *nj;
+    double *wts;
+    /* Distances */
+    const int32_t *pi_in, *pj_in, *ni_in, *nj_in;
+    const double *wts_in;
+    double hi;
+    double *dpos, *dneg;
+    /* Tally */
+    const double *dpos_in, *dneg_in;
+    int64_t N;
+    double alpha;
+    const double *Ta, *Tb, *vw, *lweight, *GD;
+    const int32_t *v2l, *old2new;
+    double *part, *out2;
+    /* form 4 */
+    const double *D, *w, *T0;
+    double eps, delta;
+    double *T, *afac, *aden;
+    int32_t *aidx;
+    int64_t iters;
+    int32_t status, pad2;
+} cge_local_score_io;
+int cge_local_score_test(void *ctx, cge_local_score_io *io);
 /* kernel-level hook (needs the GPU): the packed form of an exact sweep (cge_hip.h, option "exact_packed") on a caller's
  * embedding, through the sweep's own launch wrappers -- the extrema pass (lo_hi[0], lo_hi[1] = extrema of D over j >= i with
  * diag on the diagonal, D never stored) and the generator of one alpha (distances, normalisation, power; pow_method 1 = exp2 of

@@ -1040,6 +1040,8 @@ def test_library_drawn_samples_equal_fetched_draws(ctx, synth20k):
 
 
 def test_draw_samples_are_non_edges(ctx, synth20k):
+    """cge_draw_samples: non-edges, reproducible, uniform.  The sparse graph barely leaves the first round of the device sampler and
+    the dense one is enumerated on the host: the rejection loop, sample by sample, is covered by tests/test_gpu_local_score.py."""
     from cge.jl_amd import api
 
     g = synth20k

@@ -285,10 +285,12 @@ def _rank_rows(rank, world, port, q, case):
             # clusters that do not refine the community vector (here: two communities of different ranks merged) -- the
             # verdict is exchanged, so BOTH ranks leave by the same door
             errs = []
-            for bad in ("exact", "span"):
+            for bad in ("exact", "hook", "span"):
                 try:
                     if bad == "exact":
                         ctx.score(g["clusters"], -1, 2, "rss", seed=5, auc_samples=1000)
+                    elif bad == "hook":  # the kernel-level hook of the local score wants every row and edge on one rank
+                        ctx.local_score_test(8, draw=(1, 0, 1))
                     else:
                         a, b = int(np.flatnonzero(owner == 0)[0]), int(np.flatnonzero(owner == 1)[0])
                         cl = [c for k, c in enumerate(g["clusters"]) if k not in (a, b)] + [np.sort(np.concatenate([g["clusters"][a], g["clusters"][b]]))]
@@ -368,7 +370,7 @@ def test_two_ranks_sharded_rows(ctx, case):
         if case.get("wgcl"):
             assert extra[1] == extra_ref[1] and extra[0][0] == extra_ref[0][0] and extra[0][4] == extra_ref[0][4]
             assert np.allclose(extra[0], extra_ref[0], rtol=1e-12, atol=1e-14), (extra, extra_ref)
-            assert extra[2] == [(-7, True), (-7, True)], extra[2]  # CGE_E_ARG, naming the option, on both ranks
+            assert extra[2] == [(-7, True), (-7, True), (-7, True)], extra[2]  # CGE_E_ARG, naming the option, on both ranks
         held += resident
         assert trunc == trunc_ref
         assert crcs[6] == crc_ref[6], "v_to_l differs from the one-rank run"

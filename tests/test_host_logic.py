@@ -122,6 +122,22 @@ def test_landmark_graph_hooks_are_declared_and_refuse_a_null_context():
     assert api.wedge_geometry_test(4000, False, 105)["rshift"] == 2
 
 
+def test_local_score_hook_is_declared_and_refuses_a_null_context():
+    """The kernel-level hook of the local score (tests/test_gpu_local_score.py): among the declared symbols the export test walks;
+    the Python structure has the header's size; CGE_E_ARG for a null context or null arguments before anything touches a
+    device, the outputs untouched."""
+    from cge.jl_amd import api
+
+    assert "cge_local_score_test" in _declared("cge_hip_testing.h")
+    lib = api.load_library()
+    io = api.LocalScoreIO()
+    assert C.sizeof(io) == 51 * 8  # cge_local_score_io: 38 pointers, 6 int64, 4 doubles, six 4-byte fields
+    io.S, io.rounds, io.iters = 8, -5, -5
+    assert lib.cge_local_score_test(None, C.byref(io)) == -7
+    assert lib.cge_local_score_test(None, None) == -7
+    assert io.rounds == -5 and io.iters == -5
+
+
 def test_create_fails_loudly_without_gpu():
     import torch
 
