@@ -1217,7 +1217,7 @@ class Context:
         return [(comm[l], int(nc[l]), float(q[l]), int(rounds[l])) for l in range(count.value)]
 
     _TEST_OPTIONS = ("louvain_wave_len", "fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
-                     "exact_resident_limit")
+                     "exact_resident_limit", "test_eig_roles")
 
     def set_option(self, key, value):
         if key in self._TEST_OPTIONS:  # the testing knobs are not part of the boundary (include/cge_hip_testing.h)

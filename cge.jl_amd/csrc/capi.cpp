@@ -349,6 +349,8 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     if (!strcmp(key, "test_bvec_plain")) { c->opt_test_bvec_plain = value != 0; return CGE_OK; }
     // 1 = rss2 by the one-kernel walk at every width (the comparator of the chain + merge form)
     if (!strcmp(key, "test_rss2_one_kernel")) { c->opt_test_rss2_one_kernel = value != 0; return CGE_OK; }
+    // which wave of a batched eigen-solver workgroup plays which role: 0 by SIMD placement, 1 identity, 2 reversed, 3 rotated by one
+    if (!strcmp(key, "test_eig_roles") && value >= 0 && value <= 3) { c->opt_test_eig_roles = (int)value; return CGE_OK; }
     // start skew of the persistent fits' tile waves, in naps of ~3 us
     if (!strcmp(key, "fit_persistent_test_delay") && value >= 0 && value <= 100000) { c->opt_fit_test_delay = (int)value; return CGE_OK; }
     // 1 = the persistent fit abandons every launch at once

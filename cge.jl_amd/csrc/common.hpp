@@ -413,6 +413,8 @@ struct cge_ctx {
     int opt_shard_samples = 1; // N > 1: 1 = local-score tallies split over the ranks from 10^5 samples on (in-library RCCL), 2 = always, 0 = never
     int opt_shard_forced = 1; // N > 1: the forced per-community phase of runsplit is split over the ranks
     int opt_test_rss2_one_kernel = 0; // testing: rss2 by rss2_walk_kernel at every width (the comparator of the chain + merge form)
+    int opt_test_eig_roles = 0; // testing: the roles of group_eig_kernel's waves (0 by SIMD placement, 1 identity, 2 reversed, 3 rotated by
+                                // one); the results must not depend on it
     i64 opt_test_louvain_wave_len = -2; // testing: Louvain levels >= 2 decide segments longer than this by a wave (-2: the default
                                         // length, -1: every vertex, 2^31 - 1: none); the results must not depend on it
     int opt_test_bvec_plain = 0; // testing: vect_B without LDS staging / rows in flight (the forms of very large score graphs)

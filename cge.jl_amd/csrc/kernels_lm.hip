@@ -2066,17 +2066,46 @@ __device__ __forceinline__ void eig_pick_column(const double (&a)[NR][NC], int j
 // diagonal does).  Same operations on the same values as the LDS-broadcast form: the same bits.
 template <int NR, int NC, bool DPPF>
 __global__ __launch_bounds__(256, 2) void group_eig_kernel(const double *__restrict__ cov, int d,
-                                                           double *__restrict__ vec, int diag_stage) {
+                                                           double *__restrict__ vec, int diag_stage, int roles) {
     constexpr int DP = 64 * NR; // padded dimension (rows held); 4*NC >= d columns held
     __shared__ __attribute__((aligned(16))) double X[DP], U[DP], W[DP], Pp[4][DP], V[DP];
     __shared__ __attribute__((aligned(16))) double diag[DP], off[DP], beta[DP], V0[DP], tri[4 * DP], red[32];
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6); // (the wave's number as a scalar)
+    __shared__ int place[4];
+    const int lane = threadIdx.x & 63, pw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // (the wave's number as a scalar)
     const double *src = cov + (size_t)blockIdx.x * d * d;
     double *out = vec + (size_t)blockIdx.x * d;
     if (d == 1) {
-        if (tid == 0) out[0] = 1.0;
+        if (threadIdx.x == 0) out[0] = 1.0;
         return;
     }
+    // ---- roles.  Role w owns columns [NC w, NC w + NC); role 3 has live columns in every Householder step, role 0 has none
+    // from step NC - 1 on and runs the tridiagonal tail alone.  Two workgroups share a CU and every SIMD holds one wave of each,
+    // so which PHYSICAL wave plays a role decides which roles of the two matrices compete for one SIMD's issue slots.  Left
+    // to the wave numbers, one SIMD carries a wave 3 and a wave 2 and another a wave 1 and a wave 0 (profiles/r15_eig_parent.txt).
+    // The waves publish their SIMD (HW_ID[5:4]) and wave slot (HW_ID[3:0]); on four different SIMDs the roles run 0, 1, 2, 3
+    // along the SIMDs when the slot of the wave on SIMD 0 is even and 3, 2, 1, 0 when it is odd -- the two co-resident
+    // workgroups sit in slots 0 and 1, so role r of one shares its SIMD with role 3 - r of the other.  Otherwise, or on request
+    // (testing knob test_eig_roles: 1 identity, 2 reversed, 3 rotated by one), a fixed permutation of the wave number.  From
+    // here on `wv` and `tid` are the role's, and nothing arithmetic depends on the wave that plays it: the same bits under
+    // every permutation (tests/test_gpu_eig_roles_bits.py).
+    if (lane == 0) place[pw] = (int)__builtin_amdgcn_s_getreg(4 | (31 << 11)) & 0x3f; // HW_REG_HW_ID, bits [5:0]
+    if (threadIdx.x < DP) { beta[threadIdx.x] = 0.0; off[threadIdx.x] = 0.0; V0[threadIdx.x] = 0.0; X[threadIdx.x] = 0.0; }
+    __syncthreads();
+    int role = roles == 2 ? 3 - pw : roles == 3 ? (pw + 1) & 3 : pw;
+    if (roles == 0) {
+        const int p0 = place[0], p1 = place[1], p2 = place[2], p3 = place[3];
+        const int simds = (1 << (p0 >> 4)) | (1 << (p1 >> 4)) | (1 << (p2 >> 4)) | (1 << (p3 >> 4));
+        if (simds == 15) { // four different SIMDs
+            const int on0 = (p0 >> 4) == 0 ? p0 : (p1 >> 4) == 0 ? p1 : (p2 >> 4) == 0 ? p2 : p3; // the wave on SIMD 0
+            const int mine = place[pw] >> 4;
+            role = (on0 & 1) ? 3 - mine : mine;
+        }
+    }
+    const int wv = __builtin_amdgcn_readfirstlane(role), tid = 64 * wv + lane;
+    // Wave priority: everything in this kernel is a chain of dependent operations except the rank-2 update, 2 NC NR independent
+    // FMAs per step.  Issue between the two waves of a SIMD goes by priority, then age: at equal priority the younger matrix's
+    // chains wait behind the older one's bulk.  So the kernel runs at priority 2 and drops to 0 for the rank-2 update alone.
+    __builtin_amdgcn_s_setprio(2);
     double a[NR][NC];
 #pragma unroll
     for (int r = 0; r < NR; r++) {
@@ -2103,9 +2132,7 @@ __global__ __launch_bounds__(256, 2) void group_eig_kernel(const double *__restr
     };
     using RBlk0 = std::integral_constant<int, 0>;
     using RBlkL = std::integral_constant<int, NR - 1>;
-    if (tid < DP) { beta[tid] = 0.0; off[tid] = 0.0; V0[tid] = 0.0; X[tid] = 0.0; }
-    __syncthreads();
-    extract(0, RBlk0{});
+    extract(0, RBlk0{}); // (beta, off, V0, X were cleared in front of the barrier of the roles)
     // CGE_EIG_CLOCK (a build flag, diagnostics only): s_memtime stamps around the sections of a step, summed over the steps and
     // printed by waves 0 and 3 of the first matrix (the stamps wait for the LDS queue: shares, not absolute times)
 #ifdef CGE_EIG_CLOCK
@@ -2151,42 +2178,46 @@ __global__ __launch_bounds__(256, 2) void group_eig_kernel(const double *__restr
         // leaves every register bit as it is) -- a branch around the update would make the compiler keep two copies
         // of the matrix block.
         const bool refl = sigma != 0.0;
-        double mu, v0r, bpr;
-        if (diag_stage == 13) { mu = alpha + sigma; v0r = alpha - mu; bpr = sigma * 0.5; } // timing diagnostics (wrong results)
-        else if (diag_stage == 11) {
-            mu = sqrt(alpha * alpha + sigma);
-            v0r = (alpha <= 0.0) ? alpha - mu : -sigma * fast_rcp(alpha + mu);
-            bpr = 2.0 * fast_rcp(sigma + v0r * v0r);
-        } else {
-            mu = sqrt(alpha * alpha + sigma);
-            v0r = (alpha <= 0.0) ? alpha - mu : -sigma / (alpha + mu);
-            bpr = 2.0 / (sigma + v0r * v0r);
-        }
-        const double v0 = refl ? v0r : 0.0;
-        const double bp = refl ? bpr : 0.0; // H = I - bp u u^T, u = (v0, x[o+1..])
-        CK(2)
-        if (tid == 0) { beta[k] = bp; off[k] = refl ? mu : alpha; V0[k] = v0; }
-#pragma unroll
-        for (int r = 0; r < NR; r++) {
-            const int row = lane + 64 * r;
-            u[r] = (row == o) ? v0 : x[r];
-            if (!DPPF) U[row] = u[r]; // every wave writes the same values
-        }
-        if (DPPF) {
-#pragma unroll
-            for (int g = 0; g < NG; g++)
-                if (NC * wv + 16 * g + (lane & 15) == o) uc[g] = v0;
-            dpp_fence(uc);
-        }
-        __builtin_amdgcn_wave_barrier();
         const bool live = NC * wv + NC > o && diag_stage != 10; // this wave still owns unfinished columns
-        { // partial p = B u over the wave's columns
-            double s[NR];
+        // The reflector's scalar chain (sqrt, division -> v0; division -> bp) stands in front of as little as possible: v0 is
+        // needed before barrier (b) only by the wave that owns column k + 1 (the one slot of u that is not a published value),
+        // bp by nobody.  So the other waves run their matrix-vector FMAs first and bp follows the Pp stores.  The FMA order
+        // inside a wave (jj ascending) is as it was.
+        const bool owner = DPPF && o / NC == wv; // uniform
+        double s[NR]; // partial p = B u over the wave's columns
 #pragma unroll
-            for (int r = 0; r < NR; r++) s[r] = 0.0;
-            if (DPPF) {
-                if (live) EigCols<0, NR, NC, R0>::matvec(s, a, uc);
-            } else if (live) {
+        for (int r = 0; r < NR; r++) s[r] = 0.0;
+        if (DPPF && live && !owner) {
+            dpp_fence(uc);
+            EigCols<0, NR, NC, R0>::matvec(s, a, uc);
+        }
+        // v0 before barrier (b): the owner (for its slot of uc) and role 0 (thread 0 stores it); bp: role 0 alone.  Everybody
+        // takes both from V0[k] / beta[k] behind the barrier: the values thread 0 computed, which are the ones every wave
+        // used to compute for itself.
+        double mu = 0.0, v0r = 0.0;
+        if (owner || wv == 0 || !DPPF) {
+            if (diag_stage == 13) { mu = alpha + sigma; v0r = alpha - mu; } // timing diagnostics (wrong results)
+            else {
+                mu = sqrt(alpha * alpha + sigma);
+                if (diag_stage == 11) v0r = (alpha <= 0.0) ? alpha - mu : -sigma * fast_rcp(alpha + mu); // timing diagnostics
+                else v0r = (alpha <= 0.0) ? alpha - mu : -sigma / (alpha + mu);
+            }
+        }
+        CK(2)
+        if (DPPF) {
+            if (live && owner) {
+                const double v0o = refl ? v0r : 0.0;
+#pragma unroll
+                for (int g = 0; g < NG; g++)
+                    if (NC * wv + 16 * g + (lane & 15) == o) uc[g] = v0o;
+                dpp_fence(uc);
+                EigCols<0, NR, NC, R0>::matvec(s, a, uc);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < NR; r++) U[lane + 64 * r] = (lane + 64 * r == o) ? (refl ? v0r : 0.0) : x[r]; // every wave writes the same values
+            __builtin_amdgcn_wave_barrier();
+            if (live) {
 #pragma unroll
                 for (int jj = 0; jj < NC; jj++) {
                     if (jj % 8 == 0) asm volatile("" ::: "memory"); // at most 8 broadcast reads in flight (registers)
@@ -2195,12 +2226,22 @@ __global__ __launch_bounds__(256, 2) void group_eig_kernel(const double *__restr
                     for (int r = R0; r < NR; r++) s[r] = fma(a[r][jj], uj, s[r]);
                 }
             }
+        }
 #pragma unroll
-            for (int r = 0; r < NR; r++) Pp[wv][lane + 64 * r] = s[r];
+        for (int r = 0; r < NR; r++) Pp[wv][lane + 64 * r] = s[r];
+        if (wv == 0) {
+            double bpr;
+            if (diag_stage == 13) bpr = sigma * 0.5;
+            else if (diag_stage == 11) bpr = 2.0 * fast_rcp(sigma + v0r * v0r);
+            else bpr = 2.0 / (sigma + v0r * v0r);
+            if (tid == 0) { beta[k] = refl ? bpr : 0.0; off[k] = refl ? mu : alpha; V0[k] = refl ? v0r : 0.0; }
         }
         CK(3)
         __syncthreads(); // (b)
         CK(4)
+        const double bp = beta[k], v0 = V0[k]; // H = I - bp u u^T, u = (v0, x[o+1..])
+#pragma unroll
+        for (int r = 0; r < NR; r++) u[r] = (lane + 64 * r == o) ? v0 : x[r];
         double w[NR];
         part = 0.0;
 #pragma unroll
@@ -2219,14 +2260,19 @@ __global__ __launch_bounds__(256, 2) void group_eig_kernel(const double *__restr
         __builtin_amdgcn_wave_barrier();
         CK(5)
         if (DPPF) {
-            if (diag_stage != 10) {
+            // a wave whose columns are all finished has u_j = w_j = 0 in every slot: it leaves the update out, and its SIMD's
+            // issue slots go to the other matrix's wave (the zero products could only turn a -0.0 of a finished column into
+            // +0.0; the recorded bits of tests/golden/eig_bits.npz do not move)
+            if (live) {
 #pragma unroll
                 for (int g = 0; g < NG; g++) {
                     const int col = NC * wv + 16 * g + (lane & 15);
                     wc[g] = W[col < DP ? col : 0];
                 }
                 dpp_fence(wc);
+                __builtin_amdgcn_s_setprio(0); // the bulk of a step yields its SIMD to the other matrix's dependent chains
                 EigCols<0, NR, NC, R0>::rank2(a, uc, wc, u, w);
+                __builtin_amdgcn_s_setprio(2);
             }
         } else if (diag_stage != 10) { // rank-2 update; waves whose columns are all finished run it too (u = w = 0 there: nothing changes)
 #pragma unroll
@@ -2904,9 +2950,11 @@ bool k_group_eig(cge_ctx *c, const double *cov, i64 n_tasks, i64 d, double *vec)
     static const int diag_stage = getenv("CGE_EIG_DIAG") ? atoi(getenv("CGE_EIG_DIAG")) : 0; // timing diagnostics: 0 = normal
     const dim3 grid((unsigned)n_tasks), block(256);
     // blocked columns, reflectors in place, the column values of the two O(d^2) loops as DPP broadcasts of the FMAs
-    if (d <= 32) hipLaunchKernelGGL((group_eig_kernel<1, 8, true>), grid, block, 0, c->stream, cov, (int)d, vec, diag_stage);
-    else if (d <= 64) hipLaunchKernelGGL((group_eig_kernel<1, 16, true>), grid, block, 0, c->stream, cov, (int)d, vec, diag_stage);
-    else hipLaunchKernelGGL((group_eig_kernel<2, 32, true>), grid, block, 0, c->stream, cov, (int)d, vec, diag_stage);
+    // the waves' roles follow their SIMDs (testing knob test_eig_roles: a fixed permutation instead; the same bits)
+    const int roles = c->opt_test_eig_roles;
+    if (d <= 32) hipLaunchKernelGGL((group_eig_kernel<1, 8, true>), grid, block, 0, c->stream, cov, (int)d, vec, diag_stage, roles);
+    else if (d <= 64) hipLaunchKernelGGL((group_eig_kernel<1, 16, true>), grid, block, 0, c->stream, cov, (int)d, vec, diag_stage, roles);
+    else hipLaunchKernelGGL((group_eig_kernel<2, 32, true>), grid, block, 0, c->stream, cov, (int)d, vec, diag_stage, roles);
     return true;
 }
 

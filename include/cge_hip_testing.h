@@ -276,7 +276,10 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *   "louvain_wave_len"            l: levels >= 2 of cge_louvain_levels decide the vertices whose adjacency segment is longer than
  *                                 l by one wave each (-2: the default length, -1: every vertex, 2^31 - 1: none, the lane form alone);
  *   "test_rss2_one_kernel"        1: rss2 by the one-kernel walk (rss2_walk_kernel) at every width, d <= 128 included, where the
- *                                 chain + merge form runs otherwise: the two forms give the same bits.                           */
+ *                                 chain + merge form runs otherwise: the two forms give the same bits;
+ *   "test_eig_roles"              v: which wave of a workgroup of the batched eigen-solver (d <= 128) owns which column block and runs
+ *                                 the tridiagonal tail: 0 (default) chosen by the waves' SIMDs, 1 the wave's number, 2 reversed,
+ *                                 3 rotated by one: every choice gives the same bits.                                            */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
 /* needs the GPU: the resident row-major fp64 matrix as this rank holds it (all n rows; under shard_rows its own rows, in
  * local order, with their global 0-based ids in ids_out, which may be NULL otherwise).  *rows and *d are set first; a capacity
