@@ -256,6 +256,31 @@ def wedge_geometry_test(N, weighted, n_chunks):
     return {"rshift": rs.value, "colbits": cb.value, "ntile": nt.value, "lds_pass1": l1.value, "lds_pass2": l2.value}
 
 
+def fit_dir_geometry_test(N, cus):
+    """Host-only hook (include/cge_hip_testing.h: cge_fit_dir_geometry_test): the geometry of the directed persistent fit for N
+    vertices on `cus` CUs.  None where the form declines, else (G, NW, NSB)."""
+    L = load_library()
+    ap, G, NW, NSB = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = L.cge_fit_dir_geometry_test(C.c_int64(N), C.c_int(cus), C.byref(ap), C.byref(G), C.byref(NW), C.byref(NSB))
+    if rc:
+        raise CGEError(rc, "cge_fit_dir_geometry_test")
+    return (G.value, NW.value, NSB.value) if ap.value else None
+
+
+def batch_pack_dir_test(N, cus):
+    """Host-only hook (cge_batch_pack_dir_test): the launch groups of a directed batch whose members have N[k] landmarks on
+    `cus` CUs.  Returns (number of groups, group_of) with group_of[k] = -1 for a member that is scored on its own."""
+    L = load_library()
+    N = np.ascontiguousarray(N, dtype=np.int64)
+    out = np.full(len(N), -2, np.int32)
+    L.cge_batch_pack_dir_test.restype = C.c_int
+    L.cge_batch_pack_dir_test.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    n = L.cge_batch_pack_dir_test(N.ctypes.data, len(N), int(cus), out.ctypes.data)
+    if n < 0:
+        raise CGEError(n, "cge_batch_pack_dir_test")
+    return n, out
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -1018,7 +1043,8 @@ class Context:
     def fit_test(self, problems, directed=False, form=0, eps=None, delta=0.001, want_GD=False):
         """Testing hook (include/cge_hip_testing.h: cge_fit_test): one Chung-Lu fit per problem from a chosen start by a named
         form of the sweep (0 = what an exact-mode sweep of the shape picks).  A problem is a dict: D (N, N), alpha, w, T0
-        (undirected) or D, alpha, w = deg_in, w2 = deg_out, T0 = Tin, T0b = Tout (directed); several problems are form 5 only.
+        (undirected) or D, alpha, w = deg_in, w2 = deg_out, T0 = Tin, T0b = Tout (directed); several problems are form 5
+        (undirected) or form 6 (directed) only.
         eps defaults to the sweep's (0.25 undirected, 0.9 directed).  Returns (form_ran, [dict(T, Tb, GD, iters, status)]): Tb
         and GD are None where they do not apply / were not asked for."""
         if isinstance(problems, dict):

@@ -5,6 +5,8 @@
 // keeps what host_wgcl_sweep keeps: its T rotating through three vectors and its alpha bookkeeping (AlphaBook: the patience
 // counters of src/divergence.jl:215-223, :242-253, the partial sums added in block order).  So a member's iterates, iteration
 // counts and scores are those of its own cge_score.
+// A group of DIRECTED members (hand_off_directed) shares the fit alone: fit_flow_dir_multi_kernel between the members' own
+// power-matrix launches and their own tallies / vect_B / JS launches, without look-ahead (host_batch_sweep_dir).
 #include <algorithm>
 #include <cstring>
 
@@ -14,10 +16,97 @@ bool batch_group_closes(int g_sum, int g_nw, int g_size, int G, int NW, int cus)
     return g_size > 0 && (g_sum + G > cus || NW != g_nw || g_size >= CGE_BATCH_MAX);
 }
 
+// A directed group (members handed over by hand_off_directed).  An alpha: (1) every live member's power matrix into its own GD,
+// (2) ONE fit_flow_dir_multi_kernel launch for all of them, (3) per member the launches its own enqueue_alpha makes behind the
+// fit -- the local score's tallies, k_bvec in the form its sweep picked, k_js -- on the context's scratch, one member after the
+// other on the one stream, (4) one copy of the members' scalars to the pinned slot and an event.  Tin / Tout are updated in
+// place, so -- host_wgcl_sweep's own rule for directed sweeps -- the next alpha is not enqueued before this one's verdicts.
+static void host_batch_sweep_dir(cge_ctx *c, std::vector<BatchMember *> &group) {
+    const i64 n_alpha = AlphaBook::n_alpha;
+    const int K = (int)group.size();
+    hipStream_t st = c->stream;
+    const int NW = group[0]->h.NW;
+    c->batch_scal.ensure((size_t)K * RES_STRIDE);
+    c->batch_pin.ensure((size_t)2 * K * RES_STRIDE);
+    double *scal = c->batch_scal.p;
+    std::vector<AlphaBook> book;
+    std::vector<char> done(K, 0);
+    for (int j = 0; j < K; j++) {
+        const SweepHandoff &h = group[j]->h;
+        book.emplace_back(h.S, h.split, group[j]->trace);
+        c->sw_rowbins.ensure((size_t)h.N * h.C); // the scratch stage 3 lends every member
+        c->sw_vectB.ensure((size_t)h.C * h.C);
+    }
+    for (i64 ia = 1; ia <= n_alpha; ia++) {
+        std::vector<int> A;
+        for (int j = 0; j < K; j++)
+            if (!done[j] && !group[j]->redo) A.push_back(j);
+        if (A.empty()) break;
+        const double alpha = AlphaBook::AlphaStep * (double)ia;
+        cge_flow_dir_multi tab{};
+        tab.n = (int)A.size();
+        for (int i = 0; i < (int)A.size(); i++) {
+            SweepHandoff &h = group[A[i]]->h;
+            k_pow_matrix_from(c, h.D.p, h.logs ? h.Lh.p : nullptr, h.logs ? h.Ll.p : nullptr, h.N, alpha, h.GD.p, false);
+            cge_flow_dir_problem &q = tab.p[i];
+            q.GD = h.GD.p;
+            q.Tin = h.Tio.p; q.Tout = h.Tio.p + h.N;
+            q.deg_in = h.deg.p; q.deg_out = h.deg.p + h.N;
+            q.flags = reinterpret_cast<int *>(scal + (i64)A[i] * RES_STRIDE + RES_FIT);
+            q.N = h.N; q.Tld = h.Tld; q.Nt = (int)((h.N + 63) / 64); q.G = h.G;
+        }
+        k_fit_flow_dir_multi(c, tab, NW, 0.9, 1.0, AlphaBook::delta, c->batch_flow); // epsilon, diff (:434-435)
+        c->stat_fit_batched_launches++;
+        for (int j : A) {
+            SweepHandoff &h = group[j]->h;
+            double *sj = scal + (i64)j * RES_STRIDE;
+            const double *Ta = h.Tio.p + h.N, *Tb = h.Tio.p; // (Tout, Tin), as enqueue_alpha names them
+            const DevSamples &ds = *h.dsets[h.n_sets == 1 ? 0 : ia - 1];
+            if (!book[j].skip_auc)
+                k_auc_landmark(c, Ta, Tb, h.v2l.p, c->vw.p, h.lweight.p, ds.pi.p, ds.pj.p, ds.ni.p, ds.nj.p, ds.dpos.p, ds.dneg.p,
+                               ds.wts.p, h.S, alpha, nullptr, sj + RES_AUC);
+            if (!book[j].skip_div) {
+                double *vB = c->sw_vectB.p;
+                k_bvec(c, h.GD.p, Ta, Tb, h.cm_pos.p, h.cm_off.p, h.cm_mem.p, h.N, h.C, 1, c->sw_rowbins.p, vB, h.bvec_form);
+                if (!h.split)
+                    k_js(c, h.vectC.p, vB, h.C * h.C, h.C, 1, 0, nullptr, sj + RES_JS);
+                else {
+                    k_js(c, h.vectC.p, vB, h.C * h.C, h.C, 1, 1, nullptr, sj + RES_JS);
+                    k_js(c, h.vectC.p, vB, h.C * h.C, h.C, 1, 2, nullptr, sj + RES_JS + CGE_PARTIAL_BLOCKS);
+                }
+            }
+        }
+        const int slot = (int)(ia & 1);
+        HIP_CHECK(hipMemcpyAsync(c->batch_pin.p + (i64)slot * K * RES_STRIDE, scal, sizeof(double) * K * RES_STRIDE,
+                                 hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipEventRecord(c->sweep_ev[slot], st));
+        HIP_CHECK(hipEventSynchronize(c->sweep_ev[slot]));
+        for (int j : A) {
+            BatchMember &mb = *group[j];
+            const double *res = c->batch_pin.p + (i64)slot * K * RES_STRIDE + (i64)j * RES_STRIDE;
+            const int *hf = reinterpret_cast<const int *>(res + RES_FIT);
+            if (hf[2] || !hf[0]) { // abandoned (Tin / Tout untouched): the member is scored again on its own
+                note_fit_fallback(c);
+                mb.redo = true;
+                continue;
+            }
+            c->stat_fit_batched_alphas++;
+            book[j].take(res, alpha, hf[1]);
+            if (book[j].ended() || ia == n_alpha) {
+                done[j] = 1;
+                book[j].write(mb.out, mb.out_len);
+            }
+        }
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (c->stat_fit_batched_alphas > 0 && !c->fit_persistent_broken) c->fit_fallback_streak = 0; // clean persistent sweeps
+}
+
 void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
     const i64 n_alpha = AlphaBook::n_alpha;
     const int K = (int)group.size();
     if (K < 1) return;
+    if (group[0]->h.directed) return host_batch_sweep_dir(c, group);
     hipStream_t st = c->stream;
     const int NW = group[0]->h.NW;
     i64 vtot = 0;
@@ -161,9 +250,12 @@ static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embe
     int dev = 0, cus = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    // the members that can take the batched sweep (undirected landmark mode, the fused fit); the sweep decides the rest
+    // the members that can take the batched sweep (landmark mode; undirected: the fused fit, directed: the persistent fit of >= 256
+    // landmarks); the sweep decides the rest
     // (one member, or a member whose fit takes more than half the chip, shares nothing: it is scored as cge_score scores it)
-    const bool batchable = K >= 2 && a->land != -1 && !a->directed && c->opt_fit_fused && c->opt_fit_persistent != 1;
+    // (directed members: the shared directed fit, which has no fused chain -- option fit_fused does not apply to them)
+    const bool batchable = K >= 2 && a->land != -1 && c->opt_fit_persistent != 1 &&
+                           (a->directed ? !c->fit_persistent_broken : c->opt_fit_fused != 0);
     c->stat_fit_batched_launches = c->stat_fit_batched_alphas = 0;
     c->smp.reset();
     bool have_samples = false;

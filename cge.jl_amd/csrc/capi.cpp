@@ -468,6 +468,24 @@ int cge_batch_pack_test(const int64_t *N, int64_t K, int cus, int32_t *group_of)
     }
     return groups;
 }
+// host-only hooks (include/cge_hip_testing.h): the directed persistent fit's geometry, and the launch groups of a directed batch
+int cge_fit_dir_geometry_test(int64_t N, int cus, int *applies, int *G, int *NW, int *NSB) {
+    if (!applies || !G || !NW || !NSB) return CGE_E_ARG;
+    *applies = k_fit_dir_geometry_cus(N, cus, G, NW, NSB) ? 1 : 0;
+    return CGE_OK;
+}
+int cge_batch_pack_dir_test(const int64_t *N, int64_t K, int cus, int32_t *group_of) {
+    if (!N || !group_of || K < 0 || cus <= 0) return CGE_E_ARG;
+    int groups = 0, g_sum = 0, g_nw = 0, g_size = 0;
+    for (i64 k = 0; k < K; k++) {
+        int G = 0, NW = 0;
+        if (!batch_dir_member_geometry(N[k], cus, &G, &NW)) { group_of[k] = -1; continue; } // (sequential)
+        if (g_size == 0 || batch_group_closes(g_sum, g_nw, g_size, G, NW, cus)) { groups++; g_sum = 0; g_size = 0; }
+        g_sum += G; g_nw = NW; g_size++;
+        group_of[k] = groups - 1;
+    }
+    return groups;
+}
 int cge_host_pos_draw(int64_t seed, int64_t stream_id, int64_t S, int64_t m, int64_t *pos_idx) {
     if (!pos_idx || S <= 0 || m <= 0) return CGE_E_ARG;
     host_pos_draw(seed, stream_id, S, m, pos_idx);
@@ -569,7 +587,7 @@ int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_pro
 // testing hook (include/cge_hip_testing.h): one Chung-Lu fit from a caller's start by one named form of the sweep
 int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int directed, int form, double eps, double delta, int *form_ran) {
     cge_ctx *c = (cge_ctx *)ctx;
-    if (!c || !problems || !form_ran || form < 0 || form > 5 || n_problems < 1) return CGE_E_ARG;
+    if (!c || !problems || !form_ran || form < 0 || form > 6 || n_problems < 1) return CGE_E_ARG;
     CGE_TRY_ON_DEVICE(c)
     host_fit_test(c, problems, n_problems, directed != 0, form, eps, delta, form_ran);
     CGE_CATCH(c)

@@ -880,6 +880,8 @@ void k_gather_means_slots(cge_ctx *c, const double *arena, const i64 *off, const
                           double *dst);
 void k_pow_prepare(cge_ctx *c, const double *D, i64 N, bool upper_only, bool blocked = false);
 void k_pow_matrix(cge_ctx *c, const double *D, i64 N, double alpha, double *GD, bool upper_only = false);
+void k_pow_matrix_from(cge_ctx *c, const double *D, const double *Lh, const float *Ll, i64 N, double alpha, double *GD,
+                       bool upper_only = false); // the same kernels on a caller's logarithm (Lh == nullptr: the library pow on D)
 void k_pow_test(cge_ctx *c, const double *x, i64 n, double alpha, int method, double *out);
 // What rides on the launch of the undirected persistent fit in a landmark-mode sweep relabelled by community (round 5): the
 // power matrix computed in the prologue from the stored logarithm, vect_B's tile partials and the local score's tallies in the
@@ -929,6 +931,26 @@ struct cge_flow_multi { cge_flow_problem p[CGE_BATCH_MAX]; int n, pad; }; // pas
 // and wg0 are filled in here.  The problems share NW; the sum of their G must not exceed the CU count (the caller packs them).
 void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, double delta, DevBuf<double> &flow);
 bool k_fit_flow_multi_fits(int NW); // the multi-problem kernel of NW waves gets a workgroup on a CU
+// The same for directed graphs.  One problem of fit_flow_dir_multi_kernel: the arguments of its fit_flow_dir_kernel<NW, 1> launch
+// (Tin / Tout: N doubles each, updated in place on success only), its grid size G and its first workgroup wg0.
+struct cge_flow_dir_problem {
+    const double *GD, *T0; double *Tin, *Tout; const double *deg_in, *deg_out;
+    double *ring, *P, *fq; unsigned *sync; int *flags;
+    i64 N, Tld; int Nt, G, wg0, pad;
+};
+struct cge_flow_dir_multi { cge_flow_dir_problem p[CGE_BATCH_MAX]; int n, pad; }; // passed by value (kernel arguments)
+// the geometry fit_flow_dir_kernel uses for N on `cus` CUs / on this device (false: the persistent form does not apply); NSB =
+// quarter blocks a workgroup may have to reduce.  k_fit_persistent_dir and the shared launch both take it from here.
+bool k_fit_dir_geometry_cus(i64 N, int cus, int *G, int *NW, int *NSB);
+bool k_fit_dir_geometry(i64 N, int *G, int *NW, int *NSB);
+i64 k_fit_flow_dir_slot_doubles(i64 N, i64 Tld); // 32 sync words + 8 Tld ring + 12 Nt f + 4 Nt^2 64 P
+// lay the problems' slots and T_0 stages out in `flow`, arm every slot with one fill, stage T_0 = (Tin, Tout) zero-padded to
+// Tld and launch (timer "fit_batched"); ring / P / fq / sync / T0 and wg0 are filled in here.  CGE_E_ASSERT for more than
+// CGE_BATCH_MAX problems or a sum of G above the CU count.  eps0, f0, delta are common to the launch.
+void k_fit_flow_dir_multi(cge_ctx *c, cge_flow_dir_multi &tab, int NW, double eps0, double f0, double delta, DevBuf<double> &flow);
+bool k_fit_flow_dir_multi_fits(int NW); // fit_flow_dir_multi_kernel of NW waves gets a workgroup on a CU
+// whether cge_score_batch shares the fit of a directed member of N landmarks (>= 256, NSB = 1, G <= cus / 2), and its geometry
+bool batch_dir_member_geometry(i64 N, int cus, int *G, int *NW);
 struct cge_bins_problem { const double *partial; const i32 *cm_off, *fc, *ns, *base; i64 C; int Nt, pad; double *vectB; };
 struct cge_js_problem { const double *vC, *vB; i64 len, C; int mode, pad; double *part, *fpart; };
 struct cge_bins_multi { cge_bins_problem p[CGE_BATCH_MAX]; };
@@ -1072,6 +1094,14 @@ struct SweepHandoff {
     std::vector<std::unique_ptr<DevSamples>> dsets;
     std::vector<cge_fit_fused> h_epi;
     const double *w = nullptr; // the fit's targets (inside `vw`)
+    // A directed member (landmark mode, >= 256 landmarks; its fit shares fit_flow_dir_multi_kernel's launch): the normalised D
+    // and, under pow_exp2, its row-major logarithm (Lh / Ll above; `logs`), a power matrix of its own, Tin / Tout (Tio: N each)
+    // and the in- / out-degrees (deg: N each), the community tables, and the landmark state the local score reads (v2l, lweight).
+    // bvec_form: the form of k_bvec its own sweep picks (the context's layout flags are the next member's by then).
+    bool directed = false, logs = false;
+    int bvec_form = 0;
+    DevBuf<double> D, GD, Tio, deg, lweight;
+    DevBuf<i32> cm_mem, cm_pos, v2l;
 };
 // The alpha bookkeeping of one sweep, the reference's (src/divergence.jl:35-38, :213-223, :242-253, :256): the patience counters,
 // the skip flags and the best values.  host_wgcl_sweep keeps one, host_batch_sweep one per member (wgcl_host.cpp).
@@ -1118,7 +1148,8 @@ struct BatchMember {
     cge_trace *trace = nullptr;
     bool redo = false;
 };
-// the alpha sweeps of one launch group in lock-step (sum of G <= CUs, one NW, at most CGE_BATCH_MAX members)
+// the alpha sweeps of one launch group in lock-step (sum of G <= CUs, one NW, at most CGE_BATCH_MAX members; all members
+// undirected or all directed)
 void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group);
 int score_batch_run(cge_ctx *c, const cge_score_args *a, const cge_embedding_view *views, i64 K, const char *who, double *out,
                     int *out_len, cge_trace *traces);

@@ -139,19 +139,24 @@ void k_pow_prepare(cge_ctx *c, const double *D, i64 N, bool upper_only, bool blo
     c->pow_logs_upper = upper_only;
 }
 void k_pow_matrix(cge_ctx *c, const double *D, i64 N, double alpha, double *GD, bool upper_only) {
-    ScopedKernelTimer t(c, "pow_matrix");
     const bool logs = c->pow_logs_N == N && (upper_only || !c->pow_logs_upper);
+    k_pow_matrix_from(c, D, logs ? c->sw_Lh.p : nullptr, logs ? c->sw_Ll.p : nullptr, N, alpha, GD, upper_only);
+}
+// the same with the row-major logarithm named by the caller (Lh == nullptr: the library pow on D): a member of a directed batch
+// keeps its own D and logarithm while the context's serve the next member's landmark phase
+void k_pow_matrix_from(cge_ctx *c, const double *D, const double *Lh, const float *Ll, i64 N, double alpha, double *GD, bool upper_only) {
+    ScopedKernelTimer t(c, "pow_matrix");
+    const bool logs = Lh != nullptr;
     const unsigned nt = (unsigned)((N + 63) / 64);
     if (upper_only) {
         if (logs)
-            hipLaunchKernelGGL(exp2_matrix_upper_kernel, dim3(nt, nt), dim3(256), 0, c->stream, c->sw_Lh.p, c->sw_Ll.p, N, alpha, GD);
+            hipLaunchKernelGGL(exp2_matrix_upper_kernel, dim3(nt, nt), dim3(256), 0, c->stream, Lh, Ll, N, alpha, GD);
         else
             hipLaunchKernelGGL(pow_matrix_upper_kernel, dim3(nt, nt), dim3(256), 0, c->stream, D, N, alpha, GD);
         return;
     }
     if (logs)
-        hipLaunchKernelGGL(exp2_matrix_kernel, dim3(grid_for(N * N, 256, 256 * 16)), dim3(256), 0, c->stream, c->sw_Lh.p,
-                           c->sw_Ll.p, N * N, alpha, GD);
+        hipLaunchKernelGGL(exp2_matrix_kernel, dim3(grid_for(N * N, 256, 256 * 16)), dim3(256), 0, c->stream, Lh, Ll, N * N, alpha, GD);
     else
         hipLaunchKernelGGL(pow_matrix_kernel, dim3(grid_for(N * N, 256, 256 * 16)), dim3(256), 0, c->stream, D, N * N,
                            alpha, GD);

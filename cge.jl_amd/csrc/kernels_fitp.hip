@@ -345,258 +345,42 @@ __global__ __launch_bounds__(64 * NW) void fit_flow_dir_kernel(const double *__r
                                                                 double delta, int max_iters, double *ring, double *P,
                                                                 double *fq, unsigned *sync, int *flags,
                                                                 long long timeout_ticks, int test_naps) {
-    __shared__ double red[2][NSB][2][16][17]; // [parity of k][quarter block][Sin / Sout]
-    __shared__ double fred[2][4];
-    __shared__ __attribute__((aligned(16))) double tsh[NW][4][64];          // Tin_I, Tout_I, Tin_J, Tout_J
-    __shared__ __attribute__((aligned(16))) double rsh[NW][2][8][FLOW_RLD]; // one pass: a row and a column reduction
-    __shared__ int lds_exit;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wg = blockIdx.x, G = gridDim.x;
-    const int rq = lane >> 3, cq = lane & 7;
-    const int NT = Nt * (Nt + 1) / 2;
-    const i64 Pstride = (i64)Nt * Nt * 64, Psz = 2 * Pstride;
-    unsigned *fail = sync + 1, *done = sync + 2;
-    long long deadline = wall_clock64() + timeout_ticks; // re-armed at every iteration: it bounds one hand-off, not the whole fit
+#define FLOW_WG blockIdx.x
+#define FLOW_G gridDim.x
+#include "fit_flow_dir_body.inc"
+#undef FLOW_WG
+#undef FLOW_G
+}
 
-    double g[8][8];
-    int tI = -1, tJ = -1;
-    if (test_naps > 0 && (wg * NW + wave) < NT) // testing (option fit_persistent_test_delay): the tile waves start late
-        for (int q = 0; q < test_naps; q++) __builtin_amdgcn_s_sleep(127);
-    {
-        const int t = wg * NW + wave;
-        if (t < NT) {
-            int I = 0, rem = t;
-            while (rem >= Nt - I) { rem -= Nt - I; I++; }
-            tI = I;
-            tJ = I + rem;
-        }
-#pragma unroll
-        for (int a = 0; a < 8; a++) {
-            const i64 row = (i64)64 * tI + 8 * rq + a;
-#pragma unroll
-            for (int b = 0; b < 8; b++) {
-                const i64 col = (i64)64 * tJ + 8 * cq + b;
-                g[a][b] = (tI >= 0 && row < N && col < N) ? GD[row * N + col] : 0.0;
-            }
-        }
-    }
-    const int r16 = tid & 15, qg = (tid >> 4) & 15;
-    const bool reducer = tid < 256;
-    double tin_cur[NSB], tout_cur[NSB], din[NSB], dout[NSB];
-#pragma unroll
-    for (int i = 0; i < NSB; i++) {
-        const int sb = wg + i * G;
-        const i64 row = (i64)64 * (sb >> 2) + 16 * (sb & 3) + r16;
-        const bool mine = sb < 4 * Nt && tid < 16 && row < N;
-        tin_cur[i] = mine ? T0[row] : 0.0;
-        tout_cur[i] = mine ? T0[Tld + row] : 0.0;
-        din[i] = mine ? deg_in[row] : 0.0;
-        dout[i] = mine ? deg_out[row] : 0.0;
-    }
-    if (tid == 0) lds_exit = 0;
-    __syncthreads();
-
-    int k = 0, converged = 0, failed = 0;
-    double eps = eps0, fprev = f0;
-    if (timeout_ticks <= 0) max_iters = 0; // test hook: abandon at once
-    for (;;) {
-        deadline = wall_clock64() + timeout_ticks;
-        if (k >= max_iters) { failed = 1; break; }
-        const double *Tk = (k == 0) ? T0 : ring + (i64)(k & 3) * 2 * Tld; // Tin at Tk, Tout at Tk + Tld
-        double *Pk = P + (i64)(k & 1) * Psz;
-        int bad = 0;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the arming stores of the previous iteration have landed
-        // ---- 1. tile products with T_k ---------------------------------------------------------------------------------
-        if (tI >= 0) {
-            const int I = tI, J = tJ;
-            double v0, v1, v2, v3;
-            unsigned spins = 0;
-            for (;;) {
-                v0 = ld_sc1(Tk + 64 * I + lane);
-                v1 = ld_sc1(Tk + Tld + 64 * I + lane);
-                v2 = ld_sc1(Tk + 64 * J + lane);
-                v3 = ld_sc1(Tk + Tld + 64 * J + lane);
-                if (__all(!armed(v0) && !armed(v1) && !armed(v2) && !armed(v3))) break;
-                bad = flow_check(spins, fail, done, deadline);
-                if (bad) break;
-            }
-            if (!bad) {
-                tsh[wave][0][lane] = v0;
-                tsh[wave][1][lane] = v1;
-                tsh[wave][2][lane] = v2;
-                tsh[wave][3][lane] = v3;
-                __builtin_amdgcn_wave_barrier();
-                const bool diag_tile = I == J;
-                double(*R)[FLOW_RLD] = rsh[wave][0];
-                double(*Cc)[FLOW_RLD] = rsh[wave][1];
-#pragma unroll 1
-                for (int pass = 0; pass < 2; pass++) { // one copy of the code: the two passes share their registers
-                    // FACTORED (as fit_dataflow_dir_kernel): the row's own factor Tin_i / Tout_i is applied by the reducer.
-                    // pass 0: g * Tout -> rows: Sin partial of block I, columns: Sin partial of block J
-                    // pass 1: g * Tin  -> rows: Sout partial of block I, columns: Sout partial of block J
-                    const double *trow = tsh[wave][1 - pass], *tcol = tsh[wave][3 - pass]; // Tout_I, Tout_J / Tin_I, Tin_J
-                    double ta[8], tb[8], pr[8], pc[8];
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        ta[q] = trow[8 * rq + q];
-                        tb[q] = tcol[8 * cq + q];
-                        pr[q] = 0.0;
-                        pc[q] = 0.0;
-                    }
-#pragma unroll
-                    for (int a = 0; a < 8; a++)
-#pragma unroll
-                        for (int b = 0; b < 8; b++) {
-                            double gv = g[a][b];
-                            if (diag_tile && rq == cq && a == b) gv += gv; // the j == i term counts twice
-                            pr[a] = fma(gv, tb[b], pr[a]);
-                            pc[b] = fma(gv, ta[a], pc[b]);
-                        }
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        R[cq][8 * rq + q] = pr[q];
-                        Cc[rq][8 * cq + q] = pc[q];
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    double u[8], v[8];
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        u[q] = R[q][lane];
-                        v[q] = Cc[q][lane];
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    const double rsum = ((u[0] + u[4]) + (u[2] + u[6])) + ((u[1] + u[5]) + (u[3] + u[7]));
-                    // pass 0 -> the Sin plane (0), pass 1 -> the Sout plane (1): rows for block I, columns for block J
-                    st_sc1(Pk + (i64)pass * Pstride + ((i64)I * Nt + J) * 64 + lane, rsum);
-                    if (!diag_tile) {
-                        const double csum = ((v[0] + v[4]) + (v[2] + v[6])) + ((v[1] + v[5]) + (v[3] + v[7]));
-                        st_sc1(Pk + (i64)pass * Pstride + ((i64)J * Nt + I) * 64 + lane, csum);
-                    }
-                }
-            }
-        }
-        // ---- 2. the quarter blocks this workgroup reduces -----------------------------------------------------------------
-        bool stop = false;
-#pragma unroll
-        for (int i = 0; i < NSB; i++) {
-            const int sb = wg + i * G;
-            if (sb >= 4 * Nt) break; // uniform
-            const int b = sb >> 2, rib = 16 * (sb & 3) + r16;
-            const bool fcheck = k > 0 && i == 0;
-            double pi[4] = {0.0, 0.0, 0.0, 0.0}, po[4] = {0.0, 0.0, 0.0, 0.0}, fv = 0.0, fx[2] = {0.0, 0.0};
-            const double *fp = fq + (i64)((k + 2) % 3) * 4 * Nt; // f of iteration k-1
-            if (!bad && fcheck && reducer) {
-#pragma unroll
-                for (int u = 0; u < 2; u++)
-                    if (tid + 256 * u < 4 * Nt) fx[u] = ld_sc1(fp + tid + 256 * u);
-            }
-            if (!bad && reducer) {
-                unsigned spins = 0;
-                for (;;) {
-                    bool ok = true;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int q = qg + 16 * u;
-                        if (q < Nt) {
-                            pi[u] = ld_sc1(Pk + ((i64)b * Nt + q) * 64 + rib);
-                            po[u] = ld_sc1(Pk + Pstride + ((i64)b * Nt + q) * 64 + rib);
-                            ok = ok && !armed(pi[u]) && !armed(po[u]);
-                        }
-                    }
-                    if (__all(ok)) break;
-                    bad = flow_check(spins, fail, done, deadline);
-                    if (bad) break;
-                }
-            }
-            if (!bad && fcheck && reducer) {
-                unsigned spins = 0;
-                for (;;) {
-                    if (__all(!armed(fx[0]) && !armed(fx[1]))) break;
-                    bad = flow_check(spins, fail, done, deadline);
-                    if (bad) break;
-#pragma unroll
-                    for (int u = 0; u < 2; u++)
-                        if (tid + 256 * u < 4 * Nt) fx[u] = ld_sc1(fp + tid + 256 * u);
-                }
-                fv = fmax(fx[0], fx[1]);
-            }
-            if (bad && lane == 0) atomicOr(&lds_exit, bad);
-            if (reducer) {
-                if (fcheck) {
-                    fv = wave_max(fv);
-                    if (lane == 0) fred[k & 1][wave] = fv;
-                }
-                red[k & 1][i][0][qg][r16] = ((pi[0] + pi[1]) + pi[2]) + pi[3];
-                red[k & 1][i][1][qg][r16] = ((po[0] + po[1]) + po[2]) + po[3];
-            }
-            __syncthreads();
-            const int ex = lds_exit;
-            if (ex) { failed = (ex & 2) != 0; converged = !failed; stop = true; break; } // uniform
-            if (fcheck) { // the step-size rule replayed from the same f history by every workgroup, then `while diff > delta`
-                const double f = fmax(fmax(fred[k & 1][0], fred[k & 1][1]), fmax(fred[k & 1][2], fred[k & 1][3]));
-                if (f > fprev) eps *= 0.99;
-                fprev = f;
-                if (!(f > delta)) { converged = 1; stop = true; break; }
-            }
-            if (tid < 16) {
-                double Si = red[k & 1][i][0][0][r16], So = red[k & 1][i][1][0][r16];
-#pragma unroll
-                for (int u = 1; u < 16; u++) { Si += red[k & 1][i][0][u][r16]; So += red[k & 1][i][1][u][r16]; }
-                Si *= tin_cur[i]; // the row's own factor (the tiles summed g * Tout / g * Tin)
-                So *= tout_cur[i];
-                const i64 row = (i64)64 * b + rib;
-                double fr = 0.0, nin = 0.0, nout = 0.0;
-                if (row < N) {
-                    nin = tin_cur[i];
-                    nout = tout_cur[i];
-                    if (din[i] > 0) { nin = tin_cur[i] + (eps * tin_cur[i]) * (din[i] / Si - 1.0); fr = fmax(fr, fabs(din[i] - Si)); }
-                    if (dout[i] > 0) { nout = tout_cur[i] + (eps * tout_cur[i]) * (dout[i] / So - 1.0); fr = fmax(fr, fabs(dout[i] - So)); }
-                }
-                double *Tn = ring + (i64)((k + 1) & 3) * 2 * Tld, *Ta = ring + (i64)((k + 3) & 3) * 2 * Tld;
-                st_sc1(Tn + row, nin);
-                st_sc1(Tn + Tld + row, nout);
-                tin_cur[i] = nin;
-                tout_cur[i] = nout;
-                fr = row16_max(fr);
-                if (r16 == 0) st_sc1(fq + (i64)(k % 3) * 4 * Nt + sb, fr);
-                st_sc1(Ta + row, sentinel());
-                st_sc1(Ta + Tld + row, sentinel());
-                if (r16 == 0) st_sc1(fq + (i64)((k + 1) % 3) * 4 * Nt + sb, sentinel());
-            }
-            if (reducer) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int q = qg + 16 * u;
-                    if (q < Nt) {
-                        st_sc1(Pk + ((i64)b * Nt + q) * 64 + rib, sentinel());
-                        st_sc1(Pk + Pstride + ((i64)b * Nt + q) * 64 + rib, sentinel());
-                    }
-                }
-            }
-        }
-        if (wg >= 4 * Nt && bad) break;
-        if (stop) {
-            if (converged && tid == 0) __hip_atomic_store(done, 1u, RLX_AGENT);
-            break;
-        }
-        k++;
-    }
-    if (converged && tid < 16) {
-#pragma unroll
-        for (int i = 0; i < NSB; i++) {
-            const int sb = wg + i * G;
-            const i64 row = (i64)64 * (sb >> 2) + 16 * (sb & 3) + r16;
-            if (sb < 4 * Nt && row < N) {
-                Tin_out[row] = tin_cur[i];
-                Tout_out[row] = tout_cur[i];
-            }
-        }
-    }
-    if (wg == 0 && tid == 0) {
-        flags[0] = converged;
-        flags[1] = k;
-        flags[2] = failed || !converged;
-        flags[3] = 0;
-    }
+// ---- several directed fits in one launch (cge_score_batch on a directed graph) -------------------------------------------------
+// As fit_flow_multi_kernel: the grid is the concatenation of the problems' grids, workgroup x belongs to problem p, the last whose
+// wg0 is <= x, and is its workgroup x - wg0.  Every problem keeps the geometry (G, NW) and the arithmetic of its own
+// fit_flow_dir_kernel<NW, 1> launch and has hand-off slots, start vectors and flags of its own, so its iterates, its iteration
+// count and "written on success only" are those of that launch.  The host keeps the sum of the G within the CU count (one
+// workgroup per CU): every workgroup of every problem is resident, no problem waits for another, and every spin is bounded by
+// the per-iteration deadline of the body (flow_check).
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void fit_flow_dir_multi_kernel(const cge_flow_dir_multi tab, double eps0, double f0, double delta,
+                                                                      int max_iters, long long timeout_ticks, int test_naps) {
+    constexpr int NSB = 1;
+    int p = 0; // (uniform: the table is a kernel argument)
+    for (int i = 1; i < tab.n; i++)
+        if ((int)blockIdx.x >= tab.p[i].wg0) p = i;
+    const cge_flow_dir_problem &q = tab.p[p];
+    const double *__restrict__ GD = q.GD;
+    const i64 N = q.N, Tld = q.Tld;
+    const int Nt = q.Nt;
+    const double *T0 = q.T0;
+    double *Tin_out = q.Tin, *Tout_out = q.Tout;
+    const double *__restrict__ deg_in = q.deg_in, *__restrict__ deg_out = q.deg_out;
+    double *ring = q.ring, *P = q.P, *fq = q.fq;
+    unsigned *sync = q.sync;
+    int *flags = q.flags;
+#define FLOW_WG ((int)blockIdx.x - q.wg0)
+#define FLOW_G q.G
+#include "fit_flow_dir_body.inc"
+#undef FLOW_WG
+#undef FLOW_G
 }
 
 } // namespace
@@ -770,24 +554,107 @@ void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, doubl
     if (e != hipSuccess) CGE_THROW(CGE_E_HIP, "batched fit launch failed: %s", hipGetErrorString(e));
 }
 
+// The geometry of fit_flow_dir_kernel for N vertices on `cus` CUs (no device needed): one tile per wave on NW = 4 waves per
+// workgroup while they cover the triangle, else 8; G workgroups, one per tile group and at least one per quarter block where the
+// CUs allow; NSB = quarter blocks a workgroup may have to reduce (1 when 4 Nt <= G).  False: the form does not apply (more
+// tiles than waves, more than 64 partial vectors per reducer, more than two quarter blocks per workgroup).  k_fit_persistent_dir
+// and the batch's shared launch (k_fit_flow_dir_multi) both take their launch shape from here, so a member of a shared launch
+// runs the geometry of its own launch.
+bool k_fit_dir_geometry_cus(i64 N, int cus, int *G_out, int *NW_out, int *NSB_out) {
+    const int Nt = (int)((N + 63) / 64);
+    const i64 NT = (i64)Nt * (Nt + 1) / 2;
+    if (N <= 0 || cus <= 0 || Nt > 64) return false;
+    const int NW = (NT <= (i64)4 * cus) ? 4 : 8;
+    const int Gf = (int)std::min<i64>(cus, std::max<i64>((NT + NW - 1) / NW, (i64)4 * Nt));
+    if (!(NT <= (i64)NW * Gf && 4 * Nt <= 2 * Gf)) return false;
+    *G_out = Gf; *NW_out = NW; *NSB_out = 4 * Nt <= Gf ? 1 : 2;
+    return true;
+}
+bool k_fit_dir_geometry(i64 N, int *G, int *NW, int *NSB) {
+    int dev = 0, cus = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return k_fit_dir_geometry_cus(N, cus, G, NW, NSB);
+}
+i64 k_fit_flow_dir_slot_doubles(i64 N, i64 Tld) {
+    const i64 Nt = (N + 63) / 64;
+    return 32 + 8 * Tld + 3 * 4 * Nt + 4 * Nt * Nt * 64; // sync words, T ring, f, P (laid out as k_fit_persistent_dir does)
+}
+static const void *k_fit_flow_dir_multi_fn(int NW) {
+    return NW == 8 ? (const void *)fit_flow_dir_multi_kernel<8> : (const void *)fit_flow_dir_multi_kernel<4>;
+}
+bool k_fit_flow_dir_multi_fits(int NW) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fit_flow_dir_multi_fn(NW), 64 * NW, 0) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return true;
+}
+// `flow`: the problems' slot regions back to back (k_fit_flow_dir_slot_doubles each, armed with one fill), then their T_0
+// (Tin, Tout: Tld doubles each, zero beyond N), staged here from the problem's Tin / Tout, which the launch updates on success only
+void k_fit_flow_dir_multi(cge_ctx *c, cge_flow_dir_multi &tab, int NW, double eps0, double f0, double delta, DevBuf<double> &flow) {
+    i64 tot = 0, t0tot = 0;
+    int wg = 0;
+    int dev = 0, cus = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (tab.n < 1 || tab.n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ASSERT, "directed fit batch of %d problems", tab.n);
+    for (int i = 0; i < tab.n; i++) {
+        tot += k_fit_flow_dir_slot_doubles(tab.p[i].N, tab.p[i].Tld);
+        t0tot += 2 * tab.p[i].Tld;
+        wg += tab.p[i].G;
+    }
+    if (wg > cus) CGE_THROW(CGE_E_ASSERT, "directed fit batch of %d problems on %d workgroups does not fit %d CUs", tab.n, wg, cus);
+    flow.ensure((size_t)(tot + t0tot));
+    i64 off = 0, t0off = tot;
+    wg = 0;
+    hipStream_t st = c->stream;
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)flow.p, (int)FLOW_SENTINEL_WORD, (size_t)(2 * tot), st)); // every slot armed
+    HIP_CHECK(hipMemsetAsync(flow.p + tot, 0, sizeof(double) * t0tot, st));
+    for (int i = 0; i < tab.n; i++) {
+        cge_flow_dir_problem &q = tab.p[i];
+        double *base = flow.p + off, *t0 = flow.p + t0off;
+        q.sync = reinterpret_cast<unsigned *>(base);
+        q.ring = base + 32;
+        q.fq = q.ring + 8 * q.Tld;
+        q.P = q.fq + 3 * 4 * (i64)q.Nt;
+        q.wg0 = wg;
+        HIP_CHECK(hipMemcpyAsync(t0, q.Tin, sizeof(double) * q.N, hipMemcpyDeviceToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(t0 + q.Tld, q.Tout, sizeof(double) * q.N, hipMemcpyDeviceToDevice, st));
+        q.T0 = t0;
+        wg += q.G;
+        off += k_fit_flow_dir_slot_doubles(q.N, q.Tld);
+        t0off += 2 * q.Tld;
+    }
+    int aMax = 2000000, aNaps = c->opt_fit_test_delay;
+    long long aTicks = c->opt_fit_test_timeout ? 0LL : CGE_FIT_TIMEOUT_TICKS; // per iteration (0: the test hook)
+    void *args[] = {&tab, &eps0, &f0, &delta, &aMax, &aTicks, &aNaps};
+    hipError_t e;
+    {
+        ScopedKernelTimer tm(c, "fit_batched");
+        e = hipLaunchKernel(k_fit_flow_dir_multi_fn(NW), dim3((unsigned)wg), dim3(64 * NW), args, 0, st);
+    }
+    if (e != hipSuccess) CGE_THROW(CGE_E_HIP, "batched directed fit launch failed: %s", hipGetErrorString(e));
+}
+
 // Directed fit of one alpha from Tin / Tout (N doubles each, updated in place on success).  Returns false when the
 // persistent path does not apply or was abandoned; Tin / Tout are then untouched.
 bool k_fit_persistent_dir(cge_ctx *c, const double *GD, i64 N, double *Tin, double *Tout, const double *deg_in,
                           const double *deg_out, double eps0, double f0, double delta, i64 *iters, int *dev_flags, bool *enqueued_only) {
     if (enqueued_only) *enqueued_only = false;
     const int Nt = (int)((N + 63) / 64);
-    const i64 NT = (i64)Nt * (Nt + 1) / 2, Tld = (i64)Nt * 64;
+    const i64 Tld = (i64)Nt * 64;
     int dev = 0, cus = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     if (cus <= 0) return false;
     hipStream_t st = c->stream;
     c->fp_Td.ensure((size_t)4 * Tld);
-    if (Nt <= 64) { // the data as its own signal: one tile per wave on 4 or 8 waves per CU
-        const int NW = (NT <= (i64)4 * cus) ? 4 : 8;
-        const int Gf = (int)std::min<i64>(cus, std::max<i64>((NT + NW - 1) / NW, (i64)4 * Nt));
-        if (NT <= (i64)NW * Gf && 4 * Nt <= 2 * Gf) {
-            const bool one = 4 * Nt <= Gf; // every workgroup reduces at most one quarter block
+    {
+        int NW = 0, Gf = 0, nsb = 0;
+        if (k_fit_dir_geometry_cus(N, cus, &Gf, &NW, &nsb)) { // the data as its own signal: one tile per wave on 4 or 8 waves per CU
+            const bool one = nsb == 1; // every workgroup reduces at most one quarter block
             const void *fn = NW == 8 ? (one ? (const void *)fit_flow_dir_kernel<8, 1> : (const void *)fit_flow_dir_kernel<8, 2>)
                                      : (one ? (const void *)fit_flow_dir_kernel<4, 1> : (const void *)fit_flow_dir_kernel<4, 2>);
             int per_cu = 0;

@@ -441,6 +441,55 @@ static bool hand_off(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, const Sam
     return true;
 }
 
+// cge_score_batch on a directed graph: which members share the fit's launch, and on which geometry -- that of the member's own
+// k_fit_persistent_dir launch.  At least 256 landmarks, one quarter block per workgroup at most (the multi kernel exists for
+// NSB = 1) and no more than half the chip, so that a launch holds two members at least.
+bool batch_dir_member_geometry(i64 N, int cus, int *G, int *NW) {
+    int nsb = 0;
+    return N >= 256 && k_fit_dir_geometry_cus(N, cus, G, NW, &nsb) && nsb == 1 && *G <= cus / 2;
+}
+
+// The directed sibling of hand_off: the sweep is prepared (prepare_distances, samples_to_device) and its alphas are run by the
+// batch (batch_host.cpp: host_batch_sweep).  What they read moves out of the context -- D, the logarithm, the community tables,
+// the prepared sample sets -- or, where it is landmark state that the next member's landmark phase overwrites, is copied:
+// Tin / Tout, the degrees, vect_C, v2l and the landmarks' weights.  False: the fit shares no launch (the sweep runs here).
+static bool hand_off_directed(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, const OrigView &orig, const SampleSet &smp, int split) {
+    const i64 N = G.N, C = G.C, vlen = C * C;
+    int dev = 0, cus = 0, fG = 0, fNW = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (!batch_dir_member_geometry(N, cus, &fG, &fNW) || fG > h.max_G || !k_fit_flow_dir_multi_fits(fNW)) return false;
+    hipStream_t st = c->stream;
+    k_pow_prepare(c, c->sw_D.p, N, false); // what the sweep does once before its first alpha
+    h.logs = c->pow_logs_N == N && !c->pow_logs_upper; // (k_pow_matrix's own rule for whole rows)
+    if (h.logs) { h.Lh.swap(c->sw_Lh); h.Ll.swap(c->sw_Ll); }
+    c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the hand-off)
+    h.D.swap(c->sw_D);
+    h.GD.ensure((size_t)N * N);
+    h.cm_off.swap(c->sw_cm_off); h.cm_mem.swap(c->sw_cm_mem); h.cm_pos.swap(c->sw_cm_pos);
+    h.bvec_form = k_bvec_form(c, N);
+    h.dsets.clear();
+    for (i64 t = 0; t < smp.n_sets; t++) {
+        h.dsets.emplace_back(std::move(c->dsets[t]));
+        c->dsets[t].reset(new DevSamples());
+    }
+    h.vectC.ensure(vlen);
+    h.Tio.ensure((size_t)2 * N); h.deg.ensure((size_t)2 * N); h.lweight.ensure(N); h.v2l.ensure(orig.n);
+    HIP_CHECK(hipMemcpyAsync(h.vectC.p, G.vectC, sizeof(double) * vlen, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(h.Tio.p, c->sw_T1.p, sizeof(double) * N, hipMemcpyDeviceToDevice, st)); // Tin, Tout (zero where the degree is)
+    HIP_CHECK(hipMemcpyAsync(h.Tio.p + N, c->sw_T2.p, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(h.deg.p, G.deg_in, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(h.deg.p + N, G.deg_out, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(h.lweight.p, orig.lweight, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(h.v2l.p, orig.v2l, sizeof(i32) * orig.n, hipMemcpyDeviceToDevice, st));
+    h.N = N; h.C = C; h.S = smp.S; h.n_sets = smp.n_sets; h.Tld = (N + 63) / 64 * 64; h.split = split;
+    h.G = fG; h.NW = fNW;
+    h.directed = true;
+    h.deferred = true;
+    HIP_CHECK(hipStreamSynchronize(st)); // (the staging packer's host memory)
+    return true;
+}
+
 // ---- one alpha -------------------------------------------------------------------------------------
 
 // What the host keeps of an alpha in flight until it collects it (two at most: slot = alpha index mod 2)
@@ -790,6 +839,11 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     if (defer) defer->deferred = false;
     if (defer && lay.fuse && fuse_auc && fit.persistent && !shard && !c->has_coll && hand_off(c, *defer, G, smp, split, Tld, h_epi))
         return;
+    // a directed landmark-mode member: its fits share fit_flow_dir_multi_kernel's launch (no fused chain, so neither option
+    // fit_fused nor the fused tallies' sample limit applies; a sweep relabelled for the tile form of vect_B runs here)
+    if (defer && directed && orig && fit.persistent_dir && !shard && !c->has_coll && !lay.relabel && !c->bvec_blocks &&
+        hand_off_directed(c, *defer, G, *orig, smp, split))
+        return;
 
     // ---- alpha sweep: alpha i + 1 is enqueued before the host waits for alpha i, unless the sweep may end at alpha i (so
     // nothing is ever computed in vain) or the fit of alpha i needs the host
@@ -1070,8 +1124,8 @@ void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b
 }
 
 // ---- the testing hook of the Chung-Lu fit (include/cge_hip_testing.h: cge_fit_test) -------------------------------------------
-// One fit from a caller's start through fit_undirected / fit_directed (forms 0-4) or k_fit_flow_multi (form 5), on the buffers a
-// sweep keeps them in.  Everything that can refuse does so before the first launch.
+// One fit from a caller's start through fit_undirected / fit_directed (forms 0-4), k_fit_flow_multi (form 5) or
+// k_fit_flow_dir_multi (form 6), on the buffers a sweep keeps them in.  Everything that can refuse does so before the first launch.
 
 // D to sw_D and, when the form or the caller reads it, GD = (1 - D)^alpha to sw_GD by the sweep's two launches (upper: the upper
 // tiles alone, as a landmark-mode sweep makes it; everything else of sw_GD is NaN) and to the caller's GD
@@ -1257,9 +1311,54 @@ static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, in
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
+// form 6: every problem with its own power matrix, Tin / Tout, degrees and flags, as the directed members of a batch keep them
+static void ft_dir_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, int NW, double eps, double delta) {
+    hipStream_t st = c->stream;
+    struct Member {
+        DevBuf<double> GD, T, deg;
+    };
+    std::vector<std::unique_ptr<Member>> mem;
+    DevBuf<int> flags;
+    DevBuf<double> flow;
+    flags.ensure((size_t)4 * n);
+    HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4 * n, st));
+    cge_flow_dir_multi tab{};
+    tab.n = n;
+    for (int i = 0; i < n; i++) {
+        cge_fit_problem &p = probs[i];
+        const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
+        mem.emplace_back(new Member());
+        Member &m = *mem.back();
+        ft_matrices(c, p, false, true);
+        m.GD.swap(c->sw_GD); // (the context's power matrix leaves with the member)
+        m.T.ensure((size_t)2 * N);
+        m.deg.ensure((size_t)2 * N);
+        HIP_CHECK(hipMemcpyAsync(m.T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(m.T.p + N, p.T0b, sizeof(double) * N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(m.deg.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(m.deg.p + N, p.w2, sizeof(double) * N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        cge_flow_dir_problem &q = tab.p[i];
+        q.GD = m.GD.p;
+        q.Tin = m.T.p; q.Tout = m.T.p + N;
+        q.deg_in = m.deg.p; q.deg_out = m.deg.p + N;
+        q.flags = flags.p + 4 * i;
+        q.N = N; q.Tld = Tld; q.Nt = (int)Nt; q.G = G[i];
+    }
+    k_fit_flow_dir_multi(c, tab, NW, eps, 1.0, delta, flow);
+    for (int i = 0; i < n; i++) {
+        cge_fit_problem &p = probs[i];
+        p.status = ft_verdict(c, flags.p + 4 * i, &p.iters) ? 0 : 1;
+        HIP_CHECK(hipMemcpyAsync(p.T, tab.p[i].Tin, sizeof(double) * p.N, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(p.Tb, tab.p[i].Tout, sizeof(double) * p.N, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
 void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int form, double eps, double delta, int *form_ran) {
-    if (n > 1 && form != 5) CGE_THROW(CGE_E_ARG, "fit_test: %d problems in one call are form 5 only", n);
-    if (n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ARG, "fit_test: form 5 takes at most %d problems", CGE_BATCH_MAX);
+    if (!directed && form == 6) CGE_THROW(CGE_E_ARG, "fit_test: form 6 is directed only");
+    if (n > 1 && form != 5 && form != 6) CGE_THROW(CGE_E_ARG, "fit_test: %d problems in one call are form 5 only", n);
+    if (n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ARG, "fit_test: form %d takes at most %d problems", form, CGE_BATCH_MAX);
     if (directed && (form == 2 || form == 4 || form == 5)) CGE_THROW(CGE_E_ARG, "fit_test: form %d is undirected only", form);
     if ((form == 4 || form == 5) && !c->opt_pow_exp2)
         CGE_THROW(CGE_E_ARG, "fit_test: form %d makes its power matrix from the stored logarithm (option pow_exp2)", form);
@@ -1286,6 +1385,26 @@ void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int 
             NW0 = NW;
             sumG += G[i];
         }
+        if (form == 6) {
+            int NW = 0, nsb = 0;
+            if (!k_fit_dir_geometry_cus(p.N, cus, &G[i], &NW, &nsb))
+                CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the directed persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
+            if (nsb != 1)
+                CGE_THROW(CGE_E_ARG, "fit_test: form 6 takes problems of one quarter block per workgroup (N = %lld needs two on %d CUs)", (long long)p.N, cus);
+            if (i > 0 && NW != NW0)
+                CGE_THROW(CGE_E_ARG, "fit_test: form 6 takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", i, NW, NW0);
+            NW0 = NW;
+            sumG += G[i];
+        }
+    }
+    if (form == 6 && sumG > cus)
+        CGE_THROW(CGE_E_ARG, "fit_test: the problems of form 6 need %d workgroups in all, the device has %d CUs", sumG, cus);
+    if (form == 6 && !k_fit_flow_dir_multi_fits(NW0))
+        CGE_THROW(CGE_E_ARG, "fit_test: fit_flow_dir_multi_kernel of %d waves gets no workgroup on a CU", NW0);
+    if (form == 6) {
+        ft_dir_multi(c, probs, n, G, NW0, eps, delta);
+        *form_ran = 6;
+        return;
     }
     if (form == 5 && sumG > cus)
         CGE_THROW(CGE_E_ARG, "fit_test: the problems of form 5 need %d workgroups in all, the device has %d CUs", sumG, cus);

@@ -296,8 +296,14 @@ int cge_score(cge_ctx *ctx, const cge_score_args *args, double out[7], int *out_
  * embedding is replaced member by member, and afterwards the resident embedding and landmark state are the LAST member's.
  * Undirected landmark-mode members on the fused persistent fit (>= 256 landmarks, options fit_fused = 1, fit_persistent != 1)
  * share their sweeps: the members' fits of an alpha run in ONE launch (launch groups of at most the CU count in workgroups,
- * run one after another), and so do their vect_B and JS; the local score's samples are drawn once.  Every other member
- * (directed, exact mode land = -1, fewer landmarks) is scored on its own, as cge_score would.  Not under collectives or
+ * run one after another), and so do their vect_B and JS; the local score's samples are drawn once.  DIRECTED landmark-mode
+ * members share the fit alone: with >= 256 landmarks, fit_persistent != 1, a persistent directed fit of one quarter block per
+ * workgroup on at most half the CUs (256 <= N <= 1984 on 256 CUs) and the row forms of vect_B (not bvec_blocks = 1), the
+ * members' directed fits of an alpha run in ONE launch, each on the workgroups of its own launch; the power matrix, the local
+ * score's tallies, vect_B and JS stay launches of their own per member.  Option fit_fused and the 65 536-sample limit of the
+ * fused tallies do not apply to them.  While its launch group runs, a directed member holds 16 N^2 bytes (D and its power
+ * matrix), 28 N^2 with the stored logarithm (pow_exp2).  Every other member (exact mode land = -1, fewer landmarks, a star
+ * graph's early return) is scored on its own, as cge_score would.  Not under collectives or
  * sharding (CGE_E_ARG: one embedding per rank is the multi-GPU form).  On an error (e.g. CGE_E_HOMOGENEOUS of a member) the
  * call returns it with every out_len[k] = 0; the context stays usable.  Stats "fit_batched_launches" / "fit_batched_alphas":
  * multi-problem fit launches of the last call and the member-alphas they fitted.                                            */

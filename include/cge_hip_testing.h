@@ -14,6 +14,13 @@ int cge_host_eig_top(const double *A, int64_t d, double *v);
  * their order; a group closes when the next member's workgroups would exceed `cus`, its waves per workgroup differ, or it holds
  * 16 members. */
 int cge_batch_pack_test(const int64_t *N, int64_t K, int cus, int32_t *group_of);
+/* host-only (no device work, no context): the geometry of the directed persistent fit (fit_flow_dir_kernel) for N vertices on
+ * `cus` CUs, as k_fit_persistent_dir and the shared launch of a directed batch both take it.  *applies = 0: the form declines (the
+ * other outputs are not written).  Else G workgroups of NW waves (4 or 8), and NSB = 1 or 2 quarter blocks per workgroup. */
+int cge_fit_dir_geometry_test(int64_t N, int cus, int *applies, int *G, int *NW, int *NSB);
+/* cge_batch_pack_test for the members of a directed batch: a member of N[k] landmarks shares the fit's launch when N[k] >= 256,
+ * the directed geometry applies with NSB = 1 and G <= cus / 2 (else group_of[k] = -1); the groups close by the same rule. */
+int cge_batch_pack_dir_test(const int64_t *N, int64_t K, int cus, int32_t *group_of);
 /* the sampler's counter-based draw of positive rows: pos_idx[k] in 1..m (no device work) */
 int cge_host_pos_draw(int64_t seed, int64_t stream_id, int64_t S, int64_t m, int64_t *pos_idx);
 /* kernel-level hook (needs the GPU): principal eigenvectors of T symmetric d x d matrices (row-major, back to
@@ -164,10 +171,14 @@ int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_pro
  *      3: persistent, reading GD (fit_flow_kernel / fit_flow_dir_kernel);
  *      4: undirected, the fused instance of fit_flow_kernel without an epilogue output (needs option "pow_exp2");
  *      5: undirected, fit_flow_multi_kernel over n_problems (1..CGE_BATCH_MAX = 16) problems with slots and flags of their own.
- *      *form_ran = the form that ran.  n_problems > 1: form 5 only.
- * CGE_E_ARG, with a message and before any launch, where a form does not apply: forms 3-5 where the geometry of the persistent
- * fit declines N on this device; forms 2, 4, 5 directed; forms 4, 5 without "pow_exp2"; form 5 with problems of different waves
- * per workgroup or more workgroups in all than the device has CUs. */
+ *      6: directed, fit_flow_dir_multi_kernel over n_problems (1..16) problems with slots, start vectors and flags of their
+ *         own, each on the geometry (G, NW) of its own form-3 launch; per problem the outputs are form 3's: T, Tb, iters, status
+ *         (an abandoned launch returns every member's start).
+ *      *form_ran = the form that ran.  n_problems > 1: form 5 (undirected) and form 6 (directed) only.
+ * CGE_E_ARG, with a message and before any launch, where a form does not apply: forms 3-6 where the geometry of the persistent
+ * fit declines N on this device; forms 2, 4, 5 directed; form 6 undirected; forms 4, 5 without "pow_exp2"; forms 5, 6 with
+ * problems of different waves per workgroup, more workgroups in all than the device has CUs or more than 16 problems; form 6
+ * with a problem whose workgroups would reduce two quarter blocks each (the multi kernel exists for one). */
 typedef struct cge_fit_problem {
     const double *D, *w, *w2, *T0, *T0b;
     double *T, *Tb, *GD;
