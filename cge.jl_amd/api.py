@@ -257,14 +257,25 @@ def wedge_geometry_test(N, weighted, n_chunks):
 
 
 def fit_dir_geometry_test(N, cus):
-    """Host-only hook (include/cge_hip_testing.h: cge_fit_dir_geometry_test): the geometry of the directed persistent fit for N
-    vertices on `cus` CUs.  None where the form declines, else (G, NW, NSB)."""
+    """Host-only hook (include/cge_hip_testing.h: cge_fit_dir_geometry_test): the one geometry of the persistent fits, undirected
+    and directed, for N vertices on `cus` CUs.  None where the form declines, else (G, NW, NSB)."""
     L = load_library()
     ap, G, NW, NSB = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     rc = L.cge_fit_dir_geometry_test(C.c_int64(N), C.c_int(cus), C.byref(ap), C.byref(G), C.byref(NW), C.byref(NSB))
     if rc:
         raise CGEError(rc, "cge_fit_dir_geometry_test")
     return (G.value, NW.value, NSB.value) if ap.value else None
+
+
+def fit_slots_test(N, directed):
+    """Host-only hook (cge_fit_slots_test): the hand-off slots of one persistent-fit problem of N vertices with Tld = 64 Nt, in
+    doubles from the start of its region: a dict sync, ring, fq, P (offsets) and doubles (the region's length)."""
+    L = load_library()
+    out = (C.c_int64 * 5)()
+    rc = L.cge_fit_slots_test(C.c_int64(N), C.c_int(int(bool(directed))), out)
+    if rc:
+        raise CGEError(rc, "cge_fit_slots_test")
+    return dict(zip(("sync", "ring", "fq", "P", "doubles"), (int(v) for v in out)))
 
 
 def batch_pack_dir_test(N, cus):

@@ -25,7 +25,7 @@ static void host_batch_sweep_dir(cge_ctx *c, std::vector<BatchMember *> &group) 
     const i64 n_alpha = AlphaBook::n_alpha;
     const int K = (int)group.size();
     hipStream_t st = c->stream;
-    const int NW = group[0]->h.NW;
+    const int NW = group[0]->h.geo.NW;
     c->batch_scal.ensure((size_t)K * RES_STRIDE);
     c->batch_pin.ensure((size_t)2 * K * RES_STRIDE);
     double *scal = c->batch_scal.p;
@@ -53,7 +53,7 @@ static void host_batch_sweep_dir(cge_ctx *c, std::vector<BatchMember *> &group) 
             q.Tin = h.Tio.p; q.Tout = h.Tio.p + h.N;
             q.deg_in = h.deg.p; q.deg_out = h.deg.p + h.N;
             q.flags = reinterpret_cast<int *>(scal + (i64)A[i] * RES_STRIDE + RES_FIT);
-            q.N = h.N; q.Tld = h.Tld; q.Nt = (int)((h.N + 63) / 64); q.G = h.G;
+            q.N = h.N; q.Tld = h.Tld; q.Nt = h.geo.Nt; q.G = h.geo.G;
         }
         k_fit_flow_dir_multi(c, tab, NW, 0.9, 1.0, AlphaBook::delta, c->batch_flow); // epsilon, diff (:434-435)
         c->stat_fit_batched_launches++;
@@ -108,7 +108,7 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
     if (K < 1) return;
     if (group[0]->h.directed) return host_batch_sweep_dir(c, group);
     hipStream_t st = c->stream;
-    const int NW = group[0]->h.NW;
+    const int NW = group[0]->h.geo.NW;
     i64 vtot = 0;
     std::vector<i64> voff(K);
     for (int j = 0; j < K; j++) {
@@ -155,7 +155,7 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
             Live &L = live[j];
             SweepHandoff &h = group[j]->h;
             const bool want_auc = !book[j].skip_auc, want_div = !book[j].skip_div;
-            const int Nt = (int)((h.N + 63) / 64), tnext = (L.tpar + 1) % 3;
+            const int Nt = h.geo.Nt, tnext = (L.tpar + 1) % 3;
             double *sj = scal + (i64)j * RES_STRIDE;
             cge_flow_problem &q = tab.p[i];
             q.Lh = h.Lh.p; q.Ll = h.Ll.p; q.alpha = alpha;
@@ -165,7 +165,7 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
             q.Tout = h.T.p + (i64)tnext * h.Tld;
             q.w = h.w;
             q.flags = reinterpret_cast<int *>(sj + RES_FIT);
-            q.N = h.N; q.Tld = h.Tld; q.Nt = Nt; q.G = h.G;
+            q.N = h.N; q.Tld = h.Tld; q.Nt = Nt; q.G = h.geo.G;
             L.tpar = tnext;
             L.next_enqueue = ia + 1;
             if (!want_div) continue;
@@ -247,9 +247,7 @@ static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embe
         if (view_check(views + k, c->n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s: embedding %lld: %s", who, (long long)k, msg.c_str());
         if (views[k].on_device) check_device_pointer(c, (std::string(who) + ": embedding " + std::to_string(k)).c_str(), views[k].data);
     }
-    int dev = 0, cus = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const int cus = device_cus();
     // the members that can take the batched sweep (landmark mode; undirected: the fused fit, directed: the persistent fit of >= 256
     // landmarks); the sweep decides the rest
     // (one member, or a member whose fit takes more than half the chip, shares nothing: it is scored as cge_score scores it)
@@ -283,9 +281,9 @@ static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embe
         host_score(c, a, m->out, m->out_len, m->trace, batchable ? &m->h : nullptr, have_samples);
         have_samples = have_samples || c->smp.n_sets > 0;
         if (!m->h.deferred) continue; // (scored: the sequential path)
-        if (batch_group_closes(g_sum, g_nw, (int)group.size(), m->h.G, m->h.NW, cus)) run_group();
-        g_sum += m->h.G;
-        g_nw = m->h.NW;
+        if (batch_group_closes(g_sum, g_nw, (int)group.size(), m->h.geo.G, m->h.geo.NW, cus)) run_group();
+        g_sum += m->h.geo.G;
+        g_nw = m->h.geo.NW;
         group.push_back(std::move(m));
         group_k.push_back(k);
     }

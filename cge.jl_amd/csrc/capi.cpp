@@ -456,35 +456,35 @@ int cge_host_eig_top(const double *A, int64_t d, double *v) {
     host_eig_top(A, d, v);
     return CGE_OK;
 }
-int cge_batch_pack_test(const int64_t *N, int64_t K, int cus, int32_t *group_of) {
+// the launch groups of a batch's members, undirected or directed: flow_batch_member picks them, batch_group_closes packs them
+static int batch_pack(const int64_t *N, int64_t K, int cus, bool directed, int32_t *group_of) {
     if (!N || !group_of || K < 0 || cus <= 0) return CGE_E_ARG;
     int groups = 0, g_sum = 0, g_nw = 0, g_size = 0;
     for (i64 k = 0; k < K; k++) {
-        int G = 0, NW = 0;
-        if (N[k] < 256 || !k_fit_flow_geometry_cus(N[k], cus, &G, &NW)) { group_of[k] = -1; continue; } // (sequential)
-        if (g_size == 0 || batch_group_closes(g_sum, g_nw, g_size, G, NW, cus)) { groups++; g_sum = 0; g_size = 0; }
-        g_sum += G; g_nw = NW; g_size++;
+        FlowGeometry g;
+        if (!flow_batch_member(N[k], cus, directed, &g)) { group_of[k] = -1; continue; } // (sequential)
+        if (g_size == 0 || batch_group_closes(g_sum, g_nw, g_size, g.G, g.NW, cus)) { groups++; g_sum = 0; g_size = 0; }
+        g_sum += g.G; g_nw = g.NW; g_size++;
         group_of[k] = groups - 1;
     }
     return groups;
 }
-// host-only hooks (include/cge_hip_testing.h): the directed persistent fit's geometry, and the launch groups of a directed batch
+int cge_batch_pack_test(const int64_t *N, int64_t K, int cus, int32_t *group_of) { return batch_pack(N, K, cus, false, group_of); }
+int cge_batch_pack_dir_test(const int64_t *N, int64_t K, int cus, int32_t *group_of) { return batch_pack(N, K, cus, true, group_of); }
+// host-only hooks (include/cge_hip_testing.h): the persistent fits' one geometry and one slot layout
 int cge_fit_dir_geometry_test(int64_t N, int cus, int *applies, int *G, int *NW, int *NSB) {
     if (!applies || !G || !NW || !NSB) return CGE_E_ARG;
-    *applies = k_fit_dir_geometry_cus(N, cus, G, NW, NSB) ? 1 : 0;
+    FlowGeometry g;
+    *applies = flow_geometry(N, cus, &g) ? 1 : 0;
+    if (*applies) { *G = g.G; *NW = g.NW; *NSB = g.NSB; }
     return CGE_OK;
 }
-int cge_batch_pack_dir_test(const int64_t *N, int64_t K, int cus, int32_t *group_of) {
-    if (!N || !group_of || K < 0 || cus <= 0) return CGE_E_ARG;
-    int groups = 0, g_sum = 0, g_nw = 0, g_size = 0;
-    for (i64 k = 0; k < K; k++) {
-        int G = 0, NW = 0;
-        if (!batch_dir_member_geometry(N[k], cus, &G, &NW)) { group_of[k] = -1; continue; } // (sequential)
-        if (g_size == 0 || batch_group_closes(g_sum, g_nw, g_size, G, NW, cus)) { groups++; g_sum = 0; g_size = 0; }
-        g_sum += G; g_nw = NW; g_size++;
-        group_of[k] = groups - 1;
-    }
-    return groups;
+int cge_fit_slots_test(int64_t N, int directed, int64_t out[5]) {
+    if (!out || N <= 0 || N > 64 * 64) return CGE_E_ARG;
+    const int Nt = (int)((N + 63) / 64);
+    const FlowSlots s = flow_slots(Nt, (i64)Nt * 64, directed != 0);
+    out[0] = s.sync; out[1] = s.ring; out[2] = s.fq; out[3] = s.P; out[4] = s.doubles;
+    return CGE_OK;
 }
 int cge_host_pos_draw(int64_t seed, int64_t stream_id, int64_t S, int64_t m, int64_t *pos_idx) {
     if (!pos_idx || S <= 0 || m <= 0) return CGE_E_ARG;

@@ -900,8 +900,22 @@ bool k_fit_flow_enqueue(cge_ctx *c, const double *GD, i64 N, const double *T0, d
                         double eps, double delta, int *dev_flags, const cge_fit_fused *ff = nullptr,
                         const cge_fit_fused *ff_dev = nullptr); // ff_dev: the device copy of *ff the epilogue reads (alpha, partial and
                                                                 // auc_part are taken from *ff: they change per alpha)
-bool k_fit_flow_applies(i64 N, i64 Tld); // the persistent fits' geometry (fit_flow_kernel reading GD, fit_flow_dir_kernel) accepts N on this device
-bool k_fit_flow_fused_applies(cge_ctx *c, i64 N); // the geometry the fused instances exist for (one tile per wave, one quarter block per workgroup)
+// The ONE launch geometry of the persistent fits, undirected and directed, single and shared (kernels_fitp.hip): Nt x Nt blocks
+// of 64, NT upper tiles, G workgroups of NW waves (4 or 8), NSB = quarter blocks a workgroup may have to reduce (1 or 2).
+struct FlowGeometry {
+    int Nt; i64 NT; int G, NW, NSB;
+    bool fused() const { return NSB == 1; } // what the fused and the shared instances exist for: one quarter block per workgroup
+};
+int device_cus(); // the CU count of the current device
+bool flow_geometry(i64 N, int cus, FlowGeometry *g); // no device needed; false (g untouched): the persistent form does not apply
+bool flow_geometry(i64 N, FlowGeometry *g);          // on device_cus()
+inline bool flow_fused_applies(i64 N) { FlowGeometry g; return flow_geometry(N, &g) && g.fused(); }
+// whether cge_score_batch shares the fit of a member of N landmarks: N >= 256 and fused; directed also G <= cus / 2
+bool flow_batch_member(i64 N, int cus, bool directed, FlowGeometry *g);
+// The ONE layout of a problem's hand-off slots, as offsets in doubles from the region's start: 32 doubles of sync words, the T ring
+// (4 Tld, directed 8 Tld), f (12 Nt), P (2 Nt^2 64, directed 4 Nt^2 64); `doubles` = the region (even: armed in 16-byte units)
+struct FlowSlots { i64 sync, ring, fq, P, doubles; };
+FlowSlots flow_slots(int Nt, i64 Tld, bool directed);
 void k_bins_prepare(cge_ctx *c, const i32 *cm_off, i64 N, i64 C, i64 n_partials); // once per sweep, behind the tile tables
 // what bins_js_kernel, the last launch of an alpha's chain, does on the way out: the alpha's scalars straight into the host's
 // pinned slot (host_out; scal = their device copy, [res_js, res_js + 2 x CGE_PARTIAL_BLOCKS) = the JS partials this launch
@@ -922,15 +936,13 @@ struct cge_flow_problem {
     double *ring, *P, *fq; unsigned *sync; int *flags;
     i64 N, Tld; int Nt, G, wg0, pad1;
 };
-// the geometry fit_flow_kernel uses for N (false: the persistent form does not apply), and the hand-off slots one problem needs
-bool k_fit_flow_geometry(i64 N, int *G, int *NW);
-i64 k_fit_flow_slot_doubles(i64 N, i64 Tld);
 #define CGE_BATCH_MAX 16 // problems per launch group (G >= 16 for every fused problem: 256 CUs hold no more than 16)
 struct cge_flow_multi { cge_flow_problem p[CGE_BATCH_MAX]; int n, pad; }; // passed by value (kernel arguments)
-// lay the problems' slots out in `flow` (k_fit_flow_slot_doubles each, in order), arm them all and launch; ring / P / fq / sync
-// and wg0 are filled in here.  The problems share NW; the sum of their G must not exceed the CU count (the caller packs them).
+// lay the problems' slots out in `flow` (flow_slots each, in order), arm them all and launch (timer "fit_batched"); ring / P / fq /
+// sync and wg0 are filled in here.  The problems share NW.  CGE_E_ASSERT for more than CGE_BATCH_MAX problems or a sum of G
+// above the CU count (the caller packs them).
 void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, double delta, DevBuf<double> &flow);
-bool k_fit_flow_multi_fits(int NW); // the multi-problem kernel of NW waves gets a workgroup on a CU
+bool k_fit_flow_multi_fits(int NW, bool directed); // fit_flow_multi_kernel / fit_flow_dir_multi_kernel of NW waves gets a workgroup on a CU
 // The same for directed graphs.  One problem of fit_flow_dir_multi_kernel: the arguments of its fit_flow_dir_kernel<NW, 1> launch
 // (Tin / Tout: N doubles each, updated in place on success only), its grid size G and its first workgroup wg0.
 struct cge_flow_dir_problem {
@@ -939,18 +951,9 @@ struct cge_flow_dir_problem {
     i64 N, Tld; int Nt, G, wg0, pad;
 };
 struct cge_flow_dir_multi { cge_flow_dir_problem p[CGE_BATCH_MAX]; int n, pad; }; // passed by value (kernel arguments)
-// the geometry fit_flow_dir_kernel uses for N on `cus` CUs / on this device (false: the persistent form does not apply); NSB =
-// quarter blocks a workgroup may have to reduce.  k_fit_persistent_dir and the shared launch both take it from here.
-bool k_fit_dir_geometry_cus(i64 N, int cus, int *G, int *NW, int *NSB);
-bool k_fit_dir_geometry(i64 N, int *G, int *NW, int *NSB);
-i64 k_fit_flow_dir_slot_doubles(i64 N, i64 Tld); // 32 sync words + 8 Tld ring + 12 Nt f + 4 Nt^2 64 P
-// lay the problems' slots and T_0 stages out in `flow`, arm every slot with one fill, stage T_0 = (Tin, Tout) zero-padded to
-// Tld and launch (timer "fit_batched"); ring / P / fq / sync / T0 and wg0 are filled in here.  CGE_E_ASSERT for more than
-// CGE_BATCH_MAX problems or a sum of G above the CU count.  eps0, f0, delta are common to the launch.
+// the same, with T_0 = (Tin, Tout) zero-padded to Tld staged behind the slots (T0 is filled in here too); eps0, f0, delta are
+// common to the launch
 void k_fit_flow_dir_multi(cge_ctx *c, cge_flow_dir_multi &tab, int NW, double eps0, double f0, double delta, DevBuf<double> &flow);
-bool k_fit_flow_dir_multi_fits(int NW); // fit_flow_dir_multi_kernel of NW waves gets a workgroup on a CU
-// whether cge_score_batch shares the fit of a directed member of N landmarks (>= 256, NSB = 1, G <= cus / 2), and its geometry
-bool batch_dir_member_geometry(i64 N, int cus, int *G, int *NW);
 struct cge_bins_problem { const double *partial; const i32 *cm_off, *fc, *ns, *base; i64 C; int Nt, pad; double *vectB; };
 struct cge_js_problem { const double *vC, *vB; i64 len, C; int mode, pad; double *part, *fpart; };
 struct cge_bins_multi { cge_bins_problem p[CGE_BATCH_MAX]; };
@@ -1087,7 +1090,8 @@ struct SweepHandoff {
     int max_G = 0;          // (set by the batch) a fit of more workgroups shares no launch: the sweep runs as cge_score's
     bool deferred = false;
     i64 N = 0, C = 0, S = 0, n_sets = 0, Tld = 0;
-    int split = 0, G = 0, NW = 0; // (G, NW: the geometry of its fit)
+    int split = 0;
+    FlowGeometry geo{}; // the geometry of its fit
     DevBuf<double> Lh, vw, bt_part, vectC, T, fused_pw;
     DevBuf<float> Ll;
     DevBuf<i32> comm, bt_fc, bt_ns, bt_base, cm_off;
@@ -1172,5 +1176,3 @@ void host_wgcl(cge_ctx *c, const cge_wgcl_args *a, double out[7], int *out_len, 
 void host_js(cge_ctx *c, const double *vC, const double *vB, i64 len, const uint8_t *vI, int internal, double *out);
 void host_edge_scatter(cge_ctx *c, const int64_t *v_to_l, i64 N, i64 C, int directed, i64 e0, i64 e1, double *wedges_out,
                        double *vect_C_out);
-// fit_flow_kernel's geometry for N landmarks on `cus` CUs (no device needed); false: the fused form does not apply
-bool k_fit_flow_geometry_cus(i64 N, int cus, int *G, int *NW);

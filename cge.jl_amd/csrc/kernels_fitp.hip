@@ -401,45 +401,91 @@ void k_fit_sym_step(cge_ctx *c, const double *GD, const double *Tin, double *Tou
                        delta, k, fring, done, iters);
 }
 
-// geometry of fit_flow_kernel for N vertices on this device; false: the form does not apply
-static bool flow_geometry_cus(i64 N, i64 Tld, int cus, int *G_out, int *NW_out, int *tpw_out) {
-    const int Nt = (int)((N + 63) / 64);
-    const i64 NT = (i64)Nt * (Nt + 1) / 2;
-    if (cus <= 0 || Tld < (i64)Nt * 64) return false;
-    // one tile per wave: 4 waves per CU while they cover the triangle, else 8 (two per SIMD, 256 registers apiece).  Eight
-    // tiles per CU is what the register file holds: N <= 4032 on 256 CUs (two tiles on each of four waves hold no more).
-    const int NW = (NT <= (i64)4 * cus) ? 4 : 8;
-    const int G = (int)std::min<i64>(cus, std::max<i64>((NT + NW - 1) / NW, (i64)4 * Nt));
-    const int tpw = (int)((NT + (i64)NW * G - 1) / ((i64)NW * G));
-    if (tpw > 1 || Nt > 64 || 4 * Nt > 2 * G) return false; // (a reducer adds up to 64 partial vectors, a workgroup reduces at most two quarter blocks)
-    *G_out = G; *NW_out = NW; *tpw_out = tpw;
-    return true;
-}
-static bool flow_geometry(i64 N, i64 Tld, int *G_out, int *NW_out, int *tpw_out) {
+// ---- the host side of the persistent fits: one geometry, one slot layout, one launch path ------------------------------------
+// fit_flow_kernel, fit_flow_multi_kernel, fit_flow_dir_kernel and fit_flow_dir_multi_kernel take their launch shape from
+// flow_geometry, the place of their hand-off slots from flow_slots / flow_place, and are checked, armed and launched by
+// FlowLaunch.  What differs between the four paths is what is left in their wrappers below: the kernel instance, its arguments,
+// and the staging of T_0 for the directed fits.
+int device_cus() {
     int dev = 0, cus = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    return flow_geometry_cus(N, Tld, cus, G_out, NW_out, tpw_out);
+    return cus;
 }
-bool k_fit_flow_applies(i64 N, i64 Tld) {
-    int G = 0, NW = 0, tpw = 0;
-    return flow_geometry(N, Tld, &G, &NW, &tpw);
+// One tile per wave: NW = 4 waves per workgroup while they cover the triangle, else 8 (two per SIMD, 256 registers apiece).  Eight
+// tiles per CU is what the register file holds: N <= 4032 on 256 CUs.  G workgroups: one per NW tiles and at least one per quarter
+// block where the CUs allow.  Refused: more tiles than waves, more than 64 partial vectors per reducer (Nt > 64), more than two
+// quarter blocks per workgroup.
+bool flow_geometry(i64 N, int cus, FlowGeometry *g) {
+    if (N <= 0 || N > 64 * 64 || cus <= 0) return false;
+    const int Nt = (int)((N + 63) / 64);
+    const i64 NT = (i64)Nt * (Nt + 1) / 2;
+    const int NW = NT <= (i64)4 * cus ? 4 : 8;
+    const int G = (int)std::min<i64>(cus, std::max<i64>((NT + NW - 1) / NW, (i64)4 * Nt));
+    if (NT > (i64)NW * G || 4 * Nt > 2 * G) return false;
+    *g = FlowGeometry{Nt, NT, G, NW, 4 * Nt <= G ? 1 : 2};
+    return true;
 }
-bool k_fit_flow_fused_applies(cge_ctx *c, i64 N) {
-    int G = 0, NW = 0, tpw = 0;
-    return flow_geometry(N, (N + 63) / 64 * 64, &G, &NW, &tpw) && tpw == 1 && 4 * (int)((N + 63) / 64) <= G;
+bool flow_geometry(i64 N, FlowGeometry *g) { return flow_geometry(N, device_cus(), g); }
+// (hand_off / hand_off_directed also refuse G > max_G = cus / 2, whichever kind: the undirected predicate, and with it
+// cge_batch_pack_test, does not -- an asymmetry kept as it was)
+bool flow_batch_member(i64 N, int cus, bool directed, FlowGeometry *g) {
+    return N >= 256 && flow_geometry(N, cus, g) && g->fused() && (!directed || g->G <= cus / 2);
 }
+FlowSlots flow_slots(int Nt, i64 Tld, bool directed) {
+    FlowSlots s;
+    s.sync = 0;                                 // 32 doubles: the fail / done words, armed with everything else
+    s.ring = s.sync + 32;                       // T ring: 4 x T, directed 4 x (Tin, Tout)
+    s.fq = s.ring + (directed ? 8 : 4) * Tld;   // f: 3 x 4 Nt
+    s.P = s.fq + 3 * 4 * (i64)Nt;               // P: 2 parities (directed: x (Sin, Sout)) x Nt x Nt x 64
+    s.doubles = s.P + (directed ? 4 : 2) * (i64)Nt * Nt * 64;
+    return s;
+}
+// the slot pointers of a problem (cge_flow_problem, cge_flow_dir_problem) whose region starts at `base`
+template <class Problem>
+static void flow_place(Problem &q, double *base, const FlowSlots &s) {
+    q.sync = reinterpret_cast<unsigned *>(base + s.sync);
+    q.ring = base + s.ring;
+    q.fq = base + s.fq;
+    q.P = base + s.P;
+}
+// What every launch of a persistent fit does around its arguments: the occupancy check of the instance, the limits the kernels
+// take (iterations, the deadline per iteration, the test naps), the sentinel fill of a slot region, the timed launch.
+struct FlowLaunch {
+    cge_ctx *c;
+    const void *fn;
+    int NW, max_iters = 2000000, naps;
+    long long ticks; // per iteration (0: the test hook)
+    FlowLaunch(cge_ctx *c_, const void *fn_, int NW_)
+        : c(c_), fn(fn_), NW(NW_), naps(c_->opt_fit_test_delay), ticks(c_->opt_fit_test_timeout ? 0LL : CGE_FIT_TIMEOUT_TICKS) {}
+    static bool fits(const void *fn, int NW) { // a workgroup of the instance gets a CU
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * NW, 0) == hipSuccess && per_cu >= 1) return true;
+        (void)hipGetLastError();
+        return false;
+    }
+    void arm(double *region, i64 doubles) const {
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)region, (int)FLOW_SENTINEL_WORD, (size_t)(2 * doubles), c->stream));
+    }
+    void launch(const char *timer, const char *what, int G, void **args) const {
+        hipError_t e;
+        {
+            ScopedKernelTimer tm(c, timer);
+            e = hipLaunchKernel(fn, dim3((unsigned)G), dim3(64 * NW), args, 0, c->stream);
+        }
+        if (e != hipSuccess) CGE_THROW(CGE_E_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    }
+};
+
 // where the hand-off slots of fit_flow_kernel for N vertices live and how they are armed (the buffer is made if need be)
 bool k_fit_flow_arm_region(cge_ctx *c, i64 N, i64 Tld, uint4 **ptr, i64 *n16, unsigned *word) {
-    int G = 0, NW = 0, tpw = 0;
-    if (!flow_geometry(N, Tld, &G, &NW, &tpw)) return false;
-    const int Nt = (int)((N + 63) / 64);
-    const size_t psz = (size_t)Nt * Nt * 64, n_ring = (size_t)4 * Tld, n_fq = (size_t)3 * 4 * Nt, n_sync = 32;
-    const size_t doubles = n_sync + n_ring + n_fq + 2 * psz;
-    if (doubles % 2) return false; // (16-byte units)
-    c->fp_flow.ensure(doubles);
+    FlowGeometry g;
+    if (!flow_geometry(N, &g) || Tld < (i64)g.Nt * 64) return false;
+    const FlowSlots s = flow_slots(g.Nt, Tld, false);
+    if (s.doubles % 2) return false; // (16-byte units)
+    c->fp_flow.ensure((size_t)s.doubles);
     *ptr = reinterpret_cast<uint4 *>(c->fp_flow.p);
-    *n16 = (i64)(doubles / 2);
+    *n16 = s.doubles / 2;
     *word = FLOW_SENTINEL_WORD;
     return true;
 }
@@ -453,189 +499,90 @@ bool k_fit_flow_enqueue(cge_ctx *c, const double *GD, i64 N, const double *T0, d
         fz.epi = ff_dev;
         fz.want = (ff->partial ? 1 : 0) | (ff->auc_part ? 2 : 0);
     }
-    const int Nt = (int)((N + 63) / 64);
-    int G = 0, NW = 0, tpw = 0;
-    if (!flow_geometry(N, Tld, &G, &NW, &tpw)) return false;
-    if (fused && (tpw != 1 || 4 * Nt > G)) return false; // (callers ask k_fit_flow_fused_applies first)
-    const size_t psz = (size_t)Nt * Nt * 64, n_ring = (size_t)4 * Tld, n_fq = (size_t)3 * 4 * Nt;
-    const size_t n_sync = 32; // fail / done words, armed with everything else
-    c->fp_flow.ensure(n_sync + n_ring + n_fq + 2 * psz);
-    const bool one = 4 * Nt <= G; // every workgroup reduces at most one quarter block
+    FlowGeometry g;
+    if (!flow_geometry(N, &g) || Tld < (i64)g.Nt * 64) return false;
+    if (fused && !g.fused()) return false; // (callers ask flow_fused_applies first)
     const void *fn;
-#define FLOW_PICK(F, B) (NW == 8 ? (const void *)fit_flow_kernel<1, 8, F, B> : (const void *)fit_flow_kernel<1, 4, F, B>)
-    if (fused) fn = NW == 8 ? (const void *)fit_flow_kernel<1, 8, true, 1> : (const void *)fit_flow_kernel<1, 4, true, 1>;
-    else fn = one ? FLOW_PICK(false, 1) : FLOW_PICK(false, 2);
+#define FLOW_PICK(F, B) (g.NW == 8 ? (const void *)fit_flow_kernel<1, 8, F, B> : (const void *)fit_flow_kernel<1, 4, F, B>)
+    if (fused) fn = FLOW_PICK(true, 1);
+    else fn = g.NSB == 1 ? FLOW_PICK(false, 1) : FLOW_PICK(false, 2);
 #undef FLOW_PICK
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * NW, 0) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        return false;
-    }
-    hipStream_t st = c->stream;
-    const i64 arm_words = (i64)(2 * (n_sync + n_ring + n_fq + 2 * psz));
-    if (c->flow_armed_words != arm_words) // (else: armed by the last launch of the previous alpha's chain, bins_js_kernel)
-        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)c->fp_flow.p, (int)FLOW_SENTINEL_WORD, (size_t)arm_words, st));
+    if (!FlowLaunch::fits(fn, g.NW)) return false;
+    FlowLaunch L(c, fn, g.NW);
+    const FlowSlots s = flow_slots(g.Nt, Tld, false);
+    c->fp_flow.ensure((size_t)s.doubles);
+    if (c->flow_armed_words != 2 * s.doubles) // (else: armed by the last launch of the previous alpha's chain, bins_js_kernel)
+        L.arm(c->fp_flow.p, s.doubles);
     c->flow_armed_words = 0;
-    const double *aGD = GD, *aT0 = T0, *aW = w;
-    double *aTout = Tout, *aRing = c->fp_flow.p + n_sync, *aFq = aRing + n_ring, *aP = aFq + n_fq;
-    i64 aN = N, aTld = Tld;
-    int aNt = Nt, aMax = 2000000;
-    double aEps = eps, aDelta = delta;
-    unsigned *aSync = (unsigned *)c->fp_flow.p;
-    int *aFlags = dev_flags;
-    long long aTicks = c->opt_fit_test_timeout ? 0LL : CGE_FIT_TIMEOUT_TICKS; // per iteration (0: the test hook)
-    int aNaps = c->opt_fit_test_delay;
-    void *args[] = {&aGD, &aN, &aNt, &aT0, &aTout, &aTld, &aW, &aEps, &aDelta, &aMax, &aRing, &aP, &aFq, &aSync, &aFlags, &aTicks,
-                    &aNaps, &fz};
-    hipError_t e;
-    {
-        ScopedKernelTimer tm(c, "fit_persistent");
-        e = hipLaunchKernel(fn, dim3((unsigned)G), dim3(64 * NW), args, 0, st);
-    }
-    if (e != hipSuccess) CGE_THROW(CGE_E_HIP, "fit launch failed: %s", hipGetErrorString(e));
+    cge_flow_problem q{};
+    flow_place(q, c->fp_flow.p, s);
+    void *args[] = {&GD, &N, &g.Nt, &T0, &Tout, &Tld, &w, &eps, &delta, &L.max_iters, &q.ring, &q.P, &q.fq, &q.sync, &dev_flags,
+                    &L.ticks, &L.naps, &fz};
+    L.launch("fit_persistent", "fit", g.G, args);
     return true;
 }
 
-bool k_fit_flow_geometry_cus(i64 N, int cus, int *G, int *NW) {
-    int tpw = 0;
-    return flow_geometry_cus(N, (N + 63) / 64 * 64, cus, G, NW, &tpw) && tpw == 1 && 4 * (int)((N + 63) / 64) <= *G;
-}
-bool k_fit_flow_geometry(i64 N, int *G, int *NW) {
-    int tpw = 0;
-    return flow_geometry(N, (N + 63) / 64 * 64, G, NW, &tpw) && tpw == 1 && 4 * (int)((N + 63) / 64) <= *G;
-}
-i64 k_fit_flow_slot_doubles(i64 N, i64 Tld) {
-    const i64 Nt = (N + 63) / 64;
-    return 32 + 4 * Tld + 3 * 4 * Nt + 2 * Nt * Nt * 64; // sync words, T ring, f, P (laid out as k_fit_flow_enqueue does)
-}
-static const void *k_fit_flow_multi_fn(int NW) {
-    return NW == 8 ? (const void *)fit_flow_multi_kernel<8> : (const void *)fit_flow_multi_kernel<4>;
-}
-bool k_fit_flow_multi_fits(int NW) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fit_flow_multi_fn(NW), 64 * NW, 0) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
-}
-void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, double delta, DevBuf<double> &flow) {
-    i64 tot = 0;
-    int wg = 0;
-    for (int i = 0; i < tab.n; i++) tot += k_fit_flow_slot_doubles(tab.p[i].N, tab.p[i].Tld);
-    flow.ensure((size_t)tot);
-    i64 off = 0;
-    for (int i = 0; i < tab.n; i++) {
-        cge_flow_problem &q = tab.p[i];
-        double *base = flow.p + off;
-        q.sync = reinterpret_cast<unsigned *>(base);
-        q.ring = base + 32;
-        q.fq = q.ring + 4 * q.Tld;
-        q.P = q.fq + 3 * 4 * (i64)q.Nt;
-        q.wg0 = wg;
-        wg += q.G;
-        off += k_fit_flow_slot_doubles(q.N, q.Tld);
-    }
-    int dev = 0, cus = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (tab.n < 1 || tab.n > CGE_BATCH_MAX || wg > cus)
-        CGE_THROW(CGE_E_ASSERT, "fit batch of %d problems on %d workgroups does not fit %d CUs", tab.n, wg, cus);
-    hipStream_t st = c->stream;
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)flow.p, (int)FLOW_SENTINEL_WORD, (size_t)(2 * tot), st)); // every slot armed
-    int aMax = 2000000, aNaps = c->opt_fit_test_delay;
-    long long aTicks = c->opt_fit_test_timeout ? 0LL : CGE_FIT_TIMEOUT_TICKS; // per iteration (0: the test hook)
-    void *args[] = {&tab, &eps, &delta, &aMax, &aTicks, &aNaps};
-    hipError_t e;
-    {
-        ScopedKernelTimer tm(c, "fit_batched");
-        e = hipLaunchKernel(k_fit_flow_multi_fn(NW), dim3((unsigned)wg), dim3(64 * NW), args, 0, st);
-    }
-    if (e != hipSuccess) CGE_THROW(CGE_E_HIP, "batched fit launch failed: %s", hipGetErrorString(e));
-}
-
-// The geometry of fit_flow_dir_kernel for N vertices on `cus` CUs (no device needed): one tile per wave on NW = 4 waves per
-// workgroup while they cover the triangle, else 8; G workgroups, one per tile group and at least one per quarter block where the
-// CUs allow; NSB = quarter blocks a workgroup may have to reduce (1 when 4 Nt <= G).  False: the form does not apply (more
-// tiles than waves, more than 64 partial vectors per reducer, more than two quarter blocks per workgroup).  k_fit_persistent_dir
-// and the batch's shared launch (k_fit_flow_dir_multi) both take their launch shape from here, so a member of a shared launch
-// runs the geometry of its own launch.
-bool k_fit_dir_geometry_cus(i64 N, int cus, int *G_out, int *NW_out, int *NSB_out) {
-    const int Nt = (int)((N + 63) / 64);
-    const i64 NT = (i64)Nt * (Nt + 1) / 2;
-    if (N <= 0 || cus <= 0 || Nt > 64) return false;
-    const int NW = (NT <= (i64)4 * cus) ? 4 : 8;
-    const int Gf = (int)std::min<i64>(cus, std::max<i64>((NT + NW - 1) / NW, (i64)4 * Nt));
-    if (!(NT <= (i64)NW * Gf && 4 * Nt <= 2 * Gf)) return false;
-    *G_out = Gf; *NW_out = NW; *NSB_out = 4 * Nt <= Gf ? 1 : 2;
-    return true;
-}
-bool k_fit_dir_geometry(i64 N, int *G, int *NW, int *NSB) {
-    int dev = 0, cus = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    return k_fit_dir_geometry_cus(N, cus, G, NW, NSB);
-}
-i64 k_fit_flow_dir_slot_doubles(i64 N, i64 Tld) {
-    const i64 Nt = (N + 63) / 64;
-    return 32 + 8 * Tld + 3 * 4 * Nt + 4 * Nt * Nt * 64; // sync words, T ring, f, P (laid out as k_fit_persistent_dir does)
-}
-static const void *k_fit_flow_dir_multi_fn(int NW) {
+static const void *flow_multi_fn(int NW, bool directed) {
+    if (!directed) return NW == 8 ? (const void *)fit_flow_multi_kernel<8> : (const void *)fit_flow_multi_kernel<4>;
     return NW == 8 ? (const void *)fit_flow_dir_multi_kernel<8> : (const void *)fit_flow_dir_multi_kernel<4>;
 }
-bool k_fit_flow_dir_multi_fits(int NW) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fit_flow_dir_multi_fn(NW), 64 * NW, 0) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
-}
-// `flow`: the problems' slot regions back to back (k_fit_flow_dir_slot_doubles each, armed with one fill), then their T_0
-// (Tin, Tout: Tld doubles each, zero beyond N), staged here from the problem's Tin / Tout, which the launch updates on success only
-void k_fit_flow_dir_multi(cge_ctx *c, cge_flow_dir_multi &tab, int NW, double eps0, double f0, double delta, DevBuf<double> &flow) {
-    i64 tot = 0, t0tot = 0;
+bool k_fit_flow_multi_fits(int NW, bool directed) { return FlowLaunch::fits(flow_multi_fn(NW, directed), NW); }
+// What the two shared launches have in common: the count first, every problem's first workgroup wg0 in the concatenated grid,
+// the test that the grid is resident (one workgroup per CU), and the problems' slot regions back to back in `flow`, which also
+// gets room for `stage` x Tld doubles per problem behind them.  Returns the slots' doubles in all; *grid = the sum of the G.
+template <class Tab>
+static i64 flow_multi_place(Tab &tab, bool directed, int stage, DevBuf<double> &flow, int *grid) {
+    const char *kind = directed ? "directed " : "";
+    if (tab.n < 1 || tab.n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ASSERT, "%sfit batch of %d problems", kind, tab.n);
+    const int cus = device_cus();
+    i64 tot = 0, extra = 0;
     int wg = 0;
-    int dev = 0, cus = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (tab.n < 1 || tab.n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ASSERT, "directed fit batch of %d problems", tab.n);
     for (int i = 0; i < tab.n; i++) {
-        tot += k_fit_flow_dir_slot_doubles(tab.p[i].N, tab.p[i].Tld);
-        t0tot += 2 * tab.p[i].Tld;
+        tab.p[i].wg0 = wg;
         wg += tab.p[i].G;
+        tot += flow_slots(tab.p[i].Nt, tab.p[i].Tld, directed).doubles;
+        extra += stage * tab.p[i].Tld;
     }
-    if (wg > cus) CGE_THROW(CGE_E_ASSERT, "directed fit batch of %d problems on %d workgroups does not fit %d CUs", tab.n, wg, cus);
-    flow.ensure((size_t)(tot + t0tot));
-    i64 off = 0, t0off = tot;
-    wg = 0;
+    if (wg > cus) CGE_THROW(CGE_E_ASSERT, "%sfit batch of %d problems on %d workgroups does not fit %d CUs", kind, tab.n, wg, cus);
+    flow.ensure((size_t)(tot + extra));
+    i64 off = 0;
+    for (int i = 0; i < tab.n; i++) {
+        const FlowSlots s = flow_slots(tab.p[i].Nt, tab.p[i].Tld, directed);
+        flow_place(tab.p[i], flow.p + off, s);
+        off += s.doubles;
+    }
+    *grid = wg;
+    return tot;
+}
+void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, double delta, DevBuf<double> &flow) {
+    int grid = 0;
+    const i64 tot = flow_multi_place(tab, false, 0, flow, &grid);
+    FlowLaunch L(c, flow_multi_fn(NW, false), NW);
+    L.arm(flow.p, tot); // every slot armed
+    void *args[] = {&tab, &eps, &delta, &L.max_iters, &L.ticks, &L.naps};
+    L.launch("fit_batched", "batched fit", grid, args);
+}
+// `flow`: the problems' slot regions (armed with one fill), then their T_0 (Tin, Tout: Tld doubles each, zero beyond N), staged
+// here from the problem's Tin / Tout, which the launch updates on success only
+void k_fit_flow_dir_multi(cge_ctx *c, cge_flow_dir_multi &tab, int NW, double eps0, double f0, double delta, DevBuf<double> &flow) {
+    int grid = 0;
+    const i64 tot = flow_multi_place(tab, true, 2, flow, &grid);
     hipStream_t st = c->stream;
-    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)flow.p, (int)FLOW_SENTINEL_WORD, (size_t)(2 * tot), st)); // every slot armed
+    FlowLaunch L(c, flow_multi_fn(NW, true), NW);
+    L.arm(flow.p, tot); // every slot armed
+    i64 t0tot = 0;
+    for (int i = 0; i < tab.n; i++) t0tot += 2 * tab.p[i].Tld;
     HIP_CHECK(hipMemsetAsync(flow.p + tot, 0, sizeof(double) * t0tot, st));
+    double *t0 = flow.p + tot;
     for (int i = 0; i < tab.n; i++) {
         cge_flow_dir_problem &q = tab.p[i];
-        double *base = flow.p + off, *t0 = flow.p + t0off;
-        q.sync = reinterpret_cast<unsigned *>(base);
-        q.ring = base + 32;
-        q.fq = q.ring + 8 * q.Tld;
-        q.P = q.fq + 3 * 4 * (i64)q.Nt;
-        q.wg0 = wg;
         HIP_CHECK(hipMemcpyAsync(t0, q.Tin, sizeof(double) * q.N, hipMemcpyDeviceToDevice, st));
         HIP_CHECK(hipMemcpyAsync(t0 + q.Tld, q.Tout, sizeof(double) * q.N, hipMemcpyDeviceToDevice, st));
         q.T0 = t0;
-        wg += q.G;
-        off += k_fit_flow_dir_slot_doubles(q.N, q.Tld);
-        t0off += 2 * q.Tld;
+        t0 += 2 * q.Tld;
     }
-    int aMax = 2000000, aNaps = c->opt_fit_test_delay;
-    long long aTicks = c->opt_fit_test_timeout ? 0LL : CGE_FIT_TIMEOUT_TICKS; // per iteration (0: the test hook)
-    void *args[] = {&tab, &eps0, &f0, &delta, &aMax, &aTicks, &aNaps};
-    hipError_t e;
-    {
-        ScopedKernelTimer tm(c, "fit_batched");
-        e = hipLaunchKernel(k_fit_flow_dir_multi_fn(NW), dim3((unsigned)wg), dim3(64 * NW), args, 0, st);
-    }
-    if (e != hipSuccess) CGE_THROW(CGE_E_HIP, "batched directed fit launch failed: %s", hipGetErrorString(e));
+    void *args[] = {&tab, &eps0, &f0, &delta, &L.max_iters, &L.ticks, &L.naps};
+    L.launch("fit_batched", "batched directed fit", grid, args);
 }
 
 // Directed fit of one alpha from Tin / Tout (N doubles each, updated in place on success).  Returns false when the
@@ -643,66 +590,43 @@ void k_fit_flow_dir_multi(cge_ctx *c, cge_flow_dir_multi &tab, int NW, double ep
 bool k_fit_persistent_dir(cge_ctx *c, const double *GD, i64 N, double *Tin, double *Tout, const double *deg_in,
                           const double *deg_out, double eps0, double f0, double delta, i64 *iters, int *dev_flags, bool *enqueued_only) {
     if (enqueued_only) *enqueued_only = false;
-    const int Nt = (int)((N + 63) / 64);
-    const i64 Tld = (i64)Nt * 64;
-    int dev = 0, cus = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (cus <= 0) return false;
+    FlowGeometry g;
+    if (!flow_geometry(N, &g)) return false; // (the caller iterates with one launch pair per iteration)
+    const void *fn = g.NW == 8 ? (g.NSB == 1 ? (const void *)fit_flow_dir_kernel<8, 1> : (const void *)fit_flow_dir_kernel<8, 2>)
+                               : (g.NSB == 1 ? (const void *)fit_flow_dir_kernel<4, 1> : (const void *)fit_flow_dir_kernel<4, 2>);
+    if (!FlowLaunch::fits(fn, g.NW)) return false;
+    FlowLaunch L(c, fn, g.NW);
     hipStream_t st = c->stream;
+    i64 Tld = (i64)g.Nt * 64;
+    const FlowSlots s = flow_slots(g.Nt, Tld, true);
     c->fp_Td.ensure((size_t)4 * Tld);
-    {
-        int NW = 0, Gf = 0, nsb = 0;
-        if (k_fit_dir_geometry_cus(N, cus, &Gf, &NW, &nsb)) { // the data as its own signal: one tile per wave on 4 or 8 waves per CU
-            const bool one = nsb == 1; // every workgroup reduces at most one quarter block
-            const void *fn = NW == 8 ? (one ? (const void *)fit_flow_dir_kernel<8, 1> : (const void *)fit_flow_dir_kernel<8, 2>)
-                                     : (one ? (const void *)fit_flow_dir_kernel<4, 1> : (const void *)fit_flow_dir_kernel<4, 2>);
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * NW, 0) == hipSuccess && per_cu >= 1) {
-                const size_t pstride = (size_t)Nt * Nt * 64, n_sync = 32, n_ring = (size_t)8 * Tld, n_fq = (size_t)3 * 4 * Nt,
-                             n_p = 4 * pstride;
-                c->fp_flow.ensure(n_sync + n_ring + n_fq + n_p);
-                c->flow_armed_words = 0; // (the undirected fit's slots live in the same buffer)
-                c->fp_flags.ensure(4);
-                HIP_CHECK(hipMemsetAsync(c->fp_Td.p, 0, sizeof(double) * 2 * Tld, st));
-                HIP_CHECK(hipMemcpyAsync(c->fp_Td.p, Tin, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
-                HIP_CHECK(hipMemcpyAsync(c->fp_Td.p + Tld, Tout, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
-                HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)c->fp_flow.p, (int)FLOW_SENTINEL_WORD,
-                                            2 * (n_sync + n_ring + n_fq + n_p), st));
-                const double *aGD = GD, *aT0 = c->fp_Td.p, *aDi = deg_in, *aDo = deg_out;
-                double *aTi = Tin, *aTo = Tout, *aRing = c->fp_flow.p + n_sync, *aFq = aRing + n_ring, *aP = aFq + n_fq;
-                i64 aN = N, aTld = Tld;
-                int aNt = Nt, aMax = 2000000;
-                double aEps = eps0, aF0 = f0, aDelta = delta;
-                unsigned *aSync = (unsigned *)c->fp_flow.p;
-                int *aFlags = dev_flags ? dev_flags : c->fp_flags.p;
-                long long aTicks = c->opt_fit_test_timeout ? 0LL : CGE_FIT_TIMEOUT_TICKS;
-                int aNaps = c->opt_fit_test_delay;
-                void *args[] = {&aGD, &aN, &aNt, &aT0, &aTi, &aTo, &aTld, &aDi, &aDo, &aEps, &aF0, &aDelta, &aMax, &aRing, &aP, &aFq,
-                                &aSync, &aFlags, &aTicks, &aNaps};
-                hipError_t e;
-                {
-                    ScopedKernelTimer tm(c, "fit_persistent");
-                    e = hipLaunchKernel(fn, dim3((unsigned)Gf), dim3(64 * NW), args, 0, st);
-                }
-                if (e != hipSuccess) CGE_THROW(CGE_E_HIP, "directed fit launch failed: %s", hipGetErrorString(e));
-                if (dev_flags) { // enqueue only: the caller reads the verdict (flags) behind whatever it queues after the fit
-                    *enqueued_only = true;
-                    *iters = 0;
-                    return true;
-                }
-                int hf[4];
-                HIP_CHECK(hipMemcpyAsync(hf, c->fp_flags.p, sizeof(hf), hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                if (hf[2] || !hf[0]) { // abandoned: Tin / Tout are untouched
-                    note_fit_fallback(c);
-                    return false;
-                }
-                *iters = hf[1];
-                return true;
-            }
-            (void)hipGetLastError();
-        }
+    c->fp_flow.ensure((size_t)s.doubles);
+    c->flow_armed_words = 0; // (the undirected fit's slots live in the same buffer)
+    c->fp_flags.ensure(4);
+    HIP_CHECK(hipMemsetAsync(c->fp_Td.p, 0, sizeof(double) * 2 * Tld, st)); // T_0 = (Tin, Tout), zero beyond N
+    HIP_CHECK(hipMemcpyAsync(c->fp_Td.p, Tin, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->fp_Td.p + Tld, Tout, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+    L.arm(c->fp_flow.p, s.doubles);
+    cge_flow_dir_problem q{};
+    flow_place(q, c->fp_flow.p, s);
+    q.T0 = c->fp_Td.p;
+    q.flags = dev_flags ? dev_flags : c->fp_flags.p;
+    void *args[] = {&GD, &N, &g.Nt, &q.T0, &Tin, &Tout, &Tld, &deg_in, &deg_out, &eps0, &f0, &delta, &L.max_iters, &q.ring, &q.P,
+                    &q.fq, &q.sync, &q.flags, &L.ticks, &L.naps};
+    L.launch("fit_persistent", "directed fit", g.G, args);
+    if (dev_flags) { // enqueue only: the caller reads the verdict (flags) behind whatever it queues after the fit
+        *enqueued_only = true;
+        *iters = 0;
+        return true;
     }
-    return false; // (the form does not apply to this size: the caller iterates with one launch pair per iteration)
+    int hf[4];
+    HIP_CHECK(hipMemcpyAsync(hf, c->fp_flags.p, sizeof(hf), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (hf[2] || !hf[0]) { // abandoned: Tin / Tout are untouched
+        note_fit_fallback(c);
+        return false;
+    }
+    *iters = hf[1];
+    return true;
 }
+

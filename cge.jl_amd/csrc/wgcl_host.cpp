@@ -153,7 +153,7 @@ static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int direct
     const bool tiles_req = landmarks && !directed && c->opt_fit_fused && c->opt_exact_relabel && N >= 256 &&
                            C >= 2 && !c->opt_test_bvec_plain;
     const bool fuse_req = tiles_req && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
-                          c->opt_pow_exp2 && k_fit_flow_fused_applies(c, N);
+                          c->opt_pow_exp2 && flow_fused_applies(N);
     const bool blocks = blocks_req || tiles_req;
     bool blocks_ok = blocks, pieces_ok = true;
     // the sweep's small tables travel together: one pinned staging buffer, one copy and one scatter kernel per flush instead of a
@@ -414,8 +414,8 @@ static void fused_tables(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, 
 static bool hand_off(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, const SampleSet &smp, int split, i64 Tld,
                      std::vector<cge_fit_fused> &h_epi) {
     const i64 N = G.N, vlen = packed_len(G.C);
-    int fG = 0, fNW = 0;
-    if (!k_fit_flow_geometry(N, &fG, &fNW) || fG > h.max_G || !k_fit_flow_multi_fits(fNW)) return false;
+    FlowGeometry geo;
+    if (!flow_batch_member(N, device_cus(), false, &geo) || geo.G > h.max_G || !k_fit_flow_multi_fits(geo.NW, false)) return false;
     hipStream_t st = c->stream;
     k_pow_prepare(c, c->sw_D.p, N, true, true);
     h.Lh.swap(c->sw_Lh); h.Ll.swap(c->sw_Ll);
@@ -433,20 +433,12 @@ static bool hand_off(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, const Sam
     h.T.ensure((size_t)3 * Tld); // T rotates through three parts (as TT); T_0 = ones
     HIP_CHECK(hipMemcpyAsync(h.T.p, c->fp_T.p, sizeof(double) * 3 * Tld, hipMemcpyDeviceToDevice, st));
     h.N = N; h.C = G.C; h.S = smp.S; h.n_sets = smp.n_sets; h.Tld = Tld; h.split = split;
-    h.G = fG; h.NW = fNW;
+    h.geo = geo;
     h.h_epi = std::move(h_epi);
     h.w = G.vw;
     h.deferred = true;
     HIP_CHECK(hipStreamSynchronize(st)); // (the staging packer's host memory)
     return true;
-}
-
-// cge_score_batch on a directed graph: which members share the fit's launch, and on which geometry -- that of the member's own
-// k_fit_persistent_dir launch.  At least 256 landmarks, one quarter block per workgroup at most (the multi kernel exists for
-// NSB = 1) and no more than half the chip, so that a launch holds two members at least.
-bool batch_dir_member_geometry(i64 N, int cus, int *G, int *NW) {
-    int nsb = 0;
-    return N >= 256 && k_fit_dir_geometry_cus(N, cus, G, NW, &nsb) && nsb == 1 && *G <= cus / 2;
 }
 
 // The directed sibling of hand_off: the sweep is prepared (prepare_distances, samples_to_device) and its alphas are run by the
@@ -455,10 +447,10 @@ bool batch_dir_member_geometry(i64 N, int cus, int *G, int *NW) {
 // Tin / Tout, the degrees, vect_C, v2l and the landmarks' weights.  False: the fit shares no launch (the sweep runs here).
 static bool hand_off_directed(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, const OrigView &orig, const SampleSet &smp, int split) {
     const i64 N = G.N, C = G.C, vlen = C * C;
-    int dev = 0, cus = 0, fG = 0, fNW = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (!batch_dir_member_geometry(N, cus, &fG, &fNW) || fG > h.max_G || !k_fit_flow_dir_multi_fits(fNW)) return false;
+    // (a directed member shares the launch on the geometry of its own k_fit_persistent_dir launch: one quarter block per
+    // workgroup, which the multi kernel exists for, and no more than half the chip, so that a launch holds two members at least)
+    FlowGeometry geo;
+    if (!flow_batch_member(N, device_cus(), true, &geo) || geo.G > h.max_G || !k_fit_flow_multi_fits(geo.NW, true)) return false;
     hipStream_t st = c->stream;
     k_pow_prepare(c, c->sw_D.p, N, false); // what the sweep does once before its first alpha
     h.logs = c->pow_logs_N == N && !c->pow_logs_upper; // (k_pow_matrix's own rule for whole rows)
@@ -482,8 +474,8 @@ static bool hand_off_directed(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, 
     HIP_CHECK(hipMemcpyAsync(h.deg.p + N, G.deg_out, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipMemcpyAsync(h.lweight.p, orig.lweight, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipMemcpyAsync(h.v2l.p, orig.v2l, sizeof(i32) * orig.n, hipMemcpyDeviceToDevice, st));
-    h.N = N; h.C = C; h.S = smp.S; h.n_sets = smp.n_sets; h.Tld = (N + 63) / 64 * 64; h.split = split;
-    h.G = fG; h.NW = fNW;
+    h.N = N; h.C = C; h.S = smp.S; h.n_sets = smp.n_sets; h.Tld = (i64)geo.Nt * 64; h.split = split;
+    h.geo = geo;
     h.directed = true;
     h.deferred = true;
     HIP_CHECK(hipStreamSynchronize(st)); // (the staging packer's host memory)
@@ -1264,7 +1256,7 @@ static int ft_directed(cge_ctx *c, cge_fit_problem &p, int form, double eps, dou
 }
 
 // form 5: every problem with its own logarithm, T, weights and flags, as the members of a batch keep them (batch_host.cpp)
-static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, int NW, double eps, double delta) {
+static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const FlowGeometry *geo, double eps, double delta) {
     hipStream_t st = c->stream;
     struct Member {
         DevBuf<double> Lh, T, w;
@@ -1279,7 +1271,7 @@ static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, in
     tab.n = n;
     for (int i = 0; i < n; i++) {
         cge_fit_problem &p = probs[i];
-        const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
+        const i64 N = p.N, Tld = (i64)geo[i].Nt * 64;
         mem.emplace_back(new Member());
         Member &m = *mem.back();
         ft_matrices(c, p, true, false);
@@ -1300,9 +1292,9 @@ static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, in
         q.epi = nullptr; q.want = 0;
         q.T0 = m.T.p; q.Tout = m.T.p + Tld; q.w = m.w.p;
         q.flags = flags.p + 4 * i;
-        q.N = N; q.Tld = Tld; q.Nt = (int)Nt; q.G = G[i];
+        q.N = N; q.Tld = Tld; q.Nt = geo[i].Nt; q.G = geo[i].G;
     }
-    k_fit_flow_multi(c, tab, NW, eps, delta, flow);
+    k_fit_flow_multi(c, tab, geo[0].NW, eps, delta, flow);
     for (int i = 0; i < n; i++) {
         cge_fit_problem &p = probs[i];
         p.status = ft_verdict(c, flags.p + 4 * i, &p.iters) ? 0 : 1;
@@ -1312,7 +1304,7 @@ static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, in
 }
 
 // form 6: every problem with its own power matrix, Tin / Tout, degrees and flags, as the directed members of a batch keep them
-static void ft_dir_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G, int NW, double eps, double delta) {
+static void ft_dir_multi(cge_ctx *c, cge_fit_problem *probs, int n, const FlowGeometry *geo, double eps, double delta) {
     hipStream_t st = c->stream;
     struct Member {
         DevBuf<double> GD, T, deg;
@@ -1326,7 +1318,7 @@ static void ft_dir_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G
     tab.n = n;
     for (int i = 0; i < n; i++) {
         cge_fit_problem &p = probs[i];
-        const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
+        const i64 N = p.N, Tld = (i64)geo[i].Nt * 64;
         mem.emplace_back(new Member());
         Member &m = *mem.back();
         ft_matrices(c, p, false, true);
@@ -1343,9 +1335,9 @@ static void ft_dir_multi(cge_ctx *c, cge_fit_problem *probs, int n, const int *G
         q.Tin = m.T.p; q.Tout = m.T.p + N;
         q.deg_in = m.deg.p; q.deg_out = m.deg.p + N;
         q.flags = flags.p + 4 * i;
-        q.N = N; q.Tld = Tld; q.Nt = (int)Nt; q.G = G[i];
+        q.N = N; q.Tld = Tld; q.Nt = geo[i].Nt; q.G = geo[i].G;
     }
-    k_fit_flow_dir_multi(c, tab, NW, eps, 1.0, delta, flow);
+    k_fit_flow_dir_multi(c, tab, geo[0].NW, eps, 1.0, delta, flow);
     for (int i = 0; i < n; i++) {
         cge_fit_problem &p = probs[i];
         p.status = ft_verdict(c, flags.p + 4 * i, &p.iters) ? 0 : 1;
@@ -1363,58 +1355,41 @@ void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int 
     if ((form == 4 || form == 5) && !c->opt_pow_exp2)
         CGE_THROW(CGE_E_ARG, "fit_test: form %d makes its power matrix from the stored logarithm (option pow_exp2)", form);
     if (!(eps > 0.0) || !(delta >= 0.0)) CGE_THROW(CGE_E_ARG, "fit_test: eps > 0 and delta >= 0");
-    int G[CGE_BATCH_MAX], NW0 = 0, sumG = 0, cus = 0, dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const bool multi = form == 5 || form == 6;
+    FlowGeometry geo[CGE_BATCH_MAX];
+    int sumG = 0;
+    const int cus = device_cus();
     for (int i = 0; i < n; i++) {
         const cge_fit_problem &p = probs[i];
         if (p.N <= 0 || !p.D || !p.w || !p.T0 || !p.T) CGE_THROW(CGE_E_ARG, "fit_test: empty problem");
         if (directed && (!p.w2 || !p.T0b || !p.Tb)) CGE_THROW(CGE_E_ARG, "fit_test: a directed problem takes w2, T0b and Tb");
         if (p.N > 46340) CGE_THROW(CGE_E_ARG, "fit_test: problem too large");
-        const i64 Tld = (p.N + 63) / 64 * 64;
-        if (form == 3 && !k_fit_flow_applies(p.N, Tld))
+        FlowGeometry &g = geo[i];
+        const bool applies = flow_geometry(p.N, cus, &g);
+        if (form == 3 && !applies)
             CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-        if (form == 4 && !k_fit_flow_fused_applies(c, p.N))
+        if ((form == 4 || form == 5) && !(applies && g.fused()))
             CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the fused persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-        if (form == 5) {
-            int NW = 0;
-            if (!k_fit_flow_geometry(p.N, &G[i], &NW))
-                CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the fused persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-            if (i > 0 && NW != NW0)
-                CGE_THROW(CGE_E_ARG, "fit_test: form 5 takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", i, NW, NW0);
-            NW0 = NW;
-            sumG += G[i];
-        }
-        if (form == 6) {
-            int NW = 0, nsb = 0;
-            if (!k_fit_dir_geometry_cus(p.N, cus, &G[i], &NW, &nsb))
-                CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the directed persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-            if (nsb != 1)
-                CGE_THROW(CGE_E_ARG, "fit_test: form 6 takes problems of one quarter block per workgroup (N = %lld needs two on %d CUs)", (long long)p.N, cus);
-            if (i > 0 && NW != NW0)
-                CGE_THROW(CGE_E_ARG, "fit_test: form 6 takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", i, NW, NW0);
-            NW0 = NW;
-            sumG += G[i];
-        }
+        if (!multi) continue;
+        if (!applies)
+            CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the directed persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
+        if (!g.fused())
+            CGE_THROW(CGE_E_ARG, "fit_test: form 6 takes problems of one quarter block per workgroup (N = %lld needs two on %d CUs)", (long long)p.N, cus);
+        if (g.NW != geo[0].NW)
+            CGE_THROW(CGE_E_ARG, "fit_test: form %d takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", form, i, g.NW, geo[0].NW);
+        sumG += g.G;
     }
-    if (form == 6 && sumG > cus)
-        CGE_THROW(CGE_E_ARG, "fit_test: the problems of form 6 need %d workgroups in all, the device has %d CUs", sumG, cus);
-    if (form == 6 && !k_fit_flow_dir_multi_fits(NW0))
-        CGE_THROW(CGE_E_ARG, "fit_test: fit_flow_dir_multi_kernel of %d waves gets no workgroup on a CU", NW0);
-    if (form == 6) {
-        ft_dir_multi(c, probs, n, G, NW0, eps, delta);
-        *form_ran = 6;
+    if (!multi) {
+        *form_ran = directed ? ft_directed(c, probs[0], form, eps, delta) : ft_undirected(c, probs[0], form, eps, delta);
         return;
     }
-    if (form == 5 && sumG > cus)
-        CGE_THROW(CGE_E_ARG, "fit_test: the problems of form 5 need %d workgroups in all, the device has %d CUs", sumG, cus);
-    if (form == 5 && !k_fit_flow_multi_fits(NW0))
-        CGE_THROW(CGE_E_ARG, "fit_test: fit_flow_multi_kernel of %d waves gets no workgroup on a CU", NW0);
-    if (form == 5) {
-        ft_multi(c, probs, n, G, NW0, eps, delta);
-        *form_ran = 5;
-    } else
-        *form_ran = directed ? ft_directed(c, probs[0], form, eps, delta) : ft_undirected(c, probs[0], form, eps, delta);
+    if (sumG > cus)
+        CGE_THROW(CGE_E_ARG, "fit_test: the problems of form %d need %d workgroups in all, the device has %d CUs", form, sumG, cus);
+    if (!k_fit_flow_multi_fits(geo[0].NW, form == 6))
+        CGE_THROW(CGE_E_ARG, "fit_test: %s of %d waves gets no workgroup on a CU", form == 6 ? "fit_flow_dir_multi_kernel" : "fit_flow_multi_kernel",
+                  geo[0].NW);
+    (form == 6 ? ft_dir_multi : ft_multi)(c, probs, n, geo, eps, delta);
+    *form_ran = form;
 }
 
 // ---- the testing hook of the local score (include/cge_hip_testing.h: cge_local_score_test) -----------------------------------
@@ -1502,7 +1477,7 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
         if (!(io->eps > 0.0) || !(io->delta >= 0.0)) CGE_THROW(CGE_E_ARG, "local_score_test: eps > 0 and delta >= 0");
         if (!c->opt_pow_exp2)
             CGE_THROW(CGE_E_ARG, "local_score_test: form 4 makes its power matrix from the stored logarithm (option pow_exp2)");
-        if (!k_fit_flow_fused_applies(c, N))
+        if (!flow_fused_applies(N))
             CGE_THROW(CGE_E_ARG, "local_score_test: the geometry of the fused persistent fit declines N = %lld", (long long)N);
     }
     // ---- Draw --------------------------------------------------------------------------------------------------------------------

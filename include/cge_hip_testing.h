@@ -14,10 +14,14 @@ int cge_host_eig_top(const double *A, int64_t d, double *v);
  * their order; a group closes when the next member's workgroups would exceed `cus`, its waves per workgroup differ, or it holds
  * 16 members. */
 int cge_batch_pack_test(const int64_t *N, int64_t K, int cus, int32_t *group_of);
-/* host-only (no device work, no context): the geometry of the directed persistent fit (fit_flow_dir_kernel) for N vertices on
- * `cus` CUs, as k_fit_persistent_dir and the shared launch of a directed batch both take it.  *applies = 0: the form declines (the
- * other outputs are not written).  Else G workgroups of NW waves (4 or 8), and NSB = 1 or 2 quarter blocks per workgroup. */
+/* host-only (no device work, no context): the one geometry of the persistent fits (flow_geometry), undirected and directed, for N
+ * vertices on `cus` CUs, as every single launch and every member of a shared launch takes it.  *applies = 0: the form declines
+ * (the other outputs are not written).  Else G workgroups of NW waves (4 or 8), and NSB = 1 or 2 quarter blocks per workgroup. */
 int cge_fit_dir_geometry_test(int64_t N, int cus, int *applies, int *G, int *NW, int *NSB);
+/* host-only: the one layout of a problem's hand-off slots (flow_slots) for N vertices (1 .. 4096) and Tld = 64 ceil(N / 64), in
+ * doubles from the start of the problem's region: out = the offsets of the sync words, the T ring, f and P, and the region's
+ * length.  Problems of a shared launch lie back to back, each at the sum of the lengths before it. */
+int cge_fit_slots_test(int64_t N, int directed, int64_t out[5]);
 /* cge_batch_pack_test for the members of a directed batch: a member of N[k] landmarks shares the fit's launch when N[k] >= 256,
  * the directed geometry applies with NSB = 1 and G <= cus / 2 (else group_of[k] = -1); the groups close by the same rule. */
 int cge_batch_pack_dir_test(const int64_t *N, int64_t K, int cus, int32_t *group_of);

@@ -1,5 +1,5 @@
 """CPU tests of the directed batch's host arithmetic (no GPU): the geometry of the directed persistent fit as the library
-computes it (hook cge_fit_dir_geometry_test -- the one function k_fit_persistent_dir and the shared launch both ask) against the
+computes it (hook cge_fit_dir_geometry_test -- flow_geometry, the one function every persistent fit's launch asks) against the
 formulas restated here, and the launch groups a directed batch forms on it (cge_batch_pack_dir_test, batch_group_closes).  This
 pins "a member of a shared launch runs the geometry of its own launch"."""
 import os

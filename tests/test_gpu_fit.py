@@ -6,7 +6,7 @@ The forms go through the testing hook cge_fit_test (the sweep's own fit function
 (fit_flow_kernel / fit_flow_dir_kernel); 4 the fused instance (GD made in the prologue); 5 fit_flow_multi_kernel; 0 what a sweep
 picks.  The reference is tests/fit_ref.py (np.longdouble, pinned on the CPU by tests/test_fit_ref.py), always on the power matrix
 the hook returned, so the power's own error (tests/test_gpu_parity.py) stays out.  Which N sits on which geometry is derived from
-the device's CU count with flow_geometry_cus' formulas; the sizes are those of 256 CUs:
+the device's CU count with flow_geometry's formulas; the sizes are those of 256 CUs:
 
   1 .. 130      one to three tiles, odd and even-but-not-multiple-of-8 N (the guarded against the 16-byte loads of
                 fit_symtile_kernel), a last tile one row wide, workgroups with a quarter block but no tile
@@ -69,7 +69,7 @@ def _cus():
 
 
 def _geometry(N):
-    """flow_geometry_cus (kernels_fitp.hip): (G, NW, every workgroup has at most one quarter block) or None = declined."""
+    """flow_geometry (kernels_fitp.hip): (G, NW, every workgroup has at most one quarter block) or None = declined."""
     cus = _cus()
     Nt = (N + 63) // 64
     NT = Nt * (Nt + 1) // 2

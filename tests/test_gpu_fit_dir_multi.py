@@ -5,8 +5,8 @@ A member of a shared launch keeps the geometry (G, NW), the slots and the arithm
 its iterate, its iteration count and its status are those of form 3 bit for bit -- whatever the other members are, in whichever
 order, on a second run and under a start skew.  The kernel is also held to the long-double reference directly (tests/fit_ref.py,
 the cases and the criterion of tests/test_gpu_fit.py), so that it is not tied to the reference through form 3 alone.  Which N
-sits on which geometry is derived from the device's CU count with the formulas of k_fit_dir_geometry_cus, as test_gpu_fit.py
-does for flow_geometry_cus (the two are the same arithmetic); on 256 CUs: N = 65 -> G = 8, 300 -> 20, 700 -> 44, NW = 4 up to
+sits on which geometry is derived from the device's CU count with the formulas of flow_geometry, as test_gpu_fit.py
+does (the one geometry of every persistent fit); on 256 CUs: N = 65 -> G = 8, 300 -> 20, 700 -> 44, NW = 4 up to
 N = 2816, and no N whose workgroups would reduce two quarter blocks.
 """
 import numpy as np

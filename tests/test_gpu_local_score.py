@@ -333,7 +333,7 @@ def test_the_fused_fits_epilogue_tally(ctx, S):
     on that iterate within the weight of the samples whose reference gap is below 1e-9, that weight at most 1 % of den; (d) the
     same bits on a second run and under a start skew of 20 naps; (e) an abandoned launch is reported and writes no tally."""
     Nt = (FUSED_N + 63) // 64
-    assert 4 * Nt <= _cus() and Nt * (Nt + 1) // 2 <= 4 * _cus()  # flow_geometry_cus: one tile per wave, one quarter block per workgroup
+    assert 4 * Nt <= _cus() and Nt * (Nt + 1) // 2 <= 4 * _cus()  # flow_geometry, fused: one tile per wave, one quarter block per workgroup
     c = _fused_case(S)
     n, N, o2n, v2l = c["n"], c["N"], c["old2new"], c["v2l"]
     _ring(ctx, n)
