@@ -112,6 +112,17 @@ class FitProblem(C.Structure):
                 ("iters", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class FusedChainProblem(C.Structure):
+    """cge_fused_chain_problem (include/cge_hip_testing.h): one problem of the testing hook cge_fused_chain_test."""
+    _fields_ = [("D", C.c_void_p), ("w", C.c_void_p), ("T0", C.c_void_p), ("comm", C.c_void_p), ("N", C.c_int64),
+                ("C", C.c_int64), ("alpha", C.c_double), ("vC", C.c_void_p), ("want", C.c_int32), ("n_modes", C.c_int32),
+                ("S", C.c_int64), ("aidx", C.c_void_p), ("afac", C.c_void_p), ("aden", C.c_void_p), ("dpos", C.c_void_p),
+                ("dneg", C.c_void_p), ("wts", C.c_void_p), ("T", C.c_void_p), ("order", C.c_void_p), ("fc", C.c_void_p),
+                ("ns", C.c_void_p), ("base", C.c_void_p), ("partials", C.c_void_p), ("partials_cap", C.c_int64),
+                ("bt_total", C.c_int64), ("vectB", C.c_void_p), ("js_fused", C.c_void_p), ("part", C.c_void_p),
+                ("apw", C.c_void_p), ("iters", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 class LandmarkGraphIO(C.Structure):
     """cge_landmark_graph_io (include/cge_hip_testing.h): the arguments of the testing hook cge_landmark_graph_test."""
     _fields_ = [("v2l", C.c_void_p), ("N", C.c_int64), ("directed", C.c_int32), ("wedge_form", C.c_int32), ("part", C.c_int64),
@@ -1091,6 +1102,62 @@ class Context:
         for q, out in zip(arr, outs):
             out["iters"], out["status"] = int(q.iters), int(q.status)
         return ran.value, outs
+
+    def fused_chain_test(self, problems, directed=False, eps=0.25, delta=0.001):
+        """Testing hook (include/cge_hip_testing.h: cge_fused_chain_test): one alpha of the fused chain per problem -- the fused
+        fit with its epilogue's outputs, the bins, the divergence; one problem by fit_flow_kernel, several by one
+        fit_flow_multi_kernel launch.  A problem is a dict: D (N, N), alpha, w, T0, comm (ids in 1..C), C, want (bit 0 vect_B's
+        partials, bit 1 the tallies), optional vC with n_modes, and with want bit 1 `tally` = dict(aidx (4, S), afac (8, S),
+        aden (64,), dpos, dneg, wts (S,)).  Returns a list of dicts: T, iters, status, order, fc, ns, base, bt_total, partials
+        (bt_total,), vectB, guard, js_fused (n_modes,), part (64, 2), apw (2, S) or None."""
+        if isinstance(problems, dict):
+            problems = [problems]
+        n = len(problems)
+        arr = (FusedChainProblem * n)()
+        keep, outs = [], []
+        for q, pr in zip(arr, problems):
+            D, w, T0, comm = _f64(pr["D"]), _f64(pr["w"]), _f64(pr["T0"]), _i64(pr["comm"])
+            N, C_ = D.shape[0], int(pr["C"])
+            assert D.shape == (N, N) and w.shape == T0.shape == comm.shape == (N,)
+            Nt, ln = (N + 63) // 64, C_ * (C_ + 1) // 2
+            q.D, q.w, q.T0, q.comm = (a.ctypes.data for a in (D, w, T0, comm))
+            q.N, q.C, q.alpha, q.want, q.n_modes = N, C_, float(pr["alpha"]), int(pr["want"]), int(pr.get("n_modes", 1))
+            o = {"T": np.full(N, np.nan), "order": np.full(N, -1, np.int32), "fc": np.full(Nt, -1, np.int32),
+                 "ns": np.full(Nt, -1, np.int32), "base": np.full(Nt * Nt, -1, np.int32),
+                 # (a block spans at most min(64, C) ids: no layout has more partials)
+                 "partials": np.full(Nt * (Nt + 1) // 2 * min(64, max(C_, 1)) ** 2, np.nan),
+                 "vectB": np.full(max(ln, 0) + VECT_B_GUARD, np.nan), "js_fused": np.full(2, np.nan),
+                 "part": np.full((64, 2), np.nan), "apw": None}
+            q.T, q.order, q.fc, q.ns, q.base = (o[k].ctypes.data for k in ("T", "order", "fc", "ns", "base"))
+            q.partials, q.partials_cap = o["partials"].ctypes.data, o["partials"].size
+            q.vectB, q.js_fused, q.part = o["vectB"].ctypes.data, o["js_fused"].ctypes.data, o["part"].ctypes.data
+            if pr.get("vC") is not None:
+                vC = _f64(pr["vC"])
+                assert vC.shape == (ln,)
+                q.vC = vC.ctypes.data
+                keep.append(vC)
+            if pr.get("tally") is not None:
+                t = pr["tally"]
+                aidx = np.ascontiguousarray(t["aidx"], dtype=np.int32)
+                afac, aden, dpos, dneg, wts = (_f64(t[k]) for k in ("afac", "aden", "dpos", "dneg", "wts"))
+                S = dpos.shape[0]
+                assert aidx.shape == (4, S) and afac.shape == (8, S) and aden.shape == (64,) and dneg.shape == wts.shape == (S,)
+                o["apw"] = np.full((2, S), np.nan)
+                q.S, q.aidx, q.afac, q.aden, q.dpos, q.dneg, q.wts, q.apw = (S, aidx.ctypes.data, afac.ctypes.data, aden.ctypes.data,
+                                                                          dpos.ctypes.data, dneg.ctypes.data, wts.ctypes.data,
+                                                                          o["apw"].ctypes.data)
+                keep.extend((aidx, afac, aden, dpos, dneg, wts))
+            q.iters, q.status, q.bt_total = -1, -1, -1
+            keep.extend((D, w, T0, comm))
+            outs.append(o)
+        self._check(self.L.cge_fused_chain_test(self.h, arr, C.c_int(n), C.c_int(int(directed)), C.c_double(eps), C.c_double(delta)))
+        for q, pr, o in zip(arr, problems, outs):
+            ln = int(pr["C"]) * (int(pr["C"]) + 1) // 2
+            o["iters"], o["status"], o["bt_total"] = int(q.iters), int(q.status), int(q.bt_total)
+            o["partials"] = o["partials"][:o["bt_total"]]
+            o["vectB"], o["guard"] = o["vectB"][:ln], o["vectB"][ln:]
+            o["js_fused"] = o["js_fused"][:int(q.n_modes)]
+        return outs
 
     def local_score_test(self, S, directed=False, draw=None, draws=None, pos2=None, pairs=None, prepare=False, hi=None,
                          distances=False, dists=None, tally=None):

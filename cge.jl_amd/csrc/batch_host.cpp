@@ -157,15 +157,10 @@ void host_batch_sweep(cge_ctx *c, std::vector<BatchMember *> &group) {
             const bool want_auc = !book[j].skip_auc, want_div = !book[j].skip_div;
             const int Nt = h.geo.Nt, tnext = (L.tpar + 1) % 3;
             double *sj = scal + (i64)j * RES_STRIDE;
-            cge_flow_problem &q = tab.p[i];
-            q.Lh = h.Lh.p; q.Ll = h.Ll.p; q.alpha = alpha;
-            q.epi = reinterpret_cast<const cge_fit_fused *>(L.epi.p) + (h.n_sets == 1 ? 0 : ia - 1);
-            q.want = (want_div ? 1 : 0) | (want_auc ? 2 : 0);
-            q.T0 = h.T.p + (i64)L.tpar * h.Tld;
-            q.Tout = h.T.p + (i64)tnext * h.Tld;
-            q.w = h.w;
-            q.flags = reinterpret_cast<int *>(sj + RES_FIT);
-            q.N = h.N; q.Tld = h.Tld; q.Nt = Nt; q.G = h.geo.G;
+            tab.p[i] = flow_problem_entry(h.Lh.p, h.Ll.p, alpha,
+                                          reinterpret_cast<const cge_fit_fused *>(L.epi.p) + (h.n_sets == 1 ? 0 : ia - 1),
+                                          (want_div ? 1 : 0) | (want_auc ? 2 : 0), h.T.p + (i64)L.tpar * h.Tld,
+                                          h.T.p + (i64)tnext * h.Tld, h.w, reinterpret_cast<int *>(sj + RES_FIT), h.N, h.Tld, h.geo);
             L.tpar = tnext;
             L.next_enqueue = ia + 1;
             if (!want_div) continue;

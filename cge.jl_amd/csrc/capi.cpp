@@ -593,6 +593,16 @@ int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int direc
     CGE_CATCH(c)
 }
 
+// testing hook (include/cge_hip_testing.h): one alpha of the fused chain -- the fit with its epilogue's outputs, the bins, the divergence
+int cge_fused_chain_test(void *ctx, cge_fused_chain_problem *problems, int n_problems, int directed, double eps, double delta) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !problems || n_problems < 1) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    if (directed) CGE_THROW(CGE_E_ARG, "fused_chain_test: the fused chain is undirected only");
+    host_fused_chain_test(c, problems, n_problems, eps, delta);
+    CGE_CATCH(c)
+}
+
 // testing hook (include/cge_hip_testing.h): the local score's sampler, prepared pairs, pair distances and tallies, stage by stage
 int cge_local_score_test(void *ctx, cge_local_score_io *io) {
     cge_ctx *c = (cge_ctx *)ctx;

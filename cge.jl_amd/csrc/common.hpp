@@ -936,6 +936,19 @@ struct cge_flow_problem {
     double *ring, *P, *fq; unsigned *sync; int *flags;
     i64 N, Tld; int Nt, G, wg0, pad1;
 };
+// a problem's entry of the shared launch's table, as every caller fills it (the slots and wg0 are k_fit_flow_multi's); want: bit 0
+// vect_B's tile partials, bit 1 the tallies of epi (0: nothing of the epilogue)
+inline cge_flow_problem flow_problem_entry(const double *Lh, const float *Ll, double alpha, const cge_fit_fused *epi, int want,
+                                           const double *T0, double *Tout, const double *w, int *flags, i64 N, i64 Tld,
+                                           const FlowGeometry &g) {
+    cge_flow_problem q{};
+    q.Lh = Lh; q.Ll = Ll; q.alpha = alpha;
+    q.epi = epi; q.want = want;
+    q.T0 = T0; q.Tout = Tout; q.w = w;
+    q.flags = flags;
+    q.N = N; q.Tld = Tld; q.Nt = g.Nt; q.G = g.G;
+    return q;
+}
 #define CGE_BATCH_MAX 16 // problems per launch group (G >= 16 for every fused problem: 256 CUs hold no more than 16)
 struct cge_flow_multi { cge_flow_problem p[CGE_BATCH_MAX]; int n, pad; }; // passed by value (kernel arguments)
 // lay the problems' slots out in `flow` (flow_slots each, in order), arm them all and launch (timer "fit_batched"); ring / P / fq /
@@ -1133,6 +1146,9 @@ struct cge_vect_b_problem; // (include/cge_hip_testing.h)
 void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
                          double *GD);
 struct cge_fit_problem; // (include/cge_hip_testing.h)
+struct cge_fused_chain_problem; // (include/cge_hip_testing.h)
+void host_fused_chain_test(cge_ctx *c, cge_fused_chain_problem *probs, int n, double eps,
+                           double delta); // the testing hook of the fused chain's epilogue (wgcl_host.cpp)
 void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int form, double eps, double delta,
                    int *form_ran); // the testing hook of the Chung-Lu fit's forms (wgcl_host.cpp)
 void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b_problem *p2, int directed, int form,

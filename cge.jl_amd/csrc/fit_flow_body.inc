@@ -451,6 +451,22 @@
                         acc = __dadd_rn(acc, xr[r]);
                 }
                 if (crow >= 0 && live) out[(i64)(crow - fcI) * nsJ] = acc;
+                // Ids without a member inside a block's range of ids (an empty community between two others): their partials
+                // have no term and no run above writes them -- +0.0, as bvec_tile_kernel leaves them, so that the tile's
+                // partials are defined whoever made them.  A block's ids are ns = last - first + 1; with as many live runs
+                // nothing is missing (uniform: the tiles of a sweep without empty ids never come here).
+                const int nrunI = __popcll(segI);
+                const int nvI = nrunI - (segtab[wave_e][0][nrunI - 1] < 0 ? 1 : 0), nvJ = nrunJ - (segtab[wave_e][1][nrunJ - 1] < 0 ? 1 : 0);
+                const int nsI = segtab[wave_e][0][nvI - 1] - fcI + 1;
+                if (nvI != nsI || nvJ != nsJ) {
+                    unsigned long long presI = 0ull;
+                    for (int u = 0; u < nvI; u++) presI |= 1ull << (segtab[wave_e][0][u] - fcI);
+                    bool hasJ = false; // lane = a column id of the block
+                    for (int u = 0; u < nvJ; u++) hasJ = hasJ || (segtab[wave_e][1][u] - fcJ == lane_e);
+                    double *out0 = partial + (i64)__builtin_amdgcn_readfirstlane(ehdr[wave_e][7]);
+                    for (int r = 0; r < nsI; r++)
+                        if (lane_e < nsJ && (!((presI >> r) & 1ull) || !hasJ)) out0[(i64)r * nsJ + lane_e] = 0.0;
+                }
             }
             }
         }

@@ -381,16 +381,33 @@ static void samples_to_device(cge_ctx *c, const SampleSet &smp, i64 N, i64 d, co
 
 // The fused chain's tables, one per sample set (host copies in h_epi; the device copies, which the fit's epilogue loads after
 // its loop, in c->sw_fused_epi).  The local score tallies the samples [s0, s1) of every set; fuse_auc: on the fit's launch.
+// One table without the prepared tally operands: vect_B's half from the context's tile tables (comm: the communities in the
+// sweep's numbering) and the S samples' distances and weights.  Shared by fused_tables and the testing hook cge_fused_chain_test,
+// whose caller supplies the prepared operands.
+static cge_fit_fused fused_entry(cge_ctx *c, const i32 *comm, i64 S, const double *dpos, const double *dneg, const double *wts) {
+    cge_fit_fused e{};
+    e.comm = comm; e.fc = c->sw_bt_fc.p; e.ns = c->sw_bt_ns.p; e.base = c->sw_bt_base.p; e.partial = c->sw_bt_part.p;
+    e.S = S;
+    e.dpos = dpos; e.dneg = dneg; e.wts = wts;
+    e.auc_part = c->sw_scal.p + RES_AUC;
+    return e;
+}
+// the tables' device copies (c->sw_fused_epi), which the fit's epilogue loads after its loop
+static void fused_upload(cge_ctx *c, const std::vector<cge_fit_fused> &h_epi) {
+    c->sw_fused_epi.ensure(h_epi.size() * sizeof(cge_fit_fused));
+    static_assert(sizeof(cge_fit_fused) % 8 == 0, "packed as 4-byte words");
+    WordPacker pk(c);
+    pk.add(reinterpret_cast<i32 *>(c->sw_fused_epi.p), reinterpret_cast<const i32 *>(h_epi.data()),
+           (i64)(h_epi.size() * sizeof(cge_fit_fused) / 4));
+    pk.flush();
+}
 static void fused_tables(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *old2new, i64 n_sets, i64 s0, i64 s1,
                          bool fuse_auc, std::vector<cge_fit_fused> &h_epi) {
     h_epi.resize(n_sets);
     for (i64 t = 0; t < n_sets; t++) {
         DevSamples &ds = *c->dsets[t];
         cge_fit_fused &e = h_epi[t];
-        e = cge_fit_fused{};
-        e.comm = G.comm; e.fc = c->sw_bt_fc.p; e.ns = c->sw_bt_ns.p; e.base = c->sw_bt_base.p; e.partial = c->sw_bt_part.p;
-        e.S = s1 - s0;
-        e.dpos = ds.dpos.p + s0; e.dneg = ds.dneg.p + s0; e.wts = ds.wts.p + s0;
+        e = fused_entry(c, G.comm, s1 - s0, ds.dpos.p + s0, ds.dneg.p + s0, ds.wts.p + s0);
         if (fuse_auc && e.S > 0) { // everything of the tally that depends neither on alpha nor on T, once
             ds.aidx.ensure((size_t)4 * e.S); ds.afac.ensure((size_t)8 * e.S + CGE_PARTIAL_BLOCKS);
             c->sw_fused_pw.ensure((size_t)2 * e.S);
@@ -398,14 +415,8 @@ static void fused_tables(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, 
                           ds.nj.p + s0, e.wts, e.S, ds.aidx.p, ds.afac.p, ds.afac.p + 8 * e.S);
             e.aidx = ds.aidx.p; e.afac = ds.afac.p; e.aden = ds.afac.p + 8 * e.S; e.apw = c->sw_fused_pw.p;
         }
-        e.auc_part = c->sw_scal.p + RES_AUC;
     }
-    c->sw_fused_epi.ensure(h_epi.size() * sizeof(cge_fit_fused));
-    static_assert(sizeof(cge_fit_fused) % 8 == 0, "packed as 4-byte words");
-    WordPacker pk(c);
-    pk.add(reinterpret_cast<i32 *>(c->sw_fused_epi.p), reinterpret_cast<const i32 *>(h_epi.data()),
-           (i64)(h_epi.size() * sizeof(cge_fit_fused) / 4));
-    pk.flush();
+    fused_upload(c, h_epi);
 }
 
 // cge_score_batch: a sweep on the fused path is prepared here and run by the batch, beside other members' sweeps
@@ -1145,10 +1156,11 @@ static bool ft_verdict(cge_ctx *c, const int *dev_flags, i64 *iters) {
     return !(hf[2] || !hf[0]);
 }
 
-// epi / epi_dev (form 4, the hook of the local score): the host and device copies of the epilogue's table (fused_tables); the
-// launch then wants the tally of the epilogue and not vect_B, as enqueue_alpha asks for it once the divergence is skipped.
+// epi / epi_dev (form 4, the hooks of the local score and of the fused chain): the host and device copies of the epilogue's table
+// (fused_tables); the launch then wants of the epilogue what epi_want names (bit 0 vect_B's tile partials, bit 1 the tally), as
+// enqueue_alpha leaves out what an alpha does not want -- the local score's hook the tally alone.
 static int ft_undirected(cge_ctx *c, cge_fit_problem &p, int form, double eps, double delta, const cge_fit_fused *epi = nullptr,
-                         const cge_fit_fused *epi_dev = nullptr) {
+                         const cge_fit_fused *epi_dev = nullptr, int epi_want = 2) {
     hipStream_t st = c->stream;
     const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
     ft_matrices(c, p, true, form != 4);
@@ -1183,7 +1195,11 @@ static int ft_undirected(cge_ctx *c, cge_fit_problem &p, int form, double eps, d
     fit.delta = delta;
     fit.persistent = form == 3 || form == 4 || (form == 0 && persistent_wanted(c, N));
     cge_fit_fused ff{};
-    if (epi) { ff = *epi; ff.partial = nullptr; } // (else no partial, no auc_part: nothing is wanted of the epilogue)
+    if (epi) { // (else no partial, no auc_part: nothing is wanted of the epilogue)
+        ff = *epi;
+        if (!(epi_want & 1)) ff.partial = nullptr;
+        if (!(epi_want & 2)) ff.auc_part = nullptr;
+    }
     ff.Lh = c->sw_Lh.p; ff.Ll = c->sw_Ll.p; ff.alpha = p.alpha;
     AlphaSlot sl;
     fit_undirected(c, N, dw.p, Tld, p.alpha, true, form == 2, form == 4 ? &ff : nullptr, form == 4 ? epi_dev : nullptr, fit, sl);
@@ -1255,14 +1271,45 @@ static int ft_directed(cge_ctx *c, cge_fit_problem &p, int form, double eps, dou
     return ran;
 }
 
-// form 5: every problem with its own logarithm, T, weights and flags, as the members of a batch keep them (batch_host.cpp)
+// A member of a shared undirected launch with its own logarithm, T and weights, as the members of a batch keep them
+// (batch_host.cpp), and its entry of the launch's table: T_0 (zero beyond N), then the result (NaN until written)
+struct FtMember {
+    DevBuf<double> Lh, T, w;
+    DevBuf<float> Ll;
+};
+static cge_flow_problem ft_member(cge_ctx *c, const cge_fit_problem &p, const FlowGeometry &geo, FtMember &m, int *flags,
+                                  const cge_fit_fused *epi, int want) {
+    hipStream_t st = c->stream;
+    const i64 N = p.N, Tld = (i64)geo.Nt * 64;
+    ft_matrices(c, p, true, false);
+    k_pow_prepare(c, c->sw_D.p, N, true, true);
+    HIP_CHECK(hipStreamSynchronize(st));
+    m.Lh.swap(c->sw_Lh); m.Ll.swap(c->sw_Ll);
+    c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the member)
+    m.T.ensure((size_t)2 * Tld);
+    m.w.ensure(N);
+    const std::vector<double> nan_n(N, std::nan(""));
+    HIP_CHECK(hipMemsetAsync(m.T.p, 0, sizeof(double) * 2 * Tld, st));
+    HIP_CHECK(hipMemcpyAsync(m.T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.T.p + Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.w.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return flow_problem_entry(m.Lh.p, m.Ll.p, p.alpha, epi, want, m.T.p, m.T.p + Tld, m.w.p, flags, N, Tld, geo);
+}
+// the members' verdicts and iterates of a shared launch
+static void ft_multi_collect(cge_ctx *c, cge_fit_problem *probs, int n, const cge_flow_multi &tab) {
+    for (int i = 0; i < n; i++) {
+        cge_fit_problem &p = probs[i];
+        p.status = ft_verdict(c, tab.p[i].flags, &p.iters) ? 0 : 1;
+        HIP_CHECK(hipMemcpyAsync(p.T, tab.p[i].Tout, sizeof(double) * p.N, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+// form 5: every problem with slots and flags of its own; nothing is wanted of the epilogue
 static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const FlowGeometry *geo, double eps, double delta) {
     hipStream_t st = c->stream;
-    struct Member {
-        DevBuf<double> Lh, T, w;
-        DevBuf<float> Ll;
-    };
-    std::vector<std::unique_ptr<Member>> mem;
+    std::vector<std::unique_ptr<FtMember>> mem;
     DevBuf<int> flags;
     DevBuf<double> flow;
     flags.ensure((size_t)4 * n);
@@ -1270,37 +1317,11 @@ static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const FlowGeomet
     cge_flow_multi tab{};
     tab.n = n;
     for (int i = 0; i < n; i++) {
-        cge_fit_problem &p = probs[i];
-        const i64 N = p.N, Tld = (i64)geo[i].Nt * 64;
-        mem.emplace_back(new Member());
-        Member &m = *mem.back();
-        ft_matrices(c, p, true, false);
-        k_pow_prepare(c, c->sw_D.p, N, true, true);
-        HIP_CHECK(hipStreamSynchronize(st));
-        m.Lh.swap(c->sw_Lh); m.Ll.swap(c->sw_Ll);
-        c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the member)
-        m.T.ensure((size_t)2 * Tld); // T_0 (zero beyond N), then the result (NaN until written)
-        m.w.ensure(N);
-        const std::vector<double> nan_n(N, std::nan(""));
-        HIP_CHECK(hipMemsetAsync(m.T.p, 0, sizeof(double) * 2 * Tld, st));
-        HIP_CHECK(hipMemcpyAsync(m.T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(m.T.p + Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(m.w.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        cge_flow_problem &q = tab.p[i];
-        q.Lh = m.Lh.p; q.Ll = m.Ll.p; q.alpha = p.alpha;
-        q.epi = nullptr; q.want = 0;
-        q.T0 = m.T.p; q.Tout = m.T.p + Tld; q.w = m.w.p;
-        q.flags = flags.p + 4 * i;
-        q.N = N; q.Tld = Tld; q.Nt = geo[i].Nt; q.G = geo[i].G;
+        mem.emplace_back(new FtMember());
+        tab.p[i] = ft_member(c, probs[i], geo[i], *mem.back(), flags.p + 4 * i, nullptr, 0);
     }
     k_fit_flow_multi(c, tab, geo[0].NW, eps, delta, flow);
-    for (int i = 0; i < n; i++) {
-        cge_fit_problem &p = probs[i];
-        p.status = ft_verdict(c, flags.p + 4 * i, &p.iters) ? 0 : 1;
-        HIP_CHECK(hipMemcpyAsync(p.T, tab.p[i].Tout, sizeof(double) * p.N, hipMemcpyDeviceToHost, st));
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
+    ft_multi_collect(c, probs, n, tab);
 }
 
 // form 6: every problem with its own power matrix, Tin / Tout, degrees and flags, as the directed members of a batch keep them
@@ -1392,15 +1413,7 @@ void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int 
     *form_ran = form;
 }
 
-// ---- the testing hook of the local score (include/cge_hip_testing.h: cge_local_score_test) -----------------------------------
-// The stages of the local score on the buffers a sweep keeps them in (the first DevSamples of the context): the device sampler,
-// k_prep_samples, sampled_pair_dist and the tallies -- k_auc_landmark / k_auc_exact, or the epilogue of the fused fit through
-// fused_tables and ft_undirected.  Every check comes before the first launch.
-static void ls_range(const char *what, const i32 *v, i64 cnt, i64 lim) {
-    for (i64 k = 0; k < cnt; k++)
-        if (v[k] < 0 || v[k] >= lim)
-            CGE_THROW(CGE_E_ARG, "local_score_test: %s[%lld] = %d outside 0..%lld", what, (long long)k, (int)v[k], (long long)(lim - 1));
-}
+// host <-> device copies of the hooks below on the context's stream (down: a NULL host pointer is not copied)
 template <class T>
 static void ls_up(cge_ctx *c, DevBuf<T> &dev, const T *host, i64 cnt) {
     dev.ensure((size_t)cnt);
@@ -1409,6 +1422,242 @@ static void ls_up(cge_ctx *c, DevBuf<T> &dev, const T *host, i64 cnt) {
 template <class T>
 static void ls_down(cge_ctx *c, T *host, const T *dev, i64 cnt) {
     if (host) HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(T) * cnt, hipMemcpyDeviceToHost, c->stream));
+}
+
+// ---- the testing hook of the fused chain (include/cge_hip_testing.h: cge_fused_chain_test) -----------------------------------
+// One alpha as enqueue_alpha / host_batch_sweep run it on the fused path, on a caller's problem: the layout and its tables, the
+// epilogue's table, the fit with its epilogue's outputs wanted, the bins and the divergence.  A problem is prepared on the
+// context's buffers, as a sweep prepares it; the problems of a shared launch then take them along (FcMember), as hand_off does.
+namespace {
+struct FcOptions { // the options that decide whether a layout is the fused one, as the hook sets them; restored on the way out
+    cge_ctx *c;
+    int fused, plain, persistent;
+    bool relabel;
+    explicit FcOptions(cge_ctx *c_)
+        : c(c_), fused(c_->opt_fit_fused), plain(c_->opt_test_bvec_plain), persistent(c_->opt_fit_persistent), relabel(c_->opt_exact_relabel) {}
+    ~FcOptions() { c->opt_fit_fused = fused; c->opt_test_bvec_plain = plain; c->opt_fit_persistent = persistent; c->opt_exact_relabel = relabel; }
+};
+struct FcMember {
+    std::vector<i32> order;                  // the layout's order: the caller's vertex at each position of the sweep's numbering
+    std::vector<double> D, w, T0, T;         // the problem in the sweep's numbering
+    i64 bt_total = 0, vlen = 0;
+    cge_fit_fused epi{};                     // the host copy of the epilogue's table
+    DevBuf<i32> comm, aidx, fc, ns, base, cm_off; // (fc .. cm_off: a shared launch's members take the context's along)
+    DevBuf<double> afac, dpos, dneg, wts, apw, part, scal, vB, vC, fpart, jspart;
+    DevBuf<char> epi_dev;
+    FtMember fit;
+};
+} // namespace
+
+// The layout, the tables and the epilogue's table of one problem, on the context.  Every refusal of the layout comes first.
+static void fc_prepare(cge_ctx *c, const cge_fused_chain_problem &p, FcMember &m, bool shared) {
+    hipStream_t st = c->stream;
+    const i64 N = p.N, C = p.C, Nt = (N + 63) / 64, S = (p.want & 2) ? p.S : 0;
+    std::vector<i32> hcomm(N);
+    for (i64 i = 0; i < N; i++) {
+        if (p.comm[i] < 1 || p.comm[i] > C) CGE_THROW(CGE_E_ARG, "fused_chain_test: community id out of range");
+        hcomm[i] = (i32)(p.comm[i] - 1);
+    }
+    SweepLayout lay;
+    layout_tables(c, hcomm.data(), N, C, 0, true, false, lay);
+    if (!c->bvec_blocks)
+        CGE_THROW(CGE_E_ARG, "fused_chain_test: the tiles decline this layout (more than 64 community ids in a 64-vertex block)");
+    if (!lay.fuse)
+        CGE_THROW(CGE_E_ARG, "fused_chain_test: the fused form declines this layout (more than %d pieces in a 64-vertex block)", CGE_FLOW_NP);
+    if (p.partials && p.partials_cap < lay.bt_total)
+        CGE_THROW(CGE_E_ARG, "fused_chain_test: partials holds %lld doubles, the layout has %lld tile partials", (long long)p.partials_cap,
+                  (long long)lay.bt_total);
+    m.bt_total = lay.bt_total;
+    m.vlen = packed_len(C);
+    m.order = lay.cm_mem;
+    const std::vector<i32> &order = m.order;
+    std::vector<i32> old2new(N), comm_new(N);
+    m.D.resize((size_t)N * N); m.w.resize(N); m.T0.resize(N); m.T.assign(N, std::nan(""));
+    for (i64 q = 0; q < N; q++) {
+        const i64 a = order[q];
+        old2new[a] = (i32)q;
+        comm_new[q] = hcomm[a];
+        m.w[q] = p.w[a]; m.T0[q] = p.T0[a];
+        double *dst = m.D.data() + q * N;
+        for (i64 r = 0; r < N; r++) dst[r] = p.D[a * N + order[r]];
+    }
+    for (i64 q = 0; q < N; q++) lay.cm_mem[q] = (i32)q; // the member lists in the new numbering, as plan_layout leaves them
+    m.comm.ensure(N);
+    HIP_CHECK(hipMemcpyAsync(m.comm.p, comm_new.data(), sizeof(i32) * N, hipMemcpyHostToDevice, st));
+    WordPacker pk(c);
+    std::vector<i32> cm_pos;
+    community_tables(c, lay, N, C, pk, cm_pos);
+    pk.flush();
+    k_bins_prepare(c, c->sw_cm_off.p, N, C, lay.bt_total);
+    HIP_CHECK(hipMemsetAsync(c->sw_bt_part.p, 0xFF, sizeof(double) * lay.bt_total, st)); // (all bits set: a NaN where nothing writes)
+    ls_down(c, p.fc, c->sw_bt_fc.p, Nt);
+    ls_down(c, p.ns, c->sw_bt_ns.p, Nt);
+    ls_down(c, p.base, c->sw_bt_base.p, Nt * Nt);
+    // the tally's operands: the caller's, T's indices through old2new
+    if (S > 0) {
+        std::vector<i32> ax((size_t)4 * S);
+        for (i64 k = 0; k < 4 * S; k++) ax[k] = old2new[p.aidx[k]];
+        ls_up(c, m.aidx, ax.data(), 4 * S);
+        m.afac.ensure((size_t)8 * S + CGE_PARTIAL_BLOCKS); // (the blocks' weight sums behind the factors, as fused_tables keeps them)
+        HIP_CHECK(hipMemcpyAsync(m.afac.p, p.afac, sizeof(double) * 8 * S, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(m.afac.p + 8 * S, p.aden, sizeof(double) * CGE_PARTIAL_BLOCKS, hipMemcpyHostToDevice, st));
+        ls_up(c, m.dpos, p.dpos, S);
+        ls_up(c, m.dneg, p.dneg, S);
+        ls_up(c, m.wts, p.wts, S);
+        m.apw.ensure((size_t)2 * S);
+        HIP_CHECK(hipMemsetAsync(m.apw.p, 0xFF, sizeof(double) * 2 * S, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // (ax goes out of scope)
+    }
+    c->sw_scal.ensure(RES_STRIDE);
+    m.epi = fused_entry(c, m.comm.p, S, m.dpos.p, m.dneg.p, m.wts.p);
+    if (S > 0) { m.epi.aidx = m.aidx.p; m.epi.afac = m.afac.p; m.epi.aden = m.afac.p + 8 * S; m.epi.apw = m.apw.p; }
+    if (shared) { // the tables and the tallies' place leave the context with the member
+        m.scal.ensure(2 * CGE_PARTIAL_BLOCKS);
+        m.epi.auc_part = m.scal.p;
+        HIP_CHECK(hipStreamSynchronize(st));
+        m.fc.swap(c->sw_bt_fc); m.ns.swap(c->sw_bt_ns); m.base.swap(c->sw_bt_base); m.part.swap(c->sw_bt_part); m.cm_off.swap(c->sw_cm_off);
+        m.epi_dev.ensure(sizeof(cge_fit_fused));
+        HIP_CHECK(hipMemcpyAsync(m.epi_dev.p, &m.epi, sizeof(cge_fit_fused), hipMemcpyHostToDevice, st));
+    } else
+        fused_upload(c, std::vector<cge_fit_fused>(1, m.epi));
+    HIP_CHECK(hipMemsetAsync(m.epi.auc_part, 0xFF, sizeof(double) * 2 * CGE_PARTIAL_BLOCKS, st)); // (NaN until the epilogue writes)
+    // vect_B with its guard of NaNs behind it, and vect_C (zeros where the caller has none)
+    std::vector<double> hv((size_t)(m.vlen + CGE_VECT_B_GUARD), std::nan("")), hc((size_t)m.vlen, 0.0);
+    if (p.vC) std::memcpy(hc.data(), p.vC, sizeof(double) * m.vlen);
+    ls_up(c, m.vB, hv.data(), (i64)hv.size());
+    ls_up(c, m.vC, hc.data(), m.vlen);
+    m.fpart.ensure((size_t)2 * CGE_PARTIAL_BLOCKS);
+    HIP_CHECK(hipStreamSynchronize(st)); // (the host copies go out of scope)
+}
+
+// what a problem's launch left: the iterate in the caller's numbering, the tile partials (before the bins), the tallies, the powers
+static void fc_collect(cge_ctx *c, cge_fused_chain_problem &p, FcMember &m, const double *partial) {
+    const i64 S = (p.want & 2) ? p.S : 0;
+    for (i64 q = 0; q < p.N; q++) p.T[m.order[q]] = m.T[q];
+    if (p.order) std::memcpy(p.order, m.order.data(), sizeof(i32) * p.N);
+    p.bt_total = m.bt_total;
+    ls_down(c, p.partials, partial, m.bt_total);
+    ls_down(c, p.part, m.epi.auc_part, 2 * CGE_PARTIAL_BLOCKS);
+    if (S > 0) ls_down(c, p.apw, m.apw.p, 2 * S);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+void host_fused_chain_test(cge_ctx *c, cge_fused_chain_problem *probs, int n, double eps, double delta) {
+    hipStream_t st = c->stream;
+    // ---- the checks that need no layout ------------------------------------------------------------------------------------------
+    if (n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ARG, "fused_chain_test: a launch takes at most %d problems", CGE_BATCH_MAX);
+    if (!(eps > 0.0) || !(delta >= 0.0)) CGE_THROW(CGE_E_ARG, "fused_chain_test: eps > 0 and delta >= 0");
+    if (!c->opt_pow_exp2)
+        CGE_THROW(CGE_E_ARG, "fused_chain_test: the fused fit makes its power matrix from the stored logarithm (option pow_exp2)");
+    if (c->fit_persistent_broken) CGE_THROW(CGE_E_ARG, "fused_chain_test: this context gave the persistent fit up");
+    FlowGeometry geo[CGE_BATCH_MAX];
+    const int cus = device_cus();
+    int sumG = 0;
+    for (int i = 0; i < n; i++) {
+        const cge_fused_chain_problem &p = probs[i];
+        if (!p.D || !p.w || !p.T0 || !p.comm || !p.T) CGE_THROW(CGE_E_ARG, "fused_chain_test: empty problem");
+        if (p.N < 256 || p.C < 2)
+            CGE_THROW(CGE_E_ARG, "fused_chain_test: the tiles need 256 vertices and 2 communities (N = %lld, C = %lld)", (long long)p.N, (long long)p.C);
+        if ((double)p.N * (double)p.C > 1e9) CGE_THROW(CGE_E_ARG, "fused_chain_test: problem too large");
+        if (p.want < 1 || p.want > 3) CGE_THROW(CGE_E_ARG, "fused_chain_test: want = %d (bit 0 vect_B's partials, bit 1 the tallies)", (int)p.want);
+        if (p.n_modes < 1 || p.n_modes > 2) CGE_THROW(CGE_E_ARG, "fused_chain_test: n_modes = %d", (int)p.n_modes);
+        if (p.vC && !p.js_fused) CGE_THROW(CGE_E_ARG, "fused_chain_test: vC without js_fused");
+        if (p.want & 2) {
+            if (p.S < 1 || p.S > 65535) CGE_THROW(CGE_E_ARG, "fused_chain_test: S = %lld samples (1 .. 65535)", (long long)p.S);
+            if (!p.aidx || !p.afac || !p.aden || !p.dpos || !p.dneg || !p.wts)
+                CGE_THROW(CGE_E_ARG, "fused_chain_test: the tallies take aidx, afac, aden, dpos, dneg and wts");
+            for (i64 k = 0; k < 4 * p.S; k++)
+                if (p.aidx[k] < 0 || p.aidx[k] >= p.N)
+                    CGE_THROW(CGE_E_ARG, "fused_chain_test: aidx[%lld] = %d outside 0..%lld", (long long)k, (int)p.aidx[k], (long long)(p.N - 1));
+        }
+        if (!(flow_geometry(p.N, cus, &geo[i]) && geo[i].fused()))
+            CGE_THROW(CGE_E_ARG, "fused_chain_test: the geometry of the fused persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
+        if (geo[i].NW != geo[0].NW)
+            CGE_THROW(CGE_E_ARG, "fused_chain_test: a launch takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", i,
+                      geo[i].NW, geo[0].NW);
+        sumG += geo[i].G;
+    }
+    if (n > 1 && sumG > cus)
+        CGE_THROW(CGE_E_ARG, "fused_chain_test: the problems need %d workgroups in all, the device has %d CUs", sumG, cus);
+    if (n > 1 && !k_fit_flow_multi_fits(geo[0].NW, false))
+        CGE_THROW(CGE_E_ARG, "fused_chain_test: fit_flow_multi_kernel of %d waves gets no workgroup on a CU", geo[0].NW);
+    FcOptions restore(c);
+    c->opt_fit_fused = 1; c->opt_exact_relabel = true; c->opt_test_bvec_plain = 0;
+    if (c->opt_fit_persistent == 1) c->opt_fit_persistent = 0;
+    std::vector<std::unique_ptr<FcMember>> mem;
+    if (n == 1) { // ---- fit_flow_kernel<.., true>, as enqueue_alpha launches it, then bins_js_kernel -------------------------------
+        cge_fused_chain_problem &p = probs[0];
+        mem.emplace_back(new FcMember());
+        FcMember &m = *mem.back();
+        fc_prepare(c, p, m, false);
+        cge_fit_problem fp{};
+        fp.D = m.D.data(); fp.w = m.w.data(); fp.T0 = m.T0.data(); fp.T = m.T.data(); fp.N = p.N; fp.alpha = p.alpha;
+        ft_undirected(c, fp, 4, eps, delta, &m.epi, reinterpret_cast<const cge_fit_fused *>(c->sw_fused_epi.p), p.want);
+        p.iters = fp.iters;
+        p.status = fp.status;
+        fc_collect(c, p, m, c->sw_bt_part.p);
+        if ((p.want & 1) && p.status == 0) k_bins_js(c, c->sw_cm_off.p, p.N, p.C, m.vC.p, m.vB.p, p.n_modes, m.fpart.p);
+    } else { // ---- fit_flow_multi_kernel over the members, then the batch's bins / JS launches ------------------------------------------
+        DevBuf<int> flags;
+        DevBuf<double> flow;
+        flags.ensure((size_t)4 * n);
+        HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4 * n, st));
+        cge_flow_multi tab{};
+        tab.n = n;
+        std::vector<cge_fit_problem> fps(n);
+        for (int i = 0; i < n; i++) {
+            const cge_fused_chain_problem &p = probs[i];
+            mem.emplace_back(new FcMember());
+            FcMember &m = *mem.back();
+            fc_prepare(c, p, m, true);
+            cge_fit_problem &fp = fps[i];
+            fp = cge_fit_problem{};
+            fp.D = m.D.data(); fp.w = m.w.data(); fp.T0 = m.T0.data(); fp.T = m.T.data(); fp.N = p.N; fp.alpha = p.alpha;
+            tab.p[i] = ft_member(c, fp, geo[i], m.fit, flags.p + 4 * i, reinterpret_cast<const cge_fit_fused *>(m.epi_dev.p), p.want);
+        }
+        k_fit_flow_multi(c, tab, geo[0].NW, eps, delta, flow);
+        ft_multi_collect(c, fps.data(), n, tab);
+        cge_bins_multi bins{};
+        cge_js_multi js{};
+        int nb = 0, nj = 0;
+        i64 maxC = 0;
+        for (int i = 0; i < n; i++) {
+            cge_fused_chain_problem &p = probs[i];
+            FcMember &m = *mem[i];
+            p.iters = fps[i].iters;
+            p.status = fps[i].status;
+            fc_collect(c, p, m, m.part.p);
+            if (!((p.want & 1) && p.status == 0)) continue;
+            bins.p[nb++] = cge_bins_problem{m.part.p, m.cm_off.p, m.fc.p, m.ns.p, m.base.p, p.C, geo[i].Nt, 0, m.vB.p};
+            maxC = std::max(maxC, p.C);
+            m.jspart.ensure((size_t)2 * 3 * CGE_PARTIAL_BLOCKS);
+            for (int u = 0; u < p.n_modes; u++, nj++)
+                js.p[nj] = cge_js_problem{m.vC.p, m.vB.p, m.vlen, p.C, p.n_modes == 1 ? 0 : 1 + u, 0, m.jspart.p + (i64)u * 3 * CGE_PARTIAL_BLOCKS,
+                                          m.fpart.p + (i64)u * CGE_PARTIAL_BLOCKS};
+        }
+        k_bins_js_multi(c, bins, nb, maxC, js, nj);
+    }
+    for (int i = 0; i < n; i++) {
+        cge_fused_chain_problem &p = probs[i];
+        FcMember &m = *mem[i];
+        std::vector<double> hf((size_t)2 * CGE_PARTIAL_BLOCKS, std::nan(""));
+        const bool binned = (p.want & 1) && p.status == 0;
+        if (binned) ls_down(c, hf.data(), m.fpart.p, 2 * CGE_PARTIAL_BLOCKS);
+        ls_down(c, p.vectB, m.vB.p, m.vlen + CGE_VECT_B_GUARD);
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (p.vC)
+            for (int u = 0; u < p.n_modes; u++) p.js_fused[u] = binned ? vb_fold(hf.data() + (i64)u * CGE_PARTIAL_BLOCKS) : std::nan("");
+    }
+}
+
+// ---- the testing hook of the local score (include/cge_hip_testing.h: cge_local_score_test) -----------------------------------
+// The stages of the local score on the buffers a sweep keeps them in (the first DevSamples of the context): the device sampler,
+// k_prep_samples, sampled_pair_dist and the tallies -- k_auc_landmark / k_auc_exact, or the epilogue of the fused fit through
+// fused_tables and ft_undirected.  Every check comes before the first launch.
+static void ls_range(const char *what, const i32 *v, i64 cnt, i64 lim) {
+    for (i64 k = 0; k < cnt; k++)
+        if (v[k] < 0 || v[k] >= lim)
+            CGE_THROW(CGE_E_ARG, "local_score_test: %s[%lld] = %d outside 0..%lld", what, (long long)k, (int)v[k], (long long)(lim - 1));
 }
 
 void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {

@@ -137,7 +137,9 @@ int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method
  *      p2 is read by this form only).  *form_ran = the form that ran.  A relabelled form permutes GD, Ta, Tb and comm by the
  *      layout's order on the host, as the sweep computes GD from permuted rows.
  * CGE_E_ARG, with a message and before any launch, where the form does not apply: form 1 with N > 8192; forms 4-6 with
- * N < 256, C < 2 or more than 64 community ids in a 64-vertex block of the relabelled graph; forms 5, 6 directed. */
+ * N < 256, C < 2 or more than 64 community ids in a 64-vertex block of the relabelled graph; forms 5, 6 directed.
+ * Not covered here: forms 4-6 make the tile partials by bvec_tile_kernel on a supplied GD; the partials a landmark-mode sweep gets
+ * from the epilogue of its fused fit are cge_fused_chain_test's. */
 #define CGE_VECT_B_GUARD 64
 typedef struct cge_vect_b_problem {
     const double *GD, *Ta, *Tb;
@@ -182,7 +184,9 @@ int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_pro
  * CGE_E_ARG, with a message and before any launch, where a form does not apply: forms 3-6 where the geometry of the persistent
  * fit declines N on this device; forms 2, 4, 5 directed; form 6 undirected; forms 4, 5 without "pow_exp2"; forms 5, 6 with
  * problems of different waves per workgroup, more workgroups in all than the device has CUs or more than 16 problems; form 6
- * with a problem whose workgroups would reduce two quarter blocks each (the multi kernel exists for one). */
+ * with a problem whose workgroups would reduce two quarter blocks each (the multi kernel exists for one).
+ * Not covered here: forms 4 and 5 ask nothing of the fused launch's epilogue; its vect_B half and the tallies beside it are
+ * cge_fused_chain_test's. */
 typedef struct cge_fit_problem {
     const double *D, *w, *w2, *T0, *T0b;
     double *T, *Tb, *GD;
@@ -227,7 +231,9 @@ int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int direc
  * rounds; the context stays usable.
  * Not covered here: the exchange variants of options shard_rows / shard_ingest (pair_dist_rows_kernel, prep_*_sharded_kernel,
  * check_neg_flag_kernel) need a communicator and stay with tests/test_gpu_two_ranks.py; the multi-problem launch shares the
- * epilogue body and tests/test_gpu_batch.py holds its members to the single launch bit for bit. */
+ * epilogue body and tests/test_gpu_batch.py holds its members to the single launch bit for bit; form 4 asks for the tally alone
+ * -- the epilogue's vect_B, alone or beside the tally, and the multi-problem launch on supplied operands are
+ * cge_fused_chain_test's. */
 typedef struct cge_local_score_io {
     int64_t S, seed, stream_id;
     int32_t directed, draw_route, form, pad;
@@ -260,6 +266,53 @@ typedef struct cge_local_score_io {
     int32_t status, pad2;
 } cge_local_score_io;
 int cge_local_score_test(void *ctx, cge_local_score_io *io);
+/* kernel-level hook (needs the GPU): ONE alpha of the fused chain of an undirected landmark-mode sweep on a caller's problem -- the
+ * launch of fit_flow_kernel<.., FUSED = true> (one problem) or fit_flow_multi_kernel (2 .. 16 problems) with its epilogue's
+ * outputs wanted, then the bins and the divergence -- through the sweep's own functions: layout_tables (landmarks), community_tables,
+ * k_bins_prepare, the epilogue table of fused_tables, k_pow_prepare (blocked), fit_undirected / the shared launch's table entry and
+ * k_fit_flow_multi, k_bins_js / k_bins_js_multi.  So a test sees the tile partials themselves, bin by bin, not a score.
+ *   A problem, in: D (N x N, row-major, symmetric, values in [0, 1]), w, T0 (N), alpha; comm (N ids in 1..C, any vertex order, ids
+ *   without a member allowed); want (bit 0: vect_B's tile partials, bit 1: the tallies); vC (optional, packed C (C + 1) / 2) with
+ *   n_modes (1: all bins; 2: internal, external).  With want bit 1 the prepared operands of the tally, as k_auc_prepare leaves
+ *   them but the caller's: S in 1..65535, aidx[4 S] = indices into T in the caller's numbering (mapped through the layout's
+ *   old2new here), afac[8 S], aden[64], dpos[S], dneg[S], wts[S].  D, w, T0 and comm are permuted by the layout's order on the
+ *   host, as cge_vect_b_test permutes GD.  eps, delta: the step and the stopping threshold of every problem.
+ *   Out: T[N] = the iterate the launch left, in the caller's numbering (NaN after an abandoned launch); iters; status (1: the
+ *   launch was abandoned); order[N] = the layout's order (the 0-based vertex at each position of the sweep's numbering); the tile
+ *   tables as the device holds them, fc[Nt], ns[Nt], base[Nt Nt], and bt_total; partials[bt_total] (partials_cap = the doubles
+ *   the caller's array holds) copied out after the fit and before the bins -- [0, bt_total) is filled with NaN after
+ *   k_bins_prepare and before the launch, so a partial nothing wrote stays NaN; vectB = the packed vector followed by
+ *   CGE_VECT_B_GUARD doubles that sat behind it on the device and must still be NaN (want bit 0 of a converged launch; else all
+ *   NaN); js_fused[n_modes] (with vC) = the block partials added in block order, then halved, as the sweep's host does;
+ *   part[2 x 64] = the block tallies {num, den} (NaN unless the epilogue wrote them); apw[2 S] = the two powers per sample the
+ *   launch's prologue made.  Every output pointer but T may be NULL.
+ * Options the hook sets on the context (fit_fused, exact_relabel, test_bvec_plain, fit_persistent) are restored on the way out.
+ * CGE_E_ARG with a message, before the fit is launched (the layout's refusals: behind the upload of its tables): a directed
+ * call; N < 256 or C < 2; a context without option "pow_exp2" or one that gave the persistent fit up; a size whose geometry is not
+ * that of the fused fit on this device; a layout that declines the tiles (more than 64 community ids in a 64-vertex block) or the
+ * fused form (more than CGE_FLOW_NP = 32 pieces in a block), the message says which; want == 0 or beyond 3; want bit 1 without
+ * its operands, S outside 1..65535 or an index outside 0..N-1; partials_cap below bt_total; several problems of different waves
+ * per workgroup, with more workgroups in all than the device has CUs, or more than 16 of them; eps <= 0 or delta < 0.
+ * Not covered here: the directed shared launch (cge_fit_test form 6), the tallies split over ranks and the packed exact sweep. */
+typedef struct cge_fused_chain_problem {
+    const double *D, *w, *T0;
+    const int64_t *comm;
+    int64_t N, C;
+    double alpha;
+    const double *vC;
+    int32_t want, n_modes;
+    int64_t S;
+    const int32_t *aidx;
+    const double *afac, *aden, *dpos, *dneg, *wts;
+    double *T;
+    int32_t *order, *fc, *ns, *base;
+    double *partials;
+    int64_t partials_cap, bt_total;
+    double *vectB, *js_fused, *part, *apw;
+    int64_t iters;
+    int32_t status, pad;
+} cge_fused_chain_problem;
+int cge_fused_chain_test(void *ctx, cge_fused_chain_problem *problems, int n_problems, int directed, double eps, double delta);
 /* kernel-level hook (needs the GPU): the packed form of an exact sweep (cge_hip.h, option "exact_packed") on a caller's
  * embedding, through the sweep's own launch wrappers -- the extrema pass (lo_hi[0], lo_hi[1] = extrema of D over j >= i with
  * diag on the diagonal, D never stored) and the generator of one alpha (distances, normalisation, power; pow_method 1 = exp2 of
