@@ -133,6 +133,21 @@ class LandmarkGraphIO(C.Structure):
                 ("form_ran", C.c_int32), ("rshift", C.c_int32), ("colbits", C.c_int32), ("pad", C.c_int32)]
 
 
+class SweepSetupIO(C.Structure):
+    """cge_sweep_setup_io (include/cge_hip_testing.h): the arguments of the testing hook cge_sweep_setup_test."""
+    _fields_ = [("emb", C.c_void_p), ("dist", C.c_void_p), ("vw", C.c_void_p), ("comm", C.c_void_p), ("N", C.c_int64),
+                ("d", C.c_int64), ("C", C.c_int64), ("directed", C.c_int32), ("landmarks", C.c_int32),
+                ("force_relabel", C.c_int32), ("log_form", C.c_int32), ("alpha", C.c_double), ("src", C.c_void_p),
+                ("dst", C.c_void_p), ("w", C.c_void_p), ("m", C.c_int64),
+                ("deg_out", C.c_void_p), ("deg_in", C.c_void_p), ("star", C.c_void_p),
+                ("order", C.c_void_p), ("old2new", C.c_void_p), ("comm_rl", C.c_void_p), ("cm_off", C.c_void_p),
+                ("cm_mem", C.c_void_p), ("cm_pos", C.c_void_p), ("emb_rl", C.c_void_p), ("vec_rl", C.c_void_p),
+                ("D_raw", C.c_void_p), ("lo_hi", C.c_void_p), ("D", C.c_void_p),
+                ("Lh", C.c_void_p), ("Ll", C.c_void_p), ("log_cap", C.c_int64), ("log_count", C.c_int64), ("GD", C.c_void_p),
+                ("T1", C.c_void_p), ("T2", C.c_void_p), ("TT", C.c_void_p), ("Tld", C.c_int64), ("relabel", C.c_int32),
+                ("log_form_ran", C.c_int32)]
+
+
 class LocalScoreIO(C.Structure):
     """cge_local_score_io (include/cge_hip_testing.h): the arguments of the testing hook cge_local_score_test."""
     _fields_ = [("S", C.c_int64), ("seed", C.c_int64), ("stream_id", C.c_int64), ("directed", C.c_int32),
@@ -1158,6 +1173,65 @@ class Context:
             o["vectB"], o["guard"] = o["vectB"][:ln], o["vectB"][ln:]
             o["js_fused"] = o["js_fused"][:int(q.n_modes)]
         return outs
+
+    def sweep_setup_test(self, emb, dist, comm, C_, vw=None, directed=False, landmarks=False, force_relabel=False, log_form=0,
+                         alpha=None, edges=None, want=("layout", "D_raw", "D", "log", "start")):
+        """Testing hook (include/cge_hip_testing.h: cge_sweep_setup_test): the set-up of an alpha sweep on the score graph emb
+        (N, d), dist (N,), comm (ids in 1..C_), optional vw -- no fit runs.  edges = (src, dst, w or None), 0-based: the
+        directed degree pass (a directed call needs it).  `want` names the stages whose outputs come back: "layout" (relabel,
+        order, old2new, emb_rl, vec_rl (4, N), comm_rl, cm_off, cm_mem, cm_pos), "D_raw", "D" (lo_hi, D), "log" (Lh, Ll,
+        log_form_ran, log_count), "start" (T1, T2, TT (3, Tld), Tld); the degrees (deg_out, deg_in, star) come with edges, GD with
+        alpha.  Arrays nothing wrote keep their fill: NaN, or -1 for the integers."""
+        emb, dist, comm = _f64(emb), _f64(dist), _i64(comm)
+        N, d = emb.shape
+        assert dist.shape == comm.shape == (N,)
+        io, out, keep = SweepSetupIO(), {}, [emb, dist, comm]
+        io.emb, io.dist, io.comm = emb.ctypes.data, dist.ctypes.data, comm.ctypes.data
+        io.N, io.d, io.C = N, d, int(C_)
+        io.directed, io.landmarks, io.force_relabel, io.log_form = int(bool(directed)), int(bool(landmarks)), int(bool(force_relabel)), int(log_form)
+
+        def give(key, a, dtype):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            keep.append(a)
+            setattr(io, key, a.ctypes.data)
+            return a
+
+        def ask(key, shape, dtype=np.float64):
+            out[key] = np.full(shape, -1 if dtype == np.int32 else np.nan, dtype=dtype)
+            setattr(io, key, out[key].ctypes.data)
+
+        if vw is not None:
+            assert give("vw", vw, np.float64).shape == (N,)
+        if edges is not None:
+            src = give("src", edges[0], np.int32)
+            assert give("dst", edges[1], np.int32).shape == src.shape and src.ndim == 1
+            if edges[2] is not None:
+                assert give("w", edges[2], np.float64).shape == src.shape
+            io.m = src.size
+            ask("deg_out", N), ask("deg_in", N), ask("star", N, np.int32)
+        n_out, Nt = max(N, 1), (max(N, 1) + 63) // 64
+        if "layout" in want:
+            for key in ("order", "old2new", "comm_rl", "cm_mem", "cm_pos"):
+                ask(key, n_out, np.int32)
+            ask("cm_off", max(int(C_), 0) + 1, np.int32), ask("emb_rl", (n_out, max(d, 1))), ask("vec_rl", (4, n_out))
+        if "D_raw" in want:
+            ask("D_raw", (n_out, n_out))
+        if "D" in want:
+            ask("lo_hi", 2), ask("D", (n_out, n_out))
+        if "log" in want:
+            io.log_cap = max(n_out * n_out, Nt * (Nt + 1) // 2 * 4096)
+            ask("Lh", io.log_cap), ask("Ll", io.log_cap, np.float32)
+        if alpha is not None:
+            io.alpha = float(alpha)
+            ask("GD", (n_out, n_out))
+        if "start" in want:
+            ask("T1", n_out), ask("T2", n_out), ask("TT", (3, 64 * Nt))
+        self._check(self.L.cge_sweep_setup_test(self.h, C.byref(io)))
+        out["relabel"], out["Tld"] = int(io.relabel), int(io.Tld)
+        if "log" in want:
+            out["log_form_ran"], out["log_count"] = int(io.log_form_ran), int(io.log_count)
+            out["Lh"], out["Ll"] = out["Lh"][:io.log_count], out["Ll"][:io.log_count]
+        return out
 
     def local_score_test(self, S, directed=False, draw=None, draws=None, pos2=None, pairs=None, prepare=False, hi=None,
                          distances=False, dists=None, tally=None):

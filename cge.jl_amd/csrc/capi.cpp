@@ -603,6 +603,15 @@ int cge_fused_chain_test(void *ctx, cge_fused_chain_problem *problems, int n_pro
     CGE_CATCH(c)
 }
 
+// testing hook (include/cge_hip_testing.h): the set-up of an alpha sweep -- degrees, layout, D, extrema, logarithm, start vectors
+int cge_sweep_setup_test(void *ctx, cge_sweep_setup_io *io) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !io) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_sweep_setup_test(c, io);
+    CGE_CATCH(c)
+}
+
 // testing hook (include/cge_hip_testing.h): the local score's sampler, prepared pairs, pair distances and tallies, stage by stage
 int cge_local_score_test(void *ctx, cge_local_score_io *io) {
     cge_ctx *c = (cge_ctx *)ctx;

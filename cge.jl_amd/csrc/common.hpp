@@ -1145,6 +1145,10 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io); // the testing h
 struct cge_vect_b_problem; // (include/cge_hip_testing.h)
 void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
                          double *GD);
+struct cge_sweep_setup_io; // (include/cge_hip_testing.h)
+void host_sweep_setup_test(cge_ctx *c, cge_sweep_setup_io *io); // the testing hook of the sweep's set-up (wgcl_host.cpp)
+// the directed degree pass of a score graph given as an edge list (score_host.cpp): c->s_degin / s_degout and the star counts
+void edge_degrees(cge_ctx *c, const i32 *src, const i32 *dst, const double *w, i64 m, i64 N, DevBuf<i32> &star);
 struct cge_fit_problem; // (include/cge_hip_testing.h)
 struct cge_fused_chain_problem; // (include/cge_hip_testing.h)
 void host_fused_chain_test(cge_ctx *c, cge_fused_chain_problem *probs, int n, double eps,

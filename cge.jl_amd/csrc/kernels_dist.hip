@@ -80,7 +80,12 @@ void k_dist_matrix(cge_ctx *c, const double *emb, const double *diag, i64 N, i64
     hipLaunchKernelGGL(dist_matrix_kernel, dim3(nb, nb), dim3(256), 0, c->stream, emb, diag, N, d, D);
 }
 
-// extrema over the upper triangle (incl. diagonal); two-stage, order independent (min/max are exact)
+// extrema over the upper triangle (incl. diagonal); two-stage, order independent (min/max are exact).
+// A NaN among the values makes both extrema NaN, as extrema() does (src/divergence.jl:92): fmin / fmax drop a NaN operand, so
+// the folds below keep one instead.  Any NaN becomes THE quiet NaN, so the two scalars stay the same bits in every order.
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
+__device__ __forceinline__ double min_nan(double a, double b) { return (a != a || b != b) ? quiet_nan() : fmin(a, b); }
+__device__ __forceinline__ double max_nan(double a, double b) { return (a != a || b != b) ? quiet_nan() : fmax(a, b); }
 __global__ void minmax_partial_kernel(const double *__restrict__ D, i64 N, double *__restrict__ part) {
     __shared__ double slo[256], shi[256];
     double lo = INFINITY, hi = -INFINITY;
@@ -89,8 +94,8 @@ __global__ void minmax_partial_kernel(const double *__restrict__ D, i64 N, doubl
         const i64 i = e / N, j = e - i * N;
         if (j >= i) {
             const double v = D[e];
-            lo = fmin(lo, v);
-            hi = fmax(hi, v);
+            lo = min_nan(lo, v);
+            hi = max_nan(hi, v);
         }
     }
     slo[threadIdx.x] = lo;
@@ -98,8 +103,8 @@ __global__ void minmax_partial_kernel(const double *__restrict__ D, i64 N, doubl
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) {
-            slo[threadIdx.x] = fmin(slo[threadIdx.x], slo[threadIdx.x + s]);
-            shi[threadIdx.x] = fmax(shi[threadIdx.x], shi[threadIdx.x + s]);
+            slo[threadIdx.x] = min_nan(slo[threadIdx.x], slo[threadIdx.x + s]);
+            shi[threadIdx.x] = max_nan(shi[threadIdx.x], shi[threadIdx.x + s]);
         }
         __syncthreads();
     }
@@ -112,16 +117,16 @@ __global__ void minmax_final_kernel(const double *__restrict__ part, int nb, dou
     __shared__ double slo[256], shi[256];
     double lo = INFINITY, hi = -INFINITY;
     for (int b = threadIdx.x; b < nb; b += 256) {
-        lo = fmin(lo, part[2 * b]);
-        hi = fmax(hi, part[2 * b + 1]);
+        lo = min_nan(lo, part[2 * b]);
+        hi = max_nan(hi, part[2 * b + 1]);
     }
     slo[threadIdx.x] = lo;
     shi[threadIdx.x] = hi;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) {
-            slo[threadIdx.x] = fmin(slo[threadIdx.x], slo[threadIdx.x + s]);
-            shi[threadIdx.x] = fmax(shi[threadIdx.x], shi[threadIdx.x + s]);
+            slo[threadIdx.x] = min_nan(slo[threadIdx.x], slo[threadIdx.x + s]);
+            shi[threadIdx.x] = max_nan(shi[threadIdx.x], shi[threadIdx.x + s]);
         }
         __syncthreads();
     }
@@ -150,8 +155,8 @@ void k_normalise(cge_ctx *c, double *D, i64 N, const double *lo_hi) {
 // ------------------------------------------------------------------------------------------------
 // The packed form of an exact sweep (wgcl_host.cpp): nothing N x N but the upper tiles of the current alpha's GD.
 // Extrema of D over j >= i (diagonal = diag, src/divergence.jl:92): the workgroups stride over the upper tiles, every thread keeps
-// the extrema of its elements, one (lo, hi) per workgroup; minmax_final_kernel folds them.  min / max are order-free, so the two
-// scalars carry the bits of k_minmax_upper on the stored matrix.
+// the extrema of its elements, one (lo, hi) per workgroup; minmax_final_kernel folds them.  min / max are order-free (a NaN
+// included: min_nan / max_nan above), so the two scalars carry the bits of k_minmax_upper on the stored matrix.
 #include "pow_parts.hpp"
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 #define PK_MM_BLOCKS 4096
@@ -173,8 +178,8 @@ __global__ __launch_bounds__(256) void packed_extrema_kernel(const double *__res
                 const i64 i = I * DT + ty * 4 + a, j = J * DT + tx * 4 + b;
                 if (i < N && j < N && j >= i) {
                     const double v = (i == j) ? diag[i] : sqrt(acc[a][b]);
-                    lo = fmin(lo, v);
-                    hi = fmax(hi, v);
+                    lo = min_nan(lo, v);
+                    hi = max_nan(hi, v);
                 }
             }
     }
@@ -183,8 +188,8 @@ __global__ __launch_bounds__(256) void packed_extrema_kernel(const double *__res
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) {
-            slo[threadIdx.x] = fmin(slo[threadIdx.x], slo[threadIdx.x + s]);
-            shi[threadIdx.x] = fmax(shi[threadIdx.x], shi[threadIdx.x + s]);
+            slo[threadIdx.x] = min_nan(slo[threadIdx.x], slo[threadIdx.x + s]);
+            shi[threadIdx.x] = max_nan(shi[threadIdx.x], shi[threadIdx.x + s]);
         }
         __syncthreads();
     }

@@ -8,7 +8,8 @@
 // GD = (1 - D)^alpha, forty times per score on the same D.  x^alpha = 2^(alpha * log2 x), and log2(1 - D) does not depend
 // on alpha: it is computed ONCE per score to ~70 bits (a double plus a float correction), and an alpha then costs one
 // exp2 of a double-double exponent per element instead of a full pow (which spends most of its time on that logarithm).
-// Accuracy: below one ulp (log2 to 2^-70, the product alpha*L exact through an fma residual, 2^f as 1 + f*ln2 + f^2*P(f)
+// Accuracy: below one ulp (log2 to 2^-70 -- tests/test_gpu_sweep_setup.py holds the stored parts to that bound against a
+// 60-digit reference; the largest error met there is 2^-70.64, just above sqrt(1/2) -- the product alpha*L exact through an fma residual, 2^f as 1 + f*ln2 + f^2*P(f)
 // with the leading term carried as hi + lo) -- the same class as the library pow this replaces (option "pow_exp2" = 0).
 struct dd_t { double h, l; };
 __device__ __forceinline__ dd_t two_sum(double a, double b) {

@@ -359,7 +359,8 @@ static ScoreGraph score_graph(i64 N, i64 d, i64 C, const double *emb, const doub
 }
 
 // the directed degree pass of a score graph given as an edge list: in- / out-degrees (c->s_degin / s_degout) and star counts
-static void edge_degrees(cge_ctx *c, const i32 *src, const i32 *dst, const double *w, i64 m, i64 N, DevBuf<i32> &star) {
+// (common.hpp: the testing hook cge_sweep_setup_test calls it too)
+void edge_degrees(cge_ctx *c, const i32 *src, const i32 *dst, const double *w, i64 m, i64 N, DevBuf<i32> &star) {
     hipStream_t st = c->stream;
     c->s_degin.ensure(N); c->s_degout.ensure(N); star.ensure(N);
     HIP_CHECK(hipMemsetAsync(c->s_degin.p, 0, sizeof(double) * N, st));

@@ -211,7 +211,9 @@ static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int direct
 }
 
 // The layout decision, the tile tables and the relabelled copies of the score graph's per-vertex arrays (G points at them then).
-static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay, bool packed_req) {
+// force_relabel: layout_tables' (the testing hook cge_sweep_setup_test; every sweep passes false).
+static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay, bool packed_req,
+                        bool force_relabel = false) {
     const i64 N = G.N, d = G.d;
     std::vector<i32> hcomm(N);
     if (orig && orig->h_lcomm) std::memcpy(hcomm.data(), orig->h_lcomm, sizeof(i32) * N); // (the caller read them back for the diameter)
@@ -219,7 +221,7 @@ static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int dir
         HIP_CHECK(hipMemcpyAsync(hcomm.data(), G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    layout_tables(c, hcomm.data(), N, G.C, directed, orig != nullptr, false, lay, packed_req);
+    layout_tables(c, hcomm.data(), N, G.C, directed, orig != nullptr, force_relabel, lay, packed_req);
     if (!lay.relabel) return;
     const DevBuf<i32> &d_order = c->sw_rl_order;
     std::vector<i32> &cm_mem = lay.cm_mem;
@@ -1860,6 +1862,138 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
         io->out2[0] = num;
         io->out2[1] = den;
     }
+}
+
+// ---- the testing hook of the sweep's set-up (include/cge_hip_testing.h: cge_sweep_setup_test) ------------------------------------
+// What host_wgcl_sweep does before its first alpha, on a caller's score graph and stage by stage: edge_degrees, plan_layout,
+// prepare_distances, k_pow_prepare, k_pow_matrix -- the sweep's own functions, on the buffers a host-array sweep keeps them in
+// (s_emb .. s_comm, s_degin / s_degout / s_star, sw_*, fp_T).  No fit runs.  Everything that can refuse does so before the first
+// launch, but the layout's own verdict on the tiles.
+void host_sweep_setup_test(cge_ctx *c, cge_sweep_setup_io *io) {
+    hipStream_t st = c->stream;
+    const i64 N = io->N, d = io->d, C = io->C, m = io->m;
+    const int directed = io->directed != 0, form = io->log_form;
+    const bool landmarks = io->landmarks != 0, edges = io->src || io->dst;
+    // the stages that run
+    const bool want_log = io->Lh || io->Ll, want_gd = io->GD != nullptr;
+    const bool want_prep = io->lo_hi || io->D || io->cm_off || io->cm_mem || io->cm_pos || io->T1 || io->T2 || io->TT || want_log || want_gd;
+    io->Tld = io->log_count = 0;
+    io->relabel = io->log_form_ran = 0;
+    // ---- the checks --------------------------------------------------------------------------------------------------------------
+    if (N < 1 || d < 1 || C < 1 || N > 46340) CGE_THROW(CGE_E_ARG, "sweep_setup_test: N = %lld, d = %lld, C = %lld", (long long)N, (long long)d, (long long)C);
+    if (!io->emb || !io->dist || !io->comm) CGE_THROW(CGE_E_ARG, "sweep_setup_test: emb, dist and comm are the score graph");
+    if (c->rows_sharded || c->edges_sharded || c->opt_shard_rows || c->opt_shard_ingest)
+        CGE_THROW(CGE_E_ARG, "sweep_setup_test: not with option shard_rows / shard_ingest (every row and edge on one rank)");
+    if (form < 0 || form > 3) CGE_THROW(CGE_E_ARG, "sweep_setup_test: log_form = %d (0 .. 3)", form);
+    if (form != 0 && !c->opt_pow_exp2) CGE_THROW(CGE_E_ARG, "sweep_setup_test: a stored logarithm needs option pow_exp2");
+    if (form == 3 && N < 256) CGE_THROW(CGE_E_ARG, "sweep_setup_test: the tile-blocked logarithm belongs to the fused fit, from 256 vertices on (N = %lld)", (long long)N);
+    if (want_log && (!io->Lh || !io->Ll)) CGE_THROW(CGE_E_ARG, "sweep_setup_test: Lh and Ll go together");
+    std::vector<i32> hcomm(N);
+    for (i64 i = 0; i < N; i++) {
+        if (io->comm[i] < 1 || io->comm[i] > C) CGE_THROW(CGE_E_ARG, "sweep_setup_test: community id out of range");
+        hcomm[i] = (i32)(io->comm[i] - 1);
+    }
+    if (edges && (!io->src || !io->dst || m < 1)) CGE_THROW(CGE_E_ARG, "sweep_setup_test: an edge list is src, dst and m >= 1");
+    if (directed && !edges) CGE_THROW(CGE_E_ARG, "sweep_setup_test: a directed sweep starts from the degrees of its edge list");
+    if ((io->deg_out || io->deg_in || io->star) && !edges) CGE_THROW(CGE_E_ARG, "sweep_setup_test: the degrees need the edge list");
+    for (i64 e = 0; edges && e < m; e++)
+        if (io->src[e] < 0 || io->src[e] >= N || io->dst[e] < 0 || io->dst[e] >= N)
+            CGE_THROW(CGE_E_ARG, "sweep_setup_test: edge %lld (%d, %d) outside 0..%lld", (long long)e, (int)io->src[e], (int)io->dst[e], (long long)(N - 1));
+    const i64 Nt = (N + 63) / 64, blocked_len = Nt * (Nt + 1) / 2 * 4096;
+    if (want_log && io->log_cap < (form == 3 ? blocked_len : form == 0 ? std::max(blocked_len, N * N) : N * N))
+        CGE_THROW(CGE_E_ARG, "sweep_setup_test: Lh / Ll hold %lld elements, the form may write more", (long long)io->log_cap);
+    // ---- the score graph on the device, as a host-array sweep holds it --------------------------------------------------------
+    c->s_emb.ensure((size_t)N * d); c->s_dist.ensure(N); c->s_comm.ensure(N);
+    HIP_CHECK(hipMemcpyAsync(c->s_emb.p, io->emb, sizeof(double) * N * d, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->s_dist.p, io->dist, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->s_comm.p, hcomm.data(), sizeof(i32) * N, hipMemcpyHostToDevice, st));
+    ScoreGraph G;
+    G.N = N; G.d = d; G.C = C;
+    G.emb = c->s_emb.p; G.dist = c->s_dist.p; G.comm = c->s_comm.p;
+    if (io->vw) {
+        c->s_vw.ensure(N);
+        HIP_CHECK(hipMemcpyAsync(c->s_vw.p, io->vw, sizeof(double) * N, hipMemcpyHostToDevice, st));
+        G.vw = c->s_vw.p;
+    }
+    // ---- the degrees (score_host.cpp: edge_degrees) ----------------------------------------------------------------------------
+    DevBuf<i32> e_src, e_dst;
+    DevBuf<double> e_w;
+    if (edges) {
+        e_src.ensure(m); e_dst.ensure(m);
+        HIP_CHECK(hipMemcpyAsync(e_src.p, io->src, sizeof(i32) * m, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(e_dst.p, io->dst, sizeof(i32) * m, hipMemcpyHostToDevice, st));
+        if (io->w) {
+            e_w.ensure(m);
+            HIP_CHECK(hipMemcpyAsync(e_w.p, io->w, sizeof(double) * m, hipMemcpyHostToDevice, st));
+        }
+        edge_degrees(c, e_src.p, e_dst.p, io->w ? e_w.p : nullptr, m, N, c->s_star);
+        G.deg_in = c->s_degin.p;
+        G.deg_out = c->s_degout.p;
+        if (io->deg_out) HIP_CHECK(hipMemcpyAsync(io->deg_out, c->s_degout.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        if (io->deg_in) HIP_CHECK(hipMemcpyAsync(io->deg_in, c->s_degin.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        if (io->star) HIP_CHECK(hipMemcpyAsync(io->star, c->s_star.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    // ---- the layout ----------------------------------------------------------------------------------------------------------------
+    c->sw_T1.ensure(N); c->sw_T2.ensure(N);
+    c->sw_lohi.ensure(2);
+    SweepLayout lay;
+    const OrigView orig{}; // (landmark mode: what the layout asks of it is that it is there)
+    plan_layout(c, G, landmarks ? &orig : nullptr, directed, lay, false, io->force_relabel != 0);
+    if (form == 3 && !c->bvec_blocks)
+        CGE_THROW(CGE_E_ARG, "sweep_setup_test: the tiles decline this layout (more than 64 community ids in a 64-vertex block, or no tile form for this sweep)");
+    io->relabel = lay.relabel;
+    if (lay.relabel) {
+        if (io->order) HIP_CHECK(hipMemcpyAsync(io->order, c->sw_rl_order.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+        if (io->old2new) HIP_CHECK(hipMemcpyAsync(io->old2new, lay.old2new.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+    }
+    if (io->emb_rl) HIP_CHECK(hipMemcpyAsync(io->emb_rl, G.emb, sizeof(double) * N * d, hipMemcpyDeviceToHost, st));
+    if (io->comm_rl) HIP_CHECK(hipMemcpyAsync(io->comm_rl, G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+    if (io->vec_rl) {
+        const double *vec[4] = {G.dist, G.vw, G.deg_in, G.deg_out};
+        for (int q = 0; q < 4; q++)
+            if (vec[q]) HIP_CHECK(hipMemcpyAsync(io->vec_rl + q * N, vec[q], sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    }
+    // ---- D, its extrema and normalisation, the community tables, the start vectors ------------------------------------------
+    if (io->D_raw || want_prep) { c->sw_D.ensure((size_t)N * N); c->sw_GD.ensure((size_t)N * N); }
+    if (io->D_raw) {
+        k_dist_matrix(c, G.emb, G.dist, N, d, c->sw_D.p);
+        HIP_CHECK(hipMemcpyAsync(io->D_raw, c->sw_D.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (!want_prep) return;
+    io->Tld = prepare_distances(c, G, lay, directed, false);
+    if (io->lo_hi) HIP_CHECK(hipMemcpyAsync(io->lo_hi, c->sw_lohi.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+    if (io->D) HIP_CHECK(hipMemcpyAsync(io->D, c->sw_D.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
+    if (io->cm_off) HIP_CHECK(hipMemcpyAsync(io->cm_off, c->sw_cm_off.p, sizeof(i32) * (C + 1), hipMemcpyDeviceToHost, st));
+    if (io->cm_mem) HIP_CHECK(hipMemcpyAsync(io->cm_mem, c->sw_cm_mem.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+    if (io->cm_pos) HIP_CHECK(hipMemcpyAsync(io->cm_pos, c->sw_cm_pos.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
+    if (io->T1) HIP_CHECK(hipMemcpyAsync(io->T1, c->sw_T1.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    if (io->T2) HIP_CHECK(hipMemcpyAsync(io->T2, c->sw_T2.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    if (io->TT) HIP_CHECK(hipMemcpyAsync(io->TT, c->fp_T.p, sizeof(double) * 3 * io->Tld, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (!want_log && !want_gd) return;
+    // ---- the logarithm, and the power of one alpha from it ------------------------------------------------------------------
+    const bool upper = form == 0 ? landmarks && !directed : form >= 2, blocked = form == 0 ? lay.fuse : form == 3;
+    const i64 len = blocked ? blocked_len : N * N;
+    if (c->opt_pow_exp2) { // (all bits set: a NaN in both; k_pow_prepare's own ensure finds them large enough)
+        c->sw_Lh.ensure((size_t)len); c->sw_Ll.ensure((size_t)len);
+        HIP_CHECK(hipMemsetAsync(c->sw_Lh.p, 0xFF, sizeof(double) * len, st));
+        HIP_CHECK(hipMemsetAsync(c->sw_Ll.p, 0xFF, sizeof(float) * len, st));
+    }
+    k_pow_prepare(c, c->sw_D.p, N, upper, blocked);
+    io->log_form_ran = c->pow_logs_blocked_N == N ? 3 : c->pow_logs_N != N ? 0 : c->pow_logs_upper ? 2 : 1;
+    io->log_count = io->log_form_ran == 0 ? 0 : len;
+    if (want_log && io->log_form_ran != 0) {
+        HIP_CHECK(hipMemcpyAsync(io->Lh, c->sw_Lh.p, sizeof(double) * len, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(io->Ll, c->sw_Ll.p, sizeof(float) * len, hipMemcpyDeviceToHost, st));
+    }
+    if (want_gd && io->log_form_ran != 3) {
+        HIP_CHECK(hipMemsetAsync(c->sw_GD.p, 0xFF, sizeof(double) * N * N, st)); // (as ft_matrices does)
+        k_pow_matrix(c, c->sw_D.p, N, io->alpha, c->sw_GD.p, upper);
+        HIP_CHECK(hipMemcpyAsync(io->GD, c->sw_GD.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // ---- the testing hook of the packed form (include/cge_hip_testing.h: cge_packed_gd_test) -------------------------------

@@ -322,6 +322,72 @@ int cge_fused_chain_test(void *ctx, cge_fused_chain_problem *problems, int n_pro
  * CGE_E_ASSERT when a tile element outside the matrix is not 0 */
 int cge_packed_gd_test(void *ctx, const double *emb /* N x d row-major, host */, const double *diag /* N */, int64_t N, int64_t d,
                        double alpha, int pow_method, double *lo_hi /* 2 */, double *GD /* N x N row-major, host */);
+/* kernel-level hook (needs the GPU): the SET-UP of an alpha sweep on a caller's score graph -- everything the per-alpha kernels
+ * read, made once per sweep -- through the sweep's own functions and launch wrappers: edge_degrees (k_edge_degrees, into the
+ * context's degree buffers), plan_layout (layout_tables, k_permute_rows, k_permute_i32), prepare_distances (k_dist_matrix,
+ * k_minmax_upper, k_normalise, community_tables, the start vectors and TT), k_pow_prepare and k_pow_matrix, on the buffers a sweep
+ * keeps them in.  The hook runs NO fit and no alpha.  A struct of optional stages: an output that is NULL is not copied out, and a
+ * stage none of whose outputs is wanted and that no later stage needs is not run (the layout always runs: every later stage
+ * reads it).
+ *   In: emb (N x d, row-major), dist (N, the diagonal of D), comm (N ids in 1..C, any order, ids without a member allowed), vw
+ *   (N, optional); directed; landmarks (a landmark-mode sweep: it decides the tile rule of the layout and whether form 0 keeps
+ *   the upper tiles only); force_relabel (as cge_vect_b_test form 3 passes it to the layout); log_form 0 = what a sweep of this
+ *   shape prepares, 1 = row-major whole, 2 = row-major upper tiles, 3 = tile-blocked; alpha (read when GD is wanted); an optional
+ *   directed edge list src, dst (m 0-based ids), w (NULL = unit weights).  A directed call needs the edge list: its degrees set
+ *   the start vectors.
+ *   Degrees (with an edge list): deg_out[N], deg_in[N], star[N] (the rows of the edge list a vertex appears in, a self-loop
+ *   twice).  This pass adds doubles with float atomics: for inexact weights its sums depend on the order the hardware serves the
+ *   adds in (any order of a vertex's k terms: within (k - 1) 2^-53 sum|w| of the exact sum), for unit and dyadic weights every
+ *   partial sum is exact and so is the result.  The line "no float atomics" at the top of kernels_fit.hip speaks of that file's
+ *   reductions; it extends neither to this pass nor to the scatters of the landmark graph.
+ *   Layout: relabel (0 / 1); order[N] and old2new[N] as the device holds them (written for a relabelled sweep only); emb_rl
+ *   [N x d], vec_rl[4][N] = dist, vw, deg_in, deg_out (each where given), comm_rl[N] (0-based) = the per-vertex arrays the sweep
+ *   goes on with -- the permuted copies, or the inputs themselves where the layout does not relabel; cm_off[C + 1], cm_mem[N],
+ *   cm_pos[N] = the community tables as the device holds them.
+ *   Distances: D_raw[N x N] = D as k_dist_matrix stores it (a launch of its own, before prepare_distances makes it again);
+ *   lo_hi[2]; D[N x N] after the normalisation.
+ *   The logarithm: Lh (doubles) and Ll (floats), log_cap elements each at the caller, in the layout that ran: log_form_ran (0:
+ *   none -- option "pow_exp2" is off or there is no room; nothing is copied) and log_count, its elements (N N row-major,
+ *   Nt (Nt + 1) / 2 x 4096 blocked).  Both device arrays hold NaN before the launch, so an element nothing wrote stays NaN.
+ *   GD[N x N] (optional) by k_pow_matrix at alpha from what was prepared (the upper tiles alone after form 2), NaN where nothing
+ *   was written; not written after form 3, which k_pow_matrix cannot read.
+ *   Start: T1[N], T2[N] (undirected: ones; directed: Tin, Tout -- zero where the in- / out-degree is); TT[3 Tld] with Tld =
+ *   64 ceil(N / 64): part 0 holds T1, everything else is zero.
+ * CGE_E_ARG with a message, before any launch: N outside 1..46340, d < 1 or C < 1, a missing emb / dist / comm, a community id outside 1..C, an edge
+ * endpoint outside 0..N-1, a directed call without edges, log_form outside 0..3, log_form 1-3 on a context without option
+ * "pow_exp2", log_form 3 with N < 256, log_cap below the form's elements, a context with option shard_rows or shard_ingest; and,
+ * behind the degree pass and the upload of the layout's tables (the verdict is the layout's own), log_form 3 where the layout
+ * declines the tiles.  The hook sets no option.
+ * Not covered here: the packed form of an exact sweep, which never stores D (cge_packed_gd_test has it), and the sharded set-up
+ * (tests/test_gpu_two_ranks.py). */
+typedef struct cge_sweep_setup_io {
+    const double *emb, *dist, *vw;
+    const int64_t *comm;
+    int64_t N, d, C;
+    int32_t directed, landmarks, force_relabel, log_form;
+    double alpha;
+    const int32_t *src, *dst;
+    const double *w;
+    int64_t m;
+    /* Degrees */
+    double *deg_out, *deg_in;
+    int32_t *star;
+    /* Layout */
+    int32_t *order, *old2new, *comm_rl, *cm_off, *cm_mem, *cm_pos;
+    double *emb_rl, *vec_rl;
+    /* Distances */
+    double *D_raw, *lo_hi, *D;
+    /* The logarithm and the power */
+    double *Lh;
+    float *Ll;
+    int64_t log_cap, log_count;
+    double *GD;
+    /* Start */
+    double *T1, *T2, *TT;
+    int64_t Tld;
+    int32_t relabel, log_form_ran;
+} cge_sweep_setup_io;
+int cge_sweep_setup_test(void *ctx, cge_sweep_setup_io *io);
 /* needs the GPU and a communicator (cge_comm_init_rccl; one rank is enough): host array -> device -> the in-library
  * ncclAllReduce (op 0 sum / 1 max of doubles, 2 sum of the words as int64) -> host */
 int cge_rccl_selftest(void *ctx, double *host_inout, int64_t count, int op);
