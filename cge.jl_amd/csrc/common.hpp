@@ -1141,22 +1141,22 @@ struct AlphaBook {
     void write(double out[7], int *out_len) const; // the reference's 7-vector (:256)
 };
 struct cge_local_score_io; // (include/cge_hip_testing.h)
-void host_local_score_test(cge_ctx *c, cge_local_score_io *io); // the testing hook of the local score's stages (wgcl_host.cpp)
+void host_local_score_test(cge_ctx *c, cge_local_score_io *io); // the testing hook of the local score's stages (sweep_hooks.cpp)
 struct cge_vect_b_problem; // (include/cge_hip_testing.h)
 void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
                          double *GD);
 struct cge_sweep_setup_io; // (include/cge_hip_testing.h)
-void host_sweep_setup_test(cge_ctx *c, cge_sweep_setup_io *io); // the testing hook of the sweep's set-up (wgcl_host.cpp)
+void host_sweep_setup_test(cge_ctx *c, cge_sweep_setup_io *io); // the testing hook of the sweep's set-up (sweep_hooks.cpp)
 // the directed degree pass of a score graph given as an edge list (score_host.cpp): c->s_degin / s_degout and the star counts
 void edge_degrees(cge_ctx *c, const i32 *src, const i32 *dst, const double *w, i64 m, i64 N, DevBuf<i32> &star);
 struct cge_fit_problem; // (include/cge_hip_testing.h)
 struct cge_fused_chain_problem; // (include/cge_hip_testing.h)
 void host_fused_chain_test(cge_ctx *c, cge_fused_chain_problem *probs, int n, double eps,
-                           double delta); // the testing hook of the fused chain's epilogue (wgcl_host.cpp)
+                           double delta); // the testing hook of the fused chain's epilogue (sweep_hooks.cpp)
 void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int form, double eps, double delta,
-                   int *form_ran); // the testing hook of the Chung-Lu fit's forms (wgcl_host.cpp)
+                   int *form_ran); // the testing hook of the Chung-Lu fit's forms (sweep_hooks.cpp)
 void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b_problem *p2, int directed, int form,
-                      int landmarks, int n_modes, int *form_ran); // the testing hook of vect_B's forms (wgcl_host.cpp)
+                      int landmarks, int n_modes, int *form_ran); // the testing hook of vect_B's forms (sweep_hooks.cpp)
 void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *ex_src, const i32 *ex_dst,
                      const double *ex_hw, i64 ex_m, int directed, int split, const SampleSet &smp, double out[7],
                      int *out_len, cge_trace *trace, SweepHandoff *defer = nullptr);

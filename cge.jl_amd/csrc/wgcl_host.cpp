@@ -7,7 +7,7 @@
 #include <cstring>
 
 #include "common.hpp"
-#include "../../include/cge_hip_testing.h"
+#include "sweep_internal.hpp"
 
 // the counter-based RNG of the sampler lives in common.hpp (the device draws the same stream)
 static inline uint64_t ctr_rand(uint64_t seed, uint64_t stream, uint64_t k, uint64_t attempt, uint64_t which) {
@@ -74,12 +74,23 @@ bool sampler_uses_device(const cge_ctx *c) { return (double)c->n * (double)(c->n
 // Endpoints / weights of sampled edge rows are gathered on the host from small D2H reads of the
 // resident edge arrays (S entries), so no host mirror of the edge list is needed.
 static void gather_rows(cge_ctx *c, const i32 *d_arr, const std::vector<i64> &rows0, std::vector<i32> &out,
-                        DevBuf<i32> &d_idx, DevBuf<i32> &d_out);
+                        DevBuf<i32> &d_idx, DevBuf<i32> &d_out) {
+    const i64 S = (i64)rows0.size();
+    std::vector<i32> idx(S);
+    for (i64 k = 0; k < S; k++) idx[k] = (i32)rows0[k];
+    d_idx.ensure(S);
+    d_out.ensure(S);
+    out.resize(S);
+    HIP_CHECK(hipMemcpyAsync(d_idx.p, idx.data(), sizeof(i32) * S, hipMemcpyHostToDevice, c->stream));
+    k_gather_i32(c, d_arr, d_idx.p, S, d_out.p);
+    HIP_CHECK(hipMemcpyAsync(out.data(), d_out.p, sizeof(i32) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
 
 // full_graph_D of sampled vertex pairs (src/divergence.jl:104-114 restricted to the draws), dist()'s own arithmetic.  Option
 // shard_rows: a pair's two rows may live on two ranks -- the rows of a chunk of pairs are gathered from their owners into a
 // zero-filled buffer (all-reduce of the words: exact) and every rank evaluates the chunk from the gathered rows.
-static void sampled_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi, const i32 *pj, i64 S, double den, double *out) {
+void sampled_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi, const i32 *pj, i64 S, double den, double *out) {
     if (!c->rows_sharded) {
         k_pair_dist(c, Xr, d, pi, pj, S, den, out);
         return;
@@ -100,22 +111,13 @@ static void sampled_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi
 
 // ---- the set-up of a sweep -------------------------------------------------------------------------
 
-// How a sweep lays its score graph out: the community -> members CSR, whether the graph is relabelled by community (the sweep's
-// numbering) and whether the rest of an alpha's chain rides on the fit's launch (vect_B by tiles or not: c->bvec_blocks).
-struct SweepLayout {
-    std::vector<i32> cm_off, cm_mem; // community -> members, in the sweep's numbering
-    bool relabel = false, fuse = false;
-    i64 bt_total = 0;    // tile partials in all
-    DevBuf<i32> old2new; // (relabel) a vertex's number in the sweep
-};
-
 // The layout decision from the communities alone (hcomm: 0-based, on the host): the community CSR, the tile tables (on the
 // device when the tiles apply), c->bvec_blocks / c->bvec_contig and, for a relabelled sweep, the order (lay.cm_mem) and its
 // inverse on the device.  landmarks: a landmark-mode sweep.  force_relabel: the testing hook's contiguous-row form below 8193
 // vertices (every sweep passes false).  Shared by plan_layout and the testing hook cge_vect_b_test.
 // packed_req: the sweep wants the packed form of its matrix, which goes with the tile form of vect_B at any N >= 256.
-static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int directed, bool landmarks, bool force_relabel,
-                          SweepLayout &lay, bool packed_req = false) {
+void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int directed, bool landmarks, bool force_relabel,
+                   SweepLayout &lay, bool packed_req) {
     std::vector<i32> &cm_off = lay.cm_off, &cm_mem = lay.cm_mem;
     // community -> members CSR of the score graph
     cm_off.assign(C + 1, 0);
@@ -212,8 +214,8 @@ static void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int direct
 
 // The layout decision, the tile tables and the relabelled copies of the score graph's per-vertex arrays (G points at them then).
 // force_relabel: layout_tables' (the testing hook cge_sweep_setup_test; every sweep passes false).
-static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay, bool packed_req,
-                        bool force_relabel = false) {
+void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int directed, SweepLayout &lay, bool packed_req,
+                 bool force_relabel) {
     const i64 N = G.N, d = G.d;
     std::vector<i32> hcomm(N);
     if (orig && orig->h_lcomm) std::memcpy(hcomm.data(), orig->h_lcomm, sizeof(i32) * N); // (the caller read them back for the diameter)
@@ -242,7 +244,7 @@ static void plan_layout(cge_ctx *c, ScoreGraph &G, const OrigView *orig, int dir
 
 // The community tables of a layout for the device (sw_cm_off, sw_cm_mem, sw_cm_pos), on the caller's packer; cm_pos is the
 // caller's, since the packer reads it at its flush.  Shared by the sweep and the testing hook cge_vect_b_test.
-static void community_tables(cge_ctx *c, const SweepLayout &lay, i64 N, i64 C, WordPacker &pk, std::vector<i32> &cm_pos) {
+void community_tables(cge_ctx *c, const SweepLayout &lay, i64 N, i64 C, WordPacker &pk, std::vector<i32> &cm_pos) {
     c->sw_cm_off.ensure(C + 1);
     c->sw_cm_mem.ensure(N);
     pk.add(c->sw_cm_off.p, lay.cm_off.data(), C + 1);
@@ -256,7 +258,7 @@ static void community_tables(cge_ctx *c, const SweepLayout &lay, i64 N, i64 C, W
 // D and its normalisation (:79-93 / :359-375), the community tables on the device, the starting T (:118) / Tin, Tout
 // (:399-402), and TT, the three parts T rotates through in an undirected sweep.  Returns TT's leading dimension.
 // packed: only lo, hi -- D is never stored; every alpha makes its GD from the embedding rows (k_packed_gd).
-static i64 prepare_distances(cge_ctx *c, const ScoreGraph &G, const SweepLayout &lay, int directed, bool packed) {
+i64 prepare_distances(cge_ctx *c, const ScoreGraph &G, const SweepLayout &lay, int directed, bool packed) {
     const i64 N = G.N, C = G.C;
     hipStream_t st = c->stream;
     double *D = c->sw_D.p, *T1 = c->sw_T1.p, *T2 = c->sw_T2.p;
@@ -386,7 +388,7 @@ static void samples_to_device(cge_ctx *c, const SampleSet &smp, i64 N, i64 d, co
 // One table without the prepared tally operands: vect_B's half from the context's tile tables (comm: the communities in the
 // sweep's numbering) and the S samples' distances and weights.  Shared by fused_tables and the testing hook cge_fused_chain_test,
 // whose caller supplies the prepared operands.
-static cge_fit_fused fused_entry(cge_ctx *c, const i32 *comm, i64 S, const double *dpos, const double *dneg, const double *wts) {
+cge_fit_fused fused_entry(cge_ctx *c, const i32 *comm, i64 S, const double *dpos, const double *dneg, const double *wts) {
     cge_fit_fused e{};
     e.comm = comm; e.fc = c->sw_bt_fc.p; e.ns = c->sw_bt_ns.p; e.base = c->sw_bt_base.p; e.partial = c->sw_bt_part.p;
     e.S = S;
@@ -395,7 +397,7 @@ static cge_fit_fused fused_entry(cge_ctx *c, const i32 *comm, i64 S, const doubl
     return e;
 }
 // the tables' device copies (c->sw_fused_epi), which the fit's epilogue loads after its loop
-static void fused_upload(cge_ctx *c, const std::vector<cge_fit_fused> &h_epi) {
+void fused_upload(cge_ctx *c, const std::vector<cge_fit_fused> &h_epi) {
     c->sw_fused_epi.ensure(h_epi.size() * sizeof(cge_fit_fused));
     static_assert(sizeof(cge_fit_fused) % 8 == 0, "packed as 4-byte words");
     WordPacker pk(c);
@@ -403,8 +405,8 @@ static void fused_upload(cge_ctx *c, const std::vector<cge_fit_fused> &h_epi) {
            (i64)(h_epi.size() * sizeof(cge_fit_fused) / 4));
     pk.flush();
 }
-static void fused_tables(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *old2new, i64 n_sets, i64 s0, i64 s1,
-                         bool fuse_auc, std::vector<cge_fit_fused> &h_epi) {
+void fused_tables(cge_ctx *c, const ScoreGraph &G, const OrigView *orig, const i32 *old2new, i64 n_sets, i64 s0, i64 s1,
+                  bool fuse_auc, std::vector<cge_fit_fused> &h_epi) {
     h_epi.resize(n_sets);
     for (i64 t = 0; t < n_sets; t++) {
         DevSamples &ds = *c->dsets[t];
@@ -497,28 +499,8 @@ static bool hand_off_directed(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, 
 
 // ---- one alpha -------------------------------------------------------------------------------------
 
-// What the host keeps of an alpha in flight until it collects it (two at most: slot = alpha index mod 2)
-struct AlphaSlot {
-    bool fit_async = false;      // the fit was only enqueued: its verdict arrives with the alpha's scalars
-    bool fused = false;          // the rest of the chain rode on the fit's launch
-    bool shared_verdict = false; // N > 1, tallies split: the verdict of the fit travelled with the all-reduced tallies
-    int t0_par = 0;              // the part of TT that held T_0 of this alpha
-    i64 iters = 0;
-};
-
-// The form of the fit from alpha to alpha (a persistent form, once given up, stays given up for the sweep), the part of TT that
-// holds the current iterate (undirected) and the last iteration count (the first batch of a launch-per-iteration fit).  eps,
-// delta: the step and the stopping threshold -- a sweep's are the reference's (0.25 undirected :119, 0.9 directed :434; delta
-// :35); the testing hook cge_fit_test passes its caller's.
-struct FitForm {
-    bool persistent = false, persistent_dir = false;
-    int tpar = 0;
-    i64 prev_iters = 16;
-    double eps = 0.25, delta = AlphaBook::delta;
-};
-
 // Whether a sweep starts on the persistent form of its fit (the geometry is asked at the first launch)
-static bool persistent_wanted(const cge_ctx *c, i64 N) {
+bool persistent_wanted(const cge_ctx *c, i64 N) {
     return !c->fit_persistent_broken && c->opt_fit_persistent != 1 && (c->opt_fit_persistent >= 2 || N >= 128);
 }
 
@@ -554,8 +536,8 @@ static i64 fit_by_launches(cge_ctx *c, i64 prev_iters, double alpha, double delt
 // device copy) -- and its verdict is looked at when the alpha is collected; else one launch per iteration (k_fit_sym_step,
 // over the upper tiles only).  `upper`: GD's upper triangle suffices (the power matrix made here when the fused launch does not
 // apply after all).  `packed`: the matrix is the upper tiles in sw_PK (never persistent).
-static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double alpha, bool upper, bool packed,
-                           const cge_fit_fused *ff, const cge_fit_fused *ff_dev, FitForm &fit, AlphaSlot &sl) {
+void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double alpha, bool upper, bool packed,
+                    const cge_fit_fused *ff, const cge_fit_fused *ff_dev, FitForm &fit, AlphaSlot &sl) {
     hipStream_t st = c->stream;
     double *const GD = packed ? c->sw_PK.p : c->sw_GD.p, *const TT = c->fp_T.p;
     int *flags = c->sw_flags.p;
@@ -592,7 +574,7 @@ static void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double a
 // one launch pair per iteration.  The default persistent form is only enqueued: the rest of the alpha's chain is queued behind
 // it and its verdict arrives with the alpha's scalars (Tin / Tout are written on success only, so a failed launch is redone
 // from the same iterates with one launch pair per iteration).
-static void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm &fit, AlphaSlot &sl) {
+void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm &fit, AlphaSlot &sl) {
     hipStream_t st = c->stream;
     const i64 N = G.N;
     const double *GD = c->sw_GD.p;
@@ -621,7 +603,7 @@ static void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm 
 
 // An enqueued persistent fit was abandoned: what was enqueued behind it is drained, and this fit and every later one of the
 // sweep go by one launch per iteration -- this one again from its T_0, which is still in place.
-static void leave_persistent(cge_ctx *c, int directed, FitForm &fit, const AlphaSlot &sl) {
+void leave_persistent(cge_ctx *c, int directed, FitForm &fit, const AlphaSlot &sl) {
     HIP_CHECK(hipStreamSynchronize(c->stream));
     note_fit_fallback(c);
     if (directed) fit.persistent_dir = false;
@@ -958,1083 +940,4 @@ void AlphaBook::write(double out[7], int *out_len) const {
     out[0] = best_alpha; out[1] = best_div; out[2] = best_div_ext; out[3] = best_div_int;
     out[4] = best_alpha_auc; out[5] = best_auc; out[6] = best_auc_err; // :256
     *out_len = 7;
-}
-
-
-// ---- the testing hook of vect_B (include/cge_hip_testing.h: cge_vect_b_test) ------------------------------------------
-
-namespace {
-struct VbOptions { // the two options that choose vect_B's form, as the hook sets them for a forced form; restored on the way out
-    cge_ctx *c;
-    int blocks, plain;
-    explicit VbOptions(cge_ctx *c_) : c(c_), blocks(c_->opt_bvec_blocks), plain(c_->opt_test_bvec_plain) {}
-    ~VbOptions() { c->opt_bvec_blocks = blocks; c->opt_test_bvec_plain = plain; }
-};
-} // namespace
-
-static i64 vb_len(i64 C, int directed) { return directed ? C * C : packed_len(C); }
-
-// One problem as a sweep lays it out -- layout_tables, the host arrays permuted by its order (the sweep computes GD from permuted
-// rows), GD / Ta / Tb in sw_GD / sw_T1 / sw_T2, community_tables, k_bins_prepare -- after the checks of a forced form, which
-// come before anything is launched.  Returns the form to run.
-static int vb_prepare(cge_ctx *c, const cge_vect_b_problem &p, int directed, int form, bool landmarks) {
-    const i64 N = p.N, C = p.C;
-    if (form == 1 && N * sizeof(double) > 64 * 1024)
-        CGE_THROW(CGE_E_ARG, "vect_b_test: a row of %lld vertices does not fit the LDS of the staged row bins", (long long)N);
-    if (form >= 4 && (N < 256 || C < 2))
-        CGE_THROW(CGE_E_ARG, "vect_b_test: the tiles need 256 vertices and 2 communities (N = %lld, C = %lld)", (long long)N, (long long)C);
-    if (form == 2) c->opt_test_bvec_plain = 1;
-    else if (form != 0) { c->opt_test_bvec_plain = 0; c->opt_bvec_blocks = form >= 4; }
-    std::vector<i32> hcomm(N);
-    for (i64 i = 0; i < N; i++) {
-        if (p.comm[i] < 1 || p.comm[i] > C) CGE_THROW(CGE_E_ARG, "vect_b_test: community id out of range");
-        hcomm[i] = (i32)(p.comm[i] - 1);
-    }
-    SweepLayout lay;
-    layout_tables(c, hcomm.data(), N, C, directed, form == 0 && landmarks, form == 3, lay);
-    if (form >= 4 && !c->bvec_blocks)
-        CGE_THROW(CGE_E_ARG, "vect_b_test: the tiles decline this layout (more than 64 community ids in a 64-vertex block)");
-    const int run = form != 0 ? form : (c->bvec_blocks && !directed && !c->opt_test_bvec_plain) ? 5 : k_bvec_form(c, N);
-    hipStream_t st = c->stream;
-    c->sw_GD.ensure((size_t)N * N);
-    c->sw_T1.ensure(N); c->sw_T2.ensure(N);
-    c->sw_rowbins.ensure((size_t)N * C);
-    std::vector<double> hGD, hTa, hTb; // (relabelled) in the sweep's numbering
-    if (lay.relabel) {
-        const std::vector<i32> order = lay.cm_mem;
-        hGD.resize((size_t)N * N); hTa.resize(N); hTb.resize(N);
-        for (i64 q = 0; q < N; q++) {
-            const i64 a = order[q];
-            hTa[q] = p.Ta[a]; hTb[q] = p.Tb[a];
-            double *dst = hGD.data() + q * N;
-            if (directed)
-                for (i64 r = 0; r < N; r++) dst[r] = p.GD[a * N + order[r]];
-            else // the caller's upper triangle is the matrix
-                for (i64 r = 0; r < N; r++) {
-                    const i64 b = order[r];
-                    dst[r] = a <= b ? p.GD[a * N + b] : p.GD[b * N + a];
-                }
-        }
-        for (i64 q = 0; q < N; q++) lay.cm_mem[q] = (i32)q; // the member lists in the new numbering, as plan_layout leaves them
-    }
-    HIP_CHECK(hipMemcpyAsync(c->sw_GD.p, lay.relabel ? hGD.data() : p.GD, sizeof(double) * N * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->sw_T1.p, lay.relabel ? hTa.data() : p.Ta, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->sw_T2.p, lay.relabel ? hTb.data() : p.Tb, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    WordPacker pk(c);
-    std::vector<i32> cm_pos;
-    community_tables(c, lay, N, C, pk, cm_pos);
-    pk.flush();
-    if (c->bvec_blocks && !directed) k_bins_prepare(c, c->sw_cm_off.p, N, C, lay.bt_total);
-    HIP_CHECK(hipStreamSynchronize(st)); // (the host copies go out of scope)
-    return run;
-}
-
-// the block partials of a divergence added in block order, then halved: what AlphaBook::take and js_final_kernel do
-static double vb_fold(const double *fpart) {
-    double f = 0.0;
-    for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) f += fpart[b];
-    return f / 2.0;
-}
-
-void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b_problem *p2, int directed, int form,
-                      int landmarks, int n_modes, int *form_ran) {
-    const cge_vect_b_problem *probs[2] = {p1, form == 6 ? p2 : nullptr};
-    if ((form == 5 || form == 6) && directed) CGE_THROW(CGE_E_ARG, "vect_b_test: form %d is undirected only", form);
-    if (form == 6 && (!p2 || !p2->GD || p2->C >= p1->C)) CGE_THROW(CGE_E_ARG, "vect_b_test: form 6 takes a second problem of fewer communities");
-    for (const cge_vect_b_problem *p : probs) {
-        if (!p) continue;
-        if (p->N <= 0 || p->C <= 0 || !p->vectB) CGE_THROW(CGE_E_ARG, "vect_b_test: empty problem");
-        if (p->GD && (!p->Ta || !p->Tb || !p->comm)) CGE_THROW(CGE_E_ARG, "vect_b_test: Ta, Tb and comm go with GD");
-        if (p->vC && !p->js_dev) CGE_THROW(CGE_E_ARG, "vect_b_test: vC without js_dev");
-        if ((double)p->N * (double)p->C > 1e9) CGE_THROW(CGE_E_ARG, "vect_b_test: problem too large");
-    }
-    if (!p1->GD && (!p1->vC || form != 0)) CGE_THROW(CGE_E_ARG, "vect_b_test: the JS-only mode takes vC, vectB and form 0");
-    hipStream_t st = c->stream;
-    VbOptions restore(c);
-    const i64 G = CGE_VECT_B_GUARD;
-    const i64 len[2] = {vb_len(p1->C, directed), probs[1] ? vb_len(probs[1]->C, directed) : 0};
-    const i64 off[2] = {0, len[0] + G};
-    // both vectors back to back, each followed by a guard of NaNs that nothing may write
-    std::vector<double> hv((size_t)(len[0] + len[1] + 2 * G), std::nan(""));
-    if (!p1->GD) std::memcpy(hv.data(), p1->vectB, sizeof(double) * len[0]);
-    DevBuf<double> vB, vC, fpart, part, jsd;
-    vB.ensure(hv.size());
-    HIP_CHECK(hipMemcpyAsync(vB.p, hv.data(), sizeof(double) * hv.size(), hipMemcpyHostToDevice, st));
-    { // vect_C of both problems (zeros where the caller has none and the form reads one)
-        std::vector<double> hc((size_t)(len[0] + len[1]), 0.0);
-        for (int q = 0; q < 2; q++)
-            if (probs[q] && probs[q]->vC) std::memcpy(hc.data() + (q ? len[0] : 0), probs[q]->vC, sizeof(double) * len[q]);
-        vC.ensure(hc.size());
-        HIP_CHECK(hipMemcpyAsync(vC.p, hc.data(), sizeof(double) * hc.size(), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    const double *vCp[2] = {vC.p, vC.p + len[0]};
-    const int nm = n_modes == 2 ? 2 : 1;
-    fpart.ensure((size_t)4 * CGE_PARTIAL_BLOCKS);
-    int run = 0;
-    if (p1->GD && form != 6) {
-        run = vb_prepare(c, *p1, directed, form, landmarks != 0);
-        const i64 N = p1->N, C = p1->C;
-        if (run == 5) {
-            k_bvec_tiles(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, N, directed);
-            k_bins_js(c, c->sw_cm_off.p, N, C, vCp[0], vB.p, nm, fpart.p);
-        } else
-            k_bvec(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_pos.p, c->sw_cm_off.p, c->sw_cm_mem.p, N, C, directed,
-                   c->sw_rowbins.p, vB.p, run);
-    } else if (p1->GD) { // form 6: the tile partials of the first problem leave the context, as a batch member's do
-        run = 6;
-        DevBuf<i32> fc1, ns1, base1, off1;
-        DevBuf<double> part1;
-        vb_prepare(c, *p1, 0, 6, false);
-        k_bvec_tiles(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, p1->N, 0);
-        HIP_CHECK(hipStreamSynchronize(st));
-        fc1.swap(c->sw_bt_fc); ns1.swap(c->sw_bt_ns); base1.swap(c->sw_bt_base); part1.swap(c->sw_bt_part); off1.swap(c->sw_cm_off);
-        vb_prepare(c, *p2, 0, 6, false);
-        k_bvec_tiles(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, p2->N, 0);
-        cge_bins_multi bins{};
-        cge_js_multi js{};
-        bins.p[0] = cge_bins_problem{part1.p, off1.p, fc1.p, ns1.p, base1.p, p1->C, (int)((p1->N + 63) / 64), 0, vB.p + off[0]};
-        bins.p[1] = cge_bins_problem{c->sw_bt_part.p, c->sw_cm_off.p, c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, p2->C,
-                                     (int)((p2->N + 63) / 64), 0, vB.p + off[1]};
-        part.ensure((size_t)4 * 3 * CGE_PARTIAL_BLOCKS);
-        int nj = 0;
-        for (int q = 0; q < 2; q++)
-            for (int u = 0; u < nm; u++, nj++)
-                js.p[nj] = cge_js_problem{vCp[q], vB.p + off[q], len[q], probs[q]->C, nm == 1 ? 0 : 1 + u, 0,
-                                          part.p + (i64)nj * 3 * CGE_PARTIAL_BLOCKS, fpart.p + (i64)nj * CGE_PARTIAL_BLOCKS};
-        k_bins_js_multi(c, bins, 2, p1->C, js, nj);
-        HIP_CHECK(hipStreamSynchronize(st)); // (the first problem's tables are released below)
-    }
-    *form_ran = run;
-    std::vector<double> hf((size_t)4 * CGE_PARTIAL_BLOCKS, 0.0);
-    if (run >= 5) HIP_CHECK(hipMemcpyAsync(hf.data(), fpart.p, sizeof(double) * hf.size(), hipMemcpyDeviceToHost, st));
-    // k_js modes 0, 1, 2 over the vector(s) the form left
-    jsd.ensure(6);
-    double hj[6] = {0, 0, 0, 0, 0, 0};
-    for (int q = 0; q < 2; q++)
-        if (probs[q] && probs[q]->vC)
-            for (int mode = 0; mode < 3; mode++)
-                k_js(c, vCp[q], vB.p + off[q], len[q], probs[q]->C, directed, mode, jsd.p + 3 * q + mode);
-    HIP_CHECK(hipMemcpyAsync(hj, jsd.p, sizeof(hj), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(hv.data(), vB.p, sizeof(double) * hv.size(), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    for (int q = 0; q < 2; q++) {
-        const cge_vect_b_problem *p = probs[q];
-        if (!p) continue;
-        if (p->GD) std::memcpy(p->vectB, hv.data() + off[q], sizeof(double) * (len[q] + G));
-        if (p->vC) std::memcpy(p->js_dev, hj + 3 * q, sizeof(double) * 3);
-        if (p->js_fused && run >= 5)
-            for (int u = 0; u < nm; u++) p->js_fused[u] = vb_fold(hf.data() + (i64)((run == 6 ? q * nm : 0) + u) * CGE_PARTIAL_BLOCKS);
-    }
-}
-
-// ---- the testing hook of the Chung-Lu fit (include/cge_hip_testing.h: cge_fit_test) -------------------------------------------
-// One fit from a caller's start through fit_undirected / fit_directed (forms 0-4), k_fit_flow_multi (form 5) or
-// k_fit_flow_dir_multi (form 6), on the buffers a sweep keeps them in.  Everything that can refuse does so before the first launch.
-
-// D to sw_D and, when the form or the caller reads it, GD = (1 - D)^alpha to sw_GD by the sweep's two launches (upper: the upper
-// tiles alone, as a landmark-mode sweep makes it; everything else of sw_GD is NaN) and to the caller's GD
-static void ft_matrices(cge_ctx *c, const cge_fit_problem &p, bool upper, bool need_gd) {
-    hipStream_t st = c->stream;
-    const i64 N = p.N;
-    c->sw_D.ensure((size_t)N * N);
-    HIP_CHECK(hipMemcpyAsync(c->sw_D.p, p.D, sizeof(double) * N * N, hipMemcpyHostToDevice, st));
-    if (need_gd || p.GD) {
-        c->sw_GD.ensure((size_t)N * N);
-        HIP_CHECK(hipMemsetAsync(c->sw_GD.p, 0xFF, sizeof(double) * N * N, st)); // (all bits set: a NaN)
-        k_pow_prepare(c, c->sw_D.p, N, upper);
-        k_pow_matrix(c, c->sw_D.p, N, p.alpha, c->sw_GD.p, upper);
-        if (p.GD) HIP_CHECK(hipMemcpyAsync(p.GD, c->sw_GD.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-// the verdict of an enqueued persistent fit: flags [0] converged, [1] iterations, [2] abandoned
-static bool ft_verdict(cge_ctx *c, const int *dev_flags, i64 *iters) {
-    int hf[4];
-    HIP_CHECK(hipMemcpyAsync(hf, dev_flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    *iters = hf[1];
-    return !(hf[2] || !hf[0]);
-}
-
-// epi / epi_dev (form 4, the hooks of the local score and of the fused chain): the host and device copies of the epilogue's table
-// (fused_tables); the launch then wants of the epilogue what epi_want names (bit 0 vect_B's tile partials, bit 1 the tally), as
-// enqueue_alpha leaves out what an alpha does not want -- the local score's hook the tally alone.
-static int ft_undirected(cge_ctx *c, cge_fit_problem &p, int form, double eps, double delta, const cge_fit_fused *epi = nullptr,
-                         const cge_fit_fused *epi_dev = nullptr, int epi_want = 2) {
-    hipStream_t st = c->stream;
-    const i64 N = p.N, Nt = (N + 63) / 64, Tld = Nt * 64;
-    ft_matrices(c, p, true, form != 4);
-    if (form == 2) { // the upper tiles of GD, zeros outside the matrix, through the address inline every consumer uses
-        std::vector<double> h((size_t)N * N), pk((size_t)(Nt * (Nt + 1) / 2) * CGE_TILE_DOUBLES, 0.0);
-        HIP_CHECK(hipMemcpyAsync(h.data(), c->sw_GD.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        for (i64 i = 0; i < N; i++)
-            for (i64 j = i / 64 * 64; j < N; j++) pk[cge_packed_index(i, j, Nt)] = h[i * N + j];
-        c->sw_PK.ensure(pk.size());
-        HIP_CHECK(hipMemcpyAsync(c->sw_PK.p, pk.data(), sizeof(double) * pk.size(), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    if (form == 4) k_pow_prepare(c, c->sw_D.p, N, true, true);
-    // T_0 in part 0 of TT (zero beyond N), NaN in the rows of the two other parts
-    DevBuf<double> dw;
-    dw.ensure(N);
-    c->fp_T.ensure((size_t)3 * Tld);
-    c->sw_scal.ensure(RES_STRIDE);
-    c->sw_flags.ensure(4);
-    c->sw_fring.ensure(4);
-    const std::vector<double> nan_n(N, std::nan(""));
-    HIP_CHECK(hipMemsetAsync(c->fp_T.p, 0, sizeof(double) * 3 * Tld, st));
-    HIP_CHECK(hipMemcpyAsync(c->fp_T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->fp_T.p + Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->fp_T.p + 2 * Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(dw.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->flow_armed_words = 0; // (no alpha of a sweep armed the hand-off slots of this launch)
-    FitForm fit;
-    fit.eps = eps;
-    fit.delta = delta;
-    fit.persistent = form == 3 || form == 4 || (form == 0 && persistent_wanted(c, N));
-    cge_fit_fused ff{};
-    if (epi) { // (else no partial, no auc_part: nothing is wanted of the epilogue)
-        ff = *epi;
-        if (!(epi_want & 1)) ff.partial = nullptr;
-        if (!(epi_want & 2)) ff.auc_part = nullptr;
-    }
-    ff.Lh = c->sw_Lh.p; ff.Ll = c->sw_Ll.p; ff.alpha = p.alpha;
-    AlphaSlot sl;
-    fit_undirected(c, N, dw.p, Tld, p.alpha, true, form == 2, form == 4 ? &ff : nullptr, form == 4 ? epi_dev : nullptr, fit, sl);
-    int ran = form == 2 ? 2 : 1;
-    p.status = 0;
-    if (sl.fit_async) {
-        ran = form == 4 ? 4 : 3;
-        if (!ft_verdict(c, (const int *)(c->sw_scal.p + RES_FIT), &sl.iters)) {
-            if (form == 0) { // as the sweep: again from T_0 with one launch pair per iteration
-                leave_persistent(c, 0, fit, sl);
-                sl = AlphaSlot();
-                fit_undirected(c, N, dw.p, Tld, p.alpha, true, false, nullptr, nullptr, fit, sl);
-                ran = 1;
-            } else
-                p.status = 1;
-        }
-    } else if (form == 3 || form == 4)
-        CGE_THROW(CGE_E_ASSERT, "fit_test: the persistent launch of form %d was declined (N = %lld)", form, (long long)N);
-    p.iters = sl.iters;
-    HIP_CHECK(hipMemcpyAsync(p.T, c->fp_T.p + (i64)fit.tpar * Tld, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (form == 2) c->sw_PK.release(); // (held only while packed sweeps run)
-    return ran;
-}
-
-static int ft_directed(cge_ctx *c, cge_fit_problem &p, int form, double eps, double delta) {
-    hipStream_t st = c->stream;
-    const i64 N = p.N;
-    ft_matrices(c, p, false, true);
-    DevBuf<double> din, dout;
-    din.ensure(N); dout.ensure(N);
-    c->sw_T1.ensure(N); c->sw_T2.ensure(N); c->sw_S1.ensure(N); c->sw_S2.ensure(N);
-    c->sw_scal.ensure(RES_STRIDE);
-    c->sw_flags.ensure(4);
-    c->sw_fitstate.ensure(4);
-    HIP_CHECK(hipMemcpyAsync(c->sw_T1.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->sw_T2.p, p.T0b, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(din.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(dout.p, p.w2, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    ScoreGraph G;
-    G.N = N;
-    G.deg_in = din.p; G.deg_out = dout.p;
-    FitForm fit;
-    fit.eps = eps;
-    fit.delta = delta;
-    fit.persistent_dir = form == 3 || (form == 0 && persistent_wanted(c, N));
-    AlphaSlot sl;
-    fit_directed(c, G, p.alpha, fit, sl);
-    int ran = 1;
-    p.status = 0;
-    if (sl.fit_async) {
-        ran = 3;
-        if (!ft_verdict(c, (const int *)(c->sw_scal.p + RES_FIT), &sl.iters)) {
-            if (form == 0) {
-                leave_persistent(c, 1, fit, sl);
-                sl = AlphaSlot();
-                fit_directed(c, G, p.alpha, fit, sl);
-                ran = 1;
-            } else
-                p.status = 1;
-        }
-    } else if (form == 3)
-        CGE_THROW(CGE_E_ASSERT, "fit_test: the persistent launch of form 3 was declined (N = %lld)", (long long)N);
-    p.iters = sl.iters;
-    HIP_CHECK(hipMemcpyAsync(p.T, c->sw_T1.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(p.Tb, c->sw_T2.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return ran;
-}
-
-// A member of a shared undirected launch with its own logarithm, T and weights, as the members of a batch keep them
-// (batch_host.cpp), and its entry of the launch's table: T_0 (zero beyond N), then the result (NaN until written)
-struct FtMember {
-    DevBuf<double> Lh, T, w;
-    DevBuf<float> Ll;
-};
-static cge_flow_problem ft_member(cge_ctx *c, const cge_fit_problem &p, const FlowGeometry &geo, FtMember &m, int *flags,
-                                  const cge_fit_fused *epi, int want) {
-    hipStream_t st = c->stream;
-    const i64 N = p.N, Tld = (i64)geo.Nt * 64;
-    ft_matrices(c, p, true, false);
-    k_pow_prepare(c, c->sw_D.p, N, true, true);
-    HIP_CHECK(hipStreamSynchronize(st));
-    m.Lh.swap(c->sw_Lh); m.Ll.swap(c->sw_Ll);
-    c->pow_logs_N = c->pow_logs_blocked_N = 0; // (the context's logarithm left with the member)
-    m.T.ensure((size_t)2 * Tld);
-    m.w.ensure(N);
-    const std::vector<double> nan_n(N, std::nan(""));
-    HIP_CHECK(hipMemsetAsync(m.T.p, 0, sizeof(double) * 2 * Tld, st));
-    HIP_CHECK(hipMemcpyAsync(m.T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(m.T.p + Tld, nan_n.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(m.w.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return flow_problem_entry(m.Lh.p, m.Ll.p, p.alpha, epi, want, m.T.p, m.T.p + Tld, m.w.p, flags, N, Tld, geo);
-}
-// the members' verdicts and iterates of a shared launch
-static void ft_multi_collect(cge_ctx *c, cge_fit_problem *probs, int n, const cge_flow_multi &tab) {
-    for (int i = 0; i < n; i++) {
-        cge_fit_problem &p = probs[i];
-        p.status = ft_verdict(c, tab.p[i].flags, &p.iters) ? 0 : 1;
-        HIP_CHECK(hipMemcpyAsync(p.T, tab.p[i].Tout, sizeof(double) * p.N, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-}
-
-// form 5: every problem with slots and flags of its own; nothing is wanted of the epilogue
-static void ft_multi(cge_ctx *c, cge_fit_problem *probs, int n, const FlowGeometry *geo, double eps, double delta) {
-    hipStream_t st = c->stream;
-    std::vector<std::unique_ptr<FtMember>> mem;
-    DevBuf<int> flags;
-    DevBuf<double> flow;
-    flags.ensure((size_t)4 * n);
-    HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4 * n, st));
-    cge_flow_multi tab{};
-    tab.n = n;
-    for (int i = 0; i < n; i++) {
-        mem.emplace_back(new FtMember());
-        tab.p[i] = ft_member(c, probs[i], geo[i], *mem.back(), flags.p + 4 * i, nullptr, 0);
-    }
-    k_fit_flow_multi(c, tab, geo[0].NW, eps, delta, flow);
-    ft_multi_collect(c, probs, n, tab);
-}
-
-// form 6: every problem with its own power matrix, Tin / Tout, degrees and flags, as the directed members of a batch keep them
-static void ft_dir_multi(cge_ctx *c, cge_fit_problem *probs, int n, const FlowGeometry *geo, double eps, double delta) {
-    hipStream_t st = c->stream;
-    struct Member {
-        DevBuf<double> GD, T, deg;
-    };
-    std::vector<std::unique_ptr<Member>> mem;
-    DevBuf<int> flags;
-    DevBuf<double> flow;
-    flags.ensure((size_t)4 * n);
-    HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4 * n, st));
-    cge_flow_dir_multi tab{};
-    tab.n = n;
-    for (int i = 0; i < n; i++) {
-        cge_fit_problem &p = probs[i];
-        const i64 N = p.N, Tld = (i64)geo[i].Nt * 64;
-        mem.emplace_back(new Member());
-        Member &m = *mem.back();
-        ft_matrices(c, p, false, true);
-        m.GD.swap(c->sw_GD); // (the context's power matrix leaves with the member)
-        m.T.ensure((size_t)2 * N);
-        m.deg.ensure((size_t)2 * N);
-        HIP_CHECK(hipMemcpyAsync(m.T.p, p.T0, sizeof(double) * N, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(m.T.p + N, p.T0b, sizeof(double) * N, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(m.deg.p, p.w, sizeof(double) * N, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(m.deg.p + N, p.w2, sizeof(double) * N, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        cge_flow_dir_problem &q = tab.p[i];
-        q.GD = m.GD.p;
-        q.Tin = m.T.p; q.Tout = m.T.p + N;
-        q.deg_in = m.deg.p; q.deg_out = m.deg.p + N;
-        q.flags = flags.p + 4 * i;
-        q.N = N; q.Tld = Tld; q.Nt = geo[i].Nt; q.G = geo[i].G;
-    }
-    k_fit_flow_dir_multi(c, tab, geo[0].NW, eps, 1.0, delta, flow);
-    for (int i = 0; i < n; i++) {
-        cge_fit_problem &p = probs[i];
-        p.status = ft_verdict(c, flags.p + 4 * i, &p.iters) ? 0 : 1;
-        HIP_CHECK(hipMemcpyAsync(p.T, tab.p[i].Tin, sizeof(double) * p.N, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(p.Tb, tab.p[i].Tout, sizeof(double) * p.N, hipMemcpyDeviceToHost, st));
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int form, double eps, double delta, int *form_ran) {
-    if (!directed && form == 6) CGE_THROW(CGE_E_ARG, "fit_test: form 6 is directed only");
-    if (n > 1 && form != 5 && form != 6) CGE_THROW(CGE_E_ARG, "fit_test: %d problems in one call are form 5 only", n);
-    if (n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ARG, "fit_test: form %d takes at most %d problems", form, CGE_BATCH_MAX);
-    if (directed && (form == 2 || form == 4 || form == 5)) CGE_THROW(CGE_E_ARG, "fit_test: form %d is undirected only", form);
-    if ((form == 4 || form == 5) && !c->opt_pow_exp2)
-        CGE_THROW(CGE_E_ARG, "fit_test: form %d makes its power matrix from the stored logarithm (option pow_exp2)", form);
-    if (!(eps > 0.0) || !(delta >= 0.0)) CGE_THROW(CGE_E_ARG, "fit_test: eps > 0 and delta >= 0");
-    const bool multi = form == 5 || form == 6;
-    FlowGeometry geo[CGE_BATCH_MAX];
-    int sumG = 0;
-    const int cus = device_cus();
-    for (int i = 0; i < n; i++) {
-        const cge_fit_problem &p = probs[i];
-        if (p.N <= 0 || !p.D || !p.w || !p.T0 || !p.T) CGE_THROW(CGE_E_ARG, "fit_test: empty problem");
-        if (directed && (!p.w2 || !p.T0b || !p.Tb)) CGE_THROW(CGE_E_ARG, "fit_test: a directed problem takes w2, T0b and Tb");
-        if (p.N > 46340) CGE_THROW(CGE_E_ARG, "fit_test: problem too large");
-        FlowGeometry &g = geo[i];
-        const bool applies = flow_geometry(p.N, cus, &g);
-        if (form == 3 && !applies)
-            CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-        if ((form == 4 || form == 5) && !(applies && g.fused()))
-            CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the fused persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-        if (!multi) continue;
-        if (!applies)
-            CGE_THROW(CGE_E_ARG, "fit_test: the geometry of the directed persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-        if (!g.fused())
-            CGE_THROW(CGE_E_ARG, "fit_test: form 6 takes problems of one quarter block per workgroup (N = %lld needs two on %d CUs)", (long long)p.N, cus);
-        if (g.NW != geo[0].NW)
-            CGE_THROW(CGE_E_ARG, "fit_test: form %d takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", form, i, g.NW, geo[0].NW);
-        sumG += g.G;
-    }
-    if (!multi) {
-        *form_ran = directed ? ft_directed(c, probs[0], form, eps, delta) : ft_undirected(c, probs[0], form, eps, delta);
-        return;
-    }
-    if (sumG > cus)
-        CGE_THROW(CGE_E_ARG, "fit_test: the problems of form %d need %d workgroups in all, the device has %d CUs", form, sumG, cus);
-    if (!k_fit_flow_multi_fits(geo[0].NW, form == 6))
-        CGE_THROW(CGE_E_ARG, "fit_test: %s of %d waves gets no workgroup on a CU", form == 6 ? "fit_flow_dir_multi_kernel" : "fit_flow_multi_kernel",
-                  geo[0].NW);
-    (form == 6 ? ft_dir_multi : ft_multi)(c, probs, n, geo, eps, delta);
-    *form_ran = form;
-}
-
-// host <-> device copies of the hooks below on the context's stream (down: a NULL host pointer is not copied)
-template <class T>
-static void ls_up(cge_ctx *c, DevBuf<T> &dev, const T *host, i64 cnt) {
-    dev.ensure((size_t)cnt);
-    HIP_CHECK(hipMemcpyAsync(dev.p, host, sizeof(T) * cnt, hipMemcpyHostToDevice, c->stream));
-}
-template <class T>
-static void ls_down(cge_ctx *c, T *host, const T *dev, i64 cnt) {
-    if (host) HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(T) * cnt, hipMemcpyDeviceToHost, c->stream));
-}
-
-// ---- the testing hook of the fused chain (include/cge_hip_testing.h: cge_fused_chain_test) -----------------------------------
-// One alpha as enqueue_alpha / host_batch_sweep run it on the fused path, on a caller's problem: the layout and its tables, the
-// epilogue's table, the fit with its epilogue's outputs wanted, the bins and the divergence.  A problem is prepared on the
-// context's buffers, as a sweep prepares it; the problems of a shared launch then take them along (FcMember), as hand_off does.
-namespace {
-struct FcOptions { // the options that decide whether a layout is the fused one, as the hook sets them; restored on the way out
-    cge_ctx *c;
-    int fused, plain, persistent;
-    bool relabel;
-    explicit FcOptions(cge_ctx *c_)
-        : c(c_), fused(c_->opt_fit_fused), plain(c_->opt_test_bvec_plain), persistent(c_->opt_fit_persistent), relabel(c_->opt_exact_relabel) {}
-    ~FcOptions() { c->opt_fit_fused = fused; c->opt_test_bvec_plain = plain; c->opt_fit_persistent = persistent; c->opt_exact_relabel = relabel; }
-};
-struct FcMember {
-    std::vector<i32> order;                  // the layout's order: the caller's vertex at each position of the sweep's numbering
-    std::vector<double> D, w, T0, T;         // the problem in the sweep's numbering
-    i64 bt_total = 0, vlen = 0;
-    cge_fit_fused epi{};                     // the host copy of the epilogue's table
-    DevBuf<i32> comm, aidx, fc, ns, base, cm_off; // (fc .. cm_off: a shared launch's members take the context's along)
-    DevBuf<double> afac, dpos, dneg, wts, apw, part, scal, vB, vC, fpart, jspart;
-    DevBuf<char> epi_dev;
-    FtMember fit;
-};
-} // namespace
-
-// The layout, the tables and the epilogue's table of one problem, on the context.  Every refusal of the layout comes first.
-static void fc_prepare(cge_ctx *c, const cge_fused_chain_problem &p, FcMember &m, bool shared) {
-    hipStream_t st = c->stream;
-    const i64 N = p.N, C = p.C, Nt = (N + 63) / 64, S = (p.want & 2) ? p.S : 0;
-    std::vector<i32> hcomm(N);
-    for (i64 i = 0; i < N; i++) {
-        if (p.comm[i] < 1 || p.comm[i] > C) CGE_THROW(CGE_E_ARG, "fused_chain_test: community id out of range");
-        hcomm[i] = (i32)(p.comm[i] - 1);
-    }
-    SweepLayout lay;
-    layout_tables(c, hcomm.data(), N, C, 0, true, false, lay);
-    if (!c->bvec_blocks)
-        CGE_THROW(CGE_E_ARG, "fused_chain_test: the tiles decline this layout (more than 64 community ids in a 64-vertex block)");
-    if (!lay.fuse)
-        CGE_THROW(CGE_E_ARG, "fused_chain_test: the fused form declines this layout (more than %d pieces in a 64-vertex block)", CGE_FLOW_NP);
-    if (p.partials && p.partials_cap < lay.bt_total)
-        CGE_THROW(CGE_E_ARG, "fused_chain_test: partials holds %lld doubles, the layout has %lld tile partials", (long long)p.partials_cap,
-                  (long long)lay.bt_total);
-    m.bt_total = lay.bt_total;
-    m.vlen = packed_len(C);
-    m.order = lay.cm_mem;
-    const std::vector<i32> &order = m.order;
-    std::vector<i32> old2new(N), comm_new(N);
-    m.D.resize((size_t)N * N); m.w.resize(N); m.T0.resize(N); m.T.assign(N, std::nan(""));
-    for (i64 q = 0; q < N; q++) {
-        const i64 a = order[q];
-        old2new[a] = (i32)q;
-        comm_new[q] = hcomm[a];
-        m.w[q] = p.w[a]; m.T0[q] = p.T0[a];
-        double *dst = m.D.data() + q * N;
-        for (i64 r = 0; r < N; r++) dst[r] = p.D[a * N + order[r]];
-    }
-    for (i64 q = 0; q < N; q++) lay.cm_mem[q] = (i32)q; // the member lists in the new numbering, as plan_layout leaves them
-    m.comm.ensure(N);
-    HIP_CHECK(hipMemcpyAsync(m.comm.p, comm_new.data(), sizeof(i32) * N, hipMemcpyHostToDevice, st));
-    WordPacker pk(c);
-    std::vector<i32> cm_pos;
-    community_tables(c, lay, N, C, pk, cm_pos);
-    pk.flush();
-    k_bins_prepare(c, c->sw_cm_off.p, N, C, lay.bt_total);
-    HIP_CHECK(hipMemsetAsync(c->sw_bt_part.p, 0xFF, sizeof(double) * lay.bt_total, st)); // (all bits set: a NaN where nothing writes)
-    ls_down(c, p.fc, c->sw_bt_fc.p, Nt);
-    ls_down(c, p.ns, c->sw_bt_ns.p, Nt);
-    ls_down(c, p.base, c->sw_bt_base.p, Nt * Nt);
-    // the tally's operands: the caller's, T's indices through old2new
-    if (S > 0) {
-        std::vector<i32> ax((size_t)4 * S);
-        for (i64 k = 0; k < 4 * S; k++) ax[k] = old2new[p.aidx[k]];
-        ls_up(c, m.aidx, ax.data(), 4 * S);
-        m.afac.ensure((size_t)8 * S + CGE_PARTIAL_BLOCKS); // (the blocks' weight sums behind the factors, as fused_tables keeps them)
-        HIP_CHECK(hipMemcpyAsync(m.afac.p, p.afac, sizeof(double) * 8 * S, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(m.afac.p + 8 * S, p.aden, sizeof(double) * CGE_PARTIAL_BLOCKS, hipMemcpyHostToDevice, st));
-        ls_up(c, m.dpos, p.dpos, S);
-        ls_up(c, m.dneg, p.dneg, S);
-        ls_up(c, m.wts, p.wts, S);
-        m.apw.ensure((size_t)2 * S);
-        HIP_CHECK(hipMemsetAsync(m.apw.p, 0xFF, sizeof(double) * 2 * S, st));
-        HIP_CHECK(hipStreamSynchronize(st)); // (ax goes out of scope)
-    }
-    c->sw_scal.ensure(RES_STRIDE);
-    m.epi = fused_entry(c, m.comm.p, S, m.dpos.p, m.dneg.p, m.wts.p);
-    if (S > 0) { m.epi.aidx = m.aidx.p; m.epi.afac = m.afac.p; m.epi.aden = m.afac.p + 8 * S; m.epi.apw = m.apw.p; }
-    if (shared) { // the tables and the tallies' place leave the context with the member
-        m.scal.ensure(2 * CGE_PARTIAL_BLOCKS);
-        m.epi.auc_part = m.scal.p;
-        HIP_CHECK(hipStreamSynchronize(st));
-        m.fc.swap(c->sw_bt_fc); m.ns.swap(c->sw_bt_ns); m.base.swap(c->sw_bt_base); m.part.swap(c->sw_bt_part); m.cm_off.swap(c->sw_cm_off);
-        m.epi_dev.ensure(sizeof(cge_fit_fused));
-        HIP_CHECK(hipMemcpyAsync(m.epi_dev.p, &m.epi, sizeof(cge_fit_fused), hipMemcpyHostToDevice, st));
-    } else
-        fused_upload(c, std::vector<cge_fit_fused>(1, m.epi));
-    HIP_CHECK(hipMemsetAsync(m.epi.auc_part, 0xFF, sizeof(double) * 2 * CGE_PARTIAL_BLOCKS, st)); // (NaN until the epilogue writes)
-    // vect_B with its guard of NaNs behind it, and vect_C (zeros where the caller has none)
-    std::vector<double> hv((size_t)(m.vlen + CGE_VECT_B_GUARD), std::nan("")), hc((size_t)m.vlen, 0.0);
-    if (p.vC) std::memcpy(hc.data(), p.vC, sizeof(double) * m.vlen);
-    ls_up(c, m.vB, hv.data(), (i64)hv.size());
-    ls_up(c, m.vC, hc.data(), m.vlen);
-    m.fpart.ensure((size_t)2 * CGE_PARTIAL_BLOCKS);
-    HIP_CHECK(hipStreamSynchronize(st)); // (the host copies go out of scope)
-}
-
-// what a problem's launch left: the iterate in the caller's numbering, the tile partials (before the bins), the tallies, the powers
-static void fc_collect(cge_ctx *c, cge_fused_chain_problem &p, FcMember &m, const double *partial) {
-    const i64 S = (p.want & 2) ? p.S : 0;
-    for (i64 q = 0; q < p.N; q++) p.T[m.order[q]] = m.T[q];
-    if (p.order) std::memcpy(p.order, m.order.data(), sizeof(i32) * p.N);
-    p.bt_total = m.bt_total;
-    ls_down(c, p.partials, partial, m.bt_total);
-    ls_down(c, p.part, m.epi.auc_part, 2 * CGE_PARTIAL_BLOCKS);
-    if (S > 0) ls_down(c, p.apw, m.apw.p, 2 * S);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-}
-
-void host_fused_chain_test(cge_ctx *c, cge_fused_chain_problem *probs, int n, double eps, double delta) {
-    hipStream_t st = c->stream;
-    // ---- the checks that need no layout ------------------------------------------------------------------------------------------
-    if (n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ARG, "fused_chain_test: a launch takes at most %d problems", CGE_BATCH_MAX);
-    if (!(eps > 0.0) || !(delta >= 0.0)) CGE_THROW(CGE_E_ARG, "fused_chain_test: eps > 0 and delta >= 0");
-    if (!c->opt_pow_exp2)
-        CGE_THROW(CGE_E_ARG, "fused_chain_test: the fused fit makes its power matrix from the stored logarithm (option pow_exp2)");
-    if (c->fit_persistent_broken) CGE_THROW(CGE_E_ARG, "fused_chain_test: this context gave the persistent fit up");
-    FlowGeometry geo[CGE_BATCH_MAX];
-    const int cus = device_cus();
-    int sumG = 0;
-    for (int i = 0; i < n; i++) {
-        const cge_fused_chain_problem &p = probs[i];
-        if (!p.D || !p.w || !p.T0 || !p.comm || !p.T) CGE_THROW(CGE_E_ARG, "fused_chain_test: empty problem");
-        if (p.N < 256 || p.C < 2)
-            CGE_THROW(CGE_E_ARG, "fused_chain_test: the tiles need 256 vertices and 2 communities (N = %lld, C = %lld)", (long long)p.N, (long long)p.C);
-        if ((double)p.N * (double)p.C > 1e9) CGE_THROW(CGE_E_ARG, "fused_chain_test: problem too large");
-        if (p.want < 1 || p.want > 3) CGE_THROW(CGE_E_ARG, "fused_chain_test: want = %d (bit 0 vect_B's partials, bit 1 the tallies)", (int)p.want);
-        if (p.n_modes < 1 || p.n_modes > 2) CGE_THROW(CGE_E_ARG, "fused_chain_test: n_modes = %d", (int)p.n_modes);
-        if (p.vC && !p.js_fused) CGE_THROW(CGE_E_ARG, "fused_chain_test: vC without js_fused");
-        if (p.want & 2) {
-            if (p.S < 1 || p.S > 65535) CGE_THROW(CGE_E_ARG, "fused_chain_test: S = %lld samples (1 .. 65535)", (long long)p.S);
-            if (!p.aidx || !p.afac || !p.aden || !p.dpos || !p.dneg || !p.wts)
-                CGE_THROW(CGE_E_ARG, "fused_chain_test: the tallies take aidx, afac, aden, dpos, dneg and wts");
-            for (i64 k = 0; k < 4 * p.S; k++)
-                if (p.aidx[k] < 0 || p.aidx[k] >= p.N)
-                    CGE_THROW(CGE_E_ARG, "fused_chain_test: aidx[%lld] = %d outside 0..%lld", (long long)k, (int)p.aidx[k], (long long)(p.N - 1));
-        }
-        if (!(flow_geometry(p.N, cus, &geo[i]) && geo[i].fused()))
-            CGE_THROW(CGE_E_ARG, "fused_chain_test: the geometry of the fused persistent fit declines N = %lld on %d CUs", (long long)p.N, cus);
-        if (geo[i].NW != geo[0].NW)
-            CGE_THROW(CGE_E_ARG, "fused_chain_test: a launch takes problems of one NW (problem %d runs %d waves per workgroup, problem 0 runs %d)", i,
-                      geo[i].NW, geo[0].NW);
-        sumG += geo[i].G;
-    }
-    if (n > 1 && sumG > cus)
-        CGE_THROW(CGE_E_ARG, "fused_chain_test: the problems need %d workgroups in all, the device has %d CUs", sumG, cus);
-    if (n > 1 && !k_fit_flow_multi_fits(geo[0].NW, false))
-        CGE_THROW(CGE_E_ARG, "fused_chain_test: fit_flow_multi_kernel of %d waves gets no workgroup on a CU", geo[0].NW);
-    FcOptions restore(c);
-    c->opt_fit_fused = 1; c->opt_exact_relabel = true; c->opt_test_bvec_plain = 0;
-    if (c->opt_fit_persistent == 1) c->opt_fit_persistent = 0;
-    std::vector<std::unique_ptr<FcMember>> mem;
-    if (n == 1) { // ---- fit_flow_kernel<.., true>, as enqueue_alpha launches it, then bins_js_kernel -------------------------------
-        cge_fused_chain_problem &p = probs[0];
-        mem.emplace_back(new FcMember());
-        FcMember &m = *mem.back();
-        fc_prepare(c, p, m, false);
-        cge_fit_problem fp{};
-        fp.D = m.D.data(); fp.w = m.w.data(); fp.T0 = m.T0.data(); fp.T = m.T.data(); fp.N = p.N; fp.alpha = p.alpha;
-        ft_undirected(c, fp, 4, eps, delta, &m.epi, reinterpret_cast<const cge_fit_fused *>(c->sw_fused_epi.p), p.want);
-        p.iters = fp.iters;
-        p.status = fp.status;
-        fc_collect(c, p, m, c->sw_bt_part.p);
-        if ((p.want & 1) && p.status == 0) k_bins_js(c, c->sw_cm_off.p, p.N, p.C, m.vC.p, m.vB.p, p.n_modes, m.fpart.p);
-    } else { // ---- fit_flow_multi_kernel over the members, then the batch's bins / JS launches ------------------------------------------
-        DevBuf<int> flags;
-        DevBuf<double> flow;
-        flags.ensure((size_t)4 * n);
-        HIP_CHECK(hipMemsetAsync(flags.p, 0, sizeof(int) * 4 * n, st));
-        cge_flow_multi tab{};
-        tab.n = n;
-        std::vector<cge_fit_problem> fps(n);
-        for (int i = 0; i < n; i++) {
-            const cge_fused_chain_problem &p = probs[i];
-            mem.emplace_back(new FcMember());
-            FcMember &m = *mem.back();
-            fc_prepare(c, p, m, true);
-            cge_fit_problem &fp = fps[i];
-            fp = cge_fit_problem{};
-            fp.D = m.D.data(); fp.w = m.w.data(); fp.T0 = m.T0.data(); fp.T = m.T.data(); fp.N = p.N; fp.alpha = p.alpha;
-            tab.p[i] = ft_member(c, fp, geo[i], m.fit, flags.p + 4 * i, reinterpret_cast<const cge_fit_fused *>(m.epi_dev.p), p.want);
-        }
-        k_fit_flow_multi(c, tab, geo[0].NW, eps, delta, flow);
-        ft_multi_collect(c, fps.data(), n, tab);
-        cge_bins_multi bins{};
-        cge_js_multi js{};
-        int nb = 0, nj = 0;
-        i64 maxC = 0;
-        for (int i = 0; i < n; i++) {
-            cge_fused_chain_problem &p = probs[i];
-            FcMember &m = *mem[i];
-            p.iters = fps[i].iters;
-            p.status = fps[i].status;
-            fc_collect(c, p, m, m.part.p);
-            if (!((p.want & 1) && p.status == 0)) continue;
-            bins.p[nb++] = cge_bins_problem{m.part.p, m.cm_off.p, m.fc.p, m.ns.p, m.base.p, p.C, geo[i].Nt, 0, m.vB.p};
-            maxC = std::max(maxC, p.C);
-            m.jspart.ensure((size_t)2 * 3 * CGE_PARTIAL_BLOCKS);
-            for (int u = 0; u < p.n_modes; u++, nj++)
-                js.p[nj] = cge_js_problem{m.vC.p, m.vB.p, m.vlen, p.C, p.n_modes == 1 ? 0 : 1 + u, 0, m.jspart.p + (i64)u * 3 * CGE_PARTIAL_BLOCKS,
-                                          m.fpart.p + (i64)u * CGE_PARTIAL_BLOCKS};
-        }
-        k_bins_js_multi(c, bins, nb, maxC, js, nj);
-    }
-    for (int i = 0; i < n; i++) {
-        cge_fused_chain_problem &p = probs[i];
-        FcMember &m = *mem[i];
-        std::vector<double> hf((size_t)2 * CGE_PARTIAL_BLOCKS, std::nan(""));
-        const bool binned = (p.want & 1) && p.status == 0;
-        if (binned) ls_down(c, hf.data(), m.fpart.p, 2 * CGE_PARTIAL_BLOCKS);
-        ls_down(c, p.vectB, m.vB.p, m.vlen + CGE_VECT_B_GUARD);
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (p.vC)
-            for (int u = 0; u < p.n_modes; u++) p.js_fused[u] = binned ? vb_fold(hf.data() + (i64)u * CGE_PARTIAL_BLOCKS) : std::nan("");
-    }
-}
-
-// ---- the testing hook of the local score (include/cge_hip_testing.h: cge_local_score_test) -----------------------------------
-// The stages of the local score on the buffers a sweep keeps them in (the first DevSamples of the context): the device sampler,
-// k_prep_samples, sampled_pair_dist and the tallies -- k_auc_landmark / k_auc_exact, or the epilogue of the fused fit through
-// fused_tables and ft_undirected.  Every check comes before the first launch.
-static void ls_range(const char *what, const i32 *v, i64 cnt, i64 lim) {
-    for (i64 k = 0; k < cnt; k++)
-        if (v[k] < 0 || v[k] >= lim)
-            CGE_THROW(CGE_E_ARG, "local_score_test: %s[%lld] = %d outside 0..%lld", what, (long long)k, (int)v[k], (long long)(lim - 1));
-}
-
-void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
-    hipStream_t st = c->stream;
-    const i64 S = io->S, n = c->n, m = c->m, N = io->N;
-    const int directed = io->directed != 0, form = io->form;
-    const bool landmark_form = form == 1 || form == 4, exact_form = form == 2 || form == 3;
-    // the stages that run
-    const bool draw = io->draw_route != 0;
-    const bool pairs_in = io->pi_in || io->pj_in || io->ni_in || io->nj_in || io->wts_in;
-    const bool draws_in = io->pos_in || io->neg_i_in || io->neg_j_in;
-    const bool dist = io->dpos || io->dneg || (landmark_form && !io->dpos_in);
-    const bool prep = io->pi || io->pj || io->ni || io->nj || io->wts || ((dist || form != 0) && !pairs_in);
-    // ---- the checks --------------------------------------------------------------------------------------------------------------
-    if (S < 1 || S >= ((i64)1 << 28)) CGE_THROW(CGE_E_ARG, "local_score_test: S = %lld samples", (long long)S);
-    if (c->rows_sharded || c->edges_sharded)
-        CGE_THROW(CGE_E_ARG, "local_score_test: not with option shard_rows / shard_ingest (every row and edge on one rank)");
-    if ((draw || prep) && (!c->src.p || !c->dst.p || m <= 0 || n < 2 || (!c->unit_weights && !c->w.p)))
-        CGE_THROW(CGE_E_ARG, "local_score_test: the graph is not resident (cge_set_graph)");
-    if (prep && pairs_in) CGE_THROW(CGE_E_ARG, "local_score_test: the pairs are prepared or supplied, not both");
-    if (pairs_in && (!io->pi_in || !io->pj_in || !io->ni_in || !io->nj_in || !io->wts_in))
-        CGE_THROW(CGE_E_ARG, "local_score_test: supplied pairs are pi_in, pj_in, ni_in, nj_in and wts_in together");
-    if (draws_in && (!io->pos_in || !io->neg_i_in || !io->neg_j_in))
-        CGE_THROW(CGE_E_ARG, "local_score_test: supplied draws are pos_in, neg_i_in and neg_j_in together");
-    if (prep && !draws_in && !draw) CGE_THROW(CGE_E_ARG, "local_score_test: Prepare takes pos_in, neg_i_in and neg_j_in, or a draw");
-    if (io->pos2_in && !prep) CGE_THROW(CGE_E_ARG, "local_score_test: pos2_in goes with Prepare");
-    if ((io->dpos_in != nullptr) != (io->dneg_in != nullptr)) CGE_THROW(CGE_E_ARG, "local_score_test: dpos_in and dneg_in go together");
-    if (io->dpos_in && form == 0) CGE_THROW(CGE_E_ARG, "local_score_test: dpos_in and dneg_in go with a tally");
-    if ((landmark_form || dist) && n < 1) CGE_THROW(CGE_E_ARG, "local_score_test: nothing is resident");
-    if (dist && (!c->Xr.p || c->d <= 0 || c->Xr.n < (size_t)(n * c->d)))
-        CGE_THROW(CGE_E_ARG, "local_score_test: the embedding is not resident (cge_set_embedding)");
-    if (dist && !(io->hi > 0.0)) CGE_THROW(CGE_E_ARG, "local_score_test: hi = %g (the distances are divided by it)", io->hi);
-    if (form != 0 && (N < 1 || N > 46340)) CGE_THROW(CGE_E_ARG, "local_score_test: N = %lld", (long long)N);
-    if (exact_form && prep && N != n)
-        CGE_THROW(CGE_E_ARG, "local_score_test: forms 2 and 3 on prepared pairs take N = n (N = %lld, n = %lld)", (long long)N, (long long)n);
-    if (draws_in && prep) {
-        ls_range("pos_in", io->pos_in, S, m);
-        ls_range("neg_i_in", io->neg_i_in, S, n);
-        ls_range("neg_j_in", io->neg_j_in, S, n);
-    }
-    if (io->pos2_in) ls_range("pos2_in", io->pos2_in, S, m);
-    if (pairs_in) {
-        const i64 lim = exact_form ? (dist ? std::min(N, n) : N) : n;
-        ls_range("pi_in", io->pi_in, S, lim);
-        ls_range("pj_in", io->pj_in, S, lim);
-        ls_range("ni_in", io->ni_in, S, lim);
-        ls_range("nj_in", io->nj_in, S, lim);
-    }
-    if (landmark_form) {
-        if (!io->v2l || !io->vw || !io->lweight) CGE_THROW(CGE_E_ARG, "local_score_test: forms 1 and 4 take v2l, vw and lweight");
-        ls_range("v2l", io->v2l, n, N);
-        if (io->old2new) {
-            ls_range("old2new", io->old2new, N, N);
-            std::vector<char> seen(N, 0);
-            for (i64 l = 0; l < N; l++) {
-                if (seen[io->old2new[l]]) CGE_THROW(CGE_E_ARG, "local_score_test: old2new is not a permutation (%d twice)", (int)io->old2new[l]);
-                seen[io->old2new[l]] = 1;
-            }
-        }
-    }
-    if (form == 1 && !io->Ta) CGE_THROW(CGE_E_ARG, "local_score_test: form 1 takes Ta");
-    if (exact_form && (!io->GD || !io->Ta)) CGE_THROW(CGE_E_ARG, "local_score_test: forms 2 and 3 take GD and Ta");
-    if ((form == 3 || form == 4) && directed) CGE_THROW(CGE_E_ARG, "local_score_test: form %d is undirected only", form);
-    if (form == 4) {
-        if (!io->D || !io->w || !io->T0) CGE_THROW(CGE_E_ARG, "local_score_test: form 4 takes D, w and T0");
-        if (!(io->eps > 0.0) || !(io->delta >= 0.0)) CGE_THROW(CGE_E_ARG, "local_score_test: eps > 0 and delta >= 0");
-        if (!c->opt_pow_exp2)
-            CGE_THROW(CGE_E_ARG, "local_score_test: form 4 makes its power matrix from the stored logarithm (option pow_exp2)");
-        if (!flow_fused_applies(N))
-            CGE_THROW(CGE_E_ARG, "local_score_test: the geometry of the fused persistent fit declines N = %lld", (long long)N);
-    }
-    // ---- Draw --------------------------------------------------------------------------------------------------------------------
-    while (c->dsets.empty()) c->dsets.emplace_back(new DevSamples());
-    DevSamples &ds = *c->dsets[0];
-    DevBuf<i32> d_pos, d_pos2, d_ni, d_nj;
-    io->rounds = 0;
-    if (draw) {
-        d_pos.ensure(S); d_ni.ensure(S); d_nj.ensure(S);
-        if (io->draw_route == 1)
-            k_draw_samples_dev(c, io->seed, io->stream_id, S, directed, d_pos.p, d_ni.p, d_nj.p);
-        else {
-            k_draw_samples_begin(c, io->seed, io->stream_id, S, directed, d_pos.p, d_ni.p, d_nj.p);
-            k_draw_samples_finish(c);
-        }
-        io->rounds = c->samp_pending.round;
-        ls_down(c, io->pos, d_pos.p, S);
-        ls_down(c, io->neg_i, d_ni.p, S);
-        ls_down(c, io->neg_j, d_nj.p, S);
-        ls_down(c, io->attempt, c->samp_attempt.p, S);
-    }
-    // ---- Prepare -----------------------------------------------------------------------------------------------------------------
-    if (prep) {
-        if (draws_in) {
-            ls_up(c, d_pos, io->pos_in, S);
-            ls_up(c, d_ni, io->neg_i_in, S);
-            ls_up(c, d_nj, io->neg_j_in, S);
-        }
-        if (io->pos2_in) ls_up(c, d_pos2, io->pos2_in, S);
-        ds.pi.ensure(S); ds.pj.ensure(S); ds.ni.ensure(S); ds.nj.ensure(S); ds.wts.ensure(S);
-        k_prep_samples(c, d_pos.p, io->pos2_in ? d_pos2.p : d_pos.p, d_ni.p, d_nj.p, c->src.p, c->dst.p, c->w.p, S, directed, ds.pi.p,
-                       ds.pj.p, ds.ni.p, ds.nj.p, ds.wts.p);
-        ls_down(c, io->pi, ds.pi.p, S);
-        ls_down(c, io->pj, ds.pj.p, S);
-        ls_down(c, io->ni, ds.ni.p, S);
-        ls_down(c, io->nj, ds.nj.p, S);
-        ls_down(c, io->wts, ds.wts.p, S);
-    } else if (pairs_in) {
-        ls_up(c, ds.pi, io->pi_in, S);
-        ls_up(c, ds.pj, io->pj_in, S);
-        ls_up(c, ds.ni, io->ni_in, S);
-        ls_up(c, ds.nj, io->nj_in, S);
-        ls_up(c, ds.wts, io->wts_in, S);
-    }
-    // ---- Distances ---------------------------------------------------------------------------------------------------------------
-    if (dist) {
-        ds.dpos.ensure(S); ds.dneg.ensure(S);
-        sampled_pair_dist(c, c->Xr.p, c->d, ds.pi.p, ds.pj.p, S, io->hi, ds.dpos.p);
-        sampled_pair_dist(c, c->Xr.p, c->d, ds.ni.p, ds.nj.p, S, io->hi, ds.dneg.p);
-        ls_down(c, io->dpos, ds.dpos.p, S);
-        ls_down(c, io->dneg, ds.dneg.p, S);
-    }
-    if (io->dpos_in) { // (behind the copies out of the distance stage, when that ran for its outputs)
-        ls_up(c, ds.dpos, io->dpos_in, S);
-        ls_up(c, ds.dneg, io->dneg_in, S);
-    }
-    // ---- Tally -------------------------------------------------------------------------------------------------------------------
-    DevBuf<double> dTa, dTb, dvw, dlw, dout2;
-    DevBuf<i32> dv2l, do2n;
-    std::vector<double> hpart(2 * CGE_PARTIAL_BLOCKS, std::nan(""));
-    if (landmark_form) {
-        ls_up(c, dv2l, io->v2l, n);
-        ls_up(c, dvw, io->vw, n);
-        ls_up(c, dlw, io->lweight, N);
-        if (io->old2new) ls_up(c, do2n, io->old2new, N);
-    }
-    if (form >= 1 && form <= 3) {
-        ls_up(c, dTa, io->Ta, N);
-        if (io->Tb) ls_up(c, dTb, io->Tb, N);
-        dout2.ensure(2);
-    }
-    if (form == 1) {
-        const double *Ta = dTa.p, *Tb = io->Tb ? dTb.p : dTa.p;
-        if (io->old2new) { // T is stored in sweep order: un-permuted, as local_score_tallies does
-            c->sw_rl_T.ensure((size_t)2 * N);
-            k_permute_rows(c, Ta, do2n.p, N, 1, c->sw_rl_T.p);
-            Ta = c->sw_rl_T.p;
-            if (io->Tb) {
-                k_permute_rows(c, Tb, do2n.p, N, 1, c->sw_rl_T.p + N);
-                Tb = c->sw_rl_T.p + N;
-            } else
-                Tb = Ta;
-        }
-        k_auc_landmark(c, Ta, Tb, dv2l.p, dvw.p, dlw.p, ds.pi.p, ds.pj.p, ds.ni.p, ds.nj.p, ds.dpos.p, ds.dneg.p, ds.wts.p, S, io->alpha,
-                       dout2.p);
-    } else if (exact_form) {
-        const bool packed = form == 3;
-        const i64 Nt = (N + 63) / 64;
-        std::vector<double> pk;
-        if (packed) { // the upper tiles of GD, zeros outside the matrix, through the address inline every consumer uses
-            pk.assign((size_t)(Nt * (Nt + 1) / 2) * CGE_TILE_DOUBLES, 0.0);
-            for (i64 i = 0; i < N; i++)
-                for (i64 j = i / 64 * 64; j < N; j++) pk[cge_packed_index(i, j, Nt)] = io->GD[i * N + j];
-            ls_up(c, c->sw_PK, pk.data(), (i64)pk.size());
-        } else
-            ls_up(c, c->sw_GD, io->GD, N * N);
-        k_auc_exact(c, packed ? c->sw_PK.p : c->sw_GD.p, dTa.p, io->Tb ? dTb.p : dTa.p, N, ds.pi.p, ds.pj.p, ds.ni.p, ds.nj.p, ds.wts.p, S,
-                    dout2.p, nullptr, packed);
-        HIP_CHECK(hipStreamSynchronize(st)); // (pk goes out of scope)
-    }
-    if (form >= 1 && form <= 3) {
-        ls_down(c, hpart.data(), c->auc_part.p, 2 * CGE_PARTIAL_BLOCKS);
-        ls_down(c, io->out2, dout2.p, 2);
-    }
-    if (form == 4) {
-        c->sw_scal.ensure(RES_STRIDE);
-        HIP_CHECK(hipMemsetAsync(c->sw_scal.p + RES_AUC, 0xFF, sizeof(double) * 2 * CGE_PARTIAL_BLOCKS, st)); // (NaN until the epilogue writes)
-        OrigView orig;
-        orig.n = n; orig.v2l = dv2l.p; orig.vw = dvw.p; orig.lweight = dlw.p;
-        ScoreGraph G;
-        G.N = N;
-        std::vector<cge_fit_fused> h_epi;
-        fused_tables(c, G, &orig, io->old2new ? do2n.p : nullptr, 1, 0, S, true, h_epi);
-        std::vector<double> hT(N);
-        cge_fit_problem p{};
-        p.D = io->D; p.w = io->w; p.T0 = io->T0; p.T = io->T ? io->T : hT.data(); p.N = N; p.alpha = io->alpha;
-        ft_undirected(c, p, 4, io->eps, io->delta, &h_epi[0], reinterpret_cast<const cge_fit_fused *>(c->sw_fused_epi.p));
-        io->iters = p.iters;
-        io->status = p.status;
-        ls_down(c, hpart.data(), c->sw_scal.p + RES_AUC, 2 * CGE_PARTIAL_BLOCKS);
-        ls_down(c, io->aidx, ds.aidx.p, 4 * S);
-        ls_down(c, io->afac, ds.afac.p, 8 * S);
-        ls_down(c, io->aden, ds.afac.p + 8 * S, (i64)CGE_PARTIAL_BLOCKS);
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (form == 3) c->sw_PK.release(); // (held only while packed sweeps run)
-    if (form != 0 && io->part) std::memcpy(io->part, hpart.data(), sizeof(double) * hpart.size());
-    if (form == 4 && io->out2) { // the block tallies in block order, as the sweep's host adds them
-        double num = 0.0, den = 0.0;
-        for (int b = 0; b < CGE_PARTIAL_BLOCKS; b++) { num += hpart[2 * b]; den += hpart[2 * b + 1]; }
-        io->out2[0] = num;
-        io->out2[1] = den;
-    }
-}
-
-// ---- the testing hook of the sweep's set-up (include/cge_hip_testing.h: cge_sweep_setup_test) ------------------------------------
-// What host_wgcl_sweep does before its first alpha, on a caller's score graph and stage by stage: edge_degrees, plan_layout,
-// prepare_distances, k_pow_prepare, k_pow_matrix -- the sweep's own functions, on the buffers a host-array sweep keeps them in
-// (s_emb .. s_comm, s_degin / s_degout / s_star, sw_*, fp_T).  No fit runs.  Everything that can refuse does so before the first
-// launch, but the layout's own verdict on the tiles.
-void host_sweep_setup_test(cge_ctx *c, cge_sweep_setup_io *io) {
-    hipStream_t st = c->stream;
-    const i64 N = io->N, d = io->d, C = io->C, m = io->m;
-    const int directed = io->directed != 0, form = io->log_form;
-    const bool landmarks = io->landmarks != 0, edges = io->src || io->dst;
-    // the stages that run
-    const bool want_log = io->Lh || io->Ll, want_gd = io->GD != nullptr;
-    const bool want_prep = io->lo_hi || io->D || io->cm_off || io->cm_mem || io->cm_pos || io->T1 || io->T2 || io->TT || want_log || want_gd;
-    io->Tld = io->log_count = 0;
-    io->relabel = io->log_form_ran = 0;
-    // ---- the checks --------------------------------------------------------------------------------------------------------------
-    if (N < 1 || d < 1 || C < 1 || N > 46340) CGE_THROW(CGE_E_ARG, "sweep_setup_test: N = %lld, d = %lld, C = %lld", (long long)N, (long long)d, (long long)C);
-    if (!io->emb || !io->dist || !io->comm) CGE_THROW(CGE_E_ARG, "sweep_setup_test: emb, dist and comm are the score graph");
-    if (c->rows_sharded || c->edges_sharded || c->opt_shard_rows || c->opt_shard_ingest)
-        CGE_THROW(CGE_E_ARG, "sweep_setup_test: not with option shard_rows / shard_ingest (every row and edge on one rank)");
-    if (form < 0 || form > 3) CGE_THROW(CGE_E_ARG, "sweep_setup_test: log_form = %d (0 .. 3)", form);
-    if (form != 0 && !c->opt_pow_exp2) CGE_THROW(CGE_E_ARG, "sweep_setup_test: a stored logarithm needs option pow_exp2");
-    if (form == 3 && N < 256) CGE_THROW(CGE_E_ARG, "sweep_setup_test: the tile-blocked logarithm belongs to the fused fit, from 256 vertices on (N = %lld)", (long long)N);
-    if (want_log && (!io->Lh || !io->Ll)) CGE_THROW(CGE_E_ARG, "sweep_setup_test: Lh and Ll go together");
-    std::vector<i32> hcomm(N);
-    for (i64 i = 0; i < N; i++) {
-        if (io->comm[i] < 1 || io->comm[i] > C) CGE_THROW(CGE_E_ARG, "sweep_setup_test: community id out of range");
-        hcomm[i] = (i32)(io->comm[i] - 1);
-    }
-    if (edges && (!io->src || !io->dst || m < 1)) CGE_THROW(CGE_E_ARG, "sweep_setup_test: an edge list is src, dst and m >= 1");
-    if (directed && !edges) CGE_THROW(CGE_E_ARG, "sweep_setup_test: a directed sweep starts from the degrees of its edge list");
-    if ((io->deg_out || io->deg_in || io->star) && !edges) CGE_THROW(CGE_E_ARG, "sweep_setup_test: the degrees need the edge list");
-    for (i64 e = 0; edges && e < m; e++)
-        if (io->src[e] < 0 || io->src[e] >= N || io->dst[e] < 0 || io->dst[e] >= N)
-            CGE_THROW(CGE_E_ARG, "sweep_setup_test: edge %lld (%d, %d) outside 0..%lld", (long long)e, (int)io->src[e], (int)io->dst[e], (long long)(N - 1));
-    const i64 Nt = (N + 63) / 64, blocked_len = Nt * (Nt + 1) / 2 * 4096;
-    if (want_log && io->log_cap < (form == 3 ? blocked_len : form == 0 ? std::max(blocked_len, N * N) : N * N))
-        CGE_THROW(CGE_E_ARG, "sweep_setup_test: Lh / Ll hold %lld elements, the form may write more", (long long)io->log_cap);
-    // ---- the score graph on the device, as a host-array sweep holds it --------------------------------------------------------
-    c->s_emb.ensure((size_t)N * d); c->s_dist.ensure(N); c->s_comm.ensure(N);
-    HIP_CHECK(hipMemcpyAsync(c->s_emb.p, io->emb, sizeof(double) * N * d, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->s_dist.p, io->dist, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->s_comm.p, hcomm.data(), sizeof(i32) * N, hipMemcpyHostToDevice, st));
-    ScoreGraph G;
-    G.N = N; G.d = d; G.C = C;
-    G.emb = c->s_emb.p; G.dist = c->s_dist.p; G.comm = c->s_comm.p;
-    if (io->vw) {
-        c->s_vw.ensure(N);
-        HIP_CHECK(hipMemcpyAsync(c->s_vw.p, io->vw, sizeof(double) * N, hipMemcpyHostToDevice, st));
-        G.vw = c->s_vw.p;
-    }
-    // ---- the degrees (score_host.cpp: edge_degrees) ----------------------------------------------------------------------------
-    DevBuf<i32> e_src, e_dst;
-    DevBuf<double> e_w;
-    if (edges) {
-        e_src.ensure(m); e_dst.ensure(m);
-        HIP_CHECK(hipMemcpyAsync(e_src.p, io->src, sizeof(i32) * m, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(e_dst.p, io->dst, sizeof(i32) * m, hipMemcpyHostToDevice, st));
-        if (io->w) {
-            e_w.ensure(m);
-            HIP_CHECK(hipMemcpyAsync(e_w.p, io->w, sizeof(double) * m, hipMemcpyHostToDevice, st));
-        }
-        edge_degrees(c, e_src.p, e_dst.p, io->w ? e_w.p : nullptr, m, N, c->s_star);
-        G.deg_in = c->s_degin.p;
-        G.deg_out = c->s_degout.p;
-        if (io->deg_out) HIP_CHECK(hipMemcpyAsync(io->deg_out, c->s_degout.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-        if (io->deg_in) HIP_CHECK(hipMemcpyAsync(io->deg_in, c->s_degin.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-        if (io->star) HIP_CHECK(hipMemcpyAsync(io->star, c->s_star.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-    // ---- the layout ----------------------------------------------------------------------------------------------------------------
-    c->sw_T1.ensure(N); c->sw_T2.ensure(N);
-    c->sw_lohi.ensure(2);
-    SweepLayout lay;
-    const OrigView orig{}; // (landmark mode: what the layout asks of it is that it is there)
-    plan_layout(c, G, landmarks ? &orig : nullptr, directed, lay, false, io->force_relabel != 0);
-    if (form == 3 && !c->bvec_blocks)
-        CGE_THROW(CGE_E_ARG, "sweep_setup_test: the tiles decline this layout (more than 64 community ids in a 64-vertex block, or no tile form for this sweep)");
-    io->relabel = lay.relabel;
-    if (lay.relabel) {
-        if (io->order) HIP_CHECK(hipMemcpyAsync(io->order, c->sw_rl_order.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-        if (io->old2new) HIP_CHECK(hipMemcpyAsync(io->old2new, lay.old2new.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-    }
-    if (io->emb_rl) HIP_CHECK(hipMemcpyAsync(io->emb_rl, G.emb, sizeof(double) * N * d, hipMemcpyDeviceToHost, st));
-    if (io->comm_rl) HIP_CHECK(hipMemcpyAsync(io->comm_rl, G.comm, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-    if (io->vec_rl) {
-        const double *vec[4] = {G.dist, G.vw, G.deg_in, G.deg_out};
-        for (int q = 0; q < 4; q++)
-            if (vec[q]) HIP_CHECK(hipMemcpyAsync(io->vec_rl + q * N, vec[q], sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    }
-    // ---- D, its extrema and normalisation, the community tables, the start vectors ------------------------------------------
-    if (io->D_raw || want_prep) { c->sw_D.ensure((size_t)N * N); c->sw_GD.ensure((size_t)N * N); }
-    if (io->D_raw) {
-        k_dist_matrix(c, G.emb, G.dist, N, d, c->sw_D.p);
-        HIP_CHECK(hipMemcpyAsync(io->D_raw, c->sw_D.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (!want_prep) return;
-    io->Tld = prepare_distances(c, G, lay, directed, false);
-    if (io->lo_hi) HIP_CHECK(hipMemcpyAsync(io->lo_hi, c->sw_lohi.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
-    if (io->D) HIP_CHECK(hipMemcpyAsync(io->D, c->sw_D.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
-    if (io->cm_off) HIP_CHECK(hipMemcpyAsync(io->cm_off, c->sw_cm_off.p, sizeof(i32) * (C + 1), hipMemcpyDeviceToHost, st));
-    if (io->cm_mem) HIP_CHECK(hipMemcpyAsync(io->cm_mem, c->sw_cm_mem.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-    if (io->cm_pos) HIP_CHECK(hipMemcpyAsync(io->cm_pos, c->sw_cm_pos.p, sizeof(i32) * N, hipMemcpyDeviceToHost, st));
-    if (io->T1) HIP_CHECK(hipMemcpyAsync(io->T1, c->sw_T1.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    if (io->T2) HIP_CHECK(hipMemcpyAsync(io->T2, c->sw_T2.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    if (io->TT) HIP_CHECK(hipMemcpyAsync(io->TT, c->fp_T.p, sizeof(double) * 3 * io->Tld, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (!want_log && !want_gd) return;
-    // ---- the logarithm, and the power of one alpha from it ------------------------------------------------------------------
-    const bool upper = form == 0 ? landmarks && !directed : form >= 2, blocked = form == 0 ? lay.fuse : form == 3;
-    const i64 len = blocked ? blocked_len : N * N;
-    if (c->opt_pow_exp2) { // (all bits set: a NaN in both; k_pow_prepare's own ensure finds them large enough)
-        c->sw_Lh.ensure((size_t)len); c->sw_Ll.ensure((size_t)len);
-        HIP_CHECK(hipMemsetAsync(c->sw_Lh.p, 0xFF, sizeof(double) * len, st));
-        HIP_CHECK(hipMemsetAsync(c->sw_Ll.p, 0xFF, sizeof(float) * len, st));
-    }
-    k_pow_prepare(c, c->sw_D.p, N, upper, blocked);
-    io->log_form_ran = c->pow_logs_blocked_N == N ? 3 : c->pow_logs_N != N ? 0 : c->pow_logs_upper ? 2 : 1;
-    io->log_count = io->log_form_ran == 0 ? 0 : len;
-    if (want_log && io->log_form_ran != 0) {
-        HIP_CHECK(hipMemcpyAsync(io->Lh, c->sw_Lh.p, sizeof(double) * len, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(io->Ll, c->sw_Ll.p, sizeof(float) * len, hipMemcpyDeviceToHost, st));
-    }
-    if (want_gd && io->log_form_ran != 3) {
-        HIP_CHECK(hipMemsetAsync(c->sw_GD.p, 0xFF, sizeof(double) * N * N, st)); // (as ft_matrices does)
-        k_pow_matrix(c, c->sw_D.p, N, io->alpha, c->sw_GD.p, upper);
-        HIP_CHECK(hipMemcpyAsync(io->GD, c->sw_GD.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, st));
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-// ---- the testing hook of the packed form (include/cge_hip_testing.h: cge_packed_gd_test) -------------------------------
-// The extrema pass and the generator through the sweep's own launch wrappers on a caller's embedding; the tiles are unpacked on
-// the host through cge_packed_index: GD[i][j] for j >= i, and both halves of the diagonal tiles.
-void host_packed_gd_test(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double alpha, int pow_method, double *lo_hi,
-                         double *GD) {
-    hipStream_t st = c->stream;
-    const i64 Nt = (N + 63) / 64, NT = Nt * (Nt + 1) / 2;
-    DevBuf<double> demb, ddiag, dlohi, PK;
-    demb.ensure((size_t)N * d); ddiag.ensure(N); dlohi.ensure(2); PK.ensure((size_t)NT * CGE_TILE_DOUBLES);
-    HIP_CHECK(hipMemcpyAsync(demb.p, emb, sizeof(double) * N * d, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(ddiag.p, diag, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    k_packed_extrema(c, demb.p, ddiag.p, N, d, dlohi.p);
-    k_packed_gd(c, demb.p, ddiag.p, N, d, dlohi.p, alpha, pow_method, PK.p);
-    std::vector<double> h((size_t)NT * CGE_TILE_DOUBLES);
-    HIP_CHECK(hipMemcpyAsync(h.data(), PK.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(lo_hi, dlohi.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    for (i64 i = 0; i < N; i++)
-        for (i64 j = i / 64 * 64; j < N; j++) GD[i * N + j] = h[cge_packed_index(i, j, Nt)];
-    for (i64 I = 0; I < Nt; I++) // outside the matrix: zeros, which the fit adds unmasked
-        for (i64 J = I; J < Nt; J++)
-            for (i64 r = 0; r < 64; r++)
-                for (i64 q = 0; q < 64; q++)
-                    if ((64 * I + r >= N || 64 * J + q >= N) && h[cge_packed_index(64 * I + r, 64 * J + q, Nt)] != 0.0)
-                        CGE_THROW(CGE_E_ASSERT, "packed_gd_test: a non-zero outside the matrix (tile %lld, %lld)", (long long)I, (long long)J);
-}
-
-// ---- small helpers ---------------------------------------------------------------------------------
-
-static void gather_rows(cge_ctx *c, const i32 *d_arr, const std::vector<i64> &rows0, std::vector<i32> &out,
-                        DevBuf<i32> &d_idx, DevBuf<i32> &d_out) {
-    const i64 S = (i64)rows0.size();
-    std::vector<i32> idx(S);
-    for (i64 k = 0; k < S; k++) idx[k] = (i32)rows0[k];
-    d_idx.ensure(S);
-    d_out.ensure(S);
-    out.resize(S);
-    HIP_CHECK(hipMemcpyAsync(d_idx.p, idx.data(), sizeof(i32) * S, hipMemcpyHostToDevice, c->stream));
-    k_gather_i32(c, d_arr, d_idx.p, S, d_out.p);
-    HIP_CHECK(hipMemcpyAsync(out.data(), d_out.p, sizeof(i32) * S, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
 }
