@@ -19,4 +19,8 @@ def __getattr__(name):  # lazy: importing the package must not need the GPU libr
         from .clustering import louvain_clust
 
         return louvain_clust
+    if name == "ecg_clust":  # an extension: ECG communities into the same <file>.ecg
+        from .clustering import ecg_clust
+
+        return ecg_clust
     raise AttributeError(name)

@@ -65,6 +65,11 @@ class ScoreArgs(C.Structure):
                 ("split", C.c_int), ("seed", C.c_int64), ("auc_samples", C.c_int64)]
 
 
+class EcgArgs(C.Structure):
+    """cge_ecg_args (include/cge_hip.h)."""
+    _fields_ = [("members", C.c_int64), ("w_min", C.c_double), ("seed", C.c_int64), ("final_level", C.c_int64)]
+
+
 class EmbeddingBatch(C.Structure):
     _fields_ = [("embeddings", C.c_void_p), ("K", C.c_int64), ("d", C.c_int64), ("on_device", C.c_int),
                 ("row_major", C.c_int)]
@@ -1393,6 +1398,27 @@ class Context:
             self._check(rc)
             break
         return [(comm[l], int(nc[l]), float(q[l]), int(rounds[l])) for l in range(count.value)]
+
+    def ecg(self, members=16, w_min=0.05, seed=0, final_level=-1, edge_weights=False):
+        """ECG communities of the resident graph (cge_ecg): `members` relabelled level-1 passes, every edge reweighted by how
+        often its ends were co-clustered (w_min off the 2-core), the Louvain hierarchy on those weights.  Returns (comm 0-based
+        (n,), n_comm, modularity on the resident graph, modularity on the reweighted graph[, the new weight of every edge (m,)])."""
+        args = EcgArgs(int(members), float(w_min), int(seed), int(final_level))
+        out = np.zeros(self.n, dtype=np.int64)
+        w = np.zeros(self.m) if edge_weights else None
+        nc, q, q_ecg = C.c_int64(), C.c_double(), C.c_double()
+        self._check(self.L.cge_ecg(self.h, C.byref(args), _p(out), C.byref(nc), C.byref(q), C.byref(q_ecg), _p(w) if edge_weights else None))
+        return (out, nc.value, q.value, q_ecg.value) + ((w,) if edge_weights else ())
+
+    def ecg_members_test(self, members=16, seed=0):
+        """Testing hook (cge_ecg_members_test): the member and peel stages of `ecg` alone -- (members (K, n) each renumbered as a
+        pass is, n_comm (K,), rounds (K,), modularity (K,), core (n,) bool)."""
+        K = int(members)
+        mem = np.zeros((max(K, 1), self.n), dtype=np.int64)
+        nc, rounds, q = np.zeros(max(K, 1), dtype=np.int64), np.zeros(max(K, 1), dtype=np.int64), np.zeros(max(K, 1))
+        core = np.zeros(self.n, dtype=np.int32)
+        self._check(self.L.cge_ecg_members_test(self.h, C.c_int64(K), C.c_int64(int(seed)), _p(mem), _p(nc), _p(rounds), _p(q), _p(core)))
+        return mem, nc, rounds, q, core.astype(bool)
 
     _TEST_OPTIONS = ("louvain_wave_len", "fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
                      "exact_resident_limit", "test_eig_roles")

@@ -38,7 +38,8 @@ METHODS = {
 USAGE = (
     "\n\nUsage:\n"
     "\tpython cge_cli.py -g edgelist -e embedding [-c communities] [--seed seed] [--samples-local samples] [-v] [-d] "
-    "[--split-global] [-l [landmarks]] [-f [forced]] [--force-exact] [-m method] [--louvain-level level]\n"
+    "[--split-global] [-l [landmarks]] [-f [forced]] [--force-exact] [-m method] [--louvain-level level] "
+    "[--ecg [members]] [--ecg-wmin w_min]\n"
 )
 
 
@@ -87,7 +88,11 @@ def parseargs(argv=None, exit_on_error=True, embedding_reader=None):
 
     `--louvain-level K` is an EXTENSION, the reference has no such flag: without `-c` the communities are level K of the Louvain
     hierarchy (K >= 1: level K, or the last level when the hierarchy is shorter; -1: the last level) instead of the level 1 the
-    reference writes.  The flag is consulted only when `-c` is absent; absent flag means level 1."""
+    reference writes.  The flag is consulted only when `-c` is absent; absent flag means level 1.
+
+    `--ecg [K]` (an EXTENSION too; K missing or not a number: 16) takes ECG communities instead (`ecg_clust`: K relabelled level-1
+    passes, edges reweighted by co-membership, the last level of the hierarchy on those weights), with `--ecg-wmin x` (default 0.05)
+    for the floor weight and `--seed` (else 0) for the relabellings.  Ignored with `-c`; an error together with `--louvain-level`."""
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
         verbose = "-v" in argv
@@ -118,15 +123,28 @@ def parseargs(argv=None, exit_on_error=True, embedding_reader=None):
         if "-c" in argv:
             fn_comm = _flag_value(argv, "-c")
         else:  # :115-121: no -c => Louvain communities (level 1) of the graph itself, written to <edgelist>.ecg
-            from .clustering import louvain_clust
+            from .clustering import ecg_clust, louvain_clust
 
             level = int(_flag_value(argv, "--louvain-level")) if "--louvain-level" in argv else 1  # (an extension)
             if level < 1 and level != -1:
                 raise AssertionError("--louvain-level is 1, 2, ... or -1 (the last level)")
+            clust, how = louvain_clust, dict(level=level)
+            if "--ecg" in argv:  # (an extension) ECG communities instead of Louvain's
+                if "--louvain-level" in argv:
+                    raise AssertionError("--ecg and --louvain-level exclude each other")
+                members = _flag_value(argv, "--ecg")
+                members = int(members) if members is not None and members.isdigit() else 16  # as -l: a missing number is the default
+                w_min = float(_flag_value(argv, "--ecg-wmin")) if "--ecg-wmin" in argv else 0.05
+                if not 1 <= members <= 64:
+                    raise AssertionError("--ecg takes 1 .. 64 members")
+                if not 0.0 <= w_min < 1.0:
+                    raise AssertionError("--ecg-wmin is in [0, 1)")
+                clust = ecg_clust
+                how = dict(members=members, w_min=w_min, seed=int(_flag_value(argv, "--seed")) if "--seed" in argv else 0)
             if no_cols == 2:
-                louvain_clust(float(v_min), fn_edges, level=level)
+                clust(float(v_min), fn_edges, **how)
             else:
-                louvain_clust(fn_edges, edges, eweights, level=level)
+                clust(fn_edges, edges, eweights, **how)
             fn_comm = fn_edges + ".ecg"
         comm_raw, _ = _readdlm(fn_comm)
         if not np.all(comm_raw == np.floor(comm_raw)):

@@ -20,8 +20,9 @@ def _write_ecg(path, ids, comm):
         f.write("\n")
 
 
-def _communities(edges1, weights, ctx, level=1):
-    """edges1: (m, 2) 1-based int64; returns comm (n,) for vertices 1..n, 0-based consecutive labels."""
+def _communities(edges1, weights, ctx, level=1, ecg=None):
+    """edges1: (m, 2) 1-based int64; returns comm (n,) for vertices 1..n, 0-based consecutive labels.  `ecg` (a dict of members,
+    w_min, seed): ECG communities instead of a Louvain level."""
     from . import api
 
     level = int(level)
@@ -30,11 +31,33 @@ def _communities(edges1, weights, ctx, level=1):
     ctx = ctx or api.default_context()
     n = int(edges1.max())
     ctx.set_graph(np.asfortranarray(edges1), np.ones(len(edges1)) if weights is None else weights, n)
-    if level == 1:
+    if ecg is not None:
+        comm, n_comm, q, _ = ctx.ecg(**ecg)
+    elif level == 1:
         comm, n_comm, q, rounds = ctx.louvain()
     else:  # level k, or the last when the hierarchy is shorter (-1: the last)
         comm, n_comm, q, rounds = ctx.louvain_levels(max_levels=max(level, 0))[-1]
     return comm, n_comm, q
+
+
+def _clust(name, args, ctx, **how):
+    from . import api
+
+    if len(args) == 2:
+        v_min, path = args
+        raw, _ = api.read_table(path, column_major=False)
+        e = raw[:, :2].astype(np.int64)
+        shift = 1 if float(v_min) == 0.0 else 0
+        comm, _, _ = _communities(e + shift, None, ctx, **how)
+        n = len(comm)
+        _write_ecg(path + ".ecg", np.arange(n) + (1 - shift), comm)
+        return path + ".ecg"
+    if len(args) == 3:
+        filename, edges, weights = args
+        comm, _, _ = _communities(np.asarray(edges, dtype=np.int64), np.asarray(weights, dtype=np.float64), ctx, **how)
+        _write_ecg(filename + ".ecg", np.arange(len(comm)) + 1, comm)  # the weighted form always drops row 0 (:67)
+        return filename + ".ecg"
+    raise TypeError(f"{name}(v_min, edges_file) or {name}(filename, edges, weights)")
 
 
 def louvain_clust(*args, ctx=None, level=1):
@@ -45,20 +68,11 @@ def louvain_clust(*args, ctx=None, level=1):
 
     ``level`` (keyword only; an extension, the reference always writes level 1): k >= 1 writes level k of the Louvain
     hierarchy, or its last level if it has fewer; -1 writes the last level."""
-    from . import api
+    return _clust("louvain_clust", args, ctx, level=level)
 
-    if len(args) == 2:
-        v_min, path = args
-        raw, _ = api.read_table(path, column_major=False)
-        e = raw[:, :2].astype(np.int64)
-        shift = 1 if float(v_min) == 0.0 else 0
-        comm, _, _ = _communities(e + shift, None, ctx, level)
-        n = len(comm)
-        _write_ecg(path + ".ecg", np.arange(n) + (1 - shift), comm)
-        return path + ".ecg"
-    if len(args) == 3:
-        filename, edges, weights = args
-        comm, _, _ = _communities(np.asarray(edges, dtype=np.int64), np.asarray(weights, dtype=np.float64), ctx, level)
-        _write_ecg(filename + ".ecg", np.arange(len(comm)) + 1, comm)  # the weighted form always drops row 0 (:67)
-        return filename + ".ecg"
-    raise TypeError("louvain_clust(v_min, edges_file) or louvain_clust(filename, edges, weights)")
+
+def ecg_clust(*args, ctx=None, members=16, w_min=0.05, seed=0):
+    """An extension: the two call forms of ``louvain_clust`` and the same ``<file>.ecg``, with ECG communities
+    (``cge_ecg``: `members` relabelled level-1 passes, edges reweighted by co-membership with the floor `w_min` off the 2-core, the
+    last level of the Louvain hierarchy on those weights) -- how the community files the reference ships were made."""
+    return _clust("ecg_clust", args, ctx, ecg=dict(members=members, w_min=w_min, seed=seed))

@@ -293,6 +293,46 @@ int cge_louvain_levels(cge_ctx *c, int64_t max_levels, int64_t levels_cap, int64
     CGE_CATCH(c)
 }
 
+// ---- ECG: an ensemble of relabelled level-1 passes, edges reweighted by co-membership, the hierarchy on those weights ----
+// the checks that need no device come first (as cge_score_batch)
+static int ecg_check_args(cge_ctx *c, const cge_ecg_args *a) {
+    CGE_TRY(c)
+    if (a->members < 1 || a->members > 64) CGE_THROW(CGE_E_ARG, "ecg: members = %lld is outside 1 .. 64", (long long)a->members);
+    if (!(a->w_min >= 0.0 && a->w_min < 1.0)) CGE_THROW(CGE_E_ARG, "ecg: w_min = %g is not in [0, 1)", a->w_min);
+    if (a->final_level == 0 || a->final_level < -1)
+        CGE_THROW(CGE_E_ARG, "ecg: final_level = %lld is not 1, 2, ... or -1 (the last level)", (long long)a->final_level);
+    CGE_CATCH(c)
+}
+static void ecg_need_graph(cge_ctx *c) {
+    if (!c->src.p || c->m <= 0 || c->n <= 0) CGE_THROW(CGE_E_ARG, "ecg: no resident graph (cge_set_graph)");
+    if (c->edges_sharded) CGE_THROW(CGE_E_ARG, "ecg: the resident edge list is sharded over the ranks (option shard_ingest)");
+}
+int cge_ecg(cge_ctx *c, const cge_ecg_args *a, int64_t *comm_out, int64_t *n_comm, double *modularity, double *modularity_ecg,
+            double *edge_weights_out) {
+    if (!c || !a || !comm_out || !n_comm || !modularity) return CGE_E_ARG;
+    if (int rc = ecg_check_args(c, a)) return rc;
+    CGE_TRY_ON_DEVICE(c)
+    ecg_need_graph(c);
+    EcgHostOut o;
+    o.comm = comm_out; o.n_comm = n_comm; o.q = modularity; o.q_ecg = modularity_ecg; o.edge_w = edge_weights_out;
+    k_ecg(c, a->members, a->w_min, a->seed, a->final_level, false, o);
+    CGE_CATCH(c)
+}
+// the testing hook (include/cge_hip_testing.h): the member and peel stages alone
+int cge_ecg_members_test(void *ctx, int64_t members, int64_t seed, int64_t *members_out, int64_t *n_comm, int64_t *rounds,
+                         double *modularity, int32_t *core_out) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    const cge_ecg_args args = {members, 0.0, seed, -1}, *a = &args;
+    if (!c || !members_out || !n_comm || !rounds || !modularity || !core_out) return CGE_E_ARG;
+    if (int rc = ecg_check_args(c, a)) return rc;
+    CGE_TRY_ON_DEVICE(c)
+    ecg_need_graph(c);
+    EcgHostOut o;
+    o.member_comm = members_out; o.member_nc = n_comm; o.member_rounds = rounds; o.member_q = modularity; o.core = core_out;
+    k_ecg(c, a->members, a->w_min, a->seed, a->final_level, true, o);
+    CGE_CATCH(c)
+}
+
 // ---- options / statistics ---------------------------------------------------------------------------
 int cge_set_option(cge_ctx *c, const char *key, int64_t value) {
     if (!c || !key) return CGE_E_ARG;
@@ -339,6 +379,9 @@ int cge_set_option(cge_ctx *c, const char *key, int64_t value) {
     // 0 (default) = where the resident matrices would be refused, 1 = wherever the form applies (N >= 256, C >= 2, exact_relabel)
     if (is("exact_packed")) return ranged(c->opt_exact_packed, 0, 1);
     if (is("fit_max_iterations")) return ranged(c->opt_fit_max_iters, 1, INT64_MAX);
+    // cge_ecg: members whose rounds run in lock-step, one set of launches and one read-back per round; 0 (default) = as many as
+    // the memory holds up to the built-in bound, g >= 1 = at most g.  The results do not depend on it
+    if (is("ecg_group")) return ranged(c->opt_ecg_group, 0, 64);
     return CGE_E_ARG;
 }
 // the testing knobs (include/cge_hip_testing.h): not part of the boundary
@@ -382,6 +425,10 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "landmark_batches")) *value = c->stat_lm_batches;
     else if (!strcmp(key, "landmark_batch_rows")) *value = c->stat_lm_rows;
     else if (!strcmp(key, "landmark_splits")) *value = c->stat_lm_splits;
+    else if (!strcmp(key, "ecg_groups")) *value = c->stat_ecg_groups; // of the last cge_ecg: lock-step groups,
+    else if (!strcmp(key, "ecg_member_rounds")) *value = c->stat_ecg_member_rounds; // rounds summed over the members,
+    else if (!strcmp(key, "ecg_peel_rounds")) *value = c->stat_ecg_peel_rounds;     // rounds of the 2-core that removed a vertex,
+    else if (!strcmp(key, "ecg_levels")) *value = c->stat_ecg_levels;               // levels of the final hierarchy
     else if (!strcmp(key, "cut_tie_tasks")) { // (read from the device on request: a synchronising copy)
         int v = 0;
         if (c->cut_ties.p && (hipStreamSynchronize(c->stream) != hipSuccess ||

@@ -417,6 +417,8 @@ struct cge_ctx {
                                 // one); the results must not depend on it
     i64 opt_test_louvain_wave_len = -2; // testing: Louvain levels >= 2 decide segments longer than this by a wave (-2: the default
                                         // length, -1: every vertex, 2^31 - 1: none); the results must not depend on it
+    int opt_ecg_group = 0; // cge_ecg: members that run their rounds in lock-step (0: chosen from the free memory, g >= 1: at most g)
+    i64 stat_ecg_groups = 0, stat_ecg_member_rounds = 0, stat_ecg_peel_rounds = 0, stat_ecg_levels = 0; // last cge_ecg
     int opt_test_bvec_plain = 0; // testing: vect_B without LDS staging / rows in flight (the forms of very large score graphs)
     int opt_fit_persistent = 0; // 0 auto (score graphs of >= 128 vertices that fit the register file), 1 never, 2 whenever it fits
     i64 opt_fit_max_iters = 2000000; // a Chung-Lu fit that has not met `diff <= delta` (src/divergence.jl:151,434) after this many
@@ -777,6 +779,16 @@ void k_degrees_unpack(cge_ctx *c, const double *in3N, i64 N, double *deg_out, do
 void k_louvain_level1(cge_ctx *c, i64 *comm_out_host, i64 *n_comm, double *quality, i64 *rounds); // kernels_louvain.hip
 // the whole hierarchy (or its first max_levels > 0 levels): returns their number, writes the first levels_cap of them
 i64 k_louvain_levels(cge_ctx *c, i64 max_levels, i64 levels_cap, i64 *comm_out_host, i64 *n_comm, double *quality, i64 *rounds);
+// ECG (kernels_louvain.hip): K relabelled level-1 members, the 2-core, the reweighted graph, the hierarchy on it.  The `member_*`
+// and `core_out` host arrays are the testing hook's (all NULL otherwise); members_only stops after the peel
+struct EcgHostOut {
+    i64 *comm = nullptr, *n_comm = nullptr;
+    double *q = nullptr, *q_ecg = nullptr, *edge_w = nullptr;
+    i64 *member_comm = nullptr, *member_nc = nullptr, *member_rounds = nullptr;
+    double *member_q = nullptr;
+    i32 *core = nullptr;
+};
+void k_ecg(cge_ctx *c, i64 K, double w_min, i64 seed, i64 final_level, bool members_only, const EcgHostOut &o);
 // distances
 void k_dist_matrix(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d, double *D);
 void k_minmax_upper(cge_ctx *c, const double *D, i64 N, double *lo_hi);

@@ -169,6 +169,23 @@ function louvain_levels(c::Ctx, n::Integer; max_levels::Integer = 0)
     return [(comm[:, l], nc[l], q[l], rounds[l]) for l in 1:count[]]
 end
 
+# ECG communities of the resident graph (cge_ecg, an extension): (comm 0-based of the n vertices, n_comm, modularity on the
+# resident graph, modularity on the reweighted graph)
+struct EcgArgs
+    members::Int64
+    w_min::Float64
+    seed::Int64
+    final_level::Int64
+end
+function ecg(c::Ctx, n::Integer; members::Integer = 16, w_min::Real = 0.05, seed::Integer = 0, final_level::Integer = -1)
+    comm, nc, q, q_ecg = Vector{Int64}(undef, n), Ref{Int64}(0), Ref{Float64}(0.0), Ref{Float64}(0.0)
+    a = EcgArgs(members, w_min, seed, final_level)
+    check(c, ccall((:cge_ecg, LIB), Cint,
+                   (Ptr{Cvoid}, Ref{EcgArgs}, Ptr{Int64}, Ref{Int64}, Ref{Float64}, Ref{Float64}, Ptr{Float64}),
+                   c.h, Ref(a), comm, nc, q, q_ecg, C_NULL))
+    return comm, nc[], q[], q_ecg[]
+end
+
 # clusters derived from the resident communities (src/auxilary.jl:199-208): n_clusters = -1, the two pointers are ignored
 function landmarks_run_from_comm!(c::Ctx, land::Int, forced::Int, method::Function, directed::Bool)
     N, ne, trunc = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)

@@ -8,7 +8,8 @@ evaluated alpha and a newline go to stderr (src/divergence.jl:140,255).
     python cge_cli.py -g graph.edgelist -c graph.ecg -e graph.embedding -l 200 --seed 42
 
 An extension, not a flag of the reference: without `-c`, `--louvain-level K` takes level K of the Louvain hierarchy of the
-graph (-1: the last level) for the communities instead of level 1.
+graph (-1: the last level) for the communities instead of level 1, and `--ecg [K]` (K = 16 members when left out; `--ecg-wmin x`
+for the floor weight, default 0.05; the relabellings seeded by `--seed`, else 0) takes ECG communities instead of Louvain's.
 """
 import os
 import sys

@@ -9,7 +9,8 @@ dtype (float64 / float32 / float16), so `.npy` files of different dtype and widt
 
     python cge_compare.py -g graph.edgelist -c graph.ecg -e a.embedding -e b.embedding -l 200 --seed 42
 
-As in cge_cli.py, `--louvain-level K` (an extension; the reference has no such flag) chooses the Louvain level when `-c` is absent.
+As in cge_cli.py, `--louvain-level K` (an extension; the reference has no such flag) chooses the Louvain level when `-c` is absent,
+and `--ecg [K]` / `--ecg-wmin x` take ECG communities instead.
 """
 import os
 import sys

@@ -344,6 +344,26 @@ int cge_louvain_levels(cge_ctx *ctx, int64_t max_levels /* <= 0: until a level m
                        int64_t *comm_out /* levels_cap x n, level-major; may be NULL with levels_cap 0 */, int64_t *n_levels,
                        int64_t *n_comm /* [levels_cap] */, double *modularity /* [levels_cap] */, int64_t *rounds /* [levels_cap] */);
 
+/* ---- ECG communities (an extension; the reference ships *.ecg files made by Ensemble Clustering for Graphs, Poulin & Theberge) ----
+ * `members` level-1 passes of cge_louvain's kind on the resident graph, member r under the vertex names rank_r (v ordered by
+ * (mix(base_r ^ v), v), mix = splitmix64, base_r = mix(seed ^ mix(r))); the 2-core on adjacency entries (repeated edges are
+ * separate entries, self loops are none); every edge reweighted  w_min + (1 - w_min) c / members  (c = members that put both its
+ * ends in one community) when both ends are in the 2-core, w_min otherwise -- the graph's own weights drive the members and do not
+ * enter these; then the Louvain hierarchy on the reweighted graph, of which level final_level (-1: the last; k >= 1: level k, or
+ * the last of a shorter hierarchy) is returned.  comm_out[v] in 0 .. *n_comm-1; *modularity is that partition's on the resident
+ * graph with its own weights, *modularity_ecg on the reweighted graph; edge_weights_out receives the new weight of every edge.
+ * Departures from the published algorithm: the members are synchronous passes diversified by relabelling alone, and the 2-core
+ * counts adjacency entries.  CGE_E_ARG with a message, before any device work: members outside 1 .. 64, w_min not in [0, 1) (or
+ * NaN), final_level 0 or below -1; then as cge_louvain: no resident graph, a sharded edge list.  On integer and dyadic weights
+ * with members and 1 / w_min powers of two everything is determined to the bit; with other values (the default w_min = 0.05)
+ * the members still are (on such graph weights), but the final hierarchy runs on real weights, where -- as for cge_louvain_levels -- only the quality
+ * is comparable and two calls may break a tie differently.  Results never depend on option "ecg_group".
+ * Stats: "ecg_groups", "ecg_member_rounds" (summed over the members), "ecg_peel_rounds", "ecg_levels". */
+typedef struct { int64_t members; double w_min; int64_t seed; int64_t final_level; } cge_ecg_args;
+int cge_ecg(cge_ctx *ctx, const cge_ecg_args *args, int64_t *comm_out /* n, 0-based consecutive */, int64_t *n_comm,
+            double *modularity /* original graph */, double *modularity_ecg /* reweighted graph, may be NULL */,
+            double *edge_weights_out /* m, edge order, may be NULL */);
+
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */
 int cge_js(cge_ctx *ctx, const double *vC, const double *vB, int64_t len, const uint8_t *vI, int internal,
@@ -439,7 +459,11 @@ int cge_max_pair_dist(cge_ctx *ctx, int part, int nparts, double *hi, int64_t *a
  *             a resident sweep with "fit_persistent" = 1 and "bvec_blocks" = 1).  Directed sweeps are not affected.
  * "bvec_blocks": 1 = sweeps from 256 vertices on relabel the score graph by community and sum vect_B by 64 x 64 tiles (one read of
  *             GD); 0 (default) = row bins + row sums + fold below 8192 vertices (beyond that the sweep is relabelled and uses the
- *             tiles anyway).  Same results up to the rounding of the summation order; measured no faster at the headline.  */
+ *             tiles anyway).  Same results up to the rounding of the summation order; measured no faster at the headline.
+ * "ecg_group": cge_ecg runs its members in lock-step groups (one set of launches, one segmented sort and one read-back per round
+ *             for the whole group; a member that has stopped is masked out): 0 (default) = as many as half the free memory holds
+ *             with group x adjacency entries < 2^31, up to the built-in bound; g = 1 .. 64 = at most g (1: one member at a
+ *             time).  The results do not depend on it.  */
 int cge_set_option(cge_ctx *ctx, const char *key, int64_t value);
 /* "landmarks" (N of the last run, no side effects), "diameter_path" (1 brute / 2 pruned), "diameter_candidate_pairs", "diameter_candidate_tiles", "diameter_refs" (reference points) of the last run;
  * "collective_calls" / "collective_bytes" = all-reduces issued by the in-library RCCL path since cge_create;

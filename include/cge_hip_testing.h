@@ -434,6 +434,11 @@ typedef struct cge_resident_graph {
     int64_t cap_edges, cap_vertices, cap_comm16;
 } cge_resident_graph;
 int cge_resident_graph_test(void *ctx, cge_resident_graph *out);
+/* needs the GPU: the member and peel stages of cge_ecg alone (members and seed as in cge_ecg_args, the same refusals).  members_out: members x n,
+ * member r's partition renumbered 0 .. n_comm[r]-1 in ascending order of its labels, as a pass's is; rounds[r] and modularity[r]
+ * go with it; core_out[v] = 1 where v is in the 2-core.  The stats "ecg_groups", "ecg_member_rounds", "ecg_peel_rounds" are set */
+int cge_ecg_members_test(void *ctx, int64_t members, int64_t seed, int64_t *members_out, int64_t *n_comm, int64_t *rounds,
+                         double *modularity, int32_t *core_out);
 #ifdef __cplusplus
 }
 #endif
