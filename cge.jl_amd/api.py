@@ -1043,7 +1043,8 @@ class Context:
         (0 = what a sweep of this shape picks) and, with vC, its divergence by the device-side modes.  `second`: the
         (GD, Ta, Tb, comm, C[, vC]) of form 6's other problem.  GD = None with vB and vC: the "JS only" mode.
         Returns a dict: form_ran, vectB, guard (the doubles behind the vector on the device: all NaN unless something wrote
-        past its end), js_dev (3,), js_fused (n_modes,) for forms 5 and 6; second_* for form 6's other problem."""
+        past its end), js_dev (3,), js_fused (n_modes,) for forms 5 and 6; second_* for form 6's other problem.  Form 7: directed,
+        tiles + bins on the packed upper tiles of a symmetric GD."""
         keep, out = [], {}
 
         def problem(GD, Ta, Tb, comm, C_, vC, vB, tag):
@@ -1086,7 +1087,8 @@ class Context:
         """Testing hook (include/cge_hip_testing.h: cge_fit_test): one Chung-Lu fit per problem from a chosen start by a named
         form of the sweep (0 = what an exact-mode sweep of the shape picks).  A problem is a dict: D (N, N), alpha, w, T0
         (undirected) or D, alpha, w = deg_in, w2 = deg_out, T0 = Tin, T0b = Tout (directed); several problems are form 5
-        (undirected) or form 6 (directed) only.
+        (undirected) or form 6 (directed) only.  Forms 7 / 8: directed, one launch pair per iteration by the tile kernels on the
+        row-major GD / on the packed tiles.
         eps defaults to the sweep's (0.25 undirected, 0.9 directed).  Returns (form_ran, [dict(T, Tb, GD, iters, status)]): Tb
         and GD are None where they do not apply / were not asked for."""
         if isinstance(problems, dict):
@@ -1247,7 +1249,7 @@ class Context:
           draws = (pos, neg_i, neg_j), pos2: supplied draws for Prepare; prepare=True -> pi, pj, ni, nj, wts;
           pairs = (pi, pj, ni, nj, wts): supplied pairs in place of Prepare; hi with distances=True -> dpos, dneg;
           dists = (dpos, dneg): supplied distances for the tally;
-          tally = dict(form, N, alpha, Ta, Tb, v2l, vw, lweight, old2new, GD, D, w, T0, eps, delta) -> part (64, 2), out2 and,
+          tally = dict(form (5: k_auc_exact on the packed tiles with ordered pairs), N, alpha, Ta, Tb, v2l, vw, lweight, old2new, GD, D, w, T0, eps, delta) -> part (64, 2), out2 and,
             form 4, T, aidx (4, S), afac (8, S), aden (64,), iters, status.
         Returns a dict of what the stages that were asked for give."""
         S = int(S)
@@ -1421,7 +1423,7 @@ class Context:
         return mem, nc, rounds, q, core.astype(bool)
 
     _TEST_OPTIONS = ("louvain_wave_len", "fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
-                     "exact_resident_limit", "test_eig_roles")
+                     "exact_resident_limit", "test_eig_roles", "fit_dir_tiles")
 
     def set_option(self, key, value):
         if key in self._TEST_OPTIONS:  # the testing knobs are not part of the boundary (include/cge_hip_testing.h)

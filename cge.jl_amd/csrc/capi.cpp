@@ -378,6 +378,10 @@ int cge_set_option(cge_ctx *c, const char *key, int64_t value) {
     // an undirected exact sweep on the upper tiles of the current alpha's GD alone (about 4 N^2 bytes instead of 17.6 - 28 N^2):
     // 0 (default) = where the resident matrices would be refused, 1 = wherever the form applies (N >= 256, C >= 2, exact_relabel)
     if (is("exact_packed")) return ranged(c->opt_exact_packed, 0, 1);
+    // the same form for a directed exact sweep (the model's matrix is symmetric; the fit, vect_B and the tallies read the upper
+    // tiles): 0 (default) = never, refused beyond the resident limit; 1 = where the resident matrices would be refused; 2 = wherever
+    // the form applies (N >= 256, C >= 2, exact_relabel).  Never a persistent fit; no effect on undirected or landmark-mode sweeps
+    if (is("exact_packed_directed")) return ranged(c->opt_exact_packed_directed, 0, 2);
     if (is("fit_max_iterations")) return ranged(c->opt_fit_max_iters, 1, INT64_MAX);
     // cge_ecg: members whose rounds run in lock-step, one set of launches and one read-back per round; 0 (default) = as many as
     // the memory holds up to the built-in bound, g >= 1 = at most g.  The results do not depend on it
@@ -401,6 +405,9 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     // bytes that replace the 200e9 of the resident exact sweep's guard (0: the default)
     // Louvain levels >= 2: segments longer than this are decided by a wave (-2: the default, -1: every vertex, 2^31 - 1: none)
     if (!strcmp(key, "louvain_wave_len") && value >= -2 && value <= INT32_MAX) { c->opt_test_louvain_wave_len = value; return CGE_OK; }
+    // 1 = a resident directed launch-per-iteration fit goes by the tile pair (fit_symtile_dir_kernel<false>), the comparator of the
+    // packed directed sweep
+    if (!strcmp(key, "fit_dir_tiles")) { c->opt_test_fit_dir_tiles = value != 0; return CGE_OK; }
     if (!strcmp(key, "exact_resident_limit") && value >= 0) { c->opt_test_resident_limit = (double)value; return CGE_OK; }
     return CGE_E_ARG;
 }
@@ -625,7 +632,7 @@ int cge_packed_gd_test(void *ctx, const double *emb, const double *diag, int64_t
 int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_problem *p2, int directed, int form, int landmarks,
                     int n_modes, int *form_ran) {
     cge_ctx *c = (cge_ctx *)ctx;
-    if (!c || !p || !form_ran || form < 0 || form > 6 || n_modes < 1 || n_modes > 2) return CGE_E_ARG;
+    if (!c || !p || !form_ran || form < 0 || form > 7 || n_modes < 1 || n_modes > 2) return CGE_E_ARG;
     CGE_TRY_ON_DEVICE(c)
     host_vect_b_test(c, p, p2, directed != 0, form, landmarks, n_modes, form_ran);
     CGE_CATCH(c)
@@ -634,7 +641,7 @@ int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_pro
 // testing hook (include/cge_hip_testing.h): one Chung-Lu fit from a caller's start by one named form of the sweep
 int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int directed, int form, double eps, double delta, int *form_ran) {
     cge_ctx *c = (cge_ctx *)ctx;
-    if (!c || !problems || !form_ran || form < 0 || form > 6 || n_problems < 1) return CGE_E_ARG;
+    if (!c || !problems || !form_ran || form < 0 || form > 8 || n_problems < 1) return CGE_E_ARG;
     CGE_TRY_ON_DEVICE(c)
     host_fit_test(c, problems, n_problems, directed != 0, form, eps, delta, form_ran);
     CGE_CATCH(c)
@@ -662,7 +669,7 @@ int cge_sweep_setup_test(void *ctx, cge_sweep_setup_io *io) {
 // testing hook (include/cge_hip_testing.h): the local score's sampler, prepared pairs, pair distances and tallies, stage by stage
 int cge_local_score_test(void *ctx, cge_local_score_io *io) {
     cge_ctx *c = (cge_ctx *)ctx;
-    if (!c || !io || io->form < 0 || io->form > 4 || io->draw_route < 0 || io->draw_route > 2) return CGE_E_ARG;
+    if (!c || !io || io->form < 0 || io->form > 5 || io->draw_route < 0 || io->draw_route > 2) return CGE_E_ARG;
     CGE_TRY_ON_DEVICE(c)
     host_local_score_test(c, io);
     CGE_CATCH(c)

@@ -373,6 +373,10 @@ struct cge_ctx {
     // (cge_packed_index below), made from the embedding rows every alpha; no D, no logarithm, no row-major GD
     DevBuf<double> sw_PK;
     int opt_exact_packed = 0;           // 0 auto (where the resident matrices would be refused), 1 whenever the form applies
+    // the same form for a directed exact sweep (the model's matrix is symmetric; only Tin / Tout are not): 0 never (refused beyond
+    // the resident limit), 1 where the resident matrices would be refused, 2 wherever the form applies
+    int opt_exact_packed_directed = 0;
+    int opt_test_fit_dir_tiles = 0;     // testing: a resident directed launch-per-iteration fit goes by the tile pair (kernels_fitp.hip)
     double opt_test_resident_limit = 0; // testing: replaces the 200e9 bytes of the resident form's guard (0: the default)
     i64 stat_exact_packed = 0;          // the last sweep ran packed
     i64 stat_exact_matrix_bytes = 0;    // O(N^2) device bytes the last exact sweep required
@@ -985,7 +989,7 @@ struct cge_bins_multi { cge_bins_problem p[CGE_BATCH_MAX]; };
 struct cge_js_multi { cge_js_problem p[2 * CGE_BATCH_MAX]; }; // (--split-global: two entries per problem)
 void k_bins_js_multi(cge_ctx *c, const cge_bins_multi &bins, int n_bins, i64 max_C, const cge_js_multi &js, int n_js);
 void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *Tb, const i32 *cm_off, i64 N, int directed,
-                  bool packed = false); // the tile partials only (packed: GD is the upper tiles of cge_packed_index, undirected)
+                  bool packed = false); // the tile partials only (packed: GD is the upper tiles of cge_packed_index)
 void k_auc_prepare(cge_ctx *c, const i32 *v2l, const i32 *old2new, const double *vw_orig, const double *lweight, const i32 *pi,
                    const i32 *pj, const i32 *ni, const i32 *nj, const double *wts, i64 S, i32 *aidx, double *afac, double *aden);
 void k_bvec_bins(cge_ctx *c, const i32 *cm_off, i64 N, i64 C, int directed, double *vectB); // folds the tile partials into vect_B
@@ -996,6 +1000,9 @@ void k_fit_verdict(cge_ctx *c, const int *flags, int async, double *out); // 1.0
 // the same iteration over the upper 64 x 64 tiles only (kernels_fitp.hip): half the matrix traffic
 void k_fit_sym_step(cge_ctx *c, const double *GD, const double *Tin, double *Tout, const double *w, i64 N, double eps,
                 double delta, int k, unsigned long long *fring, int *done, int *iters, bool packed = false);
+void k_fit_sym_dir_step(cge_ctx *c, const double *GD, const double *Tin, const double *Tout, double *Tin_n, double *Tout_n,
+                        const double *deg_in, const double *deg_out, i64 N, double eps0, double f0, double delta, int k,
+                        unsigned long long *fring, double *ering, int *done, int *iters, bool packed);
 void k_fit_symv_dir(cge_ctx *c, const double *GD, const double *Tin, const double *Tout, i64 N, double *Sin,
                     double *Sout, const int *done);
 void k_fit_update_dir(cge_ctx *c, double *Tin, double *Tout, const double *Sin, const double *Sout,

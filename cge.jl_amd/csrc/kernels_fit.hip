@@ -531,6 +531,82 @@ __global__ __launch_bounds__(256) void bvec_tile_kernel(const double *__restrict
             }
     }
 }
+// The directed form on the PACKED tiles: one workgroup per STORED tile t = (I, J), I <= J.  The tile is read once, coalesced (a
+// thread takes every 256th double of the tile's 4096 and finds its element's row and column by inverting cge_tile_slot), and
+// kept in registers; from it the workgroup writes the partials of tile (I, J) -- products (Ta_i Tb_j) g_ij -- and, for I != J,
+// those of the mirror tile (J, I), whose element (j, i) is the same g_ij with the product (Ta_j Tb_i): the tile's transpose in
+// LDS.  Both go through steps (a) and (b) of bvec_tile_kernel, so every partial is at the base[] position and has the bits that
+// bvec_tile_kernel<false> with directed = 1 gives it on a symmetric row-major GD; bvec_bins_kernel follows unchanged.
+__device__ __forceinline__ void bvec_tile_sums(const double (*prod)[65], double (*rp)[65], const int *segR, const int *segC, int nsR,
+                                               int nsC, i64 base_off, double *__restrict__ partial, int t) {
+    { // (a) of bvec_tile_kernel: row r over the columns of each community, by 8-column chunks
+        const int r = t >> 2;
+        for (int s2 = t & 3; s2 < nsC; s2 += 4) {
+            const int b0 = segC[s2], b1 = segC[s2 + 1];
+            double acc = 0.0;
+            for (int c2 = b0; c2 < b1;) {
+                const int ce = min(b1, (c2 & ~7) + 8);
+                double ch = prod[r][c2];
+                for (int c3 = c2 + 1; c3 < ce; c3++) ch = __dadd_rn(ch, prod[r][c3]);
+                acc = (c2 == b0) ? ch : __dadd_rn(acc, ch);
+                c2 = ce;
+            }
+            rp[r][s2] = acc;
+        }
+    }
+    __syncthreads();
+    { // (b): the rectangle (row community rs) x (column community s2) over its rows
+        const int s2 = t & 63;
+        if (s2 < nsC)
+            for (int rs = t >> 6; rs < nsR; rs += 4) {
+                const int a0 = segR[rs], a1 = segR[rs + 1];
+                double acc = 0.0;
+                for (int r = a0; r < a1; r++) acc = __dadd_rn(acc, rp[r][s2]);
+                partial[base_off + rs * nsC + s2] = acc;
+            }
+    }
+}
+__global__ __launch_bounds__(256) void bvec_tile_dir_packed_kernel(const double *__restrict__ PK, const double *__restrict__ Ta,
+                                                                   const double *__restrict__ Tb, const i32 *__restrict__ cm_off,
+                                                                   const i32 *__restrict__ fc, const i32 *__restrict__ ns,
+                                                                   const i32 *__restrict__ base, i64 N, int Nt,
+                                                                   double *__restrict__ partial) {
+    __shared__ double prod[64][65], rp[64][65];
+    __shared__ int segI[66], segJ[66];
+    const int t = threadIdx.x;
+    i64 I64, J64;
+    cge_upper_tile_of((i64)blockIdx.x, Nt, I64, J64);
+    const int I = (int)I64, J = (int)J64;
+    const int nsI = ns[I], nsJ = ns[J], fcI = fc[I], fcJ = fc[J];
+    if (t <= nsJ) segJ[t] = min(max(cm_off[fcJ + t], 64 * J), 64 * J + 64) - 64 * J;
+    if (t >= 128 && t - 128 <= nsI) segI[t - 128] = min(max(cm_off[fcI + t - 128], 64 * I), 64 * I + 64) - 64 * I;
+    const double *tile = PK + (i64)blockIdx.x * CGE_TILE_DOUBLES;
+    double g[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) g[u] = tile[256 * u + t];
+    // slot s = ((4 a + b / 2) * 64 + lane) * 2 + b % 2 holds row 8 (lane / 8) + a, column 8 (lane % 8) + b of the tile
+    const int sl_lane = (t >> 1) & 63, sl_b0 = t & 1, sl_x0 = t >> 7; // slot 256 u + t: x = 2 u + t / 128
+#pragma unroll
+    for (int u = 0; u < 16; u++) {
+        const int x = 2 * u + sl_x0, r = 8 * (sl_lane >> 3) + (x >> 2), q = 8 * (sl_lane & 7) + 2 * (x & 3) + sl_b0;
+        const i64 i = (i64)64 * I + r, j = (i64)64 * J + q;
+        const double ti = i < N ? Ta[i] : 0.0, tbj = j < N ? Tb[j] : 0.0;
+        prod[r][q] = __dmul_rn(__dmul_rn(ti, tbj), g[u]); // (0 outside the matrix: the stored element is 0 there)
+    }
+    __syncthreads();
+    bvec_tile_sums(prod, rp, segI, segJ, nsI, nsJ, (i64)base[I * Nt + J], partial, t);
+    if (I == J) return;
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 16; u++) { // the mirror tile (J, I): row q of block J, column r of block I
+        const int x = 2 * u + sl_x0, r = 8 * (sl_lane >> 3) + (x >> 2), q = 8 * (sl_lane & 7) + 2 * (x & 3) + sl_b0;
+        const i64 i = (i64)64 * I + r, j = (i64)64 * J + q;
+        const double tj = j < N ? Ta[j] : 0.0, tbi = i < N ? Tb[i] : 0.0;
+        prod[q][r] = __dmul_rn(__dmul_rn(tj, tbi), g[u]);
+    }
+    __syncthreads();
+    bvec_tile_sums(prod, rp, segJ, segI, nsJ, nsI, (i64)base[J * Nt + I], partial, t);
+}
 __global__ __launch_bounds__(256) void bvec_bins_kernel(const double *__restrict__ partial, const i32 *__restrict__ cm_off,
                                                         const i32 *__restrict__ fc, const i32 *__restrict__ ns,
                                                         const i32 *__restrict__ base, i64 C, int Nt, int directed,
@@ -574,8 +650,10 @@ void k_bvec_tiles(cge_ctx *c, const double *GD, const double *Ta, const double *
                   bool packed) {
     ScopedKernelTimer t(c, "bvec");
     const int Nt = (int)((N + 63) / 64);
-    if (packed && directed) CGE_THROW(CGE_E_ASSERT, "vect_B by tiles: the packed matrix is undirected");
-    if (packed)
+    if (packed && directed) // one workgroup per stored tile: its own partials and its mirror tile's
+        hipLaunchKernelGGL(bvec_tile_dir_packed_kernel, dim3((unsigned)((i64)Nt * (Nt + 1) / 2)), dim3(256), 0, c->stream, GD, Ta, Tb,
+                           cm_off, c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, N, Nt, c->sw_bt_part.p);
+    else if (packed)
         hipLaunchKernelGGL(bvec_tile_kernel<true>, dim3((unsigned)Nt, (unsigned)Nt), dim3(256), 0, c->stream, GD, Ta, Tb, cm_off,
                            c->sw_bt_fc.p, c->sw_bt_ns.p, c->sw_bt_base.p, N, Nt, directed, c->sw_bt_part.p);
     else

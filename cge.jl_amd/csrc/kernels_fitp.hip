@@ -331,6 +331,172 @@ __global__ __launch_bounds__(256) void fit_symreduce_kernel(const double *__rest
         }
     }
 }
+// ---- one DIRECTED Chung-Lu iteration per launch pair, over the upper tiles only ---------------------------------------------
+// The directed model's matrix is symmetric (GD[idx(n, min, max)], src/divergence.jl:426-432); only Tin / Tout break the symmetry.
+// So one read of the upper tile (I, J) -- fit_symtile_kernel's lane layout and loads -- serves four partial vectors: toward Sin
+// and Sout of block I from Tout_J and Tin_J and, for I != J, toward Sin and Sout of block J from Tout_I and Tin_I, factored like
+// the undirected form (the row's own Tin_i / Tout_i is applied by the reducer).  The diagonal element is counted twice in both
+// sums (:439-449; fit_symv_dir_kernel, kernels_fit.hip, documents the rule): one more FMA in the lanes of a diagonal tile that
+// hold the diagonal.  Two passes over the register block (rows, then columns), as fit_flow_dir_body.inc makes them, so that the
+// block, one pair of T vectors and one pair of accumulators are live at a time.  Pin / Pout: Nt x Nt x 64 doubles each.
+// The reducer adds a block's Nt partial vectors in fit_symreduce_kernel's order, moves Tin / Tout of rows with a positive degree
+// (the others are copied: the iterates alternate between two buffers, since other workgroups of the iteration still read the
+// old one) and publishes f = max |deg - S| in fring[k % 4].  The epsilon rule needs f of the two previous iterations
+// (`if f > diff: eps *= 0.99`, :462-465, eps_0 = 0.9, diff_0 = f0 = 1.0): every workgroup of iteration k derives eps_k from
+// f_{k-1}, f_{k-2} and eps_{k-1} = ering[(k - 1) % 2], and workgroup 0 leaves eps_k in ering[k % 2].  A ring of FOUR for f: k - 2,
+// k - 1 are read, k is written and k + 1 cleared by one launch.  The end is fit_symtile_kernel's: launch k returns when
+// f_{k-1} <= delta, the reducer then records iters = k.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void fit_symtile_dir_kernel(const double *__restrict__ GD, const double *__restrict__ Tin,
+                                                              const double *__restrict__ Tout, i64 N, int Nt, i64 NT, double delta,
+                                                              int k, const unsigned long long *__restrict__ fring,
+                                                              const int *__restrict__ done, double *__restrict__ Pin,
+                                                              double *__restrict__ Pout) {
+    if (*done) return;
+    if (k > 0) {
+        const double fprev = __longlong_as_double((long long)fring[(k - 1) & 3]);
+        if (!(fprev > delta)) return; // the fit ended with iteration k - 1 (the reduce kernel records it)
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rq = lane >> 3, cq = lane & 7;
+    const i64 t = (i64)blockIdx.x * 4 + wave;
+    if (t >= NT) return;
+    i64 I, J;
+    cge_upper_tile_of(t, Nt, I, J);
+    const i64 r0 = 64 * I + 8 * rq, c0 = 64 * J + 8 * cq;
+    double g[8][8];
+    if (PACKED) {
+        const double *tile = GD + t * CGE_TILE_DOUBLES;
+#pragma unroll
+        for (int a = 0; a < 8; a++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const dbl2f v = *reinterpret_cast<const dbl2f *>(tile + cge_tile_slot(8 * rq + a, 8 * cq + 2 * b));
+                g[a][2 * b] = v.x;
+                g[a][2 * b + 1] = v.y;
+            }
+    } else if ((N & 1) == 0 && r0 + 8 <= N && c0 + 8 <= N) { // the common case: 16-byte loads, no guards
+#pragma unroll
+        for (int a = 0; a < 8; a++) {
+            const dbl2f *row = reinterpret_cast<const dbl2f *>(GD + (r0 + a) * N + c0);
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const dbl2f v = row[b];
+                g[a][2 * b] = v.x;
+                g[a][2 * b + 1] = v.y;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int a = 0; a < 8; a++)
+#pragma unroll
+            for (int b = 0; b < 8; b++) g[a][b] = (r0 + a < N && c0 + b < N) ? GD[(r0 + a) * N + c0 + b] : 0.0;
+    }
+    { // rows of block I: Sin from Tout_J, Sout from Tin_J
+        double to[8], ti[8], pin[8], pout[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            to[q] = c0 + q < N ? Tout[c0 + q] : 0.0;
+            ti[q] = c0 + q < N ? Tin[c0 + q] : 0.0;
+            pin[q] = 0.0;
+            pout[q] = 0.0;
+        }
+#pragma unroll
+        for (int a = 0; a < 8; a++)
+#pragma unroll
+            for (int b = 0; b < 8; b++) {
+                pin[a] = fma(g[a][b], to[b], pin[a]);
+                pout[a] = fma(g[a][b], ti[b], pout[a]);
+            }
+        if (I == J && rq == cq) { // the diagonal term once more
+#pragma unroll
+            for (int a = 0; a < 8; a++) {
+                pin[a] = fma(g[a][a], to[a], pin[a]);
+                pout[a] = fma(g[a][a], ti[a], pout[a]);
+            }
+        }
+        const double sin_r = transpose_reduce8<0>(pin, lane), sout_r = transpose_reduce8<0>(pout, lane); // row 8*rq + cq
+        Pin[(I * Nt + J) * 64 + lane] = sin_r;
+        Pout[(I * Nt + J) * 64 + lane] = sout_r;
+    }
+    if (I != J) { // rows of block J (the tile's columns): Sin from Tout_I, Sout from Tin_I
+        double to[8], ti[8], pin[8], pout[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            to[q] = r0 + q < N ? Tout[r0 + q] : 0.0;
+            ti[q] = r0 + q < N ? Tin[r0 + q] : 0.0;
+            pin[q] = 0.0;
+            pout[q] = 0.0;
+        }
+#pragma unroll
+        for (int a = 0; a < 8; a++)
+#pragma unroll
+            for (int b = 0; b < 8; b++) {
+                pin[b] = fma(g[a][b], to[a], pin[b]);
+                pout[b] = fma(g[a][b], ti[a], pout[b]);
+            }
+        const double sin_c = transpose_reduce8<3>(pin, lane), sout_c = transpose_reduce8<3>(pout, lane); // column 8*cq + rq
+        Pin[(J * Nt + I) * 64 + 8 * cq + rq] = sin_c;
+        Pout[(J * Nt + I) * 64 + 8 * cq + rq] = sout_c;
+    }
+}
+__global__ __launch_bounds__(256) void fit_symreduce_dir_kernel(const double *__restrict__ Pin, const double *__restrict__ Pout,
+                                                                const double *__restrict__ Tin, const double *__restrict__ Tout,
+                                                                double *__restrict__ Tin_n, double *__restrict__ Tout_n,
+                                                                const double *__restrict__ deg_in,
+                                                                const double *__restrict__ deg_out, i64 N, int Nt, double eps0,
+                                                                double f0, double delta, int k,
+                                                                unsigned long long *__restrict__ fring, double *__restrict__ ering,
+                                                                int *__restrict__ done, int *__restrict__ iters) {
+    __shared__ double red[2][4][64];
+    if (*done) return;
+    double eps = eps0;
+    if (k > 0) {
+        const double f1 = __longlong_as_double((long long)fring[(k - 1) & 3]);
+        if (!(f1 > delta)) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) { *iters = k; *done = 1; }
+            return;
+        }
+        const double f2 = k > 1 ? __longlong_as_double((long long)fring[(k - 2) & 3]) : f0;
+        const double ep = ering[(k - 1) & 1];
+        eps = f1 > f2 ? ep * 0.99 : ep; // :462-464, after iteration k - 1
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { fring[(k + 1) & 3] = 0ULL; ering[k & 1] = eps; *iters = k + 1; }
+    const int r = threadIdx.x & 63, u = threadIdx.x >> 6;
+    const i64 b = blockIdx.x;
+    const double *Pi = Pin + b * Nt * 64 + r, *Po = Pout + b * Nt * 64 + r;
+    double ai = 0.0, ao = 0.0;
+    int q = u;
+    for (; q + 12 < Nt; q += 16) { // four loads of each in flight; the additions stay in q order
+        const double p0 = Pi[(i64)q * 64], p1 = Pi[(i64)(q + 4) * 64], p2 = Pi[(i64)(q + 8) * 64], p3 = Pi[(i64)(q + 12) * 64];
+        const double o0 = Po[(i64)q * 64], o1 = Po[(i64)(q + 4) * 64], o2 = Po[(i64)(q + 8) * 64], o3 = Po[(i64)(q + 12) * 64];
+        ai += p0; ai += p1; ai += p2; ai += p3;
+        ao += o0; ao += o1; ao += o2; ao += o3;
+    }
+    for (; q < Nt; q += 4) { ai += Pi[(i64)q * 64]; ao += Po[(i64)q * 64]; }
+    red[0][u][r] = ai;
+    red[1][u][r] = ao;
+    __syncthreads();
+    if (threadIdx.x < 128) { // wave 0: Tin, wave 1: Tout
+        const int s = u;
+        const i64 row = 64 * b + r;
+        double f = 0.0;
+        if (row < N) {
+            const double ti = (s ? Tout : Tin)[row], di = (s ? deg_out : deg_in)[row];
+            double tn = ti;
+            if (di > 0) {
+                const double S = ti * (((red[s][0][r] + red[s][1][r]) + red[s][2][r]) + red[s][3][r]); // the tiles summed g * T
+                tn = ti + (eps * ti) * (di / S - 1.0);
+                f = fabs(di - S);
+            }
+            (s ? Tout_n : Tin_n)[row] = tn;
+        }
+        f = wave_max(f);
+        if (r == 0) {
+            const unsigned long long fb = (unsigned long long)__double_as_longlong(f);
+            if (fb > __hip_atomic_load(&fring[k & 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&fring[k & 3], fb);
+        }
+    }
+}
 // ---- the directed fit with the data as its own signal (the scheme of fit_flow_kernel) -------------------------------------
 // Per tile four partial vectors (e1 = (Tin_i*Tout_j)*g feeds Sin_i and Sout_j, e2 = (Tin_j*Tout_i)*g feeds Sout_i and
 // Sin_j, the diagonal term twice), computed in two passes over the register block so that a wave of 256 registers holds
@@ -399,6 +565,27 @@ void k_fit_sym_step(cge_ctx *c, const double *GD, const double *Tin, double *Tou
                            fring, done, c->fp_P.p);
     hipLaunchKernelGGL(fit_symreduce_kernel, dim3((unsigned)Nt), dim3(256), 0, c->stream, c->fp_P.p, Tin, Tout, w, N, Nt, eps,
                        delta, k, fring, done, iters);
+}
+
+// Iteration k of the directed fit by the tile pair: (Tin, Tout) -> (Tin_n, Tout_n).  fring: 4 words, zeroed before iteration 0;
+// ering: 2 doubles.  The partial vectors are the two halves of fp_P (twice the undirected fit's, which takes the first half).
+void k_fit_sym_dir_step(cge_ctx *c, const double *GD, const double *Tin, const double *Tout, double *Tin_n, double *Tout_n,
+                        const double *deg_in, const double *deg_out, i64 N, double eps0, double f0, double delta, int k,
+                        unsigned long long *fring, double *ering, int *done, int *iters, bool packed) {
+    const int Nt = (int)((N + 63) / 64);
+    const i64 NT = (i64)Nt * (Nt + 1) / 2;
+    const size_t half = (size_t)Nt * Nt * 64;
+    c->fp_P.ensure(2 * half);
+    double *Pin = c->fp_P.p, *Pout = c->fp_P.p + half;
+    ScopedKernelTimer t(c, "fit_symv");
+    if (packed)
+        hipLaunchKernelGGL(fit_symtile_dir_kernel<true>, dim3((unsigned)((NT + 3) / 4)), dim3(256), 0, c->stream, GD, Tin, Tout, N, Nt,
+                           NT, delta, k, fring, done, Pin, Pout);
+    else
+        hipLaunchKernelGGL(fit_symtile_dir_kernel<false>, dim3((unsigned)((NT + 3) / 4)), dim3(256), 0, c->stream, GD, Tin, Tout, N, Nt,
+                           NT, delta, k, fring, done, Pin, Pout);
+    hipLaunchKernelGGL(fit_symreduce_dir_kernel, dim3((unsigned)Nt), dim3(256), 0, c->stream, Pin, Pout, Tin, Tout, Tin_n, Tout_n,
+                       deg_in, deg_out, N, Nt, eps0, f0, delta, k, fring, ering, done, iters);
 }
 
 // ---- the host side of the persistent fits: one geometry, one slot layout, one launch path ------------------------------------

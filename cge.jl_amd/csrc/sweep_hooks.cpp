@@ -148,6 +148,7 @@ void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b
                       int landmarks, int n_modes, int *form_ran) {
     const cge_vect_b_problem *probs[2] = {p1, form == 6 ? p2 : nullptr};
     if ((form == 5 || form == 6) && directed) CGE_THROW(CGE_E_ARG, "vect_b_test: form %d is undirected only", form);
+    if (form == 7 && !directed) CGE_THROW(CGE_E_ARG, "vect_b_test: form 7 is directed only");
     if (form == 6 && (!p2 || !p2->GD || p2->C >= p1->C)) CGE_THROW(CGE_E_ARG, "vect_b_test: form 6 takes a second problem of fewer communities");
     for (const cge_vect_b_problem *p : probs) {
         if (!p) continue;
@@ -184,6 +185,15 @@ void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b
         if (run == 5) {
             k_bvec_tiles(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, N, directed);
             k_bins_js(c, c->sw_cm_off.p, N, C, vCp[0], vB.p, nm, fpart.p);
+        } else if (run == 7) { // directed, on the packed tiles: the stored tiles and their mirrors, then the bins
+            std::vector<double> h((size_t)N * N);
+            hook_down(c, h.data(), c->sw_GD.p, N * N); // (in the sweep's numbering)
+            HIP_CHECK(hipStreamSynchronize(st));
+            pack_upper_tiles(c, h.data(), N);
+            k_bvec_tiles(c, c->sw_PK.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_off.p, N, 1, true);
+            k_bvec_bins(c, c->sw_cm_off.p, N, C, 1, vB.p);
+            HIP_CHECK(hipStreamSynchronize(st));
+            c->sw_PK.release(); // (held only while packed sweeps run)
         } else
             k_bvec(c, c->sw_GD.p, c->sw_T1.p, c->sw_T2.p, c->sw_cm_pos.p, c->sw_cm_off.p, c->sw_cm_mem.p, N, C, directed,
                    c->sw_rowbins.p, vB.p, run);
@@ -212,7 +222,7 @@ void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b
     }
     *form_ran = run;
     std::vector<double> hf((size_t)4 * CGE_PARTIAL_BLOCKS, 0.0);
-    if (run >= 5) hook_down(c, hf.data(), fpart.p, (i64)hf.size());
+    if (run == 5 || run == 6) hook_down(c, hf.data(), fpart.p, (i64)hf.size());
     // k_js modes 0, 1, 2 over the vector(s) the form left
     jsd.ensure(6);
     double hj[6] = {0, 0, 0, 0, 0, 0};
@@ -228,7 +238,7 @@ void host_vect_b_test(cge_ctx *c, const cge_vect_b_problem *p1, const cge_vect_b
         if (!p) continue;
         if (p->GD) std::memcpy(p->vectB, hv.data() + off[q], sizeof(double) * (len[q] + G));
         if (p->vC) std::memcpy(p->js_dev, hj + 3 * q, sizeof(double) * 3);
-        if (p->js_fused && run >= 5)
+        if (p->js_fused && (run == 5 || run == 6))
             for (int u = 0; u < nm; u++) p->js_fused[u] = vb_fold(hf.data() + (i64)((run == 6 ? q * nm : 0) + u) * CGE_PARTIAL_BLOCKS);
     }
 }
@@ -284,7 +294,7 @@ static int ft_run(cge_ctx *c, cge_fit_problem &p, int form, int directed, double
     (directed ? fit.persistent_dir : fit.persistent) = form == 3 || form == 4 || (form == 0 && persistent_wanted(c, p.N));
     AlphaSlot sl;
     run_fit(sl);
-    int ran = form == 2 ? 2 : 1;
+    int ran = form == 2 || form == 7 || form == 8 ? form : 1;
     p.status = 0;
     if (sl.fit_async) {
         ran = form == 4 ? 4 : 3;
@@ -346,7 +356,14 @@ static int ft_directed(cge_ctx *c, cge_fit_problem &p, int form, double eps, dou
     hipStream_t st = c->stream;
     const i64 N = p.N;
     ft_matrices(c, p, false, true);
+    if (form == 8) { // the upper tiles of GD
+        std::vector<double> h((size_t)N * N);
+        hook_down(c, h.data(), c->sw_GD.p, N * N);
+        HIP_CHECK(hipStreamSynchronize(st));
+        pack_upper_tiles(c, h.data(), N);
+    }
     DevBuf<double> din, dout;
+    c->sw_fring.ensure(4);
     c->sw_S1.ensure(N); c->sw_S2.ensure(N);
     c->sw_scal.ensure(RES_STRIDE);
     c->sw_flags.ensure(4);
@@ -360,10 +377,12 @@ static int ft_directed(cge_ctx *c, cge_fit_problem &p, int form, double eps, dou
     G.N = N;
     G.deg_in = din.p; G.deg_out = dout.p;
     FitForm fit;
-    const int ran = ft_run(c, p, form, 1, eps, delta, fit, [&](AlphaSlot &sl) { fit_directed(c, G, p.alpha, fit, sl); }); // (forms 0, 1, 3 only)
+    fit.dir_tiles = form == 7 ? 1 : form == 8 ? 2 : 0; // (else forms 0, 1, 3 only)
+    const int ran = ft_run(c, p, form, 1, eps, delta, fit, [&](AlphaSlot &sl) { fit_directed(c, G, p.alpha, fit, sl); });
     hook_down(c, p.T, c->sw_T1.p, N);
     hook_down(c, p.Tb, c->sw_T2.p, N);
     HIP_CHECK(hipStreamSynchronize(st));
+    if (form == 8) c->sw_PK.release(); // (held only while packed sweeps run)
     return ran;
 }
 
@@ -452,6 +471,7 @@ static void ft_dir_multi(cge_ctx *c, cge_fit_problem *probs, int n, const FlowGe
 
 void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int form, double eps, double delta, int *form_ran) {
     if (!directed && form == 6) CGE_THROW(CGE_E_ARG, "fit_test: form 6 is directed only");
+    if (!directed && (form == 7 || form == 8)) CGE_THROW(CGE_E_ARG, "fit_test: form %d is directed only", form);
     if (n > 1 && form != 5 && form != 6) CGE_THROW(CGE_E_ARG, "fit_test: %d problems in one call are form 5 only", n);
     if (n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ARG, "fit_test: form %d takes at most %d problems", form, CGE_BATCH_MAX);
     if (directed && (form == 2 || form == 4 || form == 5)) CGE_THROW(CGE_E_ARG, "fit_test: form %d is undirected only", form);
@@ -700,7 +720,7 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
     hipStream_t st = c->stream;
     const i64 S = io->S, n = c->n, m = c->m, N = io->N;
     const int directed = io->directed != 0, form = io->form;
-    const bool landmark_form = form == 1 || form == 4, exact_form = form == 2 || form == 3;
+    const bool landmark_form = form == 1 || form == 4, exact_form = form == 2 || form == 3 || form == 5;
     // the stages that run
     const bool draw = io->draw_route != 0;
     const bool pairs_in = io->pi_in || io->pj_in || io->ni_in || io->nj_in || io->wts_in;
@@ -829,7 +849,8 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
         hook_up(c, dlw, io->lweight, N);
         if (io->old2new) hook_up(c, do2n, io->old2new, N);
     }
-    if (form >= 1 && form <= 3) {
+    const bool plain_tally = (form >= 1 && form <= 3) || form == 5;
+    if (plain_tally) {
         hook_up(c, dTa, io->Ta, N);
         if (io->Tb) hook_up(c, dTb, io->Tb, N);
         dout2.ensure(2);
@@ -849,13 +870,13 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
         k_auc_landmark(c, Ta, Tb, dv2l.p, dvw.p, dlw.p, ds.pi.p, ds.pj.p, ds.ni.p, ds.nj.p, ds.dpos.p, ds.dneg.p, ds.wts.p, S, io->alpha,
                        dout2.p);
     } else if (exact_form) {
-        const bool packed = form == 3;
+        const bool packed = form == 3 || form == 5; // (5: ordered pairs, either side of the diagonal -- the directed sweep's)
         if (packed) pack_upper_tiles(c, io->GD, N); // the upper tiles of GD
         else hook_up(c, c->sw_GD, io->GD, N * N);
         k_auc_exact(c, packed ? c->sw_PK.p : c->sw_GD.p, dTa.p, io->Tb ? dTb.p : dTa.p, N, ds.pi.p, ds.pj.p, ds.ni.p, ds.nj.p, ds.wts.p, S,
                     dout2.p, nullptr, packed);
     }
-    if (form >= 1 && form <= 3) {
+    if (plain_tally) {
         hook_down(c, hpart.data(), c->auc_part.p, 2 * CGE_PARTIAL_BLOCKS);
         hook_down(c, io->out2, dout2.p, 2);
     }
@@ -880,7 +901,7 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
         hook_down(c, io->aden, ds.afac.p + 8 * S, (i64)CGE_PARTIAL_BLOCKS);
     }
     HIP_CHECK(hipStreamSynchronize(st));
-    if (form == 3) c->sw_PK.release(); // (held only while packed sweeps run)
+    if (form == 3 || form == 5) c->sw_PK.release(); // (held only while packed sweeps run)
     if (form != 0 && io->part) std::memcpy(io->part, hpart.data(), sizeof(double) * hpart.size());
     if (form == 4 && io->out2) { // the block tallies in block order, as the sweep's host adds them
         double num = 0.0, den = 0.0;

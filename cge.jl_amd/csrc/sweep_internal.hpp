@@ -28,6 +28,7 @@ struct AlphaSlot {
 // :35); the testing hook cge_fit_test passes its caller's.
 struct FitForm {
     bool persistent = false, persistent_dir = false;
+    int dir_tiles = 0; // a directed launch-per-iteration fit by the tile pair: 1 on the row-major GD, 2 on the packed tiles (sw_PK)
     int tpar = 0;
     i64 prev_iters = 16;
     double eps = 0.25, delta = AlphaBook::delta;

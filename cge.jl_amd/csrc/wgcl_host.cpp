@@ -506,24 +506,24 @@ bool persistent_wanted(const cge_ctx *c, i64 N) {
 
 // One launch (pair) per iteration: `launch(k)` enqueues iteration k, in batches -- the first as long as the previous fit, at
 // most 32 from then on.  After each batch the host reads the fit's flags ([0] done, [1] iterations) and, when `ring` is given,
-// the changes of the undirected fit's last iterations.  Returns the iterations.
+// the changes of the fit's last iterations (ring_len of them: 3 undirected, 4 by the directed tile pair).  Returns the iterations.
 template <class Launch>
 static i64 fit_by_launches(cge_ctx *c, i64 prev_iters, double alpha, double delta, const int *flags,
-                           const unsigned long long *ring, Launch launch) {
+                           const unsigned long long *ring, Launch launch, int ring_len = 3) {
     hipStream_t st = c->stream;
     i64 batch = std::max<i64>(4, std::min<i64>(prev_iters, 128));
     for (i64 k = 0;;) {
         for (i64 b = 0; b < batch; b++, k++) launch(k);
         int hf[2];
-        unsigned long long hr[3];
+        unsigned long long hr[4];
         HIP_CHECK(hipMemcpyAsync(hf, flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
-        if (ring) HIP_CHECK(hipMemcpyAsync(hr, ring, sizeof(hr), hipMemcpyDeviceToHost, st));
+        if (ring) HIP_CHECK(hipMemcpyAsync(hr, ring, sizeof(unsigned long long) * ring_len, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         const i64 iters = hf[1];
         if (hf[0]) return iters;
         if (ring) {
             double flast;
-            std::memcpy(&flast, &hr[(k - 1) % 3], sizeof(double));
+            std::memcpy(&flast, &hr[(k - 1) % ring_len], sizeof(double));
             if (!(flast > delta)) return iters; // the last launch of the batch was the converging iteration (iters == k)
         }
         if (iters > c->opt_fit_max_iters) CGE_THROW(CGE_E_ASSERT, "Chung-Lu fit did not converge at alpha=%g (%lld iterations; the reference's `while diff > delta` would not return)", alpha, (long long)iters);
@@ -577,7 +577,7 @@ void fit_undirected(cge_ctx *c, i64 N, const double *w, i64 Tld, double alpha, b
 void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm &fit, AlphaSlot &sl) {
     hipStream_t st = c->stream;
     const i64 N = G.N;
-    const double *GD = c->sw_GD.p;
+    const double *GD = fit.dir_tiles == 2 ? c->sw_PK.p : c->sw_GD.p;
     double *Tin = c->sw_T1.p, *Tout = c->sw_T2.p;
     int *flags = c->sw_flags.p;
     HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
@@ -593,6 +593,24 @@ void fit_directed(cge_ctx *c, const ScoreGraph &G, double alpha, FitForm &fit, A
     if (fit.persistent_dir) { // abandoned: Tin / Tout are untouched; one launch pair per iteration from here on
         fit.persistent_dir = false;
         HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int) * 4, st));
+    }
+    if (fit.dir_tiles) {
+        // by the tile pair (kernels_fitp.hip): every upper tile read once per iteration.  The iterates alternate between
+        // (sw_T1, sw_T2) and the two halves of fp_Td; an odd count leaves the result in the latter, which is copied home.
+        // f travels in a ring of four, epsilon in the first two doubles of sw_fitstate.
+        c->fp_Td.ensure((size_t)2 * N);
+        c->sweep_used_fp_P = true;
+        HIP_CHECK(hipMemsetAsync(c->sw_fring.p, 0, sizeof(unsigned long long) * 4, st));
+        double *Ti[2] = {Tin, c->fp_Td.p}, *To[2] = {Tout, c->fp_Td.p + N};
+        sl.iters = fit_by_launches(c, fit.prev_iters, alpha, fit.delta, flags, c->sw_fring.p, [&](i64 k) {
+            k_fit_sym_dir_step(c, GD, Ti[k & 1], To[k & 1], Ti[(k + 1) & 1], To[(k + 1) & 1], G.deg_in, G.deg_out, N, fit.eps, 1.0,
+                               fit.delta, (int)k, c->sw_fring.p, c->sw_fitstate.p, flags, flags + 1, fit.dir_tiles == 2);
+        }, 4);
+        if (sl.iters & 1) {
+            HIP_CHECK(hipMemcpyAsync(Tin, Ti[1], sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(Tout, To[1], sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+        }
+        return;
     }
     sl.iters = fit_by_launches(c, fit.prev_iters, alpha, fit.delta, flags, nullptr, [&](i64) {
         k_fit_symv_dir(c, GD, Tin, Tout, N, c->sw_S1.p, c->sw_S2.p, flags);
@@ -645,7 +663,7 @@ static void divergence_and_copy_out(cge_ctx *c, const ScoreGraph &G, int directe
     hipStream_t st = c->stream;
     const i64 N = G.N, C = G.C, vlen = directed ? C * C : packed_len(C);
     const double *GD = packed ? c->sw_PK.p : c->sw_GD.p;
-    if (packed && want_div && !(c->bvec_blocks && !directed && !c->opt_test_bvec_plain))
+    if (packed && want_div && !(c->bvec_blocks && !c->opt_test_bvec_plain))
         CGE_THROW(CGE_E_ASSERT, "packed exact sweep without the tile form of vect_B");
     const i32 *cm_off = c->sw_cm_off.p;
     double *scal = c->sw_scal.p, *vectB = c->sw_vectB.p, *host_out = c->pin_scal.p + RES_STRIDE * slot;
@@ -666,7 +684,10 @@ static void divergence_and_copy_out(cge_ctx *c, const ScoreGraph &G, int directe
     } else {
         if (want_div) {
             if (bvec_partials) k_bvec_bins(c, cm_off, N, C, directed, vectB); // the tile partials came with the fit
-            else k_bvec(c, GD, Ta, Tb, c->sw_cm_pos.p, cm_off, c->sw_cm_mem.p, N, C, directed, c->sw_rowbins.p, vectB);
+            else if (packed) { // (directed) the stored tiles and their mirrors, then the C^2 bins
+                k_bvec_tiles(c, GD, Ta, Tb, cm_off, N, directed, true);
+                k_bvec_bins(c, cm_off, N, C, directed, vectB);
+            } else k_bvec(c, GD, Ta, Tb, c->sw_cm_pos.p, cm_off, c->sw_cm_mem.p, N, C, directed, c->sw_rowbins.p, vectB);
             if (!split)
                 k_js(c, G.vectC, vectB, vlen, C, directed, 0, nullptr, scal + RES_JS);
             else {
@@ -747,9 +768,10 @@ static void enqueue_alpha(cge_ctx *c, const SweepView &sw, i64 ia, bool want_auc
 // The packed form's two O(N^2) buffers: the upper tiles of GD (sw_PK) and the fit's partial vectors (fp_P).  What the context still
 // holds of the resident form from earlier sweeps -- D, GD, the logarithm -- is released first, so that a context that scored a
 // smaller graph can score a large one; then whatever has to grow must fit the free memory.
-static void packed_buffers(cge_ctx *c, i64 N) {
+// (directed: two sets of partial vectors, toward Sin and toward Sout)
+static void packed_buffers(cge_ctx *c, i64 N, int directed) {
     const i64 Nt = (N + 63) / 64, NT = Nt * (Nt + 1) / 2;
-    const size_t pk_words = (size_t)NT * CGE_TILE_DOUBLES, fp_words = (size_t)Nt * Nt * 64;
+    const size_t pk_words = (size_t)NT * CGE_TILE_DOUBLES, fp_words = (size_t)Nt * Nt * 64 * (directed ? 2 : 1);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     c->sw_D.release(); c->sw_GD.release(); c->sw_Lh.release(); c->sw_Ll.release();
     c->pow_logs_N = c->pow_logs_blocked_N = 0;
@@ -773,12 +795,19 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     const i64 vlen = directed ? C * C : packed_len(C);
     // The resident form keeps D, GD and (when they fit) the logarithm on the device; beyond its limit an undirected exact sweep
     // runs PACKED where that form applies (the tile form of vect_B: N >= 256, C >= 2, exact_relabel, the tile tables accept the
-    // layout), option "exact_packed" = 1 wherever it applies.  Directed sweeps stay resident, with the limit.
+    // layout), option "exact_packed" = 1 wherever it applies.  A directed sweep stays resident, with the limit, unless option
+    // "exact_packed_directed" allows the packed form: 1 beyond the limit, 2 wherever the form applies (the same conditions).
     const double resident_limit = c->opt_test_resident_limit > 0 ? c->opt_test_resident_limit : 200e9;
     const bool beyond = (double)N * (double)N * 8.0 * 2.2 > resident_limit;
-    const bool packed_req = !orig && !directed && (beyond || c->opt_exact_packed == 1);
+    const bool packed_req = !orig && (directed ? c->opt_exact_packed_directed == 2 || (beyond && c->opt_exact_packed_directed == 1)
+                                               : beyond || c->opt_exact_packed == 1);
     c->stat_exact_packed = 0;
-    if (beyond && !packed_req) CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit", (long long)N);
+    if (beyond && !packed_req) {
+        if (directed && !orig)
+            CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit (a directed exact sweep runs on the packed tiles only "
+                      "under option exact_packed_directed)", (long long)N);
+        CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit", (long long)N);
+    }
     c->sw_T1.ensure(N); c->sw_T2.ensure(N); c->sw_S1.ensure(N); c->sw_S2.ensure(N);
     c->sw_rowbins.ensure((size_t)N * C);
     c->sw_vectB.ensure(vlen);
@@ -795,7 +824,7 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
         CGE_THROW(CGE_E_OOM, "score graph with %lld vertices does not fit (the packed form of an exact sweep does not apply to it)",
                   (long long)N);
     const i64 Nt64 = (N + 63) / 64;
-    if (packed) packed_buffers(c, N);
+    if (packed) packed_buffers(c, N, directed);
     else {
         c->sw_PK.release(); // (held only while packed sweeps run)
         c->sw_D.ensure((size_t)N * N);
@@ -810,7 +839,8 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     fit_sweep_begin(c);
     FitForm fit;
     fit.persistent = !directed && !packed && persistent_wanted(c, N);
-    fit.persistent_dir = directed && persistent_wanted(c, N);
+    fit.persistent_dir = directed && !packed && persistent_wanted(c, N);
+    fit.dir_tiles = !directed ? 0 : packed ? 2 : c->opt_test_fit_dir_tiles ? 1 : 0;
     fit.eps = directed ? 0.9 : 0.25;
     c->stat_fit_persistent = 0;
     c->stat_fit_iters = 0;
@@ -881,7 +911,7 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
     book.write(out, out_len);
     c->stat_exact_packed = packed;
     if (!orig) { // the O(N^2) device storage this sweep required
-        const i64 fpP = c->sweep_used_fp_P ? Nt64 * Nt64 * 64 * (i64)sizeof(double) : 0;
+        const i64 fpP = c->sweep_used_fp_P ? Nt64 * Nt64 * 64 * (i64)sizeof(double) * (directed ? 2 : 1) : 0;
         const i64 logs = c->pow_logs_N == N ? N * N * 12 : 0;
         c->stat_exact_matrix_bytes = packed ? Nt64 * (Nt64 + 1) / 2 * CGE_TILE_DOUBLES * (i64)sizeof(double) + fpP : 16 * N * N + logs + fpP;
     }

@@ -53,6 +53,10 @@ def main(argv=None):
         init_edges, init_vweights, init_eweights, init_embed = edges.copy(), vweights.copy(), weights.copy(), embed.copy()
         distances, embed, comm, edges, weights, vweights, v_to_l = CGE.landmarks(
             edges, weights, vweights, clusters, comm, embed, verbose, land, forced, method, directed)   # :15-16
+    # a directed exact score beyond the resident matrices' limit runs on the packed upper tiles instead of being refused
+    from cge.jl_amd import api
+
+    api.default_context().set_option("exact_packed_directed", 1)
     fn = CGE.wGCL_directed if directed else CGE.wGCL                                 # :18-24
     results = fn(edges, weights, comm, embed, distances, vweights, init_vweights, v_to_l, init_edges, init_eweights,
                  init_embed, split, seed, samples, verbose)

@@ -62,6 +62,7 @@ def main(argv=None):
     n = embed.shape[0]
     embeddings = [embed] + [read_any_embedding(f, n) for f in files[1:]]  # (text: the library's parallel reader)
     ctx = api.default_context()
+    ctx.set_option("exact_packed_directed", 1)  # a directed exact score beyond the resident limit: packed, not refused
     # parseargs' arrays as they are; vweight (src/auxilary.jl:104-110) and the clusters (:199-208) are derived by the library
     # from what is resident -- the same bits and the same clusters as parseargs' own, without its host passes over them
     ctx.set_graph_view(np.asarray(edges), np.asarray(weights, dtype=np.float64), n=n, base=1)

@@ -278,9 +278,10 @@ int cge_wgcl(cge_ctx *ctx, const cge_wgcl_args *args, double out[7], int *out_le
  * the exact mode on the resident graph (distances = zeros, CGE_CLI.jl:4).  Exact mode -- here and in
  * cge_wgcl with an empty v_to_l -- keeps D, GD and the logarithm on the device (17.6 - 28 bytes per vertex pair) up to
  * N ~ 1.06e5 vertices; beyond, an UNDIRECTED sweep runs on the upper 64 x 64 tiles of the current alpha's GD alone
- * (~4.1 bytes per pair: N ~ 2.3e5 on a 288 GB card; option "exact_packed").  A directed exact sweep stays
- * resident and is refused beyond its limit (CGE_E_OOM), as is an undirected one the packed form does not apply to or
- * whose tiles do not fit the free memory (the message names N and the bytes needed).              */
+ * (~4.1 bytes per pair: N ~ 2.3e5 on a 288 GB card; option "exact_packed").  A DIRECTED exact sweep stays
+ * resident and is refused beyond its limit (CGE_E_OOM; the message names option "exact_packed_directed") unless that option
+ * allows it the same tiles (~4.25 bytes per pair: the model's matrix is symmetric, only Tin / Tout are not).  Refused too is a
+ * sweep the packed form does not apply to or whose tiles do not fit the free memory (the message names N and the bytes).  */
 typedef struct {
     const int64_t *clusters_flat, *clusters_off;
     int64_t n_clusters;
@@ -457,6 +458,14 @@ int cge_max_pair_dist(cge_ctx *ctx, int part, int nparts, double *hi, int64_t *a
  *             (N N 8 2.2 > 200e9 bytes), so no sweep that ran before changes; 1 = wherever it applies.  The same iteration
  *             counts; scores equal to the resident form's up to the rounding of vect_B's summation order (bit for bit against
  *             a resident sweep with "fit_persistent" = 1 and "bvec_blocks" = 1).  Directed sweeps are not affected.
+ * "exact_packed_directed": the packed form of a DIRECTED exact sweep, under the conditions of "exact_packed": the upper tiles of the
+ *             current alpha's GD serve the fit (one launch pair per iteration, every tile read once for Sin and Sout of both its
+ *             blocks; never a persistent fit), vect_B (a stored tile gives its own partials and its mirror tile's) and the tallies
+ *             (ordered pairs); no D, no row-major GD, no logarithm.  0 (default) = never: a directed sweep beyond the resident
+ *             limit is refused (CGE_E_OOM), as before; 1 = exactly where the resident matrices would be refused, so no sweep
+ *             that ran before changes (cge_cli.py and cge_compare.py set this); 2 = wherever the form applies.  The same
+ *             iteration counts; scores equal to the resident form's up to the rounding of the sums' order.  No effect on
+ *             undirected sweeps, on landmark mode or on the landmark-mode members of cge_score_batch.
  * "bvec_blocks": 1 = sweeps from 256 vertices on relabel the score graph by community and sum vect_B by 64 x 64 tiles (one read of
  *             GD); 0 (default) = row bins + row sums + fold below 8192 vertices (beyond that the sweep is relabelled and uses the
  *             tiles anyway).  Same results up to the rounding of the summation order; measured no faster at the headline.
@@ -469,8 +478,8 @@ int cge_set_option(cge_ctx *ctx, const char *key, int64_t value);
  * "collective_calls" / "collective_bytes" = all-reduces issued by the in-library RCCL path since cge_create;
  * "diameter_bits" = the bit pattern of the last `hi` (reinterpret the int64 as a double);
  * "fit_batched_launches" / "fit_batched_alphas" = multi-problem fit launches of the last cge_score_batch and the member-alphas they fitted;
- * "exact_packed" = 1 when the last sweep ran in the packed form (option "exact_packed"), "exact_matrix_bytes" = the bytes of O(N^2)
- * device storage the last exact sweep required (packed: the tiles + the fit's partial vectors; resident: D + GD + the logarithm it
+ * "exact_packed" = 1 when the last sweep ran in the packed form (options "exact_packed", "exact_packed_directed"), "exact_matrix_bytes" = the bytes of O(N^2)
+ * device storage the last exact sweep required (packed: the tiles + the fit's partial vectors, two sets when directed; resident: D + GD + the logarithm it
  * used + the partial vectors of a launch-per-iteration fit);
  * "fit_persistent_alphas" = alphas of the last sweep fitted by a persistent launch, "fit_persistent_fallbacks" = persistent fits abandoned since the context was created, "fit_iterations" = Chung-Lu
  * iterations of the last sweep (all alphas); "landmark_batches" / "landmark_batch_rows" / "landmark_splits" =

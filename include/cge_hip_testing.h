@@ -134,10 +134,13 @@ int cge_pow_test(void *ctx, const double *x, int64_t n, double alpha, int method
  * form 0: what a sweep of this shape picks with the context's options (landmarks != 0: a landmark-mode sweep, else exact mode);
  *      1: staged row bins; 2: plain gather; 3: contiguous rows of the relabelled graph; 4: tiles + bins; 5: tiles + the bins
  *      and the divergence in one launch; 6: tiles + the batch's bins / JS launches over two problems, p and p2 (p2->C < p->C;
- *      p2 is read by this form only).  *form_ran = the form that ran.  A relabelled form permutes GD, Ta, Tb and comm by the
+ *      p2 is read by this form only); 7: directed, tiles + bins on the PACKED tiles (GD, which must be symmetric, packed on the
+ *      host through cge_packed_index; bvec_tile_dir_packed_kernel: a workgroup per stored tile writes its partials and its
+ *      mirror tile's, at the positions and with the bits of form 4 directed).  *form_ran = the form that ran.  A relabelled form permutes GD, Ta, Tb and comm by the
  *      layout's order on the host, as the sweep computes GD from permuted rows.
  * CGE_E_ARG, with a message and before any launch, where the form does not apply: form 1 with N > 8192; forms 4-6 with
- * N < 256, C < 2 or more than 64 community ids in a 64-vertex block of the relabelled graph; forms 5, 6 directed.
+ * N < 256, C < 2 or more than 64 community ids in a 64-vertex block of the relabelled graph (form 7 too); forms 5, 6 directed;
+ * form 7 undirected.
  * Not covered here: forms 4-6 make the tile partials by bvec_tile_kernel on a supplied GD; the partials a landmark-mode sweep gets
  * from the epilogue of its fused fit are cge_fused_chain_test's. */
 #define CGE_VECT_B_GUARD 64
@@ -180,9 +183,13 @@ int cge_vect_b_test(void *ctx, const cge_vect_b_problem *p, const cge_vect_b_pro
  *      6: directed, fit_flow_dir_multi_kernel over n_problems (1..16) problems with slots, start vectors and flags of their
  *         own, each on the geometry (G, NW) of its own form-3 launch; per problem the outputs are form 3's: T, Tb, iters, status
  *         (an abandoned launch returns every member's start).
+ *      7: directed, one launch pair per iteration by the tile kernels (fit_symtile_dir_kernel<false> + fit_symreduce_dir_kernel)
+ *         on the row-major GD: every upper tile read once for Sin and Sout of both its blocks, the iterates alternating between
+ *         two buffers, f in a ring of four and epsilon in a ring of two;
+ *      8: directed, the same on the packed tiles (GD packed on the host through cge_packed_index); the bits of form 7.
  *      *form_ran = the form that ran.  n_problems > 1: form 5 (undirected) and form 6 (directed) only.
  * CGE_E_ARG, with a message and before any launch, where a form does not apply: forms 3-6 where the geometry of the persistent
- * fit declines N on this device; forms 2, 4, 5 directed; form 6 undirected; forms 4, 5 without "pow_exp2"; forms 5, 6 with
+ * fit declines N on this device; forms 2, 4, 5 directed; forms 6, 7, 8 undirected; forms 4, 5 without "pow_exp2"; forms 5, 6 with
  * problems of different waves per workgroup, more workgroups in all than the device has CUs or more than 16 problems; form 6
  * with a problem whose workgroups would reduce two quarter blocks each (the multi kernel exists for one).
  * Not covered here: forms 4 and 5 ask nothing of the fused launch's epilogue; its vect_B half and the tallies beside it are
@@ -217,6 +224,8 @@ int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int direc
  *             k_permute_rows first, as local_score_tallies does;
  *     form 2: k_auc_exact on GD (N x N, row-major), Ta, Tb; the pairs index the N score-graph vertices;
  *     form 3: the same on the packed tiles (GD packed on the host through cge_packed_index; undirected: i <= j);
+ *     form 5: k_auc_exact on the packed tiles with ORDERED pairs, as a packed directed sweep tallies them (GD, symmetric, packed
+ *             on the host as for form 3; i > j allowed: a pair below the diagonal tiles reads the stored mirror); directed or not;
  *     form 4: the epilogue of the fused persistent fit, launched as enqueue_alpha launches it with the tally wanted and vect_B
  *             not: tables by fused_tables / k_auc_prepare (through old2new when given), the fit of cge_fit_test form 4 on D (N x N),
  *             w, T0 (sweep order), alpha, eps, delta.  Also out: T[N] = the iterate the launch left, aidx[4 S], afac[8 S],
@@ -404,6 +413,8 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *                                 under contention);
  *   "fit_persistent_test_timeout" 1: the persistent fit abandons every launch at once (the fallback path runs);
  *   "test_bvec_plain"             1: vect_B by the kernels of score graphs beyond the LDS budget / 512 communities;
+ *   "fit_dir_tiles"               1: a resident directed launch-per-iteration fit goes by the tile pair (cge_fit_test form 7)
+ *                                 instead of fit_symv_dir_kernel + fit_update_dir_kernel: the comparator of the packed directed sweep;
  *   "exact_resident_limit"        b: b bytes replace the 200e9 of the resident exact sweep's guard, so that the auto rule of
  *                                 option "exact_packed" and the CGE_E_OOM refusal can be driven at a few hundred vertices (0: the
  *                                 default).  This one does change which form runs;
