@@ -981,6 +981,16 @@ class Context:
         assert nref.value == w
         return P, ran.value, ref, mean
 
+    def ref_dist2_test(self, refs):
+        """Testing hook (cge_ref_dist2_test): the squared distances of the reference points `refs` (nref, d) as the pruned
+        diameter forms them.  Returns (rd2 (nref, nref), centring mean (d,))."""
+        refs = _f64(refs)
+        assert refs.ndim == 2 and refs.shape[1] == self.d
+        nref = refs.shape[0]
+        rd2, mean = np.zeros((nref, nref)), np.zeros(self.d)
+        self._check(self.L.cge_ref_dist2_test(self.h, _p(refs), C.c_int64(nref), _p(rd2), _p(mean)))
+        return rd2, mean
+
     def landmark_graph_test(self, v_to_l, N, directed=False, wedge_form=0, part=0, nparts=1, aggregate=False, wedges=True,
                             positive=None, degrees=False, world=0):
         """Testing hook (include/cge_hip_testing.h: cge_landmark_graph_test): the landmark graph of the assignment v_to_l (n ids
@@ -1423,7 +1433,7 @@ class Context:
         return mem, nc, rounds, q, core.astype(bool)
 
     _TEST_OPTIONS = ("louvain_wave_len", "fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
-                     "exact_resident_limit", "test_eig_roles", "fit_dir_tiles")
+                     "exact_resident_limit", "test_eig_roles", "fit_dir_tiles", "test_pcent_form")
 
     def set_option(self, key, value):
         if key in self._TEST_OPTIONS:  # the testing knobs are not part of the boundary (include/cge_hip_testing.h)

@@ -398,6 +398,8 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     if (!strcmp(key, "test_rss2_one_kernel")) { c->opt_test_rss2_one_kernel = value != 0; return CGE_OK; }
     // which wave of a batched eigen-solver workgroup plays which role: 0 by SIMD placement, 1 identity, 2 reversed, 3 rotated by one
     if (!strcmp(key, "test_eig_roles") && value >= 0 && value <= 3) { c->opt_test_eig_roles = (int)value; return CGE_OK; }
+    // the form of the bf16-split bound pass of the diameter: 0 by the number of reference points, 1 streaming, 2 register-resident
+    if (!strcmp(key, "test_pcent_form") && value >= 0 && value <= 2) { c->opt_test_pcent_form = (int)value; return CGE_OK; }
     // start skew of the persistent fits' tile waves, in naps of ~3 us
     if (!strcmp(key, "fit_persistent_test_delay") && value >= 0 && value <= 100000) { c->opt_fit_test_delay = (int)value; return CGE_OK; }
     // 1 = the persistent fit abandons every launch at once
@@ -587,6 +589,15 @@ int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int
     if (!c || !v2l || !lcomm || !P || !nref || !pass_ran || N <= 0 || C <= 0 || pass < 0 || pass > 2) return CGE_E_ARG;
     CGE_TRY_ON_DEVICE(c)
     host_diameter_bounds_test(c, v2l, N, lcomm, C, pass, P, nref, pass_ran, ref_points, mean);
+    CGE_CATCH(c)
+}
+
+// testing hook (include/cge_hip_testing.h): the squared distances of caller-supplied reference points, as the diameter forms them
+int cge_ref_dist2_test(void *ctx, const double *refs, int64_t nref, double *rd2, double *mean) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !refs || !rd2 || nref <= 0) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_ref_dist2_test(c, refs, nref, rd2, mean);
     CGE_CATCH(c)
 }
 

@@ -419,6 +419,8 @@ struct cge_ctx {
     int opt_test_rss2_one_kernel = 0; // testing: rss2 by rss2_walk_kernel at every width (the comparator of the chain + merge form)
     int opt_test_eig_roles = 0; // testing: the roles of group_eig_kernel's waves (0 by SIMD placement, 1 identity, 2 reversed, 3 rotated by
                                 // one); the results must not depend on it
+    int opt_test_pcent_form = 0; // testing: the form of the bf16-split bound pass (0 by the number of reference points, 1 streaming,
+                                 // 2 register-resident); the results must not depend on it
     i64 opt_test_louvain_wave_len = -2; // testing: Louvain levels >= 2 decide segments longer than this by a wave (-2: the default
                                         // length, -1: every vertex, 2^31 - 1: none); the results must not depend on it
     int opt_ecg_group = 0; // cge_ecg: members that run their rounds in lock-step (0: chosen from the free memory, g >= 1: at most g)
@@ -1041,6 +1043,7 @@ double host_diameter_brute(cge_ctx *c, int part, int nparts, i64 *ai, i64 *aj);
 double host_diameter_landmarks(cge_ctx *c, const double *lemb, const double *lweight, const std::vector<i32> &lcomm, i64 C, i64 N);
 void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lcomm1, i64 C, int pass, double *P, i64 *nref_out,
                                int *pass_ran, double *ref_out, double *mean_out);
+void host_ref_dist2_test(cge_ctx *c, const double *refs, i64 nref, double *rd2, double *mean_out);
 // score_host.cpp
 struct cge_landmark_graph_io;
 void host_landmark_graph_test(cge_ctx *c, cge_landmark_graph_io *io);

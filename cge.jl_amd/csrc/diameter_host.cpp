@@ -6,7 +6,8 @@
 //   dm_prepare, dm_bound_pass               the landmark-sorted layout and the bounds P[a][r] >= max_{i in a} ||x_i - ref_r||^2;
 //   host_diameter_pruned                    branch and bound over landmark pairs, a list of stages sharing a DmSearch;
 //   host_diameter_landmarks                 the entry of a score: pruned, brute force where the bounds prune too little;
-//   host_diameter_bounds_test               the testing hook of the bound passes.
+//   host_diameter_bounds_test               the testing hook of the bound passes;
+//   host_ref_dist2_test                     the testing hook of the reference points' distance matrix.
 #include <algorithm>
 #include <cmath>
 #include <functional>
@@ -716,4 +717,25 @@ void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lco
     HIP_CHECK(hipStreamSynchronize(st));
     *nref_out = S.nref;
     *pass_ran = c->stat_bound_pass;
+}
+
+// Testing hook (include/cge_hip_testing.h: cge_ref_dist2_test): the reference points' mutual squared distances for caller-supplied
+// rows -- the gather of dm_prepare's reference operand (centred with the resident embedding's mean, feature-major, fp64), then
+// the launch wrapper dm_seed_sweep uses.
+void host_ref_dist2_test(cge_ctx *c, const double *refs, i64 nref, double *rd2, double *mean_out) {
+    const i64 d = c->d, dpad = c->dpad;
+    if (!c->Xr.p || c->n <= 0 || d <= 0) CGE_THROW(CGE_E_ARG, "reference distances: embedding not resident");
+    hipStream_t st = c->stream;
+    const i64 ldm = (nref + 127) / 128 * 128;
+    DevBuf<double> dref;
+    dref.ensure((size_t)nref * d);
+    HIP_CHECK(hipMemcpyAsync(dref.p, refs, sizeof(double) * nref * d, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    c->Ms.ensure((size_t)ldm * dpad);
+    c->mnorm.ensure(ldm);
+    k_gather_centre_fm(c, dref.p, nullptr, c->gmean.p, c->Ms.p, c->mnorm.p, nref, d, ldm, dpad, nullptr, nullptr, (dpad + 31) / 32 * 32, nullptr);
+    k_ref_dist2_fm(c, c->Ms.p, nref, dpad, ldm);
+    HIP_CHECK(hipMemcpyAsync(rd2, c->mp_rd2.p, sizeof(double) * (size_t)(nref * nref), hipMemcpyDeviceToHost, st));
+    if (mean_out) HIP_CHECK(hipMemcpyAsync(mean_out, c->gmean.p, sizeof(double) * d, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
 }

@@ -662,6 +662,7 @@ __global__ __launch_bounds__(256, 2) void pcent_f32_rowres_kernel(const float *_
 typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
 typedef short s8v __attribute__((ext_vector_type(8)));
 #define PB_APAD 8         // bf16 elements of padding per LDS row (16 bytes: the 16-byte fragment reads of 32 rows spread over the banks)
+#define PB_REG_MIN_LDM 384 // the register-resident form (2d) from this many padded reference points on
 #define PB_T 512 // 8 waves: 4 (row blocks of 32) x 2 (column blocks of 64); two waves per SIMD cover each other's LDS / epilogue latencies
 // Both operands of a (row tile, column tile) pair are RESIDENT in LDS with their whole K (2 planes x 128 x K bf16 each:
 // 139 KB at K = 128).  The next column tile of the reference points (or the next row tile of X and its first column tile)
@@ -790,6 +791,167 @@ __global__ __launch_bounds__(PB_T) void pcent_bf16_kernel(const unsigned short *
             }
             if (more_cols) stash(Bh, Bl, bv);
             __syncthreads(); // gmax may be overwritten, the next column tile read
+        }
+    }
+}
+// (2d) The register-resident form of (2c), for wide sets of reference points.  A wave owns 64 reference points of a 512-wide
+// column super-tile and ALL 128 rows of the row tile: its B fragments (both planes, every k-step: 16 NKS VGPRs, 128 at K = 128)
+// are loaded once per super-tile and stay in registers, so the reference points are never fetched twice.  The row tiles of X
+// pass through two LDS buffers (the layout of (2c)): tile t + 1 is stored and tile t + 2 requested while tile t is multiplied,
+// with one barrier per row tile.  Per 32-row block and k-step the MFMAs run in (2c)'s order (ah.bh, ah.bl, al.bh, k ascending,
+// one accumulator per 32 x 32 block), so every fp32 sum -- and every entry of P -- has (2c)'s bits.  Because a wave holds every
+// row of its columns, the 16-row group maxima and the runs of equal sub_land are combined in the lane: no LDS round trip and
+// no barrier in the epilogue, one atomic max per (landmark run, column).  A wave whose 64 columns lie past ldm (a partly
+// filled super-tile) only helps to move X.
+template <int NKS>
+__global__ __launch_bounds__(PB_T) void pcent_bf16_reg_kernel(const unsigned short *__restrict__ Xb, const double *__restrict__ rns,
+                                                              i64 lds_rows, const unsigned short *__restrict__ Mb,
+                                                              const double *__restrict__ mnorm, i64 ldm,
+                                                              const i32 *__restrict__ sub_land, i64 nref,
+                                                              unsigned long long *__restrict__ P, i64 I0, i64 I1, double e1) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short ldsb[];
+    constexpr i64 KP = 16 * NKS;
+    constexpr int LDA = (int)KP + PB_APAD;
+    constexpr size_t ABUF = (size_t)2 * 128 * LDA;                   // one buffer: the two planes of a row tile
+    double *rnl = reinterpret_cast<double *>(ldsb + 2 * ABUF);       // [2 buffers][128 rows]: the inflated squared norms
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l32 = lane & 31, lh = lane >> 5;
+    // a row tile moves as in (2c): half a wave per row, lane = 16-byte piece of the row's two planes, 8 sweeps of 16 rows
+    constexpr int apieces = (int)(KP / 8);
+    const int arow = tid >> 5, apc = tid & 31;
+    const bool aact = apc < 2 * apieces;
+    const int apl = aact && apc >= apieces ? 1 : 0, akk = 8 * (apc - apl * apieces);
+    // in halves of 64 rows (16 VGPRs in flight, not 32: with the 128 of the fragments the kernel stays within 256 without scratch)
+    uint4 av[4];
+    double rv = 0.0;
+    const size_t aoff = ((size_t)apl * lds_rows + arow) * KP + akk;
+    auto fetch = [&](i64 r0, int half) {
+        const unsigned short *px = Xb + (r0 + 64 * half) * KP + aoff; // (one address per fetch; the sweeps are constant offsets)
+#pragma unroll
+        for (int it = 0; it < 4; it++)
+            av[it] = aact ? *reinterpret_cast<const uint4 *>(px + (size_t)16 * it * KP) : make_uint4(0, 0, 0, 0);
+        if (half == 0 && tid < 128) rv = rns[r0 + tid];
+    };
+    auto stash = [&](int s, int half) {
+        if (aact) {
+#pragma unroll
+            for (int it = 0; it < 4; it++)
+                *reinterpret_cast<uint4 *>(ldsb + s * ABUF + (size_t)apl * 128 * LDA + (size_t)(64 * half + 16 * it + arow) * LDA + akk) = av[it];
+        }
+        if (half == 0 && tid < 128) rnl[s * 128 + tid] = rv * e1;
+    };
+    const i64 step = gridDim.x;
+    for (i64 c0 = 0; c0 < ldm; c0 += 512) { // column super-tiles: X is streamed once per super-tile
+        const i64 cb = c0 + 64 * wave;
+        const bool own = cb < ldm; // (ldm is a multiple of 128: a wave's 64 columns are all inside or all outside)
+        s8v bh[2][NKS], bl[2][NKS];
+        double mne[2];
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            const size_t ob = (size_t)(own ? cb + b * 32 + l32 : 0) * KP + 8 * lh;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ks++) {
+                bh[b][ks] = *reinterpret_cast<const s8v *>(Mb + ob + 16 * ks);
+                bl[b][ks] = *reinterpret_cast<const s8v *>(Mb + (size_t)ldm * KP + ob + 16 * ks);
+            }
+            mne[b] = mnorm[own ? cb + b * 32 + l32 : 0] * e1;
+        }
+        i64 I = I0 + blockIdx.x;
+        asm volatile("" : "+s"(I)); // (opaque: the first tile's addresses are formed here, not kept in registers across the super-tiles)
+        if (I < I1) { // (the previous super-tile's readers passed the barrier that ended its last row tile)
+            fetch(I * 128, 0);
+            stash(0, 0);
+            fetch(I * 128, 1);
+            stash(0, 1);
+        }
+        if (I + step < I1) fetch((I + step) * 128, 0);
+        __syncthreads();
+        for (int s = 0; I < I1; I += step, s ^= 1) {
+            const bool more = I + step < I1;
+            const unsigned short *Ah = ldsb + s * ABUF, *Al = Ah + (size_t)128 * LDA;
+            const double *rn = rnl + s * 128;
+            const i32 *sl = sub_land + ((I * 128) >> 4);
+            int curland = -1;
+            double cur[2] = {0.0, 0.0};
+            // the run of groups of one landmark so far joins P[landmark][column] (bit patterns of non-negative doubles order like
+            // integers)
+            auto flush = [&]() {
+                if (curland >= 0 && lh == 0) {
+#pragma unroll
+                    for (int b = 0; b < 2; b++) {
+                        const i64 col = cb + b * 32 + l32;
+                        if (col < nref) atomicMax(&P[(i64)curland * nref + col], (unsigned long long)__double_as_longlong(cur[b]));
+                    }
+                }
+            };
+#pragma unroll 1
+            for (int rb = 0; rb < 4; rb++) { // 32-row blocks: one block's accumulators are live at a time
+                if (own) {
+                    f16v acc[2];
+#pragma unroll
+                    for (int b = 0; b < 2; b++)
+#pragma unroll
+                        for (int r = 0; r < 16; r++) acc[b][r] = 0.f;
+                    // the A fragments of k-step ks + 1 are read while the six MFMAs of ks run; the fences keep the scheduler from
+                    // lifting every k-step's reads to the front (64 more VGPRs: scratch)
+                    const size_t oa = (size_t)(rb * 32 + l32) * LDA + 8 * lh;
+                    s8v ah = *reinterpret_cast<const s8v *>(Ah + oa), al = *reinterpret_cast<const s8v *>(Al + oa);
+#pragma unroll
+                    for (int ks = 0; ks < NKS; ks++) {
+                        s8v nh = ah, nl = al;
+                        if (ks + 1 < NKS) {
+                            nh = *reinterpret_cast<const s8v *>(Ah + oa + 16 * (ks + 1));
+                            nl = *reinterpret_cast<const s8v *>(Al + oa + 16 * (ks + 1));
+                        }
+#pragma unroll
+                        for (int b = 0; b < 2; b++) {
+                            acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8v, ah), __builtin_bit_cast(bf8v, bh[b][ks]), acc[b], 0, 0, 0);
+                            acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8v, ah), __builtin_bit_cast(bf8v, bl[b][ks]), acc[b], 0, 0, 0);
+                            acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8v, al), __builtin_bit_cast(bf8v, bh[b][ks]), acc[b], 0, 0, 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        ah = nh;
+                        al = nl;
+                    }
+#pragma unroll
+                    for (int h = 0; h < 2; h++) { // the two 16-row groups of the block (see (2c): a non-finite sum counts as +Inf)
+                        const int land = sl[rb * 2 + h]; // uniform
+                        double v[2] = {-1e300, -1e300};
+#pragma unroll
+                        for (int q = 0; q < 8; q++) {
+                            const double rq = rn[rb * 32 + 16 * h + 8 * (q >> 2) + 4 * lh + (q & 3)];
+#pragma unroll
+                            for (int b = 0; b < 2; b++) {
+                                const float af = acc[b][8 * h + q];
+                                const double t = rq - 2.0 * (double)af;
+                                v[b] = fmax(v[b], (af - af == 0.f) ? t : 1e300);
+                            }
+                        }
+                        const bool fresh = land != curland; // a new run of groups: the finished one goes out first
+                        if (fresh) {
+                            flush();
+                            curland = land;
+                        }
+#pragma unroll
+                        for (int b = 0; b < 2; b++) {
+                            double w = fmax(v[b], __shfl_xor(v[b], 32));
+                            w = fmax(w + mne[b], 0.0);
+                            cur[b] = fresh ? w : fmax(cur[b], w);
+                        }
+                    }
+                }
+                // the next row tile moves into the other buffer (its last readers passed the barrier that ended the previous row
+                // tile), a half behind each pair of row blocks; the half after it is requested at once
+                if (more && rb == 1) {
+                    stash(s ^ 1, 0);
+                    fetch((I + step) * 128, 1);
+                }
+            }
+            if (own) flush();
+            if (more) {
+                stash(s ^ 1, 1);
+                if (I + 2 * step < I1) fetch((I + 2 * step) * 128, 0);
+            }
+            __syncthreads(); // the next tile is in LDS, and this one may be overwritten from the middle of the next round on
         }
     }
 }
@@ -953,14 +1115,26 @@ void k_pcent_bf16(cge_ctx *c, const unsigned short *Xb, const double *rns, i64 l
     const i64 nTI = lds_rows / 128, I0 = nTI * part / nparts, I1 = nTI * (part + 1) / nparts;
     const double e1 = 1.0 + 1.05 * (3.0 * (double)(KP + 2) * 1.1920928955078125e-07 + 3.2 * 1.52587890625e-05); // 2^-23, 2^-16
     if (I1 > I0) {
-        const size_t lds = (size_t)4 * 128 * (KP + PB_APAD) * sizeof(unsigned short) + (size_t)8 * 128 * sizeof(double); // both operands, both planes, whole K + the group maxima
-        const int pb_diag = 0; // (the kernel's timing diagnostics: 1 no epilogue, 2 no MFMA loop)
+        // the register-resident form (2d) from PB_REG_MIN_LDM padded reference points on (at least 6 of its 8 waves own columns);
+        // testing knob test_pcent_form: 1 the streaming form always, 2 the register form always -- the same bits either way
+        const bool reg = c->opt_test_pcent_form == 2 || (c->opt_test_pcent_form == 0 && ldm >= PB_REG_MIN_LDM);
+        // streaming: both operands, both planes, whole K + the group maxima; register: two buffers of X + their norms
+        const size_t lds = (size_t)4 * 128 * (KP + PB_APAD) * sizeof(unsigned short) + (size_t)(reg ? 2 : 8) * 128 * sizeof(double);
+        const int pb_diag = 0; // (the streaming kernel's timing diagnostics: 1 no epilogue, 2 no MFMA loop)
+        const dim3 grid((unsigned)std::min<i64>(I1 - I0, 256));
+        unsigned long long *Pu = reinterpret_cast<unsigned long long *>(P);
 #define PB_GO(NKS)                                                                                                         \
     do {                                                                                                                   \
-        auto kern = pcent_bf16_kernel<NKS>;                                                                                 \
-        cge_allow_lds((const void *)kern, 160 * 1024); \
-        hipLaunchKernelGGL(kern, dim3((unsigned)std::min<i64>(I1 - I0, 256)), dim3(PB_T), lds, c->stream, Xb, rns, lds_rows, Mb, \
-                           mnorm, ldm, sub_land, N, reinterpret_cast<unsigned long long *>(P), I0, I1, e1, pb_diag);        \
+        if (reg) {                                                                                                         \
+            auto kern = pcent_bf16_reg_kernel<NKS>;                                                                        \
+            cge_allow_lds((const void *)kern, 160 * 1024);                                                                 \
+            hipLaunchKernelGGL(kern, grid, dim3(PB_T), lds, c->stream, Xb, rns, lds_rows, Mb, mnorm, ldm, sub_land, N, Pu, I0, I1, e1); \
+        } else {                                                                                                           \
+            auto kern = pcent_bf16_kernel<NKS>;                                                                            \
+            cge_allow_lds((const void *)kern, 160 * 1024);                                                                 \
+            hipLaunchKernelGGL(kern, grid, dim3(PB_T), lds, c->stream, Xb, rns, lds_rows, Mb, mnorm, ldm, sub_land, N, Pu, I0, I1, e1, \
+                               pb_diag);                                                                                   \
+        }                                                                                                                  \
     } while (0)
         if (KP == 32) PB_GO(2);
         else if (KP == 64) PB_GO(4);
@@ -1044,18 +1218,39 @@ __global__ __launch_bounds__(256) void bound_select_kernel(const double *__restr
         }
     }
 }
-// the same from the centred feature-major copy Ms (dpad x ldm, zero padded): workgroup a, thread b, coalesced along b
+// the same from the centred feature-major copy Ms (dpad x ldm, zero padded; ldm a multiple of 128), in tiles of 32 x 32 entries:
+// a workgroup stages the feature-major columns of its 32 a's and 32 b's in LDS, RD_KC features at a time, and a thread carries
+// four independent (a, b) chains.  Every entry is the sequential s += df * df over k ascending (unfused: -ffp-contract=off).
+#define RD_T 32  // entries per tile side
+#define RD_KC 64 // features per LDS chunk (32 KB for both blocks)
 __global__ __launch_bounds__(256) void ref_dist2_fm_kernel(const double *__restrict__ Ms, i64 nref, i64 dpad, i64 ldm,
                                                            double *__restrict__ rd2) {
-    const i64 a = blockIdx.x;
-    for (i64 b = threadIdx.x; b < nref; b += blockDim.x) {
-        double s = 0.0;
-#pragma unroll 8
-        for (i64 k = 0; k < dpad; k++) { // (dpad is a multiple of 16: eight pairs of loads in flight per round)
-            const double df = Ms[k * ldm + a] - Ms[k * ldm + b];
-            s += df * df;
+    __shared__ double As[RD_KC * RD_T], Bs[RD_KC * RD_T];
+    const i64 a0 = (i64)blockIdx.y * RD_T, b0 = (i64)blockIdx.x * RD_T;
+    const int tb = threadIdx.x & 31, ta = threadIdx.x >> 5; // thread: column b0 + tb, rows a0 + ta + 8 j
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (i64 k0 = 0; k0 < dpad; k0 += RD_KC) {
+        const int kc = dpad - k0 < RD_KC ? (int)(dpad - k0) : RD_KC;
+        if (k0) __syncthreads(); // the previous chunk's readers are done
+        for (int kk = ta; kk < kc; kk += 8) { // (a0 + 32, b0 + 32 <= ldm)
+            As[kk * RD_T + tb] = Ms[(k0 + kk) * ldm + a0 + tb];
+            Bs[kk * RD_T + tb] = Ms[(k0 + kk) * ldm + b0 + tb];
         }
-        rd2[a * nref + b] = s;
+        __syncthreads();
+#pragma unroll 4
+        for (int kk = 0; kk < kc; kk++) {
+            const double vb = Bs[kk * RD_T + tb];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const double df = As[kk * RD_T + ta + 8 * j] - vb;
+                s[j] += df * df;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const i64 a = a0 + ta + 8 * j, b = b0 + tb;
+        if (a < nref && b < nref) rd2[a * nref + b] = s[j];
     }
 }
 // ---- the same selection in two levels, when the reference points are the landmarks' communities -----------------------
@@ -1119,7 +1314,9 @@ __global__ __launch_bounds__(256) void bound_expand_kernel(const double *__restr
 void k_ref_dist2_fm(cge_ctx *c, const double *Ms_fm, i64 nref, i64 dpad, i64 ldm) {
     c->mp_rd2.ensure((size_t)nref * nref);
     // (differences of centred values: the centre cancels; the 1e-9 margins of the bound cover the rounding)
-    hipLaunchKernelGGL(ref_dist2_fm_kernel, dim3((unsigned)nref), dim3(256), 0, c->stream, Ms_fm, nref, dpad, ldm, c->mp_rd2.p);
+    const unsigned nt = (unsigned)((nref + RD_T - 1) / RD_T);
+    // (nt <= 65535, a grid's second dimension: beyond 2 million reference points rd2 itself is out of reach)
+    hipLaunchKernelGGL(ref_dist2_fm_kernel, dim3(nt, nt), dim3(256), 0, c->stream, Ms_fm, nref, dpad, ldm, c->mp_rd2.p);
 }
 // the candidate landmark pairs (bounds Q, reference-point distances c->mp_rd2 from k_ref_dist2_fm) into `list`; returns their
 // number (synchronises).  `ref_off` / `ref_mem` (optional, device): the landmarks grouped by reference point (lref[a] = community

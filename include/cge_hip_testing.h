@@ -76,6 +76,12 @@ int cge_group_cut_test(void *ctx, const int32_t *ids, const int32_t *task_row_of
  * row-major, uncentred) and mean (d): what the device centred with */
 int cge_diameter_bounds_test(void *ctx, const int64_t *v2l, int64_t N, const int64_t *lcomm, int64_t C, int pass, double *P,
                              int64_t *nref, int *pass_ran, double *ref_points, double *mean);
+/* kernel-level hook (needs the GPU): the mutual squared distances of caller-supplied reference points as the pruned diameter
+ * forms them for its candidate selection -- refs (nref x d doubles, row-major, d of the resident embedding) are centred with the
+ * resident embedding's mean into the feature-major copy (the gather of the bound pass's reference operand), then one launch of
+ * the distance kernel.  rd2 (nref x nref, row-major): rd2[a][b] = the sequential sum over k ascending of fl(fl(a_k - m_k) -
+ * fl(b_k - m_k))^2, unfused.  Optional: mean (d), what the device centred with */
+int cge_ref_dist2_test(void *ctx, const double *refs, int64_t nref, double *rd2, double *mean);
 /* kernel-level hook (needs the GPU): the stage of a landmark run that turns an assignment into the landmark graph, on a caller's
  * v2l[n] (ids in 1..N) over the resident graph and vertex data, by the stage's own functions and launch wrappers (the ones
  * cge_landmarks_run and cge_score call).  Every output pointer may be NULL: that work is skipped.  The call drops the results of
@@ -424,7 +430,10 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *                                 chain + merge form runs otherwise: the two forms give the same bits;
  *   "test_eig_roles"              v: which wave of a workgroup of the batched eigen-solver (d <= 128) owns which column block and runs
  *                                 the tridiagonal tail: 0 (default) chosen by the waves' SIMDs, 1 the wave's number, 2 reversed,
- *                                 3 rotated by one: every choice gives the same bits.                                            */
+ *                                 3 rotated by one: every choice gives the same bits;
+ *   "test_pcent_form"             v: the form of the bf16-split bound pass of the pruned diameter: 0 (default) by the number of
+ *                                 reference points, 1 the streaming form always, 2 the register-resident form wherever the
+ *                                 pass applies (d <= 128): both forms give the same bits.                                        */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
 /* needs the GPU: the resident row-major fp64 matrix as this rank holds it (all n rows; under shard_rows its own rows, in
  * local order, with their global 0-based ids in ids_out, which may be NULL otherwise).  *rows and *d are set first; a capacity
