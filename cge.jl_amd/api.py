@@ -335,6 +335,13 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _host_array(x):  # a numpy array of a numpy array, a sequence or a torch tensor (any device)
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(x, torch.Tensor):
+        return x.detach().cpu().numpy()
+    return np.asarray(x)
+
+
 def _colmajor(a):  # (rows, cols) array -> flat buffer in Julia (column-major) order
     a = np.asfortranarray(np.asarray(a, dtype=np.float64))
     return a, a.ravel(order="K")
@@ -1422,6 +1429,70 @@ class Context:
         self._check(self.L.cge_ecg(self.h, C.byref(args), _p(out), C.byref(nc), C.byref(q), C.byref(q_ecg), _p(w) if edge_weights else None))
         return (out, nc.value, q.value, q_ecg.value) + ((w,) if edge_weights else ())
 
+    # ---- link prediction under the fitted model (cge_link_*) -------------------------------------------
+    _LINK_WHICH = {"local": 1, "global": 2}  # CGE_LINK_BEST_LOCAL / CGE_LINK_BEST_GLOBAL
+
+    def link_fit(self, clusters, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000,
+                 which="local"):
+        """`score` that also keeps the geometric Chung-Lu model of one alpha (cge_link_fit): which = "local" the alpha of element
+        5 (best local score), "global" the alpha of element 1 (best divergence).  Returns (vector, trace); both equal `score`'s."""
+        if which not in self._LINK_WHICH:
+            raise ValueError(f"link_fit: which = {which!r} is neither 'local' nor 'global'")
+        flat, off, ncl = _cluster_args(clusters)
+        a = ScoreArgs()
+        a.clusters_flat, a.clusters_off, a.n_clusters = getattr(_p(flat), "value", None), getattr(_p(off), "value", None), ncl
+        a.land, a.forced, a.method = int(land), int(forced), _method_code(method)
+        a.directed, a.split, a.seed, a.auc_samples = int(bool(directed)), int(bool(split)), int(seed), int(auc_samples)
+        out = np.zeros(7)
+        olen = C.c_int(7)
+        tr = Trace()
+        self._check(self.L.cge_link_fit(self.h, C.byref(a), C.c_int(self._LINK_WHICH[which]), _p(out), C.byref(olen), C.byref(tr)))
+        self.last_trace = tr.as_dict()
+        return out[: olen.value].copy(), self.last_trace
+
+    def link_set_model(self, alpha, hi, f_out, f_in=None, directed=False):
+        """A caller-supplied model over the resident embedding and graph: p(i, j) = f_out[i] f_in[j] max(0, 1 - dist / hi)^alpha
+        (f_in = None: f_out)."""
+        fo = _f64(_host_array(f_out)).ravel()
+        fi = None if f_in is None else _f64(_host_array(f_in)).ravel()
+        if fi is not None and len(fi) != len(fo):
+            raise ValueError("link_set_model: f_out and f_in differ in length")
+        self._check(self.L.cge_link_set_model(self.h, C.c_int(int(bool(directed))), C.c_double(float(alpha)), C.c_double(float(hi)),
+                                              _p(fo), _p(fi), C.c_int64(len(fo))))
+
+    def link_model(self):
+        """The resident link model: {"directed", "alpha", "hi", "f_out", "f_in", "T_out", "T_in"}; the T's are the landmark (exact
+        mode: vertex) iterates of a fitted model, empty for a supplied one."""
+        d, alpha, hi, N = C.c_int(), C.c_double(), C.c_double(), C.c_int64()
+        self._check(self.L.cge_link_model_fetch(self.h, C.byref(d), C.byref(alpha), C.byref(hi), None, None, None, None, C.byref(N)))
+        fo, fi = np.zeros(self.n), np.zeros(self.n)
+        To, Ti = np.zeros(N.value), np.zeros(N.value)
+        self._check(self.L.cge_link_model_fetch(self.h, None, None, None, _p(fo), _p(fi), _p(To) if N.value else None,
+                                                _p(Ti) if N.value else None, None))
+        return {"directed": bool(d.value), "alpha": alpha.value, "hi": hi.value, "f_out": fo, "f_in": fi, "T_out": To, "T_in": Ti}
+
+    def link_prob(self, i, j):
+        """The model's probability of the pairs (i[q], j[q]): 1-based vertex ids as `draw_samples` returns them (numpy arrays or
+        torch tensors, any integer type)."""
+        ii, jj = _i64(_host_array(i)).ravel(), _i64(_host_array(j)).ravel()
+        if len(ii) != len(jj):
+            raise ValueError("link_prob: i and j differ in length")
+        out = np.zeros(len(ii))
+        self._check(self.L.cge_link_prob(self.h, _p(ii), _p(jj), C.c_int64(len(ii)), _p(out)))
+        return out
+
+    def link_topk(self, queries, k, exclude_edges=True):
+        """Per query vertex (1-based ids, repeats allowed) the k most probable candidates j != i under the model, sorted by
+        (p descending, j ascending); exclude_edges leaves out the query's resident neighbours (directed: its out-neighbours).
+        Returns (j (Q, k) 1-based, p (Q, k), count (Q,)); unused slots hold 0 / 0.0."""
+        q = _i64(_host_array(queries)).ravel()
+        Q, k = len(q), int(k)
+        kk = max(k, 1)
+        oj, op, oc = np.zeros((Q, kk), dtype=np.int64), np.zeros((Q, kk)), np.zeros(Q, dtype=np.int64)
+        self._check(self.L.cge_link_topk(self.h, _p(q), C.c_int64(Q), C.c_int64(k), C.c_int(int(bool(exclude_edges))), _p(oj), _p(op),
+                                         _p(oc)))
+        return oj, op, oc
+
     def ecg_members_test(self, members=16, seed=0):
         """Testing hook (cge_ecg_members_test): the member and peel stages of `ecg` alone -- (members (K, n) each renumbered as a
         pass is, n_comm (K,), rounds (K,), modularity (K,), core (n,) bool)."""
@@ -1590,6 +1661,23 @@ def score_tensors(edge_index, embeddings, comm, land, forced=4, method="rss", di
     ctx.set_vertex_view(comm, None, base=base)
     res = ctx.score_views(members, FROM_COMM, land, forced, method, directed, split, seed, auc_samples)
     return res[0] if one else res
+
+
+def link_predict(edge_index, embedding, comm, land, queries, k, forced=4, method="rss", directed=False, split=False, seed=-1,
+                 auc_samples=10000, which="local", exclude_edges=True, weights=None, base=-1, ctx=None):
+    """Link prediction on tensors as held, in the manner of `score_tensors`: the graph and the embedding go in as views, the
+    model of the best alpha (`which`) is fitted by `Context.link_fit`, and the k most probable candidates of every query vertex
+    come back from `Context.link_topk`.  `queries`: 1-based vertex ids (None: every vertex).  Returns (vector, j, p, count);
+    the model stays in the context for `link_prob` / further `link_topk` calls."""
+    ctx = ctx or default_context()
+    ctx.set_graph_view(edge_index, weights, n=int(embedding.shape[0]), base=base)
+    ctx.set_vertex_view(comm, None, base=base)
+    ctx.set_embedding_view(embedding)
+    vec, _ = ctx.link_fit(FROM_COMM, land, forced, method, directed, split, seed, auc_samples, which)
+    if len(vec) < 7:  # a directed star graph: the reference's early return, no model
+        return vec, None, None, None
+    q = np.arange(1, ctx.n + 1, dtype=np.int64) if queries is None else queries
+    return (vec,) + ctx.link_topk(q, k, exclude_edges)
 
 
 def draw_samples(ctx, seed, S, directed=False, n_sets=1):

@@ -251,6 +251,40 @@ int cge_score_views(cge_ctx *c, const cge_score_args *a, const cge_embedding_vie
     return score_batch_run(c, a, views, K, "score_views", out, out_len, traces);
 }
 
+// ---- link prediction under the fitted model (link_host.cpp) -------------------------------------------
+int cge_link_fit(cge_ctx *c, const cge_score_args *a, int which, double out[7], int *out_len, cge_trace *trace) {
+    if (!c || !a || !out || !out_len) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_fit(c, a, which, out, out_len, trace);
+    CGE_CATCH(c)
+}
+int cge_link_set_model(cge_ctx *c, int directed, double alpha, double hi, const double *f_out, const double *f_in, int64_t n) {
+    if (!c || !f_out) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_set_model(c, directed, alpha, hi, f_out, f_in, n);
+    CGE_CATCH(c)
+}
+int cge_link_model_fetch(cge_ctx *c, int *directed, double *alpha, double *hi, double *f_out, double *f_in, double *T_out,
+                         double *T_in, int64_t *N) {
+    if (!c) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_model_fetch(c, directed, alpha, hi, f_out, f_in, T_out, T_in, N);
+    CGE_CATCH(c)
+}
+int cge_link_prob(cge_ctx *c, const int64_t *i, const int64_t *j, int64_t P, double *out) {
+    if (!c || !i || !j || !out) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_prob(c, i, j, P, out);
+    CGE_CATCH(c)
+}
+int cge_link_topk(cge_ctx *c, const int64_t *queries, int64_t Q, int64_t k, int exclude_edges, int64_t *out_j, double *out_p,
+                  int64_t *out_cnt) {
+    if (!c || !queries || !out_j || !out_p || !out_cnt) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_topk(c, queries, Q, k, exclude_edges, out_j, out_p, out_cnt);
+    CGE_CATCH(c)
+}
+
 // ---- helpers ----------------------------------------------------------------------------------------
 int64_t cge_idx(int64_t n, int64_t i, int64_t j) { return n * (i - 1) - (i - 1) * (i - 2) / 2 + j - i + 1; }
 
@@ -438,6 +472,8 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "ecg_member_rounds")) *value = c->stat_ecg_member_rounds; // rounds summed over the members,
     else if (!strcmp(key, "ecg_peel_rounds")) *value = c->stat_ecg_peel_rounds;     // rounds of the 2-core that removed a vertex,
     else if (!strcmp(key, "ecg_levels")) *value = c->stat_ecg_levels;               // levels of the final hierarchy
+    else if (!strcmp(key, "link_topk_survivors")) *value = c->link.stat_survivors; // of the last cge_link_topk: pairs evaluated exactly,
+    else if (!strcmp(key, "link_topk_queries")) *value = c->link.stat_queries;     // its queries
     else if (!strcmp(key, "cut_tie_tasks")) { // (read from the device on request: a synchronising copy)
         int v = 0;
         if (c->cut_ties.p && (hipStreamSynchronize(c->stream) != hipSuccess ||

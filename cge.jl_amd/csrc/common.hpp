@@ -268,6 +268,38 @@ struct DevSamples { // one sample set as the AUC kernels read it (device, 0-base
     DevBuf<double> afac;
 };
 
+// The link model of cge_link_* (link_host.cpp): the geometric Chung-Lu model of ONE alpha over the resident embedding and graph,
+// p(i, j) = f_out[i] f_in[j] max(0, 1 - dist(i, j) / hi)^alpha.  Fitted (cge_link_fit: the sweep's own iterate at a best alpha,
+// copied aside while the sweep runs) or supplied (cge_link_set_model).  Dropped by whatever replaces the resident inputs.
+struct LinkModel {
+    bool valid = false;
+    int directed = 0;
+    int pow_form = 0;        // the power as the sweep's local score took it: 0 the library pow, 1 log_parts + exp2_parts (pow_parts.hpp)
+    double alpha = 0.0, hi = 0.0;
+    i64 n = 0, NT = 0;       // vertices; iterates of a fitted model (landmarks, or vertices in exact mode; 0: supplied)
+    DevBuf<double> f;        // f_out[n], f_in[n] (two copies of one vector when undirected)
+    DevBuf<double> T;        // T_out[NT], T_in[NT], original numbering
+    DevBuf<double> ftile;    // max of f_in over every 128 candidates (the top-k filter's bound), ldn / 128 entries
+    // the resident edge list as sorted 64-bit keys (a << 32 | b; undirected: a <= b), built on the first top-k that excludes edges
+    DevBuf<unsigned long long> keys, keys_in;
+    i64 nkeys = 0;
+    bool keys_ready = false;
+    // cge_link_fit while its sweep runs: which best is wanted (0: no capture), and what was copied aside last
+    int cap_which = 0;
+    bool cap_have = false;
+    double cap_alpha = 0.0, cap_hi = 0.0; // cap_hi: the diameter the sweep normalised by; cap_pow: the form of its power
+    int cap_pow = 0;
+    i64 cap_N = 0;
+    DevBuf<double> cap_T;    // Ta[N], Tb[N] of the captured alpha, original numbering
+    // scratch of the calls (grow-only)
+    DevBuf<i32> ids;
+    DevBuf<double> vals, Xq, rq, lp;
+    DevBuf<i32> lj, lcnt;
+    DevBuf<i64> oj, ocnt;
+    DevBuf<unsigned long long> surv;
+    i64 stat_survivors = 0, stat_queries = 0; // exact evaluations / queries of the last cge_link_topk
+};
+
 struct cge_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -537,6 +569,8 @@ struct cge_ctx {
     hipEvent_t samp_ev = nullptr;
     SampleSet smp;                 // library-drawn samples of the running score
     std::vector<std::unique_ptr<DevSamples>> dsets; // their device form (wgcl_host.cpp)
+
+    LinkModel link;                // cge_link_* (link_host.cpp)
 
     // ---- profiling -------------------------------------------------------------------------
     bool profiling = false;
@@ -1025,6 +1059,15 @@ void k_gather_i32(cge_ctx *c, const i32 *arr, const i32 *idx, i64 S, i32 *out); 
 void k_mark_edge_hits(cge_ctx *c, const i32 *src, const i32 *dst, i64 m, int directed, const uint64_t *table,
                       i64 table_size, i32 *hit);
 
+// kernels_link.hip: the link model's kernels
+// f_out[v] = (Ta[l] vw[v]) / lw[l], f_in[v] likewise from Tb, l = v2l[v] -- auc_landmark_kernel's own factors; v2l == nullptr: f = T
+void k_link_expand(cge_ctx *c, const double *Ta, const double *Tb, const i32 *v2l, const double *vw, const double *lw, i64 n,
+                   double *f_out, double *f_in);
+void k_link_tile_max(cge_ctx *c, const double *f_in, i64 n, i64 ntiles, double *ftile); // max over every 128 entries
+void k_link_prob(cge_ctx *c, const i32 *pi, const i32 *pj, i64 P, double *out);        // the resident model on 0-based pairs
+void k_link_keys(cge_ctx *c);                                                           // the sorted edge keys of the model
+// the top-k lists of Q queries (0-based ids, device) against every vertex: out_j (1-based) / out_p (Q x k), out_cnt (Q), device
+void k_link_topk(cge_ctx *c, const i32 *qid, i64 Q, int k, bool exclude, i64 *out_j, double *out_p, i64 *out_cnt);
 // ---- host modules -----------------------------------------------------------------------------
 // landmarks_host.cpp
 void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
@@ -1044,6 +1087,19 @@ double host_diameter_landmarks(cge_ctx *c, const double *lemb, const double *lwe
 void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lcomm1, i64 C, int pass, double *P, i64 *nref_out,
                                int *pass_ran, double *ref_out, double *mean_out);
 void host_ref_dist2_test(cge_ctx *c, const double *refs, i64 nref, double *rd2, double *mean_out);
+void host_ensure_centred(cge_ctx *c); // Xc / rnorm: the centred feature-major copy of the resident embedding (made on first demand)
+// link_host.cpp: what the cge_link_* entry points do, and the sweep's side of cge_link_fit
+static inline void link_drop(cge_ctx *c) { c->link.valid = false; c->link.keys_ready = false; }
+// a sweep that cge_link_fit runs calls this when alpha has just become the best of the wanted kind: Ta / Tb (N each, the sweep's
+// numbering; old2new un-permutes a relabelled sweep) are copied aside on the stream
+void link_capture(cge_ctx *c, const double *Ta, const double *Tb, i64 N, const i32 *old2new, double alpha);
+void host_link_fit(cge_ctx *c, const cge_score_args *a, int which, double out[7], int *out_len, cge_trace *trace);
+void host_link_set_model(cge_ctx *c, int directed, double alpha, double hi, const double *f_out, const double *f_in, i64 n);
+void host_link_model_fetch(cge_ctx *c, int *directed, double *alpha, double *hi, double *f_out, double *f_in, double *T_out,
+                           double *T_in, int64_t *N);
+void host_link_prob(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, double *out);
+void host_link_topk(cge_ctx *c, const int64_t *queries, i64 Q, i64 k, int exclude_edges, int64_t *out_j, double *out_p,
+                    int64_t *out_cnt);
 // score_host.cpp
 struct cge_landmark_graph_io;
 void host_landmark_graph_test(cge_ctx *c, cge_landmark_graph_io *io);

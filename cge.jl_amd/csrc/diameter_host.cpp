@@ -164,6 +164,7 @@ static void ensure_centred(cge_ctx *c) {
     k_gather_centre_fm(c, c->Xr.p, nullptr, c->gmean.p, c->Xc.p, c->rnorm.p, c->n, c->d, c->ldn, c->dpad);
     c->centred_ready = true;
 }
+void host_ensure_centred(cge_ctx *c) { ensure_centred(c); } // (the link model's top-k reads the same operands: link_host.cpp)
 
 // Brute force over this rank's share of the pair tiles.  The arg-max launch leaves the largest Gram value `bv` of the shard's
 // tiles and the workgroups' own (bv negative: the shard holds no pair); the pairs within rounding of it are evaluated with

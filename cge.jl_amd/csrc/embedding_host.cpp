@@ -307,6 +307,7 @@ static void ingest_finish(Ingest &S) {
 
 void set_embedding_view(cge_ctx *c, const char *who, const cge_embedding_view *v, i64 n) {
     Ingest S{c, who, v, n};
+    link_drop(c); // (a link model refers to the resident embedding)
     ingest_check(S);
     ingest_place(S);
     if (v->on_device) bring_device(S);

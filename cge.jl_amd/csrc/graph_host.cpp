@@ -108,6 +108,7 @@ void set_graph_view(cge_ctx *c, const char *who, const cge_graph_view *g, i64 m,
     std::string msg;
     if (graph_view_check(g, m, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s: %s", who, msg.c_str());
     if (n < 0 || n >= (1LL << 31)) CGE_THROW(CGE_E_ARG, "%s: n = %lld (0 .. 2^31 - 1; 0 = the maximum id)", who, (long long)n);
+    link_drop(c); // (a link model refers to the resident graph)
     const bool dev = g->on_device != 0, i64ids = g->id_dtype == CGE_ID_I64;
     if (dev) {
         check_device_pointer(c, who, g->src);
@@ -249,6 +250,7 @@ static void derive_vertex_weights(cge_ctx *c, const char *who, i64 n) {
 
 void set_vertex_view(cge_ctx *c, const char *who, const cge_vertex_view *v, i64 n, bool derive_vw) {
     if (!v || n <= 0) throw CgeError{CGE_E_ARG, c->err}; // (a bare status: the message stays)
+    link_drop(c); // (a link model refers to the resident vertex data)
     const bool dev = v->on_device != 0;
     if (v->comm) {
         if (v->id_dtype != CGE_ID_I64 && v->id_dtype != CGE_ID_I32) CGE_THROW(CGE_E_ARG, "%s: unknown id dtype %d", who, v->id_dtype);

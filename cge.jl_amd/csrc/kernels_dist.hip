@@ -321,10 +321,7 @@ __device__ __forceinline__ void reduce_best(double best, i64 best_i, i64 best_j,
     }
 }
 
-// The Gram value of a pair from the squared norms of its centred rows and their dot product: g = fl(fl(r_i + r_j) - 2 <x_i, x_j>).
-// The arg-max kernels (1), (3) and the near-tie kernel (3b) all rank pairs by THIS expression: the near-tie guarantee
-// (diameter_host.cpp) needs the three to agree bit for bit.
-__device__ __forceinline__ double gram_value(double ri, double rj, double dot) { return ri + rj - 2.0 * dot; }
+// (gram_value, the expression every kernel here ranks or filters pairs by: mfma_tile.hpp)
 
 // (1) brute force over all tile pairs J >= I of ONE operand
 __global__ __launch_bounds__(256, 2) void max_pair_kernel(const double *__restrict__ Xc,
@@ -1532,6 +1529,7 @@ __global__ __launch_bounds__(256) void pair_dist_tile_kernel(const double *__res
 }
 void k_pair_dist(cge_ctx *c, const double *Xr, i64 d, const i32 *pi, const i32 *pj, i64 S, double den, double *out) {
     if (S <= 0) return;
+    ScopedKernelTimer t(c, "pair_dist");
     const size_t lds = (size_t)16 * (d + 1) * sizeof(double);
     if (S >= 4096 && lds <= 64 * 1024) {
         const unsigned nb = (unsigned)std::min<i64>((S + 15) / 16, 256 * 16);

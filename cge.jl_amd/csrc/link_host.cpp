@@ -1,0 +1,184 @@
+// link_host.cpp -- the host side of cge_link_* (include/cge_hip.h): the link model in the context, fitted by a score's own sweep
+// or supplied by the caller, and its two queries (kernels_link.hip).
+#include "common.hpp"
+
+#include <cmath>
+
+static void link_need_inputs(cge_ctx *c, const char *who) {
+    if (!c->Xr.p || c->d <= 0 || !c->src.p || c->n <= 0 || c->m <= 0)
+        CGE_THROW(CGE_E_ARG, "%s: embedding and graph must be resident (cge_set_embedding / cge_set_graph)", who);
+    if (c->has_coll || c->rccl_comm || c->edges_sharded || c->rows_sharded || c->opt_shard_ingest || c->opt_shard_rows)
+        CGE_THROW(CGE_E_ARG, "%s: not under collectives or sharding", who);
+}
+static void link_need_model(cge_ctx *c, const char *who) {
+    if (!c->link.valid) CGE_THROW(CGE_E_ARG, "%s: no link model (cge_link_fit / cge_link_set_model)", who);
+}
+// 1-based int64 ids -> 0-based int32, checked before anything is enqueued
+static void link_ids(const char *who, const char *what, const int64_t *ids, i64 cnt, i64 n, std::vector<i32> &out, size_t at) {
+    for (i64 q = 0; q < cnt; q++) {
+        if (ids[q] < 1 || ids[q] > n)
+            CGE_THROW(CGE_E_ARG, "%s: %s %lld is vertex %lld, outside 1..%lld", who, what, (long long)(q + 1), (long long)ids[q], (long long)n);
+        out[at + (size_t)q] = (i32)(ids[q] - 1);
+    }
+}
+// the model's derived table: the largest f_in of every 128 candidates (the top-k filter's bound)
+static void link_finish(cge_ctx *c) {
+    LinkModel &m = c->link;
+    const i64 nt = c->ldn / 128;
+    m.ftile.ensure((size_t)nt);
+    k_link_tile_max(c, m.f.p + m.n, m.n, nt, m.ftile.p);
+    m.keys_ready = false;
+    m.valid = true;
+}
+
+// ---- cge_link_fit ------------------------------------------------------------------------------------------------------------------
+void link_capture(cge_ctx *c, const double *Ta, const double *Tb, i64 N, const i32 *old2new, double alpha) {
+    LinkModel &m = c->link;
+    m.cap_T.ensure((size_t)2 * N);
+    if (old2new) { // dst[v] = src[old2new[v]]: as local_score_tallies un-permutes a relabelled sweep's T
+        k_permute_rows(c, Ta, old2new, N, 1, m.cap_T.p);
+        k_permute_rows(c, Tb, old2new, N, 1, m.cap_T.p + N);
+    } else {
+        HIP_CHECK(hipMemcpyAsync(m.cap_T.p, Ta, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+        HIP_CHECK(hipMemcpyAsync(m.cap_T.p + N, Tb, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+    }
+    m.cap_have = true;
+    m.cap_alpha = alpha;
+    m.cap_N = N;
+}
+
+void host_link_fit(cge_ctx *c, const cge_score_args *a, int which, double out[7], int *out_len, cge_trace *trace) {
+    if (which != CGE_LINK_BEST_LOCAL && which != CGE_LINK_BEST_GLOBAL)
+        CGE_THROW(CGE_E_ARG, "link_fit: which = %d is neither CGE_LINK_BEST_LOCAL nor CGE_LINK_BEST_GLOBAL", which);
+    if (which == CGE_LINK_BEST_LOCAL && a->auc_samples < 1)
+        CGE_THROW(CGE_E_ARG, "link_fit: the best local score needs auc_samples >= 1 (%lld given)", (long long)a->auc_samples);
+    link_need_inputs(c, "link_fit");
+    LinkModel &m = c->link;
+    link_drop(c);
+    m.cap_have = false;
+    m.cap_which = which;
+    struct Disarm { // whatever happens, the next plain score captures nothing
+        LinkModel &m;
+        ~Disarm() { m.cap_which = 0; }
+    } disarm{m};
+    host_score(c, a, out, out_len, trace, nullptr, false);
+    m.cap_which = 0;
+    if (*out_len != 7 || !m.cap_have) return; // a directed star graph's early return, or no best of the wanted kind: no model
+    const bool landmarks = a->land != -1;
+    const i64 n = c->n, N = m.cap_N;
+    m.directed = a->directed ? 1 : 0;
+    m.alpha = m.cap_alpha;
+    m.hi = m.cap_hi;
+    m.pow_form = m.cap_pow;
+    m.n = n;
+    m.NT = N;
+    m.T.ensure((size_t)2 * N);
+    HIP_CHECK(hipMemcpyAsync(m.T.p, m.cap_T.p, sizeof(double) * 2 * N, hipMemcpyDeviceToDevice, c->stream));
+    m.f.ensure((size_t)2 * n);
+    if (landmarks) k_link_expand(c, m.T.p, m.T.p + N, c->v2l.p, c->vw.p, c->lweight.p, n, m.f.p, m.f.p + n);
+    else k_link_expand(c, m.T.p, m.T.p + N, nullptr, nullptr, nullptr, n, m.f.p, m.f.p + n);
+    link_finish(c);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+// ---- cge_link_set_model / cge_link_model_fetch -------------------------------------------------------------------------------------
+void host_link_set_model(cge_ctx *c, int directed, double alpha, double hi, const double *f_out, const double *f_in, i64 n) {
+    link_need_inputs(c, "link_set_model");
+    if (n != c->n) CGE_THROW(CGE_E_ARG, "link_set_model: n = %lld, the resident inputs have %lld vertices", (long long)n, (long long)c->n);
+    if (!std::isfinite(alpha) || alpha <= 0.0) CGE_THROW(CGE_E_ARG, "link_set_model: alpha = %g is not a positive finite number", alpha);
+    if (!std::isfinite(hi) || hi <= 0.0) CGE_THROW(CGE_E_ARG, "link_set_model: hi = %g is not a positive finite number", hi);
+    if (!directed && f_in && f_in != f_out)
+        CGE_THROW(CGE_E_ARG, "link_set_model: an undirected model has one factor per vertex (f_in must be NULL)");
+    for (int s = 0; s < 2; s++) {
+        const double *f = s ? f_in : f_out;
+        if (!f) continue;
+        for (i64 v = 0; v < n; v++)
+            if (!std::isfinite(f[v]) || f[v] < 0.0)
+                CGE_THROW(CGE_E_ARG, "link_set_model: %s[%lld] = %g is negative or not finite", s ? "f_in" : "f_out", (long long)(v + 1), f[v]);
+    }
+    LinkModel &m = c->link;
+    link_drop(c);
+    m.directed = directed ? 1 : 0;
+    m.alpha = alpha;
+    m.hi = hi;
+    m.pow_form = 0;
+    m.n = n;
+    m.NT = 0;
+    m.f.ensure((size_t)2 * n);
+    HIP_CHECK(hipMemcpyAsync(m.f.p, f_out, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(m.f.p + n, f_in ? f_in : f_out, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    link_finish(c);
+    HIP_CHECK(hipStreamSynchronize(c->stream)); // (the caller's arrays are borrowed for the call)
+}
+
+void host_link_model_fetch(cge_ctx *c, int *directed, double *alpha, double *hi, double *f_out, double *f_in, double *T_out,
+                           double *T_in, int64_t *N) {
+    link_need_model(c, "link_model_fetch");
+    const LinkModel &m = c->link;
+    if (directed) *directed = m.directed;
+    if (alpha) *alpha = m.alpha;
+    if (hi) *hi = m.hi;
+    if (N) *N = m.NT;
+    hipStream_t st = c->stream;
+    if (f_out) HIP_CHECK(hipMemcpyAsync(f_out, m.f.p, sizeof(double) * m.n, hipMemcpyDeviceToHost, st));
+    if (f_in) HIP_CHECK(hipMemcpyAsync(f_in, m.f.p + m.n, sizeof(double) * m.n, hipMemcpyDeviceToHost, st));
+    if (T_out && m.NT > 0) HIP_CHECK(hipMemcpyAsync(T_out, m.T.p, sizeof(double) * m.NT, hipMemcpyDeviceToHost, st));
+    if (T_in && m.NT > 0) HIP_CHECK(hipMemcpyAsync(T_in, m.T.p + m.NT, sizeof(double) * m.NT, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// ---- cge_link_prob -----------------------------------------------------------------------------------------------------------------
+void host_link_prob(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, double *out) {
+    link_need_model(c, "link_prob");
+    if (P < 1) CGE_THROW(CGE_E_ARG, "link_prob: P = %lld pairs", (long long)P);
+    LinkModel &m = c->link;
+    std::vector<i32> h((size_t)2 * P);
+    link_ids("link_prob", "i of pair", i, P, m.n, h, 0);
+    link_ids("link_prob", "j of pair", j, P, m.n, h, (size_t)P);
+    m.ids.ensure((size_t)2 * P);
+    m.vals.ensure((size_t)P);
+    hipStream_t st = c->stream;
+    HIP_CHECK(hipMemcpyAsync(m.ids.p, h.data(), sizeof(i32) * 2 * P, hipMemcpyHostToDevice, st));
+    k_link_prob(c, m.ids.p, m.ids.p + P, P, m.vals.p);
+    HIP_CHECK(hipMemcpyAsync(out, m.vals.p, sizeof(double) * P, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    flush_timers(c);
+}
+
+// ---- cge_link_topk -----------------------------------------------------------------------------------------------------------------
+// The queries go in chunks of 16384 (128 row tiles): the lists' scratch and the gathered query operand stay bounded, and a chunk
+// of that size already fills the device.
+void host_link_topk(cge_ctx *c, const int64_t *queries, i64 Q, i64 k, int exclude_edges, int64_t *out_j, double *out_p,
+                    int64_t *out_cnt) {
+    link_need_model(c, "link_topk");
+    if (k < 1 || k > 64) CGE_THROW(CGE_E_ARG, "link_topk: k = %lld is outside 1..64", (long long)k);
+    if (Q < 1) CGE_THROW(CGE_E_ARG, "link_topk: Q = %lld queries", (long long)Q);
+    LinkModel &m = c->link;
+    std::vector<i32> h((size_t)Q);
+    link_ids("link_topk", "query", queries, Q, m.n, h, 0);
+    hipStream_t st = c->stream;
+    host_ensure_centred(c);
+    if (exclude_edges) k_link_keys(c);
+    const i64 chunk = 16384;
+    const i64 cq = std::min(Q, chunk);
+    m.ids.ensure((size_t)Q);
+    m.oj.ensure((size_t)cq * k);
+    m.vals.ensure((size_t)cq * k);
+    m.ocnt.ensure((size_t)cq);
+    m.surv.ensure(1);
+    HIP_CHECK(hipMemcpyAsync(m.ids.p, h.data(), sizeof(i32) * Q, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(m.surv.p, 0, sizeof(unsigned long long), st));
+    for (i64 q0 = 0; q0 < Q; q0 += chunk) {
+        const i64 nq = std::min(chunk, Q - q0);
+        k_link_topk(c, m.ids.p + q0, nq, (int)k, exclude_edges != 0, m.oj.p, m.vals.p, m.ocnt.p);
+        HIP_CHECK(hipMemcpyAsync(out_j + q0 * k, m.oj.p, sizeof(i64) * nq * k, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(out_p + q0 * k, m.vals.p, sizeof(double) * nq * k, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(out_cnt + q0, m.ocnt.p, sizeof(i64) * nq, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // (the next chunk reuses the device outputs)
+    }
+    unsigned long long surv = 0;
+    HIP_CHECK(hipMemcpy(&surv, m.surv.p, sizeof(surv), hipMemcpyDeviceToHost));
+    m.stat_survivors = (i64)surv;
+    m.stat_queries = Q;
+    flush_timers(c);
+}

@@ -15,6 +15,11 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #define MP_SB 32           // super-block edge in tiles
 
 
+// The Gram value of a pair from the squared norms of its centred rows and their dot product: g = fl(fl(r_i + r_j) - 2 <x_i, x_j>).
+// The arg-max kernels (1), (3) and the near-tie kernel (3b) of kernels_dist.hip all rank pairs by THIS expression: the near-tie
+// guarantee (diameter_host.cpp) needs the three to agree bit for bit.  The link model's top-k (kernels_link.hip) filters by it.
+__device__ __forceinline__ double gram_value(double ri, double rj, double dot) { return ri + rj - 2.0 * dot; }
+
 // One 128x128 Gram tile G = A_tile * B_tile^T over the whole contraction dimension, operands delivered by
 // loader functors: la(kc, q) / lb(kc, q) return this thread's two adjacent elements (columns c2, c2+1 of the
 // tile) of k-row kc*MP_BK + wave + 4q.  SAME = true: B is A (a diagonal tile of a SYRK) -- staged once.

@@ -20,6 +20,7 @@ struct AlphaSlot {
     bool shared_verdict = false; // N > 1, tallies split: the verdict of the fit travelled with the all-reduced tallies
     int t0_par = 0;              // the part of TT that held T_0 of this alpha
     i64 iters = 0;
+    const double *Ta = nullptr, *Tb = nullptr; // where this alpha's iterate lives (directed: Tout, Tin) until the next alphas overwrite it
 };
 
 // The form of the fit from alpha to alpha (a persistent form, once given up, stays given up for the sweep), the part of TT that

@@ -746,6 +746,7 @@ static void enqueue_alpha(cge_ctx *c, const SweepView &sw, i64 ia, bool want_auc
     if (!sl.fit_async) fit.prev_iters = sl.iters;
     const double *Tcur = c->fp_T.p + (i64)fit.tpar * sw.Tld;
     const double *Ta = sw.directed ? c->sw_T2.p : Tcur, *Tb = sw.directed ? c->sw_T1.p : Tcur; // (Tout, Tin)
+    sl.Ta = Ta; sl.Tb = Tb;
     if (want_auc && !(sl.fused && ff.auc_part))
         local_score_tallies(c, Ta, Tb, N, sw.directed, sw.orig, sw.old2new, *c->dsets[set], sw.s0, sw.s1, alpha, sw.packed);
     if (sw.shard) {
@@ -906,9 +907,26 @@ void host_wgcl_sweep(cge_ctx *c, const ScoreGraph &G_in, const OrigView *orig, c
         }
         c->stat_fit_iters += sl.iters;
         book.take(res, AlphaBook::AlphaStep * (double)ia, sl.iters);
+        // cge_link_fit: this alpha has just become the best of the wanted kind -- its iterate is still where the slot says (the
+        // next alpha, if already enqueued, reads it and writes another part of the ring; the one after is not enqueued yet;
+        // directed sweeps are not enqueued ahead at all), so it is copied aside on the stream.  A redone alpha gets here once.
+        if (c->link.cap_which) {
+            const double a_now = AlphaBook::AlphaStep * (double)ia;
+            if ((c->link.cap_which == CGE_LINK_BEST_LOCAL ? book.best_alpha_auc : book.best_alpha) == a_now)
+                link_capture(c, sl.Ta, sl.Tb, N, sw.old2new, a_now);
+        }
         if (book.ended()) break;
     }
     book.write(out, out_len);
+    if (c->link.cap_which) { // what the model takes from the sweep besides the iterate: the diameter it normalised by, the power's form
+        double lohi[2] = {0.0, orig ? orig->hi : 0.0};
+        if (!orig) {
+            HIP_CHECK(hipMemcpyAsync(lohi, c->sw_lohi.p, sizeof(lohi), hipMemcpyDeviceToHost, c->stream));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+        }
+        c->link.cap_hi = lohi[1];
+        c->link.cap_pow = orig ? 0 : packed ? (c->opt_pow_exp2 ? 1 : 0) : (c->pow_logs_N == N ? 1 : 0);
+    }
     c->stat_exact_packed = packed;
     if (!orig) { // the O(N^2) device storage this sweep required
         const i64 fpP = c->sweep_used_fp_P ? Nt64 * Nt64 * 64 * (i64)sizeof(double) * (directed ? 2 : 1) : 0;

@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""cge_links.py -- link prediction under the model a score fits (an extension; the reference prints the score alone).
+
+Takes cge_cli.py's flags (src/auxilary.jl:61-219) and scores the embedding the same way, but keeps the geometric Chung-Lu model
+of the best alpha and asks it for predictions:
+
+    python cge_links.py -g graph.edgelist -c graph.ecg -e graph.embedding -l 200 --seed 42 --topk 10
+
+    --which local|global   the alpha whose model is kept: the best local score (element 5, default) or the best divergence (1)
+    --topk K               per query vertex, the K (1..64, default 10) most probable vertices it has no edge to
+    --queries FILE         the query vertices, one id per line (default: every vertex, in chunks)
+    --pairs FILE           instead of top-k lists: the model's probability of the pairs `i j` of FILE, one per line
+    --keep-edges           do not leave the query's own neighbours out (the model's nearest candidates: graph reconstruction)
+
+stdout: the 7-vector line cge_cli.py prints, then one `i j p` line per prediction, ids in the edge file's own base (0 or 1).
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from cge_cli import julia_float, julia_vector  # noqa: E402
+
+CHUNK = 16384  # query vertices per call when every vertex is asked
+
+
+class LinkArgError(Exception):
+    pass
+
+
+def link_args(argv):
+    """The flags of this script beside cge_cli.py's: {"which", "topk", "queries", "pairs", "exclude"}.  Needs no GPU."""
+    argv = list(argv)
+
+    def value(flag):
+        if flag not in argv:
+            return None
+        i = argv.index(flag)
+        if i + 1 >= len(argv) or argv[i + 1].startswith("-"):
+            raise LinkArgError(f"{flag} needs a value")
+        return argv[i + 1]
+
+    which = value("--which") or "local"
+    if which not in ("local", "global"):
+        raise LinkArgError(f"--which is local or global, not {which}")
+    topk = value("--topk")
+    try:
+        topk = 10 if topk is None else int(topk)
+    except ValueError:
+        raise LinkArgError(f"--topk takes a number, not {topk}") from None
+    if not 1 <= topk <= 64:
+        raise LinkArgError("--topk is 1 .. 64")
+    queries, pairs = value("--queries"), value("--pairs")
+    if queries is not None and pairs is not None:
+        raise LinkArgError("--queries and --pairs exclude each other")
+    for flag, fn in (("--queries", queries), ("--pairs", pairs)):
+        if fn is not None and not os.path.isfile(fn):
+            raise LinkArgError(f"{flag}: {fn} is not a file")
+    if which == "local" and "--samples-local" in argv and int(value("--samples-local")) < 1:
+        raise LinkArgError("--which local needs --samples-local >= 1")
+    return {"which": which, "topk": topk, "queries": queries, "pairs": pairs, "exclude": "--keep-edges" not in argv}
+
+
+def read_ids(path, columns, base, n):
+    """The ids of a query / pair file as 1-based int64 (rows, columns), checked against 1..n; `base` is the edge file's."""
+    from cge.jl_amd import api
+
+    raw = api.read_table(path, column_major=False)[0]
+    if raw.shape[1] < columns:
+        raise LinkArgError(f"{path}: {columns} column(s) of ids expected, {raw.shape[1]} found")
+    raw = raw[:, :columns]
+    if not np.all(raw == np.floor(raw)):
+        raise LinkArgError(f"{path}: ids must be integers")
+    ids = raw.astype(np.int64) + (1 - base)
+    if ids.size and (ids.min() < 1 or ids.max() > n):
+        raise LinkArgError(f"{path}: an id outside the graph's {n} vertices")
+    return ids
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    try:
+        la = link_args(argv)
+    except LinkArgError as e:
+        print(f"cge_links: {e}", file=sys.stderr)
+        return 1
+    import cge.jl_amd as CGE
+    from cge.jl_amd import api
+
+    (edges, weights, vweights, comm, clusters, embed, verbose, land, forced, method, directed, split, seed,
+     samples) = CGE.parseargs(argv)
+    base = int(api.read_table(CGE.args._flag_value(argv, "-g"), column_major=False)[0][:, :2].min())  # the file's own id base
+    n = len(vweights)
+    ctx = api.default_context()
+    ctx.set_option("exact_packed_directed", 1)  # as cge_cli.py
+    ctx.set_inputs(edges, weights, vweights, comm, embed)
+    try:
+        vec, trace = ctx.link_fit(clusters, land, forced, method, directed, split, seed, samples, la["which"])
+        sys.stderr.write("." * trace["n_alpha"] + "\n")
+        print(julia_vector(vec))
+        if len(vec) < 7:  # a directed star graph: the reference's early return leaves no model
+            return 0
+        out = sys.stdout
+        if la["pairs"] is not None:
+            ij = read_ids(la["pairs"], 2, base, n)
+            p = ctx.link_prob(ij[:, 0], ij[:, 1]) if len(ij) else np.zeros(0)
+            for (i, j), v in zip(ij, p):
+                out.write(f"{i - 1 + base} {j - 1 + base} {julia_float(float(v))}\n")
+            return 0
+        q = read_ids(la["queries"], 1, base, n)[:, 0] if la["queries"] is not None else np.arange(1, n + 1, dtype=np.int64)
+        for q0 in range(0, len(q), CHUNK):
+            part = q[q0:q0 + CHUNK]
+            jj, pp, cnt = ctx.link_topk(part, la["topk"], la["exclude"])
+            for r, i in enumerate(part):
+                for t in range(int(cnt[r])):
+                    out.write(f"{i - 1 + base} {jj[r, t] - 1 + base} {julia_float(float(pp[r, t]))}\n")
+    except LinkArgError as e:
+        print(f"cge_links: {e}", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -365,6 +365,57 @@ int cge_ecg(cge_ctx *ctx, const cge_ecg_args *args, int64_t *comm_out /* n, 0-ba
             double *modularity /* original graph */, double *modularity_ecg /* reweighted graph, may be NULL */,
             double *edge_weights_out /* m, edge order, may be NULL */);
 
+/* ---- link prediction under the fitted model (an extension) ---------------------------------------------------------------------
+ * The local score, elements 5-7 of the result vector, is a link-prediction AUC of the geometric Chung-Lu model fitted at an alpha
+ * (src/divergence.jl:178-213, directed :478-517).  These entry points keep that model and evaluate it on the caller's pairs:
+ *     p(i, j) = f_out[i] * f_in[j] * max(0, 1 - dist(i, j) / hi) ^ alpha         (evaluated left to right as written)
+ * with dist = src/auxilary.jl:14-20 in pair_dist_kernel's arithmetic (ascending k, one rounding per operation; dist(i, i) = 0), hi
+ * the point-set diameter (lo = 0: the diagonal of D is 0, so (D - lo) / (hi - lo) = D / hi to the bit), and the factors
+ *     landmark mode:  f[v] = T[l_v] * vw_v / lw[l_v]  (:187-188; directed: Tout into f_out, Tin into f_in, :488-489),
+ *     exact mode:     f = T  (:174, :474).
+ * A link model {directed, alpha, hi, f_out[n], f_in[n]} lives on the device beside the resident embedding and edge list it refers
+ * to.  Every call that replaces the resident embedding, graph or vertex data (cge_set_embedding*, cge_set_graph*, cge_set_vertex_*,
+ * cge_score_batch / cge_score_views, an exact-mode cge_wgcl) drops it; afterwards cge_link_model_fetch / cge_link_prob /
+ * cge_link_topk answer CGE_E_ARG "no link model".  Not under collectives or sharding (CGE_E_ARG).
+ * The power is taken in the form the sweep's local score used, so that the values have the bits its tallies compared: the library
+ * pow in landmark mode (auc_landmark_kernel) and for a supplied model; in exact mode the per-element chain of the power matrix
+ * (log2(1 - x) to ~70 bits, then exp2: option "pow_exp2", else the library pow).  The base is clamped at 0 (only a supplied hi
+ * below the diameter can make it negative).  Undirected values are symmetric in (i, j).  A non-finite embedding is not supported:
+ * its probabilities are NaN and cge_link_topk's lists are unspecified.                                                           */
+#define CGE_LINK_BEST_LOCAL 1  /* the alpha of element 5 (best local score) */
+#define CGE_LINK_BEST_GLOBAL 2 /* the alpha of element 1 (best divergence)  */
+/* cge_score(args) that also keeps the model of one alpha.  out, out_len, trace, every stat and the iteration counts are what
+ * cge_score gives on the same context with the same options, bit for bit: it is ONE sweep, and with no model wanted that sweep
+ * enqueues exactly what it always did.  The kept T is the sweep's own iterate at that alpha (warm-started as the sweep warms it,
+ * :118) -- the T the reported score was computed from -- copied aside on the stream when the alpha becomes the best of the wanted
+ * kind; a relabelled sweep's T is un-permuted to the original numbering.  Afterwards the factors are expanded on the device and
+ * hi is the value the sweep normalised by.  A directed star graph's early return (out_len = 6) leaves no model, and so does a
+ * sweep that never recorded a best of the wanted kind.  CGE_E_ARG: under collectives or sharding (as cge_score_batch); `which`
+ * other than the two values; CGE_LINK_BEST_LOCAL with auc_samples < 1.                                                          */
+int cge_link_fit(cge_ctx *ctx, const cge_score_args *args, int which, double out[7], int *out_len, cge_trace *trace);
+/* A caller-supplied model over the resident embedding and graph (f_in = NULL: f_in = f_out).  CGE_E_ARG, before any device work:
+ * no resident embedding or graph; n other than the resident n; alpha or hi non-finite or <= 0; a negative or non-finite factor;
+ * directed = 0 with an f_in of its own (an undirected model has one factor per vertex).                                          */
+int cge_link_set_model(cge_ctx *ctx, int directed, double alpha, double hi, const double *f_out, const double *f_in /* NULL: = f_out */,
+                       int64_t n);
+/* The resident model; every output is optional.  f_out / f_in: n doubles each; T_out / T_in: the *N landmark (exact mode: vertex)
+ * iterates of a fitted model in the original numbering (undirected: the same vector twice); *N = 0 for a supplied model.         */
+int cge_link_model_fetch(cge_ctx *ctx, int *directed, double *alpha, double *hi, double *f_out, double *f_in, double *T_out,
+                         double *T_in, int64_t *N);
+/* out[q] = p(i[q], j[q]) for P >= 1 pairs of 1-based vertex ids (an id outside 1 .. n: CGE_E_ARG, before any device work).      */
+int cge_link_prob(cge_ctx *ctx, const int64_t *i, const int64_t *j, int64_t P, double *out);
+/* For every query i, in the order given (repeats allowed), the k candidates j != i of largest p(i, j), sorted by (p descending,
+ * j ascending) -- ties go to the smaller j.  exclude_edges = 1 leaves out the vertices joined to i by a resident edge: undirected,
+ * either orientation of the list counts; directed, only i -> j does (j -> i does not exclude); repeated edges and self loops
+ * change nothing.  1 <= k <= 64 (else CGE_E_ARG; so is a query id outside 1 .. n, before any device work).  A query with fewer
+ * than k admissible candidates gets out_cnt < k and 0 / 0.0 in the unused slots.  Every reported p is cge_link_prob's value for
+ * that pair, bit for bit, and the ranking is by those values: the result is a function of the inputs alone, not of the grid, the
+ * slicing of the candidates or the order of insertion.  (The kernel ranks nothing by the Gram formula: that only FILTERS, with a
+ * rounding bound that keeps every pair that could belong)
+ * Stats: "link_topk_survivors" = pairs of the last call that passed the filter and were evaluated exactly, "link_topk_queries".  */
+int cge_link_topk(cge_ctx *ctx, const int64_t *queries, int64_t Q, int64_t k, int exclude_edges, int64_t *out_j /* Q x k */,
+                  double *out_p /* Q x k */, int64_t *out_cnt /* Q */);
+
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */
 int cge_js(cge_ctx *ctx, const double *vC, const double *vB, int64_t len, const uint8_t *vI, int internal,
