@@ -1493,6 +1493,23 @@ class Context:
                                          _p(oc)))
         return oj, op, oc
 
+    def link_rank(self, i, j, exclude_edges=True):
+        """The exact filtered rank of the pairs (i[q], j[q]) (1-based ids) among the candidates of their source vertex
+        (cge_link_rank): with p* = `link_prob`'s value of the pair and the candidates c other than i and j -- and, under
+        exclude_edges, not a resident neighbour of i -- returns (greater, ties, cand, p): how many candidates have p(i, c) > p*,
+        how many have p(i, c) == p*, how many there are, and p*.  All numpy, in the caller's order; see `link_metrics`."""
+        ii, jj = _i64(_host_array(i)).ravel(), _i64(_host_array(j)).ravel()
+        if len(ii) != len(jj):
+            raise ValueError("link_rank: i and j differ in length")
+        P = len(ii)
+        g, t, cand = (np.zeros(max(P, 1), dtype=np.int64) for _ in range(3))
+        p = np.zeros(max(P, 1))
+        if P == 0:  # (no pairs: the library says so; it is handed valid pointers all the same)
+            ii = jj = np.zeros(1, dtype=np.int64)
+        self._check(self.L.cge_link_rank(self.h, _p(ii), _p(jj), C.c_int64(P), C.c_int(int(bool(exclude_edges))), _p(g), _p(t),
+                                         _p(cand), _p(p)))
+        return g[:P], t[:P], cand[:P], p[:P]
+
     def ecg_members_test(self, members=16, seed=0):
         """Testing hook (cge_ecg_members_test): the member and peel stages of `ecg` alone -- (members (K, n) each renumbered as a
         pass is, n_comm (K,), rounds (K,), modularity (K,), core (n,) bool)."""
@@ -1678,6 +1695,52 @@ def link_predict(edge_index, embedding, comm, land, queries, k, forced=4, method
         return vec, None, None, None
     q = np.arange(1, ctx.n + 1, dtype=np.int64) if queries is None else queries
     return (vec,) + ctx.link_topk(q, k, exclude_edges)
+
+
+def link_metrics(greater, ties, cand, ks=(1, 10, 50, 100)):
+    """The usual link-prediction figures from `Context.link_rank`'s counts (pure numpy, no GPU).  With the realistic rank
+    1 + greater + ties / 2 of every pair: {"mrr", "hits@k" for every k of `ks` (the share of pairs of rank <= k), "mean_rank",
+    "auc" (the mean of 1 - (greater + ties / 2) / cand over the pairs with cand > 0), "mrr_optimistic" (ranks 1 + greater),
+    "mrr_pessimistic" (ranks 1 + greater + ties)}.  A figure over no pairs is NaN."""
+    g, t, c = (np.asarray(x, dtype=np.float64).ravel() for x in (greater, ties, cand))
+    if not len(g) == len(t) == len(c):
+        raise ValueError("link_metrics: greater, ties and cand differ in length")
+
+    def mean(v):
+        return float(np.mean(v)) if len(v) else float("nan")
+
+    rank = 1.0 + g + 0.5 * t
+    out = {"mrr": mean(1.0 / rank)}
+    for k in ks:
+        out[f"hits@{int(k)}"] = mean(rank <= k)
+    out["mean_rank"] = mean(rank)
+    has = c > 0
+    out["auc"] = mean(1.0 - (g[has] + 0.5 * t[has]) / c[has])
+    out["mrr_optimistic"] = mean(1.0 / (1.0 + g))
+    out["mrr_pessimistic"] = mean(1.0 / (1.0 + g + t))
+    return out
+
+
+def link_evaluate(edge_index, embedding, comm, land, test_pairs, forced=4, method="rss", directed=False, split=False, seed=-1,
+                  auc_samples=10000, which="local", exclude_edges=True, ks=(1, 10, 50, 100), weights=None, base=-1, ctx=None):
+    """Evaluation of the fitted model on held-out pairs, beside `link_predict`: the (training) graph and the embedding go in as
+    views, `Context.link_fit` fits the model of the best alpha, `Context.link_rank` ranks `test_pairs` ((P, 2) or (2, P) with
+    P != 2; 1-based vertex ids) among the non-neighbours of their source, and `link_metrics` sums up.  Returns (vector, metrics,
+    (greater, ties, cand, p)); a directed star graph's early return leaves (vector, None, None)."""
+    ctx = ctx or default_context()
+    ctx.set_graph_view(edge_index, weights, n=int(embedding.shape[0]), base=base)
+    ctx.set_vertex_view(comm, None, base=base)
+    ctx.set_embedding_view(embedding)
+    vec, _ = ctx.link_fit(FROM_COMM, land, forced, method, directed, split, seed, auc_samples, which)
+    if len(vec) < 7:
+        return vec, None, None
+    tp = _i64(_host_array(test_pairs))
+    if tp.ndim != 2 or 2 not in tp.shape:
+        raise ValueError("link_evaluate: test_pairs is (P, 2) or (2, P)")
+    if tp.shape[1] != 2:
+        tp = tp.T
+    counts = ctx.link_rank(tp[:, 0], tp[:, 1], exclude_edges)
+    return vec, link_metrics(counts[0], counts[1], counts[2], ks), counts
 
 
 def draw_samples(ctx, seed, S, directed=False, n_sets=1):

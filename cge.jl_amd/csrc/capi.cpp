@@ -284,6 +284,13 @@ int cge_link_topk(cge_ctx *c, const int64_t *queries, int64_t Q, int64_t k, int 
     host_link_topk(c, queries, Q, k, exclude_edges, out_j, out_p, out_cnt);
     CGE_CATCH(c)
 }
+int cge_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, int64_t P, int exclude_edges, int64_t *out_greater,
+                  int64_t *out_ties, int64_t *out_cand, double *out_p) {
+    if (!c || !i || !j || !out_greater || !out_ties) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_rank(c, i, j, P, exclude_edges, out_greater, out_ties, out_cand, out_p);
+    CGE_CATCH(c)
+}
 
 // ---- helpers ----------------------------------------------------------------------------------------
 int64_t cge_idx(int64_t n, int64_t i, int64_t j) { return n * (i - 1) - (i - 1) * (i - 2) / 2 + j - i + 1; }
@@ -474,6 +481,8 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "ecg_levels")) *value = c->stat_ecg_levels;               // levels of the final hierarchy
     else if (!strcmp(key, "link_topk_survivors")) *value = c->link.stat_survivors; // of the last cge_link_topk: pairs evaluated exactly,
     else if (!strcmp(key, "link_topk_queries")) *value = c->link.stat_queries;     // its queries
+    else if (!strcmp(key, "link_rank_survivors")) *value = c->link.stat_rank_survivors; // of the last cge_link_rank: the same,
+    else if (!strcmp(key, "link_rank_queries")) *value = c->link.stat_rank_queries;     // its distinct query vertices
     else if (!strcmp(key, "cut_tie_tasks")) { // (read from the device on request: a synchronising copy)
         int v = 0;
         if (c->cut_ties.p && (hipStreamSynchronize(c->stream) != hipSuccess ||

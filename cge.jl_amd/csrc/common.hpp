@@ -284,6 +284,11 @@ struct LinkModel {
     DevBuf<unsigned long long> keys, keys_in;
     i64 nkeys = 0;
     bool keys_ready = false;
+    // per vertex the distinct excluded neighbours other than itself, derived from the keys on the first rank query that excludes edges
+    DevBuf<i32> excl;
+    bool excl_ready = false;
+    DevBuf<double> fib;      // f_in[c]^(-1 / alpha), the candidate's part of the rank filter's root; built on the first rank query
+    bool fib_ready = false;
     // cge_link_fit while its sweep runs: which best is wanted (0: no capture), and what was copied aside last
     int cap_which = 0;
     bool cap_have = false;
@@ -298,6 +303,13 @@ struct LinkModel {
     DevBuf<i64> oj, ocnt;
     DevBuf<unsigned long long> surv;
     i64 stat_survivors = 0, stat_queries = 0; // exact evaluations / queries of the last cge_link_topk
+    // cge_link_rank: the distinct queries, their pairs grouped (offsets, thresholds descending, targets, the way back), the two
+    // histograms, the results
+    DevBuf<i32> ruq, rgj;
+    DevBuf<i64> roff, rperm, rout;
+    DevBuf<double> rt;
+    DevBuf<unsigned long long> rhist;
+    i64 stat_rank_survivors = 0, stat_rank_queries = 0; // exact evaluations / distinct queries of the last cge_link_rank
 };
 
 struct cge_ctx {
@@ -1068,6 +1080,14 @@ void k_link_prob(cge_ctx *c, const i32 *pi, const i32 *pj, i64 P, double *out); 
 void k_link_keys(cge_ctx *c);                                                           // the sorted edge keys of the model
 // the top-k lists of Q queries (0-based ids, device) against every vertex: out_j (1-based) / out_p (Q x k), out_cnt (Q), device
 void k_link_topk(cge_ctx *c, const i32 *qid, i64 Q, int k, bool exclude, i64 *out_j, double *out_p, i64 *out_cnt);
+void k_link_excl(cge_ctx *c); // per vertex the distinct excluded neighbours, from the sorted keys (builds those when needed)
+// a chunk of Qu distinct queries uq (off: their Qu + 1 offsets into the grouped thresholds t) counted into the histograms G / E
+void k_link_rank(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const double *t, unsigned long long *G,
+                 unsigned long long *E, bool exclude);
+// the histograms of all Qu queries turned into greater / ties / cand, written through perm to the caller's order
+void k_link_rank_final(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const double *t, const i32 *gj, const i64 *perm,
+                       const unsigned long long *G, const unsigned long long *E, bool exclude, i64 *out_greater, i64 *out_ties,
+                       i64 *out_cand);
 // ---- host modules -----------------------------------------------------------------------------
 // landmarks_host.cpp
 void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
@@ -1089,7 +1109,7 @@ void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lco
 void host_ref_dist2_test(cge_ctx *c, const double *refs, i64 nref, double *rd2, double *mean_out);
 void host_ensure_centred(cge_ctx *c); // Xc / rnorm: the centred feature-major copy of the resident embedding (made on first demand)
 // link_host.cpp: what the cge_link_* entry points do, and the sweep's side of cge_link_fit
-static inline void link_drop(cge_ctx *c) { c->link.valid = false; c->link.keys_ready = false; }
+static inline void link_drop(cge_ctx *c) { c->link.valid = false; c->link.keys_ready = false; c->link.excl_ready = false; c->link.fib_ready = false; }
 // a sweep that cge_link_fit runs calls this when alpha has just become the best of the wanted kind: Ta / Tb (N each, the sweep's
 // numbering; old2new un-permutes a relabelled sweep) are copied aside on the stream
 void link_capture(cge_ctx *c, const double *Ta, const double *Tb, i64 N, const i32 *old2new, double alpha);
@@ -1100,6 +1120,8 @@ void host_link_model_fetch(cge_ctx *c, int *directed, double *alpha, double *hi,
 void host_link_prob(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, double *out);
 void host_link_topk(cge_ctx *c, const int64_t *queries, i64 Q, i64 k, int exclude_edges, int64_t *out_j, double *out_p,
                     int64_t *out_cnt);
+void host_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, int exclude_edges, int64_t *out_greater,
+                    int64_t *out_ties, int64_t *out_cand, double *out_p);
 // score_host.cpp
 struct cge_landmark_graph_io;
 void host_landmark_graph_test(cge_ctx *c, cge_landmark_graph_io *io);

@@ -1,5 +1,6 @@
 // kernels_link.hip -- the link model's kernels (cge_link_*, link_host.cpp): the per-vertex factors of a fitted model, the model's
-// probability of given pairs, and per query the k most probable candidates.  gfx950 only.
+// probability of given pairs, per query the k most probable candidates, and the exact rank of given pairs among their query's
+// candidates (link_rank_kernel, at the end: top-k's tiles and filter stage with thresholds known before the first tile).  gfx950 only.
 //
 //     p(i, j) = (f_out[i] * f_in[j]) * max(0, 1 - dist(i, j) / hi) ^ alpha
 //
@@ -31,6 +32,8 @@
 #define LK_MAX_SLICES 512 // the merge kernel keeps nsl / 64 <= 8 list heads per lane
 #define LK_EXTRA_DOUBLES (128 /* tau */ + 128 /* thr */ + 256 /* mask: 128 x 4 words */ + 64 /* counts: 128 ints */ + 128 /* rq */)
 #define LK_LDS_BYTES ((size_t)2 * 2 * MP_BK * MP_LD * sizeof(double) + (size_t)LK_EXTRA_DOUBLES * sizeof(double))
+// link_rank_kernel: erow, arow, asure, rq (128 doubles each) and the 128 x 4 words of the mask
+#define LR_LDS_BYTES ((size_t)2 * 2 * MP_BK * MP_LD * sizeof(double) + (size_t)(4 * 128 + 256) * sizeof(double))
 
 // dist(i, j) of the resident rows in pair_dist_kernel's arithmetic: ascending k, unfused; 0 for equal indices
 __device__ __forceinline__ double link_dist(const double *__restrict__ Xr, i64 d, i64 i, i64 j) {
@@ -162,18 +165,29 @@ __device__ __forceinline__ bool link_is_edge(const unsigned long long *__restric
 }
 
 // ---- cge_link_topk ----------------------------------------------------------------------------------------------------------------
-struct LinkTopk {
+// what the two tiled queries (top-k, rank) share: the operands of the Gram tiles, the model, the filter's constants, the edge keys
+struct LinkTiles {
     const double *Xq, *rq; i64 ldq;   // the queries, centred feature-major (dpad x ldq) and their squared norms
     const double *Xc, *rn; i64 ldn;   // the candidates: every vertex, the same form
     i64 n, Q, dpad;
-    int k, nsl;
+    int nsl;
     const i32 *qid;                    // the queries' vertex ids (Q)
     const double *Xr; i64 d;           // the rows as dist() reads them
     const double *fo, *fi, *ftile;
     double hi, alpha, einfl, dinfl;
     const unsigned long long *keys; i64 nkeys; int directed; // keys == nullptr: nothing is excluded
-    double *lp; i32 *lj, *lcnt;        // the lists: [(row tile * nsl + slice) * 128 + row][k], and their lengths
     unsigned long long *surv;          // pairs evaluated exactly (a stat)
+};
+struct LinkTopk : LinkTiles {
+    int k;
+    double *lp; i32 *lj, *lcnt;        // the lists: [(row tile * nsl + slice) * 128 + row][k], and their lengths
+};
+// cge_link_rank: the distinct queries' pairs grouped, a query's thresholds descending
+struct LinkRank : LinkTiles {
+    const i64 *off;                    // [Q + 1]: query q's pairs are off[q] .. off[q + 1] of t
+    const double *t;                   // the pairs' own probabilities (cge_link_prob's values)
+    unsigned long long *G, *E;         // per pair slot: candidates that first exceed it / that equal its run (at the run's start)
+    const double *fib;                 // f_in[c]^(-1 / alpha): the candidate's part of the filter's root
 };
 
 // The squared radius beyond which no candidate of a tile can reach tau: den = f_out[i] fmax(tile).  p's own evaluation rounds (two
@@ -196,6 +210,115 @@ __device__ __forceinline__ bool link_before(double p, i32 j, double q, i32 l) { 
 __device__ __forceinline__ void lds_sync() { // (the LDS stores of this wave have landed before the barrier: tests/test_device_asm.py)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
+}
+
+// ---- the filter stage of the tiled queries (top-k and rank): ONE copy ---------------------------------------------------------------
+// this tile's thresholds from the rows' tau and the tile's largest f_in, the rows' share of the rounding bound added
+__device__ __forceinline__ void link_filter_thresholds(const LinkTiles &A, int tid, i64 i0, i64 J, const double *tau,
+                                                       const double *rqs, double *thr) {
+    if (tid < 128) {
+        const i64 qi = i0 + tid;
+        double t = -__builtin_huge_val();
+        if (qi < A.Q) t = link_radius2(tau[tid], A.fo[A.qid[qi]] * A.ftile[J], A.hi, A.alpha, A.dinfl) + A.einfl * rqs[tid];
+        thr[tid] = t;
+    }
+}
+// the filter: acc[a][b][r] is row i0 + wr*64 + a*16 + lk + 4r, column j0 + wc*64 + b*16 + lr; a pair within its limit sets its bit
+// of the 128 x 128 mask.  The limit of a pair is  thr[row] + e r_j  (PERCAND = false: thr is this tile's squared radius of the row,
+// its share of the rounding bound added -- link_filter_thresholds), or, with the candidate's own factor in the place of the tile's
+// largest (PERCAND = true: link_rank_kernel, whose thresholds never move),
+//     (hi (1 - min(1, a_i b_c)) dinfl)^2 (1 + 1e-15) + (erow_i + e r_j),    a_i = thr[row] (link_root_row),  b_c = f_in[c]^(-1 / alpha):
+// link_radius2's expression with the root of the quotient taken as a product of a row's and a candidate's root.
+// SURE (with PERCAND): the other side of the same bound.  A pair whose Gram value proves p > the row's LARGEST threshold sets its
+// bit of mask2 as well: with a+_i = asure[row] (link_root_row_sure),  r+ = a+_i b_c + 1e-12 < 1  and
+//     g + e (r_i + r_j) < ((hi / dinfl) (1 - r+))^2 (1 - 1e-14).
+// Then the true squared distance is below the right side (g is within e (r_i + r_j) of it), dist()'s K-term sum and the quotient
+// by hi stay below hi (1 - r+) and 1 - r+ (the 1 / dinfl, at least 17 u of the quotient where the base is small; where it is not,
+// the relative margins of r+ are four orders above u), the base 1 - x is at least r+ - 1e-12 >= a+_i b_c, and a+_i b_c is the
+// root of t_max / (f_out f_in) stretched by 1e-12 in the quotient and 2e-12 (1 + 1 / alpha) in the root: the power of the base
+// (within two ulp) times the two factors (an ulp each) exceeds t_max by more than 1e-12 of it.
+template <bool PERCAND, bool SURE = false>
+__device__ __forceinline__ void link_filter_mask(const LinkTiles &A, const d4 (&acc)[4][4], i64 j0, const double *rqs,
+                                                 const double *thr, const double *erow, const double *fib, unsigned *mask, int wr,
+                                                 int wc, int lr, int lk, const double *asure = nullptr, unsigned *mask2 = nullptr) {
+    const double hsure = SURE ? A.hi / A.dinfl : 0.0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int jl = wc * 64 + b * 16 + lr;
+        const i64 j = j0 + jl;
+        const double rj = A.rn[j]; // rnorm is padded to ldn
+        const double ej = A.einfl * rj;
+        if (j < A.n) {
+            const double bc = PERCAND ? fib[j] : 0.0;
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int il = wr * 64 + a * 16 + lk + 4 * r;
+                    const double g = gram_value(rqs[il], rj, acc[a][b][r]);
+                    double lim;
+                    if (PERCAND) {
+                        const double R = A.hi * (1.0 - fmin(thr[il] * bc, 1.0)) * A.dinfl;
+                        lim = R * R * (1.0 + 1e-15) + (erow[il] + ej);
+                    } else {
+                        lim = thr[il] + ej;
+                    }
+                    bool pass = g <= lim;
+                    if (SURE) {
+                        const double rp = asure[il] * bc + 1e-12;
+                        const double Rm = hsure * (1.0 - rp);
+                        if (rp < 1.0 && g + (A.einfl * rqs[il] + ej) < Rm * Rm * (1.0 - 1e-14)) {
+                            atomicOr(&mask2[il * 4 + (jl >> 5)], 1u << (jl & 31));
+                            pass = true;
+                        }
+                    }
+                    if (pass) atomicOr(&mask[il * 4 + (jl >> 5)], 1u << (jl & 31));
+                }
+        }
+    }
+}
+// The row's part of the root r = (tau / (f_out[i] f_in[c]))^(1 / alpha) = a_i b_c of link_radius2, with its margins: the quotient
+// shrunk by 1e-12, the root by 2e-12 (1 + 1 / alpha) -- link_radius2's 1e-12 (1 + 1 / alpha) and as much again for the roundings of
+// b_c (a pow, within two ulp) and of the product, five orders of magnitude below it.  -inf: every candidate passes (tau = 0: ties at
+// 0 admit everything, whatever the distance); +inf: none does.  A product that underflows only widens the radius.
+__device__ __forceinline__ double link_root_row(double tau, double fo, double alpha) {
+    const double inf = __builtin_huge_val();
+    if (!(tau > 0.0)) return -inf;
+    if (!(fo > 0.0)) return inf; // (tau = f_out[i] ... > 0 has f_out[i] > 0)
+    const double q = (tau / fo) * (1.0 - 1e-12);
+    if (!(q < inf)) return -inf;
+    return pow(q, 1.0 / alpha) * (1.0 - 2e-12 * (1.0 + 1.0 / alpha));
+}
+// the row's part of r+ (link_filter_mask, SURE): the root of t_max / f_out[i] with the margins on the other side; +inf: nothing
+// is proven (a largest threshold of 0, a NaN)
+__device__ __forceinline__ double link_root_row_sure(double tmax, double fo, double alpha) {
+    const double inf = __builtin_huge_val();
+    if (!(tmax > 0.0) || !(fo > 0.0)) return inf;
+    const double q = (tmax / fo) * (1.0 + 1e-12);
+    if (!(q < inf)) return inf;
+    return pow(q, 1.0 / alpha) * (1.0 + 2e-12 * (1.0 + 1.0 / alpha));
+}
+// a row's survivors, two candidates per lane (j0 + lane, j0 + lane + 64): the exact value of those that are admissible -- not the
+// query itself, not a resident neighbour when edges are excluded -- and -1 for the rest; returns this lane's count of mask bits.
+// SURE: an admissible survivor whose bit of ms is set is not evaluated (the filter has proven it above every threshold): -2.
+template <bool EXP2, bool SURE = false>
+__device__ __forceinline__ int link_row_survivors(const LinkTiles &A, const uint4 mw, i64 vi, double fo, i64 j0, int lane,
+                                                  double (&pc)[2], i32 (&jc)[2], const uint4 ms = uint4{0u, 0u, 0u, 0u}) {
+    const unsigned w0 = lane < 32 ? mw.x : mw.y, w1 = lane < 32 ? mw.z : mw.w;
+    const unsigned s0 = lane < 32 ? ms.x : ms.y, s1 = lane < 32 ? ms.z : ms.w;
+    int nsurv = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const i64 j = j0 + lane + 64 * h;
+        bool on = (((h ? w1 : w0) >> (lane & 31)) & 1u) != 0u;
+        const bool sure = SURE && (((h ? s1 : s0) >> (lane & 31)) & 1u) != 0u;
+        nsurv += on && !sure ? 1 : 0;
+        on = on && j != vi;
+        if (on && A.keys) on = !link_is_edge(A.keys, A.nkeys, link_key(vi, j, A.directed));
+        pc[h] = !on ? -1.0 : sure ? -2.0 : link_p<EXP2>(A.Xr, A.d, vi, j, fo, A.fi[j], A.hi, A.alpha);
+        jc[h] = (i32)j;
+    }
+    return nsurv;
 }
 
 template <bool EXP2>
@@ -228,32 +351,9 @@ __global__ __launch_bounds__(256, 2) void link_topk_kernel(LinkTopk A) {
         d4 acc[4][4];
         gram_tile_128(A.Xq + (i64)wave * A.ldq + i0 + c2, A.Xc + (i64)wave * A.ldn + j0 + c2, A.ldq, A.ldn, nchunk, lds, acc, wave,
                       c2, wr, wc, lr, lk);
-        // this tile's thresholds from the rows' tau and the tile's largest f_in, the rows' share of the rounding bound added
-        if (tid < 128) {
-            const i64 qi = i0 + tid;
-            double t = -__builtin_huge_val();
-            if (qi < A.Q) t = link_radius2(tau[tid], A.fo[A.qid[qi]] * A.ftile[J], A.hi, A.alpha, A.dinfl) + A.einfl * rqs[tid];
-            thr[tid] = t;
-        }
+        link_filter_thresholds(A, tid, i0, J, tau, rqs, thr);
         lds_sync();
-        // ---- the filter: acc[a][b][r] is row i0 + wr*64 + a*16 + lk + 4r, column j0 + wc*64 + b*16 + lr
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int jl = wc * 64 + b * 16 + lr;
-            const i64 j = j0 + jl;
-            const double rj = A.rn[j]; // rnorm is padded to ldn
-            const double ej = A.einfl * rj;
-            if (j < A.n) {
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int il = wr * 64 + a * 16 + lk + 4 * r;
-                        const double g = gram_value(rqs[il], rj, acc[a][b][r]);
-                        if (g <= thr[il] + ej) atomicOr(&mask[il * 4 + (jl >> 5)], 1u << (jl & 31));
-                    }
-            }
-        }
+        link_filter_mask<false>(A, acc, j0, rqs, thr, nullptr, nullptr, mask, wr, wc, lr, lk);
         lds_sync();
         // ---- the survivors, row by row: wave w takes the rows w, w + 4, ...
         for (int rr = 0; rr < 32; rr++) {
@@ -262,20 +362,9 @@ __global__ __launch_bounds__(256, 2) void link_topk_kernel(LinkTopk A) {
             if ((mw.x | mw.y | mw.z | mw.w) == 0u) continue; // (wave-uniform)
             const i64 vi = A.qid[i0 + il]; // (a row beyond Q has an empty mask: its threshold is -inf)
             const double fo = A.fo[vi];
-            const unsigned w0 = lane < 32 ? mw.x : mw.y, w1 = lane < 32 ? mw.z : mw.w;
             double pc[2];
             i32 jc[2];
-            int nsurv = 0;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const i64 j = j0 + lane + 64 * h;
-                bool on = (((h ? w1 : w0) >> (lane & 31)) & 1u) != 0u;
-                nsurv += on ? 1 : 0;
-                on = on && j != vi;
-                if (on && A.keys) on = !link_is_edge(A.keys, A.nkeys, link_key(vi, j, A.directed));
-                pc[h] = on ? link_p<EXP2>(A.Xr, A.d, vi, j, fo, A.fi[j], A.hi, A.alpha) : -1.0;
-                jc[h] = (i32)j;
-            }
+            const int nsurv = link_row_survivors<EXP2>(A, mw, vi, fo, j0, lane, pc, jc);
             if (lane < 4) mask[il * 4 + lane] = 0u;
             int tot = nsurv; // the survivors of this row, a stat (added up per wave, one atomic at the end)
 #pragma unroll
@@ -425,4 +514,228 @@ void k_link_topk(cge_ctx *c, const i32 *qid, i64 Q, int k, bool exclude, i64 *ou
     ScopedKernelTimer t(c, "link_merge");
     hipLaunchKernelGGL(link_merge_kernel, dim3((unsigned)Q), dim3(64), 0, c->stream, m.lp.p, m.lj.p, m.lcnt.p, Q, k, (int)nsl, out_j,
                        out_p, out_cnt);
+}
+
+// ---- cge_link_rank ----------------------------------------------------------------------------------------------------------------
+// Per vertex the number of distinct excluded neighbours other than itself, from the sorted keys: the first of every run of equal
+// keys counts, a self loop does not; undirected keys are (min, max) and count for both ends, directed ones for the source.
+__global__ void link_excl_kernel(const unsigned long long *__restrict__ keys, i64 nkeys, int directed, i32 *__restrict__ excl) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < nkeys; e += stride) {
+        const unsigned long long key = keys[e];
+        if (e > 0 && keys[e - 1] == key) continue;
+        const i64 a = (i64)(key >> 32), b = (i64)(key & 0xffffffffull);
+        if (a == b) continue;
+        atomicAdd(&excl[a], 1);
+        if (!directed) atomicAdd(&excl[b], 1);
+    }
+}
+// the candidate's part of the rank filter's root: f_in[c]^(-1 / alpha) (a zero factor: +inf, no radius at all)
+__global__ void link_fib_kernel(const double *__restrict__ fi, i64 n, double alpha, double *__restrict__ fib) {
+    const i64 v = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n) fib[v] = pow(fi[v], -1.0 / alpha);
+}
+void k_link_fib(cge_ctx *c) {
+    LinkModel &m = c->link;
+    if (m.fib_ready) return;
+    m.fib.ensure((size_t)m.n);
+    hipLaunchKernelGGL(link_fib_kernel, dim3((unsigned)((m.n + 255) / 256)), dim3(256), 0, c->stream, m.f.p + m.n, m.n, m.alpha, m.fib.p);
+    m.fib_ready = true;
+}
+void k_link_excl(cge_ctx *c) {
+    LinkModel &m = c->link;
+    if (m.excl_ready) return;
+    k_link_keys(c);
+    m.excl.ensure((size_t)m.n);
+    HIP_CHECK(hipMemsetAsync(m.excl.p, 0, sizeof(i32) * (size_t)m.n, c->stream));
+    ScopedKernelTimer t(c, "link_excl");
+    hipLaunchKernelGGL(link_excl_kernel, dim3(grid_for(m.nkeys, 256)), dim3(256), 0, c->stream, m.keys.p, m.nkeys, m.directed,
+                       m.excl.p);
+    m.excl_ready = true;
+}
+
+// The rank of given pairs among their query's candidates.  Top-k's geometry and top-k's filter, but a row's tau is known before
+// the first tile -- the smallest probability among the query's own pairs -- so there is no list, no warm-up and no merge.  A
+// survivor (p_c, c) of row i is placed by binary search in the row's descending thresholds t[off_i ..]: with s0 the first slot
+// whose threshold is below p_c, every pair from s0 on has c above it (one add into G[off_i + s0]; an inclusive prefix sum over
+// the row gives `greater`), and the run of slots equal to p_c, if any, has c as a tie (one add at the run's first slot of E).
+// Integer atomics: the counts do not depend on the grid, the slicing or the order.
+template <bool EXP2>
+__global__ __launch_bounds__(256, 2) void link_rank_kernel(LinkRank A) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *erow = lds + (size_t)2 * 2 * MP_BK * MP_LD, *arow = erow + 128, *asure = arow + 128, *rqs = asure + 128;
+    unsigned *mask = reinterpret_cast<unsigned *>(rqs + 128);
+    unsigned *mask2 = reinterpret_cast<unsigned *>(lds); // the proven pairs of a tile: in the Gram staging, free between two tiles
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4, c2 = lane * 2;
+    const i64 It = blockIdx.x / A.nsl;
+    const int sl = (int)(blockIdx.x % A.nsl);
+    const i64 i0 = It * MP_BM, nTc = A.ldn / MP_BN, nchunk = A.dpad / MP_BK;
+    if (tid < 128) { // a row's tau is the smallest of its thresholds, the last of its group, and the first is the largest: both are
+        const i64 qi = i0 + tid; // fixed for the launch, and so are their roots
+        const double rq = A.rq[i0 + tid]; // rq is padded to ldq
+        const double inf = __builtin_huge_val();
+        double ar = inf, as = inf;
+        if (qi < A.Q) {
+            const double fo = A.fo[A.qid[qi]];
+            ar = link_root_row(A.t[A.off[qi + 1] - 1], fo, A.alpha);
+            as = link_root_row_sure(A.t[A.off[qi]], fo, A.alpha);
+        }
+        rqs[tid] = rq;
+        arow[tid] = ar;
+        asure[tid] = as;
+        erow[tid] = qi < A.Q ? A.einfl * rq : -inf; // (a row beyond Q passes nothing, whatever its Gram value)
+    }
+    for (int q = tid; q < 512; q += 256) mask[q] = 0u;
+    unsigned long long wsurv = 0;
+    lds_sync();
+    for (i64 J = sl; J < nTc; J += A.nsl) {
+        const i64 j0 = J * MP_BN;
+        d4 acc[4][4];
+        gram_tile_128(A.Xq + (i64)wave * A.ldq + i0 + c2, A.Xc + (i64)wave * A.ldn + j0 + c2, A.ldq, A.ldn, nchunk, lds, acc, wave,
+                      c2, wr, wc, lr, lk);
+        // (gram_tile_128 ends behind a barrier: every wave is done with the staging)
+        for (int q = tid; q < 512; q += 256) mask2[q] = 0u;
+        lds_sync();
+        link_filter_mask<true, true>(A, acc, j0, rqs, arow, erow, A.fib, mask, wr, wc, lr, lk, asure, mask2);
+        lds_sync();
+        // ---- the survivors, row by row: wave w takes the rows w, w + 4, ...
+        for (int rr = 0; rr < 32; rr++) {
+            const int il = wave + 4 * rr;
+            const uint4 mw = *reinterpret_cast<const uint4 *>(mask + il * 4);
+            if ((mw.x | mw.y | mw.z | mw.w) == 0u) continue; // (wave-uniform)
+            const uint4 ms = *reinterpret_cast<const uint4 *>(mask2 + il * 4);
+            const i64 vi = A.qid[i0 + il]; // (a row beyond Q has an empty mask: its erow is -inf, its asure +inf)
+            const double fo = A.fo[vi];
+            double pc[2];
+            i32 jc[2];
+            const int nsurv = link_row_survivors<EXP2, true>(A, mw, vi, fo, j0, lane, pc, jc, ms);
+            if (lane < 4) mask[il * 4 + lane] = 0u;
+            int tot = nsurv, above = (pc[0] == -2.0 ? 1 : 0) + (pc[1] == -2.0 ? 1 : 0); // evaluated exactly; proven above every threshold
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) {
+                tot += __shfl_xor(tot, s);
+                above += __shfl_xor(above, s);
+            }
+            wsurv += (unsigned long long)tot;
+            const i64 o0 = A.off[i0 + il], np = A.off[i0 + il + 1] - o0;
+            if (lane == 0 && above) atomicAdd(A.G + o0, (unsigned long long)above); // above the first slot: greater for every pair
+            const double *t = A.t + o0;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const double p = pc[h];
+                if (!(p >= 0.0)) continue; // not admissible (-1), or a NaN
+                i64 lo = 0, hi = np; // the first slot with t <= p: the slots before it are above p
+                while (lo < hi) {
+                    const i64 mid = (lo + hi) >> 1;
+                    if (t[mid] > p) lo = mid + 1;
+                    else hi = mid;
+                }
+                const i64 eq0 = lo;
+                hi = np; // the first slot with t < p, from there on
+                while (lo < hi) {
+                    const i64 mid = (lo + hi) >> 1;
+                    if (t[mid] >= p) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < np) atomicAdd(A.G + o0 + lo, 1ull);
+                if (eq0 < lo) atomicAdd(A.E + o0 + eq0, 1ull);
+            }
+        }
+        // (the next tile's staging is written behind gram_tile_128's first barrier: every wave has read its rows of mask2 by then)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the cleared masks have landed before that barrier
+    }
+    if (lane == 0 && wsurv) atomicAdd(A.surv, wsurv);
+}
+
+// One wave per distinct query: the inclusive prefix sum of its G (64 slots a round, the carry passed on) is `greater` of every
+// pair; `ties` is the E of the pair's run minus the pair's own j where that is a candidate; `cand` from the excluded-neighbour
+// counts.  Written through the permutation to the caller's order.
+__global__ __launch_bounds__(64) void link_rank_final_kernel(const i32 *__restrict__ uq, const i64 *__restrict__ off,
+                                                            const double *__restrict__ t, const i32 *__restrict__ gj,
+                                                            const i64 *__restrict__ perm, const unsigned long long *__restrict__ G,
+                                                            const unsigned long long *__restrict__ E,
+                                                            const unsigned long long *__restrict__ keys, i64 nkeys, int directed,
+                                                            const i32 *__restrict__ excl, i64 n, i64 *__restrict__ out_greater,
+                                                            i64 *__restrict__ out_ties, i64 *__restrict__ out_cand) {
+    const i64 q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const i64 vi = uq[q], o0 = off[q], np = off[q + 1] - o0;
+    const i64 nexcl = keys ? (i64)excl[vi] : 0;
+    unsigned long long carry = 0;
+    for (i64 s0 = 0; s0 < np; s0 += 64) {
+        const i64 s = s0 + lane;
+        unsigned long long g = s < np ? G[o0 + s] : 0ull;
+#pragma unroll
+        for (int w = 1; w < 64; w <<= 1) {
+            const unsigned long long up = __shfl_up(g, w);
+            if (lane >= w) g += up;
+        }
+        g += carry;
+        carry = __shfl(g, 63);
+        if (s < np) {
+            const double ts = t[o0 + s];
+            i64 lo = 0, hi = s; // the first slot of the run equal to ts (descending thresholds: the first with t <= ts)
+            while (lo < hi) {
+                const i64 mid = (lo + hi) >> 1;
+                if (t[o0 + mid] > ts) lo = mid + 1;
+                else hi = mid;
+            }
+            const i64 j = gj[o0 + s];
+            const bool j_excl = keys && link_is_edge(keys, nkeys, link_key(vi, j, directed));
+            const i64 at = perm[o0 + s];
+            out_greater[at] = (i64)g;
+            out_ties[at] = (i64)E[o0 + lo] - (j_excl ? 0 : 1);
+            out_cand[at] = n - 1 - nexcl - (j_excl ? 0 : 1);
+        }
+    }
+}
+
+void k_link_rank(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const double *t, unsigned long long *G,
+                 unsigned long long *E, bool exclude) {
+    LinkModel &m = c->link;
+    const i64 nQt = (Qu + 127) / 128, ldq = nQt * 128, nTc = c->ldn / 128;
+    // enough slices of the candidate tiles to fill the CUs twice over when the queries are few (nothing is merged per slice:
+    // no other limit than the tiles)
+    i64 nsl = (2 * (i64)device_cus() + nQt - 1) / nQt;
+    nsl = std::max<i64>(1, std::min<i64>(nsl, nTc));
+    const i64 nwg = nQt * nsl;
+    if (nwg > 0x7fffffffLL) CGE_THROW(CGE_E_ARG, "link_rank: %lld workgroups exceed a launch", (long long)nwg);
+    m.Xq.ensure((size_t)ldq * c->dpad);
+    m.rq.ensure((size_t)ldq);
+    k_link_fib(c);
+    k_gather_centre_fm(c, c->Xr.p, uq, c->gmean.p, m.Xq.p, m.rq.p, Qu, c->d, ldq, c->dpad);
+    LinkRank A{};
+    A.Xq = m.Xq.p; A.rq = m.rq.p; A.ldq = ldq;
+    A.Xc = c->Xc.p; A.rn = c->rnorm.p; A.ldn = c->ldn;
+    A.n = c->n; A.Q = Qu; A.dpad = c->dpad;
+    A.nsl = (int)nsl;
+    A.qid = uq;
+    A.Xr = c->Xr.p; A.d = c->d;
+    A.fo = m.f.p; A.fi = m.f.p + m.n; A.ftile = m.ftile.p;
+    A.hi = m.hi; A.alpha = m.alpha;
+    A.einfl = (double)(c->dpad + 16) * 2.220446049250313e-16; // (K + 16) 2^-52
+    A.dinfl = 1.0 + A.einfl;
+    A.keys = exclude ? m.keys.p : nullptr; A.nkeys = exclude ? m.nkeys : 0; A.directed = m.directed;
+    A.surv = m.surv.p;
+    A.off = off; A.t = t; A.G = G; A.E = E;
+    A.fib = m.fib.p;
+    ScopedKernelTimer tm(c, "link_rank");
+    if (m.pow_form) {
+        cge_allow_lds((const void *)link_rank_kernel<true>, LR_LDS_BYTES);
+        hipLaunchKernelGGL(link_rank_kernel<true>, dim3((unsigned)nwg), dim3(256), LR_LDS_BYTES, c->stream, A);
+    } else {
+        cge_allow_lds((const void *)link_rank_kernel<false>, LR_LDS_BYTES);
+        hipLaunchKernelGGL(link_rank_kernel<false>, dim3((unsigned)nwg), dim3(256), LR_LDS_BYTES, c->stream, A);
+    }
+}
+void k_link_rank_final(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const double *t, const i32 *gj, const i64 *perm,
+                       const unsigned long long *G, const unsigned long long *E, bool exclude, i64 *out_greater, i64 *out_ties,
+                       i64 *out_cand) {
+    LinkModel &m = c->link;
+    if (Qu > 0x7fffffffLL) CGE_THROW(CGE_E_ARG, "link_rank: %lld queries exceed a launch", (long long)Qu);
+    ScopedKernelTimer tm(c, "link_rank_final");
+    hipLaunchKernelGGL(link_rank_final_kernel, dim3((unsigned)Qu), dim3(64), 0, c->stream, uq, off, t, gj, perm, G, E,
+                       exclude ? m.keys.p : nullptr, exclude ? m.nkeys : 0, m.directed, exclude ? m.excl.p : nullptr, m.n, out_greater,
+                       out_ties, out_cand);
 }

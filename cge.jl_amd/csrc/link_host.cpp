@@ -1,8 +1,10 @@
 // link_host.cpp -- the host side of cge_link_* (include/cge_hip.h): the link model in the context, fitted by a score's own sweep
-// or supplied by the caller, and its two queries (kernels_link.hip).
+// or supplied by the caller, and its three queries (kernels_link.hip).
 #include "common.hpp"
 
+#include <algorithm>
 #include <cmath>
+#include <numeric>
 
 static void link_need_inputs(cge_ctx *c, const char *who) {
     if (!c->Xr.p || c->d <= 0 || !c->src.p || c->n <= 0 || c->m <= 0)
@@ -28,6 +30,8 @@ static void link_finish(cge_ctx *c) {
     m.ftile.ensure((size_t)nt);
     k_link_tile_max(c, m.f.p + m.n, m.n, nt, m.ftile.p);
     m.keys_ready = false;
+    m.excl_ready = false;
+    m.fib_ready = false;
     m.valid = true;
 }
 
@@ -180,5 +184,91 @@ void host_link_topk(cge_ctx *c, const int64_t *queries, i64 Q, i64 k, int exclud
     HIP_CHECK(hipMemcpy(&surv, m.surv.p, sizeof(surv), hipMemcpyDeviceToHost));
     m.stat_survivors = (i64)surv;
     m.stat_queries = Q;
+    flush_timers(c);
+}
+
+// ---- cge_link_rank -----------------------------------------------------------------------------------------------------------------
+// The pairs' own probabilities come from k_link_prob (the same kernel, hence the same bits) and are fetched: the grouping by query
+// vertex and the sort of a query's pairs by p descending are done HERE, on the host (P doubles, one synchronisation).  The distinct
+// queries go through the counting kernel in chunks of 16384, as top-k's do; one finalisation over all of them follows.
+void host_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, int exclude_edges, int64_t *out_greater,
+                    int64_t *out_ties, int64_t *out_cand, double *out_p) {
+    link_need_model(c, "link_rank");
+    link_need_inputs(c, "link_rank");
+    if (P < 1) CGE_THROW(CGE_E_ARG, "link_rank: P = %lld pairs", (long long)P);
+    LinkModel &m = c->link;
+    std::vector<i32> h((size_t)2 * P);
+    link_ids("link_rank", "i of pair", i, P, m.n, h, 0);
+    link_ids("link_rank", "j of pair", j, P, m.n, h, (size_t)P);
+    for (i64 q = 0; q < P; q++)
+        if (i[q] == j[q])
+            CGE_THROW(CGE_E_ARG, "link_rank: pair %lld is (%lld, %lld): a vertex is not its own candidate", (long long)(q + 1),
+                      (long long)i[q], (long long)j[q]);
+    hipStream_t st = c->stream;
+    const bool exclude = exclude_edges != 0;
+    // the pairs' own values
+    m.ids.ensure((size_t)2 * P);
+    m.vals.ensure((size_t)P);
+    HIP_CHECK(hipMemcpyAsync(m.ids.p, h.data(), sizeof(i32) * 2 * P, hipMemcpyHostToDevice, st));
+    k_link_prob(c, m.ids.p, m.ids.p + P, P, m.vals.p);
+    std::vector<double> p((size_t)P);
+    HIP_CHECK(hipMemcpyAsync(p.data(), m.vals.p, sizeof(double) * P, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    // grouped by query, a query's pairs by p descending (a NaN -- a non-finite embedding -- last; equal values in the caller's order)
+    std::vector<i64> perm((size_t)P);
+    std::iota(perm.begin(), perm.end(), (i64)0);
+    const i32 *hi_ = h.data();
+    std::sort(perm.begin(), perm.end(), [&](i64 a, i64 b) {
+        if (hi_[a] != hi_[b]) return hi_[a] < hi_[b];
+        const double pa = p[(size_t)a], pb = p[(size_t)b];
+        const bool na = std::isnan(pa), nb = std::isnan(pb);
+        if (na || nb) return na != nb ? nb : a < b;
+        if (pa != pb) return pa > pb;
+        return a < b;
+    });
+    std::vector<i32> uq, gj((size_t)P);
+    std::vector<i64> off;
+    std::vector<double> t((size_t)P);
+    for (i64 s = 0; s < P; s++) {
+        const i64 at = perm[(size_t)s];
+        if (s == 0 || hi_[at] != uq.back()) {
+            uq.push_back(hi_[at]);
+            off.push_back(s);
+        }
+        gj[(size_t)s] = h[(size_t)(P + at)];
+        t[(size_t)s] = p[(size_t)at];
+    }
+    off.push_back(P);
+    const i64 Qu = (i64)uq.size();
+    m.ruq.ensure((size_t)Qu);
+    m.roff.ensure((size_t)Qu + 1);
+    m.rgj.ensure((size_t)P);
+    m.rperm.ensure((size_t)P);
+    m.rt.ensure((size_t)P);
+    m.rhist.ensure((size_t)2 * P);
+    m.rout.ensure((size_t)3 * P);
+    m.surv.ensure(1);
+    HIP_CHECK(hipMemcpyAsync(m.ruq.p, uq.data(), sizeof(i32) * Qu, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.roff.p, off.data(), sizeof(i64) * (Qu + 1), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.rgj.p, gj.data(), sizeof(i32) * P, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.rperm.p, perm.data(), sizeof(i64) * P, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.rt.p, t.data(), sizeof(double) * P, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(m.rhist.p, 0, sizeof(unsigned long long) * 2 * P, st));
+    HIP_CHECK(hipMemsetAsync(m.surv.p, 0, sizeof(unsigned long long), st));
+    host_ensure_centred(c);
+    if (exclude) k_link_excl(c); // (and the sorted keys it is derived from)
+    unsigned long long *G = m.rhist.p, *E = m.rhist.p + P;
+    const i64 chunk = 16384;
+    for (i64 q0 = 0; q0 < Qu; q0 += chunk) k_link_rank(c, m.ruq.p + q0, m.roff.p + q0, std::min(chunk, Qu - q0), m.rt.p, G, E, exclude);
+    k_link_rank_final(c, m.ruq.p, m.roff.p, Qu, m.rt.p, m.rgj.p, m.rperm.p, G, E, exclude, m.rout.p, m.rout.p + P, m.rout.p + 2 * P);
+    HIP_CHECK(hipMemcpyAsync(out_greater, m.rout.p, sizeof(i64) * P, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(out_ties, m.rout.p + P, sizeof(i64) * P, hipMemcpyDeviceToHost, st));
+    if (out_cand) HIP_CHECK(hipMemcpyAsync(out_cand, m.rout.p + 2 * P, sizeof(i64) * P, hipMemcpyDeviceToHost, st));
+    unsigned long long surv = 0;
+    HIP_CHECK(hipMemcpyAsync(&surv, m.surv.p, sizeof(surv), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st)); // (the host tables above are borrowed by the copies until here)
+    if (out_p) std::copy(p.begin(), p.end(), out_p);
+    m.stat_rank_survivors = (i64)surv;
+    m.stat_rank_queries = Qu;
     flush_timers(c);
 }

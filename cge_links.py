@@ -11,8 +11,12 @@ of the best alpha and asks it for predictions:
     --queries FILE         the query vertices, one id per line (default: every vertex, in chunks)
     --pairs FILE           instead of top-k lists: the model's probability of the pairs `i j` of FILE, one per line
     --keep-edges           do not leave the query's own neighbours out (the model's nearest candidates: graph reconstruction)
+    --rank FILE            instead of top-k lists: the exact filtered rank of the held-out pairs `i j` of FILE among the candidates
+                           of i (the graph given with -g is the training graph); excludes --pairs and --queries
 
 stdout: the 7-vector line cge_cli.py prints, then one `i j p` line per prediction, ids in the edge file's own base (0 or 1).
+With --rank: one `i j p greater ties cand` line per pair (candidates of i other than j that the model puts above / level with j,
+and their number), then one `# ` line with MRR, Hits@K, mean rank and AUC (api.link_metrics).
 """
 import os
 import sys
@@ -63,6 +67,28 @@ def link_args(argv):
     return {"which": which, "topk": topk, "queries": queries, "pairs": pairs, "exclude": "--keep-edges" not in argv}
 
 
+def rank_args(argv):
+    """--rank FILE beside `link_args`' flags: the file's name, or None.  Needs no GPU."""
+    argv = list(argv)
+    if "--rank" not in argv:
+        return None
+    i = argv.index("--rank")
+    if i + 1 >= len(argv) or argv[i + 1].startswith("-"):
+        raise LinkArgError("--rank needs a value")
+    fn = argv[i + 1]
+    for other in ("--pairs", "--queries"):
+        if other in argv:
+            raise LinkArgError(f"--rank and {other} exclude each other")
+    if not os.path.isfile(fn):
+        raise LinkArgError(f"--rank: {fn} is not a file")
+    return fn
+
+
+def metrics_line(mt):
+    """The summary line of --rank."""
+    return "# " + " ".join(f"{k}={julia_float(float(v))}" for k, v in mt.items())
+
+
 def read_ids(path, columns, base, n):
     """The ids of a query / pair file as 1-based int64 (rows, columns), checked against 1..n; `base` is the edge file's."""
     from cge.jl_amd import api
@@ -83,6 +109,7 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
         la = link_args(argv)
+        rank = rank_args(argv)
     except LinkArgError as e:
         print(f"cge_links: {e}", file=sys.stderr)
         return 1
@@ -103,6 +130,17 @@ def main(argv=None):
         if len(vec) < 7:  # a directed star graph: the reference's early return leaves no model
             return 0
         out = sys.stdout
+        if rank is not None:
+            ij = read_ids(rank, 2, base, n)
+            if len(ij) == 0:
+                return 0
+            if (ij[:, 0] == ij[:, 1]).any():
+                raise LinkArgError(f"{rank}: a pair (i, i): a vertex is not its own candidate")
+            g, t, cand, p = ctx.link_rank(ij[:, 0], ij[:, 1], la["exclude"])
+            for q, (i, j) in enumerate(ij):
+                out.write(f"{i - 1 + base} {j - 1 + base} {julia_float(float(p[q]))} {g[q]} {t[q]} {cand[q]}\n")
+            out.write(metrics_line(api.link_metrics(g, t, cand)) + "\n")
+            return 0
         if la["pairs"] is not None:
             ij = read_ids(la["pairs"], 2, base, n)
             p = ctx.link_prob(ij[:, 0], ij[:, 1]) if len(ij) else np.zeros(0)

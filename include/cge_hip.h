@@ -415,6 +415,23 @@ int cge_link_prob(cge_ctx *ctx, const int64_t *i, const int64_t *j, int64_t P, d
  * Stats: "link_topk_survivors" = pairs of the last call that passed the filter and were evaluated exactly, "link_topk_queries".  */
 int cge_link_topk(cge_ctx *ctx, const int64_t *queries, int64_t Q, int64_t k, int exclude_edges, int64_t *out_j /* Q x k */,
                   double *out_p /* Q x k */, int64_t *out_cnt /* Q */);
+/* The exact filtered rank of P >= 1 given pairs (i[q], j[q]), 1-based ids, among the candidates of their source vertex -- what MRR,
+ * Hits@K, mean rank and per-pair AUC are made of.  With p* = cge_link_prob's value of (i, j), bit for bit, and the admissible
+ * candidates A = {c : c != i, c != j, and -- exclude_edges = 1 -- c not joined to i by a resident edge (cge_link_topk's rules:
+ * undirected either orientation, directed i -> c alone; repeated edges and self loops change nothing)}:
+ *     out_greater[q] = #{c in A : p(i, c) > p*},   out_ties[q] = #{c in A : p(i, c) == p*},   out_cand[q] = |A|,   out_p[q] = p*.
+ * j itself is never removed from the question, even when (i, j) is a resident edge (a held-out edge is not resident; a resident
+ * one is ranked against the non-neighbours).  Every p is cge_link_prob's value and the comparisons are made on those values (the
+ * Gram formula only filters, as in cge_link_topk), so the result is a function of the inputs alone: not of the grid, the slicing,
+ * the order of the pairs or the other pairs of the call.  Pairs may repeat.  Consistent with cge_link_topk: if j is admissible
+ * there and sits at position r (0-based) of query i's list, then greater <= r <= greater + ties under the same exclude_edges.
+ * CGE_E_ARG, before any device work: no link model; P < 1; an id outside 1 .. n; i[q] == j[q] (a vertex is not its own candidate);
+ * under collectives or sharding.  A non-finite embedding is unspecified, as for cge_link_topk.  DESIGN.md section 4.12.
+ * Stats: "link_rank_survivors" = (query, candidate) pairs of the last call evaluated exactly, "link_rank_queries" = its distinct
+ * query vertices.                                                                                                                */
+int cge_link_rank(cge_ctx *ctx, const int64_t *i, const int64_t *j, int64_t P, int exclude_edges,
+                  int64_t *out_greater /* P */, int64_t *out_ties /* P */, int64_t *out_cand /* P, may be NULL */,
+                  double *out_p /* P, may be NULL */);
 
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */
