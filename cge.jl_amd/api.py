@@ -1510,6 +1510,44 @@ class Context:
                                          _p(cand), _p(p)))
         return g[:P], t[:P], cand[:P], p[:P]
 
+    def _link_sample_call(self, call, cap, want_p):
+        """`call(cap, out_i, out_j, out_p, n_edges)` -> rc, with cap = None grown once to the count the library reports."""
+        first = cap is None
+        cap = 2 * int(self.m) + 16 if first else int(cap)
+        while True:
+            k = max(cap, 1)
+            oi, oj = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64)
+            op = np.zeros(k) if want_p else None
+            ne = C.c_int64(-1)
+            rc = call(C.c_int64(cap), _p(oi) if cap > 0 else None, _p(oj) if cap > 0 else None,
+                      _p(op) if want_p and cap > 0 else None, C.byref(ne))
+            if first and rc == -7 and ne.value > cap:  # CGE_E_ARG that names the count
+                cap, first = ne.value, False
+                continue
+            self._check(rc)
+            break
+        e = ne.value if cap > 0 else 0
+        return oi[:e], oj[:e], (op[:e] if want_p else None), ne.value
+
+    def link_sample(self, seed=0, stream=0, cap=None, want_p=False):
+        """One draw of the random graph the resident model is (cge_link_sample): the pairs with u(i, j) < p(i, j), u the counter
+        stream's uniform of the pair -- i < j of an undirected model, every ordered i != j of a directed one.  Returns (i, j, p or
+        None, n_edges): 1-based ids sorted by (i, j).  cap = 0 only counts; cap = None starts from twice the resident edge count
+        and asks once more with the reported count; a given cap that is too small raises (the count is in the message)."""
+        return self._link_sample_call(
+            lambda cap_, oi, oj, op, ne: self.L.cge_link_sample(self.h, C.c_int64(int(seed)), C.c_int64(int(stream)), cap_, oi, oj, op,
+                                                                ne), cap, want_p)
+
+    def link_sample_test(self, U, directed_layout=True, cap=None, want_p=False):
+        """Testing hook (cge_link_sample_test): `link_sample` with u(a, b) = U[a, b] ((n, n), 0-based, n <= 1024;
+        directed_layout = False reads the upper triangle alone) in the place of the counter stream."""
+        Um = np.ascontiguousarray(_f64(_host_array(U)))
+        if Um.shape != (self.n, self.n):
+            raise ValueError(f"link_sample_test: U is {Um.shape}, not ({self.n}, {self.n})")
+        return self._link_sample_call(
+            lambda cap_, oi, oj, op, ne: self.L.cge_link_sample_test(self.h, _p(Um), C.c_int(int(bool(directed_layout))), cap_, oi, oj,
+                                                                     op, ne), cap, want_p)
+
     def ecg_members_test(self, members=16, seed=0):
         """Testing hook (cge_ecg_members_test): the member and peel stages of `ecg` alone -- (members (K, n) each renumbered as a
         pass is, n_comm (K,), rounds (K,), modularity (K,), core (n,) bool)."""
@@ -1741,6 +1779,22 @@ def link_evaluate(edge_index, embedding, comm, land, test_pairs, forced=4, metho
         tp = tp.T
     counts = ctx.link_rank(tp[:, 0], tp[:, 1], exclude_edges)
     return vec, link_metrics(counts[0], counts[1], counts[2], ks), counts
+
+
+def link_sample(edge_index, embedding, comm, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000,
+                which="local", sample_seed=0, samples=1, want_p=False, weights=None, base=-1, ctx=None):
+    """Random graphs from the fitted model, beside `link_predict`: the graph and the embedding go in as views, `Context.link_fit`
+    fits the model of the best alpha once, and `samples` draws follow on the streams 0 .. samples - 1 of `sample_seed`
+    (`Context.link_sample`).  Returns (vector, [(i, j, p or None, n_edges), ...]); a directed star graph's early return leaves
+    (vector, None)."""
+    ctx = ctx or default_context()
+    ctx.set_graph_view(edge_index, weights, n=int(embedding.shape[0]), base=base)
+    ctx.set_vertex_view(comm, None, base=base)
+    ctx.set_embedding_view(embedding)
+    vec, _ = ctx.link_fit(FROM_COMM, land, forced, method, directed, split, seed, auc_samples, which)
+    if len(vec) < 7:
+        return vec, None
+    return vec, [ctx.link_sample(sample_seed, r, None, want_p) for r in range(int(samples))]
 
 
 def draw_samples(ctx, seed, S, directed=False, n_sets=1):

@@ -291,6 +291,22 @@ int cge_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, int64_t P, int
     host_link_rank(c, i, j, P, exclude_edges, out_greater, out_ties, out_cand, out_p);
     CGE_CATCH(c)
 }
+int cge_link_sample(cge_ctx *c, int64_t seed, int64_t stream, int64_t cap, int64_t *out_i, int64_t *out_j, double *out_p,
+                    int64_t *n_edges) {
+    if (!c || !n_edges) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_sample(c, seed, stream, cap, out_i, out_j, out_p, n_edges, nullptr, 0);
+    CGE_CATCH(c)
+}
+// testing hook (include/cge_hip_testing.h): the same launch with the uniforms read from a caller's matrix
+int cge_link_sample_test(void *ctx, const double *U, int directed_layout, int64_t cap, int64_t *out_i, int64_t *out_j, double *out_p,
+                         int64_t *n_edges) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !U || !n_edges) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_sample(c, 0, 0, cap, out_i, out_j, out_p, n_edges, U, directed_layout != 0);
+    CGE_CATCH(c)
+}
 
 // ---- helpers ----------------------------------------------------------------------------------------
 int64_t cge_idx(int64_t n, int64_t i, int64_t j) { return n * (i - 1) - (i - 1) * (i - 2) / 2 + j - i + 1; }
@@ -483,6 +499,9 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "link_topk_queries")) *value = c->link.stat_queries;     // its queries
     else if (!strcmp(key, "link_rank_survivors")) *value = c->link.stat_rank_survivors; // of the last cge_link_rank: the same,
     else if (!strcmp(key, "link_rank_queries")) *value = c->link.stat_rank_queries;     // its distinct query vertices
+    else if (!strcmp(key, "link_sample_edges")) *value = c->link.stat_sample_edges;         // of the last cge_link_sample: its edges,
+    else if (!strcmp(key, "link_sample_survivors")) *value = c->link.stat_sample_survivors; // the pairs evaluated exactly,
+    else if (!strcmp(key, "link_sample_tiles")) *value = c->link.stat_sample_tiles;         // the tiles walked
     else if (!strcmp(key, "cut_tie_tasks")) { // (read from the device on request: a synchronising copy)
         int v = 0;
         if (c->cut_ties.p && (hipStreamSynchronize(c->stream) != hipSuccess ||

@@ -310,6 +310,13 @@ struct LinkModel {
     DevBuf<double> rt;
     DevBuf<unsigned long long> rhist;
     i64 stat_rank_survivors = 0, stat_rank_queries = 0; // exact evaluations / distinct queries of the last cge_link_rank
+    // cge_link_sample: log2 of the factors (the filter's tables; built on the first draw), the edges' keys as appended and sorted,
+    // the two counters, the ids on their way out
+    DevBuf<double> lf;
+    bool lf_ready = false;
+    DevBuf<unsigned long long> skeys_in, skeys, scnt;
+    DevBuf<i64> sout;
+    i64 stat_sample_edges = 0, stat_sample_survivors = 0, stat_sample_tiles = 0; // of the last cge_link_sample
 };
 
 struct cge_ctx {
@@ -1088,6 +1095,13 @@ void k_link_rank(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const double
 void k_link_rank_final(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const double *t, const i32 *gj, const i64 *perm,
                        const unsigned long long *G, const unsigned long long *E, bool exclude, i64 *out_greater, i64 *out_ties,
                        i64 *out_cand);
+// one draw of the model's random graph: the keys (a << 32 | b, 0-based) of the pairs with u < p appended to keys[cap] in no order,
+// cnt[0] += their number (beyond cap: counted, not stored), cnt[1] += the pairs evaluated exactly; U != nullptr: the uniforms are
+// read from that n x n matrix (the testing hook).  Returns the number of tiles walked
+i64 k_link_sample(cge_ctx *c, i64 seed, i64 stream_id, unsigned long long *keys, i64 cap, unsigned long long *cnt, const double *U,
+                  int ulay);
+void k_link_sample_finish(cge_ctx *c, const unsigned long long *keys_in, unsigned long long *keys, i64 ne, i32 *pi, i32 *pj, i64 *oi,
+                          i64 *oj);
 // ---- host modules -----------------------------------------------------------------------------
 // landmarks_host.cpp
 void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
@@ -1109,7 +1123,9 @@ void host_diameter_bounds_test(cge_ctx *c, const i64 *v2l, i64 N, const i64 *lco
 void host_ref_dist2_test(cge_ctx *c, const double *refs, i64 nref, double *rd2, double *mean_out);
 void host_ensure_centred(cge_ctx *c); // Xc / rnorm: the centred feature-major copy of the resident embedding (made on first demand)
 // link_host.cpp: what the cge_link_* entry points do, and the sweep's side of cge_link_fit
-static inline void link_drop(cge_ctx *c) { c->link.valid = false; c->link.keys_ready = false; c->link.excl_ready = false; c->link.fib_ready = false; }
+static inline void link_drop(cge_ctx *c) {
+    c->link.valid = false; c->link.keys_ready = false; c->link.excl_ready = false; c->link.fib_ready = false; c->link.lf_ready = false;
+}
 // a sweep that cge_link_fit runs calls this when alpha has just become the best of the wanted kind: Ta / Tb (N each, the sweep's
 // numbering; old2new un-permutes a relabelled sweep) are copied aside on the stream
 void link_capture(cge_ctx *c, const double *Ta, const double *Tb, i64 N, const i32 *old2new, double alpha);
@@ -1122,6 +1138,9 @@ void host_link_topk(cge_ctx *c, const int64_t *queries, i64 Q, i64 k, int exclud
                     int64_t *out_cnt);
 void host_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, int exclude_edges, int64_t *out_greater,
                     int64_t *out_ties, int64_t *out_cand, double *out_p);
+// U != nullptr: cge_link_sample_test (n x n host doubles in the place of the counter stream)
+void host_link_sample(cge_ctx *c, i64 seed, i64 stream_id, i64 cap, int64_t *out_i, int64_t *out_j, double *out_p, int64_t *n_edges,
+                      const double *U, int directed_layout);
 // score_host.cpp
 struct cge_landmark_graph_io;
 void host_landmark_graph_test(cge_ctx *c, cge_landmark_graph_io *io);

@@ -279,22 +279,7 @@ void k_packed_gd(cge_ctx *c, const double *emb, const double *diag, i64 N, i64 d
 //
 // MFMA operand maps (cdna_hip_programming.md §3, f64 note): A lane l -> A[row l&15][k l>>4],
 // B lane l -> B[k l>>4][col l&15]; C/D lane l, reg r -> row (l>>4) + 4r, col l&15.
-__host__ __device__ __forceinline__ void tile_from_linear(i64 t, i64 nS, i64 &SI, i64 &I, i64 &J) {
-    // Linear order: super-blocks (SI, SJ >= SI) row-major; inside a super-block tiles row-major.
-    const i64 per = (i64)MP_SB * MP_SB;
-    const i64 sb = t / per, loc = t - sb * per;
-    // row SI of the upper triangle: off(SI) = SI*nS - SI*(SI-1)/2 <= sb < off(SI+1)
-    const double b = 2.0 * (double)nS + 1.0;
-    i64 si = (i64)((b - sqrt(b * b - 8.0 * (double)sb)) * 0.5);
-    if (si < 0) si = 0;
-    if (si > nS - 1) si = nS - 1;
-    while (si > 0 && si * nS - si * (si - 1) / 2 > sb) si--;
-    while (si + 1 < nS && (si + 1) * nS - (si + 1) * si / 2 <= sb) si++;
-    const i64 SJ = si + (sb - (si * nS - si * (si - 1) / 2));
-    SI = si;
-    I = si * MP_SB + loc / MP_SB;
-    J = SJ * MP_SB + loc % MP_SB;
-}
+// (tile_from_linear, the super-block order of the upper tiles: mfma_tile.hpp -- the link model's sampler walks the same list)
 
 // workgroup reduction of (best, i, j) -> recs[blockIdx.x]: value max, ties -> smallest (i,j)
 __device__ __forceinline__ void reduce_best(double best, i64 best_i, i64 best_j, double *lds, MaxRec *recs) {

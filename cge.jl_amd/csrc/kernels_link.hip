@@ -1,6 +1,7 @@
 // kernels_link.hip -- the link model's kernels (cge_link_*, link_host.cpp): the per-vertex factors of a fitted model, the model's
 // probability of given pairs, per query the k most probable candidates, and the exact rank of given pairs among their query's
-// candidates (link_rank_kernel, at the end: top-k's tiles and filter stage with thresholds known before the first tile).  gfx950 only.
+// candidates (link_rank_kernel: top-k's tiles and filter stage with thresholds known before the first tile), and draws of the random
+// graph the model is (link_sample_kernel, at the end: max_pair_kernel's walk of all pair tiles, a filter of its own).  gfx950 only.
 //
 //     p(i, j) = (f_out[i] * f_in[j]) * max(0, 1 - dist(i, j) / hi) ^ alpha
 //
@@ -738,4 +739,240 @@ void k_link_rank_final(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const 
     hipLaunchKernelGGL(link_rank_final_kernel, dim3((unsigned)Qu), dim3(64), 0, c->stream, uq, off, t, gj, perm, G, E,
                        exclude ? m.keys.p : nullptr, exclude ? m.nkeys : 0, m.directed, exclude ? m.excl.p : nullptr, m.n, out_greater,
                        out_ties, out_cand);
+}
+
+// ---- cge_link_sample --------------------------------------------------------------------------------------------------------------
+// One draw of the random graph the model IS: every pair is an edge when u(i, j) < p(i, j), u the counter stream's uniform of the
+// pair (which = 5), p link_p's value.  max_pair_kernel's geometry -- a strided walk of the upper 128 x 128 tiles in super-block
+// order (directed: of all tiles) on the centred feature-major operands -- and top-k's two stages: the tile's epilogue FILTERS, a
+// wave per row evaluates the survivors exactly and appends the edges' keys (a << 32 | b) behind one atomic per row.  The keys are
+// sorted afterwards, so the result does not depend on the grid or on the order of the appends.
+//
+// The filter rejects a pair only when it has proven u >= p.  u is a multiple of 2^-53 (or the hook's value); with
+// ff = fl(f_out[i] f_in[j]) and the power pw of the computed base b = fl(1 - x), x = fl(dist / hi), p = fl(ff pw):
+//   stage 1   pw <= 1 (b <= 1, either form of the power), so p <= ff: a pair with u >= ff (1 + 1e-12) is no edge.  In a fitted
+//             model of a sparse graph ff is of the order of the edge density: whole waves stop here.
+//   stage 2   in the log2 domain, with hardware f32 root and logarithm.  glo = max(0, g - e (r_i + r_j)) is a lower bound of the
+//             squared distance (e = (K + 16) 2^-52, the bound top-k filters by), q = glo / hi^2 in fp64 (two roundings),
+//                 xf = sqrt_f32((float)q) (1 - 2^-20):  the conversion (2^-24 of q, 2^-25 of the root), the root (an ulp, 2^-23) and
+//             the product (2^-24) stay below 2^-22, the rest of the 2^-20 is beyond dist()'s own (K / 2 + 3) 2^-53 (a K-term sum,
+//             a root, a quotient), so xf <= x whatever the rounding did;
+//                 B = fl32(fl32(max(0, 1 - xf)) + 2^-22) >= max(0, b):  the two f32 additions round by at most 2^-25 + 2^-24;
+//             B > 0 also where the base is clamped (hi below the diameter: p = 0 <= any bound) and where q overflows f32 (x > 1);
+//                 p <= ff B^alpha (1 + 6 u):  the power within two ulp, two products;
+//                 log2 p <= lf_out[i] + lf_in[j] + alpha log2 B + 2^-49, the tables log2 f in fp64 (below 2^-42 each, as are the
+//             three fp64 operations of the sum).  log2_f32 is within an ulp of a result below 64 in magnitude (B >= 2^-22,
+//             u >= 2^-53): 2^-18, taken as 2^-16, once for u and alpha times for B; (float)u is at most u (1 + 2^-24), 2^-23 in
+//             the logarithm.  Together below (1 + alpha) 2^-16 + 2^-22;
+//                 slack = (1 + alpha) 2^-14
+//             is four times that.  A pair is rejected when log2_f32((float)u) >= lf_out[i] + lf_in[j] + alpha log2_f32(B) + slack.
+//             The slack widens the bound on p by (1 + alpha) 4.2e-5 of it, and the f32 steps by about alpha 1.4e-6 / b: survivors,
+//             never a wrong answer.  A zero factor: ff = 0, stage 1 rejects (u >= 0 = p).  u = 0, or anything below 2^-100 (the
+//             stream gives no such value but 0; the hook might): stage 2 is not asked, the f32 logarithm of such a value is not
+//             covered by the above.  p >= 1: u < 1 <= p <= ff, and log2 u < 0 < the right side.  A NaN on the right side passes.
+struct LinkSample {
+    const double *Xc, *rn; i64 ldn, n, dpad; // the centred feature-major operand and the squared norms
+    const double *Xr; i64 d;                 // the rows as dist() reads them
+    const double *fo, *fi, *lfo, *lfi;       // the factors and their log2
+    double hi, alpha, einfl, inv_hi2, slack;
+    int directed;
+    unsigned long long h2;                   // the counter stream after its rounds of seed and stream
+    const double *U; int ulay;               // the hook: u(a, b) = U[a n + b] (ulay = 0: U[min n + max])
+    unsigned long long *keys; i64 cap;       // the edges' keys; beyond cap they are counted and not stored
+    unsigned long long *cnt;                 // [0] edges, [1] pairs evaluated exactly
+};
+#define LS_LDS_BYTES ((size_t)2 * 2 * MP_BK * MP_LD * sizeof(double) + (size_t)(4 * 128 + 256) * sizeof(double))
+
+// the last two rounds of cge_ctr_rand(seed, stream, a, b, 5), from the row's key (the first three: link_row_key)
+__device__ __forceinline__ unsigned long long link_row_key(unsigned long long h2, i64 a) {
+    return cge_sm64(h2 ^ ((unsigned long long)a * 0x2545f4914f6cdd1dULL + 2));
+}
+template <bool UMAT>
+__device__ __forceinline__ double link_uniform(const LinkSample &A, unsigned long long rowkey, i64 a, i64 b) {
+    if (UMAT) return A.U[(A.ulay || a < b) ? a * A.n + b : b * A.n + a];
+    const unsigned long long h = cge_sm64(rowkey ^ ((unsigned long long)b * 0x9e6c63d0676a9a99ULL + 3));
+    return (double)(cge_sm64(h ^ 9ULL) >> 11) * 0x1p-53;
+}
+
+template <bool EXP2, bool UMAT>
+__global__ __launch_bounds__(256, 2) void link_sample_kernel(LinkSample A) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *rqs = lds + (size_t)2 * 2 * MP_BK * MP_LD, *fos = rqs + 128, *lfs = fos + 128;
+    unsigned long long *rkey = reinterpret_cast<unsigned long long *>(lfs + 128);
+    unsigned *mask = reinterpret_cast<unsigned *>(rkey + 128);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4, c2 = lane * 2;
+    const i64 nT = A.ldn / MP_BM, nS = (nT + MP_SB - 1) / MP_SB, nchunk = A.dpad / MP_BK;
+    const i64 per = (i64)MP_SB * MP_SB;
+    const i64 total = (A.directed ? nS * nS : nS * (nS + 1) / 2) * per;
+    const double inf = __builtin_huge_val();
+    for (int q = tid; q < 512; q += 256) mask[q] = 0u;
+    unsigned long long wsurv = 0;
+    lds_sync();
+    for (i64 t = blockIdx.x; t < total; t += gridDim.x) {
+        i64 SI = 0, I, J;
+        if (A.directed) {
+            const i64 sb = t / per, loc = t - sb * per;
+            I = (sb / nS) * MP_SB + loc / MP_SB;
+            J = (sb % nS) * MP_SB + loc % MP_SB;
+        } else {
+            tile_from_linear(t, nS, SI, I, J);
+        }
+        if (I >= nT || J >= nT || (!A.directed && J < I)) continue; // uniform per workgroup
+        const i64 i0 = I * MP_BM, j0 = J * MP_BN;
+        d4 acc[4][4];
+        gram_tile_128(A.Xc + (i64)wave * A.ldn + i0 + c2, A.Xc + (i64)wave * A.ldn + j0 + c2, A.ldn, A.ldn, nchunk, lds, acc, wave, c2,
+                      wr, wc, lr, lk);
+        // (gram_tile_128 ends behind a barrier, and every wave was done with the previous tile's rows before its first)
+        if (tid < 128) {
+            const i64 i = i0 + tid;
+            const bool in = i < A.n;
+            rqs[tid] = A.rn[i]; // rnorm is padded to ldn
+            fos[tid] = in ? A.fo[i] : 0.0;
+            lfs[tid] = in ? A.lfo[i] : -inf;
+            rkey[tid] = link_row_key(A.h2, i);
+        }
+        lds_sync();
+        // ---- the filter: acc[a][b][r] is row i0 + wr*64 + a*16 + lk + 4r, column j0 + wc*64 + b*16 + lr
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int jl = wc * 64 + b * 16 + lr;
+            const i64 j = j0 + jl;
+            const double rj = A.rn[j];
+            if (j < A.n) {
+                const double fij = A.fi[j], lfj = A.lfi[j];
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int il = wr * 64 + a * 16 + lk + 4 * r;
+                        const i64 i = i0 + il;
+                        if (!(A.directed ? (i != j && i < A.n) : i < j)) continue;
+                        const double u = link_uniform<UMAT>(A, rkey[il], i, j);
+                        if (!(u < (fos[il] * fij) * (1.0 + 1e-12))) continue; // stage 1
+                        bool pass = true;
+                        if (u >= 0x1p-100) { // stage 2
+                            const double rs = rqs[il] + rj;
+                            const double glo = fmax(gram_value(rqs[il], rj, acc[a][b][r]) - A.einfl * rs, 0.0);
+                            const float xf = __builtin_amdgcn_sqrtf((float)(glo * A.inv_hi2)) * 0.99999904632568359375f; // 1 - 2^-20
+                            const float B = fmaxf(1.0f - xf, 0.0f) + 0x1p-22f;
+                            const double rhs = (lfs[il] + lfj) + A.alpha * (double)__builtin_amdgcn_logf(B) + A.slack;
+                            pass = !((double)__builtin_amdgcn_logf((float)u) >= rhs);
+                        }
+                        if (pass) atomicOr(&mask[il * 4 + (jl >> 5)], 1u << (jl & 31));
+                    }
+            }
+        }
+        lds_sync();
+        // ---- the survivors, row by row: wave w takes the rows w, w + 4, ...; lane l the candidates j0 + l and j0 + l + 64
+        for (int rr = 0; rr < 32; rr++) {
+            const int il = wave + 4 * rr;
+            const uint4 mw = *reinterpret_cast<const uint4 *>(mask + il * 4);
+            if ((mw.x | mw.y | mw.z | mw.w) == 0u) continue; // (wave-uniform)
+            const i64 vi = i0 + il;
+            const double fo = fos[il];
+            const unsigned long long rk = rkey[il];
+            if (lane < 4) mask[il * 4 + lane] = 0u;
+            wsurv += (unsigned long long)(__popc(mw.x) + __popc(mw.y) + __popc(mw.z) + __popc(mw.w));
+            const unsigned w0 = lane < 32 ? mw.x : mw.y, w1 = lane < 32 ? mw.z : mw.w;
+            bool edge[2];
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const i64 j = j0 + lane + 64 * h;
+                edge[h] = false;
+                if (((h ? w1 : w0) >> (lane & 31)) & 1u) {
+                    const double p = link_p<EXP2>(A.Xr, A.d, vi, j, fo, A.fi[j], A.hi, A.alpha);
+                    edge[h] = link_uniform<UMAT>(A, rk, vi, j) < p;
+                }
+            }
+            const unsigned long long b0 = __ballot(edge[0]), b1 = __ballot(edge[1]);
+            const int n0 = __popcll(b0), n1 = __popcll(b1);
+            if (n0 + n1 == 0) continue;
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(A.cnt, (unsigned long long)(n0 + n1));
+            at = __shfl(at, 0);
+            const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const i64 pos = (i64)at + (h ? n0 + __popcll(b1 & below) : __popcll(b0 & below));
+                if (edge[h] && pos < A.cap)
+                    A.keys[pos] = ((unsigned long long)(unsigned)vi << 32) | (unsigned long long)(unsigned)(j0 + lane + 64 * h);
+            }
+        }
+        // (the next tile's rows are written behind gram_tile_128's barriers: every wave has read its rows of the mask by then)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the cleared masks have landed before that barrier
+    }
+    if (lane == 0 && wsurv) atomicAdd(A.cnt + 1, wsurv);
+}
+
+// the sorted keys as 0-based int32 pairs (k_link_prob's operands) and 1-based int64 ids (the caller's)
+__global__ void link_sample_unpack_kernel(const unsigned long long *__restrict__ keys, i64 ne, i32 *__restrict__ pi, i32 *__restrict__ pj,
+                                          i64 *__restrict__ oi, i64 *__restrict__ oj) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += stride) {
+        const unsigned long long key = keys[e];
+        const i32 a = (i32)(key >> 32), b = (i32)(key & 0xffffffffull);
+        pi[e] = a; pj[e] = b;
+        oi[e] = (i64)a + 1; oj[e] = (i64)b + 1;
+    }
+}
+__global__ void link_log2_kernel(const double *__restrict__ f, i64 cnt, double *__restrict__ lf) {
+    const i64 v = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < cnt) lf[v] = log2(f[v]);
+}
+void k_link_log_factors(cge_ctx *c) {
+    LinkModel &m = c->link;
+    if (m.lf_ready) return;
+    m.lf.ensure((size_t)2 * m.n);
+    hipLaunchKernelGGL(link_log2_kernel, dim3((unsigned)((2 * m.n + 255) / 256)), dim3(256), 0, c->stream, m.f.p, 2 * m.n, m.lf.p);
+    m.lf_ready = true;
+}
+
+i64 k_link_sample(cge_ctx *c, i64 seed, i64 stream_id, unsigned long long *keys, i64 cap, unsigned long long *cnt, const double *U,
+                  int ulay) {
+    LinkModel &m = c->link;
+    k_link_log_factors(c);
+    const i64 nT = c->ldn / MP_BM;
+    const i64 tiles = m.directed ? nT * nT : nT * (nT + 1) / 2;
+    LinkSample A{};
+    A.Xc = c->Xc.p; A.rn = c->rnorm.p; A.ldn = c->ldn; A.n = c->n; A.dpad = c->dpad;
+    A.Xr = c->Xr.p; A.d = c->d;
+    A.fo = m.f.p; A.fi = m.f.p + m.n; A.lfo = m.lf.p; A.lfi = m.lf.p + m.n;
+    A.hi = m.hi; A.alpha = m.alpha;
+    A.einfl = (double)(c->dpad + 16) * 2.220446049250313e-16; // (K + 16) 2^-52
+    A.inv_hi2 = 1.0 / (m.hi * m.hi);
+    A.slack = (1.0 + m.alpha) * 0x1p-14;
+    A.directed = m.directed;
+    A.h2 = cge_sm64(cge_sm64((uint64_t)seed ^ 0x6a09e667f3bcc909ULL) ^ ((uint64_t)stream_id * 0xd1342543de82ef95ULL + 1));
+    A.U = U; A.ulay = ulay;
+    A.keys = keys; A.cap = cap; A.cnt = cnt;
+    const dim3 grid((unsigned)std::max<i64>(1, std::min<i64>(tiles, 2 * (i64)device_cus())));
+    ScopedKernelTimer t(c, "link_sample");
+#define LS_LAUNCH(E, UM)                                                                                                          \
+    do {                                                                                                                           \
+        cge_allow_lds((const void *)link_sample_kernel<E, UM>, LS_LDS_BYTES);                                                      \
+        hipLaunchKernelGGL((link_sample_kernel<E, UM>), grid, dim3(256), LS_LDS_BYTES, c->stream, A);                              \
+    } while (0)
+    if (U) {
+        if (m.pow_form) LS_LAUNCH(true, true);
+        else LS_LAUNCH(false, true);
+    } else {
+        if (m.pow_form) LS_LAUNCH(true, false);
+        else LS_LAUNCH(false, false);
+    }
+#undef LS_LAUNCH
+    return tiles;
+}
+// the stored keys sorted and taken apart: pi / pj (0-based, for k_link_prob), oi / oj (1-based)
+void k_link_sample_finish(cge_ctx *c, const unsigned long long *keys_in, unsigned long long *keys, i64 ne, i32 *pi, i32 *pj, i64 *oi,
+                          i64 *oj) {
+    if (ne <= 0) return;
+    {
+        ScopedKernelTimer t(c, "link_sample_sort");
+        size_t bytes = 0;
+        HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, keys_in, keys, (size_t)ne, 0u, 64u, c->stream));
+        c->sort_tmp.ensure(bytes);
+        HIP_CHECK(rocprim::radix_sort_keys(c->sort_tmp.p, bytes, keys_in, keys, (size_t)ne, 0u, 64u, c->stream));
+    }
+    hipLaunchKernelGGL(link_sample_unpack_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c->stream, keys, ne, pi, pj, oi, oj);
 }

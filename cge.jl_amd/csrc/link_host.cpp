@@ -1,5 +1,5 @@
 // link_host.cpp -- the host side of cge_link_* (include/cge_hip.h): the link model in the context, fitted by a score's own sweep
-// or supplied by the caller, and its three queries (kernels_link.hip).
+// or supplied by the caller, its three queries and its draws (kernels_link.hip).
 #include "common.hpp"
 
 #include <algorithm>
@@ -270,5 +270,58 @@ void host_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, int e
     if (out_p) std::copy(p.begin(), p.end(), out_p);
     m.stat_rank_survivors = (i64)surv;
     m.stat_rank_queries = Qu;
+    flush_timers(c);
+}
+
+// ---- cge_link_sample ---------------------------------------------------------------------------------------------------------------
+// One launch appends the keys of the sampled pairs and counts them; the count is fetched (one synchronisation) and decides: beyond
+// cap nothing more is done.  Otherwise the keys are sorted, taken apart, and -- when wanted -- given to k_link_prob (the same
+// kernel as cge_link_prob, hence the same bits).
+void host_link_sample(cge_ctx *c, i64 seed, i64 stream_id, i64 cap, int64_t *out_i, int64_t *out_j, double *out_p, int64_t *n_edges,
+                      const double *U, int directed_layout) {
+    const char *who = U ? "link_sample_test" : "link_sample";
+    link_need_model(c, who);
+    link_need_inputs(c, who);
+    if (cap < 0) CGE_THROW(CGE_E_ARG, "%s: cap = %lld", who, (long long)cap);
+    if (cap > 0 && (!out_i || !out_j)) CGE_THROW(CGE_E_ARG, "%s: cap = %lld without out_i / out_j", who, (long long)cap);
+    LinkModel &m = c->link;
+    if (U && m.n > 1024) CGE_THROW(CGE_E_ARG, "%s: n = %lld is beyond the hook's 1024 vertices", who, (long long)m.n);
+    hipStream_t st = c->stream;
+    host_ensure_centred(c);
+    m.scnt.ensure(2);
+    m.skeys_in.ensure((size_t)std::max<i64>(cap, 1));
+    HIP_CHECK(hipMemsetAsync(m.scnt.p, 0, 2 * sizeof(unsigned long long), st));
+    DevBuf<double> dU;
+    if (U) {
+        dU.ensure((size_t)m.n * m.n);
+        HIP_CHECK(hipMemcpyAsync(dU.p, U, sizeof(double) * m.n * m.n, hipMemcpyHostToDevice, st));
+    }
+    const i64 tiles = k_link_sample(c, seed, stream_id, m.skeys_in.p, cap, m.scnt.p, U ? dU.p : nullptr, directed_layout);
+    unsigned long long cnt[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(cnt, m.scnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const i64 ne = (i64)cnt[0];
+    *n_edges = ne;
+    m.stat_sample_edges = ne;
+    m.stat_sample_survivors = (i64)cnt[1];
+    m.stat_sample_tiles = tiles;
+    if (cap > 0 && ne > cap) {
+        flush_timers(c);
+        CGE_THROW(CGE_E_ARG, "%s: the sample has n_edges = %lld, cap = %lld is too small", who, (long long)ne, (long long)cap);
+    }
+    if (cap > 0 && ne > 0) {
+        m.skeys.ensure((size_t)ne);
+        m.ids.ensure((size_t)2 * ne);
+        m.sout.ensure((size_t)2 * ne);
+        k_link_sample_finish(c, m.skeys_in.p, m.skeys.p, ne, m.ids.p, m.ids.p + ne, m.sout.p, m.sout.p + ne);
+        HIP_CHECK(hipMemcpyAsync(out_i, m.sout.p, sizeof(i64) * ne, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(out_j, m.sout.p + ne, sizeof(i64) * ne, hipMemcpyDeviceToHost, st));
+        if (out_p) {
+            m.vals.ensure((size_t)ne);
+            k_link_prob(c, m.ids.p, m.ids.p + ne, ne, m.vals.p);
+            HIP_CHECK(hipMemcpyAsync(out_p, m.vals.p, sizeof(double) * ne, hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
     flush_timers(c);
 }

@@ -14,6 +14,24 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #define MP_LD (MP_BM + 16) // LDS row stride in doubles: (2*LD) % 64 == 32 => the 2 k-rows of a half-wave hit disjoint banks
 #define MP_SB 32           // super-block edge in tiles
 
+// The upper tiles J >= I of one operand in the order max_pair_kernel (kernels_dist.hip) and the link model's sampler
+// (kernels_link.hip) walk them: 32 x 32 tiles share two 4 MiB row panels.
+__host__ __device__ __forceinline__ void tile_from_linear(i64 t, i64 nS, i64 &SI, i64 &I, i64 &J) {
+    // Linear order: super-blocks (SI, SJ >= SI) row-major; inside a super-block tiles row-major.
+    const i64 per = (i64)MP_SB * MP_SB;
+    const i64 sb = t / per, loc = t - sb * per;
+    // row SI of the upper triangle: off(SI) = SI*nS - SI*(SI-1)/2 <= sb < off(SI+1)
+    const double b = 2.0 * (double)nS + 1.0;
+    i64 si = (i64)((b - sqrt(b * b - 8.0 * (double)sb)) * 0.5);
+    if (si < 0) si = 0;
+    if (si > nS - 1) si = nS - 1;
+    while (si > 0 && si * nS - si * (si - 1) / 2 > sb) si--;
+    while (si + 1 < nS && (si + 1) * nS - (si + 1) * si / 2 <= sb) si++;
+    const i64 SJ = si + (sb - (si * nS - si * (si - 1) / 2));
+    SI = si;
+    I = si * MP_SB + loc / MP_SB;
+    J = SJ * MP_SB + loc % MP_SB;
+}
 
 // The Gram value of a pair from the squared norms of its centred rows and their dot product: g = fl(fl(r_i + r_j) - 2 <x_i, x_j>).
 // The arg-max kernels (1), (3) and the near-tie kernel (3b) of kernels_dist.hip all rank pairs by THIS expression: the near-tie

@@ -13,6 +13,9 @@ of the best alpha and asks it for predictions:
     --keep-edges           do not leave the query's own neighbours out (the model's nearest candidates: graph reconstruction)
     --rank FILE            instead of top-k lists: the exact filtered rank of the held-out pairs `i j` of FILE among the candidates
                            of i (the graph given with -g is the training graph); excludes --pairs and --queries
+    --sample FILE          instead of top-k lists: one random graph drawn from the model (every pair an edge with its probability),
+                           written to FILE as `i j` rows sorted by (i, j); excludes --rank, --pairs and --queries
+    --sample-seed S        the seed of that draw (default 0)
 
 stdout: the 7-vector line cge_cli.py prints, then one `i j p` line per prediction, ids in the edge file's own base (0 or 1).
 With --rank: one `i j p greater ties cand` line per pair (candidates of i other than j that the model puts above / level with j,
@@ -35,7 +38,8 @@ class LinkArgError(Exception):
 
 
 def link_args(argv):
-    """The flags of this script beside cge_cli.py's: {"which", "topk", "queries", "pairs", "exclude"}.  Needs no GPU."""
+    """The flags of this script beside cge_cli.py's: {"which", "topk", "queries", "pairs", "exclude"}, and with --sample FILE also
+    {"sample", "sample_seed"}.  Needs no GPU."""
     argv = list(argv)
 
     def value(flag):
@@ -64,7 +68,22 @@ def link_args(argv):
             raise LinkArgError(f"{flag}: {fn} is not a file")
     if which == "local" and "--samples-local" in argv and int(value("--samples-local")) < 1:
         raise LinkArgError("--which local needs --samples-local >= 1")
-    return {"which": which, "topk": topk, "queries": queries, "pairs": pairs, "exclude": "--keep-edges" not in argv}
+    out = {"which": which, "topk": topk, "queries": queries, "pairs": pairs, "exclude": "--keep-edges" not in argv}
+    if "--sample" in argv:  # (the keys "sample" / "sample_seed" are there only with the flag)
+        out["sample"] = value("--sample")
+        if out["sample"] is None:
+            raise LinkArgError("--sample needs a value")
+        for other in ("--rank", "--pairs", "--queries"):
+            if other in argv:
+                raise LinkArgError(f"--sample and {other} exclude each other")
+        seed = value("--sample-seed")
+        try:
+            out["sample_seed"] = 0 if seed is None else int(seed)
+        except ValueError:
+            raise LinkArgError(f"--sample-seed takes a number, not {seed}") from None
+    elif "--sample-seed" in argv:
+        raise LinkArgError("--sample-seed goes with --sample")
+    return out
 
 
 def rank_args(argv):
@@ -130,6 +149,11 @@ def main(argv=None):
         if len(vec) < 7:  # a directed star graph: the reference's early return leaves no model
             return 0
         out = sys.stdout
+        if la.get("sample") is not None:
+            si, sj, _, _ = ctx.link_sample(la["sample_seed"], 0)
+            with open(la["sample"], "w") as f:
+                f.write("".join(f"{i - 1 + base} {j - 1 + base}\n" for i, j in zip(si.tolist(), sj.tolist())))
+            return 0
         if rank is not None:
             ij = read_ids(rank, 2, base, n)
             if len(ij) == 0:

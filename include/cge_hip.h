@@ -432,6 +432,21 @@ int cge_link_topk(cge_ctx *ctx, const int64_t *queries, int64_t Q, int64_t k, in
 int cge_link_rank(cge_ctx *ctx, const int64_t *i, const int64_t *j, int64_t P, int exclude_edges,
                   int64_t *out_greater /* P */, int64_t *out_ties /* P */, int64_t *out_cand /* P, may be NULL */,
                   double *out_p /* P, may be NULL */);
+/* One draw of the random graph the model IS: every pair is an edge independently with probability p(i, j).  The sampled set is
+ *     {(i, j) : u(i, j) < p(i, j)},   u(a, b) = (cge_ctr_rand(seed, stream, a, b, 5) >> 11) * 2^-53   (a, b the 0-based ids),
+ * with p cge_link_prob's value, bit for bit (a p >= 1 is always an edge), over the pairs i < j of an undirected model and over all
+ * ordered pairs i != j of a directed one ((i, j) and (j, i) are independent draws).  No self loops; the resident edges play no
+ * part.  cge_ctr_rand is the sampler's counter stream (splitmix64 rounds over seed, stream, a, b, which; which = 5 is this call's).
+ * Output: 1-based ids, rows sorted by (i, j) ascending, out_p[e] the pair's p, *n_edges the size of the set.  The result is a
+ * function of (model, embedding, seed, stream) alone: not of the grid, the slicing or the order of the appends.
+ * cap = 0 (the arrays may be NULL) only counts.  A set larger than cap > 0 is CGE_E_ARG with *n_edges set (and named in the
+ * message) and the arrays unspecified; the context stays usable and the same call with a sufficient cap gives the set.
+ * CGE_E_ARG, before any device work: no link model; cap < 0; a NULL n_edges; cap > 0 with a NULL out_i / out_j; under collectives
+ * or sharding.  A non-finite embedding is unspecified, as for cge_link_topk.  DESIGN.md section 4.13.
+ * Stats: "link_sample_edges", "link_sample_survivors" = pairs of the last call that passed the filter and were evaluated exactly,
+ * "link_sample_tiles".                                                                                                            */
+int cge_link_sample(cge_ctx *ctx, int64_t seed, int64_t stream, int64_t cap, int64_t *out_i /* cap */, int64_t *out_j /* cap */,
+                    double *out_p /* cap, may be NULL */, int64_t *n_edges);
 
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */

@@ -459,6 +459,12 @@ int cge_resident_graph_test(void *ctx, cge_resident_graph *out);
  * go with it; core_out[v] = 1 where v is in the 2-core.  The stats "ecg_groups", "ecg_member_rounds", "ecg_peel_rounds" are set */
 int cge_ecg_members_test(void *ctx, int64_t members, int64_t seed, int64_t *members_out, int64_t *n_comm, int64_t *rounds,
                          double *modularity, int32_t *core_out);
+/* needs the GPU: cge_link_sample's launch with the uniform of a pair read from a caller-supplied n x n row-major matrix (n <= 1024)
+ * in the place of the counter stream, so that a test can put every pair on its threshold at once: u(a, b) = U[a n + b] (0-based;
+ * directed_layout = 0 reads U[min(a, b) n + max(a, b)], the upper triangle alone).  Everything else -- filter, exact evaluation,
+ * sort, outputs, capacity rules, stats -- is cge_link_sample's */
+int cge_link_sample_test(void *ctx, const double *U, int directed_layout, int64_t cap, int64_t *out_i, int64_t *out_j, double *out_p,
+                         int64_t *n_edges);
 #ifdef __cplusplus
 }
 #endif
