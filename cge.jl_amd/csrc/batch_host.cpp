@@ -242,7 +242,7 @@ static void score_batch_impl(cge_ctx *c, const cge_score_args *a, const cge_embe
         if (view_check(views + k, c->n, msg) != CGE_OK) CGE_THROW(CGE_E_ARG, "%s: embedding %lld: %s", who, (long long)k, msg.c_str());
         if (views[k].on_device) check_device_pointer(c, (std::string(who) + ": embedding " + std::to_string(k)).c_str(), views[k].data);
     }
-    const int cus = device_cus();
+    const int cus = device_cus(c);
     // the members that can take the batched sweep (landmark mode; undirected: the fused fit, directed: the persistent fit of >= 256
     // landmarks); the sweep decides the rest
     // (one member, or a member whose fit takes more than half the chip, shares nothing: it is scored as cge_score scores it)

@@ -468,6 +468,20 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     // packed directed sweep
     if (!strcmp(key, "fit_dir_tiles")) { c->opt_test_fit_dir_tiles = value != 0; return CGE_OK; }
     if (!strcmp(key, "exact_resident_limit") && value >= 0) { c->opt_test_resident_limit = (double)value; return CGE_OK; }
+    // the CU count every launch shape of this context is sized by (0: the device's own).  It only shrinks: the persistent fits are
+    // co-resident because G <= the device's CUs
+    if (!strcmp(key, "test_device_cus") && value >= 0) {
+        int real = 0;
+        try {
+            HIP_CHECK(hipSetDevice(c->device));
+            real = device_cus(c, true);
+        } catch (const CgeError &e) {
+            return e.code;
+        }
+        if (value > real) return CGE_E_ARG;
+        c->opt_test_cus = (int)value;
+        return CGE_OK;
+    }
     return CGE_E_ARG;
 }
 int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {

@@ -429,6 +429,7 @@ struct cge_ctx {
     int opt_exact_packed_directed = 0;
     int opt_test_fit_dir_tiles = 0;     // testing: a resident directed launch-per-iteration fit goes by the tile pair (kernels_fitp.hip)
     double opt_test_resident_limit = 0; // testing: replaces the 200e9 bytes of the resident form's guard (0: the default)
+    int opt_test_cus = 0;               // testing: the CU count device_cus(c) reports, 1 .. the device's own (0: the device's own)
     i64 stat_exact_packed = 0;          // the last sweep ran packed
     i64 stat_exact_matrix_bytes = 0;    // O(N^2) device bytes the last exact sweep required
     bool sweep_used_fp_P = false;       // the running sweep fitted an alpha by one launch pair per iteration (fp_P)
@@ -977,10 +978,12 @@ struct FlowGeometry {
     int Nt; i64 NT; int G, NW, NSB;
     bool fused() const { return NSB == 1; } // what the fused and the shared instances exist for: one quarter block per workgroup
 };
-int device_cus(); // the CU count of the current device
+// the CU count of the current device as this context's launch shapes see it: the testing knob test_device_cus, which only shrinks
+// it, else (and with `own`) the device's own
+int device_cus(const cge_ctx *c, bool own = false);
 bool flow_geometry(i64 N, int cus, FlowGeometry *g); // no device needed; false (g untouched): the persistent form does not apply
-bool flow_geometry(i64 N, FlowGeometry *g);          // on device_cus()
-inline bool flow_fused_applies(i64 N) { FlowGeometry g; return flow_geometry(N, &g) && g.fused(); }
+bool flow_geometry(const cge_ctx *c, i64 N, FlowGeometry *g); // on device_cus(c)
+inline bool flow_fused_applies(const cge_ctx *c, i64 N) { FlowGeometry g; return flow_geometry(c, N, &g) && g.fused(); }
 // whether cge_score_batch shares the fit of a member of N landmarks: N >= 256 and fused; directed also G <= cus / 2
 bool flow_batch_member(i64 N, int cus, bool directed, FlowGeometry *g);
 // The ONE layout of a problem's hand-off slots, as offsets in doubles from the region's start: 32 doubles of sync words, the T ring

@@ -593,7 +593,8 @@ void k_fit_sym_dir_step(cge_ctx *c, const double *GD, const double *Tin, const d
 // flow_geometry, the place of their hand-off slots from flow_slots / flow_place, and are checked, armed and launched by
 // FlowLaunch.  What differs between the four paths is what is left in their wrappers below: the kernel instance, its arguments,
 // and the staging of T_0 for the directed fits.
-int device_cus() {
+int device_cus(const cge_ctx *c, bool own) {
+    if (!own && c->opt_test_cus > 0) return c->opt_test_cus;
     int dev = 0, cus = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -613,7 +614,7 @@ bool flow_geometry(i64 N, int cus, FlowGeometry *g) {
     *g = FlowGeometry{Nt, NT, G, NW, 4 * Nt <= G ? 1 : 2};
     return true;
 }
-bool flow_geometry(i64 N, FlowGeometry *g) { return flow_geometry(N, device_cus(), g); }
+bool flow_geometry(const cge_ctx *c, i64 N, FlowGeometry *g) { return flow_geometry(N, device_cus(c), g); }
 // (hand_off / hand_off_directed also refuse G > max_G = cus / 2, whichever kind: the undirected predicate, and with it
 // cge_batch_pack_test, does not -- an asymmetry kept as it was)
 bool flow_batch_member(i64 N, int cus, bool directed, FlowGeometry *g) {
@@ -667,7 +668,7 @@ struct FlowLaunch {
 // where the hand-off slots of fit_flow_kernel for N vertices live and how they are armed (the buffer is made if need be)
 bool k_fit_flow_arm_region(cge_ctx *c, i64 N, i64 Tld, uint4 **ptr, i64 *n16, unsigned *word) {
     FlowGeometry g;
-    if (!flow_geometry(N, &g) || Tld < (i64)g.Nt * 64) return false;
+    if (!flow_geometry(c, N, &g) || Tld < (i64)g.Nt * 64) return false;
     const FlowSlots s = flow_slots(g.Nt, Tld, false);
     if (s.doubles % 2) return false; // (16-byte units)
     c->fp_flow.ensure((size_t)s.doubles);
@@ -687,7 +688,7 @@ bool k_fit_flow_enqueue(cge_ctx *c, const double *GD, i64 N, const double *T0, d
         fz.want = (ff->partial ? 1 : 0) | (ff->auc_part ? 2 : 0);
     }
     FlowGeometry g;
-    if (!flow_geometry(N, &g) || Tld < (i64)g.Nt * 64) return false;
+    if (!flow_geometry(c, N, &g) || Tld < (i64)g.Nt * 64) return false;
     if (fused && !g.fused()) return false; // (callers ask flow_fused_applies first)
     const void *fn;
 #define FLOW_PICK(F, B) (g.NW == 8 ? (const void *)fit_flow_kernel<1, 8, F, B> : (const void *)fit_flow_kernel<1, 4, F, B>)
@@ -718,10 +719,10 @@ bool k_fit_flow_multi_fits(int NW, bool directed) { return FlowLaunch::fits(flow
 // the test that the grid is resident (one workgroup per CU), and the problems' slot regions back to back in `flow`, which also
 // gets room for `stage` x Tld doubles per problem behind them.  Returns the slots' doubles in all; *grid = the sum of the G.
 template <class Tab>
-static i64 flow_multi_place(Tab &tab, bool directed, int stage, DevBuf<double> &flow, int *grid) {
+static i64 flow_multi_place(const cge_ctx *c, Tab &tab, bool directed, int stage, DevBuf<double> &flow, int *grid) {
     const char *kind = directed ? "directed " : "";
     if (tab.n < 1 || tab.n > CGE_BATCH_MAX) CGE_THROW(CGE_E_ASSERT, "%sfit batch of %d problems", kind, tab.n);
-    const int cus = device_cus();
+    const int cus = device_cus(c);
     i64 tot = 0, extra = 0;
     int wg = 0;
     for (int i = 0; i < tab.n; i++) {
@@ -743,7 +744,7 @@ static i64 flow_multi_place(Tab &tab, bool directed, int stage, DevBuf<double> &
 }
 void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, double delta, DevBuf<double> &flow) {
     int grid = 0;
-    const i64 tot = flow_multi_place(tab, false, 0, flow, &grid);
+    const i64 tot = flow_multi_place(c, tab, false, 0, flow, &grid);
     FlowLaunch L(c, flow_multi_fn(NW, false), NW);
     L.arm(flow.p, tot); // every slot armed
     void *args[] = {&tab, &eps, &delta, &L.max_iters, &L.ticks, &L.naps};
@@ -753,7 +754,7 @@ void k_fit_flow_multi(cge_ctx *c, cge_flow_multi &tab, int NW, double eps, doubl
 // here from the problem's Tin / Tout, which the launch updates on success only
 void k_fit_flow_dir_multi(cge_ctx *c, cge_flow_dir_multi &tab, int NW, double eps0, double f0, double delta, DevBuf<double> &flow) {
     int grid = 0;
-    const i64 tot = flow_multi_place(tab, true, 2, flow, &grid);
+    const i64 tot = flow_multi_place(c, tab, true, 2, flow, &grid);
     hipStream_t st = c->stream;
     FlowLaunch L(c, flow_multi_fn(NW, true), NW);
     L.arm(flow.p, tot); // every slot armed
@@ -778,7 +779,7 @@ bool k_fit_persistent_dir(cge_ctx *c, const double *GD, i64 N, double *Tin, doub
                           const double *deg_out, double eps0, double f0, double delta, i64 *iters, int *dev_flags, bool *enqueued_only) {
     if (enqueued_only) *enqueued_only = false;
     FlowGeometry g;
-    if (!flow_geometry(N, &g)) return false; // (the caller iterates with one launch pair per iteration)
+    if (!flow_geometry(c, N, &g)) return false; // (the caller iterates with one launch pair per iteration)
     const void *fn = g.NW == 8 ? (g.NSB == 1 ? (const void *)fit_flow_dir_kernel<8, 1> : (const void *)fit_flow_dir_kernel<8, 2>)
                                : (g.NSB == 1 ? (const void *)fit_flow_dir_kernel<4, 1> : (const void *)fit_flow_dir_kernel<4, 2>);
     if (!FlowLaunch::fits(fn, g.NW)) return false;

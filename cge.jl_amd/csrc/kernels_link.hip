@@ -477,7 +477,7 @@ void k_link_topk(cge_ctx *c, const i32 *qid, i64 Q, int k, bool exclude, i64 *ou
     LinkModel &m = c->link;
     const i64 nQt = (Q + 127) / 128, ldq = nQt * 128, nTc = c->ldn / 128;
     // enough slices of the candidate tiles to fill the CUs twice over when the queries are few
-    i64 nsl = (2 * (i64)device_cus() + nQt - 1) / nQt;
+    i64 nsl = (2 * (i64)device_cus(c) + nQt - 1) / nQt;
     nsl = std::max<i64>(1, std::min<i64>(std::min<i64>(nsl, nTc), LK_MAX_SLICES));
     const i64 nwg = nQt * nsl;
     if (nwg > 0x7fffffffLL) CGE_THROW(CGE_E_ARG, "link_topk: %lld workgroups exceed a launch", (long long)nwg);
@@ -698,7 +698,7 @@ void k_link_rank(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const double
     const i64 nQt = (Qu + 127) / 128, ldq = nQt * 128, nTc = c->ldn / 128;
     // enough slices of the candidate tiles to fill the CUs twice over when the queries are few (nothing is merged per slice:
     // no other limit than the tiles)
-    i64 nsl = (2 * (i64)device_cus() + nQt - 1) / nQt;
+    i64 nsl = (2 * (i64)device_cus(c) + nQt - 1) / nQt;
     nsl = std::max<i64>(1, std::min<i64>(nsl, nTc));
     const i64 nwg = nQt * nsl;
     if (nwg > 0x7fffffffLL) CGE_THROW(CGE_E_ARG, "link_rank: %lld workgroups exceed a launch", (long long)nwg);
@@ -946,7 +946,7 @@ i64 k_link_sample(cge_ctx *c, i64 seed, i64 stream_id, unsigned long long *keys,
     A.h2 = cge_sm64(cge_sm64((uint64_t)seed ^ 0x6a09e667f3bcc909ULL) ^ ((uint64_t)stream_id * 0xd1342543de82ef95ULL + 1));
     A.U = U; A.ulay = ulay;
     A.keys = keys; A.cap = cap; A.cnt = cnt;
-    const dim3 grid((unsigned)std::max<i64>(1, std::min<i64>(tiles, 2 * (i64)device_cus())));
+    const dim3 grid((unsigned)std::max<i64>(1, std::min<i64>(tiles, 2 * (i64)device_cus(c))));
     ScopedKernelTimer t(c, "link_sample");
 #define LS_LAUNCH(E, UM)                                                                                                          \
     do {                                                                                                                           \

@@ -481,7 +481,7 @@ void host_fit_test(cge_ctx *c, cge_fit_problem *probs, int n, int directed, int 
     const bool multi = form == 5 || form == 6;
     FlowGeometry geo[CGE_BATCH_MAX];
     int sumG = 0;
-    const int cus = device_cus();
+    const int cus = device_cus(c);
     for (int i = 0; i < n; i++) {
         const cge_fit_problem &p = probs[i];
         if (p.N <= 0 || !p.D || !p.w || !p.T0 || !p.T) CGE_THROW(CGE_E_ARG, "fit_test: empty problem");
@@ -627,7 +627,7 @@ void host_fused_chain_test(cge_ctx *c, cge_fused_chain_problem *probs, int n, do
         CGE_THROW(CGE_E_ARG, "fused_chain_test: the fused fit makes its power matrix from the stored logarithm (option pow_exp2)");
     if (c->fit_persistent_broken) CGE_THROW(CGE_E_ARG, "fused_chain_test: this context gave the persistent fit up");
     FlowGeometry geo[CGE_BATCH_MAX];
-    const int cus = device_cus();
+    const int cus = device_cus(c);
     int sumG = 0;
     for (int i = 0; i < n; i++) {
         const cge_fused_chain_problem &p = probs[i];
@@ -782,7 +782,7 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
         if (!(io->eps > 0.0) || !(io->delta >= 0.0)) CGE_THROW(CGE_E_ARG, "local_score_test: eps > 0 and delta >= 0");
         if (!c->opt_pow_exp2)
             CGE_THROW(CGE_E_ARG, "local_score_test: form 4 makes its power matrix from the stored logarithm (option pow_exp2)");
-        if (!flow_fused_applies(N))
+        if (!flow_fused_applies(c, N))
             CGE_THROW(CGE_E_ARG, "local_score_test: the geometry of the fused persistent fit declines N = %lld", (long long)N);
     }
     // ---- Draw --------------------------------------------------------------------------------------------------------------------

@@ -155,7 +155,7 @@ void layout_tables(cge_ctx *c, const i32 *hcomm, i64 N, i64 C, int directed, boo
     const bool tiles_req = landmarks && !directed && c->opt_fit_fused && c->opt_exact_relabel && N >= 256 &&
                            C >= 2 && !c->opt_test_bvec_plain;
     const bool fuse_req = tiles_req && !c->fit_persistent_broken && c->opt_fit_persistent != 1 &&
-                          c->opt_pow_exp2 && flow_fused_applies(N);
+                          c->opt_pow_exp2 && flow_fused_applies(c, N);
     const bool blocks = blocks_req || tiles_req;
     bool blocks_ok = blocks, pieces_ok = true;
     // the sweep's small tables travel together: one pinned staging buffer, one copy and one scatter kernel per flush instead of a
@@ -430,7 +430,7 @@ static bool hand_off(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, const Sam
                      std::vector<cge_fit_fused> &h_epi) {
     const i64 N = G.N, vlen = packed_len(G.C);
     FlowGeometry geo;
-    if (!flow_batch_member(N, device_cus(), false, &geo) || geo.G > h.max_G || !k_fit_flow_multi_fits(geo.NW, false)) return false;
+    if (!flow_batch_member(N, device_cus(c), false, &geo) || geo.G > h.max_G || !k_fit_flow_multi_fits(geo.NW, false)) return false;
     hipStream_t st = c->stream;
     k_pow_prepare(c, c->sw_D.p, N, true, true);
     h.Lh.swap(c->sw_Lh); h.Ll.swap(c->sw_Ll);
@@ -465,7 +465,7 @@ static bool hand_off_directed(cge_ctx *c, SweepHandoff &h, const ScoreGraph &G, 
     // (a directed member shares the launch on the geometry of its own k_fit_persistent_dir launch: one quarter block per
     // workgroup, which the multi kernel exists for, and no more than half the chip, so that a launch holds two members at least)
     FlowGeometry geo;
-    if (!flow_batch_member(N, device_cus(), true, &geo) || geo.G > h.max_G || !k_fit_flow_multi_fits(geo.NW, true)) return false;
+    if (!flow_batch_member(N, device_cus(c), true, &geo) || geo.G > h.max_G || !k_fit_flow_multi_fits(geo.NW, true)) return false;
     hipStream_t st = c->stream;
     k_pow_prepare(c, c->sw_D.p, N, false); // what the sweep does once before its first alpha
     h.logs = c->pow_logs_N == N && !c->pow_logs_upper; // (k_pow_matrix's own rule for whole rows)

@@ -433,7 +433,14 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *                                 3 rotated by one: every choice gives the same bits;
  *   "test_pcent_form"             v: the form of the bf16-split bound pass of the pruned diameter: 0 (default) by the number of
  *                                 reference points, 1 the streaming form always, 2 the register-resident form wherever the
- *                                 pass applies (d <= 128): both forms give the same bits.                                        */
+ *                                 pass applies (d <= 128): both forms give the same bits;
+ *   "test_device_cus"             v: v in 1 .. the device's CU count replaces the CU count that sizes this context's launches: the
+ *                                 geometry of the persistent fits (G, NW, NSB and whether they apply), the packing of
+ *                                 cge_score_batch (max_G = v / 2), the slices of cge_link_topk / cge_link_rank and the grid of
+ *                                 cge_link_sample; 0 (default): the device's own.  It only shrinks (above the device's count:
+ *                                 CGE_E_ARG), since a persistent fit needs its G <= v workgroups co-resident.  This one does change
+ *                                 which form runs -- on purpose: the forms of chips with fewer CUs run on a large one.  The link
+ *                                 queries' results do not depend on it; a fit's agree to rounding.                                */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
 /* needs the GPU: the resident row-major fp64 matrix as this rank holds it (all n rows; under shard_rows its own rows, in
  * local order, with their global 0-based ids in ids_out, which may be NULL otherwise).  *rows and *d are set first; a capacity

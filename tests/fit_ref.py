@@ -256,6 +256,23 @@ DIRECTED_CHAINS = {
     1985: (204, _BIG_D), 2816: (205, _BIG_D), 2817: (206, _BIG_D), 4032: (207, _BIG_D), 4097: (208, _BIG_D),
 }
 DESIGNATED_DIRECTED = 130
+# the sizes that tests/test_gpu_small_chip_fits.py adds for the geometries of chips with 2 .. 64 CUs (130 takes its chain above):
+# long chains while a long-double step is cheap, two short ones (one from ones, one from the previous end) beyond
+SMALL_CHIP_UNDIRECTED_CHAINS = {
+    7: (111, [(1.0, "conv", "ones"), (1.25, _rec(2), "prev"), (4.0, 3, "ones")]),
+    64: (112, [(4.0, "conv", "ones"), (4.25, _rec(3), "prev"), (2.0, 2, "ones")]),
+    256: (113, [(4.0, "conv", "ones"), (4.25, _rec(3), "prev"), (4.5, _rec(13), "prev"), (2.0, 2, "ones")]),
+    513: (114, [(10.0, "conv", "ones"), (9.75, _rec(4), "prev"), (1.0, _rec(3), "ones")]),
+    960: (115, [(1.0, 3, "ones"), (1.0, _rec(4), "prev")]), 961: (116, [(1.0, 4, "ones"), (1.0, 3, "prev")]),
+    1024: (117, [(1.0, 3, "ones"), (1.0, _rec(5), "prev")]), 1409: (118, _BIG_U),
+}
+SMALL_CHIP_DIRECTED_CHAINS = {
+    7: (211, [(4.0, _rec(6), "ones"), (4.25, _rec(2), "prev")]),
+    64: (212, [(1.0, _rec(12), "ones"), (1.25, _rec(3), "prev")]),
+    256: (213, [(1.0, _rec(12), "ones"), (1.25, _rec(3), "prev")]),
+    513: (214, [(4.0, _rec(8), "ones"), (4.25, _rec(2), "prev")]),
+    960: (215, _BIG_D), 961: (216, _BIG_D), 1024: (217, _BIG_D), 1409: (218, _BIG_D),
+}
 GAP = 1.1       # the least factor between the two values of f that bracket a case's delta (asserted of every case)
 PICK_GAP = 1.2  # ... and the factor a record is picked by, so that no pick sits on the edge of GAP
 
@@ -269,13 +286,14 @@ def pick_record(f, target):
     raise AssertionError("no record of the zig-zag at or after iteration %d" % target)
 
 
-def chain_cases(N, directed, gd_of):
-    """The cases of the chain of N with their long-double references.  gd_of(problem, alpha) -> the full symmetric power matrix
+def chain_cases(N, directed, gd_of, tables=None):
+    """The cases of the chain of N (of `tables` = (undirected, directed), else of the tables of test_gpu_fit.py) with their
+    long-double references.  gd_of(problem, alpha) -> the full symmetric power matrix
     the references run on (the device's own on the GPU, numpy's on the CPU).  Yields dicts: problem (with alpha and the start),
     K, delta, gap, eps, ref (the long-double trajectory of exactly K steps), A (the amplification max(2, 2 E64(K) / E64(1)) of
     the one-step bound, E64(k) = the relative distance of the plain fp64 iteration from the long-double one after k steps),
     decays (directed: the iterations before K after which epsilon decayed)."""
-    seed, chain = (DIRECTED_CHAINS if directed else UNDIRECTED_CHAINS)[N]
+    seed, chain = (tables or (UNDIRECTED_CHAINS, DIRECTED_CHAINS))[1 if directed else 0][N]
     base = (random_directed if directed else random_undirected)(N, chain[0][0], seed)  # (the hidden iterate: at the first alpha)
     eps = 0.9 if directed else 0.25
     prev = None

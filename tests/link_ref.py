@@ -212,4 +212,35 @@ def stress_cases():
     X = np.arange(1000, dtype=np.float64).reshape(-1, 1)
     c["ascending_scores"] = _case(X, 999.0, 2.0, np.ones(1000), None, [999, 998, 0, 500], 33, [(0, 1)], False, False,
                                   exact=True)
+    # ... and in descending score: the first candidate tile (ids 0 .. 127, a unit grid) holds every query's best 33, every later
+    # tile lies beyond a gap.  A workgroup that walks tile 0 and then others has a k-th value more than twice what they hold at
+    # best (tests/test_link_ref.py), so its filter must reject them: the thresholds are seen to bite
+    X = np.arange(1000, dtype=np.float64).reshape(-1, 1)
+    X[128:] += 500.0
+    c["descending_scores"] = _case(X, 1499.0, 2.0, np.ones(1000), None, [0, 127, 64, 31], 33, [(0, 1)], False, False, exact=True)
+    # the same grid, and in the candidate tiles 2, 4 and 6 one vertex per query that beats the query's k-th value so far by a
+    # hair: its squared distance is 1 - 2e-4 of the k-th's, 1 - 4e-4, 1 - 6e-4.  A workgroup that has walked tile 0 must let each
+    # of them through; a threshold radius that is 1e-3 too tight (squared) drops them, and the list is wrong in its last entry
+    X = np.arange(1000, dtype=np.float64).reshape(-1, 1)
+    X[128:] += 700.0
+    for t, v in enumerate(NEAR_THRESHOLD_IDS):
+        X[v, 0] = -33.0 * (1.0 - 1e-4) ** (t + 1)            # query 0: its 33rd of tile 0 is vertex 33, at distance 33
+        X[v + 1, 0] = 127.0 + 33.0 * (1.0 - 1e-4) ** (t + 1)  # query 127: vertex 94
+    c["near_threshold"] = _case(X, float(X.max() - X.min()), 2.0, np.ones(1000), None, [0, 127], 33, [(0, 1)], False, False,
+                                exact=True)
     return c
+
+
+NEAR_THRESHOLD_IDS = (300, 600, 800)  # in the candidate tiles 2, 4, 6 (with the next id: the second query's)
+
+
+def merge_case(n, seed):
+    """The input of tests/test_gpu_link.py's merge tests: Q = 2 queries, k = 64, d = 3, hi = twice the largest distance from the
+    mean (at least the diameter, without its O(n^2) search), lognormal factors; the vertices of the last 129 ids carry a factor 3,
+    so that the candidate slices with the highest numbers have entries in both lists (checked where it is used)."""
+    rng = np.random.default_rng(seed)
+    X = points(n, 3, seed)
+    hi = 2.0 * float(np.sqrt(((X - X.mean(axis=0)) ** 2).sum(axis=1)).max())
+    fo = np.exp(0.5 * rng.standard_normal(n))
+    fo[-129:] *= 3.0
+    return _case(X, hi, 2.25, fo, None, [n - 1, 5], 64, [(0, 1)], False, False)

@@ -145,6 +145,23 @@ def test_preconditions_of_the_k_step_cases(N):
     assert sum(c["start"] == "prev" for c in drc) * 2 >= len(drc)
 
 
+@pytest.mark.parametrize("N", sorted(fr.SMALL_CHIP_UNDIRECTED_CHAINS))
+def test_preconditions_of_the_small_chip_cases(N):
+    """The chains of tests/test_gpu_small_chip_fits.py (the sizes of 2 .. 64 CUs): the same preconditions, and what that file asks of
+    a chain -- a start that is not the sweep's, a case of three iterations or more (every slot of the rings of 2 and 3 written)."""
+    tables = (fr.SMALL_CHIP_UNDIRECTED_CHAINS, fr.SMALL_CHIP_DIRECTED_CHAINS)
+    assert sorted(tables[0]) == sorted(tables[1]) and not set(tables[0]) & set(fr.UNDIRECTED_CHAINS)
+    for directed in (False, True):
+        cases = fr.chain_cases(N, directed, fr.numpy_gd, tables)
+        for c in cases:
+            assert c["gap"] >= fr.GAP and c["A"] >= 2.0 and c["ref"]["iters"] == c["K"]
+            f = [float(x) for x in c["ref"]["f"]]
+            assert all(x > c["delta"] for x in f[:-1]) and f[-1] <= c["delta"]
+        assert any(c["start"] == "prev" for c in cases) and any(c["K"] >= 3 for c in cases)
+        if directed:
+            assert any(c["decays"] for c in cases)  # the decaying step size is live
+
+
 def test_the_chain_tables_cover_the_ring_residues_and_the_issue_s_counts():
     Ks = set()
     for N in (65, 130, 700):

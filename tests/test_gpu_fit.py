@@ -68,9 +68,10 @@ def _cus():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def _geometry(N):
-    """flow_geometry (kernels_fitp.hip): (G, NW, every workgroup has at most one quarter block) or None = declined."""
-    cus = _cus()
+def _geometry(N, cus=None):
+    """flow_geometry (kernels_fitp.hip): (G, NW, every workgroup has at most one quarter block) or None = declined.  cus: the
+    CU count the context is told (knob test_device_cus: tests/test_gpu_small_chip_fits.py); None = the device's own."""
+    cus = cus or _cus()
     Nt = (N + 63) // 64
     NT = Nt * (Nt + 1) // 2
     NW = 4 if NT <= 4 * cus else 8
@@ -81,8 +82,8 @@ def _geometry(N):
     return G, NW, 4 * Nt <= G
 
 
-def _forms(N, directed, with_auto=True):
-    g = _geometry(N)
+def _forms(N, directed, with_auto=True, cus=None):
+    g = _geometry(N, cus)
     forms = ([0] if with_auto else []) + [1]
     if not directed:
         forms.append(2)
@@ -93,11 +94,11 @@ def _forms(N, directed, with_auto=True):
     return forms
 
 
-def _expected(N, form):
+def _expected(N, form, cus=None):
     """The form that runs: form 0 is the persistent one from 128 vertices on where the geometry applies."""
     if form:
         return form
-    return 3 if N >= 128 and _geometry(N) else 1
+    return 3 if N >= 128 and _geometry(N, cus) else 1
 
 
 def test_the_sizes_reach_what_they_are_chosen_for():
@@ -110,10 +111,10 @@ def test_the_sizes_reach_what_they_are_chosen_for():
     assert g[4032] and g[REFUSED] is None and g[4097] is None and (4097 + 63) // 64 == 65
 
 
-def _run(ctx, pr, directed, form, delta, eps=None, want_GD=False):
+def _run(ctx, pr, directed, form, delta, eps=None, want_GD=False, cus=None):
     ran, (out,) = ctx.fit_test(pr, directed=directed, form=form, eps=eps, delta=delta, want_GD=want_GD)
     N = pr["D"].shape[0]
-    assert ran == _expected(N, form), (N, directed, form, ran)
+    assert ran == _expected(N, form, cus), (N, directed, form, ran)
     return out
 
 
@@ -225,13 +226,13 @@ def _cases(ctx, N, directed):
     return _case_cache[N, directed]
 
 
-def _check_case(ctx, c, N, directed, forms):
+def _check_case(ctx, c, N, directed, forms, cus=None, tag=""):
     """Every form ends the case at iters == K with T_K within A_K times the one-step bound.  Returns the outputs by form."""
     pr, K, ref = c["problem"], c["K"], c["ref"]
     assert c["gap"] >= fr.GAP  # from the reference alone: no form is exempted from iters == K
     outs = {}
     for form in forms:
-        out = outs[form] = _run(ctx, pr, directed, form, c["delta"])
+        out = outs[form] = _run(ctx, pr, directed, form, c["delta"], cus=cus)
         assert out["iters"] == K and out["status"] == 0, (N, directed, form, out["iters"], K)
         pairs = [(out["T"], ref["T"][K - 1], ref["T"][K], ref["S"][K - 1], pr["w"])] if not directed else [
             (out["T"], ref["T"][K - 1][0], ref["T"][K][0], ref["S"][K - 1][0], pr["w"]),
@@ -242,7 +243,7 @@ def _check_case(ctx, c, N, directed, forms):
             tol = c["A"] * fr.step_bound(ref["eps"][K - 1], Tp, deg, Sp, Tn, N)
             err = np.abs(LD(got) - Tn)
             assert np.all(err[live] <= tol[live]), (N, directed, form, K, float(np.max(err[live] / tol[live])), c["A"])
-            _note("V3 directed" if directed else "V3 undirected", np.max(err[live] / tol[live]))
+            _note(("V3 directed" if directed else "V3 undirected") + tag, np.max(err[live] / tol[live]))
     return outs
 
 

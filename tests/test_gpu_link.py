@@ -5,8 +5,22 @@ For every query of a top-k call the test asserts: the reported p are link_prob's
 with the reference within its derived bound; the lists are sorted by (p descending, j ascending), hold admissible, distinct
 candidates and the right count; and the smallest reference value among the returned candidates is at least (1 - 2 BOUND) times the
 largest reference value among the admissible candidates left out.  Where tests/test_link_ref.py has shown the reference's order
-to be beyond the reach of rounding (`exact`), the ids are compared one by one."""
+to be beyond the reach of rounding (`exact`), the ids are compared one by one.
+
+The slices of the candidate tiles follow the CU count: nsl = min(ceil(2 cus / nQt), nTc, 512).  On 256 CUs every shape below has
+nsl == nTc, one tile per workgroup: no threshold ever moves before it is read, no list merges into an earlier one.  So the shapes
+and the cases run a second time under the testing knob test_device_cus = 1 (nsl <= 2: four to eight tiles per workgroup at
+n = 1000), and what that reaches is asserted, not hoped for: `descending_scores` must leave survivors below Q (n - 1) (its
+thresholds provably reject whole tiles), `near_threshold` has entries that pass a moved threshold by 2e-4 of its squared radius.
+link_merge_kernel keeps 8 list heads per lane; the merge tests run it on 66 slices (lanes 0 and 1 hold two heads) and on the cap
+of 512 (every head, and slices that walk two tiles).  Scratch mutants (not committed) and what noticed them:
+link_filter_thresholds' squared radius divided by 1 + 1e-3 -- near_threshold under knob 1 and in the test of the CU counts
+(the last entry of both lists), no other case of either (random inputs put nothing that close to a threshold), and none of the
+earlier tests at knob 0 (61 tests of top-k and rank); link_merge_kernel reading head 0 alone -- both merge tests and nothing
+else."""
+import contextlib
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -25,6 +39,25 @@ def ctx():
     c = api.Context(0)
     yield c
     c.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _cus():
+    import torch
+
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@contextlib.contextmanager
+def _knob(ctx, cus):
+    """The context's launches sized for `cus` CUs (testing knob test_device_cus; 0: the device's own), and back."""
+    if cus > _cus():
+        pytest.skip("the device has %d CUs, the case asks for %d (test_device_cus only shrinks)" % (_cus(), cus))
+    ctx.set_option("test_device_cus", cus)
+    try:
+        yield
+    finally:
+        ctx.set_option("test_device_cus", 0)
 
 
 def _resident(ctx, X, edges0):
@@ -140,6 +173,106 @@ _STRESS = lr.stress_cases()
 @pytest.mark.parametrize("name", sorted(_STRESS))
 def test_topk_cases(ctx, name):
     _check_topk(ctx, _STRESS[name], name)
+
+
+def SHAPE_ID(s):
+    return "n%d-d%d-Q%d-k%d-%s-%s" % (s[0], s[1], s[2], s[3], "dir" if s[4] else "und", "excl" if s[5] else "all")
+
+
+@pytest.mark.parametrize("shape", lr.TOPK_SHAPES, ids=SHAPE_ID)
+def test_topk_shapes_with_several_tiles_per_workgroup(ctx, shape):
+    with _knob(ctx, 1):
+        _check_topk(ctx, lr.shape_case(*shape), "shape, knob 1")
+
+
+@pytest.mark.parametrize("name", sorted(_STRESS))
+def test_topk_cases_with_several_tiles_per_workgroup(ctx, name):
+    c = _STRESS[name]
+    with _knob(ctx, 1):
+        _check_topk(ctx, c, name + ", knob 1")
+        if name == "descending_scores":  # tests/test_link_ref.py: the k-th value after tile 0 is twice what a later tile holds
+            Q, n = len(c["queries"]), len(c["X"])
+            surv = ctx.get_stat("link_topk_survivors")
+            print(f"  survivors {surv} of {Q * n}")
+            assert Q * 128 <= surv < Q * (n - 1)  # the filter bites (and tile 0 is evaluated whole: the lists are short there)
+            assert surv <= Q * (n - 3 * 128)  # the workgroup of tile 0 rejects its three later tiles whole
+
+
+_CU_CASES = [lr.TOPK_SHAPES[8], lr.TOPK_SHAPES[9], lr.TOPK_SHAPES[10], "far_heavy_vertex", "common_offset", "near_threshold"]
+
+
+@pytest.mark.parametrize("case", _CU_CASES, ids=lambda s: s if isinstance(s, str) else SHAPE_ID(s))
+def test_link_queries_do_not_depend_on_the_cu_count(ctx, case):
+    """include/cge_hip.h promises top-k's lists, rank's counts and a sample's edges as functions of the inputs alone: the same
+    bits whatever the slices (knob 1: nsl <= 2, knob 3: nsl <= 6, the device's own)."""
+    c = _STRESS[case] if isinstance(case, str) else lr.shape_case(*case)
+    n, qs = len(c["X"]), c["queries"]
+    _resident(ctx, c["X"], c["edges"])
+    ctx.link_set_model(c["alpha"], c["hi"], c["fo"], c["fi"], c["directed"])
+    ri = np.repeat(qs[:40], 3)
+    rj = (ri * 7 + np.tile([1, 50, 333], len(qs[:40]))) % n
+    rj = np.where(rj == ri, (rj + 1) % n, rj)
+    got = {}
+    for cus in (1, 3, 0):
+        with _knob(ctx, cus):
+            top = ctx.link_topk(qs + 1, c["k"], c["exclude"])
+            surv = ctx.get_stat("link_topk_survivors")
+            rank = ctx.link_rank(ri + 1, rj + 1, c["exclude"])
+            smp = ctx.link_sample(5, 2, None, True)
+            got[cus] = (top, rank, smp)
+            print(f"  knob {cus}: top-k survivors {surv}, rank survivors {ctx.get_stat('link_rank_survivors')}, {smp[3]} sampled edges")
+    for cus in (1, 3):
+        for a, b in zip(got[cus][0], got[0][0]):  # J, P, cnt
+            assert a.tobytes() == b.tobytes(), (case, cus, "top-k")
+        for a, b in zip(got[cus][1], got[0][1]):  # greater, ties, cand, p
+            assert a.tobytes() == b.tobytes(), (case, cus, "rank")
+        assert got[cus][2][3] == got[0][2][3]
+        for a, b in zip(got[cus][2][:3], got[0][2][:3]):  # i, j, p
+            assert a.tobytes() == b.tobytes(), (case, cus, "sample")
+
+
+# ---- link_merge_kernel with several heads per lane ----------------------------------------------------------------------------------
+def _check_merge(ctx, n, nsl):
+    """Q = 2, k = 64 on n candidates in nsl slices against a full sort of lr.prob's values (no O(n^2) diameter, no insertion
+    loop): _check_topk's assertions."""
+    c = lr.merge_case(n, 90)
+    X, k, qs = c["X"], c["k"], c["queries"]
+    assert (n + 127) // 128 >= nsl
+    _resident(ctx, X, c["edges"])
+    ctx.link_set_model(c["alpha"], c["hi"], c["fo"], None, False)
+    J, P, cnt = ctx.link_topk(qs + 1, k, False)
+    assert J.shape == P.shape == (2, k) and cnt.tolist() == [k, k]
+    assert np.array_equal(P.ravel(), ctx.link_prob(np.repeat(qs, k) + 1, J.ravel())), "a reported p is not link_prob's"
+    for q, i in enumerate(qs):
+        cand = np.delete(np.arange(n), i)
+        pref = lr.prob(X, c["hi"], c["alpha"], c["fo"], None, np.full(n - 1, i), cand)
+        js, ps = lr.topk_by_sort(cand, pref, k)
+        sl = (js // 128) % nsl
+        assert (sl >= 64).sum() >= 8  # the reference's list has entries that a lane keeps under a head u >= 1
+        j, p = J[q] - 1, P[q]
+        ok, worst = _within_bound(p, pref[np.searchsorted(cand, j)])
+        print(f"  n={n} query {i}: worst relative error {worst:.3g} (bound {lr.BOUND:.3g}); the reference's entries sit in "
+              f"{len(set(sl.tolist()))} slices, {(sl >= 64).sum()} under heads >= 1, heads {sorted(set((sl // 64).tolist()))}")
+        assert ok
+        assert len(set(j.tolist())) == k and i not in j
+        assert all(p[t] > p[t + 1] or (p[t] == p[t + 1] and j[t] < j[t + 1]) for t in range(k - 1)), f"query {q} unsorted"
+        inside = np.isin(cand, j)
+        assert pref[inside].min() >= (1 - 2 * lr.BOUND) * pref[~inside].max(), f"query {q} misses a better candidate"
+        assert j.tolist() == js.tolist()  # (tests/test_link_ref.py: neighbours of the reference's list are > 2 BOUND apart)
+
+
+def test_merge_with_two_heads_in_two_lanes(ctx):
+    """n = 8321 under knob 33: nTc = 66 = nsl = ceil(2 x 33 / 1), so lanes 0 and 1 of link_merge_kernel hold two heads."""
+    with _knob(ctx, 33):
+        _check_merge(ctx, 8321, 66)
+
+
+def test_merge_at_the_cap_of_512_slices(ctx):
+    """n = 65700 on the device's own CU count: nTc = 514, nsl = min(2 cus, 514, 512) = 512 from 256 CUs on -- every lane holds 8
+    heads, and the slices 0 and 1 walk two tiles."""
+    if _cus() < 256:
+        pytest.skip("the device has %d CUs: 2 cus slices stay below the cap of 512" % _cus())
+    _check_merge(ctx, 65700, 512)
 
 
 def test_topk_does_not_depend_on_the_query_batch(ctx):

@@ -96,6 +96,20 @@ def test_rank_shapes(ctx, shape):
     _check(ctx, rr.shape_case(*shape), "shape")
 
 
+@pytest.mark.parametrize("shape", rr.RANK_SHAPES, ids=lambda s: "n%d-d%d-Qu%d-x%d-%s-%s" % (s[0], s[1], s[2], s[3], "dir" if s[4] else "und",
+                                                                                          "excl" if s[5] else "all"))
+def test_rank_shapes_with_several_tiles_per_workgroup(ctx, shape):
+    """link_rank_kernel slices the candidate tiles as top-k does (nsl = min(ceil(2 cus / nQt), nTc, 512)): one tile per workgroup
+    in every shape on 256 CUs.  Under the testing knob test_device_cus = 1 a workgroup walks up to half of them, its thresholds,
+    the proven-pairs mask in the Gram staging and its row tables carried from tile to tile.  (The counts under knobs 1, 3 and 0
+    are compared bit for bit in tests/test_gpu_link.py::test_link_queries_do_not_depend_on_the_cu_count.)"""
+    ctx.set_option("test_device_cus", 1)
+    try:
+        _check(ctx, rr.shape_case(*shape), "shape, knob 1")
+    finally:
+        ctx.set_option("test_device_cus", 0)
+
+
 _STRESS = rr.stress_cases()
 
 

@@ -77,6 +77,26 @@ def test_sample_shapes(ctx, shape):
         assert (got[2] > 1).any()  # the heavy vertex's pairs are edges whatever u is
 
 
+@pytest.mark.parametrize("shape", [s for s in sr.SHAPES if s[0] >= 257], ids=sr.shape_id)
+def test_sample_shapes_on_a_smaller_grid(ctx, shape):
+    """The grid is min(tiles, 2 cus) workgroups that stride over the tiles: on 256 CUs every shape has a workgroup per tile.  Under
+    the testing knob test_device_cus a workgroup walks several; the draw is the reference's all the same, row for row and bit for
+    bit, and so are the statistics."""
+    n, d, directed = shape
+    _model(ctx, sr.shape_case(*shape))
+    want, _ = _check_draw(ctx, n, directed, 11, 0, "shape")  # (against the reference)
+    surv = ctx.get_stat("link_sample_survivors")
+    for cus in (1, 2):
+        assert _tiles(n, directed) > 2 * cus  # more tiles than workgroups
+        ctx.set_option("test_device_cus", cus)
+        try:
+            got = ctx.link_sample(11, 0, None, True)
+        finally:
+            ctx.set_option("test_device_cus", 0)
+        assert got[3] == want[3] and all(a.tobytes() == b.tobytes() for a, b in zip(got[:3], want[:3])), cus
+        assert ctx.get_stat("link_sample_survivors") == surv and ctx.get_stat("link_sample_tiles") == _tiles(n, directed)
+
+
 @pytest.mark.parametrize("directed", [False, True], ids=["und", "dir"])
 def test_dense_and_empty(ctx, directed):
     n = 300

@@ -127,6 +127,48 @@ def test_stress_cases_are_what_they_claim():
     assert (np.diff(np.asarray(p, np.float64)) > 0).all()
     # k beyond n: five vertices, k = 7
     assert c["k_beyond_n_exclude1"]["k"] > len(c["k_beyond_n_exclude1"]["X"])
+    # descending scores: every query's best k = 33 lie in the first candidate tile, and the k-th value is more than twice the
+    # largest of every later tile -- so a workgroup that has walked tile 0 holds thresholds that reject the later tiles whole
+    # (the filter's margins are relative 1e-12 and a rounding bound of the Gram value: nothing beside a factor 2)
+    s = c["descending_scores"]
+    assert s["k"] == 33 and s["X"].shape == (1000, 1)
+    J, P, cnt, vals = lr.topk(s["X"], s["hi"], s["alpha"], s["fo"], None, s["queries"], s["k"], exclude=False)
+    for q, (cand, p) in enumerate(vals):
+        assert cnt[q] == 33 and (J[q] < 128).all()
+        for t in range(1, 8):
+            assert P[q, 32] > 2 * p[cand // 128 == t].max(), (q, t)
+    # near threshold: after tile 0 the k-th value of a query is vertex 33's (94's); the marked vertex of tile 2 beats it, that of
+    # tile 4 beats the one of tile 2, that of tile 6 the one of tile 4 -- each by more than 2 BOUND in value and by less than
+    # 1e-3 in squared distance, so a threshold radius 1e-3 too tight (squared) rejects it; the last one ends the final list
+    s = c["near_threshold"]
+    _, _, _, vals = lr.topk(s["X"], s["hi"], s["alpha"], s["fo"], None, s["queries"], s["k"], exclude=False)
+    for q, (i, kth) in enumerate(((0, 33), (127, 94))):
+        cand, p = vals[q]
+        chain = [kth] + [v + q for v in lr.NEAR_THRESHOLD_IDS]
+        assert [v // 128 for v in chain] == [0, 2, 4, 6]
+        d2 = (s["X"][chain, 0] - s["X"][i, 0]) ** 2
+        pv = [p[cand == v][0] for v in chain]
+        for t in range(3):
+            assert pv[t + 1] > pv[t] * (1 + 4 * lr.BOUND) and d2[t] / 1.001 < d2[t + 1] < d2[t]
+        js, _ = lr.topk_by_sort(cand, p, 33)
+        assert js[-1] == chain[-1] and set(js[:-1].tolist()) <= set(range(128))
+
+
+@pytest.mark.parametrize("n,nsl", [(8321, 66), (65700, 512)])
+def test_merge_cases_have_entries_in_the_late_slices(n, nsl):
+    """tests/test_gpu_link.py's merge tests: with the slices they run on (candidate tile J in slice J mod nsl, lane = slice mod 64,
+    head = slice // 64) both queries' lists hold entries of heads >= 1 -- at the cap every head of the 8 and a second tile."""
+    m = lr.merge_case(n, 90)
+    assert m["k"] == 64 and len(m["queries"]) == 2 and m["X"].shape == (n, 3) and (n + 127) // 128 in (66, 514)
+    assert m["hi"] >= np.sqrt(((m["X"][:, None, :] - m["X"][None, :4000:40, :]) ** 2).sum(axis=2)).max()  # (a spot check: hi >= distances)
+    for i in m["queries"]:
+        cand = np.delete(np.arange(n), i)
+        js, ps = lr.topk_by_sort(cand, lr.prob(m["X"], m["hi"], m["alpha"], m["fo"], None, np.full(n - 1, i), cand), 64)
+        sl = (js // 128) % nsl
+        assert (sl >= 64).sum() >= 8 and len(set(sl.tolist())) >= 20
+        if nsl == 512:
+            assert set((sl // 64).tolist()) == set(range(8)) and (js // 128 >= 512).any()
+        assert all(a == b or a - b > 2 * lr.BOUND * a for a, b in zip(ps[:-1], ps[1:]))  # the order is beyond rounding
 
 
 # ---- the C-ABI --------------------------------------------------------------------------------------------------------------------
