@@ -1548,6 +1548,32 @@ class Context:
             lambda cap_, oi, oj, op, ne: self.L.cge_link_sample_test(self.h, _p(Um), C.c_int(int(bool(directed_layout))), cap_, oi, oj,
                                                                      op, ne), cap, want_p)
 
+    def link_auc(self, part=0, nparts=1, want_counts=False, want_p=False):
+        """The exact link AUC of the resident model on the resident graph (cge_link_auc): every resident edge row against every
+        non-edge.  Returns {"local_exact": 1 - L / (W n_neg) -- what element 5 of a score estimates from samples; ties count
+        against --, "auc": (L + Tq / 2) / (W n_neg), "n_pos", "n_neg", "W", "L", "Tq"}; with want_counts also "less" / "ties"
+        (int64 (m,), the edge list's order), with want_p also "p".  `part` of `nparts` visits its share of the pair tiles: the
+        quotients of a part are of that part's sums (add the parts' counts up and use `link_auc_from_counts`).  No non-edges:
+        the quotients are NaN."""
+        part, nparts = int(part), int(nparts)
+        if nparts < 1 or not 0 <= part < nparts:
+            raise ValueError(f"link_auc: part = {part} of nparts = {nparts}")
+        m = int(self.m)
+        less = np.zeros(max(m, 1), dtype=np.int64) if want_counts else None
+        ties = np.zeros(max(m, 1), dtype=np.int64) if want_counts else None
+        p = np.zeros(max(m, 1)) if want_p else None
+        nneg, summ = C.c_int64(-1), np.zeros(3)
+        self._check(self.L.cge_link_auc(self.h, C.c_int(part), C.c_int(nparts), _p(less) if want_counts else None,
+                                        _p(ties) if want_counts else None, _p(p) if want_p else None, C.byref(nneg), _p(summ)))
+        W, L, Tq = (float(x) for x in summ)
+        out = {"n_pos": m, "n_neg": int(nneg.value), "W": W, "L": L, "Tq": Tq}
+        out["local_exact"], out["auc"] = _link_auc_quotients(W, L, Tq, nneg.value)
+        if want_counts:
+            out["less"], out["ties"] = less[:m], ties[:m]
+        if want_p:
+            out["p"] = p[:m]
+        return out
+
     def ecg_members_test(self, members=16, seed=0):
         """Testing hook (cge_ecg_members_test): the member and peel stages of `ecg` alone -- (members (K, n) each renumbered as a
         pass is, n_comm (K,), rounds (K,), modularity (K,), core (n,) bool)."""
@@ -1779,6 +1805,49 @@ def link_evaluate(edge_index, embedding, comm, land, test_pairs, forced=4, metho
         tp = tp.T
     counts = ctx.link_rank(tp[:, 0], tp[:, 1], exclude_edges)
     return vec, link_metrics(counts[0], counts[1], counts[2], ks), counts
+
+
+def _link_auc_quotients(W, L, Tq, n_neg):
+    """(1 - L / (W n_neg), (L + Tq / 2) / (W n_neg)) in long double, rounded once each; NaN without non-edges or weight."""
+    LD = np.longdouble
+    den = LD(W) * LD(int(n_neg))
+    if not den > 0:
+        return float("nan"), float("nan")
+    return float(LD(1) - LD(L) / den), float((LD(L) + LD(Tq) / LD(2)) / den)
+
+
+def link_auc_from_counts(less, ties, w, n_neg):
+    """The two quotients of `Context.link_auc` from per-edge counts (pure numpy in long double, no GPU): for callers who add the
+    parts' `less` / `ties` up.  `w`: the edge weights (None: 1 each).  Returns {"local_exact", "auc", "W", "L", "Tq"}; the sums
+    are taken in the list's order in long double and rounded once, as the library takes them."""
+    LD = np.longdouble
+    ls, ts = np.asarray(less).ravel(), np.asarray(ties).ravel()
+    ww = np.ones(len(ls)) if w is None else np.asarray(w, dtype=np.float64).ravel()
+    if not len(ls) == len(ts) == len(ww):
+        raise ValueError("link_auc_from_counts: less, ties and w differ in length")
+    W, L, Tq = LD(0), LD(0), LD(0)
+    for a, b, c in zip(ww.astype(LD), ls.astype(LD), ts.astype(LD)):  # (np.sum adds pairwise: another order)
+        W += a
+        L += a * b
+        Tq += a * c
+    W, L, Tq = float(W), float(L), float(Tq)
+    le, auc = _link_auc_quotients(W, L, Tq, n_neg)
+    return {"local_exact": le, "auc": auc, "W": W, "L": L, "Tq": Tq}
+
+
+def link_auc(edge_index, embedding, comm, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000,
+             which="local", want_counts=False, want_p=False, weights=None, base=-1, ctx=None):
+    """The exact local score and AUC of the fitted model, beside `link_evaluate`: the graph and the embedding go in as views,
+    `Context.link_fit` fits the model of the best alpha, `Context.link_auc` counts every non-edge against every edge.  Returns
+    (vector, result); a directed star graph's early return leaves (vector, None)."""
+    ctx = ctx or default_context()
+    ctx.set_graph_view(edge_index, weights, n=int(embedding.shape[0]), base=base)
+    ctx.set_vertex_view(comm, None, base=base)
+    ctx.set_embedding_view(embedding)
+    vec, _ = ctx.link_fit(FROM_COMM, land, forced, method, directed, split, seed, auc_samples, which)
+    if len(vec) < 7:
+        return vec, None
+    return vec, ctx.link_auc(0, 1, want_counts, want_p)
 
 
 def link_sample(edge_index, embedding, comm, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000,

@@ -298,6 +298,13 @@ int cge_link_sample(cge_ctx *c, int64_t seed, int64_t stream, int64_t cap, int64
     host_link_sample(c, seed, stream, cap, out_i, out_j, out_p, n_edges, nullptr, 0);
     CGE_CATCH(c)
 }
+int cge_link_auc(cge_ctx *c, int part, int nparts, int64_t *out_less, int64_t *out_ties, double *out_p, int64_t *n_neg,
+                 double summary[3]) {
+    if (!c || !n_neg || !summary) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_auc(c, part, nparts, out_less, out_ties, out_p, n_neg, summary);
+    CGE_CATCH(c)
+}
 // testing hook (include/cge_hip_testing.h): the same launch with the uniforms read from a caller's matrix
 int cge_link_sample_test(void *ctx, const double *U, int directed_layout, int64_t cap, int64_t *out_i, int64_t *out_j, double *out_p,
                          int64_t *n_edges) {
@@ -516,6 +523,9 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "link_sample_edges")) *value = c->link.stat_sample_edges;         // of the last cge_link_sample: its edges,
     else if (!strcmp(key, "link_sample_survivors")) *value = c->link.stat_sample_survivors; // the pairs evaluated exactly,
     else if (!strcmp(key, "link_sample_tiles")) *value = c->link.stat_sample_tiles;         // the tiles walked
+    else if (!strcmp(key, "link_auc_survivors")) *value = c->link.stat_auc_survivors; // of the last cge_link_auc: pairs evaluated exactly,
+    else if (!strcmp(key, "link_auc_tiles")) *value = c->link.stat_auc_tiles;         // the tiles walked,
+    else if (!strcmp(key, "link_auc_proven")) *value = c->link.stat_auc_proven;       // the pairs the filter settled alone
     else if (!strcmp(key, "cut_tie_tasks")) { // (read from the device on request: a synchronising copy)
         int v = 0;
         if (c->cut_ties.p && (hipStreamSynchronize(c->stream) != hipSuccess ||

@@ -317,6 +317,12 @@ struct LinkModel {
     DevBuf<unsigned long long> skeys_in, skeys, scnt;
     DevBuf<i64> sout;
     i64 stat_sample_edges = 0, stat_sample_survivors = 0, stat_sample_tiles = 0; // of the last cge_link_sample
+    // cge_link_auc: the positives' values sorted ascending and the way back to the edge list's order (the two histograms are
+    // rhist, the counts in edge-list order rout, the values themselves vals), the counters
+    DevBuf<double> at;
+    DevBuf<i64> aperm;
+    DevBuf<unsigned long long> acnt;
+    i64 stat_auc_survivors = 0, stat_auc_tiles = 0, stat_auc_proven = 0; // of the last cge_link_auc
 };
 
 struct cge_ctx {
@@ -1103,6 +1109,8 @@ void k_link_rank_final(cge_ctx *c, const i32 *uq, const i64 *off, i64 Qu, const 
 // read from that n x n matrix (the testing hook).  Returns the number of tiles walked
 i64 k_link_sample(cge_ctx *c, i64 seed, i64 stream_id, unsigned long long *keys, i64 cap, unsigned long long *cnt, const double *U,
                   int ulay);
+void k_link_auc(cge_ctx *c, int part, int nparts, const double *p, double *t, i64 *perm, unsigned long long *G, unsigned long long *E,
+                unsigned long long *cnt, i64 *out_less, i64 *out_ties);
 void k_link_sample_finish(cge_ctx *c, const unsigned long long *keys_in, unsigned long long *keys, i64 ne, i32 *pi, i32 *pj, i64 *oi,
                           i64 *oj);
 // ---- host modules -----------------------------------------------------------------------------
@@ -1141,6 +1149,8 @@ void host_link_topk(cge_ctx *c, const int64_t *queries, i64 Q, i64 k, int exclud
                     int64_t *out_cnt);
 void host_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, int exclude_edges, int64_t *out_greater,
                     int64_t *out_ties, int64_t *out_cand, double *out_p);
+void host_link_auc(cge_ctx *c, int part, int nparts, int64_t *out_less, int64_t *out_ties, double *out_p, int64_t *n_neg,
+                   double summary[3]);
 // U != nullptr: cge_link_sample_test (n x n host doubles in the place of the counter stream)
 void host_link_sample(cge_ctx *c, i64 seed, i64 stream_id, i64 cap, int64_t *out_i, int64_t *out_j, double *out_p, int64_t *n_edges,
                       const double *U, int directed_layout);

@@ -1,7 +1,8 @@
 // kernels_link.hip -- the link model's kernels (cge_link_*, link_host.cpp): the per-vertex factors of a fitted model, the model's
 // probability of given pairs, per query the k most probable candidates, and the exact rank of given pairs among their query's
 // candidates (link_rank_kernel: top-k's tiles and filter stage with thresholds known before the first tile), and draws of the random
-// graph the model is (link_sample_kernel, at the end: max_pair_kernel's walk of all pair tiles, a filter of its own).  gfx950 only.
+// graph the model is (link_sample_kernel: max_pair_kernel's walk of all pair tiles, a filter of its own), and the exact link AUC
+// (link_auc_kernel, at the end: the same walk, rank's filter, every non-edge placed among the edges' sorted values).  gfx950 only.
 //
 //     p(i, j) = (f_out[i] * f_in[j]) * max(0, 1 - dist(i, j) / hi) ^ alpha
 //
@@ -975,4 +976,224 @@ void k_link_sample_finish(cge_ctx *c, const unsigned long long *keys_in, unsigne
         HIP_CHECK(rocprim::radix_sort_keys(c->sort_tmp.p, bytes, keys_in, keys, (size_t)ne, 0u, 64u, c->stream));
     }
     hipLaunchKernelGGL(link_sample_unpack_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c->stream, keys, ne, pi, pj, oi, oj);
+}
+
+// ---- cge_link_auc -----------------------------------------------------------------------------------------------------------------
+// Every resident edge row e is a positive with the threshold p_e (k_link_prob's value), every non-edge a negative; per positive the
+// negatives strictly below it and level with it.  The thresholds are sorted ascending once (t, with the permutation back to the
+// edge list's order), and link_sample_kernel's walk of all pair tiles places every negative among them:
+//   * the filter is link_rank_kernel's (link_filter_mask<true, true>: the candidate's own factor, both sides) with ONE pair of
+//     thresholds for every row, t_min = t[0] and t_max = t[m - 1].  A pair it proves below t_min is below every positive, a pair
+//     it proves above t_max is below none; neither can be a resident edge (an edge's own value is one of the thresholds, and the
+//     filter never puts a value on the wrong side of one), so neither needs the edge keys.  Both are counted per lane and leave
+//     the kernel in one atomic per wave;
+//   * every other pair is evaluated with link_p.  Below t_min or above t_max it joins the two groups above.  Otherwise ub, the
+//     first slot with t > p, takes one add of G (an inclusive prefix sum gives `less`), and when slots equal p exist -- lb < ub,
+//     lb the first slot with t >= p -- the pair is a tie of that run (one add of E at the run's start) UNLESS it is a resident
+//     edge: only here are the keys searched, since an edge's value always meets its own threshold.
+// Integer atomics: the counts do not depend on the grid, the shares of the parts or the order.
+struct LinkAuc : LinkTiles {
+    const double *t; i64 m;            // the positives' values ascending
+    unsigned long long *G, *E;         // per slot: negatives that are first below it / that equal its run (at the run's start)
+    const double *fib;                 // f_in[c]^(-1 / alpha)
+    int part, nparts;                  // this call walks the positions part, part + nparts, ... of the tile order
+    unsigned long long *cnt;           // [0] pairs evaluated, [1] proven below t_min, [2] proven above t_max, [3] evaluated and
+};                                     // below t_min, [4] tiles
+
+template <bool EXP2>
+__global__ __launch_bounds__(256, 2) void link_auc_kernel(LinkAuc A) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *erow = lds + (size_t)2 * 2 * MP_BK * MP_LD, *arow = erow + 128, *asure = arow + 128, *rqs = asure + 128;
+    unsigned *mask = reinterpret_cast<unsigned *>(rqs + 128);
+    unsigned *mask2 = reinterpret_cast<unsigned *>(lds); // the pairs proven above t_max: in the Gram staging, free between two tiles
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4, c2 = lane * 2;
+    const i64 nT = A.ldn / MP_BM, nS = (nT + MP_SB - 1) / MP_SB, nchunk = A.dpad / MP_BK;
+    const i64 per = (i64)MP_SB * MP_SB;
+    const i64 total = (A.directed ? nS * nS : nS * (nS + 1) / 2) * per;
+    const double inf = __builtin_huge_val();
+    const double tmin = A.t[0], tmax = A.t[A.m - 1];
+    for (int q = tid; q < 512; q += 256) mask[q] = 0u;
+    unsigned long long lsurv = 0, lbelow = 0, labove = 0, llow = 0, ntile = 0; // per lane; added up once, at the end
+    lds_sync();
+    for (i64 t = (i64)A.part + (i64)A.nparts * blockIdx.x; t < total; t += (i64)A.nparts * gridDim.x) {
+        i64 SI = 0, I, J;
+        if (A.directed) {
+            const i64 sb = t / per, loc = t - sb * per;
+            I = (sb / nS) * MP_SB + loc / MP_SB;
+            J = (sb % nS) * MP_SB + loc % MP_SB;
+        } else {
+            tile_from_linear(t, nS, SI, I, J);
+        }
+        if (I >= nT || J >= nT || (!A.directed && J < I)) continue; // uniform per workgroup
+        const i64 i0 = I * MP_BM, j0 = J * MP_BN;
+        d4 acc[4][4];
+        gram_tile_128(A.Xc + (i64)wave * A.ldn + i0 + c2, A.Xc + (i64)wave * A.ldn + j0 + c2, A.ldn, A.ldn, nchunk, lds, acc, wave, c2,
+                      wr, wc, lr, lk);
+        // (gram_tile_128 ends behind a barrier, and every wave was done with the previous tile's rows before its first)
+        if (tid < 128) { // the rows' roots of t_min and t_max (link_root_row, link_root_row_sure); a row beyond n passes nothing
+            const i64 i = i0 + tid;
+            const double rq = A.rn[i]; // rnorm is padded to ldn
+            double ar = inf, as = inf;
+            if (i < A.n) {
+                const double fo = A.fo[i];
+                ar = link_root_row(tmin, fo, A.alpha);
+                as = link_root_row_sure(tmax, fo, A.alpha);
+            }
+            rqs[tid] = rq;
+            arow[tid] = ar;
+            asure[tid] = as;
+            erow[tid] = i < A.n ? A.einfl * rq : -inf;
+        }
+        for (int q = tid; q < 512; q += 256) mask2[q] = 0u;
+        ntile++;
+        lds_sync();
+        link_filter_mask<true, true>(A, acc, j0, rqs, arow, erow, A.fib, mask, wr, wc, lr, lk, asure, mask2);
+        lds_sync();
+        // ---- row by row: wave w takes the rows w, w + 4, ...; lane l the candidates j0 + l and j0 + l + 64
+        for (int rr = 0; rr < 32; rr++) {
+            const int il = wave + 4 * rr;
+            const i64 vi = i0 + il;
+            const uint4 mw = *reinterpret_cast<const uint4 *>(mask + il * 4);
+            const uint4 ms = *reinterpret_cast<const uint4 *>(mask2 + il * 4);
+            if (lane < 4) mask[il * 4 + lane] = 0u;
+            if (vi >= A.n) continue; // (wave-uniform)
+            const unsigned w0 = lane < 32 ? mw.x : mw.y, w1 = lane < 32 ? mw.z : mw.w;
+            const unsigned s0 = lane < 32 ? ms.x : ms.y, s1 = lane < 32 ? ms.z : ms.w;
+            const double fo = A.fo[vi];
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const i64 j = j0 + lane + 64 * h;
+                if (!(j < A.n && (A.directed ? j != vi : vi < j))) continue; // not a pair of the model
+                const bool on = (((h ? w1 : w0) >> (lane & 31)) & 1u) != 0u;
+                const bool sure = (((h ? s1 : s0) >> (lane & 31)) & 1u) != 0u;
+                if (!on) { lbelow++; continue; }
+                if (sure) { labove++; continue; }
+                lsurv++;
+                const double p = link_p<EXP2>(A.Xr, A.d, vi, j, fo, A.fi[j], A.hi, A.alpha);
+                if (!(p >= 0.0) || p > tmax) continue; // (a NaN: unspecified) above every positive
+                if (p < tmin) { llow++; continue; }
+                i64 lo = 0, hi = A.m; // lb: the first slot with t >= p
+                while (lo < hi) {
+                    const i64 mid = (lo + hi) >> 1;
+                    if (A.t[mid] < p) lo = mid + 1;
+                    else hi = mid;
+                }
+                const i64 lb = lo;
+                hi = A.m; // ub: the first slot with t > p, from there on
+                while (lo < hi) {
+                    const i64 mid = (lo + hi) >> 1;
+                    if (A.t[mid] <= p) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lb < lo) { // level with a run of positives: one of them itself, if the pair is a resident edge
+                    if (link_is_edge(A.keys, A.nkeys, link_key(vi, j, A.directed))) continue;
+                    atomicAdd(A.E + lb, 1ull);
+                }
+                if (lo < A.m) atomicAdd(A.G + lo, 1ull);
+            }
+        }
+        // (the next tile's staging is written behind gram_tile_128's first barrier: every wave has read its rows of mask2 by then)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the cleared masks have landed before that barrier
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        lsurv += __shfl_xor(lsurv, s);
+        lbelow += __shfl_xor(lbelow, s);
+        labove += __shfl_xor(labove, s);
+        llow += __shfl_xor(llow, s);
+    }
+    if (lane == 0) {
+        if (lsurv) atomicAdd(A.cnt, lsurv);
+        if (lbelow) atomicAdd(A.cnt + 1, lbelow);
+        if (labove) atomicAdd(A.cnt + 2, labove);
+        if (llow) atomicAdd(A.cnt + 3, llow);
+        if (wave == 0 && ntile) atomicAdd(A.cnt + 4, ntile);
+    }
+}
+
+// the distinct non-loop keys of the sorted edge keys: what the non-edges are counted from
+__global__ void link_distinct_kernel(const unsigned long long *__restrict__ keys, i64 nkeys, unsigned long long *__restrict__ out) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    unsigned long long cnt = 0;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < nkeys; e += stride) {
+        const unsigned long long key = keys[e];
+        if (e > 0 && keys[e - 1] == key) continue;
+        if ((key >> 32) != (key & 0xffffffffull)) cnt++;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(out, cnt);
+}
+// G holds its inclusive prefix sum here: `less` of slot s is that plus the pairs below t_min, `ties` the E of the slot's run (equal
+// thresholds -- repeated rows, symmetric configurations -- share both); written through the permutation to the edge list's order
+__global__ void link_auc_final_kernel(const double *__restrict__ t, const i64 *__restrict__ perm, const unsigned long long *__restrict__ G,
+                                      const unsigned long long *__restrict__ E, const unsigned long long *__restrict__ cnt, i64 m,
+                                      i64 *__restrict__ out_less, i64 *__restrict__ out_ties) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    const unsigned long long below = cnt[1] + cnt[3];
+    for (i64 s = (i64)blockIdx.x * blockDim.x + threadIdx.x; s < m; s += stride) {
+        const double ts = t[s];
+        i64 lo = 0, hi = s; // the first slot of the run equal to ts
+        while (lo < hi) {
+            const i64 mid = (lo + hi) >> 1;
+            if (t[mid] < ts) lo = mid + 1;
+            else hi = mid;
+        }
+        const i64 at = perm[s];
+        out_less[at] = (i64)(G[s] + below);
+        out_ties[at] = (i64)E[lo];
+    }
+}
+
+// p: the positives' values in the edge list's order (k_link_prob's).  t / perm / G / E: m entries each; cnt: 6 counters (the
+// kernel's five and the distinct non-loop keys); out_less / out_ties in the edge list's order.
+void k_link_auc(cge_ctx *c, int part, int nparts, const double *p, double *t, i64 *perm, unsigned long long *G, unsigned long long *E,
+                unsigned long long *cnt, i64 *out_less, i64 *out_ties) {
+    LinkModel &m = c->link;
+    const i64 ne = c->m;
+    k_link_fib(c);
+    HIP_CHECK(hipMemsetAsync(G, 0, sizeof(unsigned long long) * 2 * ne, c->stream)); // (G and E are one allocation)
+    HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 6, c->stream));
+    {
+        ScopedKernelTimer tm(c, "link_auc_sort"); // non-negative doubles: any order of the bits is the order of the values
+        size_t bytes = 0;
+        rocprim::counting_iterator<i64> iota(0);
+        HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, p, t, iota, perm, (size_t)ne, 0u, 64u, c->stream));
+        c->sort_tmp.ensure(bytes);
+        HIP_CHECK(rocprim::radix_sort_pairs(c->sort_tmp.p, bytes, p, t, iota, perm, (size_t)ne, 0u, 64u, c->stream));
+    }
+    hipLaunchKernelGGL(link_distinct_kernel, dim3(grid_for(m.nkeys, 256)), dim3(256), 0, c->stream, m.keys.p, m.nkeys, cnt + 5);
+    const i64 nT = c->ldn / MP_BM, nS = (nT + MP_SB - 1) / MP_SB;
+    const i64 total = (m.directed ? nS * nS : nS * (nS + 1) / 2) * MP_SB * MP_SB; // positions of the walk, padding included
+    const i64 mine = total > part ? (total - part + nparts - 1) / nparts : 0;
+    LinkAuc A{};
+    A.Xc = c->Xc.p; A.rn = c->rnorm.p; A.ldn = c->ldn;
+    A.n = c->n; A.dpad = c->dpad;
+    A.Xr = c->Xr.p; A.d = c->d;
+    A.fo = m.f.p; A.fi = m.f.p + m.n;
+    A.hi = m.hi; A.alpha = m.alpha;
+    A.einfl = (double)(c->dpad + 16) * 2.220446049250313e-16; // (K + 16) 2^-52
+    A.dinfl = 1.0 + A.einfl;
+    A.keys = m.keys.p; A.nkeys = m.nkeys; A.directed = m.directed;
+    A.t = t; A.m = ne; A.G = G; A.E = E; A.fib = m.fib.p;
+    A.part = part; A.nparts = nparts; A.cnt = cnt;
+    const dim3 grid((unsigned)std::max<i64>(1, std::min<i64>(mine, 2 * (i64)device_cus(c))));
+    {
+        ScopedKernelTimer tm(c, "link_auc");
+        if (m.pow_form) {
+            cge_allow_lds((const void *)link_auc_kernel<true>, LR_LDS_BYTES);
+            hipLaunchKernelGGL(link_auc_kernel<true>, grid, dim3(256), LR_LDS_BYTES, c->stream, A);
+        } else {
+            cge_allow_lds((const void *)link_auc_kernel<false>, LR_LDS_BYTES);
+            hipLaunchKernelGGL(link_auc_kernel<false>, grid, dim3(256), LR_LDS_BYTES, c->stream, A);
+        }
+    }
+    ScopedKernelTimer tm(c, "link_auc_final");
+    size_t bytes = 0;
+    HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, G, G, (size_t)ne, rocprim::plus<unsigned long long>(), c->stream));
+    c->sort_tmp.ensure(bytes);
+    HIP_CHECK(rocprim::inclusive_scan(c->sort_tmp.p, bytes, G, G, (size_t)ne, rocprim::plus<unsigned long long>(), c->stream));
+    hipLaunchKernelGGL(link_auc_final_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c->stream, t, perm, G, E, cnt, ne, out_less,
+                       out_ties);
 }

@@ -1,5 +1,5 @@
 // link_host.cpp -- the host side of cge_link_* (include/cge_hip.h): the link model in the context, fitted by a score's own sweep
-// or supplied by the caller, its three queries and its draws (kernels_link.hip).
+// or supplied by the caller, its three queries, its draws and its exact AUC (kernels_link.hip).
 #include "common.hpp"
 
 #include <algorithm>
@@ -323,5 +323,66 @@ void host_link_sample(cge_ctx *c, i64 seed, i64 stream_id, i64 cap, int64_t *out
         }
         HIP_CHECK(hipStreamSynchronize(st));
     }
+    flush_timers(c);
+}
+
+// ---- cge_link_auc ------------------------------------------------------------------------------------------------------------------
+// The positives' values are k_link_prob's of the resident rows (the same kernel as cge_link_prob, hence the same bits), sorted on
+// the device; one launch places the negatives of this part's tiles among them, a prefix sum and a scatter give the counts in the
+// edge list's order.  One synchronisation; the three sums are taken here, in the list's order, in long double.
+void host_link_auc(cge_ctx *c, int part, int nparts, int64_t *out_less, int64_t *out_ties, double *out_p, int64_t *n_neg,
+                   double summary[3]) {
+    link_need_model(c, "link_auc");
+    link_need_inputs(c, "link_auc");
+    if (nparts < 1 || part < 0 || part >= nparts)
+        CGE_THROW(CGE_E_ARG, "link_auc: part = %d of nparts = %d (0 <= part < nparts, nparts >= 1)", part, nparts);
+    LinkModel &m = c->link;
+    const i64 ne = c->m, n = m.n;
+    hipStream_t st = c->stream;
+    // the call's scratch: values, thresholds, permutation, G and E, the two result arrays -- 56 bytes per edge, grow-only
+    const size_t e1 = (size_t)ne, e2 = 2 * (size_t)ne;
+    const size_t grow = 8 * ((m.vals.n < e1 ? e1 : 0) + (m.at.n < e1 ? e1 : 0) + (m.aperm.n < e1 ? e1 : 0) + (m.rhist.n < e2 ? e2 : 0) +
+                             (m.rout.n < e2 ? e2 : 0)); // (a buffer that grows is allocated anew)
+    if (grow) {
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if (grow > free_b)
+            CGE_THROW(CGE_E_OOM, "link_auc: %zu bytes of scratch to allocate for m = %lld edges (56 per edge) do not fit the %zu bytes free",
+                      grow, (long long)ne, free_b);
+    }
+    m.vals.ensure((size_t)ne);
+    m.at.ensure((size_t)ne);
+    m.aperm.ensure((size_t)ne);
+    m.rhist.ensure((size_t)2 * ne);
+    m.rout.ensure((size_t)2 * ne);
+    m.acnt.ensure(6);
+    host_ensure_centred(c);
+    k_link_keys(c);
+    k_link_prob(c, c->src.p, c->dst.p, ne, m.vals.p);
+    k_link_auc(c, part, nparts, m.vals.p, m.at.p, m.aperm.p, m.rhist.p, m.rhist.p + ne, m.acnt.p, m.rout.p, m.rout.p + ne);
+    std::vector<int64_t> hl, ht;
+    if (!out_less) { hl.resize((size_t)ne); out_less = hl.data(); }
+    if (!out_ties) { ht.resize((size_t)ne); out_ties = ht.data(); }
+    unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(out_less, m.rout.p, sizeof(i64) * ne, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(out_ties, m.rout.p + ne, sizeof(i64) * ne, hipMemcpyDeviceToHost, st));
+    if (out_p) HIP_CHECK(hipMemcpyAsync(out_p, m.vals.p, sizeof(double) * ne, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(cnt, m.acnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    *n_neg = (m.directed ? n * (n - 1) : n * (n - 1) / 2) - (i64)cnt[5];
+    const double *w = c->h_w.empty() ? nullptr : c->h_w.data(); // (no mirror: unit weights)
+    long double W = 0.0L, L = 0.0L, Tq = 0.0L;
+    for (i64 e = 0; e < ne; e++) {
+        const long double we = w ? (long double)w[e] : 1.0L;
+        W += we;
+        L += we * (long double)out_less[e];
+        Tq += we * (long double)out_ties[e];
+    }
+    summary[0] = (double)W;
+    summary[1] = (double)L;
+    summary[2] = (double)Tq;
+    m.stat_auc_survivors = (i64)cnt[0];
+    m.stat_auc_proven = (i64)(cnt[1] + cnt[2]);
+    m.stat_auc_tiles = (i64)cnt[4];
     flush_timers(c);
 }

@@ -186,6 +186,18 @@ function ecg(c::Ctx, n::Integer; members::Integer = 16, w_min::Real = 0.05, seed
     return comm, nc[], q[], q_ecg[]
 end
 
+# The exact link AUC of the resident link model on the resident graph of m rows (cge_link_auc, an extension): every edge row
+# against every non-edge.  (less, ties, n_neg, (W, L, Tq)); the exact local score is 1 - L / (W n_neg), the AUC
+# (L + Tq / 2) / (W n_neg).  `part` of `nparts`: a share of the pair tiles, the counts of the parts add up.
+function link_auc(c::Ctx, m::Integer; part::Integer = 0, nparts::Integer = 1)
+    less, ties = Vector{Int64}(undef, m), Vector{Int64}(undef, m)
+    nneg, summary = Ref{Int64}(0), Vector{Float64}(undef, 3)
+    check(c, ccall((:cge_link_auc, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ref{Int64}, Ptr{Float64}),
+                   c.h, part, nparts, less, ties, C_NULL, nneg, summary))
+    return less, ties, nneg[], (summary[1], summary[2], summary[3])
+end
+
 # clusters derived from the resident communities (src/auxilary.jl:199-208): n_clusters = -1, the two pointers are ignored
 function landmarks_run_from_comm!(c::Ctx, land::Int, forced::Int, method::Function, directed::Bool)
     N, ne, trunc = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)

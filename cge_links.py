@@ -16,10 +16,14 @@ of the best alpha and asks it for predictions:
     --sample FILE          instead of top-k lists: one random graph drawn from the model (every pair an edge with its probability),
                            written to FILE as `i j` rows sorted by (i, j); excludes --rank, --pairs and --queries
     --sample-seed S        the seed of that draw (default 0)
+    --auc                  instead of top-k lists: the exact local score and AUC of the kept model, every edge against every
+                           non-edge (what element 5 of the vector estimates from samples); excludes the four above
 
 stdout: the 7-vector line cge_cli.py prints, then one `i j p` line per prediction, ids in the edge file's own base (0 or 1).
 With --rank: one `i j p greater ties cand` line per pair (candidates of i other than j that the model puts above / level with j,
 and their number), then one `# ` line with MRR, Hits@K, mean rank and AUC (api.link_metrics).
+With --auc: one line `# local_exact=... auc=... pos=... neg=... survivors=...` (Context.link_auc; survivors = the pairs the
+filter left to exact evaluation).
 """
 import os
 import sys
@@ -38,8 +42,8 @@ class LinkArgError(Exception):
 
 
 def link_args(argv):
-    """The flags of this script beside cge_cli.py's: {"which", "topk", "queries", "pairs", "exclude"}, and with --sample FILE also
-    {"sample", "sample_seed"}.  Needs no GPU."""
+    """The flags of this script beside cge_cli.py's: {"which", "topk", "queries", "pairs", "exclude"}, with --sample FILE also
+    {"sample", "sample_seed"}, with --auc also {"auc"}.  Needs no GPU."""
     argv = list(argv)
 
     def value(flag):
@@ -83,6 +87,11 @@ def link_args(argv):
             raise LinkArgError(f"--sample-seed takes a number, not {seed}") from None
     elif "--sample-seed" in argv:
         raise LinkArgError("--sample-seed goes with --sample")
+    if "--auc" in argv:  # (the key "auc" is there only with the flag)
+        for other in ("--sample", "--rank", "--pairs", "--queries"):
+            if other in argv:
+                raise LinkArgError(f"--auc and {other} exclude each other")
+        out["auc"] = True
     return out
 
 
@@ -106,6 +115,12 @@ def rank_args(argv):
 def metrics_line(mt):
     """The summary line of --rank."""
     return "# " + " ".join(f"{k}={julia_float(float(v))}" for k, v in mt.items())
+
+
+def auc_line(res, survivors):
+    """The line of --auc."""
+    return (f"# local_exact={julia_float(res['local_exact'])} auc={julia_float(res['auc'])} pos={res['n_pos']} neg={res['n_neg']} "
+            f"survivors={survivors}")
 
 
 def read_ids(path, columns, base, n):
@@ -149,6 +164,10 @@ def main(argv=None):
         if len(vec) < 7:  # a directed star graph: the reference's early return leaves no model
             return 0
         out = sys.stdout
+        if la.get("auc"):
+            res = ctx.link_auc()
+            out.write(auc_line(res, ctx.get_stat("link_auc_survivors")) + "\n")
+            return 0
         if la.get("sample") is not None:
             si, sj, _, _ = ctx.link_sample(la["sample_seed"], 0)
             with open(la["sample"], "w") as f:

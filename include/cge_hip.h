@@ -447,6 +447,32 @@ int cge_link_rank(cge_ctx *ctx, const int64_t *i, const int64_t *j, int64_t P, i
  * "link_sample_tiles".                                                                                                            */
 int cge_link_sample(cge_ctx *ctx, int64_t seed, int64_t stream, int64_t cap, int64_t *out_i /* cap */, int64_t *out_j /* cap */,
                     double *out_p /* cap, may be NULL */, int64_t *n_edges);
+/* The exact link AUC of the resident model on the resident graph: what elements 5-7 of a score estimate from auc_samples draws,
+ * over ALL edges and ALL non-edges.
+ *   Positives: the m rows of the resident edge list, in the list's order; a repeated row is a repeated positive (as the sweep's
+ *              sampler draws them), a self loop is included with p(i, i) = f_out[i] * f_in[i] (dist(i, i) = 0).  p_e =
+ *              cge_link_prob's value of row e, bit for bit (out_p).
+ *   Negatives: NE, the pairs the sampler rejects against: undirected, the pairs i < j that no resident row joins in either
+ *              orientation; directed, the ordered pairs i != j with no row i -> j.  No self pairs.  *n_neg = |NE|, from the
+ *              distinct non-loop keys of the edge list.
+ *     out_less[e] = #{(a, b) in NE : p(a, b) < p_e},      out_ties[e] = #{(a, b) in NE : p(a, b) == p_e}.
+ * Every p is cge_link_prob's value and the comparisons are made on those values (the Gram formula only filters, on both sides,
+ * with bounds that cost survivors and never correctness), so the counts are a function of the inputs alone: not of the grid, the
+ * CU count, the parts or the order of the atomics.
+ * `part` of `nparts` (0 <= part < nparts; nparts = 1: everything): the call visits the positions part, part + nparts, ... of the
+ * walk of the 128 x 128 pair tiles.  The per-edge counts of the parts add up to the whole exactly; a part without tiles returns
+ * zeros; *n_neg is the whole graph's in every part.  (A caller spreads the work over several calls or, by hand, several GPUs.)
+ * summary = {W, L, Tq} = {sum w_e, sum w_e less_e, sum w_e ties_e} with the resident edge weights, accumulated on the host in the
+ * list's order in long double and rounded once.  The exact local score -- the reference's test is the strict pos > neg, so ties
+ * count against -- is 1 - L / (W n_neg); the usual AUC is (L + Tq / 2) / (W n_neg) (sums of ALL parts).  n_neg = 0: the sums are
+ * returned, the quotients are the caller's business.
+ * CGE_E_ARG, before any device work: no link model; a NULL n_neg or summary; nparts < 1 or part outside 0 .. nparts - 1; under
+ * collectives or sharding.  CGE_E_OOM with the bytes named when the scratch (56 bytes per edge) does not fit.  A non-finite
+ * embedding is unspecified, as for cge_link_topk.  DESIGN.md section 4.15.
+ * Stats: "link_auc_survivors" = pairs of the last call evaluated exactly, "link_auc_tiles", "link_auc_proven" = pairs the filter
+ * settled alone.                                                                                                                  */
+int cge_link_auc(cge_ctx *ctx, int part, int nparts, int64_t *out_less /* m, may be NULL */, int64_t *out_ties /* m, may be NULL */,
+                 double *out_p /* m, may be NULL */, int64_t *n_neg, double summary[3]);
 
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */

@@ -436,8 +436,8 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *                                 pass applies (d <= 128): both forms give the same bits;
  *   "test_device_cus"             v: v in 1 .. the device's CU count replaces the CU count that sizes this context's launches: the
  *                                 geometry of the persistent fits (G, NW, NSB and whether they apply), the packing of
- *                                 cge_score_batch (max_G = v / 2), the slices of cge_link_topk / cge_link_rank and the grid of
- *                                 cge_link_sample; 0 (default): the device's own.  It only shrinks (above the device's count:
+ *                                 cge_score_batch (max_G = v / 2), the slices of cge_link_topk / cge_link_rank and the grids of
+ *                                 cge_link_sample / cge_link_auc; 0 (default): the device's own.  It only shrinks (above the count:
  *                                 CGE_E_ARG), since a persistent fit needs its G <= v workgroups co-resident.  This one does change
  *                                 which form runs -- on purpose: the forms of chips with fewer CUs run on a large one.  The link
  *                                 queries' results do not depend on it; a fit's agree to rounding.                                */
