@@ -1574,6 +1574,25 @@ class Context:
             out["p"] = p[:m]
         return out
 
+    def link_moments(self, diag=False):
+        """The moments of the resident model over every pair, for the resident vertex communities (cge_link_moments): a
+        `LinkMoments` with deg_out / deg_in (n; one vector under both names when undirected), B = sum p and V = sum q (1 - q),
+        q = min(p, 1), per community bin in the sweep's vect_B layout, C = the sweep's vect_C of the resident edges, n_comm and
+        directed.  diag adds the self pairs p(i, i) = f_out[i] f_in[i] as the reference's exact-mode loops do.  Sums within an
+        a-priori bound of the real-number values (include/cge_hip.h), and a function of the inputs alone."""
+        nc = C.c_int64(-1)
+        self._check(self.L.cge_link_moments(self.h, C.c_int(int(bool(diag))), None, None, None, None, None, C.byref(nc)))
+        d = C.c_int()
+        self._check(self.L.cge_link_model_fetch(self.h, C.byref(d), None, None, None, None, None, None, None))
+        directed, nco = bool(d.value), int(nc.value)
+        L = nco * nco if directed else nco * (nco + 1) // 2
+        do = np.zeros(self.n)
+        di = np.zeros(self.n) if directed else do
+        B, V, Cobs = np.zeros(L), np.zeros(L), np.zeros(L)
+        self._check(self.L.cge_link_moments(self.h, C.c_int(int(bool(diag))), _p(do), _p(di) if directed else None, _p(B), _p(V),
+                                            _p(Cobs), C.byref(nc)))
+        return LinkMoments(do, di, B, V, Cobs, nco, directed)
+
     def ecg_members_test(self, members=16, seed=0):
         """Testing hook (cge_ecg_members_test): the member and peel stages of `ecg` alone -- (members (K, n) each renumbered as a
         pass is, n_comm (K,), rounds (K,), modularity (K,), core (n,) bool)."""
@@ -1848,6 +1867,75 @@ def link_auc(edge_index, embedding, comm, land, forced=4, method="rss", directed
     if len(vec) < 7:
         return vec, None
     return vec, ctx.link_auc(0, 1, want_counts, want_p)
+
+
+class LinkMoments:
+    """What `Context.link_moments` returns: deg_out, deg_in (n), B, V, C (L, the sweep's bin layout), n_comm, directed."""
+    __slots__ = ("deg_out", "deg_in", "B", "V", "C", "n_comm", "directed")
+
+    def __init__(self, deg_out, deg_in, B, V, C_, n_comm, directed):
+        self.deg_out, self.deg_in, self.B, self.V, self.C, self.n_comm, self.directed = deg_out, deg_in, B, V, C_, n_comm, directed
+
+
+def link_bin_pairs(n_comm, directed):
+    """The community pair (a, b), 1-based, of every bin of the sweep's layout: cge_idx(C, a, b) order with a <= b when
+    undirected (L = C (C + 1) / 2), (a - 1) C + b when directed (L = C C).  Returns (a, b), int64 (L,) each."""
+    nc = int(n_comm)
+    if directed:
+        a, b = np.divmod(np.arange(nc * nc, dtype=np.int64), nc)
+        return a + 1, b + 1
+    a = np.repeat(np.arange(1, nc + 1, dtype=np.int64), np.arange(nc, 0, -1))
+    b = np.concatenate([np.arange(i, nc + 1, dtype=np.int64) for i in range(1, nc + 1)]) if nc else np.zeros(0, np.int64)
+    return a, b
+
+
+def link_bins_table(B, V, C_, n_comm, directed):
+    """Per community bin the observed edge mass beside the model's: rows (a, b, observed, expected, sd, z) with observed = C[bin]
+    (the sweep's vect_C), expected = B[bin], sd = sqrt(V[bin]) and z = (observed - expected) / sd -- 0 where both the difference
+    and sd are 0, +-inf where only sd is.  V is the variance of a draw's edge COUNT, so z means something for an unweighted graph
+    only (unit edge weights: the observed mass is a count).  Returns a list of tuples in the bins' order."""
+    Bv, Vv, Cv = (np.asarray(x, dtype=np.float64).ravel() for x in (B, V, C_))
+    a, b = link_bin_pairs(n_comm, directed)
+    if not len(Bv) == len(Vv) == len(Cv) == len(a):
+        raise ValueError(f"link_bins_table: B, V, C of {len(Bv)}, {len(Vv)}, {len(Cv)} bins, the layout has {len(a)}")
+    sd = np.sqrt(np.maximum(Vv, 0.0))
+    diff = Cv - Bv
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.where(sd > 0, diff / sd, np.where(diff == 0, 0.0, np.sign(diff) * np.inf))
+    return [(int(a[k]), int(b[k]), float(Cv[k]), float(Bv[k]), float(sd[k]), float(z[k])) for k in range(len(a))]
+
+
+def link_divergence(C_, B, n_comm, directed, split, ctx=None, js=None):
+    """The Jensen-Shannon figures of a score's elements 2-4 for the bin vectors (C, B): {"global", "external", "internal"}.
+    Without split: global = JS(C, B) over all bins, the other two 0.0; with split: internal over the bins (a, a), external over
+    the others, global their mean (src/divergence.jl:235-241, :539-545).  JS is the library's (`Context.js` of ctx or the default
+    context); js = a callable (vC, vB, vI, internal) replaces it."""
+    Cv, Bv = (np.asarray(x, dtype=np.float64).ravel() for x in (C_, B))
+    a, b = link_bin_pairs(n_comm, directed)
+    if not len(Cv) == len(Bv) == len(a):
+        raise ValueError(f"link_divergence: C, B of {len(Cv)}, {len(Bv)} bins, the layout has {len(a)}")
+    if js is None:
+        js = (ctx or default_context()).js
+    if not split:
+        return {"global": float(js(Cv, Bv, None, True)), "external": 0.0, "internal": 0.0}
+    vI = (a == b).astype(np.uint8)
+    d_int, d_ext = float(js(Cv, Bv, vI, True)), float(js(Cv, Bv, vI, False))
+    return {"global": (d_int + d_ext) / 2.0, "external": d_ext, "internal": d_int}
+
+
+def link_moments(edge_index, embedding, comm, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000,
+                 which="global", diag=False, weights=None, base=-1, ctx=None):
+    """The moments of the fitted model, beside `link_auc`: the graph and the embedding go in as views, `Context.link_fit` fits
+    the model of the best alpha (by default the best divergence's), `Context.link_moments` sums it over every pair.  Returns
+    (vector, LinkMoments); a directed star graph's early return leaves (vector, None)."""
+    ctx = ctx or default_context()
+    ctx.set_graph_view(edge_index, weights, n=int(embedding.shape[0]), base=base)
+    ctx.set_vertex_view(comm, None, base=base)
+    ctx.set_embedding_view(embedding)
+    vec, _ = ctx.link_fit(FROM_COMM, land, forced, method, directed, split, seed, auc_samples, which)
+    if len(vec) < 7:
+        return vec, None
+    return vec, ctx.link_moments(diag)
 
 
 def link_sample(edge_index, embedding, comm, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000,

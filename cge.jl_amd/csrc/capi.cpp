@@ -305,6 +305,12 @@ int cge_link_auc(cge_ctx *c, int part, int nparts, int64_t *out_less, int64_t *o
     host_link_auc(c, part, nparts, out_less, out_ties, out_p, n_neg, summary);
     CGE_CATCH(c)
 }
+int cge_link_moments(cge_ctx *c, int diag, double *deg_out, double *deg_in, double *B, double *V, double *Cobs, int64_t *n_comm) {
+    if (!c || !n_comm) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_moments(c, diag, deg_out, deg_in, B, V, Cobs, n_comm);
+    CGE_CATCH(c)
+}
 // testing hook (include/cge_hip_testing.h): the same launch with the uniforms read from a caller's matrix
 int cge_link_sample_test(void *ctx, const double *U, int directed_layout, int64_t cap, int64_t *out_i, int64_t *out_j, double *out_p,
                          int64_t *n_edges) {
@@ -526,6 +532,10 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "link_auc_survivors")) *value = c->link.stat_auc_survivors; // of the last cge_link_auc: pairs evaluated exactly,
     else if (!strcmp(key, "link_auc_tiles")) *value = c->link.stat_auc_tiles;         // the tiles walked,
     else if (!strcmp(key, "link_auc_proven")) *value = c->link.stat_auc_proven;       // the pairs the filter settled alone
+    else if (!strcmp(key, "link_moments_exact")) *value = c->link.stat_mom_exact; // of the last cge_link_moments: pairs through link_p,
+    else if (!strcmp(key, "link_moments_fast")) *value = c->link.stat_mom_fast;   // pairs from the Gram value,
+    else if (!strcmp(key, "link_moments_saturated")) *value = c->link.stat_mom_saturated; // pairs with p > 1,
+    else if (!strcmp(key, "link_moments_tiles")) *value = c->link.stat_mom_tiles;         // the tiles walked
     else if (!strcmp(key, "cut_tie_tasks")) { // (read from the device on request: a synchronising copy)
         int v = 0;
         if (c->cut_ties.p && (hipStreamSynchronize(c->stream) != hipSuccess ||

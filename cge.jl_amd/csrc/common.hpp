@@ -323,6 +323,22 @@ struct LinkModel {
     DevBuf<i64> aperm;
     DevBuf<unsigned long long> acnt;
     i64 stat_auc_survivors = 0, stat_auc_tiles = 0, stat_auc_proven = 0; // of the last cge_link_auc
+    // cge_link_moments: the centred operand, its norms and the factors in community order, the call's tables (i32 and i64), the
+    // items' row / column partials and bin partials, the counters, the outputs (released with the model: link_drop)
+    DevBuf<double> mXp, mrp, mf, mrow, mbin, mout;
+    DevBuf<i32> mtab;
+    DevBuf<i64> moff;
+    DevBuf<unsigned long long> mcnt;
+    i64 stat_mom_exact = 0, stat_mom_fast = 0, stat_mom_saturated = 0, stat_mom_tiles = 0; // of the last cge_link_moments
+};
+// the tables of one cge_link_moments call on the device (link_host.cpp builds them, kernels_link.hip reads them)
+struct LinkMomentsTables {
+    const i32 *perm, *rank;       // position -> vertex; position -> rank of its community among those present
+    const i32 *isi, *isj;         // the work items' blocks
+    const i32 *bfr, *bnc;         // per block: first rank, ranks
+    const i32 *cid, *rb0, *rb1;   // per rank: community (0-based), first and last block
+    const i64 *boff;              // per item: first bin slot
+    i64 wb, nT, nB, items, slots, Cp, C;
 };
 
 struct cge_ctx {
@@ -1113,6 +1129,9 @@ void k_link_auc(cge_ctx *c, int part, int nparts, const double *p, double *t, i6
                 unsigned long long *cnt, i64 *out_less, i64 *out_ties);
 void k_link_sample_finish(cge_ctx *c, const unsigned long long *keys_in, unsigned long long *keys, i64 ne, i32 *pi, i32 *pj, i64 *oi,
                           i64 *oj);
+i64 k_link_moments_wb(i64 nT); // tiles a block edge of cge_link_moments' work items, from the tile count alone
+// the sums of the model over every pair (LinkModel's m* buffers sized by the caller): deg (n, directed 2 n), B and V (L each)
+void k_link_moments(cge_ctx *c, const LinkMomentsTables &T, double *deg, double *B, double *V, i64 L, unsigned long long *cnt);
 // ---- host modules -----------------------------------------------------------------------------
 // landmarks_host.cpp
 void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
@@ -1136,6 +1155,9 @@ void host_ensure_centred(cge_ctx *c); // Xc / rnorm: the centred feature-major c
 // link_host.cpp: what the cge_link_* entry points do, and the sweep's side of cge_link_fit
 static inline void link_drop(cge_ctx *c) {
     c->link.valid = false; c->link.keys_ready = false; c->link.excl_ready = false; c->link.fib_ready = false; c->link.lf_ready = false;
+    // cge_link_moments' scratch (an operand as large as Xc, partials of O(n * blocks)) goes with the model
+    c->link.mXp.release(); c->link.mrp.release(); c->link.mf.release(); c->link.mrow.release(); c->link.mbin.release();
+    c->link.mout.release();
 }
 // a sweep that cge_link_fit runs calls this when alpha has just become the best of the wanted kind: Ta / Tb (N each, the sweep's
 // numbering; old2new un-permutes a relabelled sweep) are copied aside on the stream
@@ -1151,6 +1173,7 @@ void host_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, int e
                     int64_t *out_ties, int64_t *out_cand, double *out_p);
 void host_link_auc(cge_ctx *c, int part, int nparts, int64_t *out_less, int64_t *out_ties, double *out_p, int64_t *n_neg,
                    double summary[3]);
+void host_link_moments(cge_ctx *c, int diag, double *deg_out, double *deg_in, double *B, double *V, double *Cobs, int64_t *n_comm);
 // U != nullptr: cge_link_sample_test (n x n host doubles in the place of the counter stream)
 void host_link_sample(cge_ctx *c, i64 seed, i64 stream_id, i64 cap, int64_t *out_i, int64_t *out_j, double *out_p, int64_t *n_edges,
                       const double *U, int directed_layout);

@@ -2,7 +2,8 @@
 // probability of given pairs, per query the k most probable candidates, and the exact rank of given pairs among their query's
 // candidates (link_rank_kernel: top-k's tiles and filter stage with thresholds known before the first tile), and draws of the random
 // graph the model is (link_sample_kernel: max_pair_kernel's walk of all pair tiles, a filter of its own), and the exact link AUC
-// (link_auc_kernel, at the end: the same walk, rank's filter, every non-edge placed among the edges' sorted values).  gfx950 only.
+// (link_auc_kernel: the same walk, rank's filter, every non-edge placed among the edges' sorted values), and the model's sums over
+// every pair (link_moments_kernel, at the end: expected degrees and community bins in fixed-order partials).  gfx950 only.
 //
 //     p(i, j) = (f_out[i] * f_in[j]) * max(0, 1 - dist(i, j) / hi) ^ alpha
 //
@@ -1196,4 +1197,330 @@ void k_link_auc(cge_ctx *c, int part, int nparts, const double *p, double *t, i6
     HIP_CHECK(rocprim::inclusive_scan(c->sort_tmp.p, bytes, G, G, (size_t)ne, rocprim::plus<unsigned long long>(), c->stream));
     hipLaunchKernelGGL(link_auc_final_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c->stream, t, perm, G, E, cnt, ne, out_less,
                        out_ties);
+}
+
+// ---- cge_link_moments -------------------------------------------------------------------------------------------------------------
+// The sums of the model over EVERY pair: per vertex the expected degrees, per community pair the expected edge mass B = sum p and
+// the variance of a draw's edge count V = sum q (1 - q), q = min(p, 1).  The vertices are ordered by community first (host:
+// stable, ids ascending inside a community) and the centred operand is gathered in that order (k_gather_centre_fm), so a
+// 128 x 128 tile meets a handful of (row segment, column segment) rectangles, and in the undirected walk i < j by position has
+// c_i <= c_j.
+//
+// Geometry, fixed by n alone.  The tiles are grouped in blocks of wb x wb (link_moments_wb(nT)); a WORK ITEM is one block (SI, SJ)
+// -- undirected SJ >= SI and inside it only the tiles J >= I, in a diagonal tile only the pairs i < j.  Workgroups take items by
+// stride; an item's partials are its own:
+//   * rowp / colp: wb x 128 doubles each, the row sums and column sums of its tiles.  A row tile's sums are accumulated over the
+//     item's column tiles in LDS by the thread of the row and stored once; a column's are added to the item's own global slot by
+//     the thread of the column, tile after tile (one thread, one address: program order).
+//   * Bp / Vp: one slot per (community of the row block, community of the column block) and WAVE; lane 0 of a wave adds its
+//     rectangle sums to its own slot, tile after tile.
+// Inside a tile every sum has a fixed shape: a lane adds its 16 x 4 values in index order, lanes are combined by xor butterflies,
+// the two waves of a row (column) in wave order.  link_moments_deg_kernel / link_moments_bin_kernel add the items' partials per
+// vertex and per bin in item order.  No floating-point atomic anywhere; device_cus() decides how many workgroups run, never which
+// terms meet in which partial: the result is a function of the inputs alone.  The counters are integer atomics.
+//
+// Per pair: fast where safe, exact where not.  g is the Gram value, r_i, r_j the squared norms, e = (K + 16) 2^-52 the bound
+// |g - d^2| <= e (r_i + r_j) derived at pcent_kernel (kernels_dist.hip).
+//   (a) g - e (r_i + r_j) > hi^2 (1 + 1e-12): the distance is above hi by more than dist()'s own (K / 2 + 3) 2^-53, the base
+//       is clamped, p = 0 exactly as link_p gives it (only under a supplied hi below the diameter);
+//   (b) g >= theta (r_i + r_j) and b = 1 - sqrt(g) / hi >= beta, theta = beta = 2^-10: pw = pow(b, alpha).  g is within e / theta
+//       of d^2 relatively, its root within e / (2 theta), x = d / hi <= 1 within the same absolutely, so the base is off by at most
+//       e / (2 theta) (+ 3 ulp) and the power by  alpha e / (2 theta)  for alpha >= 1 (the derivative alpha b^(alpha - 1) <= alpha)
+//       and  alpha (beta / 2)^(alpha - 1) e / (2 theta)  for alpha < 1 (both bases are above beta / 2).  At K = 512 that is
+//       6e-11 alpha, resp. 6e-11 alpha (beta / 2)^(alpha - 1) = 4.6e-9 at alpha = 0.25.  (Against a reference that takes dist()
+//       in fp64, that sum's own (d + 6) 2^-52 joins e: tests/link_moments_ref.py, 9.1e-9 at d = 512, alpha = 0.25);
+//   (c) every other pair -- coincident and near points (g below theta (r_i + r_j): no relative bound), pairs at the diameter
+//       (b below beta: the power's derivative is unbounded for alpha < 1) -- goes through link_p from the rows.
+// The power is the library pow in every case.  The bound is ABSOLUTE per pair, c f_out[i] f_in[j]: a bin of far-apart
+// communities has a tiny sum and the same tolerance per pair; that is what a Gram-based sum can promise.
+//
+// Registers: pow inlined 64 times over the accumulators is what spills link_topk_kernel's epilogue.  Here a wave parks a quarter
+// of its accumulators (16 values a lane) in the Gram staging, free between two tiles, and a rolled loop of 16 evaluates them one
+// at a time -- the only state across the loop is the three counters -- then takes the values back: four copies of pow in the
+// code, not 64, and the 64 p live where the dot products lived.
+struct LinkMoments {
+    const double *Xp, *rp; i64 ldn, n, dpad; // the centred feature-major operand in community order, its squared norms
+    const double *Xr; i64 d;                 // the rows as dist() reads them (original ids)
+    const i32 *perm;                         // position -> vertex
+    const double *fo, *fi;                   // the factors by position
+    const i32 *rank;                         // by position: the community's rank among the communities present
+    int wb; i64 nT, nB, items;               // tiles a block edge, tiles, blocks, work items
+    const i32 *isi, *isj;                    // the items' blocks
+    const i32 *bfr, *bnc;                    // per block: its first rank, its ranks
+    const i64 *boff;                         // per item: its first bin slot
+    double *rowp, *colp, *Bp, *Vp;
+    unsigned long long *cnt;                 // [0] exact, [1] fast, [2] p > 1, [3] tiles
+    double hi, hi2, alpha, einfl, theta, beta;
+    int directed;
+};
+#define LM_LDS_BYTES ((size_t)2 * 2 * MP_BK * MP_LD * sizeof(double) + (size_t)(5 * 128 + 128) * sizeof(double))
+
+__device__ __forceinline__ i64 link_moments_item(i64 SI, i64 SJ, i64 nB, int directed) {
+    return directed ? SI * nB + SJ : SI * nB - SI * (SI - 1) / 2 + (SJ - SI);
+}
+
+__global__ __launch_bounds__(256, 2) void link_moments_kernel(LinkMoments A) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *rqs = lds + (size_t)2 * 2 * MP_BK * MP_LD, *fos = rqs + 128, *rcs = fos + 128, *fis = rcs + 128, *racc = fis + 128;
+    int *rkr = reinterpret_cast<int *>(racc + 128), *rkc = rkr + 128;
+    double *rs = lds + 4096, *cs = rs + 256; // in the Gram staging, behind the waves' 4 x 1024 parked values
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4, c2 = lane * 2;
+    const i64 nchunk = A.dpad / MP_BK;
+    double *mybuf = lds + wave * 1024 + lane;
+    unsigned long long nexact = 0, nfast = 0, nsat = 0, ntile = 0;
+    for (i64 it = blockIdx.x; it < A.items; it += gridDim.x) {
+        const i64 SI = A.isi[it], SJ = A.isj[it];
+        const i64 I0 = SI * A.wb, I1 = I0 + A.wb < A.nT ? I0 + A.wb : A.nT;
+        const i64 J0 = SJ * A.wb, J1 = J0 + A.wb < A.nT ? J0 + A.wb : A.nT;
+        const int frI = A.bfr[SI], frJ = A.bfr[SJ], ncJ = A.bnc[SJ];
+        const i64 slot0 = A.boff[it];
+        for (i64 I = I0; I < I1; I++) {
+            const i64 i0 = I * MP_BM;
+            if (tid < 128) racc[tid] = 0.0; // (the thread's own: read and written by no other)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            for (i64 J = (!A.directed && I > J0) ? I : J0; J < J1; J++) {
+                const i64 j0 = J * MP_BN;
+                d4 acc[4][4];
+                gram_tile_128(A.Xp + (i64)wave * A.ldn + i0 + c2, A.Xp + (i64)wave * A.ldn + j0 + c2, A.ldn, A.ldn, nchunk, lds, acc, wave,
+                              c2, wr, wc, lr, lk);
+                // (gram_tile_128 ends behind a barrier, and every wave was done with the previous tile's tables before its first)
+                {
+                    const int t = tid & 127;
+                    const i64 v = (tid < 128 ? i0 : j0) + t;
+                    const bool in = v < A.n;
+                    const double r = A.rp[v]; // padded to ldn
+                    if (tid < 128) {
+                        rqs[t] = r;
+                        fos[t] = in ? A.fo[v] : 0.0;
+                        rkr[t] = in ? A.rank[v] : -1;
+                    } else {
+                        rcs[t] = r;
+                        fis[t] = in ? A.fi[v] : 0.0;
+                        rkc[t] = in ? A.rank[v] : -1;
+                    }
+                }
+                if (tid == 0) ntile++;
+                lds_sync();
+                // ---- every pair's p: acc[a][b][r] is row i0 + wr*64 + a*16 + lk + 4r, column j0 + wc*64 + b*16 + lr
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+#pragma unroll
+                    for (int b = 0; b < 4; b++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) mybuf[(b * 4 + r) * 64] = acc[a][b][r];
+#pragma unroll 1
+                    for (int t = 0; t < 16; t++) {
+                        const int il = wr * 64 + a * 16 + lk + 4 * (t & 3), jl = wc * 64 + (t >> 2) * 16 + lr;
+                        const i64 i = i0 + il, j = j0 + jl;
+                        double p = 0.0;
+                        if (i < A.n && j < A.n && (A.directed ? i != j : i < j)) {
+                            const double ri = rqs[il], rj = rcs[jl], rsum = ri + rj;
+                            const double g = gram_value(ri, rj, mybuf[t * 64]);
+                            const double fo = fos[il], fi = fis[jl];
+                            double pw = 0.0;
+                            bool fast = false;
+                            if (g - A.einfl * rsum > A.hi2) {
+                                fast = true; // (a)
+                            } else if (g >= A.theta * rsum) {
+                                const double bb = 1.0 - sqrt(g) / A.hi;
+                                if (bb >= A.beta) { // (b)
+                                    pw = pow(bb, A.alpha);
+                                    fast = true;
+                                }
+                            }
+                            if (fast) {
+                                p = (fo * fi) * pw;
+                                nfast++;
+                            } else { // (c)
+                                p = link_p<false>(A.Xr, A.d, A.perm[i], A.perm[j], fo, fi, A.hi, A.alpha);
+                                nexact++;
+                            }
+                            if (p > 1.0) nsat++;
+                        }
+                        mybuf[t * 64] = p;
+                    }
+#pragma unroll
+                    for (int b = 0; b < 4; b++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) acc[a][b][r] = mybuf[(b * 4 + r) * 64];
+                }
+                // ---- row sums and column sums of the tile
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        double s = ((acc[a][0][r] + acc[a][1][r]) + acc[a][2][r]) + acc[a][3][r];
+                        s += __shfl_xor(s, 1);
+                        s += __shfl_xor(s, 2);
+                        s += __shfl_xor(s, 4);
+                        s += __shfl_xor(s, 8);
+                        if (lr == 0) rs[wc * 128 + wr * 64 + a * 16 + lk + 4 * r] = s;
+                    }
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 4; a++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) s += acc[a][b][r];
+                    s += __shfl_xor(s, 16);
+                    s += __shfl_xor(s, 32);
+                    if (lk == 0) cs[wr * 128 + wc * 64 + b * 16 + lr] = s;
+                }
+                lds_sync();
+                if (tid < 128) {
+                    racc[tid] += rs[tid] + rs[128 + tid];
+                } else {
+                    const int t = tid - 128;
+                    double *cp = A.colp + (it * A.wb + (J - J0)) * 128 + t;
+                    *cp += cs[t] + cs[128 + t];
+                }
+                // ---- the rectangles of the tile: (rank of the rows) x (rank of the columns), each in the same fixed order
+                {
+                    const i64 nrow = A.n - i0 < 128 ? A.n - i0 : 128, ncol = A.n - j0 < 128 ? A.n - j0 : 128;
+                    const int R0 = rkr[0], R1 = rkr[nrow - 1], C0 = rkc[0], C1 = rkc[ncol - 1];
+                    int myr[4][4], myc[4];
+#pragma unroll
+                    for (int a = 0; a < 4; a++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) myr[a][r] = rkr[wr * 64 + a * 16 + lk + 4 * r];
+#pragma unroll
+                    for (int b = 0; b < 4; b++) myc[b] = rkc[wc * 64 + b * 16 + lr];
+                    for (int R = R0; R <= R1; R++)
+                        for (int Cc = (!A.directed && R > C0) ? R : C0; Cc <= C1; Cc++) {
+                            double s = 0.0, v = 0.0;
+#pragma unroll
+                            for (int a = 0; a < 4; a++)
+#pragma unroll
+                                for (int b = 0; b < 4; b++)
+#pragma unroll
+                                    for (int r = 0; r < 4; r++) {
+                                        const double pp = (myr[a][r] == R && myc[b] == Cc) ? acc[a][b][r] : 0.0;
+                                        const double q = pp > 1.0 ? 1.0 : pp;
+                                        s += pp;
+                                        v += q * (1.0 - q);
+                                    }
+#pragma unroll
+                            for (int w = 1; w < 64; w <<= 1) {
+                                s += __shfl_xor(s, w);
+                                v += __shfl_xor(v, w);
+                            }
+                            if (lane == 0) {
+                                const i64 slot = (slot0 + (i64)(R - frI) * ncJ + (Cc - frJ)) * 4 + wave;
+                                A.Bp[slot] += s;
+                                A.Vp[slot] += v;
+                            }
+                        }
+                }
+                // (the next tile's staging is written behind gram_tile_128's first barrier: every wave has read rs / cs by then)
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+            if (tid < 128) A.rowp[(it * A.wb + (I - I0)) * 128 + tid] = racc[tid];
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        nexact += __shfl_xor(nexact, s);
+        nfast += __shfl_xor(nfast, s);
+        nsat += __shfl_xor(nsat, s);
+    }
+    if (lane == 0) {
+        if (nexact) atomicAdd(A.cnt, nexact);
+        if (nfast) atomicAdd(A.cnt + 1, nfast);
+        if (nsat) atomicAdd(A.cnt + 2, nsat);
+        if (wave == 0 && ntile) atomicAdd(A.cnt + 3, ntile);
+    }
+}
+
+// the degrees: per position the items' row partials in item order, then their column partials; written to the vertex's own id
+__global__ void link_moments_deg_kernel(LinkMoments A, double *__restrict__ deg_out, double *__restrict__ deg_in) {
+    const i64 pos = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= A.n) return;
+    const i64 stride = (i64)A.wb * 128, S = pos / stride, off = pos - S * stride;
+    double ro = 0.0, co = 0.0;
+    for (i64 SJ = A.directed ? 0 : S; SJ < A.nB; SJ++) ro += A.rowp[link_moments_item(S, SJ, A.nB, A.directed) * stride + off];
+    for (i64 SI = 0; SI < (A.directed ? A.nB : S + 1); SI++) co += A.colp[link_moments_item(SI, S, A.nB, A.directed) * stride + off];
+    const i64 v = A.perm[pos];
+    if (A.directed) {
+        deg_out[v] = ro;
+        deg_in[v] = co;
+    } else {
+        deg_out[v] = ro + co;
+    }
+}
+// the bins: one thread per pair of present communities (ranks ra, rb; undirected ra <= rb) adds the slots of the items that hold
+// it, in item order and wave order, and writes the sweep's layout (cge_idx undirected, (c_i - 1) C + c_j directed)
+__global__ void link_moments_bin_kernel(LinkMoments A, i64 Cp, i64 C, const i32 *__restrict__ cid, const i32 *__restrict__ rb0,
+                                        const i32 *__restrict__ rb1, double *__restrict__ B, double *__restrict__ V) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= Cp * Cp) return;
+    const i64 ra = t / Cp, rb = t - ra * Cp;
+    if (!A.directed && ra > rb) return;
+    double b = 0.0, v = 0.0;
+    for (i64 SI = rb0[ra]; SI <= rb1[ra]; SI++)
+        for (i64 SJ = rb0[rb]; SJ <= rb1[rb]; SJ++) {
+            if (!A.directed && SJ < SI) continue;
+            const i64 it = link_moments_item(SI, SJ, A.nB, A.directed);
+            const i64 slot = (A.boff[it] + (ra - A.bfr[SI]) * (i64)A.bnc[SJ] + (rb - A.bfr[SJ])) * 4;
+            for (int w = 0; w < 4; w++) {
+                b += A.Bp[slot + w];
+                v += A.Vp[slot + w];
+            }
+        }
+    const i64 ca = cid[ra], cb = cid[rb];
+    const i64 at = A.directed ? ca * C + cb : C * ca - ca * (ca - 1) / 2 + (cb - ca);
+    B[at] = b;
+    V[at] = v;
+}
+__global__ void link_moments_permute_kernel(const double *__restrict__ f, const i32 *__restrict__ perm, i64 n, double *__restrict__ fs) {
+    const i64 pos = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= n) return;
+    fs[pos] = f[perm[pos]];
+    fs[n + pos] = f[n + perm[pos]];
+}
+
+// tiles a block edge: 2 while that keeps the blocks under 512 a side, else the power of two that does (16 at n = 10^6)
+i64 k_link_moments_wb(i64 nT) {
+    i64 wb = 2;
+    while ((nT + wb - 1) / wb > 512) wb *= 2;
+    return wb;
+}
+// T (link_host.cpp) holds the tables of the call, already on the device; the partials are zeroed here.  deg / B / V: device outputs
+// (deg: n, or 2 n directed; B, V: L each, zeroed here: a bin no pair falls in stays 0)
+void k_link_moments(cge_ctx *c, const LinkMomentsTables &T, double *deg, double *B, double *V, i64 L, unsigned long long *cnt) {
+    LinkModel &m = c->link;
+    const i64 n = m.n;
+    hipStream_t st = c->stream;
+    k_gather_centre_fm(c, c->Xr.p, T.perm, c->gmean.p, m.mXp.p, m.mrp.p, n, c->d, c->ldn, c->dpad);
+    hipLaunchKernelGGL(link_moments_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m.f.p, T.perm, n, m.mf.p);
+    HIP_CHECK(hipMemsetAsync(m.mrow.p, 0, sizeof(double) * 2 * T.items * T.wb * 128, st));
+    HIP_CHECK(hipMemsetAsync(m.mbin.p, 0, sizeof(double) * 8 * T.slots, st));
+    HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 4, st));
+    HIP_CHECK(hipMemsetAsync(B, 0, sizeof(double) * L, st));
+    HIP_CHECK(hipMemsetAsync(V, 0, sizeof(double) * L, st));
+    LinkMoments A{};
+    A.Xp = m.mXp.p; A.rp = m.mrp.p; A.ldn = c->ldn; A.n = n; A.dpad = c->dpad;
+    A.Xr = c->Xr.p; A.d = c->d;
+    A.perm = T.perm; A.fo = m.mf.p; A.fi = m.mf.p + n; A.rank = T.rank;
+    A.wb = (int)T.wb; A.nT = T.nT; A.nB = T.nB; A.items = T.items;
+    A.isi = T.isi; A.isj = T.isj; A.bfr = T.bfr; A.bnc = T.bnc; A.boff = T.boff;
+    A.rowp = m.mrow.p; A.colp = m.mrow.p + T.items * T.wb * 128;
+    A.Bp = m.mbin.p; A.Vp = m.mbin.p + 4 * T.slots;
+    A.cnt = cnt;
+    A.hi = m.hi; A.hi2 = m.hi * m.hi * (1.0 + 1e-12); A.alpha = m.alpha;
+    A.einfl = (double)(c->dpad + 16) * 2.220446049250313e-16; // (K + 16) 2^-52
+    A.theta = 0x1p-10; A.beta = 0x1p-10;
+    A.directed = m.directed;
+    const dim3 grid((unsigned)std::max<i64>(1, std::min<i64>(T.items, 2 * (i64)device_cus(c))));
+    {
+        ScopedKernelTimer t(c, "link_moments");
+        cge_allow_lds((const void *)link_moments_kernel, LM_LDS_BYTES);
+        hipLaunchKernelGGL(link_moments_kernel, grid, dim3(256), LM_LDS_BYTES, st, A);
+    }
+    ScopedKernelTimer t(c, "link_moments_final");
+    hipLaunchKernelGGL(link_moments_deg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, deg, deg + n);
+    const i64 cc = T.Cp * T.Cp;
+    hipLaunchKernelGGL(link_moments_bin_kernel, dim3((unsigned)((cc + 255) / 256)), dim3(256), 0, st, A, T.Cp, T.C, T.cid, T.rb0, T.rb1,
+                       B, V);
 }

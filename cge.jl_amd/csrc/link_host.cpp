@@ -386,3 +386,146 @@ void host_link_auc(cge_ctx *c, int part, int nparts, int64_t *out_less, int64_t 
     m.stat_auc_tiles = (i64)cnt[4];
     flush_timers(c);
 }
+
+// ---- cge_link_moments --------------------------------------------------------------------------------------------------------------
+// The host's part: the vertices in community order (a counting sort of the host mirror: stable, ids ascending inside a community),
+// the geometry that n alone fixes (blocks of wb x wb tiles, one work item each), per block the communities it meets and per item
+// the offset of its bin slots; then one launch and two small ones (kernels_link.hip), the outputs fetched, and the self pairs of
+// diag = 1 added here, in vertex order.  Cobs is the sweep's own vect_C pass (host_edge_scatter).
+// Scratch on the device, in bytes:  8 dpad ldn  (the operand in community order)  +  16 wb 128 items  (row and column partials;
+// items = nB (nB + 1) / 2 undirected, nB^2 directed, nB = ceil(tiles / wb): O(n nB))  +  64 slots  (bin partials, a slot per wave;
+// slots = sum over the items of ranks(SI) ranks(SJ) <= (Cp + nB)^2)  +  16 L + 44 n  (outputs, factors, tables).
+void host_link_moments(cge_ctx *c, int diag, double *deg_out, double *deg_in, double *B, double *V, double *Cobs, int64_t *n_comm) {
+    link_need_inputs(c, "link_moments");
+    link_need_model(c, "link_moments");
+    if (diag != 0 && diag != 1) CGE_THROW(CGE_E_ARG, "link_moments: diag = %d is neither 0 nor 1", diag);
+    LinkModel &m = c->link;
+    const i64 n = m.n, C = c->n_comm_max;
+    if (!c->comm.p || (i64)c->h_comm.size() != n || C <= 0)
+        CGE_THROW(CGE_E_ARG, "link_moments: no resident communities (cge_set_vertex_data)");
+    *n_comm = C;
+    if (!deg_out && !deg_in && !B && !V && !Cobs) return;
+    const int directed = m.directed;
+    const i64 L = directed ? C * C : C * (C + 1) / 2;
+    hipStream_t st = c->stream;
+    // ---- the order and the geometry
+    const i64 nT = (n + 127) / 128, wb = k_link_moments_wb(nT), nB = (nT + wb - 1) / wb, bs = wb * 128;
+    const i64 items = directed ? nB * nB : nB * (nB + 1) / 2;
+    std::vector<i64> start((size_t)C + 1, 0);
+    for (i64 v = 0; v < n; v++) start[(size_t)c->h_comm[v] + 1]++;
+    i64 Cp = 0;
+    for (i64 q = 0; q < C; q++) {
+        Cp += start[(size_t)q + 1] > 0;
+        start[(size_t)q + 1] += start[(size_t)q];
+    }
+    // one i32 table: perm (n), rank (n), isi, isj (items each), bfr, bnc (nB each), cid, rb0, rb1 (Cp each)
+    const size_t o_perm = 0, o_rank = (size_t)n, o_isi = 2 * (size_t)n, o_isj = o_isi + (size_t)items, o_bfr = o_isj + (size_t)items,
+                 o_bnc = o_bfr + (size_t)nB, o_cid = o_bnc + (size_t)nB, o_rb0 = o_cid + (size_t)Cp, o_rb1 = o_rb0 + (size_t)Cp,
+                 ntab = o_rb1 + (size_t)Cp;
+    std::vector<i32> tab(ntab);
+    std::vector<i64> boff((size_t)items);
+    {
+        std::vector<i64> next(start.begin(), start.end() - 1);
+        for (i64 v = 0; v < n; v++) tab[o_perm + (size_t)next[(size_t)c->h_comm[v]]++] = (i32)v;
+        i64 r = -1;
+        for (i64 q = 0; q < C; q++) {
+            if (start[(size_t)q + 1] == start[(size_t)q]) continue;
+            r++;
+            tab[o_cid + (size_t)r] = (i32)q;
+            tab[o_rb0 + (size_t)r] = (i32)(start[(size_t)q] / bs);
+            tab[o_rb1 + (size_t)r] = (i32)((start[(size_t)q + 1] - 1) / bs);
+            for (i64 p = start[(size_t)q]; p < start[(size_t)q + 1]; p++) tab[o_rank + (size_t)p] = (i32)r;
+        }
+        for (i64 S = 0; S < nB; S++) {
+            const i64 first = tab[o_rank + (size_t)(S * bs)], last = tab[o_rank + (size_t)std::min(n - 1, (S + 1) * bs - 1)];
+            tab[o_bfr + (size_t)S] = (i32)first;
+            tab[o_bnc + (size_t)S] = (i32)(last - first + 1);
+        }
+    }
+    i64 slots = 0;
+    {
+        i64 it = 0;
+        for (i64 SI = 0; SI < nB; SI++)
+            for (i64 SJ = directed ? 0 : SI; SJ < nB; SJ++, it++) {
+                tab[o_isi + (size_t)it] = (i32)SI;
+                tab[o_isj + (size_t)it] = (i32)SJ;
+                boff[(size_t)it] = slots;
+                slots += (i64)tab[o_bnc + (size_t)SI] * tab[o_bnc + (size_t)SJ];
+            }
+    }
+    // ---- the scratch
+    const size_t nXp = (size_t)c->ldn * (size_t)c->dpad, nrow = 2 * (size_t)items * (size_t)bs, nbin = 8 * (size_t)slots,
+                 nout = 2 * (size_t)n + 2 * (size_t)L;
+    const size_t grow = 8 * ((m.mXp.n < nXp ? nXp : 0) + (m.mrow.n < nrow ? nrow : 0) + (m.mbin.n < nbin ? nbin : 0) +
+                             (m.mout.n < nout ? nout : 0) + (m.mf.n < 2 * (size_t)n ? 2 * (size_t)n : 0));
+    if (grow) {
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if (grow > free_b)
+            CGE_THROW(CGE_E_OOM,
+                      "link_moments: %zu bytes of scratch to allocate (8 dpad ldn + 16 wb 128 items + 64 slots + 16 L + 32 n: wb = %lld, "
+                      "items = %lld, slots = %lld, L = %lld) do not fit the %zu bytes free",
+                      grow, (long long)wb, (long long)items, (long long)slots, (long long)L, free_b);
+    }
+    host_ensure_centred(c);
+    m.mXp.ensure(nXp);
+    m.mrp.ensure((size_t)c->ldn);
+    m.mf.ensure(2 * (size_t)n);
+    m.mrow.ensure(nrow);
+    m.mbin.ensure(nbin);
+    m.mout.ensure(nout);
+    m.mtab.ensure(ntab);
+    m.moff.ensure((size_t)items);
+    m.mcnt.ensure(4);
+    HIP_CHECK(hipMemcpyAsync(m.mtab.p, tab.data(), sizeof(i32) * ntab, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.moff.p, boff.data(), sizeof(i64) * items, hipMemcpyHostToDevice, st));
+    LinkMomentsTables T{};
+    T.perm = m.mtab.p + o_perm; T.rank = m.mtab.p + o_rank; T.isi = m.mtab.p + o_isi; T.isj = m.mtab.p + o_isj;
+    T.bfr = m.mtab.p + o_bfr; T.bnc = m.mtab.p + o_bnc; T.cid = m.mtab.p + o_cid; T.rb0 = m.mtab.p + o_rb0; T.rb1 = m.mtab.p + o_rb1;
+    T.boff = m.moff.p;
+    T.wb = wb; T.nT = nT; T.nB = nB; T.items = items; T.slots = slots; T.Cp = Cp; T.C = C;
+    double *d_deg = m.mout.p, *d_B = m.mout.p + 2 * n, *d_V = d_B + L;
+    k_link_moments(c, T, d_deg, d_B, d_V, L, m.mcnt.p);
+    // ---- the outputs
+    std::vector<double> h_deg((size_t)(directed ? 2 * n : n)), h_B, h_V, h_f;
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    const bool bins = B || V;
+    HIP_CHECK(hipMemcpyAsync(h_deg.data(), d_deg, sizeof(double) * h_deg.size(), hipMemcpyDeviceToHost, st));
+    if (bins) {
+        h_B.resize((size_t)L);
+        h_V.resize((size_t)L);
+        HIP_CHECK(hipMemcpyAsync(h_B.data(), d_B, sizeof(double) * L, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_V.data(), d_V, sizeof(double) * L, hipMemcpyDeviceToHost, st));
+    }
+    if (diag) {
+        h_f.resize(2 * (size_t)n);
+        HIP_CHECK(hipMemcpyAsync(h_f.data(), m.f.p, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipMemcpyAsync(cnt, m.mcnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st)); // (the host tables above are borrowed by the copies until here)
+    i64 sat = (i64)cnt[2];
+    if (diag) { // p(i, i) = f_out[i] f_in[i]: once to deg_out (directed: and to deg_in), once to the bin (c_i, c_i), in vertex order
+        for (i64 v = 0; v < n; v++) {
+            const double p = h_f[(size_t)v] * h_f[(size_t)(n + v)], q = p > 1.0 ? 1.0 : p;
+            const i64 q0 = c->h_comm[(size_t)v];
+            const i64 at = directed ? q0 * C + q0 : C * q0 - q0 * (q0 - 1) / 2;
+            h_deg[(size_t)v] += p;
+            if (directed) h_deg[(size_t)(n + v)] += p;
+            if (bins) {
+                h_B[(size_t)at] += p;
+                h_V[(size_t)at] += q * (1.0 - q);
+            }
+            sat += p > 1.0;
+        }
+    }
+    if (deg_out) std::copy(h_deg.begin(), h_deg.begin() + n, deg_out);
+    if (deg_in) std::copy(h_deg.begin() + (directed ? n : 0), h_deg.begin() + (directed ? 2 * n : n), deg_in);
+    if (B) std::copy(h_B.begin(), h_B.end(), B);
+    if (V) std::copy(h_V.begin(), h_V.end(), V);
+    m.stat_mom_exact = (i64)cnt[0];
+    m.stat_mom_fast = (i64)cnt[1];
+    m.stat_mom_saturated = sat;
+    m.stat_mom_tiles = (i64)cnt[3];
+    flush_timers(c);
+    if (Cobs) host_edge_scatter(c, nullptr, 1, C, directed, 0, c->m, nullptr, Cobs);
+}

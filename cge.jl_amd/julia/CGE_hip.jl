@@ -198,6 +198,20 @@ function link_auc(c::Ctx, m::Integer; part::Integer = 0, nparts::Integer = 1)
     return less, ties, nneg[], (summary[1], summary[2], summary[3])
 end
 
+# The moments of the resident link model over every pair, for the resident communities of n vertices (cge_link_moments, an
+# extension): (deg_out, deg_in, B, V, Cobs, n_comm) -- expected degrees, per community bin (the sweep's vect_B layout) the expected
+# edge mass, the variance of a draw's edge count and the sweep's vect_C.  diag adds the self pairs as the exact-mode loops do.
+function link_moments(c::Ctx, n::Integer, directed::Bool; diag::Bool = false)
+    nc = Ref{Int64}(0)
+    sig = (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64})
+    check(c, ccall((:cge_link_moments, LIB), Cint, sig, c.h, diag, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, nc))
+    L = directed ? nc[] * nc[] : nc[] * (nc[] + 1) ÷ 2
+    dout, din = Vector{Float64}(undef, n), Vector{Float64}(undef, n)
+    B, V, Cobs = Vector{Float64}(undef, L), Vector{Float64}(undef, L), Vector{Float64}(undef, L)
+    check(c, ccall((:cge_link_moments, LIB), Cint, sig, c.h, diag, dout, din, B, V, Cobs, nc))
+    return dout, din, B, V, Cobs, nc[]
+end
+
 # clusters derived from the resident communities (src/auxilary.jl:199-208): n_clusters = -1, the two pointers are ignored
 function landmarks_run_from_comm!(c::Ctx, land::Int, forced::Int, method::Function, directed::Bool)
     N, ne, trunc = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)

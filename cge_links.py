@@ -19,11 +19,20 @@ of the best alpha and asks it for predictions:
     --auc                  instead of top-k lists: the exact local score and AUC of the kept model, every edge against every
                            non-edge (what element 5 of the vector estimates from samples); excludes the four above
 
+    --moments FILE         instead of top-k lists: the model summed over EVERY pair (Context.link_moments): per community bin the
+                           observed edge mass, the model's expectation, its standard deviation and z, written to FILE as
+                           `a b observed expected sd z` rows; --which defaults to global; excludes the five above
+    --degrees FILE         with --moments: `v weight expected_out [expected_in]` per vertex (its weight beside the model's
+                           expected degree), written to FILE
+
 stdout: the 7-vector line cge_cli.py prints, then one `i j p` line per prediction, ids in the edge file's own base (0 or 1).
 With --rank: one `i j p greater ties cand` line per pair (candidates of i other than j that the model puts above / level with j,
 and their number), then one `# ` line with MRR, Hits@K, mean rank and AUC (api.link_metrics).
 With --auc: one line `# local_exact=... auc=... pos=... neg=... survivors=...` (Context.link_auc; survivors = the pairs the
 filter left to exact evaluation).
+With --moments: one line `# global_vertex=... global_sweep=... alpha=... which=...`: the Jensen-Shannon divergence between the
+observed bins and the model's bins summed over all vertex pairs, beside element 2 of the vector (in landmark mode that one sums
+landmark pairs: the difference is what the landmark approximation costs the global score).
 """
 import os
 import sys
@@ -54,7 +63,7 @@ def link_args(argv):
             raise LinkArgError(f"{flag} needs a value")
         return argv[i + 1]
 
-    which = value("--which") or "local"
+    which = value("--which") or ("global" if "--moments" in argv else "local")
     if which not in ("local", "global"):
         raise LinkArgError(f"--which is local or global, not {which}")
     topk = value("--topk")
@@ -92,6 +101,16 @@ def link_args(argv):
             if other in argv:
                 raise LinkArgError(f"--auc and {other} exclude each other")
         out["auc"] = True
+    if "--moments" in argv:  # (the keys "moments" / "degrees" are there only with the flag)
+        out["moments"] = value("--moments")
+        if out["moments"] is None:
+            raise LinkArgError("--moments needs a value")
+        for other in ("--auc", "--sample", "--rank", "--pairs", "--queries"):
+            if other in argv:
+                raise LinkArgError(f"--moments and {other} exclude each other")
+        out["degrees"] = value("--degrees")
+    elif "--degrees" in argv:
+        raise LinkArgError("--degrees goes with --moments")
     return out
 
 
@@ -121,6 +140,12 @@ def auc_line(res, survivors):
     """The line of --auc."""
     return (f"# local_exact={julia_float(res['local_exact'])} auc={julia_float(res['auc'])} pos={res['n_pos']} neg={res['n_neg']} "
             f"survivors={survivors}")
+
+
+def moments_line(global_vertex, global_sweep, alpha, which):
+    """The line of --moments."""
+    return (f"# global_vertex={julia_float(float(global_vertex))} global_sweep={julia_float(float(global_sweep))} "
+            f"alpha={julia_float(float(alpha))} which={which}")
 
 
 def read_ids(path, columns, base, n):
@@ -167,6 +192,20 @@ def main(argv=None):
         if la.get("auc"):
             res = ctx.link_auc()
             out.write(auc_line(res, ctx.get_stat("link_auc_survivors")) + "\n")
+            return 0
+        if la.get("moments") is not None:
+            mo = ctx.link_moments()
+            gv = api.link_divergence(mo.C, mo.B, mo.n_comm, mo.directed, split, ctx=ctx)["global"]
+            out.write(moments_line(gv, vec[1], ctx.link_model()["alpha"], la["which"]) + "\n")
+            with open(la["moments"], "w") as f:
+                for a, b, obs, exp, sd, z in api.link_bins_table(mo.B, mo.V, mo.C, mo.n_comm, mo.directed):
+                    f.write(f"{a} {b} {julia_float(obs)} {julia_float(exp)} {julia_float(sd)} {julia_float(z)}\n")
+            if la.get("degrees") is not None:
+                vw = np.asarray(vweights, dtype=np.float64).ravel()
+                with open(la["degrees"], "w") as f:
+                    for v in range(n):
+                        tail = f" {julia_float(float(mo.deg_in[v]))}" if mo.directed else ""
+                        f.write(f"{v + base} {julia_float(float(vw[v]))} {julia_float(float(mo.deg_out[v]))}{tail}\n")
             return 0
         if la.get("sample") is not None:
             si, sj, _, _ = ctx.link_sample(la["sample_seed"], 0)

@@ -473,6 +473,31 @@ int cge_link_sample(cge_ctx *ctx, int64_t seed, int64_t stream, int64_t cap, int
  * settled alone.                                                                                                                  */
 int cge_link_auc(cge_ctx *ctx, int part, int nparts, int64_t *out_less /* m, may be NULL */, int64_t *out_ties /* m, may be NULL */,
                  double *out_p /* m, may be NULL */, int64_t *n_neg, double summary[3]);
+/* The moments of the resident model over EVERY pair, for the resident vertex communities: the global counterpart of cge_link_auc.
+ * p(i, j) is the model's probability (cge_link_prob's definition) and q = min(p, 1) what cge_link_sample draws with.
+ *   deg_out[i] = sum_{j != i} p(i, j),  deg_in[j] = sum_{i != j} p(i, j)  (undirected: one vector; either pointer or both).
+ *   Bins: L = C (C + 1) / 2 undirected in cge_idx(C, min, max) order, L = C * C directed at (comm[i] - 1) * C + comm[j] -- the
+ *   layout of the sweep's vect_B / vect_C (src/divergence.jl:55-62, :337-344, :532-537).  C = the largest resident community,
+ *   returned in *n_comm.  B[bin] = sum p over the unordered pairs i < j (directed: ordered pairs i != j) whose communities fall in
+ *   the bin; V[bin] = sum q (1 - q) over the same pairs, the variance of a draw's edge count there; a bin no pair falls in is 0.
+ *   Cobs = the sweep's vect_C of the resident edge list on the vertex communities, by the sweep's own pass.
+ * diag = 1 adds the self pairs, as the reference's exact-mode loops do (j in i:no_vertices, :153-158, :229-233): p(i, i) =
+ * f_out[i] f_in[i] once to deg_out[i] (directed: and once to deg_in[i]), once to B of bin (c_i, c_i), q (1 - q) of it to V.  On a
+ * model left by an exact-mode cge_link_fit(CGE_LINK_BEST_GLOBAL), B with diag = 1 is the sweep's vect_B at the reported alpha.
+ * Accuracy: these are sums, NOT defined bit for bit against cge_link_prob.  A pair far enough from coincidence and from the
+ * diameter takes its distance from the Gram value of the centred rows; every other pair goes through cge_link_prob's arithmetic.
+ * An output that sums the pair set S is within  c sum_S f_out[i] f_in[j]  of the real-number sum, c below 1e-8 for every alpha
+ * >= 0.25 and d <= 512 (DESIGN.md section 4.16 derives it) -- an ABSOLUTE bound per pair: a bin of far-apart communities has a
+ * tiny sum and the same tolerance.  The outputs ARE a function of the inputs alone: not of the CU count, the grid or the order in
+ * which workgroups finish (fixed work items, fixed-order sums, no floating-point atomics).
+ * CGE_E_ARG, before any device work: no link model; no resident communities; a NULL n_comm; diag other than 0 / 1; under
+ * collectives or sharding.  Every output NULL but n_comm: returns C, no device work.  CGE_E_OOM with the bytes named when the
+ * scratch -- 8 dpad ldn + 16 wb 128 items + 64 slots + 16 L + 32 n bytes, section 4.16 -- does not fit.
+ * Stats: "link_moments_exact" = pairs evaluated by cge_link_prob's arithmetic, "link_moments_fast" = pairs evaluated from the Gram
+ * value (the two add up to the pairs), "link_moments_saturated" = pairs with p > 1 (informational), "link_moments_tiles".        */
+int cge_link_moments(cge_ctx *ctx, int diag, double *deg_out /* n, may be NULL */, double *deg_in /* n, may be NULL */,
+                     double *B /* L, may be NULL */, double *V /* L, may be NULL */, double *Cobs /* L, may be NULL */,
+                     int64_t *n_comm);
 
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */
