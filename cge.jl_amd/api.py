@@ -156,7 +156,7 @@ class SweepSetupIO(C.Structure):
 class LocalScoreIO(C.Structure):
     """cge_local_score_io (include/cge_hip_testing.h): the arguments of the testing hook cge_local_score_test."""
     _fields_ = [("S", C.c_int64), ("seed", C.c_int64), ("stream_id", C.c_int64), ("directed", C.c_int32),
-                ("draw_route", C.c_int32), ("form", C.c_int32), ("pad", C.c_int32),
+                ("draw_route", C.c_int32), ("form", C.c_int32), ("sharded", C.c_int32),
                 ("pos", C.c_void_p), ("neg_i", C.c_void_p), ("neg_j", C.c_void_p), ("attempt", C.c_void_p), ("rounds", C.c_int64),
                 ("pos_in", C.c_void_p), ("pos2_in", C.c_void_p), ("neg_i_in", C.c_void_p), ("neg_j_in", C.c_void_p),
                 ("pi", C.c_void_p), ("pj", C.c_void_p), ("ni", C.c_void_p), ("nj", C.c_void_p), ("wts", C.c_void_p),
@@ -1258,7 +1258,7 @@ class Context:
         return out
 
     def local_score_test(self, S, directed=False, draw=None, draws=None, pos2=None, pairs=None, prepare=False, hi=None,
-                         distances=False, dists=None, tally=None):
+                         distances=False, dists=None, tally=None, sharded=False):
         """Testing hook (include/cge_hip_testing.h: cge_local_score_test): the stages of the local score on the resident graph
         and embedding; every id is 0-based.
           draw = (seed, stream_id, route): the device sampler (route 1 k_draw_samples_dev, 2 _begin + _finish) -> pos, neg_i,
@@ -1268,10 +1268,12 @@ class Context:
           dists = (dpos, dneg): supplied distances for the tally;
           tally = dict(form (5: k_auc_exact on the packed tiles with ordered pairs), N, alpha, Ta, Tb, v2l, vw, lweight, old2new, GD, D, w, T0, eps, delta) -> part (64, 2), out2 and,
             form 4, T, aidx (4, S), afac (8, S), aden (64,), iters, status.
+          sharded=True: the opt-in of a context whose rows or edges are sharded over ranks -- Draw, Prepare and Distances run
+            collectively (every rank calls with the same arguments; ids stay global); the tally forms stay refused there.
         Returns a dict of what the stages that were asked for give."""
         S = int(S)
         io, out, keep = LocalScoreIO(), {}, []
-        io.S, io.directed = S, int(bool(directed))
+        io.S, io.directed, io.sharded = S, int(bool(directed)), int(bool(sharded))
 
         def give(key, a, dtype):
             if a is None:

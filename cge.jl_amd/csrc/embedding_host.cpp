@@ -53,6 +53,15 @@ static void rows_assign_ownership(cge_ctx *c) {
         c->comm_owner[q] = r;
         load[r] += size[q];
     }
+    // A rank without a row cannot take part; EVERY rank refuses then (the loads are the same on every rank), so that no rank
+    // goes on into the all-reduce of the column sums while another has left with an error.  Nothing stays resident.
+    const int starved = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+    if (load[starved] <= 0) {
+        c->Xr.release(); c->h_Xr.clear();
+        c->d = 0;
+        rows_unshard(c);
+        CGE_THROW(CGE_E_ARG, "option shard_rows: fewer communities than ranks (rank %d would own no row)", starved);
+    }
     const int me = c->coll.rank;
     c->h_glob2loc.assign(n, -1);
     c->h_loc2glob.clear();
@@ -63,7 +72,6 @@ static void rows_assign_ownership(cge_ctx *c) {
             c->h_loc2glob.push_back((i32)i);
         }
     c->n_loc = (i64)c->h_loc2glob.size();
-    if (c->n_loc <= 0) CGE_THROW(CGE_E_ARG, "option shard_rows: fewer communities than ranks (rank %d would own no row)", me);
     c->loc2glob.alloc_exact(c->n_loc);
     c->glob2loc.alloc_exact(n);
     HIP_CHECK(hipMemcpyAsync(c->loc2glob.p, c->h_loc2glob.data(), sizeof(i32) * c->n_loc, hipMemcpyHostToDevice, c->stream));

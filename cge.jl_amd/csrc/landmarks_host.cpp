@@ -1523,6 +1523,21 @@ void forced_over_ranks(cge_ctx *c, std::vector<Local> &locals, const i64 *cl_off
             }
             if (at != cl_off[L.cidx + 1]) CGE_THROW(CGE_E_ASSERT, "forced phase: groups do not cover their community");
         }
+        // A community of at most `forced` rows owns no local heap and no rank answers for it -- yet the start of the arena is
+        // rewritten from the gathered words below, and the merge reads its members there.  Rank 0 enters them as they were
+        // staged: the ranges of [0, total) that no local heap covers.  (Without this they came back as zeros: vertex 0 in
+        // their place, and the landmark index found a row in two groups.)
+        if (me == 0) {
+            std::vector<std::pair<i64, i64>> held;
+            for (const Local &L : locals) held.emplace_back(cl_off[L.cidx], cl_off[L.cidx + 1]);
+            std::sort(held.begin(), held.end());
+            i64 at = 0;
+            for (const auto &r : held) {
+                if (r.first > at) { G.seg.push_back(at); G.seg.push_back(at); G.seg.push_back(r.first - at); }
+                at = std::max(at, r.second);
+            }
+            if (at < total) { G.seg.push_back(at); G.seg.push_back(at); G.seg.push_back(total - at); }
+        }
     });
     G.run(c, err, "forced phase (sharded)");
     // every rank: communities back into the start of the arena, one means block, fresh groups

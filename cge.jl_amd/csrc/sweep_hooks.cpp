@@ -718,7 +718,8 @@ static void ls_range(const char *what, const i32 *v, i64 cnt, i64 lim) {
 
 void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
     hipStream_t st = c->stream;
-    const i64 S = io->S, n = c->n, m = c->m, N = io->N;
+    const i64 S = io->S, n = c->n, N = io->N;
+    const i64 m = c->edges_sharded ? c->m_total : c->m; // (a sharded list: pos / pos_in are rows of the caller's whole list)
     const int directed = io->directed != 0, form = io->form;
     const bool landmark_form = form == 1 || form == 4, exact_form = form == 2 || form == 3 || form == 5;
     // the stages that run
@@ -729,8 +730,10 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
     const bool prep = io->pi || io->pj || io->ni || io->nj || io->wts || ((dist || form != 0) && !pairs_in);
     // ---- the checks --------------------------------------------------------------------------------------------------------------
     if (S < 1 || S >= ((i64)1 << 28)) CGE_THROW(CGE_E_ARG, "local_score_test: S = %lld samples", (long long)S);
-    if (c->rows_sharded || c->edges_sharded)
-        CGE_THROW(CGE_E_ARG, "local_score_test: not with option shard_rows / shard_ingest (every row and edge on one rank)");
+    if ((c->rows_sharded || c->edges_sharded) && !io->sharded)
+        CGE_THROW(CGE_E_ARG, "local_score_test: not with option shard_rows / shard_ingest (every row and edge on one rank), unless sharded = 1");
+    if ((c->rows_sharded || c->edges_sharded) && form != 0) // (sharded = 1: Draw, Prepare and Distances run collectively)
+        CGE_THROW(CGE_E_ARG, "local_score_test: the tally forms are refused under option shard_rows / shard_ingest (form = %d)", form);
     if ((draw || prep) && (!c->src.p || !c->dst.p || m <= 0 || n < 2 || (!c->unit_weights && !c->w.p)))
         CGE_THROW(CGE_E_ARG, "local_score_test: the graph is not resident (cge_set_graph)");
     if (prep && pairs_in) CGE_THROW(CGE_E_ARG, "local_score_test: the pairs are prepared or supplied, not both");
@@ -743,7 +746,7 @@ void host_local_score_test(cge_ctx *c, cge_local_score_io *io) {
     if ((io->dpos_in != nullptr) != (io->dneg_in != nullptr)) CGE_THROW(CGE_E_ARG, "local_score_test: dpos_in and dneg_in go together");
     if (io->dpos_in && form == 0) CGE_THROW(CGE_E_ARG, "local_score_test: dpos_in and dneg_in go with a tally");
     if ((landmark_form || dist) && n < 1) CGE_THROW(CGE_E_ARG, "local_score_test: nothing is resident");
-    if (dist && (!c->Xr.p || c->d <= 0 || c->Xr.n < (size_t)(n * c->d)))
+    if (dist && (!c->Xr.p || c->d <= 0 || c->Xr.n < (size_t)(lm_rows(c) * c->d)))
         CGE_THROW(CGE_E_ARG, "local_score_test: the embedding is not resident (cge_set_embedding)");
     if (dist && !(io->hi > 0.0)) CGE_THROW(CGE_E_ARG, "local_score_test: hi = %g (the distances are divided by it)", io->hi);
     if (form != 0 && (N < 1 || N > 46340)) CGE_THROW(CGE_E_ARG, "local_score_test: N = %lld", (long long)N);

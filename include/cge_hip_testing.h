@@ -237,21 +237,32 @@ int cge_fit_test(void *ctx, cge_fit_problem *problems, int n_problems, int direc
  *             w, T0 (sweep order), alpha, eps, delta.  Also out: T[N] = the iterate the launch left, aidx[4 S], afac[8 S],
  *             aden[64] as prepared, iters, status (1: the launch was abandoned -- part stays NaN); out2 is added on the host in
  *             block order, as the sweep's host does.
+ *   sharded (default 0): a context whose rows or edges are sharded over ranks (options shard_rows / shard_ingest with collectives
+ *   set) is refused.  sharded = 1 opts in: Draw, Prepare and Distances then run COLLECTIVELY -- every rank calls with the same
+ *   arguments -- through the same wrappers, which dispatch to the exchange variants (collect_hit_kernel / check_neg_flag_kernel
+ *   and the flag all-reduce of a round, prep_lookup_sharded_kernel / prep_store_sharded_kernel, pair_dist_rows_kernel behind the
+ *   row exchange of sampled_pair_dist).  Every id stays GLOBAL: pos and pos_in / pos2_in are rows of the caller's whole edge
+ *   list (range-checked against the total count, not this rank's share), pair ids are vertices, and every rank receives the
+ *   full outputs.  A check that fails does so on every rank alike (the arguments are the same), before the first exchange.  The
+ *   Tally forms stay refused on a sharded context, with or without the flag.  On a context that is not sharded the flag does
+ *   nothing.
  * CGE_E_ARG with a message, before any launch: S < 1, a missing resident (graph for Draw / Prepare, embedding for Distances), a
- * context with option shard_rows or shard_ingest, a row of pos_in / pos2_in outside the edge list, a pair id outside the
- * vertices (the landmark forms and the distances: n; forms 2, 3: N, and N = n on prepared pairs), v2l or old2new outside
+ * context with option shard_rows or shard_ingest (unless sharded = 1 and form == 0), a row of pos_in / pos2_in outside the edge
+ * list, a pair id outside the vertices (the landmark forms and the distances: n; forms 2, 3: N, and N = n on prepared pairs), v2l or old2new outside
  * 0..N-1 or old2new not a permutation, a stage without its inputs or with two sources of them, hi <= 0, N outside 1..46340,
  * forms 3, 4 directed, form 4 with eps <= 0 or delta < 0, without option "pow_exp2" or where the geometry of the fused fit
  * declines N.  The draw itself returns CGE_E_ARG ("could not find enough non-edges") when a sample is still an edge after 64
  * rounds; the context stays usable.
- * Not covered here: the exchange variants of options shard_rows / shard_ingest (pair_dist_rows_kernel, prep_*_sharded_kernel,
- * check_neg_flag_kernel) need a communicator and stay with tests/test_gpu_two_ranks.py; the multi-problem launch shares the
+ * The exchange variants of options shard_rows / shard_ingest (pair_dist_rows_kernel, prep_*_sharded_kernel, collect_hit_kernel,
+ * check_neg_flag_kernel) need a communicator: tests/test_gpu_ranks_small.py drives them through `sharded` on 2, 3 and 5 ranks.
+ * Not covered here: the tallies split over ranks (tests/test_gpu_two_ranks.py and the whole-run cases of
+ * tests/test_gpu_ranks_small.py hold them through the score); the multi-problem launch shares the
  * epilogue body and tests/test_gpu_batch.py holds its members to the single launch bit for bit; form 4 asks for the tally alone
  * -- the epilogue's vect_B, alone or beside the tally, and the multi-problem launch on supplied operands are
  * cge_fused_chain_test's. */
 typedef struct cge_local_score_io {
     int64_t S, seed, stream_id;
-    int32_t directed, draw_route, form, pad;
+    int32_t directed, draw_route, form, sharded;
     /* Draw */
     int32_t *pos, *neg_i, *neg_j;
     uint32_t *attempt;
@@ -374,7 +385,7 @@ int cge_packed_gd_test(void *ctx, const double *emb /* N x d row-major, host */,
  * behind the degree pass and the upload of the layout's tables (the verdict is the layout's own), log_form 3 where the layout
  * declines the tiles.  The hook sets no option.
  * Not covered here: the packed form of an exact sweep, which never stores D (cge_packed_gd_test has it), and the sharded set-up
- * (tests/test_gpu_two_ranks.py). */
+ * (the whole runs of tests/test_gpu_two_ranks.py and tests/test_gpu_ranks_small.py). */
 typedef struct cge_sweep_setup_io {
     const double *emb, *dist, *vw;
     const int64_t *comm;
