@@ -1595,6 +1595,28 @@ class Context:
                                             _p(Cobs), C.byref(nc)))
         return LinkMoments(do, di, B, V, Cobs, nco, directed)
 
+    def link_triangles(self, model=True, graph=True):
+        """Expected and observed triangles and wedges per vertex (cge_link_triangles; undirected models only).  Returns
+        (tri_exp, wed_exp, tri_obs, wed_obs, summary): float64 (n,) twice -- q = min(p, 1) of the resident model, the draws'
+        probability --, int64 (n,) twice -- the resident edge list as a simple undirected graph --, and summary = the four sums
+        (long double on the host, rounded once).  model = False / graph = False skips that half: its arrays are None and its
+        sums 0.  The model half holds an (n padded)^2 matrix of doubles on the device."""
+        n = int(self.n)
+        te, we = (np.zeros(n), np.zeros(n)) if model else (None, None)
+        to, wo = (np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)) if graph else (None, None)
+        summ = np.zeros(4)
+        self._check(self.L.cge_link_triangles(self.h, _p(te) if model else None, _p(we) if model else None,
+                                              _p(to) if graph else None, _p(wo) if graph else None, _p(summ)))
+        return te, we, to, wo, summ
+
+    def link_triangles_test(self):
+        """Testing hook (cge_link_triangles_test): the matrix Q of the model half, (ld, ld) with ld = 128 (ceil(n / 128) | 1),
+        n <= 2048."""
+        ld = 128 * (((int(self.n) + 127) // 128) | 1)
+        Q = np.zeros((ld, ld))
+        self._check(self.L.cge_link_triangles_test(self.h, _p(Q), C.c_int64(ld)))
+        return Q
+
     def ecg_members_test(self, members=16, seed=0):
         """Testing hook (cge_ecg_members_test): the member and peel stages of `ecg` alone -- (members (K, n) each renumbered as a
         pass is, n_comm (K,), rounds (K,), modularity (K,), core (n,) bool)."""
@@ -1938,6 +1960,46 @@ def link_moments(edge_index, embedding, comm, land, forced=4, method="rss", dire
     if len(vec) < 7:
         return vec, None
     return vec, ctx.link_moments(diag)
+
+
+def link_clustering_table(tri_exp, wed_exp, tri_obs, wed_obs, summary, comm=None):
+    """What `link_clustering` derives from `Context.link_triangles`' arrays: {"tri_exp", "wed_exp", "tri_obs", "wed_obs",
+    "c_exp" = tri_exp / wed_exp and "c_obs" = tri_obs / wed_obs per vertex (NaN where there are no wedges), "transitivity_exp" =
+    summary[0] / summary[1], "transitivity_obs" = summary[2] / summary[3] (NaN for a zero wedge sum), "triangles_exp" /
+    "triangles_obs" = the sums / 3, "summary"}; with comm (n, ids in any base) also "communities" (the distinct ids ascending) and
+    "by_community" ((len, 4): per community the sums of tri_obs, wed_obs, tri_exp, wed_exp over its vertices)."""
+    te, we = np.asarray(tri_exp, dtype=np.float64), np.asarray(wed_exp, dtype=np.float64)
+    to, wo = np.asarray(tri_obs, dtype=np.int64), np.asarray(wed_obs, dtype=np.int64)
+    s = [float(x) for x in summary]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c_exp = np.where(we > 0, te / we, np.nan)
+        c_obs = np.where(wo > 0, to / np.where(wo > 0, wo, 1), np.nan)
+    out = {"tri_exp": te, "wed_exp": we, "tri_obs": to, "wed_obs": wo, "c_exp": c_exp, "c_obs": c_obs, "summary": np.array(s),
+           "transitivity_exp": s[0] / s[1] if s[1] > 0 else float("nan"),
+           "transitivity_obs": s[2] / s[3] if s[3] > 0 else float("nan"), "triangles_exp": s[0] / 3.0, "triangles_obs": s[2] / 3.0}
+    if comm is not None:
+        ids, inv = np.unique(np.asarray(comm).ravel(), return_inverse=True)
+        if len(inv) != len(te):
+            raise ValueError(f"link_clustering_table: comm has {len(inv)} entries, the arrays {len(te)}")
+        out["communities"] = ids
+        out["by_community"] = np.stack([np.bincount(inv, weights=x.astype(np.float64), minlength=len(ids))
+                                        for x in (to, wo, te, we)], axis=1)
+    return out
+
+
+def link_clustering(edge_index, embedding, comm, land, forced=4, method="rss", split=False, seed=-1, auc_samples=10000,
+                    which="local", weights=None, base=-1, ctx=None):
+    """How much of the graph's clustering the fitted model explains, beside `link_moments`: the graph and the embedding go in as
+    views, `Context.link_fit` fits the (undirected) model of the best alpha, `Context.link_triangles` gives expected and observed
+    triangles and wedges per vertex.  Returns (vector, `link_clustering_table`'s dict with the per-community sums)."""
+    ctx = ctx or default_context()
+    ctx.set_graph_view(edge_index, weights, n=int(embedding.shape[0]), base=base)
+    ctx.set_vertex_view(comm, None, base=base)
+    ctx.set_embedding_view(embedding)
+    vec, _ = ctx.link_fit(FROM_COMM, land, forced, method, False, split, seed, auc_samples, which)
+    if len(vec) < 7:
+        return vec, None
+    return vec, link_clustering_table(*ctx.link_triangles(), comm=_host_array(comm))
 
 
 def link_sample(edge_index, embedding, comm, land, forced=4, method="rss", directed=False, split=False, seed=-1, auc_samples=10000,

@@ -311,6 +311,20 @@ int cge_link_moments(cge_ctx *c, int diag, double *deg_out, double *deg_in, doub
     host_link_moments(c, diag, deg_out, deg_in, B, V, Cobs, n_comm);
     CGE_CATCH(c)
 }
+int cge_link_triangles(cge_ctx *c, double *tri_exp, double *wed_exp, int64_t *tri_obs, int64_t *wed_obs, double summary[4]) {
+    if (!c || !summary) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_triangles(c, tri_exp, wed_exp, tri_obs, wed_obs, summary);
+    CGE_CATCH(c)
+}
+// testing hook (include/cge_hip_testing.h): the matrix Q the model half works on
+int cge_link_triangles_test(void *ctx, double *Q_out, int64_t ld) {
+    cge_ctx *c = (cge_ctx *)ctx;
+    if (!c || !Q_out) return CGE_E_ARG;
+    CGE_TRY_ON_DEVICE(c)
+    host_link_triangles_q(c, Q_out, ld);
+    CGE_CATCH(c)
+}
 // testing hook (include/cge_hip_testing.h): the same launch with the uniforms read from a caller's matrix
 int cge_link_sample_test(void *ctx, const double *U, int directed_layout, int64_t cap, int64_t *out_i, int64_t *out_j, double *out_p,
                          int64_t *n_edges) {
@@ -536,6 +550,9 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "link_moments_fast")) *value = c->link.stat_mom_fast;   // pairs from the Gram value,
     else if (!strcmp(key, "link_moments_saturated")) *value = c->link.stat_mom_saturated; // pairs with p > 1,
     else if (!strcmp(key, "link_moments_tiles")) *value = c->link.stat_mom_tiles;         // the tiles walked
+    else if (!strcmp(key, "link_tri_tiles")) *value = c->link.stat_tri_tiles; // of the last cge_link_triangles: 128 x 128 tiles walked,
+    else if (!strcmp(key, "link_tri_saturated")) *value = c->link.stat_tri_saturated;     // pairs i < j with p > 1,
+    else if (!strcmp(key, "link_tri_matrix_bytes")) *value = c->link.stat_tri_bytes;      // the bytes of Q
     else if (!strcmp(key, "cut_tie_tasks")) { // (read from the device on request: a synchronising copy)
         int v = 0;
         if (c->cut_ties.p && (hipStreamSynchronize(c->stream) != hipSuccess ||

@@ -330,6 +330,14 @@ struct LinkModel {
     DevBuf<i64> moff;
     DevBuf<unsigned long long> mcnt;
     i64 stat_mom_exact = 0, stat_mom_fast = 0, stat_mom_saturated = 0, stat_mom_tiles = 0; // of the last cge_link_moments
+    // cge_link_triangles: the matrix Q (tld x tld, tld = k_link_tri_ld(n)), the tiles' row / column partials, the two outputs
+    // (tri, wed), the counters (saturated pairs, long edges); the graph side's distinct degrees, triangle counts, oriented keys as
+    // made and sorted, list offsets and long edges (released with the model: link_drop)
+    DevBuf<double> tQ, tpart, tout;
+    DevBuf<unsigned long long> tcnt, ttri, tokeys_in, tokeys;
+    DevBuf<i32> tdeg;
+    DevBuf<i64> toff, tlong;
+    i64 stat_tri_tiles = 0, stat_tri_saturated = 0, stat_tri_bytes = 0; // of the last cge_link_triangles
 };
 // the tables of one cge_link_moments call on the device (link_host.cpp builds them, kernels_link.hip reads them)
 struct LinkMomentsTables {
@@ -1132,6 +1140,15 @@ void k_link_sample_finish(cge_ctx *c, const unsigned long long *keys_in, unsigne
 i64 k_link_moments_wb(i64 nT); // tiles a block edge of cge_link_moments' work items, from the tile count alone
 // the sums of the model over every pair (LinkModel's m* buffers sized by the caller): deg (n, directed 2 n), B and V (L each)
 void k_link_moments(cge_ctx *c, const LinkMomentsTables &T, double *deg, double *B, double *V, i64 L, unsigned long long *cnt);
+// kernels_linktri.hip: expected and observed triangles of the link model
+i64 k_link_tri_ld(i64 n); // Q's leading dimension: n padded to an odd number of 128-tiles
+void k_link_tri_q(cge_ctx *c, double *Q, i64 ld, unsigned long long *sat); // Q = min(p, 1), zero diagonal and padding; *sat = pairs p > 1
+// tri[v] = rowsum(Q o (Q Q))[v] / 2 through the partials `part` (nT^2 128, nT = ceil(n / 128)), wed[v] = sum_{j<k} q_vj q_vk; either
+// output may be nullptr (its kernels are not launched).  Returns the 128 x 128 tiles walked
+i64 k_link_tri_expected(cge_ctx *c, const double *Q, i64 ld, double *part, double *tri, double *wed);
+// the resident edge list as a simple undirected graph: deg (n) = distinct neighbours, tri (n) = triangles through the vertex
+void k_link_tri_observed(cge_ctx *c, i32 *deg, unsigned long long *tri, unsigned long long *okeys_in, unsigned long long *okeys,
+                         i64 *off, i64 *lng, unsigned long long *nlng);
 // ---- host modules -----------------------------------------------------------------------------
 // landmarks_host.cpp
 void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i64 nland, i64 forced, int method,
@@ -1158,6 +1175,9 @@ static inline void link_drop(cge_ctx *c) {
     // cge_link_moments' scratch (an operand as large as Xc, partials of O(n * blocks)) goes with the model
     c->link.mXp.release(); c->link.mrp.release(); c->link.mf.release(); c->link.mrow.release(); c->link.mbin.release();
     c->link.mout.release();
+    // and cge_link_triangles' (Q is 8 tld^2 bytes)
+    c->link.tQ.release(); c->link.tpart.release(); c->link.tout.release(); c->link.tokeys_in.release(); c->link.tokeys.release();
+    c->link.tlong.release(); c->link.tdeg.release(); c->link.ttri.release(); c->link.toff.release();
 }
 // a sweep that cge_link_fit runs calls this when alpha has just become the best of the wanted kind: Ta / Tb (N each, the sweep's
 // numbering; old2new un-permutes a relabelled sweep) are copied aside on the stream
@@ -1174,6 +1194,8 @@ void host_link_rank(cge_ctx *c, const int64_t *i, const int64_t *j, i64 P, int e
 void host_link_auc(cge_ctx *c, int part, int nparts, int64_t *out_less, int64_t *out_ties, double *out_p, int64_t *n_neg,
                    double summary[3]);
 void host_link_moments(cge_ctx *c, int diag, double *deg_out, double *deg_in, double *B, double *V, double *Cobs, int64_t *n_comm);
+void host_link_triangles(cge_ctx *c, double *tri_exp, double *wed_exp, int64_t *tri_obs, int64_t *wed_obs, double summary[4]);
+void host_link_triangles_q(cge_ctx *c, double *Q_out, i64 ld); // cge_link_triangles_test: Q of n <= 2048 vertices, copied out
 // U != nullptr: cge_link_sample_test (n x n host doubles in the place of the counter stream)
 void host_link_sample(cge_ctx *c, i64 seed, i64 stream_id, i64 cap, int64_t *out_i, int64_t *out_j, double *out_p, int64_t *n_edges,
                       const double *U, int directed_layout);

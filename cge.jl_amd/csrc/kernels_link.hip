@@ -27,7 +27,7 @@
 // scratch (128 rows x 64 entries x 12 bytes do not fit beside the 73.7 KB of Gram staging twice per CU); after the first tile
 // insertions are rare.  A second kernel merges the slices' lists per query under the same order.
 #include "mfma_tile.hpp"
-#include "pow_parts.hpp"
+#include "link_p.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -38,36 +38,7 @@
 // link_rank_kernel: erow, arow, asure, rq (128 doubles each) and the 128 x 4 words of the mask
 #define LR_LDS_BYTES ((size_t)2 * 2 * MP_BK * MP_LD * sizeof(double) + (size_t)(4 * 128 + 256) * sizeof(double))
 
-// dist(i, j) of the resident rows in pair_dist_kernel's arithmetic: ascending k, unfused; 0 for equal indices
-__device__ __forceinline__ double link_dist(const double *__restrict__ Xr, i64 d, i64 i, i64 j) {
-    if (i == j) return 0.0;
-    const double *a = Xr + i * d, *b = Xr + j * d;
-    double s = 0.0;
-    for (i64 q = 0; q < d; q++) {
-        const double df = __dsub_rn(a[q], b[q]);
-        s = __dadd_rn(s, __dmul_rn(df, df));
-    }
-    return sqrt(s);
-}
-// the power of the model: EXP2 = the per-element chain of the power matrix (log_parts + exp2_parts), else the library pow as
-// auc_landmark_kernel takes it; the base clamped at 0 (x > 1: only under a supplied hi below the diameter)
-template <bool EXP2>
-__device__ __forceinline__ double link_power(double x, double alpha) {
-    if (EXP2) {
-        double Lh;
-        float Ll;
-        log_parts(x > 1.0 ? 1.0 : x, Lh, Ll);
-        return exp2_parts(alpha, Lh, Ll);
-    }
-    const double b = 1.0 - x;
-    return pow(b < 0.0 ? 0.0 : b, alpha);
-}
-template <bool EXP2>
-__device__ __forceinline__ double link_p(const double *__restrict__ Xr, i64 d, i64 i, i64 j, double fo, double fi, double hi,
-                                         double alpha) {
-    const double x = link_dist(Xr, d, i, j) / hi;
-    return (fo * fi) * link_power<EXP2>(x, alpha);
-}
+// (link_dist, link_power, link_p -- the one definition of the value -- and lds_sync: link_p.hpp)
 
 // ---- the factors of a fitted model ------------------------------------------------------------------------------------------------
 __global__ void link_expand_kernel(const double *__restrict__ Ta, const double *__restrict__ Tb, const i32 *__restrict__ v2l,
@@ -209,11 +180,6 @@ __device__ __forceinline__ double link_radius2(double tau, double den, double hi
 }
 // (p, j) before (q, l) in the lists' total order
 __device__ __forceinline__ bool link_before(double p, i32 j, double q, i32 l) { return p > q || (p == q && j < l); }
-
-__device__ __forceinline__ void lds_sync() { // (the LDS stores of this wave have landed before the barrier: tests/test_device_asm.py)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-}
 
 // ---- the filter stage of the tiled queries (top-k and rank): ONE copy ---------------------------------------------------------------
 // this tile's thresholds from the rows' tau and the tile's largest f_in, the rows' share of the rounding bound added

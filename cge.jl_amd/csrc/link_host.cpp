@@ -529,3 +529,106 @@ void host_link_moments(cge_ctx *c, int diag, double *deg_out, double *deg_in, do
     flush_timers(c);
     if (Cobs) host_edge_scatter(c, nullptr, 1, C, directed, 0, c->m, nullptr, Cobs);
 }
+
+// ---- cge_link_triangles ------------------------------------------------------------------------------------------------------------
+// Model half: Q (8 tld^2 bytes, tld = n padded to an odd number of 128-tiles), the tiles' partials (8 nT^2 128 = tld^2 / 16 bytes at
+// most) and two vectors; one generator launch, one triangle launch and its small final, one wedge launch.  Graph half: the sorted
+// keys of the model, 24 bytes per edge of oriented keys and long edges, 20 per vertex.  One synchronisation; the four sums are
+// taken here in vertex order in long double.
+static i64 link_tri_make_q(cge_ctx *c, const char *who, size_t extra_doubles) {
+    LinkModel &m = c->link;
+    const i64 ld = k_link_tri_ld(m.n);
+    const size_t nQ = (size_t)ld * (size_t)ld;
+    const size_t grow = 8 * ((m.tQ.n < nQ ? nQ : 0) + extra_doubles);
+    if (grow) {
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if (grow > free_b)
+            CGE_THROW(CGE_E_OOM, "%s: %zu bytes to allocate for n = %lld (Q: 8 ld^2 with ld = %lld, plus the partials 8 * 128 nT^2) do "
+                      "not fit the %zu bytes free", who, grow, (long long)m.n, (long long)ld, free_b);
+    }
+    m.tQ.ensure(nQ);
+    m.tcnt.ensure(2);
+    k_link_tri_q(c, m.tQ.p, ld, m.tcnt.p);
+    return ld;
+}
+void host_link_triangles(cge_ctx *c, double *tri_exp, double *wed_exp, int64_t *tri_obs, int64_t *wed_obs, double summary[4]) {
+    link_need_inputs(c, "link_triangles");
+    link_need_model(c, "link_triangles");
+    LinkModel &m = c->link;
+    if (m.directed)
+        CGE_THROW(CGE_E_ARG, "link_triangles: the model is directed; triangles and wedges are defined for undirected models only");
+    const i64 n = m.n, ne = c->m;
+    hipStream_t st = c->stream;
+    const bool model = tri_exp || wed_exp, graph = tri_obs || wed_obs;
+    std::vector<double> h_t, h_w;
+    std::vector<unsigned long long> h_tri;
+    std::vector<i32> h_deg;
+    unsigned long long sat = 0;
+    m.stat_tri_tiles = 0;
+    m.stat_tri_saturated = 0;
+    m.stat_tri_bytes = 0;
+    if (model) {
+        const i64 nT = (n + 127) / 128;
+        const size_t npart = (size_t)nT * (size_t)nT * 128;
+        const i64 ld = link_tri_make_q(c, "link_triangles", (m.tpart.n < npart ? npart : 0) + (m.tout.n < 2 * (size_t)n ? 2 * (size_t)n : 0));
+        m.tpart.ensure(npart);
+        m.tout.ensure(2 * (size_t)n);
+        m.stat_tri_tiles = k_link_tri_expected(c, m.tQ.p, ld, m.tpart.p, tri_exp ? m.tout.p : nullptr, wed_exp ? m.tout.p + n : nullptr);
+        m.stat_tri_bytes = (i64)(8 * (size_t)ld * (size_t)ld);
+        if (tri_exp) {
+            h_t.resize((size_t)n);
+            HIP_CHECK(hipMemcpyAsync(h_t.data(), m.tout.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        }
+        if (wed_exp) {
+            h_w.resize((size_t)n);
+            HIP_CHECK(hipMemcpyAsync(h_w.data(), m.tout.p + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipMemcpyAsync(&sat, m.tcnt.p, sizeof(sat), hipMemcpyDeviceToHost, st));
+    }
+    if (graph) {
+        m.tdeg.ensure((size_t)n);
+        m.ttri.ensure((size_t)n);
+        m.toff.ensure((size_t)n + 1);
+        m.tokeys_in.ensure((size_t)ne);
+        m.tokeys.ensure((size_t)ne);
+        m.tlong.ensure((size_t)ne);
+        m.tcnt.ensure(2);
+        k_link_tri_observed(c, m.tdeg.p, m.ttri.p, m.tokeys_in.p, m.tokeys.p, m.toff.p, m.tlong.p, m.tcnt.p + 1);
+        h_tri.resize((size_t)n);
+        h_deg.resize((size_t)n);
+        HIP_CHECK(hipMemcpyAsync(h_tri.data(), m.ttri.p, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_deg.data(), m.tdeg.p, sizeof(i32) * n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    long double S[4] = {0.0L, 0.0L, 0.0L, 0.0L};
+    for (i64 v = 0; v < n; v++) {
+        if (tri_exp) S[0] += (long double)(tri_exp[v] = h_t[(size_t)v]);
+        if (wed_exp) S[1] += (long double)(wed_exp[v] = h_w[(size_t)v]);
+        if (graph) {
+            const i64 k = h_deg[(size_t)v], t = (i64)h_tri[(size_t)v], w = k * (k - 1) / 2;
+            if (tri_obs) tri_obs[v] = t;
+            if (wed_obs) wed_obs[v] = w;
+            S[2] += (long double)t;
+            S[3] += (long double)w;
+        }
+    }
+    for (int q = 0; q < 4; q++) summary[q] = (double)S[q];
+    m.stat_tri_saturated = (i64)sat;
+    flush_timers(c);
+}
+void host_link_triangles_q(cge_ctx *c, double *Q_out, i64 ld) {
+    link_need_inputs(c, "link_triangles_test");
+    link_need_model(c, "link_triangles_test");
+    LinkModel &m = c->link;
+    if (m.directed) CGE_THROW(CGE_E_ARG, "link_triangles_test: the model is directed; undirected models only");
+    if (m.n > 2048) CGE_THROW(CGE_E_ARG, "link_triangles_test: n = %lld is beyond the hook's 2048 vertices", (long long)m.n);
+    const i64 ldq = k_link_tri_ld(m.n);
+    if (ld != ldq)
+        CGE_THROW(CGE_E_ARG, "link_triangles_test: ld = %lld, Q of n = %lld has leading dimension %lld", (long long)ld, (long long)m.n,
+                  (long long)ldq);
+    link_tri_make_q(c, "link_triangles_test", 0);
+    HIP_CHECK(hipMemcpyAsync(Q_out, m.tQ.p, sizeof(double) * ldq * ldq, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    flush_timers(c);
+}

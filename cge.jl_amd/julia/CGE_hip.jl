@@ -212,6 +212,18 @@ function link_moments(c::Ctx, n::Integer, directed::Bool; diag::Bool = false)
     return dout, din, B, V, Cobs, nc[]
 end
 
+# Expected and observed triangles and wedges per vertex of the resident undirected link model and graph of n vertices
+# (cge_link_triangles, an extension): (tri_exp, wed_exp, tri_obs, wed_obs, summary) -- summary = the four sums; transitivity is
+# summary[1] / summary[2] (model) and summary[3] / summary[4] (graph).
+function link_triangles(c::Ctx, n::Integer)
+    te, we = Vector{Float64}(undef, n), Vector{Float64}(undef, n)
+    to, wo = Vector{Int64}(undef, n), Vector{Int64}(undef, n)
+    summary = Vector{Float64}(undef, 4)
+    check(c, ccall((:cge_link_triangles, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                   c.h, te, we, to, wo, summary))
+    return te, we, to, wo, summary
+end
+
 # clusters derived from the resident communities (src/auxilary.jl:199-208): n_clusters = -1, the two pointers are ignored
 function landmarks_run_from_comm!(c::Ctx, land::Int, forced::Int, method::Function, directed::Bool)
     N, ne, trunc = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)

@@ -24,6 +24,9 @@ of the best alpha and asks it for predictions:
                            `a b observed expected sd z` rows; --which defaults to global; excludes the five above
     --degrees FILE         with --moments: `v weight expected_out [expected_in]` per vertex (its weight beside the model's
                            expected degree), written to FILE
+    --clustering FILE      instead of top-k lists: expected and observed triangles and wedges per vertex (Context.link_triangles;
+                           undirected only), written to FILE as `v tri_obs wed_obs tri_exp wed_exp` rows, v 1-based; excludes
+                           the six above
 
 stdout: the 7-vector line cge_cli.py prints, then one `i j p` line per prediction, ids in the edge file's own base (0 or 1).
 With --rank: one `i j p greater ties cand` line per pair (candidates of i other than j that the model puts above / level with j,
@@ -33,6 +36,8 @@ filter left to exact evaluation).
 With --moments: one line `# global_vertex=... global_sweep=... alpha=... which=...`: the Jensen-Shannon divergence between the
 observed bins and the model's bins summed over all vertex pairs, beside element 2 of the vector (in landmark mode that one sums
 landmark pairs: the difference is what the landmark approximation costs the global score).
+With --clustering: one line `# transitivity_obs=... transitivity_exp=... triangles_obs=... triangles_exp=...` (transitivity = sum of
+the triangle column / sum of the wedge column, triangles = sum of the triangle column / 3).
 """
 import os
 import sys
@@ -111,6 +116,13 @@ def link_args(argv):
         out["degrees"] = value("--degrees")
     elif "--degrees" in argv:
         raise LinkArgError("--degrees goes with --moments")
+    if "--clustering" in argv:  # (the key "clustering" is there only with the flag)
+        out["clustering"] = value("--clustering")
+        if out["clustering"] is None:
+            raise LinkArgError("--clustering needs a value")
+        for other in ("--moments", "--auc", "--sample", "--rank", "--pairs", "--queries"):
+            if other in argv:
+                raise LinkArgError(f"--clustering and {other} exclude each other")
     return out
 
 
@@ -148,6 +160,12 @@ def moments_line(global_vertex, global_sweep, alpha, which):
             f"alpha={julia_float(float(alpha))} which={which}")
 
 
+def clustering_line(t):
+    """The line of --clustering (t: api.link_clustering_table's dict)."""
+    return (f"# transitivity_obs={julia_float(float(t['transitivity_obs']))} transitivity_exp={julia_float(float(t['transitivity_exp']))} "
+            f"triangles_obs={julia_float(float(t['triangles_obs']))} triangles_exp={julia_float(float(t['triangles_exp']))}")
+
+
 def read_ids(path, columns, base, n):
     """The ids of a query / pair file as 1-based int64 (rows, columns), checked against 1..n; `base` is the edge file's."""
     from cge.jl_amd import api
@@ -177,6 +195,9 @@ def main(argv=None):
 
     (edges, weights, vweights, comm, clusters, embed, verbose, land, forced, method, directed, split, seed,
      samples) = CGE.parseargs(argv)
+    if la.get("clustering") is not None and directed:
+        print("cge_links: --clustering is for undirected graphs", file=sys.stderr)
+        return 1
     base = int(api.read_table(CGE.args._flag_value(argv, "-g"), column_major=False)[0][:, :2].min())  # the file's own id base
     n = len(vweights)
     ctx = api.default_context()
@@ -206,6 +227,14 @@ def main(argv=None):
                     for v in range(n):
                         tail = f" {julia_float(float(mo.deg_in[v]))}" if mo.directed else ""
                         f.write(f"{v + base} {julia_float(float(vw[v]))} {julia_float(float(mo.deg_out[v]))}{tail}\n")
+            return 0
+        if la.get("clustering") is not None:
+            t = api.link_clustering_table(*ctx.link_triangles())
+            out.write(clustering_line(t) + "\n")
+            with open(la["clustering"], "w") as f:
+                for v in range(n):
+                    f.write(f"{v + 1} {t['tri_obs'][v]} {t['wed_obs'][v]} {julia_float(float(t['tri_exp'][v]))} "
+                            f"{julia_float(float(t['wed_exp'][v]))}\n")
             return 0
         if la.get("sample") is not None:
             si, sj, _, _ = ctx.link_sample(la["sample_seed"], 0)

@@ -498,6 +498,34 @@ int cge_link_auc(cge_ctx *ctx, int part, int nparts, int64_t *out_less /* m, may
 int cge_link_moments(cge_ctx *ctx, int diag, double *deg_out /* n, may be NULL */, double *deg_in /* n, may be NULL */,
                      double *B /* L, may be NULL */, double *V /* L, may be NULL */, double *Cobs /* L, may be NULL */,
                      int64_t *n_comm);
+/* Expected and observed triangles and wedges, per vertex: how much of the graph's clustering the fitted model explains, without
+ * drawing a graph.  Undirected models only.
+ * Model side.  q(i, j) = min(p(i, j), 1) is what cge_link_sample draws with, q(i, i) = 0, Q the symmetric matrix of the q (every
+ * entry cge_link_prob's value to the bit, clamped).  The edges of a draw are independent, so
+ *     tri_exp[i] = 1/2 sum_j Q_ij (Q Q)_ij   (expected triangles through i),
+ *     wed_exp[i] = sum_{j < k} Q_ij Q_ik      (expected wedges centred at i).
+ * Q is materialised (8 ld^2 bytes, ld = n padded to an odd number of 128-tiles) and Q o (Q Q) is row-summed tile by tile on the
+ * fp64 matrix cores; the wedges are summed pair by pair, not as (s1^2 - s2) / 2, which cancels.  Every summand is a product of
+ * non-negative doubles, so each output is within
+ *     (n + 8) 2^-52 exact  +  n^2 2^-1073
+ * of the exact sum over Q's entries (the floor: products that underflow; DESIGN.md section 4.17 derives both).  The outputs are a
+ * function of the inputs alone: not of the CU count, the grid or the order in which workgroups finish (fixed work items,
+ * fixed-order sums, no floating-point atomics).
+ * Graph side.  The resident edge list read as a simple undirected graph -- distinct neighbours, either orientation, repeated rows
+ * once, self loops dropped:  tri_obs[v] = triangles through v,  wed_obs[v] = k_v (k_v - 1) / 2 with k_v the distinct neighbours
+ * other than v.  Exact integers.
+ * summary = {sum tri_exp, sum wed_exp, sum tri_obs, sum wed_obs}, taken on the host in vertex order in long double and rounded
+ * once.  Transitivity is summary[0] / summary[1] (model) and summary[2] / summary[3] (graph); triangles are a sum / 3.  The library
+ * does not divide: a zero wedge sum is the caller's business.
+ * With tri_exp and wed_exp both NULL the model half is not run and summary[0], summary[1] are 0 ("link_tri_tiles" = 0); with one of
+ * them NULL its kernel is not run and its sum is 0.  Likewise tri_obs / wed_obs: both NULL skips the graph half, else both sums
+ * are returned.
+ * CGE_E_ARG, before any device work: no link model; a directed model; a NULL summary; under collectives or sharding.  CGE_E_OOM
+ * with the bytes named when Q plus the partials (8 * 128 ceil(n / 128)^2 bytes) do not fit in free memory.
+ * Stats: "link_tri_tiles" = 128 x 128 tiles of the last call, "link_tri_saturated" = pairs i < j with p > 1,
+ * "link_tri_matrix_bytes" = the bytes of Q.                                                                                      */
+int cge_link_triangles(cge_ctx *ctx, double *tri_exp /* n, may be NULL */, double *wed_exp /* n, may be NULL */,
+                       int64_t *tri_obs /* n, may be NULL */, int64_t *wed_obs /* n, may be NULL */, double summary[4]);
 
 /* ---- small helpers (same arithmetic as the reference helpers, host side) -------------------- */
 int64_t cge_idx(int64_t n, int64_t i, int64_t j);                                   /* src/auxilary.jl:57-59 */

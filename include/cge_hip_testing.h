@@ -483,6 +483,11 @@ int cge_ecg_members_test(void *ctx, int64_t members, int64_t seed, int64_t *memb
  * sort, outputs, capacity rules, stats -- is cge_link_sample's */
 int cge_link_sample_test(void *ctx, const double *U, int directed_layout, int64_t cap, int64_t *out_i, int64_t *out_j, double *out_p,
                          int64_t *n_edges);
+/* needs the GPU: the matrix Q that cge_link_triangles' model half works on, generated by the same launch and copied out whole
+ * (n <= 2048, undirected model): Q_out is ld x ld row-major with ld = 128 (ceil(n / 128) | 1), the library's own leading dimension
+ * (another ld is CGE_E_ARG with the right one named).  Q[i ld + j] = min(cge_link_prob(i, j), 1) to the bit for i != j below n, 0
+ * on the diagonal and in the padding */
+int cge_link_triangles_test(void *ctx, double *Q_out, int64_t ld);
 #ifdef __cplusplus
 }
 #endif
