@@ -1628,7 +1628,8 @@ class Context:
         return mem, nc, rounds, q, core.astype(bool)
 
     _TEST_OPTIONS = ("louvain_wave_len", "fit_persistent_test_delay", "fit_persistent_test_timeout", "test_bvec_plain", "test_rss2_one_kernel",
-                     "exact_resident_limit", "test_eig_roles", "fit_dir_tiles", "test_pcent_form", "test_device_cus")
+                     "exact_resident_limit", "test_eig_roles", "fit_dir_tiles", "test_pcent_form", "test_device_cus",
+                     "test_lm_speculate")
 
     def set_option(self, key, value):
         if key in self._TEST_OPTIONS:  # the testing knobs are not part of the boundary (include/cge_hip_testing.h)

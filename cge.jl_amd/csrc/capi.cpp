@@ -495,6 +495,13 @@ int cge_set_test_option(void *ctx, const char *key, int64_t value) {
     // packed directed sweep
     if (!strcmp(key, "fit_dir_tiles")) { c->opt_test_fit_dir_tiles = value != 0; return CGE_OK; }
     if (!strcmp(key, "exact_resident_limit") && value >= 0) { c->opt_test_resident_limit = (double)value; return CGE_OK; }
+    // which groups a round of runsplit's driver (advance_heaps) puts into its batch: 0 as ever, 1 the global phase splits the top of
+    // its heap alone, 2 every candidate above the threshold (no `take` cut), 3 as 0 and the forced phase's local heaps speculate too
+    if (!strcmp(key, "test_lm_speculate")) {
+        if (value < 0 || value > 3) return CGE_E_ARG;
+        c->opt_test_lm_speculate = (int)value;
+        return CGE_OK;
+    }
     // the CU count every launch shape of this context is sized by (0: the device's own).  It only shrinks: the persistent fits are
     // co-resident because G <= the device's CUs
     if (!strcmp(key, "test_device_cus") && value >= 0) {
@@ -532,6 +539,9 @@ int cge_get_stat(cge_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "landmark_batches")) *value = c->stat_lm_batches;
     else if (!strcmp(key, "landmark_batch_rows")) *value = c->stat_lm_rows;
     else if (!strcmp(key, "landmark_splits")) *value = c->stat_lm_splits;
+    else if (!strcmp(key, "landmark_pops")) *value = c->stat_lm_pops;                   // groups popped by the replay, both phases
+    else if (!strcmp(key, "landmark_splits_failed")) *value = c->stat_lm_failed;        // splits computed that failed, popped or not
+    else if (!strcmp(key, "landmark_take_rounded")) *value = c->stat_lm_take_rounded;   // rounds whose batch the 512 rule cut down
     else if (!strcmp(key, "ecg_groups")) *value = c->stat_ecg_groups; // of the last cge_ecg: lock-step groups,
     else if (!strcmp(key, "ecg_member_rounds")) *value = c->stat_ecg_member_rounds; // rounds summed over the members,
     else if (!strcmp(key, "ecg_peel_rounds")) *value = c->stat_ecg_peel_rounds;     // rounds of the 2-core that removed a vertex,

@@ -514,7 +514,14 @@ struct cge_ctx {
     int opt_fit_test_timeout = 0; // testing: the persistent fit gives up at once, so the fallback path runs
     int opt_fit_test_delay = 0;   // testing: the tile waves of the data-as-signal fits nap this many times (~3 us each) before
                                   // their first load -- start skew, as under contention; results must not change
-    i64 stat_lm_batches = 0, stat_lm_rows = 0, stat_lm_splits = 0; // last runsplit: device batches, their rows, groups split
+    i64 stat_lm_batches = 0, stat_lm_rows = 0, stat_lm_splits = 0; // last runsplit: device batches, their rows, groups split (those of one
+                                                                   // or two rows, which need no device batch, included)
+    i64 stat_lm_pops = 0, stat_lm_failed = 0, stat_lm_take_rounded = 0; // last runsplit: groups popped by the replay (both phases), splits
+                                                                        // computed that failed (popped or not), rounds whose batch the
+                                                                        // 512 rule of 64 < d <= 128 cut down
+    int opt_test_lm_speculate = 0; // testing: which groups a round of advance_heaps splits: 0 as ever, 1 the global phase splits the top of
+                                   // its heap alone, 2 every candidate above the threshold (no `take` cut), 3 as 0 and the forced phase's
+                                   // local heaps speculate too; the landmark ids do not depend on it
     DevBuf<int> cut_ties;                                          // last runsplit: tasks of the cut rules with a row ON the cut (device counter)
     i64 stat_fit_persistent = 0; // alphas fitted by the persistent kernel in the last sweep
     i64 stat_fit_iters = 0;      // Chung-Lu iterations of the last sweep (all alphas)

@@ -564,6 +564,10 @@ void rule_rss_batched(cge_ctx *c, const Batch &B, Group *const *groups, const do
         const Group *g = groups[t];
         const i64 k = (i64)g->what.size();
         const double *zt = &z[B.task_row_off[t]];
+        // A NaN projection: argmin and argmax (:163-164) both return the FIRST NaN, l1 == l2 and the rule throws (:165-166).
+        // (The comparisons below skip a NaN, and the median's std::nth_element is undefined on one.)
+        for (i64 j = 0; j < k; j++)
+            if (std::isnan(zt[j])) { S.rc = CGE_E_HOMOGENEOUS; S.phase = 2; return; }
         i64 imin = 0, imax = 0;
         for (i64 j = 1; j < k; j++) {
             if (zt[j] < zt[imin]) imin = j;
@@ -949,7 +953,6 @@ void split_enqueue(cge_ctx *c, SplitBatch &S) {
     group_stats_enqueue(c, S.groups, T, S.B);
     c->stat_lm_batches++;
     c->stat_lm_rows += S.B.R;
-    c->stat_lm_splits += T;
     cut_enqueue(c, S);
 }
 // ... and book the results when they have arrived
@@ -985,6 +988,7 @@ void split_collect(cge_ctx *c, SplitBatch &S) {
 void compute_splits(cge_ctx *c, std::vector<Group *> &tasks, int method) {
     const i64 d = c->d;
     std::vector<Group *> big;
+    c->stat_lm_splits += (i64)tasks.size(); // (the groups of one or two rows too: a split each, though no device work)
     for (Group *g : tasks) {
         const i64 k = g->len;
         g->has_split = true;
@@ -1266,8 +1270,9 @@ void materialise_children(std::vector<Group *> &tasks, GroupPool &pool, i64 c_d)
 }
 
 // pop the top group of `h`, push its two children (the body of src/landmarks.jl:290-307 / :317-334)
-void replay_one(Heap &h) {
+void replay_one(cge_ctx *c, Heap &h) {
     Group *g = h.pop();
+    c->stat_lm_pops++;
     if (g->rc != CGE_OK) throw_rc(g->rc);
     h.put(g->clo);
     h.put(g->chi);
@@ -1278,10 +1283,15 @@ void replay_one(Heap &h) {
 // splits alike (speculative tree expansion) -- as many per heap as pops are still missing.  The number of
 // rounds is the depth of the relevant split tree, not the length of the pop sequence; the replay order (and
 // with it every landmark id) is exactly the reference's.
-// `speculate` = false: only the current top of each heap is split per round (no wasted splits; used for the
-// many small per-community heaps of the forced phase, which need s-1 rounds anyway).
+// Without speculation only the current top of each heap is split per round (no wasted splits): the many small
+// per-community heaps of the forced phase (`global` = false), which need s-1 rounds anyway.
+// The testing knob test_lm_speculate (include/cge_hip_testing.h) changes which groups a round splits and nothing else:
+// 1 = the global phase does not speculate either (the reference's own order, one split per round), 2 = every candidate
+// above the threshold is split (no `take` cut below), 3 = the forced phase's heaps speculate too.
 void advance_heaps(cge_ctx *c, std::vector<Heap *> &heaps, const std::vector<i64> &targets, int method,
-                   GroupPool &pool, bool speculate) {
+                   GroupPool &pool, bool global) {
+    const int knob = c->opt_test_lm_speculate;
+    const bool speculate = global ? knob != 1 : knob == 3;
     std::vector<Group *> frontier, stack, keep; // (reused by every round: no allocation per round)
     std::vector<double> vals;
     for (;;) {
@@ -1290,7 +1300,7 @@ void advance_heaps(cge_ctx *c, std::vector<Heap *> &heaps, const std::vector<i64
             PhaseAcc ph(c, "lm_heap"); // replay + choice of the next batch (host)
             for (size_t q = 0; q < heaps.size(); q++) {
                 Heap &h = *heaps[q];
-                while ((i64)h.len() < targets[q] && h.top()->has_split) replay_one(h);
+                while ((i64)h.len() < targets[q] && h.top()->has_split) replay_one(c, h);
                 if ((i64)h.len() >= targets[q]) continue;
                 if (!speculate) {
                     batch.push_back(h.top());
@@ -1336,8 +1346,11 @@ void advance_heaps(cge_ctx *c, std::vector<Heap *> &heaps, const std::vector<i64
                 // The register-resident eigen-solver of 64 < d <= 128 holds two matrices per CU: 512 at a time, and a batch of 800
                 // costs two rounds (0.98 ms) where 512 cost one (0.51).  The batch is cut DOWN to a multiple of 512: one round more
                 // at the headline (8 batches), eigen-solver 4.7 -> 4.0 ms, landmarks 13.1 -> 12.3 ms (rounding up: 13.6).
-                if (c->d > 64 && c->d <= 128 && take > 512) take = take / 512 * 512;
-                if ((i64)frontier.size() > take) {
+                if (c->d > 64 && c->d <= 128 && take > 512 && knob != 2) {
+                    if (take % 512) c->stat_lm_take_rounded++;
+                    take = take / 512 * 512;
+                }
+                if ((i64)frontier.size() > take && knob != 2) {
                     std::nth_element(frontier.begin(), frontier.begin() + (take - 1), frontier.end(),
                                      [](const Group *a, const Group *b) { return a->value < b->value; });
                     const double cut = frontier[take - 1]->value;
@@ -1350,8 +1363,9 @@ void advance_heaps(cge_ctx *c, std::vector<Heap *> &heaps, const std::vector<i64
             }
         }
         if (batch.empty()) break;
-        if (speculate) compute_splits_sharded(c, batch, method); // the global phase (N > 1: split over the ranks)
+        if (global) compute_splits_sharded(c, batch, method); // (N > 1: split over the ranks)
         else compute_splits(c, batch, method);
+        for (const Group *g : batch) c->stat_lm_failed += g->rc != CGE_OK; // (raised only if the replay pops the group)
         PhaseAcc pm(c, "lm_materialise");
         materialise_children(batch, pool, c->d);
     }
@@ -1847,6 +1861,7 @@ void host_runsplit(cge_ctx *c, const i64 *cl_flat, const i64 *cl_off, i64 ncl, i
         c->lm_arena_used = 0;
         c->lm_means_used = 0;
         c->stat_lm_batches = c->stat_lm_rows = c->stat_lm_splits = 0;
+        c->stat_lm_pops = c->stat_lm_failed = c->stat_lm_take_rounded = 0;
         c->cut_ties.ensure(1);
         HIP_CHECK(hipMemsetAsync(c->cut_ties.p, 0, sizeof(int), c->stream));
         sc = c->rows_sharded ? stage_clusters_rowsharded(c, cl_flat, cl_off, ncl) : stage_clusters(c, cl_flat, cl_off, ncl);

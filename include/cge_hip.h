@@ -645,7 +645,10 @@ int cge_set_option(cge_ctx *ctx, const char *key, int64_t value);
  * used + the partial vectors of a launch-per-iteration fit);
  * "fit_persistent_alphas" = alphas of the last sweep fitted by a persistent launch, "fit_persistent_fallbacks" = persistent fits abandoned since the context was created, "fit_iterations" = Chung-Lu
  * iterations of the last sweep (all alphas); "landmark_batches" / "landmark_batch_rows" / "landmark_splits" =
- * device batches of the last runsplit, the rows they covered, the groups they split; "cut_tie_tasks" = groups of the size / diameter rules
+ * device batches of the last runsplit, the rows they covered, the groups whose split was computed (those of one or two rows, which need no
+ * device batch, included); "landmark_pops" = groups the replay popped (both phases), "landmark_splits_failed" = computed splits that
+ * failed, whether or not the group was ever popped (the error is raised only when it is), "landmark_take_rounded" = rounds of the global
+ * phase whose batch the 512 rule of 64 < d <= 128 cut down; "cut_tie_tasks" = groups of the size / diameter rules
  * of the last runsplit that held a row exactly ON the cut (settled by the reference's sequential rule; read from the device: synchronises);
  * "edges_resident" / "edges_total" (option shard_ingest), "rows_resident" / "rows_total" (option shard_rows: the embedding rows this
  * rank holds -- about n / W -- and n), "embedding_words_resident" (doubles of the resident row matrix)   */

@@ -451,7 +451,17 @@ int cge_wave_tree_test(void *ctx, const double *x, int64_t n_rows, double *out_r
  *                                 cge_link_sample / cge_link_auc; 0 (default): the device's own.  It only shrinks (above the count:
  *                                 CGE_E_ARG), since a persistent fit needs its G <= v workgroups co-resident.  This one does change
  *                                 which form runs -- on purpose: the forms of chips with fewer CUs run on a large one.  The link
- *                                 queries' results do not depend on it; a fit's agree to rounding.                                */
+ *                                 queries' results do not depend on it; a fit's agree to rounding;
+ *   "test_lm_speculate"           v: which groups a round of runsplit's host driver (advance_heaps) puts into its batch -- and nothing
+ *                                 else: which function computes the splits of a phase stays as it is.  0 (default): the global phase
+ *                                 splits a share of the candidates per round, the forced phase the top of every local heap; 1: the
+ *                                 global phase splits the top of its heap alone, the reference's own order, one split per round
+ *                                 (stats "landmark_splits" == "landmark_pops": nothing wasted); 2: every candidate above the
+ *                                 threshold is split, no `take` cut (a share of 100 %, the 512 rule of 64 < d <= 128 off); 3: as 0,
+ *                                 and the forced phase's local heaps speculate too (target `forced`), the only way the speculating
+ *                                 branch runs over more than one heap.  Other values: CGE_E_ARG.  The landmark ids and the errors are
+ *                                 the same under every value; the stats "landmark_batches", "landmark_splits",
+ *                                 "landmark_splits_failed" and "landmark_take_rounded" say what a value did.                        */
 int cge_set_test_option(void *ctx, const char *key, int64_t value);
 /* needs the GPU: the resident row-major fp64 matrix as this rank holds it (all n rows; under shard_rows its own rows, in
  * local order, with their global 0-based ids in ids_out, which may be NULL otherwise).  *rows and *d are set first; a capacity

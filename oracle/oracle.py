@@ -153,6 +153,30 @@ def use_lapack_eig(on: bool = True):
     lib().orc_set_eig_hook(_eig_cb)
 
 
+def use_jittered_eig(seed, scale=2.0 ** -44):
+    """Test inputs only (tests/runsplit_cases.py): LAPACK's eigenvector with every component moved by a seeded relative amount of
+    up to `scale` -- some 250 ulps, far more than any sound routine's error.  An input whose landmark ids survive several such
+    seeds has no decision that hangs on an eigenvector's last bits: no projection exactly on a cut, no two components of equal
+    magnitude competing for the sign rule.  (Two clean routines can agree on such an input by producing the same bits; a third
+    one, the device's, need not.)  Undo with use_lapack_eig(False)."""
+    global _eig_cb
+    from scipy.linalg import eigh
+
+    rng = np.random.default_rng(seed)
+
+    def cb(Ap, d, vp):
+        try:
+            A = np.ctypeslib.as_array(Ap, shape=(d, d))
+            w, V = eigh(A, driver="evr", check_finite=False)
+            np.ctypeslib.as_array(vp, shape=(d,))[:] = V[:, -1] * (1.0 + scale * rng.uniform(-1.0, 1.0, d))
+            return 0
+        except Exception:  # noqa: BLE001 -- nothing may propagate through the C frame
+            return 1
+
+    _eig_cb = _EIG_FN(cb)
+    lib().orc_set_eig_hook(_eig_cb)
+
+
 def total_rss(embedding, w, idxs):
     e, ef = _f(embedding)
     w = np.ascontiguousarray(w, dtype=np.float64)

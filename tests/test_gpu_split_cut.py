@@ -238,6 +238,44 @@ def test_a_nan_projection_fails_its_task_alone(ctx, cells, rule):
         assert np.array_equal(out["children"][sub_off[t]:sub_off[t + 1]], clean["children"][sub_off[t]:sub_off[t + 1]])
 
 
+@pytest.mark.parametrize("force_generic", [0, 1])
+def test_a_nan_projection_under_rss_is_a_homogeneous_group(ctx, cells, force_generic):
+    """The reference's argmin and argmax both return the FIRST NaN of z, so l1 == l2 and split_cluster_rss throws "Trying to split
+    homogenous cluster" (src/landmarks.jl:163-166).  The sorted form declines a group with a NaN, and the generic host path refuses
+    it before its arg-min / arg-max scan (whose comparisons skip a NaN) and its median (std::nth_element is undefined on one): a NaN
+    in the first row, in the middle, and in place of the group's maximum.  The neighbours are untouched, bit for bit."""
+    d, cls = 5, "gaussian"
+    X, w, ids, off = cells("rss", d, cls)[:4]
+    ctx = _load(ctx, X, w)
+    lens = np.diff(off)
+    pick = [int(np.flatnonzero(lens == k)[0]) for k in (1025, 5, 64, 257, 4097, 17, 3, 1033)]
+    sub_ids = np.concatenate([ids[off[t]:off[t + 1]] for t in pick])
+    sub_z = np.random.default_rng(17).standard_normal(len(sub_ids))  # distinct: every group splits, none by the generic path
+    sub_off = np.concatenate([[0], np.cumsum(lens[pick])]).astype(np.int32)
+    clean = ctx.group_cut_test(sub_ids, sub_off, sc.RSS, sub_z, force_generic=bool(force_generic))
+    assert (clean["rc"] == sc.OK).all()
+    zn = sub_z.copy()
+    zn[sub_off[1]] = np.nan                                                   # 5 rows: the first row
+    zn[sub_off[3] + 128] = np.copysign(np.nan, -1.0)                          # 257 rows: the middle, a NaN with the sign bit
+    zn[sub_off[4] + int(np.argmax(sub_z[sub_off[4]:sub_off[5]]))] = np.nan    # 4097 rows (two sorted pieces): the maximum
+    zn[sub_off[6] + 1] = np.nan                                               # 3 rows: the middle of the shortest group
+    bad = (1, 3, 4, 6)
+    out = ctx.group_cut_test(sub_ids, sub_off, sc.RSS, zn, force_generic=bool(force_generic))
+    assert [int(r) for r in out["rc"]] == [sc.E_HOMOGENEOUS if t in bad else sc.OK for t in range(len(pick))]
+    assert all(out["route"][t] == 1 for t in bad)  # whichever form was asked for, the generic path booked them
+    keep = [t for t in range(len(pick)) if t not in bad]
+    for k in ("rc", "nlow", "vlow", "vhigh", "cmeans", "route"):
+        assert np.array_equal(_bits_of(out[k][keep]), _bits_of(clean[k][keep])), k
+    for t in keep:
+        assert np.array_equal(out["children"][sub_off[t]:sub_off[t + 1]], clean["children"][sub_off[t]:sub_off[t + 1]])
+    assert not _same(out, ctx.group_cut_test(sub_ids, sub_off, sc.RSS, zn, force_generic=bool(force_generic)), sub_off)
+
+
+def _bits_of(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.int64) if a.dtype == np.float64 else a
+
+
 def test_group_cut_hook_refusals(ctx, cells):
     from cge.jl_amd import api
 
